@@ -8,8 +8,16 @@ A "step" is one pass of the hot path over one batch of F synthetic BGR frames pe
 RESIDENT IN HBM: compute_channels (+ pyramid) -> per-plane component tree -> NMS -> LBP + strong/weak
 cascades -> candidate records copied back to the host (and, for N > 1, gathered across ranks with RCCL).
 Frames are dealt out to ranks, so per-GPU work is fixed as N grows ("weak" scaling) and `value` = all
-frames processed by all ranks per second.  The timed region of K steps is run `--repeats` times (default 3),
-each bracketed by barrier + synchronize; `value` / `ms_per_step` are the median region, `value_min/max` the others.
+frames processed by all ranks per second.  The timed region is exactly K = --steps steps, bracketed by
+barrier + synchronize; `ms_per_step` = the region's wall time / K.  --repeats R (default 1) runs the region
+R times: `value` / `ms_per_step` are then the median region, `value_min/max` the others.
+
+--dump-outputs DIR writes what the timed path returned in its last step (rank 0): every field of the
+candidate records (`cands_<field>.npy`) and of the plane records (`planes_<field>.npy`), plus the optional
+arrays of the stages that ran (`ocr_label`, `tracks_<field>`, ...), each as a 1-D float64 array.  The
+frames are seeded, so the same arguments give the same inputs on every run and two builds can be compared
+array for array.  Above 64 MB in all, a fixed seeded sample of the rows is written (`<array>_row.npy` =
+the row indices kept).
 
 Workloads (BASELINE.json `configs`):
   pyr3x8  : configs[1] -- the metric's: 1920x1080, planes {Y,Cr,Cb} x 8 pyramid levels (24 planes, 12.40 Mpx/frame)
@@ -252,6 +260,39 @@ def make_frames(S, kind, w, h, F, first=0, ties_every=8):
         return np.stack(list(ex.map(lambda i: make(S.synth.frame_seed(first + i), w, h), range(F))))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_PAD_FIELDS = ("r0", "r1", "r2", "reserved")      # padding of the record types, not outputs
+
+
+def dump_outputs(res, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
+    """The arrays a caller of detect_bgr_device receives (Result), one 1-D float64 .npy per record field / plain array.  Above `limit` bytes every
+    source array keeps the same share of its rows, picked by a seeded generator from (rows, kept) alone -- arrays of one length (the per-candidate
+    ones) keep the same rows -- and `<name>_row.npy` holds the indices kept."""
+    srcs = [("planes", res.info), ("cands", res.cands)]
+    srcs += [(n, getattr(res, n)) for n in ("ocr_label", "ocr_prob", "tracks", "texts", "text_ers", "group_all", "group_bounds",
+                                            "line_label", "line_prob", "line_kept", "text_alive") if getattr(res, n) is not None]
+    cols = {name: ([f for f in a.dtype.names if f not in DUMP_PAD_FIELDS] if a.dtype.names else [None]) for name, a in srcs}
+    total = sum(8 * len(a) * len(cols[name]) for name, a in srcs)
+    # (a sampled array also writes its row indices: one column more)
+    scale = 1.0 if total <= limit else limit / sum(8 * len(a) * (len(cols[name]) + 1) for name, a in srcs)
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for name, a in srcs:
+        rows = None
+        if scale < 1.0:
+            k = int(len(a) * scale)
+            rows = np.sort(np.random.default_rng(seed).choice(len(a), size=k, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}_row.npy"), rows.astype(np.float64))
+            written.append(f"{name}_row")
+        for f in cols[name]:
+            col = a if f is None else a[f]
+            fn = name if f is None else f"{name}_{f}"
+            np.save(os.path.join(out_dir, f"{fn}.npy"), np.ascontiguousarray(col, dtype=np.float64).reshape(-1))
+            written.append(fn)
+    return written
+
+
 def tile_roofline(px, F, tile_ms, tile_ms_overlapped, workload, t2_ms=0.0, t2_share=0.0):
     """The tile trees of a batch are built by two kernels since round 6 -- k_tile_tree2 (level by level on bit masks: the chroma planes) and
     k_tile_tree (pieces + union-find in LDS: the luma planes, and the tiles the first one hands back) -- which between them read every plane
@@ -291,12 +332,14 @@ def tile_roofline(px, F, tile_ms, tile_ms_overlapped, workload, t2_ms=0.0, t2_sh
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=40, help="timed batches per region (one step = one batch of --frames-per-gpu frames per GPU; 40 steps = about a fifth of a second)")
+    ap.add_argument("--steps", type=int, default=200, help="timed steps (one step = one batch of --frames-per-gpu frames per GPU; 200 steps = about half a second)")
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--min-region-s", type=float, default=0.5,
-                    help="a timed region lasts at least this long whatever --steps says: a step then runs its batch several times over (config.batches_per_step; "
-                         "frames_per_gpu_per_step counts all of them).  A region of 20 single-batch steps is 0.1 s, which one box-to-box hiccup moves by 10 %%")
-    ap.add_argument("--repeats", type=int, default=3, help="the timed region of --steps steps is run this many times; `value` is the median region")
+    ap.add_argument("--min-region-s", type=float, default=0.0,
+                    help="opt-in: make a timed region last at least this long by running each step's batch several times over (config.batches_per_step; "
+                         "frames_per_gpu_per_step counts all of them).  Off by default, so that --steps is the number of timed batches")
+    ap.add_argument("--repeats", type=int, default=1, help="the timed region of --steps steps is run this many times; `value` is the median region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last step returned as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--frames-per-gpu", type=int, default=None,
                     help="frames per batch (= per step) and GPU; default 32 for pyr3x8 (round 6, six batches in flight: 16 / 24 / 32 / 40 / 48 frames -> 12.0 / 12.5 / 12.6 / 10.4 / 11.1-11.3 k frames/s; "
                          "until round 5 48-64 were best), 48 for native6 (15.8 k against 15.3 k with 32), 12 for --size 4k (8: -1 %%)")
@@ -481,6 +524,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         regions.append(el)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r, args.dump_outputs)
     ties1 = rig.tie_totals()
     n_reg = len(regions)
     elapsed = float(np.median(regions))

@@ -28,7 +28,7 @@ def test_bench_two_ranks_on_one_device():
     assert len(lines) == 1, r.stdout                                   # rank 0 prints ONE line
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == "weak"
-    # (a step runs its 4-frame batch as often as it takes for the timed region to last --min-region-s)
+    # (a step is one 4-frame batch unless --min-region-s asks for longer regions)
     per_step = d["config"]["frames_per_gpu_per_step"]
     assert d["config"]["frames_per_batch"] == 4 and per_step == 4 * d["config"]["batches_per_step"] and d["value"] > 0
     assert "gather" in d["config"]                                     # the exchange ran (torch.distributed over gloo here)
