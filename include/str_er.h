@@ -268,6 +268,30 @@ int str_er_detect_planes(str_er_ctx *ctx, const uint8_t *planes, int32_t w, int3
                          int64_t stride, int64_t plane_pitch, int32_t n_planes,
                          int mem_kind, uint32_t stages, str_er_result **out);
 
+/* ---- lists of frames of different sizes --------------------------------------------- */
+/* One frame (or plane) of a list: `data` = its top-left pixel, in host or device memory as the call's mem_kind says (one kind for
+ * the whole list); `stride` = bytes per row, >= 3*w for a BGR frame, >= w for a plane.                                           */
+typedef struct str_er_image_ref {
+    const uint8_t *data;
+    int32_t  w, h;
+    int64_t  stride;
+} str_er_image_ref;      /* 24 bytes */
+
+/* str_er_detect_bgr for n_frames interleaved-BGR 8UC3 frames that need not share a size -- the reference's image mode works on
+ * photographs as they come (src/main.cpp: one cv::imread per file).  The result for frame i is exactly what str_er_detect_bgr gives
+ * for that frame alone, with frame = i in the candidates and plane infos: same planes in the same order, same nodes, candidates,
+ * scores and records of every stage (all stages allowed).  One launch converts all frames, one launch per further pyramid level
+ * resizes them all.  Capacity is the context's: every frame w <= max_width and h <= max_height, n_frames <= max_frames; a
+ * violation returns STR_ER_ECAPACITY (STR_ER_EINVAL for bad arguments) with a message naming the frame, and the context stays usable. */
+int str_er_detect_bgr_list(str_er_ctx *ctx, const str_er_image_ref *frames, int32_t n_frames,
+                           int mem_kind, uint32_t stages, str_er_result **out);
+
+/* str_er_detect_planes for n_planes independent 8UC1 planes of assorted sizes (n_planes <= the context's planes per call:
+ * max_frames x channels x levels).  Plane i's result is what str_er_detect_planes gives for it alone, with ch = i & 255 in its plane
+ * info and candidates (as for plane i of a str_er_detect_planes call).                                                           */
+int str_er_detect_planes_list(str_er_ctx *ctx, const str_er_image_ref *planes, int32_t n_planes,
+                              int mem_kind, uint32_t stages, str_er_result **out);
+
 /* ---- single stages, one per remaining ERFilter method ------------------------------ */
 /* ERFilter::compute_channels (src/ER.cpp:114-128): planes6 receives the six w*h
  * planes [Y,Cr,Cb,255-Y,255-Cr,255-Cb], each tightly packed (host memory).           */

@@ -38,6 +38,26 @@ PLANE_DTYPE = np.dtype([("frame", "<u4"), ("ch", "u1"), ("pyr", "u1"), ("r0", "u
 assert NODE_DTYPE.itemsize == 24 and CAND_DTYPE.itemsize == 48 and PLANE_DTYPE.itemsize == 44
 
 
+class ImageRef(C.Structure):
+    """str_er_image_ref: one frame / plane of a list call (top-left pixel, size, bytes per row)."""
+    _fields_ = [("data", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32), ("stride", C.c_int64)]
+
+
+assert C.sizeof(ImageRef) == 24 and (ImageRef.data.offset, ImageRef.w.offset, ImageRef.h.offset, ImageRef.stride.offset) == (0, 8, 12, 16)
+
+
+def _row_view(a, bpp: int) -> np.ndarray:
+    """`a` as uint8 rows of bpp-byte pixels, contiguous within a row; a view with a row stride is kept as it is (no copy)."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8:
+        a = a.astype(np.uint8)
+    if a.ndim != (3 if bpp == 3 else 2) or (bpp == 3 and a.shape[2] != 3):
+        raise ValueError("expected (H,W,3) uint8 BGR frames" if bpp == 3 else "expected (H,W) uint8 planes")
+    if a.strides[-1] != 1 or (bpp == 3 and a.strides[1] != 3) or a.strides[0] < bpp * a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a
+
+
 class StrErError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"str_er error {code}: {msg}")
@@ -128,6 +148,8 @@ def load_library():
     L.str_er_comm_free.restype = None
     L.str_er_detect_planes.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int,
                                        C.c_uint32, C.POINTER(vp)]
+    L.str_er_detect_bgr_list.argtypes = [vp, vp, C.c_int32, C.c_int, C.c_uint32, C.POINTER(vp)]
+    L.str_er_detect_planes_list.argtypes = [vp, vp, C.c_int32, C.c_int, C.c_uint32, C.POINTER(vp)]
     L.str_er_compute_channels.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp]
     L.str_er_classify_boxes.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp, vp]
     L.str_er_lbp_hist.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp]
@@ -574,6 +596,36 @@ class ERFilter:
         self._check(self.L.str_er_detect_planes(self.h, dptr, w, h, stride, plane_pitch, n_planes, MEM_DEVICE, stages,
                                                 C.byref(rh)))
         return self._collect(rh)
+
+    # ---- lists of frames of different sizes -------------------------------------------------------
+    def _detect_list(self, fn, refs, mem_kind: int, stages: int) -> Result:
+        arr = (ImageRef * len(refs))(*refs)
+        rh = C.c_void_p()
+        self._check(fn(self.h, arr, len(refs), mem_kind, stages, C.byref(rh)))
+        return self._collect(rh)
+
+    def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
+        """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
+        planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
+        keep = [_row_view(f, 3) for f in frames]
+        refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
+        return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST, stages | (WANT_NODES if want_nodes else 0))
+
+    def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
+        """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
+        keep = [_row_view(p, 1) for p in planes]
+        refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
+        return self._detect_list(self.L.str_er_detect_planes_list, refs, MEM_HOST, stages | (WANT_NODES if want_nodes else 0))
+
+    def detect_bgr_list_device(self, ptrs_dims, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
+        """text_detect_list for frames resident in HBM: ptrs_dims = [(device address, w, h[, stride]), ...] (stride default 3 w)."""
+        refs = [ImageRef(int(t[0]), int(t[1]), int(t[2]), int(t[3]) if len(t) > 3 else 3 * int(t[1])) for t in ptrs_dims]
+        return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_DEVICE, stages | (WANT_NODES if want_nodes else 0))
+
+    def detect_planes_list_device(self, ptrs_dims, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
+        """detect_planes_list for planes resident in HBM: ptrs_dims = [(device address, w, h[, stride]), ...] (stride default w)."""
+        refs = [ImageRef(int(t[0]), int(t[1]), int(t[2]), int(t[3]) if len(t) > 3 else int(t[1])) for t in ptrs_dims]
+        return self._detect_list(self.L.str_er_detect_planes_list, refs, MEM_DEVICE, stages | (WANT_NODES if want_nodes else 0))
 
     # ---- single stages ---------------------------------------------------------------------------
     def compute_channels(self, src: np.ndarray) -> np.ndarray:

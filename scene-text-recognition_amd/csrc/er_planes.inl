@@ -60,29 +60,7 @@ __global__ __launch_bounds__(256) void k_bgr_to_ycrcb(const uint8_t *__restrict_
     if (x >= w) return;
     const uint8_t *src = bgr + (size_t)f * frame_pitch + (size_t)y * stride + (size_t)x * 3;
     const size_t   dof = (size_t)f * dst_frame_pitch + (size_t)y * dstride + x;
-    if (aligned && x + 4 <= w) {
-        const uint32_t *s32 = reinterpret_cast<const uint32_t *>(src);
-        const uint32_t wd[3] = {s32[0], s32[1], s32[2]};
-        // bytes: B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
-        int Y[4], Cr[4], Cb[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i0 = 3 * k, i1 = 3 * k + 1, i2 = 3 * k + 2;
-            const int B = (int)((wd[i0 >> 2] >> (8 * (i0 & 3))) & 255u);
-            const int G = (int)((wd[i1 >> 2] >> (8 * (i1 & 3))) & 255u);
-            const int R = (int)((wd[i2 >> 2] >> (8 * (i2 & 3))) & 255u);
-            ycrcb_px(B, G, R, Y[k], Cr[k], Cb[k]);
-        }
-        *reinterpret_cast<uint32_t *>(yp + dof)  = Y[0] | (Y[1] << 8) | (Y[2] << 16) | (Y[3] << 24);
-        *reinterpret_cast<uint32_t *>(crp + dof) = Cr[0] | (Cr[1] << 8) | (Cr[2] << 16) | (Cr[3] << 24);
-        *reinterpret_cast<uint32_t *>(cbp + dof) = Cb[0] | (Cb[1] << 8) | (Cb[2] << 16) | (Cb[3] << 24);
-    } else {
-        for (int k = 0; k < 4 && x + k < w; ++k) {
-            int Y, Cr, Cb;
-            ycrcb_px(src[3 * k], src[3 * k + 1], src[3 * k + 2], Y, Cr, Cb);
-            yp[dof + k] = (uint8_t)Y; crp[dof + k] = (uint8_t)Cr; cbp[dof + k] = (uint8_t)Cb;
-        }
-    }
+#include "ycrcb_quad_body.inl"
 }
 
 void launch_bgr_to_ycrcb(hipStream_t s, const uint8_t *bgr, int w, int h, int64_t stride, int64_t frame_pitch,
@@ -217,154 +195,7 @@ __global__ __launch_bounds__(64) void k_resize(const uint8_t *__restrict__ src, 
     const int f = blockIdx.z / planes_per_frame, c = blockIdx.z % planes_per_frame;
     const uint8_t *s = src + (size_t)f * sframe_pitch + (size_t)c * splane_pitch;
     uint8_t       *d = dst + (size_t)f * dframe_pitch + (size_t)c * dplane_pitch;
-    if (g.mode != 2) {      // copy / exact 2x2: no tables
-        if (!active) return;
-        for (int r = 0; r < RESIZE_ROWS && dy0 + r < g.dh; ++r)
-            for (int k = 0; k < 4 && dx0 + k < g.dw; ++k)
-                d[(size_t)(dy0 + r) * dstride + dx0 + k] = (uint8_t)resize_px(g, s, sstride, 0, dx0 + k, dy0 + r);
-        return;
-    }
-    int sx[4], sx1[4], a0[4], a1[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float fx = (float)((min(dx0 + k, g.dw - 1) + 0.5) * g.scale_x - 0.5);
-        int   x = (int)floorf(fx);
-        fx -= (float)x;
-        if (x < 0) { fx = 0.f; x = 0; }
-        if (x >= g.sw - 1) { fx = 0.f; x = g.sw - 1; }
-        sx[k] = x; sx1[k] = (x + 1 < g.sw) ? x + 1 : x;
-        a0[k] = __float2int_rn((1.f - fx) * 2048.f); a1[k] = __float2int_rn(fx * 2048.f);
-    }
-    // the rows' coefficients are the same for every lane: lane r works out those of row r (the f64 / f32 part of cv::resize's tables) once -- all 64 lanes,
-    // before the lanes beyond the plane's last column leave -- and the row loop reads them into scalar registers: as every lane computing every row's they
-    // were a sixth of the kernel's vector instructions
-    int row_sy, row_b0, row_b1;
-    {
-        const int dy = dy0 + (int)(threadIdx.x & (RESIZE_ROWS - 1));
-        float fy = (float)((dy + 0.5) * g.scale_y - 0.5);
-        row_sy = (int)floorf(fy);
-        fy -= (float)row_sy;
-        row_b0 = __float2int_rn((1.f - fy) * 2048.f); row_b1 = __float2int_rn(fy * 2048.f);
-    }
-    static_assert((RESIZE_ROWS & (RESIZE_ROWS - 1)) == 0 && RESIZE_ROWS <= 64, "a lane per row of the tile");
-    // source window of the tile (uniform over the wave)
-    const int x_lo = resize_sx(g, tx0) & ~3;
-    const int x_last = resize_sx(g, min(tx0 + 255, g.dw - 1));
-    const int x_hi = (x_last + 1 < g.sw) ? x_last + 1 : x_last;
-    const int y_lo = min(max(resize_sy(g, dy0), 0), g.sh - 1);
-    const int y_hi = min(max(resize_sy(g, min(dy0 + RESIZE_ROWS - 1, g.dh - 1)) + 1, 0), g.sh - 1);
-    const int nwords = (x_hi - x_lo) / 4 + 1, nrows = y_hi - y_lo + 1;
-    const bool staged = nwords <= RS_WORDS && nrows <= RS_ROWS && (sstride & 3) == 0 && (reinterpret_cast<uintptr_t>(s) & 3) == 0;
-    if (staged) {
-        // a lane fetches words lane and lane + 64 of every row: all loads of the window (up to 32 per lane) are issued before the first one is
-        // waited for -- a loop of load / wait / write pays the memory latency once per round, and that, not arithmetic, was the kernel's time
-        static_assert(RS_WORDS <= 128, "two words per lane and row");
-        uint32_t v[RS_ROWS][2];
-        const uint8_t *src0 = s + (size_t)y_lo * sstride + x_lo + 4 * (int)threadIdx.x;
-#pragma unroll
-        for (int r = 0; r < RS_ROWS; ++r) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                v[r][j] = 0;
-                if (r < nrows && (int)threadIdx.x + 64 * j < nwords) v[r][j] = *reinterpret_cast<const uint32_t *>(src0 + (size_t)r * sstride + 256 * j);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < RS_ROWS; ++r) {
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-                if (r < nrows && (int)threadIdx.x + 64 * j < nwords && (int)threadIdx.x + 64 * j < RS_WORDS) s_src[r * RS_WORDS + threadIdx.x + 64 * j] = v[r][j];
-        }
-        __syncthreads();
-    }
-    const uint8_t *lds = reinterpret_cast<const uint8_t *>(s_src);
-    const bool full = dx0 + 4 <= g.dw && (dstride & 3) == 0;
-    // (the lanes beyond the plane's last column stay for the form below -- their stores are masked, their taps clamped into the window: the row loop reads
-    // the coefficients of row r from lane r, and a lane that had left could not be relied on to hold them)
-    if (!(staged && g.scale_x <= 1.5) && !active) return;
-    if (staged && g.scale_x <= 1.5) {
-        // The taps of the lane's 4 columns lie within 7 source bytes (reduction <= 1.5): per SOURCE row the lane reads the three dwords
-        // that hold them, shifts them to its first tap (two v_alignbyte) and picks the 4 left and the 4 right taps with two byte
-        // permutes whose selectors are fixed for the tile; the horizontal sums of a source row are kept for the next output row, which
-        // mostly needs it again.  A third of the LDS reads of the form below (the byte reads bound this kernel: a byte read costs the
-        // LDS what a dword read costs), same arithmetic, same result.
-        const int      base = sx[0] & ~3, s0 = sx[0] - base;
-        const uint32_t selL = (uint32_t)(sx[0] - sx[0]) | (uint32_t)(sx[1] - sx[0]) << 8 | (uint32_t)(sx[2] - sx[0]) << 16 | (uint32_t)(sx[3] - sx[0]) << 24;
-        const uint32_t selR = (uint32_t)(sx1[0] - sx[0]) | (uint32_t)(sx1[1] - sx[0]) << 8 | (uint32_t)(sx1[2] - sx[0]) << 16 | (uint32_t)(sx1[3] - sx[0]) << 24;
-        const uint32_t *col = s_src + (base - x_lo) / 4;
-        auto hrow = [&](int y, int (&h)[4]) {           // horizontal pass of source row y for the lane's 4 columns
-            const uint32_t *p = col + (y - y_lo) * RS_WORDS;
-            const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
-            const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, (uint32_t)s0), hi = __builtin_amdgcn_alignbyte(d2, d1, (uint32_t)s0);
-            const uint32_t L = __builtin_amdgcn_perm(hi, lo, selL), R = __builtin_amdgcn_perm(hi, lo, selR);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) h[k] = (int)(__umul24((L >> (8 * k)) & 0xFFu, (uint32_t)a0[k]) + __umul24((R >> (8 * k)) & 0xFFu, (uint32_t)a1[k]));
-        };
-        int ca = -1, cb = -1;               // source rows whose sums are in hA / hB (rows are >= 0)
-        int hA[4] = {0, 0, 0, 0}, hB[4] = {0, 0, 0, 0};
-#pragma unroll 1
-        for (int r = 0; r < RESIZE_ROWS; ++r) {
-            const int dy = dy0 + r;
-            if (dy >= g.dh) break;
-            const int sy = __builtin_amdgcn_readlane(row_sy, r), b0 = __builtin_amdgcn_readlane(row_b0, r), b1 = __builtin_amdgcn_readlane(row_b1, r);
-            const int ya = min(max(sy, 0), g.sh - 1), yb = min(max(sy + 1, 0), g.sh - 1);
-            // (ya, yb are the same for every lane: uniform branches)
-            if (ya == cb) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) hA[k] = hB[k];
-                ca = cb;
-            } else if (ya != ca) { hrow(ya, hA); ca = ya; }
-            if (yb == ca) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) hB[k] = hA[k];
-                cb = yb;
-            } else if (yb != cb) { hrow(yb, hB); cb = yb; }
-            uint32_t v = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int o = min((int)(((__umul24((uint32_t)b0, (uint32_t)hA[k] >> 4) >> 16) + (__umul24((uint32_t)b1, (uint32_t)hB[k] >> 4) >> 16) + 2u) >> 2), 255);
-                v |= (uint32_t)o << (8 * k);
-            }
-            uint8_t *o = d + (size_t)dy * dstride + dx0;
-            if (full) *reinterpret_cast<uint32_t *>(o) = v;
-            else for (int k = 0; k < 4 && dx0 + k < g.dw; ++k) o[k] = (uint8_t)(v >> (8 * k));
-        }
-        return;
-    }
-#pragma unroll 4
-    for (int r = 0; r < RESIZE_ROWS; ++r) {
-        const int dy = min(dy0 + r, g.dh - 1);
-        const bool live = dy0 + r < g.dh;
-        float fy = (float)((dy + 0.5) * g.scale_y - 0.5);
-        int   sy = (int)floorf(fy);
-        fy -= (float)sy;
-        const int b0 = __float2int_rn((1.f - fy) * 2048.f), b1 = __float2int_rn(fy * 2048.f);
-        const int ya = min(max(sy, 0), g.sh - 1), yb = min(max(sy + 1, 0), g.sh - 1);
-        uint32_t v = 0;
-        if (staged) {
-            const uint8_t *p0 = lds + (ya - y_lo) * (RS_WORDS * 4) - x_lo, *p1 = lds + (yb - y_lo) * (RS_WORDS * 4) - x_lo;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t r0 = __umul24(p0[sx[k]], (uint32_t)a0[k]) + __umul24(p0[sx1[k]], (uint32_t)a1[k]);
-                const uint32_t r1 = __umul24(p1[sx[k]], (uint32_t)a0[k]) + __umul24(p1[sx1[k]], (uint32_t)a1[k]);
-                const int o = min((int)(((__umul24((uint32_t)b0, r0 >> 4) >> 16) + (__umul24((uint32_t)b1, r1 >> 4) >> 16) + 2u) >> 2), 255);
-                v |= (uint32_t)o << (8 * k);
-            }
-        } else {
-            const uint8_t *p0 = s + (size_t)ya * sstride, *p1 = s + (size_t)yb * sstride;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint32_t r0 = __umul24(p0[sx[k]], (uint32_t)a0[k]) + __umul24(p0[sx1[k]], (uint32_t)a1[k]);
-                const uint32_t r1 = __umul24(p1[sx[k]], (uint32_t)a0[k]) + __umul24(p1[sx1[k]], (uint32_t)a1[k]);
-                const int o = min((int)(((__umul24((uint32_t)b0, r0 >> 4) >> 16) + (__umul24((uint32_t)b1, r1 >> 4) >> 16) + 2u) >> 2), 255);
-                v |= (uint32_t)o << (8 * k);
-            }
-        }
-        uint8_t *o = d + (size_t)dy * dstride + dx0;
-        if (!live) continue;
-        if (full) *reinterpret_cast<uint32_t *>(o) = v;
-        else for (int k = 0; k < 4 && dx0 + k < g.dw; ++k) o[k] = (uint8_t)(v >> (8 * k));
-    }
+#include "resize_tile_body.inl"
 }
 
 static ResizeGeom host_resize_geom(int sw, int sh, int dw, int dh)
@@ -388,4 +219,130 @@ void launch_resize(hipStream_t s, const uint8_t *src, int sw, int sh, int sstrid
     dim3 grid((quads + 63) / 64, (dh + RESIZE_ROWS - 1) / RESIZE_ROWS, planes_per_frame * n_frames);
     hipLaunchKernelGGL(k_resize, grid, dim3(64), 0, s, src, sstride, splane_pitch, sframe_pitch, dst, dstride,
                        dplane_pitch, dframe_pitch, planes_per_frame, host_resize_geom(sw, sh, dw, dh));
+}
+
+// ------------------------------------------------------------------------------------
+// Lists of frames of different sizes (str_er_detect_bgr_list): one launch converts every frame of the list, one launch per
+// pyramid level resizes every frame's three planes.  The grid is the frames' workgroups back to back; a table in device memory --
+// first workgroup of every job (n + 1 words), then the jobs -- tells a workgroup whose it is (a binary search over the prefix words:
+// scalar loads, uniform over the workgroup).  The per-pixel work is the one of k_bgr_to_ycrcb / k_resize: the same text (*_body.inl).
+// ------------------------------------------------------------------------------------
+struct IngestEnt {
+    const uint8_t *src;          // pixel (0, 0) of the BGR frame
+    uint8_t       *y;            // pixel (0, 0) of its Y plane; Cr, Cb follow plane_pitch apart
+    int64_t        stride, plane_pitch;
+    int32_t        w, dstride, aligned, row_wgs;     // row_wgs: workgroups of a row (256 lanes x 4 pixels each)
+};
+struct ResizeEnt {
+    const uint8_t *src;          // the job's first source / destination plane; the others follow splane_pitch / dplane_pitch apart
+    uint8_t       *dst;
+    int64_t        splane_pitch, dplane_pitch;
+    int32_t        sstride, dstride, tiles_x, tiles;      // tiles of 256 x RESIZE_ROWS output pixels: in a row, of a plane
+    ResizeGeom     g;
+};
+
+static size_t list_table_head(int n) { return ((size_t)4 * (n + 1) + 63) / 64 * 64; }
+
+__device__ __forceinline__ int find_job(const uint32_t *first, int n, uint32_t wg)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (first[mid] <= wg) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_bgr_to_ycrcb_list(const uint32_t *__restrict__ first, const IngestEnt *__restrict__ jobs, int n)
+{
+    const int f = find_job(first, n, blockIdx.x);
+    const IngestEnt e = jobs[f];
+    const uint32_t local = blockIdx.x - first[f];
+    const int y = (int)(local / (uint32_t)e.row_wgs), xb = (int)(local - (uint32_t)y * (uint32_t)e.row_wgs);
+    const int x = (xb * 256 + (int)threadIdx.x) * 4;
+    const int w = e.w, aligned = e.aligned;
+    if (x >= w) return;
+    const uint8_t *src = e.src + (size_t)y * e.stride + (size_t)x * 3;
+    uint8_t       *yp = e.y, *crp = e.y + e.plane_pitch, *cbp = e.y + 2 * e.plane_pitch;
+    const size_t   dof = (size_t)y * e.dstride + x;
+#include "ycrcb_quad_body.inl"
+}
+
+__global__ __launch_bounds__(64) void k_resize_list(const uint32_t *__restrict__ first, const ResizeEnt *__restrict__ jobs, int n)
+{
+    const int j = find_job(first, n, blockIdx.x);
+    __shared__ uint32_t s_src[RS_ROWS * RS_WORDS + 2];      // (+2: a lane reads three dwords from its first tap on)
+    const ResizeEnt &e = jobs[j];
+    const ResizeGeom g = e.g;
+    const uint32_t local = blockIdx.x - first[j];
+    const int c = (int)(local / (uint32_t)e.tiles), t = (int)(local - (uint32_t)c * (uint32_t)e.tiles);
+    const int by = t / e.tiles_x, bx = t - by * e.tiles_x;
+    const int sstride = e.sstride, dstride = e.dstride;
+    const int tx0 = bx * 256;
+    const int dx0 = tx0 + (int)threadIdx.x * 4;
+    const int dy0 = by * RESIZE_ROWS;
+    const bool active = dx0 < g.dw;
+    const uint8_t *s = e.src + (size_t)c * e.splane_pitch;
+    uint8_t       *d = e.dst + (size_t)c * e.dplane_pitch;
+#include "resize_tile_body.inl"
+}
+
+size_t ingest_table_bytes(int n) { return list_table_head(n) + sizeof(IngestEnt) * (size_t)n; }
+size_t resize_table_bytes(int n) { return list_table_head(n) + sizeof(ResizeEnt) * (size_t)n; }
+
+uint32_t build_ingest_table(const IngestJob *jobs, int n, void *out)
+{
+    uint32_t  *first = static_cast<uint32_t *>(out);
+    IngestEnt *ent = reinterpret_cast<IngestEnt *>(static_cast<uint8_t *>(out) + list_table_head(n));
+    uint32_t   at = 0;
+    for (int i = 0; i < n; ++i) {
+        const IngestJob &j = jobs[i];
+        IngestEnt e{};
+        e.src = j.src; e.y = j.dst; e.stride = j.stride; e.plane_pitch = j.plane_pitch; e.w = j.w; e.dstride = j.dstride;
+        e.row_wgs = ((j.w + 3) / 4 + 255) / 256;
+        // (per frame: a host frame staged tightly has 3 w bytes a row, a device frame the caller's pitch)
+        e.aligned = ((reinterpret_cast<uintptr_t>(j.src) | (uintptr_t)j.stride) % 4 == 0) &&
+                    ((reinterpret_cast<uintptr_t>(j.dst) | (uintptr_t)j.plane_pitch | (uintptr_t)j.dstride) % 4 == 0);
+        first[i] = at;
+        at += (uint32_t)e.row_wgs * (uint32_t)j.h;
+        ent[i] = e;
+    }
+    first[n] = at;
+    return at;
+}
+
+uint32_t build_resize_table(const ResizeJob *jobs, int n, int planes, void *out)
+{
+    uint32_t  *first = static_cast<uint32_t *>(out);
+    ResizeEnt *ent = reinterpret_cast<ResizeEnt *>(static_cast<uint8_t *>(out) + list_table_head(n));
+    uint32_t   at = 0;
+    for (int i = 0; i < n; ++i) {
+        const ResizeJob &j = jobs[i];
+        ResizeEnt e{};
+        e.src = j.src; e.dst = j.dst; e.splane_pitch = j.splane_pitch; e.dplane_pitch = j.dplane_pitch; e.sstride = j.sstride; e.dstride = j.dstride;
+        e.tiles_x = ((j.dw + 3) / 4 + 63) / 64;                              // (launch_resize's grid.x ...
+        e.tiles = e.tiles_x * ((j.dh + RESIZE_ROWS - 1) / RESIZE_ROWS);      //  ... times its grid.y)
+        e.g = host_resize_geom(j.sw, j.sh, j.dw, j.dh);
+        first[i] = at;
+        at += (uint32_t)e.tiles * (uint32_t)planes;
+        ent[i] = e;
+    }
+    first[n] = at;
+    return at;
+}
+
+void launch_bgr_to_ycrcb_list(hipStream_t s, const void *d_table, int n, uint32_t n_wg)
+{
+    if (n_wg == 0) return;
+    const uint8_t *t = static_cast<const uint8_t *>(d_table);
+    hipLaunchKernelGGL(k_bgr_to_ycrcb_list, dim3(n_wg), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(t),
+                       reinterpret_cast<const IngestEnt *>(t + list_table_head(n)), n);
+}
+
+void launch_resize_list(hipStream_t s, const void *d_table, int n, uint32_t n_wg)
+{
+    if (n_wg == 0) return;
+    const uint8_t *t = static_cast<const uint8_t *>(d_table);
+    hipLaunchKernelGGL(k_resize_list, dim3(n_wg), dim3(64), 0, s, reinterpret_cast<const uint32_t *>(t),
+                       reinterpret_cast<const ResizeEnt *>(t + list_table_head(n)), n);
 }

@@ -140,9 +140,9 @@ static int launch_tile_trees(str_er_ctx *c, const Batch &b, const BatchDev &bd, 
             } else
                 for (uint32_t k = 0; k < (uint32_t)(pd.tiles_x * pd.tiles_y); ++k) c->h_t1_list.push_back(pd.tile_base + k);
         }
-        if (!c->h_t1_list.empty()) HIP_TRY(c, hipMemcpyAsync(c->d_t1_list, c->h_t1_list.data(), 4 * c->h_t1_list.size(), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(c->d_t2_pairs, c->h_t2_pairs.data(), 4 * c->h_t2_pairs.size(), hipMemcpyHostToDevice, s));
-        HIP_TRY(c, wait_stream(c, s));   // (pageable host vectors)
+        if (!c->h_t1_list.empty()) HIP_TRY(c, table_copy(c, c->d_t1_list, c->h_t1_list.data(), 4 * c->h_t1_list.size()));
+        HIP_TRY(c, table_copy(c, c->d_t2_pairs, c->h_t2_pairs.data(), 4 * c->h_t2_pairs.size()));
+        if (!c->stage_tables) HIP_TRY(c, wait_stream(c, s));   // (pageable host vectors)
         c->n_t2_tiles = n2;
         c->t2_key = key;
     }
@@ -643,14 +643,14 @@ int upload_layout(str_er_ctx *c, Batch &b)
             c->layout_key.clear();          // the tables are being rebuilt: a failure below must not leave the old key naming them
             c->h_tile_plane.clear(); c->h_sb_plane.clear(); c->h_sb_first.clear(); c->h_nb_plane.clear();
             for (int i = 0; i < np; ++i) c->h_nb_plane.insert(c->h_nb_plane.end(), (size_t)b.planes[i].nb_count, (uint16_t)i);
-            HIP_TRY(c, hipMemcpyAsync(c->d_nb_plane, c->h_nb_plane.data(), 2 * c->h_nb_plane.size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(c, table_copy(c, c->d_nb_plane, c->h_nb_plane.data(), 2 * c->h_nb_plane.size()));
             c->h_group_plane.clear();
             if (b.group_x > 0 && b.group_y > 0)
                 for (int i = 0; i < np; ++i) {
                     const PlaneDesc &pd = b.planes[i];
                     c->h_group_plane.insert(c->h_group_plane.end(), (size_t)((pd.tiles_x + b.group_x - 1) / b.group_x) * ((pd.tiles_y + b.group_y - 1) / b.group_y), (uint16_t)i);
                 }
-            if (!c->h_group_plane.empty()) HIP_TRY(c, hipMemcpyAsync(c->d_group_plane, c->h_group_plane.data(), 2 * c->h_group_plane.size(), hipMemcpyHostToDevice, s));
+            if (!c->h_group_plane.empty()) HIP_TRY(c, table_copy(c, c->d_group_plane, c->h_group_plane.data(), 2 * c->h_group_plane.size()));
             // ... and the groups by class of plane: the chroma planes' first (run_batch launches k_group_merge once per class)
             c->h_group_list.clear(); c->n_groups_small = 0;
             if (b.group_x > 0 && b.group_y > 0) {
@@ -663,7 +663,7 @@ int upload_layout(str_er_ctx *c, Batch &b)
                     }
                     if (pass == 0) c->n_groups_small = (uint32_t)c->h_group_list.size();
                 }
-                if (!c->h_group_list.empty()) HIP_TRY(c, hipMemcpyAsync(c->d_group_list, c->h_group_list.data(), 4 * c->h_group_list.size(), hipMemcpyHostToDevice, s));
+                if (!c->h_group_list.empty()) HIP_TRY(c, table_copy(c, c->d_group_list, c->h_group_list.data(), 4 * c->h_group_list.size()));
             }
             for (int i = 0; i < np; ++i) {
                 const PlaneDesc &pd = b.planes[i];
@@ -680,12 +680,12 @@ int upload_layout(str_er_ctx *c, Batch &b)
                 } else blocks(0, pd.n_pairs);
             }
             if (c->h_sb_plane.size() > c->sb_slots) return fail(c, STR_ER_ECAPACITY, "seam block table capacity exceeded");
-            HIP_TRY(c, hipMemcpyAsync(c->d_tile_plane, c->h_tile_plane.data(), 2 * c->h_tile_plane.size(), hipMemcpyHostToDevice, s));
+            HIP_TRY(c, table_copy(c, c->d_tile_plane, c->h_tile_plane.data(), 2 * c->h_tile_plane.size()));
             if (!c->h_sb_plane.empty()) {
-                HIP_TRY(c, hipMemcpyAsync(c->d_sb_plane, c->h_sb_plane.data(), 2 * c->h_sb_plane.size(), hipMemcpyHostToDevice, s));
-                HIP_TRY(c, hipMemcpyAsync(c->d_sb_first, c->h_sb_first.data(), 4 * c->h_sb_first.size(), hipMemcpyHostToDevice, s));
+                HIP_TRY(c, table_copy(c, c->d_sb_plane, c->h_sb_plane.data(), 2 * c->h_sb_plane.size()));
+                HIP_TRY(c, table_copy(c, c->d_sb_first, c->h_sb_first.data(), 4 * c->h_sb_first.size()));
             }
-            HIP_TRY(c, wait_stream(c, s));   // pageable host vectors: make sure the copies are done
+            if (!c->stage_tables) HIP_TRY(c, wait_stream(c, s));   // pageable host vectors: make sure the copies are done (a list call staged them)
             c->layout_key = key;
         }
     }
@@ -1422,6 +1422,7 @@ void str_er_destroy(str_er_ctx *c)
     if (c->h_zero) (void)hipHostFree(c->h_zero);
     if (c->h_cands_spec) (void)hipHostFree(c->h_cands_spec);
     if (c->h_ocr) (void)hipHostFree(c->h_ocr);
+    if (c->h_stage) (void)hipHostFree(c->h_stage);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
     if (c->prio) { (void)hipStreamSynchronize(c->prio); (void)hipStreamDestroy(c->prio); }
@@ -1715,6 +1716,188 @@ try {
     for (int i = 0; i < n_planes; ++i)
         add_plane(b, dp + (size_t)i * dpitch, w, h, dstride, 0, 0, i & 255, 0);
     return run_batch(c, b, stages, out, t0, false);
+} ABI_GUARD(c)
+
+} // extern "C"
+
+// ---- lists of frames of different sizes ---------------------------------------------------------------------------------------------
+namespace {
+
+// The page-locked staging buffer and the device job tables of list calls, sized for the context's largest layout (first list call).
+int ensure_list_buffers(str_er_ctx *c)
+{
+    if (c->h_stage) return STR_ER_OK;
+    const int    nf = c->prm.max_frames, nl = c->prm.n_pyr_levels;
+    size_t tab = align_up(ingest_table_bytes(nf), 256);
+    for (int l = 1; l < nl; ++l) tab += align_up(resize_table_bytes(nf), 256);
+    // (upload_layout / launch_tile_trees: tile -> plane, group -> plane, group list, the two tile kernels' lists; seam blocks; workgroups)
+    const size_t cap = 16 * c->tile_slots + 6 * c->sb_slots + 2 * (size_t)c->max_planes * str_er_ctx::NB_PLANE_SHARE + tab + 16 * 256;
+    if (!c->d_list_tab) {
+        const int rc = dev_alloc(c, c->d_list_tab, tab);
+        if (rc != STR_ER_OK) return rc;
+        c->list_tab_bytes = tab;
+    }
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_stage), cap));
+    c->stage_cap = cap;
+    c->stage_used = 0;
+    return STR_ER_OK;
+}
+
+// One list call: its tables go through the staging buffer; a call that fails after staging waits for its copies before the buffer is reused.
+struct ListCall {
+    str_er_ctx *c;
+    bool        done = false;
+    explicit ListCall(str_er_ctx *cc) : c(cc) { c->stage_tables = true; c->stage_used = 0; }
+    ~ListCall()
+    {
+        if (!done && c->stage_used) (void)wait_stream(c, c->stream);
+        c->stage_tables = false;
+        c->stage_used = 0;
+    }
+    int finish(int rc) { done = rc == STR_ER_OK; return rc; }
+};
+
+int check_list(str_er_ctx *c, const str_er_image_ref *im, int32_t n, int32_t n_max, int mem_kind, int bpp, str_er_result **out, const char *what)
+{
+    if (!im || !out) return fail(c, STR_ER_EINVAL, "null argument");
+    if (n < 1) return fail(c, STR_ER_EINVAL, std::string("empty ") + what + " list");
+    if (n > n_max)
+        return fail(c, STR_ER_ECAPACITY, std::to_string(n) + " " + what + "s: more than the context's " + std::to_string(n_max) + " per call");
+    if (mem_kind != STR_ER_MEM_HOST && mem_kind != STR_ER_MEM_DEVICE) return fail(c, STR_ER_EINVAL, "bad mem_kind");
+    for (int32_t i = 0; i < n; ++i) {
+        const str_er_image_ref &r = im[i];
+        const std::string name = std::string(what) + " " + std::to_string(i);
+        if (!r.data) return fail(c, STR_ER_EINVAL, name + ": null data");
+        if (r.w < 1 || r.h < 1) return fail(c, STR_ER_EINVAL, name + ": empty");
+        if (r.stride < (int64_t)r.w * bpp) return fail(c, STR_ER_EINVAL, name + ": stride smaller than a row");
+        if (r.stride > 0x7FFFFFFF) return fail(c, STR_ER_EINVAL, name + ": stride too large");
+        if (r.w > c->prm.max_width || r.h > c->prm.max_height)
+            return fail(c, STR_ER_ECAPACITY, name + ": " + std::to_string(r.w) + " x " + std::to_string(r.h) + " larger than the context capacity " +
+                                                 std::to_string(c->prm.max_width) + " x " + std::to_string(c->prm.max_height));
+    }
+    return STR_ER_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int str_er_detect_bgr_list(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out)
+try {
+    if (!c) return STR_ER_EINVAL;
+    int rc = check_list(c, frames, n_frames, c->prm.max_frames, mem_kind, 3, out, "frame");
+    if (rc != STR_ER_OK) return rc;
+    *out = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, hipSetDevice(c->prm.device));
+    if ((rc = ensure_list_buffers(c)) != STR_ER_OK) return rc;
+    const int n = n_frames, nl = c->prm.n_pyr_levels;
+    // physical planes: frame after frame, each laid out as detect_bgr_impl lays out one frame -- per level [Y, Cr, Cb] plane_sz apart
+    // (color_pitch finds Y from Cr / Cb for track), rows padded to 64 bytes
+    std::vector<PlaneGeom> geo((size_t)n * nl);
+    std::vector<size_t>    fbase((size_t)n);
+    size_t pix = 0;
+    for (int f = 0; f < n; ++f) {
+        fbase[(size_t)f] = pix;
+        size_t fb = 0;
+        for (int l = 0; l < nl; ++l) {
+            PlaneGeom &g = geo[(size_t)f * nl + l];
+            pyr_dims(frames[f].w, frames[f].h, l, g.w, g.h);
+            g.stride = (int)align_up(g.w, 64);
+            g.off = fb;
+            fb += 3 * align_up((size_t)g.stride * g.h, 256);
+        }
+        pix += fb;
+    }
+    if (pix > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane pool too small");
+    auto G = [&](int f, int l) -> const PlaneGeom & { return geo[(size_t)f * nl + l]; };
+    auto plane_sz = [&](int f, int l) { return align_up((size_t)G(f, l).stride * G(f, l).h, 256); };
+
+    ListCall lc(c);
+    c->n_ev = 0; c->profile.clear(); rec(c, "begin", nullptr, true);
+    const hipStream_t ws = c->stream;
+    std::vector<IngestJob> ij((size_t)n);
+    {   // host frames: staged tightly (3 w bytes a row), each from a 4-byte boundary when that fits
+        size_t need = 0;
+        for (int f = 0; f < n; ++f) need = align_up(need, 4) + (size_t)3 * frames[f].w * frames[f].h;
+        const size_t al = need <= c->in_bytes ? 4 : 1;
+        size_t at = 0;
+        for (int f = 0; f < n; ++f) {
+            const str_er_image_ref &r = frames[f];
+            IngestJob &j = ij[(size_t)f];
+            const size_t row = (size_t)3 * r.w;
+            if (mem_kind == STR_ER_MEM_HOST) {
+                at = align_up(at, al);
+                if (at + row * r.h > c->in_bytes) return fail(c, STR_ER_ECAPACITY, "staging buffer too small");
+                if (r.stride == (int64_t)row) HIP_TRY(c, hipMemcpyAsync(c->d_in + at, r.data, row * r.h, hipMemcpyHostToDevice, ws));
+                else HIP_TRY(c, hipMemcpy2DAsync(c->d_in + at, row, r.data, (size_t)r.stride, row, (size_t)r.h, hipMemcpyHostToDevice, ws));
+                j.src = c->d_in + at; j.stride = (int64_t)row;
+                at += row * r.h;
+            } else { j.src = r.data; j.stride = r.stride; }
+            j.dst = c->d_pix + fbase[(size_t)f] + G(f, 0).off; j.plane_pitch = (int64_t)plane_sz(f, 0);
+            j.w = r.w; j.h = r.h; j.dstride = G(f, 0).stride;
+        }
+    }
+    std::vector<uint8_t> tab(ingest_table_bytes(n));
+    const uint32_t n_wg = build_ingest_table(ij.data(), n, tab.data());
+    HIP_TRY(c, table_copy(c, c->d_list_tab, tab.data(), tab.size()));
+    launch_bgr_to_ycrcb_list(ws, c->d_list_tab, n, n_wg);
+    rec(c, "channels", ws);
+    size_t tab_at = align_up(ingest_table_bytes(c->prm.max_frames), 256);
+    std::vector<ResizeJob> rj((size_t)n);
+    for (int l = 1; l < nl; ++l) {
+        for (int f = 0; f < n; ++f) {
+            const PlaneGeom &a = G(f, l - 1), &d = G(f, l);
+            ResizeJob &j = rj[(size_t)f];
+            j.src = c->d_pix + fbase[(size_t)f] + a.off; j.dst = c->d_pix + fbase[(size_t)f] + d.off;
+            j.splane_pitch = (int64_t)plane_sz(f, l - 1); j.dplane_pitch = (int64_t)plane_sz(f, l);
+            j.sw = a.w; j.sh = a.h; j.sstride = a.stride; j.dw = d.w; j.dh = d.h; j.dstride = d.stride;
+        }
+        tab.assign(resize_table_bytes(n), 0);
+        const uint32_t wg = build_resize_table(rj.data(), n, 3, tab.data());
+        HIP_TRY(c, table_copy(c, c->d_list_tab + tab_at, tab.data(), tab.size()));
+        launch_resize_list(ws, c->d_list_tab + tab_at, n, wg);
+        tab_at += align_up(resize_table_bytes(c->prm.max_frames), 256);
+    }
+    rec(c, "pyramid", ws);
+
+    Batch b;
+    for (int f = 0; f < n; ++f)
+        for (int l = 0; l < nl; ++l)
+            for (size_t k = 0; k < c->chans.size(); ++k) {
+                const int ch = c->chans[k];
+                const uint8_t *p = c->d_pix + fbase[(size_t)f] + G(f, l).off + (size_t)(ch % 3) * plane_sz(f, l);
+                add_plane(b, p, G(f, l).w, G(f, l).h, G(f, l).stride, ch >= 3, (uint32_t)f, ch, l);
+                b.planes.back().color_pitch = (uint32_t)plane_sz(f, l);
+            }
+    b.planes_per_image = (int)c->chans.size();
+    return lc.finish(run_batch(c, b, stages, out, t0, true));
+} ABI_GUARD(c)
+
+int str_er_detect_planes_list(str_er_ctx *c, const str_er_image_ref *planes, int32_t n_planes, int mem_kind, uint32_t stages, str_er_result **out)
+try {
+    if (!c) return STR_ER_EINVAL;
+    int rc = check_list(c, planes, n_planes, c->max_planes, mem_kind, 1, out, "plane");
+    if (rc != STR_ER_OK) return rc;
+    *out = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, hipSetDevice(c->prm.device));
+    if ((rc = ensure_list_buffers(c)) != STR_ER_OK) return rc;
+    ListCall lc(c);
+    Batch b;
+    size_t at = 0;
+    for (int i = 0; i < n_planes; ++i) {
+        const str_er_image_ref &r = planes[i];
+        if (mem_kind == STR_ER_MEM_HOST) {      // (as str_er_detect_planes stages a plane: rows padded to 64 bytes)
+            const int ds = (int)align_up(r.w, 64);
+            const size_t sz = align_up((size_t)ds * r.h, 256);
+            if (at + sz > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane pool too small");
+            HIP_TRY(c, hipMemcpy2DAsync(c->d_pix + at, (size_t)ds, r.data, (size_t)r.stride, (size_t)r.w, (size_t)r.h, hipMemcpyHostToDevice, c->stream));
+            add_plane(b, c->d_pix + at, r.w, r.h, ds, 0, 0, i & 255, 0);
+            at += sz;
+        } else add_plane(b, r.data, r.w, r.h, (int)r.stride, 0, 0, i & 255, 0);
+    }
+    return lc.finish(run_batch(c, b, stages, out, t0, false));
 } ABI_GUARD(c)
 
 int str_er_internal_last_cands(str_er_ctx *c, const void **d_cands, uint32_t *n, int *device)

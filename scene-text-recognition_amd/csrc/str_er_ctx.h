@@ -179,6 +179,13 @@ struct str_er_ctx {
     uint8_t  *h_ocr = nullptr; size_t h_ocr_cap = 0;  // page-locked results for up to so many ERs
     uint64_t  n_ocr_spec = 0, n_ocr_redo = 0;         // statistics: batches scored behind classify / scored again
 
+    // list calls (str_er_detect_*_list): frames of different sizes make a new layout every call, and its tables -- tile / seam-block / group
+    // lookups, the list kernels' job tables -- reach the device through one page-locked buffer instead of pageable vectors and a wait.  One
+    // buffer does: a list call has waited for its stream by the time it returns.  Allocated by the first list call, for the largest layout.
+    bool      stage_tables = false;                   // set during a list call (table_copy)
+    uint8_t  *h_stage = nullptr; size_t stage_cap = 0, stage_used = 0;
+    uint8_t  *d_list_tab = nullptr; size_t list_tab_bytes = 0;      // the list kernels' job tables (device)
+
     HostCascade casc[2];
     bool svm_loaded = false;
     SvmDev svm{};
@@ -218,6 +225,23 @@ static hipError_t wait_stream(str_er_ctx *c, hipStream_t s)
         if (e != hipErrorNotReady) return e;
         if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(c->wait_spin_us)) std::this_thread::sleep_for(std::chrono::microseconds(100));
     }
+}
+
+// A host table to the device on c->stream.  In a list call through the page-locked staging buffer: nothing to wait for before the kernels that
+// read it.  Otherwise straight from `src` (pageable): the caller waits before `src` changes.
+static hipError_t table_copy(str_er_ctx *c, void *dst, const void *src, size_t n)
+{
+    if (!c->stage_tables) return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream);
+    size_t at = (c->stage_used + 255) / 256 * 256;
+    if (at + n > c->stage_cap) {        // (a batch repeated inside the same call: what was staged before has been read once the stream is idle)
+        const hipError_t e = wait_stream(c, c->stream);
+        if (e != hipSuccess) return e;
+        at = 0;
+        if (n > c->stage_cap) return hipErrorInvalidValue;
+    }
+    std::memcpy(c->h_stage + at, src, n);
+    c->stage_used = at + n;
+    return hipMemcpyAsync(dst, c->h_stage + at, n, hipMemcpyHostToDevice, c->stream);
 }
 
 #define HIP_TRY(ctx, expr)                                                                         \

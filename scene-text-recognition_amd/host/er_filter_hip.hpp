@@ -126,6 +126,41 @@ public:
         return std::vector<double>(t, t + 7);
     }
 
+    // text_detect for a batch of 8UC3 BGR images of different sizes in one call (str_er_detect_bgr_list): what the reference's image
+    // mode does one cv::imread at a time.  trees[f], root[f], pool[f], strong[f], weak[f] are what text_detect gives for frame f alone.
+    // Returns the batch's 7-slot times vector.
+    std::vector<double> text_detect_batch(const std::vector<Image8> &frames, std::vector<std::vector<ERTree>> &trees, std::vector<ERs> &root,
+                                          std::vector<std::vector<ERs>> &pool, std::vector<std::vector<ERs>> &strong,
+                                          std::vector<std::vector<ERs>> &weak)
+    {
+        std::vector<str_er_image_ref> refs(frames.size());
+        for (size_t f = 0; f < frames.size(); ++f) {
+            if (frames[f].channels != 3) throw std::runtime_error("text_detect_batch expects 8UC3 BGR images");
+            refs[f].data = frames[f].data; refs[f].w = frames[f].cols; refs[f].h = frames[f].rows; refs[f].stride = frames[f].step;
+        }
+        str_er_result *r = nullptr;
+        check(str_er_detect_bgr_list(ctx_.get(), refs.data(), (int32_t)refs.size(), STR_ER_MEM_HOST, STR_ER_STAGE_ALL | STR_ER_WANT_NODES, &r));
+        std::unique_ptr<str_er_result, void (*)(str_er_result *)> guard(r, str_er_result_free);
+        const int n = str_er_result_n_planes(r);
+        const size_t nf = frames.size();
+        std::vector<int> per(nf, 0), at(nf, 0);
+        std::vector<str_er_plane_info> info((size_t)n);
+        for (int i = 0; i < n; ++i) { str_er_result_plane_info(r, i, &info[(size_t)i]); ++per[info[(size_t)i].frame]; }
+        trees.assign(nf, std::vector<ERTree>()); root.assign(nf, ERs());
+        pool.assign(nf, std::vector<ERs>()); strong.assign(nf, std::vector<ERs>()); weak.assign(nf, std::vector<ERs>());
+        for (size_t f = 0; f < nf; ++f) {       // (sized first: the ERs point into the trees' node vectors)
+            trees[f].assign((size_t)per[f], ERTree()); root[f].assign((size_t)per[f], nullptr);
+            pool[f].assign((size_t)per[f], ERs()); strong[f].assign((size_t)per[f], ERs()); weak[f].assign((size_t)per[f], ERs());
+        }
+        for (int i = 0; i < n; ++i) {
+            const size_t f = info[(size_t)i].frame, k = (size_t)at[f]++;
+            unpack_plane(r, i, trees[f][k], pool[f][k], strong[f][k], weak[f][k]);
+            root[f][k] = trees[f][k].root;
+        }
+        const double *t = str_er_result_times(r);
+        return std::vector<double>(t, t + 7);
+    }
+
     // ER* ERFilter::er_tree_extract(Mat input) (src/ER.cpp:240-374); input must be 8UC1 (:242)
     ER *er_tree_extract(const Image8 &input, ERTree &tree)
     {
