@@ -286,6 +286,13 @@ typedef struct str_er_image_ref {
 int str_er_detect_bgr_list(str_er_ctx *ctx, const str_er_image_ref *frames, int32_t n_frames,
                            int mem_kind, uint32_t stages, str_er_result **out);
 
+/* str_er_detect_nv12 for n_frames NV12 frames that need not share a size (several cameras, or photographs through a hardware
+ * decoder): frames[i].data = the top-left pixel of its luma plane, the interleaved chroma plane follows h rows later (h / 2 rows),
+ * stride >= w bytes per row both; w and h even.  The result for frame i is exactly what str_er_detect_nv12 gives for that frame
+ * alone, with frame = i.  Capacity rules, error codes and the context after an error: those of str_er_detect_bgr_list.          */
+int str_er_detect_nv12_list(str_er_ctx *ctx, const str_er_image_ref *frames, int32_t n,
+                            int mem_kind, uint32_t stages, str_er_result **out);
+
 /* str_er_detect_planes for n_planes independent 8UC1 planes of assorted sizes (n_planes <= the context's planes per call:
  * max_frames x channels x levels).  Plane i's result is what str_er_detect_planes gives for it alone, with ch = i & 255 in its plane
  * info and candidates (as for plane i of a str_er_detect_planes call).                                                           */
@@ -554,6 +561,9 @@ int64_t str_er_workspace_bytes(const str_er_ctx *ctx);
  *     str_er_stream_submit(s, slot, w, h, stride, frame_pitch, n_frames, stages, &ticket);
  *     if (str_er_stream_pending(s) == depth) str_er_stream_next(s, &result, &ticket);   // oldest first; blocks until it is done
  *
+ * Photographs of assorted sizes: decode each into the buffer at an offset of your choosing and submit the list of them with
+ * str_er_stream_submit_list (NV12: str_er_stream_submit_nv12_list) instead.
+ *
  * acquire never blocks: with every buffer in flight it returns STR_ER_ESTATE (collect a result first).  Results come
  * back in submission order and are freed with str_er_result_free.  Models are loaded into every context with
  * str_er_stream_load_cascade (other per-context calls: str_er_stream_context).  One producer/consumer thread at a time. */
@@ -573,6 +583,21 @@ int         str_er_stream_submit_nv12(str_er_stream *s, int32_t slot, int32_t w,
 /* convenience: acquire + copy the frames in (one extra host copy) + submit */
 int         str_er_stream_submit_copy(str_er_stream *s, const uint8_t *bgr, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch,
                                       int32_t n_frames, uint32_t stages, uint64_t *ticket);
+/* A list of BGR frames of assorted sizes in the slot's staging buffer (str_er_detect_bgr_list): every frames[i].data points into
+ * the buffer str_er_stream_acquire returned for `slot`, at any offset and stride; the refs array is copied here.  The worker
+ * uploads the byte span from the lowest frame start to the highest frame end and detects on the copy in device memory; frame i
+ * of the result is what str_er_detect_bgr gives for that frame alone, with frame = i.  Checked here: a frame not wholly inside
+ * the buffer, a stride below a row, a NULL data or an empty frame -> STR_ER_EINVAL; a frame over max_width x max_height or
+ * n > max_frames -> STR_ER_ECAPACITY; the message names the frame and the slot stays acquired.  Uniform and list submissions
+ * may alternate on one stream; results come back in ticket order.                                                          */
+int         str_er_stream_submit_list(str_er_stream *s, int32_t slot, const str_er_image_ref *frames, int32_t n, uint32_t stages,
+                                      uint64_t *ticket);
+/* ... the same for NV12 frames (str_er_detect_nv12_list): a frame is h + h/2 rows of `stride` bytes; odd w or h -> STR_ER_EINVAL */
+int         str_er_stream_submit_nv12_list(str_er_stream *s, int32_t slot, const str_er_image_ref *frames, int32_t n, uint32_t stages,
+                                           uint64_t *ticket);
+/* convenience, BGR: acquire + pack the frames (host memory) into the buffer + str_er_stream_submit_list.  Frames start at 4-byte
+ * boundaries when the padded total fits the buffer, otherwise back to back.  On an error no slot stays acquired.           */
+int         str_er_stream_submit_copy_list(str_er_stream *s, const str_er_image_ref *frames, int32_t n, uint32_t stages, uint64_t *ticket);
 int         str_er_stream_next(str_er_stream *s, str_er_result **out, uint64_t *ticket);
 int32_t     str_er_stream_pending(str_er_stream *s);
 

@@ -150,6 +150,7 @@ def load_library():
                                        C.c_uint32, C.POINTER(vp)]
     L.str_er_detect_bgr_list.argtypes = [vp, vp, C.c_int32, C.c_int, C.c_uint32, C.POINTER(vp)]
     L.str_er_detect_planes_list.argtypes = [vp, vp, C.c_int32, C.c_int, C.c_uint32, C.POINTER(vp)]
+    L.str_er_detect_nv12_list.argtypes = [vp, vp, C.c_int32, C.c_int, C.c_uint32, C.POINTER(vp)]
     L.str_er_compute_channels.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp]
     L.str_er_classify_boxes.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp, vp]
     L.str_er_lbp_hist.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp]
@@ -213,6 +214,9 @@ def load_library():
     L.str_er_stream_submit_nv12.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.str_er_detect_nv12.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int, C.c_uint32, C.POINTER(vp)]
     L.str_er_stream_submit_copy.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.str_er_stream_submit_list.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.str_er_stream_submit_nv12_list.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.str_er_stream_submit_copy_list.argtypes = [vp, vp, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.str_er_stream_next.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.str_er_stream_pending.argtypes = [vp]
     L.str_er_calc_color.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp]
@@ -622,6 +626,23 @@ class ERFilter:
         refs = [ImageRef(int(t[0]), int(t[1]), int(t[2]), int(t[3]) if len(t) > 3 else 3 * int(t[1])) for t in ptrs_dims]
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_DEVICE, stages | (WANT_NODES if want_nodes else 0))
 
+    def text_detect_nv12_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
+        """text_detect_nv12 for a sequence of NV12 frames of any (even) sizes in one call: each a (h + h/2, w) uint8 array (luma rows,
+        then interleaved Cb/Cr rows) or a view of one with a row stride (not copied).  Frame i's result is text_detect_nv12's on it alone."""
+        keep = [_row_view(f, 1) for f in frames]
+        refs = []
+        for a in keep:
+            if a.shape[0] % 3:
+                raise ValueError("an NV12 frame has h + h/2 rows (h even)")
+            refs.append(ImageRef(_np_ptr(a), a.shape[1], a.shape[0] // 3 * 2, a.strides[0]))
+        return self._detect_list(self.L.str_er_detect_nv12_list, refs, MEM_HOST, stages | (WANT_NODES if want_nodes else 0))
+
+    def detect_nv12_list_device(self, ptrs_dims, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
+        """text_detect_nv12_list for frames resident in HBM: ptrs_dims = [(device address of the luma plane, w, h[, stride]), ...]
+        (stride default w; chroma h rows after the luma plane)."""
+        refs = [ImageRef(int(t[0]), int(t[1]), int(t[2]), int(t[3]) if len(t) > 3 else int(t[1])) for t in ptrs_dims]
+        return self._detect_list(self.L.str_er_detect_nv12_list, refs, MEM_DEVICE, stages | (WANT_NODES if want_nodes else 0))
+
     def detect_planes_list_device(self, ptrs_dims, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes_list for planes resident in HBM: ptrs_dims = [(device address, w, h[, stride]), ...] (stride default w)."""
         refs = [ImageRef(int(t[0]), int(t[1]), int(t[2]), int(t[3]) if len(t) > 3 else int(t[1])) for t in ptrs_dims]
@@ -944,6 +965,7 @@ class FrameStream:
             raise StrErError(rc, (self.L.str_er_last_error(None) or b"").decode())
         self.h = h
         self.params = p
+        self._base = {}                     # slot -> address of its staging buffer (acquire)
 
     def close(self) -> None:
         if getattr(self, "h", None):
@@ -971,6 +993,7 @@ class FrameStream:
         """(slot, uint8 view of the pinned staging buffer)."""
         slot, buf, cap = C.c_int32(), C.c_void_p(), C.c_int64()
         self._check(self.L.str_er_stream_acquire(self.h, C.byref(slot), C.byref(buf), C.byref(cap)))
+        self._base[slot.value] = buf.value
         arr = np.frombuffer((C.c_uint8 * cap.value).from_address(buf.value), dtype=np.uint8)
         return slot.value, arr
 
@@ -992,6 +1015,31 @@ class FrameStream:
         n, h, w, _ = a.shape
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_copy(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, n, stages, C.byref(t)))
+        return int(t.value)
+
+    def _submit_list(self, fn, slot: int, layout, stages: int) -> int:
+        base = self._base.get(slot, 0)
+        refs = [ImageRef(base + int(o), int(w), int(h), int(st)) for o, w, h, st in layout]
+        arr = (ImageRef * max(1, len(refs)))(*refs)
+        t = C.c_uint64()
+        self._check(fn(self.h, slot, arr, len(refs), stages, C.byref(t)))
+        return int(t.value)
+
+    def submit_list(self, slot: int, layout, stages: int = STAGE_ALL) -> int:
+        """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
+        return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
+
+    def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL) -> int:
+        """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
+        return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
+
+    def submit_copy_list(self, frames, stages: int = STAGE_ALL) -> int:
+        """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
+        keep = [_row_view(f, 3) for f in frames]
+        refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
+        arr = (ImageRef * max(1, len(refs)))(*refs)
+        t = C.c_uint64()
+        self._check(self.L.str_er_stream_submit_copy_list(self.h, arr, len(refs), stages, C.byref(t)))
         return int(t.value)
 
     def pending(self) -> int:

@@ -52,11 +52,11 @@ void launch_resize(hipStream_t s, const uint8_t *src, int sw, int sh, int sstrid
                    int64_t sframe_pitch, uint8_t *dst, int dw, int dh, int dstride, int64_t dplane_pitch,
                    int64_t dframe_pitch, int planes_per_frame, int n_frames);
 
-// Lists of frames of different sizes (str_er_detect_bgr_list): a job is one frame (ingest) or one frame's pyramid level (resize, `planes`
+// Lists of frames of different sizes (str_er_detect_bgr_list / _nv12_list): a job is one frame (ingest) or one frame's pyramid level (resize, `planes`
 // planes per job).  The kernels' device table -- *_table_bytes(n) bytes -- is built on the host into `out` and copied to the device by
 // the caller; the builders return the workgroups of the launch.  One launch for all jobs.
 struct IngestJob {
-    const uint8_t *src; int64_t stride;           // BGR frame (device memory)
+    const uint8_t *src; int64_t stride;           // BGR frame (device memory); NV12: its luma plane, chroma h rows further on
     uint8_t *dst; int64_t plane_pitch;            // its Y plane; Cr and Cb follow plane_pitch bytes apart
     int32_t w, h, dstride;
 };
@@ -69,6 +69,7 @@ size_t   resize_table_bytes(int n);
 uint32_t build_ingest_table(const IngestJob *jobs, int n, void *out);
 uint32_t build_resize_table(const ResizeJob *jobs, int n, int planes, void *out);
 void     launch_bgr_to_ycrcb_list(hipStream_t s, const void *d_table, int n, uint32_t n_wg);
+void     launch_nv12_to_ycrcb_list(hipStream_t s, const void *d_table, int n, uint32_t n_wg);
 void     launch_resize_list(hipStream_t s, const void *d_table, int n, uint32_t n_wg);
 
 // sparse: the small-LDS / high-occupancy size of the kernel (text-like frames); dense: the big one (noise-like frames)

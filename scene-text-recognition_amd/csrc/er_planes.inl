@@ -91,19 +91,7 @@ __global__ __launch_bounds__(256) void k_nv12_to_ycrcb(const uint8_t *__restrict
     const uint8_t *ys = nv12 + (size_t)f * frame_pitch + (size_t)y * stride + x;
     const uint8_t *uv = nv12 + (size_t)f * frame_pitch + (size_t)h * stride + (size_t)(y >> 1) * stride + x;     // (x is even: pair x / 2 starts at byte x)
     const size_t   dof = (size_t)f * dst_frame_pitch + (size_t)y * dstride + x;
-    if (aligned && x + 4 <= w) {
-        const uint32_t yy = *reinterpret_cast<const uint32_t *>(ys), c = *reinterpret_cast<const uint32_t *>(uv);     // U0 V0 U1 V1
-        const uint32_t u0 = c & 0xFFu, v0 = (c >> 8) & 0xFFu, u1 = (c >> 16) & 0xFFu, v1 = c >> 24;
-        *reinterpret_cast<uint32_t *>(yp + dof) = yy;
-        *reinterpret_cast<uint32_t *>(crp + dof) = v0 * 0x0101u | (v1 * 0x0101u) << 16;
-        *reinterpret_cast<uint32_t *>(cbp + dof) = u0 * 0x0101u | (u1 * 0x0101u) << 16;
-    } else {
-        for (int k = 0; k < 4 && x + k < w; ++k) {
-            yp[dof + k] = ys[k];
-            cbp[dof + k] = uv[(k & ~1)];
-            crp[dof + k] = uv[(k & ~1) + 1];
-        }
-    }
+#include "nv12_quad_body.inl"
 }
 
 void launch_nv12_to_ycrcb(hipStream_t s, const uint8_t *nv12, int w, int h, int64_t stride, int64_t frame_pitch, int n_frames, uint8_t *y, uint8_t *cr,
@@ -222,16 +210,18 @@ void launch_resize(hipStream_t s, const uint8_t *src, int sw, int sh, int sstrid
 }
 
 // ------------------------------------------------------------------------------------
-// Lists of frames of different sizes (str_er_detect_bgr_list): one launch converts every frame of the list, one launch per
+// Lists of frames of different sizes (str_er_detect_bgr_list / _nv12_list): one launch converts every frame of the list, one launch per
 // pyramid level resizes every frame's three planes.  The grid is the frames' workgroups back to back; a table in device memory --
 // first workgroup of every job (n + 1 words), then the jobs -- tells a workgroup whose it is (a binary search over the prefix words:
-// scalar loads, uniform over the workgroup).  The per-pixel work is the one of k_bgr_to_ycrcb / k_resize: the same text (*_body.inl).
+// scalar loads, uniform over the workgroup).  The per-pixel work is the one of k_bgr_to_ycrcb / k_nv12_to_ycrcb / k_resize: the same text
+// (*_body.inl).
 // ------------------------------------------------------------------------------------
 struct IngestEnt {
-    const uint8_t *src;          // pixel (0, 0) of the BGR frame
+    const uint8_t *src;          // pixel (0, 0) of the BGR frame (NV12: of its luma plane)
     uint8_t       *y;            // pixel (0, 0) of its Y plane; Cr, Cb follow plane_pitch apart
     int64_t        stride, plane_pitch;
     int32_t        w, dstride, aligned, row_wgs;     // row_wgs: workgroups of a row (256 lanes x 4 pixels each)
+    const uint8_t *uv;           // NV12: the first chroma row, h rows below src (not read by the BGR kernel)
 };
 struct ResizeEnt {
     const uint8_t *src;          // the job's first source / destination plane; the others follow splane_pitch / dplane_pitch apart
@@ -268,6 +258,22 @@ __global__ __launch_bounds__(256) void k_bgr_to_ycrcb_list(const uint32_t *__res
 #include "ycrcb_quad_body.inl"
 }
 
+__global__ __launch_bounds__(256) void k_nv12_to_ycrcb_list(const uint32_t *__restrict__ first, const IngestEnt *__restrict__ jobs, int n)
+{
+    const int f = find_job(first, n, blockIdx.x);
+    const IngestEnt e = jobs[f];
+    const uint32_t local = blockIdx.x - first[f];
+    const int y = (int)(local / (uint32_t)e.row_wgs), xb = (int)(local - (uint32_t)y * (uint32_t)e.row_wgs);
+    const int x = (xb * 256 + (int)threadIdx.x) * 4;
+    const int w = e.w, aligned = e.aligned;
+    if (x >= w) return;
+    const uint8_t *ys = e.src + (size_t)y * e.stride + x;
+    const uint8_t *uv = e.uv + (size_t)(y >> 1) * e.stride + x;          // (x is even: pair x / 2 starts at byte x)
+    uint8_t       *yp = e.y, *crp = e.y + e.plane_pitch, *cbp = e.y + 2 * e.plane_pitch;
+    const size_t   dof = (size_t)y * e.dstride + x;
+#include "nv12_quad_body.inl"
+}
+
 __global__ __launch_bounds__(64) void k_resize_list(const uint32_t *__restrict__ first, const ResizeEnt *__restrict__ jobs, int n)
 {
     const int j = find_job(first, n, blockIdx.x);
@@ -300,6 +306,7 @@ uint32_t build_ingest_table(const IngestJob *jobs, int n, void *out)
         IngestEnt e{};
         e.src = j.src; e.y = j.dst; e.stride = j.stride; e.plane_pitch = j.plane_pitch; e.w = j.w; e.dstride = j.dstride;
         e.row_wgs = ((j.w + 3) / 4 + 255) / 256;
+        e.uv = j.src + (size_t)j.h * (size_t)j.stride;
         // (per frame: a host frame staged tightly has 3 w bytes a row, a device frame the caller's pitch)
         e.aligned = ((reinterpret_cast<uintptr_t>(j.src) | (uintptr_t)j.stride) % 4 == 0) &&
                     ((reinterpret_cast<uintptr_t>(j.dst) | (uintptr_t)j.plane_pitch | (uintptr_t)j.dstride) % 4 == 0);
@@ -336,6 +343,14 @@ void launch_bgr_to_ycrcb_list(hipStream_t s, const void *d_table, int n, uint32_
     if (n_wg == 0) return;
     const uint8_t *t = static_cast<const uint8_t *>(d_table);
     hipLaunchKernelGGL(k_bgr_to_ycrcb_list, dim3(n_wg), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(t),
+                       reinterpret_cast<const IngestEnt *>(t + list_table_head(n)), n);
+}
+
+void launch_nv12_to_ycrcb_list(hipStream_t s, const void *d_table, int n, uint32_t n_wg)
+{
+    if (n_wg == 0) return;
+    const uint8_t *t = static_cast<const uint8_t *>(d_table);
+    hipLaunchKernelGGL(k_nv12_to_ycrcb_list, dim3(n_wg), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(t),
                        reinterpret_cast<const IngestEnt *>(t + list_table_head(n)), n);
 }
 

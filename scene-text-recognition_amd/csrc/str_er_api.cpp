@@ -1757,7 +1757,8 @@ struct ListCall {
     int finish(int rc) { done = rc == STR_ER_OK; return rc; }
 };
 
-int check_list(str_er_ctx *c, const str_er_image_ref *im, int32_t n, int32_t n_max, int mem_kind, int bpp, str_er_result **out, const char *what)
+int check_list(str_er_ctx *c, const str_er_image_ref *im, int32_t n, int32_t n_max, int mem_kind, int bpp, str_er_result **out, const char *what,
+               bool nv12 = false)
 {
     if (!im || !out) return fail(c, STR_ER_EINVAL, "null argument");
     if (n < 1) return fail(c, STR_ER_EINVAL, std::string("empty ") + what + " list");
@@ -1771,6 +1772,7 @@ int check_list(str_er_ctx *c, const str_er_image_ref *im, int32_t n, int32_t n_m
         if (r.w < 1 || r.h < 1) return fail(c, STR_ER_EINVAL, name + ": empty");
         if (r.stride < (int64_t)r.w * bpp) return fail(c, STR_ER_EINVAL, name + ": stride smaller than a row");
         if (r.stride > 0x7FFFFFFF) return fail(c, STR_ER_EINVAL, name + ": stride too large");
+        if (nv12 && ((r.w | r.h) & 1)) return fail(c, STR_ER_EINVAL, name + ": NV12 frames have even width and height");
         if (r.w > c->prm.max_width || r.h > c->prm.max_height)
             return fail(c, STR_ER_ECAPACITY, name + ": " + std::to_string(r.w) + " x " + std::to_string(r.h) + " larger than the context capacity " +
                                                  std::to_string(c->prm.max_width) + " x " + std::to_string(c->prm.max_height));
@@ -1778,14 +1780,11 @@ int check_list(str_er_ctx *c, const str_er_image_ref *im, int32_t n, int32_t n_m
     return STR_ER_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int str_er_detect_bgr_list(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out)
-try {
+// (nv12: a frame's `data` is its luma plane of h rows, the interleaved chroma plane of h / 2 rows follows, `stride` bytes per row both)
+int detect_list_impl(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out, bool nv12)
+{
     if (!c) return STR_ER_EINVAL;
-    int rc = check_list(c, frames, n_frames, c->prm.max_frames, mem_kind, 3, out, "frame");
+    int rc = check_list(c, frames, n_frames, c->prm.max_frames, mem_kind, nv12 ? 1 : 3, out, "frame", nv12);
     if (rc != STR_ER_OK) return rc;
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1817,22 +1816,24 @@ try {
     c->n_ev = 0; c->profile.clear(); rec(c, "begin", nullptr, true);
     const hipStream_t ws = c->stream;
     std::vector<IngestJob> ij((size_t)n);
-    {   // host frames: staged tightly (3 w bytes a row), each from a 4-byte boundary when that fits
+    {   // host frames: staged tightly (3 w bytes a row; NV12: h + h / 2 rows of w bytes), each from a 4-byte boundary when that fits
+        auto row_of = [&](const str_er_image_ref &r) { return nv12 ? (size_t)r.w : (size_t)3 * r.w; };
+        auto rows_of = [&](const str_er_image_ref &r) { return nv12 ? (size_t)r.h + r.h / 2 : (size_t)r.h; };
         size_t need = 0;
-        for (int f = 0; f < n; ++f) need = align_up(need, 4) + (size_t)3 * frames[f].w * frames[f].h;
+        for (int f = 0; f < n; ++f) need = align_up(need, 4) + row_of(frames[f]) * rows_of(frames[f]);
         const size_t al = need <= c->in_bytes ? 4 : 1;
         size_t at = 0;
         for (int f = 0; f < n; ++f) {
             const str_er_image_ref &r = frames[f];
             IngestJob &j = ij[(size_t)f];
-            const size_t row = (size_t)3 * r.w;
+            const size_t row = row_of(r), rows = rows_of(r);
             if (mem_kind == STR_ER_MEM_HOST) {
                 at = align_up(at, al);
-                if (at + row * r.h > c->in_bytes) return fail(c, STR_ER_ECAPACITY, "staging buffer too small");
-                if (r.stride == (int64_t)row) HIP_TRY(c, hipMemcpyAsync(c->d_in + at, r.data, row * r.h, hipMemcpyHostToDevice, ws));
-                else HIP_TRY(c, hipMemcpy2DAsync(c->d_in + at, row, r.data, (size_t)r.stride, row, (size_t)r.h, hipMemcpyHostToDevice, ws));
+                if (at + row * rows > c->in_bytes) return fail(c, STR_ER_ECAPACITY, "staging buffer too small");
+                if (r.stride == (int64_t)row) HIP_TRY(c, hipMemcpyAsync(c->d_in + at, r.data, row * rows, hipMemcpyHostToDevice, ws));
+                else HIP_TRY(c, hipMemcpy2DAsync(c->d_in + at, row, r.data, (size_t)r.stride, row, rows, hipMemcpyHostToDevice, ws));
                 j.src = c->d_in + at; j.stride = (int64_t)row;
-                at += row * r.h;
+                at += row * rows;
             } else { j.src = r.data; j.stride = r.stride; }
             j.dst = c->d_pix + fbase[(size_t)f] + G(f, 0).off; j.plane_pitch = (int64_t)plane_sz(f, 0);
             j.w = r.w; j.h = r.h; j.dstride = G(f, 0).stride;
@@ -1841,7 +1842,8 @@ try {
     std::vector<uint8_t> tab(ingest_table_bytes(n));
     const uint32_t n_wg = build_ingest_table(ij.data(), n, tab.data());
     HIP_TRY(c, table_copy(c, c->d_list_tab, tab.data(), tab.size()));
-    launch_bgr_to_ycrcb_list(ws, c->d_list_tab, n, n_wg);
+    if (nv12) launch_nv12_to_ycrcb_list(ws, c->d_list_tab, n, n_wg);
+    else launch_bgr_to_ycrcb_list(ws, c->d_list_tab, n, n_wg);
     rec(c, "channels", ws);
     size_t tab_at = align_up(ingest_table_bytes(c->prm.max_frames), 256);
     std::vector<ResizeJob> rj((size_t)n);
@@ -1872,6 +1874,20 @@ try {
             }
     b.planes_per_image = (int)c->chans.size();
     return lc.finish(run_batch(c, b, stages, out, t0, true));
+}
+
+} // namespace
+
+extern "C" {
+
+int str_er_detect_bgr_list(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out)
+try {
+    return detect_list_impl(c, frames, n_frames, mem_kind, stages, out, false);
+} ABI_GUARD(c)
+
+int str_er_detect_nv12_list(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out)
+try {
+    return detect_list_impl(c, frames, n_frames, mem_kind, stages, out, true);
 } ABI_GUARD(c)
 
 int str_er_detect_planes_list(str_er_ctx *c, const str_er_image_ref *planes, int32_t n_planes, int mem_kind, uint32_t stages, str_er_result **out)

@@ -14,6 +14,10 @@
 // stream ran at 1 / (upload + compute) instead of 1 / max(upload, compute): NV12 frames, a third of the link's capacity, at 0.81 of the
 // device-resident rate.  Now one upload owns the link at a time (a batch's frames go into a device buffer of its slot, own copy stream), the
 // next one starts when it has landed, and the kernels of the batches before it run meanwhile.
+//
+// A job is either uniform (n_frames of one size at one pitch: str_er_detect_bgr / _nv12) or a list of frames of assorted sizes at offsets of
+// the caller's choosing (str_er_detect_bgr_list / _nv12_list).  A list uploads the byte span from its lowest frame start to its highest frame
+// end, to the same offsets of the slot's device buffer, and is detected there (STR_ER_MEM_DEVICE refs); the turns are the same for both kinds.
 #include "../../include/str_er.h"
 
 #include <hip/hip_runtime.h>
@@ -44,6 +48,10 @@ struct str_er_stream {
         int64_t  stride = 0, pitch = 0;
         uint32_t stages = 0;
         bool     nv12 = false;
+        bool     list = false;                  // a list job: refs (data unused) at offs into the buffer; the upload is [span_lo, span_hi)
+        std::vector<str_er_image_ref> refs, dev_refs;
+        std::vector<size_t> offs;
+        size_t   span_lo = 0, span_hi = 0;
         uint64_t ticket = 0;
         int      rc = STR_ER_OK;
         str_er_result *result = nullptr;
@@ -53,6 +61,7 @@ struct str_er_stream {
     std::vector<Slot> slots;
     size_t   slot_bytes = 0;
     int      device = 0;
+    int32_t  max_width = 0, max_height = 0, max_frames = 0;       // the contexts' capacity (list submissions are checked against it)
     std::mutex mu;
     std::condition_variable cv;
     std::deque<int> order;       // slots in submission order, oldest first
@@ -84,7 +93,8 @@ void worker_main(str_er_stream *s, int idx)
         try {
             // the upload, when it is this batch's turn (submission order); the turn passes on when the bytes have landed
             const int64_t rows = sl.nv12 ? (int64_t)sl.h + sl.h / 2 : (int64_t)sl.h;
-            const size_t bytes = (size_t)(sl.n_frames - 1) * (size_t)sl.pitch + (size_t)sl.stride * (size_t)rows;
+            const size_t lo = sl.list ? sl.span_lo : 0;
+            const size_t bytes = sl.list ? sl.span_hi - sl.span_lo : (size_t)(sl.n_frames - 1) * (size_t)sl.pitch + (size_t)sl.stride * (size_t)rows;
             {
                 std::unique_lock<std::mutex> lk(s->mu);
                 s->cv.wait(lk, [&] { return s->upload_turn == sl.ticket; });
@@ -107,9 +117,9 @@ void worker_main(str_er_stream *s, int idx)
                     if (s->last_landed[k])
                         for (int j = 0; j < parts && e == hipSuccess; ++j) e = hipStreamWaitEvent(sl.copy[j], s->last_landed[k], 0);
                 for (int j = 0; j < parts; ++j) {
-                    const size_t lo = std::min(bytes, (size_t)j * part), hi = j + 1 == parts ? bytes : std::min(bytes, (size_t)(j + 1) * part);
-                    for (size_t at = lo; at < hi && e == hipSuccess; at += piece)
-                        e = hipMemcpyAsync(sl.d_in + at, sl.pinned + at, std::min(piece, hi - at), hipMemcpyHostToDevice, sl.copy[j]);
+                    const size_t a = lo + std::min(bytes, (size_t)j * part), b = lo + (j + 1 == parts ? bytes : std::min(bytes, (size_t)(j + 1) * part));
+                    for (size_t at = a; at < b && e == hipSuccess; at += piece)
+                        e = hipMemcpyAsync(sl.d_in + at, sl.pinned + at, std::min(piece, b - at), hipMemcpyHostToDevice, sl.copy[j]);
                     if (e == hipSuccess) e = hipEventRecord(sl.landed[j], sl.copy[j]);
                 }
                 for (int k = 0; k < str_er_stream::MAX_UPLOAD_STREAMS; ++k) s->last_landed[k] = e == hipSuccess && k < parts ? sl.landed[k] : nullptr;
@@ -123,7 +133,12 @@ void worker_main(str_er_stream *s, int idx)
                 if (++spins > 50) std::this_thread::sleep_for(std::chrono::microseconds(50));
             }
             if (e != hipSuccess) { rc = STR_ER_EHIP; upload_failed = true; sl.err = std::string("upload: ") + hipGetErrorString(e); }
-            if (rc == STR_ER_OK)
+            if (rc == STR_ER_OK && sl.list) {
+                sl.dev_refs = sl.refs;
+                for (size_t i = 0; i < sl.offs.size(); ++i) sl.dev_refs[i].data = sl.d_in + sl.offs[i];
+                rc = sl.nv12 ? str_er_detect_nv12_list(sl.ctx, sl.dev_refs.data(), (int32_t)sl.dev_refs.size(), STR_ER_MEM_DEVICE, sl.stages, &r)
+                             : str_er_detect_bgr_list(sl.ctx, sl.dev_refs.data(), (int32_t)sl.dev_refs.size(), STR_ER_MEM_DEVICE, sl.stages, &r);
+            } else if (rc == STR_ER_OK)
                 rc = sl.nv12 ? str_er_detect_nv12(sl.ctx, sl.d_in, sl.w, sl.h, sl.stride, sl.pitch, sl.n_frames, STR_ER_MEM_DEVICE, sl.stages, &r)
                              : str_er_detect_bgr(sl.ctx, sl.d_in, sl.w, sl.h, sl.stride, sl.pitch, sl.n_frames, STR_ER_MEM_DEVICE, sl.stages, &r);
         } catch (...) {
@@ -161,6 +176,7 @@ try {
     if (const char *e = std::getenv("STR_ER_UPLOAD_STREAMS")) s->upload_streams = std::max(1, std::min(std::atoi(e), (int)str_er_stream::MAX_UPLOAD_STREAMS));
     if (const char *e = std::getenv("STR_ER_UPLOAD_PIECE_MB")) { const long v = std::atol(e); if (v >= 1 && v <= 4096) s->upload_piece = (size_t)v << 20; }
     s->slot_bytes = (size_t)p->max_frames * (size_t)p->max_width * (size_t)p->max_height * 3;
+    s->max_width = p->max_width; s->max_height = p->max_height; s->max_frames = p->max_frames;
     s->slots.resize((size_t)depth);
     int rc = STR_ER_OK;
     for (int i = 0; i < depth && rc == STR_ER_OK; ++i) {
@@ -262,7 +278,7 @@ static int submit_impl(str_er_stream *s, int32_t slot, int32_t w, int32_t h, int
             s->err = "frames do not fit the staging buffer";
             return STR_ER_EINVAL;
         }
-        sl.w = w; sl.h = h; sl.stride = stride; sl.pitch = frame_pitch; sl.n_frames = n_frames; sl.stages = stages; sl.nv12 = nv12;
+        sl.w = w; sl.h = h; sl.stride = stride; sl.pitch = frame_pitch; sl.n_frames = n_frames; sl.stages = stages; sl.nv12 = nv12; sl.list = false;
         sl.ticket = s->next_ticket++;
         sl.has_job = true;
         s->order.push_back(slot);
@@ -303,6 +319,110 @@ try {
         for (int y = 0; y < h; ++y)
             std::memcpy(buf + (size_t)f * fb + (size_t)y * row, bgr + (size_t)f * (size_t)frame_pitch + (size_t)y * (size_t)stride, row);
     return str_er_stream_submit(s, slot, w, h, (int64_t)row, (int64_t)fb, n_frames, stages, ticket);
+} STREAM_GUARD(s)
+
+// A list job: every frame checked against the slot's buffer and the contexts' capacity before anything is recorded (an error leaves the slot
+// acquired, as submit_impl does).
+static int submit_list_impl(str_er_stream *s, int32_t slot, const str_er_image_ref *frames, int32_t n, uint32_t stages, uint64_t *ticket, bool nv12)
+{
+    if (!s || slot < 0 || (size_t)slot >= s->slots.size()) return STR_ER_EINVAL;
+    str_er_stream::Slot &sl = s->slots[(size_t)slot];
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        if (!sl.busy || sl.has_job || sl.done) { s->err = "slot was not acquired (or is already submitted)"; return STR_ER_ESTATE; }
+        if (!frames) { s->err = "null frame list"; return STR_ER_EINVAL; }
+        if (n < 1) { s->err = "empty frame list"; return STR_ER_EINVAL; }
+        if (n > s->max_frames) {
+            s->err = std::to_string(n) + " frames: more than the stream's " + std::to_string(s->max_frames) + " per submission";
+            return STR_ER_ECAPACITY;
+        }
+        const uintptr_t base = reinterpret_cast<uintptr_t>(sl.pinned);
+        size_t lo = s->slot_bytes, hi = 0;
+        for (int32_t i = 0; i < n; ++i) {
+            const str_er_image_ref &r = frames[i];
+            const std::string name = "frame " + std::to_string(i);
+            const int64_t row = nv12 ? (int64_t)r.w : (int64_t)r.w * 3, rows = nv12 ? (int64_t)r.h + r.h / 2 : (int64_t)r.h;
+            if (!r.data) { s->err = name + ": null data"; return STR_ER_EINVAL; }
+            if (r.w < 1 || r.h < 1) { s->err = name + ": empty"; return STR_ER_EINVAL; }
+            if (r.stride < row || r.stride > 0x7FFFFFFF) { s->err = name + ": stride smaller than a row or too large"; return STR_ER_EINVAL; }
+            if (nv12 && ((r.w | r.h) & 1)) { s->err = name + ": NV12 frames have even width and height"; return STR_ER_EINVAL; }
+            if (r.w > s->max_width || r.h > s->max_height) {
+                s->err = name + ": " + std::to_string(r.w) + " x " + std::to_string(r.h) + " larger than the stream's capacity " + std::to_string(s->max_width) +
+                         " x " + std::to_string(s->max_height);
+                return STR_ER_ECAPACITY;
+            }
+            const uintptr_t at = reinterpret_cast<uintptr_t>(r.data);
+            const uint64_t  end = (uint64_t)(rows - 1) * (uint64_t)r.stride + (uint64_t)row;        // bytes from the first pixel to the end of the last row
+            if (at < base || at - base > s->slot_bytes || end > s->slot_bytes - (at - base)) {
+                s->err = name + ": not wholly inside the slot's staging buffer";
+                return STR_ER_EINVAL;
+            }
+            lo = std::min(lo, (size_t)(at - base));
+            hi = std::max(hi, (size_t)(at - base + end));
+        }
+        sl.refs.assign(frames, frames + n);
+        sl.offs.resize((size_t)n);
+        for (int32_t i = 0; i < n; ++i) sl.offs[(size_t)i] = (size_t)(reinterpret_cast<uintptr_t>(frames[i].data) - base);
+        sl.span_lo = lo; sl.span_hi = hi;
+        sl.stages = stages; sl.nv12 = nv12; sl.list = true;
+        sl.ticket = s->next_ticket++;
+        sl.has_job = true;
+        s->order.push_back(slot);
+        if (ticket) *ticket = sl.ticket;
+    }
+    s->cv.notify_all();
+    return STR_ER_OK;
+}
+
+int str_er_stream_submit_list(str_er_stream *s, int32_t slot, const str_er_image_ref *frames, int32_t n, uint32_t stages, uint64_t *ticket)
+try {
+    return submit_list_impl(s, slot, frames, n, stages, ticket, false);
+} STREAM_GUARD(s)
+
+int str_er_stream_submit_nv12_list(str_er_stream *s, int32_t slot, const str_er_image_ref *frames, int32_t n, uint32_t stages, uint64_t *ticket)
+try {
+    return submit_list_impl(s, slot, frames, n, stages, ticket, true);
+} STREAM_GUARD(s)
+
+int str_er_stream_submit_copy_list(str_er_stream *s, const str_er_image_ref *frames, int32_t n, uint32_t stages, uint64_t *ticket)
+try {
+    if (!s || !frames || n < 1) return STR_ER_EINVAL;
+    for (int32_t i = 0; i < n; ++i)
+        if (!frames[i].data || frames[i].w < 1 || frames[i].h < 1 || frames[i].stride < (int64_t)frames[i].w * 3) {
+            s->err = "frame " + std::to_string(i) + ": null data, empty, or stride smaller than a row";
+            return STR_ER_EINVAL;
+        }
+    // frames back to back, each from a 4-byte boundary when the padded total fits (a full-size list has no room for padding)
+    size_t need = 0, tight = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const size_t fb = (size_t)frames[i].w * 3 * (size_t)frames[i].h;
+        need = ((need + 3) & ~(size_t)3) + fb;
+        tight += fb;
+    }
+    if (tight > s->slot_bytes) { s->err = "frames do not fit the staging buffer"; return STR_ER_ECAPACITY; }
+    const size_t al = need <= s->slot_bytes ? 4 : 1;
+    std::vector<str_er_image_ref> refs((size_t)n);
+    int32_t  slot = -1;
+    uint8_t *buf = nullptr;
+    int rc = str_er_stream_acquire(s, &slot, &buf, nullptr);
+    if (rc != STR_ER_OK) return rc;
+    size_t at = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const str_er_image_ref &r = frames[i];
+        const size_t row = (size_t)r.w * 3;
+        at = (at + al - 1) / al * al;
+        for (int y = 0; y < r.h; ++y) std::memcpy(buf + at + (size_t)y * row, r.data + (size_t)y * (size_t)r.stride, row);
+        refs[(size_t)i] = r;
+        refs[(size_t)i].data = buf + at;
+        refs[(size_t)i].stride = (int64_t)row;
+        at += row * (size_t)r.h;
+    }
+    rc = submit_list_impl(s, slot, refs.data(), n, stages, ticket, false);
+    if (rc != STR_ER_OK) {                      // (the caller never saw the slot)
+        std::lock_guard<std::mutex> lk(s->mu);
+        s->slots[(size_t)slot].busy = false;
+    }
+    return rc;
 } STREAM_GUARD(s)
 
 int str_er_stream_next(str_er_stream *s, str_er_result **out, uint64_t *ticket)

@@ -141,11 +141,40 @@ public:
         str_er_result *r = nullptr;
         check(str_er_detect_bgr_list(ctx_.get(), refs.data(), (int32_t)refs.size(), STR_ER_MEM_HOST, STR_ER_STAGE_ALL | STR_ER_WANT_NODES, &r));
         std::unique_ptr<str_er_result, void (*)(str_er_result *)> guard(r, str_er_result_free);
+        return unpack_batch(r, frames.size(), trees, root, pool, strong, weak);
+    }
+
+    // The same for NV12 frames of different sizes (str_er_detect_nv12_list: what a hardware decoder delivers): frames[f] is an 8UC1
+    // image of h + h/2 rows -- the luma plane, then the interleaved Cb/Cr rows -- of an even w x h frame.
+    std::vector<double> text_detect_nv12_batch(const std::vector<Image8> &frames, std::vector<std::vector<ERTree>> &trees, std::vector<ERs> &root,
+                                               std::vector<std::vector<ERs>> &pool, std::vector<std::vector<ERs>> &strong,
+                                               std::vector<std::vector<ERs>> &weak)
+    {
+        std::vector<str_er_image_ref> refs(frames.size());
+        for (size_t f = 0; f < frames.size(); ++f) {
+            if (frames[f].channels != 1 || frames[f].rows % 3) throw std::runtime_error("text_detect_nv12_batch expects 8UC1 NV12 images of h + h/2 rows");
+            refs[f].data = frames[f].data; refs[f].w = frames[f].cols; refs[f].h = frames[f].rows / 3 * 2; refs[f].stride = frames[f].step;
+        }
+        str_er_result *r = nullptr;
+        check(str_er_detect_nv12_list(ctx_.get(), refs.data(), (int32_t)refs.size(), STR_ER_MEM_HOST, STR_ER_STAGE_ALL | STR_ER_WANT_NODES, &r));
+        std::unique_ptr<str_er_result, void (*)(str_er_result *)> guard(r, str_er_result_free);
+        return unpack_batch(r, frames.size(), trees, root, pool, strong, weak);
+    }
+
+    // A list call's result (nf frames, STR_ER_WANT_NODES) as text_detect_batch hands it out -- also for the results of a str_er_stream
+    // list submission.  Returns the result's 7-slot times vector.
+    static std::vector<double> unpack_batch(const str_er_result *r, size_t nf, std::vector<std::vector<ERTree>> &trees, std::vector<ERs> &root,
+                                            std::vector<std::vector<ERs>> &pool, std::vector<std::vector<ERs>> &strong,
+                                            std::vector<std::vector<ERs>> &weak)
+    {
         const int n = str_er_result_n_planes(r);
-        const size_t nf = frames.size();
         std::vector<int> per(nf, 0), at(nf, 0);
         std::vector<str_er_plane_info> info((size_t)n);
-        for (int i = 0; i < n; ++i) { str_er_result_plane_info(r, i, &info[(size_t)i]); ++per[info[(size_t)i].frame]; }
+        for (int i = 0; i < n; ++i) {
+            str_er_result_plane_info(r, i, &info[(size_t)i]);
+            if (info[(size_t)i].frame >= nf) throw std::runtime_error("unpack_batch: a plane of a frame beyond nf");
+            ++per[info[(size_t)i].frame];
+        }
         trees.assign(nf, std::vector<ERTree>()); root.assign(nf, ERs());
         pool.assign(nf, std::vector<ERs>()); strong.assign(nf, std::vector<ERs>()); weak.assign(nf, std::vector<ERs>());
         for (size_t f = 0; f < nf; ++f) {       // (sized first: the ERs point into the trees' node vectors)
