@@ -66,6 +66,9 @@ extern "C" {
 #define STR_ER_GROUP_OVERLAP_SUP 512u /* ... with overlap_sup = true, as video_mode calls it (er_grouping(tracked, text, true, true), src/utils.cpp:196) */
 #define STR_ER_STAGE_OCR_LINES 256u /* er_ocr's per-line scoring (src/ER.cpp:695-747): chain_run with the line's slope on every member;
                                       needs STR_ER_STAGE_GROUP + an SVM model */
+/* output option: also return the pixel mask of every candidate (str_er_result_masks / str_er_result_mask_bits).  Every
+ * str_er_detect_* entry point and every str_er_stream_submit* call honours it; str_er_strip_merge[_ex] rejects it (STR_ER_EINVAL). */
+#define STR_ER_WANT_MASKS     1024u
 
 /* candidate class: which list of text_detect() the ER landed in (src/ER.cpp:516-526) */
 #define STR_ER_CLS_POOL   0   /* pooled by NMS, rejected by both cascades */
@@ -142,6 +145,19 @@ typedef struct str_er_cand {
     double   score_strong; /* stc->predict(fv): last stage score or -DBL_MAX           */
     double   score_weak;   /* wtc->predict(fv) if the strong cascade rejected, else 0  */
 } str_er_cand;           /* 48 bytes */
+
+/* The pixel mask of one region (STR_ER_WANT_MASKS, str_er_er_masks).  With L(p) = rint_half_even(P'(p) / thresh_step), P' the plane
+ * XOR its invert mask (the quantiser of the tile trees), the mask of a region c is the set of pixels reachable from pixel `key`
+ * (x = key % plane width, y = key / plane width) through 4-neighbours with L <= c.level, without leaving the box (c.x, c.y, c.w, c.h).
+ * For a candidate the box is the region's bounding box, so the mask is the whole node (t, C) of SURVEY A.3: its bounding box is
+ * the candidate's box and its popcount is |C| (the own pixels of the node and of all its descendants).
+ * Layout: h rows of pitch_words = (w + 31) / 32 32-bit words, from word word_off of str_er_result_mask_bits() on; pixel x of a row
+ * is bit (x & 31) of word (x >> 5); padding bits are 0.  pixels = popcount.                                                        */
+typedef struct str_er_mask {
+    uint64_t word_off;
+    uint32_t pixels;
+    uint32_t pitch_words;
+} str_er_mask;           /* 16 bytes */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -311,6 +327,15 @@ int str_er_classify_boxes(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int3
                           int64_t stride, const int32_t *boxes_xywh, int32_t n,
                           uint8_t *cls, double *score_strong, double *score_weak);
 
+/* The pixel masks (str_er_mask) of n regions of one host plane, at the context's current thresh_step; the plane is taken as it
+ * is (no invert mask).  Of every region only x, y, w, h, level and key are read.  The masks are written back to back in region order:
+ * region i's h rows of (w + 31) / 32 words, then region i + 1's; pixels (optional, may be NULL) receives the n popcounts.
+ * bits == NULL only reports *n_words.  cap_words too small -> STR_ER_ECAPACITY, *n_words still set.  STR_ER_EINVAL, with a message
+ * naming the region, if a box leaves the plane, key lies outside its box, L(key) > level, or level >= highest_level (255 / step + 1).
+ * Boxes of any size up to the whole plane (within the context's capacity).                                                   */
+int str_er_er_masks(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions,
+                    int32_t n, uint32_t *bits, uint64_t cap_words, uint64_t *n_words, uint32_t *pixels);
+
 /* ERFilter::make_LBP_hist(input, 2, 24) (src/ER.cpp:789-816) for n boxes of one host
  * plane: hist receives n*1024 doubles; tiles26 (optional, may be NULL) receives the
  * n ARAN(26) tiles (src/OCR.cpp:394-430), 676 bytes each.                            */
@@ -464,6 +489,10 @@ const int32_t *str_er_result_line_labels(const str_er_result *r, int32_t *n);
 const double  *str_er_result_line_probs(const str_er_result *r, int32_t *n);
 const uint8_t *str_er_result_line_kept(const str_er_result *r, int32_t *n);
 const uint8_t *str_er_result_text_alive(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_MASKS: one mask record per candidate of str_er_result_cands() (same order), and the words they index
+ * (n_words in total).  NULL unless the flag was given.                                                                    */
+const str_er_mask *str_er_result_masks(const str_er_result *r, int32_t *n);
+const uint32_t    *str_er_result_mask_bits(const str_er_result *r, uint64_t *n_words);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

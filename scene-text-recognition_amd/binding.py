@@ -19,6 +19,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 STAGE_EXTRACT, STAGE_NMS, STAGE_CLASSIFY, STAGE_ALL, STAGE_OCR, WANT_NODES, STAGE_TRACK = 1, 2, 4, 7, 8, 16, 32
 STAGE_GROUP, GROUP_INNER_SUP, STAGE_OCR_LINES, GROUP_OVERLAP_SUP = 64, 128, 256, 512
+WANT_MASKS = 1024       # output option: the pixel mask of every candidate (Result.mask)
+# str_er_mask: mask i = pitch_words 32-bit words per row, h rows, from word word_off of the call's mask words; pixels = popcount
+MASK_DTYPE = np.dtype([("word_off", "<u8"), ("pixels", "<u4"), ("pitch_words", "<u4")])
 TEXT_DTYPE = np.dtype([("frame", "<u4"), ("pyr", "u1"), ("r0", "u1"), ("r1", "u1"), ("r2", "u1"), ("first", "<i4"), ("count", "<i4"),
                        ("slope", "<f8"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4")])
 GBOUND_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("cx", "<i4"), ("cy", "<i4")])
@@ -35,7 +38,14 @@ CAND_DTYPE = np.dtype([("frame", "<u4"), ("ch", "u1"), ("pyr", "u1"), ("level", 
 PLANE_DTYPE = np.dtype([("frame", "<u4"), ("ch", "u1"), ("pyr", "u1"), ("r0", "u1"), ("r1", "u1"), ("width", "<i4"),
                         ("height", "<i4"), ("n_created", "<i4"), ("n_kept", "<i4"), ("n_pool", "<i4"), ("n_strong", "<i4"),
                         ("n_weak", "<i4"), ("ambiguous", "<i4"), ("root", "<i4")])
-assert NODE_DTYPE.itemsize == 24 and CAND_DTYPE.itemsize == 48 and PLANE_DTYPE.itemsize == 44
+assert NODE_DTYPE.itemsize == 24 and CAND_DTYPE.itemsize == 48 and PLANE_DTYPE.itemsize == 44 and MASK_DTYPE.itemsize == 16
+
+
+def unpack_mask(words: np.ndarray, word_off: int, w: int, h: int) -> np.ndarray:
+    """One mask of a str_er_mask word array as a bool array (h, w): pixel x of a row is bit x & 31 of word x >> 5."""
+    pitch = (w + 31) // 32
+    rows = np.ascontiguousarray(words[word_off:word_off + pitch * h], dtype="<u4").reshape(h, pitch)
+    return np.unpackbits(rows.view(np.uint8), axis=1, bitorder="little")[:, :w].astype(bool)
 
 
 class ImageRef(C.Structure):
@@ -194,6 +204,11 @@ def load_library():
     L.str_er_result_plane_nodes.restype = vp
     L.str_er_result_tracks.argtypes = [vp, i32p]
     L.str_er_result_tracks.restype = vp
+    L.str_er_result_masks.argtypes = [vp, i32p]
+    L.str_er_result_masks.restype = vp
+    L.str_er_result_mask_bits.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_result_mask_bits.restype = vp
+    L.str_er_er_masks.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
     L.str_er_set_min_ocr_prob.argtypes = [vp, C.c_double]
     for fn in (L.str_er_result_texts, L.str_er_result_text_ers, L.str_er_result_group_bounds, L.str_er_result_group_all,
                L.str_er_result_line_labels, L.str_er_result_line_probs, L.str_er_result_line_kept, L.str_er_result_text_alive):
@@ -303,7 +318,21 @@ class Result:
         self.line_prob = None      # whether the member survives er_ocr's two deletions, and per line whether >= 2 members do
         self.line_kept = None
         self.text_alive = None
+        self.masks = None          # with WANT_MASKS: MASK_DTYPE per candidate, and the words they index (uint32)
+        self.mask_bits = None
         self._planes = None
+
+    @property
+    def mask_pixels(self) -> Optional[np.ndarray]:
+        """With WANT_MASKS: the pixel count of every candidate's mask."""
+        return None if self.masks is None else self.masks["pixels"]
+
+    def mask(self, i: int) -> np.ndarray:
+        """With WANT_MASKS: the mask of candidate i as a bool array (h, w) over its box."""
+        if self.masks is None:
+            raise ValueError("the result has no masks (pass WANT_MASKS / want_masks=True)")
+        c = self.cands[i]
+        return unpack_mask(self.mask_bits, int(self.masks[i]["word_off"]), int(c["w"]), int(c["h"]))
 
     @property
     def planes(self) -> List[PlaneResult]:
@@ -433,6 +462,14 @@ class ERFilter:
                 bp = L.str_er_result_group_bounds(rh, C.byref(no))
                 res.group_bounds = (np.frombuffer((C.c_char * (24 * no.value)).from_address(bp), dtype=GBOUND_DTYPE).copy()
                                     if no.value else np.zeros(0, GBOUND_DTYPE))
+            mp = L.str_er_result_masks(rh, C.byref(no))
+            if mp:
+                res.masks = (np.frombuffer((C.c_char * (16 * no.value)).from_address(mp), dtype=MASK_DTYPE).copy()
+                             if no.value else np.zeros(0, MASK_DTYPE))
+                nw = C.c_uint64()
+                wp = L.str_er_result_mask_bits(rh, C.byref(nw))
+                res.mask_bits = (np.frombuffer((C.c_char * (4 * nw.value)).from_address(wp), dtype=np.uint32).copy()
+                                 if nw.value else np.zeros(0, np.uint32))
             lp2 = L.str_er_result_line_labels(rh, C.byref(no))
             if lp2:
                 k = no.value
@@ -479,7 +516,7 @@ class ERFilter:
         return {names[i].decode(): ms[i] for i in range(min(k, 32))}
 
     # ---- the hot path ---------------------------------------------------------------------------
-    def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
+    def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -490,7 +527,7 @@ class ERFilter:
         f, h, w, _ = a.shape
         rh = C.c_void_p()
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
-                                             stages | (WANT_NODES if want_nodes else 0), C.byref(rh)))
+                                             stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -608,12 +645,13 @@ class ERFilter:
         self._check(fn(self.h, arr, len(refs), mem_kind, stages, C.byref(rh)))
         return self._collect(rh)
 
-    def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
+    def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
-        return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST, stages | (WANT_NODES if want_nodes else 0))
+        return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
+                                 stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -691,6 +729,23 @@ class ERFilter:
         self._check(self.L.str_er_classify_boxes(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(b), n,
                                                  _np_ptr(cls), _np_ptr(ss), _np_ptr(sw)))
         return cls, ss, sw
+
+    def er_masks(self, plane: np.ndarray, regions: np.ndarray):
+        """str_er_er_masks: the pixel masks of `regions` (CAND_DTYPE records; x, y, w, h, level and key are read) on one (H, W) uint8
+        plane at the context's thresh_step.  Returns (words, pixels): the masks back to back in region order (region i: h rows of
+        (w + 31) // 32 uint32 words) and their popcounts.  unpack_mask(words, off, w, h) gives one as a bool array."""
+        a = np.ascontiguousarray(plane, dtype=np.uint8)
+        r = np.ascontiguousarray(regions, dtype=CAND_DTYPE).reshape(-1)
+        n = len(r)
+        nw = C.c_uint64()
+        self._check(self.L.str_er_er_masks(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(r) if n else None, n,
+                                           None, 0, C.byref(nw), None))
+        words = np.zeros(max(1, nw.value), np.uint32)
+        pixels = np.zeros(max(1, n), np.uint32)
+        if n:
+            self._check(self.L.str_er_er_masks(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(r), n,
+                                               _np_ptr(words), nw.value, C.byref(nw), _np_ptr(pixels)))
+        return words[:nw.value], pixels[:n]
 
     def predict(self, which: int, fv: np.ndarray) -> np.ndarray:
         """stc->predict(fv) / wtc->predict(fv) (inc/adaboost.h:131) for (n,1024) feature vectors."""

@@ -309,3 +309,92 @@ try {
 } ABI_GUARD(c)
 
 } // extern "C"
+
+namespace str_er_host {
+
+int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, uint32_t *pixels, uint32_t *bits)
+{
+    const size_t n = jobs.size();
+    if (n == 0) return STR_ER_OK;
+    // one launch per size class (mask_class): the jobs ordered by class, the global-scratch rows of the largest boxes laid out behind one another
+    int n_class[3] = {0, 0, 0};
+    for (const MaskJob &j : jobs) ++n_class[mask_class(j.w, j.h)];
+    std::stable_sort(jobs.begin(), jobs.end(), [](const MaskJob &a, const MaskJob &b) { return mask_class(a.w, a.h) < mask_class(b.w, b.h); });
+    size_t scratch = 0;
+    for (MaskJob &j : jobs) { j.scratch_off = scratch; scratch += mask_scratch_words(j.w, j.h); }
+    const size_t o_pix = align_up(sizeof(MaskJob) * n, 256), o_bits = align_up(o_pix + 4 * n, 256), need = o_bits + 4 * (size_t)n_words;
+    if (need > c->mask_bytes) {
+        const size_t get = std::max(need, 2 * c->mask_bytes);
+        if (c->d_mask) { (void)hipFree(c->d_mask); c->d_mask = nullptr; }
+        if (c->h_mask) { (void)hipHostFree(c->h_mask); c->h_mask = nullptr; }
+        c->mask_bytes = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&c->d_mask), get) != hipSuccess) return fail(c, STR_ER_ENOMEM, "hipMalloc (masks, " + std::to_string(get) + " bytes)");
+        if (hipHostMalloc(reinterpret_cast<void **>(&c->h_mask), get) != hipSuccess) {
+            (void)hipFree(c->d_mask); c->d_mask = nullptr;
+            return fail(c, STR_ER_ENOMEM, "hipHostMalloc (masks, " + std::to_string(get) + " bytes)");
+        }
+        c->mask_bytes = get;
+    }
+    if (scratch > c->mask_scratch_words) {
+        const size_t get = std::max(scratch, 2 * c->mask_scratch_words);
+        if (c->d_mask_scratch) { (void)hipFree(c->d_mask_scratch); c->d_mask_scratch = nullptr; }
+        c->mask_scratch_words = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&c->d_mask_scratch), 8 * get) != hipSuccess)
+            return fail(c, STR_ER_ENOMEM, "hipMalloc (mask scratch, " + std::to_string(8 * get) + " bytes)");
+        c->mask_scratch_words = get;
+    }
+    std::memcpy(c->h_mask, jobs.data(), sizeof(MaskJob) * n);
+    HIP_TRY(c, hipMemcpyAsync(c->d_mask, c->h_mask, sizeof(MaskJob) * n, hipMemcpyHostToDevice, s));
+    launch_er_masks(s, reinterpret_cast<const MaskJob *>(c->d_mask), n_class, reinterpret_cast<uint32_t *>(c->d_mask + o_bits),
+                    reinterpret_cast<uint32_t *>(c->d_mask + o_pix), c->d_mask_scratch, qscale);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->h_mask + o_pix, c->d_mask + o_pix, need - o_pix, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, wait_stream(c, s));
+    std::memcpy(pixels, c->h_mask + o_pix, 4 * n);
+    if (n_words) std::memcpy(bits, c->h_mask + o_bits, 4 * (size_t)n_words);
+    return STR_ER_OK;
+}
+
+} // namespace str_er_host
+
+extern "C" {
+
+int str_er_er_masks(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions, int32_t n,
+                    uint32_t *bits, uint64_t cap_words, uint64_t *n_words, uint32_t *pixels)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (!plane || w < 1 || h < 1 || stride < w || n < 0 || (n > 0 && !regions) || !n_words) return fail(c, STR_ER_EINVAL, "bad arguments");
+    const DetectParams dp = make_dp(c);
+    std::vector<MaskJob> jobs((size_t)n);
+    uint64_t words = 0;
+    for (int i = 0; i < n; ++i) {
+        const str_er_cand &g = regions[i];
+        const std::string  who = "region " + std::to_string(i) + ": ";
+        if (g.w < 1 || g.h < 1 || (int64_t)g.x + g.w > w || (int64_t)g.y + g.h > h) return fail(c, STR_ER_EINVAL, who + "box outside the plane");
+        if (g.w > MASK_MAX_WIDTH) return fail(c, STR_ER_ECAPACITY, who + "box wider than " + std::to_string(MASK_MAX_WIDTH) + " pixels");
+        const uint32_t kx = g.key % (uint32_t)w, ky = g.key / (uint32_t)w;
+        if (ky >= (uint32_t)h || kx < g.x || kx >= (uint32_t)g.x + g.w || ky < g.y || ky >= (uint32_t)g.y + g.h)
+            return fail(c, STR_ER_EINVAL, who + "key outside the box");
+        if ((int)g.level >= dp.hi) return fail(c, STR_ER_EINVAL, who + "level " + std::to_string(g.level) + " >= highest_level " + std::to_string(dp.hi));
+        const long lk = lrintf((float)plane[(size_t)ky * (size_t)stride + kx] * dp.qscale);
+        if (lk > (long)g.level) return fail(c, STR_ER_EINVAL, who + "the key pixel's level " + std::to_string(lk) + " exceeds the region's level " + std::to_string(g.level));
+        MaskJob &j = jobs[(size_t)i];
+        j.stride = w; j.invert = 0; j.plane_w = (uint32_t)w; j.key = g.key;
+        j.x = g.x; j.y = g.y; j.w = g.w; j.h = g.h; j.level = g.level; j.idx = (uint32_t)i; j.out_off = words; j.scratch_off = 0;
+        words += (uint64_t)g.h * ((g.w + 31u) / 32u);
+    }
+    *n_words = words;
+    if (!bits || n == 0) return STR_ER_OK;
+    if (words > cap_words) return fail(c, STR_ER_ECAPACITY, "the masks need " + std::to_string(words) + " words, cap_words is " + std::to_string(cap_words));
+    HIP_TRY(c, hipSetDevice(c->prm.device));
+    if ((size_t)w * (size_t)h > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane larger than the context capacity");
+    HIP_TRY(c, hipMemcpy2DAsync(c->d_pix, (size_t)w, plane, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, c->stream));
+    for (MaskJob &j : jobs) j.pix = c->d_pix;
+    std::vector<uint32_t> px((size_t)n);
+    const int rc = mask_stage(c, c->stream, jobs, words, dp.qscale, px.data(), bits);
+    if (rc != STR_ER_OK) return rc;
+    if (pixels) std::memcpy(pixels, px.data(), 4 * (size_t)n);
+    return STR_ER_OK;
+} ABI_GUARD(c)
+
+} // extern "C"

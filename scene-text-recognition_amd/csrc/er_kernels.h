@@ -129,4 +129,11 @@ void launch_lbp_boxes(hipStream_t s, const uint8_t *plane, int w, int h, int str
 // CascadeBoost::predict on explicit feature vectors (n x 1024 doubles).
 void launch_cascade_fv(hipStream_t s, const double *fv, int n, double *out, CascadeDev c);
 
+// Pixel masks of regions (er_masks.inl).  The jobs come ordered by size class (mask_class: 0 registers, 1 LDS, 2 global scratch),
+// n_class[k] of class k; out receives the bit rows at MaskJob::out_off, pixels[MaskJob::idx] the popcounts.  scratch: the
+// mask_scratch_words of every class-2 job, at its MaskJob::scratch_off (may be null without class-2 jobs).
+int    mask_class(int w, int h);
+size_t mask_scratch_words(int w, int h);
+void   launch_er_masks(hipStream_t s, const MaskJob *jobs, const int n_class[3], uint32_t *out, uint32_t *pixels, uint64_t *scratch, float qscale);
+
 } // namespace str_er

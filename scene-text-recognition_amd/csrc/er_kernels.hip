@@ -42,5 +42,6 @@ namespace str_er {
 #include "er_tree_passes.inl"   // k_group_merge, k_seam, strips, k_resolve, k_reduce, k_root / k_select / k_kept
 #include "er_nms.inl"           // k_nms and everything around NMS ties
 #include "er_classify.inl"      // k_classify, k_lbp_boxes, k_cascade_fv
+#include "er_masks.inl"         // k_er_masks_small / _big: the pixel masks of regions
 
 } // namespace str_er

@@ -187,4 +187,20 @@ struct CandRec {
 };
 static_assert(sizeof(CandRec) == 48, "CandRec must match str_er_cand");
 
+// One box of the mask stage (STR_ER_WANT_MASKS, str_er_er_masks): the pixels reachable from `key` through 4-neighbours of level
+// <= `level` inside the box, as bit rows of the output (er_masks.inl).
+struct MaskJob {
+    const uint8_t *pix;     // device pointer, top-left pixel of the plane
+    uint64_t out_off;       // first 32-bit word of the mask in the output
+    uint64_t scratch_off;   // boxes too large for LDS: first 64-bit word of their allowed / reached rows in the global scratch
+    int32_t  stride;
+    uint32_t invert;        // 0 or 0xFF (xor mask)
+    uint32_t plane_w;       // key = y * plane_w + x
+    uint32_t key;
+    uint16_t x, y, w, h;    // the box, in plane coordinates
+    uint32_t level;
+    uint32_t idx;           // index of the box in the call: pixels[idx] receives the mask's popcount
+};
+static_assert(sizeof(MaskJob) == 56, "MaskJob layout (host and device)");
+
 } // namespace str_er

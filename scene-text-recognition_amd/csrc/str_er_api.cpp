@@ -1264,6 +1264,28 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
         off += pc.n_pool;
     }
     r->cand_off[np] = off;
+    if (stages & STR_ER_WANT_MASKS) {
+        // the masks of the final candidates (after any NMS tie pass): sized on the host from the records just copied, one launch per size class, one wait
+        std::vector<MaskJob> jobs(total);
+        std::vector<uint32_t> px(total);
+        uint64_t words = 0;
+        r->masks.resize(total);
+        for (uint32_t k = 0; k < total; ++k) {
+            const str_er_cand &cd = r->cands[k];
+            const PlaneDesc   &pd = b.planes[cd.plane];
+            if (cd.w > MASK_MAX_WIDTH) { delete r; return fail(c, STR_ER_ECAPACITY, "STR_ER_WANT_MASKS: a candidate wider than " + std::to_string(MASK_MAX_WIDTH) + " pixels"); }
+            MaskJob &j = jobs[k];
+            j.pix = pd.pix; j.stride = pd.stride; j.invert = (uint32_t)pd.invert; j.plane_w = (uint32_t)pd.w; j.key = cd.key;
+            j.x = cd.x; j.y = cd.y; j.w = cd.w; j.h = cd.h; j.level = cd.level; j.idx = k; j.out_off = words; j.scratch_off = 0;
+            r->masks[k].word_off = words; r->masks[k].pitch_words = (cd.w + 31u) / 32u;
+            words += (uint64_t)cd.h * r->masks[k].pitch_words;
+        }
+        r->mask_bits.resize(words);
+        const int rcm = mask_stage(c, s, jobs, words, dp.qscale, px.data(), r->mask_bits.data());
+        if (rcm != STR_ER_OK) { delete r; return rcm; }
+        for (uint32_t k = 0; k < total; ++k) r->masks[k].pixels = px[k];
+        r->have_masks = true;
+    }
     if (want_nodes) {
         // candidates carry the device kept slot; translate to the sorted table through (key, level)
         for (int i = 0; i < np; ++i) {
@@ -1403,6 +1425,9 @@ void str_er_destroy(str_er_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void *p : c->allocs) (void)hipFree(p);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
+    if (c->d_mask) (void)hipFree(c->d_mask);
+    if (c->h_mask) (void)hipHostFree(c->h_mask);
+    if (c->d_mask_scratch) (void)hipFree(c->d_mask_scratch);
     if (c->d_strip_out) (void)hipFree(c->d_strip_out);
     if (c->d_strip_in) (void)hipFree(c->d_strip_in);
     if (c->d_replay) (void)hipFree(c->d_replay);
@@ -1949,6 +1974,22 @@ const str_er_cand *str_er_result_plane_cands(const str_er_result *r, int32_t pla
     if (!r || plane < 0 || plane >= (int32_t)r->planes.size()) { if (n) *n = 0; return nullptr; }
     if (n) *n = (int32_t)(r->cand_off[plane + 1] - r->cand_off[plane]);
     return r->cands.data() + r->cand_off[plane];
+}
+
+const str_er_mask *str_er_result_masks(const str_er_result *r, int32_t *n)
+{
+    if (!r || !r->have_masks) { if (n) *n = 0; return nullptr; }
+    if (n) *n = (int32_t)r->masks.size();
+    static const str_er_mask none{};
+    return r->masks.empty() ? &none : r->masks.data();
+}
+
+const uint32_t *str_er_result_mask_bits(const str_er_result *r, uint64_t *n_words)
+{
+    if (!r || !r->have_masks) { if (n_words) *n_words = 0; return nullptr; }
+    if (n_words) *n_words = r->mask_bits.size();
+    static const uint32_t none = 0;
+    return r->mask_bits.empty() ? &none : r->mask_bits.data();
 }
 
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n)

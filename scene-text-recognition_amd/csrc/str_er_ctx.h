@@ -73,6 +73,9 @@ struct str_er_result {
     std::vector<uint8_t> line_kept, text_alive;
     bool have_line_ocr = false;
     bool have_texts = false;
+    std::vector<str_er_mask> masks;          // STR_ER_WANT_MASKS: per candidate
+    std::vector<uint32_t> mask_bits;
+    bool have_masks = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -154,6 +157,9 @@ struct str_er_ctx {
     bool replay_on_gpu = false;                       // STR_ER_REPLAY=gpu: walk the flood with k_flood_order instead of a host core
     uint16_t *d_cand_plane = nullptr, *d_cand_plane2 = nullptr;
     void *d_scratch = nullptr; size_t scratch_bytes = 0;
+    // STR_ER_WANT_MASKS / str_er_er_masks: created by the first call that wants masks, grown geometrically, never shrunk
+    uint8_t  *d_mask = nullptr, *h_mask = nullptr; size_t mask_bytes = 0;       // jobs | popcounts | words, on the device and page-locked
+    uint64_t *d_mask_scratch = nullptr; size_t mask_scratch_words = 0;         // rows of the boxes too large for LDS
     uint8_t *d_strip_out = nullptr, *d_strip_in = nullptr; size_t strip_out_cap = 0, strip_in_cap = 0;   // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -361,6 +367,10 @@ int upload_layout(str_er_ctx *c, Batch &b);
 int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result **out, std::chrono::steady_clock::time_point t_start, bool pre_recorded,
               const ImportHook *import_trees = nullptr, int attempt = 0);
 int stage_input(str_er_ctx *c, const uint8_t *src, size_t bytes, int mem_kind, const uint8_t **dev);
+// ---- defined in api_stages.cpp
+// the pixel masks of `jobs` (out_off / idx set by the caller, n_words words in all): launched on s, waited for, copied to pixels[idx] and bits
+int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, uint32_t *pixels, uint32_t *bits);
+constexpr int MASK_MAX_WIDTH = 16384;       // widest box the mask kernels take (er_masks.inl: MASK_MAX_WPL words of 64 pixels per lane)
 // ---- defined in api_models.cpp
 int parse_cascade(str_er_ctx *c, HostCascade &hc, const char *text, size_t len);
 } // namespace str_er_host

@@ -262,6 +262,44 @@ public:
         for (int i = 0; i < 6; ++i) channels[i].assign(six.begin() + i * n, six.begin() + (i + 1) * n);
     }
 
+    // The pixels of ERs of one 8UC1 plane (str_er_er_masks): what the reference's flood visits for each ER and forgets.  Mask i is
+    // ers[i]'s bound and, row by row over it, 1 for a pixel of the region (reachable from ER::key through 4-neighbours of level
+    // <= ER::level inside the bound), 0 otherwise.  ER::key must be the canonical key of a region of this plane (as unpack_plane sets it).
+    struct Mask {
+        Rect bound;
+        std::vector<uint8_t> pixels;     // bound.height rows of bound.width bytes
+        int count = 0;                   // pixels set
+    };
+    std::vector<Mask> er_masks(const Image8 &plane, const ERs &ers)
+    {
+        if (plane.channels != 1) throw std::runtime_error("er_masks expects an 8UC1 plane");
+        std::vector<str_er_cand> regions(ers.size());
+        for (size_t i = 0; i < ers.size(); ++i) {
+            str_er_cand &c = regions[i];
+            c = str_er_cand{};
+            c.x = (uint16_t)ers[i]->bound.x; c.y = (uint16_t)ers[i]->bound.y; c.w = (uint16_t)ers[i]->bound.width; c.h = (uint16_t)ers[i]->bound.height;
+            c.level = (uint8_t)ers[i]->level; c.key = ers[i]->key;
+        }
+        const int32_t n = (int32_t)regions.size();
+        uint64_t      n_words = 0;
+        check(str_er_er_masks(ctx_.get(), plane.data, plane.cols, plane.rows, plane.step, regions.data(), n, nullptr, 0, &n_words, nullptr));
+        std::vector<uint32_t> bits(n_words ? n_words : 1);
+        std::vector<uint32_t> count(n ? n : 1);
+        if (n) check(str_er_er_masks(ctx_.get(), plane.data, plane.cols, plane.rows, plane.step, regions.data(), n, bits.data(), n_words, &n_words, count.data()));
+        std::vector<Mask> out(ers.size());
+        uint64_t off = 0;
+        for (size_t i = 0; i < ers.size(); ++i) {
+            const int w = regions[i].w, h = regions[i].h, pitch = (w + 31) / 32;
+            Mask &m = out[i];
+            m.bound = ers[i]->bound; m.count = (int)count[i];
+            m.pixels.resize((size_t)w * h);
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) m.pixels[(size_t)y * w + x] = (uint8_t)((bits[off + (size_t)y * pitch + (x >> 5)] >> (x & 31)) & 1u);
+            off += (uint64_t)pitch * h;
+        }
+        return out;
+    }
+
     // vector<double> ERFilter::make_LBP_hist(Mat input, N = 2, normalize_size = 24) (src/ER.cpp:789-816)
     std::vector<double> make_LBP_hist(const Image8 &input)
     {
