@@ -69,6 +69,12 @@ extern "C" {
 /* output option: also return the pixel mask of every candidate (str_er_result_masks / str_er_result_mask_bits).  Every
  * str_er_detect_* entry point and every str_er_stream_submit* call honours it; str_er_strip_merge[_ex] rejects it (STR_ER_EINVAL). */
 #define STR_ER_WANT_MASKS     1024u
+/* output options: a recogniser-ready image of every text line of str_er_result_texts() (str_er_result_line_crops): a grey crop
+ * (_CROPS) and, with _GLYPHS as well, a glyph crop made from the member masks.  Both need STR_ER_STAGE_GROUP, _GLYPHS needs _CROPS
+ * (STR_ER_EINVAL otherwise); str_er_strip_merge[_ex] rejects both.  Every str_er_detect_* entry point and str_er_stream_submit* call
+ * that can group honours them; the geometry and the sampling rules are at str_er_line_crop.                                       */
+#define STR_ER_WANT_LINE_CROPS  2048u
+#define STR_ER_WANT_LINE_GLYPHS 4096u
 
 /* candidate class: which list of text_detect() the ER landed in (src/ER.cpp:516-526) */
 #define STR_ER_CLS_POOL   0   /* pooled by NMS, rejected by both cascades */
@@ -158,6 +164,27 @@ typedef struct str_er_mask {
     uint32_t pixels;
     uint32_t pitch_words;
 } str_er_mask;           /* 16 bytes */
+
+/* The crop of one text line (STR_ER_WANT_LINE_CROPS, str_er_line_crops, str_er_line_crop_geometry).
+ * Geometry, all f64 on the host in this order: s = the line's slope (non-finite counts as 0); r = sqrt(1 + s*s); d = (1, s) / r,
+ * n = (-s, 1) / r.  The four corners of every box of the line (the members' str_er_result_group_bounds) project to u = c.d, v = c.n,
+ * giving u0, u1, v0, v1.  p = pad * (v1 - v0); U0 = u0 - p, U1 = u1 + p, V0 = v0 - p, V1 = v1 + p; kv = (V1 - V0) / height;
+ * width = min(max_width, max(1, ceil((U1 - U0) / kv))); ku = (U1 - U0) / width; a = U0*d + V0*n + 0.5*ku*d + 0.5*kv*n - (0.5, 0.5);
+ * u = ku*d, v = kv*n.  ax .. vy = llround(65536 * value): 16.16 fixed point.
+ * Grey pixel (i, j), int64: sx = ax + i*ux + j*vx, sy = ay + i*uy + j*vy; x0 = sx >> 16, fx = (sx >> 8) & 255 (y0, fy the same from
+ * sy); the taps (x0 | x0+1, y0 | y0+1) clamped into the plane; top = P[ya][xa]*(256-fx) + P[ya][xb]*fx, bot the same on the lower row;
+ * out = (top*(256-fy) + bot*fy + 32768) >> 16.  The plane is the Y plane of frame text.frame at pyramid level text.pyr (for NV12
+ * input the luma plane, resized for pyr >= 1).
+ * Glyph pixel (i, j): xn = (sx + 32768) >> 16, yn likewise; 255 if (xn, yn) lies in the plane and in the mask (STR_ER_WANT_MASKS,
+ * over the candidate's own box) of at least one member of the line, else 0.
+ * Layout: width x height bytes, row-major, pitch = width; crops back to back in line order, each from a multiple of 4 bytes on
+ * (pix_off; the 0..3 bytes between two crops are 0).  The glyph crop of a line sits at the same pix_off of the glyph bytes.       */
+typedef struct str_er_line_crop {
+    uint64_t pix_off;
+    int32_t  width, height;
+    int32_t  ax, ay;
+    int32_t  ux, uy, vx, vy;
+} str_er_line_crop;      /* 40 bytes */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -336,6 +363,21 @@ int str_er_classify_boxes(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int3
 int str_er_er_masks(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions,
                     int32_t n, uint32_t *bits, uint64_t cap_words, uint64_t *n_words, uint32_t *pixels);
 
+/* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
+ * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
+ * str_er_stream_context.                                                                                                          */
+int str_er_set_line_crop(str_er_ctx *ctx, int32_t height, int32_t max_width, double pad);
+/* The geometry of one line (str_er_line_crop; pix_off = 0) from its n_boxes boxes (x, y, w, h; w, h >= 1) and slope.  Pure host, no
+ * context.  STR_ER_EINVAL on bad arguments (out of the ranges of str_er_set_line_crop) or a geometry outside 16.16 fixed point. */
+int str_er_line_crop_geometry(const int32_t *boxes_xywh, int32_t n_boxes, double slope, int32_t height, int32_t max_width, double pad,
+                              str_er_line_crop *out);
+/* Grey crops of n_lines lines of one host plane at the context's crop settings: line k has the boxes
+ * boxes_xywh[first[k] .. first[k] + count[k]) (count >= 1) and slope slopes[k].  recs receives the n_lines records, pixels the crops
+ * (laid out as in a result).  pixels == NULL only fills recs and *n_bytes; cap too small -> STR_ER_ECAPACITY, *n_bytes still set. */
+int str_er_line_crops(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const int32_t *boxes_xywh,
+                      const int32_t *first, const int32_t *count, const double *slopes, int32_t n_lines, uint8_t *pixels, uint64_t cap,
+                      uint64_t *n_bytes, str_er_line_crop *recs);
+
 /* ERFilter::make_LBP_hist(input, 2, 24) (src/ER.cpp:789-816) for n boxes of one host
  * plane: hist receives n*1024 doubles; tiles26 (optional, may be NULL) receives the
  * n ARAN(26) tiles (src/OCR.cpp:394-430), 676 bytes each.                            */
@@ -493,6 +535,11 @@ const uint8_t *str_er_result_text_alive(const str_er_result *r, int32_t *n);
  * (n_words in total).  NULL unless the flag was given.                                                                    */
 const str_er_mask *str_er_result_masks(const str_er_result *r, int32_t *n);
 const uint32_t    *str_er_result_mask_bits(const str_er_result *r, uint64_t *n_words);
+/* With STR_ER_WANT_LINE_CROPS: one record per line of str_er_result_texts() (same order), the grey crop bytes they index and, with
+ * STR_ER_WANT_LINE_GLYPHS, the glyph crop bytes (same offsets, same size).  NULL without the flag(s).                              */
+const str_er_line_crop *str_er_result_line_crops(const str_er_result *r, int32_t *n);
+const uint8_t          *str_er_result_line_crop_pixels(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t          *str_er_result_line_glyph_pixels(const str_er_result *r, uint64_t *n_bytes);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

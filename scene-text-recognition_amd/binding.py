@@ -22,6 +22,12 @@ STAGE_GROUP, GROUP_INNER_SUP, STAGE_OCR_LINES, GROUP_OVERLAP_SUP = 64, 128, 256,
 WANT_MASKS = 1024       # output option: the pixel mask of every candidate (Result.mask)
 # str_er_mask: mask i = pitch_words 32-bit words per row, h rows, from word word_off of the call's mask words; pixels = popcount
 MASK_DTYPE = np.dtype([("word_off", "<u8"), ("pixels", "<u4"), ("pitch_words", "<u4")])
+# output options (need STAGE_GROUP): a rectified grey crop of every text line, and with WANT_LINE_GLYPHS too its glyph crop (Result.line_crop)
+WANT_LINE_CROPS, WANT_LINE_GLYPHS = 2048, 4096
+# str_er_line_crop: crop t = width x height bytes (pitch width) from byte pix_off of the crop bytes (and of the glyph bytes);
+# ax .. vy: the 16.16 sampling geometry (include/str_er.h)
+LINE_CROP_DTYPE = np.dtype([("pix_off", "<u8"), ("width", "<i4"), ("height", "<i4"), ("ax", "<i4"), ("ay", "<i4"),
+                            ("ux", "<i4"), ("uy", "<i4"), ("vx", "<i4"), ("vy", "<i4")])
 TEXT_DTYPE = np.dtype([("frame", "<u4"), ("pyr", "u1"), ("r0", "u1"), ("r1", "u1"), ("r2", "u1"), ("first", "<i4"), ("count", "<i4"),
                        ("slope", "<f8"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4")])
 GBOUND_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("cx", "<i4"), ("cy", "<i4")])
@@ -39,6 +45,7 @@ PLANE_DTYPE = np.dtype([("frame", "<u4"), ("ch", "u1"), ("pyr", "u1"), ("r0", "u
                         ("height", "<i4"), ("n_created", "<i4"), ("n_kept", "<i4"), ("n_pool", "<i4"), ("n_strong", "<i4"),
                         ("n_weak", "<i4"), ("ambiguous", "<i4"), ("root", "<i4")])
 assert NODE_DTYPE.itemsize == 24 and CAND_DTYPE.itemsize == 48 and PLANE_DTYPE.itemsize == 44 and MASK_DTYPE.itemsize == 16
+assert LINE_CROP_DTYPE.itemsize == 40
 
 
 def unpack_mask(words: np.ndarray, word_off: int, w: int, h: int) -> np.ndarray:
@@ -210,6 +217,15 @@ def load_library():
     L.str_er_result_mask_bits.restype = vp
     L.str_er_er_masks.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
     L.str_er_set_min_ocr_prob.argtypes = [vp, C.c_double]
+    L.str_er_result_line_crops.argtypes = [vp, i32p]
+    L.str_er_result_line_crops.restype = vp
+    for fn in (L.str_er_result_line_crop_pixels, L.str_er_result_line_glyph_pixels):
+        fn.argtypes = [vp, C.POINTER(C.c_uint64)]
+        fn.restype = vp
+    L.str_er_set_line_crop.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
+    L.str_er_line_crop_geometry.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, vp]
+    L.str_er_line_crops.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, C.c_uint64,
+                                    C.POINTER(C.c_uint64), vp]
     for fn in (L.str_er_result_texts, L.str_er_result_text_ers, L.str_er_result_group_bounds, L.str_er_result_group_all,
                L.str_er_result_line_labels, L.str_er_result_line_probs, L.str_er_result_line_kept, L.str_er_result_text_alive):
         fn.argtypes = [vp, i32p]
@@ -320,6 +336,9 @@ class Result:
         self.text_alive = None
         self.masks = None          # with WANT_MASKS: MASK_DTYPE per candidate, and the words they index (uint32)
         self.mask_bits = None
+        self.line_crops = None     # with WANT_LINE_CROPS: LINE_CROP_DTYPE per line of texts, the grey crop bytes and (WANT_LINE_GLYPHS) the glyph bytes
+        self.line_crop_pixels = None
+        self.line_glyph_pixels = None
         self._planes = None
 
     @property
@@ -333,6 +352,36 @@ class Result:
             raise ValueError("the result has no masks (pass WANT_MASKS / want_masks=True)")
         c = self.cands[i]
         return unpack_mask(self.mask_bits, int(self.masks[i]["word_off"]), int(c["w"]), int(c["h"]))
+
+    def _crop_of(self, pixels, t: int) -> np.ndarray:
+        if self.line_crops is None:
+            raise ValueError("the result has no line crops (pass WANT_LINE_CROPS / want_line_crops=True)")
+        g = self.line_crops[t]
+        o, w, h = int(g["pix_off"]), int(g["width"]), int(g["height"])
+        return pixels[o:o + w * h].reshape(h, w)
+
+    def line_crop(self, t: int) -> np.ndarray:
+        """With WANT_LINE_CROPS: the grey crop of line t as a (height, width) uint8 array."""
+        return self._crop_of(self.line_crop_pixels, t)
+
+    def line_glyph(self, t: int) -> np.ndarray:
+        """With WANT_LINE_GLYPHS: the glyph crop of line t (255 on the member masks, else 0) as a (height, width) uint8 array."""
+        if self.line_crops is not None and self.line_glyph_pixels is None:
+            raise ValueError("the result has no glyph crops (pass WANT_LINE_GLYPHS / want_line_crops=\"glyphs\")")
+        return self._crop_of(self.line_glyph_pixels, t)
+
+    def line_crop_batch(self, glyphs: bool = False):
+        """With WANT_LINE_CROPS: every line's crop (or glyph crop) in one (n, height, max width) uint8 array, zero-padded on the
+        right, and the widths (n,) -- the input of a recogniser that takes a batch."""
+        if self.line_crops is None:
+            raise ValueError("the result has no line crops (pass WANT_LINE_CROPS / want_line_crops=True)")
+        n = len(self.line_crops)
+        widths = self.line_crops["width"].astype(np.int32)
+        h = int(self.line_crops["height"][0]) if n else 0
+        out = np.zeros((n, h, int(widths.max()) if n else 0), np.uint8)
+        for t in range(n):
+            out[t, :, :widths[t]] = self.line_glyph(t) if glyphs else self.line_crop(t)
+        return out, widths
 
     @property
     def planes(self) -> List[PlaneResult]:
@@ -462,6 +511,16 @@ class ERFilter:
                 bp = L.str_er_result_group_bounds(rh, C.byref(no))
                 res.group_bounds = (np.frombuffer((C.c_char * (24 * no.value)).from_address(bp), dtype=GBOUND_DTYPE).copy()
                                     if no.value else np.zeros(0, GBOUND_DTYPE))
+            cp = L.str_er_result_line_crops(rh, C.byref(no))
+            if cp:
+                res.line_crops = (np.frombuffer((C.c_char * (40 * no.value)).from_address(cp), dtype=LINE_CROP_DTYPE).copy()
+                                  if no.value else np.zeros(0, LINE_CROP_DTYPE))
+                nb = C.c_uint64()
+                for name, fn in (("line_crop_pixels", L.str_er_result_line_crop_pixels), ("line_glyph_pixels", L.str_er_result_line_glyph_pixels)):
+                    bp = fn(rh, C.byref(nb))
+                    if bp:
+                        setattr(res, name, np.frombuffer((C.c_char * nb.value).from_address(bp), dtype=np.uint8).copy()
+                                if nb.value else np.zeros(0, np.uint8))
             mp = L.str_er_result_masks(rh, C.byref(no))
             if mp:
                 res.masks = (np.frombuffer((C.c_char * (16 * no.value)).from_address(mp), dtype=MASK_DTYPE).copy()
@@ -516,7 +575,8 @@ class ERFilter:
         return {names[i].decode(): ms[i] for i in range(min(k, 32))}
 
     # ---- the hot path ---------------------------------------------------------------------------
-    def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False) -> Result:
+    def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
+                    want_line_crops=False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -527,7 +587,8 @@ class ERFilter:
         f, h, w, _ = a.shape
         rh = C.c_void_p()
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
-                                             stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0), C.byref(rh)))
+                                             stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) |
+                                             _crop_flags(want_line_crops), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -645,13 +706,14 @@ class ERFilter:
         self._check(fn(self.h, arr, len(refs), mem_kind, stages, C.byref(rh)))
         return self._collect(rh)
 
-    def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False) -> Result:
+    def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
+                         want_line_crops=False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
-                                 stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0))
+                                 stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) | _crop_flags(want_line_crops))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -746,6 +808,32 @@ class ERFilter:
             self._check(self.L.str_er_er_masks(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(r), n,
                                                _np_ptr(words), nw.value, C.byref(nw), _np_ptr(pixels)))
         return words[:nw.value], pixels[:n]
+
+    def set_line_crop(self, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> None:
+        """str_er_set_line_crop: the crop height (8..256), the widest crop (1..8192) and the pad (0..1, of the line's height) of
+        WANT_LINE_CROPS and line_crops."""
+        self._check(self.L.str_er_set_line_crop(self.h, int(height), int(max_width), float(pad)))
+
+    def line_crops(self, plane: np.ndarray, boxes_xywh: np.ndarray, first, count, slopes):
+        """str_er_line_crops: grey crops of lines of one (H, W) uint8 plane at the context's crop settings.  Line k has the boxes
+        boxes_xywh[first[k]:first[k] + count[k]] and slope slopes[k].  Returns (records LINE_CROP_DTYPE, crop bytes)."""
+        a = np.ascontiguousarray(plane, dtype=np.uint8)
+        bx = np.ascontiguousarray(boxes_xywh, dtype=np.int32).reshape(-1, 4)
+        fi = np.ascontiguousarray(first, dtype=np.int32).reshape(-1)
+        co = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+        sl = np.ascontiguousarray(slopes, dtype=np.float64).reshape(-1)
+        n = len(fi)
+        if len(co) != n or len(sl) != n or (n and int((fi + co).max()) > len(bx)):
+            raise ValueError("first / count / slopes must have one entry per line, and the boxes they name must exist")
+        recs = np.zeros(max(1, n), LINE_CROP_DTYPE)
+        nb = C.c_uint64()
+        args = (self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(bx) if len(bx) else None, _np_ptr(fi) if n else None,
+                _np_ptr(co) if n else None, _np_ptr(sl) if n else None, n)
+        self._check(self.L.str_er_line_crops(*args, None, 0, C.byref(nb), _np_ptr(recs)))
+        pixels = np.zeros(max(1, nb.value), np.uint8)
+        if n:
+            self._check(self.L.str_er_line_crops(*args, _np_ptr(pixels), nb.value, C.byref(nb), _np_ptr(recs)))
+        return recs[:n], pixels[:nb.value]
 
     def predict(self, which: int, fv: np.ndarray) -> np.ndarray:
         """stc->predict(fv) / wtc->predict(fv) (inc/adaboost.h:131) for (n,1024) feature vectors."""
@@ -886,6 +974,24 @@ class ERFilter:
 
     def workspace_bytes(self) -> int:
         return int(self.L.str_er_workspace_bytes(self.h))
+
+
+def _crop_flags(want_line_crops) -> int:
+    """want_line_crops=: False, True (grey crops) or "glyphs" (grey and glyph crops)."""
+    if want_line_crops == "glyphs":
+        return WANT_LINE_CROPS | WANT_LINE_GLYPHS
+    return WANT_LINE_CROPS if want_line_crops else 0
+
+
+def line_crop_geometry(boxes_xywh: np.ndarray, slope: float, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> np.ndarray:
+    """str_er_line_crop_geometry: the crop record (LINE_CROP_DTYPE, pix_off 0) of one line with these boxes and slope."""
+    bx = np.ascontiguousarray(boxes_xywh, dtype=np.int32).reshape(-1, 4)
+    out = np.zeros(1, LINE_CROP_DTYPE)
+    rc = load_library().str_er_line_crop_geometry(_np_ptr(bx) if len(bx) else None, len(bx), float(slope), int(height), int(max_width),
+                                                  float(pad), _np_ptr(out))
+    if rc != 0:
+        raise StrErError(rc, "str_er_line_crop_geometry")
+    return out[0]
 
 
 def flood_order(plane: np.ndarray, thresh_step: int = 8) -> np.ndarray:

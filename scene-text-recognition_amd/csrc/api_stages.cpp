@@ -312,7 +312,13 @@ try {
 
 namespace str_er_host {
 
-int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, uint32_t *pixels, uint32_t *bits)
+// (o_pix / o_bits: where the popcounts and the words of n jobs sit in c->d_mask, behind the jobs)
+static void mask_offsets(size_t n, uint64_t n_words, size_t &o_pix, size_t &o_bits, size_t &need)
+{
+    o_pix = align_up(sizeof(MaskJob) * n, 256); o_bits = align_up(o_pix + 4 * n, 256); need = o_bits + 4 * (size_t)n_words;
+}
+
+int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, const uint32_t **d_bits)
 {
     const size_t n = jobs.size();
     if (n == 0) return STR_ER_OK;
@@ -322,7 +328,8 @@ int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_
     std::stable_sort(jobs.begin(), jobs.end(), [](const MaskJob &a, const MaskJob &b) { return mask_class(a.w, a.h) < mask_class(b.w, b.h); });
     size_t scratch = 0;
     for (MaskJob &j : jobs) { j.scratch_off = scratch; scratch += mask_scratch_words(j.w, j.h); }
-    const size_t o_pix = align_up(sizeof(MaskJob) * n, 256), o_bits = align_up(o_pix + 4 * n, 256), need = o_bits + 4 * (size_t)n_words;
+    size_t o_pix, o_bits, need;
+    mask_offsets(n, n_words, o_pix, o_bits, need);
     if (need > c->mask_bytes) {
         const size_t get = std::max(need, 2 * c->mask_bytes);
         if (c->d_mask) { (void)hipFree(c->d_mask); c->d_mask = nullptr; }
@@ -348,6 +355,19 @@ int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_
     launch_er_masks(s, reinterpret_cast<const MaskJob *>(c->d_mask), n_class, reinterpret_cast<uint32_t *>(c->d_mask + o_bits),
                     reinterpret_cast<uint32_t *>(c->d_mask + o_pix), c->d_mask_scratch, qscale);
     HIP_TRY(c, hipGetLastError());
+    if (d_bits) *d_bits = reinterpret_cast<const uint32_t *>(c->d_mask + o_bits);
+    return STR_ER_OK;
+}
+
+int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, uint32_t *pixels, uint32_t *bits,
+               const uint32_t **d_bits)
+{
+    const size_t n = jobs.size();
+    if (n == 0) return STR_ER_OK;
+    const int rc = mask_launch(c, s, jobs, n_words, qscale, d_bits);
+    if (rc != STR_ER_OK) return rc;
+    size_t o_pix, o_bits, need;
+    mask_offsets(n, n_words, o_pix, o_bits, need);
     HIP_TRY(c, hipMemcpyAsync(c->h_mask + o_pix, c->d_mask + o_pix, need - o_pix, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
     std::memcpy(pixels, c->h_mask + o_pix, 4 * n);

@@ -136,4 +136,8 @@ int    mask_class(int w, int h);
 size_t mask_scratch_words(int w, int h);
 void   launch_er_masks(hipStream_t s, const MaskJob *jobs, const int n_class[3], uint32_t *out, uint32_t *pixels, uint64_t *scratch, float qscale);
 
+// Line crops (er_line_crops.inl): n jobs, one workgroup each.  out receives the grey crops at LineCropJob::out_off; with glyph != null
+// also the glyph crops (same offsets), from the members and the mask words `bits` they index.
+void launch_line_crops(hipStream_t s, const LineCropJob *jobs, int n, uint8_t *out, uint8_t *glyph, const GlyphMember *members, const uint32_t *bits);
+
 } // namespace str_er

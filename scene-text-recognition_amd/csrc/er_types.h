@@ -203,4 +203,24 @@ struct MaskJob {
 };
 static_assert(sizeof(MaskJob) == 56, "MaskJob layout (host and device)");
 
+// One line of the crop stage (STR_ER_WANT_LINE_CROPS, str_er_line_crops): the 16.16 sampling geometry of str_er_line_crop over the
+// line's Y plane, and for glyph crops the line's distinct members (GlyphMember[m_first .. m_first + m_count)).
+struct LineCropJob {
+    const uint8_t *pix;     // device pointer, top-left pixel of the Y plane
+    uint64_t out_off;       // first byte of the crop in the output (a multiple of 4)
+    int32_t  stride, pw, ph;
+    int32_t  width, height;
+    int32_t  ax, ay, ux, uy, vx, vy;
+    uint32_t m_first, m_count;
+    int32_t  pad0;
+};
+static_assert(sizeof(LineCropJob) == 72, "LineCropJob layout (host and device)");
+
+// A member of a line for its glyph crop: the candidate's box and its mask (the str_er_mask layout: h rows of (w + 31) / 32 words)
+struct GlyphMember {
+    uint64_t word_off;
+    uint16_t x, y, w, h;
+};
+static_assert(sizeof(GlyphMember) == 16, "GlyphMember layout (host and device)");
+
 } // namespace str_er

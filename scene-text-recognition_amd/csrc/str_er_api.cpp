@@ -829,6 +829,9 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
     if ((stages & (STR_ER_STAGE_GROUP | STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP)) && !(stages & STR_ER_STAGE_TRACK)) return fail(c, STR_ER_EINVAL, "STR_ER_STAGE_GROUP needs STR_ER_STAGE_TRACK");
     if ((stages & (STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP)) && !(stages & STR_ER_STAGE_GROUP)) return fail(c, STR_ER_EINVAL, "STR_ER_GROUP_INNER_SUP / _OVERLAP_SUP modify STR_ER_STAGE_GROUP");
     if ((stages & STR_ER_STAGE_OCR_LINES) && !(stages & STR_ER_STAGE_GROUP)) return fail(c, STR_ER_EINVAL, "STR_ER_STAGE_OCR_LINES needs STR_ER_STAGE_GROUP");
+    if ((stages & (STR_ER_WANT_LINE_CROPS | STR_ER_WANT_LINE_GLYPHS)) && !(stages & STR_ER_STAGE_GROUP))
+        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_CROPS / _GLYPHS need STR_ER_STAGE_GROUP");
+    if ((stages & STR_ER_WANT_LINE_GLYPHS) && !(stages & STR_ER_WANT_LINE_CROPS)) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_GLYPHS needs STR_ER_WANT_LINE_CROPS");
     if ((stages & STR_ER_STAGE_OCR_LINES) && !(c->svm_loaded && c->svm.dim == 1800))
         return fail(c, STR_ER_ESTATE, "STR_ER_STAGE_OCR_LINES needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)");
     if ((stages & STR_ER_STAGE_TRACK) && b.planes_per_image <= 0)
@@ -1264,6 +1267,7 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
         off += pc.n_pool;
     }
     r->cand_off[np] = off;
+    const uint32_t *d_mask_bits = nullptr;         // (the masks' words on the device, for the glyph crops below)
     if (stages & STR_ER_WANT_MASKS) {
         // the masks of the final candidates (after any NMS tie pass): sized on the host from the records just copied, one launch per size class, one wait
         std::vector<MaskJob> jobs(total);
@@ -1281,10 +1285,15 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
             words += (uint64_t)cd.h * r->masks[k].pitch_words;
         }
         r->mask_bits.resize(words);
-        const int rcm = mask_stage(c, s, jobs, words, dp.qscale, px.data(), r->mask_bits.data());
+        const int rcm = mask_stage(c, s, jobs, words, dp.qscale, px.data(), r->mask_bits.data(), &d_mask_bits);
         if (rcm != STR_ER_OK) { delete r; return rcm; }
         for (uint32_t k = 0; k < total; ++k) r->masks[k].pixels = px[k];
         r->have_masks = true;
+    }
+    if (stages & STR_ER_WANT_LINE_CROPS) {
+        // the crops of the final lines, while the call's planes are still in the workspace: laid out on the host, one launch, one wait
+        const int rcc = line_crop_phase(c, s, b, dp.qscale, (stages & STR_ER_WANT_LINE_GLYPHS) != 0, d_mask_bits, r);
+        if (rcc != STR_ER_OK) { delete r; return rcc; }
     }
     if (want_nodes) {
         // candidates carry the device kept slot; translate to the sorted table through (key, level)
@@ -1428,6 +1437,8 @@ void str_er_destroy(str_er_ctx *c)
     if (c->d_mask) (void)hipFree(c->d_mask);
     if (c->h_mask) (void)hipHostFree(c->h_mask);
     if (c->d_mask_scratch) (void)hipFree(c->d_mask_scratch);
+    if (c->d_crop) (void)hipFree(c->d_crop);
+    if (c->h_crop) (void)hipHostFree(c->h_crop);
     if (c->d_strip_out) (void)hipFree(c->d_strip_out);
     if (c->d_strip_in) (void)hipFree(c->d_strip_in);
     if (c->d_replay) (void)hipFree(c->d_replay);

@@ -76,6 +76,9 @@ struct str_er_result {
     std::vector<str_er_mask> masks;          // STR_ER_WANT_MASKS: per candidate
     std::vector<uint32_t> mask_bits;
     bool have_masks = false;
+    std::vector<str_er_line_crop> line_crops;     // STR_ER_WANT_LINE_CROPS: per line, and the bytes they index
+    std::vector<uint8_t> crop_pixels, glyph_pixels;
+    bool have_line_crops = false, have_line_glyphs = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -160,6 +163,10 @@ struct str_er_ctx {
     // STR_ER_WANT_MASKS / str_er_er_masks: created by the first call that wants masks, grown geometrically, never shrunk
     uint8_t  *d_mask = nullptr, *h_mask = nullptr; size_t mask_bytes = 0;       // jobs | popcounts | words, on the device and page-locked
     uint64_t *d_mask_scratch = nullptr; size_t mask_scratch_words = 0;         // rows of the boxes too large for LDS
+    // STR_ER_WANT_LINE_CROPS / str_er_line_crops (str_er_set_line_crop), and the buffers of the crop stage: created by the first call
+    // that wants crops, grown geometrically, never shrunk
+    int32_t  crop_height = 32, crop_max_width = 1024; double crop_pad = 0.125;
+    uint8_t  *d_crop = nullptr, *h_crop = nullptr; size_t crop_bytes = 0;       // jobs | members | grey | glyph bytes, on the device and page-locked
     uint8_t *d_strip_out = nullptr, *d_strip_in = nullptr; size_t strip_out_cap = 0, strip_in_cap = 0;   // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -369,7 +376,17 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
 int stage_input(str_er_ctx *c, const uint8_t *src, size_t bytes, int mem_kind, const uint8_t **dev);
 // ---- defined in api_stages.cpp
 // the pixel masks of `jobs` (out_off / idx set by the caller, n_words words in all): launched on s, waited for, copied to pixels[idx] and bits
-int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, uint32_t *pixels, uint32_t *bits);
+// (d_bits, optional: where the words stay on the device, as for mask_launch)
+int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, uint32_t *pixels, uint32_t *bits,
+               const uint32_t **d_bits = nullptr);
+// the launches of mask_stage alone: the words stay on the device, at *d_bits (in c->d_mask, valid until the context's next mask launch)
+int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, const uint32_t **d_bits);
+// ---- defined in api_line_crops.cpp
+// the str_er_line_crop geometry of one line (STR_ER_EINVAL when it leaves 16.16 fixed point)
+int line_crop_geometry(const int32_t *boxes_xywh, int32_t n_boxes, double slope, int32_t height, int32_t max_width, double pad, str_er_line_crop &out);
+// STR_ER_WANT_LINE_CROPS / _GLYPHS in run_batch: the crops of the lines of r, from the Y planes of b (planes_per_image > 0)
+// (d_mask_bits: the words of this call's STR_ER_WANT_MASKS on the device, or null: then the glyphs' masks are made here)
+int line_crop_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, bool glyphs, const uint32_t *d_mask_bits, str_er_result *r);
 constexpr int MASK_MAX_WIDTH = 16384;       // widest box the mask kernels take (er_masks.inl: MASK_MAX_WPL words of 64 pixels per lane)
 // ---- defined in api_models.cpp
 int parse_cascade(str_er_ctx *c, HostCascade &hc, const char *text, size_t len);

@@ -262,6 +262,42 @@ public:
         for (int i = 0; i < 6; ++i) channels[i].assign(six.begin() + i * n, six.begin() + (i + 1) * n);
     }
 
+    // A recogniser-ready image of each line of `text` (str_er_line_crops): the line deskewed by its slope and resampled to the
+    // context's crop height (set_line_crop), from the 8UC1 Y plane the lines were found on.  A line's boxes are its ERs' bounds as
+    // er_grouping leaves them.  Crop t: geom (str_er_line_crop) and geom.height rows of geom.width bytes.
+    struct LineCrop {
+        str_er_line_crop geom{};
+        std::vector<uint8_t> pixels;
+    };
+    void set_line_crop(int height = 32, int max_width = 1024, double pad = 0.125) { check(str_er_set_line_crop(ctx_.get(), height, max_width, pad)); }
+    std::vector<LineCrop> text_crops(const Image8 &y_plane, const std::vector<Text> &text)
+    {
+        if (y_plane.channels != 1) throw std::runtime_error("text_crops expects an 8UC1 plane");
+        std::vector<int32_t> boxes, first, count;
+        std::vector<double>  slopes;
+        for (const Text &t : text) {
+            first.push_back((int32_t)(boxes.size() / 4));
+            count.push_back((int32_t)t.ers.size());
+            slopes.push_back(t.slope);
+            for (const ER *e : t.ers) boxes.insert(boxes.end(), {e->bound.x, e->bound.y, e->bound.width, e->bound.height});
+        }
+        const int32_t n = (int32_t)text.size();
+        std::vector<str_er_line_crop> recs(n ? n : 1);
+        uint64_t n_bytes = 0;
+        check(str_er_line_crops(ctx_.get(), y_plane.data, y_plane.cols, y_plane.rows, y_plane.step, boxes.data(), first.data(), count.data(),
+                                slopes.data(), n, nullptr, 0, &n_bytes, recs.data()));
+        std::vector<uint8_t> pix(n_bytes ? n_bytes : 1);
+        if (n) check(str_er_line_crops(ctx_.get(), y_plane.data, y_plane.cols, y_plane.rows, y_plane.step, boxes.data(), first.data(), count.data(),
+                                       slopes.data(), n, pix.data(), n_bytes, &n_bytes, recs.data()));
+        std::vector<LineCrop> out((size_t)n);
+        for (int32_t t = 0; t < n; ++t) {
+            const str_er_line_crop &g = recs[(size_t)t];
+            out[(size_t)t].geom = g;
+            out[(size_t)t].pixels.assign(pix.begin() + (ptrdiff_t)g.pix_off, pix.begin() + (ptrdiff_t)(g.pix_off + (uint64_t)g.width * g.height));
+        }
+        return out;
+    }
+
     // The pixels of ERs of one 8UC1 plane (str_er_er_masks): what the reference's flood visits for each ER and forgets.  Mask i is
     // ers[i]'s bound and, row by row over it, 1 for a pixel of the region (reachable from ER::key through 4-neighbours of level
     // <= ER::level inside the bound), 0 otherwise.  ER::key must be the canonical key of a region of this plane (as unpack_plane sets it).
