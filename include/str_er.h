@@ -415,6 +415,10 @@ int str_er_svm_forms(const str_er_ctx *ctx, int32_t *bytes, int32_t *class_sums)
  * be NULL) receives the nr_class*(nr_class-1)/2 decision values of svm_predict_values.              */
 int str_er_svm_predict_probability(str_er_ctx *ctx, const double *x, int32_t n, int32_t dim, int32_t *label, double *prob,
                                    double *dec);
+/* The same for n vectors given as 8-bit numerators over 255, q[n][dim] (feature j = q[i][j] / 255.0: the vectors OCR::chain_run makes from its
+ * boxes, src/OCR.cpp:211), scored by the kernels that score the boxes of chain_run and of STR_ER_STAGE_OCR / _OCR_LINES (str_er_svm_forms says which):
+ * for dim = 1800, a box's label and pv[label] are those of its q_out row here, bit for bit.  label[i], prob[i][nr_class], dec (optional) as above. */
+int str_er_svm_predict_probability_q8(str_er_ctx *ctx, const uint8_t *q, int32_t n, int32_t dim, int32_t *label, double *prob, double *dec);
 
 /* OCR::chain_run(Mat src, int thresh, double slope) (src/OCR.cpp:67-140) for n boxes (ER::bound) of one host
  * plane (the channel the ER came from), with slope == 0: Otsu-binarise 255-roi, ARAN(30), chain-code

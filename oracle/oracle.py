@@ -405,6 +405,7 @@ class OracleSVM:
             f.argtypes = [C.c_void_p]
         L.ero_svm_predict_probability.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double),
                                                   C.POINTER(C.c_double)]
+        L.ero_svm_couple.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)]
         self.L = L
         self.h = L.ero_svm_load(path.encode())
         if not self.h:
@@ -418,6 +419,16 @@ class OracleSVM:
         p = C.POINTER(C.c_double)
         lab = self.L.ero_svm_predict_probability(self.h, x.ctypes.data_as(p), x.size, dec.ctypes.data_as(p), prob.ctypes.data_as(p))
         return int(lab), prob, dec
+
+    def couple(self, dec: np.ndarray):
+        """The probability half alone (ero_svm_couple) on given decision values -> (label, prob, sweeps, margin)."""
+        dec = np.ascontiguousarray(dec, dtype=np.float64)
+        assert dec.size == self.k * (self.k - 1) // 2, dec.size
+        prob = np.zeros(self.k)
+        sweeps, margin = C.c_int(0), C.c_double(0)
+        p = C.POINTER(C.c_double)
+        lab = self.L.ero_svm_couple(self.h, dec.ctypes.data_as(p), prob.ctypes.data_as(p), C.byref(sweeps), C.byref(margin))
+        return int(lab), prob, int(sweeps.value), float(margin.value)
 
 
 class _SvmNode(C.Structure):

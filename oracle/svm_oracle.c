@@ -133,12 +133,13 @@ static double sigmoid_predict(double dv, double A, double B)   /* src/svm.cpp:18
     return 1.0 / (1 + exp(fApB));
 }
 
-/* multiclass_probability, src/svm.cpp:1829-1890 (r is k x k row-major) */
-static void multiclass_probability(int k, const double *r, double *p)
+/* multiclass_probability, src/svm.cpp:1829-1890 (r is k x k row-major).  *sweeps = the stopping tests evaluated, *margin = the smallest
+ * |max_error - eps| among them (how far the sweep count is from changing under a perturbation of r) */
+static void multiclass_probability(int k, const double *r, double *p, int *sweeps, double *margin)
 {
     int t, j, iter = 0, max_iter = k > 100 ? k : 100;
     double *Q = (double *)malloc(8 * (size_t)k * k), *Qp = (double *)malloc(8 * (size_t)k);
-    double pQp, eps = 0.005 / k;
+    double pQp, eps = 0.005 / k, mg = INFINITY;
     for (t = 0; t < k; t++) {
         p[t] = 1.0 / k;
         Q[t * k + t] = 0;
@@ -154,6 +155,7 @@ static void multiclass_probability(int k, const double *r, double *p)
         }
         double max_error = 0;
         for (t = 0; t < k; t++) { double e = fabs(Qp[t] - pQp); if (e > max_error) max_error = e; }
+        if (fabs(max_error - eps) < mg) mg = fabs(max_error - eps);
         if (max_error < eps) break;
         for (t = 0; t < k; t++) {
             double diff = (-Qp[t] + pQp) / Q[t * k + t];
@@ -162,6 +164,8 @@ static void multiclass_probability(int k, const double *r, double *p)
             for (j = 0; j < k; j++) { Qp[j] = (Qp[j] + diff * Q[t * k + j]) / (1 + diff); p[j] /= (1 + diff); }
         }
     }
+    if (sweeps) *sweeps = iter < max_iter ? iter + 1 : max_iter;
+    if (margin) *margin = mg;
     free(Q); free(Qp);
 }
 
@@ -190,9 +194,16 @@ int ero_svm_predict_probability(const ero_svm *m, const double *x, int dim, doub
             sum -= m->rho[p];
             dec[p++] = sum;
         }
+    free(xi); free(xv); free(kv); free(start);
+    return ero_svm_couple(m, dec, prob, NULL, NULL);
+}
+
+int ero_svm_couple(const ero_svm *m, const double *dec, double *prob, int *sweeps, double *margin)
+{
+    const int k = m->k;
     double *r = (double *)calloc((size_t)k * k, 8);
     const double min_prob = 1e-7;
-    p = 0;
+    int p = 0;
     for (int i = 0; i < k; ++i)                       /* svm_predict_probability, src/svm.cpp:2603-2611 */
         for (int j = i + 1; j < k; ++j) {
             double v = sigmoid_predict(dec[p], m->probA[p], m->probB[p]);
@@ -201,10 +212,10 @@ int ero_svm_predict_probability(const ero_svm *m, const double *x, int dim, doub
             r[i * k + j] = v; r[j * k + i] = 1 - v;
             ++p;
         }
-    multiclass_probability(k, r, prob);
+    multiclass_probability(k, r, prob, sweeps, margin);
     int best = 0;
     for (int i = 1; i < k; ++i) if (prob[i] > prob[best]) best = i;
     const int lab = m->label[best];
-    free(xi); free(xv); free(kv); free(start); free(r);
+    free(r);
     return lab;
 }

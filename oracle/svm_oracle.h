@@ -30,6 +30,10 @@ double   ero_svm_gamma(const ero_svm *m);
  * sparse svm_node list the reference builds in OCR::extract_feature, src/OCR.cpp:203-216).
  * dec: k(k-1)/2 decision values, prob: k probabilities.  Returns model->label[argmax prob]. */
 int      ero_svm_predict_probability(const ero_svm *m, const double *x, int dim, double *dec, double *prob);
+/* Its probability half on its own: sigmoid_predict of the k(k-1)/2 decision values dec, then multiclass_probability -> prob (k),
+ * returns model->label[argmax prob].  sweeps (may be NULL): the stopping tests evaluated; margin (may be NULL): the smallest
+ * |max_error - eps| among them -- a perturbation of dec that moves the statistic by less cannot change the number of sweeps. */
+int      ero_svm_couple(const ero_svm *m, const double *dec, double *prob, int *sweeps, double *margin);
 
 #ifdef __cplusplus
 }

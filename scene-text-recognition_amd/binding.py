@@ -178,6 +178,7 @@ def load_library():
     L.str_er_svm_info.argtypes = [vp, i32p, i32p, i32p]
     L.str_er_svm_forms.argtypes = [vp, i32p, i32p]
     L.str_er_svm_predict_probability.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
+    L.str_er_svm_predict_probability_q8.argtypes = [vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
     L.str_er_ocr_chain_run.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp, vp]
     L.str_er_ocr_chain_run_slope.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32, vp, vp, vp]
     L.str_er_nms_tree.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, i32p, i32p]
@@ -873,6 +874,20 @@ class ERFilter:
         dec = np.zeros((n, k * (k - 1) // 2), np.float64) if want_dec else None
         self._check(self.L.str_er_svm_predict_probability(self.h, _np_ptr(a), n, dim, _np_ptr(label), _np_ptr(prob),
                                                           _np_ptr(dec) if want_dec else None))
+        return (label, prob, dec) if want_dec else (label, prob)
+
+    def svm_predict_q8(self, q: np.ndarray, want_dec: bool = False):
+        """svm_predict_probability for (n, dim) 8-bit numerators over 255 (chain_run's q rows), by the kernels that score boxes -> (label, prob[, dec])."""
+        a = np.ascontiguousarray(q, dtype=np.uint8)
+        if a.ndim == 1:
+            a = a[None]
+        n, dim = a.shape
+        k = self.svm_info()[0]
+        label = np.zeros(n, np.int32)
+        prob = np.zeros((n, k), np.float64)
+        dec = np.zeros((n, k * (k - 1) // 2), np.float64) if want_dec else None
+        self._check(self.L.str_er_svm_predict_probability_q8(self.h, _np_ptr(a), n, dim, _np_ptr(label), _np_ptr(prob),
+                                                             _np_ptr(dec) if want_dec else None))
         return (label, prob, dec) if want_dec else (label, prob)
 
     def chain_run(self, plane: np.ndarray, boxes_xywh: np.ndarray, classify: bool = True, slope=None):

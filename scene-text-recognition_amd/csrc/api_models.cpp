@@ -1,4 +1,4 @@
-// api_models.cpp -- the C ABI, part 2: the models -- cascade text (CascadeBoost::load_classifier), libsvm text model, and the entry points that run them on explicit inputs (predict, svm_predict_probability, OCR::chain_run)
+// api_models.cpp -- the C ABI, part 2: the models -- cascade text (CascadeBoost::load_classifier), libsvm text model, and the entry points that run them on explicit inputs (predict, svm_predict_probability[_q8], OCR::chain_run)
 #include "str_er_ctx.h"
 #include "svm_tables.h"
 
@@ -391,6 +391,34 @@ try {
     HIP_TRY(c, hipMemcpyAsync(s + o_x, x, (size_t)n * dim * 8, hipMemcpyHostToDevice, st));
     launch_svm_prep(st, reinterpret_cast<const double *>(s + o_x), n, dim, buf, m);
     launch_svm_score(st, n, buf, m, false);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(prob, buf.prob, (size_t)n * m.k * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(label, buf.label, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (dec) HIP_TRY(c, hipMemcpyAsync(dec, buf.dec, (size_t)n * np * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, wait_stream(c, st));
+    return STR_ER_OK;
+} ABI_GUARD(c)
+
+int str_er_svm_predict_probability_q8(str_er_ctx *c, const uint8_t *q, int32_t n, int32_t dim, int32_t *label, double *prob, double *dec)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (n < 0 || (n > 0 && (!q || !label || !prob))) return fail(c, STR_ER_EINVAL, "bad arguments");
+    if (!c->svm_loaded) return fail(c, STR_ER_ESTATE, "svm model not loaded");
+    if (dim != c->svm.dim) return fail(c, STR_ER_EINVAL, "feature dimension differs from the one the model was loaded with");
+    if (n == 0) return STR_ER_OK;
+    HIP_TRY(c, hipSetDevice(c->prm.device));
+    const SvmDev &m = c->svm;
+    const size_t np = (size_t)m.k * (m.k - 1) / 2;
+    // the bytes in a region of their own, then the carve-up chain_run scores its boxes from (its q rows are not needed: the features are given)
+    const size_t o_q = 0, o_buf = align_up((size_t)n * dim, 256);
+    int rc = ensure_scratch(c, o_buf + ocr_layout(nullptr, (size_t)n, &m, false, dec != nullptr, true).bytes);
+    if (rc != STR_ER_OK) return rc;
+    uint8_t *s = static_cast<uint8_t *>(c->d_scratch);
+    const OcrBuf buf = ocr_layout(s + o_buf, (size_t)n, &m, false, dec != nullptr, true);
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(s + o_q, q, (size_t)n * dim, hipMemcpyHostToDevice, st));
+    launch_svm_prep_q8(st, s + o_q, n, dim, buf, m);
+    launch_svm_score(st, n, buf, m, true);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(prob, buf.prob, (size_t)n * m.k * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipMemcpyAsync(label, buf.label, (size_t)n * 4, hipMemcpyDeviceToHost, st));

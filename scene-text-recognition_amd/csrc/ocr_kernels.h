@@ -106,5 +106,8 @@ void launch_svm_couple(hipStream_t s, int n, const OcrBuf &buf, const SvmDev &m)
 
 // f64 feature vectors (API entry str_er_svm_predict_probability) -> buf.xf / buf.xnorm
 void launch_svm_prep(hipStream_t s, const double *x, int n, int dim, const OcrBuf &buf, const SvmDev &m);
+// 8-bit numerators over 255 (API entry str_er_svm_predict_probability_q8) -> the rows k_ocr_features writes for a box: buf.x8 / buf.x8s (models with
+// SvmDev::sv8) or buf.xq / buf.xnorm -- then launch_svm_score(..., numerators = true) as for boxes
+void launch_svm_prep_q8(hipStream_t s, const uint8_t *q, int n, int dim, const OcrBuf &buf, const SvmDev &m);
 
 } // namespace str_er

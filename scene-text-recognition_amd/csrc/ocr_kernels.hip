@@ -462,14 +462,16 @@ __global__ __launch_bounds__(64 * OCR_WAVES) void k_ocr_features(OcrSrc src, int
 // ---------------------------------------------------------------------------------------------------------
 // libsvm inference
 // ---------------------------------------------------------------------------------------------------------
-// exp(x) for x <= 0 without the library's range cases: 2^n e^r, |r| <= ln 2 / 2, degree-11 Taylor (3e-17 relative); below e^-700 the result is 0
+// exp(x) for x <= 0 without the library's range cases: 2^n e^r, |r| <= ln 2 / 2, degree-13 Taylor (truncation r^14 / 14! < 4.2e-18 relative: the
+// degree-11 form this replaces was 8.6e-15 -- 39 units of the last place -- off at the ends of the range, tests/test_svm_exact.py); below e^-700 the result is 0
 __device__ __forceinline__ double exp_neg(double x)
 {
     x = fmax(x, -700.0);
     const double nn = __builtin_rint(x * 1.4426950408889634);
     double       r = __builtin_fma(nn, -6.93147180369123816490e-01, x);
     r = __builtin_fma(nn, -1.90821492927058770002e-10, r);
-    double e = 1.0 / 39916800.0;
+    double e = 1.0 / 6227020800.0;
+    e = __builtin_fma(e, r, 1.0 / 479001600.0); e = __builtin_fma(e, r, 1.0 / 39916800.0);
     e = __builtin_fma(e, r, 1.0 / 3628800.0); e = __builtin_fma(e, r, 1.0 / 362880.0); e = __builtin_fma(e, r, 1.0 / 40320.0);
     e = __builtin_fma(e, r, 1.0 / 5040.0); e = __builtin_fma(e, r, 1.0 / 720.0); e = __builtin_fma(e, r, 1.0 / 120.0);
     e = __builtin_fma(e, r, 1.0 / 24.0); e = __builtin_fma(e, r, 1.0 / 6.0); e = __builtin_fma(e, r, 0.5);
@@ -494,6 +496,39 @@ __global__ __launch_bounds__(256) void k_svm_prep(const double *__restrict__ x, 
     }
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) xnorm[v] = s;
+}
+
+// 8-bit numerators q[n][dim] handed in (API entry str_er_svm_predict_probability_q8) -> the rows k_ocr_features writes for a box: x8 / x8s (models with
+// SvmDev::sv8) or xq / xnorm.  One wave per vector, with k_ocr_features's epilogue restated for any dim up to 33025 (the int32 sum of squares, 255^2 a
+// feature; the same limit as the loader's svm_sv_bytes): the same lane-strided f64 sum of (v / 255)^2 and
+// butterfly (for dim = 1800 the same additions in the same order, so that a box's vector scored from its q bytes gives the box's result bit for bit), the
+// same padding (x8: 0x80 = numerator 0; xq: 0).
+__global__ __launch_bounds__(256) void k_svm_prep_q8(const uint8_t *__restrict__ q, int n, int dim, uint16_t *__restrict__ xq, double *__restrict__ xnorm, int dq,
+                                                     uint8_t *__restrict__ x8, int32_t *__restrict__ x8s, int dq8)
+{
+    const int bi = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (bi >= n) return;
+    double nrm = 0;
+    int    s1 = 0, s2 = 0;
+    for (int i = lane; i < dim; i += 64) {
+        const int v = q[(size_t)bi * dim + i];
+        if (xq) {
+            const double d = v / 255.0;
+            xq[(size_t)bi * dq + i] = (uint16_t)(__float_as_uint((float)v) >> 16);
+            nrm += d * d;
+        }
+        if (x8) { x8[(size_t)bi * dq8 + i] = (uint8_t)(v ^ 0x80); s1 += v; s2 += v * v; }
+    }
+    if (x8) {
+        for (int i = dim + lane; i < dq8; i += 64) x8[(size_t)bi * dq8 + i] = 0x80;
+        for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+        if (lane == 0) { x8s[2 * (size_t)bi] = s1; x8s[2 * (size_t)bi + 1] = s2; }
+    }
+    if (xq) {
+        for (int i = dim + lane; i < dq; i += 64) xq[(size_t)bi * dq + i] = 0;
+        for (int o = 32; o > 0; o >>= 1) nrm += __shfl_xor(nrm, o);
+        if (lane == 0) xnorm[bi] = nrm;
+    }
 }
 
 // K = exp(-gamma (|x|^2 + |sv|^2 - 2 x.sv)).  Workgroup tile 128 (vectors) x 64 (support vectors), four waves, each a 64 x 32
@@ -882,8 +917,8 @@ __global__ __launch_bounds__(64 * svm_couple_wpb(MODE)) SVM_COUPLE_OCC void k_sv
     // ---- decision values, r_ij = sigmoid_predict(dec, A, B) clamped to [1e-7, 1 - 1e-7] (src/svm.cpp:2603-2611)
     const double min_prob = 1e-7;
     // sigmoid_predict (src/svm.cpp:1818-1826): exp(-f) / (1 + exp(-f)) for f >= 0, 1 / (1 + exp(f)) otherwise -- one exp of -|f| and one reciprocal serve
-    // both.  exp on (-inf, 0] without the library's range cases: 2^n e^r, |r| <= ln 2 / 2, degree-11 Taylor (3e-17 relative), below e^-40 the result is
-    // under the 1e-7 clamp whatever it is.  1 ulp here and in the reciprocal; the table entry is an f32.
+    // both.  exp on (-inf, 0] without the library's range cases: 2^n e^r, |r| <= ln 2 / 2, degree-11 Taylor (truncation up to 8.6e-15 relative at the
+    // ends of the range -- far below the f32 the entry is stored as, 6e-8), below e^-40 the result is under the 1e-7 clamp whatever it is.
     auto pair_prob = [min_prob](double fApB) -> double {
         const double x = fmax(-fabs(fApB), -40.0), nn = __builtin_rint(x * 1.4426950408889634);
         double       r = __builtin_fma(nn, -6.93147180369123816490e-01, x);
@@ -1310,6 +1345,13 @@ void launch_svm_prep(hipStream_t s, const double *x, int n, int dim, const OcrBu
 {
     if (n <= 0) return;
     hipLaunchKernelGGL(k_svm_prep, dim3((n + 3) / 4), dim3(256), 0, s, x, n, dim, buf.xf, m.dpad, buf.xnorm);
+}
+
+void launch_svm_prep_q8(hipStream_t s, const uint8_t *q, int n, int dim, const OcrBuf &buf, const SvmDev &m)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_svm_prep_q8, dim3((n + 3) / 4), dim3(256), 0, s, q, n, dim, !buf.x8 ? buf.xq : (uint16_t *)nullptr, buf.xnorm, m.dq, buf.x8,
+                       buf.x8s, m.dq8);
 }
 
 void launch_svm_kernel(hipStream_t s, int n, const OcrBuf &buf, const SvmDev &m, bool numerators)
