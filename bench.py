@@ -2,7 +2,7 @@
 """bench.py -- frames/sec of the ER hot path (extract + NMS + 2-stage classify) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-gpu F] [--size 1080p|4k]
-                    [--workload pyr3x8|native6|pyr3x12] [--kind text|noise|ties] [--no-cpu-baseline] ...
+                    [--workload pyr3x8|native6|pyr3x12] [--kind text|noise|ties] [--full [--no-cpu-baseline] ...]
 
 A "step" is one pass of the hot path over one batch of F synthetic BGR frames per GPU that are ALREADY
 RESIDENT IN HBM: compute_channels (+ pyramid) -> per-plane component tree -> NMS -> LBP + strong/weak
@@ -25,7 +25,11 @@ Workloads (BASELINE.json `configs`):
             native resolution (6 planes, 12.44 Mpx/frame; src/ER.cpp:114-128)
   pyr3x12 : configs[4]: 3840x2160, {Y,Cr,Cb} x 12 pyramid levels (36 planes, 49.75 Mpx/frame); --size 4k
 
-Extra objects on the JSON line (single-GPU default run):
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline and `config`, plus what the
+timed region itself counted (`nms_ties`, `config.host_cpus_busy`).  Everything else -- the per-kernel-group times and rooflines, which take
+runs of their own, the legs below and the CPU baseline -- is measured only with --full (each leg can still be left out with its --no-* option).
+
+Extra objects on the JSON line of a --full run (single-GPU default run):
   roofline         : HBM roofline of the dominant kernel (k_tile_tree): algorithmic bytes per launch over its ISOLATED
                      launch duration (HIP events recorded by the library on the stream the kernel runs on, one batch in
                      flight, mean of 3 launches after the timed region).
@@ -351,21 +355,24 @@ def main():
                          "makes an NMS sibling tie whose outcome changes the pool (--ties-every 8: 1.2 %% of the planes need the reference's flood "
                          "order walked, 3: 3.1 %%)")
     ap.add_argument("--ties-every", type=int, default=8, help="S-ties: one tie glyph in every N-th frame")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline: per-kernel-group times and rooflines, the legs and the CPU "
+                         "baseline (the objects the module docstring lists); a plain run times the steps and prints the line")
     ap.add_argument("--no-ties-leg", action="store_true",
-                    help="skip the `nms_ties_leg` object of the default run (the same measurement as `value`, on S-ties frames, fewer steps)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="skip the `nms_ties_leg` object of a --full run (the same measurement as `value`, on S-ties frames, fewer steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the `cpu_baseline` objects of a --full run")
     ap.add_argument("--group", action="store_true",
                     help="also run the rest of text_detect: calc_color + er_track + er_grouping(inner_sup) (SURVEY 8(f) rows 1-2)")
     ap.add_argument("--no-host-frames", action="store_true",
-                    help="skip the PCIe-inclusive leg (`pcie_inclusive`: frames start in page-locked host memory and go through the "
+                    help="skip the PCIe-inclusive leg of a --full run (`pcie_inclusive`: frames start in page-locked host memory and go through the "
                          "ingest stream str_er_stream_*, uploads overlapping compute); it is never the reported `value`")
     ap.add_argument("--sibling-order", type=int, default=0, help="developer knob: 0 = exact NMS ties (default), 2 = largest-key rule (no flood order walk)")
-    ap.add_argument("--no-latency", action="store_true", help="skip the 1-frame-per-call latency leg (`latency_1frame`)")
+    ap.add_argument("--no-latency", action="store_true", help="skip the 1-frame-per-call latency leg of a --full run (`latency_1frame`)")
     ap.add_argument("--ocr", action="store_true",
                     help="BASELINE configs[2] as the MAIN timed region: also run the chain-code + SVM character scorer on every strong/weak ER "
                          "(synthetic stand-in for the missing classifier/OCR.model: scene-text-recognition_amd/data/ocr_synth120.model.gz)")
-    ap.add_argument("--no-ocr-legs", action="store_true", help="skip `config3_ocr_leg` / `group_ocr_leg` of the default run")
-    ap.add_argument("--no-4k-leg", action="store_true", help="skip `config5_4k_leg` of the default run")
+    ap.add_argument("--no-ocr-legs", action="store_true", help="skip `config3_ocr_leg` / `group_ocr_leg` of a --full run")
+    ap.add_argument("--no-4k-leg", action="store_true", help="skip `config5_4k_leg` of a --full run")
     ap.add_argument("--batch-slots", type=int, default=5,
                     help="str_er_set_batch_slots: at most this many batches have their kernels on the GPU at a time (0: no limit).  Equal batches that share the GPU "
                          "evenly finish together and then wait together for their host side (the flood order walk of an NMS tie) with the GPU idle: with 48-frame "
@@ -461,16 +468,18 @@ def main():
     P = max(1, args.pipelines)
     tmp = tempfile.mkdtemp()
     cascades = S.cascade_io.write_golden(tmp)
+    single = world == 1 and rank == 0
+    ocr_legs = args.full and single and not args.no_ocr_legs and not args.ocr and not args.group and args.kind == "text" and args.size == "1080p" and args.workload == "pyr3x8"
     # config 3's SVM: the stand-in at the reference's training-set size (120 samples per class, src/utils.cpp:1478-1541: 4299 support vectors); the small one of
     # rounds 1-5 (5 per class, 319 support vectors) is timed beside it
-    svm_text_small = gzip.open(S.cascade_io.ocr_model_path(5)).read()
-    svm_text = gzip.open(S.cascade_io.ocr_model_path(120)).read()
-    svm_path = os.path.join(tmp, "ocr_synth.model")
-    with open(svm_path, "wb") as fh:
-        fh.write(svm_text)
-    single = world == 1 and rank == 0
-    ocr_legs = single and not args.no_ocr_legs and not args.ocr and not args.group and args.kind == "text" and args.size == "1080p" and args.workload == "pyr3x8"
-    rig = Rig(S, P, W, H, F, cfg, dev_index, args.sibling_order, cascades, svm_text if (args.ocr or ocr_legs) else None)
+    svm_text_small = svm_text = svm_path = None
+    if args.ocr or ocr_legs:
+        svm_text_small = gzip.open(S.cascade_io.ocr_model_path(5)).read()
+        svm_text = gzip.open(S.cascade_io.ocr_model_path(120)).read()
+        svm_path = os.path.join(tmp, "ocr_synth.model")
+        with open(svm_path, "wb") as fh:
+            fh.write(svm_text)
+    rig = Rig(S, P, W, H, F, cfg, dev_index, args.sibling_order, cascades, svm_text)
     # --ocr alone scores every strong/weak ER (slope 0); with --group the scorer runs where er_ocr runs it: on the members of the text lines
     st_group = S.STAGE_TRACK | S.STAGE_GROUP | S.GROUP_INNER_SUP
     stages = S.STAGE_ALL | (st_group if args.group else 0)
@@ -537,10 +546,11 @@ def main():
 
     # per-kernel-group GPU times come from runs of their own with the library's per-group events on (str_er_set_profiling): one context alone, and --
     # a short region -- all of them busy; the timed regions run without those events
-    serial_prof, _ = rig.serial_profile(d_frames, stages)
-    prof_ov = rig.overlapped_profile(d_frames, stages, 2 * P) if world == 1 else {}
-    r_tree_stats = rig.filters[0].last_tree_stats()
-    r_tile2 = {**rig.filters[0].tile2_stats(), "note": "tiles of the chroma planes given to k_tile_tree2 by this context so far, and how many it handed back to k_tile_tree"}
+    if args.full:
+        serial_prof, _ = rig.serial_profile(d_frames, stages)
+        prof_ov = rig.overlapped_profile(d_frames, stages, 2 * P) if world == 1 else {}
+        r_tree_stats = rig.filters[0].last_tree_stats()
+        r_tile2 = {**rig.filters[0].tile2_stats(), "note": "tiles of the chroma planes given to k_tile_tree2 by this context so far, and how many it handed back to k_tile_tree"}
 
     # ---- config 3: the OCR scorer on every strong / weak ER of the same batches; then the reference's own call pattern (lines first)
     ocr_leg = group_ocr_leg = None
@@ -610,7 +620,7 @@ def main():
 
     # ties leg: the same measurement on tie-rich frames (S-ties), so that the cost of exactness is on the line
     ties_leg = None
-    if not args.no_ties_leg and args.kind == "text" and world == 1 and args.sibling_order == 0 and not args.ocr and not args.group:
+    if args.full and not args.no_ties_leg and args.kind == "text" and world == 1 and args.sibling_order == 0 and not args.ocr and not args.group:
         tf_ = make_frames(S, "ties", W, H, F, first=0, ties_every=args.ties_every)
         d_ties = torch.from_numpy(tf_).to(device)
         torch.cuda.synchronize()
@@ -662,7 +672,7 @@ def main():
 
     latency = None
     rig.close()
-    if not args.no_latency and rank == 0:
+    if args.full and not args.no_latency and rank == 0:
         latency = latency_leg(W, H, cfg, frames, d_frames, stages, args.ocr)
         if ocr_legs and not args.ocr:
             # ... and with the config-3 scorer behind classify (the host reads the plane counters in between: one more round trip than the plain call)
@@ -670,7 +680,7 @@ def main():
             latency["with_stage_ocr"] = {k: lo[k] for k in ("ms_per_frame", "frames_per_s", "ms_per_frame_p90")}
 
     pcie = pcie_nv12 = None
-    if not args.no_host_frames and not args.ocr and rank == 0:
+    if args.full and not args.no_host_frames and not args.ocr and rank == 0:
         # "a frame = BGR upload excluded and included (both reported)".  The frames sit in the stream's page-locked
         # staging buffers (where a decoder would put them); every step uploads its 3*W*H*F bytes again.
         from concurrent.futures import ThreadPoolExecutor
@@ -731,7 +741,7 @@ def main():
 
     # ---- config 5 on this one GPU: 3840x2160, 12 levels (the 8-GPU plane / strip sharding of configs[4] is covered by tests; this is the single-GPU rate)
     k4_leg = None
-    if single and not args.no_4k_leg and args.size == "1080p" and args.workload == "pyr3x8" and args.kind == "text" and not args.ocr and not args.group:
+    if args.full and single and not args.no_4k_leg and args.size == "1080p" and args.workload == "pyr3x8" and args.kind == "text" and not args.ocr and not args.group:
         del d_frames
         torch.cuda.empty_cache()
         w4, h4, F4, cfg4 = 3840, 2160, 12, WORKLOADS["pyr3x12"]
@@ -774,31 +784,6 @@ def main():
         fps = total_frames / elapsed
         px = plane_pixels(args.workload)
         n_pool = len(r.cands)
-        # algorithmic bytes per frame, SURVEY.md 8(d): 3WH (BGR read) + 2*sum(plane px) (each 8-bit
-        # plane written once, read once) + N_pool*(2704+48)
-        b_alg = 3 * W * H + 2 * px + (n_pool / F) * (2704 + 48)
-        # dominant kernel: k_tile_tree reads every plane pixel once -> px bytes per frame.  Its duration is the ISOLATED one
-        # (one batch in flight, HIP events on the library's stream around the launch): with P batches sharing the GPU an
-        # event-to-event time also contains the other batches' kernels and is not a per-launch cost.
-        tile_ms_overlapped = prof_ov.get("tile_tree", 0.0) + prof_ov.get("tile_tree2", 0.0)
-        tile_ms = (serial_prof.get("tile_tree", 0.0) + serial_prof.get("tile_tree2", 0.0)) or tile_ms_overlapped
-        chans = [i for i in range(6) if cfg["channel_mask"] >> i & 1]
-        roof = tile_roofline(px, F, tile_ms, tile_ms_overlapped, args.workload, serial_prof.get("tile_tree2", 0.0), sum(1 for ch in chans if ch % 3) / max(len(chans), 1))
-        roof["tile2"] = r_tile2
-        roof["path_bytes_per_frame"] = int(b_alg)
-        roof["path_frac"] = round(b_alg * fps / world / (HBM_PEAK_GBS * 1e9), 5)
-        # the other passes of the component tree, priced the same way: algorithmic bytes = what the pass has to read and write once
-        # (32-byte node records + their 4-byte counters, two 16-bit seam entries per pixel pair across a tile border) over the pass's isolated time
-        ts = r_tree_stats
-        tree_bytes = {"group": 2 * 36 * ts["records"], "seam": 4 * ts["seam_pairs"], "resolve": 2 * 36 * ts["records"], "accumulate": 2 * 36 * ts["records"]}
-        tree_roof = {}
-        for k, nb in tree_bytes.items():
-            ms_k = serial_prof.get(k, 0.0)
-            if ms_k > 0:
-                gbs = nb / (ms_k * 1e-3) / 1e9
-                tree_roof[k] = {"ms": round(ms_k, 4), "bytes": int(nb), "achieved": round(gbs, 2), "frac": round(gbs / HBM_PEAK_GBS, 5)}
-        tree_roof["note"] = (f"k_group_merge / k_seam / k_resolve / k_reduce of one batch ({ts['records']} exported node records, {ts['seam_pairs']} border pixel pairs, "
-                             f"{ts['tiles']} tiles): isolated times as for k_tile_tree; bound by LDS / device-scope atomic latency, not by HBM (DESIGN 3.2)")
         out = {
             "metric": f"frames/sec (ER extract + 2-stage classify), {W}x{H}",
             "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -816,20 +801,48 @@ def main():
                        "workspace_bytes_per_batch_in_flight": ws_bytes, "nms_sibling_ties": "exact (reference flood order)" if args.sibling_order == 0 else "key rule",
                        **({"gather": "RCCL through the C ABI (str_er_gather_last)" if comm is not None else "torch.distributed all_gather"} if world > 1 else {})},
             "nms_ties": nms_ties,
-            **({"config3_ocr_leg": ocr_leg} if ocr_leg else {}),
-            **({"group_ocr_leg": group_ocr_leg} if group_ocr_leg else {}),
-            **({"config5_4k_leg": k4_leg} if k4_leg else {}),
-            **({"nms_ties_leg": ties_leg} if ties_leg else {}),
-            **({"pcie_inclusive": pcie} if pcie else {}),
-            **({"pcie_inclusive_nv12": pcie_nv12} if pcie_nv12 else {}),
-            **({"latency_1frame": latency} if latency else {}),
-            "roofline": roof,
-            "tree_passes_roofline": tree_roof,
-            "gpu_ms_per_step_by_kernel_group": {k: round(v, 4) for k, v in prof_ov.items()},
-            "gpu_ms_per_step_by_kernel_group_serial": {k: round(v, 4) for k, v in serial_prof.items()},
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(args.kind, args.workload, cascades, ocr_model=svm_path if args.ocr and not args.group else None)
+        if args.full:
+            # algorithmic bytes per frame, SURVEY.md 8(d): 3WH (BGR read) + 2*sum(plane px) (each 8-bit
+            # plane written once, read once) + N_pool*(2704+48)
+            b_alg = 3 * W * H + 2 * px + (n_pool / F) * (2704 + 48)
+            # dominant kernel: k_tile_tree reads every plane pixel once -> px bytes per frame.  Its duration is the ISOLATED one
+            # (one batch in flight, HIP events on the library's stream around the launch): with P batches sharing the GPU an
+            # event-to-event time also contains the other batches' kernels and is not a per-launch cost.
+            tile_ms_overlapped = prof_ov.get("tile_tree", 0.0) + prof_ov.get("tile_tree2", 0.0)
+            tile_ms = (serial_prof.get("tile_tree", 0.0) + serial_prof.get("tile_tree2", 0.0)) or tile_ms_overlapped
+            chans = [i for i in range(6) if cfg["channel_mask"] >> i & 1]
+            roof = tile_roofline(px, F, tile_ms, tile_ms_overlapped, args.workload, serial_prof.get("tile_tree2", 0.0), sum(1 for ch in chans if ch % 3) / max(len(chans), 1))
+            roof["tile2"] = r_tile2
+            roof["path_bytes_per_frame"] = int(b_alg)
+            roof["path_frac"] = round(b_alg * fps / world / (HBM_PEAK_GBS * 1e9), 5)
+            # the other passes of the component tree, priced the same way: algorithmic bytes = what the pass has to read and write once
+            # (32-byte node records + their 4-byte counters, two 16-bit seam entries per pixel pair across a tile border) over the pass's isolated time
+            ts = r_tree_stats
+            tree_bytes = {"group": 2 * 36 * ts["records"], "seam": 4 * ts["seam_pairs"], "resolve": 2 * 36 * ts["records"], "accumulate": 2 * 36 * ts["records"]}
+            tree_roof = {}
+            for k, nb in tree_bytes.items():
+                ms_k = serial_prof.get(k, 0.0)
+                if ms_k > 0:
+                    gbs = nb / (ms_k * 1e-3) / 1e9
+                    tree_roof[k] = {"ms": round(ms_k, 4), "bytes": int(nb), "achieved": round(gbs, 2), "frac": round(gbs / HBM_PEAK_GBS, 5)}
+            tree_roof["note"] = (f"k_group_merge / k_seam / k_resolve / k_reduce of one batch ({ts['records']} exported node records, {ts['seam_pairs']} border pixel pairs, "
+                                 f"{ts['tiles']} tiles): isolated times as for k_tile_tree; bound by LDS / device-scope atomic latency, not by HBM (DESIGN 3.2)")
+            out.update({
+                **({"config3_ocr_leg": ocr_leg} if ocr_leg else {}),
+                **({"group_ocr_leg": group_ocr_leg} if group_ocr_leg else {}),
+                **({"config5_4k_leg": k4_leg} if k4_leg else {}),
+                **({"nms_ties_leg": ties_leg} if ties_leg else {}),
+                **({"pcie_inclusive": pcie} if pcie else {}),
+                **({"pcie_inclusive_nv12": pcie_nv12} if pcie_nv12 else {}),
+                **({"latency_1frame": latency} if latency else {}),
+                "roofline": roof,
+                "tree_passes_roofline": tree_roof,
+                "gpu_ms_per_step_by_kernel_group": {k: round(v, 4) for k, v in prof_ov.items()},
+                "gpu_ms_per_step_by_kernel_group_serial": {k: round(v, 4) for k, v in serial_prof.items()},
+            })
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(args.kind, args.workload, cascades, ocr_model=svm_path if args.ocr and not args.group else None)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -1,5 +1,5 @@
 """bench.py --dump-outputs: the arrays of the timed path's last step as float64 .npy files, a seeded sample of the rows above the size limit;
-and --steps as the number of timed steps."""
+--steps as the number of timed steps; and what a plain run and a --full run put on the line."""
 import importlib.util
 import json
 import os
@@ -95,3 +95,28 @@ def test_bench_dump_is_what_the_timed_path_returns(S, cascade_paths, tmp_path):
                 assert not p.exists()
                 continue
             assert np.array_equal(np.load(p), a[fld].astype(np.float64)), (name, fld)
+
+
+HEADLINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+                 "repeats", "value_min", "value_max", "config", "nms_ties"}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("full", [False, True])
+def test_bench_line_plain_and_full(full):
+    """A plain run measures nothing beyond its timed steps -- no leg runs although none is switched off; --full adds the per-kernel-group
+    times, the rooflines and the legs that are not switched off (here the S-ties leg and the latency leg)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames-per-gpu", "2", "--pipelines", "1"]
+    if full:
+        cmd += ["--full", "--no-cpu-baseline", "--no-host-frames", "--no-ocr-legs", "--no-4k-leg"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    extra = {"nms_ties_leg", "latency_1frame", "roofline", "tree_passes_roofline", "gpu_ms_per_step_by_kernel_group",
+             "gpu_ms_per_step_by_kernel_group_serial"} if full else set()
+    assert set(d) == HEADLINE_KEYS | extra
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    if full:
+        assert d["roofline"]["avg_launch_ms"] > 0 and d["gpu_ms_per_step_by_kernel_group_serial"]

@@ -24,8 +24,8 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_4k -o s -- py
 bash $ROOT/tools/dev_ocr_pmc.sh profiles_$TAG/pmc_config3 > /dev/null 2>&1
 bash $ROOT/tools/dev_lat.sh profiles_$TAG/latency > /dev/null 2>&1
 cd /tmp
-python $ROOT/bench.py > $OUT/bench_${TAG}_pyr3x8_text.json 2> $OUT/bench_err.log
-python $ROOT/bench.py --workload native6 > $OUT/bench_${TAG}_native6_text.json 2>> $OUT/bench_err.log
-python $ROOT/bench.py --workload native6 --kind noise --no-cpu-baseline > $OUT/bench_${TAG}_native6_noise.json 2>> $OUT/bench_err.log
+python $ROOT/bench.py --full > $OUT/bench_${TAG}_pyr3x8_text.json 2> $OUT/bench_err.log
+python $ROOT/bench.py --full --workload native6 > $OUT/bench_${TAG}_native6_text.json 2>> $OUT/bench_err.log
+python $ROOT/bench.py --full --workload native6 --kind noise --no-cpu-baseline > $OUT/bench_${TAG}_native6_noise.json 2>> $OUT/bench_err.log
 rm -f $OUT/*/*kernel_trace.csv      # large; the stats and counter files are what we keep
 ls -R $OUT | head -40

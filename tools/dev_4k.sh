@@ -4,7 +4,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd $ROOT
 OUT=$ROOT/gpurun_out/k4; mkdir -p $OUT
 if [ -n "$TESTS" ]; then timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | tail -5 | tee $OUT/pytest.txt; fi
-python bench.py --size 4k --no-cpu-baseline --no-latency --no-host-frames --no-ocr-legs --no-ties-leg 2>/dev/null | tail -1 > $OUT/bench_4k.json
+python bench.py --full --size 4k --no-cpu-baseline --no-latency --no-host-frames --no-ocr-legs --no-ties-leg 2>/dev/null | tail -1 > $OUT/bench_4k.json
 python - <<PY
 import json
 d = json.load(open("$OUT/bench_4k.json"))

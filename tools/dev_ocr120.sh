@@ -4,7 +4,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/ocr120; mkdir -p $OUT
 cd $ROOT
 timeout 900 python -m pytest tests/test_svm.py -x -q -m gpu -k "120 or reference_vectors or other_class" 2>&1 | tail -8 | tee $OUT/pytest.txt
-timeout 1200 python bench.py --steps 20 --no-ties-leg --no-host-frames --no-latency --no-4k-leg --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+timeout 1200 python bench.py --full --steps 20 --no-ties-leg --no-host-frames --no-latency --no-4k-leg --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
 python - <<PY | tee $OUT/summary.txt
 import json
 d = json.loads(open("$OUT/bench.json").read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd $ROOT
 for n in 1 2 1 2; do
   echo "== STR_ER_UPLOAD_STREAMS=$n"
-  STR_ER_UPLOAD_STREAMS=$n timeout 600 python bench.py --steps 20 --no-ties-leg --no-latency --no-ocr-legs --no-4k-leg --no-cpu-baseline 2>/dev/null | python -c "
+  STR_ER_UPLOAD_STREAMS=$n timeout 600 python bench.py --full --steps 20 --no-ties-leg --no-latency --no-ocr-legs --no-4k-leg --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('value',d['value'])
