@@ -75,6 +75,11 @@ extern "C" {
  * that can group honours them; the geometry and the sampling rules are at str_er_line_crop.                                       */
 #define STR_ER_WANT_LINE_CROPS  2048u
 #define STR_ER_WANT_LINE_GLYPHS 4096u
+/* output option: also return the shape and intensity descriptors of every candidate (str_er_result_shapes, str_er_shape), made on
+ * the device from the candidate's mask; the mask words are returned only with STR_ER_WANT_MASKS as well (the masks are made once).
+ * Every str_er_detect_* entry point and every str_er_stream_submit* call honours it; str_er_strip_merge[_ex] rejects it (STR_ER_EINVAL);
+ * a candidate wider than 16384 pixels gives STR_ER_ECAPACITY.                                                                      */
+#define STR_ER_WANT_SHAPES    (8192u)
 
 /* candidate class: which list of text_detect() the ER landed in (src/ER.cpp:516-526) */
 #define STR_ER_CLS_POOL   0   /* pooled by NMS, rejected by both cascades */
@@ -164,6 +169,32 @@ typedef struct str_er_mask {
     uint32_t pixels;
     uint32_t pitch_words;
 } str_er_mask;           /* 16 bytes */
+
+/* The descriptors of one region (STR_ER_WANT_SHAPES, str_er_er_shapes): the Neumann-Matas features of cv::text::ERStat, all exact
+ * integers, defined on the region's mask M (str_er_mask) over its box of w x h pixels; pixels outside the box count as outside M.
+ * P' is the plane the mask was built on: the plane XOR its invert mask, at the candidate's pyramid level (for str_er_er_shapes the
+ * host plane as given).  Layout: pixels 0, perimeter 4, euler 8, hole_pixels 12, crossings 16, hull_area2 24, grey_sum 32,
+ * grey_sum2 40.  How each is computed, one wave per mask, in the epilogue of the mask kernels:
+ *   perimeter    4|M| - 2 (horizontal + vertical pairs of 4-adjacent pixels of M), from popcounts of the bit rows;
+ *   euler        |M| - pairs + 2x2 blocks of M (vertices - edges + faces of the 4-adjacency graph: Gray's bit-quad count
+ *                (Q1 - Q3 + 2 QD) / 4 over the 2x2 windows of the box padded by one ring of zeros);
+ *   hole_pixels  the complement of M in the box, flooded to a fixpoint through 8-neighbours from its pixels on the box border
+ *                (no iteration cap): what the flood does not reach;
+ *   crossings    2 x the runs of the row;
+ *   hull_area2   monotone chains over the leftmost and rightmost pixel of every row (they determine the hull);
+ *   grey_sum(2)  a second read of P' under M.                                                                                   */
+typedef struct str_er_shape {
+    uint32_t pixels;        /* |M| (== str_er_mask.pixels == the node's |C|)                                                        */
+    uint32_t perimeter;     /* unit edges between a pixel of M and a 4-neighbour not in M (hole borders included)                     */
+    int32_t  euler;         /* 4-connected components of M minus holes; a hole = an 8-connected component of the complement
+                               that does not reach outside the box.  M is one 4-component, so holes = 1 - euler                       */
+    uint32_t hole_pixels;   /* pixels of the box not in M with no 8-connected path of non-M pixels to outside the box                  */
+    uint16_t crossings[4];  /* [k] for rows y = floor(j*h/6), j = 1, 3, 5: x in [0, w] with M(x-1, y) != M(x, y)
+                               (= 2 x the runs of the row); [3] = the median of [0..2]                                                   */
+    uint64_t hull_area2;    /* twice the area of the convex hull of the corners of M's pixel squares (an integer)                      */
+    uint64_t grey_sum;      /* sum of P' over M                                                                                        */
+    uint64_t grey_sum2;     /* sum of P'^2 over M                                                                                      */
+} str_er_shape;             /* 48 bytes */
 
 /* The crop of one text line (STR_ER_WANT_LINE_CROPS, str_er_line_crops, str_er_line_crop_geometry).
  * Geometry, all f64 on the host in this order: s = the line's slope (non-finite counts as 0); r = sqrt(1 + s*s); d = (1, s) / r,
@@ -363,6 +394,11 @@ int str_er_classify_boxes(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int3
 int str_er_er_masks(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions,
                     int32_t n, uint32_t *bits, uint64_t cap_words, uint64_t *n_words, uint32_t *pixels);
 
+/* The descriptors (str_er_shape) of n regions of one host plane, at the context's current thresh_step, into out[0 .. n - 1]: the
+ * masks of str_er_er_masks (same regions, same validation and error codes), the plane taken as it is.                          */
+int str_er_er_shapes(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions,
+                     int32_t n, str_er_shape *out);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -539,6 +575,8 @@ const uint8_t *str_er_result_text_alive(const str_er_result *r, int32_t *n);
  * (n_words in total).  NULL unless the flag was given.                                                                    */
 const str_er_mask *str_er_result_masks(const str_er_result *r, int32_t *n);
 const uint32_t    *str_er_result_mask_bits(const str_er_result *r, uint64_t *n_words);
+/* With STR_ER_WANT_SHAPES: one descriptor record per candidate of str_er_result_cands() (same order); NULL and 0 without the flag. */
+const str_er_shape *str_er_result_shapes(const str_er_result *r, int32_t *n);
 /* With STR_ER_WANT_LINE_CROPS: one record per line of str_er_result_texts() (same order), the grey crop bytes they index and, with
  * STR_ER_WANT_LINE_GLYPHS, the glyph crop bytes (same offsets, same size).  NULL without the flag(s).                              */
 const str_er_line_crop *str_er_result_line_crops(const str_er_result *r, int32_t *n);

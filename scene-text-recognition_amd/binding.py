@@ -24,6 +24,11 @@ WANT_MASKS = 1024       # output option: the pixel mask of every candidate (Resu
 MASK_DTYPE = np.dtype([("word_off", "<u8"), ("pixels", "<u4"), ("pitch_words", "<u4")])
 # output options (need STAGE_GROUP): a rectified grey crop of every text line, and with WANT_LINE_GLYPHS too its glyph crop (Result.line_crop)
 WANT_LINE_CROPS, WANT_LINE_GLYPHS = 2048, 4096
+WANT_SHAPES = 8192      # output option: the shape and intensity descriptors of every candidate (Result.shapes)
+# str_er_shape: exact integers over the candidate's mask M (include/str_er.h); ERStat's hole_area_ratio = hole_pixels / pixels,
+# convex_hull_ratio = hull_area2 / (2 * pixels), med_crossings = crossings[3]
+SHAPE_DTYPE = np.dtype([("pixels", "<u4"), ("perimeter", "<u4"), ("euler", "<i4"), ("hole_pixels", "<u4"), ("crossings", "<u2", (4,)),
+                        ("hull_area2", "<u8"), ("grey_sum", "<u8"), ("grey_sum2", "<u8")])
 # str_er_line_crop: crop t = width x height bytes (pitch width) from byte pix_off of the crop bytes (and of the glyph bytes);
 # ax .. vy: the 16.16 sampling geometry (include/str_er.h)
 LINE_CROP_DTYPE = np.dtype([("pix_off", "<u8"), ("width", "<i4"), ("height", "<i4"), ("ax", "<i4"), ("ay", "<i4"),
@@ -46,6 +51,7 @@ PLANE_DTYPE = np.dtype([("frame", "<u4"), ("ch", "u1"), ("pyr", "u1"), ("r0", "u
                         ("n_weak", "<i4"), ("ambiguous", "<i4"), ("root", "<i4")])
 assert NODE_DTYPE.itemsize == 24 and CAND_DTYPE.itemsize == 48 and PLANE_DTYPE.itemsize == 44 and MASK_DTYPE.itemsize == 16
 assert LINE_CROP_DTYPE.itemsize == 40
+assert SHAPE_DTYPE.itemsize == 48
 
 
 def unpack_mask(words: np.ndarray, word_off: int, w: int, h: int) -> np.ndarray:
@@ -217,6 +223,9 @@ def load_library():
     L.str_er_result_mask_bits.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.str_er_result_mask_bits.restype = vp
     L.str_er_er_masks.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.str_er_result_shapes.argtypes = [vp, i32p]
+    L.str_er_result_shapes.restype = vp
+    L.str_er_er_shapes.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp]
     L.str_er_set_min_ocr_prob.argtypes = [vp, C.c_double]
     L.str_er_result_line_crops.argtypes = [vp, i32p]
     L.str_er_result_line_crops.restype = vp
@@ -337,6 +346,7 @@ class Result:
         self.text_alive = None
         self.masks = None          # with WANT_MASKS: MASK_DTYPE per candidate, and the words they index (uint32)
         self.mask_bits = None
+        self.shapes = None         # with WANT_SHAPES: SHAPE_DTYPE per candidate
         self.line_crops = None     # with WANT_LINE_CROPS: LINE_CROP_DTYPE per line of texts, the grey crop bytes and (WANT_LINE_GLYPHS) the glyph bytes
         self.line_crop_pixels = None
         self.line_glyph_pixels = None
@@ -530,6 +540,10 @@ class ERFilter:
                 wp = L.str_er_result_mask_bits(rh, C.byref(nw))
                 res.mask_bits = (np.frombuffer((C.c_char * (4 * nw.value)).from_address(wp), dtype=np.uint32).copy()
                                  if nw.value else np.zeros(0, np.uint32))
+            sp = L.str_er_result_shapes(rh, C.byref(no))
+            if sp:
+                res.shapes = (np.frombuffer((C.c_char * (48 * no.value)).from_address(sp), dtype=SHAPE_DTYPE).copy()
+                              if no.value else np.zeros(0, SHAPE_DTYPE))
             lp2 = L.str_er_result_line_labels(rh, C.byref(no))
             if lp2:
                 k = no.value
@@ -577,7 +591,7 @@ class ERFilter:
 
     # ---- the hot path ---------------------------------------------------------------------------
     def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
-                    want_line_crops=False) -> Result:
+                    want_line_crops=False, want_shapes: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -589,7 +603,7 @@ class ERFilter:
         rh = C.c_void_p()
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) |
-                                             _crop_flags(want_line_crops), C.byref(rh)))
+                                             (WANT_SHAPES if want_shapes else 0) | _crop_flags(want_line_crops), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -708,13 +722,14 @@ class ERFilter:
         return self._collect(rh)
 
     def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
-                         want_line_crops=False) -> Result:
+                         want_line_crops=False, want_shapes: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
-                                 stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) | _crop_flags(want_line_crops))
+                                 stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) | (WANT_SHAPES if want_shapes else 0) |
+                                 _crop_flags(want_line_crops))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -809,6 +824,16 @@ class ERFilter:
             self._check(self.L.str_er_er_masks(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(r), n,
                                                _np_ptr(words), nw.value, C.byref(nw), _np_ptr(pixels)))
         return words[:nw.value], pixels[:n]
+
+    def er_shapes(self, plane: np.ndarray, regions: np.ndarray) -> np.ndarray:
+        """str_er_er_shapes: the descriptors (SHAPE_DTYPE) of the masks er_masks gives for `regions` on one (H, W) uint8 plane."""
+        a = np.ascontiguousarray(plane, dtype=np.uint8)
+        r = np.ascontiguousarray(regions, dtype=CAND_DTYPE).reshape(-1)
+        n = len(r)
+        out = np.zeros(max(1, n), SHAPE_DTYPE)
+        self._check(self.L.str_er_er_shapes(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(r) if n else None, n,
+                                            _np_ptr(out)))
+        return out[:n]
 
     def set_line_crop(self, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> None:
         """str_er_set_line_crop: the crop height (8..256), the widest crop (1..8192) and the pad (0..1, of the line's height) of

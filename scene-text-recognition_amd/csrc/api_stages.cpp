@@ -312,13 +312,14 @@ try {
 
 namespace str_er_host {
 
-// (o_pix / o_bits: where the popcounts and the words of n jobs sit in c->d_mask, behind the jobs)
-static void mask_offsets(size_t n, uint64_t n_words, size_t &o_pix, size_t &o_bits, size_t &need)
+// (o_pix / o_shape / o_bits: where the popcounts, the ShapeRecs (with shapes) and the words of n jobs sit in c->d_mask, behind the jobs)
+static void mask_offsets(size_t n, uint64_t n_words, bool shapes, size_t &o_pix, size_t &o_shape, size_t &o_bits, size_t &need)
 {
-    o_pix = align_up(sizeof(MaskJob) * n, 256); o_bits = align_up(o_pix + 4 * n, 256); need = o_bits + 4 * (size_t)n_words;
+    o_pix = align_up(sizeof(MaskJob) * n, 256); o_shape = align_up(o_pix + 4 * n, 256);
+    o_bits = align_up(o_shape + (shapes ? sizeof(ShapeRec) * n : 0), 256); need = o_bits + 4 * (size_t)n_words;
 }
 
-int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, const uint32_t **d_bits)
+int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, const uint32_t **d_bits, bool shapes)
 {
     const size_t n = jobs.size();
     if (n == 0) return STR_ER_OK;
@@ -328,8 +329,8 @@ int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64
     std::stable_sort(jobs.begin(), jobs.end(), [](const MaskJob &a, const MaskJob &b) { return mask_class(a.w, a.h) < mask_class(b.w, b.h); });
     size_t scratch = 0;
     for (MaskJob &j : jobs) { j.scratch_off = scratch; scratch += mask_scratch_words(j.w, j.h); }
-    size_t o_pix, o_bits, need;
-    mask_offsets(n, n_words, o_pix, o_bits, need);
+    size_t o_pix, o_shape, o_bits, need;
+    mask_offsets(n, n_words, shapes, o_pix, o_shape, o_bits, need);
     if (need > c->mask_bytes) {
         const size_t get = std::max(need, 2 * c->mask_bytes);
         if (c->d_mask) { (void)hipFree(c->d_mask); c->d_mask = nullptr; }
@@ -353,40 +354,37 @@ int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64
     std::memcpy(c->h_mask, jobs.data(), sizeof(MaskJob) * n);
     HIP_TRY(c, hipMemcpyAsync(c->d_mask, c->h_mask, sizeof(MaskJob) * n, hipMemcpyHostToDevice, s));
     launch_er_masks(s, reinterpret_cast<const MaskJob *>(c->d_mask), n_class, reinterpret_cast<uint32_t *>(c->d_mask + o_bits),
-                    reinterpret_cast<uint32_t *>(c->d_mask + o_pix), c->d_mask_scratch, qscale);
+                    reinterpret_cast<uint32_t *>(c->d_mask + o_pix), shapes ? reinterpret_cast<ShapeRec *>(c->d_mask + o_shape) : nullptr,
+                    c->d_mask_scratch, qscale);
     HIP_TRY(c, hipGetLastError());
     if (d_bits) *d_bits = reinterpret_cast<const uint32_t *>(c->d_mask + o_bits);
     return STR_ER_OK;
 }
 
 int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, uint32_t *pixels, uint32_t *bits,
-               const uint32_t **d_bits)
+               const uint32_t **d_bits, str_er_shape *shapes)
 {
     const size_t n = jobs.size();
     if (n == 0) return STR_ER_OK;
-    const int rc = mask_launch(c, s, jobs, n_words, qscale, d_bits);
+    const int rc = mask_launch(c, s, jobs, n_words, qscale, d_bits, shapes != nullptr);
     if (rc != STR_ER_OK) return rc;
-    size_t o_pix, o_bits, need;
-    mask_offsets(n, n_words, o_pix, o_bits, need);
-    HIP_TRY(c, hipMemcpyAsync(c->h_mask + o_pix, c->d_mask + o_pix, need - o_pix, hipMemcpyDeviceToHost, s));
+    size_t o_pix, o_shape, o_bits, need;
+    mask_offsets(n, n_words, shapes != nullptr, o_pix, o_shape, o_bits, need);
+    HIP_TRY(c, hipMemcpyAsync(c->h_mask + o_pix, c->d_mask + o_pix, (bits ? need : o_bits) - o_pix, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
     std::memcpy(pixels, c->h_mask + o_pix, 4 * n);
-    if (n_words) std::memcpy(bits, c->h_mask + o_bits, 4 * (size_t)n_words);
+    if (shapes) std::memcpy(shapes, c->h_mask + o_shape, sizeof(ShapeRec) * n);
+    if (bits && n_words) std::memcpy(bits, c->h_mask + o_bits, 4 * (size_t)n_words);
     return STR_ER_OK;
 }
 
-} // namespace str_er_host
-
-extern "C" {
-
-int str_er_er_masks(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions, int32_t n,
-                    uint32_t *bits, uint64_t cap_words, uint64_t *n_words, uint32_t *pixels)
-try {
-    if (!c) return STR_ER_EINVAL;
-    if (!plane || w < 1 || h < 1 || stride < w || n < 0 || (n > 0 && !regions) || !n_words) return fail(c, STR_ER_EINVAL, "bad arguments");
-    const DetectParams dp = make_dp(c);
-    std::vector<MaskJob> jobs((size_t)n);
-    uint64_t words = 0;
+// the jobs of n regions of one host plane (str_er_er_masks, str_er_er_shapes), validated, and the words their masks take
+static int region_jobs(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions, int32_t n,
+                       const DetectParams &dp, std::vector<MaskJob> &jobs, uint64_t &words)
+{
+    if (!plane || w < 1 || h < 1 || stride < w || n < 0 || (n > 0 && !regions)) return fail(c, STR_ER_EINVAL, "bad arguments");
+    jobs.resize((size_t)n);
+    words = 0;
     for (int i = 0; i < n; ++i) {
         const str_er_cand &g = regions[i];
         const std::string  who = "region " + std::to_string(i) + ": ";
@@ -403,18 +401,57 @@ try {
         j.x = g.x; j.y = g.y; j.w = g.w; j.h = g.h; j.level = g.level; j.idx = (uint32_t)i; j.out_off = words; j.scratch_off = 0;
         words += (uint64_t)g.h * ((g.w + 31u) / 32u);
     }
-    *n_words = words;
-    if (!bits || n == 0) return STR_ER_OK;
-    if (words > cap_words) return fail(c, STR_ER_ECAPACITY, "the masks need " + std::to_string(words) + " words, cap_words is " + std::to_string(cap_words));
+    return STR_ER_OK;
+}
+
+// the plane of region_jobs on the device (the context's input buffer), the jobs pointed at it
+static int region_upload(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, std::vector<MaskJob> &jobs)
+{
     HIP_TRY(c, hipSetDevice(c->prm.device));
     if ((size_t)w * (size_t)h > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane larger than the context capacity");
     HIP_TRY(c, hipMemcpy2DAsync(c->d_pix, (size_t)w, plane, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, c->stream));
     for (MaskJob &j : jobs) j.pix = c->d_pix;
+    return STR_ER_OK;
+}
+
+} // namespace str_er_host
+
+extern "C" {
+
+int str_er_er_masks(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions, int32_t n,
+                    uint32_t *bits, uint64_t cap_words, uint64_t *n_words, uint32_t *pixels)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (!n_words) return fail(c, STR_ER_EINVAL, "bad arguments");
+    const DetectParams dp = make_dp(c);
+    std::vector<MaskJob> jobs;
+    uint64_t words = 0;
+    int rc = region_jobs(c, plane, w, h, stride, regions, n, dp, jobs, words);
+    if (rc != STR_ER_OK) return rc;
+    *n_words = words;
+    if (!bits || n == 0) return STR_ER_OK;
+    if (words > cap_words) return fail(c, STR_ER_ECAPACITY, "the masks need " + std::to_string(words) + " words, cap_words is " + std::to_string(cap_words));
+    if ((rc = region_upload(c, plane, w, h, stride, jobs)) != STR_ER_OK) return rc;
     std::vector<uint32_t> px((size_t)n);
-    const int rc = mask_stage(c, c->stream, jobs, words, dp.qscale, px.data(), bits);
+    rc = mask_stage(c, c->stream, jobs, words, dp.qscale, px.data(), bits);
     if (rc != STR_ER_OK) return rc;
     if (pixels) std::memcpy(pixels, px.data(), 4 * (size_t)n);
     return STR_ER_OK;
+} ABI_GUARD(c)
+
+int str_er_er_shapes(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions, int32_t n,
+                     str_er_shape *out)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (n > 0 && !out) return fail(c, STR_ER_EINVAL, "bad arguments");
+    const DetectParams dp = make_dp(c);
+    std::vector<MaskJob> jobs;
+    uint64_t words = 0;
+    int rc = region_jobs(c, plane, w, h, stride, regions, n, dp, jobs, words);
+    if (rc != STR_ER_OK || n == 0) return rc;
+    if ((rc = region_upload(c, plane, w, h, stride, jobs)) != STR_ER_OK) return rc;
+    std::vector<uint32_t> px((size_t)n);
+    return mask_stage(c, c->stream, jobs, words, dp.qscale, px.data(), nullptr, nullptr, out);
 } ABI_GUARD(c)
 
 } // extern "C"

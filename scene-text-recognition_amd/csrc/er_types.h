@@ -203,6 +203,16 @@ struct MaskJob {
 };
 static_assert(sizeof(MaskJob) == 56, "MaskJob layout (host and device)");
 
+// Matches str_er_shape in include/str_er.h (48 bytes): the descriptors of one mask (STR_ER_WANT_SHAPES, str_er_er_shapes).
+struct ShapeRec {
+    uint32_t pixels, perimeter;
+    int32_t  euler;
+    uint32_t hole_pixels;
+    uint16_t crossings[4];
+    uint64_t hull_area2, grey_sum, grey_sum2;
+};
+static_assert(sizeof(ShapeRec) == 48, "ShapeRec must match str_er_shape");
+
 // One line of the crop stage (STR_ER_WANT_LINE_CROPS, str_er_line_crops): the 16.16 sampling geometry of str_er_line_crop over the
 // line's Y plane, and for glyph crops the line's distinct members (GlyphMember[m_first .. m_first + m_count)).
 struct LineCropJob {

@@ -1268,8 +1268,10 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
     }
     r->cand_off[np] = off;
     const uint32_t *d_mask_bits = nullptr;         // (the masks' words on the device, for the glyph crops below)
-    if (stages & STR_ER_WANT_MASKS) {
-        // the masks of the final candidates (after any NMS tie pass): sized on the host from the records just copied, one launch per size class, one wait
+    if (stages & (STR_ER_WANT_MASKS | STR_ER_WANT_SHAPES)) {
+        // the masks of the final candidates (after any NMS tie pass): sized on the host from the records just copied, one launch per size class, one wait;
+        // with STR_ER_WANT_SHAPES the same launches make the descriptors, and without STR_ER_WANT_MASKS the words stay on the device
+        const bool want_masks = (stages & STR_ER_WANT_MASKS) != 0, want_shapes = (stages & STR_ER_WANT_SHAPES) != 0;
         std::vector<MaskJob> jobs(total);
         std::vector<uint32_t> px(total);
         uint64_t words = 0;
@@ -1277,18 +1279,24 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
         for (uint32_t k = 0; k < total; ++k) {
             const str_er_cand &cd = r->cands[k];
             const PlaneDesc   &pd = b.planes[cd.plane];
-            if (cd.w > MASK_MAX_WIDTH) { delete r; return fail(c, STR_ER_ECAPACITY, "STR_ER_WANT_MASKS: a candidate wider than " + std::to_string(MASK_MAX_WIDTH) + " pixels"); }
+            if (cd.w > MASK_MAX_WIDTH) {
+                delete r;
+                return fail(c, STR_ER_ECAPACITY, std::string(want_masks ? "STR_ER_WANT_MASKS" : "STR_ER_WANT_SHAPES") + ": a candidate wider than " + std::to_string(MASK_MAX_WIDTH) + " pixels");
+            }
             MaskJob &j = jobs[k];
             j.pix = pd.pix; j.stride = pd.stride; j.invert = (uint32_t)pd.invert; j.plane_w = (uint32_t)pd.w; j.key = cd.key;
             j.x = cd.x; j.y = cd.y; j.w = cd.w; j.h = cd.h; j.level = cd.level; j.idx = k; j.out_off = words; j.scratch_off = 0;
             r->masks[k].word_off = words; r->masks[k].pitch_words = (cd.w + 31u) / 32u;
             words += (uint64_t)cd.h * r->masks[k].pitch_words;
         }
-        r->mask_bits.resize(words);
-        const int rcm = mask_stage(c, s, jobs, words, dp.qscale, px.data(), r->mask_bits.data(), &d_mask_bits);
+        if (want_masks) r->mask_bits.resize(words);
+        if (want_shapes) r->shapes.resize(total);
+        const int rcm = mask_stage(c, s, jobs, words, dp.qscale, px.data(), want_masks ? r->mask_bits.data() : nullptr, &d_mask_bits,
+                                   want_shapes ? r->shapes.data() : nullptr);
         if (rcm != STR_ER_OK) { delete r; return rcm; }
         for (uint32_t k = 0; k < total; ++k) r->masks[k].pixels = px[k];
-        r->have_masks = true;
+        r->have_masks = want_masks;         // (without it r->masks only places the words on the device, for the glyph crops)
+        r->have_shapes = want_shapes;
     }
     if (stages & STR_ER_WANT_LINE_CROPS) {
         // the crops of the final lines, while the call's planes are still in the workspace: laid out on the host, one launch, one wait
@@ -1993,6 +2001,14 @@ const str_er_mask *str_er_result_masks(const str_er_result *r, int32_t *n)
     if (n) *n = (int32_t)r->masks.size();
     static const str_er_mask none{};
     return r->masks.empty() ? &none : r->masks.data();
+}
+
+const str_er_shape *str_er_result_shapes(const str_er_result *r, int32_t *n)
+{
+    if (!r || !r->have_shapes) { if (n) *n = 0; return nullptr; }
+    if (n) *n = (int32_t)r->shapes.size();
+    static const str_er_shape none{};
+    return r->shapes.empty() ? &none : r->shapes.data();
 }
 
 const uint32_t *str_er_result_mask_bits(const str_er_result *r, uint64_t *n_words)

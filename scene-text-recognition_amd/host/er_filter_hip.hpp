@@ -309,13 +309,7 @@ public:
     std::vector<Mask> er_masks(const Image8 &plane, const ERs &ers)
     {
         if (plane.channels != 1) throw std::runtime_error("er_masks expects an 8UC1 plane");
-        std::vector<str_er_cand> regions(ers.size());
-        for (size_t i = 0; i < ers.size(); ++i) {
-            str_er_cand &c = regions[i];
-            c = str_er_cand{};
-            c.x = (uint16_t)ers[i]->bound.x; c.y = (uint16_t)ers[i]->bound.y; c.w = (uint16_t)ers[i]->bound.width; c.h = (uint16_t)ers[i]->bound.height;
-            c.level = (uint8_t)ers[i]->level; c.key = ers[i]->key;
-        }
+        const std::vector<str_er_cand> regions = regions_of(ers);
         const int32_t n = (int32_t)regions.size();
         uint64_t      n_words = 0;
         check(str_er_er_masks(ctx_.get(), plane.data, plane.cols, plane.rows, plane.step, regions.data(), n, nullptr, 0, &n_words, nullptr));
@@ -333,6 +327,17 @@ public:
                 for (int x = 0; x < w; ++x) m.pixels[(size_t)y * w + x] = (uint8_t)((bits[off + (size_t)y * pitch + (x >> 5)] >> (x & 31)) & 1u);
             off += (uint64_t)pitch * h;
         }
+        return out;
+    }
+
+    // The descriptors of the same masks (str_er_er_shapes): perimeter, Euler number, hole pixels, crossings, convex-hull area and
+    // grey moments, the features of cv::text::ERStat, as exact integers (include/str_er.h, str_er_shape).  The masks stay on the device.
+    std::vector<str_er_shape> er_shapes(const Image8 &plane, const ERs &ers)
+    {
+        if (plane.channels != 1) throw std::runtime_error("er_shapes expects an 8UC1 plane");
+        const std::vector<str_er_cand> regions = regions_of(ers);
+        std::vector<str_er_shape> out(regions.size());
+        check(str_er_er_shapes(ctx_.get(), plane.data, plane.cols, plane.rows, plane.step, regions.data(), (int32_t)regions.size(), out.data()));
         return out;
     }
 
@@ -451,6 +456,18 @@ private:
     void check(int rc) const
     {
         if (rc != STR_ER_OK) throw std::runtime_error(std::string(str_er_strerror(rc)) + ": " + str_er_last_error(ctx_.get()));
+    }
+    // the regions of er_masks / er_shapes: of every ER its bound, level and key
+    static std::vector<str_er_cand> regions_of(const ERs &ers)
+    {
+        std::vector<str_er_cand> regions(ers.size());
+        for (size_t i = 0; i < ers.size(); ++i) {
+            str_er_cand &c = regions[i];
+            c = str_er_cand{};
+            c.x = (uint16_t)ers[i]->bound.x; c.y = (uint16_t)ers[i]->bound.y; c.w = (uint16_t)ers[i]->bound.width; c.h = (uint16_t)ers[i]->bound.height;
+            c.level = (uint8_t)ers[i]->level; c.key = ers[i]->key;
+        }
+        return regions;
     }
     void load(int which, const std::string &file)
     {

@@ -1,13 +1,15 @@
-// example_er_masks.cpp -- the pixels of every ER a frame yields (STR_ER_WANT_MASKS), and for plane 0 the same masks through
-// ERFilter::er_masks, the single-stage form for ERs of a host plane.
+// example_er_masks.cpp -- the pixels of every ER a frame yields (STR_ER_WANT_MASKS) and their descriptors (STR_ER_WANT_SHAPES), and
+// for plane 0 the same masks and descriptors through ERFilter::er_masks / er_shapes, the single-stage forms for ERs of a host plane.
 //
 //   g++ -std=c++17 -O2 example_er_masks.cpp -I../../include -L../lib -lstr_er_hip -o example_er_masks
 //   ./example_er_masks strong.classifier weak.classifier frame.bgr width height
 //
-// frame.bgr is a raw interleaved 8-bit BGR dump.  Prints "mask <candidate> <pixels>" for every candidate of the call, in
-// str_er_result_cands order, then whether the fused and the single-stage masks of plane 0 agree bit for bit.
+// frame.bgr is a raw interleaved 8-bit BGR dump.  Prints "mask <candidate> <pixels>" and "shape <candidate> <perimeter> <euler>
+// <hull_area2>" for every candidate of the call, in str_er_result_cands order, then whether the fused and the single-stage masks
+// and descriptors of plane 0 agree bit for bit.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 
@@ -32,16 +34,19 @@ int main(int argc, char **argv)
         f.set_wtc(argv[2]);
         str_er_result *r = nullptr;
         int rc = str_er_detect_bgr(f.handle(), pix.data(), w, h, 3 * (int64_t)w, 3 * (int64_t)w * h, 1, STR_ER_MEM_HOST,
-                                   STR_ER_STAGE_ALL | STR_ER_WANT_MASKS, &r);
+                                   STR_ER_STAGE_ALL | STR_ER_WANT_MASKS | STR_ER_WANT_SHAPES, &r);
         if (rc != STR_ER_OK) { std::fprintf(stderr, "detect: %s\n", str_er_last_error(f.handle())); return 1; }
         std::unique_ptr<str_er_result, void (*)(str_er_result *)> guard(r, str_er_result_free);
-        int32_t            n = 0, nm = 0, n0 = 0;
+        int32_t            n = 0, nm = 0, ns = 0, n0 = 0;
         uint64_t           n_words = 0;
         const str_er_cand *cands = str_er_result_cands(r, &n);
         const str_er_mask *masks = str_er_result_masks(r, &nm);
         const uint32_t    *bits = str_er_result_mask_bits(r, &n_words);
-        if (!masks || !bits || nm != n) { std::fprintf(stderr, "no masks\n"); return 1; }
+        const str_er_shape *shapes = str_er_result_shapes(r, &ns);
+        if (!masks || !bits || nm != n || !shapes || ns != n) { std::fprintf(stderr, "no masks\n"); return 1; }
         for (int32_t i = 0; i < n; ++i) std::printf("mask %d %u\n", i, masks[i].pixels);
+        for (int32_t i = 0; i < n; ++i)
+            std::printf("shape %d %u %d %llu\n", i, shapes[i].perimeter, shapes[i].euler, (unsigned long long)shapes[i].hull_area2);
         // plane 0 (Y) again, through the single-stage call on the plane compute_channels gives
         std::vector<std::vector<uint8_t>> ch;
         f.compute_channels(Image8(pix.data(), w, h, 3 * (int64_t)w, 3), ch);
@@ -55,8 +60,10 @@ int main(int argc, char **argv)
             list.push_back(&e);
         }
         const std::vector<ERFilter::Mask> single = f.er_masks(Image8(ch[0].data(), w, h, w, 1), list);
+        const std::vector<str_er_shape>   single_shapes = f.er_shapes(Image8(ch[0].data(), w, h, w, 1), list);
         const int32_t first = (int32_t)(c0 - cands);
         bool          same = true;
+        for (int32_t i = 0; i < n0 && same; ++i) same = std::memcmp(&single_shapes[(size_t)i], &shapes[first + i], sizeof(str_er_shape)) == 0;
         for (int32_t i = 0; i < n0 && same; ++i) {
             const str_er_mask &m = masks[first + i];
             const ERFilter::Mask &s = single[(size_t)i];
