@@ -80,6 +80,22 @@ extern "C" {
  * Every str_er_detect_* entry point and every str_er_stream_submit* call honours it; str_er_strip_merge[_ex] rejects it (STR_ER_EINVAL);
  * a candidate wider than 16384 pixels gives STR_ER_ECAPACITY.                                                                      */
 #define STR_ER_WANT_SHAPES    (8192u)
+/* output options: frame-resolution maps of where the detected text is (str_er_result_frame_maps, str_er_frame_map).
+ * _TEXT_MAP: one uint8 map per frame, at the frame's own (level-0) size, bits STR_ER_TEXT_MAP_* of every region that covers the
+ * pixel; needs STR_ER_STAGE_CLASSIFY.  _LINE_MAP: one int32 map per frame, the smallest index into str_er_result_texts() of a line
+ * with a member that covers the pixel, -1 where none does; needs STR_ER_STAGE_GROUP.  STR_ER_EINVAL otherwise, the context usable.
+ * The two are independent of each other and of the other output options.  str_er_detect_bgr, _nv12, _bgr_list, _nv12_list,
+ * _bgr_planes (the selected planes contribute) and every str_er_stream_submit* call honour them; str_er_detect_planes[_list] and
+ * str_er_strip_merge[_ex] have no frames and reject them (STR_ER_EINVAL).  A contributing candidate wider than 16384 pixels gives
+ * STR_ER_ECAPACITY.  The pixel rule and the layout are at str_er_frame_map.                                                      */
+#define STR_ER_WANT_TEXT_MAP  (16384u)   /* one uint8 map per frame, at the frame's own size          */
+#define STR_ER_WANT_LINE_MAP  (32768u)   /* one int32 map per frame: the text line of every pixel     */
+/* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
+#define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
+#define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
+#define STR_ER_TEXT_MAP_LINE   4u   /* a member of a line of str_er_result_texts() (STR_ER_STAGE_GROUP; never set without it)      */
+#define STR_ER_TEXT_MAP_OCR    8u   /* a member kept by STR_ER_STAGE_OCR_LINES (line_kept = 1) in a line with text_alive = 1,
+                                       for any of its occurrences (never set without the stage)                                   */
 
 /* candidate class: which list of text_detect() the ER landed in (src/ER.cpp:516-526) */
 #define STR_ER_CLS_POOL   0   /* pooled by NMS, rejected by both cascades */
@@ -216,6 +232,20 @@ typedef struct str_er_line_crop {
     int32_t  ax, ay;
     int32_t  ux, uy, vx, vy;
 } str_er_line_crop;      /* 40 bytes */
+
+/* The maps of one frame (STR_ER_WANT_TEXT_MAP / _LINE_MAP, str_er_result_frame_maps).
+ * Pixel rule, exact integers: a region lies on a plane of level size (w_p, h_p) of a frame of level-0 size (W, H); frame pixel
+ * (x, y) samples level pixel xs = ((2x + 1) * w_p) / (2W), ys = ((2y + 1) * h_p) / (2H), both rounded down (the nearest sample of
+ * the pixel centre; the identity at level 0).  The region covers (x, y) if (xs, ys) lies in its box and in its mask (str_er_mask:
+ * the same quantiser, the same 4-flood from key over the candidate's own box).  Every plane of the frame contributes (all channels,
+ * inversions and pyramid levels; only the selected ones for str_er_detect_bgr_planes); pool-only candidates (cls 0) never do.
+ * Layout: frame f's map is height x width elements, row-major, pitch = width, from element `off` of the byte map and of the id map
+ * (the same off for both, counted in elements); frames follow one another, each from a multiple of 4 elements on; the 0..3
+ * elements between two frames are 0 in the byte map and -1 in the id map.                                                        */
+typedef struct str_er_frame_map {
+    uint64_t off;            /* first element of this frame's map in the arrays below; a multiple of 4 */
+    int32_t  width, height;  /* the frame's level-0 size                                            */
+} str_er_frame_map;          /* 16 bytes */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -398,6 +428,15 @@ int str_er_er_masks(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h,
  * masks of str_er_er_masks (same regions, same validation and error codes), the plane taken as it is.                          */
 int str_er_er_shapes(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions,
                      int32_t n, str_er_shape *out);
+
+/* The text map of n regions of one host plane of w x h pixels (the level size) onto an out_w x out_h frame (out_map, out_w * out_h
+ * bytes, pitch out_w), by the pixel rule of str_er_frame_map: every output pixel is the OR of values[i] over the regions that cover
+ * it, and with ids (then out_ids != NULL, out_w * out_h int32) out_ids the smallest ids[i] of them, -1 if none.  Of every region only
+ * x, y, w, h, level and key are read; the masks are those of str_er_er_masks (same validation and error codes), at the context's
+ * current thresh_step, the plane taken as it is.                                                                               */
+int str_er_text_map_regions(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h, int64_t stride,
+                            const str_er_cand *regions, const uint8_t *values, const int32_t *ids /* or NULL */, int32_t n,
+                            int32_t out_w, int32_t out_h, uint8_t *out_map, int32_t *out_ids /* NULL iff ids is NULL */);
 
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
@@ -582,6 +621,12 @@ const str_er_shape *str_er_result_shapes(const str_er_result *r, int32_t *n);
 const str_er_line_crop *str_er_result_line_crops(const str_er_result *r, int32_t *n);
 const uint8_t          *str_er_result_line_crop_pixels(const str_er_result *r, uint64_t *n_bytes);
 const uint8_t          *str_er_result_line_glyph_pixels(const str_er_result *r, uint64_t *n_bytes);
+/* With STR_ER_WANT_TEXT_MAP and / or _LINE_MAP: one record per frame of the call (frame order), and the maps they index (n_bytes
+ * bytes / n int32 in total, padding included; layout at str_er_frame_map).  Each accessor returns NULL and 0 without its flag;
+ * str_er_result_frame_maps returns the records with either flag.                                                                 */
+const str_er_frame_map *str_er_result_frame_maps(const str_er_result *r, int32_t *n);
+const uint8_t          *str_er_result_text_map_pixels(const str_er_result *r, uint64_t *n_bytes);
+const int32_t          *str_er_result_line_map_ids(const str_er_result *r, uint64_t *n);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

@@ -29,6 +29,13 @@ WANT_SHAPES = 8192      # output option: the shape and intensity descriptors of 
 # convex_hull_ratio = hull_area2 / (2 * pixels), med_crossings = crossings[3]
 SHAPE_DTYPE = np.dtype([("pixels", "<u4"), ("perimeter", "<u4"), ("euler", "<i4"), ("hole_pixels", "<u4"), ("crossings", "<u2", (4,)),
                         ("hull_area2", "<u8"), ("grey_sum", "<u8"), ("grey_sum2", "<u8")])
+# output options: frame-resolution maps (Result.text_map / Result.line_map).  WANT_TEXT_MAP (needs STAGE_CLASSIFY): one uint8 map per
+# frame at its own size, the OR of the TEXT_MAP_* bits of every region covering the pixel; WANT_LINE_MAP (needs STAGE_GROUP): one
+# int32 map per frame, the smallest index into texts of a line with a member covering the pixel, -1 where none does
+WANT_TEXT_MAP, WANT_LINE_MAP = 16384, 32768
+TEXT_MAP_STRONG, TEXT_MAP_WEAK, TEXT_MAP_LINE, TEXT_MAP_OCR = 1, 2, 4, 8
+# str_er_frame_map: frame f's maps = height x width elements (pitch width) from element off of the byte map and of the id map
+FRAME_MAP_DTYPE = np.dtype([("off", "<u8"), ("width", "<i4"), ("height", "<i4")])
 # str_er_line_crop: crop t = width x height bytes (pitch width) from byte pix_off of the crop bytes (and of the glyph bytes);
 # ax .. vy: the 16.16 sampling geometry (include/str_er.h)
 LINE_CROP_DTYPE = np.dtype([("pix_off", "<u8"), ("width", "<i4"), ("height", "<i4"), ("ax", "<i4"), ("ay", "<i4"),
@@ -52,6 +59,7 @@ PLANE_DTYPE = np.dtype([("frame", "<u4"), ("ch", "u1"), ("pyr", "u1"), ("r0", "u
 assert NODE_DTYPE.itemsize == 24 and CAND_DTYPE.itemsize == 48 and PLANE_DTYPE.itemsize == 44 and MASK_DTYPE.itemsize == 16
 assert LINE_CROP_DTYPE.itemsize == 40
 assert SHAPE_DTYPE.itemsize == 48
+assert FRAME_MAP_DTYPE.itemsize == 16
 
 
 def unpack_mask(words: np.ndarray, word_off: int, w: int, h: int) -> np.ndarray:
@@ -233,6 +241,12 @@ def load_library():
         fn.argtypes = [vp, C.POINTER(C.c_uint64)]
         fn.restype = vp
     L.str_er_set_line_crop.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
+    L.str_er_result_frame_maps.argtypes = [vp, i32p]
+    L.str_er_result_frame_maps.restype = vp
+    for fn in (L.str_er_result_text_map_pixels, L.str_er_result_line_map_ids):
+        fn.argtypes = [vp, C.POINTER(C.c_uint64)]
+        fn.restype = vp
+    L.str_er_text_map_regions.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
     L.str_er_line_crop_geometry.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, vp]
     L.str_er_line_crops.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, C.c_uint64,
                                     C.POINTER(C.c_uint64), vp]
@@ -350,6 +364,9 @@ class Result:
         self.line_crops = None     # with WANT_LINE_CROPS: LINE_CROP_DTYPE per line of texts, the grey crop bytes and (WANT_LINE_GLYPHS) the glyph bytes
         self.line_crop_pixels = None
         self.line_glyph_pixels = None
+        self.frame_maps = None     # with WANT_TEXT_MAP / WANT_LINE_MAP: FRAME_MAP_DTYPE per frame, and the maps they index (uint8 / int32)
+        self.text_map_pixels = None
+        self.line_map_ids = None
         self._planes = None
 
     @property
@@ -380,6 +397,21 @@ class Result:
         if self.line_crops is not None and self.line_glyph_pixels is None:
             raise ValueError("the result has no glyph crops (pass WANT_LINE_GLYPHS / want_line_crops=\"glyphs\")")
         return self._crop_of(self.line_glyph_pixels, t)
+
+    def _map_of(self, flat, f: int, flag: str) -> np.ndarray:
+        if flat is None:
+            raise ValueError(f"the result has no {flag.lower()[5:]} (pass {flag} / want_{flag.lower()[5:]}=True)")
+        g = self.frame_maps[f]
+        o, w, h = int(g["off"]), int(g["width"]), int(g["height"])
+        return flat[o:o + w * h].reshape(h, w)
+
+    def text_map(self, f: int) -> np.ndarray:
+        """With WANT_TEXT_MAP: the text map of frame f as an (H, W) uint8 array of TEXT_MAP_* bits."""
+        return self._map_of(self.text_map_pixels, f, "WANT_TEXT_MAP")
+
+    def line_map(self, f: int) -> np.ndarray:
+        """With WANT_LINE_MAP: the line-id map of frame f as an (H, W) int32 array (index into texts, -1 for no line)."""
+        return self._map_of(self.line_map_ids, f, "WANT_LINE_MAP")
 
     def line_crop_batch(self, glyphs: bool = False):
         """With WANT_LINE_CROPS: every line's crop (or glyph crop) in one (n, height, max width) uint8 array, zero-padded on the
@@ -532,6 +564,19 @@ class ERFilter:
                     if bp:
                         setattr(res, name, np.frombuffer((C.c_char * nb.value).from_address(bp), dtype=np.uint8).copy()
                                 if nb.value else np.zeros(0, np.uint8))
+            fp = L.str_er_result_frame_maps(rh, C.byref(no))
+            if fp:
+                res.frame_maps = (np.frombuffer((C.c_char * (16 * no.value)).from_address(fp), dtype=FRAME_MAP_DTYPE).copy()
+                                  if no.value else np.zeros(0, FRAME_MAP_DTYPE))
+                nb = C.c_uint64()
+                bp = L.str_er_result_text_map_pixels(rh, C.byref(nb))
+                if bp:
+                    res.text_map_pixels = (np.frombuffer((C.c_char * nb.value).from_address(bp), dtype=np.uint8).copy()
+                                           if nb.value else np.zeros(0, np.uint8))
+                ip = L.str_er_result_line_map_ids(rh, C.byref(nb))
+                if ip:
+                    res.line_map_ids = (np.frombuffer((C.c_char * (4 * nb.value)).from_address(ip), dtype=np.int32).copy()
+                                        if nb.value else np.zeros(0, np.int32))
             mp = L.str_er_result_masks(rh, C.byref(no))
             if mp:
                 res.masks = (np.frombuffer((C.c_char * (16 * no.value)).from_address(mp), dtype=MASK_DTYPE).copy()
@@ -591,7 +636,7 @@ class ERFilter:
 
     # ---- the hot path ---------------------------------------------------------------------------
     def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
-                    want_line_crops=False, want_shapes: bool = False) -> Result:
+                    want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -603,7 +648,8 @@ class ERFilter:
         rh = C.c_void_p()
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) |
-                                             (WANT_SHAPES if want_shapes else 0) | _crop_flags(want_line_crops), C.byref(rh)))
+                                             (WANT_SHAPES if want_shapes else 0) | _crop_flags(want_line_crops) |
+                                             _map_flags(want_text_map, want_line_map), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -722,14 +768,14 @@ class ERFilter:
         return self._collect(rh)
 
     def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
-                         want_line_crops=False, want_shapes: bool = False) -> Result:
+                         want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) | (WANT_SHAPES if want_shapes else 0) |
-                                 _crop_flags(want_line_crops))
+                                 _crop_flags(want_line_crops) | _map_flags(want_text_map, want_line_map))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -834,6 +880,27 @@ class ERFilter:
         self._check(self.L.str_er_er_shapes(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(r) if n else None, n,
                                             _np_ptr(out)))
         return out[:n]
+
+    def text_map_regions(self, plane: np.ndarray, regions: np.ndarray, values, out_w: int, out_h: int, ids=None):
+        """str_er_text_map_regions: the text map of `regions` (CAND_DTYPE; x, y, w, h, level and key are read) of one (h, w) uint8
+        plane onto an (out_h, out_w) frame by the pixel rule of str_er_frame_map: each pixel the OR of values[i] over the regions whose
+        mask (that of er_masks) holds its sample.  Returns the (out_h, out_w) uint8 map, and with ids (int32, >= 0) also the
+        (out_h, out_w) int32 map of the smallest id covering each pixel (-1 for none): (map, id_map)."""
+        a = np.ascontiguousarray(plane, dtype=np.uint8)
+        r = np.ascontiguousarray(regions, dtype=CAND_DTYPE).reshape(-1)
+        n = len(r)
+        v = np.ascontiguousarray(values, dtype=np.uint8).reshape(-1)
+        if len(v) != n:
+            raise ValueError("values needs one entry per region")
+        d = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        if d is not None and len(d) != n:
+            raise ValueError("ids needs one entry per region")
+        out = np.zeros((int(out_h), int(out_w)), np.uint8)
+        out_ids = None if d is None else np.zeros((int(out_h), int(out_w)), np.int32)
+        self._check(self.L.str_er_text_map_regions(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(r) if n else None,
+                                                   _np_ptr(v) if n else None, (_np_ptr(d) if n else _np_ptr(np.zeros(1, np.int32))) if d is not None else None,
+                                                   n, int(out_w), int(out_h), _np_ptr(out), None if out_ids is None else _np_ptr(out_ids)))
+        return out if d is None else (out, out_ids)
 
     def set_line_crop(self, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> None:
         """str_er_set_line_crop: the crop height (8..256), the widest crop (1..8192) and the pad (0..1, of the line's height) of
@@ -1014,6 +1081,10 @@ class ERFilter:
 
     def workspace_bytes(self) -> int:
         return int(self.L.str_er_workspace_bytes(self.h))
+
+
+def _map_flags(want_text_map, want_line_map) -> int:
+    return (WANT_TEXT_MAP if want_text_map else 0) | (WANT_LINE_MAP if want_line_map else 0)
 
 
 def _crop_flags(want_line_crops) -> int:

@@ -379,7 +379,7 @@ int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_
 }
 
 // the jobs of n regions of one host plane (str_er_er_masks, str_er_er_shapes), validated, and the words their masks take
-static int region_jobs(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions, int32_t n,
+int region_jobs(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions, int32_t n,
                        const DetectParams &dp, std::vector<MaskJob> &jobs, uint64_t &words)
 {
     if (!plane || w < 1 || h < 1 || stride < w || n < 0 || (n > 0 && !regions)) return fail(c, STR_ER_EINVAL, "bad arguments");
@@ -405,7 +405,7 @@ static int region_jobs(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h
 }
 
 // the plane of region_jobs on the device (the context's input buffer), the jobs pointed at it
-static int region_upload(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, std::vector<MaskJob> &jobs)
+int region_upload(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, std::vector<MaskJob> &jobs)
 {
     HIP_TRY(c, hipSetDevice(c->prm.device));
     if ((size_t)w * (size_t)h > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane larger than the context capacity");

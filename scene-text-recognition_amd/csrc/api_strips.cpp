@@ -215,6 +215,8 @@ try {
         return fail(c, STR_ER_EINVAL, "bad strip arguments");
     if (stages & STR_ER_WANT_MASKS) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_MASKS is not supported by the strip path (str_er_strip_merge)");
     if (stages & STR_ER_WANT_SHAPES) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_SHAPES is not supported by the strip path (str_er_strip_merge)");
+    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP))
+        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP are not supported by the strip path (str_er_strip_merge)");
     if (stages & (STR_ER_WANT_LINE_CROPS | STR_ER_WANT_LINE_GLYPHS))
         return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_CROPS / _GLYPHS are not supported by the strip path (str_er_strip_merge)");
     if (w > c->prm.max_width || h > c->prm.max_height) return fail(c, STR_ER_ECAPACITY, "frame larger than the context capacity");

@@ -142,4 +142,9 @@ void   launch_er_masks(hipStream_t s, const MaskJob *jobs, const int n_class[3],
 // also the glyph crops (same offsets), from the members and the mask words `bits` they index.
 void launch_line_crops(hipStream_t s, const LineCropJob *jobs, int n, uint8_t *out, uint8_t *glyph, const GlyphMember *members, const uint32_t *bits);
 
+// Text maps (er_text_map.inl): one wave per tile.  map (or null) receives the OR of the values, ids (or null) the smallest id or -1, of
+// the regions of every tile that cover each element; tabs holds the uint16 xs / ys tables the regions index; bits the mask words.
+void launch_text_map(hipStream_t s, const TextMapTile *tiles, int n_tiles, const uint32_t *list, const TextMapCand *cands, const uint16_t *tabs,
+                     const uint32_t *bits, uint8_t *map, int32_t *ids);
+
 } // namespace str_er

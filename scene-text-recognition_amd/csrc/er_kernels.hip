@@ -44,5 +44,6 @@ namespace str_er {
 #include "er_classify.inl"      // k_classify, k_lbp_boxes, k_cascade_fv
 #include "er_masks.inl"         // k_er_masks_small / _big: the pixel masks of regions
 #include "er_line_crops.inl"    // k_line_crops: the rectified grey / glyph image of every text line
+#include "er_text_map.inl"      // k_text_map: the frame-resolution text map and line-id map of every frame
 
 } // namespace str_er

@@ -233,4 +233,30 @@ struct GlyphMember {
 };
 static_assert(sizeof(GlyphMember) == 16, "GlyphMember layout (host and device)");
 
+// A region of the text-map stage (STR_ER_WANT_TEXT_MAP / _LINE_MAP, str_er_text_map_regions): its box on its plane, its mask (the
+// str_er_mask layout: h rows of pitch words), its pre-image in frame pixels [fx0, fx1) x [fy0, fy1) (the frame pixels whose sample
+// (xs, ys) lies in the box) and where the xs / ys tables of its (frame size, level size) pair start.  value: STR_ER_TEXT_MAP_* bits;
+// id: the smallest line id, or INT32_MAX.
+struct TextMapCand {
+    uint64_t word_off;
+    uint32_t pitch;
+    uint16_t x, y, w, h;
+    int32_t  fx0, fx1, fy0, fy1;
+    uint32_t xtab, ytab;
+    uint32_t value;
+    int32_t  id;
+};
+static_assert(sizeof(TextMapCand) == 56, "TextMapCand layout (host and device)");
+
+// A tile of the text-map stage: n_elem (a multiple of 4) consecutive elements of one frame's map, from element e0 of the frame on
+// (the frame's map starts at element `off` of the output), and its regions: list[first .. first + count) index the TextMapCands.
+struct TextMapTile {
+    uint64_t off;
+    uint32_t e0, n_elem;
+    int32_t  width, height;
+    uint32_t first, count;
+};
+static_assert(sizeof(TextMapTile) == 32, "TextMapTile layout (host and device)");
+constexpr uint32_t TMAP_CHUNK_ELEMS = 2048;      // a tile is a whole number of such chunks, and at least a row of its frame (er_text_map.inl)
+
 } // namespace str_er

@@ -832,6 +832,10 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
     if ((stages & (STR_ER_WANT_LINE_CROPS | STR_ER_WANT_LINE_GLYPHS)) && !(stages & STR_ER_STAGE_GROUP))
         return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_CROPS / _GLYPHS need STR_ER_STAGE_GROUP");
     if ((stages & STR_ER_WANT_LINE_GLYPHS) && !(stages & STR_ER_WANT_LINE_CROPS)) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_GLYPHS needs STR_ER_WANT_LINE_CROPS");
+    if ((stages & STR_ER_WANT_TEXT_MAP) && !(stages & STR_ER_STAGE_CLASSIFY)) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP needs STR_ER_STAGE_CLASSIFY");
+    if ((stages & STR_ER_WANT_LINE_MAP) && !(stages & STR_ER_STAGE_GROUP)) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_MAP needs STR_ER_STAGE_GROUP");
+    if ((stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP)) && b_in.frame_wh.empty())
+        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP need frames (not the per-plane calls or the strip path)");
     if ((stages & STR_ER_STAGE_OCR_LINES) && !(c->svm_loaded && c->svm.dim == 1800))
         return fail(c, STR_ER_ESTATE, "STR_ER_STAGE_OCR_LINES needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)");
     if ((stages & STR_ER_STAGE_TRACK) && b.planes_per_image <= 0)
@@ -1303,6 +1307,11 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
         const int rcc = line_crop_phase(c, s, b, dp.qscale, (stages & STR_ER_WANT_LINE_GLYPHS) != 0, d_mask_bits, r);
         if (rcc != STR_ER_OK) { delete r; return rcc; }
     }
+    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP)) {
+        // the maps of the frames from the final candidates and lines: binned on the host, one launch (with the masks, if this call has none), one copy back
+        const int rct = text_map_phase(c, s, b, stages, dp.qscale, d_mask_bits, r);
+        if (rct != STR_ER_OK) { delete r; return rct; }
+    }
     if (want_nodes) {
         // candidates carry the device kept slot; translate to the sorted table through (key, level)
         for (int i = 0; i < np; ++i) {
@@ -1447,6 +1456,10 @@ void str_er_destroy(str_er_ctx *c)
     if (c->d_mask_scratch) (void)hipFree(c->d_mask_scratch);
     if (c->d_crop) (void)hipFree(c->d_crop);
     if (c->h_crop) (void)hipHostFree(c->h_crop);
+    if (c->d_tmap) (void)hipFree(c->d_tmap);
+    if (c->h_tmap) (void)hipHostFree(c->h_tmap);
+    if (c->d_tmap_tab) (void)hipFree(c->d_tmap_tab);
+    if (c->h_tmap_tab) (void)hipHostFree(c->h_tmap_tab);
     if (c->d_strip_out) (void)hipFree(c->d_strip_out);
     if (c->d_strip_in) (void)hipFree(c->d_strip_in);
     if (c->d_replay) (void)hipFree(c->d_replay);
@@ -1668,6 +1681,12 @@ static int detect_bgr_impl(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->prm.device));
+    std::vector<int32_t> frame_wh;
+    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP)) {     // (the maps' buffers: sized before anything of the call is enqueued)
+        for (int f = 0; f < n_frames; ++f) frame_wh.insert(frame_wh.end(), {w, h});
+        const int rcm = text_map_reserve(c, stages, frame_wh);
+        if (rcm != STR_ER_OK) return rcm;
+    }
     const uint8_t *dbgr = nullptr;
     int64_t dstride = stride, dpitch = frame_pitch;
     if (mem_kind == STR_ER_MEM_HOST) {
@@ -1729,6 +1748,7 @@ static int detect_bgr_impl(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t
                 b.planes.back().color_pitch = (uint32_t)plane_sz(l);
             }
     b.planes_per_image = plane_select ? 0 : (int)c->chans.size();
+    b.frame_wh = std::move(frame_wh);
     return run_batch(c, b, stages, out, t0, true);
 }
 
@@ -1737,6 +1757,8 @@ int str_er_detect_planes(str_er_ctx *c, const uint8_t *planes, int32_t w, int32_
 try {
     if (!c) return STR_ER_EINVAL;
     if (!planes || !out || w < 1 || h < 1 || n_planes < 1 || stride < w) return fail(c, STR_ER_EINVAL, "bad plane arguments");
+    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP))
+        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP need frames: not with str_er_detect_planes");
     if (n_planes > 1 && plane_pitch < stride * (int64_t)h) return fail(c, STR_ER_EINVAL, "plane_pitch smaller than a plane");
     if (w > c->prm.max_width || h > c->prm.max_height || n_planes > c->max_planes)
         return fail(c, STR_ER_ECAPACITY, "plane larger than / more planes than the context capacity");
@@ -1833,6 +1855,11 @@ int detect_list_impl(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_fr
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->prm.device));
+    std::vector<int32_t> frame_wh;
+    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP)) {     // (the maps' buffers: sized before anything of the call is enqueued)
+        for (int f = 0; f < n_frames; ++f) frame_wh.insert(frame_wh.end(), {frames[f].w, frames[f].h});
+        if ((rc = text_map_reserve(c, stages, frame_wh)) != STR_ER_OK) return rc;
+    }
     if ((rc = ensure_list_buffers(c)) != STR_ER_OK) return rc;
     const int n = n_frames, nl = c->prm.n_pyr_levels;
     // physical planes: frame after frame, each laid out as detect_bgr_impl lays out one frame -- per level [Y, Cr, Cb] plane_sz apart
@@ -1917,6 +1944,7 @@ int detect_list_impl(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_fr
                 b.planes.back().color_pitch = (uint32_t)plane_sz(f, l);
             }
     b.planes_per_image = (int)c->chans.size();
+    b.frame_wh = std::move(frame_wh);
     return lc.finish(run_batch(c, b, stages, out, t0, true));
 }
 
@@ -1939,6 +1967,8 @@ try {
     if (!c) return STR_ER_EINVAL;
     int rc = check_list(c, planes, n_planes, c->max_planes, mem_kind, 1, out, "plane");
     if (rc != STR_ER_OK) return rc;
+    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP))
+        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP need frames: not with str_er_detect_planes_list");
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->prm.device));

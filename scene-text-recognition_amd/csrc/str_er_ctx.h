@@ -81,6 +81,10 @@ struct str_er_result {
     std::vector<str_er_line_crop> line_crops;     // STR_ER_WANT_LINE_CROPS: per line, and the bytes they index
     std::vector<uint8_t> crop_pixels, glyph_pixels;
     bool have_line_crops = false, have_line_glyphs = false;
+    std::vector<str_er_frame_map> frame_maps;    // STR_ER_WANT_TEXT_MAP / _LINE_MAP: per frame, and the maps they index
+    std::vector<uint8_t> text_map;
+    std::vector<int32_t> line_map;
+    bool have_text_map = false, have_line_map = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -169,6 +173,10 @@ struct str_er_ctx {
     // that wants crops, grown geometrically, never shrunk
     int32_t  crop_height = 32, crop_max_width = 1024; double crop_pad = 0.125;
     uint8_t  *d_crop = nullptr, *h_crop = nullptr; size_t crop_bytes = 0;       // jobs | members | grey | glyph bytes, on the device and page-locked
+    // STR_ER_WANT_TEXT_MAP / _LINE_MAP / str_er_text_map_regions: the maps (bytes | ids), sized before a call enqueues anything, and the
+    // tables of the stage (tiles | list | regions | xs / ys); both created by the first call that wants maps, grown geometrically, never shrunk
+    uint8_t  *d_tmap = nullptr, *h_tmap = nullptr; size_t tmap_bytes = 0;
+    uint8_t  *d_tmap_tab = nullptr, *h_tmap_tab = nullptr; size_t tmap_tab_bytes = 0;
     uint8_t *d_strip_out = nullptr, *d_strip_in = nullptr; size_t strip_out_cap = 0, strip_in_cap = 0;   // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -339,6 +347,7 @@ struct Batch {
     size_t kept = 0, pool = 0;                  // entries of the kept-node / pool arrays handed to the planes
     uint32_t kept_floor = 0, pool_floor = 0;    // str_er_nms_tree: the plane's tables must hold the imported tree
     int planes_per_image = 0;       // BGR frames: planes of one (frame, pyramid level), consecutive in `planes`; 0 = no colour image
+    std::vector<int32_t> frame_wh;  // frames: (w, h) at level 0 of every frame of the call, for the text maps; empty = no frames (per-plane calls)
     uint32_t n_groups = 0; int group_x = 0, group_y = 0;       // k_group_merge: groups of group_x x group_y tiles (0: none); assign_groups()
 };
 
@@ -390,6 +399,17 @@ int line_crop_geometry(const int32_t *boxes_xywh, int32_t n_boxes, double slope,
 // STR_ER_WANT_LINE_CROPS / _GLYPHS in run_batch: the crops of the lines of r, from the Y planes of b (planes_per_image > 0)
 // (d_mask_bits: the words of this call's STR_ER_WANT_MASKS on the device, or null: then the glyphs' masks are made here)
 int line_crop_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, bool glyphs, const uint32_t *d_mask_bits, str_er_result *r);
+// the validated jobs of n regions of one host plane (str_er_er_masks and the other single stages on regions) and the words their masks take;
+// region_upload puts the plane in the context's workspace and points the jobs at it
+int region_jobs(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions, int32_t n,
+                const DetectParams &dp, std::vector<MaskJob> &jobs, uint64_t &words);
+int region_upload(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, std::vector<MaskJob> &jobs);
+// ---- defined in api_text_map.cpp
+// STR_ER_WANT_TEXT_MAP / _LINE_MAP: the flags checked and the output maps of frames (w, h pairs) sized -- before a call enqueues anything
+int text_map_reserve(str_er_ctx *c, uint32_t stages, const std::vector<int32_t> &frame_wh);
+// ... in run_batch: the maps of the frames of b (b.frame_wh) from the final candidates and lines of r (d_mask_bits: this call's mask words
+// on the device, indexed by r->masks, or null: then the masks are made here)
+int text_map_phase(str_er_ctx *c, hipStream_t s, const Batch &b, uint32_t stages, float qscale, const uint32_t *d_mask_bits, str_er_result *r);
 constexpr int MASK_MAX_WIDTH = 16384;       // widest box the mask kernels take (er_masks.inl: MASK_MAX_WPL words of 64 pixels per lane)
 // ---- defined in api_models.cpp
 int parse_cascade(str_er_ctx *c, HostCascade &hc, const char *text, size_t len);

@@ -341,6 +341,48 @@ public:
         return out;
     }
 
+    // The text map of ERs of one 8UC1 plane (its level size) onto an out_w x out_h frame (str_er_text_map_regions): every frame pixel
+    // the OR of values[i] over the ERs whose mask (that of er_masks) holds its sample (include/str_er.h, str_er_frame_map).  With ids
+    // (one per ER, >= 0) also the smallest id covering each pixel, -1 where none does.  Both maps row-major, pitch out_w.
+    struct FrameMap {
+        int width = 0, height = 0;
+        std::vector<uint8_t> text;          // STR_ER_TEXT_MAP_* bits
+        std::vector<int32_t> line;          // line ids (empty without them)
+    };
+    FrameMap text_map_regions(const Image8 &plane, const ERs &ers, const std::vector<uint8_t> &values, int out_w, int out_h,
+                              const std::vector<int32_t> *ids = nullptr)
+    {
+        if (plane.channels != 1) throw std::runtime_error("text_map_regions expects an 8UC1 plane");
+        if (values.size() != ers.size() || (ids && ids->size() != ers.size())) throw std::runtime_error("text_map_regions: one value (and id) per ER");
+        const std::vector<str_er_cand> regions = regions_of(ers);
+        FrameMap m;
+        m.width = out_w; m.height = out_h;
+        m.text.resize((size_t)out_w * out_h);
+        if (ids) m.line.resize((size_t)out_w * out_h);
+        check(str_er_text_map_regions(ctx_.get(), plane.data, plane.cols, plane.rows, plane.step, regions.data(), values.data(),
+                                      ids ? ids->data() : nullptr, (int32_t)regions.size(), out_w, out_h, m.text.data(), ids ? m.line.data() : nullptr));
+        return m;
+    }
+
+    // The maps of every frame of a result of a call with STR_ER_WANT_TEXT_MAP and / or _LINE_MAP (str_er_result_frame_maps), copied out
+    // of the result; a map whose flag was not given stays empty.
+    static std::vector<FrameMap> frame_maps(const str_er_result *r)
+    {
+        int32_t  n = 0;
+        uint64_t nb = 0, ni = 0;
+        const str_er_frame_map *fm = str_er_result_frame_maps(r, &n);
+        const uint8_t          *tm = str_er_result_text_map_pixels(r, &nb);
+        const int32_t          *lm = str_er_result_line_map_ids(r, &ni);
+        std::vector<FrameMap>   out(fm ? (size_t)n : 0);
+        for (size_t f = 0; f < out.size(); ++f) {
+            const size_t px = (size_t)fm[f].width * (size_t)fm[f].height;
+            out[f].width = fm[f].width; out[f].height = fm[f].height;
+            if (tm) out[f].text.assign(tm + fm[f].off, tm + fm[f].off + px);
+            if (lm) out[f].line.assign(lm + fm[f].off, lm + fm[f].off + px);
+        }
+        return out;
+    }
+
     // vector<double> ERFilter::make_LBP_hist(Mat input, N = 2, normalize_size = 24) (src/ER.cpp:789-816)
     std::vector<double> make_LBP_hist(const Image8 &input)
     {
