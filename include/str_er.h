@@ -80,6 +80,12 @@ extern "C" {
  * Every str_er_detect_* entry point and every str_er_stream_submit* call honours it; str_er_strip_merge[_ex] rejects it (STR_ER_EINVAL);
  * a candidate wider than 16384 pixels gives STR_ER_ECAPACITY.                                                                      */
 #define STR_ER_WANT_SHAPES    (8192u)
+/* output option: also return the stroke-width descriptor of every candidate (str_er_result_strokes, str_er_stroke), made on the device
+ * from the candidate's mask like STR_ER_WANT_SHAPES: the mask words are returned only with STR_ER_WANT_MASKS as well, and the masks are
+ * made once per call whatever combination of masks, shapes, strokes, glyphs and maps is asked for.  Every str_er_detect_* entry point
+ * and every str_er_stream_submit* call honours it; str_er_strip_merge[_ex] rejects it (STR_ER_EINVAL); a candidate wider than 16384
+ * pixels gives STR_ER_ECAPACITY.  It changes no other output of the call.                                                           */
+#define STR_ER_WANT_STROKES   (65536u)
 /* output options: frame-resolution maps of where the detected text is (str_er_result_frame_maps, str_er_frame_map).
  * _TEXT_MAP: one uint8 map per frame, at the frame's own (level-0) size, bits STR_ER_TEXT_MAP_* of every region that covers the
  * pixel; needs STR_ER_STAGE_CLASSIFY.  _LINE_MAP: one int32 map per frame, the smallest index into str_er_result_texts() of a line
@@ -211,6 +217,32 @@ typedef struct str_er_shape {
     uint64_t grey_sum;      /* sum of P' over M                                                                                        */
     uint64_t grey_sum2;     /* sum of P'^2 over M                                                                                      */
 } str_er_shape;             /* 48 bytes */
+
+/* The stroke-width descriptor of one region (STR_ER_WANT_STROKES, str_er_er_strokes), exact integers, defined by this library (the
+ * reference's StrokeWidth::SWT is compiled out): an octagonal erosion depth over the region's mask M (str_er_mask) in its box of w x h
+ * pixels; pixels outside the box are in no set below.
+ *   E_0 = M; E_k = { p in E_{k-1} : every neighbour of p in N_k lies in E_{k-1} }, N_k the 4-neighbourhood for odd k and the
+ *   8-neighbourhood for even k.  K = the smallest k with E_k empty (K >= 1: M holds the key pixel).
+ *   Depth D(p) = k for p in E_{k-1} \ E_k: 1 <= D(p) <= K on M (D = 0 off M).
+ *   Ridge = the p in M whose 8 neighbours all have D <= D(p): the local maxima of D, plateaus included.  As bit rows, the ridge at
+ *   depth k is (E_{k-1} & ~E_k) & ~dilate8(E_k).
+ * The mean ridge depth m = ridge_depth_sum / ridge_pixels estimates the stroke width: a stroke t pixels wide has depth ceil(t/2), so
+ * t = 2m - 1 for odd widths and 2m for even ones; ridge_depth_sum2 / ridge_pixels - m^2 is its spread (0 for a stroke of one width).
+ * Closed forms: an axis-parallel bar of t x L pixels that fills its box has ridge depth ceil(t/2) along its whole ridge -- for odd t
+ * a ridge one pixel wide that stops (t - 1)/2 pixels short of each end, for even t two pixels wide, t/2 - 1 short of each end; an
+ * n x n square has K = ceil(n/2), depth_sum = sum over k >= 0 with n - 2k > 0 of (n - 2k)^2, and a ridge of 1 pixel (odd n) or 4
+ * (even n); a single pixel gives {1, 1, 1, 1, 1}.
+ * How it is computed, one wave per mask in the epilogue of the mask kernels: one pass over the rows a step, E_{k-1} and E_k as bit
+ * rows, the step counting |E_k| and the ridge at depth k and making E_{k+1}; a step visits only the rows where E_{k-1} is
+ * non-empty, and the last step is the first whose E_{k+1} is empty (no cap).  Layout: depth_max 0, ridge_pixels 4, depth_sum 8,
+ * ridge_depth_sum 16, ridge_depth_sum2 24.                                                                                          */
+typedef struct str_er_stroke {
+    uint32_t depth_max;        /* K                                                                                                */
+    uint32_t ridge_pixels;     /* |ridge|                                                                                          */
+    uint64_t depth_sum;        /* sum of D over M = sum over k < K of |E_k|                                                        */
+    uint64_t ridge_depth_sum;  /* sum of D over the ridge                                                                          */
+    uint64_t ridge_depth_sum2; /* sum of D^2 over the ridge                                                                        */
+} str_er_stroke;               /* 32 bytes */
 
 /* The crop of one text line (STR_ER_WANT_LINE_CROPS, str_er_line_crops, str_er_line_crop_geometry).
  * Geometry, all f64 on the host in this order: s = the line's slope (non-finite counts as 0); r = sqrt(1 + s*s); d = (1, s) / r,
@@ -429,6 +461,11 @@ int str_er_er_masks(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h,
 int str_er_er_shapes(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions,
                      int32_t n, str_er_shape *out);
 
+/* The stroke-width descriptors (str_er_stroke) of n regions of one host plane, at the context's current thresh_step, into
+ * out[0 .. n - 1]: the masks of str_er_er_masks (same regions, same validation and error codes), the plane taken as it is.          */
+int str_er_er_strokes(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions,
+                      int32_t n, str_er_stroke *out);
+
 /* The text map of n regions of one host plane of w x h pixels (the level size) onto an out_w x out_h frame (out_map, out_w * out_h
  * bytes, pitch out_w), by the pixel rule of str_er_frame_map: every output pixel is the OR of values[i] over the regions that cover
  * it, and with ids (then out_ids != NULL, out_w * out_h int32) out_ids the smallest ids[i] of them, -1 if none.  Of every region only
@@ -616,6 +653,8 @@ const str_er_mask *str_er_result_masks(const str_er_result *r, int32_t *n);
 const uint32_t    *str_er_result_mask_bits(const str_er_result *r, uint64_t *n_words);
 /* With STR_ER_WANT_SHAPES: one descriptor record per candidate of str_er_result_cands() (same order); NULL and 0 without the flag. */
 const str_er_shape *str_er_result_shapes(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_STROKES: one stroke-width record per candidate of str_er_result_cands() (same order); NULL and 0 without the flag. */
+const str_er_stroke *str_er_result_strokes(const str_er_result *r, int32_t *n);
 /* With STR_ER_WANT_LINE_CROPS: one record per line of str_er_result_texts() (same order), the grey crop bytes they index and, with
  * STR_ER_WANT_LINE_GLYPHS, the glyph crop bytes (same offsets, same size).  NULL without the flag(s).                              */
 const str_er_line_crop *str_er_result_line_crops(const str_er_result *r, int32_t *n);

@@ -29,6 +29,12 @@ WANT_SHAPES = 8192      # output option: the shape and intensity descriptors of 
 # convex_hull_ratio = hull_area2 / (2 * pixels), med_crossings = crossings[3]
 SHAPE_DTYPE = np.dtype([("pixels", "<u4"), ("perimeter", "<u4"), ("euler", "<i4"), ("hole_pixels", "<u4"), ("crossings", "<u2", (4,)),
                         ("hull_area2", "<u8"), ("grey_sum", "<u8"), ("grey_sum2", "<u8")])
+WANT_STROKES = 65536    # output option: the stroke-width descriptor of every candidate (Result.strokes)
+# str_er_stroke: exact integers over the candidate's mask M (include/str_er.h): K erosions (4- and 8-neighbourhoods in turn) empty M;
+# the mean ridge depth m = ridge_depth_sum / ridge_pixels gives the stroke width 2m - 1 (odd) or 2m (even), and
+# ridge_depth_sum2 / ridge_pixels - m * m its spread
+STROKE_DTYPE = np.dtype([("depth_max", "<u4"), ("ridge_pixels", "<u4"), ("depth_sum", "<u8"), ("ridge_depth_sum", "<u8"),
+                         ("ridge_depth_sum2", "<u8")])
 # output options: frame-resolution maps (Result.text_map / Result.line_map).  WANT_TEXT_MAP (needs STAGE_CLASSIFY): one uint8 map per
 # frame at its own size, the OR of the TEXT_MAP_* bits of every region covering the pixel; WANT_LINE_MAP (needs STAGE_GROUP): one
 # int32 map per frame, the smallest index into texts of a line with a member covering the pixel, -1 where none does
@@ -59,6 +65,7 @@ PLANE_DTYPE = np.dtype([("frame", "<u4"), ("ch", "u1"), ("pyr", "u1"), ("r0", "u
 assert NODE_DTYPE.itemsize == 24 and CAND_DTYPE.itemsize == 48 and PLANE_DTYPE.itemsize == 44 and MASK_DTYPE.itemsize == 16
 assert LINE_CROP_DTYPE.itemsize == 40
 assert SHAPE_DTYPE.itemsize == 48
+assert STROKE_DTYPE.itemsize == 32
 assert FRAME_MAP_DTYPE.itemsize == 16
 
 
@@ -234,6 +241,9 @@ def load_library():
     L.str_er_result_shapes.argtypes = [vp, i32p]
     L.str_er_result_shapes.restype = vp
     L.str_er_er_shapes.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp]
+    L.str_er_result_strokes.argtypes = [vp, i32p]
+    L.str_er_result_strokes.restype = vp
+    L.str_er_er_strokes.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int32, vp]
     L.str_er_set_min_ocr_prob.argtypes = [vp, C.c_double]
     L.str_er_result_line_crops.argtypes = [vp, i32p]
     L.str_er_result_line_crops.restype = vp
@@ -361,6 +371,7 @@ class Result:
         self.masks = None          # with WANT_MASKS: MASK_DTYPE per candidate, and the words they index (uint32)
         self.mask_bits = None
         self.shapes = None         # with WANT_SHAPES: SHAPE_DTYPE per candidate
+        self.strokes = None        # with WANT_STROKES: STROKE_DTYPE per candidate
         self.line_crops = None     # with WANT_LINE_CROPS: LINE_CROP_DTYPE per line of texts, the grey crop bytes and (WANT_LINE_GLYPHS) the glyph bytes
         self.line_crop_pixels = None
         self.line_glyph_pixels = None
@@ -589,6 +600,10 @@ class ERFilter:
             if sp:
                 res.shapes = (np.frombuffer((C.c_char * (48 * no.value)).from_address(sp), dtype=SHAPE_DTYPE).copy()
                               if no.value else np.zeros(0, SHAPE_DTYPE))
+            kp = L.str_er_result_strokes(rh, C.byref(no))
+            if kp:
+                res.strokes = (np.frombuffer((C.c_char * (32 * no.value)).from_address(kp), dtype=STROKE_DTYPE).copy()
+                               if no.value else np.zeros(0, STROKE_DTYPE))
             lp2 = L.str_er_result_line_labels(rh, C.byref(no))
             if lp2:
                 k = no.value
@@ -636,7 +651,8 @@ class ERFilter:
 
     # ---- the hot path ---------------------------------------------------------------------------
     def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
-                    want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False) -> Result:
+                    want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
+                    want_strokes: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -648,7 +664,7 @@ class ERFilter:
         rh = C.c_void_p()
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) |
-                                             (WANT_SHAPES if want_shapes else 0) | _crop_flags(want_line_crops) |
+                                             (WANT_SHAPES if want_shapes else 0) | (WANT_STROKES if want_strokes else 0) | _crop_flags(want_line_crops) |
                                              _map_flags(want_text_map, want_line_map), C.byref(rh)))
         return self._collect(rh)
 
@@ -768,14 +784,15 @@ class ERFilter:
         return self._collect(rh)
 
     def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
-                         want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False) -> Result:
+                         want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
+                         want_strokes: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) | (WANT_SHAPES if want_shapes else 0) |
-                                 _crop_flags(want_line_crops) | _map_flags(want_text_map, want_line_map))
+                                 (WANT_STROKES if want_strokes else 0) | _crop_flags(want_line_crops) | _map_flags(want_text_map, want_line_map))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -879,6 +896,16 @@ class ERFilter:
         out = np.zeros(max(1, n), SHAPE_DTYPE)
         self._check(self.L.str_er_er_shapes(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(r) if n else None, n,
                                             _np_ptr(out)))
+        return out[:n]
+
+    def er_strokes(self, plane: np.ndarray, regions: np.ndarray) -> np.ndarray:
+        """str_er_er_strokes: the stroke-width descriptors (STROKE_DTYPE) of the masks er_masks gives for `regions` on one (H, W) uint8 plane."""
+        a = np.ascontiguousarray(plane, dtype=np.uint8)
+        r = np.ascontiguousarray(regions, dtype=CAND_DTYPE).reshape(-1)
+        n = len(r)
+        out = np.zeros(max(1, n), STROKE_DTYPE)
+        self._check(self.L.str_er_er_strokes(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(r) if n else None, n,
+                                             _np_ptr(out)))
         return out[:n]
 
     def text_map_regions(self, plane: np.ndarray, regions: np.ndarray, values, out_w: int, out_h: int, ids=None):

@@ -155,7 +155,7 @@ int line_crop_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, 
     if (glyphs) {
         members.resize(mem_cand.size());
         if (d_mask_bits) {
-            // the masks of this call (STR_ER_WANT_MASKS) are still on the device: the same words, indexed as in the result
+            // the masks of this call (STR_ER_WANT_MASKS / _SHAPES / _STROKES) are still on the device: the same words, indexed as in the result
             d_bits = d_mask_bits;
             for (size_t k = 0; k < mem_cand.size(); ++k) members[k].word_off = r->masks[mem_cand[k]].word_off;
         } else {

@@ -312,14 +312,18 @@ try {
 
 namespace str_er_host {
 
-// (o_pix / o_shape / o_bits: where the popcounts, the ShapeRecs (with shapes) and the words of n jobs sit in c->d_mask, behind the jobs)
-static void mask_offsets(size_t n, uint64_t n_words, bool shapes, size_t &o_pix, size_t &o_shape, size_t &o_bits, size_t &need)
+// (o_pix / o_shape / o_stroke / o_bits: where the popcounts, the ShapeRecs (with shapes), the StrokeRecs (with strokes) and the words of
+// n jobs sit in c->d_mask, behind the jobs)
+static void mask_offsets(size_t n, uint64_t n_words, bool shapes, bool strokes, size_t &o_pix, size_t &o_shape, size_t &o_stroke, size_t &o_bits,
+                         size_t &need)
 {
     o_pix = align_up(sizeof(MaskJob) * n, 256); o_shape = align_up(o_pix + 4 * n, 256);
-    o_bits = align_up(o_shape + (shapes ? sizeof(ShapeRec) * n : 0), 256); need = o_bits + 4 * (size_t)n_words;
+    o_stroke = align_up(o_shape + (shapes ? sizeof(ShapeRec) * n : 0), 256);
+    o_bits = align_up(o_stroke + (strokes ? sizeof(StrokeRec) * n : 0), 256); need = o_bits + 4 * (size_t)n_words;
 }
 
-int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, const uint32_t **d_bits, bool shapes)
+int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, const uint32_t **d_bits, bool shapes,
+                bool strokes)
 {
     const size_t n = jobs.size();
     if (n == 0) return STR_ER_OK;
@@ -329,8 +333,8 @@ int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64
     std::stable_sort(jobs.begin(), jobs.end(), [](const MaskJob &a, const MaskJob &b) { return mask_class(a.w, a.h) < mask_class(b.w, b.h); });
     size_t scratch = 0;
     for (MaskJob &j : jobs) { j.scratch_off = scratch; scratch += mask_scratch_words(j.w, j.h); }
-    size_t o_pix, o_shape, o_bits, need;
-    mask_offsets(n, n_words, shapes, o_pix, o_shape, o_bits, need);
+    size_t o_pix, o_shape, o_stroke, o_bits, need;
+    mask_offsets(n, n_words, shapes, strokes, o_pix, o_shape, o_stroke, o_bits, need);
     if (need > c->mask_bytes) {
         const size_t get = std::max(need, 2 * c->mask_bytes);
         if (c->d_mask) { (void)hipFree(c->d_mask); c->d_mask = nullptr; }
@@ -355,30 +359,31 @@ int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64
     HIP_TRY(c, hipMemcpyAsync(c->d_mask, c->h_mask, sizeof(MaskJob) * n, hipMemcpyHostToDevice, s));
     launch_er_masks(s, reinterpret_cast<const MaskJob *>(c->d_mask), n_class, reinterpret_cast<uint32_t *>(c->d_mask + o_bits),
                     reinterpret_cast<uint32_t *>(c->d_mask + o_pix), shapes ? reinterpret_cast<ShapeRec *>(c->d_mask + o_shape) : nullptr,
-                    c->d_mask_scratch, qscale);
+                    strokes ? reinterpret_cast<StrokeRec *>(c->d_mask + o_stroke) : nullptr, c->d_mask_scratch, qscale);
     HIP_TRY(c, hipGetLastError());
     if (d_bits) *d_bits = reinterpret_cast<const uint32_t *>(c->d_mask + o_bits);
     return STR_ER_OK;
 }
 
 int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, uint32_t *pixels, uint32_t *bits,
-               const uint32_t **d_bits, str_er_shape *shapes)
+               const uint32_t **d_bits, str_er_shape *shapes, str_er_stroke *strokes)
 {
     const size_t n = jobs.size();
     if (n == 0) return STR_ER_OK;
-    const int rc = mask_launch(c, s, jobs, n_words, qscale, d_bits, shapes != nullptr);
+    const int rc = mask_launch(c, s, jobs, n_words, qscale, d_bits, shapes != nullptr, strokes != nullptr);
     if (rc != STR_ER_OK) return rc;
-    size_t o_pix, o_shape, o_bits, need;
-    mask_offsets(n, n_words, shapes != nullptr, o_pix, o_shape, o_bits, need);
+    size_t o_pix, o_shape, o_stroke, o_bits, need;
+    mask_offsets(n, n_words, shapes != nullptr, strokes != nullptr, o_pix, o_shape, o_stroke, o_bits, need);
     HIP_TRY(c, hipMemcpyAsync(c->h_mask + o_pix, c->d_mask + o_pix, (bits ? need : o_bits) - o_pix, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
     std::memcpy(pixels, c->h_mask + o_pix, 4 * n);
     if (shapes) std::memcpy(shapes, c->h_mask + o_shape, sizeof(ShapeRec) * n);
+    if (strokes) std::memcpy(strokes, c->h_mask + o_stroke, sizeof(StrokeRec) * n);
     if (bits && n_words) std::memcpy(bits, c->h_mask + o_bits, 4 * (size_t)n_words);
     return STR_ER_OK;
 }
 
-// the jobs of n regions of one host plane (str_er_er_masks, str_er_er_shapes), validated, and the words their masks take
+// the jobs of n regions of one host plane (str_er_er_masks, str_er_er_shapes, str_er_er_strokes), validated, and the words their masks take
 int region_jobs(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions, int32_t n,
                        const DetectParams &dp, std::vector<MaskJob> &jobs, uint64_t &words)
 {
@@ -452,6 +457,21 @@ try {
     if ((rc = region_upload(c, plane, w, h, stride, jobs)) != STR_ER_OK) return rc;
     std::vector<uint32_t> px((size_t)n);
     return mask_stage(c, c->stream, jobs, words, dp.qscale, px.data(), nullptr, nullptr, out);
+} ABI_GUARD(c)
+
+int str_er_er_strokes(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions, int32_t n,
+                      str_er_stroke *out)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (n > 0 && !out) return fail(c, STR_ER_EINVAL, "bad arguments");
+    const DetectParams dp = make_dp(c);
+    std::vector<MaskJob> jobs;
+    uint64_t words = 0;
+    int rc = region_jobs(c, plane, w, h, stride, regions, n, dp, jobs, words);
+    if (rc != STR_ER_OK || n == 0) return rc;
+    if ((rc = region_upload(c, plane, w, h, stride, jobs)) != STR_ER_OK) return rc;
+    std::vector<uint32_t> px((size_t)n);
+    return mask_stage(c, c->stream, jobs, words, dp.qscale, px.data(), nullptr, nullptr, nullptr, out);
 } ABI_GUARD(c)
 
 } // extern "C"

@@ -215,6 +215,7 @@ try {
         return fail(c, STR_ER_EINVAL, "bad strip arguments");
     if (stages & STR_ER_WANT_MASKS) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_MASKS is not supported by the strip path (str_er_strip_merge)");
     if (stages & STR_ER_WANT_SHAPES) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_SHAPES is not supported by the strip path (str_er_strip_merge)");
+    if (stages & STR_ER_WANT_STROKES) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_STROKES is not supported by the strip path (str_er_strip_merge)");
     if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP))
         return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP are not supported by the strip path (str_er_strip_merge)");
     if (stages & (STR_ER_WANT_LINE_CROPS | STR_ER_WANT_LINE_GLYPHS))

@@ -210,7 +210,7 @@ int text_map_phase(str_er_ctx *c, hipStream_t s, const Batch &b, uint32_t stages
     std::vector<TmapRegion> regs(who.size());
     const uint32_t *d_bits = d_mask_bits;
     if (d_mask_bits) {
-        // the masks of this call (STR_ER_WANT_MASKS / _SHAPES) are still on the device: the same words, indexed as in the result
+        // the masks of this call (STR_ER_WANT_MASKS / _SHAPES / _STROKES) are still on the device: the same words, indexed as in the result
         for (size_t i = 0; i < who.size(); ++i) regs[i].word_off = r->masks[who[i]].word_off;
     } else if (!who.empty()) {
         // the masks of the contributing candidates, made by the mask kernels and left on the device

@@ -132,11 +132,12 @@ void launch_cascade_fv(hipStream_t s, const double *fv, int n, double *out, Casc
 // Pixel masks of regions (er_masks.inl).  The jobs come ordered by size class (mask_class: 0 registers, 1 LDS, 2 global scratch),
 // n_class[k] of class k; out receives the bit rows at MaskJob::out_off, pixels[MaskJob::idx] the popcounts.  scratch: the
 // mask_scratch_words of every class-2 job, at its MaskJob::scratch_off (may be null without class-2 jobs).  shapes != null: also
-// shapes[MaskJob::idx] receives the mask's ShapeRec (the SHAPES instantiations); null runs the mask kernels alone.
+// shapes[MaskJob::idx] receives the mask's ShapeRec (the SHAPES instantiations); strokes != null: strokes[MaskJob::idx] its StrokeRec
+// (the STROKES instantiations); both null run the mask kernels alone.
 int    mask_class(int w, int h);
 size_t mask_scratch_words(int w, int h);
-void   launch_er_masks(hipStream_t s, const MaskJob *jobs, const int n_class[3], uint32_t *out, uint32_t *pixels, ShapeRec *shapes, uint64_t *scratch,
-                       float qscale);
+void   launch_er_masks(hipStream_t s, const MaskJob *jobs, const int n_class[3], uint32_t *out, uint32_t *pixels, ShapeRec *shapes, StrokeRec *strokes,
+                       uint64_t *scratch, float qscale);
 
 // Line crops (er_line_crops.inl): n jobs, one workgroup each.  out receives the grey crops at LineCropJob::out_off; with glyph != null
 // also the glyph crops (same offsets), from the members and the mask words `bits` they index.

@@ -12,6 +12,8 @@
 // With SHAPES (STR_ER_WANT_SHAPES, str_er_er_shapes) an epilogue turns the reached rows into a ShapeRec (str_er_shape): popcounts of
 // the rows and their neighbours, the row extents for the hull, a second read of the plane for the grey sums, and a second fixpoint
 // flood -- the complement of the mask, 8-connected, seeded from the box border -- for the holes.  The mask-only instantiations run none of it.
+// With STROKES (STR_ER_WANT_STROKES, str_er_er_strokes) another epilogue erodes the mask to nothing, 4- and 8-neighbourhoods in turn, and
+// turns the depth of every pixel into a StrokeRec (str_er_stroke).  Its last step is the first whose erosion is empty (a ballot): no cap.
 
 constexpr int MASK_THREADS   = 64;
 constexpr int MASK_LDS_WORDS = 1024;     // 64-bit words per array (A, R): 16 KB of LDS a workgroup
@@ -151,9 +153,47 @@ __device__ __forceinline__ void shape_store(ShapeRec *out, uint32_t pix, uint32_
     *out = s;
 }
 
-template <bool SHAPES>
+// the record of one mask from its per-lane sums (wave sums; lane 0 writes it): k_max = K, pc = |E_{K-1}|, the ridge at depth K
+__device__ __forceinline__ void stroke_store(StrokeRec *out, uint32_t k_max, uint64_t pc, uint64_t dsum, uint64_t rp, uint64_t rs, uint64_t rs2)
+{
+    rp += pc; rs += (uint64_t)k_max * pc; rs2 += (uint64_t)k_max * k_max * pc;
+    dsum = mask_wave_sum(dsum); rp = mask_wave_sum(rp); rs = mask_wave_sum(rs); rs2 = mask_wave_sum(rs2);
+    if (threadIdx.x == 0) {
+        StrokeRec s;
+        s.depth_max = k_max;
+        s.ridge_pixels = (uint32_t)rp;
+        s.depth_sum = dsum;
+        s.ridge_depth_sum = rs;
+        s.ridge_depth_sum2 = rs2;
+        *out = s;
+    }
+}
+
+// The StrokeRec of the mask r, one row a lane (boxes up to 64 x 64).  Step k + 1 holds E_{k-1} and E_k one row a lane, takes the
+// neighbour rows of E_k by lane shifts, and makes E_{k+1} = E_k eroded through N_{k+1} (4-neighbours for odd k + 1: the row's
+// horizontal erosion AND the rows above and below; 8-neighbours: the horizontal erosions of the three rows ANDed).  It counts |E_k| and
+// the ridge at depth k, E_{k-1} & ~dilate8(E_k).  Bits outside the box are 0 in every row, so the box border erodes like any other.
+__device__ __forceinline__ void stroke_small(uint64_t r, int lane, StrokeRec *__restrict__ out)
+{
+    uint64_t ep = 0, ec = r;                    // E_{k-1} (0 for k = 0: no pixel has depth 0), E_k
+    uint64_t dsum = 0, rp = 0, rs = 0, rs2 = 0;
+    for (uint32_t k = 0;; ++k) {
+        const uint64_t hz = ec & (ec << 1) & (ec >> 1), hd = ec | (ec << 1) | (ec >> 1);
+        const uint64_t eu = __shfl_up(ec, 1), ed = __shfl_down(ec, 1), zu = __shfl_up(hz, 1), zd = __shfl_down(hz, 1);
+        const uint64_t du = __shfl_up(hd, 1), dd = __shfl_down(hd, 1);
+        const bool     t = lane > 0, b = lane < 63;
+        const uint64_t en = (k & 1) == 0 ? hz & (t ? eu : 0ull) & (b ? ed : 0ull) : hz & (t ? zu : 0ull) & (b ? zd : 0ull);
+        const uint64_t pc = (uint64_t)__popcll(ec), pr = (uint64_t)__popcll(ep & ~(hd | (t ? du : 0ull) | (b ? dd : 0ull)));
+        dsum += pc; rp += pr; rs += k * pr; rs2 += (uint64_t)k * k * pr;
+        if (__ballot(en != 0) == 0) { stroke_store(out, k + 1, pc, dsum, rp, rs, rs2); return; }
+        ep = ec; ec = en;
+    }
+}
+
+template <bool SHAPES, bool STROKES>
 __global__ __launch_bounds__(MASK_THREADS) void k_er_masks_small(const MaskJob *__restrict__ jobs, int n, uint32_t *__restrict__ out,
-                                                                 uint32_t *__restrict__ pixels, ShapeRec *__restrict__ shapes, float qscale)
+                                                                 uint32_t *__restrict__ pixels, ShapeRec *__restrict__ shapes, float qscale,
+                                                                 StrokeRec *__restrict__ strokes)
 {
     const int lane = threadIdx.x;
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
@@ -196,6 +236,7 @@ __global__ __launch_bounds__(MASK_THREADS) void k_er_masks_small(const MaskJob *
             if (lane == 0) shape_store(shapes + j.idx, cnt, hp, vp, blk, holes, cr, hull2, gs, gs2);
             __syncthreads();        // (lane 0's reads of s_x before the next box writes it)
         }
+        if constexpr (STROKES) stroke_small(r, lane, strokes + j.idx);
     }
 }
 
@@ -333,9 +374,76 @@ __device__ void shape_big(const MaskJob &j, uint64_t *A, uint64_t *R, uint32_t p
     if (lane == 0) shape_store(shapes + j.idx, pix, hp, vp, blk, holes, cr, hull2, gs, gs2);
 }
 
-template <bool SHAPES>
+// one row y of E_k for the stroke sweep: its words e (0 outside the sweep's rows), their horizontal erosion z and dilation d (the bits of
+// the neighbour words from mask_word_edges: every lane takes part)
+__device__ __forceinline__ void stroke_row(const uint64_t *Y, int y, bool in, int P, int wpl, int lane, uint64_t (&e)[MASK_MAX_WPL],
+                                           uint64_t (&z)[MASK_MAX_WPL], uint64_t (&d)[MASK_MAX_WPL])
+{
+#pragma unroll
+    for (int m = 0; m < MASK_MAX_WPL; ++m) {
+        const int k = lane + 64 * m;
+        e[m] = in && m < wpl && k < P ? Y[(size_t)y * P + k] : 0ull;
+    }
+#pragma unroll
+    for (int m = 0; m < MASK_MAX_WPL; ++m) {
+        const uint64_t g = m < wpl ? mask_word_edges(e, m, wpl, lane) : 0ull;
+        const uint64_t l = (e[m] << 1) | (g & 1ull), r = (e[m] >> 1) | (g & (1ull << 63));
+        z[m] = e[m] & l & r;
+        d[m] = e[m] | l | r;
+    }
+}
+
+// The StrokeRec of the mask R of a box of class 1 / 2, by one sweep a step over the two arrays: step k + 1 reads E_{k-1}[y] from X
+// and E_k[y - 1 .. y + 1] from Y (three rows kept in registers as the sweep goes down), counts |E_k| and the ridge at depth k, and
+// overwrites E_{k-1}[y] with E_{k+1}[y]; then X and Y trade places.  Step 1 makes E_1 in A from E_0 = M in R.  A step sweeps only the
+// rows where E_{k-1} is non-empty (E_k and E_{k+1} lie inside them, and every other row of both arrays is 0): each step removes the top
+// and bottom rows of the set, so the window shrinks by at least two rows a step.  A lane reads and writes only its own words, as in
+// mask_sweep.  A and R are left holding two of the E_k.
+__device__ void stroke_big(int w, int h, uint64_t *A, uint64_t *R, StrokeRec *__restrict__ out)
+{
+    const int lane = threadIdx.x, P = (w + 63) >> 6, wpl = (P + 63) >> 6;
+    uint64_t *X = A, *Y = R;
+    int       plo = 0, phi = h - 1, clo = 0, chi = h - 1;       // the rows of E_{k-1} (k = 0: the box) and of E_k
+    uint64_t  dsum = 0, rp = 0, rs = 0, rs2 = 0;
+    for (uint32_t k = 0;; ++k) {
+        uint64_t e0[MASK_MAX_WPL], z0[MASK_MAX_WPL], d0[MASK_MAX_WPL], e1[MASK_MAX_WPL], z1[MASK_MAX_WPL], d1[MASK_MAX_WPL];
+        uint64_t e2[MASK_MAX_WPL], z2[MASK_MAX_WPL], d2[MASK_MAX_WPL];
+        stroke_row(Y, plo - 1, false, P, wpl, lane, e0, z0, d0);
+        stroke_row(Y, plo, true, P, wpl, lane, e1, z1, d1);
+        uint64_t pc = 0, pr = 0;
+        int      nlo = h, nhi = -1;
+        for (int y = plo; y <= phi; ++y) {
+            stroke_row(Y, y + 1, y + 1 <= phi, P, wpl, lane, e2, z2, d2);
+            bool any = false;
+#pragma unroll
+            for (int m = 0; m < MASK_MAX_WPL; ++m) {
+                const int kk = lane + 64 * m;
+                if (m < wpl && kk < P) {
+                    const size_t   o = (size_t)y * P + kk;
+                    const uint64_t en = (k & 1) == 0 ? z1[m] & e0[m] & e2[m] : z0[m] & z1[m] & z2[m];
+                    if (k > 0) pr += (uint64_t)__popcll(X[o] & ~(d0[m] | d1[m] | d2[m]));
+                    pc += (uint64_t)__popcll(e1[m]);
+                    X[o] = en;
+                    any |= en != 0;
+                }
+            }
+            if (__ballot(any)) { nlo = min(nlo, y); nhi = y; }
+#pragma unroll
+            for (int m = 0; m < MASK_MAX_WPL; ++m) {
+                e0[m] = e1[m]; z0[m] = z1[m]; d0[m] = d1[m];
+                e1[m] = e2[m]; z1[m] = z2[m]; d1[m] = d2[m];
+            }
+        }
+        dsum += pc; rp += pr; rs += k * pr; rs2 += (uint64_t)k * k * pr;
+        if (nhi < 0) { stroke_store(out, k + 1, pc, dsum, rp, rs, rs2); return; }
+        uint64_t *t = X; X = Y; Y = t;
+        plo = clo; phi = chi; clo = nlo; chi = nhi;
+    }
+}
+
+template <bool SHAPES, bool STROKES>
 __device__ void mask_big_body(const MaskJob &j, uint64_t *A, uint64_t *R, uint32_t *__restrict__ out, uint32_t *__restrict__ pixels,
-                              ShapeRec *__restrict__ shapes, float qscale)
+                              ShapeRec *__restrict__ shapes, StrokeRec *__restrict__ strokes, float qscale)
 {
     const int lane = threadIdx.x, w = j.w, h = j.h, P = (w + 63) >> 6;
     for (int y = 0; y < h; ++y)
@@ -361,19 +469,33 @@ __device__ void mask_big_body(const MaskJob &j, uint64_t *A, uint64_t *R, uint32
         }
     cnt = mask_wave_sum(cnt);
     if (lane == 0) pixels[j.idx] = cnt;
+    if constexpr (STROKES) {
+        stroke_big(w, h, A, R, strokes + j.idx);
+        if constexpr (SHAPES) {
+            // R = M again for the descriptors, from the words this lane wrote to `out` above (its own words: program order is enough;
+            // the fence keeps the reload behind the stroke sweep's last writes to R)
+            __threadfence_block();
+            for (int y = 0; y < h; ++y)
+                for (int k = lane; k < P; k += 64) {
+                    const size_t o = j.out_off + (size_t)y * pitch + 2 * (size_t)k;
+                    R[(size_t)y * P + k] = (uint64_t)out[o] | (2 * k + 1 < pitch ? (uint64_t)out[o + 1] << 32 : 0ull);
+                }
+        }
+    }
     if constexpr (SHAPES) shape_big(j, A, R, cnt, shapes);
 }
 
-template <bool IN_LDS, bool SHAPES>
+template <bool IN_LDS, bool SHAPES, bool STROKES>
 __global__ __launch_bounds__(MASK_THREADS) void k_er_masks_big(const MaskJob *__restrict__ jobs, int n, uint32_t *__restrict__ out,
-                                                               uint32_t *__restrict__ pixels, ShapeRec *__restrict__ shapes, uint64_t *scratch, float qscale)
+                                                               uint32_t *__restrict__ pixels, ShapeRec *__restrict__ shapes, uint64_t *scratch,
+                                                               float qscale, StrokeRec *__restrict__ strokes)
 {
     __shared__ uint64_t s_rows[IN_LDS ? 2 * MASK_LDS_WORDS : 1];
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         const MaskJob j = jobs[i];
         const size_t  words = (size_t)j.h * (size_t)((j.w + 63) >> 6);
         uint64_t     *A = IN_LDS ? s_rows : scratch + j.scratch_off;
-        mask_big_body<SHAPES>(j, A, IN_LDS ? s_rows + MASK_LDS_WORDS : A + words, out, pixels, shapes, qscale);
+        mask_big_body<SHAPES, STROKES>(j, A, IN_LDS ? s_rows + MASK_LDS_WORDS : A + words, out, pixels, shapes, strokes, qscale);
     }
 }
 
@@ -385,26 +507,33 @@ int mask_class(int w, int h)
 
 size_t mask_scratch_words(int w, int h)
 {
+    // (A and R: the stroke sweep needs no more -- it runs in them, and with SHAPES as well R is reloaded from the mask words afterwards)
     return mask_class(w, h) == 2 ? 2 * (size_t)h * (size_t)((w + 63) >> 6) : 0;
 }
 
-template <bool SHAPES>
+template <bool SHAPES, bool STROKES>
 static void launch_er_masks_t(hipStream_t s, const MaskJob *jobs, const int n_class[3], uint32_t *out, uint32_t *pixels, ShapeRec *shapes,
-                              uint64_t *scratch, float qscale)
+                              StrokeRec *strokes, uint64_t *scratch, float qscale)
 {
     const int grid_cap = 1 << 16;
     if (n_class[0] > 0)
-        hipLaunchKernelGGL(k_er_masks_small<SHAPES>, dim3(std::min(n_class[0], grid_cap)), dim3(MASK_THREADS), 0, s, jobs, n_class[0], out, pixels, shapes, qscale);
+        hipLaunchKernelGGL((k_er_masks_small<SHAPES, STROKES>), dim3(std::min(n_class[0], grid_cap)), dim3(MASK_THREADS), 0, s, jobs, n_class[0], out, pixels,
+                           shapes, qscale, strokes);
     jobs += n_class[0];
     if (n_class[1] > 0)
-        hipLaunchKernelGGL((k_er_masks_big<true, SHAPES>), dim3(std::min(n_class[1], grid_cap)), dim3(MASK_THREADS), 0, s, jobs, n_class[1], out, pixels, shapes, scratch, qscale);
+        hipLaunchKernelGGL((k_er_masks_big<true, SHAPES, STROKES>), dim3(std::min(n_class[1], grid_cap)), dim3(MASK_THREADS), 0, s, jobs, n_class[1], out,
+                           pixels, shapes, scratch, qscale, strokes);
     jobs += n_class[1];
     if (n_class[2] > 0)
-        hipLaunchKernelGGL((k_er_masks_big<false, SHAPES>), dim3(std::min(n_class[2], grid_cap)), dim3(MASK_THREADS), 0, s, jobs, n_class[2], out, pixels, shapes, scratch, qscale);
+        hipLaunchKernelGGL((k_er_masks_big<false, SHAPES, STROKES>), dim3(std::min(n_class[2], grid_cap)), dim3(MASK_THREADS), 0, s, jobs, n_class[2], out,
+                           pixels, shapes, scratch, qscale, strokes);
 }
 
-void launch_er_masks(hipStream_t s, const MaskJob *jobs, const int n_class[3], uint32_t *out, uint32_t *pixels, ShapeRec *shapes, uint64_t *scratch, float qscale)
+void launch_er_masks(hipStream_t s, const MaskJob *jobs, const int n_class[3], uint32_t *out, uint32_t *pixels, ShapeRec *shapes, StrokeRec *strokes,
+                     uint64_t *scratch, float qscale)
 {
-    if (shapes) launch_er_masks_t<true>(s, jobs, n_class, out, pixels, shapes, scratch, qscale);
-    else        launch_er_masks_t<false>(s, jobs, n_class, out, pixels, shapes, scratch, qscale);
+    if (shapes && strokes) launch_er_masks_t<true, true>(s, jobs, n_class, out, pixels, shapes, strokes, scratch, qscale);
+    else if (shapes)       launch_er_masks_t<true, false>(s, jobs, n_class, out, pixels, shapes, strokes, scratch, qscale);
+    else if (strokes)      launch_er_masks_t<false, true>(s, jobs, n_class, out, pixels, shapes, strokes, scratch, qscale);
+    else                   launch_er_masks_t<false, false>(s, jobs, n_class, out, pixels, shapes, strokes, scratch, qscale);
 }

@@ -213,6 +213,13 @@ struct ShapeRec {
 };
 static_assert(sizeof(ShapeRec) == 48, "ShapeRec must match str_er_shape");
 
+// Matches str_er_stroke in include/str_er.h (32 bytes): the stroke-width descriptor of one mask (STR_ER_WANT_STROKES, str_er_er_strokes).
+struct StrokeRec {
+    uint32_t depth_max, ridge_pixels;
+    uint64_t depth_sum, ridge_depth_sum, ridge_depth_sum2;
+};
+static_assert(sizeof(StrokeRec) == 32, "StrokeRec must match str_er_stroke");
+
 // One line of the crop stage (STR_ER_WANT_LINE_CROPS, str_er_line_crops): the 16.16 sampling geometry of str_er_line_crop over the
 // line's Y plane, and for glyph crops the line's distinct members (GlyphMember[m_first .. m_first + m_count)).
 struct LineCropJob {

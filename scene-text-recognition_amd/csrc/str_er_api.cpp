@@ -1272,10 +1272,11 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
     }
     r->cand_off[np] = off;
     const uint32_t *d_mask_bits = nullptr;         // (the masks' words on the device, for the glyph crops below)
-    if (stages & (STR_ER_WANT_MASKS | STR_ER_WANT_SHAPES)) {
+    if (stages & (STR_ER_WANT_MASKS | STR_ER_WANT_SHAPES | STR_ER_WANT_STROKES)) {
         // the masks of the final candidates (after any NMS tie pass): sized on the host from the records just copied, one launch per size class, one wait;
-        // with STR_ER_WANT_SHAPES the same launches make the descriptors, and without STR_ER_WANT_MASKS the words stay on the device
+        // with STR_ER_WANT_SHAPES / _STROKES the same launches make the descriptors, and without STR_ER_WANT_MASKS the words stay on the device
         const bool want_masks = (stages & STR_ER_WANT_MASKS) != 0, want_shapes = (stages & STR_ER_WANT_SHAPES) != 0;
+        const bool want_strokes = (stages & STR_ER_WANT_STROKES) != 0;
         std::vector<MaskJob> jobs(total);
         std::vector<uint32_t> px(total);
         uint64_t words = 0;
@@ -1285,7 +1286,8 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
             const PlaneDesc   &pd = b.planes[cd.plane];
             if (cd.w > MASK_MAX_WIDTH) {
                 delete r;
-                return fail(c, STR_ER_ECAPACITY, std::string(want_masks ? "STR_ER_WANT_MASKS" : "STR_ER_WANT_SHAPES") + ": a candidate wider than " + std::to_string(MASK_MAX_WIDTH) + " pixels");
+                return fail(c, STR_ER_ECAPACITY, std::string(want_masks ? "STR_ER_WANT_MASKS" : want_shapes ? "STR_ER_WANT_SHAPES" : "STR_ER_WANT_STROKES") +
+                                                     ": a candidate wider than " + std::to_string(MASK_MAX_WIDTH) + " pixels");
             }
             MaskJob &j = jobs[k];
             j.pix = pd.pix; j.stride = pd.stride; j.invert = (uint32_t)pd.invert; j.plane_w = (uint32_t)pd.w; j.key = cd.key;
@@ -1295,12 +1297,14 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
         }
         if (want_masks) r->mask_bits.resize(words);
         if (want_shapes) r->shapes.resize(total);
+        if (want_strokes) r->strokes.resize(total);
         const int rcm = mask_stage(c, s, jobs, words, dp.qscale, px.data(), want_masks ? r->mask_bits.data() : nullptr, &d_mask_bits,
-                                   want_shapes ? r->shapes.data() : nullptr);
+                                   want_shapes ? r->shapes.data() : nullptr, want_strokes ? r->strokes.data() : nullptr);
         if (rcm != STR_ER_OK) { delete r; return rcm; }
         for (uint32_t k = 0; k < total; ++k) r->masks[k].pixels = px[k];
         r->have_masks = want_masks;         // (without it r->masks only places the words on the device, for the glyph crops)
         r->have_shapes = want_shapes;
+        r->have_strokes = want_strokes;
     }
     if (stages & STR_ER_WANT_LINE_CROPS) {
         // the crops of the final lines, while the call's planes are still in the workspace: laid out on the host, one launch, one wait
@@ -2039,6 +2043,14 @@ const str_er_shape *str_er_result_shapes(const str_er_result *r, int32_t *n)
     if (n) *n = (int32_t)r->shapes.size();
     static const str_er_shape none{};
     return r->shapes.empty() ? &none : r->shapes.data();
+}
+
+const str_er_stroke *str_er_result_strokes(const str_er_result *r, int32_t *n)
+{
+    if (!r || !r->have_strokes) { if (n) *n = 0; return nullptr; }
+    if (n) *n = (int32_t)r->strokes.size();
+    static const str_er_stroke none{};
+    return r->strokes.empty() ? &none : r->strokes.data();
 }
 
 const uint32_t *str_er_result_mask_bits(const str_er_result *r, uint64_t *n_words)

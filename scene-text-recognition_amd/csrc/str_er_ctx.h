@@ -78,6 +78,8 @@ struct str_er_result {
     bool have_masks = false;
     std::vector<str_er_shape> shapes;        // STR_ER_WANT_SHAPES: per candidate
     bool have_shapes = false;
+    std::vector<str_er_stroke> strokes;      // STR_ER_WANT_STROKES: per candidate
+    bool have_strokes = false;
     std::vector<str_er_line_crop> line_crops;     // STR_ER_WANT_LINE_CROPS: per line, and the bytes they index
     std::vector<uint8_t> crop_pixels, glyph_pixels;
     bool have_line_crops = false, have_line_glyphs = false;
@@ -388,11 +390,13 @@ int stage_input(str_er_ctx *c, const uint8_t *src, size_t bytes, int mem_kind, c
 // ---- defined in api_stages.cpp
 // the pixel masks of `jobs` (out_off / idx set by the caller, n_words words in all): launched on s, waited for, copied to pixels[idx] and
 // bits (bits == null: the words are not copied back) (d_bits, optional: where the words stay on the device, as for mask_launch);
-// shapes != null: the SHAPES kernels, shapes[idx] receives the str_er_shape of every mask
+// shapes != null: the SHAPES kernels, shapes[idx] receives the str_er_shape of every mask; strokes != null: the STROKES kernels,
+// strokes[idx] receives its str_er_stroke
 int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, uint32_t *pixels, uint32_t *bits,
-               const uint32_t **d_bits = nullptr, str_er_shape *shapes = nullptr);
+               const uint32_t **d_bits = nullptr, str_er_shape *shapes = nullptr, str_er_stroke *strokes = nullptr);
 // the launches of mask_stage alone: the words stay on the device, at *d_bits (in c->d_mask, valid until the context's next mask launch)
-int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, const uint32_t **d_bits, bool shapes = false);
+int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, const uint32_t **d_bits, bool shapes = false,
+                bool strokes = false);
 // ---- defined in api_line_crops.cpp
 // the str_er_line_crop geometry of one line (STR_ER_EINVAL when it leaves 16.16 fixed point)
 int line_crop_geometry(const int32_t *boxes_xywh, int32_t n_boxes, double slope, int32_t height, int32_t max_width, double pad, str_er_line_crop &out);

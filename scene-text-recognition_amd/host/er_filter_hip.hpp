@@ -341,6 +341,17 @@ public:
         return out;
     }
 
+    // The stroke-width descriptors of the same masks (str_er_er_strokes): the erosion depth K, the ridge and its depth moments, whose
+    // mean gives the stroke width (include/str_er.h, str_er_stroke).  The masks stay on the device.
+    std::vector<str_er_stroke> er_strokes(const Image8 &plane, const ERs &ers)
+    {
+        if (plane.channels != 1) throw std::runtime_error("er_strokes expects an 8UC1 plane");
+        const std::vector<str_er_cand> regions = regions_of(ers);
+        std::vector<str_er_stroke> out(regions.size());
+        check(str_er_er_strokes(ctx_.get(), plane.data, plane.cols, plane.rows, plane.step, regions.data(), (int32_t)regions.size(), out.data()));
+        return out;
+    }
+
     // The text map of ERs of one 8UC1 plane (its level size) onto an out_w x out_h frame (str_er_text_map_regions): every frame pixel
     // the OR of values[i] over the ERs whose mask (that of er_masks) holds its sample (include/str_er.h, str_er_frame_map).  With ids
     // (one per ER, >= 0) also the smallest id covering each pixel, -1 where none does.  Both maps row-major, pitch out_w.
@@ -499,7 +510,7 @@ private:
     {
         if (rc != STR_ER_OK) throw std::runtime_error(std::string(str_er_strerror(rc)) + ": " + str_er_last_error(ctx_.get()));
     }
-    // the regions of er_masks / er_shapes: of every ER its bound, level and key
+    // the regions of er_masks / er_shapes / er_strokes: of every ER its bound, level and key
     static std::vector<str_er_cand> regions_of(const ERs &ers)
     {
         std::vector<str_er_cand> regions(ers.size());
