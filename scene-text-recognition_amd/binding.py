@@ -522,99 +522,55 @@ class ERFilter:
     # ---- results ------------------------------------------------------------------------------
     def _collect(self, rh: C.c_void_p, profile: Optional[dict] = None) -> Result:
         L = self.L
+
+        n32, n64 = C.c_int32(), C.c_uint64()        # (the counts: a table's length, a byte / word array's)
+
+        def table(fn, dtype, n=n32):                 # a table a stage makes: None when the stage did not run
+            ptr = fn(rh, C.byref(n))
+            return _owned(ptr, n.value, dtype) if ptr else None
+
         try:
             n = C.c_int32()
-            ptr = L.str_er_result_cands(rh, C.byref(n))
-            if n.value:
-                cands = np.frombuffer((C.c_char * (48 * n.value)).from_address(ptr), dtype=CAND_DTYPE).copy()
-            else:
-                cands = np.zeros(0, CAND_DTYPE)
-            ptr = L.str_er_result_plane_infos(rh, C.byref(n))
-            info = np.frombuffer((C.c_char * (44 * n.value)).from_address(ptr), dtype=PLANE_DTYPE).copy()
+            cands = _owned(L.str_er_result_cands(rh, C.byref(n)), n.value, CAND_DTYPE)
+            info = _owned(L.str_er_result_plane_infos(rh, C.byref(n)), n.value, PLANE_DTYPE)
             nodes = None
             nn = C.c_int32()
             if n.value and L.str_er_result_plane_nodes(rh, 0, C.byref(nn)):
                 nodes = []
                 for i in range(n.value):
                     nptr = L.str_er_result_plane_nodes(rh, i, C.byref(nn))
-                    nodes.append(np.frombuffer((C.c_char * (24 * nn.value)).from_address(nptr), dtype=NODE_DTYPE).copy()
-                                 if nn.value else np.zeros(0, NODE_DTYPE))
+                    nodes.append(_owned(nptr, nn.value, NODE_DTYPE))
             t = L.str_er_result_times(rh)
             times = np.array([t[i] for i in range(7)])
             res = Result(info, cands, times, self.last_profile() if profile is None else profile, nodes)
-            no = C.c_int32()
-            lp = L.str_er_result_ocr_labels(rh, C.byref(no))
-            if lp:
-                res.ocr_label = np.frombuffer((C.c_char * (4 * no.value)).from_address(lp), dtype=np.int32).copy()
-                pp = L.str_er_result_ocr_probs(rh, C.byref(no))
-                res.ocr_prob = np.frombuffer((C.c_char * (8 * no.value)).from_address(pp), dtype=np.float64).copy()
-            tp = L.str_er_result_tracks(rh, C.byref(no))
-            if tp:
-                res.tracks = (np.frombuffer((C.c_char * (40 * no.value)).from_address(tp), dtype=TRACK_DTYPE).copy()
-                              if no.value else np.zeros(0, TRACK_DTYPE))
-            xp = L.str_er_result_texts(rh, C.byref(no))
-            if xp:
-                res.texts = (np.frombuffer((C.c_char * (40 * no.value)).from_address(xp), dtype=TEXT_DTYPE).copy()
-                             if no.value else np.zeros(0, TEXT_DTYPE))
-                ep = L.str_er_result_text_ers(rh, C.byref(no))
-                res.text_ers = (np.frombuffer((C.c_char * (4 * no.value)).from_address(ep), dtype=np.int32).copy()
-                                if no.value else np.zeros(0, np.int32))
-                ap = L.str_er_result_group_all(rh, C.byref(no))
-                res.group_all = (np.frombuffer((C.c_char * (4 * no.value)).from_address(ap), dtype=np.int32).copy()
-                                 if no.value else np.zeros(0, np.int32))
-                bp = L.str_er_result_group_bounds(rh, C.byref(no))
-                res.group_bounds = (np.frombuffer((C.c_char * (24 * no.value)).from_address(bp), dtype=GBOUND_DTYPE).copy()
-                                    if no.value else np.zeros(0, GBOUND_DTYPE))
-            cp = L.str_er_result_line_crops(rh, C.byref(no))
-            if cp:
-                res.line_crops = (np.frombuffer((C.c_char * (40 * no.value)).from_address(cp), dtype=LINE_CROP_DTYPE).copy()
-                                  if no.value else np.zeros(0, LINE_CROP_DTYPE))
-                nb = C.c_uint64()
-                for name, fn in (("line_crop_pixels", L.str_er_result_line_crop_pixels), ("line_glyph_pixels", L.str_er_result_line_glyph_pixels)):
-                    bp = fn(rh, C.byref(nb))
-                    if bp:
-                        setattr(res, name, np.frombuffer((C.c_char * nb.value).from_address(bp), dtype=np.uint8).copy()
-                                if nb.value else np.zeros(0, np.uint8))
-            fp = L.str_er_result_frame_maps(rh, C.byref(no))
-            if fp:
-                res.frame_maps = (np.frombuffer((C.c_char * (16 * no.value)).from_address(fp), dtype=FRAME_MAP_DTYPE).copy()
-                                  if no.value else np.zeros(0, FRAME_MAP_DTYPE))
-                nb = C.c_uint64()
-                bp = L.str_er_result_text_map_pixels(rh, C.byref(nb))
-                if bp:
-                    res.text_map_pixels = (np.frombuffer((C.c_char * nb.value).from_address(bp), dtype=np.uint8).copy()
-                                           if nb.value else np.zeros(0, np.uint8))
-                ip = L.str_er_result_line_map_ids(rh, C.byref(nb))
-                if ip:
-                    res.line_map_ids = (np.frombuffer((C.c_char * (4 * nb.value)).from_address(ip), dtype=np.int32).copy()
-                                        if nb.value else np.zeros(0, np.int32))
-            mp = L.str_er_result_masks(rh, C.byref(no))
-            if mp:
-                res.masks = (np.frombuffer((C.c_char * (16 * no.value)).from_address(mp), dtype=MASK_DTYPE).copy()
-                             if no.value else np.zeros(0, MASK_DTYPE))
-                nw = C.c_uint64()
-                wp = L.str_er_result_mask_bits(rh, C.byref(nw))
-                res.mask_bits = (np.frombuffer((C.c_char * (4 * nw.value)).from_address(wp), dtype=np.uint32).copy()
-                                 if nw.value else np.zeros(0, np.uint32))
-            sp = L.str_er_result_shapes(rh, C.byref(no))
-            if sp:
-                res.shapes = (np.frombuffer((C.c_char * (48 * no.value)).from_address(sp), dtype=SHAPE_DTYPE).copy()
-                              if no.value else np.zeros(0, SHAPE_DTYPE))
-            kp = L.str_er_result_strokes(rh, C.byref(no))
-            if kp:
-                res.strokes = (np.frombuffer((C.c_char * (32 * no.value)).from_address(kp), dtype=STROKE_DTYPE).copy()
-                               if no.value else np.zeros(0, STROKE_DTYPE))
-            lp2 = L.str_er_result_line_labels(rh, C.byref(no))
-            if lp2:
-                k = no.value
-                res.line_label = np.frombuffer((C.c_char * (4 * k)).from_address(lp2), dtype=np.int32).copy() if k else np.zeros(0, np.int32)
-                pp2 = L.str_er_result_line_probs(rh, C.byref(no))
-                res.line_prob = np.frombuffer((C.c_char * (8 * k)).from_address(pp2), dtype=np.float64).copy() if k else np.zeros(0, np.float64)
-                kp2 = L.str_er_result_line_kept(rh, C.byref(no))
-                res.line_kept = np.frombuffer((C.c_char * k).from_address(kp2), dtype=np.uint8).copy().astype(bool) if k else np.zeros(0, bool)
-                ap2 = L.str_er_result_text_alive(rh, C.byref(no))
-                res.text_alive = (np.frombuffer((C.c_char * no.value).from_address(ap2), dtype=np.uint8).copy().astype(bool)
-                                  if no.value else np.zeros(0, bool))
+            # (a table that comes with another is asked for only when that one is there: one call less per absent table on the latency path)
+            res.ocr_label = table(L.str_er_result_ocr_labels, np.int32)
+            if res.ocr_label is not None:
+                res.ocr_prob = table(L.str_er_result_ocr_probs, np.float64)
+            res.tracks = table(L.str_er_result_tracks, TRACK_DTYPE)
+            res.texts = table(L.str_er_result_texts, TEXT_DTYPE)
+            if res.texts is not None:
+                res.text_ers = table(L.str_er_result_text_ers, np.int32)
+                res.group_all = table(L.str_er_result_group_all, np.int32)
+                res.group_bounds = table(L.str_er_result_group_bounds, GBOUND_DTYPE)
+            res.line_crops = table(L.str_er_result_line_crops, LINE_CROP_DTYPE)
+            if res.line_crops is not None:
+                res.line_crop_pixels = table(L.str_er_result_line_crop_pixels, np.uint8, n64)
+                res.line_glyph_pixels = table(L.str_er_result_line_glyph_pixels, np.uint8, n64)
+            res.frame_maps = table(L.str_er_result_frame_maps, FRAME_MAP_DTYPE)
+            if res.frame_maps is not None:
+                res.text_map_pixels = table(L.str_er_result_text_map_pixels, np.uint8, n64)
+                res.line_map_ids = table(L.str_er_result_line_map_ids, np.int32, n64)
+            res.masks = table(L.str_er_result_masks, MASK_DTYPE)
+            if res.masks is not None:
+                res.mask_bits = table(L.str_er_result_mask_bits, np.uint32, n64)
+            res.shapes = table(L.str_er_result_shapes, SHAPE_DTYPE)
+            res.strokes = table(L.str_er_result_strokes, STROKE_DTYPE)
+            res.line_label = table(L.str_er_result_line_labels, np.int32)
+            if res.line_label is not None:
+                res.line_prob = table(L.str_er_result_line_probs, np.float64)
+                res.line_kept = table(L.str_er_result_line_kept, np.uint8).astype(bool)
+                res.text_alive = table(L.str_er_result_text_alive, np.uint8).astype(bool)
             return res
         finally:
             L.str_er_result_free(rh)
@@ -663,9 +619,8 @@ class ERFilter:
         f, h, w, _ = a.shape
         rh = C.c_void_p()
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
-                                             stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) |
-                                             (WANT_SHAPES if want_shapes else 0) | (WANT_STROKES if want_strokes else 0) | _crop_flags(want_line_crops) |
-                                             _map_flags(want_text_map, want_line_map), C.byref(rh)))
+                                             stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
+                                                                  text_map=want_text_map, line_map=want_line_map, strokes=want_strokes), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -791,8 +746,8 @@ class ERFilter:
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
-                                 stages | (WANT_NODES if want_nodes else 0) | (WANT_MASKS if want_masks else 0) | (WANT_SHAPES if want_shapes else 0) |
-                                 (WANT_STROKES if want_strokes else 0) | _crop_flags(want_line_crops) | _map_flags(want_text_map, want_line_map))
+                                 stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
+                                                      text_map=want_text_map, line_map=want_line_map, strokes=want_strokes))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1110,15 +1065,19 @@ class ERFilter:
         return int(self.L.str_er_workspace_bytes(self.h))
 
 
-def _map_flags(want_text_map, want_line_map) -> int:
-    return (WANT_TEXT_MAP if want_text_map else 0) | (WANT_LINE_MAP if want_line_map else 0)
+def _owned(ptr, n: int, dtype) -> np.ndarray:
+    """n records of dtype at ptr (a table of a result), copied into an array of its own; an empty array when n = 0."""
+    dtype = np.dtype(dtype)
+    if not n:
+        return np.zeros(0, dtype)
+    return np.frombuffer((C.c_char * (dtype.itemsize * n)).from_address(ptr), dtype=dtype).copy()
 
 
-def _crop_flags(want_line_crops) -> int:
-    """want_line_crops=: False, True (grey crops) or "glyphs" (grey and glyph crops)."""
-    if want_line_crops == "glyphs":
-        return WANT_LINE_CROPS | WANT_LINE_GLYPHS
-    return WANT_LINE_CROPS if want_line_crops else 0
+def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False) -> int:
+    """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
+    bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
+            (line_map, WANT_LINE_MAP), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+    return sum(bit for want, bit in bits if want)
 
 
 def line_crop_geometry(boxes_xywh: np.ndarray, slope: float, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> np.ndarray:

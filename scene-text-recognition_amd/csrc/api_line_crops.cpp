@@ -243,28 +243,10 @@ try {
     return crop_stage(c, c->stream, jobs, {}, nullptr, bytes, pixels, nullptr, false);
 } ABI_GUARD(c)
 
-const str_er_line_crop *str_er_result_line_crops(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_line_crops) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->line_crops.size();
-    static const str_er_line_crop none{};
-    return r->line_crops.empty() ? &none : r->line_crops.data();
-}
+const str_er_line_crop *str_er_result_line_crops(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_crops, &str_er_result::line_crops, n); }
 
-const uint8_t *str_er_result_line_crop_pixels(const str_er_result *r, uint64_t *n_bytes)
-{
-    if (!r || !r->have_line_crops) { if (n_bytes) *n_bytes = 0; return nullptr; }
-    if (n_bytes) *n_bytes = r->crop_pixels.size();
-    static const uint8_t none = 0;
-    return r->crop_pixels.empty() ? &none : r->crop_pixels.data();
-}
+const uint8_t *str_er_result_line_crop_pixels(const str_er_result *r, uint64_t *n_bytes) { return result_table(r, r && r->have_line_crops, &str_er_result::crop_pixels, n_bytes); }
 
-const uint8_t *str_er_result_line_glyph_pixels(const str_er_result *r, uint64_t *n_bytes)
-{
-    if (!r || !r->have_line_glyphs) { if (n_bytes) *n_bytes = 0; return nullptr; }
-    if (n_bytes) *n_bytes = r->glyph_pixels.size();
-    static const uint8_t none = 0;
-    return r->glyph_pixels.empty() ? &none : r->glyph_pixels.data();
-}
+const uint8_t *str_er_result_line_glyph_pixels(const str_er_result *r, uint64_t *n_bytes) { return result_table(r, r && r->have_line_glyphs, &str_er_result::glyph_pixels, n_bytes); }
 
 } // extern "C"

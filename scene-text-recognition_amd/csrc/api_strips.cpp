@@ -213,13 +213,6 @@ try {
     if (!bgr || !blobs || !blob_bytes || !out || w < 1 || h < 1 || stride < (int64_t)w * 3 || n_strips < 1 ||
         (blob_kind != STR_ER_MEM_HOST && blob_kind != STR_ER_MEM_DEVICE))
         return fail(c, STR_ER_EINVAL, "bad strip arguments");
-    if (stages & STR_ER_WANT_MASKS) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_MASKS is not supported by the strip path (str_er_strip_merge)");
-    if (stages & STR_ER_WANT_SHAPES) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_SHAPES is not supported by the strip path (str_er_strip_merge)");
-    if (stages & STR_ER_WANT_STROKES) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_STROKES is not supported by the strip path (str_er_strip_merge)");
-    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP))
-        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP are not supported by the strip path (str_er_strip_merge)");
-    if (stages & (STR_ER_WANT_LINE_CROPS | STR_ER_WANT_LINE_GLYPHS))
-        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_CROPS / _GLYPHS are not supported by the strip path (str_er_strip_merge)");
     if (w > c->prm.max_width || h > c->prm.max_height) return fail(c, STR_ER_ECAPACITY, "frame larger than the context capacity");
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
@@ -229,6 +222,7 @@ try {
     std::vector<size_t> sel;
     for (size_t k = 0; k < npl; ++k) if (!plane_select || plane_select[k]) sel.push_back(k);
     if (sel.empty()) return fail(c, STR_ER_EINVAL, "plane_select selects no plane");
+    { const int rcs = check_call(c, stages, {false, sel.size() == npl, true, false}); if (rcs != STR_ER_OK) return rcs; }
     // ---- the blobs: on the device (as they are, or uploaded once); their headers on the host, checked before anything is trusted ----
     const size_t head_bytes = sizeof(StripHeader) + npl * sizeof(StripPlane);
     struct View { StripHeader hd; std::vector<StripPlane> sp; StripLayout L; const uint8_t *d; };

@@ -164,8 +164,6 @@ int text_map_reserve(str_er_ctx *c, uint32_t stages, const std::vector<int32_t> 
 {
     const bool map = (stages & STR_ER_WANT_TEXT_MAP) != 0, ids = (stages & STR_ER_WANT_LINE_MAP) != 0;
     if (!map && !ids) return STR_ER_OK;
-    if (map && !(stages & STR_ER_STAGE_CLASSIFY)) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP needs STR_ER_STAGE_CLASSIFY");
-    if (ids && !(stages & STR_ER_STAGE_GROUP)) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_MAP needs STR_ER_STAGE_GROUP");
     uint64_t n_elem = 0;
     for (size_t f = 0; f + 1 < frame_wh.size(); f += 2) {
         if (frame_wh[f] > 65535 || frame_wh[f + 1] > 65535) return fail(c, STR_ER_ECAPACITY, "text map: a frame wider or taller than 65535 pixels");
@@ -298,28 +296,14 @@ try {
     return STR_ER_OK;
 } ABI_GUARD(c)
 
-const str_er_frame_map *str_er_result_frame_maps(const str_er_result *r, int32_t *n)
-{
-    if (!r || !(r->have_text_map || r->have_line_map)) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->frame_maps.size();
-    static const str_er_frame_map none{};
-    return r->frame_maps.empty() ? &none : r->frame_maps.data();
-}
+const str_er_frame_map *str_er_result_frame_maps(const str_er_result *r, int32_t *n) { return result_table(r, r && (r->have_text_map || r->have_line_map), &str_er_result::frame_maps, n); }
 
-const uint8_t *str_er_result_text_map_pixels(const str_er_result *r, uint64_t *n_bytes)
-{
-    if (!r || !r->have_text_map) { if (n_bytes) *n_bytes = 0; return nullptr; }
-    if (n_bytes) *n_bytes = r->text_map.size();
-    static const uint8_t none = 0;
-    return r->text_map.empty() ? &none : r->text_map.data();
-}
+const uint8_t *str_er_result_text_map_pixels(const str_er_result *r, uint64_t *n_bytes) { return result_table(r, r && r->have_text_map, &str_er_result::text_map, n_bytes); }
 
 const int32_t *str_er_result_line_map_ids(const str_er_result *r, uint64_t *n)
 {
-    if (!r || !r->have_line_map) { if (n) *n = 0; return nullptr; }
-    if (n) *n = r->line_map.size();
-    static const int32_t none = -1;
-    return r->line_map.empty() ? &none : r->line_map.data();
+    static const int32_t no_line = -1;        // (an empty map: a pointer to -1)
+    return result_table(r, r && r->have_line_map, &str_er_result::line_map, n, no_line);
 }
 
 } // extern "C"

@@ -1,0 +1,64 @@
+// stage_rules.h -- INTERNAL: which STR_ER_STAGE_* / STR_ER_WANT_* combinations a detect call accepts, in one place.  HIP-free: every detect entry point
+// asks it after its argument checks and before it stages, uploads, allocates or enqueues anything (tests/cpp/stage_rules_check.cpp holds it
+// against the rules as the entry points checked them one by one).
+#pragma once
+#include "../../include/str_er.h"
+
+#include <stdint.h>
+
+namespace str_er_host {
+
+// what a detect call is, as far as the flags care
+struct CallShape {
+    bool frames;          // frames of an image: the text and line maps are possible
+    bool all_planes;      // every plane of an image (planes_per_image > 0): track / group are possible
+    bool strip;           // str_er_strip_merge_ex
+    bool subset;          // str_er_detect_bgr_planes: a plane_select subset of the frames' planes
+};
+
+struct StageVerdict {
+    int         code;     // STR_ER_OK or the error
+    const char *msg;      // why (null when OK)
+};
+
+// cascades: both cascades loaded; svm1800: an SVM model loaded with dim = 1800.  The first rule that fails decides; the call's shape comes first.
+inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades, bool svm1800)
+{
+    auto any = [st](uint32_t f) { return (st & f) != 0; };
+    const uint32_t maps = STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP, crops = STR_ER_WANT_LINE_CROPS | STR_ER_WANT_LINE_GLYPHS;
+    const uint32_t sup = STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP;
+    struct Rule { bool bad; int code; const char *msg; };
+    const Rule rules[] = {
+        // the call's shape
+        {k.subset && any(STR_ER_STAGE_TRACK | STR_ER_STAGE_GROUP | STR_ER_STAGE_OCR_LINES), STR_ER_EINVAL,
+         "er_track / er_grouping read every plane of an image: not with a plane subset"},
+        {k.strip && any(STR_ER_WANT_MASKS), STR_ER_EINVAL, "STR_ER_WANT_MASKS is not supported by the strip path (str_er_strip_merge)"},
+        {k.strip && any(STR_ER_WANT_SHAPES), STR_ER_EINVAL, "STR_ER_WANT_SHAPES is not supported by the strip path (str_er_strip_merge)"},
+        {k.strip && any(STR_ER_WANT_STROKES), STR_ER_EINVAL, "STR_ER_WANT_STROKES is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(maps), STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP need frames (not the per-plane calls or the strip path)"},
+        {k.strip && any(crops), STR_ER_EINVAL, "STR_ER_WANT_LINE_CROPS / _GLYPHS are not supported by the strip path (str_er_strip_merge)"},
+        // the maps (sized before anything of a frame call is enqueued: ahead of the state of the context)
+        {any(STR_ER_WANT_TEXT_MAP) && !any(STR_ER_STAGE_CLASSIFY), STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP needs STR_ER_STAGE_CLASSIFY"},
+        {any(STR_ER_WANT_LINE_MAP) && !any(STR_ER_STAGE_GROUP), STR_ER_EINVAL, "STR_ER_WANT_LINE_MAP needs STR_ER_STAGE_GROUP"},
+        // the stages, each behind what it needs
+        {any(STR_ER_STAGE_CLASSIFY) && !cascades, STR_ER_ESTATE, "classify needs both cascades (str_er_load_cascade)"},
+        {!any(STR_ER_STAGE_EXTRACT), STR_ER_EINVAL, "stages must include STR_ER_STAGE_EXTRACT"},
+        {any(STR_ER_STAGE_CLASSIFY) && !any(STR_ER_STAGE_NMS), STR_ER_EINVAL, "STR_ER_STAGE_CLASSIFY needs STR_ER_STAGE_NMS"},
+        {any(STR_ER_STAGE_OCR) && !any(STR_ER_STAGE_CLASSIFY), STR_ER_EINVAL, "STR_ER_STAGE_OCR needs STR_ER_STAGE_CLASSIFY"},
+        {any(STR_ER_STAGE_OCR) && !svm1800, STR_ER_ESTATE, "STR_ER_STAGE_OCR needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)"},
+        {any(STR_ER_STAGE_TRACK) && !any(STR_ER_STAGE_CLASSIFY), STR_ER_EINVAL, "STR_ER_STAGE_TRACK needs STR_ER_STAGE_CLASSIFY"},
+        {any(STR_ER_STAGE_GROUP | sup) && !any(STR_ER_STAGE_TRACK), STR_ER_EINVAL, "STR_ER_STAGE_GROUP needs STR_ER_STAGE_TRACK"},
+        {any(sup) && !any(STR_ER_STAGE_GROUP), STR_ER_EINVAL, "STR_ER_GROUP_INNER_SUP / _OVERLAP_SUP modify STR_ER_STAGE_GROUP"},
+        {any(STR_ER_STAGE_OCR_LINES) && !any(STR_ER_STAGE_GROUP), STR_ER_EINVAL, "STR_ER_STAGE_OCR_LINES needs STR_ER_STAGE_GROUP"},
+        {any(crops) && !any(STR_ER_STAGE_GROUP), STR_ER_EINVAL, "STR_ER_WANT_LINE_CROPS / _GLYPHS need STR_ER_STAGE_GROUP"},
+        {any(STR_ER_WANT_LINE_GLYPHS) && !any(STR_ER_WANT_LINE_CROPS), STR_ER_EINVAL, "STR_ER_WANT_LINE_GLYPHS needs STR_ER_WANT_LINE_CROPS"},
+        {any(STR_ER_STAGE_OCR_LINES) && !svm1800, STR_ER_ESTATE,
+         "STR_ER_STAGE_OCR_LINES needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)"},
+        {any(STR_ER_STAGE_TRACK) && !k.all_planes, STR_ER_EINVAL, "STR_ER_STAGE_TRACK needs BGR frames (calc_color reads the YCrCb image)"},
+    };
+    for (const Rule &r : rules)
+        if (r.bad) return {r.code, r.msg};
+    return {STR_ER_OK, nullptr};
+}
+
+} // namespace str_er_host

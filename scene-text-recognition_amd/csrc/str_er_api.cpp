@@ -7,6 +7,7 @@
 // host; if the device or a kernel fails the call fails (there is no CPU fallback).
 #include "str_er_ctx.h"
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 
 thread_local std::string g_create_error;
@@ -772,18 +773,31 @@ struct BatchSlot {
     ~BatchSlot() { give(); }
 };
 
-int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result **out,
-              std::chrono::steady_clock::time_point t_start, bool pre_recorded, const ImportHook *import_trees, int attempt)
+// One attempt of run_batch: what its phases share.
+struct BatchRun {
+    str_er_ctx       *c;
+    uint32_t          stages;
+    const ImportHook *import_trees;
+    Batch             b;
+    int               np = 0;
+    bool              grouped = false, big_groups = false;
+    DetectParams      dp{};
+    hipStream_t       s = nullptr;
+    BatchDev          bd{};
+    int               i_extract = 0, i_nms = 0, i_cls = 0, i_trk = -1;     // the events str_er_result_times reads
+    size_t            ocr_cap = 0, ocr_cap2 = 0;        // the scorer behind classify: the batch's, the re-made planes' (0: not enqueued)
+    bool              cands_remade = false;              // an NMS tie pass re-made the candidates of some planes
+    const CandRec    *spec_src = nullptr;                // the candidate records that came back with the counters (spec_n of them)
+    uint32_t          spec_n = 0;
+    double            t_group_s = 0, t_ocr_s = 0;
+};
+constexpr int REPEAT = 1;          // (a phase's answer, never a caller's: the tables have grown, the batch is laid out and run again)
+
+// ---- the layout of the batch, and the tables grown to hold it ----
+static int layout_batch(BatchRun &R)
 {
-    // A batch whose planes outgrow their shares of the tables is laid out again with larger shares and repeated.  Every repeat raises a
-    // share (or fails), and a share stops at one entry per pixel: the repeats end; `attempt` only guards against a slip in that argument.
-    if (attempt > 24) return fail(c, STR_ER_ECAPACITY, "the batch was repeated 24 times with growing tables and still does not fit (internal error)");
-    c->last_valid = false;             // (str_er_gather_last: the candidate array is being rewritten, or re-allocated)
-    struct SpinGuard { str_er_ctx *c; int old; ~SpinGuard() { c->wait_spin_us = old; } } spin_guard{c, c->wait_spin_us};
-    c->wait_spin_us = (int)b_in.planes.size() <= SPEC_PLANES ? 2000 : 300;      // (for this call only: the guard puts the default back)
-    Batch b = b_in;
-    BatchSlot slot;                    // (str_er_set_batch_slots: given back when the batch's kernels are done, below, or on any way out)
-    if ((int)b_in.planes.size() > SPEC_PLANES) slot.take();
+    str_er_ctx *c = R.c;
+    Batch      &b = R.b;
     // tiles are joined in two steps: groups of tiles in LDS (k_group_merge), then the groups through the global passes.  Text-like
     // batches (small tile kernel: ~14 records per tile) take 8 x 4 tiles per group (a call of a frame or two: 4 x 4) with room for 2048 records,
     // noise-like ones (~250 records per tile) 2 x 5.
@@ -792,17 +806,16 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
     // pyr3x8, +0.5 % on native6, +1 % at 4K.  The other batches' kernels fill what the group kernel leaves idle, and what it saves -- groups of the luma pyramid that
     // no longer overflow the table and take the global passes whole, a third fewer records and pairs on the groups' outer borders -- are device-scope atomics, which
     // the batches in flight share.)
-    const bool grouped = !import_trees && c->group_mode != 0;
-    const bool big_groups = c->tile_sparse && (int)b_in.planes.size() > SPEC_PLANES;
+    R.grouped = !R.import_trees && c->group_mode != 0;
+    R.big_groups = c->tile_sparse && (int)b.planes.size() > SPEC_PLANES;
     {
-        int gx = c->tile_sparse ? (big_groups ? 8 : 4) : 2, gy = c->tile_sparse ? 4 : 5;
+        int gx = c->tile_sparse ? (R.big_groups ? 8 : 4) : 2, gy = c->tile_sparse ? 4 : 5;
         if (c->dbg_group[0] > 0) { gx = c->dbg_group[0]; gy = c->dbg_group[1]; }
-        if (grouped) assign_groups(b, gx, gy); else assign_groups(b, 0, 0);
+        if (R.grouped) assign_groups(b, gx, gy); else assign_groups(b, 0, 0);
     }
     assign_node_records(b, c->node_share);
     assign_tables(b, c);
-    const int ev_entry = pre_recorded ? c->n_ev : -1;
-    const int np = (int)b.planes.size();
+    const int np = R.np = (int)b.planes.size();
     if (np == 0) return fail(c, STR_ER_EINVAL, "no planes");
     if (np > c->max_planes) return fail(c, STR_ER_ECAPACITY, "more planes than the context was created for");
     if (b.slots > c->slots) return fail(c, STR_ER_ECAPACITY, "planes exceed the pixel capacity of the context");
@@ -816,35 +829,21 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
         const int rcn = alloc_node_records(c, b.nodes + b.nodes / 8);
         if (rcn != STR_ER_OK) return rcn;
     }
-    if ((stages & STR_ER_STAGE_CLASSIFY) && !(c->casc[0].loaded && c->casc[1].loaded))
-        return fail(c, STR_ER_ESTATE, "classify needs both cascades (str_er_load_cascade)");
-    if (!(stages & STR_ER_STAGE_EXTRACT)) return fail(c, STR_ER_EINVAL, "stages must include STR_ER_STAGE_EXTRACT");
-    if ((stages & STR_ER_STAGE_CLASSIFY) && !(stages & STR_ER_STAGE_NMS))
-        return fail(c, STR_ER_EINVAL, "STR_ER_STAGE_CLASSIFY needs STR_ER_STAGE_NMS");
-    if ((stages & STR_ER_STAGE_OCR) && !(stages & STR_ER_STAGE_CLASSIFY)) return fail(c, STR_ER_EINVAL, "STR_ER_STAGE_OCR needs STR_ER_STAGE_CLASSIFY");
-    if ((stages & STR_ER_STAGE_OCR) && !(c->svm_loaded && c->svm.dim == 1800))
-        return fail(c, STR_ER_ESTATE, "STR_ER_STAGE_OCR needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)");
+    return STR_ER_OK;
+}
 
-    if ((stages & STR_ER_STAGE_TRACK) && !(stages & STR_ER_STAGE_CLASSIFY)) return fail(c, STR_ER_EINVAL, "STR_ER_STAGE_TRACK needs STR_ER_STAGE_CLASSIFY");
-    if ((stages & (STR_ER_STAGE_GROUP | STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP)) && !(stages & STR_ER_STAGE_TRACK)) return fail(c, STR_ER_EINVAL, "STR_ER_STAGE_GROUP needs STR_ER_STAGE_TRACK");
-    if ((stages & (STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP)) && !(stages & STR_ER_STAGE_GROUP)) return fail(c, STR_ER_EINVAL, "STR_ER_GROUP_INNER_SUP / _OVERLAP_SUP modify STR_ER_STAGE_GROUP");
-    if ((stages & STR_ER_STAGE_OCR_LINES) && !(stages & STR_ER_STAGE_GROUP)) return fail(c, STR_ER_EINVAL, "STR_ER_STAGE_OCR_LINES needs STR_ER_STAGE_GROUP");
-    if ((stages & (STR_ER_WANT_LINE_CROPS | STR_ER_WANT_LINE_GLYPHS)) && !(stages & STR_ER_STAGE_GROUP))
-        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_CROPS / _GLYPHS need STR_ER_STAGE_GROUP");
-    if ((stages & STR_ER_WANT_LINE_GLYPHS) && !(stages & STR_ER_WANT_LINE_CROPS)) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_GLYPHS needs STR_ER_WANT_LINE_CROPS");
-    if ((stages & STR_ER_WANT_TEXT_MAP) && !(stages & STR_ER_STAGE_CLASSIFY)) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP needs STR_ER_STAGE_CLASSIFY");
-    if ((stages & STR_ER_WANT_LINE_MAP) && !(stages & STR_ER_STAGE_GROUP)) return fail(c, STR_ER_EINVAL, "STR_ER_WANT_LINE_MAP needs STR_ER_STAGE_GROUP");
-    if ((stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP)) && b_in.frame_wh.empty())
-        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP need frames (not the per-plane calls or the strip path)");
-    if ((stages & STR_ER_STAGE_OCR_LINES) && !(c->svm_loaded && c->svm.dim == 1800))
-        return fail(c, STR_ER_ESTATE, "STR_ER_STAGE_OCR_LINES needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)");
-    if ((stages & STR_ER_STAGE_TRACK) && b.planes_per_image <= 0)
-        return fail(c, STR_ER_EINVAL, "STR_ER_STAGE_TRACK needs BGR frames (calc_color reads the YCrCb image)");
-
-    const DetectParams dp = make_dp(c);
-    hipStream_t s = c->stream;
-    { const int rcu = upload_layout(c, b); if (rcu != STR_ER_OK) return rcu; }
-    BatchDev bd = make_batchdev(c, b);
+// ---- every kernel of the batch enqueued, the counters back on the host, the batch slot given back ----
+static int enqueue_batch(BatchRun &R, BatchSlot &slot, bool pre_recorded)
+{
+    str_er_ctx    *c = R.c;
+    const Batch   &b = R.b;
+    const uint32_t stages = R.stages;
+    const int      np = R.np;
+    R.dp = make_dp(c);
+    const DetectParams &dp = R.dp;
+    hipStream_t s = R.s = c->stream;
+    { const int rcu = upload_layout(c, R.b); if (rcu != STR_ER_OK) return rcu; }
+    BatchDev &bd = R.bd = make_batchdev(c, b);
     if (!pre_recorded) { c->n_ev = 0; c->profile.clear(); rec(c, "begin", nullptr, true); }
 
     // developer aid (tools/dev_exposed.py): STR_ER_DEBUG_STOP_AFTER=n ends the call (with an error) behind stage n -- 0 channels + pyramid, 1 tile trees, 2 group,
@@ -852,8 +851,8 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
     static const int dbg_stop = [] { const char *e = std::getenv("STR_ER_DEBUG_STOP_AFTER"); return e ? std::atoi(e) : -1; }();
 #define DBG_STOP(n) do { if (dbg_stop == (n)) { (void)wait_stream(c, s); return fail(c, STR_ER_ESTATE, "STR_ER_DEBUG_STOP_AFTER"); } } while (0)
     DBG_STOP(0);
-    if (import_trees) {
-        const int rci = (*import_trees)(b, bd);
+    if (R.import_trees) {
+        const int rci = (*R.import_trees)(b, bd);
         if (rci != STR_ER_OK) return rci;
         rec(c, "tile_tree");
     } else {
@@ -868,33 +867,34 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
         std::fprintf(stderr, "[str_er] tile_tree alone: %.4f ms\n", ms);
         return fail(c, STR_ER_ESTATE, "STR_ER_DEBUG_TILE_ONLY is set");
     }
-    if (grouped && b.n_groups) {
+    if (R.grouped && b.n_groups) {
         const int variant = c->dbg_group[2] >= 0 ? c->dbg_group[2] : (c->tile_sparse ? 4 : 6);       // (measured, tools/dev_groups.sh: 2048 records, 1024 lanes on text-like batches)
         // Large text-like batches: a launch per class of planes.  The groups of the chroma planes hold ~150 records: 512 slots and 256 lanes (16 KB of LDS) -- a
         // group that does overflow is k_seam_undone's.  With six batches in flight k_group_merge cost the line its WHOLE isolated time (tools/dev_exposed.py with
         // STR_ER_DEBUG_STOP_AFTER: 0.30 of 0.33 ms per 32-frame batch, where seam / resolve / reduce cost half of theirs): the tile kernels hold all 160 KB of a
         // compute unit's LDS, and a workgroup that wants 64 KB and 16 wave slots waits until four of theirs have left it.  13.0 -> 13.3 k frames/s.
-        if (big_groups && c->dbg_group[2] < 0 && c->n_groups_small && c->h_group_list.size() == b.n_groups) {
+        if (R.big_groups && c->dbg_group[2] < 0 && c->n_groups_small && c->h_group_list.size() == b.n_groups) {
             launch_group_merge(s, bd, 0, c->d_group_list, c->n_groups_small);
             launch_group_merge(s, bd, variant, c->d_group_list + c->n_groups_small, b.n_groups - c->n_groups_small);
         } else launch_group_merge(s, bd, variant);
     }
     rec(c, "group");
     DBG_STOP(2);
-    if (!import_trees) launch_seam(s, bd, !c->tile_sparse);
+    if (!R.import_trees) launch_seam(s, bd, !c->tile_sparse);
     rec(c, "seam");
     DBG_STOP(3);
     launch_resolve(s, bd);                            rec(c, "resolve");
     DBG_STOP(4);
     launch_reduce(s, bd);                             rec(c, "accumulate");
     DBG_STOP(5);
+#undef DBG_STOP
     launch_root(s, bd, dp);
     launch_select(s, bd, dp);
     launch_kept(s, bd, dp);                           rec(c, "select", nullptr, true);
-    const int i_extract = c->n_ev - 1;
+    R.i_extract = c->n_ev - 1;
     if (stages & STR_ER_STAGE_NMS) launch_nms(s, bd, dp);
     rec(c, "nms", nullptr, true);
-    const int i_nms = c->n_ev - 1;
+    R.i_nms = c->n_ev - 1;
     const bool alt_pass = (stages & STR_ER_STAGE_NMS) && c->prm.sibling_order == 0;
     if (alt_pass) {       // beside classify: it only decides whether a tie needs the flood order walk
         HIP_TRY(c, hipEventRecord(c->ev_fork, s));
@@ -908,40 +908,71 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
     }
     // everything after NMS reads the pools: enqueued once; if sibling ties had to be decided by a flood order walk, the planes whose
     // pool that changed are classified again (the others keep their records).  calc_color + er_track run when the candidates are final
-    // and the host knows how many of them are strong / weak (below): the colour pass is sized for exactly those boxes.
+    // and the host knows how many of them are strong / weak (result_track): the colour pass is sized for exactly those boxes.
     if (stages & STR_ER_STAGE_NMS) {
         launch_cand_prefix(s, bd);
         launch_classify(s, bd, dp, c->casc[0].dev, c->casc[1].dev, (stages & STR_ER_STAGE_CLASSIFY) ? 1 : 0, nullptr, nullptr, np <= SPEC_PLANES);
     }
     rec(c, "classify", nullptr, true);
-    const int i_cls = c->n_ev - 1;
-    int       i_trk = -1;
+    R.i_cls = c->n_ev - 1;
     // the scorer of STR_ER_STAGE_OCR behind classify, sized from the last batch (ocr_stage): no trip to the host between the two, like the reference's
     // call site (src/ER.cpp:728-735)
-    size_t ocr_cap = 0, ocr_cap2 = 0;
-    bool   cands_remade = false;
     if ((stages & STR_ER_STAGE_OCR) && c->ocr_spec && c->ocr_last_n > 0 && c->pool_total) {
-        ocr_cap = align_up(c->ocr_last_n + c->ocr_last_n / 8 + 256, 128);
-        const int rco = ocr_stage(c, bd, ocr_cap, s, false);
+        R.ocr_cap = align_up(c->ocr_last_n + c->ocr_last_n / 8 + 256, 128);
+        const int rco = ocr_stage(c, bd, R.ocr_cap, s, false);
         if (rco != STR_ER_OK) return rco;
     }
     if (alt_pass) HIP_TRY(c, hipStreamWaitEvent(s, c->ev_join, 0));
     HIP_TRY(c, hipGetLastError());
-    const CandRec *spec_src = nullptr;
-    uint32_t       spec_n = 0;
     if ((stages & STR_ER_STAGE_NMS) && np <= SPEC_PLANES && c->pool_total && c->last_total <= SPEC_CANDS) {
-        spec_src = c->d_cands; spec_n = (uint32_t)std::min<size_t>(SPEC_CANDS, c->pool_total);
+        R.spec_src = c->d_cands; R.spec_n = (uint32_t)std::min<size_t>(SPEC_CANDS, c->pool_total);
     }
     if (np <= SPEC_PLANES) {
         // a call of a frame or two: counters and (if they are likely to fit) the candidate records go to the page-locked block in one launch
-        launch_results_to_host(s, c->d_zero, c->h_zero, 256 + sizeof(PlaneCtr) * np, spec_src, spec_src ? c->h_cands_spec : nullptr, spec_n, c->d_total);
+        launch_results_to_host(s, c->d_zero, c->h_zero, 256 + sizeof(PlaneCtr) * np, R.spec_src, R.spec_src ? c->h_cands_spec : nullptr, R.spec_n, c->d_total);
         HIP_TRY(c, hipGetLastError());
     } else {
         HIP_TRY(c, hipMemcpyAsync(c->h_zero, c->d_zero, 256 + sizeof(PlaneCtr) * np, hipMemcpyDeviceToHost, s));        // (counters of the batch + plane counters: one block)
     }
     HIP_TRY(c, wait_stream(c, s));
     slot.give();                       // the batch's kernels are done: what follows on the host (counters, tie walks, results) leaves the GPU to the other calls
-    if (c->n_t2_tiles && !import_trees) {     // tiles k_tile_tree2 handed back: if they are many, the chroma planes stay with k_tile_tree for a while
+    return STR_ER_OK;
+}
+
+// the kept-node table (the counter says how many nodes the plane has) and the pool (it does not: double) grown when a plane overflowed them: REPEAT
+static int grow_tables(const BatchRun &R)
+{
+    str_er_ctx *c = R.c;
+    if (!c->auto_caps) return STR_ER_OK;
+    double need_k = 0;
+    bool   more_pool = false;
+    for (int i = 0; i < R.np; ++i) {
+        const double px = (double)((size_t)R.b.planes[i].tiles_x * R.b.planes[i].tiles_y * TILE_PX);
+        if (c->h_ctr[i].overflow & 1u) need_k = std::max(need_k, (double)c->h_ctr[i].n_kept / px);
+        else if (c->h_ctr[i].overflow & 2u) more_pool = true;
+    }
+    if (need_k == 0 && !more_pool) return STR_ER_OK;
+    const double kept0 = c->kept_share, pool0 = c->pool_share;
+    if (need_k > 0) c->kept_share = std::min(1.0, std::max(c->kept_share * 1.5, need_k * 1.25));
+    if (more_pool) {
+        // (the pool is a subset of the kept nodes: past the kept share it is the kept table that has to grow with it)
+        c->pool_share = std::min(1.0, c->pool_share * 2.0);
+        if (c->pool_share > c->kept_share) c->kept_share = c->pool_share;
+    }
+    if (c->kept_share == kept0 && c->pool_share == pool0)
+        return fail(c, STR_ER_ECAPACITY, "kept-node / pool tables exhausted at one entry per pixel (internal error)");
+    return REPEAT;          // (re-laid out, tables re-allocated by layout_batch)
+}
+
+// ---- after the wait: the tree stats, the tables grown where a plane overflowed them (REPEAT), the NMS tie pass ----
+static int settle_batch(BatchRun &R)
+{
+    str_er_ctx    *c = R.c;
+    const Batch   &b = R.b;
+    const uint32_t stages = R.stages;
+    const int      np = R.np;
+    hipStream_t    s = R.s;
+    if (c->n_t2_tiles && !R.import_trees) {     // tiles k_tile_tree2 handed back: if they are many, the chroma planes stay with k_tile_tree for a while
         const uint32_t fbn = c->h_total[1];
         c->t2_tiles_total += c->n_t2_tiles; c->t2_fb_total += fbn;
         if (c->t2_mode == 1 && (uint64_t)fbn * 8u > c->n_t2_tiles) c->t2_backoff = 32;
@@ -969,84 +1000,56 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
                 const int rcn = alloc_node_records(c, want);
                 if (rcn != STR_ER_OK) return rcn;
             }
-            if (ev_entry >= 0) { c->n_ev = ev_entry; c->profile.resize((size_t)ev_entry); }
-            return run_batch(c, b_in, stages, out, t_start, pre_recorded, import_trees, attempt + 1);
+            return REPEAT;
         }
     }
-    // the same for the kept-node table (the counter says how many nodes the plane has) and the pool (it does not: double).  Checked here and
-    // once more after the tie pass, whose pools can be larger than the first pass's.
-    auto grow_tables = [&](bool &again) -> int {
-        again = false;
-        if (!c->auto_caps) return STR_ER_OK;
-        double need_k = 0;
-        bool   more_pool = false;
-        for (int i = 0; i < np; ++i) {
-            const double px = (double)((size_t)b.planes[i].tiles_x * b.planes[i].tiles_y * TILE_PX);
-            if (c->h_ctr[i].overflow & 1u) need_k = std::max(need_k, (double)c->h_ctr[i].n_kept / px);
-            else if (c->h_ctr[i].overflow & 2u) more_pool = true;
-        }
-        if (need_k == 0 && !more_pool) return STR_ER_OK;
-        const double kept0 = c->kept_share, pool0 = c->pool_share;
-        if (need_k > 0) c->kept_share = std::min(1.0, std::max(c->kept_share * 1.5, need_k * 1.25));
-        if (more_pool) {
-            // (the pool is a subset of the kept nodes: past the kept share it is the kept table that has to grow with it)
-            c->pool_share = std::min(1.0, c->pool_share * 2.0);
-            if (c->pool_share > c->kept_share) c->kept_share = c->pool_share;
-        }
-        if (c->kept_share == kept0 && c->pool_share == pool0)
-            return fail(c, STR_ER_ECAPACITY, "kept-node / pool tables exhausted at one entry per pixel (internal error)");
-        again = true;
-        return STR_ER_OK;
-    };
-    {
-        bool again = false;
-        const int rcg = grow_tables(again);
-        if (rcg != STR_ER_OK) return rcg;
-        if (again) {
-            if (ev_entry >= 0) { c->n_ev = ev_entry; c->profile.resize((size_t)ev_entry); }
-            return run_batch(c, b_in, stages, out, t_start, pre_recorded, import_trees, attempt + 1);      // (re-laid out, tables re-allocated on entry)
-        }
-    }
+    // the kept-node table and the pool: checked here and once more after the tie pass, whose pools can be larger than the first pass's
+    { const int rcg = grow_tables(R); if (rcg != STR_ER_OK) return rcg; }
     if ((stages & STR_ER_STAGE_NMS) && c->prm.sibling_order == 0) {
         bool replayed = false;
         const auto tr0 = std::chrono::steady_clock::now();
-        const int rcr = resolve_sibling_ties(c, b, bd, dp, replayed);
+        const int rcr = resolve_sibling_ties(c, b, R.bd, R.dp, replayed);
         if (rcr != STR_ER_OK) return rcr;
         const auto tr1 = std::chrono::steady_clock::now();
         if (replayed && c->dbg_stats) std::fprintf(stderr, "[str_er] tie resolution (copies + walk + NMS pass): %.1f ms\n", std::chrono::duration<double, std::milli>(tr1 - tr0).count());
         if (replayed) {
-            cands_remade = true;
+            R.cands_remade = true;
             hipStream_t sp = c->prio ? c->prio : s;         // same stream as the tie pass: ordered behind it
             const CandRec *first = c->d_cands;
             std::swap(c->d_cands, c->d_cands2);
             std::swap(c->d_cand_plane, c->d_cand_plane2);
-            bd = make_batchdev(c, b);
+            R.bd = make_batchdev(c, b);
             uint32_t *n_redo = c->d_redo + c->pool_total;
-            launch_cand_reprefix(sp, bd, first, c->d_redo, n_redo);
-            launch_classify(sp, bd, dp, c->casc[0].dev, c->casc[1].dev, (stages & STR_ER_STAGE_CLASSIFY) ? 1 : 0, c->d_redo, n_redo, true);
-            if (ocr_cap && *ocr_pinned(c, ocr_cap).count <= ocr_cap) {
+            launch_cand_reprefix(sp, R.bd, first, c->d_redo, n_redo);
+            launch_classify(sp, R.bd, R.dp, c->casc[0].dev, c->casc[1].dev, (stages & STR_ER_STAGE_CLASSIFY) ? 1 : 0, c->d_redo, n_redo, true);
+            if (R.ocr_cap && *ocr_pinned(c, R.ocr_cap).count <= R.ocr_cap) {
                 // the batch was scored behind classify: the candidates of the re-made planes are scored behind THEIR classify, again without a trip to the
                 // host -- as many as the device lists (the scratch is sized for the whole batch)
-                ocr_cap2 = ocr_cap;
-                const int rco = ocr_stage(c, bd, ocr_cap2, sp, true, c->d_redo, n_redo, 1);
+                R.ocr_cap2 = R.ocr_cap;
+                const int rco = ocr_stage(c, R.bd, R.ocr_cap2, sp, true, c->d_redo, n_redo, 1);
                 if (rco != STR_ER_OK) return rco;
             }
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipMemcpyAsync(c->h_zero, c->d_zero, 256 + sizeof(PlaneCtr) * np, hipMemcpyDeviceToHost, sp));
             HIP_TRY(c, wait_stream(c, sp));
             if (c->dbg_stats) std::fprintf(stderr, "[str_er] classify again after the tie pass: %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr1).count());
-            bool again = false;             // (a pool of the tie pass did not fit: same remedy as above)
-            const int rcg = grow_tables(again);
-            if (rcg != STR_ER_OK) return rcg;
-            if (again) {
+            const int rcg = grow_tables(R);             // (a pool of the tie pass did not fit: same remedy as above)
+            if (rcg == REPEAT) {
                 std::swap(c->d_cands, c->d_cands2);         // (back to the buffers the first pass writes)
                 std::swap(c->d_cand_plane, c->d_cand_plane2);
-                if (ev_entry >= 0) { c->n_ev = ev_entry; c->profile.resize((size_t)ev_entry); }
-                return run_batch(c, b_in, stages, out, t_start, pre_recorded, import_trees, attempt + 1);
             }
+            if (rcg != STR_ER_OK) return rcg;
         }
     }
+    return STR_ER_OK;
+}
 
+// ---- the adaptive settings for the next batch (and the developer's statistics of this one) ----
+static int adapt_next(const BatchRun &R)
+{
+    str_er_ctx  *c = R.c;
+    const Batch &b = R.b;
+    const int    np = R.np;
     if (c->dbg_stats) {     // developer aid: how many nodes left the tiles
         unsigned long long tot = 0, created = 0;
         int n_tied = 0, n_rel = 0;
@@ -1088,179 +1091,205 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
         if (per_tile > 320.0) c->tile_sparse = false;
         else if (per_tile < 240.0) c->tile_sparse = true;
     }
-    str_er_result *r = new (std::nothrow) str_er_result();
-    if (!r) return fail(c, STR_ER_ENOMEM, "result allocation");
+    return STR_ER_OK;
+}
+
+// ---- the result: candidates first (the records that came back with the counters, or a copy) ----
+static int result_cands(const BatchRun &R, str_er_result *r)
+{
+    str_er_ctx    *c = R.c;
     const uint32_t total = *c->h_total;
-    c->last_total = total; c->last_valid = (stages & STR_ER_STAGE_NMS) != 0;
+    c->last_total = total; c->last_valid = (R.stages & STR_ER_STAGE_NMS) != 0;
     r->cands.resize(total);
-    r->cand_off.assign(np + 1, 0);
-    r->planes.resize(np);
-    if (total && spec_src == c->d_cands && total <= spec_n)        // (same buffer as at the time of the copy: no tie pass re-made the records)
+    r->cand_off.assign(R.np + 1, 0);
+    r->planes.resize(R.np);
+    if (total && R.spec_src == c->d_cands && total <= R.spec_n)        // (same buffer as at the time of the copy: no tie pass re-made the records)
         std::memcpy(r->cands.data(), c->h_cands_spec, sizeof(CandRec) * (size_t)total);
     else if (total)
-        if (hipMemcpyAsync(r->cands.data(), c->d_cands, sizeof(CandRec) * (size_t)total, hipMemcpyDeviceToHost, s) != hipSuccess) {
-            delete r; return fail(c, STR_ER_EHIP, "candidate copy failed");
-        }
-    if ((stages & STR_ER_STAGE_TRACK)) {
-        // calc_color + er_track on the final candidates: the strong / weak ones are listed, their boxes' Otsu thresholds and masked colour means
-        // computed a wave per box (big boxes by many workgroups), then er_track per image
-        size_t n_cls = 0;
-        for (int i = 0; i < np; ++i) n_cls += c->h_ctr[i].n_strong + c->h_ctr[i].n_weak;
-        rec(c, "track_host_gap", nullptr, true);
-        if (total) {
-            const int    n_img = np / b.planes_per_image;
-            const size_t o_list = 0, o_cs = align_up(4 * ((size_t)total + OCR_LIST_HDR) + 256, 256);
-            const int    rcs = ensure_scratch(c, o_cs + calc_color_scratch_bytes(n_cls));
-            if (rcs != STR_ER_OK) { delete r; return rcs; }
-            uint8_t  *sc = static_cast<uint8_t *>(c->d_scratch);
-            uint32_t *d_list = reinterpret_cast<uint32_t *>(sc + o_list);
-            if (hipMemsetAsync(c->d_track, 0, sizeof(TrackRec) * (size_t)total, s) != hipSuccess) { delete r; return fail(c, STR_ER_EHIP, "track reset failed"); }
-            if (n_cls) {
-                launch_ocr_list(s, bd, (uint32_t)total, d_list);
-                OcrSrc src{};
-                src.recs = bd.cands; src.list = d_list + OCR_LIST_HDR; src.planes = bd.planes;
-                launch_calc_color(s, src, ColorSrc{}, (int)n_cls, c->d_track, sc + o_cs);
-            }
-            launch_group_ranges(s, bd, b.planes_per_image, n_img, c->d_ranges);
-            launch_er_track(s, bd.cands, c->d_track, c->d_track_list, c->d_ranges, n_img);
-        }
-        rec(c, "track", nullptr, true);
-        i_trk = c->n_ev - 1;
-        r->tracks.resize(total);
-        r->have_tracks = true;
-        static_assert(sizeof(str_er_track) == sizeof(TrackRec), "track record layout");
-        if (total && (wait_stream(c, s) != hipSuccess ||          // (wait, then copy: see the OCR stage below)
-                      hipMemcpyAsync(r->tracks.data(), c->d_track, sizeof(TrackRec) * (size_t)total, hipMemcpyDeviceToHost, s) != hipSuccess)) {
-            delete r; return fail(c, STR_ER_EHIP, "track copy failed");
-        }
-    }
-    double t_group_s = 0;
-    if (stages & STR_ER_STAGE_GROUP) {
-        const auto tg0 = std::chrono::steady_clock::now();
-        if (wait_stream(c, s) != hipSuccess) { delete r; return fail(c, STR_ER_EHIP, "sync before grouping"); }
-        std::vector<uint32_t> img;
-        const int n_img = np / b.planes_per_image;
-        uint32_t off2 = 0;
-        for (int g = 0; g < n_img; ++g) {
-            img.push_back(off2);
-            for (int k = 0; k < b.planes_per_image; ++k) off2 += c->h_ctr[g * b.planes_per_image + k].n_pool;
-            img.push_back(off2);
-        }
-        const int rcg = (stages & STR_ER_GROUP_OVERLAP_SUP) ? group_phase_overlap(c, img, (stages & STR_ER_GROUP_INNER_SUP) != 0, r)
-                                                            : group_phase(c, c->d_cands, c->d_track, img, (stages & STR_ER_GROUP_INNER_SUP) != 0, r);
-        if (rcg != STR_ER_OK) { delete r; return rcg; }
-        t_group_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - tg0).count();
-    }
-    const auto t_ocr0 = std::chrono::steady_clock::now();
-    if (stages & STR_ER_STAGE_OCR_LINES) {
-        const int rcl = line_ocr_phase(c, c->d_planes, r);
-        if (rcl != STR_ER_OK) { delete r; return rcl; }
-    }
-    if (stages & STR_ER_STAGE_OCR) r->have_ocr = true;      // (an empty table, not a missing one, when there are no candidates)
-    if ((stages & STR_ER_STAGE_OCR) && total) {
-        size_t n_ocr = 0;
-        for (int i = 0; i < np; ++i) n_ocr += c->h_ctr[i].n_strong + c->h_ctr[i].n_weak;
-        r->ocr_label.assign(total, -1);
-        r->ocr_prob.assign(total, 0.0);
-        r->have_ocr = true;
-        // scored behind classify already?  Only if the guess covered the batch.  If an NMS tie pass re-made the candidates of a few planes since, the scores of
-        // the other planes are still good (their records were moved, PlaneCtr::cand_base_old -> cand_base) and only the re-made planes are scored again
-        const uint32_t early_n = ocr_cap ? *ocr_pinned(c, ocr_cap).count : 0u;
-        const bool     early = ocr_cap != 0 && early_n <= ocr_cap && (cands_remade || early_n == n_ocr);
-        auto scatter = [&](size_t cap, size_t n, int region = 0) {
-            const OcrPinned hp = ocr_pinned(c, cap, region);
-            for (size_t i = 0; i < n; ++i) {
-                if (hp.list[i] >= total) continue;
-                r->ocr_label[hp.list[i]] = hp.label[i];
-                r->ocr_prob[hp.list[i]] = hp.prob[i];
-            }
-        };
-        auto run_stage = [&](size_t cap, size_t expect, const uint32_t *from, const uint32_t *from_n) -> int {
-            bd = make_batchdev(c, b);
-            hipStream_t so = (cands_remade && c->prio) ? c->prio : s;        // (behind the tie pass and its classify)
-            const int rc2 = ocr_stage(c, bd, cap, so, ocr_cap != 0, from, from_n);
-            if (rc2 != STR_ER_OK) return rc2;
-            if (wait_stream(c, so) != hipSuccess) return fail(c, STR_ER_EHIP, "OCR stage failed");
-            if (*ocr_pinned(c, cap).count != expect)
-                return fail(c, STR_ER_EHIP, "OCR stage: the device listed a different number of strong / weak ERs than the plane counters say (internal error)");
-            return STR_ER_OK;
-        };
-        if (ocr_cap) { if (early && !cands_remade) ++c->n_ocr_spec; else ++c->n_ocr_redo; }
-        if (early && !cands_remade) {
-            scatter(ocr_cap, n_ocr);
-        } else if (early) {
-            const OcrPinned hp = ocr_pinned(c, ocr_cap);
-            size_t n2 = 0;
-            int    pl = 0;
-            for (int i = 0; i < np; ++i) if (c->h_ctr[i].pool_changed) n2 += c->h_ctr[i].n_strong + c->h_ctr[i].n_weak;
-            for (size_t i = 0; i < early_n; ++i) {                // (the list is in candidate order: the planes come by)
-                const uint32_t old = hp.list[i];
-                while (pl + 1 < np && c->h_ctr[pl + 1].cand_base_old <= old) ++pl;
-                const PlaneCtr &pc = c->h_ctr[pl];
-                if (pc.pool_changed || old < pc.cand_base_old) continue;
-                const uint32_t now = old - pc.cand_base_old + pc.cand_base;
-                if (now >= total) continue;
-                r->ocr_label[now] = hp.label[i];
-                r->ocr_prob[now] = hp.prob[i];
-            }
-            if (n2 && ocr_cap2 && n2 <= ocr_cap2 && *ocr_pinned(c, ocr_cap2, 1).count == n2) {
-                scatter(ocr_cap2, n2, 1);
-            } else if (n2) {
-                const int rc2 = run_stage(n2, n2, c->d_redo, c->d_redo + c->pool_total);
-                if (rc2 != STR_ER_OK) { delete r; return rc2; }
-                scatter(n2, n2);
-            }
-        } else if (n_ocr) {
-            // the slow way: the host knows the number now
-            const int rc2 = run_stage(n_ocr, n_ocr, nullptr, nullptr);
-            if (rc2 != STR_ER_OK) { delete r; return rc2; }
-            scatter(n_ocr, n_ocr);
-        }
-        c->ocr_last_n = n_ocr;
-    }
-    const double t_ocr_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ocr0).count();
-    const bool want_nodes = (stages & STR_ER_WANT_NODES) != 0;
-    if (want_nodes) {
-        r->nodes.resize(np);
-        for (int i = 0; i < np; ++i) {
-            const PlaneDesc &pd = b.planes[i];
-            const uint32_t nk = c->h_ctr[i].n_kept;
-            r->nodes[i].resize(nk);
-            // gather the SoA kept arrays into records on the host side of the copy
-            std::vector<uint32_t> key(nk), area(nk); std::vector<int32_t> par(nk); std::vector<uint16_t> box(4 * (size_t)nk);
-            std::vector<uint8_t> lev(nk);
-            hipError_t e = hipSuccess;
-            if (nk) {
-                e = hipMemcpyAsync(key.data(), c->ka.key + pd.kept_base, 4 * (size_t)nk, hipMemcpyDeviceToHost, s);
-                if (e == hipSuccess) e = hipMemcpyAsync(area.data(), c->ka.area + pd.kept_base, 4 * (size_t)nk, hipMemcpyDeviceToHost, s);
-                if (e == hipSuccess) e = hipMemcpyAsync(par.data(), c->ka.parent + pd.kept_base, 4 * (size_t)nk, hipMemcpyDeviceToHost, s);
-                if (e == hipSuccess) e = hipMemcpyAsync(box.data(), c->ka.box + 4 * (size_t)pd.kept_base, 8 * (size_t)nk, hipMemcpyDeviceToHost, s);
-                if (e == hipSuccess) e = hipMemcpyAsync(lev.data(), c->ka.level + pd.kept_base, (size_t)nk, hipMemcpyDeviceToHost, s);
-                if (e == hipSuccess) e = wait_stream(c, s);
-            }
-            if (e != hipSuccess) { delete r; return fail(c, STR_ER_EHIP, std::string("node copy: ") + hipGetErrorString(e)); }
-            // order by (key, level) so the table is deterministic; remap parents and the root
-            std::vector<uint32_t> order(nk), rank(nk);
-            for (uint32_t k = 0; k < nk; ++k) order[k] = k;
-            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t bb) {
-                return key[a] != key[bb] ? key[a] < key[bb] : lev[a] < lev[bb]; });
-            for (uint32_t k = 0; k < nk; ++k) rank[order[k]] = k;
-            for (uint32_t k = 0; k < nk; ++k) {
-                const uint32_t o = order[k];
-                str_er_node &n = r->nodes[i][k];
-                n.key = key[o]; n.parent = (int32_t)rank[(uint32_t)par[o]]; n.area = (int32_t)area[o];
-                n.x = box[4 * o]; n.y = box[4 * o + 1]; n.w = box[4 * o + 2]; n.h = box[4 * o + 3];
-                n.level = lev[o]; n.flags = (o == c->h_ctr[i].root_slot) ? 1 : 0; n.reserved = 0;
-            }
-            c->h_ctr[i].root_slot = nk ? rank[c->h_ctr[i].root_slot] : 0;
-        }
-    }
-    HIP_TRY(c, wait_stream(c, s));
+        if (hipMemcpyAsync(r->cands.data(), c->d_cands, sizeof(CandRec) * (size_t)total, hipMemcpyDeviceToHost, R.s) != hipSuccess)
+            return fail(c, STR_ER_EHIP, "candidate copy failed");
+    return STR_ER_OK;
+}
 
+// STR_ER_STAGE_TRACK: calc_color + er_track on the final candidates: the strong / weak ones are listed, their boxes' Otsu thresholds and masked colour
+// means computed a wave per box (big boxes by many workgroups), then er_track per image
+static int result_track(BatchRun &R, str_er_result *r)
+{
+    str_er_ctx  *c = R.c;
+    const Batch &b = R.b;
+    const int    np = R.np;
+    hipStream_t  s = R.s;
+    const uint32_t total = (uint32_t)r->cands.size();
+    size_t n_cls = 0;
+    for (int i = 0; i < np; ++i) n_cls += c->h_ctr[i].n_strong + c->h_ctr[i].n_weak;
+    rec(c, "track_host_gap", nullptr, true);
+    if (total) {
+        const int    n_img = np / b.planes_per_image;
+        const size_t o_list = 0, o_cs = align_up(4 * ((size_t)total + OCR_LIST_HDR) + 256, 256);
+        const int    rcs = ensure_scratch(c, o_cs + calc_color_scratch_bytes(n_cls));
+        if (rcs != STR_ER_OK) return rcs;
+        uint8_t  *sc = static_cast<uint8_t *>(c->d_scratch);
+        uint32_t *d_list = reinterpret_cast<uint32_t *>(sc + o_list);
+        if (hipMemsetAsync(c->d_track, 0, sizeof(TrackRec) * (size_t)total, s) != hipSuccess) return fail(c, STR_ER_EHIP, "track reset failed");
+        if (n_cls) {
+            launch_ocr_list(s, R.bd, (uint32_t)total, d_list);
+            OcrSrc src{};
+            src.recs = R.bd.cands; src.list = d_list + OCR_LIST_HDR; src.planes = R.bd.planes;
+            launch_calc_color(s, src, ColorSrc{}, (int)n_cls, c->d_track, sc + o_cs);
+        }
+        launch_group_ranges(s, R.bd, b.planes_per_image, n_img, c->d_ranges);
+        launch_er_track(s, R.bd.cands, c->d_track, c->d_track_list, c->d_ranges, n_img);
+    }
+    rec(c, "track", nullptr, true);
+    R.i_trk = c->n_ev - 1;
+    r->tracks.resize(total);
+    r->have_tracks = true;
+    static_assert(sizeof(str_er_track) == sizeof(TrackRec), "track record layout");
+    if (total && (wait_stream(c, s) != hipSuccess ||          // (wait, then copy: see the OCR stage in result_ocr)
+                  hipMemcpyAsync(r->tracks.data(), c->d_track, sizeof(TrackRec) * (size_t)total, hipMemcpyDeviceToHost, s) != hipSuccess))
+        return fail(c, STR_ER_EHIP, "track copy failed");
+    return STR_ER_OK;
+}
+
+// STR_ER_STAGE_GROUP: er_grouping per image
+static int result_group(BatchRun &R, str_er_result *r)
+{
+    str_er_ctx *c = R.c;
+    const auto  tg0 = std::chrono::steady_clock::now();
+    if (wait_stream(c, R.s) != hipSuccess) return fail(c, STR_ER_EHIP, "sync before grouping");
+    std::vector<uint32_t> img;
+    const int ppi = R.b.planes_per_image, n_img = R.np / ppi;
+    uint32_t off2 = 0;
+    for (int g = 0; g < n_img; ++g) {
+        img.push_back(off2);
+        for (int k = 0; k < ppi; ++k) off2 += c->h_ctr[g * ppi + k].n_pool;
+        img.push_back(off2);
+    }
+    const bool inner_sup = (R.stages & STR_ER_GROUP_INNER_SUP) != 0;
+    const int  rcg = (R.stages & STR_ER_GROUP_OVERLAP_SUP) ? group_phase_overlap(c, img, inner_sup, r) : group_phase(c, c->d_cands, c->d_track, img, inner_sup, r);
+    if (rcg != STR_ER_OK) return rcg;
+    R.t_group_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - tg0).count();
+    return STR_ER_OK;
+}
+
+// STR_ER_STAGE_OCR: the scores of the strong / weak candidates -- scored behind classify already (ocr_cap), or scored now
+static int result_ocr(BatchRun &R, str_er_result *r)
+{
+    str_er_ctx  *c = R.c;
+    const int    np = R.np;
+    const size_t total = r->cands.size();
+    r->have_ocr = true;      // (an empty table, not a missing one, when there are no candidates)
+    if (!total) return STR_ER_OK;
+    size_t n_ocr = 0;
+    for (int i = 0; i < np; ++i) n_ocr += c->h_ctr[i].n_strong + c->h_ctr[i].n_weak;
+    r->ocr_label.assign(total, -1);
+    r->ocr_prob.assign(total, 0.0);
+    // scored behind classify already?  Only if the guess covered the batch.  If an NMS tie pass re-made the candidates of a few planes since, the scores of
+    // the other planes are still good (their records were moved, PlaneCtr::cand_base_old -> cand_base) and only the re-made planes are scored again
+    const size_t   ocr_cap = R.ocr_cap, ocr_cap2 = R.ocr_cap2;
+    const bool     cands_remade = R.cands_remade;
+    const uint32_t early_n = ocr_cap ? *ocr_pinned(c, ocr_cap).count : 0u;
+    const bool     early = ocr_cap != 0 && early_n <= ocr_cap && (cands_remade || early_n == n_ocr);
+    auto scatter = [&](size_t cap, size_t n, int region = 0) {
+        const OcrPinned hp = ocr_pinned(c, cap, region);
+        for (size_t i = 0; i < n; ++i) {
+            if (hp.list[i] >= total) continue;
+            r->ocr_label[hp.list[i]] = hp.label[i];
+            r->ocr_prob[hp.list[i]] = hp.prob[i];
+        }
+    };
+    auto run_stage = [&](size_t cap, size_t expect, const uint32_t *from, const uint32_t *from_n) -> int {
+        R.bd = make_batchdev(c, R.b);
+        hipStream_t so = (cands_remade && c->prio) ? c->prio : R.s;        // (behind the tie pass and its classify)
+        const int rc2 = ocr_stage(c, R.bd, cap, so, ocr_cap != 0, from, from_n);
+        if (rc2 != STR_ER_OK) return rc2;
+        if (wait_stream(c, so) != hipSuccess) return fail(c, STR_ER_EHIP, "OCR stage failed");
+        if (*ocr_pinned(c, cap).count != expect)
+            return fail(c, STR_ER_EHIP, "OCR stage: the device listed a different number of strong / weak ERs than the plane counters say (internal error)");
+        return STR_ER_OK;
+    };
+    if (ocr_cap) { if (early && !cands_remade) ++c->n_ocr_spec; else ++c->n_ocr_redo; }
+    if (early && !cands_remade) {
+        scatter(ocr_cap, n_ocr);
+    } else if (early) {
+        const OcrPinned hp = ocr_pinned(c, ocr_cap);
+        size_t n2 = 0;
+        int    pl = 0;
+        for (int i = 0; i < np; ++i) if (c->h_ctr[i].pool_changed) n2 += c->h_ctr[i].n_strong + c->h_ctr[i].n_weak;
+        for (size_t i = 0; i < early_n; ++i) {                // (the list is in candidate order: the planes come by)
+            const uint32_t old = hp.list[i];
+            while (pl + 1 < np && c->h_ctr[pl + 1].cand_base_old <= old) ++pl;
+            const PlaneCtr &pc = c->h_ctr[pl];
+            if (pc.pool_changed || old < pc.cand_base_old) continue;
+            const uint32_t now = old - pc.cand_base_old + pc.cand_base;
+            if (now >= total) continue;
+            r->ocr_label[now] = hp.label[i];
+            r->ocr_prob[now] = hp.prob[i];
+        }
+        if (n2 && ocr_cap2 && n2 <= ocr_cap2 && *ocr_pinned(c, ocr_cap2, 1).count == n2) {
+            scatter(ocr_cap2, n2, 1);
+        } else if (n2) {
+            const int rc2 = run_stage(n2, n2, c->d_redo, c->d_redo + c->pool_total);
+            if (rc2 != STR_ER_OK) return rc2;
+            scatter(n2, n2);
+        }
+    } else if (n_ocr) {
+        // the slow way: the host knows the number now
+        const int rc2 = run_stage(n_ocr, n_ocr, nullptr, nullptr);
+        if (rc2 != STR_ER_OK) return rc2;
+        scatter(n_ocr, n_ocr);
+    }
+    c->ocr_last_n = n_ocr;
+    return STR_ER_OK;
+}
+
+// STR_ER_WANT_NODES: the kept-node table of every plane, gathered from the SoA kept arrays on the host side of the copy and ordered by (key, level)
+static int result_nodes(const BatchRun &R, str_er_result *r)
+{
+    str_er_ctx *c = R.c;
+    hipStream_t s = R.s;
+    r->nodes.resize(R.np);
+    for (int i = 0; i < R.np; ++i) {
+        const PlaneDesc &pd = R.b.planes[i];
+        const uint32_t nk = c->h_ctr[i].n_kept;
+        r->nodes[i].resize(nk);
+        std::vector<uint32_t> key(nk), area(nk); std::vector<int32_t> par(nk); std::vector<uint16_t> box(4 * (size_t)nk);
+        std::vector<uint8_t> lev(nk);
+        hipError_t e = hipSuccess;
+        if (nk) {
+            e = hipMemcpyAsync(key.data(), c->ka.key + pd.kept_base, 4 * (size_t)nk, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(area.data(), c->ka.area + pd.kept_base, 4 * (size_t)nk, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(par.data(), c->ka.parent + pd.kept_base, 4 * (size_t)nk, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(box.data(), c->ka.box + 4 * (size_t)pd.kept_base, 8 * (size_t)nk, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(lev.data(), c->ka.level + pd.kept_base, (size_t)nk, hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = wait_stream(c, s);
+        }
+        if (e != hipSuccess) return fail(c, STR_ER_EHIP, std::string("node copy: ") + hipGetErrorString(e));
+        // order by (key, level) so the table is deterministic; remap parents and the root
+        std::vector<uint32_t> order(nk), rank(nk);
+        for (uint32_t k = 0; k < nk; ++k) order[k] = k;
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t bb) {
+            return key[a] != key[bb] ? key[a] < key[bb] : lev[a] < lev[bb]; });
+        for (uint32_t k = 0; k < nk; ++k) rank[order[k]] = k;
+        for (uint32_t k = 0; k < nk; ++k) {
+            const uint32_t o = order[k];
+            str_er_node &n = r->nodes[i][k];
+            n.key = key[o]; n.parent = (int32_t)rank[(uint32_t)par[o]]; n.area = (int32_t)area[o];
+            n.x = box[4 * o]; n.y = box[4 * o + 1]; n.w = box[4 * o + 2]; n.h = box[4 * o + 3];
+            n.level = lev[o]; n.flags = (o == c->h_ctr[i].root_slot) ? 1 : 0; n.reserved = 0;
+        }
+        c->h_ctr[i].root_slot = nk ? rank[c->h_ctr[i].root_slot] : 0;
+    }
+    return STR_ER_OK;
+}
+
+static void result_planes(const BatchRun &R, str_er_result *r)
+{
+    const bool want_nodes = (R.stages & STR_ER_WANT_NODES) != 0;
     uint32_t off = 0;
-    for (int i = 0; i < np; ++i) {
-        const PlaneDesc &pd = b.planes[i];
-        const PlaneCtr &pc = c->h_ctr[i];
+    for (int i = 0; i < R.np; ++i) {
+        const PlaneDesc &pd = R.b.planes[i];
+        const PlaneCtr &pc = R.c->h_ctr[i];
         str_er_plane_info &pi = r->planes[i];
         pi.frame = pd.frame; pi.ch = pd.ch; pi.pyr = pd.pyr; pi.reserved0 = pi.reserved1 = 0;
         pi.width = pd.w; pi.height = pd.h;
@@ -1270,84 +1299,143 @@ int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result *
         r->cand_off[i] = off;
         off += pc.n_pool;
     }
-    r->cand_off[np] = off;
-    const uint32_t *d_mask_bits = nullptr;         // (the masks' words on the device, for the glyph crops below)
-    if (stages & (STR_ER_WANT_MASKS | STR_ER_WANT_SHAPES | STR_ER_WANT_STROKES)) {
-        // the masks of the final candidates (after any NMS tie pass): sized on the host from the records just copied, one launch per size class, one wait;
-        // with STR_ER_WANT_SHAPES / _STROKES the same launches make the descriptors, and without STR_ER_WANT_MASKS the words stay on the device
-        const bool want_masks = (stages & STR_ER_WANT_MASKS) != 0, want_shapes = (stages & STR_ER_WANT_SHAPES) != 0;
-        const bool want_strokes = (stages & STR_ER_WANT_STROKES) != 0;
-        std::vector<MaskJob> jobs(total);
-        std::vector<uint32_t> px(total);
-        uint64_t words = 0;
-        r->masks.resize(total);
-        for (uint32_t k = 0; k < total; ++k) {
-            const str_er_cand &cd = r->cands[k];
-            const PlaneDesc   &pd = b.planes[cd.plane];
-            if (cd.w > MASK_MAX_WIDTH) {
-                delete r;
-                return fail(c, STR_ER_ECAPACITY, std::string(want_masks ? "STR_ER_WANT_MASKS" : want_shapes ? "STR_ER_WANT_SHAPES" : "STR_ER_WANT_STROKES") +
-                                                     ": a candidate wider than " + std::to_string(MASK_MAX_WIDTH) + " pixels");
-            }
-            MaskJob &j = jobs[k];
-            j.pix = pd.pix; j.stride = pd.stride; j.invert = (uint32_t)pd.invert; j.plane_w = (uint32_t)pd.w; j.key = cd.key;
-            j.x = cd.x; j.y = cd.y; j.w = cd.w; j.h = cd.h; j.level = cd.level; j.idx = k; j.out_off = words; j.scratch_off = 0;
-            r->masks[k].word_off = words; r->masks[k].pitch_words = (cd.w + 31u) / 32u;
-            words += (uint64_t)cd.h * r->masks[k].pitch_words;
-        }
-        if (want_masks) r->mask_bits.resize(words);
-        if (want_shapes) r->shapes.resize(total);
-        if (want_strokes) r->strokes.resize(total);
-        const int rcm = mask_stage(c, s, jobs, words, dp.qscale, px.data(), want_masks ? r->mask_bits.data() : nullptr, &d_mask_bits,
-                                   want_shapes ? r->shapes.data() : nullptr, want_strokes ? r->strokes.data() : nullptr);
-        if (rcm != STR_ER_OK) { delete r; return rcm; }
-        for (uint32_t k = 0; k < total; ++k) r->masks[k].pixels = px[k];
-        r->have_masks = want_masks;         // (without it r->masks only places the words on the device, for the glyph crops)
-        r->have_shapes = want_shapes;
-        r->have_strokes = want_strokes;
-    }
-    if (stages & STR_ER_WANT_LINE_CROPS) {
-        // the crops of the final lines, while the call's planes are still in the workspace: laid out on the host, one launch, one wait
-        const int rcc = line_crop_phase(c, s, b, dp.qscale, (stages & STR_ER_WANT_LINE_GLYPHS) != 0, d_mask_bits, r);
-        if (rcc != STR_ER_OK) { delete r; return rcc; }
-    }
-    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP)) {
-        // the maps of the frames from the final candidates and lines: binned on the host, one launch (with the masks, if this call has none), one copy back
-        const int rct = text_map_phase(c, s, b, stages, dp.qscale, d_mask_bits, r);
-        if (rct != STR_ER_OK) { delete r; return rct; }
-    }
-    if (want_nodes) {
-        // candidates carry the device kept slot; translate to the sorted table through (key, level)
-        for (int i = 0; i < np; ++i) {
-            const auto &tbl = r->nodes[i];
-            for (uint32_t k = r->cand_off[i]; k < r->cand_off[i + 1]; ++k) {
-                str_er_cand &cd = r->cands[k];
-                auto it = std::lower_bound(tbl.begin(), tbl.end(), cd, [](const str_er_node &n, const str_er_cand &q) {
-                    return n.key != q.key ? n.key < q.key : n.level < q.level; });
-                cd.node = (it != tbl.end() && it->key == cd.key && it->level == cd.level) ? (int32_t)(it - tbl.begin()) : -1;
-            }
-        }
-        r->have_nodes = true;
-    } else {
-        for (auto &cd : r->cands) cd.node = -1;
-    }
+    r->cand_off[R.np] = off;
+}
 
+// STR_ER_WANT_MASKS / _SHAPES / _STROKES: the masks of the final candidates (after any NMS tie pass): sized on the host from the records just copied, one
+// launch per size class, one wait; with _SHAPES / _STROKES the same launches make the descriptors, and without _MASKS the words stay on the device
+// (*d_mask_bits: for the glyph crops and the maps)
+static int result_masks(const BatchRun &R, str_er_result *r, const uint32_t **d_mask_bits)
+{
+    str_er_ctx    *c = R.c;
+    const uint32_t stages = R.stages, total = (uint32_t)r->cands.size();
+    const bool want_masks = (stages & STR_ER_WANT_MASKS) != 0, want_shapes = (stages & STR_ER_WANT_SHAPES) != 0;
+    const bool want_strokes = (stages & STR_ER_WANT_STROKES) != 0;
+    std::vector<MaskJob> jobs(total);
+    std::vector<uint32_t> px(total);
+    uint64_t words = 0;
+    r->masks.resize(total);
+    for (uint32_t k = 0; k < total; ++k) {
+        const str_er_cand &cd = r->cands[k];
+        const PlaneDesc   &pd = R.b.planes[cd.plane];
+        if (cd.w > MASK_MAX_WIDTH)
+            return fail(c, STR_ER_ECAPACITY, std::string(want_masks ? "STR_ER_WANT_MASKS" : want_shapes ? "STR_ER_WANT_SHAPES" : "STR_ER_WANT_STROKES") +
+                                                 ": a candidate wider than " + std::to_string(MASK_MAX_WIDTH) + " pixels");
+        MaskJob &j = jobs[k];
+        j.pix = pd.pix; j.stride = pd.stride; j.invert = (uint32_t)pd.invert; j.plane_w = (uint32_t)pd.w; j.key = cd.key;
+        j.x = cd.x; j.y = cd.y; j.w = cd.w; j.h = cd.h; j.level = cd.level; j.idx = k; j.out_off = words; j.scratch_off = 0;
+        r->masks[k].word_off = words; r->masks[k].pitch_words = (cd.w + 31u) / 32u;
+        words += (uint64_t)cd.h * r->masks[k].pitch_words;
+    }
+    if (want_masks) r->mask_bits.resize(words);
+    if (want_shapes) r->shapes.resize(total);
+    if (want_strokes) r->strokes.resize(total);
+    const int rcm = mask_stage(c, R.s, jobs, words, R.dp.qscale, px.data(), want_masks ? r->mask_bits.data() : nullptr, d_mask_bits,
+                               want_shapes ? r->shapes.data() : nullptr, want_strokes ? r->strokes.data() : nullptr);
+    if (rcm != STR_ER_OK) return rcm;
+    for (uint32_t k = 0; k < total; ++k) r->masks[k].pixels = px[k];
+    r->have_masks = want_masks;         // (without it r->masks only places the words on the device, for the glyph crops)
+    r->have_shapes = want_shapes;
+    r->have_strokes = want_strokes;
+    return STR_ER_OK;
+}
+
+// candidates carry the device kept slot; translated to the sorted node table through (key, level) -- or -1 without STR_ER_WANT_NODES
+static void result_node_ids(const BatchRun &R, str_er_result *r)
+{
+    if (!(R.stages & STR_ER_WANT_NODES)) {
+        for (auto &cd : r->cands) cd.node = -1;
+        return;
+    }
+    for (int i = 0; i < R.np; ++i) {
+        const auto &tbl = r->nodes[i];
+        for (uint32_t k = r->cand_off[i]; k < r->cand_off[i + 1]; ++k) {
+            str_er_cand &cd = r->cands[k];
+            auto it = std::lower_bound(tbl.begin(), tbl.end(), cd, [](const str_er_node &n, const str_er_cand &q) {
+                return n.key != q.key ? n.key < q.key : n.level < q.level; });
+            cd.node = (it != tbl.end() && it->key == cd.key && it->level == cd.level) ? (int32_t)(it - tbl.begin()) : -1;
+        }
+    }
+    r->have_nodes = true;
+}
+
+static void result_times(const BatchRun &R, str_er_result *r, std::chrono::steady_clock::time_point t_start)
+{
+    str_er_ctx *c = R.c;
     float ms = 0;
     double stage_s[3] = {0, 0, 0};
-    if (hipEventElapsedTime(&ms, c->ev[0], c->ev[i_extract]) == hipSuccess) stage_s[0] = ms * 1e-3;
-    if (hipEventElapsedTime(&ms, c->ev[i_extract], c->ev[i_nms]) == hipSuccess) stage_s[1] = ms * 1e-3;
-    if (hipEventElapsedTime(&ms, c->ev[i_nms], c->ev[i_cls]) == hipSuccess) stage_s[2] = ms * 1e-3;
+    if (hipEventElapsedTime(&ms, c->ev[0], c->ev[R.i_extract]) == hipSuccess) stage_s[0] = ms * 1e-3;
+    if (hipEventElapsedTime(&ms, c->ev[R.i_extract], c->ev[R.i_nms]) == hipSuccess) stage_s[1] = ms * 1e-3;
+    if (hipEventElapsedTime(&ms, c->ev[R.i_nms], c->ev[R.i_cls]) == hipSuccess) stage_s[2] = ms * 1e-3;
     for (int i = 1; i < c->n_ev; ++i)
         if (hipEventElapsedTime(&ms, c->ev[i - 1], c->ev[i]) == hipSuccess) c->profile[i].second = ms;
     r->times[0] = stage_s[0]; r->times[1] = stage_s[1]; r->times[2] = stage_s[2];
-    if ((stages & STR_ER_STAGE_TRACK) && i_trk > 0 && hipEventElapsedTime(&ms, c->ev[i_trk - 1], c->ev[i_trk]) == hipSuccess) r->times[3] = ms * 1e-3;
-    if (stages & (STR_ER_STAGE_OCR | STR_ER_STAGE_OCR_LINES)) r->times[5] = t_ocr_s;
-    r->times[4] = t_group_s;
+    if ((R.stages & STR_ER_STAGE_TRACK) && R.i_trk > 0 && hipEventElapsedTime(&ms, c->ev[R.i_trk - 1], c->ev[R.i_trk]) == hipSuccess) r->times[3] = ms * 1e-3;
+    if (R.stages & (STR_ER_STAGE_OCR | STR_ER_STAGE_OCR_LINES)) r->times[5] = R.t_ocr_s;
+    r->times[4] = R.t_group_s;
     r->times[6] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
-    *out = r;
+}
+
+// ---- the result of a batch that has settled: every table the stages ask for ----
+static int collect_result(BatchRun &R, str_er_result *r, std::chrono::steady_clock::time_point t_start)
+{
+    str_er_ctx    *c = R.c;
+    const uint32_t stages = R.stages;
+    int rc = result_cands(R, r);
+    if (rc == STR_ER_OK && (stages & STR_ER_STAGE_TRACK)) rc = result_track(R, r);
+    if (rc == STR_ER_OK && (stages & STR_ER_STAGE_GROUP)) rc = result_group(R, r);
+    if (rc != STR_ER_OK) return rc;
+    const auto t_ocr0 = std::chrono::steady_clock::now();
+    if (stages & STR_ER_STAGE_OCR_LINES) rc = line_ocr_phase(c, c->d_planes, r);
+    if (rc == STR_ER_OK && (stages & STR_ER_STAGE_OCR)) rc = result_ocr(R, r);
+    if (rc != STR_ER_OK) return rc;
+    R.t_ocr_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_ocr0).count();
+    if ((stages & STR_ER_WANT_NODES) && (rc = result_nodes(R, r)) != STR_ER_OK) return rc;
+    HIP_TRY(c, wait_stream(c, R.s));
+    result_planes(R, r);
+    const uint32_t *d_mask_bits = nullptr;         // (the masks' words on the device, for the glyph crops and the maps)
+    if (stages & (STR_ER_WANT_MASKS | STR_ER_WANT_SHAPES | STR_ER_WANT_STROKES)) rc = result_masks(R, r, &d_mask_bits);
+    // the crops of the final lines, while the call's planes are still in the workspace: laid out on the host, one launch, one wait
+    if (rc == STR_ER_OK && (stages & STR_ER_WANT_LINE_CROPS))
+        rc = line_crop_phase(c, R.s, R.b, R.dp.qscale, (stages & STR_ER_WANT_LINE_GLYPHS) != 0, d_mask_bits, r);
+    // the maps of the frames from the final candidates and lines: binned on the host, one launch (with the masks, if this call has none), one copy back
+    if (rc == STR_ER_OK && (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP))) rc = text_map_phase(c, R.s, R.b, stages, R.dp.qscale, d_mask_bits, r);
+    if (rc != STR_ER_OK) return rc;
+    result_node_ids(R, r);
+    result_times(R, r, t_start);
+    return STR_ER_OK;
+}
+
+int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result **out,
+              std::chrono::steady_clock::time_point t_start, bool pre_recorded, const ImportHook *import_trees)
+{
+    c->last_valid = false;             // (str_er_gather_last: the candidate array is being rewritten, or re-allocated)
+    struct SpinGuard { str_er_ctx *c; int old; ~SpinGuard() { c->wait_spin_us = old; } } spin_guard{c, c->wait_spin_us};
+    c->wait_spin_us = (int)b_in.planes.size() <= SPEC_PLANES ? 2000 : 300;      // (for this call only: the guard puts the default back)
+    const int ev_entry = pre_recorded ? c->n_ev : -1;
+    // A batch whose planes outgrow their shares of the tables is laid out again with larger shares and repeated.  Every repeat raises a
+    // share (or fails), and a share stops at one entry per pixel: the repeats end; the count only guards against a slip in that argument.
+    BatchRun R{c, stages, import_trees, {}};
+    int rc = REPEAT;
+    for (int attempt = 0; rc == REPEAT; ++attempt) {
+        if (attempt > 24) return fail(c, STR_ER_ECAPACITY, "the batch was repeated 24 times with growing tables and still does not fit (internal error)");
+        if (attempt && ev_entry >= 0) { c->n_ev = ev_entry; c->profile.resize((size_t)ev_entry); }
+        R = BatchRun{c, stages, import_trees, b_in};
+        BatchSlot slot;                // (str_er_set_batch_slots: given back when the batch's kernels are done, or on any way out)
+        if ((int)b_in.planes.size() > SPEC_PLANES) slot.take();
+        rc = layout_batch(R);
+        if (rc == STR_ER_OK) rc = enqueue_batch(R, slot, pre_recorded);
+        if (rc == STR_ER_OK) rc = settle_batch(R);
+    }
+    if (rc == STR_ER_OK) rc = adapt_next(R);
+    if (rc != STR_ER_OK) return rc;
+    std::unique_ptr<str_er_result> r(new (std::nothrow) str_er_result());
+    if (!r) return fail(c, STR_ER_ENOMEM, "result allocation");
+    if ((rc = collect_result(R, r.get(), t_start)) != STR_ER_OK) return rc;
+    *out = r.release();
     {   // everything of this batch has been read: the counter block is zeroed for the context's next batch now, behind the caller's back (upload_layout)
-        const size_t need = align_up(c->zero_gd_off + b.n_groups, 256);
-        if (hipMemsetAsync(c->d_zero, 0, need, s) == hipSuccess) c->zero_clean_bytes = need;
+        const size_t need = align_up(c->zero_gd_off + R.b.n_groups, 256);
+        if (hipMemsetAsync(c->d_zero, 0, need, R.s) == hipSuccess) c->zero_clean_bytes = need;
     }
     return STR_ER_OK;
 }
@@ -1656,8 +1744,6 @@ int str_er_detect_bgr_planes(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32
 try {
     if (!c) return STR_ER_EINVAL;
     if (!plane_select || n_select != c->ppf) return fail(c, STR_ER_EINVAL, "plane_select needs one flag per logical plane of a frame (levels x channels of the context)");
-    if (stages & (STR_ER_STAGE_TRACK | STR_ER_STAGE_GROUP | STR_ER_STAGE_OCR_LINES))
-        return fail(c, STR_ER_EINVAL, "er_track / er_grouping read every plane of an image: not with a plane subset");
     bool any = false;
     for (int i = 0; i < n_select; ++i) any |= plane_select[i] != 0;
     if (!any) return fail(c, STR_ER_EINVAL, "plane_select selects nothing");
@@ -1682,6 +1768,7 @@ static int detect_bgr_impl(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t
     if (n_frames > 1 && frame_pitch < stride * src_rows) return fail(c, STR_ER_EINVAL, "frame_pitch smaller than a frame");
     if (w > c->prm.max_width || h > c->prm.max_height || n_frames > c->prm.max_frames)
         return fail(c, STR_ER_ECAPACITY, "frame larger than / more frames than the context capacity");
+    { const int rcs = check_call(c, stages, {true, !plane_select, false, plane_select != nullptr}); if (rcs != STR_ER_OK) return rcs; }
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->prm.device));
@@ -1761,12 +1848,11 @@ int str_er_detect_planes(str_er_ctx *c, const uint8_t *planes, int32_t w, int32_
 try {
     if (!c) return STR_ER_EINVAL;
     if (!planes || !out || w < 1 || h < 1 || n_planes < 1 || stride < w) return fail(c, STR_ER_EINVAL, "bad plane arguments");
-    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP))
-        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP need frames: not with str_er_detect_planes");
     if (n_planes > 1 && plane_pitch < stride * (int64_t)h) return fail(c, STR_ER_EINVAL, "plane_pitch smaller than a plane");
     if (w > c->prm.max_width || h > c->prm.max_height || n_planes > c->max_planes)
         return fail(c, STR_ER_ECAPACITY, "plane larger than / more planes than the context capacity");
     if (stride > 0x7FFFFFFF) return fail(c, STR_ER_EINVAL, "stride too large");
+    { const int rcs = check_call(c, stages, {false, false, false, false}); if (rcs != STR_ER_OK) return rcs; }
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->prm.device));
@@ -1855,7 +1941,7 @@ int detect_list_impl(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_fr
 {
     if (!c) return STR_ER_EINVAL;
     int rc = check_list(c, frames, n_frames, c->prm.max_frames, mem_kind, nv12 ? 1 : 3, out, "frame", nv12);
-    if (rc != STR_ER_OK) return rc;
+    if (rc != STR_ER_OK || (rc = check_call(c, stages, {true, true, false, false})) != STR_ER_OK) return rc;
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->prm.device));
@@ -1970,9 +2056,7 @@ int str_er_detect_planes_list(str_er_ctx *c, const str_er_image_ref *planes, int
 try {
     if (!c) return STR_ER_EINVAL;
     int rc = check_list(c, planes, n_planes, c->max_planes, mem_kind, 1, out, "plane");
-    if (rc != STR_ER_OK) return rc;
-    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP))
-        return fail(c, STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP need frames: not with str_er_detect_planes_list");
+    if (rc != STR_ER_OK || (rc = check_call(c, stages, {false, false, false, false})) != STR_ER_OK) return rc;
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->prm.device));
@@ -2029,37 +2113,13 @@ const str_er_cand *str_er_result_plane_cands(const str_er_result *r, int32_t pla
     return r->cands.data() + r->cand_off[plane];
 }
 
-const str_er_mask *str_er_result_masks(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_masks) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->masks.size();
-    static const str_er_mask none{};
-    return r->masks.empty() ? &none : r->masks.data();
-}
+const str_er_mask *str_er_result_masks(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_masks, &str_er_result::masks, n); }
 
-const str_er_shape *str_er_result_shapes(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_shapes) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->shapes.size();
-    static const str_er_shape none{};
-    return r->shapes.empty() ? &none : r->shapes.data();
-}
+const str_er_shape *str_er_result_shapes(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_shapes, &str_er_result::shapes, n); }
 
-const str_er_stroke *str_er_result_strokes(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_strokes) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->strokes.size();
-    static const str_er_stroke none{};
-    return r->strokes.empty() ? &none : r->strokes.data();
-}
+const str_er_stroke *str_er_result_strokes(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_strokes, &str_er_result::strokes, n); }
 
-const uint32_t *str_er_result_mask_bits(const str_er_result *r, uint64_t *n_words)
-{
-    if (!r || !r->have_masks) { if (n_words) *n_words = 0; return nullptr; }
-    if (n_words) *n_words = r->mask_bits.size();
-    static const uint32_t none = 0;
-    return r->mask_bits.empty() ? &none : r->mask_bits.data();
-}
+const uint32_t *str_er_result_mask_bits(const str_er_result *r, uint64_t *n_words) { return result_table(r, r && r->have_masks, &str_er_result::mask_bits, n_words); }
 
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n)
 {
@@ -2068,93 +2128,27 @@ const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t pla
     return r->nodes[plane].data();
 }
 
-const int32_t *str_er_result_ocr_labels(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_ocr) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->ocr_label.size();
-    static const int32_t none = 0;
-    return r->ocr_label.empty() ? &none : r->ocr_label.data();
-}
+const int32_t *str_er_result_ocr_labels(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_ocr, &str_er_result::ocr_label, n); }
 
-const double *str_er_result_ocr_probs(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_ocr) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->ocr_prob.size();
-    static const double none = 0;
-    return r->ocr_prob.empty() ? &none : r->ocr_prob.data();
-}
+const double *str_er_result_ocr_probs(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_ocr, &str_er_result::ocr_prob, n); }
 
-const str_er_track *str_er_result_tracks(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_tracks) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->tracks.size();
-    static const str_er_track none{};
-    return r->tracks.empty() ? &none : r->tracks.data();     // never NULL once the stage has run
-}
+const str_er_track *str_er_result_tracks(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_tracks, &str_er_result::tracks, n); }
 
-const str_er_text *str_er_result_texts(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_texts) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->texts.size();
-    static const str_er_text none{};
-    return r->texts.empty() ? &none : r->texts.data();
-}
+const str_er_text *str_er_result_texts(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_texts, &str_er_result::texts, n); }
 
-const int32_t *str_er_result_text_ers(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_texts) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->text_ers.size();
-    static const int32_t none = 0;
-    return r->text_ers.empty() ? &none : r->text_ers.data();
-}
+const int32_t *str_er_result_text_ers(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_texts, &str_er_result::text_ers, n); }
 
-const int32_t *str_er_result_group_all(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_texts) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->group_all.size();
-    static const int32_t none = 0;
-    return r->group_all.empty() ? &none : r->group_all.data();
-}
+const int32_t *str_er_result_group_all(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_texts, &str_er_result::group_all, n); }
 
-const int32_t *str_er_result_line_labels(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_line_ocr) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->line_label.size();
-    static const int32_t none = 0;
-    return r->line_label.empty() ? &none : r->line_label.data();
-}
+const int32_t *str_er_result_line_labels(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_ocr, &str_er_result::line_label, n); }
 
-const double *str_er_result_line_probs(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_line_ocr) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->line_prob.size();
-    static const double none = 0;
-    return r->line_prob.empty() ? &none : r->line_prob.data();
-}
+const double *str_er_result_line_probs(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_ocr, &str_er_result::line_prob, n); }
 
-const uint8_t *str_er_result_line_kept(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_line_ocr) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->line_kept.size();
-    static const uint8_t none = 0;
-    return r->line_kept.empty() ? &none : r->line_kept.data();
-}
+const uint8_t *str_er_result_line_kept(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_ocr, &str_er_result::line_kept, n); }
 
-const uint8_t *str_er_result_text_alive(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_line_ocr) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->text_alive.size();
-    static const uint8_t none = 0;
-    return r->text_alive.empty() ? &none : r->text_alive.data();
-}
+const uint8_t *str_er_result_text_alive(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_ocr, &str_er_result::text_alive, n); }
 
-const str_er_gbound *str_er_result_group_bounds(const str_er_result *r, int32_t *n)
-{
-    if (!r || !r->have_texts) { if (n) *n = 0; return nullptr; }
-    if (n) *n = (int32_t)r->gbounds.size();
-    static const str_er_gbound none{};
-    return r->gbounds.empty() ? &none : r->gbounds.data();
-}
+const str_er_gbound *str_er_result_group_bounds(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_texts, &str_er_result::gbounds, n); }
 
 const double *str_er_result_times(const str_er_result *r) { return r ? r->times : nullptr; }
 

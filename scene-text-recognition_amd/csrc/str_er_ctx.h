@@ -23,6 +23,7 @@
 #include "track_kernels.h"
 #include "er_group.h"
 #include "flood_order.h"
+#include "stage_rules.h"
 #include <functional>
 #include <thread>
 
@@ -89,6 +90,18 @@ struct str_er_result {
     bool have_text_map = false, have_line_map = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
+
+// A table of a result, as the str_er_result_* accessors hand it out: null (and *n = 0) when its stage did not run, and when it ran but made no
+// rows a pointer to `empty` -- never null.  N: the count's type.
+template <typename T> inline const T result_empty{};
+template <typename T, typename N>
+const T *result_table(const str_er_result *r, bool ran, std::vector<T> str_er_result::*table, N *n, const T &empty = result_empty<T>)
+{
+    if (!r || !ran) { if (n) *n = 0; return nullptr; }
+    const std::vector<T> &v = r->*table;
+    if (n) *n = (N)v.size();
+    return v.empty() ? &empty : v.data();
+}
 
 struct str_er_ctx {
     str_er_params prm{};
@@ -228,6 +241,13 @@ int fail(str_er_ctx *c, int code, const std::string &msg)
 {
     if (c) c->err = msg; else g_create_error = msg;
     return code;
+}
+
+// the flags of a detect call against its shape and the context's state (stage_rules.h): before the call stages or enqueues anything
+int check_call(str_er_ctx *c, uint32_t stages, const CallShape &k)
+{
+    const StageVerdict v = check_stages(stages, k, c->casc[0].loaded && c->casc[1].loaded, c->svm_loaded && c->svm.dim == 1800);
+    return v.code == STR_ER_OK ? STR_ER_OK : fail(c, v.code, v.msg);
 }
 
 // Waiting for a stream.  hipStreamSynchronize busy-waits (so does hipEventSynchronize on a hipEventBlockingSync event, measured): with a batch in
@@ -385,7 +405,7 @@ int resolve_sibling_ties(str_er_ctx *c, const Batch &b, const BatchDev &bd, cons
 int group_phase_overlap(str_er_ctx *c, const std::vector<uint32_t> &img, bool inner_sup, str_er_result *r);
 int upload_layout(str_er_ctx *c, Batch &b);
 int run_batch(str_er_ctx *c, const Batch &b_in, uint32_t stages, str_er_result **out, std::chrono::steady_clock::time_point t_start, bool pre_recorded,
-              const ImportHook *import_trees = nullptr, int attempt = 0);
+              const ImportHook *import_trees = nullptr);
 int stage_input(str_er_ctx *c, const uint8_t *src, size_t bytes, int mem_kind, const uint8_t **dev);
 // ---- defined in api_stages.cpp
 // the pixel masks of `jobs` (out_off / idx set by the caller, n_words words in all): launched on s, waited for, copied to pixels[idx] and
@@ -409,7 +429,7 @@ int region_jobs(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64
                 const DetectParams &dp, std::vector<MaskJob> &jobs, uint64_t &words);
 int region_upload(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, std::vector<MaskJob> &jobs);
 // ---- defined in api_text_map.cpp
-// STR_ER_WANT_TEXT_MAP / _LINE_MAP: the flags checked and the output maps of frames (w, h pairs) sized -- before a call enqueues anything
+// STR_ER_WANT_TEXT_MAP / _LINE_MAP: the output maps of frames (w, h pairs) sized -- before a call enqueues anything
 int text_map_reserve(str_er_ctx *c, uint32_t stages, const std::vector<int32_t> &frame_wh);
 // ... in run_batch: the maps of the frames of b (b.frame_wh) from the final candidates and lines of r (d_mask_bits: this call's mask words
 // on the device, indexed by r->masks, or null: then the masks are made here)

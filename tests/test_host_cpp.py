@@ -112,6 +112,19 @@ def test_flood_walk_watch_mode(tmp_path):
     assert out.strip().startswith("flood watch ok")
 
 
+def test_stage_rules_match_the_entry_points_checks(tmp_path):
+    """csrc/stage_rules.h, the one table of which STR_ER_STAGE_* / STR_ER_WANT_* combinations a detect call accepts, against the checks the
+    entry points made one by one (transcribed in tests/cpp/stage_rules_check.cpp): every combination of the 17 flag bits, every call shape
+    (frames, a plane subset of frames, planes, the strip path with every plane or a subset), cascades and SVM loaded or not -- the same code,
+    and a message that names the same flag."""
+    csrc = os.path.join(ROOT, "scene-text-recognition_amd", "csrc")
+    exe = str(tmp_path / "stage_rules_check")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", csrc, os.path.join(ROOT, "tests", "cpp", "stage_rules_check.cpp"),
+                    "-o", exe], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    assert out.strip().startswith("stage rules ok")
+
+
 @pytest.mark.parametrize("caps", ["kernel", "unbounded"])
 def test_tile2_algorithm_on_the_host(tmp_path, caps):
     """k_tile_tree2's algorithm (csrc/tile2_body.h: the component tree of a tile level by level on bit masks -- the very source the device kernel compiles,
