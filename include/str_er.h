@@ -96,6 +96,13 @@ extern "C" {
  * STR_ER_ECAPACITY.  The pixel rule and the layout are at str_er_frame_map.                                                      */
 #define STR_ER_WANT_TEXT_MAP  (16384u)   /* one uint8 map per frame, at the frame's own size          */
 #define STR_ER_WANT_LINE_MAP  (32768u)   /* one int32 map per frame: the text line of every pixel     */
+/* output option: one list of text lines per frame, in frame pixels, the lines of different pyramid levels that are the same text
+ * joined (str_er_result_line_feet / _line_pairs / _frame_lines / _frame_line_members; the contract is at str_er_line_foot).  Needs
+ * STR_ER_STAGE_GROUP and frames: STR_ER_EINVAL without the stage, on str_er_detect_planes[_list] and on str_er_strip_merge[_ex], the
+ * context usable afterwards.  str_er_detect_bgr, _nv12, _bgr_list, _nv12_list and every str_er_stream_submit* call honour it.  A
+ * contributing candidate wider than 16384 pixels gives STR_ER_ECAPACITY.  It changes no other output of the call and combines with
+ * every other STR_ER_WANT_* flag; the masks are still made once per call.                                                        */
+#define STR_ER_WANT_FRAME_LINES (131072u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -278,6 +285,41 @@ typedef struct str_er_frame_map {
     uint64_t off;            /* first element of this frame's map in the arrays below; a multiple of 4 */
     int32_t  width, height;  /* the frame's level-0 size                                            */
 } str_er_frame_map;          /* 16 bytes */
+
+/* The text lines of a frame, merged across pyramid levels (STR_ER_WANT_FRAME_LINES, str_er_line_feet_regions,
+ * str_er_frame_lines_from_pairs).  All exact integers, on top of the pixel rule of str_er_frame_map.
+ *   Footprint F(t) of line t of str_er_result_texts(): the set of pixels of frame texts[t].frame (level-0 size W x H) covered, by
+ *     that rule, by the mask (str_er_mask) of at least one member text_ers[first .. first + count).  A member listed twice counts
+ *     once.  The masks are over the candidates' own boxes, as for STR_ER_TEXT_MAP_LINE: the box and centre rewrites of
+ *     overlap_suppression play no part.
+ *   Foot box: the bounding box of F(t) in frame pixels; pixels = |F(t)|.  In a detect call (levels never larger than the frame) it
+ *     is the union of the members' pre-image boxes.  An empty footprint (only possible in str_er_line_feet_regions with a plane
+ *     larger than the output) has box 0, 0, 0, 0 and pixels = 0.
+ *   Overlap of two lines a < b of one frame: inter(a, b) = |F(a) & F(b)|.
+ *   Duplicates: a and b are duplicates iff inter > 0 and inter * den >= num * (|F(a)| + |F(b)| - inter) (Jaccard index >= num / den,
+ *     in 64-bit integers).  num / den: str_er_set_frame_merge, default 1 / 2 -- a definition of this library, like the pyramid; it
+ *     is not tuned on labelled data.
+ *   Frame line: a connected component of the duplicate relation among the lines of one frame (its transitive closure, so no order
+ *     of merging is involved).  Its representative is the member with the most pixels, ties to the smallest line index.  Frame lines
+ *     are ordered by frame, then by their smallest member line index.  Lines of different frames never meet.                       */
+typedef struct str_er_line_foot {
+    int32_t  x, y, w, h;     /*  0: the foot box, frame pixels                                          */
+    uint32_t pixels;         /* 16: |F(t)|                                                              */
+    int32_t  frame_line;     /* 20: index into str_er_result_frame_lines()                              */
+} str_er_line_foot;          /* 24 bytes; one per line of str_er_result_texts(), same order */
+typedef struct str_er_line_pair {
+    int32_t  a, b;           /*  0: two lines of one frame, a < b                                       */
+    uint32_t inter;          /*  8: |F(a) & F(b)|, > 0                                                  */
+    uint32_t dup;            /* 12: 1 if the two are duplicates at the call's num / den, else 0         */
+} str_er_line_pair;          /* 16 bytes; every pair with inter > 0, sorted by (a, b) */
+typedef struct str_er_frame_line {
+    uint32_t frame;          /*  0                                                                      */
+    int32_t  rep;            /*  4: the representative: a line index                                    */
+    int32_t  first, count;   /*  8: its members: str_er_result_frame_line_members()[first .. first + count), line indices, ascending */
+    int32_t  x, y, w, h;     /* 16: the union of the members' foot boxes                                */
+    uint32_t pixels;         /* 32: the representative's                                                */
+    uint32_t levels;         /* 36: bit k set if a member has pyr == k (k < 32)                         */
+} str_er_frame_line;         /* 40 bytes */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -475,6 +517,31 @@ int str_er_text_map_regions(str_er_ctx *ctx, const uint8_t *plane, int32_t w, in
                             const str_er_cand *regions, const uint8_t *values, const int32_t *ids /* or NULL */, int32_t n,
                             int32_t out_w, int32_t out_h, uint8_t *out_map, int32_t *out_ids /* NULL iff ids is NULL */);
 
+/* The duplicate threshold num / den of STR_ER_WANT_FRAME_LINES and str_er_line_feet_regions (str_er_line_foot): 1 <= num <= den <=
+ * 65535, default 1 / 2.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts: str_er_stream_context.        */
+int str_er_set_frame_merge(str_er_ctx *ctx, int32_t num, int32_t den);
+/* The footprints and overlaps (str_er_line_foot) of n_lines lines made of n regions of one host plane of w x h pixels (the level
+ * size): region i belongs to line line_of[i] in [0, n_lines); all lines count as one frame of out_w x out_h pixels.  Of every region
+ * only x, y, w, h, level and key are read; the masks are those of str_er_er_masks (same validation and error codes), at the context's
+ * current thresh_step, the plane taken as it is.  feet receives the n_lines records (frame_line as str_er_frame_lines_from_pairs
+ * sets it at the context's num / den).  bits receives the footprints themselves: line t's h rows of (w + 31) / 32 32-bit words over
+ * its foot box (bit i of word k of row r: frame pixel (x + 32 k + i, y + r); the layout of str_er_mask), back to back in line order;
+ * bits == NULL only reports *n_words.  pairs receives the pairs with inter > 0, sorted by (a, b), dup set; pairs == NULL only
+ * reports *n_pairs.  cap_words / cap_pairs too small -> STR_ER_ECAPACITY, both counts and feet still set.                          */
+int str_er_line_feet_regions(str_er_ctx *ctx, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions,
+                             const int32_t *line_of, int32_t n, int32_t n_lines, int32_t out_w, int32_t out_h, str_er_line_foot *feet,
+                             uint32_t *bits, uint64_t cap_words, uint64_t *n_words, str_er_line_pair *pairs, int32_t cap_pairs,
+                             int32_t *n_pairs);
+/* The frame lines of n_lines lines from their feet and pairs (str_er_line_foot).  Pure host, no context, no GPU; the detect calls use
+ * this same function.  frames_of_lines[t], pyr_of_lines[t]: the frame and pyramid level of line t (str_er_text::frame / pyr).  Reads
+ * feet[t].x, y, w, h, pixels and pairs[k].a, b, inter; sets pairs[k].dup and feet[t].frame_line, fills frame_lines (at most n_lines
+ * of them: cap_frame_lines too small -> STR_ER_ECAPACITY, *n_frame_lines still set; frame_lines == NULL only counts and sets dup)
+ * and members (n_lines line indices).  STR_ER_EINVAL: bad arguments, a pair with a >= b or an index outside [0, n_lines), a pair
+ * of lines of different frames, inter == 0 or inter larger than either footprint.                                                */
+int str_er_frame_lines_from_pairs(str_er_line_foot *feet, const uint32_t *frames_of_lines, const uint8_t *pyr_of_lines, int32_t n_lines,
+                                  str_er_line_pair *pairs, int32_t n_pairs, int32_t num, int32_t den, str_er_frame_line *frame_lines,
+                                  int32_t cap_frame_lines, int32_t *n_frame_lines, int32_t *members);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -666,6 +733,13 @@ const uint8_t          *str_er_result_line_glyph_pixels(const str_er_result *r, 
 const str_er_frame_map *str_er_result_frame_maps(const str_er_result *r, int32_t *n);
 const uint8_t          *str_er_result_text_map_pixels(const str_er_result *r, uint64_t *n_bytes);
 const int32_t          *str_er_result_line_map_ids(const str_er_result *r, uint64_t *n);
+/* With STR_ER_WANT_FRAME_LINES (str_er_line_foot): one foot per line of str_er_result_texts() (same order), the pairs of lines with
+ * common pixels sorted by (a, b), the frame lines and the line indices their first / count index.  Each returns NULL and 0 without
+ * the flag; a grouped call without lines returns empty arrays (not NULL).                                                         */
+const str_er_line_foot  *str_er_result_line_feet(const str_er_result *r, int32_t *n);
+const str_er_line_pair  *str_er_result_line_pairs(const str_er_result *r, int32_t *n);
+const str_er_frame_line *str_er_result_frame_lines(const str_er_result *r, int32_t *n);
+const int32_t           *str_er_result_frame_line_members(const str_er_result *r, int32_t *n);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

@@ -42,6 +42,16 @@ WANT_TEXT_MAP, WANT_LINE_MAP = 16384, 32768
 TEXT_MAP_STRONG, TEXT_MAP_WEAK, TEXT_MAP_LINE, TEXT_MAP_OCR = 1, 2, 4, 8
 # str_er_frame_map: frame f's maps = height x width elements (pitch width) from element off of the byte map and of the id map
 FRAME_MAP_DTYPE = np.dtype([("off", "<u8"), ("width", "<i4"), ("height", "<i4")])
+# output option: one list of text lines per frame, the lines of different pyramid levels that are the same text joined (needs
+# STAGE_GROUP; Result.line_feet / line_pairs / frame_lines / frame_line_members; the contract is at str_er_line_foot in include/str_er.h)
+WANT_FRAME_LINES = 131072
+# str_er_line_foot: per line of texts, its footprint's box and pixel count in frame pixels and its frame line
+LINE_FOOT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("pixels", "<u4"), ("frame_line", "<i4")])
+# str_er_line_pair: two lines a < b of one frame with inter > 0 common pixels; dup: duplicates at the call's threshold
+LINE_PAIR_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("inter", "<u4"), ("dup", "<u4")])
+# str_er_frame_line: members = frame_line_members[first:first + count] (line indices, ascending), rep the one with the most pixels
+FRAME_LINE_DTYPE = np.dtype([("frame", "<u4"), ("rep", "<i4"), ("first", "<i4"), ("count", "<i4"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"),
+                             ("h", "<i4"), ("pixels", "<u4"), ("levels", "<u4")])
 # str_er_line_crop: crop t = width x height bytes (pitch width) from byte pix_off of the crop bytes (and of the glyph bytes);
 # ax .. vy: the 16.16 sampling geometry (include/str_er.h)
 LINE_CROP_DTYPE = np.dtype([("pix_off", "<u8"), ("width", "<i4"), ("height", "<i4"), ("ax", "<i4"), ("ay", "<i4"),
@@ -67,6 +77,7 @@ assert LINE_CROP_DTYPE.itemsize == 40
 assert SHAPE_DTYPE.itemsize == 48
 assert STROKE_DTYPE.itemsize == 32
 assert FRAME_MAP_DTYPE.itemsize == 16
+assert LINE_FOOT_DTYPE.itemsize == 24 and LINE_PAIR_DTYPE.itemsize == 16 and FRAME_LINE_DTYPE.itemsize == 40
 
 
 def unpack_mask(words: np.ndarray, word_off: int, w: int, h: int) -> np.ndarray:
@@ -257,6 +268,13 @@ def load_library():
         fn.argtypes = [vp, C.POINTER(C.c_uint64)]
         fn.restype = vp
     L.str_er_text_map_regions.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp]
+    for fn in (L.str_er_result_line_feet, L.str_er_result_line_pairs, L.str_er_result_frame_lines, L.str_er_result_frame_line_members):
+        fn.argtypes = [vp, i32p]
+        fn.restype = vp
+    L.str_er_set_frame_merge.argtypes = [vp, C.c_int32, C.c_int32]
+    L.str_er_line_feet_regions.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp,
+                                           C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_int32, i32p]
+    L.str_er_frame_lines_from_pairs.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, i32p, vp]
     L.str_er_line_crop_geometry.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, vp]
     L.str_er_line_crops.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, C.c_uint64,
                                     C.POINTER(C.c_uint64), vp]
@@ -378,7 +396,36 @@ class Result:
         self.frame_maps = None     # with WANT_TEXT_MAP / WANT_LINE_MAP: FRAME_MAP_DTYPE per frame, and the maps they index (uint8 / int32)
         self.text_map_pixels = None
         self.line_map_ids = None
+        self._line_feet = None     # with WANT_FRAME_LINES: the tables behind line_feet / line_pairs / frame_lines / frame_line_members
+        self._line_pairs = None
+        self._frame_lines = None
+        self._frame_line_members = None
         self._planes = None
+
+    def _frame_lines_table(self, table):
+        if table is None:
+            raise ValueError("the result has no frame lines (pass WANT_FRAME_LINES / want_frame_lines=True)")
+        return table
+
+    @property
+    def line_feet(self) -> np.ndarray:
+        """With WANT_FRAME_LINES: LINE_FOOT_DTYPE per line of texts."""
+        return self._frame_lines_table(self._line_feet)
+
+    @property
+    def line_pairs(self) -> np.ndarray:
+        """With WANT_FRAME_LINES: LINE_PAIR_DTYPE per pair of lines of one frame with common pixels, sorted by (a, b)."""
+        return self._frame_lines_table(self._line_pairs)
+
+    @property
+    def frame_lines(self) -> np.ndarray:
+        """With WANT_FRAME_LINES: FRAME_LINE_DTYPE per frame line, ordered by frame, then by smallest member."""
+        return self._frame_lines_table(self._frame_lines)
+
+    @property
+    def frame_line_members(self) -> np.ndarray:
+        """With WANT_FRAME_LINES: the line indices the frame lines' first / count index (int32)."""
+        return self._frame_lines_table(self._frame_line_members)
 
     @property
     def mask_pixels(self) -> Optional[np.ndarray]:
@@ -561,6 +608,12 @@ class ERFilter:
             if res.frame_maps is not None:
                 res.text_map_pixels = table(L.str_er_result_text_map_pixels, np.uint8, n64)
                 res.line_map_ids = table(L.str_er_result_line_map_ids, np.int32, n64)
+            if res.texts is not None:
+                res._line_feet = table(L.str_er_result_line_feet, LINE_FOOT_DTYPE)
+                if res._line_feet is not None:
+                    res._line_pairs = table(L.str_er_result_line_pairs, LINE_PAIR_DTYPE)
+                    res._frame_lines = table(L.str_er_result_frame_lines, FRAME_LINE_DTYPE)
+                    res._frame_line_members = table(L.str_er_result_frame_line_members, np.int32)
             res.masks = table(L.str_er_result_masks, MASK_DTYPE)
             if res.masks is not None:
                 res.mask_bits = table(L.str_er_result_mask_bits, np.uint32, n64)
@@ -608,7 +661,7 @@ class ERFilter:
     # ---- the hot path ---------------------------------------------------------------------------
     def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
-                    want_strokes: bool = False) -> Result:
+                    want_strokes: bool = False, want_frame_lines: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -620,7 +673,7 @@ class ERFilter:
         rh = C.c_void_p()
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
-                                                                  text_map=want_text_map, line_map=want_line_map, strokes=want_strokes), C.byref(rh)))
+                                                                  text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -740,14 +793,14 @@ class ERFilter:
 
     def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
-                         want_strokes: bool = False) -> Result:
+                         want_strokes: bool = False, want_frame_lines: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
-                                                      text_map=want_text_map, line_map=want_line_map, strokes=want_strokes))
+                                                      text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -883,6 +936,32 @@ class ERFilter:
                                                    _np_ptr(v) if n else None, (_np_ptr(d) if n else _np_ptr(np.zeros(1, np.int32))) if d is not None else None,
                                                    n, int(out_w), int(out_h), _np_ptr(out), None if out_ids is None else _np_ptr(out_ids)))
         return out if d is None else (out, out_ids)
+
+    def set_frame_merge(self, num: int = 1, den: int = 2) -> None:
+        """str_er_set_frame_merge: two lines of a frame are duplicates from a Jaccard index of num / den of their footprints on
+        (1 <= num <= den <= 65535; WANT_FRAME_LINES and line_feet_regions)."""
+        self._check(self.L.str_er_set_frame_merge(self.h, int(num), int(den)))
+
+    def line_feet_regions(self, plane: np.ndarray, regions: np.ndarray, line_of, n_lines: int, out_w: int, out_h: int):
+        """str_er_line_feet_regions: the footprints of n_lines lines made of `regions` (CAND_DTYPE; x, y, w, h, level and key are
+        read; region i belongs to line line_of[i]) of one (h, w) uint8 plane on an (out_h, out_w) frame, by the pixel rule of
+        str_er_frame_map.  Returns (feet LINE_FOOT_DTYPE, bits uint32, pairs LINE_PAIR_DTYPE): line t's footprint is its h rows of
+        (w + 31) // 32 words over its foot box, back to back in line order (unpack_mask reads one)."""
+        a = np.ascontiguousarray(plane, dtype=np.uint8)
+        r = np.ascontiguousarray(regions, dtype=CAND_DTYPE).reshape(-1)
+        n = len(r)
+        lo = np.ascontiguousarray(line_of, dtype=np.int32).reshape(-1)
+        if len(lo) != n:
+            raise ValueError("line_of needs one entry per region")
+        feet = np.zeros(max(1, int(n_lines)), LINE_FOOT_DTYPE)
+        nw, npairs = C.c_uint64(), C.c_int32()
+        args = (self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(r) if n else None, _np_ptr(lo) if n else None, n, int(n_lines),
+                int(out_w), int(out_h), _np_ptr(feet))
+        self._check(self.L.str_er_line_feet_regions(*args, None, 0, C.byref(nw), None, 0, C.byref(npairs)))
+        bits = np.zeros(max(1, nw.value), np.uint32)
+        pairs = np.zeros(max(1, npairs.value), LINE_PAIR_DTYPE)
+        self._check(self.L.str_er_line_feet_regions(*args, _np_ptr(bits), len(bits), C.byref(nw), _np_ptr(pairs), len(pairs), C.byref(npairs)))
+        return feet[:int(n_lines)], bits[:nw.value], pairs[:npairs.value]
 
     def set_line_crop(self, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> None:
         """str_er_set_line_crop: the crop height (8..256), the widest crop (1..8192) and the pad (0..1, of the line's height) of
@@ -1073,11 +1152,34 @@ def _owned(ptr, n: int, dtype) -> np.ndarray:
     return np.frombuffer((C.c_char * (dtype.itemsize * n)).from_address(ptr), dtype=dtype).copy()
 
 
-def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False) -> int:
+def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
+                frame_lines=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
+
+
+def frame_lines_from_pairs(feet: np.ndarray, frames_of_lines, pyr_of_lines, pairs: np.ndarray, num: int = 1, den: int = 2):
+    """str_er_frame_lines_from_pairs (pure host): the frame lines of the lines with these feet (LINE_FOOT_DTYPE; box and pixels are
+    read), frames and pyramid levels from the pairs with common pixels (LINE_PAIR_DTYPE; a, b, inter are read).  Returns copies
+    (feet with frame_line set, pairs with dup set, frame lines FRAME_LINE_DTYPE, members int32)."""
+    ft = np.array(feet, dtype=LINE_FOOT_DTYPE).reshape(-1)
+    pr = np.array(pairs, dtype=LINE_PAIR_DTYPE).reshape(-1)
+    fr = np.ascontiguousarray(frames_of_lines, dtype=np.uint32).reshape(-1)
+    py = np.ascontiguousarray(pyr_of_lines, dtype=np.uint8).reshape(-1)
+    n = len(ft)
+    if len(fr) != n or len(py) != n:
+        raise ValueError("frames_of_lines and pyr_of_lines need one entry per line")
+    fl = np.zeros(max(1, n), FRAME_LINE_DTYPE)
+    mem = np.zeros(max(1, n), np.int32)
+    nfl = C.c_int32()
+    rc = load_library().str_er_frame_lines_from_pairs(_np_ptr(ft) if n else None, _np_ptr(fr) if n else None, _np_ptr(py) if n else None, n,
+                                                      _np_ptr(pr) if len(pr) else None, len(pr), int(num), int(den), _np_ptr(fl), len(fl),
+                                                      C.byref(nfl), _np_ptr(mem))
+    if rc != 0:
+        raise StrErError(rc, "str_er_frame_lines_from_pairs")
+    return ft, pr, fl[:nfl.value], mem[:n]
 
 
 def line_crop_geometry(boxes_xywh: np.ndarray, slope: float, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> np.ndarray:

@@ -4,11 +4,7 @@
 // str_er_frame_map), bins them into tiles of the frames' maps and lays out the xs / ys tables; k_text_map (er_text_map.inl) gathers.
 #include "str_er_ctx.h"
 
-#include <map>
-
 namespace str_er_host {
-
-namespace {
 
 // the first frame coordinate x in [0, W] whose sample ((2x + 1) * wp) / (2W) is >= a
 int32_t first_sample_at(int64_t a, int64_t W, int64_t wp)
@@ -34,6 +30,18 @@ int grow_pair(str_er_ctx *c, uint8_t *&d, uint8_t *&h, size_t &bytes, size_t nee
     bytes = get;
     return STR_ER_OK;
 }
+
+uint32_t SampleTabs::table(int32_t n, int32_t np)
+{
+    const auto it = at.find({n, np});
+    if (it != at.end()) return it->second;
+    const uint32_t first = (uint32_t)tabs.size();
+    for (int64_t x = 0; x < n; ++x) tabs.push_back((uint16_t)(((2 * x + 1) * (int64_t)np) / (2 * (int64_t)n)));
+    at.emplace(std::make_pair(n, np), first);
+    return first;
+}
+
+namespace {
 
 // where the ids sit behind the bytes in c->d_tmap / c->h_tmap, and the bytes the maps of n_elem elements need
 void tmap_out_offsets(uint64_t n_elem, bool map, bool ids, size_t &o_ids, size_t &need)
@@ -82,15 +90,8 @@ void tmap_layout(const std::vector<str_er_frame_map> &frames, const std::vector<
         }
     }
     // the xs / ys tables, one per (frame size, level size) pair
-    std::map<std::pair<int32_t, int32_t>, uint32_t> tab_at;
-    auto table = [&](int32_t n, int32_t np) -> uint32_t {
-        const auto it = tab_at.find({n, np});
-        if (it != tab_at.end()) return it->second;
-        const uint32_t at = (uint32_t)L.tabs.size();
-        for (int64_t x = 0; x < n; ++x) L.tabs.push_back((uint16_t)(((2 * x + 1) * (int64_t)np) / (2 * (int64_t)n)));
-        tab_at.emplace(std::make_pair(n, np), at);
-        return at;
-    };
+    SampleTabs st;
+    auto table = [&](int32_t n, int32_t np) -> uint32_t { return st.table(n, np); };
     L.cands.clear();
     std::vector<std::pair<uint32_t, uint32_t>> range;         // (first tile, last tile) of every region kept
     for (const TmapRegion &g : regs) {
@@ -115,6 +116,7 @@ void tmap_layout(const std::vector<str_er_frame_map> &frames, const std::vector<
     L.list.assign(at, 0);
     for (uint32_t k = 0; k < (uint32_t)range.size(); ++k)
         for (uint32_t t = range[k].first; t <= range[k].second; ++t) { TextMapTile &T = L.tiles[t]; L.list[T.first + T.count++] = k; }
+    L.tabs.swap(st.tabs);
     if (L.tabs.empty()) L.tabs.push_back(0);
 }
 
@@ -172,7 +174,8 @@ int text_map_reserve(str_er_ctx *c, uint32_t stages, const std::vector<int32_t> 
     return reserve_out(c, n_elem, map, ids);
 }
 
-int text_map_phase(str_er_ctx *c, hipStream_t s, const Batch &b, uint32_t stages, float qscale, const uint32_t *d_mask_bits, str_er_result *r)
+int text_map_phase(str_er_ctx *c, hipStream_t s, const Batch &b, uint32_t stages, float qscale, const uint32_t *d_mask_bits, str_er_result *r,
+                   const uint32_t **d_made_bits, std::vector<uint64_t> *made_word_off)
 {
     const bool map = (stages & STR_ER_WANT_TEXT_MAP) != 0, ids = (stages & STR_ER_WANT_LINE_MAP) != 0;
     const size_t n_frames = b.frame_wh.size() / 2, total = r->cands.size();
@@ -225,6 +228,11 @@ int text_map_phase(str_er_ctx *c, hipStream_t s, const Batch &b, uint32_t stages
         }
         const int rcm = mask_launch(c, s, mj, words, qscale, &d_bits);
         if (rcm != STR_ER_OK) return rcm;
+        if (d_made_bits && made_word_off) {        // (STR_ER_WANT_FRAME_LINES behind the maps: the same words serve it)
+            *d_made_bits = d_bits;
+            made_word_off->assign(total, UINT64_MAX);
+            for (size_t i = 0; i < who.size(); ++i) (*made_word_off)[who[i]] = regs[i].word_off;
+        }
     }
     for (size_t i = 0; i < who.size(); ++i) {
         const str_er_cand &cd = r->cands[who[i]];

@@ -1,0 +1,141 @@
+// er_frame_lines.inl -- the footprints of the text lines in frame pixels and their pairwise overlaps (STR_ER_WANT_FRAME_LINES,
+// str_er_line_feet_regions).  Part of er_kernels.hip.
+//
+// k_line_foot: the footprint of every line (str_er.h, str_er_line_foot) as bit rows over the union of its members' pre-image boxes.
+// A gather without atomics on pixels, for the reason er_text_map.inl gives: the members of a line come from every channel of its
+// level and nest, so they cover the same pixels many times.  The host has cut every footprint into jobs of whole rows (FootJob); a
+// wave takes a job, a lane the 64-bit words lane, lane + 64, ... of the job's rows.  Per member (a scalar walk: the line is uniform
+// in the wave) the lane clips its word against the member's pre-image box, looks xs / ys up in the uint16 tables of the text-map
+// stage (no division per pixel), reads the mask bit and ORs it in.  Every word is written once.  The wave adds up the popcounts and
+// the extent of its set bits and leaves them in the line's FootStat: five atomics per job, none per pixel.
+//
+// k_foot_pairs: a wave takes a line a and walks the later lines b of a's frame (FootLine::next .. end, scalar); where the two
+// boxes intersect it ANDs the two footprints over the intersection -- their x origins differ, so each lane funnels two words of a
+// row into the 64 bits that start at the intersection's column -- popcounts and reduces.  Pairs without a common pixel are dropped
+// here; lane 0 appends the others to the output (an atomic per surviving pair).  The order of the output is the order of arrival:
+// the host sorts it.
+
+constexpr int FOOT_THREADS = 256;           // 4 waves, a job / a line each
+
+template <typename T>
+__device__ __forceinline__ T foot_wave_sum(T v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t foot_wave_max(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
+    return v;
+}
+
+// the 64 bits of a footprint row (pitch words) from bit `off` on; what lies past the row is 0
+__device__ __forceinline__ uint64_t foot_window(const uint64_t *__restrict__ row, uint32_t pitch, uint32_t off)
+{
+    const uint32_t q = off >> 6, s = off & 63u;
+    uint64_t       v = q < pitch ? row[q] >> s : 0ull;
+    if (s && q + 1 < pitch) v |= row[q + 1] << (64u - s);
+    return v;
+}
+
+__global__ __launch_bounds__(FOOT_THREADS) void k_line_foot(const FootJob *__restrict__ jobs, int n_jobs, const FootLine *__restrict__ lines,
+                                                            const TextMapCand *__restrict__ members, const uint16_t *__restrict__ tabs,
+                                                            const uint32_t *__restrict__ bits, uint64_t *__restrict__ feet, FootStat *__restrict__ stat)
+{
+    const int lane = threadIdx.x & 63;
+    const int j = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (FOOT_THREADS / 64) + (threadIdx.x >> 6)));
+    if (j >= n_jobs) return;
+    const FootJob  J = jobs[j];
+    const FootLine L = lines[J.line];
+    const uint32_t items = J.n_rows * L.pitch;
+    uint32_t px = 0, nx0 = 0, ny0 = 0, x1 = 0, y1 = 0;
+    for (uint32_t it = (uint32_t)lane; it < items; it += 64) {
+        const uint32_t r = it / L.pitch, k = it - r * L.pitch;
+        const int      y = L.y + (int)(J.row0 + r), xb = L.x + (int)(64u * k), xe = min(xb + 64, L.x + L.w);
+        uint64_t       word = 0;
+        for (uint32_t m = 0; m < L.count; ++m) {
+            const TextMapCand C = members[L.first + m];
+            if (y < C.fy0 || y >= C.fy1) continue;
+            const int a = max(xb, C.fx0), e = min(xe, C.fx1);
+            if (a >= e) continue;
+            const int dy = (int)tabs[C.ytab + (uint32_t)y] - C.y;
+            if (dy < 0 || dy >= C.h) continue;                                  // (the pre-image is exact: never taken)
+            const uint32_t *row = bits + C.word_off + (uint64_t)dy * C.pitch;
+            for (int x = a; x < e; ++x) {
+                const int dx = (int)tabs[C.xtab + (uint32_t)x] - C.x;
+                if (dx < 0 || dx >= C.w) continue;                              // (likewise)
+                word |= (uint64_t)((row[dx >> 5] >> (dx & 31)) & 1u) << (x - xb);
+            }
+        }
+        feet[L.word_off + (uint64_t)(J.row0 + r) * L.pitch + k] = word;
+        if (word) {
+            px += (uint32_t)__popcll(word);
+            nx0 = max(nx0, 65536u - (uint32_t)(xb + (int)__builtin_ctzll(word)));
+            x1 = max(x1, (uint32_t)(xb + 64 - (int)__builtin_clzll(word)));
+            ny0 = max(ny0, 65536u - (uint32_t)y);
+            y1 = max(y1, (uint32_t)y + 1u);
+        }
+    }
+    px = foot_wave_sum(px);
+    nx0 = foot_wave_max(nx0); ny0 = foot_wave_max(ny0); x1 = foot_wave_max(x1); y1 = foot_wave_max(y1);
+    if (lane == 0 && px) {
+        FootStat *S = stat + J.line;
+        atomicAdd(&S->pixels, px);
+        atomicMax(&S->nx0, nx0); atomicMax(&S->ny0, ny0); atomicMax(&S->x1, x1); atomicMax(&S->y1, y1);
+    }
+}
+
+__global__ __launch_bounds__(FOOT_THREADS) void k_foot_pairs(const FootLine *__restrict__ lines, int n_lines, const uint32_t *__restrict__ list,
+                                                             const uint64_t *__restrict__ feet, FootHead *__restrict__ head, FootPair *__restrict__ out,
+                                                             uint32_t cap)
+{
+    const int lane = threadIdx.x & 63;
+    for (int a0 = blockIdx.x * (FOOT_THREADS / 64); a0 < n_lines; a0 += gridDim.x * (FOOT_THREADS / 64)) {
+        const int a = __builtin_amdgcn_readfirstlane(a0 + (int)(threadIdx.x >> 6));
+        if (a >= n_lines) continue;
+        const FootLine A = lines[a];
+        if (A.w <= 0) continue;
+        uint32_t n_cand = 0;
+        for (uint32_t i = A.next; i < A.end; ++i) {
+            const int      b = (int)list[i];
+            const FootLine B = lines[b];
+            const int ix0 = max(A.x, B.x), ix1 = min(A.x + A.w, B.x + B.w), iy0 = max(A.y, B.y), iy1 = min(A.y + A.h, B.y + B.h);
+            if (ix0 >= ix1 || iy0 >= iy1) continue;
+            ++n_cand;
+            const uint32_t nw = (uint32_t)(ix1 - ix0 + 63) >> 6, items = (uint32_t)(iy1 - iy0) * nw;
+            uint32_t inter = 0;
+            for (uint32_t it = (uint32_t)lane; it < items; it += 64) {
+                const uint32_t r = it / nw, k = it - r * nw;
+                const int      y = iy0 + (int)r;
+                const uint64_t wa = foot_window(feet + A.word_off + (uint64_t)(y - A.y) * A.pitch, A.pitch, (uint32_t)(ix0 - A.x) + 64u * k);
+                const uint64_t wb = foot_window(feet + B.word_off + (uint64_t)(y - B.y) * B.pitch, B.pitch, (uint32_t)(ix0 - B.x) + 64u * k);
+                inter += (uint32_t)__popcll(wa & wb);         // (past ix1 one of the two rows has ended: its bits are 0)
+            }
+            inter = foot_wave_sum(inter);
+            if (lane == 0 && inter) {
+                const uint32_t at = atomicAdd(&head->n_pairs, 1u);
+                if (at < cap) { FootPair P; P.a = a; P.b = b; P.inter = inter; P.dup = 0; out[at] = P; }
+            }
+        }
+        if (lane == 0 && n_cand) atomicAdd(&head->n_candidates, n_cand);
+    }
+}
+
+void launch_line_foot(hipStream_t s, const FootJob *jobs, int n_jobs, const FootLine *lines, const TextMapCand *members, const uint16_t *tabs,
+                      const uint32_t *bits, uint64_t *feet, FootStat *stat)
+{
+    if (n_jobs <= 0) return;
+    const dim3 grid((unsigned)((n_jobs + FOOT_THREADS / 64 - 1) / (FOOT_THREADS / 64)));
+    hipLaunchKernelGGL(k_line_foot, grid, dim3(FOOT_THREADS), 0, s, jobs, n_jobs, lines, members, tabs, bits, feet, stat);
+}
+
+void launch_foot_pairs(hipStream_t s, const FootLine *lines, int n_lines, const uint32_t *list, const uint64_t *feet, FootHead *head, FootPair *out,
+                       uint32_t cap)
+{
+    if (n_lines <= 1) return;
+    const dim3 grid((unsigned)std::min((n_lines + FOOT_THREADS / 64 - 1) / (FOOT_THREADS / 64), 1 << 16));
+    hipLaunchKernelGGL(k_foot_pairs, grid, dim3(FOOT_THREADS), 0, s, lines, n_lines, list, feet, head, out, cap);
+}

@@ -148,4 +148,13 @@ void launch_line_crops(hipStream_t s, const LineCropJob *jobs, int n, uint8_t *o
 void launch_text_map(hipStream_t s, const TextMapTile *tiles, int n_tiles, const uint32_t *list, const TextMapCand *cands, const uint16_t *tabs,
                      const uint32_t *bits, uint8_t *map, int32_t *ids);
 
+// Frame lines (er_frame_lines.inl).  launch_line_foot: one wave per job; feet receives the footprint rows of every line at
+// FootLine::word_off, stat[line] (zeroed by the caller) the pixels and the extent of the set bits; members / tabs / bits as for the
+// text maps.  launch_foot_pairs: one wave per line over the later lines of its frame (list); the pairs with a common pixel go to
+// out[0 .. cap), head (zeroed by the caller) counts them -- also those past cap -- and the pairs whose boxes intersect.
+void launch_line_foot(hipStream_t s, const FootJob *jobs, int n_jobs, const FootLine *lines, const TextMapCand *members, const uint16_t *tabs,
+                      const uint32_t *bits, uint64_t *feet, FootStat *stat);
+void launch_foot_pairs(hipStream_t s, const FootLine *lines, int n_lines, const uint32_t *list, const uint64_t *feet, FootHead *head, FootPair *out,
+                       uint32_t cap);
+
 } // namespace str_er

@@ -266,4 +266,42 @@ struct TextMapTile {
 static_assert(sizeof(TextMapTile) == 32, "TextMapTile layout (host and device)");
 constexpr uint32_t TMAP_CHUNK_ELEMS = 2048;      // a tile is a whole number of such chunks, and at least a row of its frame (er_text_map.inl)
 
+// The frame-line stage (STR_ER_WANT_FRAME_LINES, str_er_line_feet_regions; er_frame_lines.inl).
+// A line's footprint is kept on the device as h rows of `pitch` 64-bit words over the box (x, y, w, h) in frame pixels: the union of
+// its members' pre-image boxes (bit i of word k of row r: frame pixel (x + 64 k + i, y + r); the bits past w are 0).  Its members
+// are TextMapCands (value / id unused) members[first .. first + count), each listed once.  list[next .. end): the later lines of
+// the same frame, ascending (the lines k_foot_pairs pairs this one with).
+struct FootLine {
+    uint64_t word_off;
+    int32_t  x, y, w, h;
+    uint32_t pitch;
+    uint32_t first, count;
+    uint32_t next, end;
+    uint32_t pad;
+};
+static_assert(sizeof(FootLine) == 48, "FootLine layout (host and device)");
+// n_rows rows of a line's footprint from row0 on: the work of one wave of k_line_foot
+struct FootJob {
+    uint32_t line, row0, n_rows, pad;
+};
+static_assert(sizeof(FootJob) == 16, "FootJob layout (host and device)");
+// What k_line_foot leaves of a line, from an all-zero record: the set pixels, and the bounding box of the set pixels as
+// 65536 - x0, 65536 - y0 (0: no pixel) and x1 + 1, y1 + 1 in frame pixels (so that every field only grows: atomicAdd / atomicMax)
+struct FootStat {
+    uint32_t pixels, nx0, ny0, x1, y1, pad;
+};
+static_assert(sizeof(FootStat) == 24, "FootStat layout (host and device)");
+// A pair of lines with common pixels (the layout of str_er_line_pair); FootHead: the counters in front of the FootStats
+struct FootPair {
+    int32_t  a, b;
+    uint32_t inter, dup;
+};
+static_assert(sizeof(FootPair) == 16, "FootPair layout (host and device)");
+struct FootHead {
+    uint32_t n_pairs;        // pairs with inter > 0 (may exceed the capacity: then only the first `cap` were stored)
+    uint32_t n_candidates;   // pairs of lines of one frame whose footprint boxes intersect
+    uint32_t pad[2];
+};
+static_assert(sizeof(FootHead) == 16, "FootHead layout (host and device)");
+
 } // namespace str_er

@@ -37,9 +37,12 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
         {k.strip && any(STR_ER_WANT_STROKES), STR_ER_EINVAL, "STR_ER_WANT_STROKES is not supported by the strip path (str_er_strip_merge)"},
         {!k.frames && any(maps), STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP / _LINE_MAP need frames (not the per-plane calls or the strip path)"},
         {k.strip && any(crops), STR_ER_EINVAL, "STR_ER_WANT_LINE_CROPS / _GLYPHS are not supported by the strip path (str_er_strip_merge)"},
+        {k.strip && any(STR_ER_WANT_FRAME_LINES), STR_ER_EINVAL, "STR_ER_WANT_FRAME_LINES is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_FRAME_LINES), STR_ER_EINVAL, "STR_ER_WANT_FRAME_LINES needs frames (not the per-plane calls)"},
         // the maps (sized before anything of a frame call is enqueued: ahead of the state of the context)
         {any(STR_ER_WANT_TEXT_MAP) && !any(STR_ER_STAGE_CLASSIFY), STR_ER_EINVAL, "STR_ER_WANT_TEXT_MAP needs STR_ER_STAGE_CLASSIFY"},
         {any(STR_ER_WANT_LINE_MAP) && !any(STR_ER_STAGE_GROUP), STR_ER_EINVAL, "STR_ER_WANT_LINE_MAP needs STR_ER_STAGE_GROUP"},
+        {any(STR_ER_WANT_FRAME_LINES) && !any(STR_ER_STAGE_GROUP), STR_ER_EINVAL, "STR_ER_WANT_FRAME_LINES needs STR_ER_STAGE_GROUP"},
         // the stages, each behind what it needs
         {any(STR_ER_STAGE_CLASSIFY) && !cascades, STR_ER_ESTATE, "classify needs both cascades (str_er_load_cascade)"},
         {!any(STR_ER_STAGE_EXTRACT), STR_ER_EINVAL, "stages must include STR_ER_STAGE_EXTRACT"},

@@ -1340,6 +1340,18 @@ static int result_masks(const BatchRun &R, str_er_result *r, const uint32_t **d_
     return STR_ER_OK;
 }
 
+// STR_ER_WANT_FRAME_LINES: with the mask words this call has left on the device -- those of result_masks (indexed by r->masks), else those the maps
+// made, else none (frame_lines_phase makes the members' masks)
+static int frame_lines_result(const BatchRun &R, str_er_result *r, const uint32_t *d_mask_bits, const uint32_t *d_made_bits, std::vector<uint64_t> &made_word_off)
+{
+    if (d_mask_bits) {
+        made_word_off.resize(r->masks.size());
+        for (size_t k = 0; k < r->masks.size(); ++k) made_word_off[k] = r->masks[k].word_off;
+        return frame_lines_phase(R.c, R.s, R.b, R.dp.qscale, d_mask_bits, &made_word_off, r);
+    }
+    return frame_lines_phase(R.c, R.s, R.b, R.dp.qscale, d_made_bits, d_made_bits ? &made_word_off : nullptr, r);
+}
+
 // candidates carry the device kept slot; translated to the sorted node table through (key, level) -- or -1 without STR_ER_WANT_NODES
 static void result_node_ids(const BatchRun &R, str_er_result *r)
 {
@@ -1399,7 +1411,13 @@ static int collect_result(BatchRun &R, str_er_result *r, std::chrono::steady_clo
     if (rc == STR_ER_OK && (stages & STR_ER_WANT_LINE_CROPS))
         rc = line_crop_phase(c, R.s, R.b, R.dp.qscale, (stages & STR_ER_WANT_LINE_GLYPHS) != 0, d_mask_bits, r);
     // the maps of the frames from the final candidates and lines: binned on the host, one launch (with the masks, if this call has none), one copy back
-    if (rc == STR_ER_OK && (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP))) rc = text_map_phase(c, R.s, R.b, stages, R.dp.qscale, d_mask_bits, r);
+    const bool want_frame_lines = (stages & STR_ER_WANT_FRAME_LINES) != 0;
+    const uint32_t *d_made_bits = nullptr;         // (the masks the maps made, when the call has no others: for the frame lines)
+    std::vector<uint64_t> made_word_off;
+    if (rc == STR_ER_OK && (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP)))
+        rc = text_map_phase(c, R.s, R.b, stages, R.dp.qscale, d_mask_bits, r, want_frame_lines ? &d_made_bits : nullptr, want_frame_lines ? &made_word_off : nullptr);
+    // the lines of every frame merged across its pyramid levels: footprints and overlaps on the device, the frame lines on the host
+    if (rc == STR_ER_OK && want_frame_lines) rc = frame_lines_result(R, r, d_mask_bits, d_made_bits, made_word_off);
     if (rc != STR_ER_OK) return rc;
     result_node_ids(R, r);
     result_times(R, r, t_start);
@@ -1552,6 +1570,11 @@ void str_er_destroy(str_er_ctx *c)
     if (c->h_tmap) (void)hipHostFree(c->h_tmap);
     if (c->d_tmap_tab) (void)hipFree(c->d_tmap_tab);
     if (c->h_tmap_tab) (void)hipHostFree(c->h_tmap_tab);
+    if (c->d_foot_tab) (void)hipFree(c->d_foot_tab);
+    if (c->h_foot_tab) (void)hipHostFree(c->h_foot_tab);
+    if (c->d_foot_out) (void)hipFree(c->d_foot_out);
+    if (c->h_foot_out) (void)hipHostFree(c->h_foot_out);
+    if (c->d_foot_bits) (void)hipFree(c->d_foot_bits);
     if (c->d_strip_out) (void)hipFree(c->d_strip_out);
     if (c->d_strip_in) (void)hipFree(c->d_strip_in);
     if (c->d_replay) (void)hipFree(c->d_replay);
@@ -1773,7 +1796,7 @@ static int detect_bgr_impl(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->prm.device));
     std::vector<int32_t> frame_wh;
-    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP)) {     // (the maps' buffers: sized before anything of the call is enqueued)
+    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP | STR_ER_WANT_FRAME_LINES)) {     // (the maps' buffers: sized before anything of the call is enqueued; the frames' sizes for the frame lines)
         for (int f = 0; f < n_frames; ++f) frame_wh.insert(frame_wh.end(), {w, h});
         const int rcm = text_map_reserve(c, stages, frame_wh);
         if (rcm != STR_ER_OK) return rcm;
@@ -1946,7 +1969,7 @@ int detect_list_impl(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_fr
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->prm.device));
     std::vector<int32_t> frame_wh;
-    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP)) {     // (the maps' buffers: sized before anything of the call is enqueued)
+    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP | STR_ER_WANT_FRAME_LINES)) {     // (the maps' buffers: sized before anything of the call is enqueued; the frames' sizes for the frame lines)
         for (int f = 0; f < n_frames; ++f) frame_wh.insert(frame_wh.end(), {frames[f].w, frames[f].h});
         if ((rc = text_map_reserve(c, stages, frame_wh)) != STR_ER_OK) return rc;
     }

@@ -1,6 +1,7 @@
 // str_er_ctx.h -- INTERNAL: the context / result structs and the small host helpers shared by the translation units of the C ABI
 // (str_er_api.cpp: contexts, batches, the detect entry points, results; api_models.cpp: cascade / libsvm models and the OCR entry points;
-//  api_strips.cpp: one plane in strips over several GPUs; api_stages.cpp: the single-stage entry points).  Not installed, not part of the ABI.
+//  api_strips.cpp: one plane in strips over several GPUs; api_stages.cpp: the single-stage entry points; api_text_map.cpp / api_frame_lines.cpp: the
+//  frame maps and the frame lines).  Not installed, not part of the ABI.
 // The helpers in the unnamed namespace are small and private to each translation unit; what one unit defines for the others is declared in str_er_host.
 #pragma once
 #include "../../include/str_er.h"
@@ -25,6 +26,7 @@
 #include "flood_order.h"
 #include "stage_rules.h"
 #include <functional>
+#include <map>
 #include <thread>
 
 using namespace str_er;
@@ -88,6 +90,11 @@ struct str_er_result {
     std::vector<uint8_t> text_map;
     std::vector<int32_t> line_map;
     bool have_text_map = false, have_line_map = false;
+    std::vector<str_er_line_foot> line_feet;     // STR_ER_WANT_FRAME_LINES: per line, the pairs with common pixels, the frame lines and their members
+    std::vector<str_er_line_pair> line_pairs;
+    std::vector<str_er_frame_line> frame_lines;
+    std::vector<int32_t> frame_line_members;
+    bool have_frame_lines = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -192,6 +199,13 @@ struct str_er_ctx {
     // tables of the stage (tiles | list | regions | xs / ys); both created by the first call that wants maps, grown geometrically, never shrunk
     uint8_t  *d_tmap = nullptr, *h_tmap = nullptr; size_t tmap_bytes = 0;
     uint8_t  *d_tmap_tab = nullptr, *h_tmap_tab = nullptr; size_t tmap_tab_bytes = 0;
+    // STR_ER_WANT_FRAME_LINES / str_er_line_feet_regions (str_er_set_frame_merge): the stage's tables (lines | jobs | list | members |
+    // xs / ys), its output (counters | per-line statistics | pairs) and the footprint words; created by the first call that wants
+    // frame lines, grown geometrically, never shrunk
+    int32_t  merge_num = 1, merge_den = 2;
+    uint8_t  *d_foot_tab = nullptr, *h_foot_tab = nullptr; size_t foot_tab_bytes = 0;
+    uint8_t  *d_foot_out = nullptr, *h_foot_out = nullptr; size_t foot_out_bytes = 0;
+    uint64_t *d_foot_bits = nullptr; size_t foot_bits_words = 0;
     uint8_t *d_strip_out = nullptr, *d_strip_in = nullptr; size_t strip_out_cap = 0, strip_in_cap = 0;   // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -433,7 +447,26 @@ int region_upload(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int
 int text_map_reserve(str_er_ctx *c, uint32_t stages, const std::vector<int32_t> &frame_wh);
 // ... in run_batch: the maps of the frames of b (b.frame_wh) from the final candidates and lines of r (d_mask_bits: this call's mask words
 // on the device, indexed by r->masks, or null: then the masks are made here)
-int text_map_phase(str_er_ctx *c, hipStream_t s, const Batch &b, uint32_t stages, float qscale, const uint32_t *d_mask_bits, str_er_result *r);
+// (d_made_bits / made_word_off, optional: where the masks made here stay on the device and the first word of every candidate's,
+// UINT64_MAX for a candidate without one -- left alone when the masks came in through d_mask_bits)
+int text_map_phase(str_er_ctx *c, hipStream_t s, const Batch &b, uint32_t stages, float qscale, const uint32_t *d_mask_bits, str_er_result *r,
+                   const uint32_t **d_made_bits = nullptr, std::vector<uint64_t> *made_word_off = nullptr);
+// the first frame coordinate x in [0, W] whose sample ((2x + 1) * wp) / (2W) is >= a: the pre-image of a level box is
+// [first_sample_at(x), first_sample_at(x + w)), the exact inverse of the pixel rule of str_er_frame_map
+int32_t first_sample_at(int64_t a, int64_t W, int64_t wp);
+// the page-locked / device buffer pair d, h of `bytes`, grown to at least `need` (geometrically), never shrunk
+int grow_pair(str_er_ctx *c, uint8_t *&d, uint8_t *&h, size_t &bytes, size_t need, const char *what);
+// the uint16 tables xs(x) = ((2x + 1) * np) / (2n), x in [0, n), of the pixel rule, one per (frame size, level size) pair asked for
+struct SampleTabs {
+    std::vector<uint16_t> tabs;
+    std::map<std::pair<int32_t, int32_t>, uint32_t> at;
+    uint32_t table(int32_t n, int32_t np);       // where the table of (n, np) starts in tabs
+};
+// ---- defined in api_frame_lines.cpp
+// STR_ER_WANT_FRAME_LINES in run_batch: the feet, pairs and frame lines of the lines of r.  d_mask_bits / word_off: mask words of this
+// call still on the device and the first word of every candidate's (UINT64_MAX: none), or null: then the members' masks are made here
+int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
+                      str_er_result *r);
 constexpr int MASK_MAX_WIDTH = 16384;       // widest box the mask kernels take (er_masks.inl: MASK_MAX_WPL words of 64 pixels per lane)
 // ---- defined in api_models.cpp
 int parse_cascade(str_er_ctx *c, HostCascade &hc, const char *text, size_t len);

@@ -394,6 +394,50 @@ public:
         return out;
     }
 
+    // The text lines of every frame merged across pyramid levels (STR_ER_WANT_FRAME_LINES; the contract is at str_er_line_foot in
+    // include/str_er.h): a foot per line of str_er_result_texts(), the pairs of lines with common pixels, the frame lines and the line
+    // indices their first / count index.
+    struct FrameLines {
+        std::vector<str_er_line_foot>  feet;
+        std::vector<str_er_line_pair>  pairs;
+        std::vector<str_er_frame_line> lines;
+        std::vector<int32_t>           members;
+        std::vector<uint32_t>          bits;         // line_feet_regions only: the footprints, line after line (str_er_line_feet_regions)
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static FrameLines frame_lines(const str_er_result *r)
+    {
+        FrameLines out;
+        int32_t n = 0;
+        if (const str_er_line_foot *p = str_er_result_line_feet(r, &n)) out.feet.assign(p, p + n);
+        if (const str_er_line_pair *p = str_er_result_line_pairs(r, &n)) out.pairs.assign(p, p + n);
+        if (const str_er_frame_line *p = str_er_result_frame_lines(r, &n)) out.lines.assign(p, p + n);
+        if (const int32_t *p = str_er_result_frame_line_members(r, &n)) out.members.assign(p, p + n);
+        return out;
+    }
+    // two lines of a frame are duplicates from a Jaccard index of num / den of their footprints on (str_er_set_frame_merge)
+    void set_frame_merge(int num, int den) { check(str_er_set_frame_merge(ctx_.get(), num, den)); }
+    // The footprints and overlaps of n_lines lines made of ERs of one 8UC1 plane (ER i belongs to line line_of[i]) on an out_w x out_h
+    // frame (str_er_line_feet_regions); the frame lines of the one frame by str_er_frame_lines_from_pairs at the context's threshold
+    FrameLines line_feet_regions(const Image8 &plane, const ERs &ers, const std::vector<int32_t> &line_of, int n_lines, int out_w, int out_h)
+    {
+        if (plane.channels != 1) throw std::runtime_error("line_feet_regions expects an 8UC1 plane");
+        if (line_of.size() != ers.size() || n_lines < 0) throw std::runtime_error("line_feet_regions: one line per ER");
+        const std::vector<str_er_cand> regions = regions_of(ers);
+        FrameLines out;
+        out.feet.resize((size_t)n_lines);
+        uint64_t n_words = 0;
+        int32_t  n_pairs = 0;
+        check(str_er_line_feet_regions(ctx_.get(), plane.data, plane.cols, plane.rows, plane.step, regions.data(), line_of.data(), (int32_t)regions.size(),
+                                       n_lines, out_w, out_h, out.feet.data(), nullptr, 0, &n_words, nullptr, 0, &n_pairs));
+        out.bits.resize((size_t)n_words);
+        out.pairs.resize((size_t)n_pairs);
+        check(str_er_line_feet_regions(ctx_.get(), plane.data, plane.cols, plane.rows, plane.step, regions.data(), line_of.data(), (int32_t)regions.size(),
+                                       n_lines, out_w, out_h, out.feet.data(), out.bits.empty() ? nullptr : out.bits.data(), n_words, &n_words,
+                                       out.pairs.empty() ? nullptr : out.pairs.data(), n_pairs, &n_pairs));
+        return out;
+    }
+
     // vector<double> ERFilter::make_LBP_hist(Mat input, N = 2, normalize_size = 24) (src/ER.cpp:789-816)
     std::vector<double> make_LBP_hist(const Image8 &input)
     {

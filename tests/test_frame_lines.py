@@ -1,0 +1,364 @@
+"""STR_ER_WANT_FRAME_LINES / str_er_line_feet_regions on the GPU: footprints, overlaps and frame lines against the numpy reference
+(frame_lines_ref.py), bit for bit."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import frame_lines_ref as R
+from test_er_masks import flood
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+GROUPED = 7 | 32 | 64                 # STAGE_ALL | STAGE_TRACK | STAGE_GROUP
+
+
+def _crops():
+    z = np.load(os.path.join(GOLDEN, "icdar_crops.npz"))
+    return [np.ascontiguousarray(z[k]) for k in sorted(z.files)]
+
+
+def _ctx(S, cascade_paths, **kw):
+    f = S.ERFilter(params=S.Params(**kw))
+    f.load_cascade(0, cascade_paths[0])
+    f.load_cascade(1, cascade_paths[1])
+    return f
+
+
+def _regions(S, boxes):
+    r = np.zeros(len(boxes), S.CAND_DTYPE)
+    for i, (x, y, w, h, key, level) in enumerate(boxes):
+        r[i]["x"], r[i]["y"], r[i]["w"], r[i]["h"], r[i]["key"], r[i]["level"] = x, y, w, h, key, level
+    return r
+
+
+def reference(res, sizes, num=1, den=2):
+    """The feet, pairs and frame lines of a result that carries its masks (want_masks=True), by the reference."""
+    feet = []
+    for tx in res.texts:
+        W, H = sizes[int(tx["frame"])]
+        mem = []
+        for k in sorted({int(k) for k in res.text_ers[int(tx["first"]):int(tx["first"]) + int(tx["count"])]}):
+            c = res.cands[k]
+            p = res.planes[int(c["plane"])]
+            mem.append((p.width, p.height, int(c["x"]), int(c["y"]), res.mask(k)))
+        feet.append(R.footprint(W, H, mem))
+    frames, pyr = [int(t["frame"]) for t in res.texts], [int(t["pyr"]) for t in res.texts]
+    pairs = R.all_pairs(feet, frames)
+    boxes = [(f.x, f.y, f.w, f.h) for f in feet]
+    dup, frame_line, lines, members = R.frame_lines(boxes, [f.pixels for f in feet], frames, pyr, pairs, num, den)
+    return feet, pairs, dup, frame_line, lines, members
+
+
+def check(res, ref, dups=True):
+    feet, pairs, dup, frame_line, lines, members = ref
+    got = res.line_feet
+    assert len(got) == len(feet) == len(res.texts)
+    for t, f in enumerate(feet):
+        assert (int(got[t]["x"]), int(got[t]["y"]), int(got[t]["w"]), int(got[t]["h"]), int(got[t]["pixels"])) == (f.x, f.y, f.w, f.h, f.pixels), t
+    assert [(int(p["a"]), int(p["b"]), int(p["inter"])) for p in res.line_pairs] == pairs
+    if not dups:
+        return
+    assert [int(p["dup"]) for p in res.line_pairs] == dup
+    assert [int(f["frame_line"]) for f in got] == frame_line
+    assert [{k: int(g[k]) for k in g.dtype.names} for g in res.frame_lines] == lines
+    assert [int(m) for m in res.frame_line_members] == members
+
+
+# ---- str_er_line_feet_regions on a hand-made plane -------------------------------------------------------------------------------------
+
+def _hand_made(rng):
+    """A 307 x 173 plane: a dark block (every box inside it is a full mask), rings, and noise with walls (irregular floods)."""
+    pw, ph = 307, 173
+    plane = (rng.random((ph, pw)) * 120 + 120).astype(np.uint8)       # levels 15 .. 29
+    plane[:, ::7] = 247
+    plane[4:40, 2:300] = 0                                            # the block
+    boxes, line_of = [], []
+
+    def add(line, x, y, w, h, kx=None, ky=None, level=0):
+        kx, ky = x if kx is None else kx, y if ky is None else ky
+        boxes.append((x, y, w, h, ky * pw + kx, level))
+        line_of.append(line)
+
+    add(0, 3, 10, 290, 6)                   # line 0: a bar wider than 64 pixels ...
+    for k in range(64):                     # ... lines 1 .. 64: bars whose left edges take every residue modulo 64 against it
+        add(1 + k, 5 + k, 12 + (k % 3), 70 + (k % 5), 3)
+    n = 65
+    add(n, 10, 30, 50, 5); add(n, 70, 30, 50, 5)             # two lines with identical members (Jaccard 1)
+    add(n + 1, 10, 30, 50, 5); add(n + 1, 70, 30, 50, 5)
+    add(n + 1, 70, 30, 50, 5)                                # (one of them listed twice)
+    n += 2
+    plane[50:80, 10:60] = 0; plane[56:74, 16:54] = 200       # a ring, and a bar inside its hole
+    plane[60:70, 20:50] = 0
+    add(n, 10, 50, 50, 30); add(n + 1, 20, 60, 30, 10)       # two disjoint lines whose boxes nest
+    n += 2
+    plane[0, 0] = 0
+    add(n, 0, 0, 1, 1)                                       # one pixel: no sample of a smaller output hits it
+    n += 1
+    lut_q = np.rint(plane / 8.0)                             # (only to pick levels: the masks come from flood on the oracle's levels)
+    for k in range(30):                                      # irregular floods in the noise, three to a line
+        w, h = int(rng.integers(8, 120)), int(rng.integers(4, 60))
+        x, y = int(rng.integers(0, pw - w + 1)), int(rng.integers(85, ph - h + 1))
+        kx, ky = x + int(rng.integers(0, w)), y + int(rng.integers(0, h))
+        add(n + k // 3, x, y, w, h, kx, ky, min(31, int(lut_q[ky, kx]) + int(rng.integers(0, 4))))
+    n += 10
+    return plane, boxes, line_of, n
+
+
+@pytest.mark.parametrize("ow,oh", [(307, 173), (1920, 1080), (97, 55), (6000, 173)])
+def test_single_stage_hand_made(S, cascade_paths, oracle, ow, oh):
+    f = _ctx(S, cascade_paths, max_width=1024, max_height=512, max_frames=1)
+    plane, boxes, line_of, n_lines = _hand_made(np.random.default_rng(5))
+    ph, pw = plane.shape
+    q = oracle.quant_lut(8)[plane]
+    mem = [[] for _ in range(n_lines)]
+    for (x, y, w, h, key, level), t in zip(boxes, line_of):
+        mem[t].append((pw, ph, x, y, flood(q, x, y, w, h, key, level)))
+    ref = [R.footprint(ow, oh, m) for m in mem]
+    feet, bits, pairs = f.line_feet_regions(plane, _regions(S, boxes), line_of, n_lines, ow, oh)
+    for t, r in enumerate(ref):
+        g = feet[t]
+        assert (int(g["x"]), int(g["y"]), int(g["w"]), int(g["h"]), int(g["pixels"])) == (r.x, r.y, r.w, r.h, r.pixels), t
+    exp_bits = np.concatenate([r.words() for r in ref] + [np.zeros(0, "<u4")])
+    assert len(bits) == len(exp_bits) and (bits == exp_bits).all()
+    exp_pairs = R.all_pairs(ref, [0] * n_lines)
+    assert [(int(p["a"]), int(p["b"]), int(p["inter"])) for p in pairs] == exp_pairs
+    dup, frame_line, lines, members = R.frame_lines([(r.x, r.y, r.w, r.h) for r in ref], [r.pixels for r in ref], [0] * n_lines, [0] * n_lines, exp_pairs)
+    assert [int(p["dup"]) for p in pairs] == dup and [int(g["frame_line"]) for g in feet] == frame_line
+    # the cases the plane was made for
+    by = {(a, b): k for a, b, k in exp_pairs}
+    assert ref[0].w > 64 * ow // 307 and all((0, 1 + k) in by for k in range(64))
+    if ow == 307:
+        assert {(ref[1 + k].x - ref[0].x) % 64 for k in range(64)} == set(range(64))
+    if ow == 6000:
+        assert ref[0].w > 4096
+    assert by[(65, 66)] == ref[65].pixels == ref[66].pixels and frame_line[65] == frame_line[66]         # Jaccard 1
+    assert (67, 68) not in by and frame_line[67] != frame_line[68]                                         # nested boxes, no common pixel
+    assert (ref[69].pixels == 0) == (ow == 97)                                                             # the empty footprint
+    if ow == 97:
+        assert tuple(int(feet[69][k]) for k in ("x", "y", "w", "h", "pixels")) == (0, 0, 0, 0, 0)
+    assert len(exp_pairs) > 100 and 0 < sum(dup) < len(dup)
+    f.close()
+
+
+# ---- the fused call ------------------------------------------------------------------------------------------------------------------
+
+def test_fused_pyramid_1080p(S, cascade_paths):
+    """8 levels x 3 channels on the S-text frame of seed 970 (the frame test_text_map.py uses).  The reference is built from the masks,
+    lines and members of the same call (the masks and the grouping have oracle tests of their own).  The frame must have a frame line with
+    members of two pyramid levels and one that stays alone, or the test would pass without joining anything: asserted below on the
+    reference's output.  Seed 970 satisfies it: 31 lines, 12 pairs, 7 duplicates, 25 frame lines, 5 of them with two or more levels,
+    20 alone -- read off this library's lines (whose tracking and grouping are held against the oracle by test_track.py), not from a
+    run of the oracle alone."""
+    L = 8
+    f = _ctx(S, cascade_paths, max_width=1920, max_height=1080, max_frames=1, n_pyr_levels=L, channel_mask=0x07)
+    frame = S.synth.stext_bgr(S.synth.frame_seed(970), 1920, 1080)
+    res = f.text_detect(frame, GROUPED, want_masks=True, want_frame_lines=True)
+    ref = reference(res, [(1920, 1080)])
+    lines = ref[4]
+    print("lines", len(res.texts), "pairs", len(ref[1]), "dups", sum(ref[2]), "frame lines", len(lines),
+          "multi-level", sum(bin(g["levels"]).count("1") >= 2 for g in lines), "alone", sum(g["count"] == 1 for g in lines))
+    assert any(bin(g["levels"]).count("1") >= 2 for g in lines) and any(g["count"] == 1 for g in lines)
+    check(res, ref)
+    assert {int(t["pyr"]) for t in res.texts} > {0}
+    # without the masks in the result (the stage makes the members' masks itself), and behind the maps (it takes theirs)
+    for kw in ({}, {"want_line_map": True}, {"want_text_map": True, "want_strokes": True}):
+        other = f.text_detect(frame, GROUPED, want_frame_lines=True, **kw)
+        for k in ("line_feet", "line_pairs", "frame_lines", "frame_line_members"):
+            assert getattr(other, k).tobytes() == getattr(res, k).tobytes(), (kw, k)
+    f.close()
+
+
+def _cols(a, names):
+    """The named fields of a record array as bytes (a multi-field view would drag the others along)."""
+    return np.stack([a[k].astype(np.int64) for k in names], 1).tobytes() if len(a) else b""
+
+
+FOOT, PAIR = ("x", "y", "w", "h", "pixels"), ("a", "b", "inter")
+
+
+def _shifted(one, first):
+    """The records of a one-frame call as they appear in a list call whose earlier frames have `first` lines (frame lines not compared)."""
+    p = one.line_pairs.copy()
+    p["a"] += first; p["b"] += first
+    return _cols(one.line_feet, FOOT), p.tobytes()
+
+
+def test_lists_nv12_and_the_stream(S, cascade_paths):
+    prm = S.Params(max_width=640, max_height=480, max_frames=8, n_pyr_levels=3)
+    f = S.ERFilter(params=prm)
+    f.load_cascade(0, cascade_paths[0]); f.load_cascade(1, cascade_paths[1])
+    sy = S.synth
+    frames = _crops() + [sy.stext_bgr(sy.frame_seed(971), 333, 211), sy.stext_bgr(sy.frame_seed(972), 517, 301)]
+    flags = GROUPED | S.WANT_FRAME_LINES
+    lst = f.text_detect_list(frames, GROUPED, want_frame_lines=True, want_masks=True)
+    check(lst, reference(lst, [(fr.shape[1], fr.shape[0]) for fr in frames]))
+    assert len(lst.texts) > 0 and len(lst.line_pairs) > 0
+    fl_at = 0
+    for i, fr in enumerate(frames):
+        one = f.text_detect(fr, GROUPED, want_frame_lines=True)
+        first = int(np.searchsorted(lst.texts["frame"], i, "left"))
+        n = len(one.texts)
+        feet, pairs = _shifted(one, first)
+        assert _cols(lst.line_feet[first:first + n], FOOT) == feet
+        sel = lst.line_pairs[(lst.line_pairs["a"] >= first) & (lst.line_pairs["a"] < first + n)]
+        assert sel.tobytes() == pairs
+        mine = lst.frame_lines[lst.frame_lines["frame"] == i]
+        assert len(mine) == len(one.frame_lines)
+        assert (lst.line_feet["frame_line"][first:first + n] == one.line_feet["frame_line"] + fl_at).all()
+        for k in ("rep",):
+            assert (mine[k] == one.frame_lines[k] + first).all()
+        for k in ("count", "x", "y", "w", "h", "pixels", "levels"):
+            assert (mine[k] == one.frame_lines[k]).all(), k
+        fl_at += len(mine)
+    nvf = [sy.stext_bgr(sy.frame_seed(976), 640, 480), sy.stext_bgr(sy.frame_seed(977), 322, 244)]
+    nv = [sy.nv12_from_bgr(b) for b in nvf]
+    nres = f.text_detect_nv12_list(nv, flags | S.WANT_MASKS)
+    check(nres, reference(nres, [(b.shape[1], b.shape[0]) for b in nvf]))
+    one = f.text_detect_nv12(nv[0], 640, 480, flags)
+    n0 = len(one.texts)
+    assert n0 > 0 and nres.line_feet[:n0].tobytes() == one.line_feet.tobytes()
+    st = S.FrameStream(prm, depth=2)
+    st.load_cascade(0, cascade_paths[0]); st.load_cascade(1, cascade_paths[1])
+    st.submit_copy_list(frames, flags)
+    _, a = st.next()
+    for k in ("line_feet", "line_pairs", "frame_lines", "frame_line_members"):
+        assert getattr(a, k).tobytes() == getattr(lst, k).tobytes(), k
+    st.close(); f.close()
+
+
+FIELDS = ("info", "cands", "tracks", "texts", "text_ers", "group_bounds", "group_all", "masks", "mask_bits", "shapes", "strokes", "line_crops",
+          "line_crop_pixels", "line_glyph_pixels", "frame_maps", "text_map_pixels", "line_map_ids")
+
+
+def _same(a, b):
+    for k in FIELDS:
+        x, y = getattr(a, k), getattr(b, k)
+        assert (x is None) == (y is None), k
+        if x is not None:
+            assert x.tobytes() == y.tobytes(), k
+
+
+def test_frame_lines_change_nothing_else(S, cascade_paths):
+    f = _ctx(S, cascade_paths, max_width=640, max_height=480, max_frames=4, n_pyr_levels=2)
+    sy = S.synth
+    frames = [sy.stext_bgr(sy.frame_seed(2), 640, 480), _crops()[1], sy.snoise_bgr(sy.frame_seed(980), 200, 100)]
+    every = (S.WANT_NODES | S.WANT_MASKS | S.WANT_SHAPES | S.WANT_STROKES | S.WANT_LINE_CROPS | S.WANT_LINE_GLYPHS | S.WANT_TEXT_MAP |
+             S.WANT_LINE_MAP)
+    got = []
+    for extra in (0, S.WANT_MASKS, S.WANT_LINE_MAP, S.WANT_TEXT_MAP | S.WANT_LINE_CROPS | S.WANT_LINE_GLYPHS, every):
+        plain = f.text_detect_list(frames, GROUPED | extra)
+        with pytest.raises(ValueError):
+            plain.line_feet
+        with pytest.raises(ValueError):
+            plain.frame_lines
+        r = f.text_detect_list(frames, GROUPED | extra | S.WANT_FRAME_LINES)
+        _same(plain, r)
+        got.append(r)
+        _same(plain, f.text_detect_list(frames, GROUPED | extra))
+    for r in got[1:]:
+        for k in ("line_feet", "line_pairs", "frame_lines", "frame_line_members"):
+            assert getattr(r, k).tobytes() == getattr(got[0], k).tobytes(), k
+    assert len(got[0].texts) > 0 and len(got[0].frame_lines) > 0
+    check(got[1], reference(got[1], [(fr.shape[1], fr.shape[0]) for fr in frames]))
+    # a grouped call without lines: empty tables, not an error
+    blank = f.text_detect(np.full((120, 160, 3), 128, np.uint8), GROUPED, want_frame_lines=True)
+    assert len(blank.texts) == 0 and len(blank.line_feet) == 0 and len(blank.line_pairs) == 0 and len(blank.frame_lines) == 0
+    f.close()
+
+
+def test_threshold(S, cascade_paths):
+    f = _ctx(S, cascade_paths, max_width=640, max_height=480, max_frames=1, n_pyr_levels=4)
+    frame = S.synth.stext_bgr(S.synth.frame_seed(2), 640, 480)
+    base = f.text_detect(frame, GROUPED, want_masks=True, want_frame_lines=True)
+    check(base, reference(base, [(640, 480)]))
+    assert len(base.line_pairs) > 0
+    seen = {base.frame_lines.tobytes()}
+    for num, den in ((1, 1), (1, 50), (3, 4)):
+        f.set_frame_merge(num, den)
+        r = f.text_detect(frame, GROUPED, want_masks=True, want_frame_lines=True)
+        check(r, reference(r, [(640, 480)], num, den))
+        assert _cols(r.line_feet, FOOT) == _cols(base.line_feet, FOOT) and _cols(r.line_pairs, PAIR) == _cols(base.line_pairs, PAIR)
+        seen.add(r.frame_lines.tobytes())
+    assert len(seen) > 1                       # (the threshold matters on this frame)
+    for num, den in ((0, 2), (3, 2), (1, 65536), (-1, -1)):
+        with pytest.raises(S.StrErError) as e:
+            f.set_frame_merge(num, den)
+        assert e.value.code == -1
+    again = f.text_detect(frame, GROUPED, want_masks=True, want_frame_lines=True)       # the setting (3, 4) was kept
+    assert again.frame_lines.tobytes() == r.frame_lines.tobytes() and again.line_pairs.tobytes() == r.line_pairs.tobytes()
+    f.close()
+
+
+def test_errors(S, cascade_paths):
+    f = _ctx(S, cascade_paths, max_width=320, max_height=240, max_frames=1)
+    frame = S.synth.stext_bgr(S.synth.frame_seed(981), 320, 240)
+    good = f.text_detect(frame, GROUPED, want_frame_lines=True)
+
+    def usable():
+        assert f.text_detect(frame, GROUPED, want_frame_lines=True).line_feet.tobytes() == good.line_feet.tobytes()
+
+    for stages in (S.STAGE_ALL | S.WANT_FRAME_LINES, S.STAGE_ALL | S.STAGE_TRACK | S.WANT_FRAME_LINES):
+        with pytest.raises(S.StrErError) as e:
+            f.text_detect(frame, stages)
+        assert e.value.code == -1 and "FRAME_LINES" in str(e.value)
+        usable()
+    planes = f.compute_channels(frame)
+    with pytest.raises(S.StrErError) as e:
+        f.detect_planes(planes[:1], S.STAGE_ALL | S.WANT_FRAME_LINES)
+    assert e.value.code == -1
+    usable()
+    with pytest.raises(S.StrErError) as e:
+        f.detect_planes_list([planes[0], planes[1][:100, :90]], S.STAGE_ALL | S.WANT_FRAME_LINES)
+    assert e.value.code == -1
+    usable()
+    n_sel = len(good.planes)
+    for stages in (S.STAGE_ALL | S.WANT_FRAME_LINES, GROUPED | S.WANT_FRAME_LINES):
+        with pytest.raises(S.StrErError) as e:
+            f.text_detect_planes(frame, [1] + [0] * (n_sel - 1), stages)
+        assert e.value.code == -1
+        usable()
+    blob = (C.c_char * 16)()
+    blobs = (C.c_void_p * 1)(C.cast(blob, C.c_void_p))
+    sizes = (C.c_int64 * 1)(16)
+    rh = C.c_void_p()
+    rc = f.L.str_er_strip_merge(f.h, frame.ctypes.data, 320, 240, 960, 0, C.cast(blobs, C.c_void_p), C.cast(sizes, C.c_void_p), 1,
+                                S.STAGE_ALL | S.WANT_FRAME_LINES, C.byref(rh))
+    assert rc == -1 and b"FRAME_LINES" in f.L.str_er_last_error(f.h)
+    usable()
+    wide = np.zeros((1, 16385), np.uint8)
+    with pytest.raises(S.StrErError) as e:
+        f.line_feet_regions(wide, _regions(S, [(0, 0, 16385, 1, 0, 0)]), [0], 1, 100, 1)
+    assert e.value.code == -7
+    plane = np.zeros((100, 120), np.uint8)
+    ok = _regions(S, [(0, 0, 120, 50, 0, 0)])
+    with pytest.raises(S.StrErError) as e:
+        f.line_feet_regions(plane, ok, [1], 1, 120, 100)
+    assert e.value.code == -1 and "region 0" in str(e.value)
+    feet, bits, pairs = f.line_feet_regions(plane, ok, [0], 1, 120, 100)
+    assert int(feet[0]["pixels"]) == 120 * 50 and len(pairs) == 0 and len(bits) == 50 * 4
+    usable()
+    f.close()
+
+
+def test_cpp_example(S, cascade_paths, tmp_path):
+    libdir = os.path.dirname(S.lib_path())
+    exe = str(tmp_path / "example_frame_lines")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "scene-text-recognition_amd", "host", "example_frame_lines.cpp"),
+                    "-I", os.path.join(ROOT, "include"), "-L", libdir, "-lstr_er_hip", f"-Wl,-rpath,{libdir}", "-o", exe], check=True)
+    frame = S.synth.stext_bgr(S.synth.frame_seed(2), 640, 480)
+    raw = tmp_path / "f.bgr"
+    raw.write_bytes(np.ascontiguousarray(frame).tobytes())
+    out = subprocess.run([exe, cascade_paths[0], cascade_paths[1], str(raw), "640", "480", "3"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout + out.stderr
+    rows = out.stdout.splitlines()
+    f = _ctx(S, cascade_paths, max_width=640, max_height=480, max_frames=1, n_pyr_levels=3)
+    res = f.text_detect(frame, GROUPED, want_frame_lines=True)
+    assert rows[0].split() == ["frame", "640", "480", "lines", str(len(res.texts)), "pairs", str(len(res.line_pairs)), "frame_lines", str(len(res.frame_lines))]
+    assert len(rows) - 1 == len(res.frame_lines) > 0
+    g = res.frame_lines[0]
+    assert rows[1].split()[:7] == ["0", "box", str(int(g["x"])), str(int(g["y"])), str(int(g["w"])), str(int(g["h"])), "pixels"]
+    f.close()
