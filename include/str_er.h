@@ -103,6 +103,12 @@ extern "C" {
  * contributing candidate wider than 16384 pixels gives STR_ER_ECAPACITY.  It changes no other output of the call and combines with
  * every other STR_ER_WANT_* flag; the masks are still made once per call.                                                        */
 #define STR_ER_WANT_FRAME_LINES (131072u)
+/* output option: link the text lines of consecutive frames of the call into text tracks (str_er_result_line_links / _line_tracks /
+ * _text_tracks / _text_track_members / _edge_feet; the contract is at str_er_line_link).  Needs STR_ER_WANT_FRAME_LINES (which needs
+ * STR_ER_STAGE_GROUP and frames): STR_ER_EINVAL without it, and wherever _FRAME_LINES is refused (str_er_detect_planes[_list],
+ * str_er_strip_merge[_ex]), the context usable afterwards.  str_er_detect_bgr, _nv12, _bgr_list, _nv12_list and every
+ * str_er_stream_submit* call honour it.  It changes no other output of the call.                                                  */
+#define STR_ER_WANT_LINE_LINKS (262144u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -320,6 +326,31 @@ typedef struct str_er_frame_line {
     uint32_t pixels;         /* 32: the representative's                                                */
     uint32_t levels;         /* 36: bit k set if a member has pyr == k (k < 32)                         */
 } str_er_frame_line;         /* 40 bytes */
+
+/* The text lines of consecutive frames linked into text tracks (STR_ER_WANT_LINE_LINKS, str_er_link_feet,
+ * str_er_text_tracks_from_links).  All exact integers, on top of the footprints of str_er_line_foot.
+ *   Time order: the frames of a call are in time order, frame f + 1 follows frame f.  Frames f and f + 1 are adjacent iff their
+ *     level-0 sizes are equal; across a change of size (list calls) there are no links.
+ *   Overlap of a line a of frame f and a line b of an adjacent frame f + 1: inter(a, b) = |F(a) & F(b)|, the two footprints read at the
+ *     same pixel coordinates.  Every such pair with inter > 0 is a record; the table is sorted by (a, b).
+ *   Link: link = 1 iff inter * den >= num * (|F(a)| + |F(b)| - inter), in 64-bit integers.  num / den: str_er_set_line_link, default
+ *     1 / 2 -- a definition of this library, like the duplicate threshold of str_er_line_foot; it is not tuned on labelled data.
+ *   Text track: a connected component of (duplicates within a frame, str_er_line_pair::dup) u (links across adjacent frames) over all
+ *     lines of the call: the transitive closure, so no order of joining is involved.  Its representative is the member with the most
+ *     footprint pixels, ties to the smallest line index.  Tracks are ordered by first_frame, then by their smallest member.
+ *   Across calls and stream submissions nothing is remembered: a result made with the flag keeps the footprints of the lines of its
+ *     first and of its last frame on the host (str_er_result_edge_feet), and str_er_link_feet overlaps two such sets.              */
+typedef struct str_er_line_link {
+    int32_t  a, b;           /*  0: a line of frame f and a line of the adjacent frame f + 1            */
+    uint32_t inter;          /*  8: |F(a) & F(b)|, > 0                                                  */
+    uint32_t link;           /* 12: 1 if the two are linked at the call's num / den, else 0             */
+} str_er_line_link;          /* 16 bytes; every such pair with inter > 0, sorted by (a, b) */
+typedef struct str_er_text_track {
+    uint32_t first_frame, last_frame;  /*  0: the smallest and the largest frame of a member            */
+    int32_t  first, count;   /*  8: its members: str_er_result_text_track_members()[first .. first + count), line indices, ascending */
+    int32_t  rep;            /* 16: the representative: a line index                                    */
+    uint32_t pixels;         /* 20: the representative's                                                */
+} str_er_text_track;         /* 24 bytes */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -542,6 +573,29 @@ int str_er_frame_lines_from_pairs(str_er_line_foot *feet, const uint32_t *frames
                                   str_er_line_pair *pairs, int32_t n_pairs, int32_t num, int32_t den, str_er_frame_line *frame_lines,
                                   int32_t cap_frame_lines, int32_t *n_frame_lines, int32_t *members);
 
+/* The link threshold num / den of STR_ER_WANT_LINE_LINKS and str_er_link_feet (str_er_line_link): 1 <= num <= den <= 65535, default
+ * 1 / 2.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts: str_er_stream_context.                     */
+int str_er_set_line_link(str_er_ctx *ctx, int32_t num, int32_t den);
+/* The overlaps (str_er_line_link) of every line of set a with every line of set b, two sets of footprints in the pixels of one frame
+ * size W x H (1..65535): feet_x[i] is the foot box and pixel count of line i of the set, bits_x its rows of (w + 31) / 32 32-bit words
+ * over the box, back to back in set order -- the layout str_er_line_feet_regions and str_er_result_edge_feet return.  pairs receives
+ * the records with inter > 0, a an index into set a and b into set b, sorted by (a, b), link set at the context's num / den;
+ * pairs == NULL only reports *n_pairs; cap_pairs too small -> STR_ER_ECAPACITY, *n_pairs still set.  STR_ER_EINVAL: bad arguments, a
+ * box that leaves the frame, a set bit past a row's width, pixels that are not the number of set bits.  Either set may be empty.  */
+int str_er_link_feet(str_er_ctx *ctx, int32_t W, int32_t H, const str_er_line_foot *feet_a, const uint32_t *bits_a, int32_t n_a,
+                     const str_er_line_foot *feet_b, const uint32_t *bits_b, int32_t n_b, str_er_line_link *pairs, int32_t cap_pairs,
+                     int32_t *n_pairs);
+/* The text tracks of n_lines lines from their feet, pairs and links (str_er_line_link).  Pure host, no context, no GPU; the detect
+ * calls use this same function.  Reads feet[t].pixels, frames_of_lines[t], pairs[k].a, b, inter, dup and links[k].a, b, inter; sets
+ * links[k].link and line_tracks[t] (n_lines track indices), fills tracks (at most n_lines: cap_tracks too small -> STR_ER_ECAPACITY,
+ * *n_tracks still set; tracks == NULL only counts, sets link and line_tracks) and members (n_lines line indices).  STR_ER_EINVAL: bad
+ * arguments, an index outside [0, n_lines), a pair with a >= b or of two frames, a link whose b is not of the frame after a's,
+ * inter == 0 or inter larger than either footprint.                                                                             */
+int str_er_text_tracks_from_links(const str_er_line_foot *feet, const uint32_t *frames_of_lines, int32_t n_lines,
+                                  const str_er_line_pair *pairs, int32_t n_pairs, str_er_line_link *links, int32_t n_links, int32_t num,
+                                  int32_t den, int32_t *line_tracks, str_er_text_track *tracks, int32_t cap_tracks, int32_t *n_tracks,
+                                  int32_t *members);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -740,6 +794,19 @@ const str_er_line_foot  *str_er_result_line_feet(const str_er_result *r, int32_t
 const str_er_line_pair  *str_er_result_line_pairs(const str_er_result *r, int32_t *n);
 const str_er_frame_line *str_er_result_frame_lines(const str_er_result *r, int32_t *n);
 const int32_t           *str_er_result_frame_line_members(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_LINE_LINKS (str_er_line_link): the overlaps of lines of adjacent frames sorted by (a, b), one track index per line
+ * of str_er_result_texts(), the text tracks and the line indices their first / count index.  Each returns NULL and 0 without the
+ * flag; a call without lines returns empty arrays (not NULL).                                                                      */
+const str_er_line_link  *str_er_result_line_links(const str_er_result *r, int32_t *n);
+const int32_t           *str_er_result_line_tracks(const str_er_result *r, int32_t *n);
+const str_er_text_track *str_er_result_text_tracks(const str_er_result *r, int32_t *n);
+const int32_t           *str_er_result_text_track_members(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_LINE_LINKS: the edge feet of the result, which = 0: of the lines of its first frame, 1: of its last frame (the
+ * same frame in a call of one frame).  *n lines; lines[i] is the index into str_er_result_texts(), feet[i] its foot, bits its rows
+ * of (w + 31) / 32 words over the foot box, back to back (*n_words in all): what str_er_link_feet takes.  *frame_w, *frame_h: the
+ * frame's level-0 size.  STR_ER_EINVAL without the flag or with another `which`; any output pointer may be NULL.                 */
+int str_er_result_edge_feet(const str_er_result *r, int32_t which, int32_t *frame_w, int32_t *frame_h, const str_er_line_foot **feet,
+                            const int32_t **lines, int32_t *n, const uint32_t **bits, uint64_t *n_words);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

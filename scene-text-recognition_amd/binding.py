@@ -52,6 +52,13 @@ LINE_PAIR_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("inter", "<u4"), ("dup"
 # str_er_frame_line: members = frame_line_members[first:first + count] (line indices, ascending), rep the one with the most pixels
 FRAME_LINE_DTYPE = np.dtype([("frame", "<u4"), ("rep", "<i4"), ("first", "<i4"), ("count", "<i4"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"),
                              ("h", "<i4"), ("pixels", "<u4"), ("levels", "<u4")])
+# output option: the lines of consecutive frames linked into text tracks (needs WANT_FRAME_LINES; Result.line_links / line_tracks /
+# text_tracks / text_track_members / edge_feet(which); the contract is at str_er_line_link in include/str_er.h)
+WANT_LINE_LINKS = 262144
+# str_er_line_link: a line a of frame f and a line b of the adjacent frame f + 1 with inter > 0 common pixels; link: linked at the call's threshold
+LINE_LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("inter", "<u4"), ("link", "<u4")])
+# str_er_text_track: members = text_track_members[first:first + count] (line indices, ascending), rep the one with the most pixels
+TEXT_TRACK_DTYPE = np.dtype([("first_frame", "<u4"), ("last_frame", "<u4"), ("first", "<i4"), ("count", "<i4"), ("rep", "<i4"), ("pixels", "<u4")])
 # str_er_line_crop: crop t = width x height bytes (pitch width) from byte pix_off of the crop bytes (and of the glyph bytes);
 # ax .. vy: the 16.16 sampling geometry (include/str_er.h)
 LINE_CROP_DTYPE = np.dtype([("pix_off", "<u8"), ("width", "<i4"), ("height", "<i4"), ("ax", "<i4"), ("ay", "<i4"),
@@ -78,6 +85,7 @@ assert SHAPE_DTYPE.itemsize == 48
 assert STROKE_DTYPE.itemsize == 32
 assert FRAME_MAP_DTYPE.itemsize == 16
 assert LINE_FOOT_DTYPE.itemsize == 24 and LINE_PAIR_DTYPE.itemsize == 16 and FRAME_LINE_DTYPE.itemsize == 40
+assert LINE_LINK_DTYPE.itemsize == 16 and TEXT_TRACK_DTYPE.itemsize == 24
 
 
 def unpack_mask(words: np.ndarray, word_off: int, w: int, h: int) -> np.ndarray:
@@ -275,6 +283,13 @@ def load_library():
     L.str_er_line_feet_regions.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp,
                                            C.c_uint64, C.POINTER(C.c_uint64), vp, C.c_int32, i32p]
     L.str_er_frame_lines_from_pairs.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, i32p, vp]
+    for fn in (L.str_er_result_line_links, L.str_er_result_line_tracks, L.str_er_result_text_tracks, L.str_er_result_text_track_members):
+        fn.argtypes = [vp, i32p]
+        fn.restype = vp
+    L.str_er_result_edge_feet.argtypes = [vp, C.c_int32, i32p, i32p, C.POINTER(vp), C.POINTER(vp), i32p, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.str_er_set_line_link.argtypes = [vp, C.c_int32, C.c_int32]
+    L.str_er_link_feet.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, i32p]
+    L.str_er_text_tracks_from_links.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, i32p, vp]
     L.str_er_line_crop_geometry.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, vp]
     L.str_er_line_crops.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, C.c_uint64,
                                     C.POINTER(C.c_uint64), vp]
@@ -400,7 +415,44 @@ class Result:
         self._line_pairs = None
         self._frame_lines = None
         self._frame_line_members = None
+        self._line_links = None    # with WANT_LINE_LINKS: the tables behind line_links / line_tracks / text_tracks / text_track_members / edge_feet
+        self._line_tracks = None
+        self._text_tracks = None
+        self._text_track_members = None
+        self._edge_feet = None
         self._planes = None
+
+    def _line_links_table(self, table):
+        if table is None:
+            raise ValueError("the result has no line links (pass WANT_LINE_LINKS / want_line_links=True)")
+        return table
+
+    @property
+    def line_links(self) -> np.ndarray:
+        """With WANT_LINE_LINKS: LINE_LINK_DTYPE per pair of lines of adjacent frames with common pixels, sorted by (a, b)."""
+        return self._line_links_table(self._line_links)
+
+    @property
+    def line_tracks(self) -> np.ndarray:
+        """With WANT_LINE_LINKS: the index into text_tracks of every line of texts (int32)."""
+        return self._line_links_table(self._line_tracks)
+
+    @property
+    def text_tracks(self) -> np.ndarray:
+        """With WANT_LINE_LINKS: TEXT_TRACK_DTYPE per text track, ordered by first frame, then by smallest member."""
+        return self._line_links_table(self._text_tracks)
+
+    @property
+    def text_track_members(self) -> np.ndarray:
+        """With WANT_LINE_LINKS: the line indices the tracks' first / count index (int32)."""
+        return self._line_links_table(self._text_track_members)
+
+    def edge_feet(self, which: int) -> "EdgeFeet":
+        """With WANT_LINE_LINKS: the footprints of the lines of the first (which = 0) or of the last frame (1) of the call, as
+        ERFilter.link_feet takes them."""
+        if which not in (0, 1):
+            raise ValueError("which is 0 (the first frame) or 1 (the last frame)")
+        return self._line_links_table(self._edge_feet)[which]
 
     def _frame_lines_table(self, table):
         if table is None:
@@ -614,6 +666,12 @@ class ERFilter:
                     res._line_pairs = table(L.str_er_result_line_pairs, LINE_PAIR_DTYPE)
                     res._frame_lines = table(L.str_er_result_frame_lines, FRAME_LINE_DTYPE)
                     res._frame_line_members = table(L.str_er_result_frame_line_members, np.int32)
+                    res._line_links = table(L.str_er_result_line_links, LINE_LINK_DTYPE)
+                    if res._line_links is not None:
+                        res._line_tracks = table(L.str_er_result_line_tracks, np.int32)
+                        res._text_tracks = table(L.str_er_result_text_tracks, TEXT_TRACK_DTYPE)
+                        res._text_track_members = table(L.str_er_result_text_track_members, np.int32)
+                        res._edge_feet = [self._edge_feet_of(rh, which) for which in (0, 1)]
             res.masks = table(L.str_er_result_masks, MASK_DTYPE)
             if res.masks is not None:
                 res.mask_bits = table(L.str_er_result_mask_bits, np.uint32, n64)
@@ -627,6 +685,15 @@ class ERFilter:
             return res
         finally:
             L.str_er_result_free(rh)
+
+    def _edge_feet_of(self, rh, which: int) -> "EdgeFeet":
+        w, h, n, nw = C.c_int32(), C.c_int32(), C.c_int32(), C.c_uint64()
+        feet, lines, bits = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        rc = self.L.str_er_result_edge_feet(rh, which, C.byref(w), C.byref(h), C.byref(feet), C.byref(lines), C.byref(n), C.byref(bits), C.byref(nw))
+        if rc != 0:
+            raise StrErError(rc, "str_er_result_edge_feet")
+        return EdgeFeet(w.value, h.value, _owned(lines.value, n.value, np.int32), _owned(feet.value, n.value, LINE_FOOT_DTYPE),
+                        _owned(bits.value, nw.value, np.uint32))
 
     def last_tree_stats(self) -> dict:
         """Node records / border pixel pairs / tiles of the last detect call (str_er_last_tree_stats)."""
@@ -661,7 +728,8 @@ class ERFilter:
     # ---- the hot path ---------------------------------------------------------------------------
     def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
-                    want_strokes: bool = False, want_frame_lines: bool = False) -> Result:
+                    want_strokes: bool = False, want_frame_lines: bool = False,
+                    want_line_links: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -673,7 +741,8 @@ class ERFilter:
         rh = C.c_void_p()
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
-                                                                  text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines), C.byref(rh)))
+                                                                  text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
+                                                                  line_links=want_line_links), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -793,14 +862,16 @@ class ERFilter:
 
     def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
-                         want_strokes: bool = False, want_frame_lines: bool = False) -> Result:
+                         want_strokes: bool = False, want_frame_lines: bool = False,
+                         want_line_links: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
-                                                      text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines))
+                                                      text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
+                                                                  line_links=want_line_links))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -962,6 +1033,32 @@ class ERFilter:
         pairs = np.zeros(max(1, npairs.value), LINE_PAIR_DTYPE)
         self._check(self.L.str_er_line_feet_regions(*args, _np_ptr(bits), len(bits), C.byref(nw), _np_ptr(pairs), len(pairs), C.byref(npairs)))
         return feet[:int(n_lines)], bits[:nw.value], pairs[:npairs.value]
+
+    def set_line_link(self, num: int = 1, den: int = 2) -> None:
+        """str_er_set_line_link: two lines of adjacent frames are linked from a Jaccard index of num / den of their footprints on
+        (1 <= num <= den <= 65535; WANT_LINE_LINKS and link_feet)."""
+        self._check(self.L.str_er_set_line_link(self.h, int(num), int(den)))
+
+    def link_feet(self, W: int, H: int, feet_a: np.ndarray, bits_a: np.ndarray, feet_b: np.ndarray, bits_b: np.ndarray) -> np.ndarray:
+        """str_er_link_feet: the overlaps of every line of set a with every line of set b, two sets of footprints in the pixels of one
+        (H, W) frame: feet LINE_FOOT_DTYPE (box and pixels are read), bits the rows of (w + 31) // 32 words over each foot box, back to
+        back -- what line_feet_regions and Result.edge_feet return.  Returns LINE_LINK_DTYPE records with inter > 0, a / b indices into
+        the two sets, sorted by (a, b), link set at the context's threshold."""
+        fa = np.ascontiguousarray(feet_a, dtype=LINE_FOOT_DTYPE).reshape(-1)
+        fb = np.ascontiguousarray(feet_b, dtype=LINE_FOOT_DTYPE).reshape(-1)
+        ba = np.ascontiguousarray(bits_a, dtype=np.uint32).reshape(-1)
+        bb = np.ascontiguousarray(bits_b, dtype=np.uint32).reshape(-1)
+        for ft, bt in ((fa, ba), (fb, bb)):
+            if int((ft["h"].astype(np.int64).clip(0) * ((ft["w"].astype(np.int64).clip(0) + 31) // 32)).sum()) != len(bt):
+                raise ValueError("bits needs h rows of (w + 31) // 32 words per foot, back to back")
+        n = C.c_int32()
+        args = (self.h, int(W), int(H), _np_ptr(fa) if len(fa) else None, _np_ptr(ba) if len(ba) else None, len(fa),
+                _np_ptr(fb) if len(fb) else None, _np_ptr(bb) if len(bb) else None, len(fb))
+        self._check(self.L.str_er_link_feet(*args, None, 0, C.byref(n)))
+        out = np.zeros(max(1, n.value), LINE_LINK_DTYPE)
+        if n.value:
+            self._check(self.L.str_er_link_feet(*args, _np_ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
 
     def set_line_crop(self, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> None:
         """str_er_set_line_crop: the crop height (8..256), the widest crop (1..8192) and the pad (0..1, of the line's height) of
@@ -1153,10 +1250,10 @@ def _owned(ptr, n: int, dtype) -> np.ndarray:
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False) -> int:
+                frame_lines=False, line_links=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -1180,6 +1277,86 @@ def frame_lines_from_pairs(feet: np.ndarray, frames_of_lines, pyr_of_lines, pair
     if rc != 0:
         raise StrErError(rc, "str_er_frame_lines_from_pairs")
     return ft, pr, fl[:nfl.value], mem[:n]
+
+
+def text_tracks_from_links(feet: np.ndarray, frames_of_lines, pairs: np.ndarray, links: np.ndarray, num: int = 1, den: int = 2):
+    """str_er_text_tracks_from_links (pure host): the text tracks of the lines with these feet (LINE_FOOT_DTYPE; pixels are read) and
+    frames from the pairs within a frame (LINE_PAIR_DTYPE; a, b, inter, dup are read) and the overlaps across adjacent frames
+    (LINE_LINK_DTYPE; a, b, inter are read).  Returns (links with link set, line_tracks int32, tracks TEXT_TRACK_DTYPE, members int32)."""
+    ft = np.ascontiguousarray(feet, dtype=LINE_FOOT_DTYPE).reshape(-1)
+    pr = np.ascontiguousarray(pairs, dtype=LINE_PAIR_DTYPE).reshape(-1)
+    lk = np.array(links, dtype=LINE_LINK_DTYPE).reshape(-1)
+    fr = np.ascontiguousarray(frames_of_lines, dtype=np.uint32).reshape(-1)
+    n = len(ft)
+    if len(fr) != n:
+        raise ValueError("frames_of_lines needs one entry per line")
+    lt = np.zeros(max(1, n), np.int32)
+    tr = np.zeros(max(1, n), TEXT_TRACK_DTYPE)
+    mem = np.zeros(max(1, n), np.int32)
+    ntr = C.c_int32()
+    rc = load_library().str_er_text_tracks_from_links(_np_ptr(ft) if n else None, _np_ptr(fr) if n else None, n, _np_ptr(pr) if len(pr) else None, len(pr),
+                                                      _np_ptr(lk) if len(lk) else None, len(lk), int(num), int(den), _np_ptr(lt), _np_ptr(tr), len(tr),
+                                                      C.byref(ntr), _np_ptr(mem))
+    if rc != 0:
+        raise StrErError(rc, "str_er_text_tracks_from_links")
+    return lk, lt[:n], tr[:ntr.value], mem[:n]
+
+
+@dataclass
+class EdgeFeet:
+    """The footprints of the lines of one frame of a result (Result.edge_feet): the frame's size, the lines' indices into texts,
+    their feet (LINE_FOOT_DTYPE) and their rows of (w + 31) // 32 words over the foot boxes, back to back."""
+    width: int
+    height: int
+    lines: np.ndarray
+    feet: np.ndarray
+    bits: np.ndarray
+
+
+class TextTracker:
+    """Persistent text track ids over successive results (host only).  Feed it the results of consecutive calls or stream
+    submissions in time (ticket) order, each made with WANT_FRAME_LINES | WANT_LINE_LINKS: update() overlaps the last frame's
+    footprints of the previous result with the first frame's of the new one (ERFilter.link_feet on `linker`, at its
+    set_line_link threshold) and returns one id per line of the result.  A track that continues keeps its id; two tracks that a
+    later result joins keep the smaller id: resolve() maps ids handed out earlier to their current ones."""
+
+    def __init__(self, linker: "ERFilter"):
+        self.linker = linker
+        self._parent = []            # union-find over the ids handed out; the root is the smallest
+        self._prev = None            # (EdgeFeet of the last frame, id of each of its lines)
+
+    def _find(self, i: int) -> int:
+        while self._parent[i] != i:
+            self._parent[i] = self._parent[self._parent[i]]
+            i = self._parent[i]
+        return i
+
+    def _join(self, i: int, j: int) -> None:
+        i, j = self._find(i), self._find(j)
+        if i != j:
+            self._parent[max(i, j)] = min(i, j)
+
+    def reset(self) -> None:
+        """Forget the previous result (a cut the caller knows of); the ids handed out stay valid."""
+        self._prev = None
+
+    def resolve(self, ids) -> np.ndarray:
+        return np.array([self._find(int(i)) for i in np.asarray(ids).reshape(-1)], np.int64)
+
+    def update(self, res: "Result") -> np.ndarray:
+        lt = res.line_tracks
+        first, last = res.edge_feet(0), res.edge_feet(1)
+        base = len(self._parent)
+        self._parent.extend(range(base, base + len(res.text_tracks)))      # a new id per track of the result, joined with older ones below
+        if self._prev is not None:
+            pe, pid = self._prev
+            if (pe.width, pe.height) == (first.width, first.height) and len(pe.lines) and len(first.lines):
+                for k in self.linker.link_feet(first.width, first.height, pe.feet, pe.bits, first.feet, first.bits):
+                    if k["link"]:
+                        self._join(int(pid[k["a"]]), base + int(lt[first.lines[k["b"]]]))
+        ids = self.resolve(base + lt.astype(np.int64)) if len(lt) else np.zeros(0, np.int64)
+        self._prev = (last, ids[last.lines] if len(last.lines) else np.zeros(0, np.int64))
+        return ids
 
 
 def line_crop_geometry(boxes_xywh: np.ndarray, slope: float, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> np.ndarray:

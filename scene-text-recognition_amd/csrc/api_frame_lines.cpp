@@ -3,6 +3,10 @@
 // The contract is at str_er_line_foot (str_er.h).  The host lists the members of every line with their pre-image boxes, cuts the
 // footprints into jobs and lists the lines of every frame; k_line_foot and k_foot_pairs (er_frame_lines.inl) do the per-pixel work;
 // the host sorts the pairs that come back and joins the duplicates (union-find).
+// STR_ER_WANT_LINE_LINKS (the contract is at str_er_line_link) rides on the same stage: k_foot_links overlaps the lines of adjacent
+// frames behind k_line_foot, beside k_foot_pairs, and shares the stage's upload and wait; the words of the first and of the last
+// frame's footprints come back as the result's edge feet; str_er_link_feet runs the same kernel on two uploaded sets of footprints;
+// str_er_text_tracks_from_links joins duplicates and links into tracks on the host.
 #include "str_er_ctx.h"
 
 #include <numeric>
@@ -27,12 +31,17 @@ struct FootTables {
     std::vector<TextMapCand> members;
     SampleTabs               st;
     uint64_t                 words = 0;
+    // with links: per line the lines of the next adjacent frame (into list), and the words [lo, hi) that hold the footprints of the
+    // lines of the first ([0]) and of the last frame ([1])
+    std::vector<FootRange>   range;
+    uint64_t                 edge_lo[2] = {0, 0}, edge_hi[2] = {0, 0};
 };
 
 constexpr uint32_t FOOT_JOB_WORDS = 1024;        // 64-bit words of a job of k_line_foot: 16 per lane
 
 // members: ordered by line; frame_of[t]: the frame of line t, frame_wh its level-0 size
-void foot_layout(const std::vector<int32_t> &frame_wh, const std::vector<uint32_t> &frame_of, const std::vector<FootMember> &mem, FootTables &T)
+void foot_layout(const std::vector<int32_t> &frame_wh, const std::vector<uint32_t> &frame_of, const std::vector<FootMember> &mem, FootTables &T,
+                 bool links = false)
 {
     const size_t n_lines = frame_of.size(), n_frames = frame_wh.size() / 2;
     T.lines.assign(n_lines, FootLine{});
@@ -77,6 +86,24 @@ void foot_layout(const std::vector<int32_t> &frame_wh, const std::vector<uint32_
     }
     if (T.st.tabs.empty()) T.st.tabs.push_back(0);
     if (T.list.empty()) T.list.push_back(0);
+    if (!links) return;
+    T.range.assign(n_lines, FootRange{0, 0});
+    const uint32_t edge[2] = {0, (uint32_t)n_frames - 1};
+    bool seen[2] = {false, false};
+    for (size_t t = 0; t < n_lines; ++t) {
+        const FootLine &L = T.lines[t];
+        if (L.count == 0) continue;
+        const uint32_t f = frame_of[t];
+        if (f + 1 < n_frames && frame_wh[2 * f] == frame_wh[2 * f + 2] && frame_wh[2 * f + 1] == frame_wh[2 * f + 3])
+            T.range[t] = FootRange{per_frame[f + 1], per_frame[f + 2]};
+        for (int e = 0; e < 2; ++e) {
+            if (f != edge[e]) continue;
+            const uint64_t lo = L.word_off, hi = L.word_off + (uint64_t)L.h * L.pitch;
+            T.edge_lo[e] = seen[e] ? std::min(T.edge_lo[e], lo) : lo;
+            T.edge_hi[e] = seen[e] ? std::max(T.edge_hi[e], hi) : hi;
+            seen[e] = true;
+        }
+    }
 }
 
 struct FootOut {
@@ -86,8 +113,43 @@ struct FootOut {
     size_t   bytes_back = 0;
 };
 
-// one upload, the two launches on s, one copy back, one wait (the pair pass again, with a larger table, if the pairs outgrew it)
-int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t *d_bits, bool in_batch, FootOut &O)
+// what the link pass leaves: the overlaps across adjacent frames and the words of the edge frames' footprints (T.edge_lo .. edge_hi)
+struct LinkOut {
+    std::vector<FootPair> links;         // inter > 0, sorted by (a, b)
+    std::vector<uint64_t> edge[2];
+    uint32_t n_candidates = 0;
+    size_t   bytes_back = 0, edge_bytes = 0;
+};
+
+void sort_pairs(std::vector<FootPair> &v)
+{
+    std::sort(v.begin(), v.end(), [](const FootPair &p, const FootPair &q) { return p.a != q.a ? p.a < q.a : p.b < q.b; });
+}
+
+int grow_foot_bits(str_er_ctx *c, uint64_t words)
+{
+    if (words <= c->foot_bits_words) return STR_ER_OK;
+    const size_t get = std::max<size_t>((size_t)words, 2 * c->foot_bits_words);
+    if (c->d_foot_bits) { (void)hipFree(c->d_foot_bits); c->d_foot_bits = nullptr; }
+    c->foot_bits_words = 0;
+    if (hipMalloc(reinterpret_cast<void **>(&c->d_foot_bits), 8 * get) != hipSuccess)
+        return fail(c, STR_ER_ENOMEM, "hipMalloc (line footprints, " + std::to_string(8 * get) + " bytes)");
+    c->foot_bits_words = get;
+    return STR_ER_OK;
+}
+
+// the link table of a launch over n_lines lines, behind the head and `tail` more bytes of the page-locked side: at least
+// max(1024, 4 n_lines) records, and as many as the buffer already holds
+int link_table(str_er_ctx *c, size_t n_lines, size_t tail, size_t &cap)
+{
+    cap = std::max<size_t>(1024, 4 * n_lines);
+    if (c->link_out_bytes > sizeof(FootHead) + tail) cap = std::max(cap, (c->link_out_bytes - sizeof(FootHead) - tail) / sizeof(FootPair));
+    return grow_pair(c, c->d_link_out, c->h_link_out, c->link_out_bytes, sizeof(FootHead) + sizeof(FootPair) * cap + tail, "line link output");
+}
+
+// one upload, the launches on s, one copy back, one wait (a pair pass again, with a larger table, if its pairs outgrew it).
+// LK: the links across adjacent frames as well (T.range), in the same upload and wait, with a table and a copy of their own
+int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t *d_bits, bool in_batch, FootOut &O, LinkOut *LK = nullptr)
 {
     const size_t n_lines = T.lines.size();
     O.stat.assign(n_lines, FootStat{});
@@ -95,17 +157,11 @@ int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t
     if (T.members.empty()) return STR_ER_OK;
     const size_t o_jobs = align_up(sizeof(FootLine) * n_lines, 256), o_list = align_up(o_jobs + sizeof(FootJob) * T.jobs.size(), 256);
     const size_t o_mem = align_up(o_list + 4 * T.list.size(), 256), o_tab = align_up(o_mem + sizeof(TextMapCand) * T.members.size(), 256);
-    const size_t tab_need = o_tab + 2 * T.st.tabs.size();
+    const size_t o_rng = LK ? align_up(o_tab + 2 * T.st.tabs.size(), 256) : 0;
+    const size_t tab_need = LK ? o_rng + sizeof(FootRange) * n_lines : o_tab + 2 * T.st.tabs.size();
     int rc = grow_pair(c, c->d_foot_tab, c->h_foot_tab, c->foot_tab_bytes, tab_need, "frame line tables");
     if (rc != STR_ER_OK) return rc;
-    if (T.words > c->foot_bits_words) {
-        const size_t get = std::max<size_t>((size_t)T.words, 2 * c->foot_bits_words);
-        if (c->d_foot_bits) { (void)hipFree(c->d_foot_bits); c->d_foot_bits = nullptr; }
-        c->foot_bits_words = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_foot_bits), 8 * get) != hipSuccess)
-            return fail(c, STR_ER_ENOMEM, "hipMalloc (line footprints, " + std::to_string(8 * get) + " bytes)");
-        c->foot_bits_words = get;
-    }
+    if ((rc = grow_foot_bits(c, T.words)) != STR_ER_OK) return rc;
     const size_t o_stat = sizeof(FootHead), o_pairs = o_stat + sizeof(FootStat) * n_lines;
     size_t cap = std::max<size_t>(1024, 4 * n_lines);
     if (c->foot_out_bytes > o_pairs) cap = std::max(cap, (c->foot_out_bytes - o_pairs) / sizeof(FootPair));
@@ -115,41 +171,92 @@ int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t
     std::memcpy(c->h_foot_tab + o_list, T.list.data(), 4 * T.list.size());
     std::memcpy(c->h_foot_tab + o_mem, T.members.data(), sizeof(TextMapCand) * T.members.size());
     std::memcpy(c->h_foot_tab + o_tab, T.st.tabs.data(), 2 * T.st.tabs.size());
+    // the links: the edge frames' words (one range when the call is one frame) lie behind the link table on the page-locked side
+    const bool   one_edge = LK && T.edge_lo[0] == T.edge_lo[1] && T.edge_hi[0] == T.edge_hi[1];
+    const size_t edge_n[2] = {LK ? (size_t)(T.edge_hi[0] - T.edge_lo[0]) : 0, LK && !one_edge ? (size_t)(T.edge_hi[1] - T.edge_lo[1]) : 0};
+    size_t lcap = 0;
+    if (LK) {
+        LK->edge_bytes = 8 * (edge_n[0] + edge_n[1]);
+        if ((rc = link_table(c, n_lines, LK->edge_bytes, lcap)) != STR_ER_OK) return rc;
+        std::memcpy(c->h_foot_tab + o_rng, T.range.data(), sizeof(FootRange) * n_lines);
+    }
     HIP_TRY(c, hipMemcpyAsync(c->d_foot_tab, c->h_foot_tab, tab_need, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemsetAsync(c->d_foot_out, 0, o_pairs, s));
+    if (LK) HIP_TRY(c, hipMemsetAsync(c->d_link_out, 0, sizeof(FootHead), s));
     const FootLine *d_lines = reinterpret_cast<const FootLine *>(c->d_foot_tab);
     const uint32_t *d_list = reinterpret_cast<const uint32_t *>(c->d_foot_tab + o_list);
     launch_line_foot(s, reinterpret_cast<const FootJob *>(c->d_foot_tab + o_jobs), (int)T.jobs.size(), d_lines,
                      reinterpret_cast<const TextMapCand *>(c->d_foot_tab + o_mem), reinterpret_cast<const uint16_t *>(c->d_foot_tab + o_tab), d_bits,
                      c->d_foot_bits, reinterpret_cast<FootStat *>(c->d_foot_out + o_stat));
     HIP_TRY(c, hipGetLastError());
-    for (int pass = 0;; ++pass) {
-        launch_foot_pairs(s, d_lines, (int)n_lines, d_list, c->d_foot_bits, reinterpret_cast<FootHead *>(c->d_foot_out),
-                          reinterpret_cast<FootPair *>(c->d_foot_out + o_pairs), (uint32_t)cap);
+    if (LK) {
+        uint8_t *h_edge = c->h_link_out + sizeof(FootHead) + sizeof(FootPair) * lcap;
+        for (int e = 0; e < 2; ++e) {
+            if (edge_n[e]) HIP_TRY(c, hipMemcpyAsync(h_edge, c->d_foot_bits + T.edge_lo[e], 8 * edge_n[e], hipMemcpyDeviceToHost, s));
+            h_edge += 8 * edge_n[e];
+        }
+    }
+    bool run_pairs = true, run_links = LK != nullptr;
+    for (int pass = 0; run_pairs || run_links; ++pass) {
+        if (run_pairs) launch_foot_pairs(s, d_lines, (int)n_lines, d_list, c->d_foot_bits, reinterpret_cast<FootHead *>(c->d_foot_out),
+                                         reinterpret_cast<FootPair *>(c->d_foot_out + o_pairs), (uint32_t)cap);
+        if (run_links) launch_foot_links(s, d_lines, (int)n_lines, reinterpret_cast<const FootRange *>(c->d_foot_tab + o_rng), d_list, c->d_foot_bits,
+                                         reinterpret_cast<FootHead *>(c->d_link_out), reinterpret_cast<FootPair *>(c->d_link_out + sizeof(FootHead)),
+                                         (uint32_t)lcap);
         HIP_TRY(c, hipGetLastError());
         if (in_batch && pass == 0) rec(c, "frame_lines");          // (the call's one profiling event of the stage)
         // what comes back: the counters, the statistics and the pairs in one copy (the table is sized for four pairs a line: all of it is a
-        // few hundred KB at most for a batch; the host reads as many as the counter says)
-        const size_t back = o_pairs + sizeof(FootPair) * cap;
-        HIP_TRY(c, hipMemcpyAsync(c->h_foot_out, c->d_foot_out, back, hipMemcpyDeviceToHost, s));
+        // few hundred KB at most for a batch; the host reads as many as the counter says); the links' counters and table in another
+        const size_t back = o_pairs + sizeof(FootPair) * cap, lback = sizeof(FootHead) + sizeof(FootPair) * lcap;
+        if (run_pairs) HIP_TRY(c, hipMemcpyAsync(c->h_foot_out, c->d_foot_out, back, hipMemcpyDeviceToHost, s));
+        if (run_links) HIP_TRY(c, hipMemcpyAsync(c->h_link_out, c->d_link_out, lback, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, wait_stream(c, s));
-        O.bytes_back += back;
-        FootHead head;
-        std::memcpy(&head, c->h_foot_out, sizeof head);
         if (pass == 0) std::memcpy(O.stat.data(), c->h_foot_out + o_stat, sizeof(FootStat) * n_lines);
-        O.n_candidates = head.n_candidates;
-        if (head.n_pairs <= cap) {
-            O.pairs.resize(head.n_pairs);
-            if (head.n_pairs) std::memcpy(O.pairs.data(), c->h_foot_out + o_pairs, sizeof(FootPair) * head.n_pairs);
-            break;
+        if (pass == 0 && LK) {         // (before the link table may grow: the edge words lie in the same buffer)
+            const uint8_t *h_edge = c->h_link_out + lback;
+            LK->edge[0].resize(edge_n[0]);
+            if (edge_n[0]) std::memcpy(LK->edge[0].data(), h_edge, 8 * edge_n[0]);
+            LK->edge[1].resize(edge_n[1]);
+            if (edge_n[1]) std::memcpy(LK->edge[1].data(), h_edge + 8 * edge_n[0], 8 * edge_n[1]);
+            if (one_edge) LK->edge[1] = LK->edge[0];
         }
-        if (pass > 0) return fail(c, STR_ER_EHIP, "frame lines: the pair table overflowed twice (internal error)");
-        // more pairs than the table holds: a table for all of them, and the pair pass once more (the footprints are still on the device)
-        cap = head.n_pairs;
-        if ((rc = grow_pair(c, c->d_foot_out, c->h_foot_out, c->foot_out_bytes, o_pairs + sizeof(FootPair) * cap, "frame line output")) != STR_ER_OK) return rc;
-        HIP_TRY(c, hipMemsetAsync(c->d_foot_out, 0, o_pairs, s));
+        if (run_pairs) {
+            O.bytes_back += back;
+            FootHead head;
+            std::memcpy(&head, c->h_foot_out, sizeof head);
+            O.n_candidates = head.n_candidates;
+            if (head.n_pairs <= cap) {
+                O.pairs.resize(head.n_pairs);
+                if (head.n_pairs) std::memcpy(O.pairs.data(), c->h_foot_out + o_pairs, sizeof(FootPair) * head.n_pairs);
+                run_pairs = false;
+            } else {
+                if (pass > 0) return fail(c, STR_ER_EHIP, "frame lines: the pair table overflowed twice (internal error)");
+                // more pairs than the table holds: a table for all of them, and the pair pass once more (the footprints are still on the device)
+                cap = head.n_pairs;
+                if ((rc = grow_pair(c, c->d_foot_out, c->h_foot_out, c->foot_out_bytes, o_pairs + sizeof(FootPair) * cap, "frame line output")) != STR_ER_OK) return rc;
+                HIP_TRY(c, hipMemsetAsync(c->d_foot_out, 0, o_pairs, s));
+            }
+        }
+        if (run_links) {
+            LK->bytes_back += lback;
+            FootHead head;
+            std::memcpy(&head, c->h_link_out, sizeof head);
+            LK->n_candidates = head.n_candidates;
+            if (head.n_pairs <= lcap) {
+                LK->links.resize(head.n_pairs);
+                if (head.n_pairs) std::memcpy(LK->links.data(), c->h_link_out + sizeof(FootHead), sizeof(FootPair) * head.n_pairs);
+                run_links = false;
+            } else {
+                if (pass > 0) return fail(c, STR_ER_EHIP, "line links: the link table overflowed twice (internal error)");
+                lcap = head.n_pairs;        // (the same rule: a table for all of them, and the link pass once more)
+                if ((rc = grow_pair(c, c->d_link_out, c->h_link_out, c->link_out_bytes, sizeof(FootHead) + sizeof(FootPair) * lcap, "line link output")) != STR_ER_OK)
+                    return rc;
+                HIP_TRY(c, hipMemsetAsync(c->d_link_out, 0, sizeof(FootHead), s));
+            }
+        }
     }
-    std::sort(O.pairs.begin(), O.pairs.end(), [](const FootPair &p, const FootPair &q) { return p.a != q.a ? p.a < q.a : p.b < q.b; });
+    sort_pairs(O.pairs);
+    if (LK) sort_pairs(LK->links);
     return STR_ER_OK;
 }
 
@@ -174,11 +281,28 @@ int find_root(std::vector<int32_t> &parent, int32_t t)
 }
 
 static_assert(sizeof(FootPair) == sizeof(str_er_line_pair), "the device writes str_er_line_pair records");
+static_assert(sizeof(FootPair) == sizeof(str_er_line_link), "the device writes str_er_line_link records");
+
+// a footprint as it lies on the device (rows of L.pitch 64-bit words over L's box, the first at `words`), cut to the foot box F and
+// appended to out as rows of (F.w + 31) / 32 32-bit words
+void foot_rows32(const uint64_t *words, const FootLine &L, const str_er_line_foot &F, std::vector<uint32_t> &out)
+{
+    const uint32_t pitch32 = ((uint32_t)F.w + 31u) / 32u;
+    for (int32_t rr = 0; rr < F.h; ++rr) {
+        const uint64_t *row = words + (uint64_t)(F.y - L.y + rr) * L.pitch;
+        for (uint32_t k = 0; k < pitch32; ++k) {
+            const uint32_t off = (uint32_t)(F.x - L.x) + 32u * k, q = off >> 6, sh = off & 63u;
+            uint64_t v = q < L.pitch ? row[q] >> sh : 0ull;
+            if (sh && q + 1 < L.pitch) v |= row[q + 1] << (64u - sh);
+            out.push_back((uint32_t)v);
+        }
+    }
+}
 
 } // namespace
 
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
-                      str_er_result *r)
+                      str_er_result *r, bool links)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n_frames = b.frame_wh.size() / 2, n_lines = r->texts.size();
@@ -236,10 +360,11 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
             mem[i].word_off = off_of[(size_t)(std::lower_bound(uniq.begin(), uniq.end(), who[i]) - uniq.begin())];
     }
     FootTables T;
-    foot_layout(b.frame_wh, frame_of, mem, T);
+    foot_layout(b.frame_wh, frame_of, mem, T, links);
     const double ms_layout = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     FootOut O;
-    const int rc = foot_stage(c, s, T, d_bits, true, O);
+    LinkOut LK;
+    const int rc = foot_stage(c, s, T, d_bits, true, O, links ? &LK : nullptr);
     if (rc != STR_ER_OK) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     feet_from_stats(O.stat, r->line_feet);
@@ -254,6 +379,37 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
     if (rcf != STR_ER_OK) return fail(c, STR_ER_EHIP, "frame lines: the device's pairs do not fit its footprints (internal error)");
     r->frame_lines.resize((size_t)n_fl);
     r->have_frame_lines = true;
+    if (links) {
+        r->line_links.resize(LK.links.size());
+        if (!LK.links.empty()) std::memcpy(r->line_links.data(), LK.links.data(), sizeof(FootPair) * LK.links.size());
+        r->line_tracks.resize(n_lines);
+        r->text_tracks.resize(n_lines);
+        r->text_track_members.resize(n_lines);
+        int32_t n_tr = 0;
+        const int rct = str_er_text_tracks_from_links(r->line_feet.data(), frame_of.data(), (int32_t)n_lines, r->line_pairs.data(), (int32_t)r->line_pairs.size(),
+                                                      r->line_links.data(), (int32_t)r->line_links.size(), c->link_num, c->link_den, r->line_tracks.data(),
+                                                      r->text_tracks.data(), (int32_t)n_lines, &n_tr, r->text_track_members.data());
+        if (rct != STR_ER_OK) return fail(c, STR_ER_EHIP, "line links: the device's links do not fit its footprints (internal error)");
+        r->text_tracks.resize((size_t)n_tr);
+        // the edge feet: the lines of the first and of the last frame, their feet and their footprints cut to the foot boxes
+        for (int e = 0; e < 2; ++e) {
+            str_er_result::EdgeFeet &E = r->edge_feet[e];
+            const uint32_t f = e == 0 ? 0u : (uint32_t)n_frames - 1u;
+            E = str_er_result::EdgeFeet{};
+            if (n_frames == 0) continue;
+            E.w = b.frame_wh[2 * f]; E.h = b.frame_wh[2 * f + 1];
+            for (size_t t = 0; t < n_lines; ++t) {
+                if (frame_of[t] != f) continue;
+                E.lines.push_back((int32_t)t);
+                E.feet.push_back(r->line_feet[t]);
+                if (r->line_feet[t].pixels) foot_rows32(LK.edge[e].data() + (T.lines[t].word_off - T.edge_lo[e]), T.lines[t], r->line_feet[t], E.bits);
+            }
+        }
+        r->have_line_links = true;
+        if (c->dbg_stats)        // developer aid (tools/dev_line_links.py)
+            std::fprintf(stderr, "[str_er] line links: %u candidate pairs, %zu overlaps, %d tracks, %zu bytes back for the link table, %zu bytes back for the edge feet\n",
+                         LK.n_candidates, LK.links.size(), n_tr, LK.bytes_back, LK.edge_bytes);
+    }
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
                              "%zu bytes back, host %.3f ms before + %.3f ms after the device\n",
@@ -395,24 +551,213 @@ try {
         // the footprints back as they lie on the device (64-bit words over the union of the pre-image boxes), cut to the foot boxes
         std::vector<uint64_t> dev((size_t)T.words);
         HIP_TRY(c, hipMemcpy(dev.data(), c->d_foot_bits, 8 * (size_t)T.words, hipMemcpyDeviceToHost));
-        uint32_t *out = bits;
-        for (int32_t t = 0; t < n_lines; ++t) {
-            const str_er_line_foot &F = ft[(size_t)t];
-            const FootLine &L = T.lines[(size_t)t];
-            const uint32_t pitch32 = ((uint32_t)F.w + 31u) / 32u;
-            for (int32_t rr = 0; rr < F.h; ++rr) {
-                const uint64_t *row = dev.data() + L.word_off + (uint64_t)(F.y - L.y + rr) * L.pitch;
-                for (uint32_t k = 0; k < pitch32; ++k) {
-                    const uint32_t off = (uint32_t)(F.x - L.x) + 32u * k, q = off >> 6, sh = off & 63u;
-                    uint64_t v = q < L.pitch ? row[q] >> sh : 0ull;
-                    if (sh && q + 1 < L.pitch) v |= row[q + 1] << (64u - sh);
-                    *out++ = (uint32_t)v;
-                }
-            }
-        }
+        std::vector<uint32_t> cut;
+        cut.reserve((size_t)out_words);
+        for (int32_t t = 0; t < n_lines; ++t) foot_rows32(dev.data() + T.lines[(size_t)t].word_off, T.lines[(size_t)t], ft[(size_t)t], cut);
+        std::memcpy(bits, cut.data(), 4 * cut.size());
     }
     return STR_ER_OK;
 } ABI_GUARD(c)
+
+int str_er_set_line_link(str_er_ctx *c, int32_t num, int32_t den)
+{
+    if (!c) return STR_ER_EINVAL;
+    if (num < 1 || num > den || den > 65535) return fail(c, STR_ER_EINVAL, "str_er_set_line_link: 1 <= num <= den <= 65535");
+    c->link_num = num; c->link_den = den;
+    return STR_ER_OK;
+}
+
+int str_er_text_tracks_from_links(const str_er_line_foot *feet, const uint32_t *frames_of_lines, int32_t n_lines, const str_er_line_pair *pairs,
+                                  int32_t n_pairs, str_er_line_link *links, int32_t n_links, int32_t num, int32_t den, int32_t *line_tracks,
+                                  str_er_text_track *tracks, int32_t cap_tracks, int32_t *n_tracks, int32_t *members)
+try {
+    if (n_lines < 0 || n_pairs < 0 || n_links < 0 || !n_tracks || num < 1 || num > den || den > 65535) return STR_ER_EINVAL;
+    if (n_lines > 0 && (!feet || !frames_of_lines || !line_tracks)) return STR_ER_EINVAL;
+    if ((n_pairs > 0 && !pairs) || (n_links > 0 && !links) || (tracks && n_lines > 0 && !members) || (tracks && cap_tracks < 0)) return STR_ER_EINVAL;
+    for (int32_t k = 0; k < n_pairs; ++k) {
+        const str_er_line_pair &P = pairs[k];
+        if (P.a < 0 || P.a >= P.b || P.b >= n_lines || frames_of_lines[P.a] != frames_of_lines[P.b]) return STR_ER_EINVAL;
+        if (P.inter == 0 || P.inter > feet[P.a].pixels || P.inter > feet[P.b].pixels) return STR_ER_EINVAL;
+    }
+    for (int32_t k = 0; k < n_links; ++k) {
+        const str_er_line_link &P = links[k];
+        if (P.a < 0 || P.a >= n_lines || P.b < 0 || P.b >= n_lines) return STR_ER_EINVAL;
+        if ((uint64_t)frames_of_lines[P.b] != (uint64_t)frames_of_lines[P.a] + 1u) return STR_ER_EINVAL;
+        if (P.inter == 0 || P.inter > feet[P.a].pixels || P.inter > feet[P.b].pixels) return STR_ER_EINVAL;
+    }
+    // duplicates and links joined: the root of a component is its smallest line
+    std::vector<int32_t> parent((size_t)n_lines);
+    std::iota(parent.begin(), parent.end(), 0);
+    auto join = [&](int32_t a, int32_t b) {
+        const int32_t ra = find_root(parent, a), rb = find_root(parent, b);
+        if (ra != rb) parent[(size_t)std::max(ra, rb)] = std::min(ra, rb);
+    };
+    for (int32_t k = 0; k < n_pairs; ++k)
+        if (pairs[k].dup) join(pairs[k].a, pairs[k].b);
+    for (int32_t k = 0; k < n_links; ++k) {
+        str_er_line_link &P = links[k];
+        const uint64_t uni = (uint64_t)feet[P.a].pixels + (uint64_t)feet[P.b].pixels - (uint64_t)P.inter;
+        P.link = (uint64_t)P.inter * (uint64_t)den >= (uint64_t)num * uni ? 1u : 0u;
+        if (P.link) join(P.a, P.b);
+    }
+    // the tracks: by first frame, then by smallest member
+    std::vector<uint32_t> f0((size_t)n_lines, UINT32_MAX), f1((size_t)n_lines, 0);
+    for (int32_t t = 0; t < n_lines; ++t) {
+        const size_t q = (size_t)find_root(parent, t);
+        f0[q] = std::min(f0[q], frames_of_lines[t]); f1[q] = std::max(f1[q], frames_of_lines[t]);
+    }
+    std::vector<int32_t> roots;
+    for (int32_t t = 0; t < n_lines; ++t)
+        if (find_root(parent, t) == t) roots.push_back(t);
+    std::sort(roots.begin(), roots.end(), [&](int32_t p, int32_t q) { return f0[(size_t)p] != f0[(size_t)q] ? f0[(size_t)p] < f0[(size_t)q] : p < q; });
+    std::vector<int32_t> index_of((size_t)n_lines, -1);
+    for (size_t i = 0; i < roots.size(); ++i) index_of[(size_t)roots[i]] = (int32_t)i;
+    for (int32_t t = 0; t < n_lines; ++t) line_tracks[t] = index_of[(size_t)find_root(parent, t)];
+    *n_tracks = (int32_t)roots.size();
+    if (!tracks) return STR_ER_OK;
+    if ((int32_t)roots.size() > cap_tracks) return STR_ER_ECAPACITY;
+    for (size_t i = 0; i < roots.size(); ++i) {
+        str_er_text_track &G = tracks[i];
+        G = str_er_text_track{};
+        G.first_frame = f0[(size_t)roots[i]]; G.last_frame = f1[(size_t)roots[i]]; G.rep = -1;
+    }
+    for (int32_t t = 0; t < n_lines; ++t) ++tracks[line_tracks[t]].count;
+    int32_t at = 0;
+    for (size_t i = 0; i < roots.size(); ++i) { tracks[i].first = at; at += tracks[i].count; tracks[i].count = 0; }
+    for (int32_t t = 0; t < n_lines; ++t) {          // (ascending t: the members ascend, and a tie of pixels stays with the smaller line)
+        str_er_text_track &G = tracks[line_tracks[t]];
+        members[G.first + G.count++] = t;
+        if (G.rep < 0 || feet[t].pixels > G.pixels) { G.rep = t; G.pixels = feet[t].pixels; }
+    }
+    return STR_ER_OK;
+} catch (...) { return STR_ER_ENOMEM; }
+
+int str_er_link_feet(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet_a, const uint32_t *bits_a, int32_t n_a,
+                     const str_er_line_foot *feet_b, const uint32_t *bits_b, int32_t n_b, str_er_line_link *pairs, int32_t cap_pairs, int32_t *n_pairs)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (W < 1 || H < 1 || W > 65535 || H > 65535 || n_a < 0 || n_b < 0 || !n_pairs || (n_a > 0 && !feet_a) || (n_b > 0 && !feet_b) || (pairs && cap_pairs < 0))
+        return fail(c, STR_ER_EINVAL, "bad arguments");
+    // the two sets as one table of lines, a's first, their footprints as rows of 64-bit words; every footprint checked against its foot
+    const size_t n_lines = (size_t)n_a + (size_t)n_b;
+    std::vector<FootLine> lines(n_lines, FootLine{});
+    std::vector<uint64_t> words;
+    for (size_t t = 0; t < n_lines; ++t) {
+        const bool in_a = t < (size_t)n_a;
+        const str_er_line_foot &F = in_a ? feet_a[t] : feet_b[t - (size_t)n_a];
+        const std::string who = std::string("set ") + (in_a ? "a" : "b") + ", line " + std::to_string(in_a ? t : t - (size_t)n_a);
+        if (F.w < 0 || F.h < 0 || (F.w == 0) != (F.h == 0)) return fail(c, STR_ER_EINVAL, who + ": bad foot box");
+        FootLine &L = lines[t];
+        L.word_off = words.size();
+        if (F.w == 0) {
+            if (F.pixels) return fail(c, STR_ER_EINVAL, who + ": pixels in an empty foot box");
+            continue;
+        }
+        if (F.x < 0 || F.y < 0 || (int64_t)F.x + F.w > W || (int64_t)F.y + F.h > H) return fail(c, STR_ER_EINVAL, who + ": the foot box leaves the frame");
+    }
+    const uint32_t *src[2] = {bits_a, bits_b};
+    for (size_t t = 0; t < n_lines; ++t) {
+        const bool in_a = t < (size_t)n_a;
+        const str_er_line_foot &F = in_a ? feet_a[t] : feet_b[t - (size_t)n_a];
+        if (F.w == 0) continue;
+        const uint32_t *&at = src[in_a ? 0 : 1];
+        if (!at) return fail(c, STR_ER_EINVAL, "footprint bits missing");
+        FootLine &L = lines[t];
+        L.x = F.x; L.y = F.y; L.w = F.w; L.h = F.h; L.pitch = ((uint32_t)F.w + 63u) / 64u; L.count = 1;
+        L.word_off = words.size();
+        const uint32_t pitch32 = ((uint32_t)F.w + 31u) / 32u, tail = (uint32_t)F.w & 31u;
+        uint64_t px = 0;
+        for (int32_t rr = 0; rr < F.h; ++rr, at += pitch32) {
+            if (tail && (at[pitch32 - 1] >> tail)) return fail(c, STR_ER_EINVAL, "a footprint has a bit set past its row's width");
+            for (uint32_t k = 0; k < L.pitch; ++k) {
+                const uint64_t v = (uint64_t)at[2 * k] | (2 * k + 1 < pitch32 ? (uint64_t)at[2 * k + 1] << 32 : 0ull);
+                px += (uint64_t)__builtin_popcountll(v);
+                words.push_back(v);
+            }
+        }
+        if (px != F.pixels) return fail(c, STR_ER_EINVAL, "a foot's pixels are not the number of bits set in its footprint");
+    }
+    *n_pairs = 0;
+    if (n_a == 0 || n_b == 0 || words.empty()) return STR_ER_OK;
+    HIP_TRY(c, hipSetDevice(c->prm.device));
+    std::vector<FootRange> range(n_lines, FootRange{0, 0});
+    std::vector<uint32_t>  list((size_t)n_b);
+    for (int32_t i = 0; i < n_a; ++i) range[(size_t)i] = FootRange{0, (uint32_t)n_b};
+    std::iota(list.begin(), list.end(), (uint32_t)n_a);
+    const size_t o_list = align_up(sizeof(FootLine) * n_lines, 256), o_rng = align_up(o_list + 4 * list.size(), 256), tab_need = o_rng + sizeof(FootRange) * n_lines;
+    int rc = grow_pair(c, c->d_foot_tab, c->h_foot_tab, c->foot_tab_bytes, tab_need, "frame line tables");
+    if (rc != STR_ER_OK) return rc;
+    if ((rc = grow_foot_bits(c, words.size())) != STR_ER_OK) return rc;
+    size_t cap = 0;
+    if ((rc = link_table(c, n_lines, 0, cap)) != STR_ER_OK) return rc;
+    hipStream_t s = c->stream;
+    std::memcpy(c->h_foot_tab, lines.data(), sizeof(FootLine) * n_lines);
+    std::memcpy(c->h_foot_tab + o_list, list.data(), 4 * list.size());
+    std::memcpy(c->h_foot_tab + o_rng, range.data(), sizeof(FootRange) * n_lines);
+    HIP_TRY(c, hipMemcpyAsync(c->d_foot_tab, c->h_foot_tab, tab_need, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->d_foot_bits, words.data(), 8 * words.size(), hipMemcpyHostToDevice, s));      // (words lives until the wait below)
+    std::vector<FootPair> got;
+    for (int pass = 0;; ++pass) {
+        HIP_TRY(c, hipMemsetAsync(c->d_link_out, 0, sizeof(FootHead), s));
+        launch_foot_links(s, reinterpret_cast<const FootLine *>(c->d_foot_tab), (int)n_lines, reinterpret_cast<const FootRange *>(c->d_foot_tab + o_rng),
+                          reinterpret_cast<const uint32_t *>(c->d_foot_tab + o_list), c->d_foot_bits, reinterpret_cast<FootHead *>(c->d_link_out),
+                          reinterpret_cast<FootPair *>(c->d_link_out + sizeof(FootHead)), (uint32_t)cap);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(c->h_link_out, c->d_link_out, sizeof(FootHead) + sizeof(FootPair) * cap, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, wait_stream(c, s));
+        FootHead head;
+        std::memcpy(&head, c->h_link_out, sizeof head);
+        if (head.n_pairs <= cap) {
+            got.resize(head.n_pairs);
+            if (head.n_pairs) std::memcpy(got.data(), c->h_link_out + sizeof(FootHead), sizeof(FootPair) * head.n_pairs);
+            break;
+        }
+        if (pass > 0) return fail(c, STR_ER_EHIP, "line links: the link table overflowed twice (internal error)");
+        cap = head.n_pairs;        // (a table for all of them, and the pass once more)
+        if ((rc = grow_pair(c, c->d_link_out, c->h_link_out, c->link_out_bytes, sizeof(FootHead) + sizeof(FootPair) * cap, "line link output")) != STR_ER_OK) return rc;
+    }
+    sort_pairs(got);
+    *n_pairs = (int32_t)got.size();
+    if (pairs && (int64_t)got.size() > (int64_t)cap_pairs)
+        return fail(c, STR_ER_ECAPACITY, std::to_string(got.size()) + " pairs, cap_pairs is " + std::to_string(cap_pairs));
+    if (!pairs) return STR_ER_OK;
+    for (size_t k = 0; k < got.size(); ++k) {
+        str_er_line_link &P = pairs[k];
+        P.a = got[k].a; P.b = got[k].b - n_a; P.inter = got[k].inter;
+        const uint64_t uni = (uint64_t)feet_a[P.a].pixels + (uint64_t)feet_b[P.b].pixels - (uint64_t)P.inter;
+        P.link = (uint64_t)P.inter * (uint64_t)c->link_den >= (uint64_t)c->link_num * uni ? 1u : 0u;
+    }
+    return STR_ER_OK;
+} ABI_GUARD(c)
+
+const str_er_line_link *str_er_result_line_links(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_links, &str_er_result::line_links, n); }
+
+const int32_t *str_er_result_line_tracks(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_links, &str_er_result::line_tracks, n); }
+
+const str_er_text_track *str_er_result_text_tracks(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_links, &str_er_result::text_tracks, n); }
+
+const int32_t *str_er_result_text_track_members(const str_er_result *r, int32_t *n)
+{
+    return result_table(r, r && r->have_line_links, &str_er_result::text_track_members, n);
+}
+
+int str_er_result_edge_feet(const str_er_result *r, int32_t which, int32_t *frame_w, int32_t *frame_h, const str_er_line_foot **feet, const int32_t **lines,
+                            int32_t *n, const uint32_t **bits, uint64_t *n_words)
+{
+    static const str_er_line_foot no_foot{};
+    static const int32_t  no_line = 0;
+    static const uint32_t no_bits = 0;
+    if (!r || !r->have_line_links || which < 0 || which > 1) return STR_ER_EINVAL;
+    const str_er_result::EdgeFeet &E = r->edge_feet[which];
+    if (frame_w) *frame_w = E.w;
+    if (frame_h) *frame_h = E.h;
+    if (feet) *feet = E.feet.empty() ? &no_foot : E.feet.data();
+    if (lines) *lines = E.lines.empty() ? &no_line : E.lines.data();
+    if (n) *n = (int32_t)E.feet.size();
+    if (bits) *bits = E.bits.empty() ? &no_bits : E.bits.data();
+    if (n_words) *n_words = E.bits.size();
+    return STR_ER_OK;
+}
 
 const str_er_line_foot *str_er_result_line_feet(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_frame_lines, &str_er_result::line_feet, n); }
 

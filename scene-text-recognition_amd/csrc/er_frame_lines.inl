@@ -14,6 +14,11 @@
 // row into the 64 bits that start at the intersection's column -- popcounts and reduces.  Pairs without a common pixel are dropped
 // here; lane 0 appends the others to the output (an atomic per surviving pair).  The order of the output is the order of arrival:
 // the host sorts it.
+//
+// k_foot_links (STR_ER_WANT_LINE_LINKS, str_er_link_feet): the same walk across frames.  A wave takes a line a and walks the lines b of
+// the next adjacent frame -- range[a] = (first, end) into the same list, empty where the next frame has another size or there is
+// none -- with the box test fused in; a and b are in the same pixel coordinates, so the AND over the intersection is that of
+// k_foot_pairs (foot_overlap).  One wave per line was kept over one wave per candidate pair: see DESIGN.md 3.15.
 
 constexpr int FOOT_THREADS = 256;           // 4 waves, a job / a line each
 
@@ -124,6 +129,50 @@ __global__ __launch_bounds__(FOOT_THREADS) void k_foot_pairs(const FootLine *__r
     }
 }
 
+// |F(a) & F(b)| over the intersection (ix0 .. ix1) x (iy0 .. iy1) of the two boxes, summed over the wave
+__device__ __forceinline__ uint32_t foot_overlap(const uint64_t *__restrict__ feet, const FootLine &A, const FootLine &B, int ix0, int ix1, int iy0, int iy1,
+                                                 int lane)
+{
+    const uint32_t nw = (uint32_t)(ix1 - ix0 + 63) >> 6, items = (uint32_t)(iy1 - iy0) * nw;
+    uint32_t inter = 0;
+    for (uint32_t it = (uint32_t)lane; it < items; it += 64) {
+        const uint32_t r = it / nw, k = it - r * nw;
+        const int      y = iy0 + (int)r;
+        const uint64_t wa = foot_window(feet + A.word_off + (uint64_t)(y - A.y) * A.pitch, A.pitch, (uint32_t)(ix0 - A.x) + 64u * k);
+        const uint64_t wb = foot_window(feet + B.word_off + (uint64_t)(y - B.y) * B.pitch, B.pitch, (uint32_t)(ix0 - B.x) + 64u * k);
+        inter += (uint32_t)__popcll(wa & wb);         // (past ix1 one of the two rows has ended: its bits are 0)
+    }
+    return foot_wave_sum(inter);
+}
+
+__global__ __launch_bounds__(FOOT_THREADS) void k_foot_links(const FootLine *__restrict__ lines, int n_lines, const FootRange *__restrict__ range,
+                                                             const uint32_t *__restrict__ list, const uint64_t *__restrict__ feet,
+                                                             FootHead *__restrict__ head, FootPair *__restrict__ out, uint32_t cap)
+{
+    const int lane = threadIdx.x & 63;
+    for (int a0 = blockIdx.x * (FOOT_THREADS / 64); a0 < n_lines; a0 += gridDim.x * (FOOT_THREADS / 64)) {
+        const int a = __builtin_amdgcn_readfirstlane(a0 + (int)(threadIdx.x >> 6));
+        if (a >= n_lines) continue;
+        const FootLine A = lines[a];
+        const FootRange R = range[a];
+        if (A.w <= 0) continue;
+        uint32_t n_cand = 0;
+        for (uint32_t i = R.first; i < R.end; ++i) {
+            const int      b = (int)list[i];
+            const FootLine B = lines[b];
+            const int ix0 = max(A.x, B.x), ix1 = min(A.x + A.w, B.x + B.w), iy0 = max(A.y, B.y), iy1 = min(A.y + A.h, B.y + B.h);
+            if (ix0 >= ix1 || iy0 >= iy1) continue;
+            ++n_cand;
+            const uint32_t inter = foot_overlap(feet, A, B, ix0, ix1, iy0, iy1, lane);
+            if (lane == 0 && inter) {
+                const uint32_t at = atomicAdd(&head->n_pairs, 1u);
+                if (at < cap) { FootPair P; P.a = a; P.b = b; P.inter = inter; P.dup = 0; out[at] = P; }
+            }
+        }
+        if (lane == 0 && n_cand) atomicAdd(&head->n_candidates, n_cand);
+    }
+}
+
 void launch_line_foot(hipStream_t s, const FootJob *jobs, int n_jobs, const FootLine *lines, const TextMapCand *members, const uint16_t *tabs,
                       const uint32_t *bits, uint64_t *feet, FootStat *stat)
 {
@@ -138,4 +187,12 @@ void launch_foot_pairs(hipStream_t s, const FootLine *lines, int n_lines, const 
     if (n_lines <= 1) return;
     const dim3 grid((unsigned)std::min((n_lines + FOOT_THREADS / 64 - 1) / (FOOT_THREADS / 64), 1 << 16));
     hipLaunchKernelGGL(k_foot_pairs, grid, dim3(FOOT_THREADS), 0, s, lines, n_lines, list, feet, head, out, cap);
+}
+
+void launch_foot_links(hipStream_t s, const FootLine *lines, int n_lines, const FootRange *range, const uint32_t *list, const uint64_t *feet, FootHead *head,
+                       FootPair *out, uint32_t cap)
+{
+    if (n_lines <= 1) return;
+    const dim3 grid((unsigned)std::min((n_lines + FOOT_THREADS / 64 - 1) / (FOOT_THREADS / 64), 1 << 16));
+    hipLaunchKernelGGL(k_foot_links, grid, dim3(FOOT_THREADS), 0, s, lines, n_lines, range, list, feet, head, out, cap);
 }

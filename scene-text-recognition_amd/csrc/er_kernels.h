@@ -156,5 +156,9 @@ void launch_line_foot(hipStream_t s, const FootJob *jobs, int n_jobs, const Foot
                       const uint32_t *bits, uint64_t *feet, FootStat *stat);
 void launch_foot_pairs(hipStream_t s, const FootLine *lines, int n_lines, const uint32_t *list, const uint64_t *feet, FootHead *head, FootPair *out,
                        uint32_t cap);
+// launch_foot_links (STR_ER_WANT_LINE_LINKS, str_er_link_feet): one wave per line a over list[range[a].first .. range[a].end), the lines
+// of the next adjacent frame; out / head as for launch_foot_pairs (a table and a head of their own)
+void launch_foot_links(hipStream_t s, const FootLine *lines, int n_lines, const FootRange *range, const uint32_t *list, const uint64_t *feet, FootHead *head,
+                       FootPair *out, uint32_t cap);
 
 } // namespace str_er

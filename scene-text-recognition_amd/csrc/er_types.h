@@ -303,5 +303,11 @@ struct FootHead {
     uint32_t pad[2];
 };
 static_assert(sizeof(FootHead) == 16, "FootHead layout (host and device)");
+// Per line, for k_foot_links: list[first .. end) are the lines of the next frame where that frame is adjacent (equal level-0 size),
+// an empty range otherwise.  A table of its own: FootLine stays as k_foot_pairs reads it.
+struct FootRange {
+    uint32_t first, end;
+};
+static_assert(sizeof(FootRange) == 8, "FootRange layout (host and device)");
 
 } // namespace str_er

@@ -95,6 +95,17 @@ struct str_er_result {
     std::vector<str_er_frame_line> frame_lines;
     std::vector<int32_t> frame_line_members;
     bool have_frame_lines = false;
+    std::vector<str_er_line_link> line_links;    // STR_ER_WANT_LINE_LINKS: the overlaps across adjacent frames, the track of every line, the tracks and their members
+    std::vector<int32_t> line_tracks;
+    std::vector<str_er_text_track> text_tracks;
+    std::vector<int32_t> text_track_members;
+    struct EdgeFeet {                            // ... and the footprints of the lines of the first ([0]) and of the last frame ([1])
+        int32_t w = 0, h = 0;
+        std::vector<str_er_line_foot> feet;
+        std::vector<int32_t> lines;
+        std::vector<uint32_t> bits;
+    } edge_feet[2];
+    bool have_line_links = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -206,6 +217,10 @@ struct str_er_ctx {
     uint8_t  *d_foot_tab = nullptr, *h_foot_tab = nullptr; size_t foot_tab_bytes = 0;
     uint8_t  *d_foot_out = nullptr, *h_foot_out = nullptr; size_t foot_out_bytes = 0;
     uint64_t *d_foot_bits = nullptr; size_t foot_bits_words = 0;
+    // STR_ER_WANT_LINE_LINKS / str_er_link_feet (str_er_set_line_link): the link output (counters | pairs | the edge frames' footprint
+    // words on the page-locked side); created by the first call that wants links, grown geometrically, never shrunk
+    int32_t  link_num = 1, link_den = 2;
+    uint8_t  *d_link_out = nullptr, *h_link_out = nullptr; size_t link_out_bytes = 0;
     uint8_t *d_strip_out = nullptr, *d_strip_in = nullptr; size_t strip_out_cap = 0, strip_in_cap = 0;   // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -465,8 +480,9 @@ struct SampleTabs {
 // ---- defined in api_frame_lines.cpp
 // STR_ER_WANT_FRAME_LINES in run_batch: the feet, pairs and frame lines of the lines of r.  d_mask_bits / word_off: mask words of this
 // call still on the device and the first word of every candidate's (UINT64_MAX: none), or null: then the members' masks are made here
+// links: STR_ER_WANT_LINE_LINKS as well (the links, tracks and edge feet of r, in the same stage)
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
-                      str_er_result *r);
+                      str_er_result *r, bool links = false);
 constexpr int MASK_MAX_WIDTH = 16384;       // widest box the mask kernels take (er_masks.inl: MASK_MAX_WPL words of 64 pixels per lane)
 // ---- defined in api_models.cpp
 int parse_cascade(str_er_ctx *c, HostCascade &hc, const char *text, size_t len);

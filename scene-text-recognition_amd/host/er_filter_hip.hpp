@@ -438,6 +438,98 @@ public:
         return out;
     }
 
+    // The text lines of consecutive frames linked into text tracks (STR_ER_WANT_LINE_LINKS; the contract is at str_er_line_link in
+    // include/str_er.h): the overlaps across adjacent frames, the track of every line of str_er_result_texts(), the tracks, the line
+    // indices their first / count index, and the footprints of the lines of the first ([0]) and of the last frame ([1]).
+    struct EdgeFeet {
+        int32_t width = 0, height = 0;               // the frame's size
+        std::vector<int32_t>          lines;         // indices into str_er_result_texts()
+        std::vector<str_er_line_foot> feet;
+        std::vector<uint32_t>         bits;          // rows of (w + 31) / 32 words over every foot box, back to back
+    };
+    struct LineLinks {
+        std::vector<str_er_line_link>  links;
+        std::vector<int32_t>           line_tracks;
+        std::vector<str_er_text_track> tracks;
+        std::vector<int32_t>           members;
+        EdgeFeet                       edge[2];
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static LineLinks line_links(const str_er_result *r)
+    {
+        LineLinks out;
+        int32_t n = 0;
+        if (const str_er_line_link *p = str_er_result_line_links(r, &n)) out.links.assign(p, p + n);
+        if (const int32_t *p = str_er_result_line_tracks(r, &n)) out.line_tracks.assign(p, p + n);
+        if (const str_er_text_track *p = str_er_result_text_tracks(r, &n)) out.tracks.assign(p, p + n);
+        if (const int32_t *p = str_er_result_text_track_members(r, &n)) out.members.assign(p, p + n);
+        for (int which = 0; which < 2; ++which) {
+            const str_er_line_foot *feet = nullptr;
+            const int32_t  *lines = nullptr;
+            const uint32_t *bits = nullptr;
+            uint64_t n_words = 0;
+            EdgeFeet &e = out.edge[which];
+            if (str_er_result_edge_feet(r, which, &e.width, &e.height, &feet, &lines, &n, &bits, &n_words) != STR_ER_OK) continue;
+            e.lines.assign(lines, lines + n); e.feet.assign(feet, feet + n); e.bits.assign(bits, bits + n_words);
+        }
+        return out;
+    }
+    // two lines of adjacent frames are linked from a Jaccard index of num / den of their footprints on (str_er_set_line_link)
+    void set_line_link(int num, int den) { check(str_er_set_line_link(ctx_.get(), num, den)); }
+    // the overlaps of every line of a with every line of b, two sets of footprints of one frame size (str_er_link_feet): a / b of a
+    // record index the two sets, link is set at the context's threshold
+    std::vector<str_er_line_link> link_feet(const EdgeFeet &a, const EdgeFeet &b) { return link_feet(ctx_.get(), a, b); }
+    static std::vector<str_er_line_link> link_feet(str_er_ctx *ctx, const EdgeFeet &a, const EdgeFeet &b)
+    {
+        if (a.width != b.width || a.height != b.height || a.feet.empty() || b.feet.empty()) return {};      // (another frame size: not adjacent)
+        int32_t n = 0;
+        const uint32_t *ba = a.bits.empty() ? nullptr : a.bits.data(), *bb = b.bits.empty() ? nullptr : b.bits.data();
+        const auto run = [&](str_er_line_link *out, int32_t cap) {
+            return str_er_link_feet(ctx, a.width, a.height, a.feet.data(), ba, (int32_t)a.feet.size(), b.feet.data(), bb, (int32_t)b.feet.size(), out, cap, &n);
+        };
+        if (run(nullptr, 0) != STR_ER_OK) throw std::runtime_error(std::string("str_er_link_feet: ") + str_er_last_error(ctx));
+        std::vector<str_er_line_link> out((size_t)n);
+        if (n && run(out.data(), n) != STR_ER_OK) throw std::runtime_error(std::string("str_er_link_feet: ") + str_er_last_error(ctx));
+        return out;
+    }
+    // Persistent track ids over the results of consecutive calls or stream submissions, fed in time order: update() links the last
+    // frame of the previous result with the first frame of this one and returns an id per line.  A track that continues keeps its
+    // id; two tracks a later result joins keep the smaller one (resolve() maps an id handed out earlier to its current one).
+    class TextTracker {
+    public:
+        // linker: the context whose str_er_link_feet (and threshold) links the two results
+        std::vector<int64_t> update(str_er_ctx *linker, const LineLinks &res)
+        {
+            const int64_t base = (int64_t)parent_.size();
+            for (size_t i = 0; i < res.tracks.size(); ++i) parent_.push_back(base + (int64_t)i);
+            if (have_prev_)
+                for (const str_er_line_link &k : link_feet(linker, prev_, res.edge[0]))
+                    if (k.link) join(prev_ids_[(size_t)k.a], base + res.line_tracks[(size_t)res.edge[0].lines[(size_t)k.b]]);
+            std::vector<int64_t> ids(res.line_tracks.size());
+            for (size_t t = 0; t < ids.size(); ++t) ids[t] = resolve(base + res.line_tracks[t]);
+            prev_ = res.edge[1];
+            prev_ids_.clear();
+            for (const int32_t t : prev_.lines) prev_ids_.push_back(ids[(size_t)t]);
+            have_prev_ = true;
+            return ids;
+        }
+        int64_t resolve(int64_t id)
+        {
+            while (parent_[(size_t)id] != id) { parent_[(size_t)id] = parent_[(size_t)parent_[(size_t)id]]; id = parent_[(size_t)id]; }
+            return id;
+        }
+        void reset() { have_prev_ = false; }
+    private:
+        void join(int64_t a, int64_t b)
+        {
+            a = resolve(a); b = resolve(b);
+            if (a != b) parent_[(size_t)std::max(a, b)] = std::min(a, b);
+        }
+        std::vector<int64_t> parent_, prev_ids_;
+        EdgeFeet prev_;
+        bool     have_prev_ = false;
+    };
+
     // vector<double> ERFilter::make_LBP_hist(Mat input, N = 2, normalize_size = 24) (src/ER.cpp:789-816)
     std::vector<double> make_LBP_hist(const Image8 &input)
     {
