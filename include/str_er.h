@@ -109,6 +109,13 @@ extern "C" {
  * str_er_strip_merge[_ex]), the context usable afterwards.  str_er_detect_bgr, _nv12, _bgr_list, _nv12_list and every
  * str_er_stream_submit* call honour it.  It changes no other output of the call.                                                  */
 #define STR_ER_WANT_LINE_LINKS (262144u)
+/* output option: the convex hull, the moments and the oriented box of every text line and of every frame line, from the footprints
+ * (str_er_result_line_geoms / _frame_line_geoms / _geom_points; the contract is at str_er_line_geom).  Needs STR_ER_WANT_FRAME_LINES
+ * (which needs STR_ER_STAGE_GROUP and frames): STR_ER_EINVAL without it, and wherever _FRAME_LINES is refused
+ * (str_er_detect_planes[_list], str_er_strip_merge[_ex]), the context usable afterwards.  str_er_detect_bgr, _nv12, _bgr_list,
+ * _nv12_list and every str_er_stream_submit* call honour it.  A foot box wider or taller than 16384 pixels gives STR_ER_ECAPACITY.
+ * It changes no other output of the call and combines with every other STR_ER_WANT_* flag.                                      */
+#define STR_ER_WANT_LINE_GEOM (524288u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -351,6 +358,37 @@ typedef struct str_er_text_track {
     int32_t  rep;            /* 16: the representative: a line index                                    */
     uint32_t pixels;         /* 20: the representative's                                                */
 } str_er_text_track;         /* 24 bytes */
+
+/* The geometry of a text line from its footprint (STR_ER_WANT_LINE_GEOM, str_er_feet_geom, str_er_hull_of_points,
+ * str_er_quad_from_hull).  All exact, on top of the footprints F(t) of str_er_line_foot.  Screen coordinates: x to the right, y down;
+ * pixel (x, y) is the unit square with the corners (x, y) .. (x + 1, y + 1).
+ *   Hull of a line t: the convex hull of the corners of the pixel squares of F(t) (the construction of str_er_shape::hull_area2 for a
+ *     mask).  Its vertices are integer corners in [0, W] x [0, H]; the hull is strictly convex (collinear points are dropped); the
+ *     order is clockwise on screen, from the vertex with the smallest (y, then x): the pixel (0, 0) alone gives (0,0), (1,0), (1,1),
+ *     (0,1).  hull_area2 is twice its area.
+ *   Moments of F(t), over its pixels in absolute frame pixel coordinates: pixels = |F|, m10 = sum x, m01 = sum y, m20 = sum x^2,
+ *     m11 = sum x y, m02 = sum y^2, uint64.  With a foot box of at most 16384 x 16384 and x, y < 65536 nothing overflows; a larger
+ *     foot box gives STR_ER_ECAPACITY.
+ *   Oriented box: for the hull edge i (vertex i -> vertex (i + 1) mod count) with the integer vector e = (ex, ey) and the normal
+ *     (-ey, ex), d(p) = p.x ex + p.y ey and c(p) = -p.x ey + p.y ex; dmin, dmax, cmin, cmax are the extremes of d and c over the hull
+ *     vertices and A_i = (dmax - dmin)(cmax - cmin) / (ex^2 + ey^2).  The box is that of the edge with the smallest A_i, the A_i
+ *     compared as exact fractions (128-bit products), ties to the smallest i; edge = i.  Corner k takes (d, c) = (dmin, cmin),
+ *     (dmax, cmin), (dmax, cmax), (dmin, cmax): qx[k] = (double)(d ex - c ey) / (double)(ex^2 + ey^2), qy[k] = (double)(d ey + c ex) /
+ *     (double)(ex^2 + ey^2) -- the numerators stay below 2^53, so every corner is one correctly rounded division.
+ *   Frame line: its hull is the hull of the union of its member lines' hull vertices (that is the hull of the union of their
+ *     footprints), its box is made from that hull, its moments and pixels are those of its representative.
+ *   Empty footprint: count = 0, edge = -1, everything else 0.
+ *   The vertex array (str_er_result_geom_points): the hulls of the lines in line order, then those of the frame lines in their order. */
+typedef struct str_er_line_geom {
+    uint32_t first, count;              /*   0: vertices: xy[2*first .. 2*(first+count)) as int32 x, y pairs */
+    uint64_t hull_area2;                /*   8 */
+    uint64_t m10, m01, m20, m11, m02;   /*  16 .. 48 */
+    uint32_t pixels;                    /*  56 */
+    int32_t  edge;                      /*  60 */
+    int32_t  ex, ey;                    /*  64, 68 */
+    int64_t  dmin, dmax, cmin, cmax;    /*  72 .. 96 */
+    double   qx[4], qy[4];              /* 104, 136 */
+} str_er_line_geom;                     /* 168 bytes */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -596,6 +634,23 @@ int str_er_text_tracks_from_links(const str_er_line_foot *feet, const uint32_t *
                                   int32_t den, int32_t *line_tracks, str_er_text_track *tracks, int32_t cap_tracks, int32_t *n_tracks,
                                   int32_t *members);
 
+/* The geometry (str_er_line_geom) of n footprints in the pixels of one frame size W x H (1..65535), made on the GPU: feet[i] is the
+ * foot box and pixel count of line i, bits its rows of (w + 31) / 32 32-bit words over the box, back to back in line order -- the
+ * layout str_er_line_feet_regions and str_er_result_edge_feet return and str_er_link_feet takes; validation and error codes are
+ * those of str_er_link_feet, and a foot box wider or taller than 16384 gives STR_ER_ECAPACITY.  geoms receives n records, xy the
+ * vertices (x, y pairs) they index, *n_points their number; xy == NULL only counts (geoms is still filled); cap_points too small ->
+ * STR_ER_ECAPACITY, *n_points still set.                                                                                          */
+int str_er_feet_geom(str_er_ctx *ctx, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n,
+                     str_er_line_geom *geoms, int32_t *xy, int32_t cap_points, int32_t *n_points);
+/* The strictly convex hull of n points (x, y pairs, any int32), in the vertex order of str_er_line_geom.  Pure host, no context, no
+ * GPU; the detect calls merge the hulls of a frame line with this same function.  out_xy == NULL only counts; cap too small ->
+ * STR_ER_ECAPACITY, *n_out still set.  One point gives one vertex, collinear points their two ends.  STR_ER_EINVAL: bad arguments. */
+int str_er_hull_of_points(const int32_t *xy, int32_t n, int32_t *out_xy, int32_t cap, int32_t *n_out);
+/* hull_area2, edge, ex, ey, dmin .. cmax, qx and qy of *out (str_er_line_geom) from a hull of n vertices; the other fields of *out are
+ * left as they are.  Pure host, no context, no GPU; the detect calls use this same function.  STR_ER_EINVAL: fewer than 3 vertices,
+ * a hull that is not strictly convex in the order of str_er_line_geom, coordinates outside 0..65535.                               */
+int str_er_quad_from_hull(const int32_t *xy, int32_t n, str_er_line_geom *out);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -807,6 +862,12 @@ const int32_t           *str_er_result_text_track_members(const str_er_result *r
  * frame's level-0 size.  STR_ER_EINVAL without the flag or with another `which`; any output pointer may be NULL.                 */
 int str_er_result_edge_feet(const str_er_result *r, int32_t which, int32_t *frame_w, int32_t *frame_h, const str_er_line_foot **feet,
                             const int32_t **lines, int32_t *n, const uint32_t **bits, uint64_t *n_words);
+/* With STR_ER_WANT_LINE_GEOM (str_er_line_geom): one record per line of str_er_result_texts(), one per frame line of
+ * str_er_result_frame_lines(), and the vertex array (x, y pairs, *n_points of them) both sets of records index.  Each returns NULL
+ * and 0 without the flag; a call without lines returns empty arrays (not NULL).                                                    */
+const str_er_line_geom  *str_er_result_line_geoms(const str_er_result *r, int32_t *n);
+const str_er_line_geom  *str_er_result_frame_line_geoms(const str_er_result *r, int32_t *n);
+const int32_t           *str_er_result_geom_points(const str_er_result *r, int32_t *n_points);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

@@ -59,6 +59,13 @@ WANT_LINE_LINKS = 262144
 LINE_LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("inter", "<u4"), ("link", "<u4")])
 # str_er_text_track: members = text_track_members[first:first + count] (line indices, ascending), rep the one with the most pixels
 TEXT_TRACK_DTYPE = np.dtype([("first_frame", "<u4"), ("last_frame", "<u4"), ("first", "<i4"), ("count", "<i4"), ("rep", "<i4"), ("pixels", "<u4")])
+# output option: the convex hull, the moments and the oriented box of every text line and frame line (needs WANT_FRAME_LINES;
+# Result.line_geoms / frame_line_geoms / geom_points / line_hull / line_quad; the contract is at str_er_line_geom in include/str_er.h)
+WANT_LINE_GEOM = 524288
+# str_er_line_geom: the hull vertices are geom_points[first:first + count]; the box is that of hull edge `edge`, corners (qx[k], qy[k])
+LINE_GEOM_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("hull_area2", "<u8"), ("m10", "<u8"), ("m01", "<u8"), ("m20", "<u8"), ("m11", "<u8"),
+                            ("m02", "<u8"), ("pixels", "<u4"), ("edge", "<i4"), ("ex", "<i4"), ("ey", "<i4"), ("dmin", "<i8"), ("dmax", "<i8"),
+                            ("cmin", "<i8"), ("cmax", "<i8"), ("qx", "<f8", (4,)), ("qy", "<f8", (4,))])
 # str_er_line_crop: crop t = width x height bytes (pitch width) from byte pix_off of the crop bytes (and of the glyph bytes);
 # ax .. vy: the 16.16 sampling geometry (include/str_er.h)
 LINE_CROP_DTYPE = np.dtype([("pix_off", "<u8"), ("width", "<i4"), ("height", "<i4"), ("ax", "<i4"), ("ay", "<i4"),
@@ -86,6 +93,7 @@ assert STROKE_DTYPE.itemsize == 32
 assert FRAME_MAP_DTYPE.itemsize == 16
 assert LINE_FOOT_DTYPE.itemsize == 24 and LINE_PAIR_DTYPE.itemsize == 16 and FRAME_LINE_DTYPE.itemsize == 40
 assert LINE_LINK_DTYPE.itemsize == 16 and TEXT_TRACK_DTYPE.itemsize == 24
+assert LINE_GEOM_DTYPE.itemsize == 168
 
 
 def unpack_mask(words: np.ndarray, word_off: int, w: int, h: int) -> np.ndarray:
@@ -290,6 +298,12 @@ def load_library():
     L.str_er_set_line_link.argtypes = [vp, C.c_int32, C.c_int32]
     L.str_er_link_feet.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, i32p]
     L.str_er_text_tracks_from_links.argtypes = [vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, i32p, vp]
+    for fn in (L.str_er_result_line_geoms, L.str_er_result_frame_line_geoms, L.str_er_result_geom_points):
+        fn.argtypes = [vp, i32p]
+        fn.restype = vp
+    L.str_er_feet_geom.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p]
+    L.str_er_hull_of_points.argtypes = [vp, C.c_int32, vp, C.c_int32, i32p]
+    L.str_er_quad_from_hull.argtypes = [vp, C.c_int32, vp]
     L.str_er_line_crop_geometry.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, vp]
     L.str_er_line_crops.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, C.c_uint64,
                                     C.POINTER(C.c_uint64), vp]
@@ -420,7 +434,50 @@ class Result:
         self._text_tracks = None
         self._text_track_members = None
         self._edge_feet = None
+        self._line_geoms = None    # with WANT_LINE_GEOM: the tables behind line_geoms / frame_line_geoms / geom_points
+        self._frame_line_geoms = None
+        self._geom_points = None
         self._planes = None
+
+    def _line_geom_table(self, table):
+        if table is None:
+            raise ValueError("the result has no line geometry (pass WANT_LINE_GEOM / want_line_geom=True)")
+        return table
+
+    @property
+    def line_geoms(self) -> np.ndarray:
+        """With WANT_LINE_GEOM: LINE_GEOM_DTYPE per line of texts."""
+        return self._line_geom_table(self._line_geoms)
+
+    @property
+    def frame_line_geoms(self) -> np.ndarray:
+        """With WANT_LINE_GEOM: LINE_GEOM_DTYPE per frame line."""
+        return self._line_geom_table(self._frame_line_geoms)
+
+    @property
+    def geom_points(self) -> np.ndarray:
+        """With WANT_LINE_GEOM: the hull vertices both sets of records index, (n_points, 2) int32 x, y."""
+        return self._line_geom_table(self._geom_points)
+
+    def line_hull(self, t: int) -> np.ndarray:
+        """With WANT_LINE_GEOM: the hull of line t, (n, 2) int32 corners, clockwise on screen from the smallest (y, x)."""
+        g = self.line_geoms[t]
+        return self.geom_points[int(g["first"]):int(g["first"]) + int(g["count"])].copy()
+
+    def line_quad(self, t: int) -> np.ndarray:
+        """With WANT_LINE_GEOM: the oriented box of line t, (4, 2) float64 corners (x, y)."""
+        g = self.line_geoms[t]
+        return np.stack([g["qx"], g["qy"]], 1).astype(np.float64)
+
+    def frame_line_hull(self, i: int) -> np.ndarray:
+        """With WANT_LINE_GEOM: the hull of frame line i, (n, 2) int32."""
+        g = self.frame_line_geoms[i]
+        return self.geom_points[int(g["first"]):int(g["first"]) + int(g["count"])].copy()
+
+    def frame_line_quad(self, i: int) -> np.ndarray:
+        """With WANT_LINE_GEOM: the oriented box of frame line i, (4, 2) float64 corners (x, y)."""
+        g = self.frame_line_geoms[i]
+        return np.stack([g["qx"], g["qy"]], 1).astype(np.float64)
 
     def _line_links_table(self, table):
         if table is None:
@@ -666,6 +723,12 @@ class ERFilter:
                     res._line_pairs = table(L.str_er_result_line_pairs, LINE_PAIR_DTYPE)
                     res._frame_lines = table(L.str_er_result_frame_lines, FRAME_LINE_DTYPE)
                     res._frame_line_members = table(L.str_er_result_frame_line_members, np.int32)
+                    res._line_geoms = table(L.str_er_result_line_geoms, LINE_GEOM_DTYPE)
+                    if res._line_geoms is not None:
+                        res._frame_line_geoms = table(L.str_er_result_frame_line_geoms, LINE_GEOM_DTYPE)
+                        npts = C.c_int32()
+                        ptr = L.str_er_result_geom_points(rh, C.byref(npts))
+                        res._geom_points = _owned(ptr, 2 * npts.value, np.int32).reshape(-1, 2)
                     res._line_links = table(L.str_er_result_line_links, LINE_LINK_DTYPE)
                     if res._line_links is not None:
                         res._line_tracks = table(L.str_er_result_line_tracks, np.int32)
@@ -729,7 +792,7 @@ class ERFilter:
     def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
-                    want_line_links: bool = False) -> Result:
+                    want_line_links: bool = False, want_line_geom: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -742,7 +805,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -863,7 +926,7 @@ class ERFilter:
     def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
-                         want_line_links: bool = False) -> Result:
+                         want_line_links: bool = False, want_line_geom: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -871,7 +934,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links))
+                                                                  line_links=want_line_links, line_geom=want_line_geom))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1059,6 +1122,22 @@ class ERFilter:
         if n.value:
             self._check(self.L.str_er_link_feet(*args, _np_ptr(out), len(out), C.byref(n)))
         return out[:n.value]
+
+    def feet_geom(self, W: int, H: int, feet: np.ndarray, bits: np.ndarray):
+        """str_er_feet_geom: the geometry (str_er_line_geom) of footprints in the pixels of one (H, W) frame, on the GPU: feet
+        LINE_FOOT_DTYPE (box and pixels are read), bits the rows of (w + 31) // 32 words over each foot box, back to back -- what
+        line_feet_regions and Result.edge_feet return.  Returns (LINE_GEOM_DTYPE per footprint, (n_points, 2) int32 hull vertices)."""
+        ft = np.ascontiguousarray(feet, dtype=LINE_FOOT_DTYPE).reshape(-1)
+        bt = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+        if int((ft["h"].astype(np.int64).clip(0) * ((ft["w"].astype(np.int64).clip(0) + 31) // 32)).sum()) != len(bt):
+            raise ValueError("bits needs h rows of (w + 31) // 32 words per foot, back to back")
+        geoms = np.zeros(max(1, len(ft)), LINE_GEOM_DTYPE)
+        n = C.c_int32()
+        cap = int((2 * (ft["h"].astype(np.int64).clip(0) + 1)).sum())        # (a hull has at most two vertices per height 0 .. h: one call)
+        xy = np.zeros((max(1, cap), 2), np.int32)
+        self._check(self.L.str_er_feet_geom(self.h, int(W), int(H), _np_ptr(ft) if len(ft) else None, _np_ptr(bt) if len(bt) else None, len(ft),
+                                            _np_ptr(geoms), _np_ptr(xy), min(len(xy), 2 ** 31 - 1), C.byref(n)))
+        return geoms[:len(ft)], xy[:n.value].copy()
 
     def set_line_crop(self, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> None:
         """str_er_set_line_crop: the crop height (8..256), the widest crop (1..8192) and the pad (0..1, of the line's height) of
@@ -1250,10 +1329,10 @@ def _owned(ptr, n: int, dtype) -> np.ndarray:
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -1277,6 +1356,30 @@ def frame_lines_from_pairs(feet: np.ndarray, frames_of_lines, pyr_of_lines, pair
     if rc != 0:
         raise StrErError(rc, "str_er_frame_lines_from_pairs")
     return ft, pr, fl[:nfl.value], mem[:n]
+
+
+def hull_of_points(points) -> np.ndarray:
+    """str_er_hull_of_points (pure host): the strictly convex hull of (n, 2) integer points, (m, 2) int32, clockwise on screen (x to
+    the right, y down) from the vertex with the smallest (y, x)."""
+    pts = np.ascontiguousarray(points, dtype=np.int32).reshape(-1, 2)
+    out = np.zeros((max(1, len(pts)), 2), np.int32)
+    n = C.c_int32()
+    rc = load_library().str_er_hull_of_points(_np_ptr(pts) if len(pts) else None, len(pts), _np_ptr(out), len(out), C.byref(n))
+    if rc != 0:
+        raise StrErError(rc, "str_er_hull_of_points")
+    return out[:n.value]
+
+
+def quad_from_hull(hull) -> np.ndarray:
+    """str_er_quad_from_hull (pure host): one LINE_GEOM_DTYPE record with hull_area2, edge, ex .. cmax, qx and qy of a hull of (n, 2)
+    vertices in the order of hull_of_points (first = 0, count = n; the moments stay 0)."""
+    pts = np.ascontiguousarray(hull, dtype=np.int32).reshape(-1, 2)
+    g = np.zeros(1, LINE_GEOM_DTYPE)
+    rc = load_library().str_er_quad_from_hull(_np_ptr(pts) if len(pts) else None, len(pts), _np_ptr(g))
+    if rc != 0:
+        raise StrErError(rc, "str_er_quad_from_hull")
+    g["count"] = len(pts)
+    return g[0]
 
 
 def text_tracks_from_links(feet: np.ndarray, frames_of_lines, pairs: np.ndarray, links: np.ndarray, num: int = 1, den: int = 2):

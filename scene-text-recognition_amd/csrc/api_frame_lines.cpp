@@ -7,8 +7,13 @@
 // frames behind k_line_foot, beside k_foot_pairs, and shares the stage's upload and wait; the words of the first and of the last
 // frame's footprints come back as the result's edge feet; str_er_link_feet runs the same kernel on two uploaded sets of footprints;
 // str_er_text_tracks_from_links joins duplicates and links into tracks on the host.
+// STR_ER_WANT_LINE_GEOM (the contract is at str_er_line_geom) rides on the same stage as well: k_foot_geom reads every footprint once
+// behind k_line_foot and leaves the moments and the hull vertices, which come back in the stage's one wait; the host makes the oriented
+// boxes (str_er_quad_from_hull) and merges the hulls of a frame line (str_er_hull_of_points).  str_er_feet_geom runs the same kernel on
+// uploaded footprints.
 #include "str_er_ctx.h"
 
+#include <array>
 #include <numeric>
 
 namespace str_er_host {
@@ -147,9 +152,79 @@ int link_table(str_er_ctx *c, size_t n_lines, size_t tail, size_t &cap)
     return grow_pair(c, c->d_link_out, c->h_link_out, c->link_out_bytes, sizeof(FootHead) + sizeof(FootPair) * cap + tail, "line link output");
 }
 
+constexpr int32_t GEOM_MAX_BOX = 16384;          // the widest / tallest foot box whose moments are promised not to overflow
+
+// k_foot_geom over the lines of a launch: where every line's vertices and scratch rows go, and the layout of the geometry buffer
+// (slots | records | vertices; the same on both sides)
+struct GeomPlan {
+    std::vector<GeomSlot> slots;
+    size_t n_lines = 0, n_pts = 0, x_words = 0, o_rec = 0, o_xy = 0, bytes = 0;
+};
+
+// the slots uploaded, the kernel and the copy back enqueued on s behind whatever made the footprints in c->d_foot_bits; geom_collect after the wait
+int geom_enqueue(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const FootLine *d_lines, GeomPlan &P)
+{
+    P.n_lines = lines.size();
+    P.slots.assign(P.n_lines, GeomSlot{0, 0});
+    uint64_t pts = 0, xw = 0;
+    for (size_t t = 0; t < P.n_lines; ++t) {
+        const FootLine &L = lines[t];
+        if (L.w <= 0 || L.h <= 0) continue;
+        P.slots[t].pt_first = (uint32_t)pts;
+        pts += 2ull * ((uint64_t)L.h + 1u);          // (a chain has at most one vertex per height 0 .. h)
+        if (L.h + 1 > GEOM_LDS_ROWS) { P.slots[t].x_first = (uint32_t)xw; xw += (uint64_t)L.h + 1u; }
+        if (pts > 0x7FFFFFFFull) return fail(c, STR_ER_ECAPACITY, "line geometry: more than 2^31 hull vertices to reserve");
+    }
+    P.n_pts = (size_t)pts; P.x_words = (size_t)xw;
+    if (P.n_lines == 0) return STR_ER_OK;
+    P.o_rec = align_up(sizeof(GeomSlot) * P.n_lines, 256); P.o_xy = align_up(P.o_rec + sizeof(GeomRec) * P.n_lines, 256);
+    P.bytes = P.o_xy + 8 * P.n_pts;
+    int rc = grow_pair(c, c->d_geom_out, c->h_geom_out, c->geom_out_bytes, P.bytes, "line geometry output");
+    if (rc != STR_ER_OK) return rc;
+    if (P.x_words > c->geom_x_words) {
+        if (c->d_geom_x) { (void)hipFree(c->d_geom_x); c->d_geom_x = nullptr; }
+        const size_t get = std::max(P.x_words, 2 * c->geom_x_words);
+        c->geom_x_words = 0;
+        if (hipMalloc(reinterpret_cast<void **>(&c->d_geom_x), 8 * get) != hipSuccess)
+            return fail(c, STR_ER_ENOMEM, "hipMalloc (line geometry rows, " + std::to_string(8 * get) + " bytes)");
+        c->geom_x_words = get;
+    }
+    std::memcpy(c->h_geom_out, P.slots.data(), sizeof(GeomSlot) * P.n_lines);
+    HIP_TRY(c, hipMemcpyAsync(c->d_geom_out, c->h_geom_out, sizeof(GeomSlot) * P.n_lines, hipMemcpyHostToDevice, s));
+    launch_foot_geom(s, d_lines, (int)P.n_lines, reinterpret_cast<const GeomSlot *>(c->d_geom_out), c->d_foot_bits, c->d_geom_x,
+                     reinterpret_cast<GeomRec *>(c->d_geom_out + P.o_rec), reinterpret_cast<int32_t *>(c->d_geom_out + P.o_xy));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->h_geom_out + P.o_rec, c->d_geom_out + P.o_rec, P.bytes - P.o_rec, hipMemcpyDeviceToHost, s));
+    return STR_ER_OK;
+}
+
+// after the wait: one record per line, its vertices appended to xy (x, y pairs) and its box made (str_er_quad_from_hull)
+int geom_collect(str_er_ctx *c, const GeomPlan &P, std::vector<str_er_line_geom> &geoms, std::vector<int32_t> &xy)
+{
+    geoms.assign(P.n_lines, str_er_line_geom{});
+    for (size_t t = 0; t < P.n_lines; ++t) {
+        str_er_line_geom &G = geoms[t];
+        GeomRec R;
+        std::memcpy(&R, c->h_geom_out + P.o_rec + sizeof(GeomRec) * t, sizeof R);
+        G.edge = -1;
+        if (R.count == 0) continue;
+        const uint32_t first = P.slots[t].pt_first;
+        if (R.count < 4 || (size_t)first + R.count > P.n_pts) return fail(c, STR_ER_EHIP, "line geometry: a hull outside its vertices (internal error)");
+        const int32_t *src = reinterpret_cast<const int32_t *>(c->h_geom_out + P.o_xy) + 2 * (size_t)first;
+        G.first = (uint32_t)(xy.size() / 2); G.count = R.count;
+        xy.insert(xy.end(), src, src + 2 * (size_t)R.count);
+        G.pixels = R.pixels; G.m10 = R.m10; G.m01 = R.m01; G.m20 = R.m20; G.m11 = R.m11; G.m02 = R.m02;
+        if (str_er_quad_from_hull(xy.data() + 2 * (size_t)G.first, (int32_t)G.count, &G) != STR_ER_OK)
+            return fail(c, STR_ER_EHIP, "line geometry: the device's hull is not a hull (internal error)");
+    }
+    return STR_ER_OK;
+}
+
 // one upload, the launches on s, one copy back, one wait (a pair pass again, with a larger table, if its pairs outgrew it).
 // LK: the links across adjacent frames as well (T.range), in the same upload and wait, with a table and a copy of their own
-int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t *d_bits, bool in_batch, FootOut &O, LinkOut *LK = nullptr)
+// GP: the geometry of the footprints as well (k_foot_geom behind k_line_foot, its copy back ahead of the same wait; geom_collect afterwards)
+int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t *d_bits, bool in_batch, FootOut &O, LinkOut *LK = nullptr,
+               GeomPlan *GP = nullptr)
 {
     const size_t n_lines = T.lines.size();
     O.stat.assign(n_lines, FootStat{});
@@ -196,6 +271,7 @@ int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t
             h_edge += 8 * edge_n[e];
         }
     }
+    if (GP && (rc = geom_enqueue(c, s, T.lines, d_lines, *GP)) != STR_ER_OK) return rc;
     bool run_pairs = true, run_links = LK != nullptr;
     for (int pass = 0; run_pairs || run_links; ++pass) {
         if (run_pairs) launch_foot_pairs(s, d_lines, (int)n_lines, d_list, c->d_foot_bits, reinterpret_cast<FootHead *>(c->d_foot_out),
@@ -302,7 +378,7 @@ void foot_rows32(const uint64_t *words, const FootLine &L, const str_er_line_foo
 } // namespace
 
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
-                      str_er_result *r, bool links)
+                      str_er_result *r, bool links, bool geom)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n_frames = b.frame_wh.size() / 2, n_lines = r->texts.size();
@@ -364,10 +440,15 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
     const double ms_layout = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     FootOut O;
     LinkOut LK;
-    const int rc = foot_stage(c, s, T, d_bits, true, O, links ? &LK : nullptr);
+    GeomPlan GP;
+    const int rc = foot_stage(c, s, T, d_bits, true, O, links ? &LK : nullptr, geom ? &GP : nullptr);
     if (rc != STR_ER_OK) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     feet_from_stats(O.stat, r->line_feet);
+    if (geom)
+        for (const str_er_line_foot &F : r->line_feet)
+            if (F.w > GEOM_MAX_BOX || F.h > GEOM_MAX_BOX)
+                return fail(c, STR_ER_ECAPACITY, "STR_ER_WANT_LINE_GEOM: a foot box wider or taller than " + std::to_string(GEOM_MAX_BOX) + " pixels");
     r->line_pairs.resize(O.pairs.size());
     if (!O.pairs.empty()) std::memcpy(r->line_pairs.data(), O.pairs.data(), sizeof(FootPair) * O.pairs.size());
     r->frame_lines.resize(n_lines);
@@ -409,6 +490,50 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
         if (c->dbg_stats)        // developer aid (tools/dev_line_links.py)
             std::fprintf(stderr, "[str_er] line links: %u candidate pairs, %zu overlaps, %d tracks, %zu bytes back for the link table, %zu bytes back for the edge feet\n",
                          LK.n_candidates, LK.links.size(), n_tr, LK.bytes_back, LK.edge_bytes);
+    }
+    if (geom) {
+        const auto t2 = std::chrono::steady_clock::now();
+        r->geom_points.clear();
+        if (T.members.empty()) r->line_geoms.assign(n_lines, str_er_line_geom{});        // (no footprint at all: nothing was launched)
+        else if (const int rcg = geom_collect(c, GP, r->line_geoms, r->geom_points); rcg != STR_ER_OK) return rcg;
+        if (T.members.empty())
+            for (str_er_line_geom &G : r->line_geoms) G.edge = -1;
+        // the frame lines: the hull of the union of the members' hull vertices, the moments of the representative
+        r->frame_line_geoms.assign(r->frame_lines.size(), str_er_line_geom{});
+        std::vector<int32_t> uni, hull;
+        for (size_t i = 0; i < r->frame_lines.size(); ++i) {
+            const str_er_frame_line &FL = r->frame_lines[i];
+            str_er_line_geom &G = r->frame_line_geoms[i];
+            G.edge = -1;
+            uni.clear();
+            for (int32_t k = FL.first; k < FL.first + FL.count; ++k) {
+                const str_er_line_geom &M = r->line_geoms[(size_t)r->frame_line_members[(size_t)k]];
+                uni.insert(uni.end(), r->geom_points.begin() + 2 * (size_t)M.first, r->geom_points.begin() + 2 * ((size_t)M.first + M.count));
+            }
+            if (FL.rep >= 0) {
+                const str_er_line_geom &M = r->line_geoms[(size_t)FL.rep];
+                G.pixels = M.pixels; G.m10 = M.m10; G.m01 = M.m01; G.m20 = M.m20; G.m11 = M.m11; G.m02 = M.m02;
+            }
+            if (uni.empty()) continue;
+            if (FL.count == 1) {            // (one member: its hull and its box)
+                const uint32_t first = (uint32_t)(r->geom_points.size() / 2);
+                G = r->line_geoms[(size_t)r->frame_line_members[(size_t)FL.first]];
+                G.first = first;
+                r->geom_points.insert(r->geom_points.end(), uni.begin(), uni.end());
+                continue;
+            }
+            hull.resize(uni.size());
+            int32_t nh = 0;
+            if (str_er_hull_of_points(uni.data(), (int32_t)(uni.size() / 2), hull.data(), (int32_t)(uni.size() / 2), &nh) != STR_ER_OK ||
+                str_er_quad_from_hull(hull.data(), nh, &G) != STR_ER_OK)
+                return fail(c, STR_ER_EHIP, "line geometry: the hull of a frame line failed (internal error)");
+            G.first = (uint32_t)(r->geom_points.size() / 2); G.count = (uint32_t)nh;
+            r->geom_points.insert(r->geom_points.end(), hull.begin(), hull.begin() + 2 * (size_t)nh);
+        }
+        r->have_line_geom = true;
+        if (c->dbg_stats)        // developer aid (tools/dev_line_geom.py)
+            std::fprintf(stderr, "[str_er] line geometry: %zu lines, %zu vertices reserved, %zu kept, %zu bytes back, host %.3f ms\n", n_lines, GP.n_pts,
+                         r->geom_points.size() / 2, GP.bytes - GP.o_rec, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
     }
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
@@ -729,6 +854,196 @@ try {
     }
     return STR_ER_OK;
 } ABI_GUARD(c)
+
+namespace {
+
+using i128 = __int128;
+
+// > 0: o -> a -> b turns clockwise on screen (x to the right, y down)
+inline i128 turn(const int32_t *o, const int32_t *a, const int32_t *b)
+{
+    return (i128)((int64_t)a[0] - o[0]) * ((int64_t)b[1] - o[1]) - (i128)((int64_t)a[1] - o[1]) * ((int64_t)b[0] - o[0]);
+}
+
+} // namespace
+
+int str_er_hull_of_points(const int32_t *xy, int32_t n, int32_t *out_xy, int32_t cap, int32_t *n_out)
+try {
+    if (n < 0 || !n_out || (n > 0 && !xy) || (out_xy && cap < 0)) return STR_ER_EINVAL;
+    // Andrew's monotone chain over the points sorted by (y, x): down the right side, then up the left side, every turn strictly clockwise
+    std::vector<std::array<int32_t, 2>> p((size_t)n);
+    for (int32_t i = 0; i < n; ++i) p[(size_t)i] = {xy[2 * i], xy[2 * i + 1]};
+    std::sort(p.begin(), p.end(), [](const std::array<int32_t, 2> &a, const std::array<int32_t, 2> &b) { return a[1] != b[1] ? a[1] < b[1] : a[0] < b[0]; });
+    p.erase(std::unique(p.begin(), p.end()), p.end());
+    std::vector<std::array<int32_t, 2>> st;
+    if (p.size() <= 2) st = p;
+    else {
+        st.reserve(2 * p.size());
+        for (size_t i = 0; i < p.size(); ++i) {
+            while (st.size() >= 2 && turn(st[st.size() - 2].data(), st.back().data(), p[i].data()) <= 0) st.pop_back();
+            st.push_back(p[i]);
+        }
+        const size_t low = st.size() + 1;
+        for (size_t i = p.size() - 1; i-- > 0;) {
+            while (st.size() >= low && turn(st[st.size() - 2].data(), st.back().data(), p[i].data()) <= 0) st.pop_back();
+            st.push_back(p[i]);
+        }
+        st.pop_back();
+    }
+    *n_out = (int32_t)st.size();
+    if (!out_xy) return STR_ER_OK;
+    if ((int32_t)st.size() > cap) return STR_ER_ECAPACITY;
+    for (size_t i = 0; i < st.size(); ++i) { out_xy[2 * i] = st[i][0]; out_xy[2 * i + 1] = st[i][1]; }
+    return STR_ER_OK;
+} catch (...) { return STR_ER_ENOMEM; }
+
+int str_er_quad_from_hull(const int32_t *xy, int32_t n, str_er_line_geom *out)
+try {
+    if (!xy || !out || n < 3) return STR_ER_EINVAL;
+    for (int32_t i = 0; i < 2 * n; ++i)
+        if (xy[i] < 0 || xy[i] > 65535) return STR_ER_EINVAL;
+    // a hull in the stated order: it starts at the smallest (y, x), every turn is strictly clockwise, and it goes round once (y falls
+    // only after it has risen, and then never rises again)
+    int32_t flips = 0;
+    int     first_sign = 0, last_sign = 0;         // of the y steps that are not level
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t *p = xy + 2 * (size_t)i, *q = xy + 2 * (size_t)((i + 1) % n), *w = xy + 2 * (size_t)((i + 2) % n);
+        if (i > 0 && (p[1] < xy[1] || (p[1] == xy[1] && p[0] <= xy[0]))) return STR_ER_EINVAL;
+        if (turn(p, q, w) <= 0) return STR_ER_EINVAL;
+        const int sg = (q[1] > p[1]) - (q[1] < p[1]);
+        if (sg == 0) continue;
+        if (last_sign != 0 && sg != last_sign) ++flips;
+        if (first_sign == 0) first_sign = sg;
+        last_sign = sg;
+    }
+    if (flips + (first_sign != last_sign ? 1 : 0) != 2) return STR_ER_EINVAL;
+    const auto V = [&](int32_t k) { return xy + 2 * (size_t)(k % n); };
+    i128 area2 = 0;
+    for (int32_t i = 0; i < n; ++i) area2 += (i128)V(i)[0] * V(i + 1)[1] - (i128)V(i + 1)[0] * V(i)[1];
+    // rotating calipers: for the edge i the vertices with the largest d, the largest c and the smallest d only move forward as i does
+    // (c is smallest on the edge itself: the hull lies on the side of its normal); every value is exact in 64 bits
+    int32_t pd = 0, pc = 0, pm = 0;         // (positions, taken modulo n)
+    int32_t best = -1;
+    int64_t b_ex = 0, b_ey = 0, b_d0 = 0, b_d1 = 0, b_c0 = 0, b_c1 = 0;
+    i128    b_num = 0;
+    int64_t b_den = 1;
+    for (int32_t i = 0; i < n; ++i) {
+        const int64_t ex = (int64_t)V(i + 1)[0] - V(i)[0], ey = (int64_t)V(i + 1)[1] - V(i)[1];
+        const auto d = [&](int32_t k) { return V(k)[0] * ex + V(k)[1] * ey; };
+        const auto cc = [&](int32_t k) { return -V(k)[0] * ey + V(k)[1] * ex; };
+        if (i == 0) {
+            for (int32_t k = 1; k < n; ++k) {
+                if (d(k) > d(pd)) pd = k;
+                if (cc(k) > cc(pc)) pc = k;
+                if (d(k) < d(pm)) pm = k;
+            }
+        } else {
+            for (int32_t g = 0; g < n && d(pd + 1) > d(pd); ++g) pd = (pd + 1) % n;
+            for (int32_t g = 0; g < n && cc(pc + 1) > cc(pc); ++g) pc = (pc + 1) % n;
+            for (int32_t g = 0; g < n && d(pm + 1) < d(pm); ++g) pm = (pm + 1) % n;
+        }
+        const int64_t d0 = d(pm), d1 = d(pd), c0 = cc(i), c1 = cc(pc), den = ex * ex + ey * ey;
+        const i128    num = (i128)(d1 - d0) * (c1 - c0);
+        if (best < 0 || num * b_den < b_num * den) {
+            best = i; b_ex = ex; b_ey = ey; b_d0 = d0; b_d1 = d1; b_c0 = c0; b_c1 = c1; b_num = num; b_den = den;
+        }
+    }
+    out->hull_area2 = (uint64_t)area2;
+    out->edge = best; out->ex = (int32_t)b_ex; out->ey = (int32_t)b_ey;
+    out->dmin = b_d0; out->dmax = b_d1; out->cmin = b_c0; out->cmax = b_c1;
+    const int64_t dd[4] = {b_d0, b_d1, b_d1, b_d0}, cs[4] = {b_c0, b_c0, b_c1, b_c1};
+    for (int k = 0; k < 4; ++k) {
+        out->qx[k] = (double)(dd[k] * b_ex - cs[k] * b_ey) / (double)b_den;
+        out->qy[k] = (double)(dd[k] * b_ey + cs[k] * b_ex) / (double)b_den;
+    }
+    return STR_ER_OK;
+} catch (...) { return STR_ER_ENOMEM; }
+
+int str_er_feet_geom(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_geom *geoms, int32_t *xy,
+                     int32_t cap_points, int32_t *n_points)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (W < 1 || H < 1 || W > 65535 || H > 65535 || n < 0 || !n_points || (n > 0 && (!feet || !geoms)) || (xy && cap_points < 0))
+        return fail(c, STR_ER_EINVAL, "bad arguments");
+    // the footprints as a table of lines and rows of 64-bit words, every one checked against its foot (as str_er_link_feet does)
+    std::vector<FootLine> lines((size_t)n, FootLine{});
+    std::vector<uint64_t> words;
+    for (int32_t t = 0; t < n; ++t) {
+        const str_er_line_foot &F = feet[t];
+        const std::string who = "line " + std::to_string(t);
+        if (F.w < 0 || F.h < 0 || (F.w == 0) != (F.h == 0)) return fail(c, STR_ER_EINVAL, who + ": bad foot box");
+        if (F.w == 0) {
+            if (F.pixels) return fail(c, STR_ER_EINVAL, who + ": pixels in an empty foot box");
+            continue;
+        }
+        if (F.x < 0 || F.y < 0 || (int64_t)F.x + F.w > W || (int64_t)F.y + F.h > H) return fail(c, STR_ER_EINVAL, who + ": the foot box leaves the frame");
+    }
+    for (int32_t t = 0; t < n; ++t)
+        if (feet[t].w > GEOM_MAX_BOX || feet[t].h > GEOM_MAX_BOX)
+            return fail(c, STR_ER_ECAPACITY, "line " + std::to_string(t) + ": a foot box wider or taller than " + std::to_string(GEOM_MAX_BOX) + " pixels");
+    const uint32_t *at = bits;
+    for (int32_t t = 0; t < n; ++t) {
+        const str_er_line_foot &F = feet[t];
+        FootLine &L = lines[(size_t)t];
+        L.word_off = words.size();
+        if (F.w == 0) continue;
+        if (!at) return fail(c, STR_ER_EINVAL, "footprint bits missing");
+        L.x = F.x; L.y = F.y; L.w = F.w; L.h = F.h; L.pitch = ((uint32_t)F.w + 63u) / 64u; L.count = 1;
+        const uint32_t pitch32 = ((uint32_t)F.w + 31u) / 32u, tail = (uint32_t)F.w & 31u;
+        uint64_t px = 0;
+        for (int32_t rr = 0; rr < F.h; ++rr, at += pitch32) {
+            if (tail && (at[pitch32 - 1] >> tail)) return fail(c, STR_ER_EINVAL, "a footprint has a bit set past its row's width");
+            for (uint32_t k = 0; k < L.pitch; ++k) {
+                const uint64_t v = (uint64_t)at[2 * k] | (2 * k + 1 < pitch32 ? (uint64_t)at[2 * k + 1] << 32 : 0ull);
+                px += (uint64_t)__builtin_popcountll(v);
+                words.push_back(v);
+            }
+        }
+        if (px != F.pixels) return fail(c, STR_ER_EINVAL, "a foot's pixels are not the number of bits set in its footprint");
+        if (px == 0) L = FootLine{};          // (a box without a bit: an empty footprint)
+    }
+    std::vector<str_er_line_geom> out((size_t)n, str_er_line_geom{});
+    for (str_er_line_geom &G : out) G.edge = -1;
+    std::vector<int32_t> pts;
+    if (!words.empty()) {
+        HIP_TRY(c, hipSetDevice(c->prm.device));
+        int rc = grow_pair(c, c->d_foot_tab, c->h_foot_tab, c->foot_tab_bytes, sizeof(FootLine) * (size_t)n, "frame line tables");
+        if (rc != STR_ER_OK) return rc;
+        if ((rc = grow_foot_bits(c, words.size())) != STR_ER_OK) return rc;
+        hipStream_t s = c->stream;
+        std::memcpy(c->h_foot_tab, lines.data(), sizeof(FootLine) * (size_t)n);
+        HIP_TRY(c, hipMemcpyAsync(c->d_foot_tab, c->h_foot_tab, sizeof(FootLine) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->d_foot_bits, words.data(), 8 * words.size(), hipMemcpyHostToDevice, s));      // (words must outlive the copy: every path below waits)
+        GeomPlan GP;
+        if ((rc = geom_enqueue(c, s, lines, reinterpret_cast<const FootLine *>(c->d_foot_tab), GP)) != STR_ER_OK) {
+            (void)hipStreamSynchronize(s);          // (the upload of words may still be queued)
+            return rc;
+        }
+        HIP_TRY(c, wait_stream(c, s));
+        if ((rc = geom_collect(c, GP, out, pts)) != STR_ER_OK) return rc;
+    }
+    *n_points = (int32_t)(pts.size() / 2);
+    if (n > 0) std::memcpy(geoms, out.data(), sizeof(str_er_line_geom) * (size_t)n);
+    if (xy && (int64_t)(pts.size() / 2) > (int64_t)cap_points)
+        return fail(c, STR_ER_ECAPACITY, std::to_string(pts.size() / 2) + " hull vertices, cap_points is " + std::to_string(cap_points));
+    if (xy && !pts.empty()) std::memcpy(xy, pts.data(), 4 * pts.size());
+    return STR_ER_OK;
+} ABI_GUARD(c)
+
+const str_er_line_geom *str_er_result_line_geoms(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_geom, &str_er_result::line_geoms, n); }
+
+const str_er_line_geom *str_er_result_frame_line_geoms(const str_er_result *r, int32_t *n)
+{
+    return result_table(r, r && r->have_line_geom, &str_er_result::frame_line_geoms, n);
+}
+
+const int32_t *str_er_result_geom_points(const str_er_result *r, int32_t *n_points)
+{
+    int32_t n2 = 0;
+    const int32_t *p = result_table(r, r && r->have_line_geom, &str_er_result::geom_points, &n2);
+    if (n_points) *n_points = n2 / 2;
+    return p;
+}
 
 const str_er_line_link *str_er_result_line_links(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_links, &str_er_result::line_links, n); }
 

@@ -19,6 +19,16 @@
 // the next adjacent frame -- range[a] = (first, end) into the same list, empty where the next frame has another size or there is
 // none -- with the box test fused in; a and b are in the same pixel coordinates, so the AND over the intersection is that of
 // k_foot_pairs (foot_overlap).  One wave per line was kept over one wave per candidate pair: see DESIGN.md 3.15.
+//
+// k_foot_geom (STR_ER_WANT_LINE_GEOM, str_er_feet_geom; the contract is at str_er_line_geom): the moments and the convex hull of every
+// footprint, read once.  A wave (a workgroup of its own) takes a line; a lane the rows lane, lane + 64, ... of its bit rows (a lane
+// walks a whole row: the loads of neighbouring lanes lie 8 * pitch bytes apart, contiguous only where pitch is 1).  Per row
+// the lane finds the extent with ctz / clz over the row's words, and per word the popcount and the sums of x and x^2 under its bits
+// as bit-sliced sums (foot_word_sums: 27 popcounts, no loop over pixels); rows without a bit add nothing and leave the "empty" extent.
+// The six moments are wave-reduced.  Lane 0 then runs the two monotone chains of shape_hull_area2 (er_masks.inl, shape_hull_add) over
+// the row extents -- in LDS for a line of up to GEOM_LDS_ROWS - 1 rows, else in scratch words the host reserved -- keeping the last
+// point as well, and the wave writes the vertices out: left[0], the right chain downwards, the left chain upwards.  The chains were
+// kept sequential on one lane over a divide-and-merge of lane-local chains: see DESIGN.md 3.16.
 
 constexpr int FOOT_THREADS = 256;           // 4 waves, a job / a line each
 
@@ -173,6 +183,92 @@ __global__ __launch_bounds__(FOOT_THREADS) void k_foot_links(const FootLine *__r
     }
 }
 
+constexpr int GEOM_THREADS = 64;            // one wave a workgroup: the barrier between the lanes' rows and lane 0's chains is the wave's own
+
+// of the set bits b of w: their number, the sum of b and the sum of b^2, from popcounts under the six masks "bit k of b is set"
+__device__ __forceinline__ void foot_word_sums(uint64_t w, uint32_t &n, uint32_t &s1, uint32_t &s2)
+{
+    constexpr uint64_t M[6] = {0xAAAAAAAAAAAAAAAAull, 0xCCCCCCCCCCCCCCCCull, 0xF0F0F0F0F0F0F0F0ull, 0xFF00FF00FF00FF00ull, 0xFFFF0000FFFF0000ull,
+                               0xFFFFFFFF00000000ull};
+    n = (uint32_t)__popcll(w);
+    s1 = 0; s2 = 0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const uint64_t wk = w & M[k];
+        const uint32_t pk = (uint32_t)__popcll(wk);
+        s1 += pk << k;
+        s2 += pk << (2 * k);
+#pragma unroll
+        for (int j = k + 1; j < 6; ++j) s2 += (uint32_t)__popcll(wk & M[j]) << (k + j + 1);
+    }
+}
+
+__global__ __launch_bounds__(GEOM_THREADS) void k_foot_geom(const FootLine *__restrict__ lines, int n_lines, const GeomSlot *__restrict__ slots,
+                                                            const uint64_t *__restrict__ feet, uint64_t *__restrict__ scratch, GeomRec *__restrict__ recs,
+                                                            int32_t *__restrict__ xy)
+{
+    __shared__ uint64_t s_x[GEOM_LDS_ROWS];
+    const int lane = threadIdx.x;
+    for (int a = blockIdx.x; a < n_lines; a += gridDim.x) {
+        const FootLine L = lines[a];
+        const GeomSlot S = slots[a];
+        if (L.w <= 0 || L.h <= 0) {
+            if (lane == 0) recs[a] = GeomRec{0, 0, 0, 0, 0, 0, 0};
+            continue;
+        }
+        const int h = L.h;
+        // X[y] = xl | (xr + 1) << 32 relative to the box, 0xFFFFFFFF for a row without a bit; word h is the chains' last entry
+        uint64_t *X = h + 1 <= GEOM_LDS_ROWS ? s_x : scratch + S.x_first;
+        uint64_t n = 0, sx = 0, sy = 0, sxx = 0, sxy = 0, syy = 0;
+        for (int r = lane; r < h; r += 64) {
+            const uint64_t *row = feet + L.word_off + (uint64_t)r * L.pitch;
+            uint32_t xl = ~0u, xr = 0;
+            uint64_t cnt = 0, s1 = 0, s2 = 0;
+            for (uint32_t k = 0; k < L.pitch; ++k) {
+                const uint64_t w = row[k];
+                if (!w) continue;
+                if (xl == ~0u) xl = 64u * k + (uint32_t)__builtin_ctzll(w);
+                xr = 64u * k + 64u - (uint32_t)__builtin_clzll(w);
+                uint32_t p, b1, b2;
+                foot_word_sums(w, p, b1, b2);
+                const uint64_t xb = (uint64_t)L.x + 64u * k;
+                cnt += p; s1 += p * xb + b1; s2 += p * xb * xb + 2u * xb * b1 + b2;
+            }
+            X[r] = (uint64_t)xl | (uint64_t)xr << 32;
+            const uint64_t y = (uint64_t)L.y + (uint64_t)r;
+            n += cnt; sx += s1; sxx += s2; sy += cnt * y; sxy += s1 * y; syy += cnt * y * y;
+        }
+        n = foot_wave_sum(n); sx = foot_wave_sum(sx); sy = foot_wave_sum(sy); sxx = foot_wave_sum(sxx); sxy = foot_wave_sum(sxy); syy = foot_wave_sum(syy);
+        __syncthreads();
+        int nl = 0, nr = 0;
+        if (lane == 0) {
+            uint32_t *st = reinterpret_cast<uint32_t *>(X);
+            int64_t   sl = 0, sr = 0;
+            uint32_t  pl = ~0u, pr = 0;
+            for (int y = 0; y <= h; ++y) {
+                const uint64_t cur = y < h ? X[y] : 0xFFFFFFFFull;
+                const uint32_t cl = (uint32_t)cur, cr = (uint32_t)(cur >> 32);
+                if (cl != ~0u || pl != ~0u) {
+                    shape_hull_add<true>(st, nl, sl, y, min(cl, pl), true);
+                    shape_hull_add<false>(st + 1, nr, sr, y, max(cr, pr), true);
+                }
+                pl = cl; pr = cr;
+            }
+            recs[a] = GeomRec{(uint32_t)(nl + nr), (uint32_t)n, sx, sy, sxx, sxy, syy};
+        }
+        nl = __shfl(nl, 0); nr = __shfl(nr, 0);
+        __syncthreads();
+        // clockwise on screen from the smallest (y, x): the top of the left chain, the right chain downwards, the left chain upwards
+        const uint32_t *st = reinterpret_cast<const uint32_t *>(X);
+        for (int i = lane; i < nl + nr; i += 64) {
+            const uint32_t e = i == 0 ? st[0] : i <= nr ? st[2 * (i - 1) + 1] : st[2 * (nl + nr - i)];
+            int32_t *o = xy + 2 * ((size_t)S.pt_first + (size_t)i);
+            o[0] = L.x + (int32_t)(e & 0xFFFFu); o[1] = L.y + (int32_t)(e >> 16);
+        }
+        __syncthreads();        // (the wave's reads of X before the next line writes it)
+    }
+}
+
 void launch_line_foot(hipStream_t s, const FootJob *jobs, int n_jobs, const FootLine *lines, const TextMapCand *members, const uint16_t *tabs,
                       const uint32_t *bits, uint64_t *feet, FootStat *stat)
 {
@@ -195,4 +291,12 @@ void launch_foot_links(hipStream_t s, const FootLine *lines, int n_lines, const 
     if (n_lines <= 1) return;
     const dim3 grid((unsigned)std::min((n_lines + FOOT_THREADS / 64 - 1) / (FOOT_THREADS / 64), 1 << 16));
     hipLaunchKernelGGL(k_foot_links, grid, dim3(FOOT_THREADS), 0, s, lines, n_lines, range, list, feet, head, out, cap);
+}
+
+void launch_foot_geom(hipStream_t s, const FootLine *lines, int n_lines, const GeomSlot *slots, const uint64_t *feet, uint64_t *scratch, GeomRec *recs,
+                      int32_t *xy)
+{
+    if (n_lines <= 0) return;
+    const dim3 grid((unsigned)std::min(n_lines, 1 << 16));
+    hipLaunchKernelGGL(k_foot_geom, grid, dim3(GEOM_THREADS), 0, s, lines, n_lines, slots, feet, scratch, recs, xy);
 }

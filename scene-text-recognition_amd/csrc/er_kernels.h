@@ -160,5 +160,10 @@ void launch_foot_pairs(hipStream_t s, const FootLine *lines, int n_lines, const 
 // of the next adjacent frame; out / head as for launch_foot_pairs (a table and a head of their own)
 void launch_foot_links(hipStream_t s, const FootLine *lines, int n_lines, const FootRange *range, const uint32_t *list, const uint64_t *feet, FootHead *head,
                        FootPair *out, uint32_t cap);
+// launch_foot_geom (STR_ER_WANT_LINE_GEOM, str_er_feet_geom): one wave per line over its footprint in feet: the moments and the number
+// of hull vertices into recs[line], the vertices (absolute x, y pairs, in the order of str_er_line_geom) into xy from slots[line].pt_first
+// on; scratch: h + 1 words from slots[line].x_first on for every line with h + 1 > GEOM_LDS_ROWS (may be null when there is none)
+void launch_foot_geom(hipStream_t s, const FootLine *lines, int n_lines, const GeomSlot *slots, const uint64_t *feet, uint64_t *scratch, GeomRec *recs,
+                      int32_t *xy);
 
 } // namespace str_er

@@ -309,5 +309,18 @@ struct FootRange {
     uint32_t first, end;
 };
 static_assert(sizeof(FootRange) == 8, "FootRange layout (host and device)");
+// Per line, for k_foot_geom: where its hull vertices go (pt_first, in vertices: the host reserves 2 (h + 1) of them) and, for a line
+// taller than the kernel's LDS rows, where its row extents lie in the scratch words (x_first; h + 1 of them).
+struct GeomSlot {
+    uint32_t pt_first, x_first;
+};
+static_assert(sizeof(GeomSlot) == 8, "GeomSlot layout (host and device)");
+// What k_foot_geom leaves per line: the number of hull vertices and the moments of the footprint (str_er_line_geom)
+struct GeomRec {
+    uint32_t count, pixels;
+    uint64_t m10, m01, m20, m11, m02;
+};
+static_assert(sizeof(GeomRec) == 48, "GeomRec layout (host and device)");
+constexpr int GEOM_LDS_ROWS = 1024;         // k_foot_geom keeps the row extents of a line of up to GEOM_LDS_ROWS - 1 rows in LDS
 
 } // namespace str_er

@@ -29,6 +29,11 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
     const uint32_t sup = STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP;
     struct Rule { bool bad; int code; const char *msg; };
     const Rule rules[] = {
+        // STR_ER_WANT_LINE_GEOM rides on STR_ER_WANT_FRAME_LINES in the same way: refused without it and where it is refused, with a
+        // message that names this flag; with it the flag changes no verdict
+        {k.strip && any(STR_ER_WANT_LINE_GEOM), STR_ER_EINVAL, "STR_ER_WANT_LINE_GEOM is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_LINE_GEOM), STR_ER_EINVAL, "STR_ER_WANT_LINE_GEOM needs frames (not the per-plane calls)"},
+        {any(STR_ER_WANT_LINE_GEOM) && !any(STR_ER_WANT_FRAME_LINES), STR_ER_EINVAL, "STR_ER_WANT_LINE_GEOM needs STR_ER_WANT_FRAME_LINES"},
         // STR_ER_WANT_LINE_LINKS rides on STR_ER_WANT_FRAME_LINES: refused without it and where it is refused, first of all, so that the
         // refusal names this flag; with it the flag changes no verdict
         {k.strip && any(STR_ER_WANT_LINE_LINKS), STR_ER_EINVAL, "STR_ER_WANT_LINE_LINKS is not supported by the strip path (str_er_strip_merge)"},

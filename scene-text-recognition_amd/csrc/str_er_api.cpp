@@ -1345,12 +1345,13 @@ static int result_masks(const BatchRun &R, str_er_result *r, const uint32_t **d_
 static int frame_lines_result(const BatchRun &R, str_er_result *r, const uint32_t *d_mask_bits, const uint32_t *d_made_bits, std::vector<uint64_t> &made_word_off)
 {
     const bool links = (R.stages & STR_ER_WANT_LINE_LINKS) != 0;      // (the links across frames: in the same stage)
+    const bool geom = (R.stages & STR_ER_WANT_LINE_GEOM) != 0;        // (the geometry of the footprints: likewise)
     if (d_mask_bits) {
         made_word_off.resize(r->masks.size());
         for (size_t k = 0; k < r->masks.size(); ++k) made_word_off[k] = r->masks[k].word_off;
-        return frame_lines_phase(R.c, R.s, R.b, R.dp.qscale, d_mask_bits, &made_word_off, r, links);
+        return frame_lines_phase(R.c, R.s, R.b, R.dp.qscale, d_mask_bits, &made_word_off, r, links, geom);
     }
-    return frame_lines_phase(R.c, R.s, R.b, R.dp.qscale, d_made_bits, d_made_bits ? &made_word_off : nullptr, r, links);
+    return frame_lines_phase(R.c, R.s, R.b, R.dp.qscale, d_made_bits, d_made_bits ? &made_word_off : nullptr, r, links, geom);
 }
 
 // candidates carry the device kept slot; translated to the sorted node table through (key, level) -- or -1 without STR_ER_WANT_NODES
@@ -1578,6 +1579,9 @@ void str_er_destroy(str_er_ctx *c)
     if (c->d_foot_bits) (void)hipFree(c->d_foot_bits);
     if (c->d_link_out) (void)hipFree(c->d_link_out);
     if (c->h_link_out) (void)hipHostFree(c->h_link_out);
+    if (c->d_geom_out) (void)hipFree(c->d_geom_out);
+    if (c->h_geom_out) (void)hipHostFree(c->h_geom_out);
+    if (c->d_geom_x) (void)hipFree(c->d_geom_x);
     if (c->d_strip_out) (void)hipFree(c->d_strip_out);
     if (c->d_strip_in) (void)hipFree(c->d_strip_in);
     if (c->d_replay) (void)hipFree(c->d_replay);

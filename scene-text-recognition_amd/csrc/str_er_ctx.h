@@ -106,6 +106,10 @@ struct str_er_result {
         std::vector<uint32_t> bits;
     } edge_feet[2];
     bool have_line_links = false;
+    std::vector<str_er_line_geom> line_geoms;    // STR_ER_WANT_LINE_GEOM: the geometry of every line and of every frame line, and the hull vertices of both
+    std::vector<str_er_line_geom> frame_line_geoms;
+    std::vector<int32_t> geom_points;
+    bool have_line_geom = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -221,6 +225,10 @@ struct str_er_ctx {
     // words on the page-locked side); created by the first call that wants links, grown geometrically, never shrunk
     int32_t  link_num = 1, link_den = 2;
     uint8_t  *d_link_out = nullptr, *h_link_out = nullptr; size_t link_out_bytes = 0;
+    // STR_ER_WANT_LINE_GEOM / str_er_feet_geom: slots | records | hull vertices of k_foot_geom, and the scratch rows of lines taller than
+    // its LDS; created by the first call that wants the geometry, grown geometrically, never shrunk
+    uint8_t  *d_geom_out = nullptr, *h_geom_out = nullptr; size_t geom_out_bytes = 0;
+    uint64_t *d_geom_x = nullptr; size_t geom_x_words = 0;
     uint8_t *d_strip_out = nullptr, *d_strip_in = nullptr; size_t strip_out_cap = 0, strip_in_cap = 0;   // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -481,8 +489,9 @@ struct SampleTabs {
 // STR_ER_WANT_FRAME_LINES in run_batch: the feet, pairs and frame lines of the lines of r.  d_mask_bits / word_off: mask words of this
 // call still on the device and the first word of every candidate's (UINT64_MAX: none), or null: then the members' masks are made here
 // links: STR_ER_WANT_LINE_LINKS as well (the links, tracks and edge feet of r, in the same stage)
+// geom: STR_ER_WANT_LINE_GEOM as well (the geometry of the lines and frame lines of r, k_foot_geom in the same stage)
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
-                      str_er_result *r, bool links = false);
+                      str_er_result *r, bool links = false, bool geom = false);
 constexpr int MASK_MAX_WIDTH = 16384;       // widest box the mask kernels take (er_masks.inl: MASK_MAX_WPL words of 64 pixels per lane)
 // ---- defined in api_models.cpp
 int parse_cascade(str_er_ctx *c, HostCascade &hc, const char *text, size_t len);

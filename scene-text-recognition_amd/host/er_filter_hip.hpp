@@ -438,6 +438,39 @@ public:
         return out;
     }
 
+    // The convex hull, the moments and the oriented box of every text line and of every frame line (STR_ER_WANT_LINE_GEOM; the contract is
+    // at str_er_line_geom in include/str_er.h): one record per line of str_er_result_texts(), one per frame line, and the vertices
+    // (x, y pairs) that the first / count of both index.
+    struct LineGeoms {
+        std::vector<str_er_line_geom> lines, frame_lines;
+        std::vector<int32_t>          points;
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static LineGeoms line_geoms(const str_er_result *r)
+    {
+        LineGeoms out;
+        int32_t n = 0;
+        if (const str_er_line_geom *p = str_er_result_line_geoms(r, &n)) out.lines.assign(p, p + n);
+        if (const str_er_line_geom *p = str_er_result_frame_line_geoms(r, &n)) out.frame_lines.assign(p, p + n);
+        if (const int32_t *p = str_er_result_geom_points(r, &n)) out.points.assign(p, p + 2 * (size_t)n);
+        return out;
+    }
+    // the geometry of footprints of one frame size on the GPU (str_er_feet_geom): feet and bits as str_er_link_feet takes them
+    LineGeoms feet_geom(int32_t width, int32_t height, const std::vector<str_er_line_foot> &feet, const std::vector<uint32_t> &bits)
+    {
+        LineGeoms out;
+        out.lines.resize(feet.size());
+        int64_t cap = 1;                                  // (a hull has at most two vertices per height 0 .. h: one call)
+        for (const str_er_line_foot &f : feet) cap += 2 * ((int64_t)(f.h > 0 ? f.h : 0) + 1);
+        if (cap > INT32_MAX) cap = INT32_MAX;
+        out.points.resize(2 * (size_t)cap);
+        int32_t n = 0;
+        check(str_er_feet_geom(ctx_.get(), width, height, feet.empty() ? nullptr : feet.data(), bits.empty() ? nullptr : bits.data(), (int32_t)feet.size(),
+                               out.lines.empty() ? nullptr : out.lines.data(), out.points.data(), (int32_t)cap, &n));
+        out.points.resize(2 * (size_t)n);
+        return out;
+    }
+
     // The text lines of consecutive frames linked into text tracks (STR_ER_WANT_LINE_LINKS; the contract is at str_er_line_link in
     // include/str_er.h): the overlaps across adjacent frames, the track of every line of str_er_result_texts(), the tracks, the line
     // indices their first / count index, and the footprints of the lines of the first ([0]) and of the last frame ([1]).
