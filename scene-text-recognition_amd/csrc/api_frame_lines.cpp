@@ -131,25 +131,101 @@ void sort_pairs(std::vector<FootPair> &v)
     std::sort(v.begin(), v.end(), [](const FootPair &p, const FootPair &q) { return p.a != q.a ? p.a < q.a : p.b < q.b; });
 }
 
-int grow_foot_bits(str_er_ctx *c, uint64_t words)
+// A counted table of FootPair behind a FootHead in a device / page-locked pair: the head at 0, the records from o_rec on (between them
+// the pairs' per-line statistics), and behind the records of the first pass `tail` more bytes of the page-locked side (the links' edge
+// words).  A pass: enqueue, the caller's wait, collect -- which asks for one more pass when the table was too small.
+struct PairTable {
+    PairBuf    &buf;
+    const char *what, *twice;         // the buffer's name, and the error of a second overflow
+    size_t      o_rec = sizeof(FootHead);
+    size_t      cap = 0;
+    bool        grown = false;
+    uint32_t    n_candidates = 0;
+    size_t      bytes_back = 0;
+
+    size_t back() const { return o_rec + sizeof(FootPair) * cap; }         // what a pass copies back: the head and cap records
+    // the first capacity for a launch over n_lines lines: max(1024, 4 n_lines) records, and as many as the buffer already holds
+    int reserve(str_er_ctx *c, size_t n_lines, size_t tail = 0)
+    {
+        cap = std::max<size_t>(1024, 4 * n_lines);
+        if (buf.size() > o_rec + tail) cap = std::max(cap, (buf.size() - o_rec - tail) / sizeof(FootPair));
+        return buf.ensure(c, back() + tail, what);
+    }
+    // launch(head, records, cap): the kernel that counts into the zeroed head and fills the records
+    template <typename Launch> int enqueue(str_er_ctx *c, hipStream_t s, Launch launch)
+    {
+        HIP_TRY(c, hipMemsetAsync(buf.d(), 0, sizeof(FootHead), s));
+        launch(buf.d<FootHead>(), reinterpret_cast<FootPair *>(buf.d() + o_rec), (uint32_t)cap);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(buf.h(), buf.d(), back(), hipMemcpyDeviceToHost, s));
+        bytes_back += back();
+        return STR_ER_OK;
+    }
+    // after the wait: the records into out; again: there were more than the table holds -- it now holds them all (whatever else was in
+    // the buffer is lost), and the pass is to run once more (what it reads is still on the device)
+    int collect(str_er_ctx *c, std::vector<FootPair> &out, bool &again)
+    {
+        FootHead head;
+        std::memcpy(&head, buf.h(), sizeof head);
+        n_candidates = head.n_candidates;
+        again = head.n_pairs > cap;
+        if (!again) {
+            out.resize(head.n_pairs);
+            if (head.n_pairs) std::memcpy(out.data(), buf.h() + o_rec, sizeof(FootPair) * head.n_pairs);
+            return STR_ER_OK;
+        }
+        if (grown) return fail(c, STR_ER_EHIP, twice);
+        grown = true;
+        cap = head.n_pairs;
+        return buf.ensure(c, back(), what);
+    }
+};
+
+PairTable link_table(str_er_ctx *c) { return {c->link_out, "line link output", "line links: the link table overflowed twice (internal error)"}; }
+
+// A caller's feet and footprints (str_er_link_feet, str_er_feet_geom), in two steps.  The boxes of all feet; who: in front of "line t"
+int check_foot_boxes(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, int32_t n, const char *who)
 {
-    if (words <= c->foot_bits_words) return STR_ER_OK;
-    const size_t get = std::max<size_t>((size_t)words, 2 * c->foot_bits_words);
-    if (c->d_foot_bits) { (void)hipFree(c->d_foot_bits); c->d_foot_bits = nullptr; }
-    c->foot_bits_words = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&c->d_foot_bits), 8 * get) != hipSuccess)
-        return fail(c, STR_ER_ENOMEM, "hipMalloc (line footprints, " + std::to_string(8 * get) + " bytes)");
-    c->foot_bits_words = get;
+    for (int32_t t = 0; t < n; ++t) {
+        const str_er_line_foot &F = feet[t];
+        const std::string line = who + ("line " + std::to_string(t));
+        if (F.w < 0 || F.h < 0 || (F.w == 0) != (F.h == 0)) return fail(c, STR_ER_EINVAL, line + ": bad foot box");
+        if (F.w == 0) {
+            if (F.pixels) return fail(c, STR_ER_EINVAL, line + ": pixels in an empty foot box");
+            continue;
+        }
+        if (F.x < 0 || F.y < 0 || (int64_t)F.x + F.w > W || (int64_t)F.y + F.h > H) return fail(c, STR_ER_EINVAL, line + ": the foot box leaves the frame");
+    }
     return STR_ER_OK;
 }
 
-// the link table of a launch over n_lines lines, behind the head and `tail` more bytes of the page-locked side: at least
-// max(1024, 4 n_lines) records, and as many as the buffer already holds
-int link_table(str_er_ctx *c, size_t n_lines, size_t tail, size_t &cap)
+// ... then the footprints (rows of 32-bit words behind one another in bits) appended to lines / words as rows of 64-bit words, every
+// one checked against its foot
+int pack_footprints(str_er_ctx *c, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, std::vector<FootLine> &lines, std::vector<uint64_t> &words)
 {
-    cap = std::max<size_t>(1024, 4 * n_lines);
-    if (c->link_out_bytes > sizeof(FootHead) + tail) cap = std::max(cap, (c->link_out_bytes - sizeof(FootHead) - tail) / sizeof(FootPair));
-    return grow_pair(c, c->d_link_out, c->h_link_out, c->link_out_bytes, sizeof(FootHead) + sizeof(FootPair) * cap + tail, "line link output");
+    const uint32_t *at = bits;
+    for (int32_t t = 0; t < n; ++t) {
+        const str_er_line_foot &F = feet[t];
+        FootLine L{};
+        L.word_off = words.size();
+        if (F.w != 0) {
+            if (!at) return fail(c, STR_ER_EINVAL, "footprint bits missing");
+            L.x = F.x; L.y = F.y; L.w = F.w; L.h = F.h; L.pitch = ((uint32_t)F.w + 63u) / 64u; L.count = 1;
+            const uint32_t pitch32 = ((uint32_t)F.w + 31u) / 32u, tail = (uint32_t)F.w & 31u;
+            uint64_t px = 0;
+            for (int32_t rr = 0; rr < F.h; ++rr, at += pitch32) {
+                if (tail && (at[pitch32 - 1] >> tail)) return fail(c, STR_ER_EINVAL, "a footprint has a bit set past its row's width");
+                for (uint32_t k = 0; k < L.pitch; ++k) {
+                    const uint64_t v = (uint64_t)at[2 * k] | (2 * k + 1 < pitch32 ? (uint64_t)at[2 * k + 1] << 32 : 0ull);
+                    px += (uint64_t)__builtin_popcountll(v);
+                    words.push_back(v);
+                }
+            }
+            if (px != F.pixels) return fail(c, STR_ER_EINVAL, "a foot's pixels are not the number of bits set in its footprint");
+        }
+        lines.push_back(L);
+    }
+    return STR_ER_OK;
 }
 
 constexpr int32_t GEOM_MAX_BOX = 16384;          // the widest / tallest foot box whose moments are promised not to overflow
@@ -161,7 +237,7 @@ struct GeomPlan {
     size_t n_lines = 0, n_pts = 0, x_words = 0, o_rec = 0, o_xy = 0, bytes = 0;
 };
 
-// the slots uploaded, the kernel and the copy back enqueued on s behind whatever made the footprints in c->d_foot_bits; geom_collect after the wait
+// the slots uploaded, the kernel and the copy back enqueued on s behind whatever made the footprints in c->foot_bits.d<uint64_t>(); geom_collect after the wait
 int geom_enqueue(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const FootLine *d_lines, GeomPlan &P)
 {
     P.n_lines = lines.size();
@@ -179,22 +255,14 @@ int geom_enqueue(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &line
     if (P.n_lines == 0) return STR_ER_OK;
     P.o_rec = align_up(sizeof(GeomSlot) * P.n_lines, 256); P.o_xy = align_up(P.o_rec + sizeof(GeomRec) * P.n_lines, 256);
     P.bytes = P.o_xy + 8 * P.n_pts;
-    int rc = grow_pair(c, c->d_geom_out, c->h_geom_out, c->geom_out_bytes, P.bytes, "line geometry output");
-    if (rc != STR_ER_OK) return rc;
-    if (P.x_words > c->geom_x_words) {
-        if (c->d_geom_x) { (void)hipFree(c->d_geom_x); c->d_geom_x = nullptr; }
-        const size_t get = std::max(P.x_words, 2 * c->geom_x_words);
-        c->geom_x_words = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_geom_x), 8 * get) != hipSuccess)
-            return fail(c, STR_ER_ENOMEM, "hipMalloc (line geometry rows, " + std::to_string(8 * get) + " bytes)");
-        c->geom_x_words = get;
-    }
-    std::memcpy(c->h_geom_out, P.slots.data(), sizeof(GeomSlot) * P.n_lines);
-    HIP_TRY(c, hipMemcpyAsync(c->d_geom_out, c->h_geom_out, sizeof(GeomSlot) * P.n_lines, hipMemcpyHostToDevice, s));
-    launch_foot_geom(s, d_lines, (int)P.n_lines, reinterpret_cast<const GeomSlot *>(c->d_geom_out), c->d_foot_bits, c->d_geom_x,
-                     reinterpret_cast<GeomRec *>(c->d_geom_out + P.o_rec), reinterpret_cast<int32_t *>(c->d_geom_out + P.o_xy));
+    int rc = c->geom_out.ensure(c, P.bytes, "line geometry output");
+    if (rc != STR_ER_OK || (rc = c->geom_x.ensure(c, 8 * P.x_words, "line geometry rows")) != STR_ER_OK) return rc;
+    std::memcpy(c->geom_out.h(), P.slots.data(), sizeof(GeomSlot) * P.n_lines);
+    HIP_TRY(c, hipMemcpyAsync(c->geom_out.d(), c->geom_out.h(), sizeof(GeomSlot) * P.n_lines, hipMemcpyHostToDevice, s));
+    launch_foot_geom(s, d_lines, (int)P.n_lines, reinterpret_cast<const GeomSlot *>(c->geom_out.d()), c->foot_bits.d<uint64_t>(), c->geom_x.d<uint64_t>(),
+                     reinterpret_cast<GeomRec *>(c->geom_out.d() + P.o_rec), reinterpret_cast<int32_t *>(c->geom_out.d() + P.o_xy));
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_geom_out + P.o_rec, c->d_geom_out + P.o_rec, P.bytes - P.o_rec, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(c->geom_out.h() + P.o_rec, c->geom_out.d() + P.o_rec, P.bytes - P.o_rec, hipMemcpyDeviceToHost, s));
     return STR_ER_OK;
 }
 
@@ -205,12 +273,12 @@ int geom_collect(str_er_ctx *c, const GeomPlan &P, std::vector<str_er_line_geom>
     for (size_t t = 0; t < P.n_lines; ++t) {
         str_er_line_geom &G = geoms[t];
         GeomRec R;
-        std::memcpy(&R, c->h_geom_out + P.o_rec + sizeof(GeomRec) * t, sizeof R);
+        std::memcpy(&R, c->geom_out.h() + P.o_rec + sizeof(GeomRec) * t, sizeof R);
         G.edge = -1;
         if (R.count == 0) continue;
         const uint32_t first = P.slots[t].pt_first;
         if (R.count < 4 || (size_t)first + R.count > P.n_pts) return fail(c, STR_ER_EHIP, "line geometry: a hull outside its vertices (internal error)");
-        const int32_t *src = reinterpret_cast<const int32_t *>(c->h_geom_out + P.o_xy) + 2 * (size_t)first;
+        const int32_t *src = reinterpret_cast<const int32_t *>(c->geom_out.h() + P.o_xy) + 2 * (size_t)first;
         G.first = (uint32_t)(xy.size() / 2); G.count = R.count;
         xy.insert(xy.end(), src, src + 2 * (size_t)R.count);
         G.pixels = R.pixels; G.m10 = R.m10; G.m01 = R.m01; G.m20 = R.m20; G.m11 = R.m11; G.m02 = R.m02;
@@ -234,103 +302,68 @@ int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t
     const size_t o_mem = align_up(o_list + 4 * T.list.size(), 256), o_tab = align_up(o_mem + sizeof(TextMapCand) * T.members.size(), 256);
     const size_t o_rng = LK ? align_up(o_tab + 2 * T.st.tabs.size(), 256) : 0;
     const size_t tab_need = LK ? o_rng + sizeof(FootRange) * n_lines : o_tab + 2 * T.st.tabs.size();
-    int rc = grow_pair(c, c->d_foot_tab, c->h_foot_tab, c->foot_tab_bytes, tab_need, "frame line tables");
-    if (rc != STR_ER_OK) return rc;
-    if ((rc = grow_foot_bits(c, T.words)) != STR_ER_OK) return rc;
-    const size_t o_stat = sizeof(FootHead), o_pairs = o_stat + sizeof(FootStat) * n_lines;
-    size_t cap = std::max<size_t>(1024, 4 * n_lines);
-    if (c->foot_out_bytes > o_pairs) cap = std::max(cap, (c->foot_out_bytes - o_pairs) / sizeof(FootPair));
-    if ((rc = grow_pair(c, c->d_foot_out, c->h_foot_out, c->foot_out_bytes, o_pairs + sizeof(FootPair) * cap, "frame line output")) != STR_ER_OK) return rc;
-    std::memcpy(c->h_foot_tab, T.lines.data(), sizeof(FootLine) * n_lines);
-    if (!T.jobs.empty()) std::memcpy(c->h_foot_tab + o_jobs, T.jobs.data(), sizeof(FootJob) * T.jobs.size());
-    std::memcpy(c->h_foot_tab + o_list, T.list.data(), 4 * T.list.size());
-    std::memcpy(c->h_foot_tab + o_mem, T.members.data(), sizeof(TextMapCand) * T.members.size());
-    std::memcpy(c->h_foot_tab + o_tab, T.st.tabs.data(), 2 * T.st.tabs.size());
+    int rc = c->foot_tab.ensure(c, tab_need, "frame line tables");
+    if (rc != STR_ER_OK || (rc = c->foot_bits.ensure(c, 8 * (size_t)T.words, "line footprints")) != STR_ER_OK) return rc;
+    const size_t o_stat = sizeof(FootHead);
+    PairTable PT{c->foot_out, "frame line output", "frame lines: the pair table overflowed twice (internal error)", o_stat + sizeof(FootStat) * n_lines};
+    PairTable LT = link_table(c);
+    if ((rc = PT.reserve(c, n_lines)) != STR_ER_OK) return rc;
+    std::memcpy(c->foot_tab.h(), T.lines.data(), sizeof(FootLine) * n_lines);
+    if (!T.jobs.empty()) std::memcpy(c->foot_tab.h() + o_jobs, T.jobs.data(), sizeof(FootJob) * T.jobs.size());
+    std::memcpy(c->foot_tab.h() + o_list, T.list.data(), 4 * T.list.size());
+    std::memcpy(c->foot_tab.h() + o_mem, T.members.data(), sizeof(TextMapCand) * T.members.size());
+    std::memcpy(c->foot_tab.h() + o_tab, T.st.tabs.data(), 2 * T.st.tabs.size());
     // the links: the edge frames' words (one range when the call is one frame) lie behind the link table on the page-locked side
     const bool   one_edge = LK && T.edge_lo[0] == T.edge_lo[1] && T.edge_hi[0] == T.edge_hi[1];
     const size_t edge_n[2] = {LK ? (size_t)(T.edge_hi[0] - T.edge_lo[0]) : 0, LK && !one_edge ? (size_t)(T.edge_hi[1] - T.edge_lo[1]) : 0};
-    size_t lcap = 0;
     if (LK) {
         LK->edge_bytes = 8 * (edge_n[0] + edge_n[1]);
-        if ((rc = link_table(c, n_lines, LK->edge_bytes, lcap)) != STR_ER_OK) return rc;
-        std::memcpy(c->h_foot_tab + o_rng, T.range.data(), sizeof(FootRange) * n_lines);
+        if ((rc = LT.reserve(c, n_lines, LK->edge_bytes)) != STR_ER_OK) return rc;
+        std::memcpy(c->foot_tab.h() + o_rng, T.range.data(), sizeof(FootRange) * n_lines);
     }
-    HIP_TRY(c, hipMemcpyAsync(c->d_foot_tab, c->h_foot_tab, tab_need, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(c->d_foot_out, 0, o_pairs, s));
-    if (LK) HIP_TRY(c, hipMemsetAsync(c->d_link_out, 0, sizeof(FootHead), s));
-    const FootLine *d_lines = reinterpret_cast<const FootLine *>(c->d_foot_tab);
-    const uint32_t *d_list = reinterpret_cast<const uint32_t *>(c->d_foot_tab + o_list);
-    launch_line_foot(s, reinterpret_cast<const FootJob *>(c->d_foot_tab + o_jobs), (int)T.jobs.size(), d_lines,
-                     reinterpret_cast<const TextMapCand *>(c->d_foot_tab + o_mem), reinterpret_cast<const uint16_t *>(c->d_foot_tab + o_tab), d_bits,
-                     c->d_foot_bits, reinterpret_cast<FootStat *>(c->d_foot_out + o_stat));
+    HIP_TRY(c, hipMemcpyAsync(c->foot_tab.d(), c->foot_tab.h(), tab_need, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemsetAsync(c->foot_out.d() + o_stat, 0, sizeof(FootStat) * n_lines, s));
+    const FootLine *d_lines = reinterpret_cast<const FootLine *>(c->foot_tab.d());
+    const uint32_t *d_list = reinterpret_cast<const uint32_t *>(c->foot_tab.d() + o_list);
+    uint64_t       *feet = c->foot_bits.d<uint64_t>();
+    launch_line_foot(s, reinterpret_cast<const FootJob *>(c->foot_tab.d() + o_jobs), (int)T.jobs.size(), d_lines,
+                     reinterpret_cast<const TextMapCand *>(c->foot_tab.d() + o_mem), reinterpret_cast<const uint16_t *>(c->foot_tab.d() + o_tab), d_bits,
+                     feet, reinterpret_cast<FootStat *>(c->foot_out.d() + o_stat));
     HIP_TRY(c, hipGetLastError());
     if (LK) {
-        uint8_t *h_edge = c->h_link_out + sizeof(FootHead) + sizeof(FootPair) * lcap;
+        uint8_t *h_edge = c->link_out.h() + LT.back();
         for (int e = 0; e < 2; ++e) {
-            if (edge_n[e]) HIP_TRY(c, hipMemcpyAsync(h_edge, c->d_foot_bits + T.edge_lo[e], 8 * edge_n[e], hipMemcpyDeviceToHost, s));
+            if (edge_n[e]) HIP_TRY(c, hipMemcpyAsync(h_edge, feet + T.edge_lo[e], 8 * edge_n[e], hipMemcpyDeviceToHost, s));
             h_edge += 8 * edge_n[e];
         }
     }
     if (GP && (rc = geom_enqueue(c, s, T.lines, d_lines, *GP)) != STR_ER_OK) return rc;
+    const auto launch_pairs = [&](FootHead *head, FootPair *out, uint32_t cap) { launch_foot_pairs(s, d_lines, (int)n_lines, d_list, feet, head, out, cap); };
+    const auto launch_links = [&](FootHead *head, FootPair *out, uint32_t cap) {
+        launch_foot_links(s, d_lines, (int)n_lines, reinterpret_cast<const FootRange *>(c->foot_tab.d() + o_rng), d_list, feet, head, out, cap);
+    };
     bool run_pairs = true, run_links = LK != nullptr;
-    for (int pass = 0; run_pairs || run_links; ++pass) {
-        if (run_pairs) launch_foot_pairs(s, d_lines, (int)n_lines, d_list, c->d_foot_bits, reinterpret_cast<FootHead *>(c->d_foot_out),
-                                         reinterpret_cast<FootPair *>(c->d_foot_out + o_pairs), (uint32_t)cap);
-        if (run_links) launch_foot_links(s, d_lines, (int)n_lines, reinterpret_cast<const FootRange *>(c->d_foot_tab + o_rng), d_list, c->d_foot_bits,
-                                         reinterpret_cast<FootHead *>(c->d_link_out), reinterpret_cast<FootPair *>(c->d_link_out + sizeof(FootHead)),
-                                         (uint32_t)lcap);
-        HIP_TRY(c, hipGetLastError());
-        if (in_batch && pass == 0) rec(c, "frame_lines");          // (the call's one profiling event of the stage)
+    for (bool first = true; run_pairs || run_links; first = false) {
         // what comes back: the counters, the statistics and the pairs in one copy (the table is sized for four pairs a line: all of it is a
         // few hundred KB at most for a batch; the host reads as many as the counter says); the links' counters and table in another
-        const size_t back = o_pairs + sizeof(FootPair) * cap, lback = sizeof(FootHead) + sizeof(FootPair) * lcap;
-        if (run_pairs) HIP_TRY(c, hipMemcpyAsync(c->h_foot_out, c->d_foot_out, back, hipMemcpyDeviceToHost, s));
-        if (run_links) HIP_TRY(c, hipMemcpyAsync(c->h_link_out, c->d_link_out, lback, hipMemcpyDeviceToHost, s));
+        if (run_pairs && (rc = PT.enqueue(c, s, launch_pairs)) != STR_ER_OK) return rc;
+        if (run_links && (rc = LT.enqueue(c, s, launch_links)) != STR_ER_OK) return rc;
+        if (in_batch && first) rec(c, "frame_lines");          // (the call's one profiling event of the stage)
         HIP_TRY(c, wait_stream(c, s));
-        if (pass == 0) std::memcpy(O.stat.data(), c->h_foot_out + o_stat, sizeof(FootStat) * n_lines);
-        if (pass == 0 && LK) {         // (before the link table may grow: the edge words lie in the same buffer)
-            const uint8_t *h_edge = c->h_link_out + lback;
+        if (first) std::memcpy(O.stat.data(), c->foot_out.h() + o_stat, sizeof(FootStat) * n_lines);
+        if (first && LK) {         // (before the link table may grow: the edge words lie in the same buffer)
+            const uint8_t *h_edge = c->link_out.h() + LT.back();
             LK->edge[0].resize(edge_n[0]);
             if (edge_n[0]) std::memcpy(LK->edge[0].data(), h_edge, 8 * edge_n[0]);
             LK->edge[1].resize(edge_n[1]);
             if (edge_n[1]) std::memcpy(LK->edge[1].data(), h_edge + 8 * edge_n[0], 8 * edge_n[1]);
             if (one_edge) LK->edge[1] = LK->edge[0];
         }
-        if (run_pairs) {
-            O.bytes_back += back;
-            FootHead head;
-            std::memcpy(&head, c->h_foot_out, sizeof head);
-            O.n_candidates = head.n_candidates;
-            if (head.n_pairs <= cap) {
-                O.pairs.resize(head.n_pairs);
-                if (head.n_pairs) std::memcpy(O.pairs.data(), c->h_foot_out + o_pairs, sizeof(FootPair) * head.n_pairs);
-                run_pairs = false;
-            } else {
-                if (pass > 0) return fail(c, STR_ER_EHIP, "frame lines: the pair table overflowed twice (internal error)");
-                // more pairs than the table holds: a table for all of them, and the pair pass once more (the footprints are still on the device)
-                cap = head.n_pairs;
-                if ((rc = grow_pair(c, c->d_foot_out, c->h_foot_out, c->foot_out_bytes, o_pairs + sizeof(FootPair) * cap, "frame line output")) != STR_ER_OK) return rc;
-                HIP_TRY(c, hipMemsetAsync(c->d_foot_out, 0, o_pairs, s));
-            }
-        }
-        if (run_links) {
-            LK->bytes_back += lback;
-            FootHead head;
-            std::memcpy(&head, c->h_link_out, sizeof head);
-            LK->n_candidates = head.n_candidates;
-            if (head.n_pairs <= lcap) {
-                LK->links.resize(head.n_pairs);
-                if (head.n_pairs) std::memcpy(LK->links.data(), c->h_link_out + sizeof(FootHead), sizeof(FootPair) * head.n_pairs);
-                run_links = false;
-            } else {
-                if (pass > 0) return fail(c, STR_ER_EHIP, "line links: the link table overflowed twice (internal error)");
-                lcap = head.n_pairs;        // (the same rule: a table for all of them, and the link pass once more)
-                if ((rc = grow_pair(c, c->d_link_out, c->h_link_out, c->link_out_bytes, sizeof(FootHead) + sizeof(FootPair) * lcap, "line link output")) != STR_ER_OK)
-                    return rc;
-                HIP_TRY(c, hipMemsetAsync(c->d_link_out, 0, sizeof(FootHead), s));
-            }
-        }
+        if (run_pairs && (rc = PT.collect(c, O.pairs, run_pairs)) != STR_ER_OK) return rc;
+        if (run_links && (rc = LT.collect(c, LK->links, run_links)) != STR_ER_OK) return rc;
     }
+    O.n_candidates = PT.n_candidates; O.bytes_back = PT.bytes_back;
+    if (LK) { LK->n_candidates = LT.n_candidates; LK->bytes_back = LT.bytes_back; }
     sort_pairs(O.pairs);
     if (LK) sort_pairs(LK->links);
     return STR_ER_OK;
@@ -675,7 +708,7 @@ try {
     if (bits && out_words) {
         // the footprints back as they lie on the device (64-bit words over the union of the pre-image boxes), cut to the foot boxes
         std::vector<uint64_t> dev((size_t)T.words);
-        HIP_TRY(c, hipMemcpy(dev.data(), c->d_foot_bits, 8 * (size_t)T.words, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(dev.data(), c->foot_bits.d<uint64_t>(), 8 * (size_t)T.words, hipMemcpyDeviceToHost));
         std::vector<uint32_t> cut;
         cut.reserve((size_t)out_words);
         for (int32_t t = 0; t < n_lines; ++t) foot_rows32(dev.data() + T.lines[(size_t)t].word_off, T.lines[(size_t)t], ft[(size_t)t], cut);
@@ -765,43 +798,11 @@ try {
         return fail(c, STR_ER_EINVAL, "bad arguments");
     // the two sets as one table of lines, a's first, their footprints as rows of 64-bit words; every footprint checked against its foot
     const size_t n_lines = (size_t)n_a + (size_t)n_b;
-    std::vector<FootLine> lines(n_lines, FootLine{});
+    std::vector<FootLine> lines;
     std::vector<uint64_t> words;
-    for (size_t t = 0; t < n_lines; ++t) {
-        const bool in_a = t < (size_t)n_a;
-        const str_er_line_foot &F = in_a ? feet_a[t] : feet_b[t - (size_t)n_a];
-        const std::string who = std::string("set ") + (in_a ? "a" : "b") + ", line " + std::to_string(in_a ? t : t - (size_t)n_a);
-        if (F.w < 0 || F.h < 0 || (F.w == 0) != (F.h == 0)) return fail(c, STR_ER_EINVAL, who + ": bad foot box");
-        FootLine &L = lines[t];
-        L.word_off = words.size();
-        if (F.w == 0) {
-            if (F.pixels) return fail(c, STR_ER_EINVAL, who + ": pixels in an empty foot box");
-            continue;
-        }
-        if (F.x < 0 || F.y < 0 || (int64_t)F.x + F.w > W || (int64_t)F.y + F.h > H) return fail(c, STR_ER_EINVAL, who + ": the foot box leaves the frame");
-    }
-    const uint32_t *src[2] = {bits_a, bits_b};
-    for (size_t t = 0; t < n_lines; ++t) {
-        const bool in_a = t < (size_t)n_a;
-        const str_er_line_foot &F = in_a ? feet_a[t] : feet_b[t - (size_t)n_a];
-        if (F.w == 0) continue;
-        const uint32_t *&at = src[in_a ? 0 : 1];
-        if (!at) return fail(c, STR_ER_EINVAL, "footprint bits missing");
-        FootLine &L = lines[t];
-        L.x = F.x; L.y = F.y; L.w = F.w; L.h = F.h; L.pitch = ((uint32_t)F.w + 63u) / 64u; L.count = 1;
-        L.word_off = words.size();
-        const uint32_t pitch32 = ((uint32_t)F.w + 31u) / 32u, tail = (uint32_t)F.w & 31u;
-        uint64_t px = 0;
-        for (int32_t rr = 0; rr < F.h; ++rr, at += pitch32) {
-            if (tail && (at[pitch32 - 1] >> tail)) return fail(c, STR_ER_EINVAL, "a footprint has a bit set past its row's width");
-            for (uint32_t k = 0; k < L.pitch; ++k) {
-                const uint64_t v = (uint64_t)at[2 * k] | (2 * k + 1 < pitch32 ? (uint64_t)at[2 * k + 1] << 32 : 0ull);
-                px += (uint64_t)__builtin_popcountll(v);
-                words.push_back(v);
-            }
-        }
-        if (px != F.pixels) return fail(c, STR_ER_EINVAL, "a foot's pixels are not the number of bits set in its footprint");
-    }
+    int rc = check_foot_boxes(c, W, H, feet_a, n_a, "set a, ");
+    if (rc != STR_ER_OK || (rc = check_foot_boxes(c, W, H, feet_b, n_b, "set b, ")) != STR_ER_OK) return rc;
+    if ((rc = pack_footprints(c, feet_a, bits_a, n_a, lines, words)) != STR_ER_OK || (rc = pack_footprints(c, feet_b, bits_b, n_b, lines, words)) != STR_ER_OK) return rc;
     *n_pairs = 0;
     if (n_a == 0 || n_b == 0 || words.empty()) return STR_ER_OK;
     HIP_TRY(c, hipSetDevice(c->prm.device));
@@ -810,36 +811,25 @@ try {
     for (int32_t i = 0; i < n_a; ++i) range[(size_t)i] = FootRange{0, (uint32_t)n_b};
     std::iota(list.begin(), list.end(), (uint32_t)n_a);
     const size_t o_list = align_up(sizeof(FootLine) * n_lines, 256), o_rng = align_up(o_list + 4 * list.size(), 256), tab_need = o_rng + sizeof(FootRange) * n_lines;
-    int rc = grow_pair(c, c->d_foot_tab, c->h_foot_tab, c->foot_tab_bytes, tab_need, "frame line tables");
-    if (rc != STR_ER_OK) return rc;
-    if ((rc = grow_foot_bits(c, words.size())) != STR_ER_OK) return rc;
-    size_t cap = 0;
-    if ((rc = link_table(c, n_lines, 0, cap)) != STR_ER_OK) return rc;
+    PairTable LT = link_table(c);
+    if ((rc = c->foot_tab.ensure(c, tab_need, "frame line tables")) != STR_ER_OK || (rc = c->foot_bits.ensure(c, 8 * words.size(), "line footprints")) != STR_ER_OK ||
+        (rc = LT.reserve(c, n_lines)) != STR_ER_OK)
+        return rc;
     hipStream_t s = c->stream;
-    std::memcpy(c->h_foot_tab, lines.data(), sizeof(FootLine) * n_lines);
-    std::memcpy(c->h_foot_tab + o_list, list.data(), 4 * list.size());
-    std::memcpy(c->h_foot_tab + o_rng, range.data(), sizeof(FootRange) * n_lines);
-    HIP_TRY(c, hipMemcpyAsync(c->d_foot_tab, c->h_foot_tab, tab_need, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->d_foot_bits, words.data(), 8 * words.size(), hipMemcpyHostToDevice, s));      // (words lives until the wait below)
+    std::memcpy(c->foot_tab.h(), lines.data(), sizeof(FootLine) * n_lines);
+    std::memcpy(c->foot_tab.h() + o_list, list.data(), 4 * list.size());
+    std::memcpy(c->foot_tab.h() + o_rng, range.data(), sizeof(FootRange) * n_lines);
+    HIP_TRY(c, hipMemcpyAsync(c->foot_tab.d(), c->foot_tab.h(), tab_need, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->foot_bits.d<uint64_t>(), words.data(), 8 * words.size(), hipMemcpyHostToDevice, s));      // (words lives until the wait below)
+    const auto launch = [&](FootHead *head, FootPair *out, uint32_t cap) {
+        launch_foot_links(s, reinterpret_cast<const FootLine *>(c->foot_tab.d()), (int)n_lines, reinterpret_cast<const FootRange *>(c->foot_tab.d() + o_rng),
+                          reinterpret_cast<const uint32_t *>(c->foot_tab.d() + o_list), c->foot_bits.d<uint64_t>(), head, out, cap);
+    };
     std::vector<FootPair> got;
-    for (int pass = 0;; ++pass) {
-        HIP_TRY(c, hipMemsetAsync(c->d_link_out, 0, sizeof(FootHead), s));
-        launch_foot_links(s, reinterpret_cast<const FootLine *>(c->d_foot_tab), (int)n_lines, reinterpret_cast<const FootRange *>(c->d_foot_tab + o_rng),
-                          reinterpret_cast<const uint32_t *>(c->d_foot_tab + o_list), c->d_foot_bits, reinterpret_cast<FootHead *>(c->d_link_out),
-                          reinterpret_cast<FootPair *>(c->d_link_out + sizeof(FootHead)), (uint32_t)cap);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(c->h_link_out, c->d_link_out, sizeof(FootHead) + sizeof(FootPair) * cap, hipMemcpyDeviceToHost, s));
+    for (bool again = true; again;) {
+        if ((rc = LT.enqueue(c, s, launch)) != STR_ER_OK) return rc;
         HIP_TRY(c, wait_stream(c, s));
-        FootHead head;
-        std::memcpy(&head, c->h_link_out, sizeof head);
-        if (head.n_pairs <= cap) {
-            got.resize(head.n_pairs);
-            if (head.n_pairs) std::memcpy(got.data(), c->h_link_out + sizeof(FootHead), sizeof(FootPair) * head.n_pairs);
-            break;
-        }
-        if (pass > 0) return fail(c, STR_ER_EHIP, "line links: the link table overflowed twice (internal error)");
-        cap = head.n_pairs;        // (a table for all of them, and the pass once more)
-        if ((rc = grow_pair(c, c->d_link_out, c->h_link_out, c->link_out_bytes, sizeof(FootHead) + sizeof(FootPair) * cap, "line link output")) != STR_ER_OK) return rc;
+        if ((rc = LT.collect(c, got, again)) != STR_ER_OK) return rc;
     }
     sort_pairs(got);
     *n_pairs = (int32_t)got.size();
@@ -965,57 +955,31 @@ try {
     if (!c) return STR_ER_EINVAL;
     if (W < 1 || H < 1 || W > 65535 || H > 65535 || n < 0 || !n_points || (n > 0 && (!feet || !geoms)) || (xy && cap_points < 0))
         return fail(c, STR_ER_EINVAL, "bad arguments");
-    // the footprints as a table of lines and rows of 64-bit words, every one checked against its foot (as str_er_link_feet does)
-    std::vector<FootLine> lines((size_t)n, FootLine{});
+    // the footprints as a table of lines and rows of 64-bit words, every one checked against its foot
+    std::vector<FootLine> lines;
     std::vector<uint64_t> words;
-    for (int32_t t = 0; t < n; ++t) {
-        const str_er_line_foot &F = feet[t];
-        const std::string who = "line " + std::to_string(t);
-        if (F.w < 0 || F.h < 0 || (F.w == 0) != (F.h == 0)) return fail(c, STR_ER_EINVAL, who + ": bad foot box");
-        if (F.w == 0) {
-            if (F.pixels) return fail(c, STR_ER_EINVAL, who + ": pixels in an empty foot box");
-            continue;
-        }
-        if (F.x < 0 || F.y < 0 || (int64_t)F.x + F.w > W || (int64_t)F.y + F.h > H) return fail(c, STR_ER_EINVAL, who + ": the foot box leaves the frame");
-    }
+    int rc = check_foot_boxes(c, W, H, feet, n, "");
+    if (rc != STR_ER_OK) return rc;
     for (int32_t t = 0; t < n; ++t)
         if (feet[t].w > GEOM_MAX_BOX || feet[t].h > GEOM_MAX_BOX)
             return fail(c, STR_ER_ECAPACITY, "line " + std::to_string(t) + ": a foot box wider or taller than " + std::to_string(GEOM_MAX_BOX) + " pixels");
-    const uint32_t *at = bits;
-    for (int32_t t = 0; t < n; ++t) {
-        const str_er_line_foot &F = feet[t];
-        FootLine &L = lines[(size_t)t];
-        L.word_off = words.size();
-        if (F.w == 0) continue;
-        if (!at) return fail(c, STR_ER_EINVAL, "footprint bits missing");
-        L.x = F.x; L.y = F.y; L.w = F.w; L.h = F.h; L.pitch = ((uint32_t)F.w + 63u) / 64u; L.count = 1;
-        const uint32_t pitch32 = ((uint32_t)F.w + 31u) / 32u, tail = (uint32_t)F.w & 31u;
-        uint64_t px = 0;
-        for (int32_t rr = 0; rr < F.h; ++rr, at += pitch32) {
-            if (tail && (at[pitch32 - 1] >> tail)) return fail(c, STR_ER_EINVAL, "a footprint has a bit set past its row's width");
-            for (uint32_t k = 0; k < L.pitch; ++k) {
-                const uint64_t v = (uint64_t)at[2 * k] | (2 * k + 1 < pitch32 ? (uint64_t)at[2 * k + 1] << 32 : 0ull);
-                px += (uint64_t)__builtin_popcountll(v);
-                words.push_back(v);
-            }
-        }
-        if (px != F.pixels) return fail(c, STR_ER_EINVAL, "a foot's pixels are not the number of bits set in its footprint");
-        if (px == 0) L = FootLine{};          // (a box without a bit: an empty footprint)
-    }
+    if ((rc = pack_footprints(c, feet, bits, n, lines, words)) != STR_ER_OK) return rc;
+    for (int32_t t = 0; t < n; ++t)
+        if (feet[t].pixels == 0) lines[(size_t)t] = FootLine{};          // (a box without a bit: an empty footprint)
     std::vector<str_er_line_geom> out((size_t)n, str_er_line_geom{});
     for (str_er_line_geom &G : out) G.edge = -1;
     std::vector<int32_t> pts;
     if (!words.empty()) {
         HIP_TRY(c, hipSetDevice(c->prm.device));
-        int rc = grow_pair(c, c->d_foot_tab, c->h_foot_tab, c->foot_tab_bytes, sizeof(FootLine) * (size_t)n, "frame line tables");
-        if (rc != STR_ER_OK) return rc;
-        if ((rc = grow_foot_bits(c, words.size())) != STR_ER_OK) return rc;
+        if ((rc = c->foot_tab.ensure(c, sizeof(FootLine) * (size_t)n, "frame line tables")) != STR_ER_OK ||
+            (rc = c->foot_bits.ensure(c, 8 * words.size(), "line footprints")) != STR_ER_OK)
+            return rc;
         hipStream_t s = c->stream;
-        std::memcpy(c->h_foot_tab, lines.data(), sizeof(FootLine) * (size_t)n);
-        HIP_TRY(c, hipMemcpyAsync(c->d_foot_tab, c->h_foot_tab, sizeof(FootLine) * (size_t)n, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(c->d_foot_bits, words.data(), 8 * words.size(), hipMemcpyHostToDevice, s));      // (words must outlive the copy: every path below waits)
+        std::memcpy(c->foot_tab.h(), lines.data(), sizeof(FootLine) * (size_t)n);
+        HIP_TRY(c, hipMemcpyAsync(c->foot_tab.d(), c->foot_tab.h(), sizeof(FootLine) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->foot_bits.d<uint64_t>(), words.data(), 8 * words.size(), hipMemcpyHostToDevice, s));      // (words must outlive the copy: every path below waits)
         GeomPlan GP;
-        if ((rc = geom_enqueue(c, s, lines, reinterpret_cast<const FootLine *>(c->d_foot_tab), GP)) != STR_ER_OK) {
+        if ((rc = geom_enqueue(c, s, lines, reinterpret_cast<const FootLine *>(c->foot_tab.d()), GP)) != STR_ER_OK) {
             (void)hipStreamSynchronize(s);          // (the upload of words may still be queued)
             return rc;
         }

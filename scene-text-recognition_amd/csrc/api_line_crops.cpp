@@ -28,23 +28,6 @@ uint64_t crop_span(const str_er_line_crop &g)
     return ((uint64_t)g.width * (uint64_t)g.height + 3u) & ~(uint64_t)3u;
 }
 
-// jobs | members | grey | glyph in c->d_crop / c->h_crop, grown geometrically
-int ensure_crop_buffers(str_er_ctx *c, size_t need)
-{
-    if (need <= c->crop_bytes) return STR_ER_OK;
-    const size_t get = std::max(need, 2 * c->crop_bytes);
-    if (c->d_crop) { (void)hipFree(c->d_crop); c->d_crop = nullptr; }
-    if (c->h_crop) { (void)hipHostFree(c->h_crop); c->h_crop = nullptr; }
-    c->crop_bytes = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&c->d_crop), get) != hipSuccess) return fail(c, STR_ER_ENOMEM, "hipMalloc (line crops, " + std::to_string(get) + " bytes)");
-    if (hipHostMalloc(reinterpret_cast<void **>(&c->h_crop), get) != hipSuccess) {
-        (void)hipFree(c->d_crop); c->d_crop = nullptr;
-        return fail(c, STR_ER_ENOMEM, "hipHostMalloc (line crops, " + std::to_string(get) + " bytes)");
-    }
-    c->crop_bytes = get;
-    return STR_ER_OK;
-}
-
 // the crops of `jobs` (out_off set, n_bytes in all): uploaded, launched on s, one copy back through the page-locked buffer, one wait.
 // Glyph crops when d_bits is set (members index the words there).
 int crop_stage(str_er_ctx *c, hipStream_t s, const std::vector<LineCropJob> &jobs, const std::vector<GlyphMember> &members, const uint32_t *d_bits,
@@ -54,19 +37,19 @@ int crop_stage(str_er_ctx *c, hipStream_t s, const std::vector<LineCropJob> &job
     if (n == 0) return STR_ER_OK;
     const size_t o_mem = align_up(sizeof(LineCropJob) * n, 256), o_pix = align_up(o_mem + sizeof(GlyphMember) * members.size(), 256);
     const size_t o_glyph = o_pix + (size_t)n_bytes, need = o_glyph + (d_bits ? (size_t)n_bytes : 0);
-    const int rc = ensure_crop_buffers(c, need);
+    const int rc = c->crop.ensure(c, need, "line crops");         // (jobs | members | grey | glyph)
     if (rc != STR_ER_OK) return rc;
-    std::memcpy(c->h_crop, jobs.data(), sizeof(LineCropJob) * n);
-    if (!members.empty()) std::memcpy(c->h_crop + o_mem, members.data(), sizeof(GlyphMember) * members.size());
-    HIP_TRY(c, hipMemcpyAsync(c->d_crop, c->h_crop, o_pix, hipMemcpyHostToDevice, s));
-    launch_line_crops(s, reinterpret_cast<const LineCropJob *>(c->d_crop), (int)n, c->d_crop + o_pix, d_bits ? c->d_crop + o_glyph : nullptr,
-                      reinterpret_cast<const GlyphMember *>(c->d_crop + o_mem), d_bits);
+    std::memcpy(c->crop.h(), jobs.data(), sizeof(LineCropJob) * n);
+    if (!members.empty()) std::memcpy(c->crop.h() + o_mem, members.data(), sizeof(GlyphMember) * members.size());
+    HIP_TRY(c, hipMemcpyAsync(c->crop.d(), c->crop.h(), o_pix, hipMemcpyHostToDevice, s));
+    launch_line_crops(s, reinterpret_cast<const LineCropJob *>(c->crop.d()), (int)n, c->crop.d() + o_pix, d_bits ? c->crop.d() + o_glyph : nullptr,
+                      reinterpret_cast<const GlyphMember *>(c->crop.d() + o_mem), d_bits);
     HIP_TRY(c, hipGetLastError());
     if (in_batch) rec(c, "line_crops");         // (the call's one profiling event of the stage)
-    HIP_TRY(c, hipMemcpyAsync(c->h_crop + o_pix, c->d_crop + o_pix, need - o_pix, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(c->crop.h() + o_pix, c->crop.d() + o_pix, need - o_pix, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
-    std::memcpy(grey, c->h_crop + o_pix, (size_t)n_bytes);
-    if (d_bits) std::memcpy(glyph, c->h_crop + o_glyph, (size_t)n_bytes);
+    std::memcpy(grey, c->crop.h() + o_pix, (size_t)n_bytes);
+    if (d_bits) std::memcpy(glyph, c->crop.h() + o_glyph, (size_t)n_bytes);
     return STR_ER_OK;
 }
 

@@ -186,7 +186,7 @@ try {
     const size_t in_b = 8192 * (size_t)n, total = in_b + 8 * (size_t)n;
     int rc = ensure_scratch(c, total);
     if (rc != STR_ER_OK) return rc;
-    uint8_t *s = static_cast<uint8_t *>(c->d_scratch);
+    uint8_t *s = c->scratch.d();
     HIP_TRY(c, hipMemcpyAsync(s, fv, in_b, hipMemcpyHostToDevice, c->stream));
     launch_cascade_fv(c->stream, reinterpret_cast<const double *>(s), n, reinterpret_cast<double *>(s + in_b), c->casc[which].dev);
     HIP_TRY(c, hipGetLastError());
@@ -385,7 +385,7 @@ try {
     const size_t o_x = 0, o_buf = align_up((size_t)n * dim * 8, 256);
     int rc = ensure_scratch(c, o_buf + ocr_layout(nullptr, (size_t)n, &m, false, dec != nullptr, true).bytes);
     if (rc != STR_ER_OK) return rc;
-    uint8_t *s = static_cast<uint8_t *>(c->d_scratch);
+    uint8_t *s = c->scratch.d();
     const OcrBuf buf = ocr_layout(s + o_buf, (size_t)n, &m, false, dec != nullptr, true);
     hipStream_t st = c->stream;
     HIP_TRY(c, hipMemcpyAsync(s + o_x, x, (size_t)n * dim * 8, hipMemcpyHostToDevice, st));
@@ -413,7 +413,7 @@ try {
     const size_t o_q = 0, o_buf = align_up((size_t)n * dim, 256);
     int rc = ensure_scratch(c, o_buf + ocr_layout(nullptr, (size_t)n, &m, false, dec != nullptr, true).bytes);
     if (rc != STR_ER_OK) return rc;
-    uint8_t *s = static_cast<uint8_t *>(c->d_scratch);
+    uint8_t *s = c->scratch.d();
     const OcrBuf buf = ocr_layout(s + o_buf, (size_t)n, &m, false, dec != nullptr, true);
     hipStream_t st = c->stream;
     HIP_TRY(c, hipMemcpyAsync(s + o_q, q, (size_t)n * dim, hipMemcpyHostToDevice, st));
@@ -458,7 +458,7 @@ try {
     const size_t o_rot = take(slope ? sizeof(RotGeom) * (size_t)n : 0), o_box = take(16 * (size_t)n), o_buf = take(0);
     int rc = ensure_scratch(c, o_buf + ocr_layout(nullptr, (size_t)n, m, true, false, false).bytes);
     if (rc != STR_ER_OK) return rc;
-    uint8_t *s = static_cast<uint8_t *>(c->d_scratch);
+    uint8_t *s = c->scratch.d();
     const OcrBuf buf = ocr_layout(s + o_buf, (size_t)n, m, true, false, false);
     HIP_TRY(c, hipMemcpyAsync(s + o_box, boxes, 16 * (size_t)n, hipMemcpyHostToDevice, st));
     std::vector<RotGeom> rot;

@@ -42,7 +42,7 @@ static int boxes_call(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h,
                  o_code = align_up(o_sw + 8 * (size_t)n, 256), total = o_code + 576 * (size_t)n;
     int rc = ensure_scratch(c, total);
     if (rc != STR_ER_OK) return rc;
-    uint8_t *s = static_cast<uint8_t *>(c->d_scratch);
+    uint8_t *s = c->scratch.d();
     HIP_TRY(c, hipMemcpyAsync(s + o_box, boxes, 16 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     launch_lbp_boxes(c->stream, c->d_pix, w, h, w, reinterpret_cast<const int32_t *>(s + o_box), n,
                      hist ? reinterpret_cast<double *>(s + o_hist) : nullptr, tiles ? s + o_tile : nullptr, codes ? s + o_code : nullptr, s + o_cls,
@@ -222,7 +222,7 @@ try {
         const size_t o_c = 0, o_tr = align_up(sizeof(CandRec) * (size_t)n, 256);
         rc = ensure_scratch(c, o_tr + sizeof(TrackRec) * (size_t)n);
         if (rc == STR_ER_OK) {
-            uint8_t *sc = static_cast<uint8_t *>(c->d_scratch);
+            uint8_t *sc = c->scratch.d();
             hipError_t e = hipMemcpyAsync(sc + o_c, cands, sizeof(CandRec) * (size_t)n, hipMemcpyHostToDevice, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(sc + o_tr, tracks, sizeof(TrackRec) * (size_t)n, hipMemcpyHostToDevice, c->stream);
             if (e != hipSuccess) rc = fail(c, STR_ER_EHIP, hipGetErrorString(e));
@@ -259,7 +259,7 @@ try {
     const size_t o_box = 0, o_tr = align_up(16 * (size_t)n, 256), o_cs = align_up(o_tr + sizeof(TrackRec) * (size_t)n, 256);
     int rc = ensure_scratch(c, o_cs + calc_color_scratch_bytes((size_t)n));
     if (rc != STR_ER_OK) return rc;
-    uint8_t *sc = static_cast<uint8_t *>(c->d_scratch);
+    uint8_t *sc = c->scratch.d();
     HIP_TRY(c, hipMemcpyAsync(sc + o_box, boxes, 16 * (size_t)n, hipMemcpyHostToDevice, st));
     ColorSrc col{c->d_in, c->d_in + 1, c->d_in + 2, 3, (int64_t)cw * 3};
     OcrSrc src{};
@@ -284,7 +284,7 @@ try {
                  o_rng = align_up(o_list + 4 * (size_t)n, 256);
     int rc = ensure_scratch(c, o_rng + 64);
     if (rc != STR_ER_OK) return rc;
-    uint8_t *sc = static_cast<uint8_t *>(c->d_scratch);
+    uint8_t *sc = c->scratch.d();
     std::vector<TrackRec> tr((size_t)n);
     for (int i = 0; i < n; ++i) {
         TrackRec t{};
@@ -313,7 +313,7 @@ try {
 namespace str_er_host {
 
 // (o_pix / o_shape / o_stroke / o_bits: where the popcounts, the ShapeRecs (with shapes), the StrokeRecs (with strokes) and the words of
-// n jobs sit in c->d_mask, behind the jobs)
+// n jobs sit in c->mask, behind the jobs)
 static void mask_offsets(size_t n, uint64_t n_words, bool shapes, bool strokes, size_t &o_pix, size_t &o_shape, size_t &o_stroke, size_t &o_bits,
                          size_t &need)
 {
@@ -335,33 +335,15 @@ int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64
     for (MaskJob &j : jobs) { j.scratch_off = scratch; scratch += mask_scratch_words(j.w, j.h); }
     size_t o_pix, o_shape, o_stroke, o_bits, need;
     mask_offsets(n, n_words, shapes, strokes, o_pix, o_shape, o_stroke, o_bits, need);
-    if (need > c->mask_bytes) {
-        const size_t get = std::max(need, 2 * c->mask_bytes);
-        if (c->d_mask) { (void)hipFree(c->d_mask); c->d_mask = nullptr; }
-        if (c->h_mask) { (void)hipHostFree(c->h_mask); c->h_mask = nullptr; }
-        c->mask_bytes = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_mask), get) != hipSuccess) return fail(c, STR_ER_ENOMEM, "hipMalloc (masks, " + std::to_string(get) + " bytes)");
-        if (hipHostMalloc(reinterpret_cast<void **>(&c->h_mask), get) != hipSuccess) {
-            (void)hipFree(c->d_mask); c->d_mask = nullptr;
-            return fail(c, STR_ER_ENOMEM, "hipHostMalloc (masks, " + std::to_string(get) + " bytes)");
-        }
-        c->mask_bytes = get;
-    }
-    if (scratch > c->mask_scratch_words) {
-        const size_t get = std::max(scratch, 2 * c->mask_scratch_words);
-        if (c->d_mask_scratch) { (void)hipFree(c->d_mask_scratch); c->d_mask_scratch = nullptr; }
-        c->mask_scratch_words = 0;
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_mask_scratch), 8 * get) != hipSuccess)
-            return fail(c, STR_ER_ENOMEM, "hipMalloc (mask scratch, " + std::to_string(8 * get) + " bytes)");
-        c->mask_scratch_words = get;
-    }
-    std::memcpy(c->h_mask, jobs.data(), sizeof(MaskJob) * n);
-    HIP_TRY(c, hipMemcpyAsync(c->d_mask, c->h_mask, sizeof(MaskJob) * n, hipMemcpyHostToDevice, s));
-    launch_er_masks(s, reinterpret_cast<const MaskJob *>(c->d_mask), n_class, reinterpret_cast<uint32_t *>(c->d_mask + o_bits),
-                    reinterpret_cast<uint32_t *>(c->d_mask + o_pix), shapes ? reinterpret_cast<ShapeRec *>(c->d_mask + o_shape) : nullptr,
-                    strokes ? reinterpret_cast<StrokeRec *>(c->d_mask + o_stroke) : nullptr, c->d_mask_scratch, qscale);
+    int rc = c->mask.ensure(c, need, "masks");
+    if (rc != STR_ER_OK || (rc = c->mask_scratch.ensure(c, 8 * scratch, "mask scratch")) != STR_ER_OK) return rc;
+    std::memcpy(c->mask.h(), jobs.data(), sizeof(MaskJob) * n);
+    HIP_TRY(c, hipMemcpyAsync(c->mask.d(), c->mask.h(), sizeof(MaskJob) * n, hipMemcpyHostToDevice, s));
+    launch_er_masks(s, reinterpret_cast<const MaskJob *>(c->mask.d()), n_class, reinterpret_cast<uint32_t *>(c->mask.d() + o_bits),
+                    reinterpret_cast<uint32_t *>(c->mask.d() + o_pix), shapes ? reinterpret_cast<ShapeRec *>(c->mask.d() + o_shape) : nullptr,
+                    strokes ? reinterpret_cast<StrokeRec *>(c->mask.d() + o_stroke) : nullptr, c->mask_scratch.d<uint64_t>(), qscale);
     HIP_TRY(c, hipGetLastError());
-    if (d_bits) *d_bits = reinterpret_cast<const uint32_t *>(c->d_mask + o_bits);
+    if (d_bits) *d_bits = reinterpret_cast<const uint32_t *>(c->mask.d() + o_bits);
     return STR_ER_OK;
 }
 
@@ -374,12 +356,12 @@ int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_
     if (rc != STR_ER_OK) return rc;
     size_t o_pix, o_shape, o_stroke, o_bits, need;
     mask_offsets(n, n_words, shapes != nullptr, strokes != nullptr, o_pix, o_shape, o_stroke, o_bits, need);
-    HIP_TRY(c, hipMemcpyAsync(c->h_mask + o_pix, c->d_mask + o_pix, (bits ? need : o_bits) - o_pix, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(c->mask.h() + o_pix, c->mask.d() + o_pix, (bits ? need : o_bits) - o_pix, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
-    std::memcpy(pixels, c->h_mask + o_pix, 4 * n);
-    if (shapes) std::memcpy(shapes, c->h_mask + o_shape, sizeof(ShapeRec) * n);
-    if (strokes) std::memcpy(strokes, c->h_mask + o_stroke, sizeof(StrokeRec) * n);
-    if (bits && n_words) std::memcpy(bits, c->h_mask + o_bits, 4 * (size_t)n_words);
+    std::memcpy(pixels, c->mask.h() + o_pix, 4 * n);
+    if (shapes) std::memcpy(shapes, c->mask.h() + o_shape, sizeof(ShapeRec) * n);
+    if (strokes) std::memcpy(strokes, c->mask.h() + o_stroke, sizeof(StrokeRec) * n);
+    if (bits && n_words) std::memcpy(bits, c->mask.h() + o_bits, 4 * (size_t)n_words);
     return STR_ER_OK;
 }
 

@@ -65,16 +65,6 @@ int frame_to_planes(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t h, int
     return STR_ER_OK;
 }
 
-int ensure_strip_buf(str_er_ctx *c, uint8_t *&p, size_t &cap, size_t need)
-{
-    if (need <= cap) return STR_ER_OK;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    need += need / 4;
-    if (hipMalloc(reinterpret_cast<void **>(&p), need) != hipSuccess) return fail(c, STR_ER_ENOMEM, "hipMalloc (strip blob)");
-    cap = need;
-    return STR_ER_OK;
-}
-
 } // namespace
 } // extern "C++"
 
@@ -118,7 +108,7 @@ try {
             const uint8_t *src = c->d_pix + (size_t)(ch % 3) * psize + (size_t)r0 * pstride;
             const uint8_t *lay = src;
             if (ptop) {
-                uint8_t *dst = static_cast<uint8_t *>(c->d_scratch) + k * pad_plane;
+                uint8_t *dst = c->scratch.d() + k * pad_plane;
                 HIP_TRY(c, hipMemsetAsync(dst, ch >= 3 ? 0x00 : 0xFF, (size_t)TILE_H * pstride, s));      // (inverted channels read pixel ^ 0xFF)
                 HIP_TRY(c, hipMemcpyAsync(dst + (size_t)TILE_H * pstride, src, (size_t)rows * pstride, hipMemcpyDeviceToDevice, s));
                 lay = dst;
@@ -163,27 +153,27 @@ try {
     // what leaves the GPU, put together on the GPU: the records, and the node of every pixel of the first / last row (seam map:
     // index in the tile's records; tile_nbase: the tile's first record)
     const StripLayout L = strip_layout(sp, (uint32_t)w);
-    rc = ensure_strip_buf(c, c->d_strip_out, c->strip_out_cap, L.total);
+    rc = ensure_quarter_more(c, c->strip_out, L.total, "strip blob");
     if (rc != STR_ER_OK) return rc;
     std::vector<uint8_t> head(L.head);
     const StripHeader hd{STRIP_MAGIC, STRIP_VERSION, (uint32_t)w, (uint32_t)h, (uint32_t)strip, (uint32_t)n_strips, (uint32_t)std::max(0, r0 - (r0 > 0 ? TILE_H : 0)), (uint32_t)rows,
                          (uint32_t)npl, (uint32_t)c->prm.thresh_step, c->prm.channel_mask, 0u};
     std::memcpy(head.data(), &hd, sizeof(hd));
     std::memcpy(head.data() + sizeof(hd), sp.data(), npl * sizeof(StripPlane));
-    HIP_TRY(c, hipMemcpyAsync(c->d_strip_out, head.data(), L.head, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(c->strip_out.d(), head.data(), L.head, hipMemcpyHostToDevice, s));
     for (size_t k = 0; k < npl && rows > 0; ++k) {
         const PlaneDesc &pd = b.planes[k];
-        if (sp[k].n_nodes) HIP_TRY(c, hipMemcpyAsync(c->d_strip_out + L.rec[k], c->na.rec + pd.node_base, (size_t)sp[k].n_nodes * sizeof(NodeRec), hipMemcpyDeviceToDevice, s));
+        if (sp[k].n_nodes) HIP_TRY(c, hipMemcpyAsync(c->strip_out.d() + L.rec[k], c->na.rec + pd.node_base, (size_t)sp[k].n_nodes * sizeof(NodeRec), hipMemcpyDeviceToDevice, s));
         // seam map: boundary j holds pixel row (j+1)*TILE_H - 1 at [2j * w, +w) and pixel row (j+1)*TILE_H at [(2j+1) * w, +w)
         const int jt = 0, jb = pd.tiles_y - 2;               // the seams under the phantom row above / over the phantom row below
         if (ptop) launch_strip_border_ids(s, c->d_seam + pd.seam_base + (size_t)(2 * jt + 1) * w, c->d_tile_nbase + pd.tile_base + (size_t)(jt + 1) * pd.tiles_x, w,
-                                          reinterpret_cast<uint32_t *>(c->d_strip_out + L.top[k]));
+                                          reinterpret_cast<uint32_t *>(c->strip_out.d() + L.top[k]));
         if (pbot) launch_strip_border_ids(s, c->d_seam + pd.seam_base + (size_t)(2 * jb) * w, c->d_tile_nbase + pd.tile_base + (size_t)jb * pd.tiles_x, w,
-                                          reinterpret_cast<uint32_t *>(c->d_strip_out + L.bot[k]));
+                                          reinterpret_cast<uint32_t *>(c->strip_out.d() + L.bot[k]));
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, wait_stream(c, s));        // (also: `head` is pageable memory)
-    *d_blob = c->d_strip_out; *blob_bytes = (int64_t)L.total;
+    *d_blob = c->strip_out.d(); *blob_bytes = (int64_t)L.total;
     return STR_ER_OK;
 } ABI_GUARD(c)
 
@@ -233,7 +223,7 @@ try {
         up_total += align_up((size_t)blob_bytes[i], 256);
     }
     if (blob_kind == STR_ER_MEM_HOST) {
-        const int rcb = ensure_strip_buf(c, c->d_strip_in, c->strip_in_cap, up_total);
+        const int rcb = ensure_quarter_more(c, c->strip_in, up_total, "strip blob");
         if (rcb != STR_ER_OK) return rcb;
     }
     size_t up_at = 0;
@@ -243,8 +233,8 @@ try {
         std::vector<uint8_t> head(head_bytes);
         if (blob_kind == STR_ER_MEM_HOST) {
             std::memcpy(head.data(), blobs[i], head_bytes);
-            HIP_TRY(c, hipMemcpyAsync(c->d_strip_in + up_at, blobs[i], (size_t)blob_bytes[i], hipMemcpyHostToDevice, c->stream));
-            v.d = c->d_strip_in + up_at;
+            HIP_TRY(c, hipMemcpyAsync(c->strip_in.d() + up_at, blobs[i], (size_t)blob_bytes[i], hipMemcpyHostToDevice, c->stream));
+            v.d = c->strip_in.d() + up_at;
             up_at += align_up((size_t)blob_bytes[i], 256);
         } else {
             HIP_TRY(c, hipMemcpy(head.data(), blobs[i], head_bytes, hipMemcpyDeviceToHost));

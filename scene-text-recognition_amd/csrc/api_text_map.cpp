@@ -14,23 +14,6 @@ int32_t first_sample_at(int64_t a, int64_t W, int64_t wp)
     return (int32_t)std::min<int64_t>(x, W);
 }
 
-// the page-locked / device buffer pair `d`, `h` of `bytes`, grown to at least `need` (geometrically), never shrunk
-int grow_pair(str_er_ctx *c, uint8_t *&d, uint8_t *&h, size_t &bytes, size_t need, const char *what)
-{
-    if (need <= bytes) return STR_ER_OK;
-    const size_t get = std::max(need, 2 * bytes);
-    if (d) { (void)hipFree(d); d = nullptr; }
-    if (h) { (void)hipHostFree(h); h = nullptr; }
-    bytes = 0;
-    if (hipMalloc(reinterpret_cast<void **>(&d), get) != hipSuccess) return fail(c, STR_ER_ENOMEM, std::string("hipMalloc (") + what + ", " + std::to_string(get) + " bytes)");
-    if (hipHostMalloc(reinterpret_cast<void **>(&h), get) != hipSuccess) {
-        (void)hipFree(d); d = nullptr;
-        return fail(c, STR_ER_ENOMEM, std::string("hipHostMalloc (") + what + ", " + std::to_string(get) + " bytes)");
-    }
-    bytes = get;
-    return STR_ER_OK;
-}
-
 uint32_t SampleTabs::table(int32_t n, int32_t np)
 {
     const auto it = at.find({n, np});
@@ -43,7 +26,7 @@ uint32_t SampleTabs::table(int32_t n, int32_t np)
 
 namespace {
 
-// where the ids sit behind the bytes in c->d_tmap / c->h_tmap, and the bytes the maps of n_elem elements need
+// where the ids sit behind the bytes in c->tmap, and the bytes the maps of n_elem elements need
 void tmap_out_offsets(uint64_t n_elem, bool map, bool ids, size_t &o_ids, size_t &need)
 {
     o_ids = map ? align_up((size_t)n_elem, 256) : 0;
@@ -120,7 +103,7 @@ void tmap_layout(const std::vector<str_er_frame_map> &frames, const std::vector<
     if (L.tabs.empty()) L.tabs.push_back(0);
 }
 
-// the launch of one layout on s (the maps into c->d_tmap, sized by text_map_reserve / the caller), one copy back, one wait;
+// the launch of one layout on s (the maps into c->tmap, sized by text_map_reserve / the caller), one copy back, one wait;
 // n_elem elements of map bytes and / or ids to out_map / out_ids
 int tmap_stage(str_er_ctx *c, hipStream_t s, const TmapLayout &L, const uint32_t *d_bits, uint64_t n_elem, uint8_t *out_map, int32_t *out_ids,
                bool in_batch)
@@ -128,25 +111,25 @@ int tmap_stage(str_er_ctx *c, hipStream_t s, const TmapLayout &L, const uint32_t
     const bool map = out_map != nullptr, ids = out_ids != nullptr;
     size_t o_ids, need;
     tmap_out_offsets(n_elem, map, ids, o_ids, need);
-    if (need > c->tmap_bytes) return fail(c, STR_ER_EHIP, "text map: the output buffer was not sized (internal error)");
+    if (need > c->tmap.size()) return fail(c, STR_ER_EHIP, "text map: the output buffer was not sized (internal error)");
     const size_t o_list = align_up(sizeof(TextMapTile) * L.tiles.size(), 256), o_cand = align_up(o_list + 4 * L.list.size(), 256);
     const size_t o_tab = align_up(o_cand + sizeof(TextMapCand) * L.cands.size(), 256), tab_need = o_tab + 2 * L.tabs.size();
-    const int rc = grow_pair(c, c->d_tmap_tab, c->h_tmap_tab, c->tmap_tab_bytes, tab_need, "text map tables");
+    const int rc = c->tmap_tab.ensure(c, tab_need, "text map tables");
     if (rc != STR_ER_OK) return rc;
-    std::memcpy(c->h_tmap_tab, L.tiles.data(), sizeof(TextMapTile) * L.tiles.size());
-    if (!L.list.empty()) std::memcpy(c->h_tmap_tab + o_list, L.list.data(), 4 * L.list.size());
-    if (!L.cands.empty()) std::memcpy(c->h_tmap_tab + o_cand, L.cands.data(), sizeof(TextMapCand) * L.cands.size());
-    std::memcpy(c->h_tmap_tab + o_tab, L.tabs.data(), 2 * L.tabs.size());
-    HIP_TRY(c, hipMemcpyAsync(c->d_tmap_tab, c->h_tmap_tab, tab_need, hipMemcpyHostToDevice, s));
-    launch_text_map(s, reinterpret_cast<const TextMapTile *>(c->d_tmap_tab), (int)L.tiles.size(), reinterpret_cast<const uint32_t *>(c->d_tmap_tab + o_list),
-                    reinterpret_cast<const TextMapCand *>(c->d_tmap_tab + o_cand), reinterpret_cast<const uint16_t *>(c->d_tmap_tab + o_tab), d_bits,
-                    map ? c->d_tmap : nullptr, ids ? reinterpret_cast<int32_t *>(c->d_tmap + o_ids) : nullptr);
+    std::memcpy(c->tmap_tab.h(), L.tiles.data(), sizeof(TextMapTile) * L.tiles.size());
+    if (!L.list.empty()) std::memcpy(c->tmap_tab.h() + o_list, L.list.data(), 4 * L.list.size());
+    if (!L.cands.empty()) std::memcpy(c->tmap_tab.h() + o_cand, L.cands.data(), sizeof(TextMapCand) * L.cands.size());
+    std::memcpy(c->tmap_tab.h() + o_tab, L.tabs.data(), 2 * L.tabs.size());
+    HIP_TRY(c, hipMemcpyAsync(c->tmap_tab.d(), c->tmap_tab.h(), tab_need, hipMemcpyHostToDevice, s));
+    launch_text_map(s, reinterpret_cast<const TextMapTile *>(c->tmap_tab.d()), (int)L.tiles.size(), reinterpret_cast<const uint32_t *>(c->tmap_tab.d() + o_list),
+                    reinterpret_cast<const TextMapCand *>(c->tmap_tab.d() + o_cand), reinterpret_cast<const uint16_t *>(c->tmap_tab.d() + o_tab), d_bits,
+                    map ? c->tmap.d() : nullptr, ids ? reinterpret_cast<int32_t *>(c->tmap.d() + o_ids) : nullptr);
     HIP_TRY(c, hipGetLastError());
     if (in_batch) rec(c, "text_map");          // (the call's one profiling event of the stage)
-    HIP_TRY(c, hipMemcpyAsync(c->h_tmap, c->d_tmap, need, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(c->tmap.h(), c->tmap.d(), need, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
-    if (map) std::memcpy(out_map, c->h_tmap, (size_t)n_elem);
-    if (ids) std::memcpy(out_ids, c->h_tmap + o_ids, 4 * (size_t)n_elem);
+    if (map) std::memcpy(out_map, c->tmap.h(), (size_t)n_elem);
+    if (ids) std::memcpy(out_ids, c->tmap.h() + o_ids, 4 * (size_t)n_elem);
     return STR_ER_OK;
 }
 
@@ -154,12 +137,12 @@ uint64_t frame_span(int32_t w, int32_t h) { return ((uint64_t)w * (uint64_t)h + 
 
 } // namespace
 
-// the output maps of n_elem elements in c->d_tmap / c->h_tmap
+// the output maps of n_elem elements in c->tmap
 static int reserve_out(str_er_ctx *c, uint64_t n_elem, bool map, bool ids)
 {
     size_t o_ids, need;
     tmap_out_offsets(n_elem, map, ids, o_ids, need);
-    return grow_pair(c, c->d_tmap, c->h_tmap, c->tmap_bytes, need, "text maps");
+    return c->tmap.ensure(c, need, "text maps");
 }
 
 int text_map_reserve(str_er_ctx *c, uint32_t stages, const std::vector<int32_t> &frame_wh)

@@ -246,7 +246,7 @@ int line_ocr_phase(str_er_ctx *c, const PlaneDesc *d_planes, str_er_result *r)
     const size_t o_rec = take(sizeof(CandRec) * n_m), o_rot = take(sizeof(RotGeom) * n_m), o_list = take(4 * n_m), o_buf = take(0);
     int rc2 = ensure_scratch(c, o_buf + ocr_layout(nullptr, n_m, &m, false, false, false).bytes);
     if (rc2 != STR_ER_OK) return rc2;
-    uint8_t *sc = static_cast<uint8_t *>(c->d_scratch);
+    uint8_t *sc = c->scratch.d();
     const OcrBuf buf = ocr_layout(sc + o_buf, n_m, &m, false, false, false);
     HIP_TRY(c, hipMemcpyAsync(sc + o_rec, recs.data(), sizeof(CandRec) * n_m, hipMemcpyHostToDevice, s));
     HIP_TRY(c, hipMemcpyAsync(sc + o_rot, rot.data(), sizeof(RotGeom) * n_m, hipMemcpyHostToDevice, s));
@@ -314,28 +314,17 @@ int group_phase(str_er_ctx *c, const CandRec *d_cands, const TrackRec *d_track, 
     for (int g = 0; g < G; ++g)
         if (img[2 * g + 1] - img[2 * g] > 65535u) return fail(c, STR_ER_ECAPACITY, "more than 65535 candidates in one image");
     hipStream_t s = c->stream;
-    const size_t words = 4 * n_c + 4 * (size_t)G + 64;
-    if (words > c->group_words) {          // (a quarter more than needed: the candidate count differs from batch to batch, and hipFree / hipMalloc wait for the whole device)
-        const size_t get = words + words / 4;
-        if (c->d_group) { (void)hipFree(c->d_group); c->d_group = nullptr; c->group_words = 0; }
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_group), 4 * get) != hipSuccess) return fail(c, STR_ER_ENOMEM, "hipMalloc (grouping workspace)");
-        c->group_words = get;
-    }
-    auto grow_pairs = [&](size_t cap) -> int {
-        if (cap <= c->group_pair_cap) return STR_ER_OK;
-        cap += cap / 4;
-        if (c->d_group_pairs) { (void)hipFree(c->d_group_pairs); c->d_group_pairs = nullptr; c->group_pair_cap = 0; }
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_group_pairs), 4 * cap) != hipSuccess) return fail(c, STR_ER_ENOMEM, "hipMalloc (pair list)");
-        c->group_pair_cap = cap;
-        return STR_ER_OK;
-    };
-    int rc = grow_pairs(std::max<size_t>(8 * n_c, 4096));
+    // (both a quarter more than needed: the candidate count differs from batch to batch)
+    int rc = ensure_quarter_more(c, c->group, 4 * (4 * n_c + 4 * (size_t)G + 64), "grouping workspace");
     if (rc != STR_ER_OK) return rc;
+    const auto grow_pairs = [&](size_t cap) { return ensure_quarter_more(c, c->group_pairs, 4 * cap, "pair list"); };
+    const auto pair_cap = [&] { return (uint32_t)std::min<size_t>(c->group_pairs.size() / 4, 0xFFFFFFFFu); };
+    if ((rc = grow_pairs(std::max<size_t>(8 * n_c, 4096))) != STR_ER_OK) return rc;
     GroupBufs gb{};
-    gb.tmp_a = c->d_group; gb.tmp_b = gb.tmp_a + n_c; gb.sorted = gb.tmp_b + n_c; gb.row_cnt = gb.sorted + n_c;
+    gb.tmp_a = c->group.d<uint32_t>(); gb.tmp_b = gb.tmp_a + n_c; gb.sorted = gb.tmp_b + n_c; gb.row_cnt = gb.sorted + n_c;
     gb.n_sorted = gb.row_cnt + n_c; gb.pair_off = gb.n_sorted + G;
     uint32_t *d_rng = gb.pair_off + G + 1;
-    gb.pairs = c->d_group_pairs; gb.pair_cap = (uint32_t)std::min<size_t>(c->group_pair_cap, 0xFFFFFFFFu);
+    gb.pairs = c->group_pairs.d<uint32_t>(); gb.pair_cap = pair_cap();
     HIP_TRY(c, hipMemcpyAsync(d_rng, img.data(), 4 * img.size(), hipMemcpyHostToDevice, s));
     launch_group_prepare(s, d_cands, d_track, d_rng, G, (inner_sup ? 1 : 0) | (presorted ? 2 : 0), gb);
     launch_group_pairs_count(s, d_cands, d_track, d_rng, G, gb);
@@ -348,10 +337,10 @@ int group_phase(str_er_ctx *c, const CandRec *d_cands, const TrackRec *d_track, 
     HIP_TRY(c, hipMemcpyAsync(sorted.data(), gb.sorted, 4 * n_c, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
     const size_t n_pairs = pair_off[(size_t)G];
-    if (n_pairs > c->group_pair_cap) {               // the optimistic buffer was too small: the fill kernel did nothing
+    if (n_pairs > c->group_pairs.size() / 4) {               // the optimistic buffer was too small: the fill kernel did nothing
         rc = grow_pairs(n_pairs + n_pairs / 4);
         if (rc != STR_ER_OK) return rc;
-        gb.pairs = c->d_group_pairs; gb.pair_cap = (uint32_t)std::min<size_t>(c->group_pair_cap, 0xFFFFFFFFu);
+        gb.pairs = c->group_pairs.d<uint32_t>(); gb.pair_cap = pair_cap();
         launch_group_pairs_fill(s, d_cands, d_track, d_rng, G, gb);
         HIP_TRY(c, hipGetLastError());
     }
@@ -413,14 +402,9 @@ int resolve_sibling_ties(str_er_ctx *c, const Batch &b, const BatchDev &bd, cons
     size_t largest = 0, total = 0;
     for (int i : amb) { largest = std::max(largest, scratch_need(i)); total += scratch_need(i); }
     const size_t want = std::max(largest, std::min<size_t>(total, (size_t)1 << 30));
-    if (want > c->replay_bytes) {
-        // (grown in steps of at least 2 x: hipFree / hipMalloc wait for the whole device -- every other context's kernels included; a rocprofv3 timeline of
-        // six batches in flight showed one such call as a 64 ms hole in the GPU's work)
-        const size_t get = std::max(want, 2 * c->replay_bytes);
-        if (c->d_replay) { (void)hipFree(c->d_replay); c->d_replay = nullptr; c->replay_bytes = 0; }
-        if (hipMalloc(reinterpret_cast<void **>(&c->d_replay), get) != hipSuccess) return fail(c, STR_ER_ENOMEM, "hipMalloc (flood replay scratch)");
-        c->replay_bytes = get;
-    }
+    // (grown in steps of at least 2 x: hipFree / hipMalloc wait for the whole device -- every other context's kernels included; a rocprofv3 timeline of
+    // six batches in flight showed one such call as a 64 ms hole in the GPU's work)
+    if (const int rcr = c->replay.ensure(c, want, "flood replay scratch"); rcr != STR_ER_OK) return rcr;
 
     // Planes go in rounds that fit the scratch (one round unless dozens of planes have dense stamps).  A round of the host walk is
     // two device round trips: planes + watch lists down, [walk], stamps up + the tie pass of the NMS; everything the device reads or
@@ -430,7 +414,7 @@ int resolve_sibling_ties(str_er_ctx *c, const Batch &b, const BatchDev &bd, cons
         std::vector<ReplayItem> items;
         size_t pos = 0, hneed = ((sizeof(ReplayItem) * amb.size() + 255) / 256) * 256;
         std::vector<size_t> hoff;
-        while (at < amb.size() && (items.empty() || pos + scratch_need(amb[at]) <= c->replay_bytes)) {
+        while (at < amb.size() && (items.empty() || pos + scratch_need(amb[at]) <= c->replay.size())) {
             const int i = amb[at++];
             ReplayItem it{};
             it.plane = (uint32_t)i; it.off = pos;
@@ -444,17 +428,14 @@ int resolve_sibling_ties(str_er_ctx *c, const Batch &b, const BatchDev &bd, cons
         }
         for (size_t o : hoff) if (o % 256 != 0) return fail(c, STR_ER_ESTATE, "tie plane arena: unaligned plane offset");
         const size_t m = items.size();
-        if (hneed > c->h_replay_bytes) {
+        if (hneed > c->replay_host.size()) {
             // (the arena's need follows the number of tie planes of a batch, which differs from batch to batch: room for 8 planes of the context's size at once --
             // at most 64 MB -- then doubling; a page-locked allocation is a 4 ms call that the other contexts' copies queue behind)
             const size_t plane_bytes = (((size_t)c->prm.max_width * c->prm.max_height + 255) / 256) * 256 + ((3 * 4 * (size_t)NMS_WATCH_CAP + 255) / 256) * 256;
-            const size_t get = std::max(hneed, std::max(2 * c->h_replay_bytes, std::min<size_t>(8 * plane_bytes, (size_t)64 << 20)));
-            if (c->h_replay) { (void)hipHostFree(c->h_replay); c->h_replay = nullptr; c->h_replay_bytes = 0; }
-            if (hipHostMalloc(reinterpret_cast<void **>(&c->h_replay), get, hipHostMallocMapped) != hipSuccess)
-                return fail(c, STR_ER_ENOMEM, "hipHostMalloc (flood order walk staging)");
-            c->h_replay_bytes = get;
+            const int rch = c->replay_host.ensure(c, std::max(hneed, std::min<size_t>(8 * plane_bytes, (size_t)64 << 20)), "flood order walk staging");
+            if (rch != STR_ER_OK) return rch;
         }
-        ReplayItem *h_items = reinterpret_cast<ReplayItem *>(c->h_replay);
+        ReplayItem *h_items = c->replay_host.h<ReplayItem>();
         // which planes the device has already put into host memory (k_export_tie_planes: the first TIE_SLOTS tie planes of the batch)
         std::vector<int> slot_of(m, -1);
         if (!c->replay_on_gpu && c->h_tie && !from_tree)
@@ -465,7 +446,7 @@ int resolve_sibling_ties(str_er_ctx *c, const Batch &b, const BatchDev &bd, cons
         std::memcpy(h_items, items.data(), sizeof(ReplayItem) * m);
         HIP_TRY(c, hipMemcpyAsync(c->d_replay_items, h_items, sizeof(ReplayItem) * m, hipMemcpyHostToDevice, s));
         if (c->replay_on_gpu) {
-            launch_flood_order(s, bd, dp, c->d_replay_items, (int)m, c->d_replay);
+            launch_flood_order(s, bd, dp, c->d_replay_items, (int)m, c->replay.d());
         } else {
             struct HostPlane { uint8_t *pix; uint32_t *watch, *group, *stamp; uint32_t n_watch; };
             std::vector<HostPlane> hp(m);
@@ -473,7 +454,7 @@ int resolve_sibling_ties(str_er_ctx *c, const Batch &b, const BatchDev &bd, cons
             for (size_t k = 0; k < m; ++k) {
                 const int        i = (int)items[k].plane;
                 HostPlane       &h = hp[k];
-                h.pix = c->h_replay + hoff[k];
+                h.pix = c->replay_host.h() + hoff[k];
                 h.watch = reinterpret_cast<uint32_t *>(h.pix + ((plane_px(i) + 255) / 256) * 256);
                 h.group = h.watch + NMS_WATCH_CAP;
                 h.stamp = h.group + NMS_WATCH_CAP;          // NMS_WATCH_CAP entries, or w * h when dense
@@ -487,7 +468,7 @@ int resolve_sibling_ties(str_er_ctx *c, const Batch &b, const BatchDev &bd, cons
                 need_sync = true;
             }
             // the planes without a slot: one launch writes them (and their watch lists) into the arena
-            if (need_sync) { launch_export_listed_planes(s, bd, c->d_replay_items, (int)m, c->h_replay); HIP_TRY(c, hipGetLastError()); }
+            if (need_sync) { launch_export_listed_planes(s, bd, c->d_replay_items, (int)m, c->replay_host.h()); HIP_TRY(c, hipGetLastError()); }
             if (need_sync) HIP_TRY(c, wait_stream(c, s));
             const auto tw0 = std::chrono::steady_clock::now();
             auto walk = [&](size_t k) {
@@ -522,11 +503,11 @@ int resolve_sibling_ties(str_er_ctx *c, const Batch &b, const BatchDev &bd, cons
                 if (!dense(i)) {
                     if (hp[k].n_watch) HIP_TRY(c, hipMemcpyAsync(c->d_wstamp + (size_t)i * NMS_WATCH_CAP, hp[k].stamp, 4 * (size_t)hp[k].n_watch, hipMemcpyHostToDevice, s));
                 } else {
-                    HIP_TRY(c, hipMemcpyAsync(c->d_replay + items[k].off, hp[k].stamp, 4 * plane_px(i), hipMemcpyHostToDevice, s));
+                    HIP_TRY(c, hipMemcpyAsync(c->replay.d() + items[k].off, hp[k].stamp, 4 * plane_px(i), hipMemcpyHostToDevice, s));
                 }
             }
         }
-        launch_nms_resolve(s, bd, dp, c->d_replay_items, (int)m, c->d_replay);
+        launch_nms_resolve(s, bd, dp, c->d_replay_items, (int)m, c->replay.d());
         HIP_TRY(c, hipGetLastError());
         c->n_replayed += m;
         // (the arena and the item table are reused by the next round; the last round is left to the caller's synchronisation)
@@ -581,7 +562,7 @@ int group_phase_overlap(str_er_ctx *c, const std::vector<uint32_t> &img, bool in
     const size_t o_tr = align_up(sizeof(CandRec) * m, 256);
     int rc = ensure_scratch(c, o_tr + sizeof(TrackRec) * m);
     if (rc != STR_ER_OK) return rc;
-    uint8_t *sc = static_cast<uint8_t *>(c->d_scratch);
+    uint8_t *sc = c->scratch.d();
     HIP_TRY(c, hipMemcpyAsync(sc, tmp.cands.data(), sizeof(CandRec) * m, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(sc + o_tr, tmp.tracks.data(), sizeof(TrackRec) * m, hipMemcpyHostToDevice, c->stream));
     rc = group_phase(c, reinterpret_cast<const CandRec *>(sc), reinterpret_cast<const TrackRec *>(sc + o_tr), img2, inner_sup, &tmp, /*presorted=*/true);
@@ -704,7 +685,7 @@ struct OcrPinned { uint32_t *count; uint32_t *list; int32_t *label; double *prob
 static OcrPinned ocr_pinned(const str_er_ctx *c, size_t cap, int region = 0)
 {
     OcrPinned p;
-    uint8_t  *base = c->h_ocr + (size_t)region * (64 + 16 * c->h_ocr_cap);
+    uint8_t  *base = c->ocr_host.h() + (size_t)region * (64 + 16 * c->ocr_cap());
     p.count = reinterpret_cast<uint32_t *>(base);
     p.prob = reinterpret_cast<double *>(base + 64);
     p.list = reinterpret_cast<uint32_t *>(base + 64 + 8 * cap);
@@ -715,18 +696,16 @@ static int ocr_stage(str_er_ctx *c, const BatchDev &bd, size_t cap, hipStream_t 
 {
     static const char *const names[2][4] = {{"ocr_host_gap", "ocr_features", "svm_kernel", "svm_couple"}, {"ocr_again_host_gap", "ocr_again_features", "ocr_again_svm_kernel", "ocr_again_svm_couple"}};
     const char *const *nm = names[again ? 1 : 0];
-    if (cap > c->h_ocr_cap) {
-        const size_t want = cap + cap / 4;
-        if (c->h_ocr) { (void)hipHostFree(c->h_ocr); c->h_ocr = nullptr; c->h_ocr_cap = 0; }
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void **>(&c->h_ocr), 2 * (64 + 16 * want)));
-        c->h_ocr_cap = want;
+    if (cap > c->ocr_cap()) {          // (room for a quarter more ERs than asked for)
+        const int rco = c->ocr_host.ensure(c, 2 * (64 + 16 * (cap + cap / 4)), "OCR results");
+        if (rco != STR_ER_OK) return rco;
     }
     const SvmDev &m = c->svm;
     const size_t  n_cands = c->pool_total;        // (the list has room for every candidate the tables hold)
     const size_t  o_list = 0, o_buf = align_up(4 * (n_cands + OCR_LIST_HDR), 256);
     const int     rc = ensure_scratch(c, o_buf + ocr_layout(nullptr, cap, &m, false, false, false).bytes);
     if (rc != STR_ER_OK) return rc;
-    uint8_t  *sc = static_cast<uint8_t *>(c->d_scratch);
+    uint8_t  *sc = c->scratch.d();
     OcrBuf    buf = ocr_layout(sc + o_buf, cap, &m, false, false, false);
     uint32_t *d_list = reinterpret_cast<uint32_t *>(sc + o_list);
     buf.n_dev = d_list;                          // (hdr[0]: k_ocr_list's count)
@@ -1128,7 +1107,7 @@ static int result_track(BatchRun &R, str_er_result *r)
         const size_t o_list = 0, o_cs = align_up(4 * ((size_t)total + OCR_LIST_HDR) + 256, 256);
         const int    rcs = ensure_scratch(c, o_cs + calc_color_scratch_bytes(n_cls));
         if (rcs != STR_ER_OK) return rcs;
-        uint8_t  *sc = static_cast<uint8_t *>(c->d_scratch);
+        uint8_t  *sc = c->scratch.d();
         uint32_t *d_list = reinterpret_cast<uint32_t *>(sc + o_list);
         if (hipMemsetAsync(c->d_track, 0, sizeof(TrackRec) * (size_t)total, s) != hipSuccess) return fail(c, STR_ER_EHIP, "track reset failed");
         if (n_cls) {
@@ -1562,30 +1541,6 @@ void str_er_destroy(str_er_ctx *c)
     (void)hipSetDevice(c->prm.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (void *p : c->allocs) (void)hipFree(p);
-    if (c->d_scratch) (void)hipFree(c->d_scratch);
-    if (c->d_mask) (void)hipFree(c->d_mask);
-    if (c->h_mask) (void)hipHostFree(c->h_mask);
-    if (c->d_mask_scratch) (void)hipFree(c->d_mask_scratch);
-    if (c->d_crop) (void)hipFree(c->d_crop);
-    if (c->h_crop) (void)hipHostFree(c->h_crop);
-    if (c->d_tmap) (void)hipFree(c->d_tmap);
-    if (c->h_tmap) (void)hipHostFree(c->h_tmap);
-    if (c->d_tmap_tab) (void)hipFree(c->d_tmap_tab);
-    if (c->h_tmap_tab) (void)hipHostFree(c->h_tmap_tab);
-    if (c->d_foot_tab) (void)hipFree(c->d_foot_tab);
-    if (c->h_foot_tab) (void)hipHostFree(c->h_foot_tab);
-    if (c->d_foot_out) (void)hipFree(c->d_foot_out);
-    if (c->h_foot_out) (void)hipHostFree(c->h_foot_out);
-    if (c->d_foot_bits) (void)hipFree(c->d_foot_bits);
-    if (c->d_link_out) (void)hipFree(c->d_link_out);
-    if (c->h_link_out) (void)hipHostFree(c->h_link_out);
-    if (c->d_geom_out) (void)hipFree(c->d_geom_out);
-    if (c->h_geom_out) (void)hipHostFree(c->h_geom_out);
-    if (c->d_geom_x) (void)hipFree(c->d_geom_x);
-    if (c->d_strip_out) (void)hipFree(c->d_strip_out);
-    if (c->d_strip_in) (void)hipFree(c->d_strip_in);
-    if (c->d_replay) (void)hipFree(c->d_replay);
-    if (c->h_replay) (void)hipHostFree(c->h_replay);
     if (c->h_tie) (void)hipHostFree(c->h_tie);
     if (c->na.rec) (void)hipFree(c->na.rec);
     if (c->na.aux) (void)hipFree(c->na.aux);
@@ -1593,14 +1548,11 @@ void str_er_destroy(str_er_ctx *c)
                     (void *)c->ka.ncand, (void *)c->ka.best, (void *)c->ka.perm, (void *)c->d_pool, (void *)c->d_pool_tmp, (void *)c->d_cands, (void *)c->d_cand_plane, (void *)c->d_cands2,
                     (void *)c->d_cand_plane2, (void *)c->d_redo, (void *)c->d_track, (void *)c->d_track_list})
         if (p) (void)hipFree(p);
-    if (c->d_group) (void)hipFree(c->d_group);
-    if (c->d_group_pairs) (void)hipFree(c->d_group_pairs);
     for (auto &hc : c->casc) if (hc.d_blob) (void)hipFree(hc.d_blob);
     if (c->d_svm_blob) (void)hipFree(c->d_svm_blob);
     if (c->h_planes) (void)hipHostFree(c->h_planes);
     if (c->h_zero) (void)hipHostFree(c->h_zero);
     if (c->h_cands_spec) (void)hipHostFree(c->h_cands_spec);
-    if (c->h_ocr) (void)hipHostFree(c->h_ocr);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
@@ -1608,7 +1560,7 @@ void str_er_destroy(str_er_ctx *c)
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;          // (and with it the on-demand buffers: OnDemand)
 }
 
 int str_er_create(const str_er_params *p, str_er_ctx **out)

@@ -17,6 +17,7 @@
 #include <new>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "er_kernels.h"
@@ -52,6 +53,38 @@ static_assert(sizeof(str_er_node) == 24, "node layout");
 static_assert(sizeof(CandRec) == sizeof(str_er_cand), "cand layout");
 
 struct PlaneGeom { int w, h, stride; size_t off; }; // physical planes of one pyramid level
+
+// An on-demand buffer of a context: created by the first call that needs it, grown when a call needs more, never shrunk, freed with
+// the context.  Device memory (d), page-locked host memory (h, allocated with the hipHostMalloc flags given) or a pair of both of
+// equal size.  It does no accounting: these buffers are not part of the fixed workspace and never were in str_er_workspace_bytes
+// (ws_bytes), which bench.py reports.
+template <bool DEV, bool HOST> class OnDemand {
+public:
+    explicit OnDemand(unsigned host_flags = hipHostMallocDefault) : host_flags_(host_flags) {}
+    OnDemand(OnDemand &&o) noexcept : host_flags_(o.host_flags_) { *this = std::move(o); }
+    OnDemand &operator=(OnDemand &&o) noexcept { std::swap(d_, o.d_); std::swap(h_, o.h_); std::swap(bytes_, o.bytes_); return *this; }
+    ~OnDemand() { release(); }
+    size_t size() const { return bytes_; }
+    template <typename T = uint8_t> T *d() const { static_assert(DEV, "no device side"); return static_cast<T *>(d_); }
+    template <typename T = uint8_t> T *h() const { static_assert(HOST, "no page-locked side"); return static_cast<T *>(h_); }
+    // room for `need` bytes.  Growing frees first (the contents are lost) and allocates max(need, 2 * size()): hipFree / hipMalloc wait
+    // for the whole device, every other context's kernels included.  On failure the buffer is empty.
+    int ensure(str_er_ctx *c, size_t need, const char *what);
+
+private:
+    void release()
+    {
+        if (d_) (void)hipFree(d_);
+        if (h_) (void)hipHostFree(h_);
+        d_ = h_ = nullptr; bytes_ = 0;
+    }
+    void *d_ = nullptr, *h_ = nullptr;
+    size_t bytes_ = 0;
+    unsigned host_flags_;
+};
+using DevBuf = OnDemand<true, false>;
+using HostBuf = OnDemand<false, true>;
+using PairBuf = OnDemand<true, true>;
 
 } // namespace str_er_host
 using namespace str_er_host;
@@ -184,52 +217,47 @@ struct str_er_ctx {
     CandRec *d_cands = nullptr, *d_cands2 = nullptr;      // (second set: the layout after an NMS tie pass changed pools, then swapped)
     uint32_t *d_redo = nullptr;                          // candidates to classify again + their count (last word)
     TrackRec *d_track = nullptr; uint32_t *d_track_list = nullptr, *d_ranges = nullptr;   // STR_ER_STAGE_TRACK
-    uint32_t *d_group = nullptr, *d_group_pairs = nullptr; size_t group_words = 0, group_pair_cap = 0;   // STR_ER_STAGE_GROUP, grown on demand
+    DevBuf group, group_pairs;                        // STR_ER_STAGE_GROUP: the grouping workspace and the pair list, both of 32-bit words
     uint32_t *d_total = nullptr;
     uint32_t *d_wparent = nullptr;
     // tie planes exported by the device itself (k_export_tie_planes): TIE_SLOTS x tie_slot_bytes of page-locked, device-addressable memory,
     // then the slot -> plane table and the slot counter
     uint8_t *h_tie = nullptr; size_t tie_slot_bytes = 0; int n_tie_slots = 0; uint32_t *h_tie_plane = nullptr, *h_tie_count = nullptr;
-    uint8_t *h_replay = nullptr; size_t h_replay_bytes = 0;   // page-locked: the planes (and watch lists) the flood order walk reads
+    HostBuf replay_host{hipHostMallocMapped};         // the planes (and watch lists) the flood order walk reads
     uint32_t *d_watch = nullptr, *d_wstamp = nullptr; // NMS: watched key pixels per plane (k_nms -> flood order walk) and their stamps (-> k_nms)
     ReplayItem *d_replay_items = nullptr;
     uint32_t *d_alt_list = nullptr;                   // planes of the opposite-rule NMS pass (k_alt_list)
     uint32_t *d_tie_slot_plane = nullptr;             // plane of every tie slot of the batch (k_tie_slots -> k_export_tie_planes)
-    uint8_t *d_replay = nullptr; size_t replay_bytes = 0;   // flood-replay scratch, allocated the first time a plane has sibling ties
+    DevBuf replay;                                    // flood-replay scratch, of the first batch in which a plane has sibling ties
     uint32_t last_total = 0; bool last_valid = false;   // candidates of the last detect call, still in d_cands (str_er_gather_last)
     uint64_t n_replayed = 0;                          // planes whose NMS ties were decided by a flood replay (statistics)
     double   walk_ms_total = 0;                       // host time those walks took, summed over planes (statistics)
     uint64_t n_batches = 0;
     bool replay_on_gpu = false;                       // STR_ER_REPLAY=gpu: walk the flood with k_flood_order instead of a host core
     uint16_t *d_cand_plane = nullptr, *d_cand_plane2 = nullptr;
-    void *d_scratch = nullptr; size_t scratch_bytes = 0;
-    // STR_ER_WANT_MASKS / str_er_er_masks: created by the first call that wants masks, grown geometrically, never shrunk
-    uint8_t  *d_mask = nullptr, *h_mask = nullptr; size_t mask_bytes = 0;       // jobs | popcounts | words, on the device and page-locked
-    uint64_t *d_mask_scratch = nullptr; size_t mask_scratch_words = 0;         // rows of the boxes too large for LDS
-    // STR_ER_WANT_LINE_CROPS / str_er_line_crops (str_er_set_line_crop), and the buffers of the crop stage: created by the first call
-    // that wants crops, grown geometrically, never shrunk
+    // the on-demand buffers of the stages (OnDemand)
+    DevBuf   scratch;                 // whatever a stage lays out in it (ensure_scratch)
+    // STR_ER_WANT_MASKS / str_er_er_masks
+    PairBuf  mask;                    // jobs | popcounts | words
+    DevBuf   mask_scratch;            // 64-bit words: rows of the boxes too large for LDS
+    // STR_ER_WANT_LINE_CROPS / str_er_line_crops (str_er_set_line_crop)
     int32_t  crop_height = 32, crop_max_width = 1024; double crop_pad = 0.125;
-    uint8_t  *d_crop = nullptr, *h_crop = nullptr; size_t crop_bytes = 0;       // jobs | members | grey | glyph bytes, on the device and page-locked
-    // STR_ER_WANT_TEXT_MAP / _LINE_MAP / str_er_text_map_regions: the maps (bytes | ids), sized before a call enqueues anything, and the
-    // tables of the stage (tiles | list | regions | xs / ys); both created by the first call that wants maps, grown geometrically, never shrunk
-    uint8_t  *d_tmap = nullptr, *h_tmap = nullptr; size_t tmap_bytes = 0;
-    uint8_t  *d_tmap_tab = nullptr, *h_tmap_tab = nullptr; size_t tmap_tab_bytes = 0;
-    // STR_ER_WANT_FRAME_LINES / str_er_line_feet_regions (str_er_set_frame_merge): the stage's tables (lines | jobs | list | members |
-    // xs / ys), its output (counters | per-line statistics | pairs) and the footprint words; created by the first call that wants
-    // frame lines, grown geometrically, never shrunk
+    PairBuf  crop;                    // jobs | members | grey | glyph bytes
+    // STR_ER_WANT_TEXT_MAP / _LINE_MAP / str_er_text_map_regions
+    PairBuf  tmap;                    // the maps (bytes | ids), sized before a call enqueues anything
+    PairBuf  tmap_tab;                // tiles | list | regions | xs / ys
+    // STR_ER_WANT_FRAME_LINES / str_er_line_feet_regions (str_er_set_frame_merge)
     int32_t  merge_num = 1, merge_den = 2;
-    uint8_t  *d_foot_tab = nullptr, *h_foot_tab = nullptr; size_t foot_tab_bytes = 0;
-    uint8_t  *d_foot_out = nullptr, *h_foot_out = nullptr; size_t foot_out_bytes = 0;
-    uint64_t *d_foot_bits = nullptr; size_t foot_bits_words = 0;
-    // STR_ER_WANT_LINE_LINKS / str_er_link_feet (str_er_set_line_link): the link output (counters | pairs | the edge frames' footprint
-    // words on the page-locked side); created by the first call that wants links, grown geometrically, never shrunk
+    PairBuf  foot_tab;                // lines | jobs | list | members | xs / ys
+    PairBuf  foot_out;                // counters | per-line statistics | pairs
+    DevBuf   foot_bits;               // 64-bit words: the footprints
+    // STR_ER_WANT_LINE_LINKS / str_er_link_feet (str_er_set_line_link)
     int32_t  link_num = 1, link_den = 2;
-    uint8_t  *d_link_out = nullptr, *h_link_out = nullptr; size_t link_out_bytes = 0;
-    // STR_ER_WANT_LINE_GEOM / str_er_feet_geom: slots | records | hull vertices of k_foot_geom, and the scratch rows of lines taller than
-    // its LDS; created by the first call that wants the geometry, grown geometrically, never shrunk
-    uint8_t  *d_geom_out = nullptr, *h_geom_out = nullptr; size_t geom_out_bytes = 0;
-    uint64_t *d_geom_x = nullptr; size_t geom_x_words = 0;
-    uint8_t *d_strip_out = nullptr, *d_strip_in = nullptr; size_t strip_out_cap = 0, strip_in_cap = 0;   // strip blobs: made here / uploaded for a merge
+    PairBuf  link_out;                // counters | pairs | on the page-locked side the edge frames' footprint words
+    // STR_ER_WANT_LINE_GEOM / str_er_feet_geom
+    PairBuf  geom_out;                // slots | records | hull vertices of k_foot_geom
+    DevBuf   geom_x;                  // 64-bit words: the scratch rows of lines taller than its LDS
+    DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
     uint16_t *d_tile_nrec = nullptr;                  // records per tile (k_tile_tree -> k_group_merge)
@@ -251,7 +279,8 @@ struct str_er_ctx {
     // (count | list | labels | probabilities).  A batch with more ERs than guessed, or whose candidates an NMS tie pass re-made, is scored again the slow way.
     bool      ocr_spec = true;                        // STR_ER_OCR_SPEC=0 turns it off (developer switch)
     size_t    ocr_last_n = 0;                         // strong + weak ERs of the last batch scored
-    uint8_t  *h_ocr = nullptr; size_t h_ocr_cap = 0;  // page-locked results for up to so many ERs
+    HostBuf   ocr_host;                               // the results: two regions of 64 + 16 bytes per ER
+    size_t    ocr_cap() const { return ocr_host.size() ? (ocr_host.size() / 2 - 64) / 16 : 0; }      // ... for up to so many ERs
     uint64_t  n_ocr_spec = 0, n_ocr_redo = 0;         // statistics: batches scored behind classify / scored again
 
     // list calls (str_er_detect_*_list): frames of different sizes make a new layout every call, and its tables -- tile / seam-block / group
@@ -362,18 +391,14 @@ int alloc_node_records(str_er_ctx *c, size_t n)
     return STR_ER_OK;
 }
 
-int ensure_scratch(str_er_ctx *c, size_t bytes)
+// Where the need follows a batch's content (how many ERs are scored, how many lines have members, how many candidates are grouped,
+// how large a strip's blob is) a buffer asks for a quarter more than the call needs, so that the next, slightly larger batch does not
+// allocate again.  (The scratch used to ask for at least 1.5 x what there was as well: OnDemand::ensure never gives less than 2 x.)
+int ensure_quarter_more(str_er_ctx *c, DevBuf &b, size_t need, const char *what)
 {
-    if (bytes <= c->scratch_bytes) return STR_ER_OK;
-    // (a quarter more than asked for, and at least 1.5 x what there was: the need follows the batch's content -- how many ERs are scored, how many lines have
-    // members -- and hipFree / hipMalloc wait for the whole device, every other context's kernels included)
-    bytes = std::max(bytes + bytes / 4, c->scratch_bytes + c->scratch_bytes / 2);
-    if (c->d_scratch) { (void)hipFree(c->d_scratch); c->d_scratch = nullptr; c->scratch_bytes = 0; }
-    hipError_t e = hipMalloc(&c->d_scratch, bytes);
-    if (e != hipSuccess) return fail(c, STR_ER_ENOMEM, std::string("hipMalloc scratch: ") + hipGetErrorString(e));
-    c->scratch_bytes = bytes;
-    return STR_ER_OK;
+    return need <= b.size() ? STR_ER_OK : b.ensure(c, need + need / 4, what);
 }
+int ensure_scratch(str_er_ctx *c, size_t bytes) { return ensure_quarter_more(c, c->scratch, bytes, "scratch"); }
 
 void pyr_dims(int w0, int h0, int level, int &w, int &h)
 {
@@ -396,6 +421,21 @@ DetectParams make_dp(const str_er_ctx *c)
 }
 
 } // namespace
+
+template <bool DEV, bool HOST> int str_er_host::OnDemand<DEV, HOST>::ensure(str_er_ctx *c, size_t need, const char *what)
+{
+    if (need <= bytes_) return STR_ER_OK;
+    const size_t get = std::max(need, 2 * bytes_);
+    const auto   failed = [&](const char *call) {
+        release();
+        return fail(c, STR_ER_ENOMEM, std::string(call) + " (" + what + ", " + std::to_string(get) + " bytes)");
+    };
+    release();
+    if (DEV && hipMalloc(&d_, get) != hipSuccess) { d_ = nullptr; return failed("hipMalloc"); }
+    if (HOST && hipHostMalloc(&h_, get, host_flags_) != hipSuccess) { h_ = nullptr; return failed("hipHostMalloc"); }
+    bytes_ = get;
+    return STR_ER_OK;
+}
 
 namespace str_er_host {
 // ---- batch layout -------------------------------------------------------------------------------
@@ -451,7 +491,7 @@ int stage_input(str_er_ctx *c, const uint8_t *src, size_t bytes, int mem_kind, c
 // strokes[idx] receives its str_er_stroke
 int mask_stage(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, uint32_t *pixels, uint32_t *bits,
                const uint32_t **d_bits = nullptr, str_er_shape *shapes = nullptr, str_er_stroke *strokes = nullptr);
-// the launches of mask_stage alone: the words stay on the device, at *d_bits (in c->d_mask, valid until the context's next mask launch)
+// the launches of mask_stage alone: the words stay on the device, at *d_bits (in c->mask, valid until the context's next mask launch)
 int mask_launch(str_er_ctx *c, hipStream_t s, std::vector<MaskJob> &jobs, uint64_t n_words, float qscale, const uint32_t **d_bits, bool shapes = false,
                 bool strokes = false);
 // ---- defined in api_line_crops.cpp
@@ -477,8 +517,6 @@ int text_map_phase(str_er_ctx *c, hipStream_t s, const Batch &b, uint32_t stages
 // the first frame coordinate x in [0, W] whose sample ((2x + 1) * wp) / (2W) is >= a: the pre-image of a level box is
 // [first_sample_at(x), first_sample_at(x + w)), the exact inverse of the pixel rule of str_er_frame_map
 int32_t first_sample_at(int64_t a, int64_t W, int64_t wp);
-// the page-locked / device buffer pair d, h of `bytes`, grown to at least `need` (geometrically), never shrunk
-int grow_pair(str_er_ctx *c, uint8_t *&d, uint8_t *&h, size_t &bytes, size_t need, const char *what);
 // the uint16 tables xs(x) = ((2x + 1) * np) / (2n), x in [0, n), of the pixel rule, one per (frame size, level size) pair asked for
 struct SampleTabs {
     std::vector<uint16_t> tabs;

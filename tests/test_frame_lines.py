@@ -144,6 +144,40 @@ def test_single_stage_hand_made(S, cascade_paths, oracle, ow, oh):
     f.close()
 
 
+def test_pair_table_overflows_once(S, cascade_paths, oracle):
+    """48 lines of one bar each in the dark block of the hand-made plane, every two overlapping: 1128 pairs, more than the first table of
+    max(1024, 4 * 48) records, so the pair pass runs a second time with a table grown for all of them.  The same call on the same
+    context again finds the table large enough."""
+    f = _ctx(S, cascade_paths, max_width=1024, max_height=512, max_frames=1)
+    plane, _, _, _ = _hand_made(np.random.default_rng(5))
+    ph, pw = plane.shape
+    n_lines = 48
+    boxes = [(3 + k, 5 + k % 4, 200, 30, (5 + k % 4) * pw + 3 + k, 0) for k in range(n_lines)]
+    q = oracle.quant_lut(8)[plane]
+    masks = [flood(q, *b) for b in boxes]
+    assert all(m.all() for m in masks)                                  # every box is a full mask
+    ref = [R.footprint(pw, ph, [(pw, ph, b[0], b[1], m)]) for b, m in zip(boxes, masks)]
+    exp_pairs = R.all_pairs(ref, [0] * n_lines)
+    assert len(exp_pairs) == n_lines * (n_lines - 1) // 2 > max(1024, 4 * n_lines)
+    exp_bits = np.concatenate([r.words() for r in ref])
+    dup, frame_line, _, _ = R.frame_lines([(r.x, r.y, r.w, r.h) for r in ref], [r.pixels for r in ref], [0] * n_lines, [0] * n_lines, exp_pairs)
+    regions, lo = _regions(S, boxes), np.arange(n_lines, dtype=np.int32)
+    for _ in range(2):                  # (a fresh context: the table overflows; then it holds them all)
+        # one call of the C function with room for everything (ERFilter.line_feet_regions asks for the sizes first: that call would
+        # take the overflow, and the one whose output is read would not)
+        feet, bits, pairs = np.zeros(n_lines, S.LINE_FOOT_DTYPE), np.zeros(len(exp_bits), np.uint32), np.zeros(len(exp_pairs), S.LINE_PAIR_DTYPE)
+        nw, npairs = C.c_uint64(), C.c_int32()
+        rc = f.L.str_er_line_feet_regions(f.h, plane.ctypes.data, pw, ph, pw, regions.ctypes.data, lo.ctypes.data, n_lines, n_lines, pw, ph, feet.ctypes.data,
+                                          bits.ctypes.data, len(bits), C.byref(nw), pairs.ctypes.data, len(pairs), C.byref(npairs))
+        assert rc == 0, f.L.str_er_last_error(f.h)
+        assert nw.value == len(exp_bits) and npairs.value == len(exp_pairs)
+        assert [tuple(int(g[k]) for k in ("x", "y", "w", "h", "pixels")) for g in feet] == [(r.x, r.y, r.w, r.h, r.pixels) for r in ref]
+        assert len(bits) == len(exp_bits) and (bits == exp_bits).all()
+        assert [(int(p["a"]), int(p["b"]), int(p["inter"])) for p in pairs] == exp_pairs
+        assert [int(p["dup"]) for p in pairs] == dup and [int(g["frame_line"]) for g in feet] == frame_line
+    f.close()
+
+
 # ---- the fused call ------------------------------------------------------------------------------------------------------------------
 
 def test_fused_pyramid_1080p(S, cascade_paths):
