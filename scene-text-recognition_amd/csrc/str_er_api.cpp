@@ -6,6 +6,7 @@
 // counters and the packed candidate records.  No computation of the path happens on the
 // host; if the device or a kernel fails the call fails (there is no CPU fallback).
 #include "str_er_ctx.h"
+#include "frame_rules.h"
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -1711,154 +1712,9 @@ try {
     return STR_ER_OK;
 } ABI_GUARD(c)
 
-static int detect_bgr_impl(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch, int32_t n_frames,
-                           int mem_kind, uint32_t stages, const uint8_t *plane_select, str_er_result **out, bool nv12 = false);
-
-int str_er_detect_bgr(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch,
-                      int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out)
-try {
-    return detect_bgr_impl(c, bgr, w, h, stride, frame_pitch, n_frames, mem_kind, stages, nullptr, out);
-} ABI_GUARD(c)
-
-int str_er_detect_bgr_planes(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch,
-                             int32_t n_frames, int mem_kind, uint32_t stages, const uint8_t *plane_select, int32_t n_select,
-                             str_er_result **out)
-try {
-    if (!c) return STR_ER_EINVAL;
-    if (!plane_select || n_select != c->ppf) return fail(c, STR_ER_EINVAL, "plane_select needs one flag per logical plane of a frame (levels x channels of the context)");
-    bool any = false;
-    for (int i = 0; i < n_select; ++i) any |= plane_select[i] != 0;
-    if (!any) return fail(c, STR_ER_EINVAL, "plane_select selects nothing");
-    return detect_bgr_impl(c, bgr, w, h, stride, frame_pitch, n_frames, mem_kind, stages, plane_select, out);
-} ABI_GUARD(c)
-
-int str_er_detect_nv12(str_er_ctx *c, const uint8_t *nv12, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch,
-                       int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out)
-try {
-    return detect_bgr_impl(c, nv12, w, h, stride, frame_pitch, n_frames, mem_kind, stages, nullptr, out, /*nv12=*/true);
-} ABI_GUARD(c)
-
-// (nv12: `bgr` is a luma plane of h rows followed by the interleaved chroma plane of h / 2 rows, `stride` bytes per row both)
-static int detect_bgr_impl(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch, int32_t n_frames,
-                           int mem_kind, uint32_t stages, const uint8_t *plane_select, str_er_result **out, bool nv12)
-{
-    if (!c) return STR_ER_EINVAL;
-    const int64_t row_bytes = nv12 ? (int64_t)w : (int64_t)w * 3;                 // bytes of a source row
-    const int64_t src_rows = nv12 ? (int64_t)h + h / 2 : (int64_t)h;              // rows of a source frame
-    if (!bgr || !out || w < 1 || h < 1 || n_frames < 1 || stride < row_bytes) return fail(c, STR_ER_EINVAL, "bad frame arguments");
-    if (nv12 && ((w | h) & 1)) return fail(c, STR_ER_EINVAL, "NV12 frames have even width and height");
-    if (n_frames > 1 && frame_pitch < stride * src_rows) return fail(c, STR_ER_EINVAL, "frame_pitch smaller than a frame");
-    if (w > c->prm.max_width || h > c->prm.max_height || n_frames > c->prm.max_frames)
-        return fail(c, STR_ER_ECAPACITY, "frame larger than / more frames than the context capacity");
-    { const int rcs = check_call(c, stages, {true, !plane_select, false, plane_select != nullptr}); if (rcs != STR_ER_OK) return rcs; }
-    *out = nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(c, hipSetDevice(c->prm.device));
-    std::vector<int32_t> frame_wh;
-    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP | STR_ER_WANT_FRAME_LINES)) {     // (the maps' buffers: sized before anything of the call is enqueued; the frames' sizes for the frame lines)
-        for (int f = 0; f < n_frames; ++f) frame_wh.insert(frame_wh.end(), {w, h});
-        const int rcm = text_map_reserve(c, stages, frame_wh);
-        if (rcm != STR_ER_OK) return rcm;
-    }
-    const uint8_t *dbgr = nullptr;
-    int64_t dstride = stride, dpitch = frame_pitch;
-    if (mem_kind == STR_ER_MEM_HOST) {
-        // pack rows tightly while staging
-        dstride = row_bytes; dpitch = dstride * src_rows;
-        if ((size_t)dpitch * n_frames > c->in_bytes) return fail(c, STR_ER_ECAPACITY, "staging buffer too small");
-        if (stride == dstride && (n_frames == 1 || frame_pitch == dpitch))      // already tight: one linear copy
-            HIP_TRY(c, hipMemcpyAsync(c->d_in, bgr, (size_t)dpitch * n_frames, hipMemcpyHostToDevice, c->stream));
-        else
-            for (int f = 0; f < n_frames; ++f)
-                HIP_TRY(c, hipMemcpy2DAsync(c->d_in + (size_t)f * dpitch, (size_t)dstride, bgr + (size_t)f * frame_pitch, (size_t)stride,
-                                            (size_t)row_bytes, (size_t)src_rows, hipMemcpyHostToDevice, c->stream));
-        dbgr = c->d_in;
-    } else if (mem_kind == STR_ER_MEM_DEVICE) dbgr = bgr;
-    else return fail(c, STR_ER_EINVAL, "bad mem_kind");
-
-    // physical planes: per level, [Y, Cr, Cb], row stride padded to 64 bytes (a plane subset builds the pyramid only as far
-    // down as its deepest selected level)
-    int nl = c->prm.n_pyr_levels;
-    if (plane_select) {
-        int deepest = 0;
-        for (int l = 0; l < nl; ++l)
-            for (size_t k = 0; k < c->chans.size(); ++k) if (plane_select[(size_t)l * c->chans.size() + k]) deepest = l;
-        nl = deepest + 1;
-    }
-    std::vector<PlaneGeom> geo(nl);
-    size_t frame_bytes = 0;
-    for (int l = 0; l < nl; ++l) {
-        pyr_dims(w, h, l, geo[l].w, geo[l].h);
-        geo[l].stride = (int)align_up(geo[l].w, 64);
-        geo[l].off = frame_bytes;
-        frame_bytes += 3 * align_up((size_t)geo[l].stride * geo[l].h, 256);
-    }
-    if (frame_bytes * n_frames > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane pool too small");
-    auto plane_sz = [&](int l) { return align_up((size_t)geo[l].stride * geo[l].h, 256); };
-    c->n_ev = 0; c->profile.clear(); rec(c, "begin", nullptr, true);
-    const hipStream_t ws = c->stream;
-    if (nv12)
-        launch_nv12_to_ycrcb(ws, dbgr, w, h, dstride, dpitch, n_frames, c->d_pix + geo[0].off, c->d_pix + geo[0].off + plane_sz(0),
-                             c->d_pix + geo[0].off + 2 * plane_sz(0), geo[0].stride, (int64_t)frame_bytes);
-    else
-        launch_bgr_to_ycrcb(ws, dbgr, w, h, dstride, dpitch, n_frames, c->d_pix + geo[0].off, c->d_pix + geo[0].off + plane_sz(0),
-                            c->d_pix + geo[0].off + 2 * plane_sz(0), geo[0].stride, (int64_t)frame_bytes);
-    rec(c, "channels", ws);
-    for (int l = 1; l < nl; ++l)
-        launch_resize(ws, c->d_pix + geo[l - 1].off, geo[l - 1].w, geo[l - 1].h, geo[l - 1].stride, (int64_t)plane_sz(l - 1),
-                      (int64_t)frame_bytes, c->d_pix + geo[l].off, geo[l].w, geo[l].h, geo[l].stride, (int64_t)plane_sz(l),
-                      (int64_t)frame_bytes, 3, n_frames);
-    rec(c, "pyramid", ws);
-
-    Batch b;
-    for (int f = 0; f < n_frames; ++f)
-        for (int l = 0; l < nl; ++l)
-            for (size_t k = 0; k < c->chans.size(); ++k) {
-                if (plane_select && !plane_select[(size_t)l * c->chans.size() + k]) continue;
-                const int ch = c->chans[k];
-                const uint8_t *pix = c->d_pix + (size_t)f * frame_bytes + geo[l].off + (size_t)(ch % 3) * plane_sz(l);
-                add_plane(b, pix, geo[l].w, geo[l].h, geo[l].stride, ch >= 3, (uint32_t)f, ch, l);
-                b.planes.back().color_pitch = (uint32_t)plane_sz(l);
-            }
-    b.planes_per_image = plane_select ? 0 : (int)c->chans.size();
-    b.frame_wh = std::move(frame_wh);
-    return run_batch(c, b, stages, out, t0, true);
-}
-
-int str_er_detect_planes(str_er_ctx *c, const uint8_t *planes, int32_t w, int32_t h, int64_t stride, int64_t plane_pitch,
-                         int32_t n_planes, int mem_kind, uint32_t stages, str_er_result **out)
-try {
-    if (!c) return STR_ER_EINVAL;
-    if (!planes || !out || w < 1 || h < 1 || n_planes < 1 || stride < w) return fail(c, STR_ER_EINVAL, "bad plane arguments");
-    if (n_planes > 1 && plane_pitch < stride * (int64_t)h) return fail(c, STR_ER_EINVAL, "plane_pitch smaller than a plane");
-    if (w > c->prm.max_width || h > c->prm.max_height || n_planes > c->max_planes)
-        return fail(c, STR_ER_ECAPACITY, "plane larger than / more planes than the context capacity");
-    if (stride > 0x7FFFFFFF) return fail(c, STR_ER_EINVAL, "stride too large");
-    { const int rcs = check_call(c, stages, {false, false, false, false}); if (rcs != STR_ER_OK) return rcs; }
-    *out = nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(c, hipSetDevice(c->prm.device));
-    const uint8_t *dp = nullptr;
-    int dstride = (int)stride;
-    int64_t dpitch = plane_pitch;
-    if (mem_kind == STR_ER_MEM_HOST) {
-        dstride = (int)align_up(w, 64); dpitch = (int64_t)align_up((size_t)dstride * h, 256);
-        if ((size_t)dpitch * n_planes > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane pool too small");
-        for (int i = 0; i < n_planes; ++i)
-            HIP_TRY(c, hipMemcpy2DAsync(c->d_pix + (size_t)i * dpitch, (size_t)dstride, planes + (size_t)i * plane_pitch, (size_t)stride,
-                                        (size_t)w, (size_t)h, hipMemcpyHostToDevice, c->stream));
-        dp = c->d_pix;
-    } else if (mem_kind == STR_ER_MEM_DEVICE) dp = planes;
-    else return fail(c, STR_ER_EINVAL, "bad mem_kind");
-    Batch b;
-    for (int i = 0; i < n_planes; ++i)
-        add_plane(b, dp + (size_t)i * dpitch, w, h, dstride, 0, 0, i & 255, 0);
-    return run_batch(c, b, stages, out, t0, false);
-} ABI_GUARD(c)
-
 } // extern "C"
 
-// ---- lists of frames of different sizes ---------------------------------------------------------------------------------------------
+// ---- the frame front end: a call's frames (a uniform batch or a list of frames of different sizes) become the planes of one Batch ---
 namespace {
 
 // The page-locked staging buffer and the device job tables of list calls, sized for the context's largest layout (first list call).
@@ -1895,107 +1751,154 @@ struct ListCall {
     int finish(int rc) { done = rc == STR_ER_OK; return rc; }
 };
 
-int check_list(str_er_ctx *c, const str_er_image_ref *im, int32_t n, int32_t n_max, int mem_kind, int bpp, str_er_result **out, const char *what,
-               bool nv12 = false)
+int check_list(str_er_ctx *c, const str_er_image_ref *im, int32_t n, int32_t n_max, int mem_kind, SrcFormat fmt, str_er_result **out, const char *what)
 {
     if (!im || !out) return fail(c, STR_ER_EINVAL, "null argument");
     if (n < 1) return fail(c, STR_ER_EINVAL, std::string("empty ") + what + " list");
     if (n > n_max)
         return fail(c, STR_ER_ECAPACITY, std::to_string(n) + " " + what + "s: more than the context's " + std::to_string(n_max) + " per call");
     if (mem_kind != STR_ER_MEM_HOST && mem_kind != STR_ER_MEM_DEVICE) return fail(c, STR_ER_EINVAL, "bad mem_kind");
+    std::string msg;
     for (int32_t i = 0; i < n; ++i) {
-        const str_er_image_ref &r = im[i];
-        const std::string name = std::string(what) + " " + std::to_string(i);
-        if (!r.data) return fail(c, STR_ER_EINVAL, name + ": null data");
-        if (r.w < 1 || r.h < 1) return fail(c, STR_ER_EINVAL, name + ": empty");
-        if (r.stride < (int64_t)r.w * bpp) return fail(c, STR_ER_EINVAL, name + ": stride smaller than a row");
-        if (r.stride > 0x7FFFFFFF) return fail(c, STR_ER_EINVAL, name + ": stride too large");
-        if (nv12 && ((r.w | r.h) & 1)) return fail(c, STR_ER_EINVAL, name + ": NV12 frames have even width and height");
-        if (r.w > c->prm.max_width || r.h > c->prm.max_height)
-            return fail(c, STR_ER_ECAPACITY, name + ": " + std::to_string(r.w) + " x " + std::to_string(r.h) + " larger than the context capacity " +
-                                                 std::to_string(c->prm.max_width) + " x " + std::to_string(c->prm.max_height));
+        const int rc = check_image_ref(im[i], fmt, std::string(what) + " " + std::to_string(i), c->prm.max_width, c->prm.max_height, "the context capacity", msg);
+        if (rc != STR_ER_OK) return fail(c, rc, msg);
     }
     return STR_ER_OK;
 }
 
-// (nv12: a frame's `data` is its luma plane of h rows, the interleaved chroma plane of h / 2 rows follows, `stride` bytes per row both)
-int detect_list_impl(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out, bool nv12)
+// What every detect call does between its argument checks and its first copy or launch: the flags against the call's shape, the start of
+// its clock, the device, and the buffers of the frame maps for frames of frame_wh's sizes (none in a per-plane call).
+int begin_call(str_er_ctx *c, uint32_t stages, const CallShape &shape, const std::vector<int32_t> &frame_wh, str_er_result **out, std::chrono::steady_clock::time_point &t0)
 {
-    if (!c) return STR_ER_EINVAL;
-    int rc = check_list(c, frames, n_frames, c->prm.max_frames, mem_kind, nv12 ? 1 : 3, out, "frame", nv12);
-    if (rc != STR_ER_OK || (rc = check_call(c, stages, {true, true, false, false})) != STR_ER_OK) return rc;
+    const int rc = check_call(c, stages, shape);
+    if (rc != STR_ER_OK) return rc;
     *out = nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
+    t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->prm.device));
-    std::vector<int32_t> frame_wh;
-    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP | STR_ER_WANT_FRAME_LINES)) {     // (the maps' buffers: sized before anything of the call is enqueued; the frames' sizes for the frame lines)
-        for (int f = 0; f < n_frames; ++f) frame_wh.insert(frame_wh.end(), {frames[f].w, frames[f].h});
-        if ((rc = text_map_reserve(c, stages, frame_wh)) != STR_ER_OK) return rc;
-    }
-    if ((rc = ensure_list_buffers(c)) != STR_ER_OK) return rc;
-    const int n = n_frames, nl = c->prm.n_pyr_levels;
-    // physical planes: frame after frame, each laid out as detect_bgr_impl lays out one frame -- per level [Y, Cr, Cb] plane_sz apart
-    // (color_pitch finds Y from Cr / Cb for track), rows padded to 64 bytes
-    std::vector<PlaneGeom> geo((size_t)n * nl);
-    std::vector<size_t>    fbase((size_t)n);
-    size_t pix = 0;
-    for (int f = 0; f < n; ++f) {
-        fbase[(size_t)f] = pix;
-        size_t fb = 0;
-        for (int l = 0; l < nl; ++l) {
-            PlaneGeom &g = geo[(size_t)f * nl + l];
-            pyr_dims(frames[f].w, frames[f].h, l, g.w, g.h);
-            g.stride = (int)align_up(g.w, 64);
-            g.off = fb;
-            fb += 3 * align_up((size_t)g.stride * g.h, 256);
-        }
-        pix += fb;
-    }
-    if (pix > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane pool too small");
-    auto G = [&](int f, int l) -> const PlaneGeom & { return geo[(size_t)f * nl + l]; };
-    auto plane_sz = [&](int f, int l) { return align_up((size_t)G(f, l).stride * G(f, l).h, 256); };
+    if (stages & (STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP | STR_ER_WANT_FRAME_LINES)) return text_map_reserve(c, stages, frame_wh);
+    return STR_ER_OK;
+}
 
-    ListCall lc(c);
+// Where the physical planes of a call's frames lie in d_pix: frame after frame; in a frame level after level, per level [Y, Cr, Cb]
+// plane_sz apart (color_pitch finds Y from Cr / Cb for track); rows padded to 64 bytes, planes to 256.  Frames of one size are
+// bytes / n apart, which is what the uniform kernels take as their frame pitch.
+struct FramePlan {
+    const int nl; int n = 0;         // levels of a frame; frames added
+    std::vector<int32_t> wh;         // (w, h) of every frame
+    std::vector<PlaneGeom> geo;      // [f * nl + l]; off: where the level's Y plane starts in d_pix
+    size_t bytes = 0;                // of all frames
+    explicit FramePlan(int levels) : nl(levels) {}
+    const PlaneGeom &g(int f, int l) const { return geo[(size_t)f * nl + l]; }
+    size_t plane_sz(int f, int l) const { return align_up((size_t)g(f, l).stride * g(f, l).h, 256); }
+    void add(int32_t w, int32_t h)
+    {
+        wh.insert(wh.end(), {w, h});
+        for (int l = 0; l < nl; ++l) {
+            PlaneGeom g;
+            pyr_dims(w, h, l, g.w, g.h);
+            g.stride = (int)align_up(g.w, 64);
+            g.off = bytes;
+            bytes += 3 * align_up((size_t)g.stride * g.h, 256);
+            geo.push_back(g);
+        }
+        ++n;
+    }
+};
+
+// The planes of the plan's frames as one Batch: per frame and level the context's channels (plane_select: a subset of a frame's levels x channels).
+Batch frame_batch(const FramePlan &p, const str_er_ctx *c, const uint8_t *plane_select)
+{
+    Batch b;
+    const size_t nc = c->chans.size();
+    for (int f = 0; f < p.n; ++f)
+        for (int l = 0; l < p.nl; ++l)
+            for (size_t k = 0; k < nc; ++k) {
+                if (plane_select && !plane_select[(size_t)l * nc + k]) continue;
+                const int ch = c->chans[k];
+                const PlaneGeom &g = p.g(f, l);
+                add_plane(b, c->d_pix + g.off + (size_t)(ch % 3) * p.plane_sz(f, l), g.w, g.h, g.stride, ch >= 3, (uint32_t)f, ch, l);
+                b.planes.back().color_pitch = (uint32_t)p.plane_sz(f, l);
+            }
+    b.planes_per_image = plane_select ? 0 : (int)nc;
+    b.frame_wh = p.wh;
+    return b;
+}
+
+// Ingest of a uniform batch: host frames go to d_in with their rows packed tightly; channels and pyramid by the kernels that take a frame count and pitch.
+int ingest_uniform(str_er_ctx *c, const FramePlan &p, const uint8_t *bgr, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch, int mem_kind, SrcFormat fmt)
+{
+    const int64_t row_bytes = src_row_bytes(w, fmt), rows = src_rows(h, fmt);
+    const uint8_t *dbgr = bgr;
+    int64_t dstride = stride, dpitch = frame_pitch;
+    if (mem_kind == STR_ER_MEM_HOST) {
+        dstride = row_bytes; dpitch = dstride * rows;
+        if ((size_t)dpitch * p.n > c->in_bytes) return fail(c, STR_ER_ECAPACITY, "staging buffer too small");
+        if (stride == dstride && (p.n == 1 || frame_pitch == dpitch))      // already tight: one linear copy
+            HIP_TRY(c, hipMemcpyAsync(c->d_in, bgr, (size_t)dpitch * p.n, hipMemcpyHostToDevice, c->stream));
+        else
+            for (int f = 0; f < p.n; ++f)
+                HIP_TRY(c, hipMemcpy2DAsync(c->d_in + (size_t)f * dpitch, (size_t)dstride, bgr + (size_t)f * frame_pitch, (size_t)stride,
+                                            (size_t)row_bytes, (size_t)rows, hipMemcpyHostToDevice, c->stream));
+        dbgr = c->d_in;
+    } else if (mem_kind != STR_ER_MEM_DEVICE) return fail(c, STR_ER_EINVAL, "bad mem_kind");
+    if (p.bytes > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane pool too small");
+    c->n_ev = 0; c->profile.clear(); rec(c, "begin", nullptr, true);        // (behind the staging copies; a list call's is ahead of them)
+    const hipStream_t ws = c->stream;
+    const int64_t frame_bytes = (int64_t)(p.bytes / (size_t)p.n);
+    uint8_t *const y = c->d_pix + p.g(0, 0).off;
+    (fmt == SrcFormat::NV12 ? launch_nv12_to_ycrcb : launch_bgr_to_ycrcb)(ws, dbgr, w, h, dstride, dpitch, p.n, y, y + p.plane_sz(0, 0),
+                                                                         y + 2 * p.plane_sz(0, 0), p.g(0, 0).stride, frame_bytes);
+    rec(c, "channels", ws);
+    for (int l = 1; l < p.nl; ++l) {
+        const PlaneGeom &a = p.g(0, l - 1), &d = p.g(0, l);
+        launch_resize(ws, c->d_pix + a.off, a.w, a.h, a.stride, (int64_t)p.plane_sz(0, l - 1), frame_bytes, c->d_pix + d.off, d.w, d.h, d.stride,
+                      (int64_t)p.plane_sz(0, l), frame_bytes, 3, p.n);
+    }
+    rec(c, "pyramid", ws);
+    return STR_ER_OK;
+}
+
+// Ingest of a list: host frames go to d_in tightly, each from a 4-byte boundary when that fits; channels and pyramid by the kernels that find a
+// frame's job in a table (one table per kernel, uploaded through the call's staging buffer).
+int ingest_list(str_er_ctx *c, const FramePlan &p, const str_er_image_ref *frames, int mem_kind, SrcFormat fmt)
+{
+    const int n = p.n;
     c->n_ev = 0; c->profile.clear(); rec(c, "begin", nullptr, true);
     const hipStream_t ws = c->stream;
     std::vector<IngestJob> ij((size_t)n);
-    {   // host frames: staged tightly (3 w bytes a row; NV12: h + h / 2 rows of w bytes), each from a 4-byte boundary when that fits
-        auto row_of = [&](const str_er_image_ref &r) { return nv12 ? (size_t)r.w : (size_t)3 * r.w; };
-        auto rows_of = [&](const str_er_image_ref &r) { return nv12 ? (size_t)r.h + r.h / 2 : (size_t)r.h; };
-        size_t need = 0;
-        for (int f = 0; f < n; ++f) need = align_up(need, 4) + row_of(frames[f]) * rows_of(frames[f]);
-        const size_t al = need <= c->in_bytes ? 4 : 1;
-        size_t at = 0;
-        for (int f = 0; f < n; ++f) {
-            const str_er_image_ref &r = frames[f];
-            IngestJob &j = ij[(size_t)f];
-            const size_t row = row_of(r), rows = rows_of(r);
-            if (mem_kind == STR_ER_MEM_HOST) {
-                at = align_up(at, al);
-                if (at + row * rows > c->in_bytes) return fail(c, STR_ER_ECAPACITY, "staging buffer too small");
-                if (r.stride == (int64_t)row) HIP_TRY(c, hipMemcpyAsync(c->d_in + at, r.data, row * rows, hipMemcpyHostToDevice, ws));
-                else HIP_TRY(c, hipMemcpy2DAsync(c->d_in + at, row, r.data, (size_t)r.stride, row, rows, hipMemcpyHostToDevice, ws));
-                j.src = c->d_in + at; j.stride = (int64_t)row;
-                at += row * rows;
-            } else { j.src = r.data; j.stride = r.stride; }
-            j.dst = c->d_pix + fbase[(size_t)f] + G(f, 0).off; j.plane_pitch = (int64_t)plane_sz(f, 0);
-            j.w = r.w; j.h = r.h; j.dstride = G(f, 0).stride;
-        }
+    size_t need = 0;
+    for (int f = 0; f < n; ++f) need = align_up(need, 4) + (size_t)(src_row_bytes(frames[f].w, fmt) * src_rows(frames[f].h, fmt));
+    const size_t al = need <= c->in_bytes ? 4 : 1;
+    size_t at = 0;
+    for (int f = 0; f < n; ++f) {
+        const str_er_image_ref &r = frames[f];
+        IngestJob &j = ij[(size_t)f];
+        const size_t row = (size_t)src_row_bytes(r.w, fmt), rows = (size_t)src_rows(r.h, fmt);
+        if (mem_kind == STR_ER_MEM_HOST) {
+            at = align_up(at, al);
+            if (at + row * rows > c->in_bytes) return fail(c, STR_ER_ECAPACITY, "staging buffer too small");
+            if (r.stride == (int64_t)row) HIP_TRY(c, hipMemcpyAsync(c->d_in + at, r.data, row * rows, hipMemcpyHostToDevice, ws));
+            else HIP_TRY(c, hipMemcpy2DAsync(c->d_in + at, row, r.data, (size_t)r.stride, row, rows, hipMemcpyHostToDevice, ws));
+            j.src = c->d_in + at; j.stride = (int64_t)row;
+            at += row * rows;
+        } else { j.src = r.data; j.stride = r.stride; }
+        j.dst = c->d_pix + p.g(f, 0).off; j.plane_pitch = (int64_t)p.plane_sz(f, 0);
+        j.w = r.w; j.h = r.h; j.dstride = p.g(f, 0).stride;
     }
     std::vector<uint8_t> tab(ingest_table_bytes(n));
     const uint32_t n_wg = build_ingest_table(ij.data(), n, tab.data());
     HIP_TRY(c, table_copy(c, c->d_list_tab, tab.data(), tab.size()));
-    if (nv12) launch_nv12_to_ycrcb_list(ws, c->d_list_tab, n, n_wg);
+    if (fmt == SrcFormat::NV12) launch_nv12_to_ycrcb_list(ws, c->d_list_tab, n, n_wg);
     else launch_bgr_to_ycrcb_list(ws, c->d_list_tab, n, n_wg);
     rec(c, "channels", ws);
     size_t tab_at = align_up(ingest_table_bytes(c->prm.max_frames), 256);
     std::vector<ResizeJob> rj((size_t)n);
-    for (int l = 1; l < nl; ++l) {
+    for (int l = 1; l < p.nl; ++l) {
         for (int f = 0; f < n; ++f) {
-            const PlaneGeom &a = G(f, l - 1), &d = G(f, l);
+            const PlaneGeom &a = p.g(f, l - 1), &d = p.g(f, l);
             ResizeJob &j = rj[(size_t)f];
-            j.src = c->d_pix + fbase[(size_t)f] + a.off; j.dst = c->d_pix + fbase[(size_t)f] + d.off;
-            j.splane_pitch = (int64_t)plane_sz(f, l - 1); j.dplane_pitch = (int64_t)plane_sz(f, l);
+            j.src = c->d_pix + a.off; j.dst = c->d_pix + d.off;
+            j.splane_pitch = (int64_t)p.plane_sz(f, l - 1); j.dplane_pitch = (int64_t)p.plane_sz(f, l);
             j.sw = a.w; j.sh = a.h; j.sstride = a.stride; j.dw = d.w; j.dh = d.h; j.dstride = d.stride;
         }
         tab.assign(resize_table_bytes(n), 0);
@@ -2005,58 +1908,125 @@ int detect_list_impl(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_fr
         tab_at += align_up(resize_table_bytes(c->prm.max_frames), 256);
     }
     rec(c, "pyramid", ws);
+    return STR_ER_OK;
+}
 
-    Batch b;
-    for (int f = 0; f < n; ++f)
-        for (int l = 0; l < nl; ++l)
-            for (size_t k = 0; k < c->chans.size(); ++k) {
-                const int ch = c->chans[k];
-                const uint8_t *p = c->d_pix + fbase[(size_t)f] + G(f, l).off + (size_t)(ch % 3) * plane_sz(f, l);
-                add_plane(b, p, G(f, l).w, G(f, l).h, G(f, l).stride, ch >= 3, (uint32_t)f, ch, l);
-                b.planes.back().color_pitch = (uint32_t)plane_sz(f, l);
-            }
-    b.planes_per_image = (int)c->chans.size();
-    b.frame_wh = std::move(frame_wh);
-    return lc.finish(run_batch(c, b, stages, out, t0, true));
+int detect_bgr_impl(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch, int32_t n_frames, int mem_kind,
+                    uint32_t stages, const uint8_t *plane_select, str_er_result **out, SrcFormat fmt)
+{
+    if (!c) return STR_ER_EINVAL;
+    if (!bgr || !out || w < 1 || h < 1 || n_frames < 1 || stride < src_row_bytes(w, fmt)) return fail(c, STR_ER_EINVAL, "bad frame arguments");
+    if (fmt == SrcFormat::NV12 && ((w | h) & 1)) return fail(c, STR_ER_EINVAL, "NV12 frames have even width and height");
+    if (n_frames > 1 && frame_pitch < stride * src_rows(h, fmt)) return fail(c, STR_ER_EINVAL, "frame_pitch smaller than a frame");
+    if (w > c->prm.max_width || h > c->prm.max_height || n_frames > c->prm.max_frames)
+        return fail(c, STR_ER_ECAPACITY, "frame larger than / more frames than the context capacity");
+    int nl = plane_select ? 1 : c->prm.n_pyr_levels;
+    if (plane_select)      // (a plane subset builds the pyramid only as far down as its deepest selected level: flag l * channels + k)
+        for (int i = 0, nc = (int)c->chans.size(); i < c->ppf; ++i) if (plane_select[i]) nl = i / nc + 1;
+    FramePlan p(nl);
+    for (int f = 0; f < n_frames; ++f) p.add(w, h);
+    std::chrono::steady_clock::time_point t0;
+    int rc = begin_call(c, stages, {true, !plane_select, false, plane_select != nullptr}, p.wh, out, t0);
+    if (rc != STR_ER_OK || (rc = ingest_uniform(c, p, bgr, w, h, stride, frame_pitch, mem_kind, fmt)) != STR_ER_OK) return rc;
+    return run_batch(c, frame_batch(p, c, plane_select), stages, out, t0, true);
+}
+
+int detect_list_impl(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out, SrcFormat fmt)
+{
+    if (!c) return STR_ER_EINVAL;
+    int rc = check_list(c, frames, n_frames, c->prm.max_frames, mem_kind, fmt, out, "frame");
+    if (rc != STR_ER_OK) return rc;
+    FramePlan p(c->prm.n_pyr_levels);
+    for (int f = 0; f < n_frames; ++f) p.add(frames[f].w, frames[f].h);
+    std::chrono::steady_clock::time_point t0;
+    if ((rc = begin_call(c, stages, {true, true, false, false}, p.wh, out, t0)) != STR_ER_OK || (rc = ensure_list_buffers(c)) != STR_ER_OK) return rc;
+    if (p.bytes > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane pool too small");
+    ListCall lc(c);
+    if ((rc = ingest_list(c, p, frames, mem_kind, fmt)) != STR_ER_OK) return rc;
+    return lc.finish(run_batch(c, frame_batch(p, c, nullptr), stages, out, t0, true));
+}
+
+// Plane i of a per-plane call: a host plane is staged at `at` of d_pix (rows padded to 64 bytes, the plane to 256), a device plane used where it lies.
+int add_call_plane(str_er_ctx *c, Batch &b, const uint8_t *pix, int32_t w, int32_t h, int64_t stride, int i, int mem_kind, size_t &at)
+{
+    if (mem_kind == STR_ER_MEM_HOST) {
+        const size_t ds = align_up(w, 64), sz = align_up(ds * h, 256);
+        if (at + sz > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane pool too small");
+        HIP_TRY(c, hipMemcpy2DAsync(c->d_pix + at, ds, pix, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, c->stream));
+        pix = c->d_pix + at; stride = (int64_t)ds; at += sz;
+    }
+    add_plane(b, pix, w, h, (int)stride, 0, 0, i & 255, 0);
+    return STR_ER_OK;
 }
 
 } // namespace
 
 extern "C" {
 
+int str_er_detect_bgr(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch,
+                      int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out)
+try {
+    return detect_bgr_impl(c, bgr, w, h, stride, frame_pitch, n_frames, mem_kind, stages, nullptr, out, SrcFormat::BGR);
+} ABI_GUARD(c)
+
+int str_er_detect_bgr_planes(str_er_ctx *c, const uint8_t *bgr, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch,
+                             int32_t n_frames, int mem_kind, uint32_t stages, const uint8_t *plane_select, int32_t n_select,
+                             str_er_result **out)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (!plane_select || n_select != c->ppf) return fail(c, STR_ER_EINVAL, "plane_select needs one flag per logical plane of a frame (levels x channels of the context)");
+    bool any = false;
+    for (int i = 0; i < n_select; ++i) any |= plane_select[i] != 0;
+    if (!any) return fail(c, STR_ER_EINVAL, "plane_select selects nothing");
+    return detect_bgr_impl(c, bgr, w, h, stride, frame_pitch, n_frames, mem_kind, stages, plane_select, out, SrcFormat::BGR);
+} ABI_GUARD(c)
+
+int str_er_detect_nv12(str_er_ctx *c, const uint8_t *nv12, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch,
+                       int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out)
+try {
+    return detect_bgr_impl(c, nv12, w, h, stride, frame_pitch, n_frames, mem_kind, stages, nullptr, out, SrcFormat::NV12);
+} ABI_GUARD(c)
+
 int str_er_detect_bgr_list(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out)
 try {
-    return detect_list_impl(c, frames, n_frames, mem_kind, stages, out, false);
+    return detect_list_impl(c, frames, n_frames, mem_kind, stages, out, SrcFormat::BGR);
 } ABI_GUARD(c)
 
 int str_er_detect_nv12_list(str_er_ctx *c, const str_er_image_ref *frames, int32_t n_frames, int mem_kind, uint32_t stages, str_er_result **out)
 try {
-    return detect_list_impl(c, frames, n_frames, mem_kind, stages, out, true);
+    return detect_list_impl(c, frames, n_frames, mem_kind, stages, out, SrcFormat::NV12);
+} ABI_GUARD(c)
+
+int str_er_detect_planes(str_er_ctx *c, const uint8_t *planes, int32_t w, int32_t h, int64_t stride, int64_t plane_pitch,
+                         int32_t n_planes, int mem_kind, uint32_t stages, str_er_result **out)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (!planes || !out || w < 1 || h < 1 || n_planes < 1 || stride < w) return fail(c, STR_ER_EINVAL, "bad plane arguments");
+    if (n_planes > 1 && plane_pitch < stride * (int64_t)h) return fail(c, STR_ER_EINVAL, "plane_pitch smaller than a plane");
+    if (w > c->prm.max_width || h > c->prm.max_height || n_planes > c->max_planes)
+        return fail(c, STR_ER_ECAPACITY, "plane larger than / more planes than the context capacity");
+    if (stride > 0x7FFFFFFF) return fail(c, STR_ER_EINVAL, "stride too large");
+    std::chrono::steady_clock::time_point t0;
+    int rc = begin_call(c, stages, {false, false, false, false}, {}, out, t0);
+    if (rc != STR_ER_OK) return rc;
+    if (mem_kind != STR_ER_MEM_HOST && mem_kind != STR_ER_MEM_DEVICE) return fail(c, STR_ER_EINVAL, "bad mem_kind");
+    Batch b; size_t at = 0;          // (at: where the next host plane is staged in d_pix)
+    for (int i = 0; i < n_planes; ++i)
+        if ((rc = add_call_plane(c, b, planes + (size_t)i * plane_pitch, w, h, stride, i, mem_kind, at)) != STR_ER_OK) return rc;
+    return run_batch(c, b, stages, out, t0, false);
 } ABI_GUARD(c)
 
 int str_er_detect_planes_list(str_er_ctx *c, const str_er_image_ref *planes, int32_t n_planes, int mem_kind, uint32_t stages, str_er_result **out)
 try {
     if (!c) return STR_ER_EINVAL;
-    int rc = check_list(c, planes, n_planes, c->max_planes, mem_kind, 1, out, "plane");
-    if (rc != STR_ER_OK || (rc = check_call(c, stages, {false, false, false, false})) != STR_ER_OK) return rc;
-    *out = nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(c, hipSetDevice(c->prm.device));
+    int rc = check_list(c, planes, n_planes, c->max_planes, mem_kind, SrcFormat::PLANE, out, "plane");
+    std::chrono::steady_clock::time_point t0;
+    if (rc != STR_ER_OK || (rc = begin_call(c, stages, {false, false, false, false}, {}, out, t0)) != STR_ER_OK) return rc;
     if ((rc = ensure_list_buffers(c)) != STR_ER_OK) return rc;
     ListCall lc(c);
-    Batch b;
-    size_t at = 0;
-    for (int i = 0; i < n_planes; ++i) {
-        const str_er_image_ref &r = planes[i];
-        if (mem_kind == STR_ER_MEM_HOST) {      // (as str_er_detect_planes stages a plane: rows padded to 64 bytes)
-            const int ds = (int)align_up(r.w, 64);
-            const size_t sz = align_up((size_t)ds * r.h, 256);
-            if (at + sz > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane pool too small");
-            HIP_TRY(c, hipMemcpy2DAsync(c->d_pix + at, (size_t)ds, r.data, (size_t)r.stride, (size_t)r.w, (size_t)r.h, hipMemcpyHostToDevice, c->stream));
-            add_plane(b, c->d_pix + at, r.w, r.h, ds, 0, 0, i & 255, 0);
-            at += sz;
-        } else add_plane(b, r.data, r.w, r.h, (int)r.stride, 0, 0, i & 255, 0);
-    }
+    Batch b; size_t at = 0;          // (at: where the next host plane is staged in d_pix)
+    for (int i = 0; i < n_planes; ++i)
+        if ((rc = add_call_plane(c, b, planes[i].data, planes[i].w, planes[i].h, planes[i].stride, i, mem_kind, at)) != STR_ER_OK) return rc;
     return lc.finish(run_batch(c, b, stages, out, t0, false));
 } ABI_GUARD(c)
 

@@ -6,7 +6,7 @@
 // page-locked staging buffer per context and one worker thread per context: the producer acquires a staging buffer,
 // decodes / copies its frames straight into it, submits; the worker issues the H2D copy (true DMA, the buffer is pinned)
 // and the kernels on its context's stream while the other contexts compute; results come back in submission order.
-// Built on the public C ABI only (str_er_create / str_er_detect_bgr / ...).
+// Built on the public C ABI only (str_er_create / str_er_detect_bgr / ...); of the library's own headers it takes the frame rules alone.
 //
 // Round 4: the uploads take TURNS, in submission order, and a batch's kernels start only behind its own upload.  Before, every worker handed its
 // pinned buffer to str_er_detect_bgr (upload + kernels in one call): the `depth` uploads in flight shared the host link and the `depth` batches of
@@ -19,6 +19,7 @@
 // the caller's choosing (str_er_detect_bgr_list / _nv12_list).  A list uploads the byte span from its lowest frame start to its highest frame
 // end, to the same offsets of the slot's device buffer, and is detected there (STR_ER_MEM_DEVICE refs); the turns are the same for both kinds.
 #include "../../include/str_er.h"
+#include "frame_rules.h"
 
 #include <hip/hip_runtime.h>
 
@@ -34,6 +35,8 @@
 #include <thread>
 #include <vector>
 
+using namespace str_er_host;
+
 struct str_er_stream {
     static constexpr int MAX_UPLOAD_STREAMS = 4;
     struct Slot {
@@ -47,7 +50,7 @@ struct str_er_stream {
         int32_t  w = 0, h = 0, n_frames = 0;
         int64_t  stride = 0, pitch = 0;
         uint32_t stages = 0;
-        bool     nv12 = false;
+        SrcFormat fmt = SrcFormat::BGR;
         bool     list = false;                  // a list job: refs (data unused) at offs into the buffer; the upload is [span_lo, span_hi)
         std::vector<str_er_image_ref> refs, dev_refs;
         std::vector<size_t> offs;
@@ -92,9 +95,8 @@ void worker_main(str_er_stream *s, int idx)
         // (nothing may leave this thread as an exception -- std::terminate -- and the upload turn must pass on whatever happens: every later ticket waits for it)
         try {
             // the upload, when it is this batch's turn (submission order); the turn passes on when the bytes have landed
-            const int64_t rows = sl.nv12 ? (int64_t)sl.h + sl.h / 2 : (int64_t)sl.h;
             const size_t lo = sl.list ? sl.span_lo : 0;
-            const size_t bytes = sl.list ? sl.span_hi - sl.span_lo : (size_t)(sl.n_frames - 1) * (size_t)sl.pitch + (size_t)sl.stride * (size_t)rows;
+            const size_t bytes = sl.list ? sl.span_hi - sl.span_lo : (size_t)(sl.n_frames - 1) * (size_t)sl.pitch + (size_t)sl.stride * (size_t)src_rows(sl.h, sl.fmt);
             {
                 std::unique_lock<std::mutex> lk(s->mu);
                 s->cv.wait(lk, [&] { return s->upload_turn == sl.ticket; });
@@ -136,11 +138,11 @@ void worker_main(str_er_stream *s, int idx)
             if (rc == STR_ER_OK && sl.list) {
                 sl.dev_refs = sl.refs;
                 for (size_t i = 0; i < sl.offs.size(); ++i) sl.dev_refs[i].data = sl.d_in + sl.offs[i];
-                rc = sl.nv12 ? str_er_detect_nv12_list(sl.ctx, sl.dev_refs.data(), (int32_t)sl.dev_refs.size(), STR_ER_MEM_DEVICE, sl.stages, &r)
-                             : str_er_detect_bgr_list(sl.ctx, sl.dev_refs.data(), (int32_t)sl.dev_refs.size(), STR_ER_MEM_DEVICE, sl.stages, &r);
+                rc = sl.fmt == SrcFormat::NV12 ? str_er_detect_nv12_list(sl.ctx, sl.dev_refs.data(), (int32_t)sl.dev_refs.size(), STR_ER_MEM_DEVICE, sl.stages, &r)
+                                               : str_er_detect_bgr_list(sl.ctx, sl.dev_refs.data(), (int32_t)sl.dev_refs.size(), STR_ER_MEM_DEVICE, sl.stages, &r);
             } else if (rc == STR_ER_OK)
-                rc = sl.nv12 ? str_er_detect_nv12(sl.ctx, sl.d_in, sl.w, sl.h, sl.stride, sl.pitch, sl.n_frames, STR_ER_MEM_DEVICE, sl.stages, &r)
-                             : str_er_detect_bgr(sl.ctx, sl.d_in, sl.w, sl.h, sl.stride, sl.pitch, sl.n_frames, STR_ER_MEM_DEVICE, sl.stages, &r);
+                rc = sl.fmt == SrcFormat::NV12 ? str_er_detect_nv12(sl.ctx, sl.d_in, sl.w, sl.h, sl.stride, sl.pitch, sl.n_frames, STR_ER_MEM_DEVICE, sl.stages, &r)
+                                               : str_er_detect_bgr(sl.ctx, sl.d_in, sl.w, sl.h, sl.stride, sl.pitch, sl.n_frames, STR_ER_MEM_DEVICE, sl.stages, &r);
         } catch (...) {
             rc = STR_ER_ENOMEM; r = nullptr; upload_failed = true;
             try { sl.err = "stream worker: out of host memory"; } catch (...) { }
@@ -155,6 +157,79 @@ void worker_main(str_er_stream *s, int idx)
         }
         s->cv.notify_all();
     }
+}
+
+// A submission's slot is acquired and idle (under the stream's lock), or the error is written.
+bool slot_idle(str_er_stream *s, const str_er_stream::Slot &sl)
+{
+    if (!sl.busy || sl.has_job || sl.done) s->err = "slot was not acquired (or is already submitted)";
+    return sl.busy && !sl.has_job && !sl.done;
+}
+
+// The job recorded in the slot gets its ticket and goes to the slot's worker.  (A submission that fails before this leaves the slot acquired.)
+int enqueue(str_er_stream *s, int32_t slot, std::unique_lock<std::mutex> &lk, uint32_t stages, SrcFormat fmt, bool list, uint64_t *ticket)
+{
+    str_er_stream::Slot &sl = s->slots[(size_t)slot];
+    sl.stages = stages; sl.fmt = fmt; sl.list = list;
+    sl.ticket = s->next_ticket++; sl.has_job = true;
+    s->order.push_back(slot);
+    if (ticket) *ticket = sl.ticket;
+    lk.unlock();
+    s->cv.notify_all();
+    return STR_ER_OK;
+}
+
+int submit_impl(str_er_stream *s, int32_t slot, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch, int32_t n_frames, uint32_t stages,
+                uint64_t *ticket, SrcFormat fmt)
+{
+    if (!s || slot < 0 || (size_t)slot >= s->slots.size()) return STR_ER_EINVAL;
+    str_er_stream::Slot &sl = s->slots[(size_t)slot];
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (!slot_idle(s, sl)) return STR_ER_ESTATE;
+    const int64_t rows = src_rows(h, fmt);
+    if (w < 1 || h < 1 || n_frames < 1 || stride < src_row_bytes(w, fmt) || (n_frames > 1 && frame_pitch < stride * rows) ||
+        (uint64_t)(n_frames - 1) * (uint64_t)frame_pitch + (uint64_t)stride * (uint64_t)rows > (uint64_t)s->slot_bytes) {
+        s->err = "frames do not fit the staging buffer";
+        return STR_ER_EINVAL;
+    }
+    sl.w = w; sl.h = h; sl.stride = stride; sl.pitch = frame_pitch; sl.n_frames = n_frames;
+    return enqueue(s, slot, lk, stages, fmt, false, ticket);
+}
+
+// A list job: every frame checked against the contexts' capacity and the slot's buffer before anything is recorded.
+int submit_list_impl(str_er_stream *s, int32_t slot, const str_er_image_ref *frames, int32_t n, uint32_t stages, uint64_t *ticket, SrcFormat fmt)
+{
+    if (!s || slot < 0 || (size_t)slot >= s->slots.size()) return STR_ER_EINVAL;
+    str_er_stream::Slot &sl = s->slots[(size_t)slot];
+    std::unique_lock<std::mutex> lk(s->mu);
+    if (!slot_idle(s, sl)) return STR_ER_ESTATE;
+    if (!frames) { s->err = "null frame list"; return STR_ER_EINVAL; }
+    if (n < 1) { s->err = "empty frame list"; return STR_ER_EINVAL; }
+    if (n > s->max_frames) {
+        s->err = std::to_string(n) + " frames: more than the stream's " + std::to_string(s->max_frames) + " per submission";
+        return STR_ER_ECAPACITY;
+    }
+    const uintptr_t base = reinterpret_cast<uintptr_t>(sl.pinned);
+    size_t lo = s->slot_bytes, hi = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        const str_er_image_ref &r = frames[i];
+        const std::string name = "frame " + std::to_string(i);
+        const int rc = check_image_ref(r, fmt, name, s->max_width, s->max_height, "the stream's capacity", s->err);
+        if (rc != STR_ER_OK) return rc;
+        const uintptr_t at = reinterpret_cast<uintptr_t>(r.data);
+        const uint64_t  end = (uint64_t)(src_rows(r.h, fmt) - 1) * (uint64_t)r.stride + (uint64_t)src_row_bytes(r.w, fmt);   // from the first pixel to the end of the last row
+        if (at < base || at - base > s->slot_bytes || end > s->slot_bytes - (at - base)) {
+            s->err = name + ": not wholly inside the slot's staging buffer";
+            return STR_ER_EINVAL;
+        }
+        lo = std::min(lo, (size_t)(at - base));
+        hi = std::max(hi, (size_t)(at - base + end));
+    }
+    sl.refs.assign(frames, frames + n);
+    sl.offs.resize((size_t)n);
+    for (int32_t i = 0; i < n; ++i) sl.offs[(size_t)i] = (size_t)(reinterpret_cast<uintptr_t>(frames[i].data) - base);
+    sl.span_lo = lo; sl.span_hi = hi;
+    return enqueue(s, slot, lk, stages, fmt, true, ticket);
 }
 
 } // namespace
@@ -264,51 +339,27 @@ try {
     return STR_ER_ESTATE;
 } STREAM_GUARD(s)
 
-static int submit_impl(str_er_stream *s, int32_t slot, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch, int32_t n_frames,
-                       uint32_t stages, uint64_t *ticket, bool nv12)
-{
-    if (!s || slot < 0 || (size_t)slot >= s->slots.size()) return STR_ER_EINVAL;
-    str_er_stream::Slot &sl = s->slots[(size_t)slot];
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (!sl.busy || sl.has_job || sl.done) { s->err = "slot was not acquired (or is already submitted)"; return STR_ER_ESTATE; }
-        const int64_t row = nv12 ? (int64_t)w : (int64_t)w * 3, rows = nv12 ? (int64_t)h + h / 2 : (int64_t)h;
-        if (w < 1 || h < 1 || n_frames < 1 || stride < row || (n_frames > 1 && frame_pitch < stride * rows) ||
-            (uint64_t)(n_frames - 1) * (uint64_t)frame_pitch + (uint64_t)stride * (uint64_t)rows > (uint64_t)s->slot_bytes) {
-            s->err = "frames do not fit the staging buffer";
-            return STR_ER_EINVAL;
-        }
-        sl.w = w; sl.h = h; sl.stride = stride; sl.pitch = frame_pitch; sl.n_frames = n_frames; sl.stages = stages; sl.nv12 = nv12; sl.list = false;
-        sl.ticket = s->next_ticket++;
-        sl.has_job = true;
-        s->order.push_back(slot);
-        if (ticket) *ticket = sl.ticket;
-    }
-    s->cv.notify_all();
-    return STR_ER_OK;
-}
-
 int str_er_stream_submit(str_er_stream *s, int32_t slot, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch, int32_t n_frames,
                          uint32_t stages, uint64_t *ticket)
 try {
-    return submit_impl(s, slot, w, h, stride, frame_pitch, n_frames, stages, ticket, false);
+    return submit_impl(s, slot, w, h, stride, frame_pitch, n_frames, stages, ticket, SrcFormat::BGR);
 } STREAM_GUARD(s)
 
 int str_er_stream_submit_nv12(str_er_stream *s, int32_t slot, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch, int32_t n_frames,
                               uint32_t stages, uint64_t *ticket)
 try {
-    return submit_impl(s, slot, w, h, stride, frame_pitch, n_frames, stages, ticket, true);
+    return submit_impl(s, slot, w, h, stride, frame_pitch, n_frames, stages, ticket, SrcFormat::NV12);
 } STREAM_GUARD(s)
 
 int str_er_stream_submit_copy(str_er_stream *s, const uint8_t *bgr, int32_t w, int32_t h, int64_t stride, int64_t frame_pitch,
                               int32_t n_frames, uint32_t stages, uint64_t *ticket)
 try {
-    if (!s || !bgr || w < 1 || h < 1 || n_frames < 1 || stride < (int64_t)w * 3) return STR_ER_EINVAL;
+    if (!s || !bgr || w < 1 || h < 1 || n_frames < 1 || stride < src_row_bytes(w, SrcFormat::BGR)) return STR_ER_EINVAL;
     int32_t  slot = -1;
     uint8_t *buf = nullptr;
     int rc = str_er_stream_acquire(s, &slot, &buf, nullptr);
     if (rc != STR_ER_OK) return rc;
-    const size_t row = (size_t)w * 3, fb = row * (size_t)h;
+    const size_t row = (size_t)src_row_bytes(w, SrcFormat::BGR), fb = row * (size_t)h;
     if (fb * (size_t)n_frames > s->slot_bytes) {
         std::lock_guard<std::mutex> lk(s->mu);
         s->slots[(size_t)slot].busy = false;
@@ -321,81 +372,28 @@ try {
     return str_er_stream_submit(s, slot, w, h, (int64_t)row, (int64_t)fb, n_frames, stages, ticket);
 } STREAM_GUARD(s)
 
-// A list job: every frame checked against the slot's buffer and the contexts' capacity before anything is recorded (an error leaves the slot
-// acquired, as submit_impl does).
-static int submit_list_impl(str_er_stream *s, int32_t slot, const str_er_image_ref *frames, int32_t n, uint32_t stages, uint64_t *ticket, bool nv12)
-{
-    if (!s || slot < 0 || (size_t)slot >= s->slots.size()) return STR_ER_EINVAL;
-    str_er_stream::Slot &sl = s->slots[(size_t)slot];
-    {
-        std::lock_guard<std::mutex> lk(s->mu);
-        if (!sl.busy || sl.has_job || sl.done) { s->err = "slot was not acquired (or is already submitted)"; return STR_ER_ESTATE; }
-        if (!frames) { s->err = "null frame list"; return STR_ER_EINVAL; }
-        if (n < 1) { s->err = "empty frame list"; return STR_ER_EINVAL; }
-        if (n > s->max_frames) {
-            s->err = std::to_string(n) + " frames: more than the stream's " + std::to_string(s->max_frames) + " per submission";
-            return STR_ER_ECAPACITY;
-        }
-        const uintptr_t base = reinterpret_cast<uintptr_t>(sl.pinned);
-        size_t lo = s->slot_bytes, hi = 0;
-        for (int32_t i = 0; i < n; ++i) {
-            const str_er_image_ref &r = frames[i];
-            const std::string name = "frame " + std::to_string(i);
-            const int64_t row = nv12 ? (int64_t)r.w : (int64_t)r.w * 3, rows = nv12 ? (int64_t)r.h + r.h / 2 : (int64_t)r.h;
-            if (!r.data) { s->err = name + ": null data"; return STR_ER_EINVAL; }
-            if (r.w < 1 || r.h < 1) { s->err = name + ": empty"; return STR_ER_EINVAL; }
-            if (r.stride < row || r.stride > 0x7FFFFFFF) { s->err = name + ": stride smaller than a row or too large"; return STR_ER_EINVAL; }
-            if (nv12 && ((r.w | r.h) & 1)) { s->err = name + ": NV12 frames have even width and height"; return STR_ER_EINVAL; }
-            if (r.w > s->max_width || r.h > s->max_height) {
-                s->err = name + ": " + std::to_string(r.w) + " x " + std::to_string(r.h) + " larger than the stream's capacity " + std::to_string(s->max_width) +
-                         " x " + std::to_string(s->max_height);
-                return STR_ER_ECAPACITY;
-            }
-            const uintptr_t at = reinterpret_cast<uintptr_t>(r.data);
-            const uint64_t  end = (uint64_t)(rows - 1) * (uint64_t)r.stride + (uint64_t)row;        // bytes from the first pixel to the end of the last row
-            if (at < base || at - base > s->slot_bytes || end > s->slot_bytes - (at - base)) {
-                s->err = name + ": not wholly inside the slot's staging buffer";
-                return STR_ER_EINVAL;
-            }
-            lo = std::min(lo, (size_t)(at - base));
-            hi = std::max(hi, (size_t)(at - base + end));
-        }
-        sl.refs.assign(frames, frames + n);
-        sl.offs.resize((size_t)n);
-        for (int32_t i = 0; i < n; ++i) sl.offs[(size_t)i] = (size_t)(reinterpret_cast<uintptr_t>(frames[i].data) - base);
-        sl.span_lo = lo; sl.span_hi = hi;
-        sl.stages = stages; sl.nv12 = nv12; sl.list = true;
-        sl.ticket = s->next_ticket++;
-        sl.has_job = true;
-        s->order.push_back(slot);
-        if (ticket) *ticket = sl.ticket;
-    }
-    s->cv.notify_all();
-    return STR_ER_OK;
-}
-
 int str_er_stream_submit_list(str_er_stream *s, int32_t slot, const str_er_image_ref *frames, int32_t n, uint32_t stages, uint64_t *ticket)
 try {
-    return submit_list_impl(s, slot, frames, n, stages, ticket, false);
+    return submit_list_impl(s, slot, frames, n, stages, ticket, SrcFormat::BGR);
 } STREAM_GUARD(s)
 
 int str_er_stream_submit_nv12_list(str_er_stream *s, int32_t slot, const str_er_image_ref *frames, int32_t n, uint32_t stages, uint64_t *ticket)
 try {
-    return submit_list_impl(s, slot, frames, n, stages, ticket, true);
+    return submit_list_impl(s, slot, frames, n, stages, ticket, SrcFormat::NV12);
 } STREAM_GUARD(s)
 
 int str_er_stream_submit_copy_list(str_er_stream *s, const str_er_image_ref *frames, int32_t n, uint32_t stages, uint64_t *ticket)
 try {
     if (!s || !frames || n < 1) return STR_ER_EINVAL;
     for (int32_t i = 0; i < n; ++i)
-        if (!frames[i].data || frames[i].w < 1 || frames[i].h < 1 || frames[i].stride < (int64_t)frames[i].w * 3) {
+        if (!frames[i].data || frames[i].w < 1 || frames[i].h < 1 || frames[i].stride < src_row_bytes(frames[i].w, SrcFormat::BGR)) {
             s->err = "frame " + std::to_string(i) + ": null data, empty, or stride smaller than a row";
             return STR_ER_EINVAL;
         }
     // frames back to back, each from a 4-byte boundary when the padded total fits (a full-size list has no room for padding)
     size_t need = 0, tight = 0;
     for (int32_t i = 0; i < n; ++i) {
-        const size_t fb = (size_t)frames[i].w * 3 * (size_t)frames[i].h;
+        const size_t fb = (size_t)src_row_bytes(frames[i].w, SrcFormat::BGR) * (size_t)frames[i].h;
         need = ((need + 3) & ~(size_t)3) + fb;
         tight += fb;
     }
@@ -409,7 +407,7 @@ try {
     size_t at = 0;
     for (int32_t i = 0; i < n; ++i) {
         const str_er_image_ref &r = frames[i];
-        const size_t row = (size_t)r.w * 3;
+        const size_t row = (size_t)src_row_bytes(r.w, SrcFormat::BGR);
         at = (at + al - 1) / al * al;
         for (int y = 0; y < r.h; ++y) std::memcpy(buf + at + (size_t)y * row, r.data + (size_t)y * (size_t)r.stride, row);
         refs[(size_t)i] = r;
@@ -417,7 +415,7 @@ try {
         refs[(size_t)i].stride = (int64_t)row;
         at += row * (size_t)r.h;
     }
-    rc = submit_list_impl(s, slot, refs.data(), n, stages, ticket, false);
+    rc = submit_list_impl(s, slot, refs.data(), n, stages, ticket, SrcFormat::BGR);
     if (rc != STR_ER_OK) {                      // (the caller never saw the slot)
         std::lock_guard<std::mutex> lk(s->mu);
         s->slots[(size_t)slot].busy = false;

@@ -125,6 +125,18 @@ def test_stage_rules_match_the_entry_points_checks(tmp_path):
     assert out.strip().startswith("stage rules ok")
 
 
+def test_frame_rules(tmp_path):
+    """csrc/frame_rules.h, the one statement of what a source frame is (bytes of a row, rows of a frame, BGR / NV12 / plane) and of which
+    str_er_image_ref a list call or a list submission of the stream accepts: every rejection with its code and message and their order,
+    the 1 x 1 and 2 x 2 NV12 edges, a stride of exactly one row, stride 0x7FFFFFFF accepted and 0x80000000 rejected."""
+    csrc = os.path.join(ROOT, "scene-text-recognition_amd", "csrc")
+    exe = str(tmp_path / "frame_rules_check")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", csrc, os.path.join(ROOT, "tests", "cpp", "frame_rules_check.cpp"),
+                    "-o", exe], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    assert out.strip().startswith("frame rules ok")
+
+
 @pytest.mark.parametrize("caps", ["kernel", "unbounded"])
 def test_tile2_algorithm_on_the_host(tmp_path, caps):
     """k_tile_tree2's algorithm (csrc/tile2_body.h: the component tree of a tile level by level on bit masks -- the very source the device kernel compiles,

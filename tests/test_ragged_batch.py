@@ -162,6 +162,79 @@ def test_device_frames_at_odd_pitches(S, cascade_paths):
     assert "device list == host list" in r.stdout
 
 
+def _same_result(a, b, what):
+    assert a.info.tobytes() == b.info.tobytes(), what + ": plane infos"
+    assert a.cands.tobytes() == b.cands.tobytes(), what + ": cands"
+    assert len(a.planes) == len(b.planes) > 0
+    for k, (x, y) in enumerate(zip(a.planes, b.planes)):
+        assert x.nodes.tobytes() == y.nodes.tobytes(), "%s: nodes of plane %d" % (what, k)
+
+
+def test_equal_frames_uniform_and_list_front_ends_agree(S, cascade_paths):
+    """Frames of one size through the uniform front end and through the list front end: byte-identical plane infos, candidates and nodes.
+    211 x 97 (212 x 98 for NV12): odd sizes, so every level's rows are padded and end in a row tail, and level 1 (x 2^-1/2) is 149 x 69 -- a
+    layout of the planes that differs between the two front ends shows as a frame read at the wrong address.  The uniform call from
+    a host cube at a row stride and a frame pitch that are not tight, and from the same bytes in device memory; the per-plane calls;
+    a plane subset (level 0 only) against the level-0 planes of the full call."""
+    import ctypes as C
+    W, H, N, L = 211, 97, 3, 2
+    f = _ctx(S, cascade_paths, max_width=224, max_height=112, max_frames=N, n_pyr_levels=L)
+    sy = S.synth
+    d_cube = C.c_void_p()
+    # (device memory from the HIP runtime the library itself is linked with, found through the library's handle: PyTorch's would be a
+    # second runtime in this process)
+    hip_malloc, hip_memcpy, hip_free = f.L.hipMalloc, f.L.hipMemcpy, f.L.hipFree
+    hip_malloc.argtypes, hip_memcpy.argtypes, hip_free.argtypes = [C.POINTER(C.c_void_p), C.c_size_t], [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], [C.c_void_p]
+    try:
+        frames = [sy.stext_bgr(sy.frame_seed(90 + k), W, H) for k in range(N)]
+        assert all(fr.shape == (H, W, 3) for fr in frames) and len({fr.tobytes() for fr in frames}) == 3
+        lst = f.text_detect_list(frames, want_nodes=True)
+        assert [(p.frame, p.pyr, p.ch) for p in lst.planes] == [(k, l, c) for k in range(N) for l in range(L) for c in range(6)]
+        assert [(p.width, p.height) for p in lst.planes[6:12]] == [(149, 69)] * 6 and len(lst.cands) > 0
+        # the uniform call: a host cube with 11 bytes between rows and 13 more between frames, filled with 0xA5 around the pixels
+        stride = 3 * W + 11
+        pitch = stride * H + 13
+        cube = np.full(N * pitch, 0xA5, np.uint8)
+        for k, fr in enumerate(frames):
+            for y in range(H):
+                cube[k * pitch + y * stride:k * pitch + y * stride + 3 * W] = fr[y].reshape(-1)
+        rh = C.c_void_p()
+        f._check(f.L.str_er_detect_bgr(f.h, cube.ctypes.data, W, H, stride, pitch, N, 0, S.STAGE_ALL | S.WANT_NODES, C.byref(rh)))      # (0: STR_ER_MEM_HOST)
+        _same_result(f._collect(rh), lst, "uniform host cube (stride %d, pitch %d) against the list" % (stride, pitch))
+        # ... the same bytes on the device
+        assert hip_malloc(C.byref(d_cube), cube.size) == 0
+        assert hip_memcpy(d_cube, cube.ctypes.data, cube.size, 1) == 0          # (hipMemcpyHostToDevice)
+        dev = f.detect_bgr_device(d_cube.value, W, H, N, S.STAGE_ALL | S.WANT_NODES, stride=stride, frame_pitch=pitch)
+        _same_result(dev, lst, "uniform device cube against the list")
+        # the tight host batch, as text_detect passes it
+        full = f.text_detect(np.stack(frames), want_nodes=True)
+        _same_result(full, lst, "text_detect against text_detect_list")
+        # NV12
+        nv = [sy.nv12_from_bgr(sy.stext_bgr(sy.frame_seed(93 + k), W + 1, H + 1)) for k in range(N)]
+        assert all(a.shape == ((H + 1) * 3 // 2, W + 1) for a in nv)
+        nv_lst = f.text_detect_nv12_list(nv, want_nodes=True)
+        assert len(nv_lst.planes) == N * L * 6 and len(nv_lst.cands) > 0
+        _same_result(f.text_detect_nv12(np.stack(nv), W + 1, H + 1, want_nodes=True), nv_lst, "text_detect_nv12 against text_detect_nv12_list")
+        # the per-plane calls
+        planes = [sy.gray(fr) for fr in frames]
+        pl_lst = f.detect_planes_list(planes, want_nodes=True)
+        assert [(p.width, p.height, p.ch) for p in pl_lst.planes] == [(W, H, k) for k in range(N)]
+        _same_result(f.detect_planes(np.stack(planes), want_nodes=True), pl_lst, "detect_planes against detect_planes_list")
+        # a plane subset: level 0 only (the pyramid is not built), exactly the level-0 planes of the full call
+        sub = f.text_detect_planes(np.stack(frames), [1] * 6 + [0] * 6, want_nodes=True)
+        keep = np.nonzero(full.info["pyr"] == 0)[0]
+        assert len(keep) == N * 6 and sub.info.tobytes() == full.info[keep].tobytes()
+        exp = full.cands[np.isin(full.cands["plane"], keep)].copy()
+        exp["plane"] = np.searchsorted(keep, exp["plane"])
+        assert len(exp) > 0 and sub.cands.tobytes() == exp.tobytes()
+        for k, j in enumerate(keep):
+            assert sub.planes[k].nodes.tobytes() == full.planes[j].nodes.tobytes()
+    finally:
+        if d_cube.value:
+            hip_free(d_cube)
+        f.close()
+
+
 def test_sibling_ties_in_a_list(S, cascade_paths, oracle, oracle_cascades):
     f = _ctx(S, cascade_paths, max_width=480, max_height=360, max_frames=2, sibling_order=0)
     sy = S.synth
