@@ -116,6 +116,13 @@ extern "C" {
  * _nv12_list and every str_er_stream_submit* call honour it.  A foot box wider or taller than 16384 pixels gives STR_ER_ECAPACITY.
  * It changes no other output of the call and combines with every other STR_ER_WANT_* flag.                                      */
 #define STR_ER_WANT_LINE_GEOM (524288u)
+/* output option: every text line split into glyph runs and words, from the footprints (str_er_result_line_words / _line_runs / _words;
+ * the contract is at str_er_line_run; the gap that breaks a word: str_er_set_word_gap).  Needs STR_ER_WANT_FRAME_LINES (which needs
+ * STR_ER_STAGE_GROUP and frames): STR_ER_EINVAL without it, and wherever _FRAME_LINES is refused (str_er_detect_planes[_list],
+ * str_er_strip_merge[_ex]), the context usable afterwards.  str_er_detect_bgr, _nv12, _bgr_list, _nv12_list and every
+ * str_er_stream_submit* call honour it.  A footprint wider or taller than 16384 pixels gives STR_ER_ECAPACITY.  It changes no other
+ * output of the call and combines with every other STR_ER_WANT_* flag.                                                             */
+#define STR_ER_WANT_LINE_WORDS (1048576u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -390,6 +397,42 @@ typedef struct str_er_line_geom {
     double   qx[4], qy[4];              /* 104, 136 */
 } str_er_line_geom;                     /* 168 bytes */
 
+/* The glyph runs and words of a text line from its footprint (STR_ER_WANT_LINE_WORDS, str_er_feet_words, str_er_words_from_runs).  All
+ * exact integers, on top of the footprint F(t) and the foot box (x, y, w, h) of str_er_line_foot.
+ *   Column count n(c), 0 <= c < w: the number of pixels of F(t) in the frame column x + c.  colmax = max over c of n(c).
+ *   Glyph run: a maximal interval [c0, c1) of columns with n(c) > 0 throughout.  The runs of a line are ordered by c0; the foot box
+ *     is tight, so the first run of a footprint that is not empty starts at column 0 and its last ends at w.  A run carries, over
+ *     the pixels of F(t) in its columns, their number (pixels) and their row extent [y0, y1).  The record holds frame columns and
+ *     rows: x0 = x + c0, x1 = x + c1.
+ *   Gap between consecutive runs p, q of one line: g = q.x0 - p.x1 (>= 1).  It is a word break iff g * den >= num * colmax in 64-bit
+ *     integers; num / den is set with str_er_set_word_gap and is 1 / 3 by default.  That default is a definition of this library,
+ *     like the duplicate and the link thresholds: it is not tuned on labelled data.  (1, 65535) makes every gap a break, (65535, 1)
+ *     makes none a break (colmax <= 16384).
+ *   Word: a maximal sequence of consecutive runs of one line without a break between them.  Its box is the bounding box of its
+ *     runs' pixels, its pixels their sum.
+ *   Empty footprint: no runs, no words, colmax 0.
+ *   Frame line: its words and runs are those of its representative line (str_er_frame_line::rep), the rule its moments follow;
+ *     there is no separate table.
+ *   The columns are those of the upright frame: a sloped baseline does not change the gaps between upright glyphs, rotated glyphs
+ *     smear them.  Nothing is deskewed, and the runs are not mapped into the columns of a line crop.
+ *   Runs and words lie back to back in line order.                                                                                 */
+typedef struct str_er_line_run {
+    int32_t  x0, x1;         /*  0,  4: frame columns, half open                     */
+    int32_t  y0, y1;         /*  8, 12: frame rows, half open                        */
+    uint32_t pixels;         /* 16                                                    */
+    int32_t  word;           /* 20: index into the word table                         */
+} str_er_line_run;           /* 24 bytes */
+typedef struct str_er_line_word {
+    int32_t  line;           /*  0: index into str_er_result_texts() / the feet given */
+    int32_t  first_run, n_runs;      /*  4,  8: into the run table                    */
+    int32_t  x, y, w, h;     /* 12 .. 24: the bounding box of its runs' pixels        */
+    uint32_t pixels;         /* 28                                                    */
+} str_er_line_word;          /* 32 bytes */
+typedef struct str_er_line_words {
+    int32_t  first_word, n_words, first_run, n_runs;      /* 0 .. 12                  */
+    uint32_t colmax, reserved;       /* 16, 20                                        */
+} str_er_line_words;         /* 24 bytes; one per line of str_er_result_texts() */
+
 typedef struct str_er_plane_info {
     uint32_t frame;
     uint8_t  ch, pyr, reserved0, reserved1;
@@ -651,6 +694,27 @@ int str_er_hull_of_points(const int32_t *xy, int32_t n, int32_t *out_xy, int32_t
  * a hull that is not strictly convex in the order of str_er_line_geom, coordinates outside 0..65535.                               */
 int str_er_quad_from_hull(const int32_t *xy, int32_t n, str_er_line_geom *out);
 
+/* The gap that breaks a word (str_er_line_run): num / den of the line's colmax, 1 <= num, den <= 65535.  Default 1 / 3.  Anything else
+ * -> STR_ER_EINVAL, the context unchanged.  A stream's contexts: str_er_stream_context.                                            */
+int str_er_set_word_gap(str_er_ctx *ctx, int32_t num, int32_t den);
+/* The glyph runs and words (str_er_line_run) of n footprints in the pixels of one frame size W x H (1..65535), the runs made on the
+ * GPU: feet and bits as str_er_feet_geom and str_er_link_feet take them, with their validation and error codes; a foot box wider or
+ * taller than 16384 gives STR_ER_ECAPACITY.  line_words receives n records, runs and words the tables they index, *n_runs and
+ * *n_words their sizes; runs == NULL or words == NULL only counts (line_words is still filled); cap_runs or cap_words too small ->
+ * STR_ER_ECAPACITY, both counts still set.  The words are those of str_er_words_from_runs with the context's word gap.             */
+int str_er_feet_words(str_er_ctx *ctx, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n,
+                      str_er_line_words *line_words, str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words,
+                      int32_t cap_words, int32_t *n_words);
+/* The words of n_lines lines from their runs.  Pure host, no context, no GPU; the detect calls use this same function.  In:
+ * line_words[t].first_run, .n_runs and .colmax (the lines' runs back to back in line order: first_run is the sum of the earlier
+ * n_runs, and they add up to n_runs) and x0 .. pixels of every run.  Out: the word of every run, first_word and n_words of every line
+ * (reserved = 0), and the word records; words == NULL only counts (the runs and line_words are still filled); cap_words too small ->
+ * STR_ER_ECAPACITY, *n_words still set.  STR_ER_EINVAL: bad arguments, num or den outside 1..65535, run lists that do not lie back to
+ * back, a line with runs and colmax 0, a run with x0 >= x1, y0 >= y1 or pixels == 0, runs of a line out of order, overlapping or
+ * touching (every gap is >= 1).                                                                                                    */
+int str_er_words_from_runs(str_er_line_run *runs, int32_t n_runs, str_er_line_words *line_words, int32_t n_lines, int32_t num, int32_t den,
+                           str_er_line_word *words, int32_t cap_words, int32_t *n_words);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -868,6 +932,11 @@ int str_er_result_edge_feet(const str_er_result *r, int32_t which, int32_t *fram
 const str_er_line_geom  *str_er_result_line_geoms(const str_er_result *r, int32_t *n);
 const str_er_line_geom  *str_er_result_frame_line_geoms(const str_er_result *r, int32_t *n);
 const int32_t           *str_er_result_geom_points(const str_er_result *r, int32_t *n_points);
+/* With STR_ER_WANT_LINE_WORDS (str_er_line_run): one str_er_line_words per line of str_er_result_texts(), the runs and the words they
+ * index.  Each returns NULL and 0 without the flag; a call without lines returns empty arrays (not NULL).                          */
+const str_er_line_words *str_er_result_line_words(const str_er_result *r, int32_t *n);
+const str_er_line_run   *str_er_result_line_runs(const str_er_result *r, int32_t *n);
+const str_er_line_word  *str_er_result_words(const str_er_result *r, int32_t *n);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

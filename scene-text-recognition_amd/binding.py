@@ -66,6 +66,15 @@ WANT_LINE_GEOM = 524288
 LINE_GEOM_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("hull_area2", "<u8"), ("m10", "<u8"), ("m01", "<u8"), ("m20", "<u8"), ("m11", "<u8"),
                             ("m02", "<u8"), ("pixels", "<u4"), ("edge", "<i4"), ("ex", "<i4"), ("ey", "<i4"), ("dmin", "<i8"), ("dmax", "<i8"),
                             ("cmin", "<i8"), ("cmax", "<i8"), ("qx", "<f8", (4,)), ("qy", "<f8", (4,))])
+# output option: every text line split into glyph runs and words (needs WANT_FRAME_LINES; Result.line_words / line_runs / words /
+# words_of_line / runs_of_line / frame_line_words; the contract is at str_er_line_run in include/str_er.h)
+WANT_LINE_WORDS = 1048576
+# str_er_line_run: frame columns [x0, x1) and rows [y0, y1), half open; word: its row of the word table
+LINE_RUN_DTYPE = np.dtype([("x0", "<i4"), ("x1", "<i4"), ("y0", "<i4"), ("y1", "<i4"), ("pixels", "<u4"), ("word", "<i4")])
+# str_er_line_word: the runs line_runs[first_run:first_run + n_runs] of line `line`, their bounding box and pixels
+LINE_WORD_DTYPE = np.dtype([("line", "<i4"), ("first_run", "<i4"), ("n_runs", "<i4"), ("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("pixels", "<u4")])
+# str_er_line_words: per line, its rows of the word and run tables and the largest column count of its footprint
+LINE_WORDS_DTYPE = np.dtype([("first_word", "<i4"), ("n_words", "<i4"), ("first_run", "<i4"), ("n_runs", "<i4"), ("colmax", "<u4"), ("reserved", "<u4")])
 # str_er_line_crop: crop t = width x height bytes (pitch width) from byte pix_off of the crop bytes (and of the glyph bytes);
 # ax .. vy: the 16.16 sampling geometry (include/str_er.h)
 LINE_CROP_DTYPE = np.dtype([("pix_off", "<u8"), ("width", "<i4"), ("height", "<i4"), ("ax", "<i4"), ("ay", "<i4"),
@@ -94,6 +103,7 @@ assert FRAME_MAP_DTYPE.itemsize == 16
 assert LINE_FOOT_DTYPE.itemsize == 24 and LINE_PAIR_DTYPE.itemsize == 16 and FRAME_LINE_DTYPE.itemsize == 40
 assert LINE_LINK_DTYPE.itemsize == 16 and TEXT_TRACK_DTYPE.itemsize == 24
 assert LINE_GEOM_DTYPE.itemsize == 168
+assert LINE_RUN_DTYPE.itemsize == 24 and LINE_WORD_DTYPE.itemsize == 32 and LINE_WORDS_DTYPE.itemsize == 24
 
 
 def unpack_mask(words: np.ndarray, word_off: int, w: int, h: int) -> np.ndarray:
@@ -304,6 +314,12 @@ def load_library():
     L.str_er_feet_geom.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p]
     L.str_er_hull_of_points.argtypes = [vp, C.c_int32, vp, C.c_int32, i32p]
     L.str_er_quad_from_hull.argtypes = [vp, C.c_int32, vp]
+    for fn in (L.str_er_result_line_words, L.str_er_result_line_runs, L.str_er_result_words):
+        fn.argtypes = [vp, i32p]
+        fn.restype = vp
+    L.str_er_set_word_gap.argtypes = [vp, C.c_int32, C.c_int32]
+    L.str_er_feet_words.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p, vp, C.c_int32, i32p]
+    L.str_er_words_from_runs.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, i32p]
     L.str_er_line_crop_geometry.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, vp]
     L.str_er_line_crops.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, C.c_uint64,
                                     C.POINTER(C.c_uint64), vp]
@@ -437,7 +453,44 @@ class Result:
         self._line_geoms = None    # with WANT_LINE_GEOM: the tables behind line_geoms / frame_line_geoms / geom_points
         self._frame_line_geoms = None
         self._geom_points = None
+        self._line_words = None    # with WANT_LINE_WORDS: the tables behind line_words / line_runs / words
+        self._line_runs = None
+        self._words = None
         self._planes = None
+
+    def _line_words_table(self, table):
+        if table is None:
+            raise ValueError("the result has no line words (pass WANT_LINE_WORDS / want_line_words=True)")
+        return table
+
+    @property
+    def line_words(self) -> np.ndarray:
+        """With WANT_LINE_WORDS: LINE_WORDS_DTYPE per line of texts."""
+        return self._line_words_table(self._line_words)
+
+    @property
+    def line_runs(self) -> np.ndarray:
+        """With WANT_LINE_WORDS: LINE_RUN_DTYPE, the glyph runs of the lines back to back in line order."""
+        return self._line_words_table(self._line_runs)
+
+    @property
+    def words(self) -> np.ndarray:
+        """With WANT_LINE_WORDS: LINE_WORD_DTYPE, the words of the lines back to back in line order."""
+        return self._line_words_table(self._words)
+
+    def words_of_line(self, t: int) -> np.ndarray:
+        """With WANT_LINE_WORDS: the words of line t (LINE_WORD_DTYPE), left to right."""
+        lw = self.line_words[t]
+        return self.words[int(lw["first_word"]):int(lw["first_word"]) + int(lw["n_words"])].copy()
+
+    def runs_of_line(self, t: int) -> np.ndarray:
+        """With WANT_LINE_WORDS: the glyph runs of line t (LINE_RUN_DTYPE), left to right."""
+        lw = self.line_words[t]
+        return self.line_runs[int(lw["first_run"]):int(lw["first_run"]) + int(lw["n_runs"])].copy()
+
+    def frame_line_words(self, i: int) -> np.ndarray:
+        """With WANT_LINE_WORDS: the words of frame line i: those of its representative line."""
+        return self.words_of_line(int(self.frame_lines[i]["rep"]))
 
     def _line_geom_table(self, table):
         if table is None:
@@ -729,6 +782,10 @@ class ERFilter:
                         npts = C.c_int32()
                         ptr = L.str_er_result_geom_points(rh, C.byref(npts))
                         res._geom_points = _owned(ptr, 2 * npts.value, np.int32).reshape(-1, 2)
+                    res._line_words = table(L.str_er_result_line_words, LINE_WORDS_DTYPE)
+                    if res._line_words is not None:
+                        res._line_runs = table(L.str_er_result_line_runs, LINE_RUN_DTYPE)
+                        res._words = table(L.str_er_result_words, LINE_WORD_DTYPE)
                     res._line_links = table(L.str_er_result_line_links, LINE_LINK_DTYPE)
                     if res._line_links is not None:
                         res._line_tracks = table(L.str_er_result_line_tracks, np.int32)
@@ -792,7 +849,7 @@ class ERFilter:
     def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
-                    want_line_links: bool = False, want_line_geom: bool = False) -> Result:
+                    want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -805,7 +862,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -926,7 +983,7 @@ class ERFilter:
     def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
-                         want_line_links: bool = False, want_line_geom: bool = False) -> Result:
+                         want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -934,7 +991,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1139,6 +1196,28 @@ class ERFilter:
                                             _np_ptr(geoms), _np_ptr(xy), min(len(xy), 2 ** 31 - 1), C.byref(n)))
         return geoms[:len(ft)], xy[:n.value].copy()
 
+    def set_word_gap(self, num: int = 1, den: int = 3) -> None:
+        """str_er_set_word_gap: a gap between glyph runs breaks a word when gap * den >= num * colmax (1 <= num, den <= 65535)."""
+        self._check(self.L.str_er_set_word_gap(self.h, int(num), int(den)))
+
+    def feet_words(self, W: int, H: int, feet: np.ndarray, bits: np.ndarray):
+        """str_er_feet_words: the glyph runs and words (str_er_line_run) of footprints in the pixels of one (H, W) frame, the runs made
+        on the GPU: feet and bits as feet_geom takes them.  Returns (LINE_WORDS_DTYPE per footprint, LINE_RUN_DTYPE runs, LINE_WORD_DTYPE
+        words), the words at the gap of set_word_gap."""
+        ft = np.ascontiguousarray(feet, dtype=LINE_FOOT_DTYPE).reshape(-1)
+        bt = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+        if int((ft["h"].astype(np.int64).clip(0) * ((ft["w"].astype(np.int64).clip(0) + 31) // 32)).sum()) != len(bt):
+            raise ValueError("bits needs h rows of (w + 31) // 32 words per foot, back to back")
+        lw = np.zeros(max(1, len(ft)), LINE_WORDS_DTYPE)
+        cap = int(((ft["w"].astype(np.int64).clip(0) + 1) // 2).sum())          # (a row of w columns holds at most (w + 1) // 2 runs: one call)
+        runs = np.zeros(max(1, cap), LINE_RUN_DTYPE)
+        words = np.zeros(max(1, cap), LINE_WORD_DTYPE)
+        nr, nw = C.c_int32(), C.c_int32()
+        self._check(self.L.str_er_feet_words(self.h, int(W), int(H), _np_ptr(ft) if len(ft) else None, _np_ptr(bt) if len(bt) else None, len(ft),
+                                             _np_ptr(lw), _np_ptr(runs), min(len(runs), 2 ** 31 - 1), C.byref(nr), _np_ptr(words),
+                                             min(len(words), 2 ** 31 - 1), C.byref(nw)))
+        return lw[:len(ft)], runs[:nr.value].copy(), words[:nw.value].copy()
+
     def set_line_crop(self, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> None:
         """str_er_set_line_crop: the crop height (8..256), the widest crop (1..8192) and the pad (0..1, of the line's height) of
         WANT_LINE_CROPS and line_crops."""
@@ -1329,10 +1408,10 @@ def _owned(ptr, n: int, dtype) -> np.ndarray:
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False, line_geom=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False, line_words=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -1356,6 +1435,22 @@ def frame_lines_from_pairs(feet: np.ndarray, frames_of_lines, pyr_of_lines, pair
     if rc != 0:
         raise StrErError(rc, "str_er_frame_lines_from_pairs")
     return ft, pr, fl[:nfl.value], mem[:n]
+
+
+def words_from_runs(line_words: np.ndarray, runs: np.ndarray, num: int = 1, den: int = 3):
+    """str_er_words_from_runs (pure host): the words of lines from their glyph runs: line_words (LINE_WORDS_DTYPE; first_run, n_runs and
+    colmax are read) and runs (LINE_RUN_DTYPE; x0 .. pixels are read), the runs of the lines back to back.  A gap g between two runs
+    breaks a word when g * den >= num * colmax.  Returns copies (line_words, runs, words) with first_word / n_words, word and the
+    LINE_WORD_DTYPE records filled."""
+    lw = np.array(line_words, dtype=LINE_WORDS_DTYPE).reshape(-1)
+    rn = np.array(runs, dtype=LINE_RUN_DTYPE).reshape(-1)
+    words = np.zeros(max(1, len(rn)), LINE_WORD_DTYPE)
+    n = C.c_int32()
+    rc = load_library().str_er_words_from_runs(_np_ptr(rn) if len(rn) else None, len(rn), _np_ptr(lw) if len(lw) else None, len(lw), int(num), int(den),
+                                               _np_ptr(words), len(words), C.byref(n))
+    if rc != 0:
+        raise StrErError(rc, "str_er_words_from_runs")
+    return lw, rn, words[:n.value].copy()
 
 
 def hull_of_points(points) -> np.ndarray:
@@ -1637,18 +1732,21 @@ class FrameStream:
         arr = np.frombuffer((C.c_uint8 * cap.value).from_address(buf.value), dtype=np.uint8)
         return slot.value, arr
 
-    def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL) -> int:
+    def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
+        stages |= WANT_LINE_WORDS if want_line_words else 0
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit(self.h, slot, w, h, 3 * w, 3 * w * h, n_frames, stages, C.byref(t)))
         return int(t.value)
 
-    def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL) -> int:
+    def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
         """The staging buffer holds n_frames tightly packed NV12 frames (w * h * 3 / 2 bytes each)."""
+        stages |= WANT_LINE_WORDS if want_line_words else 0
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_nv12(self.h, slot, w, h, w, w * (h + h // 2), n_frames, stages, C.byref(t)))
         return int(t.value)
 
-    def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL) -> int:
+    def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
+        stages |= WANT_LINE_WORDS if want_line_words else 0
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         if a.ndim == 3:
             a = a[None]
@@ -1665,16 +1763,19 @@ class FrameStream:
         self._check(fn(self.h, slot, arr, len(refs), stages, C.byref(t)))
         return int(t.value)
 
-    def submit_list(self, slot: int, layout, stages: int = STAGE_ALL) -> int:
+    def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
         """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
+        stages |= WANT_LINE_WORDS if want_line_words else 0
         return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
 
-    def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL) -> int:
+    def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
         """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
+        stages |= WANT_LINE_WORDS if want_line_words else 0
         return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
 
-    def submit_copy_list(self, frames, stages: int = STAGE_ALL) -> int:
+    def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
         """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
+        stages |= WANT_LINE_WORDS if want_line_words else 0
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         arr = (ImageRef * max(1, len(refs)))(*refs)

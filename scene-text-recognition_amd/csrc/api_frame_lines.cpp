@@ -11,6 +11,9 @@
 // behind k_line_foot and leaves the moments and the hull vertices, which come back in the stage's one wait; the host makes the oriented
 // boxes (str_er_quad_from_hull) and merges the hulls of a frame line (str_er_hull_of_points).  str_er_feet_geom runs the same kernel on
 // uploaded footprints.
+// STR_ER_WANT_LINE_WORDS (the contract is at str_er_line_run) likewise: k_foot_words cuts every footprint into glyph runs behind
+// k_line_foot, into (w + 1) / 2 reserved slots a line, which come back in the stage's one wait; the host compacts the slots and forms
+// the words (str_er_words_from_runs, words_host.cpp).  str_er_feet_words runs the same kernel on uploaded footprints.
 #include "str_er_ctx.h"
 
 #include <array>
@@ -288,11 +291,87 @@ int geom_collect(str_er_ctx *c, const GeomPlan &P, std::vector<str_er_line_geom>
     return STR_ER_OK;
 }
 
+static_assert(sizeof(WordsRun) == sizeof(str_er_line_run), "the device writes str_er_line_run records");
+
+// k_foot_words over the lines of a launch: the run slots of every line, and the layout of the buffer (slots | records | run slots;
+// the same on both sides)
+struct WordsPlan {
+    std::vector<WordsSlot> slots;
+    size_t n_lines = 0, n_slots = 0, o_rec = 0, o_run = 0, bytes = 0;
+};
+
+// a footprint box k_foot_words does not take (checked before anything is enqueued); who: in front of the message
+int words_check_boxes(str_er_ctx *c, const std::vector<FootLine> &lines, const char *who)
+{
+    for (const FootLine &L : lines)
+        if (L.w > WORDS_MAX_BOX || L.h > WORDS_MAX_BOX)
+            return fail(c, STR_ER_ECAPACITY, std::string(who) + "a footprint wider or taller than " + std::to_string(WORDS_MAX_BOX) + " pixels");
+    return STR_ER_OK;
+}
+
+// the slots uploaded, the kernel and the copy back enqueued on s behind whatever made the footprints in c->foot_bits; words_collect after the wait
+int words_enqueue(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const FootLine *d_lines, WordsPlan &P)
+{
+    P.n_lines = lines.size();
+    P.slots.assign(P.n_lines, WordsSlot{0, 0});
+    uint64_t at = 0;
+    for (size_t t = 0; t < P.n_lines; ++t) {
+        const FootLine &L = lines[t];
+        if (L.w <= 0 || L.h <= 0) continue;
+        P.slots[t] = WordsSlot{(uint32_t)at, ((uint32_t)L.w + 1u) / 2u};          // (the most runs a row of w columns holds)
+        at += P.slots[t].cap;
+        if (at > 0x7FFFFFFFull) return fail(c, STR_ER_ECAPACITY, "line words: more than 2^31 glyph runs to reserve");
+    }
+    P.n_slots = (size_t)at;
+    if (P.n_lines == 0) return STR_ER_OK;
+    P.o_rec = align_up(sizeof(WordsSlot) * P.n_lines, 256); P.o_run = align_up(P.o_rec + sizeof(WordsRec) * P.n_lines, 256);
+    P.bytes = P.o_run + sizeof(WordsRun) * P.n_slots;
+    const int rc = c->words_out.ensure(c, P.bytes, "line words output");
+    if (rc != STR_ER_OK) return rc;
+    std::memcpy(c->words_out.h(), P.slots.data(), sizeof(WordsSlot) * P.n_lines);
+    HIP_TRY(c, hipMemcpyAsync(c->words_out.d(), c->words_out.h(), sizeof(WordsSlot) * P.n_lines, hipMemcpyHostToDevice, s));
+    launch_foot_words(s, d_lines, (int)P.n_lines, reinterpret_cast<const WordsSlot *>(c->words_out.d()), c->foot_bits.d<uint64_t>(),
+                      reinterpret_cast<WordsRec *>(c->words_out.d() + P.o_rec), reinterpret_cast<WordsRun *>(c->words_out.d() + P.o_run));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->words_out.h() + P.o_rec, c->words_out.d() + P.o_rec, P.bytes - P.o_rec, hipMemcpyDeviceToHost, s));
+    return STR_ER_OK;
+}
+
+// after the wait: the slots compacted into runs (back to back in line order), one record per line, and the words formed
+// (str_er_words_from_runs with the context's gap)
+int words_collect(str_er_ctx *c, const WordsPlan &P, std::vector<str_er_line_words> &line_words, std::vector<str_er_line_run> &runs,
+                  std::vector<str_er_line_word> &words)
+{
+    line_words.assign(P.n_lines, str_er_line_words{});
+    runs.clear();
+    const uint8_t *h = P.n_lines ? c->words_out.h() : nullptr;
+    for (size_t t = 0; t < P.n_lines; ++t) {
+        WordsRec R;
+        std::memcpy(&R, h + P.o_rec + sizeof(WordsRec) * t, sizeof R);
+        if (R.n_runs > P.slots[t].cap || (R.n_runs == 0) != (R.colmax == 0))
+            return fail(c, STR_ER_EHIP, "line words: a line's runs outside its slots (internal error)");
+        str_er_line_words &LW = line_words[t];
+        LW.first_run = (int32_t)runs.size(); LW.n_runs = (int32_t)R.n_runs; LW.colmax = R.colmax;
+        if (R.n_runs == 0) continue;
+        runs.resize(runs.size() + R.n_runs);
+        std::memcpy(runs.data() + LW.first_run, h + P.o_run + sizeof(WordsRun) * P.slots[t].first, sizeof(WordsRun) * R.n_runs);
+    }
+    if (runs.size() > 0x7FFFFFFFull) return fail(c, STR_ER_ECAPACITY, "line words: more than 2^31 glyph runs");
+    words.resize(runs.size());
+    int32_t n_words = 0;
+    if (str_er_words_from_runs(runs.data(), (int32_t)runs.size(), line_words.data(), (int32_t)P.n_lines, c->word_num, c->word_den, words.data(),
+                               (int32_t)words.size(), &n_words) != STR_ER_OK)
+        return fail(c, STR_ER_EHIP, "line words: the device's runs are not runs (internal error)");
+    words.resize((size_t)n_words);
+    return STR_ER_OK;
+}
+
 // one upload, the launches on s, one copy back, one wait (a pair pass again, with a larger table, if its pairs outgrew it).
 // LK: the links across adjacent frames as well (T.range), in the same upload and wait, with a table and a copy of their own
 // GP: the geometry of the footprints as well (k_foot_geom behind k_line_foot, its copy back ahead of the same wait; geom_collect afterwards)
+// WP: their glyph runs as well (k_foot_words, in the same way; words_collect afterwards)
 int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t *d_bits, bool in_batch, FootOut &O, LinkOut *LK = nullptr,
-               GeomPlan *GP = nullptr)
+               GeomPlan *GP = nullptr, WordsPlan *WP = nullptr)
 {
     const size_t n_lines = T.lines.size();
     O.stat.assign(n_lines, FootStat{});
@@ -338,6 +417,7 @@ int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t
         }
     }
     if (GP && (rc = geom_enqueue(c, s, T.lines, d_lines, *GP)) != STR_ER_OK) return rc;
+    if (WP && (rc = words_enqueue(c, s, T.lines, d_lines, *WP)) != STR_ER_OK) return rc;
     const auto launch_pairs = [&](FootHead *head, FootPair *out, uint32_t cap) { launch_foot_pairs(s, d_lines, (int)n_lines, d_list, feet, head, out, cap); };
     const auto launch_links = [&](FootHead *head, FootPair *out, uint32_t cap) {
         launch_foot_links(s, d_lines, (int)n_lines, reinterpret_cast<const FootRange *>(c->foot_tab.d() + o_rng), d_list, feet, head, out, cap);
@@ -411,7 +491,7 @@ void foot_rows32(const uint64_t *words, const FootLine &L, const str_er_line_foo
 } // namespace
 
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
-                      str_er_result *r, bool links, bool geom)
+                      str_er_result *r, bool links, bool geom, bool words)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n_frames = b.frame_wh.size() / 2, n_lines = r->texts.size();
@@ -474,7 +554,10 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
     FootOut O;
     LinkOut LK;
     GeomPlan GP;
-    const int rc = foot_stage(c, s, T, d_bits, true, O, links ? &LK : nullptr, geom ? &GP : nullptr);
+    WordsPlan WP;
+    if (words)
+        if (const int rcw = words_check_boxes(c, T.lines, "STR_ER_WANT_LINE_WORDS: "); rcw != STR_ER_OK) return rcw;
+    const int rc = foot_stage(c, s, T, d_bits, true, O, links ? &LK : nullptr, geom ? &GP : nullptr, words ? &WP : nullptr);
     if (rc != STR_ER_OK) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     feet_from_stats(O.stat, r->line_feet);
@@ -567,6 +650,18 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
         if (c->dbg_stats)        // developer aid (tools/dev_line_geom.py)
             std::fprintf(stderr, "[str_er] line geometry: %zu lines, %zu vertices reserved, %zu kept, %zu bytes back, host %.3f ms\n", n_lines, GP.n_pts,
                          r->geom_points.size() / 2, GP.bytes - GP.o_rec, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
+    }
+    if (words) {
+        const auto t2 = std::chrono::steady_clock::now();
+        if (T.members.empty()) {          // (no footprint at all: nothing was launched)
+            r->line_words.assign(n_lines, str_er_line_words{});
+            r->line_runs.clear(); r->words.clear();
+        } else if (const int rcw = words_collect(c, WP, r->line_words, r->line_runs, r->words); rcw != STR_ER_OK) return rcw;
+        r->have_line_words = true;
+        if (c->dbg_stats)        // developer aid (tools/dev_line_words.py)
+            std::fprintf(stderr, "[str_er] line words: %zu lines, %zu run slots reserved, %zu runs, %zu words, %zu bytes back, host %.3f ms\n", n_lines,
+                         WP.n_slots, r->line_runs.size(), r->words.size(), WP.bytes - WP.o_rec,
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
     }
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
@@ -993,6 +1088,68 @@ try {
     if (xy && !pts.empty()) std::memcpy(xy, pts.data(), 4 * pts.size());
     return STR_ER_OK;
 } ABI_GUARD(c)
+
+int str_er_set_word_gap(str_er_ctx *c, int32_t num, int32_t den)
+{
+    if (!c) return STR_ER_EINVAL;
+    if (!word_gap_ok(num, den)) return fail(c, STR_ER_EINVAL, "str_er_set_word_gap: 1 <= num, den <= 65535");
+    c->word_num = num; c->word_den = den;
+    return STR_ER_OK;
+}
+
+int str_er_feet_words(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_words *line_words,
+                      str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words, int32_t *n_words)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (W < 1 || H < 1 || W > 65535 || H > 65535 || n < 0 || !n_runs || !n_words || (n > 0 && (!feet || !line_words)) || (runs && cap_runs < 0) ||
+        (words && cap_words < 0))
+        return fail(c, STR_ER_EINVAL, "bad arguments");
+    // the footprints as a table of lines and rows of 64-bit words, every one checked against its foot
+    std::vector<FootLine> lines;
+    std::vector<uint64_t> bitwords;
+    int rc = check_foot_boxes(c, W, H, feet, n, "");
+    if (rc != STR_ER_OK) return rc;
+    for (int32_t t = 0; t < n; ++t)
+        if (feet[t].w > WORDS_MAX_BOX || feet[t].h > WORDS_MAX_BOX)
+            return fail(c, STR_ER_ECAPACITY, "line " + std::to_string(t) + ": a foot box wider or taller than " + std::to_string(WORDS_MAX_BOX) + " pixels");
+    if ((rc = pack_footprints(c, feet, bits, n, lines, bitwords)) != STR_ER_OK) return rc;
+    for (int32_t t = 0; t < n; ++t)
+        if (feet[t].pixels == 0) lines[(size_t)t] = FootLine{};          // (a box without a bit: an empty footprint)
+    std::vector<str_er_line_words> lw((size_t)n, str_er_line_words{});
+    std::vector<str_er_line_run>   rn;
+    std::vector<str_er_line_word>  wd;
+    if (!bitwords.empty()) {
+        HIP_TRY(c, hipSetDevice(c->prm.device));
+        if ((rc = c->foot_tab.ensure(c, sizeof(FootLine) * (size_t)n, "frame line tables")) != STR_ER_OK ||
+            (rc = c->foot_bits.ensure(c, 8 * bitwords.size(), "line footprints")) != STR_ER_OK)
+            return rc;
+        hipStream_t s = c->stream;
+        std::memcpy(c->foot_tab.h(), lines.data(), sizeof(FootLine) * (size_t)n);
+        HIP_TRY(c, hipMemcpyAsync(c->foot_tab.d(), c->foot_tab.h(), sizeof(FootLine) * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(c->foot_bits.d<uint64_t>(), bitwords.data(), 8 * bitwords.size(), hipMemcpyHostToDevice, s));      // (bitwords must outlive the copy: every path below waits)
+        WordsPlan WP;
+        if ((rc = words_enqueue(c, s, lines, reinterpret_cast<const FootLine *>(c->foot_tab.d()), WP)) != STR_ER_OK) {
+            (void)hipStreamSynchronize(s);          // (the upload of bitwords may still be queued)
+            return rc;
+        }
+        HIP_TRY(c, wait_stream(c, s));
+        if ((rc = words_collect(c, WP, lw, rn, wd)) != STR_ER_OK) return rc;
+    }
+    *n_runs = (int32_t)rn.size(); *n_words = (int32_t)wd.size();
+    if (n > 0) std::memcpy(line_words, lw.data(), sizeof(str_er_line_words) * (size_t)n);
+    if (!runs || !words) return STR_ER_OK;
+    if ((int64_t)rn.size() > (int64_t)cap_runs) return fail(c, STR_ER_ECAPACITY, std::to_string(rn.size()) + " glyph runs, cap_runs is " + std::to_string(cap_runs));
+    if ((int64_t)wd.size() > (int64_t)cap_words) return fail(c, STR_ER_ECAPACITY, std::to_string(wd.size()) + " words, cap_words is " + std::to_string(cap_words));
+    if (!rn.empty()) std::memcpy(runs, rn.data(), sizeof(str_er_line_run) * rn.size());
+    if (!wd.empty()) std::memcpy(words, wd.data(), sizeof(str_er_line_word) * wd.size());
+    return STR_ER_OK;
+} ABI_GUARD(c)
+
+const str_er_line_words *str_er_result_line_words(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_words, &str_er_result::line_words, n); }
+
+const str_er_line_run *str_er_result_line_runs(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_words, &str_er_result::line_runs, n); }
+
+const str_er_line_word *str_er_result_words(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_words, &str_er_result::words, n); }
 
 const str_er_line_geom *str_er_result_line_geoms(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_geom, &str_er_result::line_geoms, n); }
 

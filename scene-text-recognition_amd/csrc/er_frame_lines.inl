@@ -29,6 +29,17 @@
 // the row extents -- in LDS for a line of up to GEOM_LDS_ROWS - 1 rows, else in scratch words the host reserved -- keeping the last
 // point as well, and the wave writes the vertices out: left[0], the right chain downwards, the left chain upwards.  The chains were
 // kept sequential on one lane over a divide-and-merge of lane-local chains: see DESIGN.md 3.16.
+//
+// k_foot_words (STR_ER_WANT_LINE_WORDS, str_er_feet_words; the contract is at str_er_line_run): the glyph runs of every footprint.  A wave
+// (a workgroup of its own) takes a line; a lane the word columns lane, lane + 64, ... of its bit rows, so the loads of neighbouring
+// lanes are neighbouring words of a row.  Pass 1: the lane walks down the rows of its word column, ORs them into the column's
+// occupancy word and adds every row word to 64 column counts kept bit-sliced in 15 planes (a ripple of AND / XOR that stops when the
+// carry is 0); the largest of the 64 counts falls out of one descent from the top plane, colmax is a wave max.  The occupancy row
+// (at most 256 words) lies in LDS: run starts are m & ~(m << 1 | carry in), run ends the mirror image, both numbered by popcounts and
+// a wave prefix sum, so that the k-th start and the k-th end fill slot k whatever number of words the run or the gap before it spans.
+// Pass 2: the lane walks its word column once per interval of its occupancy word -- the popcount under the interval's bits and the
+// rows that have one -- and adds the result to the run's slot: in LDS (ds_add / ds_min / ds_max) for a line of up to WORDS_LDS_RUNS
+// runs, else with atomics on the run's output slot.  See DESIGN.md 3.17.
 
 constexpr int FOOT_THREADS = 256;           // 4 waves, a job / a line each
 
@@ -269,6 +280,149 @@ __global__ __launch_bounds__(GEOM_THREADS) void k_foot_geom(const FootLine *__re
     }
 }
 
+constexpr int WORDS_THREADS = 64;           // one wave a workgroup, as k_foot_geom
+constexpr int WORDS_PLANES = 15;            // column counts up to WORDS_MAX_BOX = 2^14
+constexpr int WORDS_MAX_PITCH = WORDS_MAX_BOX / 64;
+
+// the inclusive prefix sum of v over the lanes of the wave
+__device__ __forceinline__ uint32_t foot_wave_scan(uint32_t v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)v, o);
+        if (lane >= o) v += u;
+    }
+    return v;
+}
+
+// planes K0 .. K1 - 1 of a bit-sliced add: carry is added at plane K0, what is left of it comes back
+template <int K0, int K1>
+__device__ __forceinline__ void foot_ripple(uint64_t (&p)[WORDS_PLANES], uint64_t &carry)
+{
+#pragma unroll
+    for (int k = K0; k < K1; ++k) {
+        const uint64_t t = p[k] & carry;
+        p[k] ^= carry;
+        carry = t;
+    }
+}
+
+__global__ __launch_bounds__(WORDS_THREADS) void k_foot_words(const FootLine *__restrict__ lines, int n_lines, const WordsSlot *__restrict__ slots,
+                                                              const uint64_t *__restrict__ feet, WordsRec *__restrict__ recs, WordsRun *__restrict__ runs)
+{
+    __shared__ uint64_t s_occ[WORDS_MAX_PITCH];          // the occupancy row: bit i of word j: column 64 j + i has a pixel
+    __shared__ uint32_t s_base[WORDS_MAX_PITCH];         // the run of the first interval of word j
+    __shared__ uint32_t s_px[WORDS_LDS_RUNS];
+    __shared__ int32_t  s_y0[WORDS_LDS_RUNS], s_y1[WORDS_LDS_RUNS];
+    const int lane = threadIdx.x;
+    for (int a = blockIdx.x; a < n_lines; a += gridDim.x) {
+        const FootLine  L = lines[a];
+        const WordsSlot S = slots[a];
+        if (L.w <= 0 || L.h <= 0 || L.w > WORDS_MAX_BOX || L.h > WORDS_MAX_BOX || L.pitch > (uint32_t)WORDS_MAX_PITCH) {
+            if (lane == 0) recs[a] = WordsRec{0, 0};
+            continue;
+        }
+        const uint32_t  P = L.pitch;
+        const uint64_t *box = feet + L.word_off;
+        // pass 1: the occupancy word and the largest column count of every word column
+        uint32_t cmax = 0;
+        for (uint32_t j = (uint32_t)lane; j < P; j += 64) {
+            uint64_t p[WORDS_PLANES];
+#pragma unroll
+            for (int k = 0; k < WORDS_PLANES; ++k) p[k] = 0;
+            uint64_t occ = 0;
+            for (int r = 0; r < L.h; ++r) {
+                uint64_t carry = box[(uint64_t)r * P + j];
+                occ |= carry;
+                // (planes 0 .. 1 always, the others only while a carry is left: two steps on average; every index is a constant)
+                foot_ripple<0, 2>(p, carry);
+                if (carry) {
+                    foot_ripple<2, 4>(p, carry);
+                    if (carry) {
+                        foot_ripple<4, 8>(p, carry);
+                        if (carry) foot_ripple<8, WORDS_PLANES>(p, carry);
+                    }
+                }
+            }
+            s_occ[j] = occ;
+            uint64_t cand = occ;
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = WORDS_PLANES - 1; k >= 0; --k) {
+                const uint64_t t = cand & p[k];
+                if (t) { cand = t; v |= 1u << k; }
+            }
+            cmax = max(cmax, v);
+        }
+        cmax = foot_wave_max(cmax);
+        __syncthreads();
+        // the starts and the ends of the runs, numbered along the row: the k-th start and the k-th end are run k
+        uint32_t n_st = 0, n_en = 0;
+        for (uint32_t j0 = 0; j0 < P; j0 += 64) {
+            const uint32_t j = j0 + (uint32_t)lane;
+            uint64_t st = 0, en = 0;
+            uint32_t cont = 0;          // the word's first interval goes on from the word before
+            if (j < P) {
+                const uint64_t m = s_occ[j];
+                const uint64_t prev = j > 0 ? s_occ[j - 1] >> 63 : 0ull, next = j + 1 < P ? s_occ[j + 1] & 1ull : 0ull;
+                st = m & ~(m << 1 | prev);
+                en = m & ~(m >> 1 | next << 63);
+                cont = (uint32_t)(prev & m);
+            }
+            const uint32_t ns = (uint32_t)__popcll(st), ne = (uint32_t)__popcll(en);
+            const uint32_t is = foot_wave_scan(ns, lane), ie = foot_wave_scan(ne, lane);
+            uint32_t ks = n_st + is - ns, ke = n_en + ie - ne;
+            if (j < P) s_base[j] = ks - cont;
+            for (; st; st &= st - 1, ++ks)
+                if (ks < S.cap) runs[S.first + ks].x0 = L.x + (int32_t)(64u * j) + (int32_t)__builtin_ctzll(st);
+            for (; en; en &= en - 1, ++ke)
+                if (ke < S.cap) runs[S.first + ke].x1 = L.x + (int32_t)(64u * j) + (int32_t)__builtin_ctzll(en) + 1;
+            n_st += (uint32_t)__shfl((int)is, 63); n_en += (uint32_t)__shfl((int)ie, 63);
+        }
+        const uint32_t n_runs = min(n_st, S.cap);         // (n_st <= (w + 1) / 2 = cap: the bits past w are 0)
+        const bool     in_lds = n_runs <= (uint32_t)WORDS_LDS_RUNS;
+        for (uint32_t k = (uint32_t)lane; k < n_runs; k += 64) {
+            if (in_lds) { s_px[k] = 0; s_y0[k] = 0x7FFFFFFF; s_y1[k] = 0; }
+            else { WordsRun *R = runs + S.first + k; R->y0 = 0x7FFFFFFF; R->y1 = 0; R->pixels = 0; R->word = -1; }
+        }
+        if (!in_lds) __threadfence();          // (the slots' first values ahead of the atomics on them)
+        __syncthreads();
+        // pass 2: per interval of the lane's occupancy word, the pixels under it and the rows that have one
+        for (uint32_t j = (uint32_t)lane; j < P; j += 64) {
+            uint64_t m = s_occ[j];
+            uint32_t idx = s_base[j];
+            for (; m; ++idx) {
+                const int      b = __builtin_ctzll(m);
+                const uint64_t z = ~(m >> b);
+                const int      len = z ? __builtin_ctzll(z) : 64;
+                const uint64_t mask = (len == 64 ? ~0ull : (1ull << len) - 1ull) << b;
+                uint32_t px = 0;
+                int      y0 = L.h, y1 = 0;
+                for (int r = 0; r < L.h; ++r) {
+                    const uint64_t w = box[(uint64_t)r * P + j] & mask;
+                    if (w) { px += (uint32_t)__popcll(w); y0 = min(y0, r); y1 = r + 1; }
+                }
+                m &= ~mask;
+                if (idx >= n_runs) continue;
+                if (in_lds) {
+                    atomicAdd(&s_px[idx], px); atomicMin(&s_y0[idx], L.y + y0); atomicMax(&s_y1[idx], L.y + y1);
+                } else {
+                    WordsRun *R = runs + S.first + idx;
+                    atomicAdd(&R->pixels, px); atomicMin(&R->y0, L.y + y0); atomicMax(&R->y1, L.y + y1);
+                }
+            }
+        }
+        __syncthreads();
+        if (in_lds)
+            for (uint32_t k = (uint32_t)lane; k < n_runs; k += 64) {
+                WordsRun *R = runs + S.first + k;
+                R->y0 = s_y0[k]; R->y1 = s_y1[k]; R->pixels = s_px[k]; R->word = -1;
+            }
+        if (lane == 0) recs[a] = WordsRec{n_runs, cmax};
+        __syncthreads();        // (the wave's reads of the LDS rows before the next line writes them)
+    }
+}
+
 void launch_line_foot(hipStream_t s, const FootJob *jobs, int n_jobs, const FootLine *lines, const TextMapCand *members, const uint16_t *tabs,
                       const uint32_t *bits, uint64_t *feet, FootStat *stat)
 {
@@ -299,4 +453,11 @@ void launch_foot_geom(hipStream_t s, const FootLine *lines, int n_lines, const G
     if (n_lines <= 0) return;
     const dim3 grid((unsigned)std::min(n_lines, 1 << 16));
     hipLaunchKernelGGL(k_foot_geom, grid, dim3(GEOM_THREADS), 0, s, lines, n_lines, slots, feet, scratch, recs, xy);
+}
+
+void launch_foot_words(hipStream_t s, const FootLine *lines, int n_lines, const WordsSlot *slots, const uint64_t *feet, WordsRec *recs, WordsRun *runs)
+{
+    if (n_lines <= 0) return;
+    const dim3 grid((unsigned)std::min(n_lines, 1 << 16));
+    hipLaunchKernelGGL(k_foot_words, grid, dim3(WORDS_THREADS), 0, s, lines, n_lines, slots, feet, recs, runs);
 }

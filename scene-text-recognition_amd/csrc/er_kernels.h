@@ -165,5 +165,9 @@ void launch_foot_links(hipStream_t s, const FootLine *lines, int n_lines, const 
 // on; scratch: h + 1 words from slots[line].x_first on for every line with h + 1 > GEOM_LDS_ROWS (may be null when there is none)
 void launch_foot_geom(hipStream_t s, const FootLine *lines, int n_lines, const GeomSlot *slots, const uint64_t *feet, uint64_t *scratch, GeomRec *recs,
                       int32_t *xy);
+// launch_foot_words (STR_ER_WANT_LINE_WORDS, str_er_feet_words): one wave per line over its footprint in feet: the number of glyph runs
+// and colmax into recs[line], the runs (frame columns and rows, ordered by column, word = -1) into runs from slots[line].first on, at
+// most slots[line].cap of them.  Every line must be at most WORDS_MAX_BOX wide and tall (a larger one is left without runs)
+void launch_foot_words(hipStream_t s, const FootLine *lines, int n_lines, const WordsSlot *slots, const uint64_t *feet, WordsRec *recs, WordsRun *runs);
 
 } // namespace str_er

@@ -322,5 +322,24 @@ struct GeomRec {
 };
 static_assert(sizeof(GeomRec) == 48, "GeomRec layout (host and device)");
 constexpr int GEOM_LDS_ROWS = 1024;         // k_foot_geom keeps the row extents of a line of up to GEOM_LDS_ROWS - 1 rows in LDS
+// Per line, for k_foot_words: its run slots are runs[first .. first + cap), cap = (w + 1) / 2: the most runs a row of w columns holds
+struct WordsSlot {
+    uint32_t first, cap;
+};
+static_assert(sizeof(WordsSlot) == 8, "WordsSlot layout (host and device)");
+// What k_foot_words leaves per line: the number of glyph runs (they fill the line's first slots, ordered by column) and colmax
+struct WordsRec {
+    uint32_t n_runs, colmax;
+};
+static_assert(sizeof(WordsRec) == 8, "WordsRec layout (host and device)");
+// A run slot: the layout of str_er_line_run (word is left -1: the host forms the words)
+struct WordsRun {
+    int32_t  x0, x1, y0, y1;
+    uint32_t pixels;
+    int32_t  word;
+};
+static_assert(sizeof(WordsRun) == 24, "WordsRun layout (host and device)");
+constexpr int WORDS_MAX_BOX = 16384;        // the widest / tallest footprint k_foot_words takes: 256 occupancy words in LDS, counts of 15 bits
+constexpr int WORDS_LDS_RUNS = 1024;        // k_foot_words combines the statistics of a line of up to WORDS_LDS_RUNS runs in LDS, of more in its slots
 
 } // namespace str_er

@@ -29,6 +29,10 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
     const uint32_t sup = STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP;
     struct Rule { bool bad; int code; const char *msg; };
     const Rule rules[] = {
+        // STR_ER_WANT_LINE_WORDS rides on STR_ER_WANT_FRAME_LINES as the two flags below do
+        {k.strip && any(STR_ER_WANT_LINE_WORDS), STR_ER_EINVAL, "STR_ER_WANT_LINE_WORDS is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_LINE_WORDS), STR_ER_EINVAL, "STR_ER_WANT_LINE_WORDS needs frames (not the per-plane calls)"},
+        {any(STR_ER_WANT_LINE_WORDS) && !any(STR_ER_WANT_FRAME_LINES), STR_ER_EINVAL, "STR_ER_WANT_LINE_WORDS needs STR_ER_WANT_FRAME_LINES"},
         // STR_ER_WANT_LINE_GEOM rides on STR_ER_WANT_FRAME_LINES in the same way: refused without it and where it is refused, with a
         // message that names this flag; with it the flag changes no verdict
         {k.strip && any(STR_ER_WANT_LINE_GEOM), STR_ER_EINVAL, "STR_ER_WANT_LINE_GEOM is not supported by the strip path (str_er_strip_merge)"},

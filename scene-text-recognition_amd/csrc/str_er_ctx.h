@@ -143,6 +143,10 @@ struct str_er_result {
     std::vector<str_er_line_geom> frame_line_geoms;
     std::vector<int32_t> geom_points;
     bool have_line_geom = false;
+    std::vector<str_er_line_words> line_words;   // STR_ER_WANT_LINE_WORDS: per line, and the glyph runs and words they index
+    std::vector<str_er_line_run> line_runs;
+    std::vector<str_er_line_word> words;
+    bool have_line_words = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -257,6 +261,9 @@ struct str_er_ctx {
     // STR_ER_WANT_LINE_GEOM / str_er_feet_geom
     PairBuf  geom_out;                // slots | records | hull vertices of k_foot_geom
     DevBuf   geom_x;                  // 64-bit words: the scratch rows of lines taller than its LDS
+    // STR_ER_WANT_LINE_WORDS / str_er_feet_words (str_er_set_word_gap)
+    int32_t  word_num = 1, word_den = 3;
+    PairBuf  words_out;               // slots | records | run slots of k_foot_words
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -528,8 +535,11 @@ struct SampleTabs {
 // call still on the device and the first word of every candidate's (UINT64_MAX: none), or null: then the members' masks are made here
 // links: STR_ER_WANT_LINE_LINKS as well (the links, tracks and edge feet of r, in the same stage)
 // geom: STR_ER_WANT_LINE_GEOM as well (the geometry of the lines and frame lines of r, k_foot_geom in the same stage)
+// words: STR_ER_WANT_LINE_WORDS as well (the glyph runs and words of the lines of r, k_foot_words in the same stage)
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
-                      str_er_result *r, bool links = false, bool geom = false);
+                      str_er_result *r, bool links = false, bool geom = false, bool words = false);
+// ---- defined in words_host.cpp (HIP-free)
+bool word_gap_ok(int32_t num, int32_t den);       // what str_er_set_word_gap takes
 constexpr int MASK_MAX_WIDTH = 16384;       // widest box the mask kernels take (er_masks.inl: MASK_MAX_WPL words of 64 pixels per lane)
 // ---- defined in api_models.cpp
 int parse_cascade(str_er_ctx *c, HostCascade &hc, const char *text, size_t len);

@@ -471,6 +471,43 @@ public:
         return out;
     }
 
+    // Every text line split into glyph runs and words (STR_ER_WANT_LINE_WORDS; the contract is at str_er_line_run in include/str_er.h): one
+    // record per line of str_er_result_texts(), and the runs and words they index.  A frame line's words are those of its rep.
+    struct LineWords {
+        std::vector<str_er_line_words> lines;
+        std::vector<str_er_line_run>   runs;
+        std::vector<str_er_line_word>  words;
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static LineWords line_words(const str_er_result *r)
+    {
+        LineWords out;
+        int32_t n = 0;
+        if (const str_er_line_words *p = str_er_result_line_words(r, &n)) out.lines.assign(p, p + n);
+        if (const str_er_line_run *p = str_er_result_line_runs(r, &n)) out.runs.assign(p, p + n);
+        if (const str_er_line_word *p = str_er_result_words(r, &n)) out.words.assign(p, p + n);
+        return out;
+    }
+    // the gap that breaks a word: gap * den >= num * colmax (str_er_set_word_gap; 1 / 3 by default)
+    void set_word_gap(int32_t num, int32_t den) { check(str_er_set_word_gap(ctx_.get(), num, den)); }
+    // the runs and words of footprints of one frame size, the runs made on the GPU (str_er_feet_words): feet and bits as feet_geom takes them
+    LineWords feet_words(int32_t width, int32_t height, const std::vector<str_er_line_foot> &feet, const std::vector<uint32_t> &bits)
+    {
+        LineWords out;
+        out.lines.resize(feet.size());
+        int64_t cap = 1;                                  // (a row of w columns holds at most (w + 1) / 2 runs: one call)
+        for (const str_er_line_foot &f : feet) cap += ((int64_t)(f.w > 0 ? f.w : 0) + 1) / 2;
+        if (cap > INT32_MAX) cap = INT32_MAX;
+        out.runs.resize((size_t)cap);
+        out.words.resize((size_t)cap);
+        int32_t nr = 0, nw = 0;
+        check(str_er_feet_words(ctx_.get(), width, height, feet.empty() ? nullptr : feet.data(), bits.empty() ? nullptr : bits.data(), (int32_t)feet.size(),
+                                out.lines.empty() ? nullptr : out.lines.data(), out.runs.data(), (int32_t)cap, &nr, out.words.data(), (int32_t)cap, &nw));
+        out.runs.resize((size_t)nr);
+        out.words.resize((size_t)nw);
+        return out;
+    }
+
     // The text lines of consecutive frames linked into text tracks (STR_ER_WANT_LINE_LINKS; the contract is at str_er_line_link in
     // include/str_er.h): the overlaps across adjacent frames, the track of every line of str_er_result_texts(), the tracks, the line
     // indices their first / count index, and the footprints of the lines of the first ([0]) and of the last frame ([1]).
