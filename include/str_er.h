@@ -123,6 +123,12 @@ extern "C" {
  * str_er_stream_submit* call honour it.  A footprint wider or taller than 16384 pixels gives STR_ER_ECAPACITY.  It changes no other
  * output of the call and combines with every other STR_ER_WANT_* flag.                                                             */
 #define STR_ER_WANT_LINE_WORDS (1048576u)
+/* output option: every glyph run of STR_ER_WANT_LINE_WORDS read by the OCR scorer: a label, a character and a probability per run
+ * (str_er_result_run_reads / _run_features; the contract is at str_er_run_read).  Needs STR_ER_WANT_LINE_WORDS: STR_ER_EINVAL without it
+ * and wherever that flag is refused, and an SVM model of dim 1800 (str_er_load_svm_model): STR_ER_ESTATE without one; the context is
+ * usable afterwards.  It does not need STR_ER_STAGE_OCR_LINES.  Every call that honours _LINE_WORDS honours it.  It changes no other
+ * output of the call and combines with every other STR_ER_WANT_* flag.                                                             */
+#define STR_ER_WANT_RUN_READ (2097152u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -433,6 +439,26 @@ typedef struct str_er_line_words {
     uint32_t colmax, reserved;       /* 16, 20                                        */
 } str_er_line_words;         /* 24 bytes; one per line of str_er_result_texts() */
 
+/* The reading of a glyph run (STR_ER_WANT_RUN_READ, str_er_feet_read): one character per run and one string per word.  A definition of
+ * this library, like the word gap, on top of the footprint F(t) and OCR::chain_run (str_er_ocr_chain_run_slope).
+ *   Tile of a run r = (x0, x1, y0, y1) of line t: T_r has (x1 - x0) x (y1 - y0) bytes, T_r(i, j) = 0 if the frame pixel
+ *     (x0 + i, y0 + j) is in F(t), else 255.  Only line t's own footprint counts: another line's pixels inside the box do not.  A glyph
+ *     is dark on light, so chain_run's 255 - roi makes it bright, as for a region of a plane that is not inverted.
+ *   Reading of a run: what OCR::chain_run gives for the whole tile as its box with the slope s of the line: the 1800 feature bytes q,
+ *     label and prob = pv[label].  s = str_er_text::slope of line t (str_er_feet_read: slopes[t]); a slope that is not finite counts
+ *     as 0, as for the line crops.  The slope is in the coordinates of the line's pyramid level and the tile is in frame pixels: the
+ *     pyramid scales both axes alike up to the rounding of the level sizes, so the slope is used as it is.
+ *   Character of a run: str_er_ocr_char(label).  No run is dropped for a low probability: prob is returned and the caller filters.
+ *   String of a word: the characters of runs[first_run .. first_run + n_runs).  Text of a frame line: the words of its representative
+ *     joined by one blank.
+ *   Limits: there is no spelling correction and no language model (the reference's word graph, bigram table and corrector are not
+ *     rebuilt), and a run of touching glyphs reads as one character: runs are not split.                                            */
+typedef struct str_er_run_read {
+    int32_t  label;          /*  0: the scorer's label                                */
+    int32_t  ch;             /*  4: str_er_ocr_char(label)                            */
+    double   prob;           /*  8: pv[label]                                         */
+} str_er_run_read;           /* 16 bytes; one per run of str_er_result_line_runs()    */
+
 typedef struct str_er_plane_info {
     uint32_t frame;
     uint8_t  ch, pyr, reserved0, reserved1;
@@ -714,6 +740,20 @@ int str_er_feet_words(str_er_ctx *ctx, int32_t W, int32_t H, const str_er_line_f
  * touching (every gap is >= 1).                                                                                                    */
 int str_er_words_from_runs(str_er_line_run *runs, int32_t n_runs, str_er_line_words *line_words, int32_t n_lines, int32_t num, int32_t den,
                            str_er_line_word *words, int32_t cap_words, int32_t *n_words);
+/* The character of a label of the OCR scorer (str_er_run_read): table[label] for 0 <= label < 65 with the reference's table
+ * "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz&()" (src/OCR.cpp:10), else '?'.  Pure: no context, no GPU.          */
+int32_t str_er_ocr_char(int32_t label);
+/* str_er_feet_words and the reading of every run (str_er_run_read): slopes receives one slope per footprint (NULL: all 0; a slope that
+ * is not finite -> STR_ER_EINVAL, as in str_er_ocr_chain_run_slope).  reads receives one record per run and q_out (optional) the
+ * 1800 feature bytes of every run, both in the order of runs; reads == NULL gives the features only, and no SVM model is needed then
+ * (with reads: STR_ER_ESTATE without a model of dim 1800).  Arguments, validation and capacity codes are those of str_er_feet_words:
+ * reads and q_out hold cap_runs records / 1800 * cap_runs bytes, and a counting call (runs == NULL or words == NULL) reads nothing. */
+int str_er_feet_read(str_er_ctx *ctx, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, const double *slopes, int32_t n,
+                     str_er_line_words *line_words, str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words,
+                     int32_t cap_words, int32_t *n_words, str_er_run_read *reads, uint8_t *q_out);
+/* Statistics of the tile atlas of STR_ER_WANT_RUN_READ / str_er_feet_read: its size in bytes (0: never made) and how often it was
+ * allocated or grown since the context was created.  Either pointer may be NULL.                                                  */
+int str_er_run_atlas_stats(const str_er_ctx *ctx, uint64_t *bytes, uint64_t *grown);
 
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
@@ -937,6 +977,10 @@ const int32_t           *str_er_result_geom_points(const str_er_result *r, int32
 const str_er_line_words *str_er_result_line_words(const str_er_result *r, int32_t *n);
 const str_er_line_run   *str_er_result_line_runs(const str_er_result *r, int32_t *n);
 const str_er_line_word  *str_er_result_words(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_RUN_READ (str_er_run_read): one record per run of str_er_result_line_runs(), in the same order, and the 1800 * n
+ * feature bytes of the runs.  Each returns NULL and 0 without the flag; a call without runs returns empty arrays (not NULL).       */
+const str_er_run_read   *str_er_result_run_reads(const str_er_result *r, int32_t *n);
+const uint8_t           *str_er_result_run_features(const str_er_result *r, uint64_t *n_bytes);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

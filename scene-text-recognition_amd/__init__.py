@@ -16,7 +16,7 @@ from .binding import (  # noqa: F401
     CLS_POOL, CLS_STRONG, CLS_WEAK, STAGE_ALL, STAGE_CLASSIFY, STAGE_OCR, STAGE_EXTRACT, STAGE_NMS, STAGE_TRACK, STAGE_GROUP, GROUP_INNER_SUP, GROUP_OVERLAP_SUP, STAGE_OCR_LINES, TRACK_DTYPE, TEXT_DTYPE, GBOUND_DTYPE, WANT_NODES, WANT_MASKS, MASK_DTYPE, unpack_mask, WANT_SHAPES, SHAPE_DTYPE, WANT_STROKES, STROKE_DTYPE, WANT_LINE_CROPS, WANT_LINE_GLYPHS, LINE_CROP_DTYPE, line_crop_geometry,
     WANT_TEXT_MAP, WANT_LINE_MAP, TEXT_MAP_STRONG, TEXT_MAP_WEAK, TEXT_MAP_LINE, TEXT_MAP_OCR, FRAME_MAP_DTYPE,
     WANT_LINE_GEOM, LINE_GEOM_DTYPE, hull_of_points, quad_from_hull,
-    WANT_LINE_WORDS, LINE_RUN_DTYPE, LINE_WORD_DTYPE, LINE_WORDS_DTYPE, words_from_runs,
+    WANT_LINE_WORDS, LINE_RUN_DTYPE, LINE_WORD_DTYPE, LINE_WORDS_DTYPE, words_from_runs, WANT_RUN_READ, RUN_READ_DTYPE, ocr_char,
     WANT_LINE_LINKS, LINE_LINK_DTYPE, TEXT_TRACK_DTYPE, text_tracks_from_links, EdgeFeet, TextTracker,
     WANT_FRAME_LINES, LINE_FOOT_DTYPE, LINE_PAIR_DTYPE, FRAME_LINE_DTYPE, frame_lines_from_pairs,
     CAND_DTYPE, NODE_DTYPE, PLANE_DTYPE, ERFilter, FrameStream, PlaneResult, Params, Result, StrErError, apply_runtime_hint, set_batch_slots, lib_path, load_library,

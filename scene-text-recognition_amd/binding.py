@@ -69,6 +69,12 @@ LINE_GEOM_DTYPE = np.dtype([("first", "<u4"), ("count", "<u4"), ("hull_area2", "
 # output option: every text line split into glyph runs and words (needs WANT_FRAME_LINES; Result.line_words / line_runs / words /
 # words_of_line / runs_of_line / frame_line_words; the contract is at str_er_line_run in include/str_er.h)
 WANT_LINE_WORDS = 1048576
+# output option: every glyph run read by the OCR scorer (needs WANT_LINE_WORDS and an SVM model of dim 1800; Result.run_reads /
+# run_features / word_text / words_text_of_line / frame_line_text; the contract is at str_er_run_read in include/str_er.h)
+WANT_RUN_READ = 2097152
+# str_er_run_read: per glyph run, the scorer's label, its character (str_er_ocr_char) and pv[label]
+RUN_READ_DTYPE = np.dtype([("label", "<i4"), ("ch", "<i4"), ("prob", "<f8")])
+assert RUN_READ_DTYPE.itemsize == 16
 # str_er_line_run: frame columns [x0, x1) and rows [y0, y1), half open; word: its row of the word table
 LINE_RUN_DTYPE = np.dtype([("x0", "<i4"), ("x1", "<i4"), ("y0", "<i4"), ("y1", "<i4"), ("pixels", "<u4"), ("word", "<i4")])
 # str_er_line_word: the runs line_runs[first_run:first_run + n_runs] of line `line`, their bounding box and pixels
@@ -320,6 +326,14 @@ def load_library():
     L.str_er_set_word_gap.argtypes = [vp, C.c_int32, C.c_int32]
     L.str_er_feet_words.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p, vp, C.c_int32, i32p]
     L.str_er_words_from_runs.argtypes = [vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, i32p]
+    L.str_er_result_run_reads.argtypes = [vp, i32p]
+    L.str_er_result_run_reads.restype = vp
+    L.str_er_result_run_features.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_result_run_features.restype = vp
+    L.str_er_ocr_char.argtypes = [C.c_int32]
+    L.str_er_ocr_char.restype = C.c_int32
+    L.str_er_feet_read.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p, vp, C.c_int32, i32p, vp, vp]
+    L.str_er_run_atlas_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.str_er_line_crop_geometry.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, vp]
     L.str_er_line_crops.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int64, vp, vp, vp, vp, C.c_int32, vp, C.c_uint64,
                                     C.POINTER(C.c_uint64), vp]
@@ -456,6 +470,8 @@ class Result:
         self._line_words = None    # with WANT_LINE_WORDS: the tables behind line_words / line_runs / words
         self._line_runs = None
         self._words = None
+        self._run_reads = None     # with WANT_RUN_READ: the tables behind run_reads / run_features
+        self._run_features = None
         self._planes = None
 
     def _line_words_table(self, table):
@@ -491,6 +507,35 @@ class Result:
     def frame_line_words(self, i: int) -> np.ndarray:
         """With WANT_LINE_WORDS: the words of frame line i: those of its representative line."""
         return self.words_of_line(int(self.frame_lines[i]["rep"]))
+
+    def _run_read_table(self, table):
+        if table is None:
+            raise ValueError("the result has no run reads (pass WANT_RUN_READ / want_run_read=True)")
+        return table
+
+    @property
+    def run_reads(self) -> np.ndarray:
+        """With WANT_RUN_READ: RUN_READ_DTYPE per glyph run of line_runs, in the same order."""
+        return self._run_read_table(self._run_reads)
+
+    @property
+    def run_features(self) -> np.ndarray:
+        """With WANT_RUN_READ: (n runs, 1800) uint8, the feature bytes the scorer read from every run's tile."""
+        return self._run_read_table(self._run_features)
+
+    def word_text(self, w: int) -> str:
+        """With WANT_RUN_READ: the string of word w (an index into words): the characters of its runs."""
+        wd = self.words[w]
+        return "".join(chr(int(c)) for c in self.run_reads["ch"][int(wd["first_run"]):int(wd["first_run"]) + int(wd["n_runs"])])
+
+    def words_text_of_line(self, t: int) -> list:
+        """With WANT_RUN_READ: the strings of the words of line t, left to right."""
+        lw = self.line_words[t]
+        return [self.word_text(w) for w in range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))]
+
+    def frame_line_text(self, i: int) -> str:
+        """With WANT_RUN_READ: the text of frame line i: the words of its representative line joined by one blank."""
+        return " ".join(self.words_text_of_line(int(self.frame_lines[i]["rep"])))
 
     def _line_geom_table(self, table):
         if table is None:
@@ -786,6 +831,9 @@ class ERFilter:
                     if res._line_words is not None:
                         res._line_runs = table(L.str_er_result_line_runs, LINE_RUN_DTYPE)
                         res._words = table(L.str_er_result_words, LINE_WORD_DTYPE)
+                        res._run_reads = table(L.str_er_result_run_reads, RUN_READ_DTYPE)
+                        if res._run_reads is not None:
+                            res._run_features = table(L.str_er_result_run_features, np.uint8, n64).reshape(-1, 1800)
                     res._line_links = table(L.str_er_result_line_links, LINE_LINK_DTYPE)
                     if res._line_links is not None:
                         res._line_tracks = table(L.str_er_result_line_tracks, np.int32)
@@ -849,7 +897,8 @@ class ERFilter:
     def text_detect(self, src: np.ndarray, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
-                    want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False) -> Result:
+                    want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
+                    want_run_read: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -862,7 +911,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -983,7 +1032,8 @@ class ERFilter:
     def text_detect_list(self, frames, stages: int = STAGE_ALL, want_nodes: bool = False, want_masks: bool = False,
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
-                         want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False) -> Result:
+                         want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
+                    want_run_read: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -991,7 +1041,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1218,6 +1268,38 @@ class ERFilter:
                                              min(len(words), 2 ** 31 - 1), C.byref(nw)))
         return lw[:len(ft)], runs[:nr.value].copy(), words[:nw.value].copy()
 
+    def feet_read(self, W: int, H: int, feet: np.ndarray, bits: np.ndarray, slopes=None, want_reads: bool = True):
+        """str_er_feet_read: feet_words and the reading of every glyph run (str_er_run_read): slopes one per footprint (None: all 0).
+        Returns (line_words, runs, words, reads RUN_READ_DTYPE or None without want_reads, features (n runs, 1800) uint8); without
+        want_reads no SVM model is needed."""
+        ft = np.ascontiguousarray(feet, dtype=LINE_FOOT_DTYPE).reshape(-1)
+        bt = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+        if int((ft["h"].astype(np.int64).clip(0) * ((ft["w"].astype(np.int64).clip(0) + 31) // 32)).sum()) != len(bt):
+            raise ValueError("bits needs h rows of (w + 31) // 32 words per foot, back to back")
+        sl = None
+        if slopes is not None:
+            sl = np.ascontiguousarray(slopes, dtype=np.float64).reshape(-1)
+            if len(sl) != len(ft):
+                raise ValueError("slopes needs one entry per foot")
+        lw = np.zeros(max(1, len(ft)), LINE_WORDS_DTYPE)
+        nr, nw = C.c_int32(), C.c_int32()
+        args = (self.h, int(W), int(H), _np_ptr(ft) if len(ft) else None, _np_ptr(bt) if len(bt) else None,
+                _np_ptr(sl) if sl is not None and len(sl) else None, len(ft), _np_ptr(lw))
+        self._check(self.L.str_er_feet_read(*args, None, 0, C.byref(nr), None, 0, C.byref(nw), None, None))         # (the counting call)
+        runs = np.zeros(max(1, nr.value), LINE_RUN_DTYPE)
+        words = np.zeros(max(1, nw.value), LINE_WORD_DTYPE)
+        reads = np.zeros(max(1, nr.value), RUN_READ_DTYPE) if want_reads else None
+        q = np.zeros((max(1, nr.value), 1800), np.uint8)
+        self._check(self.L.str_er_feet_read(*args, _np_ptr(runs), len(runs), C.byref(nr), _np_ptr(words), len(words), C.byref(nw),
+                                            _np_ptr(reads) if want_reads else None, _np_ptr(q)))
+        return lw[:len(ft)], runs[:nr.value].copy(), words[:nw.value].copy(), reads[:nr.value].copy() if want_reads else None, q[:nr.value].copy()
+
+    def run_atlas_stats(self):
+        """str_er_run_atlas_stats: (bytes of the run tile atlas, how often it was allocated or grown)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self.L.str_er_run_atlas_stats(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def set_line_crop(self, height: int = 32, max_width: int = 1024, pad: float = 0.125) -> None:
         """str_er_set_line_crop: the crop height (8..256), the widest crop (1..8192) and the pad (0..1, of the line's height) of
         WANT_LINE_CROPS and line_crops."""
@@ -1408,10 +1490,10 @@ def _owned(ptr, n: int, dtype) -> np.ndarray:
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False, line_geom=False, line_words=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -1435,6 +1517,11 @@ def frame_lines_from_pairs(feet: np.ndarray, frames_of_lines, pyr_of_lines, pair
     if rc != 0:
         raise StrErError(rc, "str_er_frame_lines_from_pairs")
     return ft, pr, fl[:nfl.value], mem[:n]
+
+
+def ocr_char(label: int) -> str:
+    """str_er_ocr_char (pure host): the character of a label of the OCR scorer, '?' outside 0 .. 64."""
+    return chr(load_library().str_er_ocr_char(int(label)))
 
 
 def words_from_runs(line_words: np.ndarray, runs: np.ndarray, num: int = 1, den: int = 3):
@@ -1724,6 +1811,13 @@ class FrameStream:
     def load_cascade(self, which: int, path: str) -> None:
         self._check(self.L.str_er_stream_load_cascade(self.h, which, path.encode()))
 
+    def load_svm_model(self, path: str, dim: int = 1800) -> None:
+        """str_er_load_svm_model on every context of the stream (str_er_stream_context): what WANT_RUN_READ submissions need."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            if self.L.str_er_load_svm_model(ctx, path.encode(), dim) != 0:
+                raise StrErError(-6, (self.L.str_er_last_error(ctx) or b"").decode())
+
     def acquire(self):
         """(slot, uint8 view of the pinned staging buffer)."""
         slot, buf, cap = C.c_int32(), C.c_void_p(), C.c_int64()
@@ -1732,21 +1826,21 @@ class FrameStream:
         arr = np.frombuffer((C.c_uint8 * cap.value).from_address(buf.value), dtype=np.uint8)
         return slot.value, arr
 
-    def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
-        stages |= WANT_LINE_WORDS if want_line_words else 0
+    def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit(self.h, slot, w, h, 3 * w, 3 * w * h, n_frames, stages, C.byref(t)))
         return int(t.value)
 
-    def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
+    def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
         """The staging buffer holds n_frames tightly packed NV12 frames (w * h * 3 / 2 bytes each)."""
-        stages |= WANT_LINE_WORDS if want_line_words else 0
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_nv12(self.h, slot, w, h, w, w * (h + h // 2), n_frames, stages, C.byref(t)))
         return int(t.value)
 
-    def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
-        stages |= WANT_LINE_WORDS if want_line_words else 0
+    def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         if a.ndim == 3:
             a = a[None]
@@ -1763,19 +1857,19 @@ class FrameStream:
         self._check(fn(self.h, slot, arr, len(refs), stages, C.byref(t)))
         return int(t.value)
 
-    def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
+    def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
         """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
-        stages |= WANT_LINE_WORDS if want_line_words else 0
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
         return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
 
-    def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
+    def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
         """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
-        stages |= WANT_LINE_WORDS if want_line_words else 0
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
         return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
 
-    def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False) -> int:
+    def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
         """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
-        stages |= WANT_LINE_WORDS if want_line_words else 0
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         arr = (ImageRef * max(1, len(refs)))(*refs)

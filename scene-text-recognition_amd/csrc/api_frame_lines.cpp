@@ -14,6 +14,10 @@
 // STR_ER_WANT_LINE_WORDS (the contract is at str_er_line_run) likewise: k_foot_words cuts every footprint into glyph runs behind
 // k_line_foot, into (w + 1) / 2 reserved slots a line, which come back in the stage's one wait; the host compacts the slots and forms
 // the words (str_er_words_from_runs, words_host.cpp).  str_er_feet_words runs the same kernel on uploaded footprints.
+// STR_ER_WANT_RUN_READ (the contract is at str_er_run_read) behind that: only the host knows the compacted runs, so after the stage's
+// wait it lays their tiles out in an atlas (pack_run_tiles), k_run_tiles expands the footprint words still in c->foot_bits into it,
+// and the scorer's launch chain reads the atlas as a device plane (run_read_stage: a second enqueue and wait).  str_er_feet_read does
+// the same behind str_er_feet_words' kernel.
 #include "str_er_ctx.h"
 
 #include <array>
@@ -366,6 +370,85 @@ int words_collect(str_er_ctx *c, const WordsPlan &P, std::vector<str_er_line_wor
     return STR_ER_OK;
 }
 
+// The reading of the compacted runs of a launch whose footprints are still in c->foot_bits (lines: the table k_foot_words read):
+// the tiles laid out and expanded into the atlas, then chain_run's launch chain on the atlas as a device plane with one box a run and
+// the slope of the run's line (slopes: one per line, or null: all 0; a slope that is not finite counts as 0).  One upload, the
+// launches, the copies back and a wait of its own on s.  reads == null: the features only (no model needed).
+int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
+                   const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q)
+{
+    const size_t n = runs.size();
+    if (reads) reads->assign(n, str_er_run_read{});
+    q.assign(1800 * n, 0);
+    if (n == 0) return STR_ER_OK;
+    if (n > 0x7FFFFFFFull / 1800) return fail(c, STR_ER_ECAPACITY, "run read: too many glyph runs");
+    std::vector<RunTile> tiles(n);
+    std::vector<RotGeom> rot(n);
+    for (size_t t = 0; t < lines.size(); ++t) {
+        const FootLine &L = lines[t];
+        const double    sl = slopes && std::isfinite(slopes[t]) ? slopes[t] : 0.0;
+        for (int32_t k = 0; k < line_words[t].n_runs; ++k) {
+            const size_t           i = (size_t)line_words[t].first_run + (size_t)k;
+            const str_er_line_run &R = runs[i];
+            // (the kernel reads the rows and columns of the run in its line's words: they must lie inside the foot box)
+            if (i >= n || R.x0 < L.x || R.x1 <= R.x0 || R.x1 > L.x + L.w || R.y0 < L.y || R.y1 <= R.y0 || R.y1 > L.y + L.h)
+                return fail(c, STR_ER_EHIP, "run read: a glyph run outside its line's footprint (internal error)");
+            RunTile &T = tiles[i];
+            T.bit_off = L.word_off + (uint64_t)(R.y0 - L.y) * L.pitch; T.pitch = L.pitch; T.c0 = (uint32_t)(R.x0 - L.x);
+            T.w = (uint32_t)(R.x1 - R.x0); T.h = (uint32_t)(R.y1 - R.y0);
+            rot[i] = make_rot_geom((int)T.w, (int)T.h, sl);
+        }
+    }
+    RunAtlas A;
+    if (!pack_run_tiles(tiles.data(), n, RUN_SHELF_W, A)) return fail(c, STR_ER_ECAPACITY, "run read: the tiles of the glyph runs do not fit an atlas");
+    std::vector<int32_t> boxes(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const RunTile &T = tiles[i];
+        if ((uint64_t)T.ax + (T.w + 3u) / 4u * 4u > A.width || (uint64_t)T.ay + T.h > A.height)
+            return fail(c, STR_ER_EHIP, "run read: a tile outside the atlas (internal error)");
+        boxes[4 * i] = (int32_t)T.ax; boxes[4 * i + 1] = (int32_t)T.ay; boxes[4 * i + 2] = (int32_t)T.w; boxes[4 * i + 3] = (int32_t)T.h;
+    }
+    const size_t atlas_bytes = (size_t)A.width * A.height;
+    const size_t o_box = align_up(sizeof(RunTile) * n, 256), o_rot = align_up(o_box + 16 * n, 256), tab_bytes = o_rot + sizeof(RotGeom) * n;
+    const SvmDev *m = reads ? &c->svm : nullptr;
+    int rc = STR_ER_OK;
+    if (atlas_bytes > c->run_atlas.size()) {
+        if ((rc = c->run_atlas.ensure(c, atlas_bytes, "run tile atlas")) != STR_ER_OK) return rc;
+        ++c->n_atlas_grown;
+    }
+    if ((rc = c->run_tab.ensure(c, tab_bytes, "run tile tables")) != STR_ER_OK ||
+        (rc = ensure_scratch(c, ocr_layout(nullptr, n, m, true, false, false).bytes)) != STR_ER_OK)
+        return rc;
+    const OcrBuf buf = ocr_layout(c->scratch.d(), n, m, true, false, false);
+    uint8_t *h = c->run_tab.h(), *d = c->run_tab.d();
+    std::memcpy(h, tiles.data(), sizeof(RunTile) * n);
+    std::memcpy(h + o_box, boxes.data(), 16 * n);
+    std::memcpy(h + o_rot, rot.data(), sizeof(RotGeom) * n);
+    HIP_TRY(c, hipMemcpyAsync(d, h, tab_bytes, hipMemcpyHostToDevice, s));
+    launch_run_tiles(s, reinterpret_cast<const RunTile *>(d), (int)n, c->foot_bits.d<uint64_t>(), c->run_atlas.d(), A.width);
+    OcrSrc src{};
+    src.plane = c->run_atlas.d(); src.stride = (int32_t)A.width; src.inv = 0; src.boxes = reinterpret_cast<const int32_t *>(d + o_box);
+    src.rot = reinterpret_cast<const RotGeom *>(d + o_rot);
+    launch_ocr_features(s, src, (int)n, buf, m);
+    if (m) launch_svm_score(s, (int)n, buf, *m, true);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int32_t> label(reads ? n : 0);
+    std::vector<double>  prob(reads ? n : 0);
+    HIP_TRY(c, wait_stream(c, s));          // (wait, then copy into pageable memory, as the line scoring does)
+    HIP_TRY(c, hipMemcpyAsync(q.data(), buf.q, 1800 * n, hipMemcpyDeviceToHost, s));
+    if (reads) {
+        HIP_TRY(c, hipMemcpyAsync(label.data(), buf.label, 4 * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(prob.data(), buf.pbest, 8 * n, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, wait_stream(c, s));
+    if (reads)
+        for (size_t i = 0; i < n; ++i) (*reads)[i] = str_er_run_read{label[i], str_er_ocr_char(label[i]), prob[i]};
+    if (c->dbg_stats)        // developer aid
+        std::fprintf(stderr, "[str_er] run read: %zu runs, atlas %u x %u (%zu bytes, %zu bytes of tiles)\n", n, A.width, A.height, atlas_bytes,
+                     [&] { size_t b = 0; for (const RunTile &T : tiles) b += (size_t)(T.w + 3u) / 4u * 4u * T.h; return b; }());
+    return STR_ER_OK;
+}
+
 // one upload, the launches on s, one copy back, one wait (a pair pass again, with a larger table, if its pairs outgrew it).
 // LK: the links across adjacent frames as well (T.range), in the same upload and wait, with a table and a copy of their own
 // GP: the geometry of the footprints as well (k_foot_geom behind k_line_foot, its copy back ahead of the same wait; geom_collect afterwards)
@@ -491,7 +574,7 @@ void foot_rows32(const uint64_t *words, const FootLine &L, const str_er_line_foo
 } // namespace
 
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
-                      str_er_result *r, bool links, bool geom, bool words)
+                      str_er_result *r, bool links, bool geom, bool words, bool read)
 {
     const auto t0 = std::chrono::steady_clock::now();
     const size_t n_frames = b.frame_wh.size() / 2, n_lines = r->texts.size();
@@ -658,6 +741,13 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
             r->line_runs.clear(); r->words.clear();
         } else if (const int rcw = words_collect(c, WP, r->line_words, r->line_runs, r->words); rcw != STR_ER_OK) return rcw;
         r->have_line_words = true;
+        if (read) {         // (T.lines is the table k_foot_words read; its footprints are still in c->foot_bits)
+            std::vector<double> slopes(n_lines);
+            for (size_t t = 0; t < n_lines; ++t) slopes[t] = r->texts[t].slope;
+            if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features); rcr != STR_ER_OK)
+                return rcr;
+            r->have_run_reads = true;
+        }
         if (c->dbg_stats)        // developer aid (tools/dev_line_words.py)
             std::fprintf(stderr, "[str_er] line words: %zu lines, %zu run slots reserved, %zu runs, %zu words, %zu bytes back, host %.3f ms\n", n_lines,
                          WP.n_slots, r->line_runs.size(), r->words.size(), WP.bytes - WP.o_rec,
@@ -1097,10 +1187,11 @@ int str_er_set_word_gap(str_er_ctx *c, int32_t num, int32_t den)
     return STR_ER_OK;
 }
 
-int str_er_feet_words(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_words *line_words,
-                      str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words, int32_t *n_words)
-try {
-    if (!c) return STR_ER_EINVAL;
+// str_er_feet_words, and with read_runs str_er_feet_read on top of it (slopes, reads, q_out: its arguments)
+static int feet_words_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_words *line_words,
+                           str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words, int32_t *n_words,
+                           bool read_runs, const double *slopes, str_er_run_read *reads, uint8_t *q_out)
+{
     if (W < 1 || H < 1 || W > 65535 || H > 65535 || n < 0 || !n_runs || !n_words || (n > 0 && (!feet || !line_words)) || (runs && cap_runs < 0) ||
         (words && cap_words < 0))
         return fail(c, STR_ER_EINVAL, "bad arguments");
@@ -1109,6 +1200,12 @@ try {
     std::vector<uint64_t> bitwords;
     int rc = check_foot_boxes(c, W, H, feet, n, "");
     if (rc != STR_ER_OK) return rc;
+    const bool reading = read_runs && runs && words;          // (a counting call reads nothing)
+    if (read_runs && reads && !(c->svm_loaded && c->svm.dim == 1800))
+        return fail(c, STR_ER_ESTATE, "str_er_feet_read needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)");
+    if (read_runs && slopes)
+        for (int32_t t = 0; t < n; ++t)
+            if (!std::isfinite(slopes[t])) return fail(c, STR_ER_EINVAL, "slope " + std::to_string(t) + " is not finite");
     for (int32_t t = 0; t < n; ++t)
         if (feet[t].w > WORDS_MAX_BOX || feet[t].h > WORDS_MAX_BOX)
             return fail(c, STR_ER_ECAPACITY, "line " + std::to_string(t) + ": a foot box wider or taller than " + std::to_string(WORDS_MAX_BOX) + " pixels");
@@ -1140,10 +1237,44 @@ try {
     if (!runs || !words) return STR_ER_OK;
     if ((int64_t)rn.size() > (int64_t)cap_runs) return fail(c, STR_ER_ECAPACITY, std::to_string(rn.size()) + " glyph runs, cap_runs is " + std::to_string(cap_runs));
     if ((int64_t)wd.size() > (int64_t)cap_words) return fail(c, STR_ER_ECAPACITY, std::to_string(wd.size()) + " words, cap_words is " + std::to_string(cap_words));
+    if (reading && !rn.empty()) {          // (the footprints are still in c->foot_bits, the lines as the kernel read them in `lines`)
+        std::vector<str_er_run_read> rd;
+        std::vector<uint8_t>         q;
+        if ((rc = run_read_stage(c, c->stream, lines, lw, rn, slopes, reads ? &rd : nullptr, q)) != STR_ER_OK) return rc;
+        if (reads) std::memcpy(reads, rd.data(), sizeof(str_er_run_read) * rd.size());
+        if (q_out) std::memcpy(q_out, q.data(), q.size());
+    }
     if (!rn.empty()) std::memcpy(runs, rn.data(), sizeof(str_er_line_run) * rn.size());
     if (!wd.empty()) std::memcpy(words, wd.data(), sizeof(str_er_line_word) * wd.size());
     return STR_ER_OK;
+}
+
+int str_er_feet_words(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_words *line_words,
+                      str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words, int32_t *n_words)
+try {
+    if (!c) return STR_ER_EINVAL;
+    return feet_words_read(c, W, H, feet, bits, n, line_words, runs, cap_runs, n_runs, words, cap_words, n_words, false, nullptr, nullptr, nullptr);
 } ABI_GUARD(c)
+
+int str_er_feet_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, const double *slopes, int32_t n,
+                     str_er_line_words *line_words, str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words,
+                     int32_t *n_words, str_er_run_read *reads, uint8_t *q_out)
+try {
+    if (!c) return STR_ER_EINVAL;
+    return feet_words_read(c, W, H, feet, bits, n, line_words, runs, cap_runs, n_runs, words, cap_words, n_words, true, slopes, reads, q_out);
+} ABI_GUARD(c)
+
+int str_er_run_atlas_stats(const str_er_ctx *c, uint64_t *bytes, uint64_t *grown)
+{
+    if (!c) return STR_ER_EINVAL;
+    if (bytes) *bytes = c->run_atlas.size();
+    if (grown) *grown = c->n_atlas_grown;
+    return STR_ER_OK;
+}
+
+const str_er_run_read *str_er_result_run_reads(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_run_reads, &str_er_result::run_reads, n); }
+
+const uint8_t *str_er_result_run_features(const str_er_result *r, uint64_t *n_bytes) { return result_table(r, r && r->have_run_reads, &str_er_result::run_features, n_bytes); }
 
 const str_er_line_words *str_er_result_line_words(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_line_words, &str_er_result::line_words, n); }
 

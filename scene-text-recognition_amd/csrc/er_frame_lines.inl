@@ -40,6 +40,11 @@
 // Pass 2: the lane walks its word column once per interval of its occupancy word -- the popcount under the interval's bits and the
 // rows that have one -- and adds the result to the run's slot: in LDS (ds_add / ds_min / ds_max) for a line of up to WORDS_LDS_RUNS
 // runs, else with atomics on the run's output slot.  See DESIGN.md 3.17.
+//
+// k_run_tiles (STR_ER_WANT_RUN_READ, str_er_feet_read; the contract is at str_er_run_read): the glyph runs as byte tiles for the OCR scorer.
+// A wave takes a run; a lane four pixels of a tile row, lane after lane along the row and then down the rows, so that the stores of a
+// wave are consecutive dwords of the tile's rows.  The four bits come out of the footprint row with one shift, merged with the next
+// word once where they straddle it, and are spread into four bytes by shifts and one multiply.  See DESIGN.md 3.18.
 
 constexpr int FOOT_THREADS = 256;           // 4 waves, a job / a line each
 
@@ -423,6 +428,32 @@ __global__ __launch_bounds__(WORDS_THREADS) void k_foot_words(const FootLine *__
     }
 }
 
+constexpr int TILES_THREADS = 256;          // 4 waves, a run each
+
+__global__ __launch_bounds__(TILES_THREADS) void k_run_tiles(const RunTile *__restrict__ tiles, int n_tiles, const uint64_t *__restrict__ feet,
+                                                             uint8_t *__restrict__ atlas, uint32_t stride)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int a = blockIdx.x * (TILES_THREADS / 64) + wave; a < n_tiles; a += gridDim.x * (TILES_THREADS / 64)) {
+        const RunTile   T = tiles[a];
+        const uint32_t  wd = (T.w + 3u) / 4u, total = wd * T.h;         // dwords of a tile row, of the tile (at most 2^12 x 2^14)
+        const uint64_t *box = feet + T.bit_off;
+        uint8_t        *out = atlas + (size_t)T.ay * stride + T.ax;
+        for (uint32_t i = (uint32_t)lane; i < total; i += 64) {
+            const uint32_t  row = i / wd, d = i - row * wd;
+            const uint32_t  p = T.c0 + 4u * d, j = p >> 6, sh = p & 63u;
+            const uint64_t *rw = box + (uint64_t)row * T.pitch;
+            uint64_t v = rw[j] >> sh;
+            if (sh > 60u && j + 1u < T.pitch) v |= rw[j + 1u] << (64u - sh);        // (the four bits straddle two words)
+            uint32_t b = (uint32_t)v & 0xFu;
+            const uint32_t left = T.w - 4u * d;                                     // (columns past the run: another run's, or none)
+            if (left < 4u) b &= (1u << left) - 1u;
+            const uint32_t ones = (b & 1u) | (b & 2u) << 7 | (b & 4u) << 14 | (b & 8u) << 21;
+            *reinterpret_cast<uint32_t *>(out + (size_t)row * stride + 4u * d) = ~(ones * 0xFFu);
+        }
+    }
+}
+
 void launch_line_foot(hipStream_t s, const FootJob *jobs, int n_jobs, const FootLine *lines, const TextMapCand *members, const uint16_t *tabs,
                       const uint32_t *bits, uint64_t *feet, FootStat *stat)
 {
@@ -460,4 +491,11 @@ void launch_foot_words(hipStream_t s, const FootLine *lines, int n_lines, const 
     if (n_lines <= 0) return;
     const dim3 grid((unsigned)std::min(n_lines, 1 << 16));
     hipLaunchKernelGGL(k_foot_words, grid, dim3(WORDS_THREADS), 0, s, lines, n_lines, slots, feet, recs, runs);
+}
+
+void launch_run_tiles(hipStream_t s, const RunTile *tiles, int n_tiles, const uint64_t *feet, uint8_t *atlas, uint32_t stride)
+{
+    if (n_tiles <= 0) return;
+    const dim3 grid((unsigned)std::min((n_tiles + TILES_THREADS / 64 - 1) / (TILES_THREADS / 64), 1 << 16));
+    hipLaunchKernelGGL(k_run_tiles, grid, dim3(TILES_THREADS), 0, s, tiles, n_tiles, feet, atlas, stride);
 }

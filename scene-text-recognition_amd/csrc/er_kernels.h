@@ -169,5 +169,10 @@ void launch_foot_geom(hipStream_t s, const FootLine *lines, int n_lines, const G
 // and colmax into recs[line], the runs (frame columns and rows, ordered by column, word = -1) into runs from slots[line].first on, at
 // most slots[line].cap of them.  Every line must be at most WORDS_MAX_BOX wide and tall (a larger one is left without runs)
 void launch_foot_words(hipStream_t s, const FootLine *lines, int n_lines, const WordsSlot *slots, const uint64_t *feet, WordsRec *recs, WordsRun *runs);
+// launch_run_tiles (STR_ER_WANT_RUN_READ, str_er_feet_read): the byte tile of every run of tiles (0 where the footprint has the pixel,
+// else 255; the contract is at str_er_run_read) from the footprint words in feet into atlas, whose rows are stride bytes (a multiple
+// of 4; atlas aligned to 4).  A tile's rows and columns must lie inside its line's footprint and its place inside the atlas
+// (pack_run_tiles): the host checks both before the launch
+void launch_run_tiles(hipStream_t s, const RunTile *tiles, int n_tiles, const uint64_t *feet, uint8_t *atlas, uint32_t stride);
 
 } // namespace str_er

@@ -45,6 +45,6 @@ namespace str_er {
 #include "er_masks.inl"         // k_er_masks_small / _big: the pixel masks of regions
 #include "er_line_crops.inl"    // k_line_crops: the rectified grey / glyph image of every text line
 #include "er_text_map.inl"      // k_text_map: the frame-resolution text map and line-id map of every frame
-#include "er_frame_lines.inl"   // k_line_foot, k_foot_pairs, k_foot_links, k_foot_geom, k_foot_words: the footprints of the text lines in frame pixels, their overlaps, geometry and glyph runs
+#include "er_frame_lines.inl"   // k_line_foot, k_foot_pairs, k_foot_links, k_foot_geom, k_foot_words, k_run_tiles: the footprints of the text lines in frame pixels, their overlaps, geometry, glyph runs and the runs' byte tiles
 
 } // namespace str_er

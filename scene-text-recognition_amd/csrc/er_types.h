@@ -341,5 +341,23 @@ struct WordsRun {
 static_assert(sizeof(WordsRun) == 24, "WordsRun layout (host and device)");
 constexpr int WORDS_MAX_BOX = 16384;        // the widest / tallest footprint k_foot_words takes: 256 occupancy words in LDS, counts of 15 bits
 constexpr int WORDS_LDS_RUNS = 1024;        // k_foot_words combines the statistics of a line of up to WORDS_LDS_RUNS runs in LDS, of more in its slots
+// A glyph run as k_run_tiles expands it (STR_ER_WANT_RUN_READ, str_er_feet_read; the contract is at str_er_run_read): where its rows lie
+// in the footprint words of its line and where its byte tile lies in the atlas.  The host makes the table once the runs are compacted.
+struct RunTile {
+    uint64_t bit_off;        // the first word of the run's first row: the line's word_off + (y0 - the foot box's y) * pitch
+    uint32_t pitch;          // words of a footprint row of its line
+    uint32_t c0;             // the run's first column in the foot box: bit c0 of a row
+    uint32_t ax, ay;         // the tile's first byte in the atlas: column (a multiple of 4) and row
+    uint32_t w, h;           // the tile; it owns the columns ax .. ax + (w rounded up to 4) of its rows
+};
+static_assert(sizeof(RunTile) == 32, "RunTile layout (host and device)");
+constexpr uint32_t RUN_SHELF_W = 1024;      // bytes of an atlas row (a wider run widens the atlas to itself)
+struct RunAtlas {
+    uint32_t width, height;  // bytes of a row (the stride, a multiple of 4) and rows; 0 x 0 without tiles
+};
+// The places (ax, ay) of n tiles from their w, h: shelves of shelf_w bytes -- or of the widest tile, where one is wider -- filled
+// next-fit in the order given; a shelf is as tall as its tallest tile.  False when the atlas would take more than 2^31 - 1 rows or
+// a tile is empty.  HIP-free (words_host.cpp), so that a check program links it alone.
+bool pack_run_tiles(RunTile *tiles, size_t n, uint32_t shelf_w, RunAtlas &atlas);
 
 } // namespace str_er

@@ -29,6 +29,11 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
     const uint32_t sup = STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP;
     struct Rule { bool bad; int code; const char *msg; };
     const Rule rules[] = {
+        // STR_ER_WANT_RUN_READ rides on STR_ER_WANT_LINE_WORDS: refused without it and where it is refused, with a message that names
+        // this flag (its model rule is with STR_ER_STAGE_OCR_LINES' below); a call without the flag meets no new rule
+        {k.strip && any(STR_ER_WANT_RUN_READ), STR_ER_EINVAL, "STR_ER_WANT_RUN_READ is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_RUN_READ), STR_ER_EINVAL, "STR_ER_WANT_RUN_READ needs frames (not the per-plane calls)"},
+        {any(STR_ER_WANT_RUN_READ) && !any(STR_ER_WANT_LINE_WORDS), STR_ER_EINVAL, "STR_ER_WANT_RUN_READ needs STR_ER_WANT_LINE_WORDS"},
         // STR_ER_WANT_LINE_WORDS rides on STR_ER_WANT_FRAME_LINES as the two flags below do
         {k.strip && any(STR_ER_WANT_LINE_WORDS), STR_ER_EINVAL, "STR_ER_WANT_LINE_WORDS is not supported by the strip path (str_er_strip_merge)"},
         {!k.frames && any(STR_ER_WANT_LINE_WORDS), STR_ER_EINVAL, "STR_ER_WANT_LINE_WORDS needs frames (not the per-plane calls)"},
@@ -71,6 +76,8 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
         {any(STR_ER_WANT_LINE_GLYPHS) && !any(STR_ER_WANT_LINE_CROPS), STR_ER_EINVAL, "STR_ER_WANT_LINE_GLYPHS needs STR_ER_WANT_LINE_CROPS"},
         {any(STR_ER_STAGE_OCR_LINES) && !svm1800, STR_ER_ESTATE,
          "STR_ER_STAGE_OCR_LINES needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)"},
+        {any(STR_ER_WANT_RUN_READ) && !svm1800, STR_ER_ESTATE,
+         "STR_ER_WANT_RUN_READ needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)"},
         {any(STR_ER_STAGE_TRACK) && !k.all_planes, STR_ER_EINVAL, "STR_ER_STAGE_TRACK needs BGR frames (calc_color reads the YCrCb image)"},
     };
     for (const Rule &r : rules)

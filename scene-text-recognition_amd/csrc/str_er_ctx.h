@@ -147,6 +147,9 @@ struct str_er_result {
     std::vector<str_er_line_run> line_runs;
     std::vector<str_er_line_word> words;
     bool have_line_words = false;
+    std::vector<str_er_run_read> run_reads;      // STR_ER_WANT_RUN_READ: per run of line_runs, and their 1800 feature bytes each
+    std::vector<uint8_t> run_features;
+    bool have_run_reads = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -264,6 +267,10 @@ struct str_er_ctx {
     // STR_ER_WANT_LINE_WORDS / str_er_feet_words (str_er_set_word_gap)
     int32_t  word_num = 1, word_den = 3;
     PairBuf  words_out;               // slots | records | run slots of k_foot_words
+    // STR_ER_WANT_RUN_READ / str_er_feet_read
+    DevBuf   run_atlas;               // the byte tiles of the runs of a call (k_run_tiles), in shelves (pack_run_tiles)
+    PairBuf  run_tab;                 // tiles | boxes | rotations of the runs
+    uint64_t n_atlas_grown = 0;       // statistics: how often run_atlas was allocated or grown (str_er_run_atlas_stats)
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -536,8 +543,9 @@ struct SampleTabs {
 // links: STR_ER_WANT_LINE_LINKS as well (the links, tracks and edge feet of r, in the same stage)
 // geom: STR_ER_WANT_LINE_GEOM as well (the geometry of the lines and frame lines of r, k_foot_geom in the same stage)
 // words: STR_ER_WANT_LINE_WORDS as well (the glyph runs and words of the lines of r, k_foot_words in the same stage)
+// read: STR_ER_WANT_RUN_READ as well (the reading of every run: k_run_tiles and the scorer behind the stage's wait, with a wait of their own)
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
-                      str_er_result *r, bool links = false, bool geom = false, bool words = false);
+                      str_er_result *r, bool links = false, bool geom = false, bool words = false, bool read = false);
 // ---- defined in words_host.cpp (HIP-free)
 bool word_gap_ok(int32_t num, int32_t den);       // what str_er_set_word_gap takes
 constexpr int MASK_MAX_WIDTH = 16384;       // widest box the mask kernels take (er_masks.inl: MASK_MAX_WPL words of 64 pixels per lane)

@@ -1,8 +1,10 @@
 // words_host.cpp -- the C ABI, part 8b: the words of text lines from their glyph runs (str_er_words_from_runs; the contract is at
-// str_er_line_run in str_er.h).  Pure host and HIP-free: it includes nothing of the library but the public header, so that
-// tests/cpp/line_words_rules_check.cpp links this file alone under the host sanitizers.  The detect calls and str_er_feet_words
-// (api_frame_lines.cpp) form their words with this same function.
+// str_er_line_run in str_er.h), the character of a label (str_er_ocr_char) and the shelf packer of the run tiles' atlas
+// (pack_run_tiles; STR_ER_WANT_RUN_READ).  Pure host and HIP-free: it includes nothing of the library but the public header and the
+// plain structures of er_types.h, so that tests/cpp/line_words_rules_check.cpp and run_read_rules_check.cpp link this file alone
+// under the host sanitizers.  The detect calls, str_er_feet_words and str_er_feet_read (api_frame_lines.cpp) use these same functions.
 #include "../../include/str_er.h"
+#include "er_types.h"
 
 #include <algorithm>
 #include <cstring>
@@ -15,7 +17,40 @@ bool word_gap_ok(int32_t num, int32_t den) { return num >= 1 && num <= 65535 && 
 
 } // namespace str_er_host
 
+namespace str_er {
+
+bool pack_run_tiles(RunTile *tiles, size_t n, uint32_t shelf_w, RunAtlas &atlas)
+{
+    atlas = RunAtlas{0, 0};
+    if (n == 0) return true;
+    uint64_t width = (shelf_w + 3u) / 4u * 4u;
+    for (size_t k = 0; k < n; ++k) {
+        if (tiles[k].w == 0 || tiles[k].h == 0) return false;
+        width = std::max<uint64_t>(width, ((uint64_t)tiles[k].w + 3u) / 4u * 4u);
+    }
+    uint64_t x = 0, y = 0, shelf_h = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const uint64_t w4 = ((uint64_t)tiles[k].w + 3u) / 4u * 4u;
+        if (x + w4 > width) { y += shelf_h; x = 0; shelf_h = 0; }         // (the shelf is full: the next one)
+        tiles[k].ax = (uint32_t)x; tiles[k].ay = (uint32_t)y;
+        x += w4;
+        shelf_h = std::max<uint64_t>(shelf_h, tiles[k].h);
+        if (y + shelf_h > 0x7FFFFFFFull) return false;
+    }
+    atlas.width = (uint32_t)width; atlas.height = (uint32_t)(y + shelf_h);
+    return true;
+}
+
+} // namespace str_er
+
 extern "C" {
+
+int32_t str_er_ocr_char(int32_t label)
+{
+    static const char table[] = "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz&()";        // src/OCR.cpp:10
+    static_assert(sizeof(table) == 66, "65 characters");
+    return label >= 0 && label < 65 ? (int32_t)table[label] : (int32_t)'?';
+}
 
 int str_er_words_from_runs(str_er_line_run *runs, int32_t n_runs, str_er_line_words *line_words, int32_t n_lines, int32_t num, int32_t den,
                            str_er_line_word *words, int32_t cap_words, int32_t *n_words)

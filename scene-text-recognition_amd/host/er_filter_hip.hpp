@@ -508,6 +508,66 @@ public:
         return out;
     }
 
+    // Every glyph run read by the OCR scorer (STR_ER_WANT_RUN_READ; the contract is at str_er_run_read in include/str_er.h): one record per
+    // run of LineWords::runs, in the same order, and 1800 feature bytes per run.  Needs an SVM model of dim 1800 in the context.
+    struct RunReads {
+        std::vector<str_er_run_read> reads;
+        std::vector<uint8_t>         features;
+    };
+    // ... copied out of the result of a call with the flag (both empty without it)
+    static RunReads run_reads(const str_er_result *r)
+    {
+        RunReads out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_run_read *p = str_er_result_run_reads(r, &n)) out.reads.assign(p, p + n);
+        if (const uint8_t *p = str_er_result_run_features(r, &nb)) out.features.assign(p, p + nb);
+        return out;
+    }
+    // the string of word w: the characters of its runs
+    static std::string word_text(const LineWords &lw, const RunReads &rd, size_t w)
+    {
+        std::string s;
+        const str_er_line_word &W = lw.words.at(w);
+        for (int32_t k = W.first_run; k < W.first_run + W.n_runs; ++k) s.push_back((char)rd.reads.at((size_t)k).ch);
+        return s;
+    }
+    // the text of line t: its words joined by one blank (a frame line's text is that of its rep)
+    static std::string line_text(const LineWords &lw, const RunReads &rd, size_t t)
+    {
+        std::string s;
+        const str_er_line_words &L = lw.lines.at(t);
+        for (int32_t k = L.first_word; k < L.first_word + L.n_words; ++k) s += (k > L.first_word ? " " : "") + word_text(lw, rd, (size_t)k);
+        return s;
+    }
+    // feet_words and the reading of every run (str_er_feet_read): slopes one per foot, or empty: all 0; want_reads = false: the features
+    // only (no model needed)
+    std::pair<LineWords, RunReads> feet_read(int32_t width, int32_t height, const std::vector<str_er_line_foot> &feet, const std::vector<uint32_t> &bits,
+                                             const std::vector<double> &slopes = {}, bool want_reads = true)
+    {
+        if (!slopes.empty() && slopes.size() != feet.size()) throw std::invalid_argument("feet_read: one slope per foot");
+        LineWords lw;
+        RunReads  rd;
+        lw.lines.resize(feet.size());
+        const str_er_line_foot *fp = feet.empty() ? nullptr : feet.data();
+        const uint32_t         *bp = bits.empty() ? nullptr : bits.data();
+        const double           *sp = slopes.empty() ? nullptr : slopes.data();
+        str_er_line_words      *lp = lw.lines.empty() ? nullptr : lw.lines.data();
+        int32_t nr = 0, nw = 0;
+        check(str_er_feet_read(ctx_.get(), width, height, fp, bp, sp, (int32_t)feet.size(), lp, nullptr, 0, &nr, nullptr, 0, &nw, nullptr, nullptr));      // (counts)
+        lw.runs.resize((size_t)nr + 1);
+        lw.words.resize((size_t)nw + 1);
+        rd.reads.resize(want_reads ? (size_t)nr + 1 : 0);
+        rd.features.resize(1800 * ((size_t)nr + 1));
+        check(str_er_feet_read(ctx_.get(), width, height, fp, bp, sp, (int32_t)feet.size(), lp, lw.runs.data(), nr + 1, &nr, lw.words.data(), nw + 1, &nw,
+                               want_reads ? rd.reads.data() : nullptr, rd.features.data()));
+        lw.runs.resize((size_t)nr);
+        lw.words.resize((size_t)nw);
+        if (want_reads) rd.reads.resize((size_t)nr);
+        rd.features.resize(1800 * (size_t)nr);
+        return {std::move(lw), std::move(rd)};
+    }
+
     // The text lines of consecutive frames linked into text tracks (STR_ER_WANT_LINE_LINKS; the contract is at str_er_line_link in
     // include/str_er.h): the overlaps across adjacent frames, the track of every line of str_er_result_texts(), the tracks, the line
     // indices their first / count index, and the footprints of the lines of the first ([0]) and of the last frame ([1]).
