@@ -1,5 +1,6 @@
 // api_frame_lines.cpp -- the C ABI, part 8: one list of text lines per frame, merged across pyramid levels (STR_ER_WANT_FRAME_LINES in
-// run_batch, str_er_line_feet_regions on one host plane, str_er_frame_lines_from_pairs on the host alone) and the result accessors.
+// run_batch, str_er_line_feet_regions on one host plane) and the result accessors.  What touches no device is in lines_host.cpp
+// (str_er_frame_lines_from_pairs, str_er_text_tracks_from_links, the hulls and the oriented boxes) and in words_host.cpp.
 // The contract is at str_er_line_foot (str_er.h).  The host lists the members of every line with their pre-image boxes, cuts the
 // footprints into jobs and lists the lines of every frame; k_line_foot and k_foot_pairs (er_frame_lines.inl) do the per-pixel work;
 // the host sorts the pairs that come back and joins the duplicates (union-find).
@@ -14,13 +15,9 @@
 // STR_ER_WANT_LINE_WORDS (the contract is at str_er_line_run) likewise: k_foot_words cuts every footprint into glyph runs behind
 // k_line_foot, into (w + 1) / 2 reserved slots a line, which come back in the stage's one wait; the host compacts the slots and forms
 // the words (str_er_words_from_runs, words_host.cpp).  str_er_feet_words runs the same kernel on uploaded footprints.
-// STR_ER_WANT_RUN_READ (the contract is at str_er_run_read) behind that: only the host knows the compacted runs, so after the stage's
-// wait it lays their tiles out in an atlas (pack_run_tiles), k_run_tiles expands the footprint words still in c->foot_bits into it,
-// and the scorer's launch chain reads the atlas as a device plane (run_read_stage: a second enqueue and wait).  str_er_feet_read does
-// the same behind str_er_feet_words' kernel.
+// STR_ER_WANT_RUN_READ behind that, with a second enqueue and wait: run_read_stage (api_run_read.cpp).
 #include "str_er_ctx.h"
 
-#include <array>
 #include <numeric>
 
 namespace str_er_host {
@@ -190,102 +187,200 @@ struct PairTable {
 
 PairTable link_table(str_er_ctx *c) { return {c->link_out, "line link output", "line links: the link table overflowed twice (internal error)"}; }
 
-// A caller's feet and footprints (str_er_link_feet, str_er_feet_geom), in two steps.  The boxes of all feet; who: in front of "line t"
-int check_foot_boxes(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, int32_t n, const char *who)
+
+// n rows for a caller's array of cap rows; what: "pairs, cap_pairs"
+int check_cap(str_er_ctx *c, size_t n, int64_t cap, const char *what)
 {
-    for (int32_t t = 0; t < n; ++t) {
-        const str_er_line_foot &F = feet[t];
-        const std::string line = who + ("line " + std::to_string(t));
-        if (F.w < 0 || F.h < 0 || (F.w == 0) != (F.h == 0)) return fail(c, STR_ER_EINVAL, line + ": bad foot box");
-        if (F.w == 0) {
-            if (F.pixels) return fail(c, STR_ER_EINVAL, line + ": pixels in an empty foot box");
-            continue;
-        }
-        if (F.x < 0 || F.y < 0 || (int64_t)F.x + F.w > W || (int64_t)F.y + F.h > H) return fail(c, STR_ER_EINVAL, line + ": the foot box leaves the frame");
-    }
-    return STR_ER_OK;
+    return (int64_t)n > cap ? fail(c, STR_ER_ECAPACITY, std::to_string(n) + " " + what + " is " + std::to_string(cap)) : STR_ER_OK;
 }
 
-// ... then the footprints (rows of 32-bit words behind one another in bits) appended to lines / words as rows of 64-bit words, every
-// one checked against its foot
-int pack_footprints(str_er_ctx *c, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, std::vector<FootLine> &lines, std::vector<uint64_t> &words)
+// ... and copied into it; dst == null: the caller asked for the count alone
+int copy_out(str_er_ctx *c, const void *src, size_t n, size_t row_bytes, void *dst, int64_t cap, const char *what)
 {
-    const uint32_t *at = bits;
-    for (int32_t t = 0; t < n; ++t) {
-        const str_er_line_foot &F = feet[t];
-        FootLine L{};
-        L.word_off = words.size();
-        if (F.w != 0) {
-            if (!at) return fail(c, STR_ER_EINVAL, "footprint bits missing");
-            L.x = F.x; L.y = F.y; L.w = F.w; L.h = F.h; L.pitch = ((uint32_t)F.w + 63u) / 64u; L.count = 1;
-            const uint32_t pitch32 = ((uint32_t)F.w + 31u) / 32u, tail = (uint32_t)F.w & 31u;
-            uint64_t px = 0;
-            for (int32_t rr = 0; rr < F.h; ++rr, at += pitch32) {
-                if (tail && (at[pitch32 - 1] >> tail)) return fail(c, STR_ER_EINVAL, "a footprint has a bit set past its row's width");
-                for (uint32_t k = 0; k < L.pitch; ++k) {
-                    const uint64_t v = (uint64_t)at[2 * k] | (2 * k + 1 < pitch32 ? (uint64_t)at[2 * k + 1] << 32 : 0ull);
-                    px += (uint64_t)__builtin_popcountll(v);
-                    words.push_back(v);
-                }
-            }
-            if (px != F.pixels) return fail(c, STR_ER_EINVAL, "a foot's pixels are not the number of bits set in its footprint");
-        }
-        lines.push_back(L);
-    }
+    if (!dst) return STR_ER_OK;
+    if (const int rc = check_cap(c, n, cap, what); rc != STR_ER_OK) return rc;
+    if (n) std::memcpy(dst, src, row_bytes * n);
     return STR_ER_OK;
 }
 
 constexpr int32_t GEOM_MAX_BOX = 16384;          // the widest / tallest foot box whose moments are promised not to overflow
 
-// k_foot_geom over the lines of a launch: where every line's vertices and scratch rows go, and the layout of the geometry buffer
-// (slots | records | vertices; the same on both sides)
-struct GeomPlan {
-    std::vector<GeomSlot> slots;
-    size_t n_lines = 0, n_pts = 0, x_words = 0, o_rec = 0, o_xy = 0, bytes = 0;
+// The feet and footprints a caller hands in (str_er_link_feet: two sets behind one another; str_er_feet_geom, str_er_feet_words,
+// str_er_feet_read: one): checked, packed into a table of lines and rows of 64-bit words, and uploaded into c->foot_tab (the lines
+// first) and c->foot_bits on c->stream.  It owns the host words, which the queued upload reads: whoever leaves the scope before a wait
+// of the stream has succeeded (wait) -- an enqueue that failed behind the upload -- drains the stream first.
+struct CallerFeet {
+    str_er_ctx           *c;
+    std::vector<FootLine> lines;
+    std::vector<uint64_t> words;
+    bool                  queued = false;
+
+    explicit CallerFeet(str_er_ctx *ctx) : c(ctx) {}
+    ~CallerFeet() { if (queued) (void)hipStreamSynchronize(c->stream); }
+
+    // the boxes of all feet of a set; who: in front of "line t"
+    int check_boxes(int32_t W, int32_t H, const str_er_line_foot *feet, int32_t n, const char *who)
+    {
+        for (int32_t t = 0; t < n; ++t) {
+            const str_er_line_foot &F = feet[t];
+            const std::string line = who + ("line " + std::to_string(t));
+            if (F.w < 0 || F.h < 0 || (F.w == 0) != (F.h == 0)) return fail(c, STR_ER_EINVAL, line + ": bad foot box");
+            if (F.w == 0) {
+                if (F.pixels) return fail(c, STR_ER_EINVAL, line + ": pixels in an empty foot box");
+                continue;
+            }
+            if (F.x < 0 || F.y < 0 || (int64_t)F.x + F.w > W || (int64_t)F.y + F.h > H) return fail(c, STR_ER_EINVAL, line + ": the foot box leaves the frame");
+        }
+        return STR_ER_OK;
+    }
+    // ... against the largest box the kernel behind takes (GEOM_MAX_BOX, WORDS_MAX_BOX)
+    int check_limit(const str_er_line_foot *feet, int32_t n, int32_t max_box)
+    {
+        for (int32_t t = 0; t < n; ++t)
+            if (feet[t].w > max_box || feet[t].h > max_box)
+                return fail(c, STR_ER_ECAPACITY, "line " + std::to_string(t) + ": a foot box wider or taller than " + std::to_string(max_box) + " pixels");
+        return STR_ER_OK;
+    }
+    // ... then the footprints of the set (rows of 32-bit words behind one another in bits) appended to lines / words as rows of 64-bit
+    // words, every one checked against its foot.  blank_empty: a box without a bit is an empty footprint (a zeroed line)
+    int pack(const str_er_line_foot *feet, const uint32_t *bits, int32_t n, bool blank_empty)
+    {
+        const uint32_t *at = bits;
+        for (int32_t t = 0; t < n; ++t) {
+            const str_er_line_foot &F = feet[t];
+            FootLine L{};
+            L.word_off = words.size();
+            if (F.w != 0) {
+                if (!at) return fail(c, STR_ER_EINVAL, "footprint bits missing");
+                L.x = F.x; L.y = F.y; L.w = F.w; L.h = F.h; L.pitch = ((uint32_t)F.w + 63u) / 64u; L.count = 1;
+                const uint32_t pitch32 = ((uint32_t)F.w + 31u) / 32u, tail = (uint32_t)F.w & 31u;
+                uint64_t px = 0;
+                for (int32_t rr = 0; rr < F.h; ++rr, at += pitch32) {
+                    if (tail && (at[pitch32 - 1] >> tail)) return fail(c, STR_ER_EINVAL, "a footprint has a bit set past its row's width");
+                    for (uint32_t k = 0; k < L.pitch; ++k) {
+                        const uint64_t v = (uint64_t)at[2 * k] | (2 * k + 1 < pitch32 ? (uint64_t)at[2 * k + 1] << 32 : 0ull);
+                        px += (uint64_t)__builtin_popcountll(v);
+                        words.push_back(v);
+                    }
+                }
+                if (px != F.pixels) return fail(c, STR_ER_EINVAL, "a foot's pixels are not the number of bits set in its footprint");
+            }
+            lines.push_back(blank_empty && F.pixels == 0 ? FootLine{} : L);
+        }
+        return STR_ER_OK;
+    }
+    // room for tab_need bytes of tables and for the words; the caller puts what lies behind the lines into c->foot_tab.h() ...
+    int reserve(size_t tab_need)
+    {
+        HIP_TRY(c, hipSetDevice(c->prm.device));
+        const int rc = c->foot_tab.ensure(c, tab_need, "frame line tables");
+        return rc != STR_ER_OK ? rc : c->foot_bits.ensure(c, 8 * words.size(), "line footprints");
+    }
+    // ... and both are on their way
+    int upload(size_t tab_need)
+    {
+        hipStream_t s = c->stream;
+        std::memcpy(c->foot_tab.h(), lines.data(), sizeof(FootLine) * lines.size());
+        HIP_TRY(c, hipMemcpyAsync(c->foot_tab.d(), c->foot_tab.h(), tab_need, hipMemcpyHostToDevice, s));
+        queued = true;
+        HIP_TRY(c, hipMemcpyAsync(c->foot_bits.d<uint64_t>(), words.data(), 8 * words.size(), hipMemcpyHostToDevice, s));
+        return STR_ER_OK;
+    }
+    int wait()
+    {
+        hipStream_t s = c->stream;
+        HIP_TRY(c, wait_stream(c, s));
+        queued = false;
+        return STR_ER_OK;
+    }
+    const FootLine *d_lines() const { return reinterpret_cast<const FootLine *>(c->foot_tab.d()); }
 };
 
-// the slots uploaded, the kernel and the copy back enqueued on s behind whatever made the footprints in c->foot_bits.d<uint64_t>(); geom_collect after the wait
-int geom_enqueue(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const FootLine *d_lines, GeomPlan &P)
-{
-    P.n_lines = lines.size();
-    P.slots.assign(P.n_lines, GeomSlot{0, 0});
-    uint64_t pts = 0, xw = 0;
-    for (size_t t = 0; t < P.n_lines; ++t) {
-        const FootLine &L = lines[t];
-        if (L.w <= 0 || L.h <= 0) continue;
-        P.slots[t].pt_first = (uint32_t)pts;
-        pts += 2ull * ((uint64_t)L.h + 1u);          // (a chain has at most one vertex per height 0 .. h)
-        if (L.h + 1 > GEOM_LDS_ROWS) { P.slots[t].x_first = (uint32_t)xw; xw += (uint64_t)L.h + 1u; }
-        if (pts > 0x7FFFFFFFull) return fail(c, STR_ER_ECAPACITY, "line geometry: more than 2^31 hull vertices to reserve");
+// One per-line side pass behind the footprints in c->foot_bits (k_foot_geom, k_foot_words): a slot per line that tells the kernel
+// where the line's elements go, a record per line that the kernel leaves, and the elements (hull vertices, run slots), in one buffer
+// laid out as slots | records | elements (the same on both sides).  enqueue; the caller's wait; then the records and elements are
+// on the page-locked side.
+template <typename Slot, typename Rec, size_t ELEM> struct LinePass {
+    PairBuf    &buf;
+    const char *what, *too_many;          // the buffer's name, and the error of more than 2^31 elements
+    DevBuf     *extra = nullptr;          // a second buffer of the kernel's, of extra_bytes (the slot rule counts them)
+    const char *extra_what = nullptr;
+    size_t      extra_bytes = 0;
+    std::vector<Slot> slots;
+    size_t      n_lines = 0, n_elems = 0, o_rec = 0, o_elem = 0, bytes = 0;
+
+    bool   launched() const { return bytes != 0; }
+    size_t bytes_back() const { return bytes - o_rec; }
+    Rec    rec(size_t t) const { Rec R; std::memcpy(&R, buf.h() + o_rec + sizeof(Rec) * t, sizeof R); return R; }
+    const uint8_t *elems() const { return buf.h() + o_elem; }
+
+    // rule(L, slot, first): fills the slot of a line with a footprint, whose elements start at `first`, and returns how many it reserves;
+    // launch(slots, records, elements): the kernel, on the device side.  The slots uploaded, the kernel and the copy back enqueued on s.
+    template <typename Rule, typename Launch> int enqueue(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, Rule rule, Launch launch)
+    {
+        n_lines = lines.size();
+        slots.assign(n_lines, Slot{0, 0});
+        uint64_t at = 0;
+        for (size_t t = 0; t < n_lines; ++t) {
+            const FootLine &L = lines[t];
+            if (L.w <= 0 || L.h <= 0) continue;
+            at += rule(L, slots[t], (uint32_t)at);
+            if (at > 0x7FFFFFFFull) return fail(c, STR_ER_ECAPACITY, too_many);
+        }
+        n_elems = (size_t)at;
+        if (n_lines == 0) return STR_ER_OK;
+        o_rec = align_up(sizeof(Slot) * n_lines, 256); o_elem = align_up(o_rec + sizeof(Rec) * n_lines, 256);
+        bytes = o_elem + ELEM * n_elems;
+        int rc = buf.ensure(c, bytes, what);
+        if (rc != STR_ER_OK || (extra && (rc = extra->ensure(c, extra_bytes, extra_what)) != STR_ER_OK)) return rc;
+        std::memcpy(buf.h(), slots.data(), sizeof(Slot) * n_lines);
+        HIP_TRY(c, hipMemcpyAsync(buf.d(), buf.h(), sizeof(Slot) * n_lines, hipMemcpyHostToDevice, s));
+        launch(reinterpret_cast<const Slot *>(buf.d()), reinterpret_cast<Rec *>(buf.d() + o_rec), buf.d() + o_elem);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(buf.h() + o_rec, buf.d() + o_rec, bytes - o_rec, hipMemcpyDeviceToHost, s));
+        return STR_ER_OK;
     }
-    P.n_pts = (size_t)pts; P.x_words = (size_t)xw;
-    if (P.n_lines == 0) return STR_ER_OK;
-    P.o_rec = align_up(sizeof(GeomSlot) * P.n_lines, 256); P.o_xy = align_up(P.o_rec + sizeof(GeomRec) * P.n_lines, 256);
-    P.bytes = P.o_xy + 8 * P.n_pts;
-    int rc = c->geom_out.ensure(c, P.bytes, "line geometry output");
-    if (rc != STR_ER_OK || (rc = c->geom_x.ensure(c, 8 * P.x_words, "line geometry rows")) != STR_ER_OK) return rc;
-    std::memcpy(c->geom_out.h(), P.slots.data(), sizeof(GeomSlot) * P.n_lines);
-    HIP_TRY(c, hipMemcpyAsync(c->geom_out.d(), c->geom_out.h(), sizeof(GeomSlot) * P.n_lines, hipMemcpyHostToDevice, s));
-    launch_foot_geom(s, d_lines, (int)P.n_lines, reinterpret_cast<const GeomSlot *>(c->geom_out.d()), c->foot_bits.d<uint64_t>(), c->geom_x.d<uint64_t>(),
-                     reinterpret_cast<GeomRec *>(c->geom_out.d() + P.o_rec), reinterpret_cast<int32_t *>(c->geom_out.d() + P.o_xy));
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->geom_out.h() + P.o_rec, c->geom_out.d() + P.o_rec, P.bytes - P.o_rec, hipMemcpyDeviceToHost, s));
-    return STR_ER_OK;
+};
+
+static_assert(sizeof(WordsRun) == sizeof(str_er_line_run), "the device writes str_er_line_run records");
+using GeomPass = LinePass<GeomSlot, GeomRec, 8>;                          // elements: hull vertices, x and y
+using WordsPass = LinePass<WordsSlot, WordsRec, sizeof(WordsRun)>;        // elements: run slots
+
+GeomPass geom_pass(str_er_ctx *c)
+{
+    return {c->geom_out, "line geometry output", "line geometry: more than 2^31 hull vertices to reserve", &c->geom_x, "line geometry rows"};
+}
+WordsPass words_pass(str_er_ctx *c) { return {c->words_out, "line words output", "line words: more than 2^31 glyph runs to reserve"}; }
+
+// k_foot_geom over the lines of a launch, behind whatever made their footprints; geom_collect after the wait
+int geom_enqueue(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const FootLine *d_lines, GeomPass &P)
+{
+    return P.enqueue(
+        c, s, lines,
+        [&](const FootLine &L, GeomSlot &S, uint32_t first) {
+            S.pt_first = first;
+            if (L.h + 1 > GEOM_LDS_ROWS) { S.x_first = (uint32_t)(P.extra_bytes / 8); P.extra_bytes += 8 * ((size_t)L.h + 1u); }         // (its scratch rows)
+            return 2ull * ((uint64_t)L.h + 1u);          // (a chain has at most one vertex per height 0 .. h)
+        },
+        [&](const GeomSlot *slots, GeomRec *recs, uint8_t *xy) {
+            launch_foot_geom(s, d_lines, (int)lines.size(), slots, c->foot_bits.d<uint64_t>(), c->geom_x.d<uint64_t>(), recs, reinterpret_cast<int32_t *>(xy));
+        });
 }
 
-// after the wait: one record per line, its vertices appended to xy (x, y pairs) and its box made (str_er_quad_from_hull)
-int geom_collect(str_er_ctx *c, const GeomPlan &P, std::vector<str_er_line_geom> &geoms, std::vector<int32_t> &xy)
+// after the wait: one record per line (n_lines of them), its vertices appended to xy (x, y pairs) and its box made
+// (str_er_quad_from_hull).  Nothing was launched (no footprint at all): every line is empty
+int geom_collect(str_er_ctx *c, const GeomPass &P, size_t n_lines, std::vector<str_er_line_geom> &geoms, std::vector<int32_t> &xy)
 {
-    geoms.assign(P.n_lines, str_er_line_geom{});
-    for (size_t t = 0; t < P.n_lines; ++t) {
+    geoms.assign(n_lines, str_er_line_geom{});
+    for (str_er_line_geom &G : geoms) G.edge = -1;
+    if (!P.launched()) return STR_ER_OK;
+    for (size_t t = 0; t < n_lines; ++t) {
         str_er_line_geom &G = geoms[t];
-        GeomRec R;
-        std::memcpy(&R, c->geom_out.h() + P.o_rec + sizeof(GeomRec) * t, sizeof R);
-        G.edge = -1;
+        const GeomRec R = P.rec(t);
         if (R.count == 0) continue;
         const uint32_t first = P.slots[t].pt_first;
-        if (R.count < 4 || (size_t)first + R.count > P.n_pts) return fail(c, STR_ER_EHIP, "line geometry: a hull outside its vertices (internal error)");
-        const int32_t *src = reinterpret_cast<const int32_t *>(c->geom_out.h() + P.o_xy) + 2 * (size_t)first;
+        if (R.count < 4 || (size_t)first + R.count > P.n_elems) return fail(c, STR_ER_EHIP, "line geometry: a hull outside its vertices (internal error)");
+        const int32_t *src = reinterpret_cast<const int32_t *>(P.elems()) + 2 * (size_t)first;
         G.first = (uint32_t)(xy.size() / 2); G.count = R.count;
         xy.insert(xy.end(), src, src + 2 * (size_t)R.count);
         G.pixels = R.pixels; G.m10 = R.m10; G.m01 = R.m01; G.m20 = R.m20; G.m11 = R.m11; G.m02 = R.m02;
@@ -294,15 +389,6 @@ int geom_collect(str_er_ctx *c, const GeomPlan &P, std::vector<str_er_line_geom>
     }
     return STR_ER_OK;
 }
-
-static_assert(sizeof(WordsRun) == sizeof(str_er_line_run), "the device writes str_er_line_run records");
-
-// k_foot_words over the lines of a launch: the run slots of every line, and the layout of the buffer (slots | records | run slots;
-// the same on both sides)
-struct WordsPlan {
-    std::vector<WordsSlot> slots;
-    size_t n_lines = 0, n_slots = 0, o_rec = 0, o_run = 0, bytes = 0;
-};
 
 // a footprint box k_foot_words does not take (checked before anything is enqueued); who: in front of the message
 int words_check_boxes(str_er_ctx *c, const std::vector<FootLine> &lines, const char *who)
@@ -313,149 +399,65 @@ int words_check_boxes(str_er_ctx *c, const std::vector<FootLine> &lines, const c
     return STR_ER_OK;
 }
 
-// the slots uploaded, the kernel and the copy back enqueued on s behind whatever made the footprints in c->foot_bits; words_collect after the wait
-int words_enqueue(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const FootLine *d_lines, WordsPlan &P)
+// k_foot_words over the lines of a launch, behind whatever made their footprints; words_collect after the wait
+int words_enqueue(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const FootLine *d_lines, WordsPass &P)
 {
-    P.n_lines = lines.size();
-    P.slots.assign(P.n_lines, WordsSlot{0, 0});
-    uint64_t at = 0;
-    for (size_t t = 0; t < P.n_lines; ++t) {
-        const FootLine &L = lines[t];
-        if (L.w <= 0 || L.h <= 0) continue;
-        P.slots[t] = WordsSlot{(uint32_t)at, ((uint32_t)L.w + 1u) / 2u};          // (the most runs a row of w columns holds)
-        at += P.slots[t].cap;
-        if (at > 0x7FFFFFFFull) return fail(c, STR_ER_ECAPACITY, "line words: more than 2^31 glyph runs to reserve");
-    }
-    P.n_slots = (size_t)at;
-    if (P.n_lines == 0) return STR_ER_OK;
-    P.o_rec = align_up(sizeof(WordsSlot) * P.n_lines, 256); P.o_run = align_up(P.o_rec + sizeof(WordsRec) * P.n_lines, 256);
-    P.bytes = P.o_run + sizeof(WordsRun) * P.n_slots;
-    const int rc = c->words_out.ensure(c, P.bytes, "line words output");
-    if (rc != STR_ER_OK) return rc;
-    std::memcpy(c->words_out.h(), P.slots.data(), sizeof(WordsSlot) * P.n_lines);
-    HIP_TRY(c, hipMemcpyAsync(c->words_out.d(), c->words_out.h(), sizeof(WordsSlot) * P.n_lines, hipMemcpyHostToDevice, s));
-    launch_foot_words(s, d_lines, (int)P.n_lines, reinterpret_cast<const WordsSlot *>(c->words_out.d()), c->foot_bits.d<uint64_t>(),
-                      reinterpret_cast<WordsRec *>(c->words_out.d() + P.o_rec), reinterpret_cast<WordsRun *>(c->words_out.d() + P.o_run));
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->words_out.h() + P.o_rec, c->words_out.d() + P.o_rec, P.bytes - P.o_rec, hipMemcpyDeviceToHost, s));
-    return STR_ER_OK;
+    return P.enqueue(
+        c, s, lines,
+        [](const FootLine &L, WordsSlot &S, uint32_t first) {
+            S = WordsSlot{first, ((uint32_t)L.w + 1u) / 2u};          // (the most runs a row of w columns holds)
+            return (uint64_t)S.cap;
+        },
+        [&](const WordsSlot *slots, WordsRec *recs, uint8_t *runs) {
+            launch_foot_words(s, d_lines, (int)lines.size(), slots, c->foot_bits.d<uint64_t>(), recs, reinterpret_cast<WordsRun *>(runs));
+        });
 }
 
-// after the wait: the slots compacted into runs (back to back in line order), one record per line, and the words formed
-// (str_er_words_from_runs with the context's gap)
-int words_collect(str_er_ctx *c, const WordsPlan &P, std::vector<str_er_line_words> &line_words, std::vector<str_er_line_run> &runs,
+// after the wait: the slots compacted into runs (back to back in line order), one record per line (n_lines of them), and the words
+// formed (str_er_words_from_runs with the context's gap).  Nothing was launched (no footprint at all): no runs and no words
+int words_collect(str_er_ctx *c, const WordsPass &P, size_t n_lines, std::vector<str_er_line_words> &line_words, std::vector<str_er_line_run> &runs,
                   std::vector<str_er_line_word> &words)
 {
-    line_words.assign(P.n_lines, str_er_line_words{});
-    runs.clear();
-    const uint8_t *h = P.n_lines ? c->words_out.h() : nullptr;
-    for (size_t t = 0; t < P.n_lines; ++t) {
-        WordsRec R;
-        std::memcpy(&R, h + P.o_rec + sizeof(WordsRec) * t, sizeof R);
+    line_words.assign(n_lines, str_er_line_words{});
+    runs.clear(); words.clear();
+    if (!P.launched()) return STR_ER_OK;
+    for (size_t t = 0; t < n_lines; ++t) {
+        const WordsRec R = P.rec(t);
         if (R.n_runs > P.slots[t].cap || (R.n_runs == 0) != (R.colmax == 0))
             return fail(c, STR_ER_EHIP, "line words: a line's runs outside its slots (internal error)");
         str_er_line_words &LW = line_words[t];
         LW.first_run = (int32_t)runs.size(); LW.n_runs = (int32_t)R.n_runs; LW.colmax = R.colmax;
         if (R.n_runs == 0) continue;
         runs.resize(runs.size() + R.n_runs);
-        std::memcpy(runs.data() + LW.first_run, h + P.o_run + sizeof(WordsRun) * P.slots[t].first, sizeof(WordsRun) * R.n_runs);
+        std::memcpy(runs.data() + LW.first_run, P.elems() + sizeof(WordsRun) * P.slots[t].first, sizeof(WordsRun) * R.n_runs);
     }
     if (runs.size() > 0x7FFFFFFFull) return fail(c, STR_ER_ECAPACITY, "line words: more than 2^31 glyph runs");
     words.resize(runs.size());
     int32_t n_words = 0;
-    if (str_er_words_from_runs(runs.data(), (int32_t)runs.size(), line_words.data(), (int32_t)P.n_lines, c->word_num, c->word_den, words.data(),
+    if (str_er_words_from_runs(runs.data(), (int32_t)runs.size(), line_words.data(), (int32_t)n_lines, c->word_num, c->word_den, words.data(),
                                (int32_t)words.size(), &n_words) != STR_ER_OK)
         return fail(c, STR_ER_EHIP, "line words: the device's runs are not runs (internal error)");
     words.resize((size_t)n_words);
     return STR_ER_OK;
 }
 
-// The reading of the compacted runs of a launch whose footprints are still in c->foot_bits (lines: the table k_foot_words read):
-// the tiles laid out and expanded into the atlas, then chain_run's launch chain on the atlas as a device plane with one box a run and
-// the slope of the run's line (slopes: one per line, or null: all 0; a slope that is not finite counts as 0).  One upload, the
-// launches, the copies back and a wait of its own on s.  reads == null: the features only (no model needed).
-int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
-                   const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q)
-{
-    const size_t n = runs.size();
-    if (reads) reads->assign(n, str_er_run_read{});
-    q.assign(1800 * n, 0);
-    if (n == 0) return STR_ER_OK;
-    if (n > 0x7FFFFFFFull / 1800) return fail(c, STR_ER_ECAPACITY, "run read: too many glyph runs");
-    std::vector<RunTile> tiles(n);
-    std::vector<RotGeom> rot(n);
-    for (size_t t = 0; t < lines.size(); ++t) {
-        const FootLine &L = lines[t];
-        const double    sl = slopes && std::isfinite(slopes[t]) ? slopes[t] : 0.0;
-        for (int32_t k = 0; k < line_words[t].n_runs; ++k) {
-            const size_t           i = (size_t)line_words[t].first_run + (size_t)k;
-            const str_er_line_run &R = runs[i];
-            // (the kernel reads the rows and columns of the run in its line's words: they must lie inside the foot box)
-            if (i >= n || R.x0 < L.x || R.x1 <= R.x0 || R.x1 > L.x + L.w || R.y0 < L.y || R.y1 <= R.y0 || R.y1 > L.y + L.h)
-                return fail(c, STR_ER_EHIP, "run read: a glyph run outside its line's footprint (internal error)");
-            RunTile &T = tiles[i];
-            T.bit_off = L.word_off + (uint64_t)(R.y0 - L.y) * L.pitch; T.pitch = L.pitch; T.c0 = (uint32_t)(R.x0 - L.x);
-            T.w = (uint32_t)(R.x1 - R.x0); T.h = (uint32_t)(R.y1 - R.y0);
-            rot[i] = make_rot_geom((int)T.w, (int)T.h, sl);
-        }
-    }
-    RunAtlas A;
-    if (!pack_run_tiles(tiles.data(), n, RUN_SHELF_W, A)) return fail(c, STR_ER_ECAPACITY, "run read: the tiles of the glyph runs do not fit an atlas");
-    std::vector<int32_t> boxes(4 * n);
-    for (size_t i = 0; i < n; ++i) {
-        const RunTile &T = tiles[i];
-        if ((uint64_t)T.ax + (T.w + 3u) / 4u * 4u > A.width || (uint64_t)T.ay + T.h > A.height)
-            return fail(c, STR_ER_EHIP, "run read: a tile outside the atlas (internal error)");
-        boxes[4 * i] = (int32_t)T.ax; boxes[4 * i + 1] = (int32_t)T.ay; boxes[4 * i + 2] = (int32_t)T.w; boxes[4 * i + 3] = (int32_t)T.h;
-    }
-    const size_t atlas_bytes = (size_t)A.width * A.height;
-    const size_t o_box = align_up(sizeof(RunTile) * n, 256), o_rot = align_up(o_box + 16 * n, 256), tab_bytes = o_rot + sizeof(RotGeom) * n;
-    const SvmDev *m = reads ? &c->svm : nullptr;
-    int rc = STR_ER_OK;
-    if (atlas_bytes > c->run_atlas.size()) {
-        if ((rc = c->run_atlas.ensure(c, atlas_bytes, "run tile atlas")) != STR_ER_OK) return rc;
-        ++c->n_atlas_grown;
-    }
-    if ((rc = c->run_tab.ensure(c, tab_bytes, "run tile tables")) != STR_ER_OK ||
-        (rc = ensure_scratch(c, ocr_layout(nullptr, n, m, true, false, false).bytes)) != STR_ER_OK)
-        return rc;
-    const OcrBuf buf = ocr_layout(c->scratch.d(), n, m, true, false, false);
-    uint8_t *h = c->run_tab.h(), *d = c->run_tab.d();
-    std::memcpy(h, tiles.data(), sizeof(RunTile) * n);
-    std::memcpy(h + o_box, boxes.data(), 16 * n);
-    std::memcpy(h + o_rot, rot.data(), sizeof(RotGeom) * n);
-    HIP_TRY(c, hipMemcpyAsync(d, h, tab_bytes, hipMemcpyHostToDevice, s));
-    launch_run_tiles(s, reinterpret_cast<const RunTile *>(d), (int)n, c->foot_bits.d<uint64_t>(), c->run_atlas.d(), A.width);
-    OcrSrc src{};
-    src.plane = c->run_atlas.d(); src.stride = (int32_t)A.width; src.inv = 0; src.boxes = reinterpret_cast<const int32_t *>(d + o_box);
-    src.rot = reinterpret_cast<const RotGeom *>(d + o_rot);
-    launch_ocr_features(s, src, (int)n, buf, m);
-    if (m) launch_svm_score(s, (int)n, buf, *m, true);
-    HIP_TRY(c, hipGetLastError());
-    std::vector<int32_t> label(reads ? n : 0);
-    std::vector<double>  prob(reads ? n : 0);
-    HIP_TRY(c, wait_stream(c, s));          // (wait, then copy into pageable memory, as the line scoring does)
-    HIP_TRY(c, hipMemcpyAsync(q.data(), buf.q, 1800 * n, hipMemcpyDeviceToHost, s));
-    if (reads) {
-        HIP_TRY(c, hipMemcpyAsync(label.data(), buf.label, 4 * n, hipMemcpyDeviceToHost, s));
-        HIP_TRY(c, hipMemcpyAsync(prob.data(), buf.pbest, 8 * n, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(c, wait_stream(c, s));
-    if (reads)
-        for (size_t i = 0; i < n; ++i) (*reads)[i] = str_er_run_read{label[i], str_er_ocr_char(label[i]), prob[i]};
-    if (c->dbg_stats)        // developer aid
-        std::fprintf(stderr, "[str_er] run read: %zu runs, atlas %u x %u (%zu bytes, %zu bytes of tiles)\n", n, A.width, A.height, atlas_bytes,
-                     [&] { size_t b = 0; for (const RunTile &T : tiles) b += (size_t)(T.w + 3u) / 4u * 4u * T.h; return b; }());
-    return STR_ER_OK;
-}
+// what a stage leaves behind its wait: the pairs, and what rode along (LineStageWants)
+struct StageOut {
+    FootOut   feet;
+    LinkOut   links;
+    GeomPass  geom;
+    WordsPass words;
+    explicit StageOut(str_er_ctx *c) : geom(geom_pass(c)), words(words_pass(c)) {}
+};
 
 // one upload, the launches on s, one copy back, one wait (a pair pass again, with a larger table, if its pairs outgrew it).
-// LK: the links across adjacent frames as well (T.range), in the same upload and wait, with a table and a copy of their own
-// GP: the geometry of the footprints as well (k_foot_geom behind k_line_foot, its copy back ahead of the same wait; geom_collect afterwards)
-// WP: their glyph runs as well (k_foot_words, in the same way; words_collect afterwards)
-int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t *d_bits, bool in_batch, FootOut &O, LinkOut *LK = nullptr,
-               GeomPlan *GP = nullptr, WordsPlan *WP = nullptr)
+// want.links: the links across adjacent frames as well (T.range), in the same upload and wait, with a table and a copy of their own
+// want.geom: the geometry of the footprints as well (k_foot_geom behind k_line_foot, its copy back ahead of the same wait; geom_collect afterwards)
+// want.words: their glyph runs as well (k_foot_words, in the same way; words_collect afterwards)
+int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t *d_bits, bool in_batch, const LineStageWants &want, StageOut &S)
 {
+    FootOut &O = S.feet;
+    LinkOut *LK = want.links ? &S.links : nullptr;
     const size_t n_lines = T.lines.size();
     O.stat.assign(n_lines, FootStat{});
     O.pairs.clear();
@@ -499,8 +501,8 @@ int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t
             h_edge += 8 * edge_n[e];
         }
     }
-    if (GP && (rc = geom_enqueue(c, s, T.lines, d_lines, *GP)) != STR_ER_OK) return rc;
-    if (WP && (rc = words_enqueue(c, s, T.lines, d_lines, *WP)) != STR_ER_OK) return rc;
+    if (want.geom && (rc = geom_enqueue(c, s, T.lines, d_lines, S.geom)) != STR_ER_OK) return rc;
+    if (want.words && (rc = words_enqueue(c, s, T.lines, d_lines, S.words)) != STR_ER_OK) return rc;
     const auto launch_pairs = [&](FootHead *head, FootPair *out, uint32_t cap) { launch_foot_pairs(s, d_lines, (int)n_lines, d_list, feet, head, out, cap); };
     const auto launch_links = [&](FootHead *head, FootPair *out, uint32_t cap) {
         launch_foot_links(s, d_lines, (int)n_lines, reinterpret_cast<const FootRange *>(c->foot_tab.d() + o_rng), d_list, feet, head, out, cap);
@@ -546,12 +548,6 @@ void feet_from_stats(const std::vector<FootStat> &stat, std::vector<str_er_line_
     }
 }
 
-int find_root(std::vector<int32_t> &parent, int32_t t)
-{
-    while (parent[(size_t)t] != t) { parent[(size_t)t] = parent[(size_t)parent[(size_t)t]]; t = parent[(size_t)t]; }
-    return t;
-}
-
 static_assert(sizeof(FootPair) == sizeof(str_er_line_pair), "the device writes str_er_line_pair records");
 static_assert(sizeof(FootPair) == sizeof(str_er_line_link), "the device writes str_er_line_link records");
 
@@ -571,19 +567,13 @@ void foot_rows32(const uint64_t *words, const FootLine &L, const str_er_line_foo
     }
 }
 
-} // namespace
-
-int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
-                      str_er_result *r, bool links, bool geom, bool words, bool read)
+// The steps of frame_lines_phase.  The members of every line of r, each once, and where their masks start on the device (d_bits): this
+// call's mask words (d_mask_bits / word_off), or made here by the mask kernels and left on the device
+int gather_members(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
+                   const str_er_result *r, std::vector<uint32_t> &frame_of, std::vector<uint8_t> &pyr_of, std::vector<FootMember> &mem, const uint32_t *&d_bits)
 {
-    const auto t0 = std::chrono::steady_clock::now();
     const size_t n_frames = b.frame_wh.size() / 2, n_lines = r->texts.size();
-    for (size_t f = 0; f < n_frames; ++f)
-        if (b.frame_wh[2 * f] > 65535 || b.frame_wh[2 * f + 1] > 65535) return fail(c, STR_ER_ECAPACITY, "STR_ER_WANT_FRAME_LINES: a frame wider or taller than 65535 pixels");
-    // the members of every line, each once
-    std::vector<uint32_t> frame_of(n_lines);
-    std::vector<uint8_t>  pyr_of(n_lines);
-    std::vector<FootMember> mem;
+    frame_of.resize(n_lines); pyr_of.resize(n_lines);
     std::vector<uint32_t> who;             // candidate of every member
     std::vector<int32_t>  ers;
     for (size_t t = 0; t < n_lines; ++t) {
@@ -603,14 +593,13 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
             who.push_back((uint32_t)k);
         }
     }
-    const uint32_t *d_bits = d_mask_bits;
+    d_bits = d_mask_bits;
     if (d_mask_bits && word_off) {
         for (size_t i = 0; i < mem.size(); ++i) {
             mem[i].word_off = (*word_off)[who[i]];
             if (mem[i].word_off == UINT64_MAX) return fail(c, STR_ER_EHIP, "frame lines: a member without a mask (internal error)");
         }
     } else if (!mem.empty()) {
-        // the masks of the candidates that are members, made by the mask kernels and left on the device
         std::vector<uint32_t> uniq(who);
         std::sort(uniq.begin(), uniq.end());
         uniq.erase(std::unique(uniq.begin(), uniq.end()), uniq.end());
@@ -631,133 +620,182 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
         for (size_t i = 0; i < mem.size(); ++i)
             mem[i].word_off = off_of[(size_t)(std::lower_bound(uniq.begin(), uniq.end(), who[i]) - uniq.begin())];
     }
-    FootTables T;
-    foot_layout(b.frame_wh, frame_of, mem, T, links);
-    const double ms_layout = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    FootOut O;
-    LinkOut LK;
-    GeomPlan GP;
-    WordsPlan WP;
-    if (words)
-        if (const int rcw = words_check_boxes(c, T.lines, "STR_ER_WANT_LINE_WORDS: "); rcw != STR_ER_OK) return rcw;
-    const int rc = foot_stage(c, s, T, d_bits, true, O, links ? &LK : nullptr, geom ? &GP : nullptr, words ? &WP : nullptr);
-    if (rc != STR_ER_OK) return rc;
-    const auto t1 = std::chrono::steady_clock::now();
-    feet_from_stats(O.stat, r->line_feet);
-    if (geom)
-        for (const str_er_line_foot &F : r->line_feet)
-            if (F.w > GEOM_MAX_BOX || F.h > GEOM_MAX_BOX)
-                return fail(c, STR_ER_ECAPACITY, "STR_ER_WANT_LINE_GEOM: a foot box wider or taller than " + std::to_string(GEOM_MAX_BOX) + " pixels");
-    r->line_pairs.resize(O.pairs.size());
-    if (!O.pairs.empty()) std::memcpy(r->line_pairs.data(), O.pairs.data(), sizeof(FootPair) * O.pairs.size());
+    return STR_ER_OK;
+}
+
+// the pairs, the frame lines and their members from the feet and the stage's pairs; n_fl: the number of frame lines
+int fill_frame_lines(str_er_ctx *c, str_er_result *r, const std::vector<uint32_t> &frame_of, const std::vector<uint8_t> &pyr_of, const std::vector<FootPair> &pairs,
+                     int32_t &n_fl)
+{
+    const size_t n_lines = frame_of.size();
+    r->line_pairs.resize(pairs.size());
+    if (!pairs.empty()) std::memcpy(r->line_pairs.data(), pairs.data(), sizeof(FootPair) * pairs.size());
     r->frame_lines.resize(n_lines);
     r->frame_line_members.resize(n_lines);
-    int32_t n_fl = 0;
     const int rcf = str_er_frame_lines_from_pairs(r->line_feet.data(), frame_of.data(), pyr_of.data(), (int32_t)n_lines, r->line_pairs.data(),
                                                   (int32_t)r->line_pairs.size(), c->merge_num, c->merge_den, r->frame_lines.data(), (int32_t)n_lines, &n_fl,
                                                   r->frame_line_members.data());
     if (rcf != STR_ER_OK) return fail(c, STR_ER_EHIP, "frame lines: the device's pairs do not fit its footprints (internal error)");
     r->frame_lines.resize((size_t)n_fl);
     r->have_frame_lines = true;
-    if (links) {
-        r->line_links.resize(LK.links.size());
-        if (!LK.links.empty()) std::memcpy(r->line_links.data(), LK.links.data(), sizeof(FootPair) * LK.links.size());
-        r->line_tracks.resize(n_lines);
-        r->text_tracks.resize(n_lines);
-        r->text_track_members.resize(n_lines);
-        int32_t n_tr = 0;
-        const int rct = str_er_text_tracks_from_links(r->line_feet.data(), frame_of.data(), (int32_t)n_lines, r->line_pairs.data(), (int32_t)r->line_pairs.size(),
-                                                      r->line_links.data(), (int32_t)r->line_links.size(), c->link_num, c->link_den, r->line_tracks.data(),
-                                                      r->text_tracks.data(), (int32_t)n_lines, &n_tr, r->text_track_members.data());
-        if (rct != STR_ER_OK) return fail(c, STR_ER_EHIP, "line links: the device's links do not fit its footprints (internal error)");
-        r->text_tracks.resize((size_t)n_tr);
-        // the edge feet: the lines of the first and of the last frame, their feet and their footprints cut to the foot boxes
-        for (int e = 0; e < 2; ++e) {
-            str_er_result::EdgeFeet &E = r->edge_feet[e];
-            const uint32_t f = e == 0 ? 0u : (uint32_t)n_frames - 1u;
-            E = str_er_result::EdgeFeet{};
-            if (n_frames == 0) continue;
-            E.w = b.frame_wh[2 * f]; E.h = b.frame_wh[2 * f + 1];
-            for (size_t t = 0; t < n_lines; ++t) {
-                if (frame_of[t] != f) continue;
-                E.lines.push_back((int32_t)t);
-                E.feet.push_back(r->line_feet[t]);
-                if (r->line_feet[t].pixels) foot_rows32(LK.edge[e].data() + (T.lines[t].word_off - T.edge_lo[e]), T.lines[t], r->line_feet[t], E.bits);
-            }
+    return STR_ER_OK;
+}
+
+// the links, the tracks and the edge feet: the lines of the first and of the last frame, their feet and their footprints cut to the foot boxes
+int fill_links(str_er_ctx *c, const Batch &b, str_er_result *r, const std::vector<uint32_t> &frame_of, const FootTables &T, const LinkOut &LK)
+{
+    const size_t n_frames = b.frame_wh.size() / 2, n_lines = frame_of.size();
+    r->line_links.resize(LK.links.size());
+    if (!LK.links.empty()) std::memcpy(r->line_links.data(), LK.links.data(), sizeof(FootPair) * LK.links.size());
+    r->line_tracks.resize(n_lines);
+    r->text_tracks.resize(n_lines);
+    r->text_track_members.resize(n_lines);
+    int32_t n_tr = 0;
+    const int rct = str_er_text_tracks_from_links(r->line_feet.data(), frame_of.data(), (int32_t)n_lines, r->line_pairs.data(), (int32_t)r->line_pairs.size(),
+                                                  r->line_links.data(), (int32_t)r->line_links.size(), c->link_num, c->link_den, r->line_tracks.data(),
+                                                  r->text_tracks.data(), (int32_t)n_lines, &n_tr, r->text_track_members.data());
+    if (rct != STR_ER_OK) return fail(c, STR_ER_EHIP, "line links: the device's links do not fit its footprints (internal error)");
+    r->text_tracks.resize((size_t)n_tr);
+    for (int e = 0; e < 2; ++e) {
+        str_er_result::EdgeFeet &E = r->edge_feet[e];
+        const uint32_t f = e == 0 ? 0u : (uint32_t)n_frames - 1u;
+        E = str_er_result::EdgeFeet{};
+        if (n_frames == 0) continue;
+        E.w = b.frame_wh[2 * f]; E.h = b.frame_wh[2 * f + 1];
+        for (size_t t = 0; t < n_lines; ++t) {
+            if (frame_of[t] != f) continue;
+            E.lines.push_back((int32_t)t);
+            E.feet.push_back(r->line_feet[t]);
+            if (r->line_feet[t].pixels) foot_rows32(LK.edge[e].data() + (T.lines[t].word_off - T.edge_lo[e]), T.lines[t], r->line_feet[t], E.bits);
         }
-        r->have_line_links = true;
-        if (c->dbg_stats)        // developer aid (tools/dev_line_links.py)
-            std::fprintf(stderr, "[str_er] line links: %u candidate pairs, %zu overlaps, %d tracks, %zu bytes back for the link table, %zu bytes back for the edge feet\n",
-                         LK.n_candidates, LK.links.size(), n_tr, LK.bytes_back, LK.edge_bytes);
     }
-    if (geom) {
-        const auto t2 = std::chrono::steady_clock::now();
-        r->geom_points.clear();
-        if (T.members.empty()) r->line_geoms.assign(n_lines, str_er_line_geom{});        // (no footprint at all: nothing was launched)
-        else if (const int rcg = geom_collect(c, GP, r->line_geoms, r->geom_points); rcg != STR_ER_OK) return rcg;
-        if (T.members.empty())
-            for (str_er_line_geom &G : r->line_geoms) G.edge = -1;
-        // the frame lines: the hull of the union of the members' hull vertices, the moments of the representative
-        r->frame_line_geoms.assign(r->frame_lines.size(), str_er_line_geom{});
-        std::vector<int32_t> uni, hull;
-        for (size_t i = 0; i < r->frame_lines.size(); ++i) {
-            const str_er_frame_line &FL = r->frame_lines[i];
-            str_er_line_geom &G = r->frame_line_geoms[i];
-            G.edge = -1;
-            uni.clear();
-            for (int32_t k = FL.first; k < FL.first + FL.count; ++k) {
-                const str_er_line_geom &M = r->line_geoms[(size_t)r->frame_line_members[(size_t)k]];
-                uni.insert(uni.end(), r->geom_points.begin() + 2 * (size_t)M.first, r->geom_points.begin() + 2 * ((size_t)M.first + M.count));
-            }
-            if (FL.rep >= 0) {
-                const str_er_line_geom &M = r->line_geoms[(size_t)FL.rep];
-                G.pixels = M.pixels; G.m10 = M.m10; G.m01 = M.m01; G.m20 = M.m20; G.m11 = M.m11; G.m02 = M.m02;
-            }
-            if (uni.empty()) continue;
-            if (FL.count == 1) {            // (one member: its hull and its box)
-                const uint32_t first = (uint32_t)(r->geom_points.size() / 2);
-                G = r->line_geoms[(size_t)r->frame_line_members[(size_t)FL.first]];
-                G.first = first;
-                r->geom_points.insert(r->geom_points.end(), uni.begin(), uni.end());
-                continue;
-            }
-            hull.resize(uni.size());
-            int32_t nh = 0;
-            if (str_er_hull_of_points(uni.data(), (int32_t)(uni.size() / 2), hull.data(), (int32_t)(uni.size() / 2), &nh) != STR_ER_OK ||
-                str_er_quad_from_hull(hull.data(), nh, &G) != STR_ER_OK)
-                return fail(c, STR_ER_EHIP, "line geometry: the hull of a frame line failed (internal error)");
-            G.first = (uint32_t)(r->geom_points.size() / 2); G.count = (uint32_t)nh;
-            r->geom_points.insert(r->geom_points.end(), hull.begin(), hull.begin() + 2 * (size_t)nh);
-        }
-        r->have_line_geom = true;
-        if (c->dbg_stats)        // developer aid (tools/dev_line_geom.py)
-            std::fprintf(stderr, "[str_er] line geometry: %zu lines, %zu vertices reserved, %zu kept, %zu bytes back, host %.3f ms\n", n_lines, GP.n_pts,
-                         r->geom_points.size() / 2, GP.bytes - GP.o_rec, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
+    r->have_line_links = true;
+    if (c->dbg_stats)        // developer aid (tools/dev_line_links.py)
+        std::fprintf(stderr, "[str_er] line links: %u candidate pairs, %zu overlaps, %d tracks, %zu bytes back for the link table, %zu bytes back for the edge feet\n",
+                     LK.n_candidates, LK.links.size(), n_tr, LK.bytes_back, LK.edge_bytes);
+    return STR_ER_OK;
+}
+
+// the geometry of the lines (what k_foot_geom left) and of the frame lines (frame_line_geoms, lines_host.cpp)
+int fill_geometry(str_er_ctx *c, str_er_result *r, const GeomPass &GP)
+{
+    const auto   t2 = std::chrono::steady_clock::now();
+    const size_t n_lines = r->line_feet.size();
+    r->geom_points.clear();
+    if (const int rcg = geom_collect(c, GP, n_lines, r->line_geoms, r->geom_points); rcg != STR_ER_OK) return rcg;
+    if (frame_line_geoms(r->frame_lines.data(), r->frame_lines.size(), r->frame_line_members.data(), r->line_geoms.data(), r->geom_points, r->frame_line_geoms) !=
+        STR_ER_OK)
+        return fail(c, STR_ER_EHIP, "line geometry: the hull of a frame line failed (internal error)");
+    r->have_line_geom = true;
+    if (c->dbg_stats)        // developer aid (tools/dev_line_geom.py)
+        std::fprintf(stderr, "[str_er] line geometry: %zu lines, %zu vertices reserved, %zu kept, %zu bytes back, host %.3f ms\n", n_lines, GP.n_elems,
+                     r->geom_points.size() / 2, GP.bytes_back(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
+    return STR_ER_OK;
+}
+
+// the runs and words of the lines (what k_foot_words left), and with read the reading of every run: T.lines is the table k_foot_words
+// read, and its footprints are still in c->foot_bits
+int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read)
+{
+    const auto   t2 = std::chrono::steady_clock::now();
+    const size_t n_lines = r->line_feet.size();
+    if (const int rcw = words_collect(c, WP, n_lines, r->line_words, r->line_runs, r->words); rcw != STR_ER_OK) return rcw;
+    r->have_line_words = true;
+    if (read) {
+        std::vector<double> slopes(n_lines);
+        for (size_t t = 0; t < n_lines; ++t) slopes[t] = r->texts[t].slope;
+        if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features); rcr != STR_ER_OK)
+            return rcr;
+        r->have_run_reads = true;
     }
-    if (words) {
-        const auto t2 = std::chrono::steady_clock::now();
-        if (T.members.empty()) {          // (no footprint at all: nothing was launched)
-            r->line_words.assign(n_lines, str_er_line_words{});
-            r->line_runs.clear(); r->words.clear();
-        } else if (const int rcw = words_collect(c, WP, r->line_words, r->line_runs, r->words); rcw != STR_ER_OK) return rcw;
-        r->have_line_words = true;
-        if (read) {         // (T.lines is the table k_foot_words read; its footprints are still in c->foot_bits)
-            std::vector<double> slopes(n_lines);
-            for (size_t t = 0; t < n_lines; ++t) slopes[t] = r->texts[t].slope;
-            if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features); rcr != STR_ER_OK)
-                return rcr;
-            r->have_run_reads = true;
-        }
-        if (c->dbg_stats)        // developer aid (tools/dev_line_words.py)
-            std::fprintf(stderr, "[str_er] line words: %zu lines, %zu run slots reserved, %zu runs, %zu words, %zu bytes back, host %.3f ms\n", n_lines,
-                         WP.n_slots, r->line_runs.size(), r->words.size(), WP.bytes - WP.o_rec,
-                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
-    }
+    if (c->dbg_stats)        // developer aid (tools/dev_line_words.py)
+        std::fprintf(stderr, "[str_er] line words: %zu lines, %zu run slots reserved, %zu runs, %zu words, %zu bytes back, host %.3f ms\n", n_lines,
+                     WP.n_elems, r->line_runs.size(), r->words.size(), WP.bytes_back(),
+                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t2).count());
+    return STR_ER_OK;
+}
+
+} // namespace
+
+int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
+                      str_er_result *r, const LineStageWants &want)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t n_frames = b.frame_wh.size() / 2, n_lines = r->texts.size();
+    for (size_t f = 0; f < n_frames; ++f)
+        if (b.frame_wh[2 * f] > 65535 || b.frame_wh[2 * f + 1] > 65535) return fail(c, STR_ER_ECAPACITY, "STR_ER_WANT_FRAME_LINES: a frame wider or taller than 65535 pixels");
+    std::vector<uint32_t>   frame_of;
+    std::vector<uint8_t>    pyr_of;
+    std::vector<FootMember> mem;
+    const uint32_t         *d_bits = nullptr;
+    int rc = gather_members(c, s, b, qscale, d_mask_bits, word_off, r, frame_of, pyr_of, mem, d_bits);
+    if (rc != STR_ER_OK) return rc;
+    FootTables T;
+    foot_layout(b.frame_wh, frame_of, mem, T, want.links);
+    const double ms_layout = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    StageOut S(c);
+    if (want.words && (rc = words_check_boxes(c, T.lines, "STR_ER_WANT_LINE_WORDS: ")) != STR_ER_OK) return rc;
+    if ((rc = foot_stage(c, s, T, d_bits, true, want, S)) != STR_ER_OK) return rc;
+    const auto t1 = std::chrono::steady_clock::now();
+    feet_from_stats(S.feet.stat, r->line_feet);
+    if (want.geom)
+        for (const str_er_line_foot &F : r->line_feet)
+            if (F.w > GEOM_MAX_BOX || F.h > GEOM_MAX_BOX)
+                return fail(c, STR_ER_ECAPACITY, "STR_ER_WANT_LINE_GEOM: a foot box wider or taller than " + std::to_string(GEOM_MAX_BOX) + " pixels");
+    int32_t n_fl = 0;
+    if ((rc = fill_frame_lines(c, r, frame_of, pyr_of, S.feet.pairs, n_fl)) != STR_ER_OK) return rc;
+    if (want.links && (rc = fill_links(c, b, r, frame_of, T, S.links)) != STR_ER_OK) return rc;
+    if (want.geom && (rc = fill_geometry(c, r, S.geom)) != STR_ER_OK) return rc;
+    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read)) != STR_ER_OK) return rc;
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
                              "%zu bytes back, host %.3f ms before + %.3f ms after the device\n",
-                     n_lines, T.members.size(), T.jobs.size(), (unsigned long long)T.words, O.n_candidates, O.pairs.size(), n_fl, O.bytes_back, ms_layout,
+                     n_lines, T.members.size(), T.jobs.size(), (unsigned long long)T.words, S.feet.n_candidates, S.feet.pairs.size(), n_fl, S.feet.bytes_back, ms_layout,
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
+    return STR_ER_OK;
+}
+
+int feet_words_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_words *line_words,
+                    str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words, int32_t *n_words, bool read_runs,
+                    const double *slopes, str_er_run_read *reads, uint8_t *q_out)
+{
+    if (W < 1 || H < 1 || W > 65535 || H > 65535 || n < 0 || !n_runs || !n_words || (n > 0 && (!feet || !line_words)) || (runs && cap_runs < 0) ||
+        (words && cap_words < 0))
+        return fail(c, STR_ER_EINVAL, "bad arguments");
+    CallerFeet F(c);
+    int rc = F.check_boxes(W, H, feet, n, "");
+    if (rc != STR_ER_OK) return rc;
+    const bool reading = read_runs && runs && words;          // (a counting call reads nothing)
+    if (read_runs && reads && !(c->svm_loaded && c->svm.dim == 1800))
+        return fail(c, STR_ER_ESTATE, "str_er_feet_read needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)");
+    if (read_runs && slopes)
+        for (int32_t t = 0; t < n; ++t)
+            if (!std::isfinite(slopes[t])) return fail(c, STR_ER_EINVAL, "slope " + std::to_string(t) + " is not finite");
+    if ((rc = F.check_limit(feet, n, WORDS_MAX_BOX)) != STR_ER_OK || (rc = F.pack(feet, bits, n, true)) != STR_ER_OK) return rc;
+    WordsPass WP = words_pass(c);
+    if (!F.words.empty()) {
+        const size_t tab_need = sizeof(FootLine) * (size_t)n;
+        if ((rc = F.reserve(tab_need)) != STR_ER_OK || (rc = F.upload(tab_need)) != STR_ER_OK) return rc;
+        if ((rc = words_enqueue(c, c->stream, F.lines, F.d_lines(), WP)) != STR_ER_OK || (rc = F.wait()) != STR_ER_OK) return rc;
+    }
+    std::vector<str_er_line_words> lw;
+    std::vector<str_er_line_run>   rn;
+    std::vector<str_er_line_word>  wd;
+    if ((rc = words_collect(c, WP, (size_t)n, lw, rn, wd)) != STR_ER_OK) return rc;
+    *n_runs = (int32_t)rn.size(); *n_words = (int32_t)wd.size();
+    if (n > 0) std::memcpy(line_words, lw.data(), sizeof(str_er_line_words) * (size_t)n);
+    if (!runs || !words) return STR_ER_OK;
+    if ((rc = check_cap(c, rn.size(), cap_runs, "glyph runs, cap_runs")) != STR_ER_OK || (rc = check_cap(c, wd.size(), cap_words, "words, cap_words")) != STR_ER_OK)
+        return rc;
+    if (reading && !rn.empty()) {          // (the footprints are still in c->foot_bits, the lines as the kernel read them in F.lines)
+        std::vector<str_er_run_read> rd;
+        std::vector<uint8_t>         q;
+        if ((rc = run_read_stage(c, c->stream, F.lines, lw, rn, slopes, reads ? &rd : nullptr, q)) != STR_ER_OK) return rc;
+        if (reads) std::memcpy(reads, rd.data(), sizeof(str_er_run_read) * rd.size());
+        if (q_out) std::memcpy(q_out, q.data(), q.size());
+    }
+    if (!rn.empty()) std::memcpy(runs, rn.data(), sizeof(str_er_line_run) * rn.size());
+    if (!wd.empty()) std::memcpy(words, wd.data(), sizeof(str_er_line_word) * wd.size());
     return STR_ER_OK;
 }
 
@@ -772,65 +810,6 @@ int str_er_set_frame_merge(str_er_ctx *c, int32_t num, int32_t den)
     c->merge_num = num; c->merge_den = den;
     return STR_ER_OK;
 }
-
-int str_er_frame_lines_from_pairs(str_er_line_foot *feet, const uint32_t *frames_of_lines, const uint8_t *pyr_of_lines, int32_t n_lines,
-                                  str_er_line_pair *pairs, int32_t n_pairs, int32_t num, int32_t den, str_er_frame_line *frame_lines,
-                                  int32_t cap_frame_lines, int32_t *n_frame_lines, int32_t *members)
-try {
-    if (n_lines < 0 || n_pairs < 0 || !n_frame_lines || num < 1 || num > den || den > 65535) return STR_ER_EINVAL;
-    if (n_lines > 0 && (!feet || !frames_of_lines || !pyr_of_lines)) return STR_ER_EINVAL;
-    if ((n_pairs > 0 && !pairs) || (frame_lines && n_lines > 0 && !members) || (frame_lines && cap_frame_lines < 0)) return STR_ER_EINVAL;
-    for (int32_t k = 0; k < n_pairs; ++k) {
-        const str_er_line_pair &P = pairs[k];
-        if (P.a < 0 || P.a >= P.b || P.b >= n_lines || frames_of_lines[P.a] != frames_of_lines[P.b]) return STR_ER_EINVAL;
-        if (P.inter == 0 || P.inter > feet[P.a].pixels || P.inter > feet[P.b].pixels) return STR_ER_EINVAL;
-    }
-    // the duplicates joined: the root of a component is its smallest line
-    std::vector<int32_t> parent((size_t)n_lines);
-    std::iota(parent.begin(), parent.end(), 0);
-    for (int32_t k = 0; k < n_pairs; ++k) {
-        str_er_line_pair &P = pairs[k];
-        const uint64_t uni = (uint64_t)feet[P.a].pixels + (uint64_t)feet[P.b].pixels - (uint64_t)P.inter;
-        P.dup = (uint64_t)P.inter * (uint64_t)den >= (uint64_t)num * uni ? 1u : 0u;
-        if (!P.dup) continue;
-        const int32_t ra = find_root(parent, P.a), rb = find_root(parent, P.b);
-        if (ra != rb) parent[(size_t)std::max(ra, rb)] = std::min(ra, rb);
-    }
-    // the frame lines: by frame, then by smallest member
-    std::vector<int32_t> roots;
-    for (int32_t t = 0; t < n_lines; ++t)
-        if (find_root(parent, t) == t) roots.push_back(t);
-    std::sort(roots.begin(), roots.end(), [&](int32_t p, int32_t q) { return frames_of_lines[p] != frames_of_lines[q] ? frames_of_lines[p] < frames_of_lines[q] : p < q; });
-    std::vector<int32_t> index_of((size_t)n_lines, -1);
-    for (size_t i = 0; i < roots.size(); ++i) index_of[(size_t)roots[i]] = (int32_t)i;
-    for (int32_t t = 0; t < n_lines; ++t) feet[t].frame_line = index_of[(size_t)find_root(parent, t)];
-    *n_frame_lines = (int32_t)roots.size();
-    if (!frame_lines) return STR_ER_OK;
-    if ((int32_t)roots.size() > cap_frame_lines) return STR_ER_ECAPACITY;
-    for (size_t i = 0; i < roots.size(); ++i) {
-        str_er_frame_line &G = frame_lines[i];
-        G = str_er_frame_line{};
-        G.frame = frames_of_lines[roots[i]]; G.rep = -1;
-    }
-    for (int32_t t = 0; t < n_lines; ++t) ++frame_lines[feet[t].frame_line].count;
-    int32_t at = 0;
-    for (size_t i = 0; i < roots.size(); ++i) { frame_lines[i].first = at; at += frame_lines[i].count; frame_lines[i].count = 0; }
-    for (int32_t t = 0; t < n_lines; ++t) {          // (ascending t: the members ascend, and a tie of pixels stays with the smaller line)
-        str_er_frame_line      &G = frame_lines[feet[t].frame_line];
-        const str_er_line_foot &F = feet[t];
-        members[G.first + G.count++] = t;
-        if (G.rep < 0 || F.pixels > G.pixels) { G.rep = t; G.pixels = F.pixels; }
-        if (pyr_of_lines[t] < 32) G.levels |= 1u << pyr_of_lines[t];
-        if (F.w > 0 && F.h > 0) {
-            if (G.w == 0) { G.x = F.x; G.y = F.y; G.w = F.w; G.h = F.h; }
-            else {
-                const int32_t x1 = std::max(G.x + G.w, F.x + F.w), y1 = std::max(G.y + G.h, F.y + F.h);
-                G.x = std::min(G.x, F.x); G.y = std::min(G.y, F.y); G.w = x1 - G.x; G.h = y1 - G.y;
-            }
-        }
-    }
-    return STR_ER_OK;
-} catch (...) { return STR_ER_ENOMEM; }
 
 int str_er_line_feet_regions(str_er_ctx *c, const uint8_t *plane, int32_t w, int32_t h, int64_t stride, const str_er_cand *regions,
                              const int32_t *line_of, int32_t n, int32_t n_lines, int32_t out_w, int32_t out_h, str_er_line_foot *feet,
@@ -870,8 +849,9 @@ try {
     const std::vector<uint8_t>  pyr_of((size_t)n_lines, 0);
     FootTables T;
     foot_layout(frame_wh, frame_of, mem, T);
-    FootOut O;
-    if ((rc = foot_stage(c, c->stream, T, d_bits, false, O)) != STR_ER_OK) return rc;
+    StageOut S(c);
+    if ((rc = foot_stage(c, c->stream, T, d_bits, false, LineStageWants{}, S)) != STR_ER_OK) return rc;
+    const FootOut &O = S.feet;
     std::vector<str_er_line_foot> ft;
     feet_from_stats(O.stat, ft);
     std::vector<str_er_line_pair> pr(O.pairs.size());
@@ -887,9 +867,7 @@ try {
     if (n_lines > 0) std::memcpy(feet, ft.data(), sizeof(str_er_line_foot) * (size_t)n_lines);
     if (bits && out_words > cap_words)
         return fail(c, STR_ER_ECAPACITY, "the footprints need " + std::to_string(out_words) + " words, cap_words is " + std::to_string(cap_words));
-    if (pairs && (int64_t)pr.size() > (int64_t)cap_pairs)
-        return fail(c, STR_ER_ECAPACITY, std::to_string(pr.size()) + " pairs, cap_pairs is " + std::to_string(cap_pairs));
-    if (pairs && !pr.empty()) std::memcpy(pairs, pr.data(), sizeof(str_er_line_pair) * pr.size());
+    if ((rc = copy_out(c, pr.data(), pr.size(), sizeof(str_er_line_pair), pairs, cap_pairs, "pairs, cap_pairs")) != STR_ER_OK) return rc;
     if (bits && out_words) {
         // the footprints back as they lie on the device (64-bit words over the union of the pre-image boxes), cut to the foot boxes
         std::vector<uint64_t> dev((size_t)T.words);
@@ -910,229 +888,49 @@ int str_er_set_line_link(str_er_ctx *c, int32_t num, int32_t den)
     return STR_ER_OK;
 }
 
-int str_er_text_tracks_from_links(const str_er_line_foot *feet, const uint32_t *frames_of_lines, int32_t n_lines, const str_er_line_pair *pairs,
-                                  int32_t n_pairs, str_er_line_link *links, int32_t n_links, int32_t num, int32_t den, int32_t *line_tracks,
-                                  str_er_text_track *tracks, int32_t cap_tracks, int32_t *n_tracks, int32_t *members)
-try {
-    if (n_lines < 0 || n_pairs < 0 || n_links < 0 || !n_tracks || num < 1 || num > den || den > 65535) return STR_ER_EINVAL;
-    if (n_lines > 0 && (!feet || !frames_of_lines || !line_tracks)) return STR_ER_EINVAL;
-    if ((n_pairs > 0 && !pairs) || (n_links > 0 && !links) || (tracks && n_lines > 0 && !members) || (tracks && cap_tracks < 0)) return STR_ER_EINVAL;
-    for (int32_t k = 0; k < n_pairs; ++k) {
-        const str_er_line_pair &P = pairs[k];
-        if (P.a < 0 || P.a >= P.b || P.b >= n_lines || frames_of_lines[P.a] != frames_of_lines[P.b]) return STR_ER_EINVAL;
-        if (P.inter == 0 || P.inter > feet[P.a].pixels || P.inter > feet[P.b].pixels) return STR_ER_EINVAL;
-    }
-    for (int32_t k = 0; k < n_links; ++k) {
-        const str_er_line_link &P = links[k];
-        if (P.a < 0 || P.a >= n_lines || P.b < 0 || P.b >= n_lines) return STR_ER_EINVAL;
-        if ((uint64_t)frames_of_lines[P.b] != (uint64_t)frames_of_lines[P.a] + 1u) return STR_ER_EINVAL;
-        if (P.inter == 0 || P.inter > feet[P.a].pixels || P.inter > feet[P.b].pixels) return STR_ER_EINVAL;
-    }
-    // duplicates and links joined: the root of a component is its smallest line
-    std::vector<int32_t> parent((size_t)n_lines);
-    std::iota(parent.begin(), parent.end(), 0);
-    auto join = [&](int32_t a, int32_t b) {
-        const int32_t ra = find_root(parent, a), rb = find_root(parent, b);
-        if (ra != rb) parent[(size_t)std::max(ra, rb)] = std::min(ra, rb);
-    };
-    for (int32_t k = 0; k < n_pairs; ++k)
-        if (pairs[k].dup) join(pairs[k].a, pairs[k].b);
-    for (int32_t k = 0; k < n_links; ++k) {
-        str_er_line_link &P = links[k];
-        const uint64_t uni = (uint64_t)feet[P.a].pixels + (uint64_t)feet[P.b].pixels - (uint64_t)P.inter;
-        P.link = (uint64_t)P.inter * (uint64_t)den >= (uint64_t)num * uni ? 1u : 0u;
-        if (P.link) join(P.a, P.b);
-    }
-    // the tracks: by first frame, then by smallest member
-    std::vector<uint32_t> f0((size_t)n_lines, UINT32_MAX), f1((size_t)n_lines, 0);
-    for (int32_t t = 0; t < n_lines; ++t) {
-        const size_t q = (size_t)find_root(parent, t);
-        f0[q] = std::min(f0[q], frames_of_lines[t]); f1[q] = std::max(f1[q], frames_of_lines[t]);
-    }
-    std::vector<int32_t> roots;
-    for (int32_t t = 0; t < n_lines; ++t)
-        if (find_root(parent, t) == t) roots.push_back(t);
-    std::sort(roots.begin(), roots.end(), [&](int32_t p, int32_t q) { return f0[(size_t)p] != f0[(size_t)q] ? f0[(size_t)p] < f0[(size_t)q] : p < q; });
-    std::vector<int32_t> index_of((size_t)n_lines, -1);
-    for (size_t i = 0; i < roots.size(); ++i) index_of[(size_t)roots[i]] = (int32_t)i;
-    for (int32_t t = 0; t < n_lines; ++t) line_tracks[t] = index_of[(size_t)find_root(parent, t)];
-    *n_tracks = (int32_t)roots.size();
-    if (!tracks) return STR_ER_OK;
-    if ((int32_t)roots.size() > cap_tracks) return STR_ER_ECAPACITY;
-    for (size_t i = 0; i < roots.size(); ++i) {
-        str_er_text_track &G = tracks[i];
-        G = str_er_text_track{};
-        G.first_frame = f0[(size_t)roots[i]]; G.last_frame = f1[(size_t)roots[i]]; G.rep = -1;
-    }
-    for (int32_t t = 0; t < n_lines; ++t) ++tracks[line_tracks[t]].count;
-    int32_t at = 0;
-    for (size_t i = 0; i < roots.size(); ++i) { tracks[i].first = at; at += tracks[i].count; tracks[i].count = 0; }
-    for (int32_t t = 0; t < n_lines; ++t) {          // (ascending t: the members ascend, and a tie of pixels stays with the smaller line)
-        str_er_text_track &G = tracks[line_tracks[t]];
-        members[G.first + G.count++] = t;
-        if (G.rep < 0 || feet[t].pixels > G.pixels) { G.rep = t; G.pixels = feet[t].pixels; }
-    }
-    return STR_ER_OK;
-} catch (...) { return STR_ER_ENOMEM; }
-
 int str_er_link_feet(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet_a, const uint32_t *bits_a, int32_t n_a,
                      const str_er_line_foot *feet_b, const uint32_t *bits_b, int32_t n_b, str_er_line_link *pairs, int32_t cap_pairs, int32_t *n_pairs)
 try {
     if (!c) return STR_ER_EINVAL;
     if (W < 1 || H < 1 || W > 65535 || H > 65535 || n_a < 0 || n_b < 0 || !n_pairs || (n_a > 0 && !feet_a) || (n_b > 0 && !feet_b) || (pairs && cap_pairs < 0))
         return fail(c, STR_ER_EINVAL, "bad arguments");
-    // the two sets as one table of lines, a's first, their footprints as rows of 64-bit words; every footprint checked against its foot
+    // the two sets as one table of lines, a's first
     const size_t n_lines = (size_t)n_a + (size_t)n_b;
-    std::vector<FootLine> lines;
-    std::vector<uint64_t> words;
-    int rc = check_foot_boxes(c, W, H, feet_a, n_a, "set a, ");
-    if (rc != STR_ER_OK || (rc = check_foot_boxes(c, W, H, feet_b, n_b, "set b, ")) != STR_ER_OK) return rc;
-    if ((rc = pack_footprints(c, feet_a, bits_a, n_a, lines, words)) != STR_ER_OK || (rc = pack_footprints(c, feet_b, bits_b, n_b, lines, words)) != STR_ER_OK) return rc;
+    CallerFeet F(c);
+    int rc = F.check_boxes(W, H, feet_a, n_a, "set a, ");
+    if (rc != STR_ER_OK || (rc = F.check_boxes(W, H, feet_b, n_b, "set b, ")) != STR_ER_OK) return rc;
+    if ((rc = F.pack(feet_a, bits_a, n_a, false)) != STR_ER_OK || (rc = F.pack(feet_b, bits_b, n_b, false)) != STR_ER_OK) return rc;
     *n_pairs = 0;
-    if (n_a == 0 || n_b == 0 || words.empty()) return STR_ER_OK;
-    HIP_TRY(c, hipSetDevice(c->prm.device));
+    if (n_a == 0 || n_b == 0 || F.words.empty()) return STR_ER_OK;
     std::vector<FootRange> range(n_lines, FootRange{0, 0});
     std::vector<uint32_t>  list((size_t)n_b);
     for (int32_t i = 0; i < n_a; ++i) range[(size_t)i] = FootRange{0, (uint32_t)n_b};
     std::iota(list.begin(), list.end(), (uint32_t)n_a);
     const size_t o_list = align_up(sizeof(FootLine) * n_lines, 256), o_rng = align_up(o_list + 4 * list.size(), 256), tab_need = o_rng + sizeof(FootRange) * n_lines;
     PairTable LT = link_table(c);
-    if ((rc = c->foot_tab.ensure(c, tab_need, "frame line tables")) != STR_ER_OK || (rc = c->foot_bits.ensure(c, 8 * words.size(), "line footprints")) != STR_ER_OK ||
-        (rc = LT.reserve(c, n_lines)) != STR_ER_OK)
-        return rc;
-    hipStream_t s = c->stream;
-    std::memcpy(c->foot_tab.h(), lines.data(), sizeof(FootLine) * n_lines);
+    if ((rc = F.reserve(tab_need)) != STR_ER_OK || (rc = LT.reserve(c, n_lines)) != STR_ER_OK) return rc;
     std::memcpy(c->foot_tab.h() + o_list, list.data(), 4 * list.size());
     std::memcpy(c->foot_tab.h() + o_rng, range.data(), sizeof(FootRange) * n_lines);
-    HIP_TRY(c, hipMemcpyAsync(c->foot_tab.d(), c->foot_tab.h(), tab_need, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(c->foot_bits.d<uint64_t>(), words.data(), 8 * words.size(), hipMemcpyHostToDevice, s));      // (words lives until the wait below)
+    if ((rc = F.upload(tab_need)) != STR_ER_OK) return rc;
+    hipStream_t s = c->stream;
     const auto launch = [&](FootHead *head, FootPair *out, uint32_t cap) {
-        launch_foot_links(s, reinterpret_cast<const FootLine *>(c->foot_tab.d()), (int)n_lines, reinterpret_cast<const FootRange *>(c->foot_tab.d() + o_rng),
+        launch_foot_links(s, F.d_lines(), (int)n_lines, reinterpret_cast<const FootRange *>(c->foot_tab.d() + o_rng),
                           reinterpret_cast<const uint32_t *>(c->foot_tab.d() + o_list), c->foot_bits.d<uint64_t>(), head, out, cap);
     };
     std::vector<FootPair> got;
     for (bool again = true; again;) {
-        if ((rc = LT.enqueue(c, s, launch)) != STR_ER_OK) return rc;
-        HIP_TRY(c, wait_stream(c, s));
+        if ((rc = LT.enqueue(c, s, launch)) != STR_ER_OK || (rc = F.wait()) != STR_ER_OK) return rc;
         if ((rc = LT.collect(c, got, again)) != STR_ER_OK) return rc;
     }
     sort_pairs(got);
     *n_pairs = (int32_t)got.size();
-    if (pairs && (int64_t)got.size() > (int64_t)cap_pairs)
-        return fail(c, STR_ER_ECAPACITY, std::to_string(got.size()) + " pairs, cap_pairs is " + std::to_string(cap_pairs));
-    if (!pairs) return STR_ER_OK;
-    for (size_t k = 0; k < got.size(); ++k) {
-        str_er_line_link &P = pairs[k];
-        P.a = got[k].a; P.b = got[k].b - n_a; P.inter = got[k].inter;
-        const uint64_t uni = (uint64_t)feet_a[P.a].pixels + (uint64_t)feet_b[P.b].pixels - (uint64_t)P.inter;
-        P.link = (uint64_t)P.inter * (uint64_t)c->link_den >= (uint64_t)c->link_num * uni ? 1u : 0u;
-    }
-    return STR_ER_OK;
+    if (pairs)          // the records as the caller's (str_er_line_link): b within its set, and the link
+        for (FootPair &P : got) {
+            P.b -= n_a;
+            P.dup = overlap_passes(P.inter, feet_a[P.a].pixels, feet_b[P.b].pixels, c->link_num, c->link_den) ? 1u : 0u;
+        }
+    return copy_out(c, got.data(), got.size(), sizeof(FootPair), pairs, cap_pairs, "pairs, cap_pairs");
 } ABI_GUARD(c)
-
-namespace {
-
-using i128 = __int128;
-
-// > 0: o -> a -> b turns clockwise on screen (x to the right, y down)
-inline i128 turn(const int32_t *o, const int32_t *a, const int32_t *b)
-{
-    return (i128)((int64_t)a[0] - o[0]) * ((int64_t)b[1] - o[1]) - (i128)((int64_t)a[1] - o[1]) * ((int64_t)b[0] - o[0]);
-}
-
-} // namespace
-
-int str_er_hull_of_points(const int32_t *xy, int32_t n, int32_t *out_xy, int32_t cap, int32_t *n_out)
-try {
-    if (n < 0 || !n_out || (n > 0 && !xy) || (out_xy && cap < 0)) return STR_ER_EINVAL;
-    // Andrew's monotone chain over the points sorted by (y, x): down the right side, then up the left side, every turn strictly clockwise
-    std::vector<std::array<int32_t, 2>> p((size_t)n);
-    for (int32_t i = 0; i < n; ++i) p[(size_t)i] = {xy[2 * i], xy[2 * i + 1]};
-    std::sort(p.begin(), p.end(), [](const std::array<int32_t, 2> &a, const std::array<int32_t, 2> &b) { return a[1] != b[1] ? a[1] < b[1] : a[0] < b[0]; });
-    p.erase(std::unique(p.begin(), p.end()), p.end());
-    std::vector<std::array<int32_t, 2>> st;
-    if (p.size() <= 2) st = p;
-    else {
-        st.reserve(2 * p.size());
-        for (size_t i = 0; i < p.size(); ++i) {
-            while (st.size() >= 2 && turn(st[st.size() - 2].data(), st.back().data(), p[i].data()) <= 0) st.pop_back();
-            st.push_back(p[i]);
-        }
-        const size_t low = st.size() + 1;
-        for (size_t i = p.size() - 1; i-- > 0;) {
-            while (st.size() >= low && turn(st[st.size() - 2].data(), st.back().data(), p[i].data()) <= 0) st.pop_back();
-            st.push_back(p[i]);
-        }
-        st.pop_back();
-    }
-    *n_out = (int32_t)st.size();
-    if (!out_xy) return STR_ER_OK;
-    if ((int32_t)st.size() > cap) return STR_ER_ECAPACITY;
-    for (size_t i = 0; i < st.size(); ++i) { out_xy[2 * i] = st[i][0]; out_xy[2 * i + 1] = st[i][1]; }
-    return STR_ER_OK;
-} catch (...) { return STR_ER_ENOMEM; }
-
-int str_er_quad_from_hull(const int32_t *xy, int32_t n, str_er_line_geom *out)
-try {
-    if (!xy || !out || n < 3) return STR_ER_EINVAL;
-    for (int32_t i = 0; i < 2 * n; ++i)
-        if (xy[i] < 0 || xy[i] > 65535) return STR_ER_EINVAL;
-    // a hull in the stated order: it starts at the smallest (y, x), every turn is strictly clockwise, and it goes round once (y falls
-    // only after it has risen, and then never rises again)
-    int32_t flips = 0;
-    int     first_sign = 0, last_sign = 0;         // of the y steps that are not level
-    for (int32_t i = 0; i < n; ++i) {
-        const int32_t *p = xy + 2 * (size_t)i, *q = xy + 2 * (size_t)((i + 1) % n), *w = xy + 2 * (size_t)((i + 2) % n);
-        if (i > 0 && (p[1] < xy[1] || (p[1] == xy[1] && p[0] <= xy[0]))) return STR_ER_EINVAL;
-        if (turn(p, q, w) <= 0) return STR_ER_EINVAL;
-        const int sg = (q[1] > p[1]) - (q[1] < p[1]);
-        if (sg == 0) continue;
-        if (last_sign != 0 && sg != last_sign) ++flips;
-        if (first_sign == 0) first_sign = sg;
-        last_sign = sg;
-    }
-    if (flips + (first_sign != last_sign ? 1 : 0) != 2) return STR_ER_EINVAL;
-    const auto V = [&](int32_t k) { return xy + 2 * (size_t)(k % n); };
-    i128 area2 = 0;
-    for (int32_t i = 0; i < n; ++i) area2 += (i128)V(i)[0] * V(i + 1)[1] - (i128)V(i + 1)[0] * V(i)[1];
-    // rotating calipers: for the edge i the vertices with the largest d, the largest c and the smallest d only move forward as i does
-    // (c is smallest on the edge itself: the hull lies on the side of its normal); every value is exact in 64 bits
-    int32_t pd = 0, pc = 0, pm = 0;         // (positions, taken modulo n)
-    int32_t best = -1;
-    int64_t b_ex = 0, b_ey = 0, b_d0 = 0, b_d1 = 0, b_c0 = 0, b_c1 = 0;
-    i128    b_num = 0;
-    int64_t b_den = 1;
-    for (int32_t i = 0; i < n; ++i) {
-        const int64_t ex = (int64_t)V(i + 1)[0] - V(i)[0], ey = (int64_t)V(i + 1)[1] - V(i)[1];
-        const auto d = [&](int32_t k) { return V(k)[0] * ex + V(k)[1] * ey; };
-        const auto cc = [&](int32_t k) { return -V(k)[0] * ey + V(k)[1] * ex; };
-        if (i == 0) {
-            for (int32_t k = 1; k < n; ++k) {
-                if (d(k) > d(pd)) pd = k;
-                if (cc(k) > cc(pc)) pc = k;
-                if (d(k) < d(pm)) pm = k;
-            }
-        } else {
-            for (int32_t g = 0; g < n && d(pd + 1) > d(pd); ++g) pd = (pd + 1) % n;
-            for (int32_t g = 0; g < n && cc(pc + 1) > cc(pc); ++g) pc = (pc + 1) % n;
-            for (int32_t g = 0; g < n && d(pm + 1) < d(pm); ++g) pm = (pm + 1) % n;
-        }
-        const int64_t d0 = d(pm), d1 = d(pd), c0 = cc(i), c1 = cc(pc), den = ex * ex + ey * ey;
-        const i128    num = (i128)(d1 - d0) * (c1 - c0);
-        if (best < 0 || num * b_den < b_num * den) {
-            best = i; b_ex = ex; b_ey = ey; b_d0 = d0; b_d1 = d1; b_c0 = c0; b_c1 = c1; b_num = num; b_den = den;
-        }
-    }
-    out->hull_area2 = (uint64_t)area2;
-    out->edge = best; out->ex = (int32_t)b_ex; out->ey = (int32_t)b_ey;
-    out->dmin = b_d0; out->dmax = b_d1; out->cmin = b_c0; out->cmax = b_c1;
-    const int64_t dd[4] = {b_d0, b_d1, b_d1, b_d0}, cs[4] = {b_c0, b_c0, b_c1, b_c1};
-    for (int k = 0; k < 4; ++k) {
-        out->qx[k] = (double)(dd[k] * b_ex - cs[k] * b_ey) / (double)b_den;
-        out->qy[k] = (double)(dd[k] * b_ey + cs[k] * b_ex) / (double)b_den;
-    }
-    return STR_ER_OK;
-} catch (...) { return STR_ER_ENOMEM; }
 
 int str_er_feet_geom(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_geom *geoms, int32_t *xy,
                      int32_t cap_points, int32_t *n_points)
@@ -1140,43 +938,21 @@ try {
     if (!c) return STR_ER_EINVAL;
     if (W < 1 || H < 1 || W > 65535 || H > 65535 || n < 0 || !n_points || (n > 0 && (!feet || !geoms)) || (xy && cap_points < 0))
         return fail(c, STR_ER_EINVAL, "bad arguments");
-    // the footprints as a table of lines and rows of 64-bit words, every one checked against its foot
-    std::vector<FootLine> lines;
-    std::vector<uint64_t> words;
-    int rc = check_foot_boxes(c, W, H, feet, n, "");
-    if (rc != STR_ER_OK) return rc;
-    for (int32_t t = 0; t < n; ++t)
-        if (feet[t].w > GEOM_MAX_BOX || feet[t].h > GEOM_MAX_BOX)
-            return fail(c, STR_ER_ECAPACITY, "line " + std::to_string(t) + ": a foot box wider or taller than " + std::to_string(GEOM_MAX_BOX) + " pixels");
-    if ((rc = pack_footprints(c, feet, bits, n, lines, words)) != STR_ER_OK) return rc;
-    for (int32_t t = 0; t < n; ++t)
-        if (feet[t].pixels == 0) lines[(size_t)t] = FootLine{};          // (a box without a bit: an empty footprint)
-    std::vector<str_er_line_geom> out((size_t)n, str_er_line_geom{});
-    for (str_er_line_geom &G : out) G.edge = -1;
-    std::vector<int32_t> pts;
-    if (!words.empty()) {
-        HIP_TRY(c, hipSetDevice(c->prm.device));
-        if ((rc = c->foot_tab.ensure(c, sizeof(FootLine) * (size_t)n, "frame line tables")) != STR_ER_OK ||
-            (rc = c->foot_bits.ensure(c, 8 * words.size(), "line footprints")) != STR_ER_OK)
-            return rc;
-        hipStream_t s = c->stream;
-        std::memcpy(c->foot_tab.h(), lines.data(), sizeof(FootLine) * (size_t)n);
-        HIP_TRY(c, hipMemcpyAsync(c->foot_tab.d(), c->foot_tab.h(), sizeof(FootLine) * (size_t)n, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(c->foot_bits.d<uint64_t>(), words.data(), 8 * words.size(), hipMemcpyHostToDevice, s));      // (words must outlive the copy: every path below waits)
-        GeomPlan GP;
-        if ((rc = geom_enqueue(c, s, lines, reinterpret_cast<const FootLine *>(c->foot_tab.d()), GP)) != STR_ER_OK) {
-            (void)hipStreamSynchronize(s);          // (the upload of words may still be queued)
-            return rc;
-        }
-        HIP_TRY(c, wait_stream(c, s));
-        if ((rc = geom_collect(c, GP, out, pts)) != STR_ER_OK) return rc;
+    CallerFeet F(c);
+    int rc = F.check_boxes(W, H, feet, n, "");
+    if (rc != STR_ER_OK || (rc = F.check_limit(feet, n, GEOM_MAX_BOX)) != STR_ER_OK || (rc = F.pack(feet, bits, n, true)) != STR_ER_OK) return rc;
+    GeomPass GP = geom_pass(c);
+    if (!F.words.empty()) {
+        const size_t tab_need = sizeof(FootLine) * (size_t)n;
+        if ((rc = F.reserve(tab_need)) != STR_ER_OK || (rc = F.upload(tab_need)) != STR_ER_OK) return rc;
+        if ((rc = geom_enqueue(c, c->stream, F.lines, F.d_lines(), GP)) != STR_ER_OK || (rc = F.wait()) != STR_ER_OK) return rc;
     }
+    std::vector<str_er_line_geom> out;
+    std::vector<int32_t>          pts;
+    if ((rc = geom_collect(c, GP, (size_t)n, out, pts)) != STR_ER_OK) return rc;
     *n_points = (int32_t)(pts.size() / 2);
     if (n > 0) std::memcpy(geoms, out.data(), sizeof(str_er_line_geom) * (size_t)n);
-    if (xy && (int64_t)(pts.size() / 2) > (int64_t)cap_points)
-        return fail(c, STR_ER_ECAPACITY, std::to_string(pts.size() / 2) + " hull vertices, cap_points is " + std::to_string(cap_points));
-    if (xy && !pts.empty()) std::memcpy(xy, pts.data(), 4 * pts.size());
-    return STR_ER_OK;
+    return copy_out(c, pts.data(), pts.size() / 2, 8, xy, cap_points, "hull vertices, cap_points");
 } ABI_GUARD(c)
 
 int str_er_set_word_gap(str_er_ctx *c, int32_t num, int32_t den)
@@ -1187,90 +963,12 @@ int str_er_set_word_gap(str_er_ctx *c, int32_t num, int32_t den)
     return STR_ER_OK;
 }
 
-// str_er_feet_words, and with read_runs str_er_feet_read on top of it (slopes, reads, q_out: its arguments)
-static int feet_words_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_words *line_words,
-                           str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words, int32_t *n_words,
-                           bool read_runs, const double *slopes, str_er_run_read *reads, uint8_t *q_out)
-{
-    if (W < 1 || H < 1 || W > 65535 || H > 65535 || n < 0 || !n_runs || !n_words || (n > 0 && (!feet || !line_words)) || (runs && cap_runs < 0) ||
-        (words && cap_words < 0))
-        return fail(c, STR_ER_EINVAL, "bad arguments");
-    // the footprints as a table of lines and rows of 64-bit words, every one checked against its foot
-    std::vector<FootLine> lines;
-    std::vector<uint64_t> bitwords;
-    int rc = check_foot_boxes(c, W, H, feet, n, "");
-    if (rc != STR_ER_OK) return rc;
-    const bool reading = read_runs && runs && words;          // (a counting call reads nothing)
-    if (read_runs && reads && !(c->svm_loaded && c->svm.dim == 1800))
-        return fail(c, STR_ER_ESTATE, "str_er_feet_read needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)");
-    if (read_runs && slopes)
-        for (int32_t t = 0; t < n; ++t)
-            if (!std::isfinite(slopes[t])) return fail(c, STR_ER_EINVAL, "slope " + std::to_string(t) + " is not finite");
-    for (int32_t t = 0; t < n; ++t)
-        if (feet[t].w > WORDS_MAX_BOX || feet[t].h > WORDS_MAX_BOX)
-            return fail(c, STR_ER_ECAPACITY, "line " + std::to_string(t) + ": a foot box wider or taller than " + std::to_string(WORDS_MAX_BOX) + " pixels");
-    if ((rc = pack_footprints(c, feet, bits, n, lines, bitwords)) != STR_ER_OK) return rc;
-    for (int32_t t = 0; t < n; ++t)
-        if (feet[t].pixels == 0) lines[(size_t)t] = FootLine{};          // (a box without a bit: an empty footprint)
-    std::vector<str_er_line_words> lw((size_t)n, str_er_line_words{});
-    std::vector<str_er_line_run>   rn;
-    std::vector<str_er_line_word>  wd;
-    if (!bitwords.empty()) {
-        HIP_TRY(c, hipSetDevice(c->prm.device));
-        if ((rc = c->foot_tab.ensure(c, sizeof(FootLine) * (size_t)n, "frame line tables")) != STR_ER_OK ||
-            (rc = c->foot_bits.ensure(c, 8 * bitwords.size(), "line footprints")) != STR_ER_OK)
-            return rc;
-        hipStream_t s = c->stream;
-        std::memcpy(c->foot_tab.h(), lines.data(), sizeof(FootLine) * (size_t)n);
-        HIP_TRY(c, hipMemcpyAsync(c->foot_tab.d(), c->foot_tab.h(), sizeof(FootLine) * (size_t)n, hipMemcpyHostToDevice, s));
-        HIP_TRY(c, hipMemcpyAsync(c->foot_bits.d<uint64_t>(), bitwords.data(), 8 * bitwords.size(), hipMemcpyHostToDevice, s));      // (bitwords must outlive the copy: every path below waits)
-        WordsPlan WP;
-        if ((rc = words_enqueue(c, s, lines, reinterpret_cast<const FootLine *>(c->foot_tab.d()), WP)) != STR_ER_OK) {
-            (void)hipStreamSynchronize(s);          // (the upload of bitwords may still be queued)
-            return rc;
-        }
-        HIP_TRY(c, wait_stream(c, s));
-        if ((rc = words_collect(c, WP, lw, rn, wd)) != STR_ER_OK) return rc;
-    }
-    *n_runs = (int32_t)rn.size(); *n_words = (int32_t)wd.size();
-    if (n > 0) std::memcpy(line_words, lw.data(), sizeof(str_er_line_words) * (size_t)n);
-    if (!runs || !words) return STR_ER_OK;
-    if ((int64_t)rn.size() > (int64_t)cap_runs) return fail(c, STR_ER_ECAPACITY, std::to_string(rn.size()) + " glyph runs, cap_runs is " + std::to_string(cap_runs));
-    if ((int64_t)wd.size() > (int64_t)cap_words) return fail(c, STR_ER_ECAPACITY, std::to_string(wd.size()) + " words, cap_words is " + std::to_string(cap_words));
-    if (reading && !rn.empty()) {          // (the footprints are still in c->foot_bits, the lines as the kernel read them in `lines`)
-        std::vector<str_er_run_read> rd;
-        std::vector<uint8_t>         q;
-        if ((rc = run_read_stage(c, c->stream, lines, lw, rn, slopes, reads ? &rd : nullptr, q)) != STR_ER_OK) return rc;
-        if (reads) std::memcpy(reads, rd.data(), sizeof(str_er_run_read) * rd.size());
-        if (q_out) std::memcpy(q_out, q.data(), q.size());
-    }
-    if (!rn.empty()) std::memcpy(runs, rn.data(), sizeof(str_er_line_run) * rn.size());
-    if (!wd.empty()) std::memcpy(words, wd.data(), sizeof(str_er_line_word) * wd.size());
-    return STR_ER_OK;
-}
-
 int str_er_feet_words(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_words *line_words,
                       str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words, int32_t *n_words)
 try {
     if (!c) return STR_ER_EINVAL;
     return feet_words_read(c, W, H, feet, bits, n, line_words, runs, cap_runs, n_runs, words, cap_words, n_words, false, nullptr, nullptr, nullptr);
 } ABI_GUARD(c)
-
-int str_er_feet_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, const double *slopes, int32_t n,
-                     str_er_line_words *line_words, str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words,
-                     int32_t *n_words, str_er_run_read *reads, uint8_t *q_out)
-try {
-    if (!c) return STR_ER_EINVAL;
-    return feet_words_read(c, W, H, feet, bits, n, line_words, runs, cap_runs, n_runs, words, cap_words, n_words, true, slopes, reads, q_out);
-} ABI_GUARD(c)
-
-int str_er_run_atlas_stats(const str_er_ctx *c, uint64_t *bytes, uint64_t *grown)
-{
-    if (!c) return STR_ER_EINVAL;
-    if (bytes) *bytes = c->run_atlas.size();
-    if (grown) *grown = c->n_atlas_grown;
-    return STR_ER_OK;
-}
 
 const str_er_run_read *str_er_result_run_reads(const str_er_result *r, int32_t *n) { return result_table(r, r && r->have_run_reads, &str_er_result::run_reads, n); }
 

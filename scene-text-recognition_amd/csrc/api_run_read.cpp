@@ -1,0 +1,105 @@
+// api_run_read.cpp -- the C ABI, part 8c: the reading of the glyph runs of text lines (STR_ER_WANT_RUN_READ behind the line stage of
+// api_frame_lines.cpp, str_er_feet_read on uploaded footprints; the contract is at str_er_run_read in str_er.h).  Only the host knows
+// the compacted runs, so after the line stage's wait it lays their tiles out in an atlas (pack_run_tiles, words_host.cpp), k_run_tiles
+// expands the footprint words still in c->foot_bits into it, and the scorer's launch chain reads the atlas as a device plane
+// (run_read_stage: a second enqueue and wait).
+#include "str_er_ctx.h"
+
+namespace str_er_host {
+
+int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
+                   const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q)
+{
+    const size_t n = runs.size();
+    if (reads) reads->assign(n, str_er_run_read{});
+    q.assign(1800 * n, 0);
+    if (n == 0) return STR_ER_OK;
+    if (n > 0x7FFFFFFFull / 1800) return fail(c, STR_ER_ECAPACITY, "run read: too many glyph runs");
+    std::vector<RunTile> tiles(n);
+    std::vector<RotGeom> rot(n);
+    for (size_t t = 0; t < lines.size(); ++t) {
+        const FootLine &L = lines[t];
+        const double    sl = slopes && std::isfinite(slopes[t]) ? slopes[t] : 0.0;
+        for (int32_t k = 0; k < line_words[t].n_runs; ++k) {
+            const size_t           i = (size_t)line_words[t].first_run + (size_t)k;
+            const str_er_line_run &R = runs[i];
+            // (the kernel reads the rows and columns of the run in its line's words: they must lie inside the foot box)
+            if (i >= n || R.x0 < L.x || R.x1 <= R.x0 || R.x1 > L.x + L.w || R.y0 < L.y || R.y1 <= R.y0 || R.y1 > L.y + L.h)
+                return fail(c, STR_ER_EHIP, "run read: a glyph run outside its line's footprint (internal error)");
+            RunTile &T = tiles[i];
+            T.bit_off = L.word_off + (uint64_t)(R.y0 - L.y) * L.pitch; T.pitch = L.pitch; T.c0 = (uint32_t)(R.x0 - L.x);
+            T.w = (uint32_t)(R.x1 - R.x0); T.h = (uint32_t)(R.y1 - R.y0);
+            rot[i] = make_rot_geom((int)T.w, (int)T.h, sl);
+        }
+    }
+    RunAtlas A;
+    if (!pack_run_tiles(tiles.data(), n, RUN_SHELF_W, A)) return fail(c, STR_ER_ECAPACITY, "run read: the tiles of the glyph runs do not fit an atlas");
+    std::vector<int32_t> boxes(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+        const RunTile &T = tiles[i];
+        if ((uint64_t)T.ax + (T.w + 3u) / 4u * 4u > A.width || (uint64_t)T.ay + T.h > A.height)
+            return fail(c, STR_ER_EHIP, "run read: a tile outside the atlas (internal error)");
+        boxes[4 * i] = (int32_t)T.ax; boxes[4 * i + 1] = (int32_t)T.ay; boxes[4 * i + 2] = (int32_t)T.w; boxes[4 * i + 3] = (int32_t)T.h;
+    }
+    const size_t atlas_bytes = (size_t)A.width * A.height;
+    const size_t o_box = align_up(sizeof(RunTile) * n, 256), o_rot = align_up(o_box + 16 * n, 256), tab_bytes = o_rot + sizeof(RotGeom) * n;
+    const SvmDev *m = reads ? &c->svm : nullptr;
+    int rc = STR_ER_OK;
+    if (atlas_bytes > c->run_atlas.size()) {
+        if ((rc = c->run_atlas.ensure(c, atlas_bytes, "run tile atlas")) != STR_ER_OK) return rc;
+        ++c->n_atlas_grown;
+    }
+    if ((rc = c->run_tab.ensure(c, tab_bytes, "run tile tables")) != STR_ER_OK ||
+        (rc = ensure_scratch(c, ocr_layout(nullptr, n, m, true, false, false).bytes)) != STR_ER_OK)
+        return rc;
+    const OcrBuf buf = ocr_layout(c->scratch.d(), n, m, true, false, false);
+    uint8_t *h = c->run_tab.h(), *d = c->run_tab.d();
+    std::memcpy(h, tiles.data(), sizeof(RunTile) * n);
+    std::memcpy(h + o_box, boxes.data(), 16 * n);
+    std::memcpy(h + o_rot, rot.data(), sizeof(RotGeom) * n);
+    HIP_TRY(c, hipMemcpyAsync(d, h, tab_bytes, hipMemcpyHostToDevice, s));
+    launch_run_tiles(s, reinterpret_cast<const RunTile *>(d), (int)n, c->foot_bits.d<uint64_t>(), c->run_atlas.d(), A.width);
+    OcrSrc src{};
+    src.plane = c->run_atlas.d(); src.stride = (int32_t)A.width; src.inv = 0; src.boxes = reinterpret_cast<const int32_t *>(d + o_box);
+    src.rot = reinterpret_cast<const RotGeom *>(d + o_rot);
+    launch_ocr_features(s, src, (int)n, buf, m);
+    if (m) launch_svm_score(s, (int)n, buf, *m, true);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int32_t> label(reads ? n : 0);
+    std::vector<double>  prob(reads ? n : 0);
+    HIP_TRY(c, wait_stream(c, s));          // (wait, then copy into pageable memory, as the line scoring does)
+    HIP_TRY(c, hipMemcpyAsync(q.data(), buf.q, 1800 * n, hipMemcpyDeviceToHost, s));
+    if (reads) {
+        HIP_TRY(c, hipMemcpyAsync(label.data(), buf.label, 4 * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(prob.data(), buf.pbest, 8 * n, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(c, wait_stream(c, s));
+    if (reads)
+        for (size_t i = 0; i < n; ++i) (*reads)[i] = str_er_run_read{label[i], str_er_ocr_char(label[i]), prob[i]};
+    if (c->dbg_stats)        // developer aid
+        std::fprintf(stderr, "[str_er] run read: %zu runs, atlas %u x %u (%zu bytes, %zu bytes of tiles)\n", n, A.width, A.height, atlas_bytes,
+                     [&] { size_t b = 0; for (const RunTile &T : tiles) b += (size_t)(T.w + 3u) / 4u * 4u * T.h; return b; }());
+    return STR_ER_OK;
+}
+
+} // namespace str_er_host
+
+extern "C" {
+
+int str_er_feet_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, const double *slopes, int32_t n,
+                     str_er_line_words *line_words, str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words,
+                     int32_t *n_words, str_er_run_read *reads, uint8_t *q_out)
+try {
+    if (!c) return STR_ER_EINVAL;
+    return feet_words_read(c, W, H, feet, bits, n, line_words, runs, cap_runs, n_runs, words, cap_words, n_words, true, slopes, reads, q_out);
+} ABI_GUARD(c)
+
+int str_er_run_atlas_stats(const str_er_ctx *c, uint64_t *bytes, uint64_t *grown)
+{
+    if (!c) return STR_ER_EINVAL;
+    if (bytes) *bytes = c->run_atlas.size();
+    if (grown) *grown = c->n_atlas_grown;
+    return STR_ER_OK;
+}
+
+} // extern "C"

@@ -1324,16 +1324,17 @@ static int result_masks(const BatchRun &R, str_er_result *r, const uint32_t **d_
 // made, else none (frame_lines_phase makes the members' masks)
 static int frame_lines_result(const BatchRun &R, str_er_result *r, const uint32_t *d_mask_bits, const uint32_t *d_made_bits, std::vector<uint64_t> &made_word_off)
 {
-    const bool links = (R.stages & STR_ER_WANT_LINE_LINKS) != 0;      // (the links across frames: in the same stage)
-    const bool geom = (R.stages & STR_ER_WANT_LINE_GEOM) != 0;        // (the geometry of the footprints: likewise)
-    const bool words = (R.stages & STR_ER_WANT_LINE_WORDS) != 0;      // (their glyph runs and words: likewise)
-    const bool read = (R.stages & STR_ER_WANT_RUN_READ) != 0;         // (the reading of every run: behind the stage)
+    LineStageWants want;
+    want.links = (R.stages & STR_ER_WANT_LINE_LINKS) != 0;      // (the links across frames: in the same stage)
+    want.geom = (R.stages & STR_ER_WANT_LINE_GEOM) != 0;        // (the geometry of the footprints: likewise)
+    want.words = (R.stages & STR_ER_WANT_LINE_WORDS) != 0;      // (their glyph runs and words: likewise)
+    want.read = (R.stages & STR_ER_WANT_RUN_READ) != 0;         // (the reading of every run: behind the stage)
     if (d_mask_bits) {
         made_word_off.resize(r->masks.size());
         for (size_t k = 0; k < r->masks.size(); ++k) made_word_off[k] = r->masks[k].word_off;
-        return frame_lines_phase(R.c, R.s, R.b, R.dp.qscale, d_mask_bits, &made_word_off, r, links, geom, words, read);
+        return frame_lines_phase(R.c, R.s, R.b, R.dp.qscale, d_mask_bits, &made_word_off, r, want);
     }
-    return frame_lines_phase(R.c, R.s, R.b, R.dp.qscale, d_made_bits, d_made_bits ? &made_word_off : nullptr, r, links, geom, words, read);
+    return frame_lines_phase(R.c, R.s, R.b, R.dp.qscale, d_made_bits, d_made_bits ? &made_word_off : nullptr, r, want);
 }
 
 // candidates carry the device kept slot; translated to the sorted node table through (key, level) -- or -1 without STR_ER_WANT_NODES

@@ -1,7 +1,8 @@
 // str_er_ctx.h -- INTERNAL: the context / result structs and the small host helpers shared by the translation units of the C ABI
 // (str_er_api.cpp: contexts, batches, the detect entry points, results; api_models.cpp: cascade / libsvm models and the OCR entry points;
 //  api_strips.cpp: one plane in strips over several GPUs; api_stages.cpp: the single-stage entry points; api_text_map.cpp / api_frame_lines.cpp: the
-//  frame maps and the frame lines).  Not installed, not part of the ABI.
+//  frame maps and the frame lines; api_run_read.cpp: the reading of the glyph runs; lines_host.cpp / words_host.cpp: the host side of the
+//  line stage that touches no device).  Not installed, not part of the ABI.
 // The helpers in the unnamed namespace are small and private to each translation unit; what one unit defines for the others is declared in str_er_host.
 #pragma once
 #include "../../include/str_er.h"
@@ -540,14 +541,34 @@ struct SampleTabs {
 // ---- defined in api_frame_lines.cpp
 // STR_ER_WANT_FRAME_LINES in run_batch: the feet, pairs and frame lines of the lines of r.  d_mask_bits / word_off: mask words of this
 // call still on the device and the first word of every candidate's (UINT64_MAX: none), or null: then the members' masks are made here
-// links: STR_ER_WANT_LINE_LINKS as well (the links, tracks and edge feet of r, in the same stage)
-// geom: STR_ER_WANT_LINE_GEOM as well (the geometry of the lines and frame lines of r, k_foot_geom in the same stage)
-// words: STR_ER_WANT_LINE_WORDS as well (the glyph runs and words of the lines of r, k_foot_words in the same stage)
-// read: STR_ER_WANT_RUN_READ as well (the reading of every run: k_run_tiles and the scorer behind the stage's wait, with a wait of their own)
+// want: what rides on the same stage
+struct LineStageWants {
+    bool links = false;       // STR_ER_WANT_LINE_LINKS: the links, tracks and edge feet of r (k_foot_links)
+    bool geom = false;        // STR_ER_WANT_LINE_GEOM: the geometry of the lines and frame lines of r (k_foot_geom)
+    bool words = false;       // STR_ER_WANT_LINE_WORDS: the glyph runs and words of the lines of r (k_foot_words)
+    bool read = false;        // STR_ER_WANT_RUN_READ: the reading of every run (k_run_tiles and the scorer behind the stage's wait, with a wait of their own)
+};
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
-                      str_er_result *r, bool links = false, bool geom = false, bool words = false, bool read = false);
-// ---- defined in words_host.cpp (HIP-free)
+                      str_er_result *r, const LineStageWants &want);
+// the caller's footprints of str_er_feet_words / str_er_feet_read (api_run_read.cpp) cut into runs and words, and with read_runs read
+// (slopes, reads, q_out: str_er_feet_read's arguments)
+int feet_words_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_words *line_words,
+                    str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words, int32_t *n_words, bool read_runs,
+                    const double *slopes, str_er_run_read *reads, uint8_t *q_out);
+// ---- defined in api_run_read.cpp
+// The reading of the compacted runs of a launch whose footprints are still in c->foot_bits (lines: the table k_foot_words read):
+// the tiles laid out and expanded into the atlas, then the scorer's launch chain on the atlas as a device plane with one box a run and
+// the slope of the run's line (slopes: one per line, or null: all 0; a slope that is not finite counts as 0).  One upload, the
+// launches, the copies back and a wait of its own on s.  reads == null: the features only (no model needed).
+int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
+                   const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q);
+// ---- defined in words_host.cpp and lines_host.cpp (HIP-free)
 bool word_gap_ok(int32_t num, int32_t den);       // what str_er_set_word_gap takes
+// inter * den >= num * (pa + pb - inter): footprints of pa and pb pixels, inter of them common, are duplicates (links) at num / den
+bool overlap_passes(uint32_t inter, uint32_t pa, uint32_t pb, int32_t num, int32_t den);
+// the geometry of frame lines: the hull of the union of the members' hull vertices (appended to points), the moments of the representative
+int frame_line_geoms(const str_er_frame_line *frame_lines, size_t n_frame_lines, const int32_t *members, const str_er_line_geom *line_geoms,
+                     std::vector<int32_t> &points, std::vector<str_er_line_geom> &out);
 constexpr int MASK_MAX_WIDTH = 16384;       // widest box the mask kernels take (er_masks.inl: MASK_MAX_WPL words of 64 pixels per lane)
 // ---- defined in api_models.cpp
 int parse_cascade(str_er_ctx *c, HostCascade &hc, const char *text, size_t len);

@@ -2,7 +2,8 @@
 // str_er_line_run in str_er.h), the character of a label (str_er_ocr_char) and the shelf packer of the run tiles' atlas
 // (pack_run_tiles; STR_ER_WANT_RUN_READ).  Pure host and HIP-free: it includes nothing of the library but the public header and the
 // plain structures of er_types.h, so that tests/cpp/line_words_rules_check.cpp and run_read_rules_check.cpp link this file alone
-// under the host sanitizers.  The detect calls, str_er_feet_words and str_er_feet_read (api_frame_lines.cpp) use these same functions.
+// under the host sanitizers.  The detect calls, str_er_feet_words (api_frame_lines.cpp) and str_er_feet_read (api_run_read.cpp) use
+// these same functions.  lines_host.cpp holds the rest of the line stage's host code in the same way.
 #include "../../include/str_er.h"
 #include "er_types.h"
 

@@ -142,6 +142,30 @@ def test_link_feet_hand_made(S, cascade_paths):
     f.close()
 
 
+def test_link_feet_feet_geom_and_feet_words_in_turn(S, cascade_paths):
+    """The three calls on a caller's footprints share the context's line table and footprint words: one after the other on one context,
+    each with another number of footprints, twice, each result against its reference with ==."""
+    import line_geom_ref as G
+    import line_words_ref as WD
+    rng = np.random.default_rng(11)
+    bar = np.ones((3, 70), bool)
+    bar[:, 20:24] = False                                               # two glyph runs, 70 columns: two device words a row
+    items = [(5, 10, bar), (30, 11, _tight(rng.random((2, 65)) < 0.6)), (40, 12, _tight(rng.random((3, 33)) < 0.6))]
+    feet = [FR.Foot(x, y, b) for x, y, b in items]
+    f = _ctx(S, cascade_paths, max_width=640, max_height=480, max_frames=1)
+    ref_links = R.set_links(feet[:2], feet[2:])
+    assert len(ref_links) == 2
+    for _ in range(2):
+        assert _link_rows(f.link_feet(200, 100, *_feet(S, feet[:2]), *_feet(S, feet[2:]))) == ref_links          # three lines
+        geoms, points = f.feet_geom(200, 100, *_feet(S, [feet[2], feet[0]]))                                      # two
+        assert len(geoms) == 2 and len(points) == sum(len(G.geom(b, x, y)[3]) for x, y, b in (items[2], items[0]))
+        for g, (x, y, b) in zip(geoms, (items[2], items[0])):
+            assert G.same(g, points, G.geom(b, x, y)) is None
+        got = WD.as_lists(*f.feet_words(200, 100, *_feet(S, [feet[1]])))                                          # one
+        assert list(got) == list(WD.tables([items[1]]))
+    f.close()
+
+
 # ---- the fused call ---------------------------------------------------------------------------------------------------------------------
 
 MOTION = (2, 1)          # pixels per frame, x and y
