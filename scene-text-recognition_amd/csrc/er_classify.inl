@@ -81,6 +81,7 @@ __device__ double block_cascade(ClsShared &sh, const CascadeDev &c)
             }
             __syncthreads();
         }
+        __syncthreads();        // (a stage without stumps has no chunk, so no barrier of the loop stands between lane 0's reset of acc and the reads below)
         score = sh.acc;
         __syncthreads();
         if (score < (double)c.stage_thresh[s]) return -DBL_MAX;
@@ -615,6 +616,7 @@ __global__ __launch_bounds__(CLS_THREADS) void k_cascade_fv(const double *__rest
                 }
                 __syncthreads();
             }
+            __syncthreads();    // (as in block_cascade: an empty stage has no chunk)
             score = s_acc;
             __syncthreads();
             if (score < (double)c.stage_thresh[s]) rejected = true;

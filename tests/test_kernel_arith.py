@@ -166,3 +166,89 @@ def test_chain_winner_in_parallel_is_the_sequential_one(T):
         steps = rng.choice([0, 0, 1, 2, 3, 10, 100, 5000], n)
         areas = (int(rng.integers(1, 50)) + np.cumsum(steps)).tolist()
         assert _winner_parallel(areas, T) == _winner_sequential(areas, T), (areas, T)
+
+
+# ---- parse_cascade's integer table (api_models.cpp): (h < T) ? A : B for 8-bit counts, T = ceil(thr) for dir +1, floor(thr) + 1 with the outputs swapped
+# ---- for dir -1, NaN -> 0 / 1e9, T clamped to [0, 300], packed as dim | T << 10 ------------------------------------------------------------------------
+
+def _table_entry(thr, dirn, vp, vn):
+    if dirn == 1:
+        T, A, B = (0.0 if math.isnan(thr) else math.ceil(thr) if math.isfinite(thr) else thr), vp, vn
+    else:
+        T, A, B = (1e9 if math.isnan(thr) else math.floor(thr) + 1.0 if math.isfinite(thr) else thr), vn, vp
+    return int(min(max(T, 0.0), 300.0)), A, B
+
+
+def _listed_thresholds():
+    from cascade_cases import threshold_tokens
+    return [float(t) for t in threshold_tokens()]
+
+
+@pytest.mark.parametrize("dirn", [1, -1])
+def test_integer_table_decides_like_the_stump(dirn):
+    """For every count a byte can hold and every listed threshold (k, k +- 0.5, the doubles next to k at both ends of 0 .. 144, values past the
+    clamp, a negative one, -0.0, the infinities, NaN): the table's entry gives what `h * dir < thr * dir ? vp : vn` gives."""
+    h = np.arange(256, dtype=np.float64)
+    vp, vn = 1.25, -0.75
+    thrs = _listed_thresholds()
+    assert any(math.isnan(t) for t in thrs) and math.inf in thrs and -math.inf in thrs and any(t == 0 and math.copysign(1, t) < 0 for t in thrs)
+    for thr in thrs + [t + 0.25 for t in range(0, 146)] + [float(t) for t in range(-2, 147)]:
+        T, A, B = _table_entry(thr, dirn, vp, vn)
+        assert 0 <= T <= 300
+        with np.errstate(invalid="ignore"):
+            want = np.where(h * dirn < thr * dirn, vp, vn)
+        got = np.where(h < T, A, B)
+        np.testing.assert_array_equal(got, want, err_msg=f"thr {thr!r} dir {dirn}")
+
+
+def test_integer_table_word_round_trips():
+    dim, T = np.meshgrid(np.arange(1024, dtype=np.uint32), np.arange(301, dtype=np.uint32))
+    w = dim | (T << np.uint32(10))
+    assert int(w.max()) < (1 << 19)                         # 10 bits of dim, 9 of T: the readlane'd int stays positive
+    np.testing.assert_array_equal(w & np.uint32(1023), dim)
+    np.testing.assert_array_equal(w >> np.uint32(10), T)
+
+
+# ---- k_classify's box arithmetic over every box NMS admits (0.1 < w / h < 2) -------------------------------------------------------------------------------
+
+def _aran_dims(w, h):
+    """OCR::ARAN's tile size (src/OCR.cpp:394-430) as k_classify computes it: the longer side becomes 26, the other (int)(26 * sqrt(ratio))"""
+    w, h = np.asarray(w, np.float64), np.asarray(h, np.float64)
+    wide = w > h
+    k = (26.0 * np.sqrt(np.where(wide, h / w, w / h))).astype(np.int64)
+    return np.where(wide, 26, k), np.where(wide, k, 26)
+
+
+def _resize_mode(sw, sh, dw, dh):
+    """er_device.h resize_geom: 0 copy, 1 exact 2 x 2 area, 2 fixed-point bilinear"""
+    sx, sy = 1.0 / (dw / sw), 1.0 / (dh / sh)
+    eps = np.finfo(np.float64).eps
+    fast = (np.abs(sx - np.rint(sx)) < eps) & (np.abs(sy - np.rint(sy)) < eps) & (np.rint(sx) == 2) & (np.rint(sy) == 2)
+    return np.where((dw == sw) & (dh == sh), 0, np.where(fast, 1, 2))
+
+
+def test_box_arithmetic_over_every_admitted_box():
+    w, h = np.meshgrid(np.arange(1, 601), np.arange(1, 601))
+    ok = (w / h > 0.1) & (w / h < 2.0)
+    w, h = w[ok], h[ok]
+    dw, dh = _aran_dims(w, h)
+    assert dw.min() >= 8 and dh.min() >= 8 and dw.max() == 26 and dh.max() == 26          # never 0: the dw > 0 && dh > 0 test is k_lbp_boxes' business
+    assert ((dw == 26) | (dh == 26)).all()
+    mode = _resize_mode(w.astype(np.float64), h.astype(np.float64), dw.astype(np.float64), dh.astype(np.float64))
+    # copy: the box IS its tile; exact 2 x: the box is twice its tile both ways, nothing else comes within DBL_EPSILON of scale 2
+    np.testing.assert_array_equal(mode == 0, (w == dw) & (h == dh))
+    np.testing.assert_array_equal(mode == 1, (w == 2 * dw) & (h == 2 * dh))
+    assert set(zip(w[mode == 0].tolist(), h[mode == 0].tolist())) >= {(26, 26), (25, 26), (26, 25)} and (np.maximum(w, h)[mode == 0] == 26).all()
+    assert (np.maximum(w, h)[mode == 1] == 52).all()
+    from cascade_cases import WANTED_SIZES
+    ww, wh = np.array([s[0] for s in WANTED_SIZES]), np.array([s[1] for s in WANTED_SIZES])
+    assert ((ww / wh > 0.1) & (ww / wh < 2.0)).all()
+    wdw, wdh = _aran_dims(ww, wh)
+    got = _resize_mode(ww.astype(np.float64), wh.astype(np.float64), wdw.astype(np.float64), wdh.astype(np.float64)).tolist()
+    assert got == [0, 0, 1, 1, 1] + [2] * 13          # what tests/test_classify_edges.py assumes of its rectangles
+    # the separable resize's tables: a column entry is (sx, sx1) in 16 bits each, a row entry the byte offset y0 * stride with bit 31 free for
+    # "y1 is the next row"; 26 entries of each fit the wave's two halves
+    assert dw.max() <= 32 and dh.max() <= 32 and int(w.max()) - 1 < (1 << 16)
+    for stride, rows in ((3840, 2160), (7680, 4320)):
+        tallest = int(math.ceil(0.8 * rows)) - 1            # NMS: h < 0.8 * rows
+        assert max(int(h.max()) - 1, tallest - 1) * stride + stride < (1 << 31)
