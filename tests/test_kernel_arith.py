@@ -252,3 +252,118 @@ def test_box_arithmetic_over_every_admitted_box():
     for stride, rows in ((3840, 2160), (7680, 4320)):
         tallest = int(math.ceil(0.8 * rows)) - 1            # NMS: h < 0.8 * rows
         assert max(int(h.max()) - 1, tallest - 1) * stride + stride < (1 << 31)
+
+
+# ---- k_ocr_features (ocr_kernels.hip): the row index, the packed bit rows and the blur through a table of 7-bit patterns ---------------------------------
+
+def test_ocr_row_index_from_a_float_reciprocal():
+    # dy = (int)(((float)i + 0.5f) * (1.0f / dw)) for a pixel index i < dw * dh <= 900 of the ARAN(30) tile
+    i = np.arange(900, dtype=np.float32)
+    for dw in range(1, 31):
+        inv = np.float32(1.0) / np.float32(dw)
+        got = ((i + np.float32(0.5)) * inv).astype(np.int64)
+        assert got.dtype == np.int64 and ((i + np.float32(0.5)) * inv).dtype == np.float32
+        np.testing.assert_array_equal(got, np.arange(900) // dw, err_msg=f"dw {dw}")
+
+
+def test_ocr_bit_of_four_bytes_gathered_by_a_multiplication():
+    # ((((row >> c) & 0x01010101) * 0x00204081 >> 21) & 0xF): bit c of the four bytes of a word, in byte order, whatever the other bits hold
+    rng = np.random.default_rng(21)
+    for c in range(8):
+        for pat in range(16):
+            for other in [0, 0xFFFFFFFF] + rng.integers(0, 1 << 32, 20).tolist():
+                row = int(other) & ~(0x01010101 << c) & 0xFFFFFFFF
+                for b in range(4):
+                    row |= ((pat >> b) & 1) << (8 * b + c)
+                got = ((((row >> c) & 0x01010101) * 0x00204081 & 0xFFFFFFFF) >> 21) & 0xF           # (a 32-bit product: the high bits fall away)
+                assert got == pat, (c, pat, hex(row))
+
+
+def _reflect101(i, n):
+    """oracle/er_oracle.c reflect101 (BORDER_REFLECT_101)"""
+    if n == 1:
+        return 0
+    while i < 0 or i >= n:
+        i = -i if i < 0 else 2 * n - 2 - i
+    return i
+
+
+def _padded_row(bits):
+    """The 36-bit row of L.rows: marks at bits 3 .. 32, reflected columns at 0 .. 2 and 33 .. 35"""
+    bits &= 0x3FFFFFFF
+    p = bits << 3
+    p |= ((bits >> 3) & 1) | ((bits >> 2) & 1) << 1 | ((bits >> 1) & 1) << 2
+    p |= ((bits >> 28) & 1) << 33 | ((bits >> 27) & 1) << 34 | ((bits >> 26) & 1) << 35
+    return p
+
+
+def test_ocr_bit_row_padding_is_reflect_101():
+    rng = np.random.default_rng(22)
+    for bits in [0, 0x3FFFFFFF, 1, 1 << 29, 0b1110, 0b0111 << 26] + rng.integers(0, 1 << 30, 300).tolist():
+        p = _padded_row(int(bits))
+        assert p < (1 << 36)
+        for x in range(-3, 33):
+            assert (p >> (x + 3)) & 1 == (int(bits) >> _reflect101(x, 30)) & 1, (hex(int(bits)), x)
+
+
+_KG = (8, 28, 56, 72, 56, 28, 8)
+
+
+def _g7():
+    t = np.arange(128)
+    return 255 * sum(_KG[k] * ((t >> k) & 1) for k in range(7))
+
+
+def test_ocr_blur_table_fits_16_bits():
+    g = _g7()
+    assert g.max() == 255 * 256 < (1 << 16) and g[0] == 0 and g[0b0001000] == 255 * 72
+    # the vertical pass of seven such entries: below 2^32, and 255 after the rounding shift at the most -- the clamp never acts
+    s = 256 * int(g.max())
+    assert s < (1 << 32) and (s + (1 << 15)) >> 16 == 255
+
+
+def _blur_two_pass(m):
+    """The oracle's blur (ero_chain_features_slope): a row pass in 8.8 fixed point, a column pass rounded to nearest from 16 fractional bits"""
+    L = 30
+    hrow = np.zeros((L, L), np.int64)
+    for y in range(L):
+        for x in range(L):
+            hrow[y, x] = sum(int(m[y, _reflect101(x + k, L)]) * _KG[k + 3] for k in range(-3, 4))
+    out = np.zeros((L, L), np.int64)
+    for y in range(L):
+        for x in range(L):
+            s = sum(int(hrow[_reflect101(y + k, L), x]) * _KG[k + 3] for k in range(-3, 4))
+            out[y, x] = min((s + (1 << 15)) >> 16, 255)
+    return out
+
+
+def _blur_kernel_form(m):
+    """k_ocr_features: packed rows, s_g7 by 7-bit window, 8 (h0 + h6) + 28 (h1 + h5) + 56 (h2 + h4) + 72 h3"""
+    L = 30
+    g = _g7()
+    rows = [_padded_row(sum(1 << x for x in range(L) if m[y, x])) for y in range(L)]
+    out = np.zeros((L, L), np.int64)
+    top = 0
+    for x in range(L):
+        h = [int(g[(rows[_reflect101(y, L)] >> x) & 127]) for y in range(-3, L + 3)]
+        for y in range(L):
+            h0, h1, h2, h3, h4, h5, h6 = h[y:y + 7]
+            s = 8 * (h0 + h6) + 28 * (h1 + h5) + 56 * (h2 + h4) + 72 * h3
+            top = max(top, (s + (1 << 15)) >> 16)
+            out[y, x] = min((s + (1 << 15)) >> 16, 255)
+    return out, top
+
+
+def test_ocr_blur_by_table_is_the_two_pass_blur():
+    rng = np.random.default_rng(23)
+    maps = [np.zeros((30, 30), np.uint8), np.full((30, 30), 255, np.uint8)]
+    for density in (0.03, 0.2, 0.5, 0.9):
+        maps += [np.where(rng.random((30, 30)) < density, 255, 0).astype(np.uint8) for _ in range(3)]
+    edge = np.zeros((30, 30), np.uint8)
+    edge[0, :] = edge[29, :] = edge[:, 0] = edge[:, 29] = 255
+    maps.append(edge)
+    for m in maps:
+        got, top = _blur_kernel_form(m)
+        np.testing.assert_array_equal(got, _blur_two_pass(m))
+        assert top <= 255
+    assert _blur_kernel_form(maps[1])[0].max() == 255 and _blur_kernel_form(maps[1])[0].min() == 255
