@@ -128,7 +128,9 @@ static int launch_tile_trees(str_er_ctx *c, const Batch &b, const BatchDev &bd, 
         any |= t;
         key.push_back((uint32_t)pd.w); key.push_back((uint32_t)pd.h); key.push_back(t ? 1u : 0u);
     }
-    if (!any) { launch_tile_tree(s, bd, dp, c->tile_sparse); c->n_t2_tiles = 0; return STR_ER_OK; }
+    // (the key goes with the count: a later batch of the same layout must set n_t2_tiles again -- it sizes k_tile_tree_fb's grid, and with 0 the tiles
+    // k_tile_tree2 hands back would be nobody's, which is what the first batch after a back-off used to get)
+    if (!any) { launch_tile_tree(s, bd, dp, c->tile_sparse); c->n_t2_tiles = 0; c->t2_key.clear(); return STR_ER_OK; }
     if (key != c->t2_key) {
         c->t2_key.clear();
         c->h_t1_list.clear(); c->h_t2_pairs.clear();

@@ -327,10 +327,11 @@ static void run_body(const Plane &P, RunOut &o, unsigned long long *ops_out)
     if (ops_out) *ops_out = g_ops - ops0;
 }
 
-static int check_plane(const Plane &P, const char *what, unsigned long long *ops_out, unsigned *fb_out)
+static int check_plane(const Plane &P, const char *what, unsigned long long *ops_out, unsigned *fb_out, std::vector<uint32_t> *fb_tiles = nullptr)
 {
     RunOut o;
     run_body(P, o, ops_out);
+    if (fb_tiles) { fb_tiles->assign(o.fb_list.begin(), o.fb_list.begin() + o.fb_count); std::sort(fb_tiles->begin(), fb_tiles->end()); }
     std::vector<char> is_fb((size_t)P.tiles_x * P.tiles_y, 0);
     for (uint32_t i = 0; i < o.fb_count; ++i) is_fb[o.fb_list[i]] = 1;
     if (fb_out) *fb_out = o.fb_count;
@@ -406,15 +407,22 @@ int main(int argc, char **argv)
         // a real plane (tools/sim_tile_dump.py writes quantised levels, one byte per pixel, 255 = wall): cost per tile
         const int W = atoi(argv[3]), H = atoi(argv[4]);
         Plane P;
-        P.w = W; P.h = H; P.step = 8; P.hi = 32; P.min_area = 120; P.invert = 0; P.stride = (W + 63) / 64 * 64; P.tiles_x = (W + 63) / 64; P.tiles_y = (H + 31) / 32;
+        // (optional: the thresh step -- a power of two, 8 by default -- and MIN_AREA, 120 by default)
+        const int step = argc > 5 ? atoi(argv[5]) : 8;
+        P.w = W; P.h = H; P.step = step; P.hi = 255 / step + 1; P.min_area = argc > 6 ? atoi(argv[6]) : 120; P.invert = 0; P.stride = (W + 63) / 64 * 64; P.tiles_x = (W + 63) / 64; P.tiles_y = (H + 31) / 32;
         P.pix.assign((size_t)P.stride * H + 64, 0);
         std::vector<uint8_t> lev((size_t)W * H);
         FILE *f = fopen(argv[2], "rb");
         if (!f || fread(lev.data(), 1, lev.size(), f) != lev.size()) { puts("cannot read the plane"); return 1; }
         fclose(f);
-        for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) P.pix[(size_t)y * P.stride + x] = lev[(size_t)y * W + x] == 255 ? 255 : (uint8_t)(lev[(size_t)y * W + x] * 8);
+        for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) P.pix[(size_t)y * P.stride + x] = lev[(size_t)y * W + x] == 255 ? 255 : (uint8_t)(lev[(size_t)y * W + x] * step);
         unsigned long long ops = 0; unsigned fbn = 0;
-        const int e = check_plane(P, "file", &ops, &fbn);
+        std::vector<uint32_t> fb;
+        const int e = check_plane(P, "file", &ops, &fbn, &fb);
+        // which tiles the kernel's own source hands back, in tile order (tests/test_tree_edges.py compares its census with this line)
+        printf("handed back:");
+        for (uint32_t t : fb) printf(" %u", t);
+        printf("\n");
         const double tiles = (double)P.tiles_x * P.tiles_y;
         printf("%s: %d errors, %.0f tiles, %u to the fall-back, %.0f vector ops per tile = %.0f per 512 pixels\n", argv[2], e, tiles, fbn, ops / tiles, ops / tiles / 4.0);
         HostWave::mark(0);

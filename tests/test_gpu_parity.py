@@ -660,7 +660,8 @@ def test_groups_left_alone_are_joined_by_the_undone_pass(S, cascade_paths, monke
     """k_seam only sees the seams BETWEEN groups of tiles; the seams inside a group are k_group_merge's -- or, for a group with more records than its table
     holds, k_seam_undone's (the group puts itself on a device-side list).  With the smallest table (512 records) and large groups most groups of a text-like
     pyramid frame and every group of a noise frame overflow; with 1 x 1 groups nothing is inside a group; without grouping every seam is k_seam's.  All give
-    the records of the default shape, node for node -- on a batch large enough to take the 8 x 4 default (> 96 planes) and on a call of one frame."""
+    the records of the default shape, node for node -- on a batch large enough to take the 8 x 4 default (> 96 planes) and on a call of one frame.
+    (Groups of exactly the table's size and one record above it, and more listed groups than k_seam_undone has workgroups: tests/test_tree_edges.py.)"""
     W, H = 448, 320
     rng = np.random.default_rng(77)
     one = S.synth.stext_bgr(S.synth.frame_seed(70), W, H)[None]
