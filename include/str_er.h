@@ -129,6 +129,12 @@ extern "C" {
  * usable afterwards.  It does not need STR_ER_STAGE_OCR_LINES.  Every call that honours _LINE_WORDS honours it.  It changes no other
  * output of the call and combines with every other STR_ER_WANT_* flag.                                                             */
 #define STR_ER_WANT_RUN_READ (2097152u)
+/* output option: every word of STR_ER_WANT_RUN_READ matched against the lexicon of str_er_set_lexicon: the best and the second-best
+ * entry per word (str_er_result_word_matches), the cost row of every run (str_er_result_run_costs) and its class probabilities
+ * (str_er_result_run_probs); the contract is at str_er_word_match.  Needs STR_ER_WANT_RUN_READ: STR_ER_EINVAL without it and wherever
+ * that flag is refused, and a lexicon: STR_ER_ESTATE without one; the context is usable afterwards.  Every call that honours
+ * _RUN_READ honours it.  It changes no other output of the call and combines with every other STR_ER_WANT_* flag.                  */
+#define STR_ER_WANT_WORD_MATCH (4194304u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -451,13 +457,44 @@ typedef struct str_er_line_words {
  *   Character of a run: str_er_ocr_char(label).  No run is dropped for a low probability: prob is returned and the caller filters.
  *   String of a word: the characters of runs[first_run .. first_run + n_runs).  Text of a frame line: the words of its representative
  *     joined by one blank.
- *   Limits: there is no spelling correction and no language model (the reference's word graph, bigram table and corrector are not
- *     rebuilt), and a run of touching glyphs reads as one character: runs are not split.                                            */
+ *   Limits: the string of a word is the arg max of its runs: in it there is no spelling correction and no language model (the
+ *     reference's word graph, bigram table and corrector are not rebuilt), and a run of touching glyphs reads as one character: runs
+ *     are not split in the image.  The match of a word against a lexicon, which may spend a character without a run of its own or a
+ *     run without a character, is a separate output: str_er_word_match (STR_ER_WANT_WORD_MATCH).                                    */
 typedef struct str_er_run_read {
     int32_t  label;          /*  0: the scorer's label                                */
     int32_t  ch;             /*  4: str_er_ocr_char(label)                            */
     double   prob;           /*  8: pv[label]                                         */
 } str_er_run_read;           /* 16 bytes; one per run of str_er_result_line_runs()    */
+
+/* The match of a word against a lexicon (STR_ER_WANT_WORD_MATCH, str_er_match_words): a weighted edit distance, in integers, between
+ * the glyph runs of the word and every entry of the caller's lexicon, with the best and the second-best entry.  A definition of this
+ * library, like the word gap and the reading of a run; it is exact, and the host states the same rules (str_er_prob_costs,
+ * str_er_match_words_host).
+ *   Alphabet: the 65 characters of str_er_ocr_char; the index a of a character is its label 0 .. 64.
+ *   Cost of a probability: T[c] = ldexp(M[c % 8], -(c / 8)) for c = 0 .. 254, M the eight doubles nearest to 2^(-j/8)
+ *     (str_er_cost_thresholds).  cost(p) is the smallest c in 0 .. 254 with p >= T[c], otherwise 255; NaN and negative values give
+ *     255.  The unit is 1/8 bit.  Only comparisons of doubles are involved: the host and the device agree exactly.
+ *   Cost row of a run: 65 bytes, C[a] = cost(prob[j]) for the class j of the model whose label is a (the first such class), 255 where
+ *     the model has no such class; classes with a label outside 0 .. 64 are ignored.  With the lexicon's fold-case flag both letters
+ *     of a case pair get the minimum of the two.
+ *   Lexicon: n entries, 0 <= n <= 2^20, each of 1 .. 32 bytes over the alphabet; duplicates are allowed.  With
+ *     STR_ER_LEXICON_FOLD_CASE the entries are compared without regard to case -- the matcher reads min(C[a], C[a']) for a letter a
+ *     and its other case a' -- and reported as given.
+ *   Cost of entry e (length l) for a word with the runs 1 .. m: D[0][0] = 0, D[i][0] = i * DEL, D[0][j] = j * INS,
+ *     D[i][j] = min(D[i-1][j-1] + C_i[e_j], D[i-1][j] + DEL, D[i][j-1] + INS); the cost is D[m][l].  DEL is a run with no character
+ *     of its own (a speck, a broken piece), INS a character with no run of its own (touching glyphs); both are in 1 .. 255 and 64 by
+ *     default (str_er_set_word_match).
+ *   Band: an entry is tried iff |l - m| <= band; the band is in 0 .. 31 and 2 by default.  A word with m > 32 tries nothing.
+ *   Result: (cost, entry) is the minimum over the tried entries of (cost, index); second_* the same minimum over the tried entries
+ *     other than `entry`; free_cost the sum over the runs of min_a C_i[a], the cost of the word's own reading (of every run, also
+ *     for m > 32); n_tried the number of entries tried.  entry and second_entry are -1, with their costs -1, where nothing qualifies. */
+typedef struct str_er_word_match {
+    int32_t  entry, cost;                 /*  0,  4                                   */
+    int32_t  second_entry, second_cost;   /*  8, 12                                   */
+    int32_t  free_cost, n_tried;          /* 16, 20                                   */
+} str_er_word_match;         /* 24 bytes; one per word of str_er_result_words()       */
+#define STR_ER_LEXICON_FOLD_CASE 1u
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -755,6 +792,36 @@ int str_er_feet_read(str_er_ctx *ctx, int32_t W, int32_t H, const str_er_line_fo
  * allocated or grown since the context was created.  Either pointer may be NULL.                                                  */
 int str_er_run_atlas_stats(const str_er_ctx *ctx, uint64_t *bytes, uint64_t *grown);
 
+/* The lexicon of the context (str_er_word_match): n entries, entry i the bytes [offsets[i], offsets[i + 1]) of `bytes`, the
+ * characters themselves ('0' .. '9', 'A' .. 'Z', 'a' .. 'z', '&', '(', ')'); offsets has n + 1 values and starts at 0.  n = 0 clears
+ * the lexicon (bytes and offsets may be NULL).  flags: 0 or STR_ER_LEXICON_FOLD_CASE.  STR_ER_EINVAL on a byte outside the alphabet,
+ * on a length of 0 or above 32, on offsets that do not lie back to back from 0 and on other flags; STR_ER_ECAPACITY above 2^20
+ * entries; the context is unchanged then.  The call waits for the context's work.  A stream's contexts: str_er_stream_context.      */
+int str_er_set_lexicon(str_er_ctx *ctx, const char *bytes, const int32_t *offsets, int32_t n, uint32_t flags);
+/* The lexicon that is set: its entries, its flags, the chunk size in entries (a workgroup of the matcher takes so many slots of the
+ * padded lexicon) and the bytes it takes on the device (0 without one).  Any pointer may be NULL.                                  */
+int str_er_lexicon_info(const str_er_ctx *ctx, int32_t *n, uint32_t *flags, int32_t *chunk_entries, uint64_t *device_bytes);
+/* INS, DEL (1 .. 255) and the band (0 .. 31) of str_er_word_match; defaults 64, 64, 2.  Anything else -> STR_ER_EINVAL, the context
+ * unchanged.  A stream's contexts: str_er_stream_context.                                                                          */
+int str_er_set_word_match(str_er_ctx *ctx, int32_t ins, int32_t del, int32_t band);
+/* The table T of str_er_word_match.  Pure: no context, no GPU.                                                                     */
+void str_er_cost_thresholds(double out[255]);
+/* The cost rows (65 bytes each, into cost_out) of n runs from their k class probabilities (prob: n x k) of a model with the given k
+ * labels; fold: the fold-case rule.  Pure: no context, no GPU.  STR_ER_EINVAL on NULL or negative arguments.                        */
+int str_er_prob_costs(const double *prob, int32_t n, int32_t k, const int32_t *labels, int32_t fold, uint8_t *cost_out);
+/* The same on the GPU with the labels of the loaded SVM model (prob: n x nr_class) and the fold-case flag of the lexicon (none: not
+ * folded).  STR_ER_ESTATE without a model.                                                                                         */
+int str_er_run_costs(str_er_ctx *ctx, const double *prob, int32_t n, uint8_t *cost_out);
+/* The matcher on the caller's cost rows: costs holds n_runs rows of 65 bytes, word w has the rows first_run[w] .. first_run[w] +
+ * n_runs_of_word[w]; matches receives n_words records.  STR_ER_ESTATE without a lexicon; STR_ER_EINVAL on a word outside the rows.
+ * It needs no SVM model.                                                                                                           */
+int str_er_match_words(str_er_ctx *ctx, const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
+                       str_er_word_match *matches);
+/* The same rules on one host thread, with the lexicon and the parameters as arguments (as for str_er_set_lexicon and
+ * str_er_set_word_match, with their checks).  Pure: no context, no GPU.                                                            */
+int str_er_match_words_host(const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, const char *bytes,
+                            const int32_t *offsets, int32_t n, uint32_t flags, int32_t ins, int32_t del, int32_t band, str_er_word_match *matches);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -981,6 +1048,12 @@ const str_er_line_word  *str_er_result_words(const str_er_result *r, int32_t *n)
  * feature bytes of the runs.  Each returns NULL and 0 without the flag; a call without runs returns empty arrays (not NULL).       */
 const str_er_run_read   *str_er_result_run_reads(const str_er_result *r, int32_t *n);
 const uint8_t           *str_er_result_run_features(const str_er_result *r, uint64_t *n_bytes);
+/* With STR_ER_WANT_WORD_MATCH (str_er_word_match): one record per word of str_er_result_words(), the 65 * n cost bytes of the runs
+ * and their k * n class probabilities (k: nr_class of str_er_svm_info, in the model's class order), the runs in the order of
+ * str_er_result_line_runs().  Each returns NULL and 0 without the flag; a call without runs returns empty arrays (not NULL).        */
+const str_er_word_match *str_er_result_word_matches(const str_er_result *r, int32_t *n);
+const uint8_t           *str_er_result_run_costs(const str_er_result *r, uint64_t *n_bytes);
+const double            *str_er_result_run_probs(const str_er_result *r, uint64_t *n_values);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

@@ -72,6 +72,14 @@ WANT_LINE_WORDS = 1048576
 # output option: every glyph run read by the OCR scorer (needs WANT_LINE_WORDS and an SVM model of dim 1800; Result.run_reads /
 # run_features / word_text / words_text_of_line / frame_line_text; the contract is at str_er_run_read in include/str_er.h)
 WANT_RUN_READ = 2097152
+# output option: every word matched against the lexicon of set_lexicon (needs WANT_RUN_READ and a lexicon; Result.word_matches /
+# run_costs / run_probs / word_match_text / words_match_text_of_line / frame_line_match_text; the contract is at str_er_word_match)
+WANT_WORD_MATCH = 4194304
+LEXICON_FOLD_CASE = 1
+# str_er_word_match: per word, the best and the second-best lexicon entry with their costs (-1: none), the cost of the word's own
+# reading and the number of entries tried
+WORD_MATCH_DTYPE = np.dtype([("entry", "<i4"), ("cost", "<i4"), ("second_entry", "<i4"), ("second_cost", "<i4"), ("free_cost", "<i4"), ("n_tried", "<i4")])
+assert WORD_MATCH_DTYPE.itemsize == 24
 # str_er_run_read: per glyph run, the scorer's label, its character (str_er_ocr_char) and pv[label]
 RUN_READ_DTYPE = np.dtype([("label", "<i4"), ("ch", "<i4"), ("prob", "<f8")])
 assert RUN_READ_DTYPE.itemsize == 16
@@ -330,6 +338,21 @@ def load_library():
     L.str_er_result_run_reads.restype = vp
     L.str_er_result_run_features.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.str_er_result_run_features.restype = vp
+    L.str_er_set_lexicon.argtypes = [vp, vp, vp, C.c_int32, C.c_uint32]
+    L.str_er_lexicon_info.argtypes = [vp, i32p, C.POINTER(C.c_uint32), i32p, C.POINTER(C.c_uint64)]
+    L.str_er_set_word_match.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.str_er_cost_thresholds.argtypes = [vp]
+    L.str_er_cost_thresholds.restype = None
+    L.str_er_prob_costs.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp]
+    L.str_er_run_costs.argtypes = [vp, vp, C.c_int32, vp]
+    L.str_er_match_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp]
+    L.str_er_match_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.str_er_result_word_matches.argtypes = [vp, i32p]
+    L.str_er_result_word_matches.restype = vp
+    L.str_er_result_run_costs.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_result_run_costs.restype = vp
+    L.str_er_result_run_probs.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_result_run_probs.restype = vp
     L.str_er_ocr_char.argtypes = [C.c_int32]
     L.str_er_ocr_char.restype = C.c_int32
     L.str_er_feet_read.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p, vp, C.c_int32, i32p, vp, vp]
@@ -472,6 +495,10 @@ class Result:
         self._words = None
         self._run_reads = None     # with WANT_RUN_READ: the tables behind run_reads / run_features
         self._run_features = None
+        self._word_matches = None  # with WANT_WORD_MATCH: the tables behind word_matches / run_costs / run_probs, and the lexicon's words
+        self._run_costs = None
+        self._run_probs = None
+        self._lexicon = ()
         self._planes = None
 
     def _line_words_table(self, table):
@@ -536,6 +563,41 @@ class Result:
     def frame_line_text(self, i: int) -> str:
         """With WANT_RUN_READ: the text of frame line i: the words of its representative line joined by one blank."""
         return " ".join(self.words_text_of_line(int(self.frame_lines[i]["rep"])))
+
+    def _word_match_table(self, table):
+        if table is None:
+            raise ValueError("the result has no word matches (pass WANT_WORD_MATCH / want_word_match=True)")
+        return table
+
+    @property
+    def word_matches(self) -> np.ndarray:
+        """With WANT_WORD_MATCH: WORD_MATCH_DTYPE per word of words, in the same order."""
+        return self._word_match_table(self._word_matches)
+
+    @property
+    def run_costs(self) -> np.ndarray:
+        """With WANT_WORD_MATCH: (n runs, 65) uint8, the cost row of every glyph run of line_runs."""
+        return self._word_match_table(self._run_costs)
+
+    @property
+    def run_probs(self) -> np.ndarray:
+        """With WANT_WORD_MATCH: (n runs, nr_class) float64, the class probabilities of every glyph run in the model's class order."""
+        return self._word_match_table(self._run_probs)
+
+    def word_match_text(self, w: int) -> str:
+        """With WANT_WORD_MATCH: the lexicon entry that matches word w best, as it was given to set_lexicon; word_text(w) for a
+        word without a match."""
+        e = int(self.word_matches[w]["entry"])
+        return self._lexicon[e] if 0 <= e < len(self._lexicon) else self.word_text(w)
+
+    def words_match_text_of_line(self, t: int) -> list:
+        """With WANT_WORD_MATCH: word_match_text of the words of line t, left to right."""
+        lw = self.line_words[t]
+        return [self.word_match_text(w) for w in range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))]
+
+    def frame_line_match_text(self, i: int) -> str:
+        """With WANT_WORD_MATCH: the matched text of frame line i: words_match_text_of_line of its representative joined by one blank."""
+        return " ".join(self.words_match_text_of_line(int(self.frame_lines[i]["rep"])))
 
     def _line_geom_table(self, table):
         if table is None:
@@ -834,6 +896,13 @@ class ERFilter:
                         res._run_reads = table(L.str_er_result_run_reads, RUN_READ_DTYPE)
                         if res._run_reads is not None:
                             res._run_features = table(L.str_er_result_run_features, np.uint8, n64).reshape(-1, 1800)
+                            res._word_matches = table(L.str_er_result_word_matches, WORD_MATCH_DTYPE)
+                            if res._word_matches is not None:
+                                nr = len(res._run_reads)
+                                res._run_costs = table(L.str_er_result_run_costs, np.uint8, n64).reshape(nr, 65)
+                                pr = table(L.str_er_result_run_probs, np.float64, n64)
+                                res._run_probs = pr.reshape(nr, len(pr) // nr if nr else 0)
+                                res._lexicon = tuple(getattr(self, "_lexicon", ()))
                     res._line_links = table(L.str_er_result_line_links, LINE_LINK_DTYPE)
                     if res._line_links is not None:
                         res._line_tracks = table(L.str_er_result_line_tracks, np.int32)
@@ -898,7 +967,7 @@ class ERFilter:
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
                     want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -911,7 +980,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -1033,7 +1102,7 @@ class ERFilter:
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
                          want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -1041,7 +1110,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1249,6 +1318,46 @@ class ERFilter:
     def set_word_gap(self, num: int = 1, den: int = 3) -> None:
         """str_er_set_word_gap: a gap between glyph runs breaks a word when gap * den >= num * colmax (1 <= num, den <= 65535)."""
         self._check(self.L.str_er_set_word_gap(self.h, int(num), int(den)))
+
+    def set_lexicon(self, words, fold_case: bool = True) -> None:
+        """str_er_set_lexicon: the lexicon of the word matcher (str_er_word_match): strings (or bytes) of 1 .. 32 characters of the
+        alphabet of ocr_char, at most 2^20 of them; an empty sequence clears it.  fold_case: compared without regard to case."""
+        self._check(_set_lexicon(self.L, self.h, words, fold_case))
+        self._lexicon = _lexicon_strings(words)
+
+    def lexicon_info(self) -> dict:
+        """str_er_lexicon_info: the entries and flags of the lexicon, the matcher's chunk size in entries, its bytes on the device."""
+        n, fl, ch, by = C.c_int32(), C.c_uint32(), C.c_int32(), C.c_uint64()
+        self._check(self.L.str_er_lexicon_info(self.h, C.byref(n), C.byref(fl), C.byref(ch), C.byref(by)))
+        return {"n": int(n.value), "flags": int(fl.value), "chunk_entries": int(ch.value), "device_bytes": int(by.value)}
+
+    def set_word_match(self, ins: int = 64, dele: int = 64, band: int = 2) -> None:
+        """str_er_set_word_match: INS, DEL (1 .. 255) and the band (0 .. 31) of the word matcher."""
+        self._check(self.L.str_er_set_word_match(self.h, int(ins), int(dele), int(band)))
+
+    def run_costs(self, prob: np.ndarray) -> np.ndarray:
+        """str_er_run_costs: the cost rows (n, 65) uint8 of (n, nr_class) class probabilities, on the GPU, with the labels of the
+        loaded SVM model and the fold-case flag of the lexicon."""
+        p = np.ascontiguousarray(prob, dtype=np.float64)
+        k = self.svm_info()[0]
+        if p.ndim != 2 or (k and p.shape[1] != k):
+            raise ValueError("prob must be (n, nr_class)")
+        out = np.zeros((len(p), 65), np.uint8)
+        self._check(self.L.str_er_run_costs(self.h, _np_ptr(p) if p.size else None, len(p), _np_ptr(out) if len(p) else None))
+        return out
+
+    def match_words(self, costs: np.ndarray, first_run, n_runs_of_word) -> np.ndarray:
+        """str_er_match_words: the words [first_run[w], first_run[w] + n_runs_of_word[w]) of the cost rows (n runs, 65) uint8
+        against the lexicon; WORD_MATCH_DTYPE per word."""
+        cs = np.ascontiguousarray(costs, dtype=np.uint8).reshape(-1, 65)
+        fr = np.ascontiguousarray(first_run, dtype=np.int32).reshape(-1)
+        no = np.ascontiguousarray(n_runs_of_word, dtype=np.int32).reshape(-1)
+        if len(fr) != len(no):
+            raise ValueError("first_run and n_runs_of_word: one value per word each")
+        out = np.zeros(max(1, len(fr)), WORD_MATCH_DTYPE)
+        self._check(self.L.str_er_match_words(self.h, _np_ptr(cs) if len(cs) else None, len(cs), _np_ptr(fr) if len(fr) else None,
+                                              _np_ptr(no) if len(no) else None, len(fr), _np_ptr(out)))
+        return out[:len(fr)]
 
     def feet_words(self, W: int, H: int, feet: np.ndarray, bits: np.ndarray):
         """str_er_feet_words: the glyph runs and words (str_er_line_run) of footprints in the pixels of one (H, W) frame, the runs made
@@ -1489,11 +1598,70 @@ def _owned(ptr, n: int, dtype) -> np.ndarray:
     return np.frombuffer((C.c_char * (dtype.itemsize * n)).from_address(ptr), dtype=dtype).copy()
 
 
+def _lexicon_bytes(words):
+    """(bytes back to back, int32 offsets of n + 1 values) of a sequence of strings or bytes."""
+    enc = [w.encode("latin-1", "replace") if isinstance(w, str) else bytes(w) for w in words]
+    off = np.zeros(len(enc) + 1, np.int64)
+    np.cumsum([len(e) for e in enc], out=off[1:])
+    if len(off) and off[-1] > 2 ** 31 - 1:
+        raise ValueError("lexicon too large")
+    return b"".join(enc), off.astype(np.int32)
+
+
+def _lexicon_strings(words) -> tuple:
+    return tuple(w if isinstance(w, str) else bytes(w).decode("latin-1") for w in words)
+
+
+def _set_lexicon(L, ctx, words, fold_case: bool) -> int:
+    words = list(words)
+    raw, off = _lexicon_bytes(words)
+    buf = np.frombuffer(raw, np.uint8) if raw else np.zeros(1, np.uint8)
+    return L.str_er_set_lexicon(ctx, _np_ptr(buf), _np_ptr(off), len(words), LEXICON_FOLD_CASE if fold_case else 0)
+
+
+def cost_thresholds() -> np.ndarray:
+    """str_er_cost_thresholds (pure host): the 255 thresholds T of str_er_word_match."""
+    out = np.zeros(255, np.float64)
+    load_library().str_er_cost_thresholds(_np_ptr(out))
+    return out
+
+
+def prob_costs(prob: np.ndarray, labels, fold: bool = False) -> np.ndarray:
+    """str_er_prob_costs (pure host): the cost rows (n, 65) uint8 of (n, k) class probabilities of a model with the k labels."""
+    p = np.ascontiguousarray(prob, dtype=np.float64)
+    lab = np.ascontiguousarray(labels, dtype=np.int32).reshape(-1)
+    if p.ndim != 2 or p.shape[1] != len(lab):
+        raise ValueError("prob must be (n, k) with k labels")
+    out = np.zeros((len(p), 65), np.uint8)
+    rc = load_library().str_er_prob_costs(_np_ptr(p) if p.size else None, len(p), len(lab), _np_ptr(lab) if len(lab) else None, 1 if fold else 0,
+                                          _np_ptr(out) if len(p) else None)
+    if rc != 0:
+        raise StrErError(rc, "str_er_prob_costs")
+    return out
+
+
+def match_words_host(costs: np.ndarray, first_run, n_runs_of_word, words, fold_case: bool = True, ins: int = 64, dele: int = 64, band: int = 2) -> np.ndarray:
+    """str_er_match_words_host (pure host, one thread): ERFilter.match_words with the lexicon and the parameters as arguments."""
+    cs = np.ascontiguousarray(costs, dtype=np.uint8).reshape(-1, 65)
+    fr = np.ascontiguousarray(first_run, dtype=np.int32).reshape(-1)
+    no = np.ascontiguousarray(n_runs_of_word, dtype=np.int32).reshape(-1)
+    words = list(words)
+    raw, off = _lexicon_bytes(words)
+    buf = np.frombuffer(raw, np.uint8) if raw else np.zeros(1, np.uint8)
+    out = np.zeros(max(1, len(fr)), WORD_MATCH_DTYPE)
+    rc = load_library().str_er_match_words_host(_np_ptr(cs) if len(cs) else None, len(cs), _np_ptr(fr) if len(fr) else None, _np_ptr(no) if len(no) else None,
+                                                len(fr), _np_ptr(buf), _np_ptr(off), len(words), LEXICON_FOLD_CASE if fold_case else 0, int(ins), int(dele),
+                                                int(band), _np_ptr(out))
+    if rc != 0:
+        raise StrErError(rc, "str_er_match_words_host")
+    return out[:len(fr)]
+
+
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -1818,6 +1986,23 @@ class FrameStream:
             if self.L.str_er_load_svm_model(ctx, path.encode(), dim) != 0:
                 raise StrErError(-6, (self.L.str_er_last_error(ctx) or b"").decode())
 
+    def set_lexicon(self, words, fold_case: bool = True) -> None:
+        """str_er_set_lexicon on every context of the stream (str_er_stream_context): what WANT_WORD_MATCH submissions need."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = _set_lexicon(self.L, ctx, words, fold_case)
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+        self._lexicon = _lexicon_strings(words)
+
+    def set_word_match(self, ins: int = 64, dele: int = 64, band: int = 2) -> None:
+        """str_er_set_word_match on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_word_match(ctx, int(ins), int(dele), int(band))
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
     def acquire(self):
         """(slot, uint8 view of the pinned staging buffer)."""
         slot, buf, cap = C.c_int32(), C.c_void_p(), C.c_int64()
@@ -1826,21 +2011,24 @@ class FrameStream:
         arr = np.frombuffer((C.c_uint8 * cap.value).from_address(buf.value), dtype=np.uint8)
         return slot.value, arr
 
-    def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
+    def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
+               want_word_match: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit(self.h, slot, w, h, 3 * w, 3 * w * h, n_frames, stages, C.byref(t)))
         return int(t.value)
 
-    def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
+    def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
+               want_word_match: bool = False) -> int:
         """The staging buffer holds n_frames tightly packed NV12 frames (w * h * 3 / 2 bytes each)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_nv12(self.h, slot, w, h, w, w * (h + h // 2), n_frames, stages, C.byref(t)))
         return int(t.value)
 
-    def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
+    def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
+               want_word_match: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         if a.ndim == 3:
             a = a[None]
@@ -1857,19 +2045,22 @@ class FrameStream:
         self._check(fn(self.h, slot, arr, len(refs), stages, C.byref(t)))
         return int(t.value)
 
-    def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
+    def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
+               want_word_match: bool = False) -> int:
         """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
         return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
 
-    def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
+    def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
+               want_word_match: bool = False) -> int:
         """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
         return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
 
-    def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False) -> int:
+    def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
+               want_word_match: bool = False) -> int:
         """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         arr = (ImageRef * max(1, len(refs)))(*refs)
@@ -1888,4 +2079,5 @@ class FrameStream:
         shim = object.__new__(ERFilter)
         shim.L = self.L
         shim.h = None
+        shim._lexicon = getattr(self, "_lexicon", ())
         return int(t.value), ERFilter._collect(shim, rh, profile={})

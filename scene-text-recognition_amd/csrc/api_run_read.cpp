@@ -2,17 +2,26 @@
 // api_frame_lines.cpp, str_er_feet_read on uploaded footprints; the contract is at str_er_run_read in str_er.h).  Only the host knows
 // the compacted runs, so after the line stage's wait it lays their tiles out in an atlas (pack_run_tiles, words_host.cpp), k_run_tiles
 // expands the footprint words still in c->foot_bits into it, and the scorer's launch chain reads the atlas as a device plane
-// (run_read_stage: a second enqueue and wait).
+// (run_read_stage: a second enqueue and wait).  With STR_ER_WANT_WORD_MATCH the scorer also leaves its class probabilities, and k_run_costs and
+// the matcher (word_match_kernels.h) follow it on the same stream; their tables come down with the same wait.
 #include "str_er_ctx.h"
 
 namespace str_er_host {
 
 int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
-                   const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q)
+                   const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q,
+                   const WordMatchOut *match)
 {
     const size_t n = runs.size();
     if (reads) reads->assign(n, str_er_run_read{});
     q.assign(1800 * n, 0);
+    const bool   wmatch = match && reads;
+    const size_t n_words = wmatch ? match->words->size() : 0;
+    if (wmatch) {
+        match->matches->assign(n_words, str_er_word_match{-1, -1, -1, -1, 0, 0});
+        match->costs->assign(65 * n, 0);
+        match->probs->assign((size_t)c->svm.k * n, 0.0);
+    }
     if (n == 0) return STR_ER_OK;
     if (n > 0x7FFFFFFFull / 1800) return fail(c, STR_ER_ECAPACITY, "run read: too many glyph runs");
     std::vector<RunTile> tiles(n);
@@ -50,9 +59,19 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         ++c->n_atlas_grown;
     }
     if ((rc = c->run_tab.ensure(c, tab_bytes, "run tile tables")) != STR_ER_OK ||
-        (rc = ensure_scratch(c, ocr_layout(nullptr, n, m, true, false, false).bytes)) != STR_ER_OK)
+        (rc = ensure_scratch(c, ocr_layout(nullptr, n, m, true, false, wmatch).bytes)) != STR_ER_OK)
         return rc;
-    const OcrBuf buf = ocr_layout(c->scratch.d(), n, m, true, false, false);
+    const OcrBuf buf = ocr_layout(c->scratch.d(), n, m, true, false, wmatch);
+    WmTab WH{}, WD{};
+    if (wmatch) {
+        if (n > 0x7FFFFFFFull / 65 || n_words > 0x7FFFFFFFull) return fail(c, STR_ER_ECAPACITY, "word match: too many glyph runs");
+        for (const str_er_line_word &w : *match->words)
+            if (w.first_run < 0 || w.n_runs < 0 || (size_t)w.first_run + (size_t)w.n_runs > n)
+                return fail(c, STR_ER_EHIP, "word match: a word outside the glyph runs (internal error)");
+        const int n_chunks = wm_chunks(c->lex);
+        if ((rc = c->wm_tab.ensure(c, wm_layout(nullptr, n, n_words, n_chunks).bytes, "word match tables")) != STR_ER_OK) return rc;
+        WH = wm_layout(c->wm_tab.h(), n, n_words, n_chunks); WD = wm_layout(c->wm_tab.d(), n, n_words, n_chunks);
+    }
     uint8_t *h = c->run_tab.h(), *d = c->run_tab.d();
     std::memcpy(h, tiles.data(), sizeof(RunTile) * n);
     std::memcpy(h + o_box, boxes.data(), 16 * n);
@@ -64,6 +83,13 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     src.rot = reinterpret_cast<const RotGeom *>(d + o_rot);
     launch_ocr_features(s, src, (int)n, buf, m);
     if (m) launch_svm_score(s, (int)n, buf, *m, true);
+    if (wmatch) {
+        for (size_t w = 0; w < n_words; ++w) { WH.first[w] = (*match->words)[w].first_run; WH.n_of[w] = (*match->words)[w].n_runs; }
+        const size_t o_first = (size_t)(reinterpret_cast<uint8_t *>(WH.first) - c->wm_tab.h());
+        if (n_words > 0) HIP_TRY(c, hipMemcpyAsync(c->wm_tab.d() + o_first, c->wm_tab.h() + o_first, WH.up_bytes - o_first, hipMemcpyHostToDevice, s));
+        launch_run_costs(s, buf.prob, (int)n, m->k, m->label, c->lex.fold != 0, WD.costs);
+        launch_word_match(s, c->lex, c->wm_prm, WD.costs, WD.first, WD.n_of, (int)n_words, WD.partial, WD.matches);
+    }
     HIP_TRY(c, hipGetLastError());
     std::vector<int32_t> label(reads ? n : 0);
     std::vector<double>  prob(reads ? n : 0);
@@ -72,6 +98,11 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     if (reads) {
         HIP_TRY(c, hipMemcpyAsync(label.data(), buf.label, 4 * n, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(prob.data(), buf.pbest, 8 * n, hipMemcpyDeviceToHost, s));
+    }
+    if (wmatch) {
+        if (n_words > 0) HIP_TRY(c, hipMemcpyAsync(match->matches->data(), WD.matches, sizeof(str_er_word_match) * n_words, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(match->costs->data(), WD.costs, 65 * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, hipMemcpyAsync(match->probs->data(), buf.prob, 8 * (size_t)m->k * n, hipMemcpyDeviceToHost, s));
     }
     HIP_TRY(c, wait_stream(c, s));
     if (reads)

@@ -21,14 +21,20 @@ struct StageVerdict {
     const char *msg;      // why (null when OK)
 };
 
-// cascades: both cascades loaded; svm1800: an SVM model loaded with dim = 1800.  The first rule that fails decides; the call's shape comes first.
-inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades, bool svm1800)
+// cascades: both cascades loaded; svm1800: an SVM model loaded with dim = 1800; lexicon: a lexicon set (str_er_set_lexicon).  The first rule that
+// fails decides; the call's shape comes first.
+inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades, bool svm1800, bool lexicon = false)
 {
     auto any = [st](uint32_t f) { return (st & f) != 0; };
     const uint32_t maps = STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP, crops = STR_ER_WANT_LINE_CROPS | STR_ER_WANT_LINE_GLYPHS;
     const uint32_t sup = STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP;
     struct Rule { bool bad; int code; const char *msg; };
     const Rule rules[] = {
+        // STR_ER_WANT_WORD_MATCH rides on STR_ER_WANT_RUN_READ: refused without it and where it is refused, first of all, so that the
+        // refusal names this flag (its lexicon rule is with the models' below); a call without the flag meets no new rule
+        {k.strip && any(STR_ER_WANT_WORD_MATCH), STR_ER_EINVAL, "STR_ER_WANT_WORD_MATCH is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_WORD_MATCH), STR_ER_EINVAL, "STR_ER_WANT_WORD_MATCH needs frames (not the per-plane calls)"},
+        {any(STR_ER_WANT_WORD_MATCH) && !any(STR_ER_WANT_RUN_READ), STR_ER_EINVAL, "STR_ER_WANT_WORD_MATCH needs STR_ER_WANT_RUN_READ"},
         // STR_ER_WANT_RUN_READ rides on STR_ER_WANT_LINE_WORDS: refused without it and where it is refused, with a message that names
         // this flag (its model rule is with STR_ER_STAGE_OCR_LINES' below); a call without the flag meets no new rule
         {k.strip && any(STR_ER_WANT_RUN_READ), STR_ER_EINVAL, "STR_ER_WANT_RUN_READ is not supported by the strip path (str_er_strip_merge)"},
@@ -78,6 +84,7 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
          "STR_ER_STAGE_OCR_LINES needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)"},
         {any(STR_ER_WANT_RUN_READ) && !svm1800, STR_ER_ESTATE,
          "STR_ER_WANT_RUN_READ needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)"},
+        {any(STR_ER_WANT_WORD_MATCH) && !lexicon, STR_ER_ESTATE, "STR_ER_WANT_WORD_MATCH needs a lexicon (str_er_set_lexicon)"},
         {any(STR_ER_STAGE_TRACK) && !k.all_planes, STR_ER_EINVAL, "STR_ER_STAGE_TRACK needs BGR frames (calc_color reads the YCrCb image)"},
     };
     for (const Rule &r : rules)

@@ -1,7 +1,7 @@
 // str_er_ctx.h -- INTERNAL: the context / result structs and the small host helpers shared by the translation units of the C ABI
 // (str_er_api.cpp: contexts, batches, the detect entry points, results; api_models.cpp: cascade / libsvm models and the OCR entry points;
 //  api_strips.cpp: one plane in strips over several GPUs; api_stages.cpp: the single-stage entry points; api_text_map.cpp / api_frame_lines.cpp: the
-//  frame maps and the frame lines; api_run_read.cpp: the reading of the glyph runs; lines_host.cpp / words_host.cpp: the host side of the
+//  frame maps and the frame lines; api_run_read.cpp: the reading of the glyph runs; api_word_match.cpp: the lexicon matcher; lines_host.cpp / words_host.cpp: the host side of the
 //  line stage that touches no device).  Not installed, not part of the ABI.
 // The helpers in the unnamed namespace are small and private to each translation unit; what one unit defines for the others is declared in str_er_host.
 #pragma once
@@ -24,6 +24,7 @@
 #include "er_kernels.h"
 #include "ocr_kernels.h"
 #include "track_kernels.h"
+#include "word_match_kernels.h"
 #include "er_group.h"
 #include "flood_order.h"
 #include "stage_rules.h"
@@ -151,6 +152,10 @@ struct str_er_result {
     std::vector<str_er_run_read> run_reads;      // STR_ER_WANT_RUN_READ: per run of line_runs, and their 1800 feature bytes each
     std::vector<uint8_t> run_features;
     bool have_run_reads = false;
+    std::vector<str_er_word_match> word_matches; // STR_ER_WANT_WORD_MATCH: per word of words, and the cost rows and class probabilities of the runs
+    std::vector<uint8_t> run_costs;
+    std::vector<double> run_probs;
+    bool have_word_matches = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -272,6 +277,12 @@ struct str_er_ctx {
     DevBuf   run_atlas;               // the byte tiles of the runs of a call (k_run_tiles), in shelves (pack_run_tiles)
     PairBuf  run_tab;                 // tiles | boxes | rotations of the runs
     uint64_t n_atlas_grown = 0;       // statistics: how often run_atlas was allocated or grown (str_er_run_atlas_stats)
+    // STR_ER_WANT_WORD_MATCH / str_er_set_lexicon / str_er_match_words / str_er_run_costs
+    DevBuf   lexicon;                 // length tables | goff | index | chars of the padded lexicon (lex.n_groups > 0: one is set)
+    WmLexDev lex{};
+    int32_t  lex_n = 0; uint32_t lex_flags = 0;
+    WmParams wm_prm{64, 64, 2};
+    PairBuf  wm_tab;                  // cost rows | first run, run count per word | chunk keys | matches
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -327,7 +338,7 @@ int fail(str_er_ctx *c, int code, const std::string &msg)
 // the flags of a detect call against its shape and the context's state (stage_rules.h): before the call stages or enqueues anything
 int check_call(str_er_ctx *c, uint32_t stages, const CallShape &k)
 {
-    const StageVerdict v = check_stages(stages, k, c->casc[0].loaded && c->casc[1].loaded, c->svm_loaded && c->svm.dim == 1800);
+    const StageVerdict v = check_stages(stages, k, c->casc[0].loaded && c->casc[1].loaded, c->svm_loaded && c->svm.dim == 1800, c->lex_n > 0);
     return v.code == STR_ER_OK ? STR_ER_OK : fail(c, v.code, v.msg);
 }
 
@@ -547,6 +558,7 @@ struct LineStageWants {
     bool geom = false;        // STR_ER_WANT_LINE_GEOM: the geometry of the lines and frame lines of r (k_foot_geom)
     bool words = false;       // STR_ER_WANT_LINE_WORDS: the glyph runs and words of the lines of r (k_foot_words)
     bool read = false;        // STR_ER_WANT_RUN_READ: the reading of every run (k_run_tiles and the scorer behind the stage's wait, with a wait of their own)
+    bool match = false;       // STR_ER_WANT_WORD_MATCH: every word against the lexicon (k_run_costs and the matcher behind the scorer)
 };
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
                       str_er_result *r, const LineStageWants &want);
@@ -560,8 +572,25 @@ int feet_words_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot 
 // the tiles laid out and expanded into the atlas, then the scorer's launch chain on the atlas as a device plane with one box a run and
 // the slope of the run's line (slopes: one per line, or null: all 0; a slope that is not finite counts as 0).  One upload, the
 // launches, the copies back and a wait of its own on s.  reads == null: the features only (no model needed).
+// match (optional, with reads): STR_ER_WANT_WORD_MATCH -- k_run_costs and the matcher behind the scorer on s, their tables back with the
+// same wait: the words of `words` against the context's lexicon, the cost rows and the class probabilities of the runs
+struct WordMatchOut {
+    const std::vector<str_er_line_word> *words;
+    std::vector<str_er_word_match> *matches;
+    std::vector<uint8_t> *costs;
+    std::vector<double> *probs;
+};
 int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
-                   const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q);
+                   const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q,
+                   const WordMatchOut *match = nullptr);
+// ---- defined in api_word_match.cpp
+// the layout of c->wm_tab for n_runs cost rows and n_words words (base: either side of the pair, or null for the size alone)
+struct WmTab {
+    uint8_t *costs; int32_t *first, *n_of; uint64_t *partial; str_er_word_match *matches;
+    size_t up_bytes;        // costs | first | n_of lie at the front: what a caller's input takes
+    size_t o_matches, bytes;
+};
+WmTab wm_layout(uint8_t *base, size_t n_runs, size_t n_words, int n_chunks);
 // ---- defined in words_host.cpp and lines_host.cpp (HIP-free)
 bool word_gap_ok(int32_t num, int32_t den);       // what str_er_set_word_gap takes
 // inter * den >= num * (pa + pb - inter): footprints of pa and pb pixels, inter of them common, are duplicates (links) at num / den

@@ -568,6 +568,70 @@ public:
         return {std::move(lw), std::move(rd)};
     }
 
+    // Every word matched against a lexicon (STR_ER_WANT_WORD_MATCH; the contract is at str_er_word_match in include/str_er.h): one record
+    // per word of LineWords::words, the 65 cost bytes of every run and its class probabilities (probs.size() / n runs a run).  Needs
+    // STR_ER_WANT_RUN_READ and a lexicon in the context.
+    struct WordMatches {
+        std::vector<str_er_word_match> matches;
+        std::vector<uint8_t>           costs;
+        std::vector<double>            probs;
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static WordMatches word_matches(const str_er_result *r)
+    {
+        WordMatches out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_word_match *p = str_er_result_word_matches(r, &n)) out.matches.assign(p, p + n);
+        if (const uint8_t *p = str_er_result_run_costs(r, &nb)) out.costs.assign(p, p + nb);
+        if (const double *p = str_er_result_run_probs(r, &nb)) out.probs.assign(p, p + nb);
+        return out;
+    }
+    // the lexicon of the matcher: words of 1 .. 32 characters of the alphabet of str_er_ocr_char, at most 2^20; none clears it
+    void set_lexicon(const std::vector<std::string> &words, bool fold_case = true)
+    {
+        std::string          bytes;
+        std::vector<int32_t> offsets{0};
+        for (const std::string &w : words) {
+            bytes += w;
+            if (bytes.size() > (size_t)INT32_MAX) throw std::invalid_argument("set_lexicon: too many bytes");
+            offsets.push_back((int32_t)bytes.size());
+        }
+        check(str_er_set_lexicon(ctx_.get(), bytes.data(), offsets.data(), (int32_t)words.size(), fold_case ? STR_ER_LEXICON_FOLD_CASE : 0u));
+    }
+    // INS, DEL (1 .. 255) and the band (0 .. 31) of the matcher (str_er_set_word_match; 64, 64, 2 by default)
+    void set_word_match(int32_t ins, int32_t del, int32_t band) { check(str_er_set_word_match(ctx_.get(), ins, del, band)); }
+    // the cost rows (65 bytes a run) of n x nr_class class probabilities, with the labels of the loaded model (str_er_run_costs)
+    std::vector<uint8_t> run_costs(const std::vector<double> &prob, int32_t n)
+    {
+        std::vector<uint8_t> out(65 * (size_t)(n > 0 ? n : 0));
+        check(str_er_run_costs(ctx_.get(), prob.empty() ? nullptr : prob.data(), n, out.empty() ? nullptr : out.data()));
+        return out;
+    }
+    // the words [first_run[w], first_run[w] + n_runs[w]) of the caller's cost rows against the lexicon (str_er_match_words)
+    std::vector<str_er_word_match> match_words(const std::vector<uint8_t> &costs, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs)
+    {
+        if (first_run.size() != n_runs.size() || costs.size() % 65) throw std::invalid_argument("match_words: 65 bytes a run, one span a word");
+        std::vector<str_er_word_match> out(first_run.size());
+        check(str_er_match_words(ctx_.get(), costs.empty() ? nullptr : costs.data(), (int32_t)(costs.size() / 65), first_run.empty() ? nullptr : first_run.data(),
+                                 n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(), out.empty() ? nullptr : out.data()));
+        return out;
+    }
+    // the matched string of word w: the lexicon entry (as given in `lexicon`) that matches it best, its own reading where none does
+    static std::string word_match_text(const LineWords &lw, const RunReads &rd, const WordMatches &wm, const std::vector<std::string> &lexicon, size_t w)
+    {
+        const int32_t e = wm.matches.at(w).entry;
+        return e >= 0 && (size_t)e < lexicon.size() ? lexicon[(size_t)e] : word_text(lw, rd, w);
+    }
+    // the matched text of line t: its words' matched strings joined by one blank
+    static std::string line_match_text(const LineWords &lw, const RunReads &rd, const WordMatches &wm, const std::vector<std::string> &lexicon, size_t t)
+    {
+        std::string s;
+        const str_er_line_words &L = lw.lines.at(t);
+        for (int32_t k = L.first_word; k < L.first_word + L.n_words; ++k) s += (k > L.first_word ? " " : "") + word_match_text(lw, rd, wm, lexicon, (size_t)k);
+        return s;
+    }
+
     // The text lines of consecutive frames linked into text tracks (STR_ER_WANT_LINE_LINKS; the contract is at str_er_line_link in
     // include/str_er.h): the overlaps across adjacent frames, the track of every line of str_er_result_texts(), the tracks, the line
     // indices their first / count index, and the footprints of the lines of the first ([0]) and of the last frame ([1]).
