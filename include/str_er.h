@@ -135,6 +135,13 @@ extern "C" {
  * that flag is refused, and a lexicon: STR_ER_ESTATE without one; the context is usable afterwards.  Every call that honours
  * _RUN_READ honours it.  It changes no other output of the call and combines with every other STR_ER_WANT_* flag.                  */
 #define STR_ER_WANT_WORD_MATCH (4194304u)
+/* output option: every word of STR_ER_WANT_RUN_READ decoded under the bigram table of str_er_set_bigram: the cheapest character string
+ * per word with the run every character came from (str_er_result_word_decodes / _word_decode_chars / _word_decode_src); the cost rows
+ * and class probabilities of the runs come with it (str_er_result_run_costs / _run_probs); the contract is at str_er_word_decode.
+ * Needs STR_ER_WANT_RUN_READ: STR_ER_EINVAL without it and wherever that flag is refused, and a table: STR_ER_ESTATE without one; the
+ * context is usable afterwards.  It needs no lexicon.  Every call that honours _RUN_READ honours it.  It changes no other output of
+ * the call and combines with every other STR_ER_WANT_* flag; beside STR_ER_WANT_WORD_MATCH the run costs stay the matcher's.        */
+#define STR_ER_WANT_WORD_DECODE (8388608u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -458,9 +465,10 @@ typedef struct str_er_line_words {
  *   String of a word: the characters of runs[first_run .. first_run + n_runs).  Text of a frame line: the words of its representative
  *     joined by one blank.
  *   Limits: the string of a word is the arg max of its runs: in it there is no spelling correction and no language model (the
- *     reference's word graph, bigram table and corrector are not rebuilt), and a run of touching glyphs reads as one character: runs
+ *     reference's word graph and corrector are not rebuilt), and a run of touching glyphs reads as one character: runs
  *     are not split in the image.  The match of a word against a lexicon, which may spend a character without a run of its own or a
- *     run without a character, is a separate output: str_er_word_match (STR_ER_WANT_WORD_MATCH).                                    */
+ *     run without a character, is a separate output: str_er_word_match (STR_ER_WANT_WORD_MATCH); so is the cheapest string of a word
+ *     under a character bigram table, with the same two moves: str_er_word_decode (STR_ER_WANT_WORD_DECODE).                        */
 typedef struct str_er_run_read {
     int32_t  label;          /*  0: the scorer's label                                */
     int32_t  ch;             /*  4: str_er_ocr_char(label)                            */
@@ -495,6 +503,40 @@ typedef struct str_er_word_match {
     int32_t  free_cost, n_tried;          /* 16, 20                                   */
 } str_er_word_match;         /* 24 bytes; one per word of str_er_result_words()       */
 #define STR_ER_LEXICON_FOLD_CASE 1u
+
+/* The decoding of a word under a character bigram table (STR_ER_WANT_WORD_DECODE, str_er_decode_words): the cheapest character string
+ * of a word under the cost rows of its glyph runs plus a table of costs of one character after another, which may drop a run (a speck)
+ * or spend a character that has no run of its own (touching glyphs), the two moves of str_er_word_match.  A definition of this
+ * library; integers only, exact, and the host states the same rules (str_er_decode_words_host).
+ *   Symbols: the 65 characters of str_er_ocr_char with their labels 0 .. 64, and 65 = E, the word boundary ("no character yet", "end
+ *     of word").
+ *   Table: B, 66 x 66 bytes, row-major, in the unit of the cost rows (1/8 bit): B[a][b] the cost of b directly after a, B[E][b] of
+ *     beginning with b, B[a][E] of ending on a, B[E][E] of the empty word (str_er_set_bigram; str_er_bigram_from_probs makes one).
+ *   Cost rows: the 65-byte rows of str_er_word_match, never folded: case matters to a bigram table.
+ *   Moves: INS and DEL in 0 .. 255, 0 switches a move off; both are 0 by default (str_er_set_word_decode): a plain Viterbi pass, one
+ *     character per run.
+ *   Recurrence, for a word with the runs 1 .. m, m <= 32, in int32 with INF = 2^20: V_0[E] = 0, V_0[a] = INF for a < 65.  For
+ *     i = 1 .. m: SUB, for b < 65: S[b] = min over a in 0 .. 65 of (V_{i-1}[a] + B[a][b]) + C_i[b], the predecessor the smallest a
+ *     that attains the minimum; U[b] = S[b], U[E] = INF.  DEL, if DEL > 0, for a in 0 .. 65: D = V_{i-1}[a] + DEL; if D < U[a] then
+ *     U[a] = D and the move is DEL (on a tie SUB stays).  INS, if INS > 0, for c < 65: I = min over b in 0 .. 64 of (U[b] + B[b][c])
+ *     + INS, with the smallest b; if I < U[c] then V_i[c] = I and the move is INS, else V_i[c] = U[c]; always V_i[E] = U[E].  So at
+ *     most one character is inserted after a run, and only after some character.  cost = min over a in 0 .. 65 of V_m[a] + B[a][E],
+ *     with the smallest a; for m = 0 that is B[E][E].  INF is never the minimum.
+ *   String: the backtrack from the end state by the recorded moves.  At (i, c) an INS move emits c with the source (i-1) | 0x80 and
+ *     goes to the U-level state b; a SUB move emits b with the source i-1 and goes to (i-1, predecessor); a DEL move emits nothing
+ *     and goes to (i-1, a).  Reversed: at most 2m <= 64 labels, each with the word-relative index of the run it came from, bit 7 set
+ *     on an inserted character.  Per word 64 bytes of labels and 64 bytes of sources, padded with 0xFF past n_chars.
+ *   Record: read_cost is the cost under B of the plain reading -- the first arg min of every row, all SUB, with the boundary terms --
+ *     and is made for every m.  Hence cost <= read_cost, n_sub + n_ins = n_chars and n_sub + n_del = m.  A word with m > 32 is not
+ *     decoded: cost = -1 and the four counts are 0.
+ *   Limits: runs are not split in the image; one path per word, no margins; the table is the caller's.  The bridge from a table of
+ *     transition probabilities (str_er_bigram_from_probs) takes 65 x 65 doubles as P(b after a); whether the floats of the
+ *     reference's dictionary/tp_table.txt are such probabilities has not been checked, and nothing beyond that reading is promised. */
+typedef struct str_er_word_decode {
+    int32_t  cost, read_cost;             /*  0,  4                                   */
+    int32_t  n_chars, n_sub;              /*  8, 12                                   */
+    int32_t  n_del, n_ins;                /* 16, 20                                   */
+} str_er_word_decode;        /* 24 bytes; one per word of str_er_result_words()       */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -822,6 +864,28 @@ int str_er_match_words(str_er_ctx *ctx, const uint8_t *costs, int32_t n_runs, co
 int str_er_match_words_host(const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, const char *bytes,
                             const int32_t *offsets, int32_t n, uint32_t flags, int32_t ins, int32_t del, int32_t band, str_er_word_match *matches);
 
+/* The bigram table of the context (str_er_word_decode): 66 * 66 bytes, copied.  NULL removes the table.  The call waits for the
+ * context's work.  A stream's contexts: str_er_stream_context.                                                                     */
+int str_er_set_bigram(str_er_ctx *ctx, const uint8_t *cost);
+/* Whether a table is set (1 / 0) and the bytes it takes on the device (0 without one).  Either pointer may be NULL.                 */
+int str_er_bigram_info(const str_er_ctx *ctx, int32_t *set, uint64_t *device_bytes);
+/* INS and DEL (0 .. 255, 0: the move is off) of str_er_word_decode; defaults 0, 0.  Anything else -> STR_ER_EINVAL, the context
+ * unchanged.  A stream's contexts: str_er_stream_context.                                                                          */
+int str_er_set_word_decode(str_er_ctx *ctx, int32_t ins, int32_t del);
+/* A table from probabilities: out[a][b] = cost(tp[a * 65 + b]) with the cost() of str_er_word_match, tp taken as P(b after a);
+ * out[E][b] = cost(start[b]) and out[a][E] = cost(end[a]), 0 where start / end is NULL; out[E][E] = 0.  Pure: no context, no GPU.
+ * STR_ER_EINVAL on a NULL tp or out.  (See the limits at str_er_word_decode for what is known of the reference's tp_table.txt.)      */
+int str_er_bigram_from_probs(const double *tp, const double *start, const double *end, uint8_t out[4356]);
+/* The decoder on the caller's cost rows: costs holds n_runs rows of 65 bytes, word w has the rows first_run[w] .. first_run[w] +
+ * n_runs_of_word[w]; dec receives n_words records, chars and src 64 bytes per word each.  STR_ER_ESTATE without a table;
+ * STR_ER_EINVAL on a word outside the rows.  n_words = 0 is fine.  It needs no SVM model and no lexicon.                             */
+int str_er_decode_words(str_er_ctx *ctx, const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
+                        str_er_word_decode *dec, uint8_t *chars, uint8_t *src);
+/* The same rules on one host thread, with the table and INS / DEL as arguments (with the checks of str_er_set_word_decode).  Pure:
+ * no context, no GPU.                                                                                                              */
+int str_er_decode_words_host(const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
+                             const uint8_t *bigram, int32_t ins, int32_t del, str_er_word_decode *dec, uint8_t *chars, uint8_t *src);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -1054,6 +1118,13 @@ const uint8_t           *str_er_result_run_features(const str_er_result *r, uint
 const str_er_word_match *str_er_result_word_matches(const str_er_result *r, int32_t *n);
 const uint8_t           *str_er_result_run_costs(const str_er_result *r, uint64_t *n_bytes);
 const double            *str_er_result_run_probs(const str_er_result *r, uint64_t *n_values);
+/* With STR_ER_WANT_WORD_DECODE (str_er_word_decode): one record per word of str_er_result_words() and 64 label bytes and 64 source
+ * bytes per word; str_er_result_run_costs and _run_probs are filled with this flag too: the unfolded rows, unless
+ * STR_ER_WANT_WORD_MATCH is set as well, when they stay the matcher's (folded as its lexicon says).  Each returns NULL and 0 without
+ * the flag; a call without words returns empty arrays (not NULL).                                                                  */
+const str_er_word_decode *str_er_result_word_decodes(const str_er_result *r, int32_t *n);
+const uint8_t            *str_er_result_word_decode_chars(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t            *str_er_result_word_decode_src(const str_er_result *r, uint64_t *n_bytes);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

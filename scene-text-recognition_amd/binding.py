@@ -76,6 +76,14 @@ WANT_RUN_READ = 2097152
 # run_costs / run_probs / word_match_text / words_match_text_of_line / frame_line_match_text; the contract is at str_er_word_match)
 WANT_WORD_MATCH = 4194304
 LEXICON_FOLD_CASE = 1
+# output option: every word decoded under the bigram table of set_bigram (needs WANT_RUN_READ and a table, no lexicon;
+# Result.word_decodes / word_decode_chars / word_decode_src / word_decode_text / word_decode_runs / words_decode_text_of_line /
+# frame_line_decode_text, and run_costs / run_probs; the contract is at str_er_word_decode)
+WANT_WORD_DECODE = 8388608
+# str_er_word_decode: per word, the cost of the cheapest string (-1: more than 32 runs, not decoded) and of the plain reading, the
+# characters of the string and the runs read, dropped and the characters inserted
+WORD_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
+assert WORD_DECODE_DTYPE.itemsize == 24
 # str_er_word_match: per word, the best and the second-best lexicon entry with their costs (-1: none), the cost of the word's own
 # reading and the number of entries tried
 WORD_MATCH_DTYPE = np.dtype([("entry", "<i4"), ("cost", "<i4"), ("second_entry", "<i4"), ("second_cost", "<i4"), ("free_cost", "<i4"), ("n_tried", "<i4")])
@@ -353,6 +361,18 @@ def load_library():
     L.str_er_result_run_costs.restype = vp
     L.str_er_result_run_probs.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.str_er_result_run_probs.restype = vp
+    L.str_er_set_bigram.argtypes = [vp, vp]
+    L.str_er_bigram_info.argtypes = [vp, i32p, C.POINTER(C.c_uint64)]
+    L.str_er_set_word_decode.argtypes = [vp, C.c_int32, C.c_int32]
+    L.str_er_bigram_from_probs.argtypes = [vp, vp, vp, vp]
+    L.str_er_decode_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]
+    L.str_er_decode_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp]
+    L.str_er_result_word_decodes.argtypes = [vp, i32p]
+    L.str_er_result_word_decodes.restype = vp
+    L.str_er_result_word_decode_chars.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_result_word_decode_chars.restype = vp
+    L.str_er_result_word_decode_src.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_result_word_decode_src.restype = vp
     L.str_er_ocr_char.argtypes = [C.c_int32]
     L.str_er_ocr_char.restype = C.c_int32
     L.str_er_feet_read.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p, vp, C.c_int32, i32p, vp, vp]
@@ -499,6 +519,9 @@ class Result:
         self._run_costs = None
         self._run_probs = None
         self._lexicon = ()
+        self._word_decodes = None  # with WANT_WORD_DECODE: the tables behind word_decodes / word_decode_chars / word_decode_src (and run_costs / run_probs)
+        self._word_decode_chars = None
+        self._word_decode_src = None
         self._planes = None
 
     def _line_words_table(self, table):
@@ -569,6 +592,51 @@ class Result:
             raise ValueError("the result has no word matches (pass WANT_WORD_MATCH / want_word_match=True)")
         return table
 
+    def _word_decode_table(self, table):
+        if table is None:
+            raise ValueError("the result has no word decodes (pass WANT_WORD_DECODE / want_word_decode=True)")
+        return table
+
+    @property
+    def word_decodes(self) -> np.ndarray:
+        """With WANT_WORD_DECODE: WORD_DECODE_DTYPE per word of words, in the same order."""
+        return self._word_decode_table(getattr(self, "_word_decodes", None))
+
+    @property
+    def word_decode_chars(self) -> np.ndarray:
+        """With WANT_WORD_DECODE: (n words, 64) uint8, the labels of every word's string, 0xFF past n_chars."""
+        return self._word_decode_table(getattr(self, "_word_decode_chars", None))
+
+    @property
+    def word_decode_src(self) -> np.ndarray:
+        """With WANT_WORD_DECODE: (n words, 64) uint8, per character the word-relative index of the run it came from, bit 7 set on an
+        inserted character; 0xFF past n_chars."""
+        return self._word_decode_table(getattr(self, "_word_decode_src", None))
+
+    def word_decode_text(self, w: int) -> str:
+        """With WANT_WORD_DECODE: the decoded string of word w; word_text(w) for a word that was not decoded (cost < 0)."""
+        d = self.word_decodes[w]
+        if int(d["cost"]) < 0:
+            return self.word_text(w)
+        return "".join(_OCR_ALPHABET[int(a)] for a in self.word_decode_chars[w, :int(d["n_chars"])])
+
+    def word_decode_runs(self, w: int) -> list:
+        """With WANT_WORD_DECODE: per character of word_decode_text(w), (index into line_runs of the run it came from, whether it
+        was inserted behind that run); for a word that was not decoded its runs, none inserted."""
+        d, first = self.word_decodes[w], int(self.words[w]["first_run"])
+        if int(d["cost"]) < 0:
+            return [(first + k, False) for k in range(int(self.words[w]["n_runs"]))]
+        return [(first + (int(v) & 0x7F), bool(int(v) & 0x80)) for v in self.word_decode_src[w, :int(d["n_chars"])]]
+
+    def words_decode_text_of_line(self, t: int) -> list:
+        """With WANT_WORD_DECODE: word_decode_text of the words of line t, left to right."""
+        lw = self.line_words[t]
+        return [self.word_decode_text(w) for w in range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))]
+
+    def frame_line_decode_text(self, i: int) -> str:
+        """With WANT_WORD_DECODE: the decoded text of frame line i: words_decode_text_of_line of its representative joined by one blank."""
+        return " ".join(self.words_decode_text_of_line(int(self.frame_lines[i]["rep"])))
+
     @property
     def word_matches(self) -> np.ndarray:
         """With WANT_WORD_MATCH: WORD_MATCH_DTYPE per word of words, in the same order."""
@@ -576,12 +644,13 @@ class Result:
 
     @property
     def run_costs(self) -> np.ndarray:
-        """With WANT_WORD_MATCH: (n runs, 65) uint8, the cost row of every glyph run of line_runs."""
+        """With WANT_WORD_MATCH or WANT_WORD_DECODE: (n runs, 65) uint8, the cost row of every glyph run of line_runs (folded as the
+        lexicon says with WANT_WORD_MATCH, else unfolded)."""
         return self._word_match_table(self._run_costs)
 
     @property
     def run_probs(self) -> np.ndarray:
-        """With WANT_WORD_MATCH: (n runs, nr_class) float64, the class probabilities of every glyph run in the model's class order."""
+        """With WANT_WORD_MATCH or WANT_WORD_DECODE: (n runs, nr_class) float64, the class probabilities of every glyph run in the model's class order."""
         return self._word_match_table(self._run_probs)
 
     def word_match_text(self, w: int) -> str:
@@ -897,7 +966,11 @@ class ERFilter:
                         if res._run_reads is not None:
                             res._run_features = table(L.str_er_result_run_features, np.uint8, n64).reshape(-1, 1800)
                             res._word_matches = table(L.str_er_result_word_matches, WORD_MATCH_DTYPE)
-                            if res._word_matches is not None:
+                            res._word_decodes = table(L.str_er_result_word_decodes, WORD_DECODE_DTYPE)
+                            if res._word_decodes is not None:
+                                res._word_decode_chars = table(L.str_er_result_word_decode_chars, np.uint8, n64).reshape(-1, 64)
+                                res._word_decode_src = table(L.str_er_result_word_decode_src, np.uint8, n64).reshape(-1, 64)
+                            if res._word_matches is not None or res._word_decodes is not None:
                                 nr = len(res._run_reads)
                                 res._run_costs = table(L.str_er_result_run_costs, np.uint8, n64).reshape(nr, 65)
                                 pr = table(L.str_er_result_run_probs, np.float64, n64)
@@ -967,7 +1040,7 @@ class ERFilter:
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
                     want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -980,7 +1053,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -1102,7 +1175,7 @@ class ERFilter:
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
                          want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -1110,7 +1183,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1358,6 +1431,29 @@ class ERFilter:
         self._check(self.L.str_er_match_words(self.h, _np_ptr(cs) if len(cs) else None, len(cs), _np_ptr(fr) if len(fr) else None,
                                               _np_ptr(no) if len(no) else None, len(fr), _np_ptr(out)))
         return out[:len(fr)]
+
+    def set_bigram(self, table) -> None:
+        """str_er_set_bigram: the (66, 66) uint8 table of the word decoder (str_er_word_decode; bigram_from_probs / bigram_from_words
+        make one); None removes it."""
+        self._check(self.L.str_er_set_bigram(self.h, None if table is None else _np_ptr(_bigram_table(table))))
+
+    def bigram_info(self) -> dict:
+        """str_er_bigram_info: whether a table is set and its bytes on the device."""
+        st, by = C.c_int32(), C.c_uint64()
+        self._check(self.L.str_er_bigram_info(self.h, C.byref(st), C.byref(by)))
+        return {"set": bool(st.value), "device_bytes": int(by.value)}
+
+    def set_word_decode(self, ins: int = 0, dele: int = 0) -> None:
+        """str_er_set_word_decode: INS and DEL (0 .. 255, 0: off) of the word decoder."""
+        self._check(self.L.str_er_set_word_decode(self.h, int(ins), int(dele)))
+
+    def decode_words(self, costs: np.ndarray, first_run, n_runs_of_word):
+        """str_er_decode_words: the words [first_run[w], first_run[w] + n_runs_of_word[w]) of the cost rows (n runs, 65) uint8 under
+        the table; (WORD_DECODE_DTYPE per word, (n, 64) uint8 labels, (n, 64) uint8 sources)."""
+        cs, fr, no, out, ch, sr = _decode_args(costs, first_run, n_runs_of_word)
+        self._check(self.L.str_er_decode_words(self.h, _np_ptr(cs) if len(cs) else None, len(cs), _np_ptr(fr) if len(fr) else None,
+                                               _np_ptr(no) if len(no) else None, len(fr), _np_ptr(out), _np_ptr(ch), _np_ptr(sr)))
+        return out[:len(fr)], ch[:len(fr)], sr[:len(fr)]
 
     def feet_words(self, W: int, H: int, feet: np.ndarray, bits: np.ndarray):
         """str_er_feet_words: the glyph runs and words (str_er_line_run) of footprints in the pixels of one (H, W) frame, the runs made
@@ -1657,11 +1753,88 @@ def match_words_host(costs: np.ndarray, first_run, n_runs_of_word, words, fold_c
     return out[:len(fr)]
 
 
+def _bigram_table(table) -> np.ndarray:
+    t = np.ascontiguousarray(table, dtype=np.uint8)
+    if t.size != 66 * 66:
+        raise ValueError("a bigram table is (66, 66) uint8")
+    return t.reshape(66, 66)
+
+
+def _decode_args(costs, first_run, n_runs_of_word):
+    cs = np.ascontiguousarray(costs, dtype=np.uint8).reshape(-1, 65)
+    fr = np.ascontiguousarray(first_run, dtype=np.int32).reshape(-1)
+    no = np.ascontiguousarray(n_runs_of_word, dtype=np.int32).reshape(-1)
+    if len(fr) != len(no):
+        raise ValueError("first_run and n_runs_of_word: one value per word each")
+    n = max(1, len(fr))
+    return cs, fr, no, np.zeros(n, WORD_DECODE_DTYPE), np.full((n, 64), 0xFF, np.uint8), np.full((n, 64), 0xFF, np.uint8)
+
+
+def bigram_from_probs(tp, start=None, end=None) -> np.ndarray:
+    """str_er_bigram_from_probs (pure host): the (66, 66) uint8 table of (65, 65) probabilities tp[a][b] = P(b after a), with the
+    boundary row from start (65) and the boundary column from end (65), 0 where they are None."""
+    t = np.ascontiguousarray(tp, dtype=np.float64)
+    if t.size != 65 * 65:
+        raise ValueError("tp must be (65, 65)")
+    st = None if start is None else np.ascontiguousarray(start, dtype=np.float64).reshape(65)
+    en = None if end is None else np.ascontiguousarray(end, dtype=np.float64).reshape(65)
+    out = np.zeros((66, 66), np.uint8)
+    rc = load_library().str_er_bigram_from_probs(_np_ptr(t), None if st is None else _np_ptr(st), None if en is None else _np_ptr(en), _np_ptr(out))
+    if rc != 0:
+        raise StrErError(rc, "str_er_bigram_from_probs")
+    return out
+
+
+_OCR_ALPHABET = "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz&()"
+
+
+def bigram_from_words(words, alpha: float = 1.0) -> np.ndarray:
+    """A (66, 66) uint8 table from a word list: the counts of every character pair of the words, with the word boundary as the
+    66th symbol (before the first and after the last character), plus alpha everywhere, every row normalised to probabilities, then
+    cost() of str_er_word_match.  The entry [65][65] (the empty word) is 0.  Characters outside the alphabet of ocr_char raise."""
+    label = {ch: a for a, ch in enumerate(_OCR_ALPHABET)}
+    cnt = np.full((66, 66), float(alpha), np.float64)
+    for w in words:
+        w = w if isinstance(w, str) else bytes(w).decode("latin-1")
+        prev = 65
+        for ch in w:
+            if ch not in label:
+                raise ValueError(f"bigram_from_words: {ch!r} is outside the alphabet")
+            cnt[prev, label[ch]] += 1
+            prev = label[ch]
+        if w:
+            cnt[prev, 65] += 1
+    tot = cnt.sum(axis=1, keepdims=True)
+    p = np.divide(cnt, tot, out=np.zeros_like(cnt), where=tot > 0)
+    return bigram_from_probs(p[:65, :65], p[65, :65], p[:65, 65])
+
+
+def load_tp_table(path: str) -> np.ndarray:
+    """The (66, 66) uint8 table of a text file of 65 x 65 numbers in row order (the layout of the reference's
+    dictionary/tp_table.txt), taken as P(b after a); the boundary row and column are 0.  Whether the reference's file holds such
+    probabilities has not been checked (str_er_word_decode, Limits)."""
+    with open(path) as fh:
+        v = np.array(fh.read().split(), dtype=np.float64)
+    if v.size != 65 * 65:
+        raise ValueError(f"{path}: expected 65 x 65 numbers, found {v.size}")
+    return bigram_from_probs(v.reshape(65, 65))
+
+
+def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: int = 0, dele: int = 0):
+    """str_er_decode_words_host (pure host, one thread): ERFilter.decode_words with the table and the parameters as arguments."""
+    cs, fr, no, out, ch, sr = _decode_args(costs, first_run, n_runs_of_word)
+    rc = load_library().str_er_decode_words_host(_np_ptr(cs) if len(cs) else None, len(cs), _np_ptr(fr) if len(fr) else None, _np_ptr(no) if len(no) else None,
+                                                 len(fr), _np_ptr(_bigram_table(table)), int(ins), int(dele), _np_ptr(out), _np_ptr(ch), _np_ptr(sr))
+    if rc != 0:
+        raise StrErError(rc, "str_er_decode_words_host")
+    return out[:len(fr)], ch[:len(fr)], sr[:len(fr)]
+
+
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -2003,6 +2176,23 @@ class FrameStream:
             if rc != 0:
                 raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
 
+    def set_bigram(self, table) -> None:
+        """str_er_set_bigram on every context of the stream: what WANT_WORD_DECODE submissions need."""
+        t = None if table is None else _bigram_table(table)
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_bigram(ctx, None if t is None else _np_ptr(t))
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
+    def set_word_decode(self, ins: int = 0, dele: int = 0) -> None:
+        """str_er_set_word_decode on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_word_decode(ctx, int(ins), int(dele))
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
     def acquire(self):
         """(slot, uint8 view of the pinned staging buffer)."""
         slot, buf, cap = C.c_int32(), C.c_void_p(), C.c_int64()
@@ -2012,23 +2202,23 @@ class FrameStream:
         return slot.value, arr
 
     def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
+               want_word_match: bool = False, want_word_decode: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit(self.h, slot, w, h, 3 * w, 3 * w * h, n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False) -> int:
         """The staging buffer holds n_frames tightly packed NV12 frames (w * h * 3 / 2 bytes each)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_nv12(self.h, slot, w, h, w, w * (h + h // 2), n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
+               want_word_match: bool = False, want_word_decode: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         if a.ndim == 3:
             a = a[None]
@@ -2046,21 +2236,21 @@ class FrameStream:
         return int(t.value)
 
     def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False) -> int:
         """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
         return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
 
     def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False) -> int:
         """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
         return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
 
     def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False) -> int:
         """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         arr = (ImageRef * max(1, len(refs)))(*refs)

@@ -695,7 +695,7 @@ int fill_geometry(str_er_ctx *c, str_er_result *r, const GeomPass &GP)
 
 // the runs and words of the lines (what k_foot_words left), and with read the reading of every run: T.lines is the table k_foot_words
 // read, and its footprints are still in c->foot_bits
-int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match)
+int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode)
 {
     const auto   t2 = std::chrono::steady_clock::now();
     const size_t n_lines = r->line_feet.size();
@@ -705,11 +705,14 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         std::vector<double> slopes(n_lines);
         for (size_t t = 0; t < n_lines; ++t) slopes[t] = r->texts[t].slope;
         const WordMatchOut wmo{&r->words, &r->word_matches, &r->run_costs, &r->run_probs};
-        if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features, match ? &wmo : nullptr);
+        const WordDecodeOut wdo{&r->words, &r->word_decodes, &r->word_decode_chars, &r->word_decode_src, &r->run_costs, &r->run_probs};
+        if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features, match ? &wmo : nullptr,
+                                           decode ? &wdo : nullptr);
             rcr != STR_ER_OK)
             return rcr;
         r->have_run_reads = true;
         r->have_word_matches = match;
+        r->have_word_decodes = decode;
     }
     if (c->dbg_stats)        // developer aid (tools/dev_line_words.py)
         std::fprintf(stderr, "[str_er] line words: %zu lines, %zu run slots reserved, %zu runs, %zu words, %zu bytes back, host %.3f ms\n", n_lines,
@@ -749,7 +752,7 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
     if ((rc = fill_frame_lines(c, r, frame_of, pyr_of, S.feet.pairs, n_fl)) != STR_ER_OK) return rc;
     if (want.links && (rc = fill_links(c, b, r, frame_of, T, S.links)) != STR_ER_OK) return rc;
     if (want.geom && (rc = fill_geometry(c, r, S.geom)) != STR_ER_OK) return rc;
-    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match)) != STR_ER_OK) return rc;
+    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode)) != STR_ER_OK) return rc;
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
                              "%zu bytes back, host %.3f ms before + %.3f ms after the device\n",

@@ -3,14 +3,16 @@
 // the compacted runs, so after the line stage's wait it lays their tiles out in an atlas (pack_run_tiles, words_host.cpp), k_run_tiles
 // expands the footprint words still in c->foot_bits into it, and the scorer's launch chain reads the atlas as a device plane
 // (run_read_stage: a second enqueue and wait).  With STR_ER_WANT_WORD_MATCH the scorer also leaves its class probabilities, and k_run_costs and
-// the matcher (word_match_kernels.h) follow it on the same stream; their tables come down with the same wait.
+// the matcher (word_match_kernels.h) follow it on the same stream; their tables come down with the same wait.  With STR_ER_WANT_WORD_DECODE
+// the decoder (word_decode_kernels.h) follows in the same way, on unfolded cost rows: the matcher's where its lexicon does not fold, else
+// those of a second k_run_costs into the decoder's own buffer.
 #include "str_er_ctx.h"
 
 namespace str_er_host {
 
 int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
                    const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q,
-                   const WordMatchOut *match)
+                   const WordMatchOut *match, const WordDecodeOut *decode)
 {
     const size_t n = runs.size();
     if (reads) reads->assign(n, str_er_run_read{});
@@ -21,6 +23,17 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         match->matches->assign(n_words, str_er_word_match{-1, -1, -1, -1, 0, 0});
         match->costs->assign(65 * n, 0);
         match->probs->assign((size_t)c->svm.k * n, 0.0);
+    }
+    const bool   wdecode = decode && reads;
+    const size_t n_dwords = wdecode ? decode->words->size() : 0;
+    if (wdecode) {
+        decode->decodes->assign(n_dwords, str_er_word_decode{});
+        decode->chars->assign(64 * n_dwords, 0xFF);
+        decode->src->assign(64 * n_dwords, 0xFF);
+        if (!wmatch) {
+            decode->costs->assign(65 * n, 0);
+            decode->probs->assign((size_t)c->svm.k * n, 0.0);
+        }
     }
     if (n == 0) return STR_ER_OK;
     if (n > 0x7FFFFFFFull / 1800) return fail(c, STR_ER_ECAPACITY, "run read: too many glyph runs");
@@ -59,9 +72,9 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         ++c->n_atlas_grown;
     }
     if ((rc = c->run_tab.ensure(c, tab_bytes, "run tile tables")) != STR_ER_OK ||
-        (rc = ensure_scratch(c, ocr_layout(nullptr, n, m, true, false, wmatch).bytes)) != STR_ER_OK)
+        (rc = ensure_scratch(c, ocr_layout(nullptr, n, m, true, false, wmatch || wdecode).bytes)) != STR_ER_OK)
         return rc;
-    const OcrBuf buf = ocr_layout(c->scratch.d(), n, m, true, false, wmatch);
+    const OcrBuf buf = ocr_layout(c->scratch.d(), n, m, true, false, wmatch || wdecode);
     WmTab WH{}, WD{};
     if (wmatch) {
         if (n > 0x7FFFFFFFull / 65 || n_words > 0x7FFFFFFFull) return fail(c, STR_ER_ECAPACITY, "word match: too many glyph runs");
@@ -71,6 +84,15 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         const int n_chunks = wm_chunks(c->lex);
         if ((rc = c->wm_tab.ensure(c, wm_layout(nullptr, n, n_words, n_chunks).bytes, "word match tables")) != STR_ER_OK) return rc;
         WH = wm_layout(c->wm_tab.h(), n, n_words, n_chunks); WD = wm_layout(c->wm_tab.d(), n, n_words, n_chunks);
+    }
+    WdTab DH{}, DD{};
+    if (wdecode) {
+        if (n > 0x7FFFFFFFull / 65 || n_dwords > 0x7FFFFFFFull / 64) return fail(c, STR_ER_ECAPACITY, "word decode: too many glyph runs");
+        for (const str_er_line_word &w : *decode->words)
+            if (w.first_run < 0 || w.n_runs < 0 || (size_t)w.first_run + (size_t)w.n_runs > n)
+                return fail(c, STR_ER_EHIP, "word decode: a word outside the glyph runs (internal error)");
+        if ((rc = c->wd_tab.ensure(c, wd_layout(nullptr, n, n_dwords).bytes, "word decode tables")) != STR_ER_OK) return rc;
+        DH = wd_layout(c->wd_tab.h(), n, n_dwords); DD = wd_layout(c->wd_tab.d(), n, n_dwords);
     }
     uint8_t *h = c->run_tab.h(), *d = c->run_tab.d();
     std::memcpy(h, tiles.data(), sizeof(RunTile) * n);
@@ -90,6 +112,14 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         launch_run_costs(s, buf.prob, (int)n, m->k, m->label, c->lex.fold != 0, WD.costs);
         launch_word_match(s, c->lex, c->wm_prm, WD.costs, WD.first, WD.n_of, (int)n_words, WD.partial, WD.matches);
     }
+    const uint8_t *dcosts = wmatch && !c->lex.fold ? WD.costs : DD.costs;          // (the decoder's rows are never folded)
+    if (wdecode) {
+        for (size_t w = 0; w < n_dwords; ++w) { DH.first[w] = (*decode->words)[w].first_run; DH.n_of[w] = (*decode->words)[w].n_runs; }
+        const size_t o_first = (size_t)(reinterpret_cast<uint8_t *>(DH.first) - c->wd_tab.h());
+        if (n_dwords > 0) HIP_TRY(c, hipMemcpyAsync(c->wd_tab.d() + o_first, c->wd_tab.h() + o_first, DH.up_bytes - o_first, hipMemcpyHostToDevice, s));
+        if (dcosts == DD.costs) launch_run_costs(s, buf.prob, (int)n, m->k, m->label, false, DD.costs);
+        launch_word_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, dcosts, DD.first, DD.n_of, (int)n_dwords, DD.dec, DD.chars, DD.src);
+    }
     HIP_TRY(c, hipGetLastError());
     std::vector<int32_t> label(reads ? n : 0);
     std::vector<double>  prob(reads ? n : 0);
@@ -103,6 +133,17 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         if (n_words > 0) HIP_TRY(c, hipMemcpyAsync(match->matches->data(), WD.matches, sizeof(str_er_word_match) * n_words, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(match->costs->data(), WD.costs, 65 * n, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(match->probs->data(), buf.prob, 8 * (size_t)m->k * n, hipMemcpyDeviceToHost, s));
+    }
+    if (wdecode) {
+        if (n_dwords > 0) {
+            HIP_TRY(c, hipMemcpyAsync(decode->decodes->data(), DD.dec, sizeof(str_er_word_decode) * n_dwords, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(decode->chars->data(), DD.chars, 64 * n_dwords, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(decode->src->data(), DD.src, 64 * n_dwords, hipMemcpyDeviceToHost, s));
+        }
+        if (!wmatch) {
+            HIP_TRY(c, hipMemcpyAsync(decode->costs->data(), dcosts, 65 * n, hipMemcpyDeviceToHost, s));
+            HIP_TRY(c, hipMemcpyAsync(decode->probs->data(), buf.prob, 8 * (size_t)m->k * n, hipMemcpyDeviceToHost, s));
+        }
     }
     HIP_TRY(c, wait_stream(c, s));
     if (reads)

@@ -21,15 +21,20 @@ struct StageVerdict {
     const char *msg;      // why (null when OK)
 };
 
-// cascades: both cascades loaded; svm1800: an SVM model loaded with dim = 1800; lexicon: a lexicon set (str_er_set_lexicon).  The first rule that
-// fails decides; the call's shape comes first.
-inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades, bool svm1800, bool lexicon = false)
+// cascades: both cascades loaded; svm1800: an SVM model loaded with dim = 1800; lexicon: a lexicon set (str_er_set_lexicon); bigram: a bigram
+// table set (str_er_set_bigram).  The first rule that fails decides; the call's shape comes first.
+inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades, bool svm1800, bool lexicon = false, bool bigram = false)
 {
     auto any = [st](uint32_t f) { return (st & f) != 0; };
     const uint32_t maps = STR_ER_WANT_TEXT_MAP | STR_ER_WANT_LINE_MAP, crops = STR_ER_WANT_LINE_CROPS | STR_ER_WANT_LINE_GLYPHS;
     const uint32_t sup = STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP;
     struct Rule { bool bad; int code; const char *msg; };
     const Rule rules[] = {
+        // STR_ER_WANT_WORD_DECODE rides on STR_ER_WANT_RUN_READ as STR_ER_WANT_WORD_MATCH does (its table rule is with the models' below);
+        // a call without the flag meets no new rule
+        {k.strip && any(STR_ER_WANT_WORD_DECODE), STR_ER_EINVAL, "STR_ER_WANT_WORD_DECODE is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_WORD_DECODE), STR_ER_EINVAL, "STR_ER_WANT_WORD_DECODE needs frames (not the per-plane calls)"},
+        {any(STR_ER_WANT_WORD_DECODE) && !any(STR_ER_WANT_RUN_READ), STR_ER_EINVAL, "STR_ER_WANT_WORD_DECODE needs STR_ER_WANT_RUN_READ"},
         // STR_ER_WANT_WORD_MATCH rides on STR_ER_WANT_RUN_READ: refused without it and where it is refused, first of all, so that the
         // refusal names this flag (its lexicon rule is with the models' below); a call without the flag meets no new rule
         {k.strip && any(STR_ER_WANT_WORD_MATCH), STR_ER_EINVAL, "STR_ER_WANT_WORD_MATCH is not supported by the strip path (str_er_strip_merge)"},
@@ -85,6 +90,7 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
         {any(STR_ER_WANT_RUN_READ) && !svm1800, STR_ER_ESTATE,
          "STR_ER_WANT_RUN_READ needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)"},
         {any(STR_ER_WANT_WORD_MATCH) && !lexicon, STR_ER_ESTATE, "STR_ER_WANT_WORD_MATCH needs a lexicon (str_er_set_lexicon)"},
+        {any(STR_ER_WANT_WORD_DECODE) && !bigram, STR_ER_ESTATE, "STR_ER_WANT_WORD_DECODE needs a bigram table (str_er_set_bigram)"},
         {any(STR_ER_STAGE_TRACK) && !k.all_planes, STR_ER_EINVAL, "STR_ER_STAGE_TRACK needs BGR frames (calc_color reads the YCrCb image)"},
     };
     for (const Rule &r : rules)

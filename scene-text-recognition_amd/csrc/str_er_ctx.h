@@ -1,7 +1,7 @@
 // str_er_ctx.h -- INTERNAL: the context / result structs and the small host helpers shared by the translation units of the C ABI
 // (str_er_api.cpp: contexts, batches, the detect entry points, results; api_models.cpp: cascade / libsvm models and the OCR entry points;
 //  api_strips.cpp: one plane in strips over several GPUs; api_stages.cpp: the single-stage entry points; api_text_map.cpp / api_frame_lines.cpp: the
-//  frame maps and the frame lines; api_run_read.cpp: the reading of the glyph runs; api_word_match.cpp: the lexicon matcher; lines_host.cpp / words_host.cpp: the host side of the
+//  frame maps and the frame lines; api_run_read.cpp: the reading of the glyph runs; api_word_match.cpp: the lexicon matcher; api_word_decode.cpp: the bigram decoder; lines_host.cpp / words_host.cpp: the host side of the
 //  line stage that touches no device).  Not installed, not part of the ABI.
 // The helpers in the unnamed namespace are small and private to each translation unit; what one unit defines for the others is declared in str_er_host.
 #pragma once
@@ -25,6 +25,7 @@
 #include "ocr_kernels.h"
 #include "track_kernels.h"
 #include "word_match_kernels.h"
+#include "word_decode_kernels.h"
 #include "er_group.h"
 #include "flood_order.h"
 #include "stage_rules.h"
@@ -156,6 +157,9 @@ struct str_er_result {
     std::vector<uint8_t> run_costs;
     std::vector<double> run_probs;
     bool have_word_matches = false;
+    std::vector<str_er_word_decode> word_decodes; // STR_ER_WANT_WORD_DECODE: per word of words, and 64 label and 64 source bytes per word (run_costs / run_probs too)
+    std::vector<uint8_t> word_decode_chars, word_decode_src;
+    bool have_word_decodes = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -283,6 +287,11 @@ struct str_er_ctx {
     int32_t  lex_n = 0; uint32_t lex_flags = 0;
     WmParams wm_prm{64, 64, 2};
     PairBuf  wm_tab;                  // cost rows | first run, run count per word | chunk keys | matches
+    // STR_ER_WANT_WORD_DECODE / str_er_set_bigram / str_er_decode_words
+    DevBuf   bigram;                  // the 66 x 66 table (bigram_set: one is set)
+    bool     bigram_set = false;
+    int32_t  wd_ins = 0, wd_del = 0;
+    PairBuf  wd_tab;                  // cost rows | first run, run count per word | records | labels | sources
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -338,7 +347,7 @@ int fail(str_er_ctx *c, int code, const std::string &msg)
 // the flags of a detect call against its shape and the context's state (stage_rules.h): before the call stages or enqueues anything
 int check_call(str_er_ctx *c, uint32_t stages, const CallShape &k)
 {
-    const StageVerdict v = check_stages(stages, k, c->casc[0].loaded && c->casc[1].loaded, c->svm_loaded && c->svm.dim == 1800, c->lex_n > 0);
+    const StageVerdict v = check_stages(stages, k, c->casc[0].loaded && c->casc[1].loaded, c->svm_loaded && c->svm.dim == 1800, c->lex_n > 0, c->bigram_set);
     return v.code == STR_ER_OK ? STR_ER_OK : fail(c, v.code, v.msg);
 }
 
@@ -559,6 +568,7 @@ struct LineStageWants {
     bool words = false;       // STR_ER_WANT_LINE_WORDS: the glyph runs and words of the lines of r (k_foot_words)
     bool read = false;        // STR_ER_WANT_RUN_READ: the reading of every run (k_run_tiles and the scorer behind the stage's wait, with a wait of their own)
     bool match = false;       // STR_ER_WANT_WORD_MATCH: every word against the lexicon (k_run_costs and the matcher behind the scorer)
+    bool decode = false;      // STR_ER_WANT_WORD_DECODE: every word under the bigram table (k_run_costs and the decoder behind the scorer)
 };
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
                       str_er_result *r, const LineStageWants &want);
@@ -580,9 +590,18 @@ struct WordMatchOut {
     std::vector<uint8_t> *costs;
     std::vector<double> *probs;
 };
+// decode (optional, with reads): STR_ER_WANT_WORD_DECODE -- the decoder behind the scorer on s in the same way, on unfolded cost rows (a
+// second k_run_costs into wd_tab where the matcher's are folded); costs / probs are filled here only where match is null
+struct WordDecodeOut {
+    const std::vector<str_er_line_word> *words;
+    std::vector<str_er_word_decode> *decodes;
+    std::vector<uint8_t> *chars, *src;
+    std::vector<uint8_t> *costs;
+    std::vector<double> *probs;
+};
 int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
                    const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q,
-                   const WordMatchOut *match = nullptr);
+                   const WordMatchOut *match = nullptr, const WordDecodeOut *decode = nullptr);
 // ---- defined in api_word_match.cpp
 // the layout of c->wm_tab for n_runs cost rows and n_words words (base: either side of the pair, or null for the size alone)
 struct WmTab {
@@ -591,6 +610,14 @@ struct WmTab {
     size_t o_matches, bytes;
 };
 WmTab wm_layout(uint8_t *base, size_t n_runs, size_t n_words, int n_chunks);
+// ---- defined in api_word_decode.cpp
+// the layout of c->wd_tab in the same way
+struct WdTab {
+    uint8_t *costs; int32_t *first, *n_of; str_er_word_decode *dec; uint8_t *chars, *src;
+    size_t up_bytes;        // costs | first | n_of lie at the front: what a caller's input takes
+    size_t o_dec, down_bytes, bytes;      // dec | chars | src lie back to back (each aligned): one copy down
+};
+WdTab wd_layout(uint8_t *base, size_t n_runs, size_t n_words);
 // ---- defined in words_host.cpp and lines_host.cpp (HIP-free)
 bool word_gap_ok(int32_t num, int32_t den);       // what str_er_set_word_gap takes
 // inter * den >= num * (pa + pb - inter): footprints of pa and pb pixels, inter of them common, are duplicates (links) at num / den

@@ -22,6 +22,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/str_er.h"
@@ -629,6 +630,92 @@ public:
         std::string s;
         const str_er_line_words &L = lw.lines.at(t);
         for (int32_t k = L.first_word; k < L.first_word + L.n_words; ++k) s += (k > L.first_word ? " " : "") + word_match_text(lw, rd, wm, lexicon, (size_t)k);
+        return s;
+    }
+
+    // Every word decoded under a character bigram table (STR_ER_WANT_WORD_DECODE; the contract is at str_er_word_decode in
+    // include/str_er.h): one record per word of LineWords::words, 64 label bytes and 64 source bytes per word (0xFF past n_chars), and
+    // the cost bytes and class probabilities of the runs as in WordMatches.  Needs STR_ER_WANT_RUN_READ and a table in the context.
+    struct WordDecodes {
+        std::vector<str_er_word_decode> decodes;
+        std::vector<uint8_t>            chars, src;
+        std::vector<uint8_t>            costs;
+        std::vector<double>             probs;
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static WordDecodes word_decodes(const str_er_result *r)
+    {
+        WordDecodes out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_word_decode *p = str_er_result_word_decodes(r, &n)) out.decodes.assign(p, p + n);
+        if (const uint8_t *p = str_er_result_word_decode_chars(r, &nb)) out.chars.assign(p, p + nb);
+        if (const uint8_t *p = str_er_result_word_decode_src(r, &nb)) out.src.assign(p, p + nb);
+        if (const uint8_t *p = str_er_result_run_costs(r, &nb)) out.costs.assign(p, p + nb);
+        if (const double *p = str_er_result_run_probs(r, &nb)) out.probs.assign(p, p + nb);
+        return out;
+    }
+    // the table of the decoder: 66 x 66 cost bytes (str_er_set_bigram); an empty vector removes it
+    void set_bigram(const std::vector<uint8_t> &table)
+    {
+        if (!table.empty() && table.size() != 66 * 66) throw std::invalid_argument("set_bigram: 66 x 66 bytes");
+        check(str_er_set_bigram(ctx_.get(), table.empty() ? nullptr : table.data()));
+    }
+    // a table from 65 x 65 probabilities P(b after a) and, optionally, 65 of beginning with and 65 of ending on a character
+    static std::vector<uint8_t> bigram_from_probs(const std::vector<double> &tp, const std::vector<double> &start = {}, const std::vector<double> &end = {})
+    {
+        if (tp.size() != 65 * 65 || (!start.empty() && start.size() != 65) || (!end.empty() && end.size() != 65))
+            throw std::invalid_argument("bigram_from_probs: 65 x 65 probabilities, 65 start and 65 end values");
+        std::vector<uint8_t> out(66 * 66);
+        if (str_er_bigram_from_probs(tp.data(), start.empty() ? nullptr : start.data(), end.empty() ? nullptr : end.data(), out.data()) != STR_ER_OK)
+            throw std::invalid_argument("bigram_from_probs");
+        return out;
+    }
+    // INS and DEL (0 .. 255, 0: off) of the decoder (str_er_set_word_decode; 0, 0 by default)
+    void set_word_decode(int32_t ins, int32_t del) { check(str_er_set_word_decode(ctx_.get(), ins, del)); }
+    // the words [first_run[w], first_run[w] + n_runs[w]) of the caller's cost rows under the table (str_er_decode_words)
+    WordDecodes decode_words(const std::vector<uint8_t> &costs, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs)
+    {
+        if (first_run.size() != n_runs.size() || costs.size() % 65) throw std::invalid_argument("decode_words: 65 bytes a run, one span a word");
+        WordDecodes out;
+        out.decodes.resize(first_run.size());
+        out.chars.resize(64 * first_run.size());
+        out.src.resize(64 * first_run.size());
+        check(str_er_decode_words(ctx_.get(), costs.empty() ? nullptr : costs.data(), (int32_t)(costs.size() / 65), first_run.empty() ? nullptr : first_run.data(),
+                                  n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(), out.decodes.empty() ? nullptr : out.decodes.data(),
+                                  out.chars.empty() ? nullptr : out.chars.data(), out.src.empty() ? nullptr : out.src.data()));
+        return out;
+    }
+    // the decoded string of word w: its own reading where it was not decoded (more than 32 runs)
+    static std::string word_decode_text(const LineWords &lw, const RunReads &rd, const WordDecodes &wd, size_t w)
+    {
+        const str_er_word_decode &d = wd.decodes.at(w);
+        if (d.cost < 0) return word_text(lw, rd, w);
+        std::string s;
+        for (int32_t k = 0; k < d.n_chars; ++k) s += (char)str_er_ocr_char(wd.chars.at(64 * w + (size_t)k));
+        return s;
+    }
+    // per character of word_decode_text(w): the index of the run it came from in LineWords::runs, and whether it was inserted behind it
+    static std::vector<std::pair<int32_t, bool>> word_decode_runs(const LineWords &lw, const WordDecodes &wd, size_t w)
+    {
+        std::vector<std::pair<int32_t, bool>> out;
+        const str_er_word_decode &d = wd.decodes.at(w);
+        const str_er_line_word   &W = lw.words.at(w);
+        if (d.cost < 0)
+            for (int32_t k = 0; k < W.n_runs; ++k) out.emplace_back(W.first_run + k, false);
+        else
+            for (int32_t k = 0; k < d.n_chars; ++k) {
+                const uint8_t v = wd.src.at(64 * w + (size_t)k);
+                out.emplace_back(W.first_run + (v & 0x7F), (v & 0x80) != 0);
+            }
+        return out;
+    }
+    // the decoded text of line t: its words' decoded strings joined by one blank
+    static std::string line_decode_text(const LineWords &lw, const RunReads &rd, const WordDecodes &wd, size_t t)
+    {
+        std::string s;
+        const str_er_line_words &L = lw.lines.at(t);
+        for (int32_t k = L.first_word; k < L.first_word + L.n_words; ++k) s += (k > L.first_word ? " " : "") + word_decode_text(lw, rd, wd, (size_t)k);
         return s;
     }
 
