@@ -142,6 +142,14 @@ extern "C" {
  * context is usable afterwards.  It needs no lexicon.  Every call that honours _RUN_READ honours it.  It changes no other output of
  * the call and combines with every other STR_ER_WANT_* flag; beside STR_ER_WANT_WORD_MATCH the run costs stay the matcher's.        */
 #define STR_ER_WANT_WORD_DECODE (8388608u)
+/* output option: every glyph run of STR_ER_WANT_RUN_READ cut at the valleys of its column profile, every piece read, and per run the
+ * segmentation the scorer likes best (str_er_result_run_splits / _run_pieces / _piece_reads / _piece_costs / _split_parts /
+ * _word_splits; the contract is at str_er_run_split, the parameters: str_er_set_run_split).  Needs STR_ER_WANT_RUN_READ: STR_ER_EINVAL
+ * without it and wherever that flag is refused; its parameters have defaults, so it needs no further state.  Every call that honours
+ * _RUN_READ honours it.  Beside STR_ER_WANT_WORD_MATCH / _WORD_DECODE both work on the split sequence of a word instead of its runs.
+ * It changes no other output of the call -- the runs' own reads are byte for byte those of a call without it -- and combines with
+ * every other STR_ER_WANT_* flag.                                                                                                   */
+#define STR_ER_WANT_RUN_SPLIT (16777216u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -465,8 +473,8 @@ typedef struct str_er_line_words {
  *   String of a word: the characters of runs[first_run .. first_run + n_runs).  Text of a frame line: the words of its representative
  *     joined by one blank.
  *   Limits: the string of a word is the arg max of its runs: in it there is no spelling correction and no language model (the
- *     reference's word graph and corrector are not rebuilt), and a run of touching glyphs reads as one character: runs
- *     are not split in the image.  The match of a word against a lexicon, which may spend a character without a run of its own or a
+ *     reference's word graph and corrector are not rebuilt), and a run of touching glyphs reads as one character here: runs
+ *     are split in the image by a separate output, str_er_run_split (STR_ER_WANT_RUN_SPLIT).  The match of a word against a lexicon, which may spend a character without a run of its own or a
  *     run without a character, is a separate output: str_er_word_match (STR_ER_WANT_WORD_MATCH); so is the cheapest string of a word
  *     under a character bigram table, with the same two moves: str_er_word_decode (STR_ER_WANT_WORD_DECODE).                        */
 typedef struct str_er_run_read {
@@ -529,7 +537,8 @@ typedef struct str_er_word_match {
  *   Record: read_cost is the cost under B of the plain reading -- the first arg min of every row, all SUB, with the boundary terms --
  *     and is made for every m.  Hence cost <= read_cost, n_sub + n_ins = n_chars and n_sub + n_del = m.  A word with m > 32 is not
  *     decoded: cost = -1 and the four counts are 0.
- *   Limits: runs are not split in the image; one path per word, no margins; the table is the caller's.  The bridge from a table of
+ *   Limits: runs are split in the image only with STR_ER_WANT_RUN_SPLIT (str_er_run_split), then the rows are those of the word's
+ *     parts; one path per word, no margins; the table is the caller's.  The bridge from a table of
  *     transition probabilities (str_er_bigram_from_probs) takes 65 x 65 doubles as P(b after a); whether the floats of the
  *     reference's dictionary/tp_table.txt are such probabilities has not been checked, and nothing beyond that reading is promised. */
 typedef struct str_er_word_decode {
@@ -537,6 +546,65 @@ typedef struct str_er_word_decode {
     int32_t  n_chars, n_sub;              /*  8, 12                                   */
     int32_t  n_del, n_ins;                /* 16, 20                                   */
 } str_er_word_decode;        /* 24 bytes; one per word of str_er_result_words()       */
+
+/* The splitting of touching glyphs (str_er_feet_split, str_er_split_words): candidate cut columns inside a glyph run, the pieces they
+ * make, the reading of every piece, and per run the segmentation the scorer likes best (STR_ER_WANT_RUN_SPLIT).  A definition of this library, like the word
+ * gap and the reading of a run: exact integers, not tuned on labelled data; the host states the same rules (str_er_cuts_from_counts,
+ * str_er_split_words_host).
+ *   Column profile of a run r of line t with the frame columns [x0, x1) and rows [y0, y1): W = x1 - x0, H = y1 - y0, and n(c),
+ *     0 <= c < W, the number of pixels of F(t) in the frame column x0 + c (>= 1 by the definition of a run).  Only line t's own
+ *     footprint counts.
+ *   Threshold: thr = floor(H * num / den) in 64-bit integers; num / den is set with str_er_set_run_split, 1 <= num, den <= 65535,
+ *     1 / 4 by default.
+ *   Valley: a maximal interval [a, b) of columns with n(c) <= thr throughout, with a > 0 and b < W: an interval that touches either
+ *     end of the run is no valley.  Its depth d = min n(c) over the interval; its cut column p = floor((cf + cl) / 2), cf and cl the
+ *     first and the last column of the interval that attain d.  p lies in the valley and need not attain d itself.
+ *   Cuts: the valleys' cut columns; of more than 3 valleys the 3 with the smallest (d, p) are kept.  The kept cuts p_1 < .. < p_k
+ *     (k <= 3) split the run into A = k + 1 atoms [0, p_1), [p_1, p_2), .., [p_k, W).  A run with W > 1024 is not split (k = 0);
+ *     thr = 0 gives no valley.
+ *   Pieces: the nodes are 0 .. A, the piece (i, j), i < j, is the union of the atoms i .. j - 1.  (0, A) is the run itself and is not
+ *     listed again, so a cut run has A (A + 1) / 2 - 1 pieces: 2, 5 or 9, ordered by (i, j).  A piece carries its frame columns, its
+ *     pixel count and its own tight row extent over the pixels of F(t) in its columns.  The pieces of all runs lie back to back in
+ *     run order.
+ *   Reading of a piece: the definition of str_er_run_read with the piece's box as the tile: the same T(i, j) rule (0 in F(t), else
+ *     255), the line's slope, the same scorer.  The cost row of a piece is that of str_er_word_match, never folded.
+ *   Segmentation of a run: m(i, j) is the minimum of the 65 bytes of the cost row of piece (i, j), for (0, A) of the run's own row.
+ *     D[0] = 0, D[j] = min over 0 <= i < j of D[i] + m(i, j) + (i > 0 ? SPLIT : 0), the predecessor the smallest i that attains the
+ *     minimum; the parts of the run are the pieces on the backtrack from A.  SPLIT is in 0 .. 255 and 8 by default (one bit: a split
+ *     must double the product of the parts' best probabilities).  The minimum of a folded row equals that of the unfolded row, so a
+ *     lexicon's fold flag does not enter.
+ *   Split word: the parts of a word's runs in run order are its split sequence, each part (run, piece) with piece = -1 for a whole
+ *     run.  Per word: first_part and n_parts, cost = the sum of the parts' m plus the SPLIT terms, read_cost = the sum of the runs'
+ *     own minima (the matcher's free_cost).  Hence cost <= read_cost and n_parts >= n_runs.  The string of a split word is the first
+ *     arg min of the row of each part.
+ *   Limits: at most 3 cuts a run; the cut follows the upright column profile, no slanted or curved cuts; the segmentation is chosen
+ *     per run from the scorer alone, ahead of any lexicon or bigram table: there is no joint decode over the piece lattice.
+ *   Beside the matcher and the decoder: with STR_ER_WANT_RUN_SPLIT next to STR_ER_WANT_WORD_MATCH or _WORD_DECODE both run on the split
+ *     sequence instead of the runs: m in their contracts is n_parts, with the same limit of 32, and src of the decoder indexes the
+ *     word's parts.  run_costs and run_probs stay per run; the rows of the pieces (str_er_result_piece_costs) are folded where the
+ *     runs' are (a lexicon with the fold-case flag), which moves no minimum.  Without STR_ER_WANT_RUN_SPLIT nothing of theirs changes.  */
+typedef struct str_er_run_split {
+    int32_t  n_cuts;                      /*  0: 0 .. 3                               */
+    int32_t  cut[3];                      /*  4: frame columns, ascending, -1 unused  */
+    uint32_t thr;                         /* 16                                       */
+    int32_t  first_piece, n_pieces;       /* 20, 24: into the piece table             */
+    int32_t  n_parts;                     /* 28: parts of its segmentation (0 where no model ran) */
+} str_er_run_split;          /* 32 bytes; one per run                                 */
+typedef struct str_er_run_piece {
+    int32_t  run;                         /*  0: index into the run table             */
+    int32_t  from, to;                    /*  4,  8: the nodes i < j                  */
+    int32_t  x0, x1;                      /* 12, 16: frame columns, half open         */
+    int32_t  y0, y1;                      /* 20, 24: frame rows, half open            */
+    uint32_t pixels;                      /* 28                                       */
+} str_er_run_piece;          /* 32 bytes */
+typedef struct str_er_split_part {
+    int32_t  run, piece;                  /*  0,  4: piece -1: the whole run          */
+} str_er_split_part;         /*  8 bytes */
+typedef struct str_er_word_split {
+    int32_t  first_part, n_parts;         /*  0,  4: into the part table              */
+    int32_t  cost, read_cost;             /*  8, 12                                   */
+} str_er_word_split;         /* 16 bytes; one per word                                */
+#define STR_ER_RUN_SPLIT_MAX_W 1024
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -886,6 +954,42 @@ int str_er_decode_words(str_er_ctx *ctx, const uint8_t *costs, int32_t n_runs, c
 int str_er_decode_words_host(const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
                              const uint8_t *bigram, int32_t ins, int32_t del, str_er_word_decode *dec, uint8_t *chars, uint8_t *src);
 
+/* num / den of the valley threshold (1 .. 65535 each) and SPLIT (0 .. 255) of str_er_run_split; defaults 1 / 4 and 8.  Anything else
+ * -> STR_ER_EINVAL, the context unchanged.                                                                                          */
+int str_er_set_run_split(str_er_ctx *ctx, int32_t num, int32_t den, int32_t split_cost);
+/* Statistics of the buffers of STR_ER_WANT_RUN_SPLIT / str_er_feet_split / str_er_split_words: the bytes of the cut records and of the
+ * segmentation tables on the device (0: never made).  Either pointer may be NULL.                                                   */
+int str_er_run_split_stats(const str_er_ctx *ctx, uint64_t *cut_bytes, uint64_t *table_bytes);
+/* The kept cuts of one run from its column counts n[0 .. W) and its height H (str_er_run_split): cut receives the columns relative
+ * to the run, ascending, -1 unused; *n_cuts their number; *thr (optional) the threshold.  Pure: no context, no GPU.  STR_ER_EINVAL on
+ * NULL arguments, W < 1, H < 1 or num / den outside 1 .. 65535.                                                                     */
+int str_er_cuts_from_counts(const uint32_t *n, int32_t W, int32_t H, int32_t num, int32_t den, int32_t cut[3], int32_t *n_cuts, uint32_t *thr);
+/* str_er_feet_read and the cuts and pieces of every run (str_er_run_split), made on the GPU from the run slots and the footprint
+ * words: splits receives one record per run (cap_runs of them; n_parts is left 0), pieces the piece table and *n_pieces its size
+ * (pieces == NULL only counts; cap_pieces too small -> STR_ER_ECAPACITY, *n_pieces still set).  piece_reads (optional) receives the
+ * reading of every piece and piece_q (optional) its 1800 feature bytes, both for cap_pieces pieces; piece_reads needs an SVM model of
+ * dim 1800 (STR_ER_ESTATE without), cuts, pieces and piece_q need none.  splits == NULL or n_pieces == NULL -> STR_ER_EINVAL.  The
+ * other arguments, their validation and capacity codes are those of str_er_feet_read; a counting call (runs == NULL or words ==
+ * NULL) makes no cuts.  The runs' own results are those of str_er_feet_read, byte for byte.                                        */
+int str_er_feet_split(str_er_ctx *ctx, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, const double *slopes, int32_t n,
+                      str_er_line_words *line_words, str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words,
+                      int32_t cap_words, int32_t *n_words, str_er_run_read *reads, uint8_t *q_out, str_er_run_split *splits,
+                      str_er_run_piece *pieces, int32_t cap_pieces, int32_t *n_pieces, str_er_run_read *piece_reads, uint8_t *piece_q);
+/* The segmentation (str_er_run_split) of the runs of n_words words on the caller's cost rows, on the GPU: splits holds n_runs records
+ * (n_cuts, first_piece and n_pieces are read), run_costs n_runs rows of 65 bytes, piece_costs n_pieces rows; word w has the runs
+ * first_run[w] .. first_run[w] + n_runs_of_word[w].  word_splits receives n_words records, parts the split sequences of the words back
+ * to back in word order and *n_parts their number; part_costs (optional) the 65-byte rows of the parts in the same order, which
+ * str_er_match_words and str_er_decode_words take with (first_part, n_parts) as the windows.  cap_parts too small -> STR_ER_ECAPACITY,
+ * *n_parts still set (it is at most the sum over the words' runs of n_cuts + 1).  STR_ER_EINVAL on a word outside the runs, a record
+ * whose n_cuts is outside 0 .. 3, whose n_pieces does not follow from n_cuts or whose pieces lie outside the rows.  It needs no model. */
+int str_er_split_words(str_er_ctx *ctx, const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs,
+                       int32_t n_pieces, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, str_er_word_split *word_splits,
+                       str_er_split_part *parts, int32_t cap_parts, int32_t *n_parts, uint8_t *part_costs);
+/* The same rules on one host thread, with SPLIT as an argument (0 .. 255).  Pure: no context, no GPU.                               */
+int str_er_split_words_host(const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs, int32_t n_pieces,
+                            const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, int32_t split_cost,
+                            str_er_word_split *word_splits, str_er_split_part *parts, int32_t cap_parts, int32_t *n_parts, uint8_t *part_costs);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -1114,7 +1218,8 @@ const str_er_run_read   *str_er_result_run_reads(const str_er_result *r, int32_t
 const uint8_t           *str_er_result_run_features(const str_er_result *r, uint64_t *n_bytes);
 /* With STR_ER_WANT_WORD_MATCH (str_er_word_match): one record per word of str_er_result_words(), the 65 * n cost bytes of the runs
  * and their k * n class probabilities (k: nr_class of str_er_svm_info, in the model's class order), the runs in the order of
- * str_er_result_line_runs().  Each returns NULL and 0 without the flag; a call without runs returns empty arrays (not NULL).        */
+ * str_er_result_line_runs().  Each returns NULL and 0 without the flag; a call without runs returns empty arrays (not NULL).  The
+ * cost bytes also come with STR_ER_WANT_WORD_DECODE and with STR_ER_WANT_RUN_SPLIT (unfolded where there is no matcher).             */
 const str_er_word_match *str_er_result_word_matches(const str_er_result *r, int32_t *n);
 const uint8_t           *str_er_result_run_costs(const str_er_result *r, uint64_t *n_bytes);
 const double            *str_er_result_run_probs(const str_er_result *r, uint64_t *n_values);
@@ -1125,6 +1230,15 @@ const double            *str_er_result_run_probs(const str_er_result *r, uint64_
 const str_er_word_decode *str_er_result_word_decodes(const str_er_result *r, int32_t *n);
 const uint8_t            *str_er_result_word_decode_chars(const str_er_result *r, uint64_t *n_bytes);
 const uint8_t            *str_er_result_word_decode_src(const str_er_result *r, uint64_t *n_bytes);
+/* With STR_ER_WANT_RUN_SPLIT (str_er_run_split): one split record per run of str_er_result_line_runs(); the pieces they index, with
+ * one reading and one 65-byte cost row per piece; the parts of the words back to back in word order; one record per word of
+ * str_er_result_words().  NULL (and *n = 0) without the flag.                                                                       */
+const str_er_run_split   *str_er_result_run_splits(const str_er_result *r, int32_t *n);
+const str_er_run_piece   *str_er_result_run_pieces(const str_er_result *r, int32_t *n);
+const str_er_run_read    *str_er_result_piece_reads(const str_er_result *r, int32_t *n);
+const uint8_t            *str_er_result_piece_costs(const str_er_result *r, uint64_t *n_bytes);
+const str_er_split_part  *str_er_result_split_parts(const str_er_result *r, int32_t *n);
+const str_er_word_split  *str_er_result_word_splits(const str_er_result *r, int32_t *n);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

@@ -80,6 +80,11 @@ LEXICON_FOLD_CASE = 1
 # Result.word_decodes / word_decode_chars / word_decode_src / word_decode_text / word_decode_runs / words_decode_text_of_line /
 # frame_line_decode_text, and run_costs / run_probs; the contract is at str_er_word_decode)
 WANT_WORD_DECODE = 8388608
+# output option: every glyph run cut at the valleys of its column profile, every piece read, per run the segmentation the scorer likes
+# best (needs WANT_RUN_READ; Result.run_splits / run_pieces / piece_reads / piece_costs / split_parts / word_splits / word_split_text /
+# words_split_text_of_line / frame_line_split_text; the contract is at str_er_run_split).  Beside WANT_WORD_MATCH / WANT_WORD_DECODE both
+# work on the split sequence of a word: word_decode_src then indexes the word's parts
+WANT_RUN_SPLIT = 16777216
 # str_er_word_decode: per word, the cost of the cheapest string (-1: more than 32 runs, not decoded) and of the plain reading, the
 # characters of the string and the runs read, dropped and the characters inserted
 WORD_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
@@ -91,6 +96,14 @@ assert WORD_MATCH_DTYPE.itemsize == 24
 # str_er_run_read: per glyph run, the scorer's label, its character (str_er_ocr_char) and pv[label]
 RUN_READ_DTYPE = np.dtype([("label", "<i4"), ("ch", "<i4"), ("prob", "<f8")])
 assert RUN_READ_DTYPE.itemsize == 16
+# str_er_run_split (ERFilter.feet_split / split_words, cuts_from_counts, split_words_host): per run its kept cut columns (frame columns,
+# -1 unused), the valley threshold and its pieces in the piece table; per piece its run, nodes, box and pixels; per part of a split
+# word (run, piece or -1 for the whole run); per word its parts in the part table, the cost of its split sequence and of its runs' own reading
+RUN_SPLIT_DTYPE = np.dtype([("n_cuts", "<i4"), ("cut", "<i4", (3,)), ("thr", "<u4"), ("first_piece", "<i4"), ("n_pieces", "<i4"), ("n_parts", "<i4")])
+RUN_PIECE_DTYPE = np.dtype([("run", "<i4"), ("from", "<i4"), ("to", "<i4"), ("x0", "<i4"), ("x1", "<i4"), ("y0", "<i4"), ("y1", "<i4"), ("pixels", "<u4")])
+SPLIT_PART_DTYPE = np.dtype([("run", "<i4"), ("piece", "<i4")])
+WORD_SPLIT_DTYPE = np.dtype([("first_part", "<i4"), ("n_parts", "<i4"), ("cost", "<i4"), ("read_cost", "<i4")])
+assert RUN_SPLIT_DTYPE.itemsize == 32 and RUN_PIECE_DTYPE.itemsize == 32 and SPLIT_PART_DTYPE.itemsize == 8 and WORD_SPLIT_DTYPE.itemsize == 16
 # str_er_line_run: frame columns [x0, x1) and rows [y0, y1), half open; word: its row of the word table
 LINE_RUN_DTYPE = np.dtype([("x0", "<i4"), ("x1", "<i4"), ("y0", "<i4"), ("y1", "<i4"), ("pixels", "<u4"), ("word", "<i4")])
 # str_er_line_word: the runs line_runs[first_run:first_run + n_runs] of line `line`, their bounding box and pixels
@@ -375,6 +388,17 @@ def load_library():
     L.str_er_result_word_decode_src.restype = vp
     L.str_er_ocr_char.argtypes = [C.c_int32]
     L.str_er_ocr_char.restype = C.c_int32
+    for name, cnt in (("run_splits", i32p), ("run_pieces", i32p), ("piece_reads", i32p), ("piece_costs", C.POINTER(C.c_uint64)), ("split_parts", i32p),
+                      ("word_splits", i32p)):
+        fn = getattr(L, "str_er_result_" + name)
+        fn.argtypes, fn.restype = [vp, cnt], vp
+    L.str_er_run_split_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.str_er_set_run_split.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.str_er_cuts_from_counts.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, i32p, C.POINTER(C.c_uint32)]
+    L.str_er_feet_split.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p, vp, C.c_int32, i32p, vp, vp,
+                                    vp, vp, C.c_int32, i32p, vp, vp]
+    L.str_er_split_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p, vp]
+    L.str_er_split_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, i32p, vp]
     L.str_er_feet_read.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p, vp, C.c_int32, i32p, vp, vp]
     L.str_er_run_atlas_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.str_er_line_crop_geometry.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double, vp]
@@ -522,6 +546,12 @@ class Result:
         self._word_decodes = None  # with WANT_WORD_DECODE: the tables behind word_decodes / word_decode_chars / word_decode_src (and run_costs / run_probs)
         self._word_decode_chars = None
         self._word_decode_src = None
+        self._run_splits = None    # with WANT_RUN_SPLIT: the tables behind run_splits / run_pieces / piece_reads / piece_costs / split_parts / word_splits
+        self._run_pieces = None
+        self._piece_reads = None
+        self._piece_costs = None
+        self._split_parts = None
+        self._word_splits = None
         self._planes = None
 
     def _line_words_table(self, table):
@@ -597,6 +627,60 @@ class Result:
             raise ValueError("the result has no word decodes (pass WANT_WORD_DECODE / want_word_decode=True)")
         return table
 
+    def _run_split_table(self, table):
+        if table is None:
+            raise ValueError("the result has no run splits (pass WANT_RUN_SPLIT / want_run_split=True)")
+        return table
+
+    @property
+    def run_splits(self) -> np.ndarray:
+        """With WANT_RUN_SPLIT: RUN_SPLIT_DTYPE per run of line_runs, in the same order."""
+        return self._run_split_table(getattr(self, "_run_splits", None))
+
+    @property
+    def run_pieces(self) -> np.ndarray:
+        """With WANT_RUN_SPLIT: RUN_PIECE_DTYPE, the pieces of the cut runs back to back in run order."""
+        return self._run_split_table(getattr(self, "_run_pieces", None))
+
+    @property
+    def piece_reads(self) -> np.ndarray:
+        """With WANT_RUN_SPLIT: RUN_READ_DTYPE per piece of run_pieces."""
+        return self._run_split_table(getattr(self, "_piece_reads", None))
+
+    @property
+    def piece_costs(self) -> np.ndarray:
+        """With WANT_RUN_SPLIT: (n pieces, 65) uint8, the cost row of every piece (folded where run_costs are)."""
+        return self._run_split_table(getattr(self, "_piece_costs", None))
+
+    @property
+    def split_parts(self) -> np.ndarray:
+        """With WANT_RUN_SPLIT: SPLIT_PART_DTYPE, the split sequences of the words back to back in word order."""
+        return self._run_split_table(getattr(self, "_split_parts", None))
+
+    @property
+    def word_splits(self) -> np.ndarray:
+        """With WANT_RUN_SPLIT: WORD_SPLIT_DTYPE per word of words, in the same order."""
+        return self._run_split_table(getattr(self, "_word_splits", None))
+
+    def word_split_text(self, w: int) -> str:
+        """With WANT_RUN_SPLIT: the string of the split sequence of word w: per part -- a whole run or a piece -- the character of the
+        first minimum of its cost row (run_costs / piece_costs; where a lexicon folds them, the first of a case pair)."""
+        ws = self.word_splits[w]
+        out = []
+        for p in self.split_parts[int(ws["first_part"]):int(ws["first_part"]) + int(ws["n_parts"])]:
+            row = self.run_costs[int(p["run"])] if int(p["piece"]) < 0 else self.piece_costs[int(p["piece"])]
+            out.append(_OCR_ALPHABET[int(np.argmin(row))])
+        return "".join(out)
+
+    def words_split_text_of_line(self, t: int) -> list:
+        """With WANT_RUN_SPLIT: word_split_text of the words of line t, left to right."""
+        lw = self.line_words[t]
+        return [self.word_split_text(w) for w in range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))]
+
+    def frame_line_split_text(self, i: int) -> str:
+        """With WANT_RUN_SPLIT: the split text of frame line i: words_split_text_of_line of its representative joined by one blank."""
+        return " ".join(self.words_split_text_of_line(int(self.frame_lines[i]["rep"])))
+
     @property
     def word_decodes(self) -> np.ndarray:
         """With WANT_WORD_DECODE: WORD_DECODE_DTYPE per word of words, in the same order."""
@@ -644,8 +728,8 @@ class Result:
 
     @property
     def run_costs(self) -> np.ndarray:
-        """With WANT_WORD_MATCH or WANT_WORD_DECODE: (n runs, 65) uint8, the cost row of every glyph run of line_runs (folded as the
-        lexicon says with WANT_WORD_MATCH, else unfolded)."""
+        """With WANT_WORD_MATCH, WANT_WORD_DECODE or WANT_RUN_SPLIT: (n runs, 65) uint8, the cost row of every glyph run of line_runs
+        (folded as the lexicon says with WANT_WORD_MATCH, else unfolded)."""
         return self._word_match_table(self._run_costs)
 
     @property
@@ -970,6 +1054,14 @@ class ERFilter:
                             if res._word_decodes is not None:
                                 res._word_decode_chars = table(L.str_er_result_word_decode_chars, np.uint8, n64).reshape(-1, 64)
                                 res._word_decode_src = table(L.str_er_result_word_decode_src, np.uint8, n64).reshape(-1, 64)
+                            res._run_splits = table(L.str_er_result_run_splits, RUN_SPLIT_DTYPE)
+                            if res._run_splits is not None:
+                                res._run_pieces = table(L.str_er_result_run_pieces, RUN_PIECE_DTYPE)
+                                res._piece_reads = table(L.str_er_result_piece_reads, RUN_READ_DTYPE)
+                                res._piece_costs = table(L.str_er_result_piece_costs, np.uint8, n64).reshape(-1, 65)
+                                res._split_parts = table(L.str_er_result_split_parts, SPLIT_PART_DTYPE)
+                                res._word_splits = table(L.str_er_result_word_splits, WORD_SPLIT_DTYPE)
+                                res._run_costs = table(L.str_er_result_run_costs, np.uint8, n64).reshape(len(res._run_reads), 65)
                             if res._word_matches is not None or res._word_decodes is not None:
                                 nr = len(res._run_reads)
                                 res._run_costs = table(L.str_er_result_run_costs, np.uint8, n64).reshape(nr, 65)
@@ -1040,7 +1132,7 @@ class ERFilter:
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
                     want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -1053,7 +1145,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -1175,7 +1267,7 @@ class ERFilter:
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
                          want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -1183,7 +1275,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1498,6 +1590,62 @@ class ERFilter:
         self._check(self.L.str_er_feet_read(*args, _np_ptr(runs), len(runs), C.byref(nr), _np_ptr(words), len(words), C.byref(nw),
                                             _np_ptr(reads) if want_reads else None, _np_ptr(q)))
         return lw[:len(ft)], runs[:nr.value].copy(), words[:nw.value].copy(), reads[:nr.value].copy() if want_reads else None, q[:nr.value].copy()
+
+    def set_run_split(self, num: int = 1, den: int = 4, split_cost: int = 8) -> None:
+        """str_er_set_run_split: the valley threshold num / den of a run's height (1 .. 65535 each) and SPLIT (0 .. 255) of
+        feet_split and split_words (str_er_run_split)."""
+        self._check(self.L.str_er_set_run_split(self.h, int(num), int(den), int(split_cost)))
+
+    def run_split_stats(self):
+        """str_er_run_split_stats: (bytes of the cut records, bytes of the segmentation tables) on the device; 0: never made."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self.L.str_er_run_split_stats(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def feet_split(self, W: int, H: int, feet: np.ndarray, bits: np.ndarray, slopes=None, want_reads: bool = True, want_q: bool = True):
+        """str_er_feet_split: feet_read and the cuts and pieces of every glyph run (str_er_run_split), made on the GPU.  Returns a dict:
+        line_words, runs, words, reads (None without want_reads), q, splits (RUN_SPLIT_DTYPE per run), pieces (RUN_PIECE_DTYPE),
+        piece_reads (None without want_reads) and piece_q ((n pieces, 1800) uint8, None without want_q).  Without want_reads no SVM
+        model is needed."""
+        ft = np.ascontiguousarray(feet, dtype=LINE_FOOT_DTYPE).reshape(-1)
+        bt = np.ascontiguousarray(bits, dtype=np.uint32).reshape(-1)
+        if int((ft["h"].astype(np.int64).clip(0) * ((ft["w"].astype(np.int64).clip(0) + 31) // 32)).sum()) != len(bt):
+            raise ValueError("bits needs h rows of (w + 31) // 32 words per foot, back to back")
+        sl = None
+        if slopes is not None:
+            sl = np.ascontiguousarray(slopes, dtype=np.float64).reshape(-1)
+            if len(sl) != len(ft):
+                raise ValueError("slopes needs one entry per foot")
+        lw = np.zeros(max(1, len(ft)), LINE_WORDS_DTYPE)
+        nr, nw, npc = C.c_int32(), C.c_int32(), C.c_int32()
+        args = (self.h, int(W), int(H), _np_ptr(ft) if len(ft) else None, _np_ptr(bt) if len(bt) else None,
+                _np_ptr(sl) if sl is not None and len(sl) else None, len(ft), _np_ptr(lw))
+        self._check(self.L.str_er_feet_read(*args, None, 0, C.byref(nr), None, 0, C.byref(nw), None, None))         # (the counting call)
+        n = nr.value
+        runs = np.zeros(max(1, n), LINE_RUN_DTYPE)
+        words = np.zeros(max(1, nw.value), LINE_WORD_DTYPE)
+        reads = np.zeros(max(1, n), RUN_READ_DTYPE) if want_reads else None
+        q = np.zeros((max(1, n), 1800), np.uint8)
+        splits = np.zeros(max(1, n), RUN_SPLIT_DTYPE)
+        cap = 9 * n                                                    # (a run has at most 9 pieces: one call)
+        pieces = np.zeros(max(1, cap), RUN_PIECE_DTYPE)
+        preads = np.zeros(max(1, cap), RUN_READ_DTYPE) if want_reads else None
+        pq = np.zeros((max(1, cap), 1800), np.uint8) if want_q else None
+        self._check(self.L.str_er_feet_split(*args, _np_ptr(runs), len(runs), C.byref(nr), _np_ptr(words), len(words), C.byref(nw),
+                                             _np_ptr(reads) if want_reads else None, _np_ptr(q), _np_ptr(splits), _np_ptr(pieces), cap, C.byref(npc),
+                                             _np_ptr(preads) if want_reads else None, _np_ptr(pq) if want_q else None))
+        k = npc.value
+        return {"line_words": lw[:len(ft)], "runs": runs[:nr.value].copy(), "words": words[:nw.value].copy(),
+                "reads": reads[:nr.value].copy() if want_reads else None, "q": q[:nr.value].copy(), "splits": splits[:nr.value].copy(),
+                "pieces": pieces[:k].copy(), "piece_reads": preads[:k].copy() if want_reads else None, "piece_q": pq[:k].copy() if want_q else None}
+
+    def split_words(self, splits, run_costs, piece_costs, first_run, n_runs_of_word):
+        """str_er_split_words: the segmentation (str_er_run_split) of the runs of the words [first_run[w], first_run[w] +
+        n_runs_of_word[w]) from the cost rows of the runs (n runs, 65) and of their pieces (n pieces, 65), at the SPLIT of
+        set_run_split.  Returns (WORD_SPLIT_DTYPE per word, SPLIT_PART_DTYPE parts, (n parts, 65) uint8 rows of the parts)."""
+        a = _split_args(splits, run_costs, piece_costs, first_run, n_runs_of_word)
+        self._check(self.L.str_er_split_words(self.h, *a[0], *a[1]))
+        return _split_out(a)
 
     def run_atlas_stats(self):
         """str_er_run_atlas_stats: (bytes of the run tile atlas, how often it was allocated or grown)."""
@@ -1820,6 +1968,50 @@ def load_tp_table(path: str) -> np.ndarray:
     return bigram_from_probs(v.reshape(65, 65))
 
 
+def cuts_from_counts(counts, H: int, num: int = 1, den: int = 4):
+    """str_er_cuts_from_counts (pure host): the kept cut columns of one run of height H with the column counts `counts`, relative to the
+    run and ascending, and the threshold: (list of cuts, thr)."""
+    n = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    cut = np.zeros(3, np.int32)
+    k, thr = C.c_int32(), C.c_uint32()
+    rc = load_library().str_er_cuts_from_counts(_np_ptr(n) if len(n) else None, len(n), int(H), int(num), int(den), _np_ptr(cut), C.byref(k), C.byref(thr))
+    if rc != 0:
+        raise StrErError(rc, "str_er_cuts_from_counts")
+    return [int(v) for v in cut[:k.value]], int(thr.value)
+
+
+def _split_args(splits, run_costs, piece_costs, first_run, n_runs_of_word):
+    sp = np.ascontiguousarray(splits, dtype=RUN_SPLIT_DTYPE).reshape(-1)
+    rc = np.ascontiguousarray(run_costs, dtype=np.uint8).reshape(-1, 65)
+    pc = np.ascontiguousarray(piece_costs, dtype=np.uint8).reshape(-1, 65)
+    fr = np.ascontiguousarray(first_run, dtype=np.int32).reshape(-1)
+    no = np.ascontiguousarray(n_runs_of_word, dtype=np.int32).reshape(-1)
+    if len(sp) != len(rc) or len(fr) != len(no):
+        raise ValueError("splits and run_costs need one row per run, first_run and n_runs_of_word one entry per word")
+    cap = int(min(4 * int(no.astype(np.int64).clip(0).sum()), 2 ** 31 - 1))          # (a run has at most 4 parts)
+    ws = np.zeros(max(1, len(fr)), WORD_SPLIT_DTYPE)
+    parts = np.zeros(max(1, cap), SPLIT_PART_DTYPE)
+    rows = np.zeros((max(1, cap), 65), np.uint8)
+    n = C.c_int32()
+    p = lambda a: _np_ptr(a) if len(a) else None
+    return ((p(sp), len(sp), p(rc), p(pc), len(pc), p(fr), p(no), len(fr)), (_np_ptr(ws), _np_ptr(parts), cap, C.byref(n), _np_ptr(rows)),
+            (sp, rc, pc, fr, no), ws, parts, rows, n)
+
+
+def _split_out(a):
+    ws, parts, rows, n = a[3], a[4], a[5], a[6]
+    return ws[:len(a[2][3])], parts[:n.value].copy(), rows[:n.value].copy()
+
+
+def split_words_host(splits, run_costs, piece_costs, first_run, n_runs_of_word, split_cost: int = 8):
+    """str_er_split_words_host (pure host, one thread): ERFilter.split_words with SPLIT as an argument."""
+    a = _split_args(splits, run_costs, piece_costs, first_run, n_runs_of_word)
+    rc = load_library().str_er_split_words_host(*a[0], int(split_cost), *a[1])
+    if rc != 0:
+        raise StrErError(rc, "str_er_split_words_host")
+    return _split_out(a)
+
+
 def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: int = 0, dele: int = 0):
     """str_er_decode_words_host (pure host, one thread): ERFilter.decode_words with the table and the parameters as arguments."""
     cs, fr, no, out, ch, sr = _decode_args(costs, first_run, n_runs_of_word)
@@ -1831,10 +2023,10 @@ def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: 
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -2193,6 +2385,14 @@ class FrameStream:
             if rc != 0:
                 raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
 
+    def set_run_split(self, num: int = 1, den: int = 4, split_cost: int = 8) -> None:
+        """str_er_set_run_split on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_run_split(ctx, int(num), int(den), int(split_cost))
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
     def acquire(self):
         """(slot, uint8 view of the pinned staging buffer)."""
         slot, buf, cap = C.c_int32(), C.c_void_p(), C.c_int64()
@@ -2202,23 +2402,23 @@ class FrameStream:
         return slot.value, arr
 
     def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit(self.h, slot, w, h, 3 * w, 3 * w * h, n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
         """The staging buffer holds n_frames tightly packed NV12 frames (w * h * 3 / 2 bytes each)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_nv12(self.h, slot, w, h, w, w * (h + h // 2), n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         if a.ndim == 3:
             a = a[None]
@@ -2236,21 +2436,21 @@ class FrameStream:
         return int(t.value)
 
     def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
         """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
         return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
 
     def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
         """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
         return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
 
     def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
         """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         arr = (ImageRef * max(1, len(refs)))(*refs)

@@ -503,6 +503,10 @@ int foot_stage(str_er_ctx *c, hipStream_t s, const FootTables &T, const uint32_t
     }
     if (want.geom && (rc = geom_enqueue(c, s, T.lines, d_lines, S.geom)) != STR_ER_OK) return rc;
     if (want.words && (rc = words_enqueue(c, s, T.lines, d_lines, S.words)) != STR_ER_OK) return rc;
+    // (k_run_cuts directly behind k_foot_words, on its run slots: its records come down with this stage's wait)
+    if (want.words && want.split &&
+        (rc = run_cuts_enqueue(c, s, d_lines, (int32_t)n_lines, S.words.buf.d(), S.words.o_rec, S.words.o_elem, S.words.n_elems)) != STR_ER_OK)
+        return rc;
     const auto launch_pairs = [&](FootHead *head, FootPair *out, uint32_t cap) { launch_foot_pairs(s, d_lines, (int)n_lines, d_list, feet, head, out, cap); };
     const auto launch_links = [&](FootHead *head, FootPair *out, uint32_t cap) {
         launch_foot_links(s, d_lines, (int)n_lines, reinterpret_cast<const FootRange *>(c->foot_tab.d() + o_rng), d_list, feet, head, out, cap);
@@ -695,7 +699,7 @@ int fill_geometry(str_er_ctx *c, str_er_result *r, const GeomPass &GP)
 
 // the runs and words of the lines (what k_foot_words left), and with read the reading of every run: T.lines is the table k_foot_words
 // read, and its footprints are still in c->foot_bits
-int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode)
+int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode, bool split)
 {
     const auto   t2 = std::chrono::steady_clock::now();
     const size_t n_lines = r->line_feet.size();
@@ -706,10 +710,20 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         for (size_t t = 0; t < n_lines; ++t) slopes[t] = r->texts[t].slope;
         const WordMatchOut wmo{&r->words, &r->word_matches, &r->run_costs, &r->run_probs};
         const WordDecodeOut wdo{&r->words, &r->word_decodes, &r->word_decode_chars, &r->word_decode_src, &r->run_costs, &r->run_probs};
+        std::vector<uint8_t> piece_q;          // (the pieces' features are not part of the result)
+        RunPieces rp{};
+        if (split) {
+            rp = RunPieces{&r->run_pieces, &r->piece_reads, &piece_q, &r->run_splits, &r->words, &r->piece_costs, &r->run_costs, &r->split_parts, &r->word_splits};          // (the cut records of the compacted runs: down with the stage's wait)
+            std::vector<uint32_t> slot_of(r->line_runs.size());
+            for (size_t t = 0; t < n_lines; ++t)
+                for (int32_t k = 0; k < r->line_words[t].n_runs; ++k) slot_of[(size_t)r->line_words[t].first_run + (size_t)k] = WP.slots[t].first + (uint32_t)k;
+            if (const int rcs = run_cuts_collect(c, r->line_runs, slot_of, r->run_splits, r->run_pieces); rcs != STR_ER_OK) return rcs;
+        }
         if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features, match ? &wmo : nullptr,
-                                           decode ? &wdo : nullptr);
+                                           decode ? &wdo : nullptr, split ? &rp : nullptr);
             rcr != STR_ER_OK)
             return rcr;
+        r->have_run_splits = split;
         r->have_run_reads = true;
         r->have_word_matches = match;
         r->have_word_decodes = decode;
@@ -752,7 +766,7 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
     if ((rc = fill_frame_lines(c, r, frame_of, pyr_of, S.feet.pairs, n_fl)) != STR_ER_OK) return rc;
     if (want.links && (rc = fill_links(c, b, r, frame_of, T, S.links)) != STR_ER_OK) return rc;
     if (want.geom && (rc = fill_geometry(c, r, S.geom)) != STR_ER_OK) return rc;
-    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode)) != STR_ER_OK) return rc;
+    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split)) != STR_ER_OK) return rc;
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
                              "%zu bytes back, host %.3f ms before + %.3f ms after the device\n",
@@ -763,17 +777,20 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
 
 int feet_words_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_words *line_words,
                     str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words, int32_t *n_words, bool read_runs,
-                    const double *slopes, str_er_run_read *reads, uint8_t *q_out)
+                    const double *slopes, str_er_run_read *reads, uint8_t *q_out, const FeetSplitOut *split)
 {
+    if (split && (!split->splits || !split->n_pieces || (split->pieces && split->cap_pieces < 0))) return fail(c, STR_ER_EINVAL, "bad arguments");
     if (W < 1 || H < 1 || W > 65535 || H > 65535 || n < 0 || !n_runs || !n_words || (n > 0 && (!feet || !line_words)) || (runs && cap_runs < 0) ||
         (words && cap_words < 0))
         return fail(c, STR_ER_EINVAL, "bad arguments");
+    if (split) *split->n_pieces = 0;
     CallerFeet F(c);
     int rc = F.check_boxes(W, H, feet, n, "");
     if (rc != STR_ER_OK) return rc;
     const bool reading = read_runs && runs && words;          // (a counting call reads nothing)
-    if (read_runs && reads && !(c->svm_loaded && c->svm.dim == 1800))
-        return fail(c, STR_ER_ESTATE, "str_er_feet_read needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)");
+    const bool scoring = reads || (split && split->pieces && split->piece_reads);
+    if (read_runs && scoring && !(c->svm_loaded && c->svm.dim == 1800))
+        return fail(c, STR_ER_ESTATE, std::string(split ? "str_er_feet_split" : "str_er_feet_read") + " needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)");
     if (read_runs && slopes)
         for (int32_t t = 0; t < n; ++t)
             if (!std::isfinite(slopes[t])) return fail(c, STR_ER_EINVAL, "slope " + std::to_string(t) + " is not finite");
@@ -782,7 +799,10 @@ int feet_words_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot 
     if (!F.words.empty()) {
         const size_t tab_need = sizeof(FootLine) * (size_t)n;
         if ((rc = F.reserve(tab_need)) != STR_ER_OK || (rc = F.upload(tab_need)) != STR_ER_OK) return rc;
-        if ((rc = words_enqueue(c, c->stream, F.lines, F.d_lines(), WP)) != STR_ER_OK || (rc = F.wait()) != STR_ER_OK) return rc;
+        if ((rc = words_enqueue(c, c->stream, F.lines, F.d_lines(), WP)) != STR_ER_OK) return rc;
+        // (the cuts ride on the same wait: k_run_cuts reads the run slots where k_foot_words left them)
+        if (split && reading && (rc = run_cuts_enqueue(c, c->stream, F.d_lines(), n, WP.buf.d(), WP.o_rec, WP.o_elem, WP.n_elems)) != STR_ER_OK) return rc;
+        if ((rc = F.wait()) != STR_ER_OK) return rc;
     }
     std::vector<str_er_line_words> lw;
     std::vector<str_er_line_run>   rn;
@@ -793,13 +813,30 @@ int feet_words_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot 
     if (!runs || !words) return STR_ER_OK;
     if ((rc = check_cap(c, rn.size(), cap_runs, "glyph runs, cap_runs")) != STR_ER_OK || (rc = check_cap(c, wd.size(), cap_words, "words, cap_words")) != STR_ER_OK)
         return rc;
+    std::vector<str_er_run_split> sp;
+    std::vector<str_er_run_piece> pc;
+    if (split && reading && !rn.empty()) {
+        std::vector<uint32_t> slot_of(rn.size());
+        for (size_t t = 0; t < (size_t)n; ++t)
+            for (int32_t k = 0; k < lw[t].n_runs; ++k) slot_of[(size_t)lw[t].first_run + (size_t)k] = WP.slots[t].first + (uint32_t)k;
+        if ((rc = run_cuts_collect(c, rn, slot_of, sp, pc)) != STR_ER_OK) return rc;
+        *split->n_pieces = (int32_t)pc.size();
+        if (split->pieces && (rc = check_cap(c, pc.size(), split->cap_pieces, "pieces, cap_pieces")) != STR_ER_OK) return rc;
+    }
+    const bool with_pieces = split && split->pieces;
     if (reading && !rn.empty()) {          // (the footprints are still in c->foot_bits, the lines as the kernel read them in F.lines)
-        std::vector<str_er_run_read> rd;
-        std::vector<uint8_t>         q;
-        if ((rc = run_read_stage(c, c->stream, F.lines, lw, rn, slopes, reads ? &rd : nullptr, q)) != STR_ER_OK) return rc;
+        std::vector<str_er_run_read> rd, prd;
+        std::vector<uint8_t>         q, pq;
+        const RunPieces RP{&pc, split && split->piece_reads ? &prd : nullptr, &pq};
+        if ((rc = run_read_stage(c, c->stream, F.lines, lw, rn, slopes, scoring ? &rd : nullptr, q, nullptr, nullptr, with_pieces ? &RP : nullptr)) != STR_ER_OK)
+            return rc;
         if (reads) std::memcpy(reads, rd.data(), sizeof(str_er_run_read) * rd.size());
         if (q_out) std::memcpy(q_out, q.data(), q.size());
+        if (with_pieces && split->piece_reads && !prd.empty()) std::memcpy(split->piece_reads, prd.data(), sizeof(str_er_run_read) * prd.size());
+        if (with_pieces && split->piece_q && !pq.empty()) std::memcpy(split->piece_q, pq.data(), pq.size());
     }
+    if (split && !sp.empty()) std::memcpy(split->splits, sp.data(), sizeof(str_er_run_split) * sp.size());
+    if (with_pieces && !pc.empty()) std::memcpy(split->pieces, pc.data(), sizeof(str_er_run_piece) * pc.size());
     if (!rn.empty()) std::memcpy(runs, rn.data(), sizeof(str_er_line_run) * rn.size());
     if (!wd.empty()) std::memcpy(words, wd.data(), sizeof(str_er_line_word) * wd.size());
     return STR_ER_OK;

@@ -208,7 +208,7 @@ const str_er_word_match *str_er_result_word_matches(const str_er_result *r, int3
 }
 const uint8_t *str_er_result_run_costs(const str_er_result *r, uint64_t *n_bytes)
 {
-    return result_table(r, r && (r->have_word_matches || r->have_word_decodes), &str_er_result::run_costs, n_bytes);
+    return result_table(r, r && (r->have_word_matches || r->have_word_decodes || r->have_run_splits), &str_er_result::run_costs, n_bytes);
 }
 const double *str_er_result_run_probs(const str_er_result *r, uint64_t *n_values)
 {

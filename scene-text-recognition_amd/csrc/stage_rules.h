@@ -30,6 +30,11 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
     const uint32_t sup = STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP;
     struct Rule { bool bad; int code; const char *msg; };
     const Rule rules[] = {
+        // STR_ER_WANT_RUN_SPLIT rides on STR_ER_WANT_RUN_READ as STR_ER_WANT_WORD_MATCH does; its parameters have defaults, so it needs no
+        // state of the context; a call without the flag meets no new rule
+        {k.strip && any(STR_ER_WANT_RUN_SPLIT), STR_ER_EINVAL, "STR_ER_WANT_RUN_SPLIT is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_RUN_SPLIT), STR_ER_EINVAL, "STR_ER_WANT_RUN_SPLIT needs frames (not the per-plane calls)"},
+        {any(STR_ER_WANT_RUN_SPLIT) && !any(STR_ER_WANT_RUN_READ), STR_ER_EINVAL, "STR_ER_WANT_RUN_SPLIT needs STR_ER_WANT_RUN_READ"},
         // STR_ER_WANT_WORD_DECODE rides on STR_ER_WANT_RUN_READ as STR_ER_WANT_WORD_MATCH does (its table rule is with the models' below);
         // a call without the flag meets no new rule
         {k.strip && any(STR_ER_WANT_WORD_DECODE), STR_ER_EINVAL, "STR_ER_WANT_WORD_DECODE is not supported by the strip path (str_er_strip_merge)"},

@@ -160,6 +160,13 @@ struct str_er_result {
     std::vector<str_er_word_decode> word_decodes; // STR_ER_WANT_WORD_DECODE: per word of words, and 64 label and 64 source bytes per word (run_costs / run_probs too)
     std::vector<uint8_t> word_decode_chars, word_decode_src;
     bool have_word_decodes = false;
+    std::vector<str_er_run_split> run_splits;    // STR_ER_WANT_RUN_SPLIT: per run of line_runs; the pieces they index with a reading and a cost row each;
+    std::vector<str_er_run_piece> run_pieces;    // the parts of the words; per word of words
+    std::vector<str_er_run_read> piece_reads;
+    std::vector<uint8_t> piece_costs;
+    std::vector<str_er_split_part> split_parts;
+    std::vector<str_er_word_split> word_splits;
+    bool have_run_splits = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -292,6 +299,10 @@ struct str_er_ctx {
     bool     bigram_set = false;
     int32_t  wd_ins = 0, wd_del = 0;
     PairBuf  wd_tab;                  // cost rows | first run, run count per word | records | labels | sources
+    // str_er_feet_split / str_er_split_words (str_er_set_run_split)
+    int32_t  rs_num = 1, rs_den = 4, rs_split = 8;
+    PairBuf  rs_out;                  // a record per run slot of k_run_cuts
+    PairBuf  rs_tab;                  // splits | rows of the runs and pieces | first run, run count, slot per word | records | parts | part rows
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -569,14 +580,30 @@ struct LineStageWants {
     bool read = false;        // STR_ER_WANT_RUN_READ: the reading of every run (k_run_tiles and the scorer behind the stage's wait, with a wait of their own)
     bool match = false;       // STR_ER_WANT_WORD_MATCH: every word against the lexicon (k_run_costs and the matcher behind the scorer)
     bool decode = false;      // STR_ER_WANT_WORD_DECODE: every word under the bigram table (k_run_costs and the decoder behind the scorer)
+    bool split = false;       // STR_ER_WANT_RUN_SPLIT: the cuts of every run (k_run_cuts behind k_foot_words, down with the stage's wait), the pieces read with the runs, k_split_words behind the scorer
 };
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
                       str_er_result *r, const LineStageWants &want);
 // the caller's footprints of str_er_feet_words / str_er_feet_read (api_run_read.cpp) cut into runs and words, and with read_runs read
 // (slopes, reads, q_out: str_er_feet_read's arguments)
+// split (optional): str_er_feet_split's further arguments -- the cuts and pieces of every run, and the pieces read with the runs
+struct FeetSplitOut {
+    str_er_run_split *splits;
+    str_er_run_piece *pieces;
+    int32_t           cap_pieces, *n_pieces;
+    str_er_run_read  *piece_reads;
+    uint8_t          *piece_q;
+};
 int feet_words_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot *feet, const uint32_t *bits, int32_t n, str_er_line_words *line_words,
                     str_er_line_run *runs, int32_t cap_runs, int32_t *n_runs, str_er_line_word *words, int32_t cap_words, int32_t *n_words, bool read_runs,
-                    const double *slopes, str_er_run_read *reads, uint8_t *q_out);
+                    const double *slopes, str_er_run_read *reads, uint8_t *q_out, const FeetSplitOut *split = nullptr);
+// ---- defined in api_run_split.cpp
+// k_run_cuts over the run slots k_foot_words leaves in `words` (the device side of its LinePass buffer: records at o_rec, n_slots run
+// slots at o_elem), behind it on s, and the copy back of its records into c->rs_out; run_cuts_collect after the wait: the records
+// of the compacted runs (slot_of: the slot of every run) as str_er_run_split, and the pieces formed from the atoms
+int run_cuts_enqueue(str_er_ctx *c, hipStream_t s, const FootLine *d_lines, int32_t n_lines, const uint8_t *words, size_t o_rec, size_t o_elem, size_t n_slots);
+int run_cuts_collect(str_er_ctx *c, const std::vector<str_er_line_run> &runs, const std::vector<uint32_t> &slot_of, std::vector<str_er_run_split> &splits,
+                     std::vector<str_er_run_piece> &pieces);
 // ---- defined in api_run_read.cpp
 // The reading of the compacted runs of a launch whose footprints are still in c->foot_bits (lines: the table k_foot_words read):
 // the tiles laid out and expanded into the atlas, then the scorer's launch chain on the atlas as a device plane with one box a run and
@@ -599,9 +626,42 @@ struct WordDecodeOut {
     std::vector<uint8_t> *costs;
     std::vector<double> *probs;
 };
+// pieces (optional): the pieces of the runs (str_er_run_split) read with them -- their tiles behind the runs' in the one atlas, one
+// launch chain over both; reads (null: no labels) and q receive the pieces' results, the runs' are what they are without pieces
+struct RunPieces {
+    const std::vector<str_er_run_piece> *pieces;
+    std::vector<str_er_run_read> *reads;
+    std::vector<uint8_t> *q;
+    // STR_ER_WANT_RUN_SPLIT (all null otherwise; with reads): k_split_words behind k_run_costs on s -- the segmentation of the runs of
+    // `words` (splits: their records; n_parts is filled in), the parts and word records, the pieces' cost rows; the matcher and the
+    // decoder then work on the parts' rows
+    std::vector<str_er_run_split> *splits = nullptr;
+    const std::vector<str_er_line_word> *words = nullptr;
+    std::vector<uint8_t> *costs = nullptr;
+    std::vector<uint8_t> *run_costs = nullptr;          // (the runs' rows, filled where neither the matcher nor the decoder leaves them)
+    std::vector<str_er_split_part> *parts = nullptr;
+    std::vector<str_er_word_split> *word_splits = nullptr;
+};
+// the layout of c->rs_tab for k_split_words (base: either side of the pair, or null for the size alone): n_rows cost rows of which the
+// first n_runs are the runs' and the others the pieces', n_words words with n_slots part slots in all.  rows2: a second set of part rows
+struct RsTab {
+    str_er_run_split *splits;
+    uint8_t *costs;
+    int32_t *first, *n_of, *slot, *word_out, *parts, *n_parts;
+    uint8_t *part_costs, *part_costs2;
+    size_t   o_first, up_bytes, o_out, bytes;
+    size_t   down_tables, down_bytes;        // from o_out: the word records and the parts; ... and the parts' rows behind them
+};
+RsTab rs_layout(uint8_t *base, size_t n_runs, size_t n_rows, size_t n_words, size_t n_slots, bool rows2 = false);
+// the part slot of every word: the atoms of the words before it; the total in *n_slots; false above 2^31 - 1
+bool rs_word_slots(const str_er_run_split *splits, const int32_t *first_run, const int32_t *n_of, size_t n_words, std::vector<int32_t> &slot, uint64_t *n_slots);
+// after the wait: the word records and the compacted parts from the host side of the layout (null parts / part_costs: not copied);
+// false where a word's parts lie outside its slots
+bool rs_compact(const RsTab &H, const std::vector<int32_t> &slot, uint64_t n_slots, str_er_word_split *word_splits, str_er_split_part *parts, uint8_t *part_costs,
+                uint64_t *n_parts);
 int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
                    const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q,
-                   const WordMatchOut *match = nullptr, const WordDecodeOut *decode = nullptr);
+                   const WordMatchOut *match = nullptr, const WordDecodeOut *decode = nullptr, const RunPieces *pieces = nullptr);
 // ---- defined in api_word_match.cpp
 // the layout of c->wm_tab for n_runs cost rows and n_words words (base: either side of the pair, or null for the size alone)
 struct WmTab {

@@ -22,6 +22,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <tuple>
 #include <utility>
 #include <vector>
 
@@ -716,6 +717,131 @@ public:
         std::string s;
         const str_er_line_words &L = lw.lines.at(t);
         for (int32_t k = L.first_word; k < L.first_word + L.n_words; ++k) s += (k > L.first_word ? " " : "") + word_decode_text(lw, rd, wd, (size_t)k);
+        return s;
+    }
+
+    // Touching glyphs split (STR_ER_WANT_RUN_SPLIT; the contract is at str_er_run_split in include/str_er.h): one split record per run of
+    // LineWords::runs, the pieces they index with one reading and 65 cost bytes each, the parts of the words back to back in word order
+    // (piece -1: the whole run), one record per word of LineWords::words, and the 65 cost bytes of every run.  Needs STR_ER_WANT_RUN_READ.
+    struct RunSplits {
+        std::vector<str_er_run_split>  splits;
+        std::vector<str_er_run_piece>  pieces;
+        std::vector<str_er_run_read>   piece_reads;
+        std::vector<uint8_t>           piece_costs, piece_features;      // (the features: feet_split alone)
+        std::vector<str_er_split_part> parts;
+        std::vector<str_er_word_split> word_splits;
+        std::vector<uint8_t>           run_costs;
+        std::vector<uint8_t>           part_costs;                       // (the parts' rows: split_words alone)
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static RunSplits run_splits(const str_er_result *r)
+    {
+        RunSplits out;
+        int32_t   n = 0;
+        uint64_t  nb = 0;
+        if (const str_er_run_split *p = str_er_result_run_splits(r, &n)) out.splits.assign(p, p + n);
+        if (const str_er_run_piece *p = str_er_result_run_pieces(r, &n)) out.pieces.assign(p, p + n);
+        if (const str_er_run_read *p = str_er_result_piece_reads(r, &n)) out.piece_reads.assign(p, p + n);
+        if (const uint8_t *p = str_er_result_piece_costs(r, &nb)) out.piece_costs.assign(p, p + nb);
+        if (const str_er_split_part *p = str_er_result_split_parts(r, &n)) out.parts.assign(p, p + n);
+        if (const str_er_word_split *p = str_er_result_word_splits(r, &n)) out.word_splits.assign(p, p + n);
+        if (str_er_result_run_splits(r, &n))          // (the runs' rows come with other flags too: here only with this one)
+            if (const uint8_t *p = str_er_result_run_costs(r, &nb)) out.run_costs.assign(p, p + nb);
+        return out;
+    }
+    // the valley threshold num / den of a run's height (1 .. 65535 each) and SPLIT (0 .. 255) (str_er_set_run_split; 1 / 4 and 8 by default)
+    void set_run_split(int32_t num, int32_t den, int32_t split_cost) { check(str_er_set_run_split(ctx_.get(), num, den, split_cost)); }
+    // the kept cut columns of one run from its column counts and height, relative to the run (str_er_cuts_from_counts; pure host)
+    static std::vector<int32_t> cuts_from_counts(const std::vector<uint32_t> &counts, int32_t height, int32_t num = 1, int32_t den = 4)
+    {
+        int32_t cut[3], n = 0;
+        if (str_er_cuts_from_counts(counts.empty() ? nullptr : counts.data(), (int32_t)counts.size(), height, num, den, cut, &n, nullptr) != STR_ER_OK)
+            throw std::invalid_argument("cuts_from_counts");
+        return std::vector<int32_t>(cut, cut + n);
+    }
+    // feet_read and the cuts and pieces of every run, the pieces read with the runs (str_er_feet_split): slopes one per foot, or empty:
+    // all 0; want_reads = false: cuts, pieces and features only (no model needed)
+    std::tuple<LineWords, RunReads, RunSplits> feet_split(int32_t width, int32_t height, const std::vector<str_er_line_foot> &feet,
+                                                          const std::vector<uint32_t> &bits, const std::vector<double> &slopes = {}, bool want_reads = true)
+    {
+        if (!slopes.empty() && slopes.size() != feet.size()) throw std::invalid_argument("feet_split: one slope per foot");
+        LineWords lw;
+        RunReads  rd;
+        RunSplits sp;
+        lw.lines.resize(feet.size());
+        const str_er_line_foot *fp = feet.empty() ? nullptr : feet.data();
+        const uint32_t         *bp = bits.empty() ? nullptr : bits.data();
+        const double           *dp = slopes.empty() ? nullptr : slopes.data();
+        str_er_line_words      *lp = lw.lines.empty() ? nullptr : lw.lines.data();
+        int32_t nr = 0, nw = 0, np = 0;
+        check(str_er_feet_read(ctx_.get(), width, height, fp, bp, dp, (int32_t)feet.size(), lp, nullptr, 0, &nr, nullptr, 0, &nw, nullptr, nullptr));      // (counts)
+        const size_t cap = 9 * (size_t)nr + 1;                            // (a run has at most 9 pieces)
+        if (cap > 0x7FFFFFFFull) throw std::invalid_argument("feet_split: too many runs");
+        lw.runs.resize((size_t)nr + 1);
+        lw.words.resize((size_t)nw + 1);
+        rd.reads.resize(want_reads ? (size_t)nr + 1 : 0);
+        rd.features.resize(1800 * ((size_t)nr + 1));
+        sp.splits.resize((size_t)nr + 1);
+        sp.pieces.resize(cap);
+        sp.piece_reads.resize(want_reads ? cap : 0);
+        sp.piece_features.resize(1800 * cap);
+        check(str_er_feet_split(ctx_.get(), width, height, fp, bp, dp, (int32_t)feet.size(), lp, lw.runs.data(), nr + 1, &nr, lw.words.data(), nw + 1, &nw,
+                                want_reads ? rd.reads.data() : nullptr, rd.features.data(), sp.splits.data(), sp.pieces.data(), (int32_t)cap, &np,
+                                want_reads ? sp.piece_reads.data() : nullptr, sp.piece_features.data()));
+        lw.runs.resize((size_t)nr);
+        lw.words.resize((size_t)nw);
+        if (want_reads) rd.reads.resize((size_t)nr);
+        rd.features.resize(1800 * (size_t)nr);
+        sp.splits.resize((size_t)nr);
+        sp.pieces.resize((size_t)np);
+        if (want_reads) sp.piece_reads.resize((size_t)np);
+        sp.piece_features.resize(1800 * (size_t)np);
+        return {std::move(lw), std::move(rd), std::move(sp)};
+    }
+    // the segmentation of the runs of the words [first_run[w], first_run[w] + n_runs[w]) on the caller's cost rows (str_er_split_words):
+    // splits one record per run, run_costs and piece_costs 65 bytes a row.  Returns word_splits, parts and part_costs (the parts' rows,
+    // which match_words / decode_words take with first_part and n_parts as the words' spans)
+    RunSplits split_words(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                          const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs)
+    {
+        if (first_run.size() != n_runs.size() || run_costs.size() != 65 * splits.size() || piece_costs.size() % 65)
+            throw std::invalid_argument("split_words: 65 bytes a run and a piece, one record a run, one span a word");
+        size_t cap = 1;
+        for (const int32_t k : n_runs) cap += 4 * (size_t)(k > 0 ? k : 0);          // (a run has at most 4 parts)
+        if (cap > 0x7FFFFFFFull) throw std::invalid_argument("split_words: too many runs");
+        RunSplits out;
+        out.word_splits.resize(first_run.size());
+        out.parts.resize(cap);
+        out.part_costs.resize(65 * cap);
+        int32_t n = 0;
+        check(str_er_split_words(ctx_.get(), splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                 piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65), first_run.empty() ? nullptr : first_run.data(),
+                                 n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(), out.word_splits.empty() ? nullptr : out.word_splits.data(),
+                                 out.parts.data(), (int32_t)cap, &n, out.part_costs.data()));
+        out.parts.resize((size_t)n);
+        out.part_costs.resize(65 * (size_t)n);
+        return out;
+    }
+    // the string of the split sequence of word w: per part the character of the first minimum of its cost row
+    static std::string word_split_text(const RunSplits &sp, size_t w)
+    {
+        std::string s;
+        const str_er_word_split &W = sp.word_splits.at(w);
+        for (int32_t k = W.first_part; k < W.first_part + W.n_parts; ++k) {
+            const str_er_split_part &P = sp.parts.at((size_t)k);
+            const uint8_t *row = P.piece < 0 ? &sp.run_costs.at(65 * (size_t)P.run) : &sp.piece_costs.at(65 * (size_t)P.piece);
+            int best = 0;
+            for (int a = 1; a < 65; ++a) best = row[a] < row[best] ? a : best;
+            s += (char)str_er_ocr_char(best);
+        }
+        return s;
+    }
+    // the split text of line t: its words' split strings joined by one blank
+    static std::string line_split_text(const LineWords &lw, const RunSplits &sp, size_t t)
+    {
+        std::string s;
+        const str_er_line_words &L = lw.lines.at(t);
+        for (int32_t k = L.first_word; k < L.first_word + L.n_words; ++k) s += (k > L.first_word ? " " : "") + word_split_text(sp, (size_t)k);
         return s;
     }
 
