@@ -150,6 +150,13 @@ extern "C" {
  * It changes no other output of the call -- the runs' own reads are byte for byte those of a call without it -- and combines with
  * every other STR_ER_WANT_* flag.                                                                                                   */
 #define STR_ER_WANT_RUN_SPLIT (16777216u)
+/* output option: the words of adjacent frames linked into word tracks, and per word track one lexicon match over the cost rows of
+ * all its members (str_er_result_word_links / _word_tracks / _word_track_members / _word_track_of_words / _track_matches /
+ * _track_member_costs; the contract is at str_er_word_link).  Needs STR_ER_WANT_LINE_LINKS and STR_ER_WANT_WORD_MATCH: STR_ER_EINVAL
+ * without either and wherever either is refused (the strip path, the per-plane calls), and through them a model and a lexicon:
+ * STR_ER_ESTATE without; the context is usable afterwards.  Beside STR_ER_WANT_RUN_SPLIT the members' rows are those of their parts.
+ * It changes no other output of the call and combines with every other STR_ER_WANT_* flag.                                          */
+#define STR_ER_WANT_TRACK_READ (33554432u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -511,6 +518,55 @@ typedef struct str_er_word_match {
     int32_t  free_cost, n_tried;          /* 16, 20                                   */
 } str_er_word_match;         /* 24 bytes; one per word of str_er_result_words()       */
 #define STR_ER_LEXICON_FOLD_CASE 1u
+
+/* The words of consecutive frames linked into word tracks, and one lexicon match per word track over the cost rows of all its
+ * members (STR_ER_WANT_TRACK_READ, str_er_word_links, str_er_word_tracks_from_links, str_er_match_tracks).  All exact integers and
+ * a definition of this library, on top of the text tracks of str_er_line_link, the words of str_er_line_word and the matcher of
+ * str_er_word_match; nothing is tuned on labelled data.
+ *   Reading line: for a text track k and a frame f that holds members of k, R(k, f) is the member line of frame f with the most
+ *     footprint pixels, ties to the smallest line index (the representative's rule).  A word is eligible iff its line is a reading
+ *     line: of the duplicate lines of several pyramid levels only one is read.
+ *   Word link: frames f and f + 1 are adjacent as for str_er_line_link (equal level-0 sizes).  For every track k with reading lines
+ *     in both, every word u of R(k, f) and every word v of R(k, f + 1): inter(u, v) is the area of the intersection of the two
+ *     boxes (x, y, w, h) of str_er_line_word, as uint32.  Every such pair with inter > 0 is a record; the table is sorted by (a, b).
+ *     link = 1 iff inter * den >= num * (area(u) + area(v) - inter) in 64-bit integers; num / den: str_er_set_word_link, each in
+ *     1 .. 65535, 1 / 2 by default.  Words of different tracks, of frames that are not adjacent and of lines that are not reading
+ *     lines never meet.  Boxes are linked, not footprints.
+ *   Word track: a connected component of the links with link = 1 over the eligible words: the transitive closure, so two words of
+ *     one frame can land in one track.  Its members are word indices, ascending; rep is the member with the most pixels
+ *     (str_er_line_word::pixels), ties to the smallest index.  Tracks are ordered by first_frame, then by their smallest member.  An
+ *     eligible word without a link is a track of one.  One int32 per word gives its track, -1 for a word that is not eligible.
+ *   Track match of a track with the members w_1 .. w_n: member i has m_i cost rows, the rows the matcher read for that word (with
+ *     STR_ER_WANT_RUN_SPLIT those of its parts).  The fold, INS, DEL and the band are those of str_er_word_match.  A member is usable
+ *     iff m_i <= 32.  For an entry e of length l, cost(e) is the sum over the usable members of D_i[m_i][l], the recurrence of
+ *     str_er_word_match, whatever |l - m_i| is.  e is tried iff |l - m_i| <= band for at least one usable member: the lengths tried
+ *     are a union of bands and may have gaps.  (cost, entry) is the minimum of (cost, index) over the tried entries, second_* the
+ *     same over the tried entries other than `entry`; both are -1 with their costs where nothing qualifies.  free_cost is the sum of
+ *     the free costs of all members (also the unusable ones), n_tried the number of entries tried, n_used the number of usable
+ *     members.  Per slot of the member array, member_cost is D_i[m_i][l] for the winning entry, -1 for an unusable member or where
+ *     entry is -1: their sum is cost.  best_member is the word with the smallest member_cost, ties to the earliest slot, or -1.  A
+ *     track has at most 65536 members (STR_ER_ECAPACITY above): with at most 64 * 255 a member the sum stays inside int32.
+ *     A track of one usable member has the six fields of that word's str_er_word_match; a track of unusable members tries nothing.
+ *   Limits: across calls and stream submissions nothing is remembered -- str_er_word_links, str_er_word_tracks_from_links and
+ *     str_er_match_tracks are what a caller needs to pool over submissions himself.  There is no pooled open-vocabulary decode
+ *     (a median string over members with different run counts is another problem).                                               */
+typedef struct str_er_word_link {
+    int32_t  a, b;           /*  0: a word of frame f and a word of the adjacent frame f + 1            */
+    uint32_t inter;          /*  8: the area of the intersection of their boxes, > 0                    */
+    uint32_t link;           /* 12: 1 if the two are linked at the call's num / den, else 0             */
+} str_er_word_link;          /* 16 bytes; every such pair with inter > 0, sorted by (a, b) */
+typedef struct str_er_word_track {
+    uint32_t first_frame, last_frame;  /*  0: the smallest and the largest frame of a member            */
+    int32_t  first, count;   /*  8: its members: str_er_result_word_track_members()[first .. first + count), word indices, ascending */
+    int32_t  rep;            /* 16: the representative: a word index                                    */
+    int32_t  text_track;     /* 20: the text track of its members' lines                                */
+} str_er_word_track;         /* 24 bytes */
+typedef struct str_er_track_match {
+    int32_t  entry, cost;                 /*  0,  4                                   */
+    int32_t  second_entry, second_cost;   /*  8, 12                                   */
+    int32_t  free_cost, n_tried;          /* 16, 20                                   */
+    int32_t  n_used, best_member;         /* 24, 28                                   */
+} str_er_track_match;        /* 32 bytes; one per word track                          */
 
 /* The decoding of a word under a character bigram table (STR_ER_WANT_WORD_DECODE, str_er_decode_words): the cheapest character string
  * of a word under the cost rows of its glyph runs plus a table of costs of one character after another, which may drop a run (a speck)
@@ -932,6 +988,42 @@ int str_er_match_words(str_er_ctx *ctx, const uint8_t *costs, int32_t n_runs, co
 int str_er_match_words_host(const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, const char *bytes,
                             const int32_t *offsets, int32_t n, uint32_t flags, int32_t ins, int32_t del, int32_t band, str_er_word_match *matches);
 
+/* The link threshold num / den of STR_ER_WANT_TRACK_READ (str_er_word_link): 1 <= num, den <= 65535, default 1 / 2.  Anything else
+ * -> STR_ER_EINVAL, the context unchanged.  A stream's contexts: str_er_stream_context.                                            */
+int str_er_set_word_link(str_er_ctx *ctx, int32_t num, int32_t den);
+/* The reading lines and the word links (str_er_word_link) of n_words words of n_lines lines of n_frames frames.  Pure host, no
+ * context, no GPU; the detect calls run the same rules.  Reads feet[t].pixels, frames_of_lines[t] (< n_frames), line_tracks[t]
+ * (>= 0: the text track of line t), frame_wh (w, h of every frame at level 0) and words[w].line, x, y, w, h.  reading receives one
+ * byte per line, 1 for a reading line; links the records with inter > 0 sorted by (a, b), link set at num / den; links == NULL only
+ * reports *n_links; cap_links too small -> STR_ER_ECAPACITY, *n_links still set.  STR_ER_EINVAL: bad arguments, num or den outside
+ * 1 .. 65535, a frame, a track or a word's line out of range, a word box with w or h outside 0 .. 65535.                          */
+int str_er_word_links(const str_er_line_foot *feet, const uint32_t *frames_of_lines, const int32_t *line_tracks, int32_t n_lines, const int32_t *frame_wh,
+                      int32_t n_frames, const str_er_line_word *words, int32_t n_words, int32_t num, int32_t den, uint8_t *reading, str_er_word_link *links,
+                      int32_t cap_links, int32_t *n_links);
+/* The word tracks (str_er_word_track) from the reading flags and the links of str_er_word_links.  Pure host, no context, no GPU; the
+ * detect calls run the same rules.  Reads links[k].a, b, link.  track_of_words receives one track index per word, -1 for a word
+ * that is not eligible; tracks at most n_words records (cap_tracks too small -> STR_ER_ECAPACITY, *n_tracks still set; tracks == NULL
+ * only counts and sets track_of_words); members the eligible words, at most n_words.  STR_ER_EINVAL: bad arguments, an index out of
+ * range, a link between words that are not eligible.                                                                              */
+int str_er_word_tracks_from_links(const uint32_t *frames_of_lines, const int32_t *line_tracks, const uint8_t *reading, int32_t n_lines,
+                                  const str_er_line_word *words, int32_t n_words, const str_er_word_link *links, int32_t n_links, int32_t *track_of_words,
+                                  str_er_word_track *tracks, int32_t cap_tracks, int32_t *n_tracks, int32_t *members);
+/* The track match (str_er_track_match) on the caller's cost rows, on the GPU: costs holds n_rows rows of 65 bytes, word w has the
+ * rows first_run[w] .. first_run[w] + n_runs_of_word[w] as for str_er_match_words; track g has the members members[track_first[g] ..
+ * track_first[g] + track_count[g]) of the member array of n_members word indices; the tracks lie in it in ascending order without
+ * overlap.  Any word may appear in any member list, also twice, in which case it counts twice.  out receives n_tracks records,
+ * member_cost n_members values (-1 in a slot of no track).  STR_ER_ESTATE without a lexicon; STR_ER_EINVAL on a word outside the rows,
+ * a member outside the words, a track outside the member array; STR_ER_ECAPACITY on a track of more than 65536 members.             */
+int str_er_match_tracks(str_er_ctx *ctx, const uint8_t *costs, int32_t n_rows, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
+                        const int32_t *track_first, const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks,
+                        str_er_track_match *out, int32_t *member_cost);
+/* The same rules on one host thread, with the lexicon and the parameters as arguments (as for str_er_match_words_host).  Pure: no
+ * context, no GPU.                                                                                                                */
+int str_er_match_tracks_host(const uint8_t *costs, int32_t n_rows, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
+                             const int32_t *track_first, const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks,
+                             const char *bytes, const int32_t *offsets, int32_t n, uint32_t flags, int32_t ins, int32_t del, int32_t band,
+                             str_er_track_match *out, int32_t *member_cost);
+
 /* The bigram table of the context (str_er_word_decode): 66 * 66 bytes, copied.  NULL removes the table.  The call waits for the
  * context's work.  A stream's contexts: str_er_stream_context.                                                                     */
 int str_er_set_bigram(str_er_ctx *ctx, const uint8_t *cost);
@@ -1239,6 +1331,15 @@ const str_er_run_read    *str_er_result_piece_reads(const str_er_result *r, int3
 const uint8_t            *str_er_result_piece_costs(const str_er_result *r, uint64_t *n_bytes);
 const str_er_split_part  *str_er_result_split_parts(const str_er_result *r, int32_t *n);
 const str_er_word_split  *str_er_result_word_splits(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_TRACK_READ (str_er_word_link): the word links sorted by (a, b); the word tracks; their members (word indices); one
+ * track index per word of str_er_result_words() (-1: not eligible); one match per word track; one cost per slot of the member array.
+ * Each returns NULL and 0 without the flag; a call without words returns empty arrays (not NULL).                                  */
+const str_er_word_link   *str_er_result_word_links(const str_er_result *r, int32_t *n);
+const str_er_word_track  *str_er_result_word_tracks(const str_er_result *r, int32_t *n);
+const int32_t            *str_er_result_word_track_members(const str_er_result *r, int32_t *n);
+const int32_t            *str_er_result_word_track_of_words(const str_er_result *r, int32_t *n);
+const str_er_track_match *str_er_result_track_matches(const str_er_result *r, int32_t *n);
+const int32_t            *str_er_result_track_member_costs(const str_er_result *r, int32_t *n);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

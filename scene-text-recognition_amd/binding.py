@@ -85,6 +85,18 @@ WANT_WORD_DECODE = 8388608
 # words_split_text_of_line / frame_line_split_text; the contract is at str_er_run_split).  Beside WANT_WORD_MATCH / WANT_WORD_DECODE both
 # work on the split sequence of a word: word_decode_src then indexes the word's parts
 WANT_RUN_SPLIT = 16777216
+# output option: the words of adjacent frames linked into word tracks and one lexicon match per word track over the cost rows of all
+# its members (needs WANT_LINE_LINKS and WANT_WORD_MATCH; Result.word_links / word_tracks / word_track_members / word_track_of_words /
+# track_matches / track_member_costs / word_track_text / text_track_match_text; the contract is at str_er_word_link)
+WANT_TRACK_READ = 33554432
+# str_er_word_link: a word a of frame f and a word b of the adjacent frame f + 1 whose boxes share inter > 0 pixels; link: linked at the call's threshold
+WORD_LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("inter", "<u4"), ("link", "<u4")])
+# str_er_word_track: members = word_track_members[first:first + count] (word indices, ascending), rep the one with the most pixels
+WORD_TRACK_DTYPE = np.dtype([("first_frame", "<u4"), ("last_frame", "<u4"), ("first", "<i4"), ("count", "<i4"), ("rep", "<i4"), ("text_track", "<i4")])
+# str_er_track_match: str_er_word_match over the summed costs of the usable members, their number and the word with the smallest own cost
+TRACK_MATCH_DTYPE = np.dtype([("entry", "<i4"), ("cost", "<i4"), ("second_entry", "<i4"), ("second_cost", "<i4"), ("free_cost", "<i4"), ("n_tried", "<i4"),
+                              ("n_used", "<i4"), ("best_member", "<i4")])
+assert WORD_LINK_DTYPE.itemsize == 16 and WORD_TRACK_DTYPE.itemsize == 24 and TRACK_MATCH_DTYPE.itemsize == 32
 # str_er_word_decode: per word, the cost of the cheapest string (-1: more than 32 runs, not decoded) and of the plain reading, the
 # characters of the string and the runs read, dropped and the characters inserted
 WORD_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
@@ -370,6 +382,16 @@ def load_library():
     L.str_er_match_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, vp]
     L.str_er_result_word_matches.argtypes = [vp, i32p]
     L.str_er_result_word_matches.restype = vp
+    L.str_er_set_word_link.argtypes = [vp, C.c_int32, C.c_int32]
+    L.str_er_word_links.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, i32p]
+    L.str_er_word_tracks_from_links.argtypes = [vp, vp, vp, C.c_int32, vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, i32p, vp]
+    L.str_er_match_tracks.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp]
+    L.str_er_match_tracks_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_uint32, C.c_int32,
+                                           C.c_int32, C.c_int32, vp, vp]
+    for fn in (L.str_er_result_word_links, L.str_er_result_word_tracks, L.str_er_result_word_track_members, L.str_er_result_word_track_of_words,
+               L.str_er_result_track_matches, L.str_er_result_track_member_costs):
+        fn.argtypes = [vp, i32p]
+        fn.restype = vp
     L.str_er_result_run_costs.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.str_er_result_run_costs.restype = vp
     L.str_er_result_run_probs.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -547,6 +569,8 @@ class Result:
         self._word_decode_chars = None
         self._word_decode_src = None
         self._run_splits = None    # with WANT_RUN_SPLIT: the tables behind run_splits / run_pieces / piece_reads / piece_costs / split_parts / word_splits
+        self._word_links = None    # with WANT_TRACK_READ: the tables behind word_links / word_tracks / word_track_members / word_track_of_words / track_matches / track_member_costs
+        self._word_tracks = self._word_track_members = self._word_track_of_words = self._track_matches = self._track_member_costs = None
         self._run_pieces = None
         self._piece_reads = None
         self._piece_costs = None
@@ -751,6 +775,55 @@ class Result:
     def frame_line_match_text(self, i: int) -> str:
         """With WANT_WORD_MATCH: the matched text of frame line i: words_match_text_of_line of its representative joined by one blank."""
         return " ".join(self.words_match_text_of_line(int(self.frame_lines[i]["rep"])))
+
+    def _track_read_table(self, table):
+        if table is None:
+            raise ValueError("the result has no word tracks (pass WANT_TRACK_READ / want_track_read=True)")
+        return table
+
+    @property
+    def word_links(self) -> np.ndarray:
+        """With WANT_TRACK_READ: WORD_LINK_DTYPE, the pairs of words of adjacent frames whose boxes overlap, sorted by (a, b)."""
+        return self._track_read_table(self._word_links)
+
+    @property
+    def word_tracks(self) -> np.ndarray:
+        """With WANT_TRACK_READ: WORD_TRACK_DTYPE per word track, by first frame, then by smallest member."""
+        return self._track_read_table(self._word_tracks)
+
+    @property
+    def word_track_members(self) -> np.ndarray:
+        """With WANT_TRACK_READ: the word indices the word tracks index (int32)."""
+        return self._track_read_table(self._word_track_members)
+
+    @property
+    def word_track_of_words(self) -> np.ndarray:
+        """With WANT_TRACK_READ: the word track of every word of words (int32), -1 for a word that is not eligible."""
+        return self._track_read_table(self._word_track_of_words)
+
+    @property
+    def track_matches(self) -> np.ndarray:
+        """With WANT_TRACK_READ: TRACK_MATCH_DTYPE per word track."""
+        return self._track_read_table(self._track_matches)
+
+    @property
+    def track_member_costs(self) -> np.ndarray:
+        """With WANT_TRACK_READ: the own cost of every member of word_track_members for its track's entry (int32), -1 without one."""
+        return self._track_read_table(self._track_member_costs)
+
+    def word_track_text(self, g: int) -> str:
+        """With WANT_TRACK_READ: the lexicon entry word track g takes, as it was given to set_lexicon; the representative's own
+        reading (word_text) where the track has no entry."""
+        e = int(self.track_matches[g]["entry"])
+        return self._lexicon[e] if 0 <= e < len(self._lexicon) else self.word_text(int(self.word_tracks[g]["rep"]))
+
+    def text_track_match_text(self, k: int) -> str:
+        """With WANT_TRACK_READ: the words of the representative line of text track k in order, each as its word track's text
+        (its own word_text where the line is no reading line), joined by one blank."""
+        lw = self.line_words[int(self.text_tracks[k]["rep"])]
+        of = self.word_track_of_words
+        ws = range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))
+        return " ".join(self.word_track_text(int(of[w])) if of[w] >= 0 else self.word_text(w) for w in ws)
 
     def _line_geom_table(self, table):
         if table is None:
@@ -1074,6 +1147,13 @@ class ERFilter:
                         res._text_tracks = table(L.str_er_result_text_tracks, TEXT_TRACK_DTYPE)
                         res._text_track_members = table(L.str_er_result_text_track_members, np.int32)
                         res._edge_feet = [self._edge_feet_of(rh, which) for which in (0, 1)]
+                        res._word_links = table(L.str_er_result_word_links, WORD_LINK_DTYPE)
+                        if res._word_links is not None:
+                            res._word_tracks = table(L.str_er_result_word_tracks, WORD_TRACK_DTYPE)
+                            res._word_track_members = table(L.str_er_result_word_track_members, np.int32)
+                            res._word_track_of_words = table(L.str_er_result_word_track_of_words, np.int32)
+                            res._track_matches = table(L.str_er_result_track_matches, TRACK_MATCH_DTYPE)
+                            res._track_member_costs = table(L.str_er_result_track_member_costs, np.int32)
             res.masks = table(L.str_er_result_masks, MASK_DTYPE)
             if res.masks is not None:
                 res.mask_bits = table(L.str_er_result_mask_bits, np.uint32, n64)
@@ -1132,7 +1212,7 @@ class ERFilter:
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
                     want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -1145,7 +1225,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -1267,7 +1347,7 @@ class ERFilter:
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
                          want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -1275,7 +1355,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1523,6 +1603,32 @@ class ERFilter:
         self._check(self.L.str_er_match_words(self.h, _np_ptr(cs) if len(cs) else None, len(cs), _np_ptr(fr) if len(fr) else None,
                                               _np_ptr(no) if len(no) else None, len(fr), _np_ptr(out)))
         return out[:len(fr)]
+
+    def set_word_link(self, num: int = 1, den: int = 2) -> None:
+        """str_er_set_word_link: two words of adjacent frames are linked from a Jaccard index of num / den of their boxes on
+        (str_er_word_link); each in 1 .. 65535."""
+        self._check(self.L.str_er_set_word_link(self.h, int(num), int(den)))
+        self._word_link = (int(num), int(den))
+
+    def word_links(self, feet, frames_of_lines, line_tracks, frame_wh, words):
+        """word_links (pure host) at the threshold of set_word_link."""
+        return word_links(feet, frames_of_lines, line_tracks, frame_wh, words, *getattr(self, "_word_link", (1, 2)))
+
+    def word_tracks_from_links(self, frames_of_lines, line_tracks, reading, words, links):
+        """word_tracks_from_links (pure host)."""
+        return word_tracks_from_links(frames_of_lines, line_tracks, reading, words, links)
+
+    def match_tracks(self, costs: np.ndarray, first_run, n_runs_of_word, track_first, track_count, members):
+        """str_er_match_tracks: the tracks members[track_first[g]:track_first[g] + track_count[g]] of the words [first_run[w],
+        first_run[w] + n_runs_of_word[w]) of the cost rows (n rows, 65) uint8 against the lexicon; returns (TRACK_MATCH_DTYPE per
+        track, int32 member costs per slot of members)."""
+        cs, fr, no, tf, tc, mem = _track_args(costs, first_run, n_runs_of_word, track_first, track_count, members)
+        out = np.zeros(max(1, len(tf)), TRACK_MATCH_DTYPE)
+        mc = np.zeros(max(1, len(mem)), np.int32)
+        opt = lambda a: _np_ptr(a) if len(a) else None
+        self._check(self.L.str_er_match_tracks(self.h, opt(cs), len(cs), opt(fr), opt(no), len(fr), opt(tf), opt(tc), opt(mem), len(mem), len(tf),
+                                               _np_ptr(out), _np_ptr(mc)))
+        return out[:len(tf)], mc[:len(mem)]
 
     def set_bigram(self, table) -> None:
         """str_er_set_bigram: the (66, 66) uint8 table of the word decoder (str_er_word_decode; bigram_from_probs / bigram_from_words
@@ -2023,10 +2129,10 @@ def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: 
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False, track_read=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (track_read, WANT_TRACK_READ), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -2095,6 +2201,86 @@ def quad_from_hull(hull) -> np.ndarray:
         raise StrErError(rc, "str_er_quad_from_hull")
     g["count"] = len(pts)
     return g[0]
+
+
+def _track_args(costs, first_run, n_runs_of_word, track_first, track_count, members):
+    cs = np.ascontiguousarray(costs, dtype=np.uint8).reshape(-1, 65)
+    fr = np.ascontiguousarray(first_run, dtype=np.int32).reshape(-1)
+    no = np.ascontiguousarray(n_runs_of_word, dtype=np.int32).reshape(-1)
+    tf = np.ascontiguousarray(track_first, dtype=np.int32).reshape(-1)
+    tc = np.ascontiguousarray(track_count, dtype=np.int32).reshape(-1)
+    mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+    if len(fr) != len(no) or len(tf) != len(tc):
+        raise ValueError("first_run and n_runs_of_word: one value per word each; track_first and track_count: one per track each")
+    return cs, fr, no, tf, tc, mem
+
+
+def match_tracks_host(costs: np.ndarray, first_run, n_runs_of_word, track_first, track_count, members, words, fold_case: bool = True, ins: int = 64,
+                      dele: int = 64, band: int = 2):
+    """str_er_match_tracks_host (pure host, one thread): ERFilter.match_tracks with the lexicon and the parameters as arguments."""
+    cs, fr, no, tf, tc, mem = _track_args(costs, first_run, n_runs_of_word, track_first, track_count, members)
+    words = list(words)
+    raw, off = _lexicon_bytes(words)
+    buf = np.frombuffer(raw, np.uint8) if raw else np.zeros(1, np.uint8)
+    out = np.zeros(max(1, len(tf)), TRACK_MATCH_DTYPE)
+    mc = np.zeros(max(1, len(mem)), np.int32)
+    opt = lambda a: _np_ptr(a) if len(a) else None
+    rc = load_library().str_er_match_tracks_host(opt(cs), len(cs), opt(fr), opt(no), len(fr), opt(tf), opt(tc), opt(mem), len(mem), len(tf), _np_ptr(buf),
+                                                 _np_ptr(off), len(words), LEXICON_FOLD_CASE if fold_case else 0, int(ins), int(dele), int(band),
+                                                 _np_ptr(out), _np_ptr(mc))
+    if rc != 0:
+        raise StrErError(rc, "str_er_match_tracks_host")
+    return out[:len(tf)], mc[:len(mem)]
+
+
+def word_links(feet, frames_of_lines, line_tracks, frame_wh, words, num: int = 1, den: int = 2):
+    """str_er_word_links (pure host): the reading lines and the word links of the words (LINE_WORD_DTYPE; line and the box are read)
+    of the lines with these feet (LINE_FOOT_DTYPE; pixels are read), frames and text tracks; frame_wh: (n frames, 2) level-0 sizes.
+    Returns (reading uint8 per line, links WORD_LINK_DTYPE)."""
+    ft = np.ascontiguousarray(feet, dtype=LINE_FOOT_DTYPE).reshape(-1)
+    fr = np.ascontiguousarray(frames_of_lines, dtype=np.uint32).reshape(-1)
+    lt = np.ascontiguousarray(line_tracks, dtype=np.int32).reshape(-1)
+    wh = np.ascontiguousarray(frame_wh, dtype=np.int32).reshape(-1, 2)
+    ws = np.ascontiguousarray(words, dtype=LINE_WORD_DTYPE).reshape(-1)
+    n = len(ft)
+    if len(fr) != n or len(lt) != n:
+        raise ValueError("frames_of_lines and line_tracks need one entry per line")
+    reading = np.zeros(max(1, n), np.uint8)
+    opt = lambda a: _np_ptr(a) if len(a) else None
+    L, nl = load_library(), C.c_int32()
+    rc = L.str_er_word_links(opt(ft), opt(fr), opt(lt), n, opt(wh), len(wh), opt(ws), len(ws), int(num), int(den), _np_ptr(reading), None, 0, C.byref(nl))
+    if rc != 0:
+        raise StrErError(rc, "str_er_word_links")
+    links = np.zeros(max(1, nl.value), WORD_LINK_DTYPE)
+    rc = L.str_er_word_links(opt(ft), opt(fr), opt(lt), n, opt(wh), len(wh), opt(ws), len(ws), int(num), int(den), _np_ptr(reading), _np_ptr(links), len(links),
+                             C.byref(nl))
+    if rc != 0:
+        raise StrErError(rc, "str_er_word_links")
+    return reading[:n], links[:nl.value]
+
+
+def word_tracks_from_links(frames_of_lines, line_tracks, reading, words, links):
+    """str_er_word_tracks_from_links (pure host): the word tracks from the reading flags and the links of word_links.  Returns
+    (track_of_words int32, tracks WORD_TRACK_DTYPE, members int32)."""
+    fr = np.ascontiguousarray(frames_of_lines, dtype=np.uint32).reshape(-1)
+    lt = np.ascontiguousarray(line_tracks, dtype=np.int32).reshape(-1)
+    rd = np.ascontiguousarray(reading, dtype=np.uint8).reshape(-1)
+    ws = np.ascontiguousarray(words, dtype=LINE_WORD_DTYPE).reshape(-1)
+    lk = np.ascontiguousarray(links, dtype=WORD_LINK_DTYPE).reshape(-1)
+    n, nw = len(fr), len(ws)
+    if len(lt) != n or len(rd) != n:
+        raise ValueError("line_tracks and reading need one entry per line")
+    of = np.zeros(max(1, nw), np.int32)
+    tr = np.zeros(max(1, nw), WORD_TRACK_DTYPE)
+    mem = np.zeros(max(1, nw), np.int32)
+    opt = lambda a: _np_ptr(a) if len(a) else None
+    ntr = C.c_int32()
+    rc = load_library().str_er_word_tracks_from_links(opt(fr), opt(lt), opt(rd), n, opt(ws), nw, opt(lk), len(lk), _np_ptr(of), _np_ptr(tr), len(tr), C.byref(ntr),
+                                                      _np_ptr(mem))
+    if rc != 0:
+        raise StrErError(rc, "str_er_word_tracks_from_links")
+    tr = tr[:ntr.value]
+    return of[:nw], tr, mem[:int(tr["count"].sum()) if len(tr) else 0]
 
 
 def text_tracks_from_links(feet: np.ndarray, frames_of_lines, pairs: np.ndarray, links: np.ndarray, num: int = 1, den: int = 2):
@@ -2368,6 +2554,14 @@ class FrameStream:
             if rc != 0:
                 raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
 
+    def set_word_link(self, num: int = 1, den: int = 2) -> None:
+        """str_er_set_word_link on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_word_link(ctx, int(num), int(den))
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
     def set_bigram(self, table) -> None:
         """str_er_set_bigram on every context of the stream: what WANT_WORD_DECODE submissions need."""
         t = None if table is None else _bigram_table(table)
@@ -2402,23 +2596,23 @@ class FrameStream:
         return slot.value, arr
 
     def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit(self.h, slot, w, h, 3 * w, 3 * w * h, n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
         """The staging buffer holds n_frames tightly packed NV12 frames (w * h * 3 / 2 bytes each)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_nv12(self.h, slot, w, h, w, w * (h + h // 2), n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         if a.ndim == 3:
             a = a[None]
@@ -2436,21 +2630,21 @@ class FrameStream:
         return int(t.value)
 
     def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
         """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
         return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
 
     def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
         """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
         return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
 
     def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
         """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         arr = (ImageRef * max(1, len(refs)))(*refs)

@@ -17,6 +17,7 @@
 // the words (str_er_words_from_runs, words_host.cpp).  str_er_feet_words runs the same kernel on uploaded footprints.
 // STR_ER_WANT_RUN_READ behind that, with a second enqueue and wait: run_read_stage (api_run_read.cpp).
 #include "str_er_ctx.h"
+#include "track_read_rules.h"
 
 #include <numeric>
 
@@ -699,7 +700,10 @@ int fill_geometry(str_er_ctx *c, str_er_result *r, const GeomPass &GP)
 
 // the runs and words of the lines (what k_foot_words left), and with read the reading of every run: T.lines is the table k_foot_words
 // read, and its footprints are still in c->foot_bits
-int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode, bool split)
+// track: the word links and word tracks of STR_ER_WANT_TRACK_READ on the host before the reading (the text tracks of r are made: fill_links),
+// the track match behind the matcher (frame_of: the frame of every line, frame_wh: the level-0 sizes of the frames)
+int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode, bool split, bool track,
+               const std::vector<uint32_t> &frame_of, const std::vector<int32_t> &frame_wh)
 {
     const auto   t2 = std::chrono::steady_clock::now();
     const size_t n_lines = r->line_feet.size();
@@ -719,10 +723,29 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
                 for (int32_t k = 0; k < r->line_words[t].n_runs; ++k) slot_of[(size_t)r->line_words[t].first_run + (size_t)k] = WP.slots[t].first + (uint32_t)k;
             if (const int rcs = run_cuts_collect(c, r->line_runs, slot_of, r->run_splits, r->run_pieces); rcs != STR_ER_OK) return rcs;
         }
+        const TrackReadOut tro{&r->word_tracks, &r->word_track_members, &r->track_matches, &r->track_member_costs};
+        if (track) {
+            if (!r->have_line_links || !match) return fail(c, STR_ER_EHIP, "track read: no text tracks or no matcher (internal error)");
+            for (const str_er_line_word &w : r->words)
+                if (w.line < 0 || (size_t)w.line >= n_lines || !str_er_tr::box_ok(w)) return fail(c, STR_ER_EHIP, "track read: a word outside the lines (internal error)");
+            const auto           t3 = std::chrono::steady_clock::now();
+            std::vector<uint8_t> reading(n_lines);
+            str_er_tr::reading_lines(r->line_feet.data(), frame_of.data(), r->line_tracks.data(), (int32_t)n_lines, reading.data());
+            str_er_tr::word_links(frame_of.data(), r->line_tracks.data(), reading.data(), (int32_t)n_lines, frame_wh.data(), r->words.data(), (int32_t)r->words.size(),
+                                  c->wlink_num, c->wlink_den, r->word_links);
+            str_er_tr::word_tracks(frame_of.data(), r->line_tracks.data(), reading.data(), r->words.data(), (int32_t)r->words.size(), r->word_links.data(),
+                                   (int32_t)r->word_links.size(), r->word_track_of_words, r->word_tracks, r->word_track_members);
+            for (const str_er_word_track &G : r->word_tracks)
+                if (G.count > str_er_tr::MAX_MEMBERS) return fail(c, STR_ER_ECAPACITY, "STR_ER_WANT_TRACK_READ: a word track of more than 65536 members");
+            if (c->dbg_stats)        // developer aid (tools/dev_track_read.py)
+                std::fprintf(stderr, "[str_er] track read: %zu words, %zu word links, %zu word tracks, %zu members, host %.3f ms\n", r->words.size(), r->word_links.size(),
+                             r->word_tracks.size(), r->word_track_members.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t3).count());
+        }
         if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features, match ? &wmo : nullptr,
-                                           decode ? &wdo : nullptr, split ? &rp : nullptr);
+                                           decode ? &wdo : nullptr, split ? &rp : nullptr, track ? &tro : nullptr);
             rcr != STR_ER_OK)
             return rcr;
+        r->have_track_read = track;
         r->have_run_splits = split;
         r->have_run_reads = true;
         r->have_word_matches = match;
@@ -766,7 +789,7 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
     if ((rc = fill_frame_lines(c, r, frame_of, pyr_of, S.feet.pairs, n_fl)) != STR_ER_OK) return rc;
     if (want.links && (rc = fill_links(c, b, r, frame_of, T, S.links)) != STR_ER_OK) return rc;
     if (want.geom && (rc = fill_geometry(c, r, S.geom)) != STR_ER_OK) return rc;
-    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split)) != STR_ER_OK) return rc;
+    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split, want.track, frame_of, b.frame_wh)) != STR_ER_OK) return rc;
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
                              "%zu bytes back, host %.3f ms before + %.3f ms after the device\n",

@@ -7,7 +7,8 @@
 // the decoder (word_decode_kernels.h) follows in the same way, on unfolded cost rows: the matcher's where its lexicon does not fold, else
 // those of a second k_run_costs into the decoder's own buffer.  With STR_ER_WANT_RUN_SPLIT (str_er_feet_split: the tiles alone) the pieces of
 // the cut runs (api_run_split.cpp) are tiles behind the runs' in the same atlas and rows behind the runs' in the same cost buffer, and
-// k_split_words (run_split_kernels.h) goes between k_run_costs and the matcher / decoder, which then read the parts' rows.
+// k_split_words (run_split_kernels.h) goes between k_run_costs and the matcher / decoder, which then read the parts' rows.  With
+// STR_ER_WANT_TRACK_READ the track match (api_track_read.cpp) follows the matcher on the same rows, for the word tracks the host made before.
 #include "str_er_ctx.h"
 #include "run_split_kernels.h"
 
@@ -15,7 +16,7 @@ namespace str_er_host {
 
 int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
                    const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q,
-                   const WordMatchOut *match, const WordDecodeOut *decode, const RunPieces *pieces)
+                   const WordMatchOut *match, const WordDecodeOut *decode, const RunPieces *pieces, const TrackReadOut *track)
 {
     // n_run runs and behind them n_pc pieces (str_er_run_split): n tiles, and whatever is per run below takes the first n_run of them
     const size_t n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0, n = n_run + n_pc;
@@ -31,6 +32,13 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         match->matches->assign(n_words, str_er_word_match{-1, -1, -1, -1, 0, 0});
         match->costs->assign(65 * n_run, 0);
         match->probs->assign((size_t)c->svm.k * n_run, 0.0);
+    }
+    // STR_ER_WANT_TRACK_READ: the track match behind the matcher, on the rows and the (first, n) arrays it read
+    const bool   wtrack = track && wmatch;
+    const size_t n_tracks = wtrack ? track->tracks->size() : 0, n_members = wtrack ? track->members->size() : 0;
+    if (wtrack) {
+        track->matches->assign(n_tracks, str_er_track_match{-1, -1, -1, -1, 0, 0, 0, -1});
+        track->member_costs->assign(n_members, -1);
     }
     const bool   wdecode = decode && reads;
     const size_t n_dwords = wdecode ? decode->words->size() : 0;
@@ -184,6 +192,21 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         } else
             launch_word_match(s, c->lex, c->wm_prm, WD.costs, WD.first, WD.n_of, (int)n_words, WD.partial, WD.matches);
     }
+    TmTab TD{};
+    if (wtrack && n_tracks > 0) {
+        std::vector<int32_t> tfirst(n_tracks), tcount(n_tracks);
+        for (size_t g = 0; g < n_tracks; ++g) {
+            const str_er_word_track &G = (*track->tracks)[g];
+            if (G.first < 0 || G.count < 0 || (size_t)G.first + (size_t)G.count > n_members)
+                return fail(c, STR_ER_EHIP, "track read: a track outside the member array (internal error)");
+            tfirst[g] = G.first; tcount[g] = G.count;
+        }
+        for (const int32_t w : *track->members)
+            if (w < 0 || (size_t)w >= n_words) return fail(c, STR_ER_EHIP, "track read: a member outside the words (internal error)");
+        if ((rc = track_match_enqueue(c, s, wsplit ? SD.part_costs : WD.costs, wsplit ? SD.slot : WD.first, wsplit ? SD.n_parts : WD.n_of, tfirst.data(),
+                                      tcount.data(), track->members->data(), n_members, n_tracks, TD)) != STR_ER_OK)
+            return rc;
+    }
     const uint8_t *dcosts = wmatch && !c->lex.fold ? WD.costs : DD.costs;          // (the decoder's rows are never folded)
     if (wdecode) {
         for (size_t w = 0; w < n_dwords; ++w) { DH.first[w] = (*decode->words)[w].first_run; DH.n_of[w] = (*decode->words)[w].n_runs; }
@@ -217,6 +240,10 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         if (n_words > 0) HIP_TRY(c, hipMemcpyAsync(match->matches->data(), WD.matches, sizeof(str_er_word_match) * n_words, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(match->costs->data(), WD.costs, 65 * n_run, hipMemcpyDeviceToHost, s));
         HIP_TRY(c, hipMemcpyAsync(match->probs->data(), buf.prob, 8 * (size_t)m->k * n_run, hipMemcpyDeviceToHost, s));
+    }
+    if (wtrack && n_tracks > 0) {
+        HIP_TRY(c, hipMemcpyAsync(track->matches->data(), TD.matches, sizeof(str_er_track_match) * n_tracks, hipMemcpyDeviceToHost, s));
+        if (n_members > 0) HIP_TRY(c, hipMemcpyAsync(track->member_costs->data(), TD.member_cost, 4 * n_members, hipMemcpyDeviceToHost, s));
     }
     if (wdecode) {
         if (n_dwords > 0) {

@@ -78,10 +78,10 @@ try {
     L.n_groups = len_first[33];      // ([0] = [1] = 0: no entry is shorter than 1)
     L.fold = (flags & STR_ER_LEXICON_FOLD_CASE) ? 1 : 0;
     const size_t o_lens = 0, o_goff = 512, o_index = align_up(o_goff + 4 * (size_t)L.n_groups, 256), o_chars = align_up(o_index + 4 * (size_t)L.n_groups * WM_GROUP, 256),
-                 total = o_chars + 4 * n_words32;
+                 o_pos = align_up(o_chars + 4 * n_words32, 256), total = o_pos + 4 * (size_t)n;
     std::vector<uint8_t> img(total, 0);
     uint32_t *goff = reinterpret_cast<uint32_t *>(img.data() + o_goff), *chars = reinterpret_cast<uint32_t *>(img.data() + o_chars);
-    int32_t  *index = reinterpret_cast<int32_t *>(img.data() + o_index);
+    int32_t  *index = reinterpret_cast<int32_t *>(img.data() + o_index), *pos = reinterpret_cast<int32_t *>(img.data() + o_pos);
     std::fill(index, index + (size_t)L.n_groups * WM_GROUP, -1);
     std::memcpy(img.data() + o_lens, len_first, sizeof(len_first));
     std::memcpy(img.data() + o_lens + sizeof(len_first), len_count, sizeof(len_count));
@@ -95,6 +95,7 @@ try {
         const int     len = offsets[e + 1] - offsets[e];
         const int32_t slot = placed[len]++, g = len_first[len] + slot / WM_GROUP, lane = slot % WM_GROUP;
         index[(size_t)g * WM_GROUP + lane] = e;
+        pos[e] = g * WM_GROUP + lane;
         for (int j = 0; j < len; ++j)
             chars[goff[g] + (size_t)(j / 4) * WM_GROUP + lane] |= (uint32_t)wm::char_label((unsigned char)bytes[offsets[e] + j]) << (8 * (j % 4));
     }
@@ -106,6 +107,7 @@ try {
     L.goff = reinterpret_cast<const uint32_t *>(c->lexicon.d() + o_goff);
     L.index = reinterpret_cast<const int32_t *>(c->lexicon.d() + o_index);
     L.chars = reinterpret_cast<const uint32_t *>(c->lexicon.d() + o_chars);
+    L.pos = reinterpret_cast<const int32_t *>(c->lexicon.d() + o_pos);
     c->lex = L;
     c->lex_n = n; c->lex_flags = flags;
     return STR_ER_OK;

@@ -30,6 +30,13 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
     const uint32_t sup = STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP;
     struct Rule { bool bad; int code; const char *msg; };
     const Rule rules[] = {
+        // STR_ER_WANT_TRACK_READ rides on STR_ER_WANT_LINE_LINKS (the text tracks) and on STR_ER_WANT_WORD_MATCH (the cost rows and the
+        // lexicon): refused without either and where either is refused, first of all, so that the refusal names this flag; a call
+        // without the flag meets no new rule
+        {k.strip && any(STR_ER_WANT_TRACK_READ), STR_ER_EINVAL, "STR_ER_WANT_TRACK_READ is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_TRACK_READ), STR_ER_EINVAL, "STR_ER_WANT_TRACK_READ needs frames (not the per-plane calls)"},
+        {any(STR_ER_WANT_TRACK_READ) && !any(STR_ER_WANT_LINE_LINKS), STR_ER_EINVAL, "STR_ER_WANT_TRACK_READ needs STR_ER_WANT_LINE_LINKS"},
+        {any(STR_ER_WANT_TRACK_READ) && !any(STR_ER_WANT_WORD_MATCH), STR_ER_EINVAL, "STR_ER_WANT_TRACK_READ needs STR_ER_WANT_WORD_MATCH"},
         // STR_ER_WANT_RUN_SPLIT rides on STR_ER_WANT_RUN_READ as STR_ER_WANT_WORD_MATCH does; its parameters have defaults, so it needs no
         // state of the context; a call without the flag meets no new rule
         {k.strip && any(STR_ER_WANT_RUN_SPLIT), STR_ER_EINVAL, "STR_ER_WANT_RUN_SPLIT is not supported by the strip path (str_er_strip_merge)"},

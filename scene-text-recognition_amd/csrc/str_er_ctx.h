@@ -25,6 +25,7 @@
 #include "ocr_kernels.h"
 #include "track_kernels.h"
 #include "word_match_kernels.h"
+#include "track_match_kernels.h"
 #include "word_decode_kernels.h"
 #include "er_group.h"
 #include "flood_order.h"
@@ -167,6 +168,12 @@ struct str_er_result {
     std::vector<str_er_split_part> split_parts;
     std::vector<str_er_word_split> word_splits;
     bool have_run_splits = false;
+    std::vector<str_er_word_link> word_links;    // STR_ER_WANT_TRACK_READ: the word links, the word tracks, their members, the track of every word of words,
+    std::vector<str_er_word_track> word_tracks;  // one match per word track and one cost per slot of the member array
+    std::vector<int32_t> word_track_members, word_track_of_words;
+    std::vector<str_er_track_match> track_matches;
+    std::vector<int32_t> track_member_costs;
+    bool have_track_read = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -294,6 +301,9 @@ struct str_er_ctx {
     int32_t  lex_n = 0; uint32_t lex_flags = 0;
     WmParams wm_prm{64, 64, 2};
     PairBuf  wm_tab;                  // cost rows | first run, run count per word | chunk keys | matches
+    // STR_ER_WANT_TRACK_READ / str_er_match_tracks (str_er_set_word_link)
+    int32_t  wlink_num = 1, wlink_den = 2;
+    PairBuf  tm_tab;                  // first member, member count per track | members | chunk keys | matches | member costs
     // STR_ER_WANT_WORD_DECODE / str_er_set_bigram / str_er_decode_words
     DevBuf   bigram;                  // the 66 x 66 table (bigram_set: one is set)
     bool     bigram_set = false;
@@ -580,6 +590,7 @@ struct LineStageWants {
     bool read = false;        // STR_ER_WANT_RUN_READ: the reading of every run (k_run_tiles and the scorer behind the stage's wait, with a wait of their own)
     bool match = false;       // STR_ER_WANT_WORD_MATCH: every word against the lexicon (k_run_costs and the matcher behind the scorer)
     bool decode = false;      // STR_ER_WANT_WORD_DECODE: every word under the bigram table (k_run_costs and the decoder behind the scorer)
+    bool track = false;       // STR_ER_WANT_TRACK_READ: the word links and word tracks on the host before the reading, k_track_match behind the matcher
     bool split = false;       // STR_ER_WANT_RUN_SPLIT: the cuts of every run (k_run_cuts behind k_foot_words, down with the stage's wait), the pieces read with the runs, k_split_words behind the scorer
 };
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
@@ -659,9 +670,30 @@ bool rs_word_slots(const str_er_run_split *splits, const int32_t *first_run, con
 // false where a word's parts lie outside its slots
 bool rs_compact(const RsTab &H, const std::vector<int32_t> &slot, uint64_t n_slots, str_er_word_split *word_splits, str_er_split_part *parts, uint8_t *part_costs,
                 uint64_t *n_parts);
+// track (optional, with match): STR_ER_WANT_TRACK_READ -- the track match of the word tracks (made on the host before the call) behind
+// the matcher on s, on the rows and the (first, n) arrays the matcher read; its tables back with the same wait
+struct TrackReadOut {
+    const std::vector<str_er_word_track> *tracks;
+    const std::vector<int32_t> *members;
+    std::vector<str_er_track_match> *matches;
+    std::vector<int32_t> *member_costs;
+};
 int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
                    const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q,
-                   const WordMatchOut *match = nullptr, const WordDecodeOut *decode = nullptr, const RunPieces *pieces = nullptr);
+                   const WordMatchOut *match = nullptr, const WordDecodeOut *decode = nullptr, const RunPieces *pieces = nullptr,
+                   const TrackReadOut *track = nullptr);
+// ---- defined in api_track_read.cpp
+// the layout of c->tm_tab for n_tracks tracks over a member array of n_members (base: either side of the pair, or null for the size alone)
+struct TmTab {
+    int32_t *first, *count, *members; uint64_t *partial; str_er_track_match *matches; int32_t *member_cost;
+    size_t up_bytes;        // first | count | members lie at the front: what goes up
+    size_t o_matches, o_mcost, bytes;
+};
+TmTab tm_layout(uint8_t *base, size_t n_tracks, size_t n_members, int n_chunks);
+// the track tables into c->tm_tab and up on s, the two kernels behind what is on s (rows, first, n_of: on the device), the member costs
+// preset to -1; D receives the device side of the layout (matches and member_cost come down from there)
+int track_match_enqueue(str_er_ctx *c, hipStream_t s, const uint8_t *d_rows, const int32_t *d_first, const int32_t *d_n_of, const int32_t *track_first,
+                        const int32_t *track_count, const int32_t *members, size_t n_members, size_t n_tracks, TmTab &D);
 // ---- defined in api_word_match.cpp
 // the layout of c->wm_tab for n_runs cost rows and n_words words (base: either side of the pair, or null for the size alone)
 struct WmTab {

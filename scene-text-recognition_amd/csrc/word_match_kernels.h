@@ -22,6 +22,7 @@ struct WmLexDev {
     const int32_t  *len_count;  // [34] [len] entries shorter than len, [33] = n
     int32_t n_groups;
     int32_t fold;               // the lexicon's fold-case flag
+    const int32_t  *pos;        // [n] the slot g * 64 + lane of entry i in `index`: its inverse (the track match reads the winner's labels by it)
 };
 
 struct WmParams { int32_t ins, del, band; };

@@ -634,6 +634,55 @@ public:
         return s;
     }
 
+    // The words of adjacent frames linked into word tracks and one lexicon match per word track over the cost rows of all its members
+    // (STR_ER_WANT_TRACK_READ; the contract is at str_er_word_link in include/str_er.h): the links, the tracks, the word indices their
+    // first / count index, the track of every word (-1: not eligible), one match per track and one cost per slot of the member array.
+    // Needs STR_ER_WANT_LINE_LINKS and STR_ER_WANT_WORD_MATCH.
+    struct TrackRead {
+        std::vector<str_er_word_link>   links;
+        std::vector<str_er_word_track>  tracks;
+        std::vector<int32_t>            members, track_of_words;
+        std::vector<str_er_track_match> matches;
+        std::vector<int32_t>            member_costs;
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static TrackRead track_read(const str_er_result *r)
+    {
+        TrackRead out;
+        int32_t n = 0;
+        if (const str_er_word_link *p = str_er_result_word_links(r, &n)) out.links.assign(p, p + n);
+        if (const str_er_word_track *p = str_er_result_word_tracks(r, &n)) out.tracks.assign(p, p + n);
+        if (const int32_t *p = str_er_result_word_track_members(r, &n)) out.members.assign(p, p + n);
+        if (const int32_t *p = str_er_result_word_track_of_words(r, &n)) out.track_of_words.assign(p, p + n);
+        if (const str_er_track_match *p = str_er_result_track_matches(r, &n)) out.matches.assign(p, p + n);
+        if (const int32_t *p = str_er_result_track_member_costs(r, &n)) out.member_costs.assign(p, p + n);
+        return out;
+    }
+    // two words of adjacent frames are linked from a Jaccard index of num / den of their boxes on (str_er_set_word_link)
+    void set_word_link(int num, int den) { check(str_er_set_word_link(ctx_.get(), num, den)); }
+    // the tracks members[track_first[g] .. track_first[g] + track_count[g]) of the words of the caller's cost rows against the lexicon
+    // (str_er_match_tracks): the records, and in member_cost one cost per slot of members
+    std::vector<str_er_track_match> match_tracks(const std::vector<uint8_t> &costs, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs,
+                                                 const std::vector<int32_t> &track_first, const std::vector<int32_t> &track_count,
+                                                 const std::vector<int32_t> &members, std::vector<int32_t> &member_cost)
+    {
+        if (first_run.size() != n_runs.size() || track_first.size() != track_count.size() || costs.size() % 65)
+            throw std::invalid_argument("match_tracks: 65 bytes a run, one span a word, one span a track");
+        std::vector<str_er_track_match> out(track_first.size());
+        member_cost.assign(members.size(), -1);
+        check(str_er_match_tracks(ctx_.get(), costs.empty() ? nullptr : costs.data(), (int32_t)(costs.size() / 65), first_run.empty() ? nullptr : first_run.data(),
+                                  n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(), track_first.empty() ? nullptr : track_first.data(),
+                                  track_count.empty() ? nullptr : track_count.data(), members.empty() ? nullptr : members.data(), (int32_t)members.size(),
+                                  (int32_t)track_first.size(), out.empty() ? nullptr : out.data(), member_cost.empty() ? nullptr : member_cost.data()));
+        return out;
+    }
+    // the string of word track g: the lexicon entry it takes (as given in `lexicon`), its representative's own reading where it has none
+    static std::string word_track_text(const LineWords &lw, const RunReads &rd, const TrackRead &tr, const std::vector<std::string> &lexicon, size_t g)
+    {
+        const int32_t e = tr.matches.at(g).entry;
+        return e >= 0 && (size_t)e < lexicon.size() ? lexicon[(size_t)e] : word_text(lw, rd, (size_t)tr.tracks.at(g).rep);
+    }
+
     // Every word decoded under a character bigram table (STR_ER_WANT_WORD_DECODE; the contract is at str_er_word_decode in
     // include/str_er.h): one record per word of LineWords::words, 64 label bytes and 64 source bytes per word (0xFF past n_chars), and
     // the cost bytes and class probabilities of the runs as in WordMatches.  Needs STR_ER_WANT_RUN_READ and a table in the context.
