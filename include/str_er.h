@@ -157,6 +157,14 @@ extern "C" {
  * STR_ER_ESTATE without; the context is usable afterwards.  Beside STR_ER_WANT_RUN_SPLIT the members' rows are those of their parts.
  * It changes no other output of the call and combines with every other STR_ER_WANT_* flag.                                          */
 #define STR_ER_WANT_TRACK_READ (33554432u)
+/* output option: every word of STR_ER_WANT_RUN_SPLIT decoded jointly over the lattice of all pieces of all its runs under the bigram table
+ * of str_er_set_bigram: segmentation and string come out together (str_er_result_lattice_decodes / _lattice_decode_chars /
+ * _lattice_decode_src / _lattice_parts; the contract is at str_er_lattice_decode).  Needs STR_ER_WANT_RUN_SPLIT (and through it
+ * STR_ER_WANT_RUN_READ): STR_ER_EINVAL without it and wherever that flag is refused (the strip path, the per-plane calls), and a table:
+ * STR_ER_ESTATE without one; the context is usable afterwards.  It needs no lexicon and is independent of STR_ER_WANT_WORD_DECODE and
+ * _WORD_MATCH.  Every call that honours _RUN_SPLIT honours it.  It changes no other output of the call and combines with every other
+ * STR_ER_WANT_* flag.                                                                                                               */
+#define STR_ER_WANT_LATTICE_DECODE (67108864u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -594,7 +602,8 @@ typedef struct str_er_track_match {
  *     and is made for every m.  Hence cost <= read_cost, n_sub + n_ins = n_chars and n_sub + n_del = m.  A word with m > 32 is not
  *     decoded: cost = -1 and the four counts are 0.
  *   Limits: runs are split in the image only with STR_ER_WANT_RUN_SPLIT (str_er_run_split), then the rows are those of the word's
- *     parts; one path per word, no margins; the table is the caller's.  The bridge from a table of
+ *     parts, a segmentation fixed ahead of the table; segmentation and string chosen together over all pieces are a separate output,
+ *     str_er_lattice_decode (STR_ER_WANT_LATTICE_DECODE); one path per word, no margins; the table is the caller's.  The bridge from a table of
  *     transition probabilities (str_er_bigram_from_probs) takes 65 x 65 doubles as P(b after a); whether the floats of the
  *     reference's dictionary/tp_table.txt are such probabilities has not been checked, and nothing beyond that reading is promised. */
 typedef struct str_er_word_decode {
@@ -634,7 +643,8 @@ typedef struct str_er_word_decode {
  *     own minima (the matcher's free_cost).  Hence cost <= read_cost and n_parts >= n_runs.  The string of a split word is the first
  *     arg min of the row of each part.
  *   Limits: at most 3 cuts a run; the cut follows the upright column profile, no slanted or curved cuts; the segmentation is chosen
- *     per run from the scorer alone, ahead of any lexicon or bigram table: there is no joint decode over the piece lattice.
+ *     per run from the scorer alone, ahead of any lexicon or bigram table: this output makes no joint decode over the piece lattice.
+ *     That is a separate output, str_er_lattice_decode (STR_ER_WANT_LATTICE_DECODE): one pass per word over all pieces under the table.
  *   Beside the matcher and the decoder: with STR_ER_WANT_RUN_SPLIT next to STR_ER_WANT_WORD_MATCH or _WORD_DECODE both run on the split
  *     sequence instead of the runs: m in their contracts is n_parts, with the same limit of 32, and src of the decoder indexes the
  *     word's parts.  run_costs and run_probs stay per run; the rows of the pieces (str_er_result_piece_costs) are folded where the
@@ -661,6 +671,48 @@ typedef struct str_er_word_split {
     int32_t  cost, read_cost;             /*  8, 12                                   */
 } str_er_word_split;         /* 16 bytes; one per word                                */
 #define STR_ER_RUN_SPLIT_MAX_W 1024
+
+/* The joint decode of a word over its piece lattice and the bigram table (STR_ER_WANT_LATTICE_DECODE, str_er_lattice_decode_words): one
+ * Viterbi pass per word over the lattice of all pieces of all its runs, under the table of str_er_word_decode; the segmentation of the
+ * runs and the string come out together.  A definition of this library; integers only, exact, and the host states the same rules
+ * (str_er_lattice_decode_words_host).
+ *   Lattice of a word with the runs r = 0 .. R-1: run r has k_r kept cuts (str_er_run_split.n_cuts), A_r = k_r + 1 atoms and the local
+ *     nodes 0 .. A_r.  The word's nodes are 0 .. N, N = sum of A_r, off_r = sum of A_r' over r' < r: local node i of run r is the
+ *     word's node off_r + i, and local node A_r of run r is local node 0 of run r + 1.  The edges are the pieces (i, j),
+ *     0 <= i < j <= A_r, of every run, from node off_r + i to node off_r + j; no edge crosses a run boundary.  The row C_{r,i,j} of an
+ *     edge is the unfolded 65-byte cost row of that piece, for (0, A_r) the run's own row.  The penalty of an edge is s = SPLIT if
+ *     i > 0, else 0: the term of str_er_run_split, with the SPLIT of str_er_set_run_split.
+ *   Symbols, the table B (66 x 66, E = 65), INS, DEL and INF = 2^20 are those of str_er_word_decode; INS and DEL come from
+ *     str_er_set_word_decode.
+ *   Recurrence, in int32: V_0[E] = 0, V_0[a] = INF for a < 65.  For n = 1 .. N, in run r with the local index j = n - off_r:
+ *     U_n[x] = INF for all x in 0 .. 65; then for i = 0 .. j - 1 in ascending order, with f = off_r + i: SUB, for b < 65:
+ *     S = min over a in 0 .. 65 of (V_f[a] + B[a][b]) + C_{r,i,j}[b] + s, the predecessor the smallest a that attains the minimum;
+ *     if S < U_n[b] then U_n[b] = S with the move (SUB, i, a).  DEL, if DEL > 0, for a in 0 .. 65: D = V_f[a] + DEL + s; if
+ *     D < U_n[a] then U_n[a] = D with the move (DEL, i).  The comparisons are strict: on equal values the smaller i wins, then SUB
+ *     before DEL, then the smaller a.  INS on U_n gives V_n exactly as in str_er_word_decode: if INS > 0, for c < 65:
+ *     I = min over b in 0 .. 64 of (U_n[b] + B[b][c]) + INS, with the smallest b; if I < U_n[c] then V_n[c] = I and the move is INS,
+ *     else V_n[c] = U_n[c]; always V_n[E] = U_n[E]: at most one inserted character per node.  cost = min over a in 0 .. 65 of
+ *     V_N[a] + B[a][E], with the smallest a; for N = 0 that is B[E][E].  INF is never the minimum, and every value is below 2^21.
+ *   Backtrack from the end state by the recorded moves, as in str_er_word_decode; a SUB or DEL step at node n also goes to the node
+ *     off_r + i.  The edges on the path, in word order, are the word's lattice parts, each (run, piece) as str_er_split_part with
+ *     piece = -1 for a whole run and the indices of str_er_result_split_parts.  The string has at most 2N <= 64 labels; the source
+ *     byte of a label is the word-relative index of the part it came from, bit 7 set on an inserted character (the part that ends at
+ *     the node it was inserted at).  Per word 64 bytes of labels and 64 bytes of sources, padded with 0xFF past n_chars.
+ *   Record: read_cost is str_er_word_decode's read_cost on the word's unsplit runs and is made for every word.  Hence
+ *     cost <= read_cost, n_sub + n_ins = n_chars, n_sub + n_del = n_parts and n_runs <= n_parts <= N.  A word with N > 32 is not
+ *     decoded: cost = -1, the four counts and n_parts are 0.
+ *   It follows: (1) if no run of the word has a cut, record, labels and sources equal str_er_word_decode's on the runs byte for
+ *     byte, and the parts are the runs; (2) cost <= the str_er_word_decode cost of the word on its runs; (3) cost <= the
+ *     str_er_word_decode cost on the split sequence of str_er_run_split plus SPLIT * (n_parts of that sequence - n_runs) -- both are
+ *     paths of the lattice (where those words are decoded at all).
+ *   Limits: the lattice is that of str_er_run_split (at most 3 upright cuts a run); one path per word, no margins; no lexicon
+ *     enters: the matcher still reads the split sequence of str_er_run_split.                                                          */
+typedef struct str_er_lattice_decode {
+    int32_t  cost, read_cost;             /*  0,  4                                   */
+    int32_t  n_chars, n_sub;              /*  8, 12                                   */
+    int32_t  n_del, n_ins;                /* 16, 20                                   */
+    int32_t  first_part, n_parts;         /* 24, 28: into the lattice part table      */
+} str_er_lattice_decode;     /* 32 bytes; one per word                                */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -1082,6 +1134,24 @@ int str_er_split_words_host(const str_er_run_split *splits, int32_t n_runs, cons
                             const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, int32_t split_cost,
                             str_er_word_split *word_splits, str_er_split_part *parts, int32_t cap_parts, int32_t *n_parts, uint8_t *part_costs);
 
+/* The joint decode (str_er_lattice_decode) of n_words words on the caller's rows, on the GPU, with the context's table, INS / DEL
+ * (str_er_set_word_decode) and SPLIT (str_er_set_run_split): the arguments up to n_words are those of str_er_split_words (the rows
+ * unfolded).  dec receives n_words records, chars and src 64 bytes per word each, parts the lattice parts of the words back to back in
+ * word order and *n_parts their number.  cap_parts too small -> STR_ER_ECAPACITY, *n_parts still set (it is at most the sum over
+ * the words' runs of n_cuts + 1).  STR_ER_ESTATE without a table; the validation is that of str_er_split_words.  It needs no model.   */
+int str_er_lattice_decode_words(str_er_ctx *ctx, const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs,
+                                int32_t n_pieces, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, str_er_lattice_decode *dec,
+                                uint8_t *chars, uint8_t *src, str_er_split_part *parts, int32_t cap_parts, int32_t *n_parts);
+/* The same rules on one host thread, with SPLIT, the table and INS / DEL as arguments (with the checks of str_er_set_run_split and
+ * str_er_set_word_decode).  Pure: no context, no GPU.                                                                              */
+int str_er_lattice_decode_words_host(const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs, int32_t n_pieces,
+                                     const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, int32_t split_cost, const uint8_t *bigram,
+                                     int32_t ins, int32_t del, str_er_lattice_decode *dec, uint8_t *chars, uint8_t *src, str_er_split_part *parts,
+                                     int32_t cap_parts, int32_t *n_parts);
+/* Statistics of the buffer of STR_ER_WANT_LATTICE_DECODE / str_er_lattice_decode_words: the bytes of its tables on the device (0: never
+ * made).  The pointer may be NULL.                                                                                                  */
+int str_er_lattice_decode_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -1331,6 +1401,13 @@ const str_er_run_read    *str_er_result_piece_reads(const str_er_result *r, int3
 const uint8_t            *str_er_result_piece_costs(const str_er_result *r, uint64_t *n_bytes);
 const str_er_split_part  *str_er_result_split_parts(const str_er_result *r, int32_t *n);
 const str_er_word_split  *str_er_result_word_splits(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_LATTICE_DECODE (str_er_lattice_decode): one record per word of str_er_result_words(), 64 label bytes and 64 source
+ * bytes per word, and the lattice parts of the words back to back in word order.  Each returns NULL and 0 without the flag; a call
+ * without words returns empty arrays (not NULL).                                                                                   */
+const str_er_lattice_decode *str_er_result_lattice_decodes(const str_er_result *r, int32_t *n);
+const uint8_t               *str_er_result_lattice_decode_chars(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t               *str_er_result_lattice_decode_src(const str_er_result *r, uint64_t *n_bytes);
+const str_er_split_part     *str_er_result_lattice_parts(const str_er_result *r, int32_t *n);
 /* With STR_ER_WANT_TRACK_READ (str_er_word_link): the word links sorted by (a, b); the word tracks; their members (word indices); one
  * track index per word of str_er_result_words() (-1: not eligible); one match per word track; one cost per slot of the member array.
  * Each returns NULL and 0 without the flag; a call without words returns empty arrays (not NULL).                                  */

@@ -89,6 +89,7 @@ WANT_RUN_SPLIT = 16777216
 # its members (needs WANT_LINE_LINKS and WANT_WORD_MATCH; Result.word_links / word_tracks / word_track_members / word_track_of_words /
 # track_matches / track_member_costs / word_track_text / text_track_match_text; the contract is at str_er_word_link)
 WANT_TRACK_READ = 33554432
+WANT_LATTICE_DECODE = 67108864
 # str_er_word_link: a word a of frame f and a word b of the adjacent frame f + 1 whose boxes share inter > 0 pixels; link: linked at the call's threshold
 WORD_LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("inter", "<u4"), ("link", "<u4")])
 # str_er_word_track: members = word_track_members[first:first + count] (word indices, ascending), rep the one with the most pixels
@@ -116,6 +117,9 @@ RUN_PIECE_DTYPE = np.dtype([("run", "<i4"), ("from", "<i4"), ("to", "<i4"), ("x0
 SPLIT_PART_DTYPE = np.dtype([("run", "<i4"), ("piece", "<i4")])
 WORD_SPLIT_DTYPE = np.dtype([("first_part", "<i4"), ("n_parts", "<i4"), ("cost", "<i4"), ("read_cost", "<i4")])
 assert RUN_SPLIT_DTYPE.itemsize == 32 and RUN_PIECE_DTYPE.itemsize == 32 and SPLIT_PART_DTYPE.itemsize == 8 and WORD_SPLIT_DTYPE.itemsize == 16
+LATTICE_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4"),
+                                 ("first_part", "<i4"), ("n_parts", "<i4")])
+assert LATTICE_DECODE_DTYPE.itemsize == 32
 # str_er_line_run: frame columns [x0, x1) and rows [y0, y1), half open; word: its row of the word table
 LINE_RUN_DTYPE = np.dtype([("x0", "<i4"), ("x1", "<i4"), ("y0", "<i4"), ("y1", "<i4"), ("pixels", "<u4"), ("word", "<i4")])
 # str_er_line_word: the runs line_runs[first_run:first_run + n_runs] of line `line`, their bounding box and pixels
@@ -415,6 +419,13 @@ def load_library():
         fn = getattr(L, "str_er_result_" + name)
         fn.argtypes, fn.restype = [vp, cnt], vp
     L.str_er_run_split_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    for name, cnt in (("lattice_decodes", i32p), ("lattice_decode_chars", C.POINTER(C.c_uint64)), ("lattice_decode_src", C.POINTER(C.c_uint64)), ("lattice_parts", i32p)):
+        fn = getattr(L, "str_er_result_" + name)
+        fn.argtypes, fn.restype = [vp, cnt], vp
+    L.str_er_lattice_decode_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_lattice_decode_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, i32p]
+    L.str_er_lattice_decode_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp,
+                                                   C.c_int32, i32p]
     L.str_er_set_run_split.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
     L.str_er_cuts_from_counts.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, i32p, C.POINTER(C.c_uint32)]
     L.str_er_feet_split.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, i32p, vp, C.c_int32, i32p, vp, vp,
@@ -569,6 +580,7 @@ class Result:
         self._word_decode_chars = None
         self._word_decode_src = None
         self._run_splits = None    # with WANT_RUN_SPLIT: the tables behind run_splits / run_pieces / piece_reads / piece_costs / split_parts / word_splits
+        self._lattice_decodes = None  # with WANT_LATTICE_DECODE: the tables behind lattice_decodes / lattice_decode_chars / lattice_decode_src / lattice_parts
         self._word_links = None    # with WANT_TRACK_READ: the tables behind word_links / word_tracks / word_track_members / word_track_of_words / track_matches / track_member_costs
         self._word_tracks = self._word_track_members = self._word_track_of_words = self._track_matches = self._track_member_costs = None
         self._run_pieces = None
@@ -704,6 +716,55 @@ class Result:
     def frame_line_split_text(self, i: int) -> str:
         """With WANT_RUN_SPLIT: the split text of frame line i: words_split_text_of_line of its representative joined by one blank."""
         return " ".join(self.words_split_text_of_line(int(self.frame_lines[i]["rep"])))
+
+    def _lattice_decode_table(self, table):
+        if table is None:
+            raise ValueError("the result has no lattice decodes (pass WANT_LATTICE_DECODE / want_lattice_decode=True)")
+        return table
+
+    @property
+    def lattice_decodes(self) -> np.ndarray:
+        """With WANT_LATTICE_DECODE: LATTICE_DECODE_DTYPE per word of words, in the same order."""
+        return self._lattice_decode_table(getattr(self, "_lattice_decodes", None))
+
+    @property
+    def lattice_decode_chars(self) -> np.ndarray:
+        """With WANT_LATTICE_DECODE: (n words, 64) uint8, the labels of every word's string, 0xFF past n_chars."""
+        return self._lattice_decode_table(getattr(self, "_lattice_decode_chars", None))
+
+    @property
+    def lattice_decode_src(self) -> np.ndarray:
+        """With WANT_LATTICE_DECODE: (n words, 64) uint8, per character the word-relative index of the lattice part it came from, bit 7
+        set on an inserted character; 0xFF past n_chars."""
+        return self._lattice_decode_table(getattr(self, "_lattice_decode_src", None))
+
+    @property
+    def lattice_parts(self) -> np.ndarray:
+        """With WANT_LATTICE_DECODE: SPLIT_PART_DTYPE, the lattice parts of the words back to back in word order (piece -1: a whole
+        run; the indices are those of split_parts)."""
+        return self._lattice_decode_table(getattr(self, "_lattice_parts", None))
+
+    def word_lattice_text(self, w: int) -> str:
+        """With WANT_LATTICE_DECODE: the jointly decoded string of word w; word_text(w) for a word that was not decoded (cost < 0)."""
+        d = self.lattice_decodes[w]
+        if int(d["cost"]) < 0:
+            return self.word_text(w)
+        return "".join(_OCR_ALPHABET[int(a)] for a in self.lattice_decode_chars[w, :int(d["n_chars"])])
+
+    def word_lattice_parts(self, w: int) -> np.ndarray:
+        """With WANT_LATTICE_DECODE: the lattice parts of word w (SPLIT_PART_DTYPE), the segmentation chosen with its string; none for
+        a word that was not decoded."""
+        d = self.lattice_decodes[w]
+        return self.lattice_parts[int(d["first_part"]):int(d["first_part"]) + int(d["n_parts"])]
+
+    def words_lattice_text_of_line(self, t: int) -> list:
+        """With WANT_LATTICE_DECODE: word_lattice_text of the words of line t, left to right."""
+        lw = self.line_words[t]
+        return [self.word_lattice_text(w) for w in range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))]
+
+    def frame_line_lattice_text(self, i: int) -> str:
+        """With WANT_LATTICE_DECODE: the jointly decoded text of frame line i: words_lattice_text_of_line of its representative joined by one blank."""
+        return " ".join(self.words_lattice_text_of_line(int(self.frame_lines[i]["rep"])))
 
     @property
     def word_decodes(self) -> np.ndarray:
@@ -1135,6 +1196,11 @@ class ERFilter:
                                 res._split_parts = table(L.str_er_result_split_parts, SPLIT_PART_DTYPE)
                                 res._word_splits = table(L.str_er_result_word_splits, WORD_SPLIT_DTYPE)
                                 res._run_costs = table(L.str_er_result_run_costs, np.uint8, n64).reshape(len(res._run_reads), 65)
+                                res._lattice_decodes = table(L.str_er_result_lattice_decodes, LATTICE_DECODE_DTYPE)
+                                if res._lattice_decodes is not None:
+                                    res._lattice_decode_chars = table(L.str_er_result_lattice_decode_chars, np.uint8, n64).reshape(-1, 64)
+                                    res._lattice_decode_src = table(L.str_er_result_lattice_decode_src, np.uint8, n64).reshape(-1, 64)
+                                    res._lattice_parts = table(L.str_er_result_lattice_parts, SPLIT_PART_DTYPE)
                             if res._word_matches is not None or res._word_decodes is not None:
                                 nr = len(res._run_reads)
                                 res._run_costs = table(L.str_er_result_run_costs, np.uint8, n64).reshape(nr, 65)
@@ -1212,7 +1278,7 @@ class ERFilter:
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
                     want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -1225,7 +1291,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -1347,7 +1413,7 @@ class ERFilter:
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
                          want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -1355,7 +1421,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1753,6 +1819,21 @@ class ERFilter:
         self._check(self.L.str_er_split_words(self.h, *a[0], *a[1]))
         return _split_out(a)
 
+    def lattice_decode_stats(self) -> int:
+        """str_er_lattice_decode_stats: the bytes of the lattice decode tables on the device; 0: never made."""
+        a = C.c_uint64()
+        self._check(self.L.str_er_lattice_decode_stats(self.h, C.byref(a)))
+        return int(a.value)
+
+    def lattice_decode_words(self, splits, run_costs, piece_costs, first_run, n_runs_of_word):
+        """str_er_lattice_decode_words: the joint decode (str_er_lattice_decode) of the words [first_run[w], first_run[w] +
+        n_runs_of_word[w]) over the pieces of their runs, from the unfolded cost rows of the runs (n runs, 65) and of their pieces
+        (n pieces, 65), under the table of set_bigram with INS / DEL of set_word_decode and SPLIT of set_run_split.  Returns
+        (LATTICE_DECODE_DTYPE per word, (n, 64) uint8 labels, (n, 64) uint8 sources, SPLIT_PART_DTYPE lattice parts)."""
+        a = _lattice_args(splits, run_costs, piece_costs, first_run, n_runs_of_word)
+        self._check(self.L.str_er_lattice_decode_words(self.h, *a[0], *a[1]))
+        return _lattice_out(a)
+
     def run_atlas_stats(self):
         """str_er_run_atlas_stats: (bytes of the run tile atlas, how often it was allocated or grown)."""
         a, b = C.c_uint64(), C.c_uint64()
@@ -2118,6 +2199,40 @@ def split_words_host(splits, run_costs, piece_costs, first_run, n_runs_of_word, 
     return _split_out(a)
 
 
+def _lattice_args(splits, run_costs, piece_costs, first_run, n_runs_of_word):
+    sp = np.ascontiguousarray(splits, dtype=RUN_SPLIT_DTYPE).reshape(-1)
+    rc = np.ascontiguousarray(run_costs, dtype=np.uint8).reshape(-1, 65)
+    pc = np.ascontiguousarray(piece_costs, dtype=np.uint8).reshape(-1, 65)
+    fr = np.ascontiguousarray(first_run, dtype=np.int32).reshape(-1)
+    no = np.ascontiguousarray(n_runs_of_word, dtype=np.int32).reshape(-1)
+    if len(sp) != len(rc) or len(fr) != len(no):
+        raise ValueError("splits and run_costs need one row per run, first_run and n_runs_of_word one entry per word")
+    cap = int(min(4 * int(no.astype(np.int64).clip(0).sum()), 2 ** 31 - 1))          # (a run has at most 4 parts)
+    dec = np.zeros(max(1, len(fr)), LATTICE_DECODE_DTYPE)
+    ch = np.full((max(1, len(fr)), 64), 0xFF, np.uint8)
+    sr = np.full((max(1, len(fr)), 64), 0xFF, np.uint8)
+    parts = np.zeros(max(1, cap), SPLIT_PART_DTYPE)
+    n = C.c_int32()
+    p = lambda a: _np_ptr(a) if len(a) else None
+    return ((p(sp), len(sp), p(rc), p(pc), len(pc), p(fr), p(no), len(fr)), (_np_ptr(dec), _np_ptr(ch), _np_ptr(sr), _np_ptr(parts), cap, C.byref(n)),
+            (sp, rc, pc, fr, no), dec, ch, sr, parts, n)
+
+
+def _lattice_out(a):
+    nw = len(a[2][3])
+    return a[3][:nw], a[4][:nw], a[5][:nw], a[6][:a[7].value].copy()
+
+
+def lattice_decode_words_host(splits, run_costs, piece_costs, first_run, n_runs_of_word, table, ins: int = 0, dele: int = 0, split_cost: int = 8):
+    """str_er_lattice_decode_words_host (pure host, one thread): ERFilter.lattice_decode_words with the table and the parameters as arguments."""
+    a = _lattice_args(splits, run_costs, piece_costs, first_run, n_runs_of_word)
+    tb = _bigram_table(table)
+    rc = load_library().str_er_lattice_decode_words_host(*a[0], int(split_cost), _np_ptr(tb), int(ins), int(dele), *a[1])
+    if rc != 0:
+        raise StrErError(rc, "str_er_lattice_decode_words_host")
+    return _lattice_out(a)
+
+
 def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: int = 0, dele: int = 0):
     """str_er_decode_words_host (pure host, one thread): ERFilter.decode_words with the table and the parameters as arguments."""
     cs, fr, no, out, ch, sr = _decode_args(costs, first_run, n_runs_of_word)
@@ -2129,10 +2244,10 @@ def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: 
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False, track_read=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False, track_read=False, lattice_decode=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (track_read, WANT_TRACK_READ), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (track_read, WANT_TRACK_READ), (lattice_decode, WANT_LATTICE_DECODE), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -2596,23 +2711,23 @@ class FrameStream:
         return slot.value, arr
 
     def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit(self.h, slot, w, h, 3 * w, 3 * w * h, n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
         """The staging buffer holds n_frames tightly packed NV12 frames (w * h * 3 / 2 bytes each)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_nv12(self.h, slot, w, h, w, w * (h + h // 2), n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         if a.ndim == 3:
             a = a[None]
@@ -2630,21 +2745,21 @@ class FrameStream:
         return int(t.value)
 
     def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
         """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
         return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
 
     def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
         """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
         return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
 
     def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
         """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         arr = (ImageRef * max(1, len(refs)))(*refs)

@@ -9,14 +9,17 @@
 // the cut runs (api_run_split.cpp) are tiles behind the runs' in the same atlas and rows behind the runs' in the same cost buffer, and
 // k_split_words (run_split_kernels.h) goes between k_run_costs and the matcher / decoder, which then read the parts' rows.  With
 // STR_ER_WANT_TRACK_READ the track match (api_track_read.cpp) follows the matcher on the same rows, for the word tracks the host made before.
+// With STR_ER_WANT_LATTICE_DECODE k_lattice_decode (lattice_decode_kernels.h, api_lattice_decode.cpp) follows the scorer as well: it reads
+// what k_split_words reads, on unfolded rows, and its tables come down with the same wait.
 #include "str_er_ctx.h"
+#include "lattice_decode_kernels.h"
 #include "run_split_kernels.h"
 
 namespace str_er_host {
 
 int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
                    const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q,
-                   const WordMatchOut *match, const WordDecodeOut *decode, const RunPieces *pieces, const TrackReadOut *track)
+                   const WordMatchOut *match, const WordDecodeOut *decode, const RunPieces *pieces, const TrackReadOut *track, const LatticeOut *lattice)
 {
     // n_run runs and behind them n_pc pieces (str_er_run_split): n tiles, and whatever is per run below takes the first n_run of them
     const size_t n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0, n = n_run + n_pc;
@@ -58,6 +61,14 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         pieces->costs->assign(65 * n_pc, 0);
         pieces->parts->clear();
         pieces->word_splits->assign(n_swords, str_er_word_split{0, 0, 0, 0});
+    }
+    // STR_ER_WANT_LATTICE_DECODE: k_lattice_decode on the split records, words and slots of k_split_words
+    const bool wlattice = lattice && wsplit;
+    if (wlattice) {
+        lattice->decodes->assign(n_swords, str_er_lattice_decode{});
+        lattice->chars->assign(64 * n_swords, 0xFF);
+        lattice->src->assign(64 * n_swords, 0xFF);
+        lattice->parts->clear();
     }
     if (n_run == 0) return STR_ER_OK;
     if (n > 0x7FFFFFFFull / 1800) return fail(c, STR_ER_ECAPACITY, "run read: too many glyph runs");
@@ -162,6 +173,14 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
             std::memcpy(SH.first, first.data(), 4 * n_swords); std::memcpy(SH.n_of, n_of.data(), 4 * n_swords); std::memcpy(SH.slot, slot.data(), 4 * n_swords);
         }
     }
+    LdTab      LH{}, LD{};
+    const bool lrows = wlattice && !wdecode && wmatch && c->lex.fold != 0;          // (no unfolded rows in this call yet: the lattice's own)
+    if (wlattice) {
+        if (n_swords > 0x7FFFFFFFull / 64) return fail(c, STR_ER_ECAPACITY, "lattice decode: too many words");
+        if ((rc = c->ld_tab.ensure(c, ld_layout(nullptr, 0, lrows ? n : 0, n_swords, (size_t)n_slots, false).bytes, "lattice decode tables")) != STR_ER_OK) return rc;
+        LH = ld_layout(c->ld_tab.h(), 0, lrows ? n : 0, n_swords, (size_t)n_slots, false);
+        LD = ld_layout(c->ld_tab.d(), 0, lrows ? n : 0, n_swords, (size_t)n_slots, false);
+    }
     uint8_t *h = c->run_tab.h(), *d = c->run_tab.d();
     std::memcpy(h, tiles.data(), sizeof(RunTile) * n);
     std::memcpy(h + o_box, boxes.data(), 16 * n);
@@ -226,6 +245,12 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
         launch_run_costs(s, buf.prob, (int)n_rows, m->k, m->label, false, SD.costs);
         split_on(SD.costs, SD.part_costs);
     }
+    if (wlattice && n_swords > 0) {          // unfolded rows of the runs and, behind them, the pieces
+        const uint8_t *lcosts = wdecode ? dcosts : wmatch ? (lrows ? LD.costs : WD.costs) : SD.costs;
+        if (lrows) launch_run_costs(s, buf.prob, (int)n_rows, m->k, m->label, false, LD.costs);
+        launch_lattice_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, c->rs_split, SD.splits, lcosts, lcosts + 65 * n_run, SD.first, SD.n_of, SD.slot, (int)n_swords,
+                              reinterpret_cast<int32_t *>(LD.dec), LD.chars, LD.src, reinterpret_cast<int32_t *>(LD.parts));
+    }
     HIP_TRY(c, hipGetLastError());
     std::vector<int32_t> label(reads ? n : 0);
     std::vector<double>  prob(reads ? n : 0);
@@ -264,7 +289,16 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
             HIP_TRY(c, hipMemcpyAsync(pieces->run_costs->data(), scosts, 65 * n_run, hipMemcpyDeviceToHost, s));
         }
     }
+    if (wlattice && n_swords > 0) HIP_TRY(c, hipMemcpyAsync(c->ld_tab.h() + LH.o_dec, c->ld_tab.d() + LH.o_dec, LH.down_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
+    if (wlattice && n_swords > 0) {          // the records with their first parts, the parts compacted, the strings as they are
+        uint64_t total = 0;
+        if (!ld_compact(LH, slot, n_slots, nullptr, nullptr, &total)) return fail(c, STR_ER_EHIP, "lattice decode: a word's parts outside its slots (internal error)");
+        lattice->parts->assign((size_t)total, str_er_split_part{0, 0});
+        ld_compact(LH, slot, n_slots, lattice->decodes->data(), lattice->parts->data(), &total);
+        std::memcpy(lattice->chars->data(), LH.chars, 64 * n_swords);
+        std::memcpy(lattice->src->data(), LH.src, 64 * n_swords);
+    }
     if (wsplit) {          // the parts compacted, and every run's share of them
         uint64_t total = 0;
         if (!rs_compact(SH, slot, n_slots, nullptr, nullptr, nullptr, &total)) return fail(c, STR_ER_EHIP, "run split: a word's parts outside its slots (internal error)");

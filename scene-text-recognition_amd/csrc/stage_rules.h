@@ -37,6 +37,13 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
         {!k.frames && any(STR_ER_WANT_TRACK_READ), STR_ER_EINVAL, "STR_ER_WANT_TRACK_READ needs frames (not the per-plane calls)"},
         {any(STR_ER_WANT_TRACK_READ) && !any(STR_ER_WANT_LINE_LINKS), STR_ER_EINVAL, "STR_ER_WANT_TRACK_READ needs STR_ER_WANT_LINE_LINKS"},
         {any(STR_ER_WANT_TRACK_READ) && !any(STR_ER_WANT_WORD_MATCH), STR_ER_EINVAL, "STR_ER_WANT_TRACK_READ needs STR_ER_WANT_WORD_MATCH"},
+        // STR_ER_WANT_LATTICE_DECODE rides on STR_ER_WANT_RUN_SPLIT (and through it on STR_ER_WANT_RUN_READ): refused without it and where
+        // it is refused, ahead of that flag's rules, so that the refusal names this flag (its table rule is with the models' below); a
+        // call without the flag meets no new rule
+        {k.strip && any(STR_ER_WANT_LATTICE_DECODE), STR_ER_EINVAL, "STR_ER_WANT_LATTICE_DECODE is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_LATTICE_DECODE), STR_ER_EINVAL, "STR_ER_WANT_LATTICE_DECODE needs frames (not the per-plane calls)"},
+        {any(STR_ER_WANT_LATTICE_DECODE) && !any(STR_ER_WANT_RUN_SPLIT), STR_ER_EINVAL, "STR_ER_WANT_LATTICE_DECODE needs STR_ER_WANT_RUN_SPLIT"},
+        {any(STR_ER_WANT_LATTICE_DECODE) && !any(STR_ER_WANT_RUN_READ), STR_ER_EINVAL, "STR_ER_WANT_LATTICE_DECODE needs STR_ER_WANT_RUN_READ (through STR_ER_WANT_RUN_SPLIT)"},
         // STR_ER_WANT_RUN_SPLIT rides on STR_ER_WANT_RUN_READ as STR_ER_WANT_WORD_MATCH does; its parameters have defaults, so it needs no
         // state of the context; a call without the flag meets no new rule
         {k.strip && any(STR_ER_WANT_RUN_SPLIT), STR_ER_EINVAL, "STR_ER_WANT_RUN_SPLIT is not supported by the strip path (str_er_strip_merge)"},
@@ -103,6 +110,7 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
          "STR_ER_WANT_RUN_READ needs an SVM model loaded with dim = 1800 (str_er_load_svm_model)"},
         {any(STR_ER_WANT_WORD_MATCH) && !lexicon, STR_ER_ESTATE, "STR_ER_WANT_WORD_MATCH needs a lexicon (str_er_set_lexicon)"},
         {any(STR_ER_WANT_WORD_DECODE) && !bigram, STR_ER_ESTATE, "STR_ER_WANT_WORD_DECODE needs a bigram table (str_er_set_bigram)"},
+        {any(STR_ER_WANT_LATTICE_DECODE) && !bigram, STR_ER_ESTATE, "STR_ER_WANT_LATTICE_DECODE needs a bigram table (str_er_set_bigram)"},
         {any(STR_ER_STAGE_TRACK) && !k.all_planes, STR_ER_EINVAL, "STR_ER_STAGE_TRACK needs BGR frames (calc_color reads the YCrCb image)"},
     };
     for (const Rule &r : rules)

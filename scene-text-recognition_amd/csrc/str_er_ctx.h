@@ -168,6 +168,10 @@ struct str_er_result {
     std::vector<str_er_split_part> split_parts;
     std::vector<str_er_word_split> word_splits;
     bool have_run_splits = false;
+    std::vector<str_er_lattice_decode> lattice_decodes; // STR_ER_WANT_LATTICE_DECODE: per word of words, 64 label and 64 source bytes per word, and the lattice parts
+    std::vector<uint8_t> lattice_decode_chars, lattice_decode_src;
+    std::vector<str_er_split_part> lattice_parts;
+    bool have_lattice_decodes = false;
     std::vector<str_er_word_link> word_links;    // STR_ER_WANT_TRACK_READ: the word links, the word tracks, their members, the track of every word of words,
     std::vector<str_er_word_track> word_tracks;  // one match per word track and one cost per slot of the member array
     std::vector<int32_t> word_track_members, word_track_of_words;
@@ -313,6 +317,8 @@ struct str_er_ctx {
     int32_t  rs_num = 1, rs_den = 4, rs_split = 8;
     PairBuf  rs_out;                  // a record per run slot of k_run_cuts
     PairBuf  rs_tab;                  // splits | rows of the runs and pieces | first run, run count, slot per word | records | parts | part rows
+    // STR_ER_WANT_LATTICE_DECODE / str_er_lattice_decode_words
+    PairBuf  ld_tab;                  // (the caller's splits | rows of the runs and pieces | first run, run count, slot per word) | records | labels | sources | parts
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -591,6 +597,7 @@ struct LineStageWants {
     bool match = false;       // STR_ER_WANT_WORD_MATCH: every word against the lexicon (k_run_costs and the matcher behind the scorer)
     bool decode = false;      // STR_ER_WANT_WORD_DECODE: every word under the bigram table (k_run_costs and the decoder behind the scorer)
     bool track = false;       // STR_ER_WANT_TRACK_READ: the word links and word tracks on the host before the reading, k_track_match behind the matcher
+    bool lattice = false;     // STR_ER_WANT_LATTICE_DECODE: every word over its piece lattice under the bigram table (k_lattice_decode behind the scorer, on what k_split_words reads)
     bool split = false;       // STR_ER_WANT_RUN_SPLIT: the cuts of every run (k_run_cuts behind k_foot_words, down with the stage's wait), the pieces read with the runs, k_split_words behind the scorer
 };
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
@@ -678,10 +685,34 @@ struct TrackReadOut {
     std::vector<str_er_track_match> *matches;
     std::vector<int32_t> *member_costs;
 };
+// lattice (optional, with the splits of pieces): STR_ER_WANT_LATTICE_DECODE -- k_lattice_decode behind the scorer on s, on the split
+// records, words and slots k_split_words reads and on unfolded rows of the runs and pieces: the decoder's where it runs, else the
+// matcher's where its lexicon does not fold, else the split's own, else those of one more k_run_costs into ld_tab; its tables back with
+// the same wait
+struct LatticeOut {
+    std::vector<str_er_lattice_decode> *decodes;
+    std::vector<uint8_t> *chars, *src;
+    std::vector<str_er_split_part> *parts;
+};
 int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
                    const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q,
                    const WordMatchOut *match = nullptr, const WordDecodeOut *decode = nullptr, const RunPieces *pieces = nullptr,
-                   const TrackReadOut *track = nullptr);
+                   const TrackReadOut *track = nullptr, const LatticeOut *lattice = nullptr);
+// ---- defined in api_lattice_decode.cpp
+// the layout of c->ld_tab (base: either side of the pair, or null for the size alone): with inputs the caller's n_runs split records,
+// n_rows cost rows (the pieces' behind the runs') and the words' (first, n, slot); without, n_rows rows of its own alone (0: none); then
+// what comes down: n_words records, labels and sources and n_slots part slots
+struct LdTab {
+    str_er_run_split *splits;
+    uint8_t *costs;
+    int32_t *first, *n_of, *slot;
+    str_er_lattice_decode *dec; uint8_t *chars, *src; str_er_split_part *parts;
+    size_t up_bytes, o_dec, down_bytes, bytes;      // dec | chars | src | parts lie back to back (each aligned): one copy down
+};
+LdTab ld_layout(uint8_t *base, size_t n_runs, size_t n_rows, size_t n_words, size_t n_slots, bool inputs);
+// after the wait: the records with first_part set and the compacted parts from the host side of the layout (null: not copied); false
+// where a word's parts lie outside its slots
+bool ld_compact(const LdTab &H, const std::vector<int32_t> &slot, uint64_t n_slots, str_er_lattice_decode *dec, str_er_split_part *parts, uint64_t *n_parts);
 // ---- defined in api_track_read.cpp
 // the layout of c->tm_tab for n_tracks tracks over a member array of n_members (base: either side of the pair, or null for the size alone)
 struct TmTab {

@@ -894,6 +894,78 @@ public:
         return s;
     }
 
+    // Every word decoded jointly over the lattice of the pieces of its runs and the bigram table (STR_ER_WANT_LATTICE_DECODE; the contract
+    // is at str_er_lattice_decode in include/str_er.h): one record per word of LineWords::words, 64 label bytes and 64 source bytes per
+    // word (0xFF past n_chars; a source indexes the word's lattice parts), and the lattice parts of the words back to back in word order
+    // (piece -1: the whole run; the indices are those of RunSplits::parts).  Needs STR_ER_WANT_RUN_SPLIT and a table in the context.
+    struct LatticeDecodes {
+        std::vector<str_er_lattice_decode> decodes;
+        std::vector<uint8_t>               chars, src;
+        std::vector<str_er_split_part>     parts;
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static LatticeDecodes lattice_decodes(const str_er_result *r)
+    {
+        LatticeDecodes out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_lattice_decode *p = str_er_result_lattice_decodes(r, &n)) out.decodes.assign(p, p + n);
+        if (const uint8_t *p = str_er_result_lattice_decode_chars(r, &nb)) out.chars.assign(p, p + nb);
+        if (const uint8_t *p = str_er_result_lattice_decode_src(r, &nb)) out.src.assign(p, p + nb);
+        if (const str_er_split_part *p = str_er_result_lattice_parts(r, &n)) out.parts.assign(p, p + n);
+        return out;
+    }
+    // the joint decode of the words [first_run[w], first_run[w] + n_runs[w]) on the caller's unfolded cost rows (str_er_lattice_decode_words):
+    // splits one record per run, run_costs and piece_costs 65 bytes a row; the context's table, INS / DEL and SPLIT
+    LatticeDecodes lattice_decode_words(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                                        const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs)
+    {
+        LatticeDecodes out = lattice_out(splits, run_costs, piece_costs, first_run, n_runs);
+        int32_t n = 0;
+        check(str_er_lattice_decode_words(ctx_.get(), splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                          piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65),
+                                          first_run.empty() ? nullptr : first_run.data(), n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(),
+                                          out.decodes.empty() ? nullptr : out.decodes.data(), out.chars.empty() ? nullptr : out.chars.data(),
+                                          out.src.empty() ? nullptr : out.src.data(), out.parts.data(), (int32_t)out.parts.size(), &n));
+        out.parts.resize((size_t)n);
+        return out;
+    }
+    // the same rules on one host thread, with the table (66 x 66 bytes), INS / DEL and SPLIT as arguments (str_er_lattice_decode_words_host)
+    static LatticeDecodes lattice_decode_words_host(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs,
+                                                    const std::vector<uint8_t> &piece_costs, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs,
+                                                    const std::vector<uint8_t> &table, int32_t ins = 0, int32_t del = 0, int32_t split_cost = 8)
+    {
+        if (table.size() != 66 * 66) throw std::invalid_argument("lattice_decode_words_host: 66 x 66 bytes");
+        LatticeDecodes out = lattice_out(splits, run_costs, piece_costs, first_run, n_runs);
+        int32_t n = 0;
+        if (str_er_lattice_decode_words_host(splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                             piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65),
+                                             first_run.empty() ? nullptr : first_run.data(), n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(),
+                                             split_cost, table.data(), ins, del, out.decodes.empty() ? nullptr : out.decodes.data(),
+                                             out.chars.empty() ? nullptr : out.chars.data(), out.src.empty() ? nullptr : out.src.data(), out.parts.data(),
+                                             (int32_t)out.parts.size(), &n) != STR_ER_OK)
+            throw std::invalid_argument("lattice_decode_words_host");
+        out.parts.resize((size_t)n);
+        return out;
+    }
+    // the jointly decoded string of word w: its own reading where it was not decoded (more than 32 atoms)
+    static std::string word_lattice_text(const LineWords &lw, const RunReads &rd, const LatticeDecodes &ld, size_t w)
+    {
+        const str_er_lattice_decode &d = ld.decodes.at(w);
+        if (d.cost < 0) return word_text(lw, rd, w);
+        std::string s;
+        for (int32_t k = 0; k < d.n_chars; ++k) s += (char)str_er_ocr_char(ld.chars.at(64 * w + (size_t)k));
+        return s;
+    }
+    // the jointly decoded text of line t: its words' strings joined by one blank
+    static std::string line_lattice_text(const LineWords &lw, const RunReads &rd, const LatticeDecodes &ld, size_t t)
+    {
+        std::string s;
+        const str_er_line_words &L = lw.lines.at(t);
+        for (int32_t k = L.first_word; k < L.first_word + L.n_words; ++k) s += (k > L.first_word ? " " : "") + word_lattice_text(lw, rd, ld, (size_t)k);
+        return s;
+    }
+
     // The text lines of consecutive frames linked into text tracks (STR_ER_WANT_LINE_LINKS; the contract is at str_er_line_link in
     // include/str_er.h): the overlaps across adjacent frames, the track of every line of str_er_result_texts(), the tracks, the line
     // indices their first / count index, and the footprints of the lines of the first ([0]) and of the last frame ([1]).
@@ -1101,6 +1173,22 @@ private:
     void check(int rc) const
     {
         if (rc != STR_ER_OK) throw std::runtime_error(std::string(str_er_strerror(rc)) + ": " + str_er_last_error(ctx_.get()));
+    }
+    // the outputs of lattice_decode_words(_host) sized for the words: a run has at most 4 lattice parts
+    static LatticeDecodes lattice_out(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                                      const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs)
+    {
+        if (first_run.size() != n_runs.size() || run_costs.size() != 65 * splits.size() || piece_costs.size() % 65)
+            throw std::invalid_argument("lattice_decode_words: 65 bytes a run and a piece, one record a run, one span a word");
+        size_t cap = 1;
+        for (const int32_t k : n_runs) cap += 4 * (size_t)(k > 0 ? k : 0);
+        if (cap > 0x7FFFFFFFull) throw std::invalid_argument("lattice_decode_words: too many runs");
+        LatticeDecodes out;
+        out.decodes.resize(first_run.size());
+        out.chars.resize(64 * first_run.size());
+        out.src.resize(64 * first_run.size());
+        out.parts.resize(cap);
+        return out;
     }
     // the regions of er_masks / er_shapes / er_strokes: of every ER its bound, level and key
     static std::vector<str_er_cand> regions_of(const ERs &ers)
