@@ -776,6 +776,12 @@ int  str_er_last_tree_stats(const str_er_ctx *ctx, uint64_t *records, uint64_t *
  * more levels / nodes than it takes is handed back to k_tile_tree.  Since the context was created: tiles given to k_tile_tree2, tiles it handed
  * back.  Measurement aid; results do not depend on which kernel built a tile's tree.  Any pointer may be NULL. */
 int  str_er_tile2_stats(const str_er_ctx *ctx, uint64_t *tiles, uint64_t *handed_back);
+/* Where the groups of tiles of this context's last detect call went.  A large text-like batch (more than 96 planes) sorts its groups by their record count
+ * on the device (k_group_bins): per_table[0..3] = the groups k_group_merge joined in its tables of 512 / 1024 / 2048 / 2528 records, one_tile = the groups
+ * of a single tile (no inner seam: nobody's); by default the 2048-record list stays empty, its groups are the 2528-record table's.  listed = the groups whose inner seams k_seam_undone joined on the global records instead -- more records than
+ * the largest table, or a plane that ran out of node records.  Any other call joins its groups with one table for all (or one per class of plane) and fills
+ * `listed` only, the rest is 0.  Measurement aid; results do not depend on where a group went.  Any pointer may be NULL. */
+int  str_er_last_group_stats(const str_er_ctx *ctx, uint32_t per_table[4], uint32_t *listed, uint32_t *one_tile);
 /* STR_ER_STAGE_OCR is enqueued right behind classify, sized from the previous batch of the context and working on the device's own count of strong / weak
  * ERs (the reference's call site, src/ER.cpp:728-735, has no barrier between the two either); a batch with more ERs than guessed, or whose candidates an NMS
  * tie pass re-made, is scored again after the counters were read.  Since the context was created: batches whose early scores were used, batches scored again.

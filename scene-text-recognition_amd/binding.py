@@ -473,6 +473,7 @@ def load_library():
     L.str_er_result_free.argtypes = [vp]
     L.str_er_last_tree_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.str_er_tile2_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.str_er_last_group_stats.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.str_er_ocr_stage_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.str_er_last_profile.argtypes = [vp, C.POINTER(C.c_char_p), f64p, C.c_int32]
     L.str_er_set_profiling.argtypes = [vp, C.c_int]
@@ -1248,6 +1249,13 @@ class ERFilter:
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.str_er_last_tree_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return {"records": int(a.value), "seam_pairs": int(b.value), "tiles": int(c.value)}
+
+    def last_group_stats(self) -> dict:
+        """Where the groups of tiles of the last detect call went: groups per k_group_merge table (512 / 1024 / 2048 / 2528 records; a large text-like
+        batch only), groups listed for k_seam_undone, groups of one tile (str_er_last_group_stats)."""
+        t, a, b = (C.c_uint32 * 4)(), C.c_uint32(), C.c_uint32()
+        self._check(self.L.str_er_last_group_stats(self.h, t, C.byref(a), C.byref(b)))
+        return {"per_table": {cap: int(v) for cap, v in zip((512, 1024, 2048, 2528), t)}, "listed": int(a.value), "one_tile": int(b.value)}
 
     def tile2_stats(self) -> dict:
         """Tiles given to the second tile kernel (k_tile_tree2) since the context was created, and how many it handed back (str_er_tile2_stats)."""

@@ -24,6 +24,7 @@ struct BatchDev {
     uint16_t        *tile_nrec;  // ... and how many records the tile has
     uint8_t         *group_done; // per group of tiles: k_group_merge has joined its inner seams
     uint32_t        *undone_list, *undone_count;    // the groups k_group_merge left alone (too many records): their inner seams are joined by k_seam_undone
+    uint32_t        *bin_list, *bin_count;          // k_group_bins: the groups by the table that holds their records (list k at bin_list + k * n_groups, bin_count[k] long; bin_count[4]: one-tile groups)
     const uint16_t  *group_plane; // plane of every group
     uint32_t         n_groups;   // batch-wide
     int32_t          group_x, group_y;   // tiles per group (0: no grouping in this batch)
@@ -82,6 +83,10 @@ void launch_tile_tree_fb(hipStream_t s, const BatchDev &b, const DetectParams &p
 void launch_tile_tree2(hipStream_t s, const BatchDev &b, const DetectParams &p, const uint32_t *pairs, uint32_t n_pairs, uint32_t *fb_list, uint32_t *fb_count);
 // the tiles of every group of BatchDev::group_x x group_y tiles joined in LDS, in place (variant: LDS capacity / lanes, see er_kernels.hip)
 void launch_group_merge(hipStream_t s, const BatchDev &b, int variant, const uint32_t *glist = nullptr, uint32_t n = 0);
+// the groups sorted by their record count into the lists of four tables of caps[k] records (BatchDev::bin_list / bin_count), the rest onto the undone list;
+// then per table k (512 / 1024 / 2048 / 2528 records) `grid` workgroups walk its list
+void launch_group_bins(hipStream_t s, const BatchDev &b, const uint32_t caps[4]);
+void launch_group_merge_list(hipStream_t s, const BatchDev &b, int k, uint32_t grid);
 void launch_seam(hipStream_t s, const BatchDev &b, bool xcd_affine);
 void launch_resolve(hipStream_t s, const BatchDev &b);
 // strips of a plane extracted elsewhere: make a strip's record ids plane-wide; join pixel pairs (plane-local ids) across a cut

@@ -14,10 +14,10 @@
 // ------------------------------------------------------------------------------------
 constexpr int GROUP_MAX_TILES = 64;
 
+// one group, by one workgroup (every exit is taken by the whole workgroup)
 template <int CAP, int GROUP_THREADS>
-__global__ __launch_bounds__(GROUP_THREADS) void k_group_merge(BatchDev b, const uint32_t *glist)
+__device__ __forceinline__ void group_merge_one(const BatchDev &b, const uint32_t group)
 {
-    const uint32_t group = glist ? glist[blockIdx.x] : blockIdx.x;       // (a launch per class of planes takes its groups from a list)
     __shared__ uint32_t s_par[CAP], s_cnt[CAP], s_nod[CAP], s_key[CAP], s_x0[CAP], s_y0[CAP], s_x1[CAP], s_y1[CAP];
     __shared__ uint32_t s_toff[GROUP_MAX_TILES + 1], s_tbase[GROUP_MAX_TILES];
     __shared__ uint32_t s_levels[8];
@@ -201,6 +201,66 @@ __global__ __launch_bounds__(GROUP_THREADS) void k_group_merge(BatchDev b, const
     GM_MARK(6);
 }
 
+// a group per workgroup; glist: a launch per class of planes takes its groups from a list (nullptr: the groups are the workgroups' numbers)
+template <int CAP, int GROUP_THREADS>
+__global__ __launch_bounds__(GROUP_THREADS) void k_group_merge(BatchDev b, const uint32_t *glist)
+{
+    group_merge_one<CAP, GROUP_THREADS>(b, glist ? glist[blockIdx.x] : blockIdx.x);
+}
+
+// ... and the groups of a list written on the device (k_group_bins), whose length only the device knows: a fixed grid walks it, whatever its size.
+// (A kernel of its own: the loop costs the one-group form registers -- 26 -> 50 -- and measured 0.8 % of the line where no list is walked.)
+template <int CAP, int GROUP_THREADS>
+__global__ __launch_bounds__(GROUP_THREADS) void k_group_merge_list(BatchDev b, const uint32_t *glist, const uint32_t *gcount)
+{
+    const uint32_t n = *gcount;
+    for (uint32_t u = blockIdx.x; u < n; u += gridDim.x) {
+        group_merge_one<CAP, GROUP_THREADS>(b, glist[u]);
+        __syncthreads();        // (the group's tables in LDS are read until its last record is back in place)
+    }
+}
+
+// The groups of a batch sorted by what they hold, behind the tile kernels: one lane per group adds up the records of its tiles and puts the group on the
+// list of the smallest table that holds them (caps: the four tables' records; two equal neighbours leave the second list empty) -- or, with more records
+// than the largest or a tile without records of its own (tile_nbase NONE), on k_seam_undone's list: what k_group_merge itself decides for a group it is
+// given.  A group of one tile has no inner seam and goes nowhere.  Lists: bin_list + k * n_groups, their lengths bin_count[k]; bin_count[4] counts the
+// one-tile groups.  The order inside a list is whatever the appends give: groups are independent.
+__global__ __launch_bounds__(256) void k_group_bins(BatchDev b, uint4 caps)
+{
+    const uint32_t group = blockIdx.x * 256u + threadIdx.x;
+    const int      lane = (int)(threadIdx.x & 63u);
+    int            cls = -1;        // 0..3: table, 4: one tile, 5: k_seam_undone's
+    if (group < b.n_groups) {
+        const int       GX = b.group_x, GY = b.group_y;
+        const PlaneDesc &pd = b.planes[b.group_plane[group]];
+        const int       groups_x = (pd.tiles_x + GX - 1) / GX;
+        const uint32_t  gl = group - pd.group_base;
+        const int       tx0 = (int)(gl % (uint32_t)groups_x) * GX, ty0 = (int)(gl / (uint32_t)groups_x) * GY;
+        const int       gw = min(GX, pd.tiles_x - tx0), gh = min(GY, pd.tiles_y - ty0);
+        if (gw * gh < 2) cls = 4;
+        else {
+            uint32_t sum = 0;
+            bool     bad = false;
+            for (int iy = 0; iy < gh; ++iy)
+                for (int ix = 0; ix < gw; ++ix) {
+                    const uint32_t tile = pd.tile_base + (uint32_t)(ty0 + iy) * pd.tiles_x + (uint32_t)(tx0 + ix);
+                    bad |= b.tile_nbase[tile] == NONE;
+                    sum += b.tile_nrec[tile];
+                }
+            cls = bad ? 5 : sum <= caps.x ? 0 : sum <= caps.y ? 1 : sum <= caps.z ? 2 : sum <= caps.w ? 3 : 5;
+        }
+    }
+    for (int k = 0; k < 6; ++k) {       // one atomic per wave and list
+        const unsigned long long m = __ballot(cls == k);
+        if (!m) continue;
+        const int leader = __ffsll(m) - 1;
+        uint32_t  at = 0;
+        if (lane == leader) at = atomicAdd(k < 5 ? b.bin_count + k : b.undone_count, (uint32_t)__popcll(m));
+        at = __shfl(at, leader) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+        if (cls == k && k != 4) (k < 4 ? b.bin_list + (size_t)k * b.n_groups : b.undone_list)[at] = group;
+    }
+}
+
 // variant: LDS for 512 / 1024 / 2048 / 3072 records per group, 256 / 512 / 1024 lanes; glist / n: the groups of this launch (nullptr: all b.n_groups)
 void launch_group_merge(hipStream_t s, const BatchDev &b, int variant, const uint32_t *glist, uint32_t n)
 {
@@ -218,6 +278,26 @@ void launch_group_merge(hipStream_t s, const BatchDev &b, int variant, const uin
     case 6: hipLaunchKernelGGL((k_group_merge<2528, 1024>), dim3(n), dim3(1024), 0, s, b, glist); break;
     default: hipLaunchKernelGGL((k_group_merge<2528, 512>), dim3(n), dim3(512), 0, s, b, glist); break;
     }
+}
+
+// list k of k_group_bins (table 0: 512 records / 256 lanes, 1: 1024 / 512, 2: 2048 / 1024, 3: 2528 / 1024), walked by `grid` workgroups
+void launch_group_merge_list(hipStream_t s, const BatchDev &b, int k, uint32_t grid)
+{
+    if (!b.n_groups || b.group_x <= 0 || b.group_y <= 0 || b.group_x * b.group_y > GROUP_MAX_TILES || !b.bin_list || !b.bin_count || k < 0 || k > 3) return;
+    const uint32_t *glist = b.bin_list + (size_t)k * b.n_groups, *gcount = b.bin_count + k;
+    grid = grid < 1u ? 1u : (grid > b.n_groups ? b.n_groups : grid);
+    switch (k) {
+    case 0: hipLaunchKernelGGL((k_group_merge_list<512, 256>), dim3(grid), dim3(256), 0, s, b, glist, gcount); break;
+    case 1: hipLaunchKernelGGL((k_group_merge_list<1024, 512>), dim3(grid), dim3(512), 0, s, b, glist, gcount); break;
+    case 2: hipLaunchKernelGGL((k_group_merge_list<2048, 1024>), dim3(grid), dim3(1024), 0, s, b, glist, gcount); break;
+    default: hipLaunchKernelGGL((k_group_merge_list<2528, 1024>), dim3(grid), dim3(1024), 0, s, b, glist, gcount); break;
+    }
+}
+
+void launch_group_bins(hipStream_t s, const BatchDev &b, const uint32_t caps[4])
+{
+    if (!b.n_groups || b.group_x <= 0 || b.group_y <= 0 || b.group_x * b.group_y > GROUP_MAX_TILES || !b.bin_list || !b.bin_count) return;
+    hipLaunchKernelGGL(k_group_bins, dim3((b.n_groups + 255u) / 256u), dim3(256), 0, s, b, make_uint4(caps[0], caps[1], caps[2], caps[3]));
 }
 
 // ------------------------------------------------------------------------------------
@@ -377,8 +457,10 @@ __global__ __launch_bounds__(SEAM_BLOCK) void k_seam(BatchDev b, int xcd_affine)
     node_connect(b.na.rec + pd.node_base, s_pa[threadIdx.x], s_pb[threadIdx.x]);
 }
 
-// The inner seams of the groups k_group_merge left alone (more records than its table holds: noise-like content; none on text-like batches), joined on the
-// global records like any other seam.  A fixed grid walks the list: k_group_merge wrote it, so its length is only known on the device.
+// The inner seams of the groups k_group_merge left alone (more records than its table holds), joined on the global records like any other seam.  Noise-like
+// content -- and, as long as the luma groups of a large text-like batch all took the 2048-record table, one or two 8 x 4 groups of levels 3-4 of every frame's
+// luma pyramid (2063-2271 records: 46 groups of a 32-frame batch of 1080p S-text frames, 0.12 ms here, and their records unfolded through the global passes).
+// k_group_bins gives those the 2528-record table: on such batches the list is empty now.  A fixed grid walks the list: k_group_merge wrote it, so its length is only known on the device.
 __global__ __launch_bounds__(SEAM_BLOCK) void k_seam_undone(BatchDev b)
 {
     const uint32_t n = *b.undone_count;

@@ -101,6 +101,7 @@ BatchDev make_batchdev(str_er_ctx *c, const Batch &b)
     d.n_tiles = b.n_tiles; d.n_pairs = b.n_pairs; d.n_node_blocks = c->n_node_blocks; d.nb_plane = c->d_nb_plane;
     d.tile_plane = c->d_tile_plane; d.seam_block_plane = c->d_sb_plane; d.seam_block_first = c->d_sb_first;
     d.n_seam_blocks = (uint32_t)c->h_sb_plane.size();
+    d.bin_list = c->d_bin_list; d.bin_count = c->d_total ? c->d_total + str_er_ctx::GROUP_BIN_WORD : nullptr;
     d.tile_nrec = c->d_tile_nrec; d.group_done = c->d_group_done; d.group_plane = c->d_group_plane; d.undone_list = c->d_undone; d.undone_count = c->d_total ? c->d_total + 2 : nullptr; d.n_groups = b.n_groups; d.group_x = b.group_x; d.group_y = b.group_y;
     d.na = c->na; d.ka = c->ka; d.tile_nbase = c->d_tile_nbase; d.seam = c->d_seam; d.pool = c->d_pool; d.pool_tmp = c->d_pool_tmp;
     d.cands = c->d_cands; d.total_cands = c->d_total; d.cand_plane = c->d_cand_plane; d.watch = c->d_watch; d.wstamp = c->d_wstamp; d.wparent = c->d_wparent;
@@ -762,7 +763,7 @@ struct BatchRun {
     const ImportHook *import_trees;
     Batch             b;
     int               np = 0;
-    bool              grouped = false, big_groups = false;
+    bool              grouped = false, big_groups = false, binned = false;     // (binned: k_group_bins chose every group's table, enqueue_batch)
     DetectParams      dp{};
     hipStream_t       s = nullptr;
     BatchDev          bd{};
@@ -855,7 +856,26 @@ static int enqueue_batch(BatchRun &R, BatchSlot &slot, bool pre_recorded)
         // group that does overflow is k_seam_undone's.  With six batches in flight k_group_merge cost the line its WHOLE isolated time (tools/dev_exposed.py with
         // STR_ER_DEBUG_STOP_AFTER: 0.30 of 0.33 ms per 32-frame batch, where seam / resolve / reduce cost half of theirs): the tile kernels hold all 160 KB of a
         // compute unit's LDS, and a workgroup that wants 64 KB and 16 wave slots waits until four of theirs have left it.  13.0 -> 13.3 k frames/s.
-        if (R.big_groups && c->dbg_group[2] < 0 && c->n_groups_small && c->h_group_list.size() == b.n_groups) {
+        // ... and the class of a plane is a poor proxy for what a group holds: of the 78 luma groups of a 1080p S-text frame at pyr3x8 12 hold at most 512 records,
+        // 41 more at most 1024, and one or two of the pyramid's levels 3-4 hold 2063-2271 -- more than the 2048-record table, so they took k_seam_undone and the
+        // global passes whole (tools/group_census.py; profiles/group_bins.md).  tile_nrec says what a group holds as soon as the tile kernels are done: k_group_bins
+        // lists the groups by the smallest table that holds them, and a launch per table walks its list with a grid sized from the context's last batch (only a
+        // hint: the kernel's loop covers any length).  Not for calls of a frame or two (a launch more is latency), noise-like batches, forced variants or shapes.
+        R.binned = R.big_groups && c->group_bins > 0 && c->dbg_group[2] < 0 && c->dbg_group[0] <= 0 && c->d_bin_list && b.group_x * b.group_y <= 64;
+        if (R.binned) {
+            // (three tables: a list of its own for the 2048-record table measured 1 % less on the line than its groups in the 2528-record one, which is as
+            // large a workgroup -- profiles/group_bins.md; two equal caps leave the second list empty and unlaunched)
+            static const uint32_t caps3[4] = {512, 1024, 1024, 2528}, caps4[4] = {512, 1024, 2048, 2528}, caps2[4] = {512, 512, 512, 2528};
+            const uint32_t *caps = c->group_bins == 4 ? caps4 : c->group_bins == 2 ? caps2 : caps3;
+            launch_group_bins(s, bd, caps);
+            const bool hint = c->bin_hint_valid && c->bin_hint_groups == b.n_groups;
+            for (int k = 0; k < 4; ++k) {
+                if (k > 0 && caps[k] == caps[k - 1]) continue;
+                uint32_t grid = hint ? c->bin_hint[k] + c->bin_hint[k] / 8u + 8u : (k == 0 ? b.n_groups : 1024u);
+                if (c->dbg_group_grid > 0) grid = (uint32_t)c->dbg_group_grid;
+                launch_group_merge_list(s, bd, k, grid);
+            }
+        } else if (R.big_groups && c->dbg_group[2] < 0 && c->n_groups_small && c->h_group_list.size() == b.n_groups) {
             launch_group_merge(s, bd, 0, c->d_group_list, c->n_groups_small);
             launch_group_merge(s, bd, variant, c->d_group_list + c->n_groups_small, b.n_groups - c->n_groups_small);
         } else launch_group_merge(s, bd, variant);
@@ -959,6 +979,13 @@ static int settle_batch(BatchRun &R)
         c->t2_tiles_total += c->n_t2_tiles; c->t2_fb_total += fbn;
         if (c->t2_mode == 1 && (uint64_t)fbn * 8u > c->n_t2_tiles) c->t2_backoff = 32;
     } else if (c->t2_backoff > 0) --c->t2_backoff;
+    {   // where the groups of tiles went (str_er_last_group_stats); a binned batch's lists size the grids of the context's next one
+        const uint32_t *bins = c->h_total + str_er_ctx::GROUP_BIN_WORD;
+        for (int k = 0; k < 4; ++k) c->last_group_stats[k] = R.binned ? bins[k] : 0;
+        c->last_group_stats[4] = R.grouped && b.n_groups ? c->h_total[2] : 0;
+        c->last_group_stats[5] = R.binned ? bins[4] : 0;
+        if (R.binned) { std::memcpy(c->bin_hint, bins, sizeof(c->bin_hint)); c->bin_hint_groups = b.n_groups; c->bin_hint_valid = true; }
+    }
     {   // what the tree passes of this batch worked on (str_er_last_tree_stats: bench.py prices them against the HBM roofline)
         uint64_t recs = 0, pairs = 0, tiles = 0;
         for (int i = 0; i < np; ++i) {
@@ -1488,6 +1515,15 @@ try {
     return STR_ER_OK;
 } ABI_GUARD(const_cast<str_er_ctx *>(c))
 
+int str_er_last_group_stats(const str_er_ctx *c, uint32_t per_table[4], uint32_t *listed, uint32_t *one_tile)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (per_table) std::memcpy(per_table, c->last_group_stats, 4 * sizeof(uint32_t));
+    if (listed) *listed = c->last_group_stats[4];
+    if (one_tile) *one_tile = c->last_group_stats[5];
+    return STR_ER_OK;
+} ABI_GUARD(const_cast<str_er_ctx *>(c))
+
 int str_er_tile2_stats(const str_er_ctx *c, uint64_t *tiles, uint64_t *handed_back)
 try {
     if (!c) return STR_ER_EINVAL;
@@ -1605,6 +1641,8 @@ int str_er_create(const str_er_params *p, str_er_ctx **out)
     if (const char *g = std::getenv("STR_ER_GROUP_X")) c->dbg_group[0] = std::atoi(g);
     if (const char *g = std::getenv("STR_ER_GROUP_Y")) c->dbg_group[1] = std::atoi(g);
     if (const char *g = std::getenv("STR_ER_GROUP_KERNEL")) c->dbg_group[2] = std::atoi(g);
+    if (const char *g = std::getenv("STR_ER_GROUP_BINS")) c->group_bins = std::max(0, std::min(4, std::atoi(g)));      // developer switch: 0 = a launch per class of planes, 4 / 2 = four / two tables
+    if (const char *g = std::getenv("STR_ER_GROUP_GRID")) c->dbg_group_grid = std::max(0, std::atoi(g));
     if (const char *t2 = std::getenv("STR_ER_TILE2")) c->t2_mode = std::max(0, std::min(2, std::atoi(t2)));      // developer switch: 0 k_tile_tree only, 2 k_tile_tree2 on every plane
     c->dbg_tile_only = std::getenv("STR_ER_DEBUG_TILE_ONLY") != nullptr;
     if (c->dbg_tile_only) c->profiling = true;
@@ -1680,6 +1718,7 @@ int str_er_create(const str_er_params *p, str_er_ctx **out)
     A(dev_alloc(c, c->d_t1_list, c->tile_slots)); A(dev_alloc(c, c->d_t2_pairs, c->tile_slots)); A(dev_alloc(c, c->d_fb_list, c->tile_slots));
     A(dev_alloc(c, c->d_nb_plane, (size_t)c->max_planes * str_er_ctx::NB_PLANE_SHARE));
     A(dev_alloc(c, c->d_tile_nrec, c->tile_slots)); A(dev_alloc(c, c->d_group_plane, c->tile_slots)); A(dev_alloc(c, c->d_undone, c->tile_slots)); A(dev_alloc(c, c->d_group_list, c->tile_slots));
+    A(dev_alloc(c, c->d_bin_list, 4 * c->tile_slots));
     A(dev_alloc(c, c->d_ranges, 2 * (size_t)c->max_planes + 2));
     {   // what a batch starts from zero -- the candidate / handed-back-tile counters, the plane counters, the groups' done flags -- is ONE block: one
         // memset per batch, and the counters come back with one copy (a call of one frame is a chain of ~30 operations: each costs 5 - 10 us)

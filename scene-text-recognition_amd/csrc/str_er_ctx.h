@@ -326,6 +326,14 @@ struct str_er_ctx {
     uint16_t *d_group_plane = nullptr; std::vector<uint16_t> h_group_plane;      // plane of every group of tiles
     uint32_t *d_group_list = nullptr; std::vector<uint32_t> h_group_list; uint32_t n_groups_small = 0;      // the groups by class of plane: first those of the chroma planes (few records a tile: k_group_merge with a small table), then the others
     uint32_t *d_undone = nullptr;                     // the groups k_group_merge left alone, listed on the device (their number: d_total[2]) for k_seam_undone
+    // k_group_bins (large text-like batches): the groups listed on the device by the table that holds their records -- four lists of tile_slots words, their
+    // lengths in d_total[GROUP_BIN_WORD + 0..3], the one-tile groups counted in [GROUP_BIN_WORD + 4]
+    static constexpr int GROUP_BIN_WORD = 8;
+    uint32_t *d_bin_list = nullptr;
+    int       group_bins = 1;                         // STR_ER_GROUP_BINS: 0 the launches per class of PLANE; else by record count: three tables (512 / 1024 / 2528 records), 4: four (+ 2048), 2: two (512 / 2528)
+    int       dbg_group_grid = 0;                     // STR_ER_GROUP_GRID: so many workgroups per table, whatever its list holds (developer knob: the kernel's loop)
+    uint32_t  bin_hint[4] = {0, 0, 0, 0}, bin_hint_groups = 0; bool bin_hint_valid = false;      // the lists' lengths in the context's last binned batch (of so many groups): the grids of the next one like it
+    uint32_t  last_group_stats[6] = {0, 0, 0, 0, 0, 0};                     // str_er_last_group_stats: groups per table, listed for k_seam_undone, of one tile
     uint8_t  *d_group_done = nullptr;                 // per group of tiles: joined in LDS (k_group_merge -> k_seam)
     int       dbg_group[3] = {0, 0, -1};              // developer knobs STR_ER_GROUP_X / _Y / _KERNEL
     int       group_mode = -1;                        // STR_ER_GROUPS: -1 automatic (4 x 4 tiles with the small tile kernel, 2 x 5 with the big one), 0 off
