@@ -712,20 +712,24 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
     if (read) {
         std::vector<double> slopes(n_lines);
         for (size_t t = 0; t < n_lines; ++t) slopes[t] = r->texts[t].slope;
-        const WordMatchOut wmo{&r->words, &r->word_matches, &r->run_costs, &r->run_probs};
-        const WordDecodeOut wdo{&r->words, &r->word_decodes, &r->word_decode_chars, &r->word_decode_src, &r->run_costs, &r->run_probs};
+        ReadChainOut out;          // (a consumer behind the scorer runs where its first table is given)
+        out.words = &r->words; out.run_costs = &r->run_costs; out.run_probs = &r->run_probs;
+        if (match) out.matches = &r->word_matches;
+        if (decode) { out.decodes = &r->word_decodes; out.decode_chars = &r->word_decode_chars; out.decode_src = &r->word_decode_src; }
         std::vector<uint8_t> piece_q;          // (the pieces' features are not part of the result)
-        RunPieces rp{};
-        if (split) {
-            rp = RunPieces{&r->run_pieces, &r->piece_reads, &piece_q, &r->run_splits, &r->words, &r->piece_costs, &r->run_costs, &r->split_parts, &r->word_splits};          // (the cut records of the compacted runs: down with the stage's wait)
+        const RunPieces rp{&r->run_pieces, &r->piece_reads, &piece_q};
+        if (split) {          // (the cut records of the compacted runs: down with the stage's wait)
+            out.splits = &r->run_splits; out.piece_costs = &r->piece_costs; out.parts = &r->split_parts; out.word_splits = &r->word_splits;
             std::vector<uint32_t> slot_of(r->line_runs.size());
             for (size_t t = 0; t < n_lines; ++t)
                 for (int32_t k = 0; k < r->line_words[t].n_runs; ++k) slot_of[(size_t)r->line_words[t].first_run + (size_t)k] = WP.slots[t].first + (uint32_t)k;
             if (const int rcs = run_cuts_collect(c, r->line_runs, slot_of, r->run_splits, r->run_pieces); rcs != STR_ER_OK) return rcs;
         }
-        const LatticeOut lto{&r->lattice_decodes, &r->lattice_decode_chars, &r->lattice_decode_src, &r->lattice_parts};
-        const TrackReadOut tro{&r->word_tracks, &r->word_track_members, &r->track_matches, &r->track_member_costs};
+        if (lattice && split) {
+            out.lattice_decodes = &r->lattice_decodes; out.lattice_chars = &r->lattice_decode_chars; out.lattice_src = &r->lattice_decode_src; out.lattice_parts = &r->lattice_parts;
+        }
         if (track) {
+            out.tracks = &r->word_tracks; out.track_members = &r->word_track_members; out.track_matches = &r->track_matches; out.track_member_costs = &r->track_member_costs;
             if (!r->have_line_links || !match) return fail(c, STR_ER_EHIP, "track read: no text tracks or no matcher (internal error)");
             for (const str_er_line_word &w : r->words)
                 if (w.line < 0 || (size_t)w.line >= n_lines || !str_er_tr::box_ok(w)) return fail(c, STR_ER_EHIP, "track read: a word outside the lines (internal error)");
@@ -742,9 +746,7 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
                 std::fprintf(stderr, "[str_er] track read: %zu words, %zu word links, %zu word tracks, %zu members, host %.3f ms\n", r->words.size(), r->word_links.size(),
                              r->word_tracks.size(), r->word_track_members.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t3).count());
         }
-        if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features, match ? &wmo : nullptr,
-                                           decode ? &wdo : nullptr, split ? &rp : nullptr, track ? &tro : nullptr, lattice && split ? &lto : nullptr);
-            rcr != STR_ER_OK)
+        if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features, split ? &rp : nullptr, &out); rcr != STR_ER_OK)
             return rcr;
         r->have_track_read = track;
         r->have_run_splits = split;
@@ -853,7 +855,7 @@ int feet_words_read(str_er_ctx *c, int32_t W, int32_t H, const str_er_line_foot 
         std::vector<str_er_run_read> rd, prd;
         std::vector<uint8_t>         q, pq;
         const RunPieces RP{&pc, split && split->piece_reads ? &prd : nullptr, &pq};
-        if ((rc = run_read_stage(c, c->stream, F.lines, lw, rn, slopes, scoring ? &rd : nullptr, q, nullptr, nullptr, with_pieces ? &RP : nullptr)) != STR_ER_OK)
+        if ((rc = run_read_stage(c, c->stream, F.lines, lw, rn, slopes, scoring ? &rd : nullptr, q, with_pieces ? &RP : nullptr)) != STR_ER_OK)
             return rc;
         if (reads) std::memcpy(reads, rd.data(), sizeof(str_er_run_read) * rd.size());
         if (q_out) std::memcpy(q_out, q.data(), q.size());

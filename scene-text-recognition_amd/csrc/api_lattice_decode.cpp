@@ -14,21 +14,15 @@ static_assert(ld::MAX_NODES == rs::MAX_PARTS, "a decoded word's parts fit the li
 
 namespace str_er_host {
 
-LdTab ld_layout(uint8_t *base, size_t n_runs, size_t n_rows, size_t n_words, size_t n_slots, bool inputs)
+LdTab ld_layout(uint8_t *base, size_t at, size_t n_words, size_t n_slots)
 {
-    LdTab  t{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_sp = take(inputs ? sizeof(str_er_run_split) * n_runs : 0), o_costs = take(rs::ALPHABET * n_rows);
-    const size_t o_first = take(inputs ? 4 * n_words : 0), o_nof = take(inputs ? 4 * n_words : 0), o_slot = take(inputs ? 4 * n_words : 0);
-    t.up_bytes = off;
-    t.o_dec = take(sizeof(str_er_lattice_decode) * n_words);
-    const size_t o_chars = take(ld::MAX_CHARS * n_words), o_src = take(ld::MAX_CHARS * n_words), o_parts = take(sizeof(str_er_split_part) * n_slots);
-    t.bytes = off;
-    t.down_bytes = off - t.o_dec;
+    LdTab t{};
+    Carve cv{at};
+    t.o_dec = cv.take(sizeof(str_er_lattice_decode) * n_words);
+    const size_t o_chars = cv.take(ld::MAX_CHARS * n_words), o_src = cv.take(ld::MAX_CHARS * n_words), o_parts = cv.take(sizeof(str_er_split_part) * n_slots);
+    t.bytes = cv.off;
+    t.down_bytes = cv.off - t.o_dec;
     if (base) {
-        t.splits = reinterpret_cast<str_er_run_split *>(base + o_sp); t.costs = base + o_costs;
-        t.first = reinterpret_cast<int32_t *>(base + o_first); t.n_of = reinterpret_cast<int32_t *>(base + o_nof); t.slot = reinterpret_cast<int32_t *>(base + o_slot);
         t.dec = reinterpret_cast<str_er_lattice_decode *>(base + t.o_dec); t.chars = base + o_chars; t.src = base + o_src;
         t.parts = reinterpret_cast<str_er_split_part *>(base + o_parts);
     }
@@ -63,13 +57,6 @@ bool args_ok(const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_
            (n_words == 0 || (first_run && n_of && dec && chars && src)) && (cap_parts == 0 || parts);
 }
 
-bool words_ok(int32_t n_runs, const int32_t *first_run, const int32_t *n_of, int32_t n_words)
-{
-    for (int32_t w = 0; w < n_words; ++w)
-        if (first_run[w] < 0 || n_of[w] < 0 || (int64_t)first_run[w] + n_of[w] > n_runs) return false;
-    return true;
-}
-
 } // namespace
 
 extern "C" {
@@ -92,21 +79,20 @@ try {
     *n_parts = 0;
     if (!c->bigram_set) return fail(c, STR_ER_ESTATE, "str_er_lattice_decode_words needs a bigram table (str_er_set_bigram)");
     if (!rs::splits_ok(splits, n_runs, n_pieces)) return fail(c, STR_ER_EINVAL, "lattice decode: a record with cuts or pieces that are none");
-    if (!words_ok(n_runs, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "lattice decode: a word outside the glyph runs");
+    if (!words_in_rows(n_runs, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "lattice decode: a word outside the glyph runs");
     if (n_words == 0) return STR_ER_OK;
     std::vector<int32_t> slot;
     uint64_t             n_slots = 0;
     if (!rs_word_slots(splits, first_run, n_runs_of_word, (size_t)n_words, slot, &n_slots)) return fail(c, STR_ER_ECAPACITY, "lattice decode: more than 2^31 parts to reserve");
     const size_t nr = (size_t)n_runs, np = (size_t)n_pieces, nw = (size_t)n_words;
     if (nr + np > 0x7FFFFFFFull / 65 || nw > 0x7FFFFFFFull / 64) return fail(c, STR_ER_ECAPACITY, "lattice decode: too many rows or words");
-    if (const int rc = c->ld_tab.ensure(c, ld_layout(nullptr, nr, nr + np, nw, (size_t)n_slots, true).bytes, "lattice decode tables"); rc != STR_ER_OK) return rc;
-    const LdTab H = ld_layout(c->ld_tab.h(), nr, nr + np, nw, (size_t)n_slots, true), D = ld_layout(c->ld_tab.d(), nr, nr + np, nw, (size_t)n_slots, true);
+    const size_t at = rows_in_layout(nullptr, nr, nr + np, nw, true).bytes;
+    if (const int rc = c->ld_tab.ensure(c, ld_layout(nullptr, at, nw, (size_t)n_slots).bytes, "lattice decode tables"); rc != STR_ER_OK) return rc;
+    const LdTab H = ld_layout(c->ld_tab.h(), at, nw, (size_t)n_slots), D = ld_layout(c->ld_tab.d(), at, nw, (size_t)n_slots);
     hipStream_t s = c->stream;
-    if (nr > 0) { std::memcpy(H.splits, splits, sizeof(str_er_run_split) * nr); std::memcpy(H.costs, run_costs, rs::ALPHABET * nr); }
-    if (np > 0) std::memcpy(H.costs + rs::ALPHABET * nr, piece_costs, rs::ALPHABET * np);          // (the pieces' rows behind the runs')
-    std::memcpy(H.first, first_run, 4 * nw); std::memcpy(H.n_of, n_runs_of_word, 4 * nw); std::memcpy(H.slot, slot.data(), 4 * nw);
-    HIP_TRY(c, hipMemcpyAsync(c->ld_tab.d(), c->ld_tab.h(), H.up_bytes, hipMemcpyHostToDevice, s));
-    launch_lattice_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, c->rs_split, D.splits, D.costs, D.costs + rs::ALPHABET * nr, D.first, D.n_of, D.slot, n_words,
+    RowsIn      I{};
+    if (const int rc = rows_in_upload(c, s, c->ld_tab, splits, run_costs, nr, piece_costs, np, first_run, n_runs_of_word, slot.data(), nw, I); rc != STR_ER_OK) return rc;
+    launch_lattice_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, c->rs_split, I.splits, I.costs, I.costs + rs::ALPHABET * nr, I.first, I.n_of, I.slot, n_words,
                           reinterpret_cast<int32_t *>(D.dec), D.chars, D.src, reinterpret_cast<int32_t *>(D.parts));
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->ld_tab.h() + H.o_dec, c->ld_tab.d() + H.o_dec, H.down_bytes, hipMemcpyDeviceToHost, s));
@@ -129,7 +115,7 @@ try {
     if (!args_ok(splits, n_runs, run_costs, piece_costs, n_pieces, first_run, n_runs_of_word, n_words, dec, chars, src, parts, cap_parts, n_parts) || !bigram)
         return STR_ER_EINVAL;
     *n_parts = 0;
-    if (!ld::params_ok(ins, del, split_cost) || !rs::splits_ok(splits, n_runs, n_pieces) || !words_ok(n_runs, first_run, n_runs_of_word, n_words)) return STR_ER_EINVAL;
+    if (!ld::params_ok(ins, del, split_cost) || !rs::splits_ok(splits, n_runs, n_pieces) || !words_in_rows(n_runs, first_run, n_runs_of_word, n_words)) return STR_ER_EINVAL;
     // every word once, its parts behind those of the words before it; the count is set even where cap_parts is too small, and nothing
     // is written to the caller's arrays before it is known to fit
     std::vector<str_er_lattice_decode> recs((size_t)n_words);

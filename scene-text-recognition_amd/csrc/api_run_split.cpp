@@ -61,27 +61,20 @@ int run_cuts_collect(str_er_ctx *c, const std::vector<str_er_line_run> &runs, co
     return STR_ER_OK;
 }
 
-RsTab rs_layout(uint8_t *base, size_t n_runs, size_t n_rows, size_t n_words, size_t n_slots, bool rows2)
+RsTab rs_layout(uint8_t *base, size_t at, size_t n_words, size_t n_slots, bool part_rows)
 {
-    RsTab  t{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_sp = take(sizeof(str_er_run_split) * n_runs), o_costs = take(rs::ALPHABET * n_rows);
-    t.o_first = take(4 * n_words);
-    const size_t o_nof = take(4 * n_words), o_slot = take(4 * n_words);
-    t.up_bytes = off;
-    t.o_out = take(16 * n_words);
-    const size_t o_parts = take(8 * n_slots);
-    t.down_tables = off - t.o_out;
-    const size_t o_rows = take(rs::ALPHABET * n_slots);
-    t.down_bytes = off - t.o_out;
-    const size_t o_np = take(4 * n_words), o_rows2 = take(rows2 ? rs::ALPHABET * n_slots : 0);
-    t.bytes = off;
+    RsTab t{};
+    Carve cv{at};
+    t.o_out = cv.take(16 * n_words);
+    const size_t o_parts = cv.take(8 * n_slots);
+    t.down_tables = cv.off - t.o_out;
+    const size_t o_rows = cv.take(part_rows ? rs::ALPHABET * n_slots : 0);
+    t.down_bytes = cv.off - t.o_out;
+    const size_t o_np = cv.take(4 * n_words);
+    t.bytes = cv.off;
     if (base) {
-        t.splits = reinterpret_cast<str_er_run_split *>(base + o_sp); t.costs = base + o_costs;
-        t.first = reinterpret_cast<int32_t *>(base + t.o_first); t.n_of = reinterpret_cast<int32_t *>(base + o_nof); t.slot = reinterpret_cast<int32_t *>(base + o_slot);
         t.word_out = reinterpret_cast<int32_t *>(base + t.o_out); t.parts = reinterpret_cast<int32_t *>(base + o_parts); t.part_costs = base + o_rows;
-        t.n_parts = reinterpret_cast<int32_t *>(base + o_np); t.part_costs2 = base + o_rows2;
+        t.n_parts = reinterpret_cast<int32_t *>(base + o_np);
     }
     return t;
 }
@@ -124,13 +117,6 @@ bool args_ok(const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_
 {
     return n_runs >= 0 && n_pieces >= 0 && n_words >= 0 && cap_parts >= 0 && n_parts && (n_runs == 0 || (splits && run_costs)) && (n_pieces == 0 || piece_costs) &&
            (n_words == 0 || (first_run && n_of && word_splits)) && (cap_parts == 0 || parts);
-}
-
-bool words_ok(int32_t n_runs, const int32_t *first_run, const int32_t *n_of, int32_t n_words)
-{
-    for (int32_t w = 0; w < n_words; ++w)
-        if (first_run[w] < 0 || n_of[w] < 0 || (int64_t)first_run[w] + n_of[w] > n_runs) return false;
-    return true;
 }
 
 } // namespace
@@ -182,20 +168,19 @@ try {
         return fail(c, STR_ER_EINVAL, "bad arguments");
     *n_parts = 0;
     if (!rs::splits_ok(splits, n_runs, n_pieces)) return fail(c, STR_ER_EINVAL, "run split: a record with cuts or pieces that are none");
-    if (!words_ok(n_runs, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "run split: a word outside the glyph runs");
+    if (!words_in_rows(n_runs, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "run split: a word outside the glyph runs");
     if (n_words == 0) return STR_ER_OK;
     std::vector<int32_t> slot;
     uint64_t             n_slots = 0;
     if (!rs_word_slots(splits, first_run, n_runs_of_word, (size_t)n_words, slot, &n_slots)) return fail(c, STR_ER_ECAPACITY, "run split: more than 2^31 parts to reserve");
     const size_t nr = (size_t)n_runs, np = (size_t)n_pieces, nw = (size_t)n_words;
-    if (const int rc = c->rs_tab.ensure(c, rs_layout(nullptr, nr, nr + np, nw, (size_t)n_slots).bytes, "run split tables"); rc != STR_ER_OK) return rc;
-    const RsTab H = rs_layout(c->rs_tab.h(), nr, nr + np, nw, (size_t)n_slots), D = rs_layout(c->rs_tab.d(), nr, nr + np, nw, (size_t)n_slots);
+    const size_t at = rows_in_layout(nullptr, nr, nr + np, nw, true).bytes;
+    if (const int rc = c->rs_tab.ensure(c, rs_layout(nullptr, at, nw, (size_t)n_slots, true).bytes, "run split tables"); rc != STR_ER_OK) return rc;
+    const RsTab H = rs_layout(c->rs_tab.h(), at, nw, (size_t)n_slots, true), D = rs_layout(c->rs_tab.d(), at, nw, (size_t)n_slots, true);
     hipStream_t s = c->stream;
-    if (nr > 0) { std::memcpy(H.splits, splits, sizeof(str_er_run_split) * nr); std::memcpy(H.costs, run_costs, rs::ALPHABET * nr); }
-    if (np > 0) std::memcpy(H.costs + rs::ALPHABET * nr, piece_costs, rs::ALPHABET * np);          // (the pieces' rows behind the runs')
-    std::memcpy(H.first, first_run, 4 * nw); std::memcpy(H.n_of, n_runs_of_word, 4 * nw); std::memcpy(H.slot, slot.data(), 4 * nw);
-    HIP_TRY(c, hipMemcpyAsync(c->rs_tab.d(), c->rs_tab.h(), H.up_bytes, hipMemcpyHostToDevice, s));
-    launch_split_words(s, D.splits, D.costs, D.costs + rs::ALPHABET * nr, D.first, D.n_of, D.slot, n_words, c->rs_split, D.word_out, D.parts, D.part_costs);
+    RowsIn      I{};
+    if (const int rc = rows_in_upload(c, s, c->rs_tab, splits, run_costs, nr, piece_costs, np, first_run, n_runs_of_word, slot.data(), nw, I); rc != STR_ER_OK) return rc;
+    launch_split_words(s, I.splits, I.costs, I.costs + rs::ALPHABET * nr, I.first, I.n_of, I.slot, n_words, c->rs_split, D.word_out, D.parts, D.part_costs);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->rs_tab.h() + H.o_out, c->rs_tab.d() + H.o_out, H.down_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
@@ -214,7 +199,7 @@ try {
     using namespace str_er_host;
     if (!args_ok(splits, n_runs, run_costs, piece_costs, n_pieces, first_run, n_runs_of_word, n_words, word_splits, parts, cap_parts, n_parts)) return STR_ER_EINVAL;
     *n_parts = 0;
-    if (!rs::params_ok(1, 1, split_cost) || !rs::splits_ok(splits, n_runs, n_pieces) || !words_ok(n_runs, first_run, n_runs_of_word, n_words)) return STR_ER_EINVAL;
+    if (!rs::params_ok(1, 1, split_cost) || !rs::splits_ok(splits, n_runs, n_pieces) || !words_in_rows(n_runs, first_run, n_runs_of_word, n_words)) return STR_ER_EINVAL;
     // every word once, its parts behind those of the words before it; the count is set even where cap_parts is too small
     std::vector<str_er_word_split> ws((size_t)n_words);
     std::vector<str_er_split_part> all;

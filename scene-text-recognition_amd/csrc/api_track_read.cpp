@@ -14,15 +14,14 @@ namespace str_er_host {
 
 TmTab tm_layout(uint8_t *base, size_t n_tracks, size_t n_members, int n_chunks)
 {
-    TmTab  t{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_first = take(4 * n_tracks), o_count = take(4 * n_tracks), o_mem = take(4 * n_members);
-    t.up_bytes = off;
-    const size_t o_part = take(16 * n_tracks * (size_t)n_chunks);
-    t.o_matches = take(sizeof(str_er_track_match) * n_tracks);
-    t.o_mcost = take(4 * n_members);
-    t.bytes = off;
+    TmTab t{};
+    Carve cv;
+    const size_t o_first = cv.take(4 * n_tracks), o_count = cv.take(4 * n_tracks), o_mem = cv.take(4 * n_members);
+    t.up_bytes = cv.off;
+    const size_t o_part = cv.take(16 * n_tracks * (size_t)n_chunks);
+    t.o_matches = cv.take(sizeof(str_er_track_match) * n_tracks);
+    t.o_mcost = cv.take(4 * n_members);
+    t.bytes = cv.off;
     if (base) {
         t.first = reinterpret_cast<int32_t *>(base + o_first); t.count = reinterpret_cast<int32_t *>(base + o_count);
         t.members = reinterpret_cast<int32_t *>(base + o_mem); t.partial = reinterpret_cast<uint64_t *>(base + o_part);
@@ -52,13 +51,6 @@ int track_match_enqueue(str_er_ctx *c, hipStream_t s, const uint8_t *d_rows, con
 } // namespace str_er_host
 
 namespace {
-
-bool words_ok(int32_t n_rows, const int32_t *first_run, const int32_t *n_of, int32_t n_words)
-{
-    for (int32_t w = 0; w < n_words; ++w)
-        if (first_run[w] < 0 || n_of[w] < 0 || (int64_t)first_run[w] + n_of[w] > n_rows) return false;
-    return true;
-}
 
 // STR_ER_OK, or why not: the tracks ascend in the member array without overlap, the members are words
 int tracks_check(const int32_t *track_first, const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks, int32_t n_words)
@@ -149,21 +141,19 @@ try {
     if (!track_args_ok(costs, n_rows, first_run, n_runs_of_word, n_words, track_first, track_count, members, n_members, n_tracks, out, member_cost))
         return fail(c, STR_ER_EINVAL, "bad arguments");
     if (c->lex_n <= 0) return fail(c, STR_ER_ESTATE, "str_er_match_tracks needs a lexicon (str_er_set_lexicon)");
-    if (!words_ok(n_rows, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "track match: a word outside the cost rows");
+    if (!words_in_rows(n_rows, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "track match: a word outside the cost rows");
     if (const int rc = tracks_check(track_first, track_count, members, n_members, n_tracks, n_words); rc != STR_ER_OK)
         return fail(c, rc, rc == STR_ER_ECAPACITY ? "track match: a track of more than 65536 members"
                                                   : "track match: a member outside the words, or tracks that do not ascend in the member array");
     for (int32_t i = 0; i < n_members; ++i) member_cost[i] = -1;
     if (n_tracks == 0) return STR_ER_OK;
-    // the rows and the words' (first, n) in the matcher's buffer, laid out as for str_er_match_words (no chunk keys of its own)
-    if (const int rc = c->wm_tab.ensure(c, wm_layout(nullptr, (size_t)n_rows, (size_t)n_words, 0).bytes, "word match tables"); rc != STR_ER_OK) return rc;
-    const WmTab H = wm_layout(c->wm_tab.h(), (size_t)n_rows, (size_t)n_words, 0), D = wm_layout(c->wm_tab.d(), (size_t)n_rows, (size_t)n_words, 0);
+    // the rows and the words' (first, n) in the matcher's buffer, as for str_er_match_words
+    if (const int rc = c->wm_tab.ensure(c, rows_in_layout(nullptr, 0, (size_t)n_rows, (size_t)n_words, false).bytes, "word match tables"); rc != STR_ER_OK) return rc;
     hipStream_t s = c->stream;
-    if (n_rows > 0) std::memcpy(H.costs, costs, (size_t)n_rows * wm::ALPHABET);
-    if (n_words > 0) { std::memcpy(H.first, first_run, 4 * (size_t)n_words); std::memcpy(H.n_of, n_runs_of_word, 4 * (size_t)n_words); }
-    HIP_TRY(c, hipMemcpyAsync(c->wm_tab.d(), c->wm_tab.h(), H.up_bytes, hipMemcpyHostToDevice, s));
+    RowsIn      I{};
+    if (const int rc = rows_in_upload(c, s, c->wm_tab, nullptr, costs, (size_t)n_rows, nullptr, 0, first_run, n_runs_of_word, nullptr, (size_t)n_words, I); rc != STR_ER_OK) return rc;
     TmTab T{};
-    if (const int rc = track_match_enqueue(c, s, D.costs, D.first, D.n_of, track_first, track_count, members, (size_t)n_members, (size_t)n_tracks, T); rc != STR_ER_OK)
+    if (const int rc = track_match_enqueue(c, s, I.costs, I.first, I.n_of, track_first, track_count, members, (size_t)n_members, (size_t)n_tracks, T); rc != STR_ER_OK)
         return rc;
     const size_t down = T.o_mcost + 4 * (size_t)n_members - T.o_matches;          // (matches | member costs lie back to back)
     HIP_TRY(c, hipMemcpyAsync(c->tm_tab.h() + T.o_matches, c->tm_tab.d() + T.o_matches, down, hipMemcpyDeviceToHost, s));
@@ -181,10 +171,9 @@ try {
     if (!track_args_ok(costs, n_rows, first_run, n_runs_of_word, n_words, track_first, track_count, members, n_members, n_tracks, out, member_cost))
         return STR_ER_EINVAL;
     if (const int rc = wm::lexicon_check(bytes, offsets, n, flags, nullptr); rc != STR_ER_OK) return rc;
-    if (!wm::params_ok(ins, del, band) || !words_ok(n_rows, first_run, n_runs_of_word, n_words)) return STR_ER_EINVAL;
+    if (!wm::params_ok(ins, del, band) || !words_in_rows(n_rows, first_run, n_runs_of_word, n_words)) return STR_ER_EINVAL;
     if (const int rc = tracks_check(track_first, track_count, members, n_members, n_tracks, n_words); rc != STR_ER_OK) return rc;
-    std::vector<uint8_t> lab(n > 0 ? (size_t)offsets[n] : 0);
-    for (size_t i = 0; i < lab.size(); ++i) lab[i] = (uint8_t)wm::char_label((unsigned char)bytes[i]);
+    const std::vector<uint8_t> lab = lexicon_labels(bytes, offsets, n);
     const int32_t         zero = 0;
     const wm::MatchParams p{ins, del, band};
     for (int32_t i = 0; i < n_members; ++i) member_cost[i] = -1;

@@ -11,34 +11,21 @@ static_assert(sizeof(str_er_word_decode) == 24, "word decode layout");
 
 namespace str_er_host {
 
-WdTab wd_layout(uint8_t *base, size_t n_runs, size_t n_words)
+WdTab wd_layout(uint8_t *base, size_t at, size_t n_words)
 {
-    WdTab  t{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_costs = take(n_runs * wd::ALPHABET), o_first = take(4 * n_words), o_nof = take(4 * n_words);
-    t.up_bytes = off;
-    t.o_dec = take(sizeof(str_er_word_decode) * n_words);
-    const size_t o_chars = take(wd::MAX_CHARS * n_words), o_src = take(wd::MAX_CHARS * n_words);
-    t.bytes = off;
-    t.down_bytes = off - t.o_dec;
-    if (base) {
-        t.costs = base + o_costs; t.first = reinterpret_cast<int32_t *>(base + o_first); t.n_of = reinterpret_cast<int32_t *>(base + o_nof);
-        t.dec = reinterpret_cast<str_er_word_decode *>(base + t.o_dec); t.chars = base + o_chars; t.src = base + o_src;
-    }
+    WdTab t{};
+    Carve cv{at};
+    t.o_dec = cv.take(sizeof(str_er_word_decode) * n_words);
+    const size_t o_chars = cv.take(wd::MAX_CHARS * n_words), o_src = cv.take(wd::MAX_CHARS * n_words);
+    t.bytes = cv.off;
+    t.down_bytes = cv.off - t.o_dec;
+    if (base) { t.dec = reinterpret_cast<str_er_word_decode *>(base + t.o_dec); t.chars = base + o_chars; t.src = base + o_src; }
     return t;
 }
 
 } // namespace str_er_host
 
 namespace {
-
-bool words_ok(int32_t n_runs, const int32_t *first_run, const int32_t *n_of, int32_t n_words)
-{
-    for (int32_t w = 0; w < n_words; ++w)
-        if (first_run[w] < 0 || n_of[w] < 0 || (int64_t)first_run[w] + n_of[w] > n_runs) return false;
-    return true;
-}
 
 bool args_ok(const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_of, int32_t n_words, const str_er_word_decode *dec,
              const uint8_t *chars, const uint8_t *src)
@@ -96,16 +83,15 @@ try {
     if (!c) return STR_ER_EINVAL;
     if (!args_ok(costs, n_runs, first_run, n_runs_of_word, n_words, dec, chars, src)) return fail(c, STR_ER_EINVAL, "bad arguments");
     if (!c->bigram_set) return fail(c, STR_ER_ESTATE, "str_er_decode_words needs a bigram table (str_er_set_bigram)");
-    if (!words_ok(n_runs, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "word decode: a word outside the cost rows");
+    if (!words_in_rows(n_runs, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "word decode: a word outside the cost rows");
     if (n_words == 0) return STR_ER_OK;
-    if (const int rc = c->wd_tab.ensure(c, wd_layout(nullptr, (size_t)n_runs, (size_t)n_words).bytes, "word decode tables"); rc != STR_ER_OK) return rc;
-    const WdTab H = wd_layout(c->wd_tab.h(), (size_t)n_runs, (size_t)n_words), D = wd_layout(c->wd_tab.d(), (size_t)n_runs, (size_t)n_words);
+    const size_t at = rows_in_layout(nullptr, 0, (size_t)n_runs, (size_t)n_words, false).bytes;
+    if (const int rc = c->wd_tab.ensure(c, wd_layout(nullptr, at, (size_t)n_words).bytes, "word decode tables"); rc != STR_ER_OK) return rc;
+    const WdTab H = wd_layout(c->wd_tab.h(), at, (size_t)n_words), D = wd_layout(c->wd_tab.d(), at, (size_t)n_words);
     hipStream_t s = c->stream;
-    if (n_runs > 0) std::memcpy(H.costs, costs, (size_t)n_runs * wd::ALPHABET);
-    std::memcpy(H.first, first_run, 4 * (size_t)n_words);
-    std::memcpy(H.n_of, n_runs_of_word, 4 * (size_t)n_words);
-    HIP_TRY(c, hipMemcpyAsync(c->wd_tab.d(), c->wd_tab.h(), H.up_bytes, hipMemcpyHostToDevice, s));
-    launch_word_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, D.costs, D.first, D.n_of, n_words, D.dec, D.chars, D.src);
+    RowsIn      I{};
+    if (const int rc = rows_in_upload(c, s, c->wd_tab, nullptr, costs, (size_t)n_runs, nullptr, 0, first_run, n_runs_of_word, nullptr, (size_t)n_words, I); rc != STR_ER_OK) return rc;
+    launch_word_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, I.costs, I.first, I.n_of, n_words, D.dec, D.chars, D.src);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->wd_tab.h() + H.o_dec, c->wd_tab.d() + H.o_dec, H.down_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
@@ -119,7 +105,7 @@ int str_er_decode_words_host(const uint8_t *costs, int32_t n_runs, const int32_t
                              const uint8_t *bigram, int32_t ins, int32_t del, str_er_word_decode *dec, uint8_t *chars, uint8_t *src)
 {
     if (!args_ok(costs, n_runs, first_run, n_runs_of_word, n_words, dec, chars, src) || !bigram) return STR_ER_EINVAL;
-    if (!wd::params_ok(ins, del) || !words_ok(n_runs, first_run, n_runs_of_word, n_words)) return STR_ER_EINVAL;
+    if (!wd::params_ok(ins, del) || !words_in_rows(n_runs, first_run, n_runs_of_word, n_words)) return STR_ER_EINVAL;
     for (int32_t w = 0; w < n_words; ++w)
         dec[w] = wd::decode_word(costs + (size_t)first_run[w] * wd::ALPHABET, n_runs_of_word[w], bigram, ins, del, chars + (size_t)w * wd::MAX_CHARS,
                                  src + (size_t)w * wd::MAX_CHARS);

@@ -12,43 +12,56 @@ static_assert(WM_GROUP == 64, "a lane an entry");
 
 namespace str_er_host {
 
-WmTab wm_layout(uint8_t *base, size_t n_runs, size_t n_words, int n_chunks)
+RowsIn rows_in_layout(uint8_t *base, size_t n_splits, size_t n_rows, size_t n_words, bool slots)
 {
-    WmTab  t{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    const size_t o_costs = take(n_runs * wm::ALPHABET), o_first = take(4 * n_words), o_nof = take(4 * n_words);
-    t.up_bytes = off;
-    const size_t o_part = take(16 * n_words * (size_t)n_chunks);
-    t.o_matches = take(sizeof(str_er_word_match) * n_words);
-    t.bytes = off;
+    RowsIn t{};
+    Carve  cv;
+    const size_t o_sp = cv.take(sizeof(str_er_run_split) * n_splits), o_costs = cv.take(wm::ALPHABET * n_rows);
+    const size_t o_first = cv.take(4 * n_words), o_nof = cv.take(4 * n_words), o_slot = cv.take(slots ? 4 * n_words : 0);
+    t.bytes = cv.off;
     if (base) {
-        t.costs = base + o_costs; t.first = reinterpret_cast<int32_t *>(base + o_first); t.n_of = reinterpret_cast<int32_t *>(base + o_nof);
-        t.partial = reinterpret_cast<uint64_t *>(base + o_part); t.matches = reinterpret_cast<str_er_word_match *>(base + t.o_matches);
+        t.splits = reinterpret_cast<str_er_run_split *>(base + o_sp); t.costs = base + o_costs;
+        t.first = reinterpret_cast<int32_t *>(base + o_first); t.n_of = reinterpret_cast<int32_t *>(base + o_nof); t.slot = reinterpret_cast<int32_t *>(base + o_slot);
     }
     return t;
 }
 
-} // namespace str_er_host
+int rows_in_upload(str_er_ctx *c, hipStream_t s, PairBuf &buf, const str_er_run_split *splits, const uint8_t *run_costs, size_t n_runs, const uint8_t *piece_costs,
+                   size_t n_pieces, const int32_t *first, const int32_t *n_of, const int32_t *slot, size_t n_words, RowsIn &D)
+{
+    const size_t n_splits = splits ? n_runs : 0, n_rows = n_runs + n_pieces;
+    const RowsIn H = rows_in_layout(buf.h(), n_splits, n_rows, n_words, slot != nullptr);
+    D = rows_in_layout(buf.d(), n_splits, n_rows, n_words, slot != nullptr);
+    if (n_splits > 0) std::memcpy(H.splits, splits, sizeof(str_er_run_split) * n_splits);
+    if (n_runs > 0) std::memcpy(H.costs, run_costs, wm::ALPHABET * n_runs);
+    if (n_pieces > 0) std::memcpy(H.costs + wm::ALPHABET * n_runs, piece_costs, wm::ALPHABET * n_pieces);          // (the pieces' rows behind the runs')
+    if (n_words > 0) {
+        std::memcpy(H.first, first, 4 * n_words); std::memcpy(H.n_of, n_of, 4 * n_words);
+        if (slot) std::memcpy(H.slot, slot, 4 * n_words);
+    }
+    HIP_TRY(c, hipMemcpyAsync(buf.d(), buf.h(), H.bytes, hipMemcpyHostToDevice, s));
+    return STR_ER_OK;
+}
 
-namespace {
+WmTab wm_layout(uint8_t *base, size_t at, size_t n_words, int n_chunks)
+{
+    WmTab t{};
+    Carve cv{at};
+    const size_t o_part = cv.take(16 * n_words * (size_t)n_chunks);
+    t.o_matches = cv.take(sizeof(str_er_word_match) * n_words);
+    t.bytes = cv.off;
+    if (base) { t.partial = reinterpret_cast<uint64_t *>(base + o_part); t.matches = reinterpret_cast<str_er_word_match *>(base + t.o_matches); }
+    return t;
+}
 
-// the entries as labels, by what the caller gave (checked before)
-std::vector<uint8_t> to_labels(const char *bytes, const int32_t *offsets, int32_t n)
+std::vector<uint8_t> lexicon_labels(const char *bytes, const int32_t *offsets, int32_t n)
 {
     std::vector<uint8_t> lab(n > 0 ? (size_t)offsets[n] : 0);
     for (size_t i = 0; i < lab.size(); ++i) lab[i] = (uint8_t)wm::char_label((unsigned char)bytes[i]);
     return lab;
 }
 
-bool words_ok(int32_t n_runs, const int32_t *first_run, const int32_t *n_of, int32_t n_words)
-{
-    for (int32_t w = 0; w < n_words; ++w)
-        if (first_run[w] < 0 || n_of[w] < 0 || (int64_t)first_run[w] + n_of[w] > n_runs) return false;
-    return true;
-}
-
-} // namespace
+} // namespace str_er_host
 
 extern "C" {
 
@@ -171,17 +184,16 @@ try {
     if (n_runs < 0 || n_words < 0 || (n_runs > 0 && !costs) || (n_words > 0 && (!first_run || !n_runs_of_word || !matches)))
         return fail(c, STR_ER_EINVAL, "bad arguments");
     if (c->lex_n <= 0) return fail(c, STR_ER_ESTATE, "str_er_match_words needs a lexicon (str_er_set_lexicon)");
-    if (!words_ok(n_runs, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "word match: a word outside the cost rows");
+    if (!words_in_rows(n_runs, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "word match: a word outside the cost rows");
     if (n_words == 0) return STR_ER_OK;
-    const int n_chunks = wm_chunks(c->lex);
-    if (const int rc = c->wm_tab.ensure(c, wm_layout(nullptr, (size_t)n_runs, (size_t)n_words, n_chunks).bytes, "word match tables"); rc != STR_ER_OK) return rc;
-    const WmTab H = wm_layout(c->wm_tab.h(), (size_t)n_runs, (size_t)n_words, n_chunks), D = wm_layout(c->wm_tab.d(), (size_t)n_runs, (size_t)n_words, n_chunks);
+    const int    n_chunks = wm_chunks(c->lex);
+    const size_t at = rows_in_layout(nullptr, 0, (size_t)n_runs, (size_t)n_words, false).bytes;
+    if (const int rc = c->wm_tab.ensure(c, wm_layout(nullptr, at, (size_t)n_words, n_chunks).bytes, "word match tables"); rc != STR_ER_OK) return rc;
+    const WmTab H = wm_layout(c->wm_tab.h(), at, (size_t)n_words, n_chunks), D = wm_layout(c->wm_tab.d(), at, (size_t)n_words, n_chunks);
     hipStream_t s = c->stream;
-    if (n_runs > 0) std::memcpy(H.costs, costs, (size_t)n_runs * wm::ALPHABET);
-    std::memcpy(H.first, first_run, 4 * (size_t)n_words);
-    std::memcpy(H.n_of, n_runs_of_word, 4 * (size_t)n_words);
-    HIP_TRY(c, hipMemcpyAsync(c->wm_tab.d(), c->wm_tab.h(), H.up_bytes, hipMemcpyHostToDevice, s));
-    launch_word_match(s, c->lex, c->wm_prm, D.costs, D.first, D.n_of, n_words, D.partial, D.matches);
+    RowsIn      I{};
+    if (const int rc = rows_in_upload(c, s, c->wm_tab, nullptr, costs, (size_t)n_runs, nullptr, 0, first_run, n_runs_of_word, nullptr, (size_t)n_words, I); rc != STR_ER_OK) return rc;
+    launch_word_match(s, c->lex, c->wm_prm, I.costs, I.first, I.n_of, n_words, D.partial, D.matches);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(H.matches, D.matches, sizeof(str_er_word_match) * (size_t)n_words, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
@@ -194,8 +206,8 @@ int str_er_match_words_host(const uint8_t *costs, int32_t n_runs, const int32_t 
 try {
     if (n_runs < 0 || n_words < 0 || (n_runs > 0 && !costs) || (n_words > 0 && (!first_run || !n_runs_of_word || !matches))) return STR_ER_EINVAL;
     if (const int rc = wm::lexicon_check(bytes, offsets, n, flags, nullptr); rc != STR_ER_OK) return rc;
-    if (!wm::params_ok(ins, del, band) || !words_ok(n_runs, first_run, n_runs_of_word, n_words)) return STR_ER_EINVAL;
-    const std::vector<uint8_t> lab = to_labels(bytes, offsets, n);
+    if (!wm::params_ok(ins, del, band) || !words_in_rows(n_runs, first_run, n_runs_of_word, n_words)) return STR_ER_EINVAL;
+    const std::vector<uint8_t> lab = lexicon_labels(bytes, offsets, n);
     const int32_t          zero = 0;
     const wm::MatchParams  p{ins, del, band};
     for (int32_t w = 0; w < n_words; ++w)

@@ -30,6 +30,7 @@
 #include "er_group.h"
 #include "flood_order.h"
 #include "stage_rules.h"
+#include "read_plan.h"
 #include <functional>
 #include <map>
 #include <thread>
@@ -297,14 +298,15 @@ struct str_er_ctx {
     PairBuf  words_out;               // slots | records | run slots of k_foot_words
     // STR_ER_WANT_RUN_READ / str_er_feet_read
     DevBuf   run_atlas;               // the byte tiles of the runs of a call (k_run_tiles), in shelves (pack_run_tiles)
-    PairBuf  run_tab;                 // tiles | boxes | rotations of the runs
+    PairBuf  run_tab;                 // tiles | boxes | rotations of the runs | first run, run count, part slot per word and the split records of the reading chain
+    DevBuf   read_rows;               // the cost rows of a detect call's reading chain (read_plan.h): A | U | parts of A | parts of U, an absent set taking no bytes
     uint64_t n_atlas_grown = 0;       // statistics: how often run_atlas was allocated or grown (str_er_run_atlas_stats)
     // STR_ER_WANT_WORD_MATCH / str_er_set_lexicon / str_er_match_words / str_er_run_costs
     DevBuf   lexicon;                 // length tables | goff | index | chars of the padded lexicon (lex.n_groups > 0: one is set)
     WmLexDev lex{};
     int32_t  lex_n = 0; uint32_t lex_flags = 0;
     WmParams wm_prm{64, 64, 2};
-    PairBuf  wm_tab;                  // cost rows | first run, run count per word | chunk keys | matches
+    PairBuf  wm_tab;                  // (str_er_match_words / _match_tracks: cost rows | first run, run count per word) | chunk keys | matches
     // STR_ER_WANT_TRACK_READ / str_er_match_tracks (str_er_set_word_link)
     int32_t  wlink_num = 1, wlink_den = 2;
     PairBuf  tm_tab;                  // first member, member count per track | members | chunk keys | matches | member costs
@@ -312,13 +314,13 @@ struct str_er_ctx {
     DevBuf   bigram;                  // the 66 x 66 table (bigram_set: one is set)
     bool     bigram_set = false;
     int32_t  wd_ins = 0, wd_del = 0;
-    PairBuf  wd_tab;                  // cost rows | first run, run count per word | records | labels | sources
+    PairBuf  wd_tab;                  // (str_er_decode_words: cost rows | first run, run count per word) | records | labels | sources
     // str_er_feet_split / str_er_split_words (str_er_set_run_split)
     int32_t  rs_num = 1, rs_den = 4, rs_split = 8;
     PairBuf  rs_out;                  // a record per run slot of k_run_cuts
-    PairBuf  rs_tab;                  // splits | rows of the runs and pieces | first run, run count, slot per word | records | parts | part rows
+    PairBuf  rs_tab;                  // (str_er_split_words: splits | rows of the runs and pieces | first run, run count, slot per word) | records | parts | (its part rows) | part counts
     // STR_ER_WANT_LATTICE_DECODE / str_er_lattice_decode_words
-    PairBuf  ld_tab;                  // (the caller's splits | rows of the runs and pieces | first run, run count, slot per word) | records | labels | sources | parts
+    PairBuf  ld_tab;                  // (str_er_lattice_decode_words: splits | rows of the runs and pieces | first run, run count, slot per word) | records | labels | sources | parts
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -635,89 +637,79 @@ int run_cuts_collect(str_er_ctx *c, const std::vector<str_er_line_run> &runs, co
 // the tiles laid out and expanded into the atlas, then the scorer's launch chain on the atlas as a device plane with one box a run and
 // the slope of the run's line (slopes: one per line, or null: all 0; a slope that is not finite counts as 0).  One upload, the
 // launches, the copies back and a wait of its own on s.  reads == null: the features only (no model needed).
-// match (optional, with reads): STR_ER_WANT_WORD_MATCH -- k_run_costs and the matcher behind the scorer on s, their tables back with the
-// same wait: the words of `words` against the context's lexicon, the cost rows and the class probabilities of the runs
-struct WordMatchOut {
-    const std::vector<str_er_line_word> *words;
-    std::vector<str_er_word_match> *matches;
-    std::vector<uint8_t> *costs;
-    std::vector<double> *probs;
-};
-// decode (optional, with reads): STR_ER_WANT_WORD_DECODE -- the decoder behind the scorer on s in the same way, on unfolded cost rows (a
-// second k_run_costs into wd_tab where the matcher's are folded); costs / probs are filled here only where match is null
-struct WordDecodeOut {
-    const std::vector<str_er_line_word> *words;
-    std::vector<str_er_word_decode> *decodes;
-    std::vector<uint8_t> *chars, *src;
-    std::vector<uint8_t> *costs;
-    std::vector<double> *probs;
-};
 // pieces (optional): the pieces of the runs (str_er_run_split) read with them -- their tiles behind the runs' in the one atlas, one
 // launch chain over both; reads (null: no labels) and q receive the pieces' results, the runs' are what they are without pieces
 struct RunPieces {
     const std::vector<str_er_run_piece> *pieces;
     std::vector<str_er_run_read> *reads;
     std::vector<uint8_t> *q;
-    // STR_ER_WANT_RUN_SPLIT (all null otherwise; with reads): k_split_words behind k_run_costs on s -- the segmentation of the runs of
-    // `words` (splits: their records; n_parts is filled in), the parts and word records, the pieces' cost rows; the matcher and the
-    // decoder then work on the parts' rows
-    std::vector<str_er_run_split> *splits = nullptr;
-    const std::vector<str_er_line_word> *words = nullptr;
-    std::vector<uint8_t> *costs = nullptr;
-    std::vector<uint8_t> *run_costs = nullptr;          // (the runs' rows, filled where neither the matcher nor the decoder leaves them)
-    std::vector<str_er_split_part> *parts = nullptr;
-    std::vector<str_er_word_split> *word_splits = nullptr;
 };
-// the layout of c->rs_tab for k_split_words (base: either side of the pair, or null for the size alone): n_rows cost rows of which the
-// first n_runs are the runs' and the others the pieces', n_words words with n_slots part slots in all.  rows2: a second set of part rows
-struct RsTab {
+// chain (optional, with reads): the consumers behind the scorer on s, their tables back with the same wait.  A consumer runs where its
+// first table is given; read_plan.h says which cost rows and part rows the call then makes and what every consumer and table reads.
+struct ReadChainOut {
+    const std::vector<str_er_line_word> *words = nullptr;      // the words every consumer works on
+    std::vector<uint8_t> *run_costs = nullptr;                  // the runs' cost rows (match, decode or split) ...
+    std::vector<double>  *run_probs = nullptr;                  // ... and class probabilities (match or decode)
+    std::vector<str_er_word_match> *matches = nullptr;          // STR_ER_WANT_WORD_MATCH: the words against the context's lexicon
+    std::vector<str_er_word_decode> *decodes = nullptr;         // STR_ER_WANT_WORD_DECODE: the words under the context's bigram table
+    std::vector<uint8_t> *decode_chars = nullptr, *decode_src = nullptr;
+    // STR_ER_WANT_RUN_SPLIT (with pieces): the segmentation of the words' runs (splits: their records; n_parts is filled in), the pieces'
+    // cost rows, the parts and word records; the matcher and the decoder then work on the parts' rows
+    std::vector<str_er_run_split> *splits = nullptr; std::vector<uint8_t> *piece_costs = nullptr;
+    std::vector<str_er_split_part> *parts = nullptr; std::vector<str_er_word_split> *word_splits = nullptr;
+    // STR_ER_WANT_TRACK_READ (with match): the track match of the word tracks the host made before the call
+    const std::vector<str_er_word_track> *tracks = nullptr; const std::vector<int32_t> *track_members = nullptr;
+    std::vector<str_er_track_match> *track_matches = nullptr; std::vector<int32_t> *track_member_costs = nullptr;
+    // STR_ER_WANT_LATTICE_DECODE (with split): the words over their piece lattices under the bigram table
+    std::vector<str_er_lattice_decode> *lattice_decodes = nullptr; std::vector<str_er_split_part> *lattice_parts = nullptr;
+    std::vector<uint8_t> *lattice_chars = nullptr, *lattice_src = nullptr;
+    void preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k) const;      // every table of the plan as a call without runs leaves it (k: the model's classes)
+};
+// carving a table buffer: take(bytes) is the offset of the next piece, and the one after it starts at the next multiple of 256
+struct Carve {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
+};
+// what a caller-rows entry point (str_er_match_words, _decode_words, _split_words, _lattice_decode_words, _match_tracks) puts up at the
+// front of its table buffer (base: either side of the pair, or null for the size alone): n_splits split records, n_rows cost rows, the
+// words' first run and run count, and with slots their part slot.  The detect calls keep their rows elsewhere (str_er_ctx::read_rows).
+struct RowsIn {
     str_er_run_split *splits;
     uint8_t *costs;
-    int32_t *first, *n_of, *slot, *word_out, *parts, *n_parts;
-    uint8_t *part_costs, *part_costs2;
-    size_t   o_first, up_bytes, o_out, bytes;
+    int32_t *first, *n_of, *slot;
+    size_t   bytes;
+};
+RowsIn rows_in_layout(uint8_t *base, size_t n_splits, size_t n_rows, size_t n_words, bool slots);
+// the caller's arrays into the front of buf (sized before) and up on s: splits (null: none) of the n_runs runs, the runs' rows and
+// behind them the pieces', the words' (first, n) and slot (null: none); D receives the device side of the layout
+int rows_in_upload(str_er_ctx *c, hipStream_t s, PairBuf &buf, const str_er_run_split *splits, const uint8_t *run_costs, size_t n_runs, const uint8_t *piece_costs,
+                   size_t n_pieces, const int32_t *first, const int32_t *n_of, const int32_t *slot, size_t n_words, RowsIn &D);
+// the layout of what k_split_words leaves in c->rs_tab from byte `at` on (the inputs' bytes): n_words word records and part counts,
+// n_slots part slots, and with part_rows the parts' rows
+struct RsTab {
+    int32_t *word_out, *parts, *n_parts;
+    uint8_t *part_costs;
+    size_t   o_out, bytes;
     size_t   down_tables, down_bytes;        // from o_out: the word records and the parts; ... and the parts' rows behind them
 };
-RsTab rs_layout(uint8_t *base, size_t n_runs, size_t n_rows, size_t n_words, size_t n_slots, bool rows2 = false);
+RsTab rs_layout(uint8_t *base, size_t at, size_t n_words, size_t n_slots, bool part_rows);
 // the part slot of every word: the atoms of the words before it; the total in *n_slots; false above 2^31 - 1
 bool rs_word_slots(const str_er_run_split *splits, const int32_t *first_run, const int32_t *n_of, size_t n_words, std::vector<int32_t> &slot, uint64_t *n_slots);
 // after the wait: the word records and the compacted parts from the host side of the layout (null parts / part_costs: not copied);
 // false where a word's parts lie outside its slots
 bool rs_compact(const RsTab &H, const std::vector<int32_t> &slot, uint64_t n_slots, str_er_word_split *word_splits, str_er_split_part *parts, uint8_t *part_costs,
                 uint64_t *n_parts);
-// track (optional, with match): STR_ER_WANT_TRACK_READ -- the track match of the word tracks (made on the host before the call) behind
-// the matcher on s, on the rows and the (first, n) arrays the matcher read; its tables back with the same wait
-struct TrackReadOut {
-    const std::vector<str_er_word_track> *tracks;
-    const std::vector<int32_t> *members;
-    std::vector<str_er_track_match> *matches;
-    std::vector<int32_t> *member_costs;
-};
-// lattice (optional, with the splits of pieces): STR_ER_WANT_LATTICE_DECODE -- k_lattice_decode behind the scorer on s, on the split
-// records, words and slots k_split_words reads and on unfolded rows of the runs and pieces: the decoder's where it runs, else the
-// matcher's where its lexicon does not fold, else the split's own, else those of one more k_run_costs into ld_tab; its tables back with
-// the same wait
-struct LatticeOut {
-    std::vector<str_er_lattice_decode> *decodes;
-    std::vector<uint8_t> *chars, *src;
-    std::vector<str_er_split_part> *parts;
-};
 int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words,
                    const std::vector<str_er_line_run> &runs, const double *slopes, std::vector<str_er_run_read> *reads, std::vector<uint8_t> &q,
-                   const WordMatchOut *match = nullptr, const WordDecodeOut *decode = nullptr, const RunPieces *pieces = nullptr,
-                   const TrackReadOut *track = nullptr, const LatticeOut *lattice = nullptr);
+                   const RunPieces *pieces = nullptr, const ReadChainOut *chain = nullptr);
 // ---- defined in api_lattice_decode.cpp
-// the layout of c->ld_tab (base: either side of the pair, or null for the size alone): with inputs the caller's n_runs split records,
-// n_rows cost rows (the pieces' behind the runs') and the words' (first, n, slot); without, n_rows rows of its own alone (0: none); then
-// what comes down: n_words records, labels and sources and n_slots part slots
+// the layout of what k_lattice_decode leaves in c->ld_tab from byte `at` on (the inputs' bytes), all of which comes down: n_words
+// records, labels and sources and n_slots part slots
 struct LdTab {
-    str_er_run_split *splits;
-    uint8_t *costs;
-    int32_t *first, *n_of, *slot;
     str_er_lattice_decode *dec; uint8_t *chars, *src; str_er_split_part *parts;
-    size_t up_bytes, o_dec, down_bytes, bytes;      // dec | chars | src | parts lie back to back (each aligned): one copy down
+    size_t o_dec, down_bytes, bytes;      // dec | chars | src | parts lie back to back (each aligned): one copy down
 };
-LdTab ld_layout(uint8_t *base, size_t n_runs, size_t n_rows, size_t n_words, size_t n_slots, bool inputs);
+LdTab ld_layout(uint8_t *base, size_t at, size_t n_words, size_t n_slots);
 // after the wait: the records with first_part set and the compacted parts from the host side of the layout (null: not copied); false
 // where a word's parts lie outside its slots
 bool ld_compact(const LdTab &H, const std::vector<int32_t> &slot, uint64_t n_slots, str_er_lattice_decode *dec, str_er_split_part *parts, uint64_t *n_parts);
@@ -734,21 +726,21 @@ TmTab tm_layout(uint8_t *base, size_t n_tracks, size_t n_members, int n_chunks);
 int track_match_enqueue(str_er_ctx *c, hipStream_t s, const uint8_t *d_rows, const int32_t *d_first, const int32_t *d_n_of, const int32_t *track_first,
                         const int32_t *track_count, const int32_t *members, size_t n_members, size_t n_tracks, TmTab &D);
 // ---- defined in api_word_match.cpp
-// the layout of c->wm_tab for n_runs cost rows and n_words words (base: either side of the pair, or null for the size alone)
+// the layout of what the matcher leaves in c->wm_tab from byte `at` on (the inputs' bytes) for n_words words: chunk keys | matches
 struct WmTab {
-    uint8_t *costs; int32_t *first, *n_of; uint64_t *partial; str_er_word_match *matches;
-    size_t up_bytes;        // costs | first | n_of lie at the front: what a caller's input takes
+    uint64_t *partial; str_er_word_match *matches;
     size_t o_matches, bytes;
 };
-WmTab wm_layout(uint8_t *base, size_t n_runs, size_t n_words, int n_chunks);
+WmTab wm_layout(uint8_t *base, size_t at, size_t n_words, int n_chunks);
+// a lexicon's entries as labels (checked before: wm::lexicon_check)
+std::vector<uint8_t> lexicon_labels(const char *bytes, const int32_t *offsets, int32_t n);
 // ---- defined in api_word_decode.cpp
-// the layout of c->wd_tab in the same way
+// the layout of what the decoder leaves in c->wd_tab in the same way, all of which comes down
 struct WdTab {
-    uint8_t *costs; int32_t *first, *n_of; str_er_word_decode *dec; uint8_t *chars, *src;
-    size_t up_bytes;        // costs | first | n_of lie at the front: what a caller's input takes
+    str_er_word_decode *dec; uint8_t *chars, *src;
     size_t o_dec, down_bytes, bytes;      // dec | chars | src lie back to back (each aligned): one copy down
 };
-WdTab wd_layout(uint8_t *base, size_t n_runs, size_t n_words);
+WdTab wd_layout(uint8_t *base, size_t at, size_t n_words);
 // ---- defined in words_host.cpp and lines_host.cpp (HIP-free)
 bool word_gap_ok(int32_t num, int32_t den);       // what str_er_set_word_gap takes
 // inter * den >= num * (pa + pb - inter): footprints of pa and pb pixels, inter of them common, are duplicates (links) at num / den

@@ -125,6 +125,19 @@ def test_stage_rules_match_the_entry_points_checks(tmp_path):
     assert out.strip().startswith("stage rules ok")
 
 
+def test_read_plan_matches_the_stages_conditions(tmp_path):
+    """csrc/read_plan.h, the one statement of which cost rows and part rows the reading chain behind the run scorer makes and who reads
+    them, against the conditions run_read_stage spelled out one by one (transcribed in tests/cpp/read_plan_check.cpp): for all 64 inputs
+    the same launches in the same order, every consumer on the rows of the same launch with the same window, every returned table from
+    the same launch."""
+    csrc = os.path.join(ROOT, "scene-text-recognition_amd", "csrc")
+    exe = str(tmp_path / "read_plan_check")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", csrc, os.path.join(ROOT, "tests", "cpp", "read_plan_check.cpp"),
+                    "-o", exe], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    assert out.strip().startswith("read plan ok: 64 inputs")
+
+
 def test_frame_rules(tmp_path):
     """csrc/frame_rules.h, the one statement of what a source frame is (bytes of a row, rows of a frame, BGR / NV12 / plane) and of which
     str_er_image_ref a list call or a list submission of the stream accepts: every rejection with its code and message and their order,
