@@ -165,6 +165,14 @@ extern "C" {
  * _WORD_MATCH.  Every call that honours _RUN_SPLIT honours it.  It changes no other output of the call and combines with every other
  * STR_ER_WANT_* flag.                                                                                                               */
 #define STR_ER_WANT_LATTICE_DECODE (67108864u)
+/* output option: every word of STR_ER_WANT_RUN_SPLIT matched against the lexicon of str_er_set_lexicon with the segmentation of its runs
+ * free: the best and the second-best entry over the lattice of all pieces of all its runs, and for the best its segmentation and its
+ * alignment (str_er_result_lattice_matches / _lattice_match_src / _lattice_match_parts; the contract is at str_er_lattice_match).  Needs
+ * STR_ER_WANT_RUN_SPLIT and STR_ER_WANT_WORD_MATCH (and through them STR_ER_WANT_RUN_READ): STR_ER_EINVAL without either and wherever
+ * they are refused (the strip path, the per-plane calls), and a lexicon: STR_ER_ESTATE without one (the matcher's rule); the context
+ * is usable afterwards.  It needs no bigram table.  It changes no other output of the call -- str_er_result_word_matches still reads the
+ * split sequence -- and combines with every other STR_ER_WANT_* flag.                                                               */
+#define STR_ER_WANT_LATTICE_MATCH (134217728u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -644,7 +652,8 @@ typedef struct str_er_word_decode {
  *     arg min of the row of each part.
  *   Limits: at most 3 cuts a run; the cut follows the upright column profile, no slanted or curved cuts; the segmentation is chosen
  *     per run from the scorer alone, ahead of any lexicon or bigram table: this output makes no joint decode over the piece lattice.
- *     That is a separate output, str_er_lattice_decode (STR_ER_WANT_LATTICE_DECODE): one pass per word over all pieces under the table.
+ *     That is a separate output, str_er_lattice_decode (STR_ER_WANT_LATTICE_DECODE): one pass per word over all pieces under the table;
+ *     and, against the lexicon, str_er_lattice_match (STR_ER_WANT_LATTICE_MATCH): every entry over all pieces of the word.
  *   Beside the matcher and the decoder: with STR_ER_WANT_RUN_SPLIT next to STR_ER_WANT_WORD_MATCH or _WORD_DECODE both run on the split
  *     sequence instead of the runs: m in their contracts is n_parts, with the same limit of 32, and src of the decoder indexes the
  *     word's parts.  run_costs and run_probs stay per run; the rows of the pieces (str_er_result_piece_costs) are folded where the
@@ -706,13 +715,54 @@ typedef struct str_er_word_split {
  *     str_er_word_decode cost on the split sequence of str_er_run_split plus SPLIT * (n_parts of that sequence - n_runs) -- both are
  *     paths of the lattice (where those words are decoded at all).
  *   Limits: the lattice is that of str_er_run_split (at most 3 upright cuts a run); one path per word, no margins; no lexicon
- *     enters: the matcher still reads the split sequence of str_er_run_split.                                                          */
+ *     enters here: the lexicon over the same lattice is a separate output, str_er_lattice_match (STR_ER_WANT_LATTICE_MATCH), while
+ *     str_er_word_match still reads the split sequence of str_er_run_split.                                                            */
 typedef struct str_er_lattice_decode {
     int32_t  cost, read_cost;             /*  0,  4                                   */
     int32_t  n_chars, n_sub;              /*  8, 12                                   */
     int32_t  n_del, n_ins;                /* 16, 20                                   */
     int32_t  first_part, n_parts;         /* 24, 28: into the lattice part table      */
 } str_er_lattice_decode;     /* 32 bytes; one per word                                */
+
+/* The lexicon match of a word over its piece lattice (STR_ER_WANT_LATTICE_MATCH, str_er_lattice_match_words): for every word the best
+ * and the second-best entry of the lexicon when the segmentation of its runs is free, and for the best its segmentation and its
+ * alignment.  A definition of this library; integers only, exact, and the host states the same rules
+ * (str_er_lattice_match_words_host).
+ *   Lattice: that of str_er_lattice_decode.  Run r has A_r = n_cuts + 1 atoms; the word's nodes are 0 .. N, N = sum of A_r, off_r as
+ *     there.  The edges are the pieces (i, j) of every run with the row C_{r,i,j}: the run's own row for (0, A_r), else the piece's
+ *     row.  The penalty of an edge is s = SPLIT if i > 0, else 0; no edge crosses a run boundary.  SPLIT comes from
+ *     str_er_set_run_split; INS, DEL, the band and the fold from str_er_set_word_match and the lexicon.  With the fold a row is read as
+ *     min(C[a], C[a']) for the two letters a, a' of a case pair, as in str_er_word_match.
+ *   Cost of the entry e of the length l, in int32: D[0][0] = 0 and D[0][j] = j * INS.  For the node n >= 1 in run r with the local
+ *     index jl = n - off_r, D[n][j] is the minimum of these candidates, in this order: for i = 0 .. jl - 1 ascending, with
+ *     f = off_r + i: SUB(i) = D[f][j - 1] + C_{r,i,jl}[e_j] + s, only for j >= 1; then DEL(i) = D[f][j] + DEL + s; last
+ *     INS = D[n][j - 1] + INS, only for j >= 1.  cost(e) = D[N][l].  Equivalently cost(e) is the minimum over all segmentations P of
+ *     the word of the str_er_word_match cost of e on the rows of P's parts plus SPLIT * (|P| - n_runs).
+ *   Band: an entry is tried iff max(1, R - band) <= l <= min(32, N + band), with R the word's run count: every part count from R to N
+ *     is reachable, so this is the union of the matcher's bands over all segmentations.  A word with N > 32 tries nothing; N = 0 (a
+ *     word without runs) behaves as the matcher does for m = 0.
+ *   Record: (cost, entry) and (second_cost, second_entry) are the two smallest (cost, index) of the entries tried, as in
+ *     str_er_word_match, -1 where nothing qualifies; n_tried is the number of entries tried.  free_cost is the word's
+ *     str_er_word_split cost, the cheapest segmentation with free characters; it is made for every word, also for N > 32.  The parts of
+ *     the winning entry come from a backtrack from (N, l): at every cell the first candidate in the order above that attains D[n][j]
+ *     is the move taken.  The edges taken, in word order, are the word's parts: str_er_split_part records with piece = -1 for a whole
+ *     run and the indices of str_er_result_split_parts, in a part table of their own, back to back in word order.  n_parts, n_del and
+ *     n_ins are 0 where entry is -1; n_parts - n_del characters are substituted, and n_parts - n_del + n_ins = l.
+ *   Sources: 32 bytes per word, padded with 0xFF.  The byte for character j of the winning entry is the word-relative index of the part
+ *     it was read from; for an inserted character it is 0x80 | (the number of parts that end at or before the node it was inserted at).
+ *   It follows: (1) if no run of the word has a cut, the first six fields equal str_er_word_match's on the runs, field for field, and
+ *     the parts are the runs; (2) cost <= the str_er_word_match cost on the unsplit runs, wherever that matcher tried anything;
+ *     (3) cost <= the str_er_word_match cost on the split sequence of str_er_run_split + SPLIT * (n_parts of that sequence - n_runs):
+ *     both are paths of the lattice, and their bands lie inside this one.
+ *   Limits: one path per word, for the best entry only; the track match (str_er_track_match) still reads the matcher's rows: pooling
+ *     lattices over a word track is not part of this; no bigram table enters.                                                          */
+typedef struct str_er_lattice_match {
+    int32_t  entry, cost;                 /*  0,  4                                   */
+    int32_t  second_entry, second_cost;   /*  8, 12                                   */
+    int32_t  free_cost, n_tried;          /* 16, 20                                   */
+    int32_t  first_part, n_parts;         /* 24, 28: into the lattice match part table */
+    int32_t  n_del, n_ins;                /* 32, 36                                   */
+} str_er_lattice_match;      /* 40 bytes; one per word                                */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -1158,6 +1208,25 @@ int str_er_lattice_decode_words_host(const str_er_run_split *splits, int32_t n_r
  * made).  The pointer may be NULL.                                                                                                  */
 int str_er_lattice_decode_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
 
+/* The lexicon match over the piece lattice (str_er_lattice_match) of n_words words on the caller's rows, on the GPU, with the context's
+ * lexicon (str_er_set_lexicon), INS / DEL / band (str_er_set_word_match) and SPLIT (str_er_set_run_split): the arguments up to n_words,
+ * the validation and the capacity rule are those of str_er_lattice_decode_words.  The rows are taken as given; the fold of the lexicon
+ * is applied when they are read.  matches receives n_words records, src 32 bytes per word, parts the parts of the winning entries back
+ * to back in word order and *n_parts their number.  cap_parts too small -> STR_ER_ECAPACITY, *n_parts still set (it is at most the sum
+ * over the words' runs of n_cuts + 1).  STR_ER_ESTATE without a lexicon.  It needs no model.                                        */
+int str_er_lattice_match_words(str_er_ctx *ctx, const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs,
+                               int32_t n_pieces, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, str_er_lattice_match *matches,
+                               uint8_t *src, str_er_split_part *parts, int32_t cap_parts, int32_t *n_parts);
+/* The same rules on one host thread, with the lexicon (as str_er_set_lexicon takes it), INS / DEL / band and SPLIT as arguments (with
+ * the checks of str_er_set_lexicon, str_er_set_word_match and str_er_set_run_split).  Pure: no context, no GPU.                       */
+int str_er_lattice_match_words_host(const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs, int32_t n_pieces,
+                                    const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, const char *bytes, const int32_t *offsets,
+                                    int32_t n, uint32_t flags, int32_t ins, int32_t del, int32_t band, int32_t split_cost, str_er_lattice_match *matches,
+                                    uint8_t *src, str_er_split_part *parts, int32_t cap_parts, int32_t *n_parts);
+/* Statistics of the buffer of STR_ER_WANT_LATTICE_MATCH / str_er_lattice_match_words: the bytes of its tables on the device (0: never
+ * made).  The pointer may be NULL.                                                                                                  */
+int str_er_lattice_match_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -1414,6 +1483,12 @@ const str_er_lattice_decode *str_er_result_lattice_decodes(const str_er_result *
 const uint8_t               *str_er_result_lattice_decode_chars(const str_er_result *r, uint64_t *n_bytes);
 const uint8_t               *str_er_result_lattice_decode_src(const str_er_result *r, uint64_t *n_bytes);
 const str_er_split_part     *str_er_result_lattice_parts(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_LATTICE_MATCH (str_er_lattice_match): one record per word of str_er_result_words(), 32 source bytes per word, and the
+ * parts of the winning entries back to back in word order.  Each returns NULL and 0 without the flag; a call without words returns
+ * empty arrays (not NULL).                                                                                                          */
+const str_er_lattice_match  *str_er_result_lattice_matches(const str_er_result *r, int32_t *n);
+const uint8_t               *str_er_result_lattice_match_src(const str_er_result *r, uint64_t *n_bytes);
+const str_er_split_part     *str_er_result_lattice_match_parts(const str_er_result *r, int32_t *n);
 /* With STR_ER_WANT_TRACK_READ (str_er_word_link): the word links sorted by (a, b); the word tracks; their members (word indices); one
  * track index per word of str_er_result_words() (-1: not eligible); one match per word track; one cost per slot of the member array.
  * Each returns NULL and 0 without the flag; a call without words returns empty arrays (not NULL).                                  */

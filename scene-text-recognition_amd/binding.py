@@ -90,6 +90,10 @@ WANT_RUN_SPLIT = 16777216
 # track_matches / track_member_costs / word_track_text / text_track_match_text; the contract is at str_er_word_link)
 WANT_TRACK_READ = 33554432
 WANT_LATTICE_DECODE = 67108864
+# every word of WANT_RUN_SPLIT against the lexicon with the segmentation of its runs free: the best and second entry over the lattice of all
+# pieces of all its runs, the winner's parts and sources (needs WANT_RUN_SPLIT and WANT_WORD_MATCH; Result.lattice_matches /
+# lattice_match_src / lattice_match_parts / word_lattice_match_text; the contract is at str_er_lattice_match)
+WANT_LATTICE_MATCH = 134217728
 # str_er_word_link: a word a of frame f and a word b of the adjacent frame f + 1 whose boxes share inter > 0 pixels; link: linked at the call's threshold
 WORD_LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("inter", "<u4"), ("link", "<u4")])
 # str_er_word_track: members = word_track_members[first:first + count] (word indices, ascending), rep the one with the most pixels
@@ -120,6 +124,9 @@ assert RUN_SPLIT_DTYPE.itemsize == 32 and RUN_PIECE_DTYPE.itemsize == 32 and SPL
 LATTICE_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4"),
                                  ("first_part", "<i4"), ("n_parts", "<i4")])
 assert LATTICE_DECODE_DTYPE.itemsize == 32
+LATTICE_MATCH_DTYPE = np.dtype([("entry", "<i4"), ("cost", "<i4"), ("second_entry", "<i4"), ("second_cost", "<i4"), ("free_cost", "<i4"), ("n_tried", "<i4"),
+                                ("first_part", "<i4"), ("n_parts", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
+assert LATTICE_MATCH_DTYPE.itemsize == 40
 # str_er_line_run: frame columns [x0, x1) and rows [y0, y1), half open; word: its row of the word table
 LINE_RUN_DTYPE = np.dtype([("x0", "<i4"), ("x1", "<i4"), ("y0", "<i4"), ("y1", "<i4"), ("pixels", "<u4"), ("word", "<i4")])
 # str_er_line_word: the runs line_runs[first_run:first_run + n_runs] of line `line`, their bounding box and pixels
@@ -423,6 +430,13 @@ def load_library():
         fn = getattr(L, "str_er_result_" + name)
         fn.argtypes, fn.restype = [vp, cnt], vp
     L.str_er_lattice_decode_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    for name, cnt in (("lattice_matches", i32p), ("lattice_match_src", C.POINTER(C.c_uint64)), ("lattice_match_parts", i32p)):
+        fn = getattr(L, "str_er_result_" + name)
+        fn.argtypes, fn.restype = [vp, cnt], vp
+    L.str_er_lattice_match_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_lattice_match_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, i32p]
+    L.str_er_lattice_match_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_int32, vp, vp, vp, C.c_int32, i32p]
     L.str_er_lattice_decode_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, i32p]
     L.str_er_lattice_decode_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp,
                                                    C.c_int32, i32p]
@@ -581,6 +595,8 @@ class Result:
         self._word_decode_chars = None
         self._word_decode_src = None
         self._run_splits = None    # with WANT_RUN_SPLIT: the tables behind run_splits / run_pieces / piece_reads / piece_costs / split_parts / word_splits
+        self._lattice_matches = None  # with WANT_LATTICE_MATCH: the tables behind lattice_matches / lattice_match_src / lattice_match_parts
+        self._lattice_match_src = self._lattice_match_parts = None
         self._lattice_decodes = None  # with WANT_LATTICE_DECODE: the tables behind lattice_decodes / lattice_decode_chars / lattice_decode_src / lattice_parts
         self._word_links = None    # with WANT_TRACK_READ: the tables behind word_links / word_tracks / word_track_members / word_track_of_words / track_matches / track_member_costs
         self._word_tracks = self._word_track_members = self._word_track_of_words = self._track_matches = self._track_member_costs = None
@@ -766,6 +782,51 @@ class Result:
     def frame_line_lattice_text(self, i: int) -> str:
         """With WANT_LATTICE_DECODE: the jointly decoded text of frame line i: words_lattice_text_of_line of its representative joined by one blank."""
         return " ".join(self.words_lattice_text_of_line(int(self.frame_lines[i]["rep"])))
+
+    def _lattice_match_table(self, table):
+        if table is None:
+            raise ValueError("the result has no lattice matches (pass WANT_LATTICE_MATCH / want_lattice_match=True)")
+        return table
+
+    @property
+    def lattice_matches(self) -> np.ndarray:
+        """With WANT_LATTICE_MATCH: LATTICE_MATCH_DTYPE per word of words, in the same order."""
+        return self._lattice_match_table(getattr(self, "_lattice_matches", None))
+
+    @property
+    def lattice_match_src(self) -> np.ndarray:
+        """With WANT_LATTICE_MATCH: (n words, 32) uint8, per character of the winning entry the word-relative index of the part it was
+        read from; for an inserted character 0x80 | the number of parts that end at or before its node; 0xFF past the entry."""
+        return self._lattice_match_table(getattr(self, "_lattice_match_src", None))
+
+    @property
+    def lattice_match_parts(self) -> np.ndarray:
+        """With WANT_LATTICE_MATCH: SPLIT_PART_DTYPE, the parts of the winning entries of the words back to back in word order (piece
+        -1: a whole run; the indices are those of split_parts)."""
+        return self._lattice_match_table(getattr(self, "_lattice_match_parts", None))
+
+    def word_lattice_match_text(self, w: int) -> str:
+        """With WANT_LATTICE_MATCH: the lexicon entry that matches word w best over its piece lattice, as it was given to set_lexicon;
+        word_text(w) for a word without a match."""
+        e = int(self.lattice_matches[w]["entry"])
+        lex = getattr(self, "_lexicon", ())
+        return lex[e] if 0 <= e < len(lex) else self.word_text(w)
+
+    def word_lattice_match_parts(self, w: int) -> np.ndarray:
+        """With WANT_LATTICE_MATCH: the parts of word w (SPLIT_PART_DTYPE), the segmentation chosen with its best entry; none for a word
+        without a match."""
+        d = self.lattice_matches[w]
+        return self.lattice_match_parts[int(d["first_part"]):int(d["first_part"]) + int(d["n_parts"])]
+
+    def words_lattice_match_text_of_line(self, t: int) -> list:
+        """With WANT_LATTICE_MATCH: word_lattice_match_text of the words of line t, left to right."""
+        lw = self.line_words[t]
+        return [self.word_lattice_match_text(w) for w in range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))]
+
+    def frame_line_lattice_match_text(self, i: int) -> str:
+        """With WANT_LATTICE_MATCH: the text of frame line i matched over the piece lattices: words_lattice_match_text_of_line of its
+        representative joined by one blank."""
+        return " ".join(self.words_lattice_match_text_of_line(int(self.frame_lines[i]["rep"])))
 
     @property
     def word_decodes(self) -> np.ndarray:
@@ -1202,6 +1263,10 @@ class ERFilter:
                                     res._lattice_decode_chars = table(L.str_er_result_lattice_decode_chars, np.uint8, n64).reshape(-1, 64)
                                     res._lattice_decode_src = table(L.str_er_result_lattice_decode_src, np.uint8, n64).reshape(-1, 64)
                                     res._lattice_parts = table(L.str_er_result_lattice_parts, SPLIT_PART_DTYPE)
+                                res._lattice_matches = table(L.str_er_result_lattice_matches, LATTICE_MATCH_DTYPE)
+                                if res._lattice_matches is not None:
+                                    res._lattice_match_src = table(L.str_er_result_lattice_match_src, np.uint8, n64).reshape(-1, 32)
+                                    res._lattice_match_parts = table(L.str_er_result_lattice_match_parts, SPLIT_PART_DTYPE)
                             if res._word_matches is not None or res._word_decodes is not None:
                                 nr = len(res._run_reads)
                                 res._run_costs = table(L.str_er_result_run_costs, np.uint8, n64).reshape(nr, 65)
@@ -1286,7 +1351,7 @@ class ERFilter:
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
                     want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -1299,7 +1364,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode, lattice_match=want_lattice_match), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -1421,7 +1486,7 @@ class ERFilter:
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
                          want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -1429,7 +1494,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode, lattice_match=want_lattice_match))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1842,6 +1907,21 @@ class ERFilter:
         self._check(self.L.str_er_lattice_decode_words(self.h, *a[0], *a[1]))
         return _lattice_out(a)
 
+    def lattice_match_stats(self) -> int:
+        """str_er_lattice_match_stats: the bytes of the lattice match tables on the device; 0: never made."""
+        a = C.c_uint64()
+        self._check(self.L.str_er_lattice_match_stats(self.h, C.byref(a)))
+        return int(a.value)
+
+    def lattice_match_words(self, splits, run_costs, piece_costs, first_run, n_runs_of_word):
+        """str_er_lattice_match_words: the lexicon match over the piece lattice (str_er_lattice_match) of the words [first_run[w],
+        first_run[w] + n_runs_of_word[w]), from the cost rows of the runs (n runs, 65) and of their pieces (n pieces, 65) as they are (the
+        fold is applied when they are read), with the lexicon of set_lexicon, INS / DEL / band of set_word_match and SPLIT of
+        set_run_split.  Returns (LATTICE_MATCH_DTYPE per word, (n, 32) uint8 sources, SPLIT_PART_DTYPE parts)."""
+        a = _lattice_match_args(splits, run_costs, piece_costs, first_run, n_runs_of_word)
+        self._check(self.L.str_er_lattice_match_words(self.h, *a[0], *a[1]))
+        return _lattice_match_out(a)
+
     def run_atlas_stats(self):
         """str_er_run_atlas_stats: (bytes of the run tile atlas, how often it was allocated or grown)."""
         a, b = C.c_uint64(), C.c_uint64()
@@ -2241,6 +2321,43 @@ def lattice_decode_words_host(splits, run_costs, piece_costs, first_run, n_runs_
     return _lattice_out(a)
 
 
+def _lattice_match_args(splits, run_costs, piece_costs, first_run, n_runs_of_word):
+    sp = np.ascontiguousarray(splits, dtype=RUN_SPLIT_DTYPE).reshape(-1)
+    rc = np.ascontiguousarray(run_costs, dtype=np.uint8).reshape(-1, 65)
+    pc = np.ascontiguousarray(piece_costs, dtype=np.uint8).reshape(-1, 65)
+    fr = np.ascontiguousarray(first_run, dtype=np.int32).reshape(-1)
+    no = np.ascontiguousarray(n_runs_of_word, dtype=np.int32).reshape(-1)
+    if len(sp) != len(rc) or len(fr) != len(no):
+        raise ValueError("splits and run_costs need one row per run, first_run and n_runs_of_word one entry per word")
+    cap = int(min(4 * int(no.astype(np.int64).clip(0).sum()), 2 ** 31 - 1))          # (a run has at most 4 parts)
+    rec = np.zeros(max(1, len(fr)), LATTICE_MATCH_DTYPE)
+    sr = np.full((max(1, len(fr)), 32), 0xFF, np.uint8)
+    parts = np.zeros(max(1, cap), SPLIT_PART_DTYPE)
+    n = C.c_int32()
+    p = lambda a: _np_ptr(a) if len(a) else None
+    return ((p(sp), len(sp), p(rc), p(pc), len(pc), p(fr), p(no), len(fr)), (_np_ptr(rec), _np_ptr(sr), _np_ptr(parts), cap, C.byref(n)),
+            (sp, rc, pc, fr, no), rec, sr, parts, n)
+
+
+def _lattice_match_out(a):
+    nw = len(a[2][3])
+    return a[3][:nw], a[4][:nw], a[5][:a[6].value].copy()
+
+
+def lattice_match_words_host(splits, run_costs, piece_costs, first_run, n_runs_of_word, words, fold_case: bool = True, ins: int = 64, dele: int = 64,
+                             band: int = 2, split_cost: int = 8):
+    """str_er_lattice_match_words_host (pure host, one thread): ERFilter.lattice_match_words with the lexicon and the parameters as arguments."""
+    a = _lattice_match_args(splits, run_costs, piece_costs, first_run, n_runs_of_word)
+    words = list(words)
+    raw, off = _lexicon_bytes(words)
+    buf = np.frombuffer(raw, np.uint8) if raw else np.zeros(1, np.uint8)
+    rc = load_library().str_er_lattice_match_words_host(*a[0], _np_ptr(buf), _np_ptr(off), len(words), LEXICON_FOLD_CASE if fold_case else 0, int(ins), int(dele),
+                                                        int(band), int(split_cost), *a[1])
+    if rc != 0:
+        raise StrErError(rc, "str_er_lattice_match_words_host")
+    return _lattice_match_out(a)
+
+
 def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: int = 0, dele: int = 0):
     """str_er_decode_words_host (pure host, one thread): ERFilter.decode_words with the table and the parameters as arguments."""
     cs, fr, no, out, ch, sr = _decode_args(costs, first_run, n_runs_of_word)
@@ -2252,10 +2369,10 @@ def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: 
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False, track_read=False, lattice_decode=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False, track_read=False, lattice_decode=False, lattice_match=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (track_read, WANT_TRACK_READ), (lattice_decode, WANT_LATTICE_DECODE), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (track_read, WANT_TRACK_READ), (lattice_decode, WANT_LATTICE_DECODE), (lattice_match, WANT_LATTICE_MATCH), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -2719,23 +2836,23 @@ class FrameStream:
         return slot.value, arr
 
     def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit(self.h, slot, w, h, 3 * w, 3 * w * h, n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
         """The staging buffer holds n_frames tightly packed NV12 frames (w * h * 3 / 2 bytes each)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_nv12(self.h, slot, w, h, w, w * (h + h // 2), n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         if a.ndim == 3:
             a = a[None]
@@ -2753,21 +2870,21 @@ class FrameStream:
         return int(t.value)
 
     def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
         """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
         return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
 
     def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
         """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
         return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
 
     def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
         """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         arr = (ImageRef * max(1, len(refs)))(*refs)

@@ -702,7 +702,7 @@ int fill_geometry(str_er_ctx *c, str_er_result *r, const GeomPass &GP)
 // read, and its footprints are still in c->foot_bits
 // track: the word links and word tracks of STR_ER_WANT_TRACK_READ on the host before the reading (the text tracks of r are made: fill_links),
 // the track match behind the matcher (frame_of: the frame of every line, frame_wh: the level-0 sizes of the frames)
-int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode, bool split, bool lattice, bool track,
+int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode, bool split, bool lattice, bool lmatch, bool track,
                const std::vector<uint32_t> &frame_of, const std::vector<int32_t> &frame_wh)
 {
     const auto   t2 = std::chrono::steady_clock::now();
@@ -728,6 +728,7 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         if (lattice && split) {
             out.lattice_decodes = &r->lattice_decodes; out.lattice_chars = &r->lattice_decode_chars; out.lattice_src = &r->lattice_decode_src; out.lattice_parts = &r->lattice_parts;
         }
+        if (lmatch && split && match) { out.lattice_matches = &r->lattice_matches; out.lattice_match_src = &r->lattice_match_src; out.lattice_match_parts = &r->lattice_match_parts; }
         if (track) {
             out.tracks = &r->word_tracks; out.track_members = &r->word_track_members; out.track_matches = &r->track_matches; out.track_member_costs = &r->track_member_costs;
             if (!r->have_line_links || !match) return fail(c, STR_ER_EHIP, "track read: no text tracks or no matcher (internal error)");
@@ -751,6 +752,7 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         r->have_track_read = track;
         r->have_run_splits = split;
         r->have_lattice_decodes = lattice && split;
+        r->have_lattice_matches = lmatch && split && match;
         r->have_run_reads = true;
         r->have_word_matches = match;
         r->have_word_decodes = decode;
@@ -793,7 +795,7 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
     if ((rc = fill_frame_lines(c, r, frame_of, pyr_of, S.feet.pairs, n_fl)) != STR_ER_OK) return rc;
     if (want.links && (rc = fill_links(c, b, r, frame_of, T, S.links)) != STR_ER_OK) return rc;
     if (want.geom && (rc = fill_geometry(c, r, S.geom)) != STR_ER_OK) return rc;
-    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split, want.lattice, want.track, frame_of, b.frame_wh)) != STR_ER_OK) return rc;
+    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split, want.lattice, want.lmatch, want.track, frame_of, b.frame_wh)) != STR_ER_OK) return rc;
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
                              "%zu bytes back, host %.3f ms before + %.3f ms after the device\n",

@@ -16,16 +16,18 @@
 //   track match      the same window as the matcher
 //   decoder          U's part rows (A's where U is A) with (slot, n_parts) if split, else U with (first, n_of)
 //   lattice decode   U's rows (runs first, pieces from row n_run on) with (first, n_of, slot) and the split records
+//   lattice match    A's rows (runs first, pieces from row n_run on) with (first, n_of, slot) and the split records; iff match && split
 //
 //   result table     source
 //   run_costs        A if match, else U
 //   piece_costs      A if match, else U
 //   run_probs        present iff match or decode
 //
-// The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, rs_tab, ld_tab and
+// The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, rs_tab, ld_tab, lm_tab and
 // tm_tab hold what their kernels leave.
 #include "str_er_ctx.h"
 #include "lattice_decode_kernels.h"
+#include "lattice_match_kernels.h"
 #include "run_split_kernels.h"
 
 namespace str_er_host {
@@ -42,6 +44,10 @@ void ReadChainOut::preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k
     if (p.lattice) {
         lattice_decodes->assign(n_words, str_er_lattice_decode{}); lattice_chars->assign(64 * n_words, 0xFF); lattice_src->assign(64 * n_words, 0xFF);
         lattice_parts->clear();
+    }
+    if (p.lmatch) {
+        lattice_matches->assign(n_words, str_er_lattice_match{-1, -1, -1, -1, 0, 0, 0, 0, 0, 0}); lattice_match_src->assign(32 * n_words, 0xFF);
+        lattice_match_parts->clear();
     }
 }
 
@@ -83,7 +89,7 @@ struct ReadCall {
     RunTab   TH{}, TD{};
     OcrBuf   buf{};
     uint8_t *rows[2] = {nullptr, nullptr}, *parts[2] = {nullptr, nullptr};
-    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; WmTab WD{}; WdTab DD{}; TmTab KD{};
+    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; WmTab WD{}; WdTab DD{}; TmTab KD{};
 
     // phase 1 (host alone): the tiles and rotations of the runs and pieces, every box checked, and their places in the atlas
     int geometry(const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words, const std::vector<str_er_line_run> &runs, const double *slopes,
@@ -177,12 +183,14 @@ struct ReadCall {
         if ((p.match && (rc = c->wm_tab.ensure(c, wm_layout(nullptr, 0, n_words, n_chunks).bytes, "word match tables")) != STR_ER_OK) ||
             (p.decode && (rc = c->wd_tab.ensure(c, wd_layout(nullptr, 0, n_words).bytes, "word decode tables")) != STR_ER_OK) ||
             (p.split && (rc = c->rs_tab.ensure(c, rs_layout(nullptr, 0, n_words, (size_t)n_slots, false).bytes, "run split tables")) != STR_ER_OK) ||
-            (p.lattice && (rc = c->ld_tab.ensure(c, ld_layout(nullptr, 0, n_words, (size_t)n_slots).bytes, "lattice decode tables")) != STR_ER_OK))
+            (p.lattice && (rc = c->ld_tab.ensure(c, ld_layout(nullptr, 0, n_words, (size_t)n_slots).bytes, "lattice decode tables")) != STR_ER_OK) ||
+            (p.lmatch && (rc = c->lm_tab.ensure(c, lm_layout(nullptr, 0, n_words, (size_t)n_slots, n_chunks).bytes, "lattice match tables")) != STR_ER_OK))
             return rc;
         if (p.match) WD = wm_layout(c->wm_tab.d(), 0, n_words, n_chunks);
         if (p.decode) DD = wd_layout(c->wd_tab.d(), 0, n_words);
         if (p.split) { SH = rs_layout(c->rs_tab.h(), 0, n_words, (size_t)n_slots, false); SD = rs_layout(c->rs_tab.d(), 0, n_words, (size_t)n_slots, false); }
         if (p.lattice) { LH = ld_layout(c->ld_tab.h(), 0, n_words, (size_t)n_slots); LD = ld_layout(c->ld_tab.d(), 0, n_words, (size_t)n_slots); }
+        if (p.lmatch) { MH = lm_layout(c->lm_tab.h(), 0, n_words, (size_t)n_slots, n_chunks); MD = lm_layout(c->lm_tab.d(), 0, n_words, (size_t)n_slots, n_chunks); }
         return STR_ER_OK;
     }
 
@@ -221,6 +229,9 @@ struct ReadCall {
                     rc != STR_ER_OK)
                     return rc;
         }
+        if (p.lmatch && n_words > 0)          // the matcher's rows of the runs and, behind them, the pieces: folded when they are staged
+            launch_lattice_match(s, c->lex, c->wm_prm, c->rs_split, TD.splits, rows[p.lattice_match_set], rows[p.lattice_match_set] + 65 * n_run, TD.first, TD.n_of, TD.slot,
+                                 (int)n_words, MD.partial, reinterpret_cast<int32_t *>(MD.matches), MD.src, reinterpret_cast<int32_t *>(MD.parts));
         make_set(SET_U, false);
         if (p.decode) {
             const Window W = window(p.decode_set);
@@ -260,7 +271,15 @@ struct ReadCall {
         }
         if (p.split && n_words > 0) HIP_TRY(c, down(c->rs_tab.h() + SH.o_out, c->rs_tab.d() + SH.o_out, SH.down_tables));          // (into page-locked memory: compacted below)
         if (p.lattice && n_words > 0) HIP_TRY(c, down(c->ld_tab.h() + LH.o_dec, c->ld_tab.d() + LH.o_dec, LH.down_bytes));
+        if (p.lmatch && n_words > 0) HIP_TRY(c, down(c->lm_tab.h() + MH.o_matches, c->lm_tab.d() + MH.o_matches, MH.down_bytes));
         HIP_TRY(c, wait_stream(c, s));
+        if (p.lmatch && n_words > 0) {          // the records with their first parts, the parts compacted, the sources as they are
+            uint64_t total = 0;
+            if (!lm_compact(MH, slot, n_slots, nullptr, nullptr, &total)) return fail(c, STR_ER_EHIP, "lattice match: a word's parts outside its slots (internal error)");
+            o.lattice_match_parts->assign((size_t)total, str_er_split_part{0, 0});
+            lm_compact(MH, slot, n_slots, o.lattice_matches->data(), o.lattice_match_parts->data(), &total);
+            std::memcpy(o.lattice_match_src->data(), MH.src, 32 * n_words);
+        }
         if (p.lattice && n_words > 0) {          // the records with their first parts, the parts compacted, the strings as they are
             uint64_t total = 0;
             if (!ld_compact(LH, slot, n_slots, nullptr, nullptr, &total)) return fail(c, STR_ER_EHIP, "lattice decode: a word's parts outside its slots (internal error)");
@@ -294,7 +313,8 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     static const ReadChainOut none{};
     const ReadChainOut       &o = chain && reads ? *chain : none;
     const size_t              n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0;
-    const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.tracks != nullptr, c->lex.fold != 0);
+    const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.tracks != nullptr, c->lex.fold != 0,
+                                   o.lattice_matches != nullptr);
     if (reads) reads->assign(n_run, str_er_run_read{});
     q.assign(1800 * n_run, 0);
     if (pieces) {

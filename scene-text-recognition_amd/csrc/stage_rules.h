@@ -37,6 +37,15 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
         {!k.frames && any(STR_ER_WANT_TRACK_READ), STR_ER_EINVAL, "STR_ER_WANT_TRACK_READ needs frames (not the per-plane calls)"},
         {any(STR_ER_WANT_TRACK_READ) && !any(STR_ER_WANT_LINE_LINKS), STR_ER_EINVAL, "STR_ER_WANT_TRACK_READ needs STR_ER_WANT_LINE_LINKS"},
         {any(STR_ER_WANT_TRACK_READ) && !any(STR_ER_WANT_WORD_MATCH), STR_ER_EINVAL, "STR_ER_WANT_TRACK_READ needs STR_ER_WANT_WORD_MATCH"},
+        // STR_ER_WANT_LATTICE_MATCH rides on STR_ER_WANT_RUN_SPLIT (the lattice) and on STR_ER_WANT_WORD_MATCH (the rows and the lexicon):
+        // refused without either and where either is refused, ahead of those flags' rules, so that the refusal names this flag (the
+        // lexicon rule stays the matcher's, below); a call without the flag meets no new rule
+        {k.strip && any(STR_ER_WANT_LATTICE_MATCH), STR_ER_EINVAL, "STR_ER_WANT_LATTICE_MATCH is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_LATTICE_MATCH), STR_ER_EINVAL, "STR_ER_WANT_LATTICE_MATCH needs frames (not the per-plane calls)"},
+        {any(STR_ER_WANT_LATTICE_MATCH) && !any(STR_ER_WANT_RUN_SPLIT), STR_ER_EINVAL, "STR_ER_WANT_LATTICE_MATCH needs STR_ER_WANT_RUN_SPLIT"},
+        {any(STR_ER_WANT_LATTICE_MATCH) && !any(STR_ER_WANT_WORD_MATCH), STR_ER_EINVAL, "STR_ER_WANT_LATTICE_MATCH needs STR_ER_WANT_WORD_MATCH"},
+        {any(STR_ER_WANT_LATTICE_MATCH) && !any(STR_ER_WANT_RUN_READ), STR_ER_EINVAL,
+         "STR_ER_WANT_LATTICE_MATCH needs STR_ER_WANT_RUN_READ (through STR_ER_WANT_RUN_SPLIT and STR_ER_WANT_WORD_MATCH)"},
         // STR_ER_WANT_LATTICE_DECODE rides on STR_ER_WANT_RUN_SPLIT (and through it on STR_ER_WANT_RUN_READ): refused without it and where
         // it is refused, ahead of that flag's rules, so that the refusal names this flag (its table rule is with the models' below); a
         // call without the flag meets no new rule

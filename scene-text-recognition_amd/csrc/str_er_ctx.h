@@ -173,6 +173,10 @@ struct str_er_result {
     std::vector<uint8_t> lattice_decode_chars, lattice_decode_src;
     std::vector<str_er_split_part> lattice_parts;
     bool have_lattice_decodes = false;
+    std::vector<str_er_lattice_match> lattice_matches;  // STR_ER_WANT_LATTICE_MATCH: per word of words, 32 source bytes per word, and the parts of the winning entries
+    std::vector<uint8_t> lattice_match_src;
+    std::vector<str_er_split_part> lattice_match_parts;
+    bool have_lattice_matches = false;
     std::vector<str_er_word_link> word_links;    // STR_ER_WANT_TRACK_READ: the word links, the word tracks, their members, the track of every word of words,
     std::vector<str_er_word_track> word_tracks;  // one match per word track and one cost per slot of the member array
     std::vector<int32_t> word_track_members, word_track_of_words;
@@ -321,6 +325,8 @@ struct str_er_ctx {
     PairBuf  rs_tab;                  // (str_er_split_words: splits | rows of the runs and pieces | first run, run count, slot per word) | records | parts | (its part rows) | part counts
     // STR_ER_WANT_LATTICE_DECODE / str_er_lattice_decode_words
     PairBuf  ld_tab;                  // (str_er_lattice_decode_words: splits | rows of the runs and pieces | first run, run count, slot per word) | records | labels | sources | parts
+    // STR_ER_WANT_LATTICE_MATCH / str_er_lattice_match_words
+    PairBuf  lm_tab;                  // (str_er_lattice_match_words: splits | rows of the runs and pieces | first run, run count, slot per word) | chunk keys | records | sources | parts
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -608,6 +614,7 @@ struct LineStageWants {
     bool decode = false;      // STR_ER_WANT_WORD_DECODE: every word under the bigram table (k_run_costs and the decoder behind the scorer)
     bool track = false;       // STR_ER_WANT_TRACK_READ: the word links and word tracks on the host before the reading, k_track_match behind the matcher
     bool lattice = false;     // STR_ER_WANT_LATTICE_DECODE: every word over its piece lattice under the bigram table (k_lattice_decode behind the scorer, on what k_split_words reads)
+    bool lmatch = false;      // STR_ER_WANT_LATTICE_MATCH: every word against the lexicon over its piece lattice (k_lattice_match behind k_split_words on the matcher's rows)
     bool split = false;       // STR_ER_WANT_RUN_SPLIT: the cuts of every run (k_run_cuts behind k_foot_words, down with the stage's wait), the pieces read with the runs, k_split_words behind the scorer
 };
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
@@ -663,6 +670,9 @@ struct ReadChainOut {
     // STR_ER_WANT_LATTICE_DECODE (with split): the words over their piece lattices under the bigram table
     std::vector<str_er_lattice_decode> *lattice_decodes = nullptr; std::vector<str_er_split_part> *lattice_parts = nullptr;
     std::vector<uint8_t> *lattice_chars = nullptr, *lattice_src = nullptr;
+    // STR_ER_WANT_LATTICE_MATCH (with split and match): the words against the context's lexicon over their piece lattices
+    std::vector<str_er_lattice_match> *lattice_matches = nullptr; std::vector<uint8_t> *lattice_match_src = nullptr;
+    std::vector<str_er_split_part> *lattice_match_parts = nullptr;
     void preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k) const;      // every table of the plan as a call without runs leaves it (k: the model's classes)
 };
 // carving a table buffer: take(bytes) is the offset of the next piece, and the one after it starts at the next multiple of 256
@@ -670,7 +680,7 @@ struct Carve {
     size_t off = 0;
     size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
 };
-// what a caller-rows entry point (str_er_match_words, _decode_words, _split_words, _lattice_decode_words, _match_tracks) puts up at the
+// what a caller-rows entry point (str_er_match_words, _decode_words, _split_words, _lattice_decode_words, _lattice_match_words, _match_tracks) puts up at the
 // front of its table buffer (base: either side of the pair, or null for the size alone): n_splits split records, n_rows cost rows, the
 // words' first run and run count, and with slots their part slot.  The detect calls keep their rows elsewhere (str_er_ctx::read_rows).
 struct RowsIn {
@@ -713,6 +723,17 @@ LdTab ld_layout(uint8_t *base, size_t at, size_t n_words, size_t n_slots);
 // after the wait: the records with first_part set and the compacted parts from the host side of the layout (null: not copied); false
 // where a word's parts lie outside its slots
 bool ld_compact(const LdTab &H, const std::vector<int32_t> &slot, uint64_t n_slots, str_er_lattice_decode *dec, str_er_split_part *parts, uint64_t *n_parts);
+// ---- defined in api_lattice_match.cpp
+// the layout of what k_lattice_match and k_lattice_match_final leave in c->lm_tab from byte `at` on (the inputs' bytes): the chunk keys
+// of n_words words, and what comes down: their records and sources and n_slots part slots
+struct LmTab {
+    uint64_t *partial; str_er_lattice_match *matches; uint8_t *src; str_er_split_part *parts;
+    size_t o_matches, down_bytes, bytes;      // matches | src | parts lie back to back (each aligned): one copy down
+};
+LmTab lm_layout(uint8_t *base, size_t at, size_t n_words, size_t n_slots, int n_chunks);
+// after the wait: the records with first_part set and the compacted parts from the host side of the layout (null: not copied); false
+// where a word's parts lie outside its slots
+bool lm_compact(const LmTab &H, const std::vector<int32_t> &slot, uint64_t n_slots, str_er_lattice_match *matches, str_er_split_part *parts, uint64_t *n_parts);
 // ---- defined in api_track_read.cpp
 // the layout of c->tm_tab for n_tracks tracks over a member array of n_members (base: either side of the pair, or null for the size alone)
 struct TmTab {

@@ -966,6 +966,83 @@ public:
         return s;
     }
 
+    // Every word matched against the lexicon over the lattice of the pieces of its runs (STR_ER_WANT_LATTICE_MATCH; the contract is at
+    // str_er_lattice_match in include/str_er.h): one record per word of LineWords::words, 32 source bytes per word (0xFF past the winning
+    // entry; a source indexes the word's parts) and the parts of the winning entries back to back in word order (piece -1: the whole run;
+    // the indices are those of RunSplits::parts).  Needs STR_ER_WANT_RUN_SPLIT, STR_ER_WANT_WORD_MATCH and a lexicon in the context.
+    struct LatticeMatches {
+        std::vector<str_er_lattice_match> matches;
+        std::vector<uint8_t>              src;
+        std::vector<str_er_split_part>    parts;
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static LatticeMatches lattice_matches(const str_er_result *r)
+    {
+        LatticeMatches out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_lattice_match *p = str_er_result_lattice_matches(r, &n)) out.matches.assign(p, p + n);
+        if (const uint8_t *p = str_er_result_lattice_match_src(r, &nb)) out.src.assign(p, p + nb);
+        if (const str_er_split_part *p = str_er_result_lattice_match_parts(r, &n)) out.parts.assign(p, p + n);
+        return out;
+    }
+    // the lattice match of the words [first_run[w], first_run[w] + n_runs[w]) on the caller's cost rows (str_er_lattice_match_words): splits
+    // one record per run, run_costs and piece_costs 65 bytes a row; the context's lexicon, INS / DEL / band and SPLIT
+    LatticeMatches lattice_match_words(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                                       const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs)
+    {
+        LatticeMatches out = lattice_match_out(splits, run_costs, piece_costs, first_run, n_runs);
+        int32_t n = 0;
+        check(str_er_lattice_match_words(ctx_.get(), splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                         piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65),
+                                         first_run.empty() ? nullptr : first_run.data(), n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(),
+                                         out.matches.empty() ? nullptr : out.matches.data(), out.src.empty() ? nullptr : out.src.data(), out.parts.data(),
+                                         (int32_t)out.parts.size(), &n));
+        out.parts.resize((size_t)n);
+        return out;
+    }
+    // the same rules on one host thread, with the lexicon, INS / DEL / band and SPLIT as arguments (str_er_lattice_match_words_host)
+    static LatticeMatches lattice_match_words_host(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs,
+                                                   const std::vector<uint8_t> &piece_costs, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs,
+                                                   const std::vector<std::string> &lexicon, bool fold_case = true, int32_t ins = 64, int32_t del = 64, int32_t band = 2,
+                                                   int32_t split_cost = 8)
+    {
+        std::string          bytes;
+        std::vector<int32_t> offsets{0};
+        for (const std::string &w : lexicon) {
+            bytes += w;
+            if (bytes.size() > (size_t)INT32_MAX) throw std::invalid_argument("lattice_match_words_host: too many bytes");
+            offsets.push_back((int32_t)bytes.size());
+        }
+        LatticeMatches out = lattice_match_out(splits, run_costs, piece_costs, first_run, n_runs);
+        int32_t n = 0;
+        if (str_er_lattice_match_words_host(splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                            piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65),
+                                            first_run.empty() ? nullptr : first_run.data(), n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(),
+                                            bytes.data(), offsets.data(), (int32_t)lexicon.size(), fold_case ? STR_ER_LEXICON_FOLD_CASE : 0u, ins, del, band, split_cost,
+                                            out.matches.empty() ? nullptr : out.matches.data(), out.src.empty() ? nullptr : out.src.data(), out.parts.data(),
+                                            (int32_t)out.parts.size(), &n) != STR_ER_OK)
+            throw std::invalid_argument("lattice_match_words_host");
+        out.parts.resize((size_t)n);
+        return out;
+    }
+    // the string of word w matched over its piece lattice: the lexicon entry (as given in `lexicon`) that matches it best, its own reading
+    // where none does
+    static std::string word_lattice_match_text(const LineWords &lw, const RunReads &rd, const LatticeMatches &lm, const std::vector<std::string> &lexicon, size_t w)
+    {
+        const int32_t e = lm.matches.at(w).entry;
+        return e >= 0 && (size_t)e < lexicon.size() ? lexicon[(size_t)e] : word_text(lw, rd, w);
+    }
+    // the text of line t matched over the piece lattices: its words' strings joined by one blank
+    static std::string line_lattice_match_text(const LineWords &lw, const RunReads &rd, const LatticeMatches &lm, const std::vector<std::string> &lexicon, size_t t)
+    {
+        std::string s;
+        const str_er_line_words &L = lw.lines.at(t);
+        for (int32_t k = L.first_word; k < L.first_word + L.n_words; ++k)
+            s += (k > L.first_word ? " " : "") + word_lattice_match_text(lw, rd, lm, lexicon, (size_t)k);
+        return s;
+    }
+
     // The text lines of consecutive frames linked into text tracks (STR_ER_WANT_LINE_LINKS; the contract is at str_er_line_link in
     // include/str_er.h): the overlaps across adjacent frames, the track of every line of str_er_result_texts(), the tracks, the line
     // indices their first / count index, and the footprints of the lines of the first ([0]) and of the last frame ([1]).
@@ -1187,6 +1264,21 @@ private:
         out.decodes.resize(first_run.size());
         out.chars.resize(64 * first_run.size());
         out.src.resize(64 * first_run.size());
+        out.parts.resize(cap);
+        return out;
+    }
+    // the outputs of lattice_match_words(_host) sized for the words: a run has at most 4 parts
+    static LatticeMatches lattice_match_out(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                                            const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs)
+    {
+        if (first_run.size() != n_runs.size() || run_costs.size() != 65 * splits.size() || piece_costs.size() % 65)
+            throw std::invalid_argument("lattice_match_words: 65 bytes a run and a piece, one record a run, one span a word");
+        size_t cap = 1;
+        for (const int32_t k : n_runs) cap += 4 * (size_t)(k > 0 ? k : 0);
+        if (cap > 0x7FFFFFFFull) throw std::invalid_argument("lattice_match_words: too many runs");
+        LatticeMatches out;
+        out.matches.resize(first_run.size());
+        out.src.resize(32 * first_run.size());
         out.parts.resize(cap);
         return out;
     }
