@@ -173,6 +173,14 @@ extern "C" {
  * is usable afterwards.  It needs no bigram table.  It changes no other output of the call -- str_er_result_word_matches still reads the
  * split sequence -- and combines with every other STR_ER_WANT_* flag.                                                               */
 #define STR_ER_WANT_LATTICE_MATCH (134217728u)
+/* output option: every word track of STR_ER_WANT_TRACK_READ matched against the lexicon over the piece lattices of all its members: the
+ * pooled evidence of the track chooses the entry, and for that entry every member gets its own segmentation and alignment
+ * (str_er_result_lattice_track_matches / _lattice_track_members / _lattice_track_src / _lattice_track_parts; the contract is at
+ * str_er_lattice_track_member).  Needs STR_ER_WANT_TRACK_READ and STR_ER_WANT_LATTICE_MATCH (and through them STR_ER_WANT_RUN_SPLIT,
+ * _WORD_MATCH, _LINE_LINKS and _RUN_READ): STR_ER_EINVAL without either and wherever they are refused (the strip path, the per-plane
+ * calls), and a lexicon: STR_ER_ESTATE without one (the matcher's rule); the context is usable afterwards.  It changes no other output
+ * of the call -- str_er_result_track_matches still reads the split sequence -- and combines with every other STR_ER_WANT_* flag.     */
+#define STR_ER_WANT_LATTICE_TRACK (268435456u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -565,7 +573,9 @@ typedef struct str_er_word_match {
  *     A track of one usable member has the six fields of that word's str_er_word_match; a track of unusable members tries nothing.
  *   Limits: across calls and stream submissions nothing is remembered -- str_er_word_links, str_er_word_tracks_from_links and
  *     str_er_match_tracks are what a caller needs to pool over submissions himself.  There is no pooled open-vocabulary decode
- *     (a median string over members with different run counts is another problem).                                               */
+ *     (a median string over members with different run counts is another problem).  The members enter with the rows the matcher
+ *     read; the track match in which every member's segmentation is free is a separate output, str_er_lattice_track_member
+ *     (STR_ER_WANT_LATTICE_TRACK).                                                                                                */
 typedef struct str_er_word_link {
     int32_t  a, b;           /*  0: a word of frame f and a word of the adjacent frame f + 1            */
     uint32_t inter;          /*  8: the area of the intersection of their boxes, > 0                    */
@@ -754,8 +764,8 @@ typedef struct str_er_lattice_decode {
  *     the parts are the runs; (2) cost <= the str_er_word_match cost on the unsplit runs, wherever that matcher tried anything;
  *     (3) cost <= the str_er_word_match cost on the split sequence of str_er_run_split + SPLIT * (n_parts of that sequence - n_runs):
  *     both are paths of the lattice, and their bands lie inside this one.
- *   Limits: one path per word, for the best entry only; the track match (str_er_track_match) still reads the matcher's rows: pooling
- *     lattices over a word track is not part of this; no bigram table enters.                                                          */
+ *   Limits: one path per word, for the best entry only; per word and per frame: pooling lattices over a word track is not part of this
+ *     output but a separate one, str_er_lattice_track_member (STR_ER_WANT_LATTICE_TRACK); no bigram table enters.                     */
 typedef struct str_er_lattice_match {
     int32_t  entry, cost;                 /*  0,  4                                   */
     int32_t  second_entry, second_cost;   /*  8, 12                                   */
@@ -763,6 +773,42 @@ typedef struct str_er_lattice_match {
     int32_t  first_part, n_parts;         /* 24, 28: into the lattice match part table */
     int32_t  n_del, n_ins;                /* 32, 36                                   */
 } str_er_lattice_match;      /* 40 bytes; one per word                                */
+
+/* The lexicon match of a word track over the piece lattices of its members (STR_ER_WANT_LATTICE_TRACK, str_er_lattice_match_tracks): one
+ * entry per track, chosen by the sum over the members of each member's cheapest segmentation for that entry, and for that entry every
+ * member's own parts and alignment.  A definition of this library; integers only, exact, and the host states the same rules
+ * (str_er_lattice_match_tracks_host).
+ *   Members: a word track with the members w_1 .. w_n is given as for str_er_match_tracks.  Member i has R_i runs; its lattice is that
+ *     of str_er_lattice_decode, with N_i nodes; the rows, the fold, INS, DEL, the band and SPLIT are exactly those of
+ *     str_er_lattice_match.  A member is usable iff N_i <= 32.
+ *   Cost: for an entry e of the length l, L_i(e) is D_i[N_i][l] of the recurrence of str_er_lattice_match, whatever l is, and cost(e)
+ *     is the sum of L_i(e) over the usable members.  Equivalently every usable member adds the minimum over its segmentations P of the
+ *     str_er_word_match cost of e on the rows of P's parts plus SPLIT * (|P| - R_i).
+ *   Tried: e is tried iff max(1, R_i - band) <= l <= min(32, N_i + band) for at least one usable member: a union of the bands of
+ *     str_er_lattice_match, which may have gaps.  A member with N_i = 0 behaves as str_er_lattice_match says for N = 0.
+ *   Record per track, a str_er_track_match: (cost, entry) and (second_cost, second_entry) are the two smallest (cost, index) over the
+ *     tried entries, -1 where nothing qualifies; free_cost is the sum of the str_er_word_split costs of all members, the unusable ones
+ *     included; n_tried the number of entries tried; n_used the number of usable members; best_member the word with the smallest member
+ *     cost, ties to the earliest slot, -1 where there is none.  A track has at most 65536 members (STR_ER_ECAPACITY above): L_i is at
+ *     most the cost of the unsplit path, at most 64 * 255, so the sum stays inside int32.
+ *   Record per slot of the member array, a str_er_lattice_track_member: for the winning entry of the slot's track, cost = L_i, and
+ *     the parts, n_del and n_ins of member i's own backtrack from (N_i, l) with the first-candidate rule of str_er_lattice_match
+ *     (SUB(i) and DEL(i) for i ascending, then INS); word is the member.  For an unusable member or where entry is -1, cost = -1 and
+ *     the counts are 0; in a slot of no track word is -1 as well.  The parts are str_er_split_part records in a table of their own,
+ *     back to back in slot order; every slot has 32 source bytes with the meaning and the 0xFF padding of str_er_lattice_match.
+ *   It follows: (1) a track of one usable member has the first six fields of that word's str_er_lattice_match, and that word's parts,
+ *     sources, n_del and n_ins; (2) if no member has a cut, the record and every member cost equal str_er_track_match's on the runs'
+ *     rows field for field, and every member's parts are its runs; (3) where every member has N_i <= 32, cost <= the
+ *     str_er_track_match cost on the unsplit runs wherever that one tried anything: per entry every term is smaller or equal, and the
+ *     entries tried are a superset.
+ *   Limits: only the winning entry gets segmentations; nothing is remembered across calls or stream submissions; no bigram table
+ *     enters.                                                                                                                           */
+typedef struct str_er_lattice_track_member {
+    int32_t  cost;                        /*  0: L_i of the track's entry, -1 without  */
+    int32_t  first_part, n_parts;         /*  4,  8: into the lattice track part table */
+    int32_t  n_del, n_ins;                /* 12, 16                                   */
+    int32_t  word;                        /* 20: the member (a word index), -1 in a slot of no track */
+} str_er_lattice_track_member; /* 24 bytes; one per slot of the member array          */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -1227,6 +1273,28 @@ int str_er_lattice_match_words_host(const str_er_run_split *splits, int32_t n_ru
  * made).  The pointer may be NULL.                                                                                                  */
 int str_er_lattice_match_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
 
+/* The track match over the members' piece lattices (str_er_lattice_track_member) on the caller's rows, on the GPU, with the context's
+ * lexicon, INS / DEL / band and SPLIT: the arguments up to n_words are those of str_er_lattice_match_words, the tracks those of
+ * str_er_match_tracks, each with its validation.  out receives n_tracks records, members_out n_members records, src 32 bytes per slot
+ * of the member array, parts the members' parts back to back in slot order and *n_parts their number.  cap_parts too small ->
+ * STR_ER_ECAPACITY, *n_parts still set (it is at most the sum over the slots of the member's N).  STR_ER_ESTATE without a lexicon;
+ * STR_ER_ECAPACITY on a track of more than 65536 members.  It needs no model.                                                        */
+int str_er_lattice_match_tracks(str_er_ctx *ctx, const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs,
+                                int32_t n_pieces, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, const int32_t *track_first,
+                                const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks, str_er_track_match *out,
+                                str_er_lattice_track_member *members_out, uint8_t *src, str_er_split_part *parts, int32_t cap_parts, int32_t *n_parts);
+/* The same rules on one host thread, with the lexicon, INS / DEL / band and SPLIT as arguments (as for
+ * str_er_lattice_match_words_host).  Pure: no context, no GPU.                                                                       */
+int str_er_lattice_match_tracks_host(const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs, int32_t n_pieces,
+                                     const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, const int32_t *track_first,
+                                     const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks, const char *bytes,
+                                     const int32_t *offsets, int32_t n, uint32_t flags, int32_t ins, int32_t del, int32_t band, int32_t split_cost,
+                                     str_er_track_match *out, str_er_lattice_track_member *members_out, uint8_t *src, str_er_split_part *parts,
+                                     int32_t cap_parts, int32_t *n_parts);
+/* Statistics of the buffer of STR_ER_WANT_LATTICE_TRACK / str_er_lattice_match_tracks: the bytes of its tables on the device (0: never
+ * made).  The pointer may be NULL.                                                                                                  */
+int str_er_lattice_track_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
+
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:
  * str_er_stream_context.                                                                                                          */
@@ -1498,6 +1566,13 @@ const int32_t            *str_er_result_word_track_members(const str_er_result *
 const int32_t            *str_er_result_word_track_of_words(const str_er_result *r, int32_t *n);
 const str_er_track_match *str_er_result_track_matches(const str_er_result *r, int32_t *n);
 const int32_t            *str_er_result_track_member_costs(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_LATTICE_TRACK (str_er_lattice_track_member): one match per word track of str_er_result_word_tracks(), one record and
+ * 32 source bytes per slot of str_er_result_word_track_members(), and the members' parts back to back in slot order.  Each returns NULL
+ * and 0 without the flag; a call without words returns empty arrays (not NULL).                                                      */
+const str_er_track_match          *str_er_result_lattice_track_matches(const str_er_result *r, int32_t *n);
+const str_er_lattice_track_member *str_er_result_lattice_track_members(const str_er_result *r, int32_t *n);
+const uint8_t                     *str_er_result_lattice_track_src(const str_er_result *r, uint64_t *n_bytes);
+const str_er_split_part           *str_er_result_lattice_track_parts(const str_er_result *r, int32_t *n);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

@@ -94,6 +94,14 @@ WANT_LATTICE_DECODE = 67108864
 # pieces of all its runs, the winner's parts and sources (needs WANT_RUN_SPLIT and WANT_WORD_MATCH; Result.lattice_matches /
 # lattice_match_src / lattice_match_parts / word_lattice_match_text; the contract is at str_er_lattice_match)
 WANT_LATTICE_MATCH = 134217728
+# every word track of WANT_TRACK_READ against the lexicon over the piece lattices of all its members: the pooled evidence chooses the entry,
+# and for it every member gets its own parts and sources (needs WANT_TRACK_READ and WANT_LATTICE_MATCH; Result.lattice_track_matches /
+# lattice_track_members / lattice_track_src / lattice_track_parts / word_track_lattice_text; the contract is at str_er_lattice_track_member)
+WANT_LATTICE_TRACK = 268435456
+# str_er_lattice_track_member: per slot of the member array, the member's own cost for its track's entry (-1: none), its parts in the
+# lattice track part table, the parts dropped and the characters inserted, and the member (a word index; -1 in a slot of no track)
+LATTICE_TRACK_MEMBER_DTYPE = np.dtype([("cost", "<i4"), ("first_part", "<i4"), ("n_parts", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4"), ("word", "<i4")])
+assert LATTICE_TRACK_MEMBER_DTYPE.itemsize == 24
 # str_er_word_link: a word a of frame f and a word b of the adjacent frame f + 1 whose boxes share inter > 0 pixels; link: linked at the call's threshold
 WORD_LINK_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("inter", "<u4"), ("link", "<u4")])
 # str_er_word_track: members = word_track_members[first:first + count] (word indices, ascending), rep the one with the most pixels
@@ -434,6 +442,13 @@ def load_library():
         fn = getattr(L, "str_er_result_" + name)
         fn.argtypes, fn.restype = [vp, cnt], vp
     L.str_er_lattice_match_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    for name, cnt in (("lattice_track_matches", i32p), ("lattice_track_members", i32p), ("lattice_track_src", C.POINTER(C.c_uint64)), ("lattice_track_parts", i32p)):
+        fn = getattr(L, "str_er_result_" + name)
+        fn.argtypes, fn.restype = [vp, cnt], vp
+    L.str_er_lattice_track_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_lattice_match_tracks.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, i32p]
+    L.str_er_lattice_match_tracks_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_uint32,
+                                                   C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, i32p]
     L.str_er_lattice_match_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, i32p]
     L.str_er_lattice_match_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_int32, vp, vp, vp, C.c_int32, i32p]
@@ -600,6 +615,8 @@ class Result:
         self._lattice_decodes = None  # with WANT_LATTICE_DECODE: the tables behind lattice_decodes / lattice_decode_chars / lattice_decode_src / lattice_parts
         self._word_links = None    # with WANT_TRACK_READ: the tables behind word_links / word_tracks / word_track_members / word_track_of_words / track_matches / track_member_costs
         self._word_tracks = self._word_track_members = self._word_track_of_words = self._track_matches = self._track_member_costs = None
+        self._lattice_track_matches = None  # with WANT_LATTICE_TRACK: the tables behind lattice_track_matches / lattice_track_members / lattice_track_src / lattice_track_parts
+        self._lattice_track_members = self._lattice_track_src = self._lattice_track_parts = None
         self._run_pieces = None
         self._piece_reads = None
         self._piece_costs = None
@@ -948,6 +965,53 @@ class Result:
         ws = range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))
         return " ".join(self.word_track_text(int(of[w])) if of[w] >= 0 else self.word_text(w) for w in ws)
 
+    def _lattice_track_table(self, table):
+        if table is None:
+            raise ValueError("the result has no lattice track matches (pass WANT_LATTICE_TRACK / want_lattice_track=True)")
+        return table
+
+    @property
+    def lattice_track_matches(self) -> np.ndarray:
+        """With WANT_LATTICE_TRACK: TRACK_MATCH_DTYPE per word track, over the members' piece lattices."""
+        return self._lattice_track_table(getattr(self, "_lattice_track_matches", None))
+
+    @property
+    def lattice_track_members(self) -> np.ndarray:
+        """With WANT_LATTICE_TRACK: LATTICE_TRACK_MEMBER_DTYPE per slot of word_track_members."""
+        return self._lattice_track_table(getattr(self, "_lattice_track_members", None))
+
+    @property
+    def lattice_track_src(self) -> np.ndarray:
+        """With WANT_LATTICE_TRACK: (slots of word_track_members, 32) uint8, per character of the track's entry the member's part it was
+        read from, or 0x80 | the parts before the place it was inserted at; 0xFF behind the entry's end."""
+        return self._lattice_track_table(getattr(self, "_lattice_track_src", None))
+
+    @property
+    def lattice_track_parts(self) -> np.ndarray:
+        """With WANT_LATTICE_TRACK: SPLIT_PART_DTYPE, the members' parts back to back in slot order (piece: an index of run_pieces, or
+        -1 for a whole run)."""
+        return self._lattice_track_table(getattr(self, "_lattice_track_parts", None))
+
+    def word_track_lattice_text(self, g: int) -> str:
+        """With WANT_LATTICE_TRACK: the lexicon entry word track g takes over its members' piece lattices, as it was given to
+        set_lexicon; the representative's own reading (word_text) where the track has no entry."""
+        e = int(self.lattice_track_matches[g]["entry"])
+        return self._lexicon[e] if 0 <= e < len(self._lexicon) else self.word_text(int(self.word_tracks[g]["rep"]))
+
+    def text_track_lattice_match_text(self, k: int) -> str:
+        """With WANT_LATTICE_TRACK: the words of the representative line of text track k in order, each as its word track's
+        word_track_lattice_text (its own word_text where the line is no reading line), joined by one blank."""
+        lw = self.line_words[int(self.text_tracks[k]["rep"])]
+        of = self.word_track_of_words
+        ws = range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))
+        return " ".join(self.word_track_lattice_text(int(of[w])) if of[w] >= 0 else self.word_text(w) for w in ws)
+
+    def track_member_lattice_parts(self, slot: int) -> np.ndarray:
+        """With WANT_LATTICE_TRACK: the parts of the member in `slot` of word_track_members for its track's entry (SPLIT_PART_DTYPE;
+        none for an unusable member and without an entry)."""
+        d = self.lattice_track_members[slot]
+        return self.lattice_track_parts[int(d["first_part"]):int(d["first_part"]) + int(d["n_parts"])]
+
     def _line_geom_table(self, table):
         if table is None:
             raise ValueError("the result has no line geometry (pass WANT_LINE_GEOM / want_line_geom=True)")
@@ -1286,6 +1350,11 @@ class ERFilter:
                             res._word_track_of_words = table(L.str_er_result_word_track_of_words, np.int32)
                             res._track_matches = table(L.str_er_result_track_matches, TRACK_MATCH_DTYPE)
                             res._track_member_costs = table(L.str_er_result_track_member_costs, np.int32)
+                            res._lattice_track_matches = table(L.str_er_result_lattice_track_matches, TRACK_MATCH_DTYPE)
+                            if res._lattice_track_matches is not None:
+                                res._lattice_track_members = table(L.str_er_result_lattice_track_members, LATTICE_TRACK_MEMBER_DTYPE)
+                                res._lattice_track_src = table(L.str_er_result_lattice_track_src, np.uint8, n64).reshape(-1, 32)
+                                res._lattice_track_parts = table(L.str_er_result_lattice_track_parts, SPLIT_PART_DTYPE)
             res.masks = table(L.str_er_result_masks, MASK_DTYPE)
             if res.masks is not None:
                 res.mask_bits = table(L.str_er_result_mask_bits, np.uint32, n64)
@@ -1351,7 +1420,7 @@ class ERFilter:
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
                     want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -1364,7 +1433,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode, lattice_match=want_lattice_match), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode, lattice_match=want_lattice_match, lattice_track=want_lattice_track), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -1486,7 +1555,7 @@ class ERFilter:
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
                          want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -1494,7 +1563,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode, lattice_match=want_lattice_match))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode, lattice_match=want_lattice_match, lattice_track=want_lattice_track))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1906,6 +1975,21 @@ class ERFilter:
         a = _lattice_args(splits, run_costs, piece_costs, first_run, n_runs_of_word)
         self._check(self.L.str_er_lattice_decode_words(self.h, *a[0], *a[1]))
         return _lattice_out(a)
+
+    def lattice_track_stats(self) -> int:
+        """str_er_lattice_track_stats: the bytes of the lattice track tables on the device; 0: never made."""
+        a = C.c_uint64()
+        self._check(self.L.str_er_lattice_track_stats(self.h, C.byref(a)))
+        return int(a.value)
+
+    def lattice_match_tracks(self, splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members):
+        """str_er_lattice_match_tracks: the track match over the members' piece lattices (str_er_lattice_track_member) of the tracks
+        members[track_first[g]:track_first[g] + track_count[g]] of the words [first_run[w], first_run[w] + n_runs_of_word[w]) of the runs
+        (splits: RUN_SPLIT_DTYPE, run_costs (n runs, 65), piece_costs (n pieces, 65)) against the lexicon; returns (TRACK_MATCH_DTYPE
+        per track, LATTICE_TRACK_MEMBER_DTYPE per slot of members, (slots, 32) uint8 sources, SPLIT_PART_DTYPE parts)."""
+        a = _lattice_track_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members)
+        self._check(self.L.str_er_lattice_match_tracks(self.h, *a[0], *a[1]))
+        return _lattice_track_out(a)
 
     def lattice_match_stats(self) -> int:
         """str_er_lattice_match_stats: the bytes of the lattice match tables on the device; 0: never made."""
@@ -2358,6 +2442,47 @@ def lattice_match_words_host(splits, run_costs, piece_costs, first_run, n_runs_o
     return _lattice_match_out(a)
 
 
+def _lattice_track_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members):
+    sp = np.ascontiguousarray(splits, dtype=RUN_SPLIT_DTYPE).reshape(-1)
+    rc = np.ascontiguousarray(run_costs, dtype=np.uint8).reshape(-1, 65)
+    pc = np.ascontiguousarray(piece_costs, dtype=np.uint8).reshape(-1, 65)
+    fr = np.ascontiguousarray(first_run, dtype=np.int32).reshape(-1)
+    no = np.ascontiguousarray(n_runs_of_word, dtype=np.int32).reshape(-1)
+    tf = np.ascontiguousarray(track_first, dtype=np.int32).reshape(-1)
+    tc = np.ascontiguousarray(track_count, dtype=np.int32).reshape(-1)
+    mem = np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+    if len(sp) != len(rc) or len(fr) != len(no) or len(tf) != len(tc):
+        raise ValueError("splits and run_costs need one row per run, first_run and n_runs_of_word one entry per word, track_first and track_count one per track")
+    cap = int(min(32 * len(mem), 2 ** 31 - 1))          # (a usable member has at most 32 parts)
+    out = np.zeros(max(1, len(tf)), TRACK_MATCH_DTYPE)
+    mrec = np.zeros(max(1, len(mem)), LATTICE_TRACK_MEMBER_DTYPE)
+    sr = np.full((max(1, len(mem)), 32), 0xFF, np.uint8)
+    parts = np.zeros(max(1, cap), SPLIT_PART_DTYPE)
+    n = C.c_int32()
+    p = lambda a: _np_ptr(a) if len(a) else None
+    return ((p(sp), len(sp), p(rc), p(pc), len(pc), p(fr), p(no), len(fr), p(tf), p(tc), p(mem), len(mem), len(tf)),
+            (_np_ptr(out), _np_ptr(mrec), _np_ptr(sr), _np_ptr(parts), cap, C.byref(n)), (sp, rc, pc, fr, no, tf, tc, mem), out, mrec, sr, parts, n)
+
+
+def _lattice_track_out(a):
+    nt, nm = len(a[2][5]), len(a[2][7])
+    return a[3][:nt], a[4][:nm], a[5][:nm], a[6][:a[7].value].copy()
+
+
+def lattice_match_tracks_host(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members, words, fold_case: bool = True,
+                              ins: int = 64, dele: int = 64, band: int = 2, split_cost: int = 8):
+    """str_er_lattice_match_tracks_host (pure host, one thread): ERFilter.lattice_match_tracks with the lexicon and the parameters as arguments."""
+    a = _lattice_track_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members)
+    words = list(words)
+    raw, off = _lexicon_bytes(words)
+    buf = np.frombuffer(raw, np.uint8) if raw else np.zeros(1, np.uint8)
+    rc = load_library().str_er_lattice_match_tracks_host(*a[0], _np_ptr(buf), _np_ptr(off), len(words), LEXICON_FOLD_CASE if fold_case else 0, int(ins), int(dele),
+                                                         int(band), int(split_cost), *a[1])
+    if rc != 0:
+        raise StrErError(rc, "str_er_lattice_match_tracks_host")
+    return _lattice_track_out(a)
+
+
 def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: int = 0, dele: int = 0):
     """str_er_decode_words_host (pure host, one thread): ERFilter.decode_words with the table and the parameters as arguments."""
     cs, fr, no, out, ch, sr = _decode_args(costs, first_run, n_runs_of_word)
@@ -2369,10 +2494,10 @@ def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: 
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False, track_read=False, lattice_decode=False, lattice_match=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False, track_read=False, lattice_decode=False, lattice_match=False, lattice_track=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (track_read, WANT_TRACK_READ), (lattice_decode, WANT_LATTICE_DECODE), (lattice_match, WANT_LATTICE_MATCH), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (track_read, WANT_TRACK_READ), (lattice_decode, WANT_LATTICE_DECODE), (lattice_match, WANT_LATTICE_MATCH), (lattice_track, WANT_LATTICE_TRACK), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -2836,23 +2961,23 @@ class FrameStream:
         return slot.value, arr
 
     def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit(self.h, slot, w, h, 3 * w, 3 * w * h, n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
         """The staging buffer holds n_frames tightly packed NV12 frames (w * h * 3 / 2 bytes each)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_nv12(self.h, slot, w, h, w, w * (h + h // 2), n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         if a.ndim == 3:
             a = a[None]
@@ -2870,21 +2995,21 @@ class FrameStream:
         return int(t.value)
 
     def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
         """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
         return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
 
     def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
         """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
         return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
 
     def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
         """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         arr = (ImageRef * max(1, len(refs)))(*refs)

@@ -701,8 +701,8 @@ int fill_geometry(str_er_ctx *c, str_er_result *r, const GeomPass &GP)
 // the runs and words of the lines (what k_foot_words left), and with read the reading of every run: T.lines is the table k_foot_words
 // read, and its footprints are still in c->foot_bits
 // track: the word links and word tracks of STR_ER_WANT_TRACK_READ on the host before the reading (the text tracks of r are made: fill_links),
-// the track match behind the matcher (frame_of: the frame of every line, frame_wh: the level-0 sizes of the frames)
-int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode, bool split, bool lattice, bool lmatch, bool track,
+// the track match behind the matcher, with ltrack the one over the members' piece lattices behind the lattice match (frame_of: the frame of every line, frame_wh: the level-0 sizes of the frames)
+int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode, bool split, bool lattice, bool lmatch, bool ltrack, bool track,
                const std::vector<uint32_t> &frame_of, const std::vector<int32_t> &frame_wh)
 {
     const auto   t2 = std::chrono::steady_clock::now();
@@ -747,12 +747,17 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
                 std::fprintf(stderr, "[str_er] track read: %zu words, %zu word links, %zu word tracks, %zu members, host %.3f ms\n", r->words.size(), r->word_links.size(),
                              r->word_tracks.size(), r->word_track_members.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t3).count());
         }
+        if (ltrack && track && lmatch && split && match) {
+            out.lattice_track_matches = &r->lattice_track_matches; out.lattice_track_members = &r->lattice_track_members;
+            out.lattice_track_src = &r->lattice_track_src; out.lattice_track_parts = &r->lattice_track_parts;
+        }
         if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features, split ? &rp : nullptr, &out); rcr != STR_ER_OK)
             return rcr;
         r->have_track_read = track;
         r->have_run_splits = split;
         r->have_lattice_decodes = lattice && split;
         r->have_lattice_matches = lmatch && split && match;
+        r->have_lattice_track = ltrack && track && lmatch && split && match;
         r->have_run_reads = true;
         r->have_word_matches = match;
         r->have_word_decodes = decode;
@@ -795,7 +800,7 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
     if ((rc = fill_frame_lines(c, r, frame_of, pyr_of, S.feet.pairs, n_fl)) != STR_ER_OK) return rc;
     if (want.links && (rc = fill_links(c, b, r, frame_of, T, S.links)) != STR_ER_OK) return rc;
     if (want.geom && (rc = fill_geometry(c, r, S.geom)) != STR_ER_OK) return rc;
-    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split, want.lattice, want.lmatch, want.track, frame_of, b.frame_wh)) != STR_ER_OK) return rc;
+    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split, want.lattice, want.lmatch, want.ltrack, want.track, frame_of, b.frame_wh)) != STR_ER_OK) return rc;
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
                              "%zu bytes back, host %.3f ms before + %.3f ms after the device\n",

@@ -17,13 +17,14 @@
 //   decoder          U's part rows (A's where U is A) with (slot, n_parts) if split, else U with (first, n_of)
 //   lattice decode   U's rows (runs first, pieces from row n_run on) with (first, n_of, slot) and the split records
 //   lattice match    A's rows (runs first, pieces from row n_run on) with (first, n_of, slot) and the split records; iff match && split
+//   lattice track    the same rows and records as the lattice match, with the track match's tracks; iff the lattice match and the track match run
 //
 //   result table     source
 //   run_costs        A if match, else U
 //   piece_costs      A if match, else U
 //   run_probs        present iff match or decode
 //
-// The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, rs_tab, ld_tab, lm_tab and
+// The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, rs_tab, ld_tab, lm_tab, lt_tab and
 // tm_tab hold what their kernels leave.
 #include "str_er_ctx.h"
 #include "lattice_decode_kernels.h"
@@ -48,6 +49,11 @@ void ReadChainOut::preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k
     if (p.lmatch) {
         lattice_matches->assign(n_words, str_er_lattice_match{-1, -1, -1, -1, 0, 0, 0, 0, 0, 0}); lattice_match_src->assign(32 * n_words, 0xFF);
         lattice_match_parts->clear();
+    }
+    if (p.ltrack) {
+        lattice_track_matches->assign(tracks->size(), str_er_track_match{-1, -1, -1, -1, 0, 0, 0, -1});
+        lattice_track_members->assign(track_members->size(), str_er_lattice_track_member{-1, 0, 0, 0, 0, -1}); lattice_track_src->assign(32 * track_members->size(), 0xFF);
+        lattice_track_parts->clear();
     }
 }
 
@@ -82,14 +88,14 @@ struct ReadCall {
     const SvmDev       *m;                           // null: the features only
     const size_t        n_run, n_pc, n, n_rows, n_words;      // n tiles: the runs' and behind them the pieces'; n_rows cost rows a set
     // on the host: the geometry, the tracks and with split the part slot of every word
-    std::vector<RunTile> tiles; std::vector<RotGeom> rot; std::vector<int32_t> boxes, slot, tfirst, tcount;
+    std::vector<RunTile> tiles; std::vector<RotGeom> rot; std::vector<int32_t> boxes, slot, tfirst, tcount, pslot;
     RunAtlas             A{}; size_t atlas_bytes = 0;
-    uint64_t             n_slots = 0;
+    uint64_t             n_slots = 0, n_pslots = 0;
     // the buffers (device, H: page-locked): the tables, the scorer's scratch, the row sets and their part rows in c->read_rows, what the consumers' kernels leave
     RunTab   TH{}, TD{};
     OcrBuf   buf{};
     uint8_t *rows[2] = {nullptr, nullptr}, *parts[2] = {nullptr, nullptr};
-    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; WmTab WD{}; WdTab DD{}; TmTab KD{};
+    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; TmTab KD{};
 
     // phase 1 (host alone): the tiles and rotations of the runs and pieces, every box checked, and their places in the atlas
     int geometry(const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words, const std::vector<str_er_line_run> &runs, const double *slopes,
@@ -232,6 +238,12 @@ struct ReadCall {
         if (p.lmatch && n_words > 0)          // the matcher's rows of the runs and, behind them, the pieces: folded when they are staged
             launch_lattice_match(s, c->lex, c->wm_prm, c->rs_split, TD.splits, rows[p.lattice_match_set], rows[p.lattice_match_set] + 65 * n_run, TD.first, TD.n_of, TD.slot,
                                  (int)n_words, MD.partial, reinterpret_cast<int32_t *>(MD.matches), MD.src, reinterpret_cast<int32_t *>(MD.parts));
+        if (p.ltrack && !tfirst.empty())          // the same rows and records, and the tracks the track match took
+            if (const int rc = lattice_track_enqueue(c, s, 0, TD.splits, rows[p.lattice_track_set], rows[p.lattice_track_set] + 65 * n_run, TD.first, TD.n_of, o.splits->data(),
+                                                     TH.first, TH.n_of, n_words, tfirst.data(), tcount.data(), o.track_members->data(), o.track_members->size(),
+                                                     tfirst.size(), pslot, &n_pslots, GH, GD);
+                rc != STR_ER_OK)
+                return rc;
         make_set(SET_U, false);
         if (p.decode) {
             const Window W = window(p.decode_set);
@@ -272,6 +284,7 @@ struct ReadCall {
         if (p.split && n_words > 0) HIP_TRY(c, down(c->rs_tab.h() + SH.o_out, c->rs_tab.d() + SH.o_out, SH.down_tables));          // (into page-locked memory: compacted below)
         if (p.lattice && n_words > 0) HIP_TRY(c, down(c->ld_tab.h() + LH.o_dec, c->ld_tab.d() + LH.o_dec, LH.down_bytes));
         if (p.lmatch && n_words > 0) HIP_TRY(c, down(c->lm_tab.h() + MH.o_matches, c->lm_tab.d() + MH.o_matches, MH.down_bytes));
+        if (p.ltrack && !tfirst.empty()) HIP_TRY(c, down(c->lt_tab.h() + GH.o_matches, c->lt_tab.d() + GH.o_matches, GH.down_bytes));
         HIP_TRY(c, wait_stream(c, s));
         if (p.lmatch && n_words > 0) {          // the records with their first parts, the parts compacted, the sources as they are
             uint64_t total = 0;
@@ -279,6 +292,14 @@ struct ReadCall {
             o.lattice_match_parts->assign((size_t)total, str_er_split_part{0, 0});
             lm_compact(MH, slot, n_slots, o.lattice_matches->data(), o.lattice_match_parts->data(), &total);
             std::memcpy(o.lattice_match_src->data(), MH.src, 32 * n_words);
+        }
+        if (p.ltrack && !tfirst.empty()) {          // the member records with their first parts, the parts compacted, the records and sources as they are
+            uint64_t total = 0;
+            if (!lt_compact(GH, pslot, n_pslots, nullptr, nullptr, &total)) return fail(c, STR_ER_EHIP, "lattice track: a member's parts outside its slots (internal error)");
+            o.lattice_track_parts->assign((size_t)total, str_er_split_part{0, 0});
+            lt_compact(GH, pslot, n_pslots, o.lattice_track_members->data(), o.lattice_track_parts->data(), &total);
+            std::memcpy(o.lattice_track_matches->data(), GH.matches, sizeof(str_er_track_match) * tfirst.size());
+            std::memcpy(o.lattice_track_src->data(), GH.src, 32 * o.track_members->size());
         }
         if (p.lattice && n_words > 0) {          // the records with their first parts, the parts compacted, the strings as they are
             uint64_t total = 0;
@@ -314,7 +335,7 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     const ReadChainOut       &o = chain && reads ? *chain : none;
     const size_t              n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0;
     const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.tracks != nullptr, c->lex.fold != 0,
-                                   o.lattice_matches != nullptr);
+                                   o.lattice_matches != nullptr, o.lattice_track_matches != nullptr);
     if (reads) reads->assign(n_run, str_er_run_read{});
     q.assign(1800 * n_run, 0);
     if (pieces) {

@@ -52,19 +52,7 @@ int track_match_enqueue(str_er_ctx *c, hipStream_t s, const uint8_t *d_rows, con
 
 namespace {
 
-// STR_ER_OK, or why not: the tracks ascend in the member array without overlap, the members are words
-int tracks_check(const int32_t *track_first, const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks, int32_t n_words)
-{
-    int64_t at = 0;
-    for (int32_t g = 0; g < n_tracks; ++g) {
-        if (track_count[g] < 0 || track_first[g] < at || (int64_t)track_first[g] + track_count[g] > n_members) return STR_ER_EINVAL;
-        if (track_count[g] > tr::MAX_MEMBERS) return STR_ER_ECAPACITY;
-        at = (int64_t)track_first[g] + track_count[g];
-    }
-    for (int32_t i = 0; i < n_members; ++i)
-        if (members[i] < 0 || members[i] >= n_words) return STR_ER_EINVAL;
-    return STR_ER_OK;
-}
+using tr::tracks_check;
 
 bool track_args_ok(const uint8_t *costs, int32_t n_rows, const int32_t *first_run, const int32_t *n_of, int32_t n_words, const int32_t *track_first,
                    const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks, const str_er_track_match *out,

@@ -22,88 +22,13 @@
 #include <hip/hip_runtime.h>
 
 #include "lattice_match_kernels.h"
-#include "word_match_device.h"
+#include "lattice_match_device.h"
 
 namespace str_er {
 
 namespace {
 
 constexpr int LM_THREADS = 256, LM_WAVES = LM_THREADS / 64;
-constexpr int LM_MAX_NODES = 32, LM_MAX_RUNS = 33;      // (33 runs: enough to see that N > 32)
-constexpr int LM_SLOTS = 4 * LM_MAX_NODES;                                  // row slots in LDS: (node, span)
-constexpr int LM_PIECE = 0x40000000;                                       // a slot's row: the run's row, or with this bit the piece's; -1: none
-constexpr int LM_TROW = 33;                                                 // ints of a row of the final table
-
-// the piece (i, j) of a run of A atoms in the order by (i, j) without (0, A); -1: the run itself
-__device__ __forceinline__ int lm_piece_index(int A, int i, int j)
-{
-    if (i == 0) return j == A ? -1 : j - 1;
-    return (A - 1) + (i - 1) * A - (i - 1) * i / 2 + (j - i - 1);
-}
-
-__device__ __forceinline__ int lm_atoms(const str_er_run_split *splits, int r) { return min(max(splits[r].n_cuts, 0), 3) + 1; }
-
-// one edge into the node n (static) from D_ nodes back: the old value there (SUB) and the new one (DEL), with the edge's penalty
-#define LM_EDGE(D_, OLD_, PEN_, DELPEN_)                                                          \
-    {                                                                                             \
-        const int c = ct[((n - 1) * 4 + (D_ - 1)) * WM_ALPHABET + a];                              \
-        best = min(best, min(OLD_ + c + PEN_, col[n - D_] + DELPEN_));                            \
-    }
-
-// The edit distance of the lane's entry of `len` labels over the lattice of N <= MC nodes: jl - 1 of the node n in the bits 2 (n - 1) of
-// S0 (n <= 16) or 2 (n - 17) of S1 (uniform), d0[n] = D[n][0].  Rows past N are computed and not used.  A node with jl = 1 takes the
-// matcher's cell after one uniform branch; the edge that begins its run (d = jl) has no penalty, the shorter ones pay SPLIT.
-template <int MC>
-__device__ __forceinline__ int lm_entry_cost(const uint8_t *ct, uint32_t S0, uint32_t S1, const int *d0, const uint32_t *__restrict__ words, int len, int N, int ins,
-                                             int del, int split)
-{
-    int       col[MC + 1];
-    const int dsp = del + split;
-#pragma unroll
-    for (int n = 0; n <= MC; ++n) col[n] = d0[n];
-    for (int q = 0; q * 4 < len; ++q) {
-        const uint32_t w = words[q * WM_GROUP];
-        for (int jj = 0; jj < 4 && q * 4 + jj < len; ++jj) {
-            const int a = (int)(w >> (8 * jj) & 0xFFu);
-            int o1 = col[0], o2 = 0, o3 = 0, o4 = 0;          // the old values of the nodes n - 1 .. n - 4
-            col[0] = (q * 4 + jj + 1) * ins;
-            // (the structure words are made opaque per character step: what is derived from them is then worked out on the scalar unit
-            // where it is used, not kept in a hundred scalar registers across the loop and spilled)
-            uint32_t s0 = S0, s1 = S1;
-            asm volatile("" : "+s"(s0), "+s"(s1));
-#pragma unroll
-            for (int n = 1; n <= MC; ++n) {
-                const uint32_t fld = (n <= 16 ? s0 : s1) >> (2 * ((n - 1) & 15)) & 3u;          // jl - 1
-                const int      old = col[n];
-                int            best = old + ins;
-                if (fld == 0) LM_EDGE(1, o1, 0, del)
-                else {
-                    LM_EDGE(1, o1, split, dsp)
-                    if (n >= 2) {
-                        if (fld == 1) LM_EDGE(2, o2, 0, del)
-                        else {
-                            LM_EDGE(2, o2, split, dsp)
-                            if (n >= 3) {
-                                if (fld == 2) LM_EDGE(3, o3, 0, del)
-                                else {
-                                    LM_EDGE(3, o3, split, dsp)
-                                    if (n >= 4) LM_EDGE(4, o4, 0, del)
-                                }
-                            }
-                        }
-                    }
-                }
-                col[n] = best;
-                o4 = o3; o3 = o2; o2 = o1; o1 = old;
-            }
-        }
-    }
-    int res = col[0];
-#pragma unroll
-    for (int n = 1; n <= MC; ++n) res = n == N ? col[n] : res;
-    return res;
-}
-#undef LM_EDGE
 
 // The groups [g0, g1) of one chunk against the word staged in ct / node_s / d0: a wave takes every LM_WAVES-th group, a lane one entry.
 // A word without a cut is a sequence of rows: its rows are staged back to back and the matcher's own cell loop runs on them.
@@ -220,27 +145,6 @@ __global__ void __launch_bounds__(LM_THREADS) k_lattice_match(WmLexDev lex, WmPa
 }
 
 // ---- k_lattice_match_final --------------------------------------------------------------------------------------------------------
-// what one lane writes another lane of the same wave reads: the wave runs in lockstep and its LDS operations complete in order
-__device__ __forceinline__ void lm_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ int lm_wave_min(int v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = min(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
-// the minimum of a cost row, on every lane
-__device__ __forceinline__ int lm_row_min(const uint8_t *row, int lane)
-{
-    return lm_wave_min(min((int)row[lane], (int)row[64]));
-}
-
 // a wave per word
 __global__ void __launch_bounds__(64 * LM_FINAL_WORDS) k_lattice_match_final(WmLexDev lex, WmParams prm, int split, const str_er_run_split *__restrict__ splits,
                                                                              const uint8_t *__restrict__ run_costs, const uint8_t *__restrict__ piece_costs,
@@ -249,13 +153,7 @@ __global__ void __launch_bounds__(64 * LM_FINAL_WORDS) k_lattice_match_final(WmL
                                                                              const uint64_t *__restrict__ partial, int32_t *__restrict__ matches,
                                                                              uint8_t *__restrict__ src, int32_t *__restrict__ parts)
 {
-    __shared__ int32_t T[LM_FINAL_WORDS][(LM_MAX_NODES + 1) * LM_TROW];
-    __shared__ uint8_t cc[LM_FINAL_WORDS][LM_MAX_NODES + 1][4][LM_TROW + 3];          // the byte SUB(i) into node n reads for the character j
-    __shared__ int32_t node_run[LM_FINAL_WORDS][LM_MAX_NODES + 1], node_fp[LM_FINAL_WORDS][LM_MAX_NODES + 1];
-    __shared__ uint8_t node_ja[LM_FINAL_WORDS][LM_MAX_NODES + 1];                     // the node's local index j | its run's atoms << 4
-    __shared__ int32_t part_run[LM_FINAL_WORDS][LM_MAX_NODES], part_piece[LM_FINAL_WORDS][LM_MAX_NODES];
-    __shared__ uint8_t from[LM_FINAL_WORDS][32];
-    __shared__ int32_t rec[LM_FINAL_WORDS][4];                                        // n_parts, n_del, n_ins
+    __shared__ LmWaveLds lds[LM_FINAL_WORDS];
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int w = (int)blockIdx.x * LM_FINAL_WORDS + wave;
     if (w >= n_words) return;          // (no workgroup barrier below: a wave is on its own)
@@ -276,111 +174,15 @@ __global__ void __launch_bounds__(64 * LM_FINAL_WORDS) k_lattice_match_final(WmL
         b1 = lo;
     }
     // the runs one after the other: the free segmentation of each on the minima of its rows, and the nodes while they are at most 32
-    int32_t fc = 0;
-    int     N = 0;
-    for (int t = 0; t < m; ++t) {
-        const int      r = first + t, A = __builtin_amdgcn_readfirstlane(lm_atoms(splits, r)), fp = __builtin_amdgcn_readfirstlane(splits[r].first_piece);
-        const uint8_t *rrow = run_costs + (size_t)r * WM_ALPHABET;
-        int            D[5];
-        D[0] = 0;
-#pragma unroll
-        for (int j = 1; j <= 4; ++j) {
-            D[j] = 0;
-            if (j <= A) {
-                int best = 0x7FFFFFFF;
-#pragma unroll
-                for (int i = 0; i < j; ++i) {
-                    const int k = lm_piece_index(A, i, j);
-                    const int v = D[i] + lm_row_min(k < 0 ? rrow : piece_costs + ((size_t)fp + (size_t)k) * WM_ALPHABET, lane) + (i > 0 ? split : 0);
-                    best = min(best, v);
-                }
-                D[j] = best;
-                if (lane == 0 && N + j <= LM_MAX_NODES) { node_run[wave][N + j] = r; node_fp[wave][N + j] = fp; node_ja[wave][N + j] = (uint8_t)(j | A << 4); }
-            }
-        }
-        int da = D[1];
-#pragma unroll
-        for (int j = 2; j <= 4; ++j) da = j == A ? D[j] : da;
-        fc += da;
-        N = min(N + A, LM_MAX_NODES + 1);
-    }
+    LmWaveLds    &L = lds[wave];
+    int           N = 0;
+    const int32_t fc = lm_wave_nodes(L, splits, run_costs, piece_costs, first, m, split, lane, N);
     const int  len_lo = max(1, m - prm.band), len_hi = min(32, N + prm.band);
     const bool tried = N <= LM_MAX_NODES && len_lo <= len_hi;
     const int  entry = b1 == WM_NO_KEY ? -1 : (int)(uint32_t)b1;
-    int        len = 0;
-    if (lane == 0) { rec[wave][0] = rec[wave][1] = rec[wave][2] = 0; }
-    if (lane < 32) from[wave][lane] = 0xFF;
-    if (entry >= 0 && tried) {          // (uniform) the table of the winner, a column a lane, and the backtrack
-        const int pos = __builtin_amdgcn_readfirstlane(lex.pos[entry]), g = pos >> 6, el = pos & 63;
-        len = 1;
-        while (len < 32 && g >= lex.len_first[len + 1]) ++len;
-        const int j = min(lane, 32);
-        int       a = 0;          // the character j of the entry (1 .. len)
-        if (j >= 1 && j <= len) a = (int)(lex.chars[lex.goff[g] + (size_t)((j - 1) >> 2) * WM_GROUP + el] >> (8 * ((j - 1) & 3)) & 0xFFu);
-        const int ap = lex.fold ? wm_partner(a) : a;
-        int32_t  *Tw = T[wave];
-        if (lane <= 32) Tw[j] = j * prm.ins;
-        lm_wave_sync();
-        for (int n = 1; n <= N; ++n) {
-            const int      r = node_run[wave][n], fp = node_fp[wave][n], jl = node_ja[wave][n] & 15, A = node_ja[wave][n] >> 4;
-            const uint8_t *rrow = run_costs + (size_t)r * WM_ALPHABET;
-            int            X = 0x3FFFFFFF;
-            for (int i = 0; i < jl; ++i) {
-                const int      f = n - jl + i, k = lm_piece_index(A, i, jl), s = i > 0 ? split : 0;
-                const uint8_t *row = k < 0 ? rrow : piece_costs + ((size_t)fp + (size_t)k) * WM_ALPHABET;
-                const int      c = min((int)row[a], (int)row[ap]);
-                if (lane <= 32) cc[wave][n][i][j] = (uint8_t)c;
-                if (j >= 1) X = min(X, Tw[f * LM_TROW + j - 1] + c + s);
-                X = min(X, Tw[f * LM_TROW + j] + prm.del + s);
-            }
-            int v = X - j * prm.ins;          // the INS chain: a prefix minimum over the lanes
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const int o = __shfl_up(v, off, 64);
-                if (lane >= off) v = min(v, o);
-            }
-            if (lane <= 32) Tw[n * LM_TROW + j] = v + j * prm.ins;
-            lm_wave_sync();
-        }
-        if (lane == 0) {          // the first candidate, in the contract's order, that attains the cell
-            int n = N, jj = len, np = 0, nd = 0, ni = 0;
-            while (n > 0 || jj > 0) {          // (every step lowers n or jj; a part is taken only while n > 0, so np stays below N <= 32)
-                const int d = Tw[n * LM_TROW + jj];
-                int       mv = -1, jl = 0;
-                if (n > 0) {
-                    jl = node_ja[wave][n] & 15;
-                    for (int i = 0; i < jl && mv < 0; ++i) {
-                        const int f = n - jl + i, s = i > 0 ? split : 0;
-                        if (jj >= 1 && Tw[f * LM_TROW + jj - 1] + (int)cc[wave][n][i][jj] + s == d) mv = 2 * i;
-                        else if (Tw[f * LM_TROW + jj] + prm.del + s == d) mv = 2 * i + 1;
-                    }
-                }
-                if (mv < 0) {          // INS: the character jj is inserted at the node n
-                    if (jj <= 0) break;
-                    from[wave][jj - 1] = (uint8_t)(np | 0x80);
-                    ++ni; --jj;
-                    continue;
-                }
-                const int i = mv >> 1, A = node_ja[wave][n] >> 4, k = lm_piece_index(A, i, jl);
-                part_run[wave][np] = node_run[wave][n]; part_piece[wave][np] = k < 0 ? -1 : node_fp[wave][n] + k;
-                if (mv & 1) ++nd;
-                else { from[wave][jj - 1] = (uint8_t)np; --jj; }
-                ++np;
-                n -= jl - i;
-            }
-            rec[wave][0] = np; rec[wave][1] = nd; rec[wave][2] = ni;
-        }
-    }
+    const int  len = lm_wave_winner(L, lex, prm, split, run_costs, piece_costs, entry, N, entry >= 0 && tried, lane);
     lm_wave_sync();
-    const int np = rec[wave][0];
-    if (lane < 32) {          // a read character: its part in word order; an inserted one: the parts that end at or before its node
-        const int fb = from[wave][lane];
-        src[(size_t)w * 32 + lane] = lane < len ? (fb & 0x80 ? (uint8_t)(0x80 | (np - (fb & 0x7F))) : (uint8_t)(np - 1 - fb)) : (uint8_t)0xFF;
-    }
-    if (lane < np) {          // (n_parts <= N <= 32, the slots of the word)
-        parts[2 * (base + (size_t)lane)] = part_run[wave][np - 1 - lane];
-        parts[2 * (base + (size_t)lane) + 1] = part_piece[wave][np - 1 - lane];
-    }
+    lm_wave_store(L, len, lane, src + (size_t)w * 32, parts + 2 * base);
     if (lane == 0) {
         int32_t *o = matches + (size_t)w * 10;
         o[0] = entry;
@@ -389,7 +191,7 @@ __global__ void __launch_bounds__(64 * LM_FINAL_WORDS) k_lattice_match_final(WmL
         o[3] = b2 == WM_NO_KEY ? -1 : (int32_t)(b2 >> 32);
         o[4] = fc;
         o[5] = tried ? lex.len_count[len_hi + 1] - lex.len_count[len_lo] : 0;
-        o[6] = 0; o[7] = np; o[8] = rec[wave][1]; o[9] = rec[wave][2];
+        o[6] = 0; o[7] = L.rec[0]; o[8] = L.rec[1]; o[9] = L.rec[2];
     }
 }
 

@@ -14,22 +14,25 @@ enum { SET_A = 0, SET_U = 1, SET_NONE = -1 };
 struct ReadPlan {
     bool match, decode, split, lattice, track;        // the flags as they count: track only with match, lattice only with split
     bool lmatch;           // ... and the lattice match only with split and match
+    bool ltrack;           // ... and the lattice track match only with the lattice match and the track match
     bool rows[2];          // a k_run_costs launch into the set ([SET_U]: only where U is a set of its own)
     bool fold_a;           // A's launch folds
     bool parts[2];         // a k_split_words launch on the set, into its part rows
     int  match_set, decode_set, lattice_set;        // the set each consumer reads (SET_NONE: it does not run); the track match reads the matcher's
     int  lattice_match_set;                         // ... and the lattice match: A, the matcher's rows (folded when they are read where A is not)
+    int  lattice_track_set;                         // ... and the lattice track match: A as well, the runs' rows with the pieces behind them
     int  result_set;       // the set run_costs and piece_costs come from (SET_NONE: the call returns no rows)
     int  split_down;       // the set of the last k_split_words (SET_NONE: none)
     bool run_probs;
     bool any() const { return match || decode || split; }      // some consumer reads the words and the class probabilities
 };
 
-inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, bool track, bool fold, bool lmatch = false)
+inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, bool track, bool fold, bool lmatch = false, bool ltrack = false)
 {
     ReadPlan p{};
     p.match = match; p.decode = decode; p.split = split; p.lattice = lattice && split; p.track = track && match;
     p.lmatch = lmatch && split && match;
+    p.ltrack = ltrack && p.lmatch && p.track;
     const bool need_u = p.decode || p.lattice || (p.split && !p.match), u_is_a = p.match && !fold;
     const int  u = !need_u ? SET_NONE : u_is_a ? SET_A : SET_U;
     p.rows[SET_A] = p.match; p.rows[SET_U] = u == SET_U;
@@ -39,6 +42,7 @@ inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, boo
     p.decode_set = p.decode ? u : SET_NONE;
     p.lattice_set = p.lattice ? u : SET_NONE;
     p.lattice_match_set = p.lmatch ? SET_A : SET_NONE;
+    p.lattice_track_set = p.ltrack ? SET_A : SET_NONE;
     p.result_set = p.match ? SET_A : u;
     p.split_down = p.parts[SET_U] ? SET_U : p.parts[SET_A] ? SET_A : SET_NONE;
     p.run_probs = p.match || p.decode;

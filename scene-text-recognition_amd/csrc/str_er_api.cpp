@@ -1363,6 +1363,7 @@ static int frame_lines_result(const BatchRun &R, str_er_result *r, const uint32_
     want.split = (R.stages & STR_ER_WANT_RUN_SPLIT) != 0;       // (... and every run cut and segmented: the cuts in the stage, the rest behind the reading)
     want.lattice = (R.stages & STR_ER_WANT_LATTICE_DECODE) != 0;      // (... and every word over its piece lattice under the bigram table, behind the reading)
     want.lmatch = (R.stages & STR_ER_WANT_LATTICE_MATCH) != 0;  // (... and every word against the lexicon over its piece lattice, behind k_split_words)
+    want.ltrack = (R.stages & STR_ER_WANT_LATTICE_TRACK) != 0; // (... and every word track against the lexicon over its members' piece lattices, behind the lattice match)
     want.track = (R.stages & STR_ER_WANT_TRACK_READ) != 0;      // (... and the words linked across frames, every word track against the lexicon behind the matcher)
     if (d_mask_bits) {
         made_word_off.resize(r->masks.size());

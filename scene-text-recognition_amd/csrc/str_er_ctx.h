@@ -183,6 +183,11 @@ struct str_er_result {
     std::vector<str_er_track_match> track_matches;
     std::vector<int32_t> track_member_costs;
     bool have_track_read = false;
+    std::vector<str_er_track_match> lattice_track_matches;          // STR_ER_WANT_LATTICE_TRACK: one match per word track, one record and 32 source bytes per slot of
+    std::vector<str_er_lattice_track_member> lattice_track_members; // the member array, and the members' parts
+    std::vector<uint8_t> lattice_track_src;
+    std::vector<str_er_split_part> lattice_track_parts;
+    bool have_lattice_track = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -327,6 +332,8 @@ struct str_er_ctx {
     PairBuf  ld_tab;                  // (str_er_lattice_decode_words: splits | rows of the runs and pieces | first run, run count, slot per word) | records | labels | sources | parts
     // STR_ER_WANT_LATTICE_MATCH / str_er_lattice_match_words
     PairBuf  lm_tab;                  // (str_er_lattice_match_words: splits | rows of the runs and pieces | first run, run count, slot per word) | chunk keys | records | sources | parts
+    // STR_ER_WANT_LATTICE_TRACK / str_er_lattice_match_tracks
+    PairBuf  lt_tab;                  // (str_er_lattice_match_tracks: splits | rows of the runs and pieces | first run, run count per word) | tracks, members and their slots | words' structure | chunk keys | records | member records | sources | parts | free costs
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels
@@ -615,6 +622,7 @@ struct LineStageWants {
     bool track = false;       // STR_ER_WANT_TRACK_READ: the word links and word tracks on the host before the reading, k_track_match behind the matcher
     bool lattice = false;     // STR_ER_WANT_LATTICE_DECODE: every word over its piece lattice under the bigram table (k_lattice_decode behind the scorer, on what k_split_words reads)
     bool lmatch = false;      // STR_ER_WANT_LATTICE_MATCH: every word against the lexicon over its piece lattice (k_lattice_match behind k_split_words on the matcher's rows)
+    bool ltrack = false;      // STR_ER_WANT_LATTICE_TRACK: every word track against the lexicon over its members' piece lattices (k_lattice_track_match behind k_lattice_match)
     bool split = false;       // STR_ER_WANT_RUN_SPLIT: the cuts of every run (k_run_cuts behind k_foot_words, down with the stage's wait), the pieces read with the runs, k_split_words behind the scorer
 };
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
@@ -673,6 +681,9 @@ struct ReadChainOut {
     // STR_ER_WANT_LATTICE_MATCH (with split and match): the words against the context's lexicon over their piece lattices
     std::vector<str_er_lattice_match> *lattice_matches = nullptr; std::vector<uint8_t> *lattice_match_src = nullptr;
     std::vector<str_er_split_part> *lattice_match_parts = nullptr;
+    // STR_ER_WANT_LATTICE_TRACK (with the lattice match and the track match): the word tracks over their members' piece lattices
+    std::vector<str_er_track_match> *lattice_track_matches = nullptr; std::vector<str_er_lattice_track_member> *lattice_track_members = nullptr;
+    std::vector<uint8_t> *lattice_track_src = nullptr; std::vector<str_er_split_part> *lattice_track_parts = nullptr;
     void preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k) const;      // every table of the plan as a call without runs leaves it (k: the model's classes)
 };
 // carving a table buffer: take(bytes) is the offset of the next piece, and the one after it starts at the next multiple of 256
@@ -680,7 +691,7 @@ struct Carve {
     size_t off = 0;
     size_t take(size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; }
 };
-// what a caller-rows entry point (str_er_match_words, _decode_words, _split_words, _lattice_decode_words, _lattice_match_words, _match_tracks) puts up at the
+// what a caller-rows entry point (str_er_match_words, _decode_words, _split_words, _lattice_decode_words, _lattice_match_words, _match_tracks, _lattice_match_tracks) puts up at the
 // front of its table buffer (base: either side of the pair, or null for the size alone): n_splits split records, n_rows cost rows, the
 // words' first run and run count, and with slots their part slot.  The detect calls keep their rows elsewhere (str_er_ctx::read_rows).
 struct RowsIn {
@@ -734,6 +745,27 @@ LmTab lm_layout(uint8_t *base, size_t at, size_t n_words, size_t n_slots, int n_
 // after the wait: the records with first_part set and the compacted parts from the host side of the layout (null: not copied); false
 // where a word's parts lie outside its slots
 bool lm_compact(const LmTab &H, const std::vector<int32_t> &slot, uint64_t n_slots, str_er_lattice_match *matches, str_er_split_part *parts, uint64_t *n_parts);
+// ---- defined in api_lattice_track.cpp
+// the layout of c->lt_tab from byte `at` on (the inputs' bytes) for n_tracks tracks over a member array of n_members with n_pslots part
+// slots: what goes up (the tracks, the members, the track and the part slot of every member slot), the structure of the n_words words
+// and the chunk keys, and what comes down: the records, the member records, the sources and the parts; the free costs stay on the device
+struct LtTab {
+    int32_t *first, *count, *members, *slot_track, *pslot, *tab; uint64_t *partial; str_er_track_match *matches; str_er_lattice_track_member *mrec;
+    uint8_t *src; str_er_split_part *parts; int32_t *mfree;
+    size_t o_up, up_bytes;                    // first | count | members | slot_track | pslot lie back to back: one copy up
+    size_t o_matches, down_bytes, bytes;      // matches | mrec | src | parts lie back to back (each aligned): one copy down
+};
+LtTab lt_layout(uint8_t *base, size_t at, size_t n_words, size_t n_tracks, size_t n_members, size_t n_pslots, int n_chunks);
+// The track tables into c->lt_tab (from byte `at` on) and up on s, the kernels behind what is on s.  d_*: on the device; splits,
+// first_run, n_of: the same on the host, checked by the caller as the tracks are.  pslot receives the part slot of every member slot
+// and *n_pslots their sum; H and D the two sides of the layout (what comes down: H.o_matches, H.down_bytes)
+int lattice_track_enqueue(str_er_ctx *c, hipStream_t s, size_t at, const str_er_run_split *d_splits, const uint8_t *d_run_costs, const uint8_t *d_piece_costs,
+                          const int32_t *d_first, const int32_t *d_n_of, const str_er_run_split *splits, const int32_t *first_run, const int32_t *n_of, size_t n_words,
+                          const int32_t *track_first, const int32_t *track_count, const int32_t *members, size_t n_members, size_t n_tracks, std::vector<int32_t> &pslot,
+                          uint64_t *n_pslots, LtTab &H, LtTab &D);
+// after the wait: the member records with first_part set and the compacted parts from the host side of the layout (null: not copied);
+// false where a slot's parts lie outside its part slots
+bool lt_compact(const LtTab &H, const std::vector<int32_t> &pslot, uint64_t n_pslots, str_er_lattice_track_member *mrec, str_er_split_part *parts, uint64_t *n_parts);
 // ---- defined in api_track_read.cpp
 // the layout of c->tm_tab for n_tracks tracks over a member array of n_members (base: either side of the pair, or null for the size alone)
 struct TmTab {

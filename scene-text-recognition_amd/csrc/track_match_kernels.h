@@ -5,6 +5,10 @@
 
 namespace str_er {
 
+// groups of a (track, chunk) workgroup: a quarter of the matcher's chunk.  A workgroup stays for all members of its track, and there
+// are far fewer tracks than words: with the matcher's 64 groups the 125 tracks of profiles/track_read.md gave 1.2 rounds of
+// workgroups on the device and the second round ran nearly empty.  (lattice_track_kernels.hip cuts the lexicon in the same way)
+constexpr int TM_CHUNK_GROUPS = 16;
 // chunks of a track: they cover the whole lexicon, since the lengths a track tries are a union of bands
 int tm_chunks(const WmLexDev &lex);
 // costs [rows x 65], first_run / n_of [words] as for launch_word_match; track g has the members members[track_first[g] ..

@@ -16,10 +16,6 @@ namespace {
 
 constexpr int TM_THREADS = 256, TM_WAVES = TM_THREADS / 64;
 constexpr int TM_SLOT = 32 * WM_ALPHABET;                  // bytes of the staged member: up to 32 rows
-// groups of a (track, chunk) workgroup: a quarter of the matcher's chunk.  A workgroup stays for all members of its track, and there
-// are far fewer tracks than words: with the matcher's 64 groups the 125 tracks of profiles/track_read.md gave 1.2 rounds of
-// workgroups on the device and the second round ran nearly empty.
-constexpr int TM_CHUNK_GROUPS = 16;
 constexpr int TM_WAVE_GROUPS = TM_CHUNK_GROUPS / TM_WAVES; // groups of a chunk that one wave takes
 
 // bit l - 1 set iff |l - m| <= band for a length l in 1 .. 32 and m <= 32 (track_read_rules.h: len_mask_of)

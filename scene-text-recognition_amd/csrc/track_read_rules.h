@@ -140,6 +140,20 @@ inline void word_tracks(const uint32_t *frames_of_lines, const int32_t *line_tra
     }
 }
 
+// STR_ER_OK, or why not: the tracks ascend in the member array without overlap, the members are words
+inline int tracks_check(const int32_t *track_first, const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks, int32_t n_words)
+{
+    int64_t at = 0;
+    for (int32_t g = 0; g < n_tracks; ++g) {
+        if (track_count[g] < 0 || track_first[g] < at || (int64_t)track_first[g] + track_count[g] > n_members) return STR_ER_EINVAL;
+        if (track_count[g] > MAX_MEMBERS) return STR_ER_ECAPACITY;
+        at = (int64_t)track_first[g] + track_count[g];
+    }
+    for (int32_t i = 0; i < n_members; ++i)
+        if (members[i] < 0 || members[i] >= n_words) return STR_ER_EINVAL;
+    return STR_ER_OK;
+}
+
 // bit l - 1 set iff an entry of length l (1 .. 32) is tried: |l - m| <= band for a usable member
 inline uint32_t len_mask_of(int m, int band)
 {

@@ -1043,6 +1043,79 @@ public:
         return s;
     }
 
+    // The track match over the members' piece lattices of a detect call made with STR_ER_WANT_LATTICE_TRACK (needs STR_ER_WANT_TRACK_READ and
+    // STR_ER_WANT_LATTICE_MATCH; the contract is at str_er_lattice_track_member in include/str_er.h): one record per word track, one member
+    // record and 32 source bytes per slot of the word tracks' member array, and the members' parts back to back in slot order
+    struct LatticeTrackMatches {
+        std::vector<str_er_track_match>          matches;
+        std::vector<str_er_lattice_track_member> members;
+        std::vector<uint8_t>                     src;
+        std::vector<str_er_split_part>           parts;
+    };
+    static LatticeTrackMatches lattice_track_matches(const str_er_result *r)
+    {
+        LatticeTrackMatches out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_track_match *p = str_er_result_lattice_track_matches(r, &n)) out.matches.assign(p, p + n);
+        if (const str_er_lattice_track_member *p = str_er_result_lattice_track_members(r, &n)) out.members.assign(p, p + n);
+        if (const uint8_t *p = str_er_result_lattice_track_src(r, &nb)) out.src.assign(p, p + nb);
+        if (const str_er_split_part *p = str_er_result_lattice_track_parts(r, &n)) out.parts.assign(p, p + n);
+        return out;
+    }
+    // the same match of the tracks members[track_first[g] .. track_first[g] + track_count[g]) of the words [first_run[w], first_run[w] +
+    // n_runs[w]) on the caller's rows (str_er_lattice_match_tracks): the context's lexicon, INS / DEL / band and SPLIT
+    LatticeTrackMatches lattice_match_tracks(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                                             const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs, const std::vector<int32_t> &track_first,
+                                             const std::vector<int32_t> &track_count, const std::vector<int32_t> &members)
+    {
+        LatticeTrackMatches out = lattice_track_out(splits, run_costs, piece_costs, first_run, n_runs, track_first, track_count, members);
+        int32_t n = 0;
+        check(str_er_lattice_match_tracks(ctx_.get(), splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                          piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65),
+                                          first_run.empty() ? nullptr : first_run.data(), n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(),
+                                          track_first.empty() ? nullptr : track_first.data(), track_count.empty() ? nullptr : track_count.data(),
+                                          members.empty() ? nullptr : members.data(), (int32_t)members.size(), (int32_t)track_first.size(),
+                                          out.matches.empty() ? nullptr : out.matches.data(), out.members.empty() ? nullptr : out.members.data(),
+                                          out.src.empty() ? nullptr : out.src.data(), out.parts.data(), (int32_t)out.parts.size(), &n));
+        out.parts.resize((size_t)n);
+        return out;
+    }
+    // the same rules on one host thread, with the lexicon, INS / DEL / band and SPLIT as arguments (str_er_lattice_match_tracks_host)
+    static LatticeTrackMatches lattice_match_tracks_host(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs,
+                                                         const std::vector<uint8_t> &piece_costs, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs,
+                                                         const std::vector<int32_t> &track_first, const std::vector<int32_t> &track_count,
+                                                         const std::vector<int32_t> &members, const std::vector<std::string> &lexicon, bool fold_case = true,
+                                                         int32_t ins = 64, int32_t del = 64, int32_t band = 2, int32_t split_cost = 8)
+    {
+        std::string          bytes;
+        std::vector<int32_t> offsets{0};
+        for (const std::string &w : lexicon) {
+            bytes += w;
+            if (bytes.size() > (size_t)INT32_MAX) throw std::invalid_argument("lattice_match_tracks_host: too many bytes");
+            offsets.push_back((int32_t)bytes.size());
+        }
+        LatticeTrackMatches out = lattice_track_out(splits, run_costs, piece_costs, first_run, n_runs, track_first, track_count, members);
+        int32_t n = 0;
+        if (str_er_lattice_match_tracks_host(splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                             piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65),
+                                             first_run.empty() ? nullptr : first_run.data(), n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(),
+                                             track_first.empty() ? nullptr : track_first.data(), track_count.empty() ? nullptr : track_count.data(),
+                                             members.empty() ? nullptr : members.data(), (int32_t)members.size(), (int32_t)track_first.size(), bytes.data(),
+                                             offsets.data(), (int32_t)lexicon.size(), fold_case ? STR_ER_LEXICON_FOLD_CASE : 0u, ins, del, band, split_cost,
+                                             out.matches.empty() ? nullptr : out.matches.data(), out.members.empty() ? nullptr : out.members.data(),
+                                             out.src.empty() ? nullptr : out.src.data(), out.parts.data(), (int32_t)out.parts.size(), &n) != STR_ER_OK)
+            throw std::invalid_argument("lattice_match_tracks_host");
+        out.parts.resize((size_t)n);
+        return out;
+    }
+    // the string word track g takes over its members' piece lattices: the lexicon entry (as given in `lexicon`), "" where it has none
+    static std::string word_track_lattice_text(const LatticeTrackMatches &lt, const std::vector<std::string> &lexicon, size_t g)
+    {
+        const int32_t e = lt.matches.at(g).entry;
+        return e >= 0 && (size_t)e < lexicon.size() ? lexicon[(size_t)e] : std::string();
+    }
+
     // The text lines of consecutive frames linked into text tracks (STR_ER_WANT_LINE_LINKS; the contract is at str_er_line_link in
     // include/str_er.h): the overlaps across adjacent frames, the track of every line of str_er_result_texts(), the tracks, the line
     // indices their first / count index, and the footprints of the lines of the first ([0]) and of the last frame ([1]).
@@ -1279,6 +1352,22 @@ private:
         LatticeMatches out;
         out.matches.resize(first_run.size());
         out.src.resize(32 * first_run.size());
+        out.parts.resize(cap);
+        return out;
+    }
+    // the outputs of lattice_match_tracks(_host) sized for the tracks: a usable member has at most 32 parts
+    static LatticeTrackMatches lattice_track_out(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                                                 const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs, const std::vector<int32_t> &track_first,
+                                                 const std::vector<int32_t> &track_count, const std::vector<int32_t> &members)
+    {
+        if (first_run.size() != n_runs.size() || run_costs.size() != 65 * splits.size() || piece_costs.size() % 65 || track_first.size() != track_count.size())
+            throw std::invalid_argument("lattice_match_tracks: 65 bytes a run and a piece, one record a run, one span a word, one span a track");
+        const size_t cap = 1 + 32 * members.size();
+        if (cap > 0x7FFFFFFFull) throw std::invalid_argument("lattice_match_tracks: too many members");
+        LatticeTrackMatches out;
+        out.matches.resize(track_first.size());
+        out.members.resize(members.size());
+        out.src.resize(32 * members.size());
         out.parts.resize(cap);
         return out;
     }
