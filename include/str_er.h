@@ -411,7 +411,8 @@ typedef struct str_er_frame_line {
  *     lines of the call: the transitive closure, so no order of joining is involved.  Its representative is the member with the most
  *     footprint pixels, ties to the smallest line index.  Tracks are ordered by first_frame, then by their smallest member.
  *   Across calls and stream submissions nothing is remembered: a result made with the flag keeps the footprints of the lines of its
- *     first and of its last frame on the host (str_er_result_edge_feet), and str_er_link_feet overlaps two such sets.              */
+ *     first and of its last frame on the host (str_er_result_edge_feet), and str_er_link_feet overlaps two such sets.  The word
+ *     tracks' readings are pooled across calls by a track pool (str_er_pool_match).                                               */
 typedef struct str_er_line_link {
     int32_t  a, b;           /*  0: a line of frame f and a line of the adjacent frame f + 1            */
     uint32_t inter;          /*  8: |F(a) & F(b)|, > 0                                                  */
@@ -571,8 +572,9 @@ typedef struct str_er_word_match {
  *     entry is -1: their sum is cost.  best_member is the word with the smallest member_cost, ties to the earliest slot, or -1.  A
  *     track has at most 65536 members (STR_ER_ECAPACITY above): with at most 64 * 255 a member the sum stays inside int32.
  *     A track of one usable member has the six fields of that word's str_er_word_match; a track of unusable members tries nothing.
- *   Limits: across calls and stream submissions nothing is remembered -- str_er_word_links, str_er_word_tracks_from_links and
- *     str_er_match_tracks are what a caller needs to pool over submissions himself.  There is no pooled open-vocabulary decode
+ *   Limits: across calls and stream submissions a detect call remembers nothing -- str_er_word_links and
+ *     str_er_word_tracks_from_links link words over submissions, and a track pool (str_er_pool_match) keeps the summed costs of a
+ *     track on the device from call to call.  There is no pooled open-vocabulary decode
  *     (a median string over members with different run counts is another problem).  The members enter with the rows the matcher
  *     read; the track match in which every member's segmentation is free is a separate output, str_er_lattice_track_member
  *     (STR_ER_WANT_LATTICE_TRACK).                                                                                                */
@@ -593,6 +595,33 @@ typedef struct str_er_track_match {
     int32_t  free_cost, n_tried;          /* 16, 20                                   */
     int32_t  n_used, best_member;         /* 24, 28                                   */
 } str_er_track_match;        /* 32 bytes; one per word track                          */
+
+/* The track pool: the track match of str_er_track_match pooled across calls (str_er_track_pool_create, _add, _add_lattice, _join,
+ * _clear, _read).  A pool belongs to one context and has cap_tracks slots; a slot is one pooled word track.  At creation (and at
+ * every _reset) the pool is bound to the context's lexicon and its INS / DEL / band, and in lattice mode (STR_ER_POOL_LATTICE) to the
+ * SPLIT of str_er_set_run_split as well: str_er_set_lexicon, str_er_set_word_match and str_er_set_run_split make every pool of the
+ * context stale, and a stale pool answers STR_ER_ESTATE to everything except _reset and _destroy.
+ *   State of a slot, on the device: for every entry of the lexicon the int32 sum, over the usable members added so far, of
+ *     D_i[m_i][l] (in lattice mode L_i of str_er_lattice_track_member), whatever |l - m_i| is -- a member added later may widen the
+ *     lengths tried, and the entries of the new lengths then carry the earlier members' distances already; the 32-bit mask of the
+ *     lengths tried so far; free_cost, n_used and the number of members.
+ *   Defining property: the first seven fields of a slot's record equal the first seven fields of the str_er_track_match that
+ *     str_er_match_tracks_host (in lattice mode str_er_lattice_match_tracks_host) gives, with the pool's lexicon, flags and
+ *     parameters, for one track whose member list is the concatenation, in any order, of everything added to the slot; n_members
+ *     is the length of that list.  Costs are exact integers and a sum does not depend on its order: the record is the same bytes
+ *     whatever the order and the grouping of the additions.  An empty slot reads as a track of no members: -1, -1, -1, -1, 0, 0, 0, 0.
+ *   A slot holds at most 65536 members (STR_ER_ECAPACITY above), the bound under which the int32 sums are safe.
+ *   Limits: member_cost, best_member and the members' segmentations are not pooled -- the winning entry can change with every
+ *     addition, and the members' rows are not kept; str_er_match_tracks / str_er_lattice_match_tracks give them for the members of
+ *     one call.  There is no pooled open-vocabulary decode.  The pool must be destroyed before its context.                        */
+#define STR_ER_POOL_LATTICE 1u
+typedef struct str_er_track_pool str_er_track_pool;
+typedef struct str_er_pool_match {
+    int32_t  entry, cost;                 /*  0,  4                                   */
+    int32_t  second_entry, second_cost;   /*  8, 12                                   */
+    int32_t  free_cost, n_tried;          /* 16, 20                                   */
+    int32_t  n_used, n_members;           /* 24, 28                                   */
+} str_er_pool_match;         /* 32 bytes; one per slot read                           */
 
 /* The decoding of a word under a character bigram table (STR_ER_WANT_WORD_DECODE, str_er_decode_words): the cheapest character string
  * of a word under the cost rows of its glyph runs plus a table of costs of one character after another, which may drop a run (a speck)
@@ -801,8 +830,8 @@ typedef struct str_er_lattice_match {
  *     rows field for field, and every member's parts are its runs; (3) where every member has N_i <= 32, cost <= the
  *     str_er_track_match cost on the unsplit runs wherever that one tried anything: per entry every term is smaller or equal, and the
  *     entries tried are a superset.
- *   Limits: only the winning entry gets segmentations; nothing is remembered across calls or stream submissions; no bigram table
- *     enters.                                                                                                                           */
+ *   Limits: only the winning entry gets segmentations; a call remembers nothing across calls or stream submissions (a track pool in
+ *     lattice mode, str_er_pool_match, pools the summed costs across them); no bigram table enters.                                     */
 typedef struct str_er_lattice_track_member {
     int32_t  cost;                        /*  0: L_i of the track's entry, -1 without  */
     int32_t  first_part, n_parts;         /*  4,  8: into the lattice track part table */
@@ -1294,6 +1323,41 @@ int str_er_lattice_match_tracks_host(const str_er_run_split *splits, int32_t n_r
 /* Statistics of the buffer of STR_ER_WANT_LATTICE_TRACK / str_er_lattice_match_tracks: the bytes of its tables on the device (0: never
  * made).  The pointer may be NULL.                                                                                                  */
 int str_er_lattice_track_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
+
+/* The track pool (str_er_pool_match).  Every entry point returns the library's codes and leaves the pool unchanged on any error; the
+ * error text is the context's (str_er_last_error).  The calls run on the context's stream and wait for it.
+ * _create: a pool of cap_tracks >= 1 empty slots in *pool; flags: 0 (the members' rows, as str_er_match_tracks) or
+ * STR_ER_POOL_LATTICE (the members' piece lattices, as str_er_lattice_match_tracks).  STR_ER_ESTATE without a lexicon;
+ * STR_ER_ECAPACITY where cap_tracks * groups * 256 bytes (groups: the 64-entry groups of the padded device lexicon) pass 2^40,
+ * STR_ER_ENOMEM where the device does not have them.                                                                              */
+int str_er_track_pool_create(str_er_ctx *ctx, int32_t cap_tracks, uint32_t flags, str_er_track_pool **pool);
+void str_er_track_pool_destroy(str_er_track_pool *pool);
+/* Every slot empty, and the pool bound to the context's lexicon and parameters as they are now (the accumulators are allocated again
+ * if the lexicon's size changed).  STR_ER_ESTATE without a lexicon: the pool then stays stale.                                      */
+int str_er_track_pool_reset(str_er_track_pool *pool);
+/* The slots, the flags, the entries of the lexicon the pool is bound to, its bytes on the device, the slots with a member, and
+ * whether it is stale (1 / 0).  Any pointer may be NULL.  This one call works on a stale pool.                                      */
+int str_er_track_pool_info(const str_er_track_pool *pool, int32_t *cap_tracks, uint32_t *flags, int32_t *n_entries, uint64_t *device_bytes,
+                           int32_t *n_in_use, int32_t *stale);
+/* Track g of the call, given as for str_er_match_tracks with that call's checks, is added to the slot slots[g].  STR_ER_EINVAL on a
+ * slot outside 0 .. cap_tracks - 1 or named twice in one call (distinct slots: the kernel owns its rows without atomics);
+ * STR_ER_ECAPACITY where a slot would pass 65536 members; STR_ER_ESTATE on a lattice pool.                                          */
+int str_er_track_pool_add(str_er_track_pool *pool, const uint8_t *costs, int32_t n_rows, const int32_t *first_run, const int32_t *n_runs_of_word,
+                          int32_t n_words, const int32_t *track_first, const int32_t *track_count, const int32_t *members, int32_t n_members,
+                          int32_t n_tracks, const int32_t *slots);
+/* The same for a lattice pool, with the arguments and checks of str_er_lattice_match_tracks.  STR_ER_ESTATE on a rows pool.         */
+int str_er_track_pool_add_lattice(str_er_track_pool *pool, const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs,
+                                  const uint8_t *piece_costs, int32_t n_pieces, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
+                                  const int32_t *track_first, const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks,
+                                  const int32_t *slots);
+/* Slot dst becomes the pooled track of its own and all srcs' members (sums added, masks or-ed, counts and free costs summed); the
+ * srcs become empty.  STR_ER_EINVAL on a slot out of range, a repeated slot or dst among the srcs; STR_ER_ECAPACITY where the
+ * members pass 65536.  n_srcs = 0 is fine.                                                                                          */
+int str_er_track_pool_join(str_er_track_pool *pool, int32_t dst, const int32_t *srcs, int32_t n_srcs);
+/* Those slots become empty (a slot may be named more than once).                                                                    */
+int str_er_track_pool_clear(str_er_track_pool *pool, const int32_t *slots, int32_t n);
+/* out receives n records, out[i] of the slot slots[i]; a slot may be named more than once.                                          */
+int str_er_track_pool_read(str_er_track_pool *pool, const int32_t *slots, int32_t n, str_er_pool_match *out);
 
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:

@@ -110,6 +110,11 @@ WORD_TRACK_DTYPE = np.dtype([("first_frame", "<u4"), ("last_frame", "<u4"), ("fi
 TRACK_MATCH_DTYPE = np.dtype([("entry", "<i4"), ("cost", "<i4"), ("second_entry", "<i4"), ("second_cost", "<i4"), ("free_cost", "<i4"), ("n_tried", "<i4"),
                               ("n_used", "<i4"), ("best_member", "<i4")])
 assert WORD_LINK_DTYPE.itemsize == 16 and WORD_TRACK_DTYPE.itemsize == 24 and TRACK_MATCH_DTYPE.itemsize == 32
+# str_er_pool_match: the first seven fields of str_er_track_match for everything a slot of a track pool was given, and how many members that is
+POOL_MATCH_DTYPE = np.dtype([("entry", "<i4"), ("cost", "<i4"), ("second_entry", "<i4"), ("second_cost", "<i4"), ("free_cost", "<i4"), ("n_tried", "<i4"),
+                             ("n_used", "<i4"), ("n_members", "<i4")])
+POOL_LATTICE = 1
+assert POOL_MATCH_DTYPE.itemsize == 32
 # str_er_word_decode: per word, the cost of the cheapest string (-1: more than 32 runs, not decoded) and of the plain reading, the
 # characters of the string and the runs read, dropped and the characters inserted
 WORD_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
@@ -449,6 +454,15 @@ def load_library():
     L.str_er_lattice_match_tracks.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, i32p]
     L.str_er_lattice_match_tracks_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_uint32,
                                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, i32p]
+    L.str_er_track_pool_create.argtypes = [vp, C.c_int32, C.c_uint32, C.POINTER(vp)]
+    L.str_er_track_pool_destroy.argtypes, L.str_er_track_pool_destroy.restype = [vp], None
+    L.str_er_track_pool_reset.argtypes = [vp]
+    L.str_er_track_pool_info.argtypes = [vp, i32p, C.POINTER(C.c_uint32), i32p, C.POINTER(C.c_uint64), i32p, i32p]
+    L.str_er_track_pool_add.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp]
+    L.str_er_track_pool_add_lattice.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp]
+    L.str_er_track_pool_join.argtypes = [vp, C.c_int32, vp, C.c_int32]
+    L.str_er_track_pool_clear.argtypes = [vp, vp, C.c_int32]
+    L.str_er_track_pool_read.argtypes = [vp, vp, C.c_int32, vp]
     L.str_er_lattice_match_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, i32p]
     L.str_er_lattice_match_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_int32, vp, vp, vp, C.c_int32, i32p]
@@ -2725,6 +2739,225 @@ class TextTracker:
                         self._join(int(pid[k["a"]]), base + int(lt[first.lines[k["b"]]]))
         ids = self.resolve(base + lt.astype(np.int64)) if len(lt) else np.zeros(0, np.int64)
         self._prev = (last, ids[last.lines] if len(last.lines) else np.zeros(0, np.int64))
+        return ids
+
+
+class TrackPool:
+    """str_er_track_pool_*: cap_tracks pooled word tracks on the device of the ERFilter f (str_er_pool_match): per slot the summed
+    costs of everything added to it against every entry of f's lexicon, kept from call to call.  Bound to f's lexicon, set_word_match
+    and (lattice=True) set_run_split as they are at creation: after one of those setters every call raises STR_ER_ESTATE until
+    reset().  Close it before f."""
+
+    def __init__(self, f: "ERFilter", cap_tracks: int, lattice: bool = False):
+        self.f, self.L, self.lattice = f, f.L, bool(lattice)
+        h = C.c_void_p()
+        f._check(self.L.str_er_track_pool_create(f.h, int(cap_tracks), POOL_LATTICE if lattice else 0, C.byref(h)))
+        self.h = h
+        self.cap_tracks = int(cap_tracks)
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            if getattr(self.f, "h", None):          # (the context frees nothing of the pool: without it only the handle is dropped)
+                self.L.str_er_track_pool_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int) -> None:
+        self.f._check(rc)
+
+    @staticmethod
+    def _slots(slots) -> np.ndarray:
+        return np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+
+    def add(self, costs, first_run, n_runs_of_word, track_first, track_count, members, slots) -> None:
+        """str_er_track_pool_add: the tracks, given as for ERFilter.match_tracks, are added to the slots slots[g] (distinct)."""
+        cs, fr, no, tf, tc, mem = _track_args(costs, first_run, n_runs_of_word, track_first, track_count, members)
+        sl = self._slots(slots)
+        if len(sl) != len(tf):
+            raise ValueError("slots: one per track")
+        opt = lambda a: _np_ptr(a) if len(a) else None
+        self._check(self.L.str_er_track_pool_add(self.h, opt(cs), len(cs), opt(fr), opt(no), len(fr), opt(tf), opt(tc), opt(mem), len(mem), len(tf), opt(sl)))
+
+    def add_lattice(self, splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members, slots) -> None:
+        """str_er_track_pool_add_lattice: the same for a lattice pool, the tracks given as for ERFilter.lattice_match_tracks."""
+        a = _lattice_track_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members)
+        sl = self._slots(slots)
+        if len(sl) != a[0][-1]:
+            raise ValueError("slots: one per track")
+        self._check(self.L.str_er_track_pool_add_lattice(self.h, *a[0], _np_ptr(sl) if len(sl) else None))
+
+    def join(self, dst: int, srcs) -> None:
+        """str_er_track_pool_join: slot dst takes the members of the slots srcs, which become empty."""
+        sl = self._slots(srcs)
+        self._check(self.L.str_er_track_pool_join(self.h, int(dst), _np_ptr(sl) if len(sl) else None, len(sl)))
+
+    def clear(self, slots) -> None:
+        """str_er_track_pool_clear: those slots become empty."""
+        sl = self._slots(slots)
+        self._check(self.L.str_er_track_pool_clear(self.h, _np_ptr(sl) if len(sl) else None, len(sl)))
+
+    def read(self, slots) -> np.ndarray:
+        """str_er_track_pool_read: POOL_MATCH_DTYPE per slot named (a slot may be named more than once)."""
+        sl = self._slots(slots)
+        out = np.zeros(max(1, len(sl)), POOL_MATCH_DTYPE)
+        self._check(self.L.str_er_track_pool_read(self.h, _np_ptr(sl) if len(sl) else None, len(sl), _np_ptr(out)))
+        return out[:len(sl)]
+
+    def reset(self) -> None:
+        """str_er_track_pool_reset: every slot empty, the pool bound to f's lexicon and parameters as they are now."""
+        self._check(self.L.str_er_track_pool_reset(self.h))
+
+    def info(self) -> dict:
+        """str_er_track_pool_info: the slots, the mode, the entries of the lexicon it is bound to, its bytes on the device, the
+        slots in use and whether it is stale."""
+        cap, fl, n, by, use, st = C.c_int32(), C.c_uint32(), C.c_int32(), C.c_uint64(), C.c_int32(), C.c_int32()
+        self._check(self.L.str_er_track_pool_info(self.h, C.byref(cap), C.byref(fl), C.byref(n), C.byref(by), C.byref(use), C.byref(st)))
+        return {"cap_tracks": int(cap.value), "lattice": bool(fl.value & POOL_LATTICE), "n_entries": int(n.value), "device_bytes": int(by.value),
+                "in_use": int(use.value), "stale": bool(st.value)}
+
+
+class WordTracker:
+    """Persistent word track ids and pooled readings over successive results: the word-level sibling of TextTracker, which it holds.
+    Feed update() the results of consecutive calls or stream submissions in time order, each made with want_frame_lines,
+    want_line_links, want_line_words, want_run_read, want_word_match and want_track_read (and want_run_split for a lattice pool).
+    Every word track of a result gets a fresh id and a fresh slot of `pool` (a TrackPool on `linker`, whose lexicon and parameters
+    are those of the calls), to which its members are added with the rows the call's own track match read: run_costs, the rows of
+    split_parts where the result has them, or for a lattice pool run_splits / run_costs / piece_costs.  Where the previous result's
+    last frame and this result's first frame have equal sizes, a word u of the one and a word v of the other, both eligible in their
+    own call and on lines whose persistent text ids are the same after TextTracker.update, are linked iff their boxes share pixels and
+    inter * den >= num * (area(u) + area(v) - inter), the rule of str_er_word_link at linker's set_word_link threshold.  Linked ids
+    are joined, the smaller id stays, and their slots are joined.  A pooled track without a member in the result's last frame cannot
+    be extended: its final record goes to `closed` as (id, record) and its slot is freed."""
+
+    def __init__(self, linker: "ERFilter", pool: TrackPool):
+        self.linker, self.pool = linker, pool
+        self.lines = TextTracker(linker)
+        self.closed = []
+        self._parent = []            # union-find over the ids handed out; the root is the smallest
+        self._slot = {}              # root id of a live track -> its slot
+        self._free = list(range(pool.cap_tracks - 1, -1, -1))      # (pop() hands out the smallest)
+        self._final = {}             # id of a closed track -> its record
+        self._prev = None            # (w, h, boxes (n, 4) int64, text ids, word track ids) of the eligible words of the last frame
+
+    def _find(self, i: int) -> int:
+        while self._parent[i] != i:
+            self._parent[i] = self._parent[self._parent[i]]
+            i = self._parent[i]
+        return i
+
+    def reset(self) -> None:
+        """Forget the previous frame (a cut the caller knows of): the live tracks are closed, the ids handed out stay valid."""
+        self._close(list(self._slot))
+        self._prev = None
+        self.lines.reset()
+
+    def resolve(self, ids) -> np.ndarray:
+        return np.array([self._find(int(i)) if int(i) >= 0 else -1 for i in np.asarray(ids).reshape(-1)], np.int64)
+
+    def read(self, ids) -> np.ndarray:
+        """POOL_MATCH_DTYPE per id: the pooled record of a live track, the final record of a closed one."""
+        roots = self.resolve(ids)
+        out = np.zeros(len(roots), POOL_MATCH_DTYPE)
+        live = [k for k, r in enumerate(roots) if int(r) in self._slot]
+        if live:
+            out[live] = self.pool.read([self._slot[int(roots[k])] for k in live])
+        for k, r in enumerate(roots):
+            if int(r) not in self._slot:
+                out[k] = self._final[int(r)]
+        return out
+
+    def text(self, i: int):
+        """The lexicon entry of the track's pooled match, None where it has none."""
+        e = int(self.read([i])[0]["entry"])
+        return self.linker._lexicon[e] if e >= 0 else None
+
+    def _close(self, roots) -> None:
+        roots = sorted(int(r) for r in roots)
+        if not roots:
+            return
+        slots = [self._slot[r] for r in roots]
+        recs = self.pool.read(slots)
+        self.pool.clear(slots)
+        for r, s, rec in zip(roots, slots, recs):
+            self.closed.append((r, rec.copy()))
+            self._final[r] = rec.copy()
+            del self._slot[r]
+            self._free.append(s)
+        self._free.sort(reverse=True)
+
+    def _rows(self, res: "Result"):
+        try:
+            parts = res.split_parts
+        except ValueError:
+            return res.run_costs, res.words["first_run"], res.words["n_runs"]
+        rows = np.zeros((len(parts), 65), np.uint8)
+        whole = parts["piece"] < 0
+        rows[whole] = res.run_costs[parts["run"][whole]]
+        rows[~whole] = res.piece_costs[parts["piece"][~whole]]
+        return rows, res.word_splits["first_part"], res.word_splits["n_parts"]
+
+    def update(self, res: "Result") -> np.ndarray:
+        tow, tracks, members, words = res.word_track_of_words, res.word_tracks, res.word_track_members, res.words
+        nt = len(tracks)
+        if nt > len(self._free):
+            raise StrErError(-7, "WordTracker: the pool has %d free slots, the result %d word tracks" % (len(self._free), nt))
+        first, last = res.edge_feet(0), res.edge_feet(1)
+        slots = self._free[::-1][:nt]          # (the smallest free slots; an addition that is refused leaves the tracker as it was)
+        if nt:
+            if self.pool.lattice:
+                self.pool.add_lattice(res.run_splits, res.run_costs, res.piece_costs, words["first_run"], words["n_runs"], tracks["first"], tracks["count"], members, slots)
+            else:
+                self.pool.add(*self._rows(res), tracks["first"], tracks["count"], members, slots)
+            del self._free[-nt:]
+        tids = self.lines.update(res)
+        base = len(self._parent)
+        self._parent.extend(range(base, base + nt))
+        for g, s in enumerate(slots):
+            self._slot[base + g] = s
+        box = lambda ws: np.stack([words[k][ws].astype(np.int64) for k in ("x", "y", "w", "h")], 1) if len(ws) else np.zeros((0, 4), np.int64)
+        eligible = lambda lines: np.flatnonzero((tow >= 0) & np.isin(words["line"], lines)).astype(np.int64) if len(words) else np.zeros(0, np.int64)
+        # the boundary: the eligible words of the previous last frame against those of this first frame
+        if self._prev is not None and (self._prev[0], self._prev[1]) == (first.width, first.height):
+            num, den = getattr(self.linker, "_word_link", (1, 2))
+            _, _, pbox, ptid, pwid = self._prev
+            vs = eligible(first.lines)
+            vbox = box(vs)
+            for u in range(len(pbox)):
+                tu = int(self.lines.resolve([ptid[u]])[0])
+                for k, v in enumerate(vs):
+                    if int(tids[int(words["line"][v])]) != tu:
+                        continue
+                    (ux, uy, uw, uh), (vx, vy, vw, vh) = (int(a) for a in pbox[u]), (int(a) for a in vbox[k])
+                    iw, ih = min(ux + uw, vx + vw) - max(ux, vx), min(uy + uh, vy + vh) - max(uy, vy)
+                    inter = iw * ih if iw > 0 and ih > 0 else 0
+                    if inter > 0 and inter * den >= num * (uw * uh + vw * vh - inter):
+                        i, j = self._find(int(pwid[u])), self._find(base + int(tow[v]))
+                        if i != j:
+                            self._parent[max(i, j)] = min(i, j)
+        # one join per component of live tracks: the smallest id keeps its slot
+        comp = {}
+        for r in list(self._slot):
+            comp.setdefault(self._find(r), []).append(r)
+        for root, rs in comp.items():
+            if len(rs) > 1:
+                srcs = [self._slot[r] for r in sorted(rs) if r != root]
+                self.pool.join(self._slot[root], srcs)
+                for r in rs:
+                    if r != root:
+                        del self._slot[r]
+                self._free.extend(srcs)
+        self._free.sort(reverse=True)
+        ids = np.array([self._find(base + int(t)) if t >= 0 else -1 for t in tow], np.int64)
+        # what has no member in the last frame cannot be extended
+        ends = eligible(last.lines)
+        open_roots = set(int(ids[w]) for w in ends)
+        self._close([r for r in self._slot if r not in open_roots])
+        self._prev = (last.width, last.height, box(ends), np.array([tids[int(words["line"][w])] for w in ends], np.int64), ids[ends] if len(ends) else np.zeros(0, np.int64))
         return ids
 
 

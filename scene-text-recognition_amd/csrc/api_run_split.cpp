@@ -130,6 +130,7 @@ try {
     if (!c) return STR_ER_EINVAL;
     if (!rs::params_ok(num, den, split_cost)) return fail(c, STR_ER_EINVAL, "str_er_set_run_split: 1 <= num, den <= 65535 and split_cost in 0 .. 255");
     c->rs_num = num; c->rs_den = den; c->rs_split = split_cost;
+    ++c->pool_gen;          // (a track pool is bound to SPLIT: str_er_pool_match)
     return STR_ER_OK;
 } ABI_GUARD(c)
 

@@ -71,6 +71,7 @@ try {
     const char *why = nullptr;
     if (const int rc = wm::lexicon_check(bytes, offsets, n, flags, &why); rc != STR_ER_OK) return fail(c, rc, why);
     HIP_TRY(c, hipStreamSynchronize(c->stream));       // (a call in flight still reads the lexicon that is replaced)
+    ++c->pool_gen;          // (a track pool is bound to the lexicon it was made with: str_er_pool_match)
     if (n == 0) {
         c->lexicon = DevBuf();
         c->lex = WmLexDev{};
@@ -141,6 +142,7 @@ try {
     if (!c) return STR_ER_EINVAL;
     if (!wm::params_ok(ins, del, band)) return fail(c, STR_ER_EINVAL, "word match: INS and DEL are in 1 .. 255 and the band in 0 .. 31");
     c->wm_prm = WmParams{ins, del, band};
+    ++c->pool_gen;          // (a track pool is bound to them: str_er_pool_match)
     return STR_ER_OK;
 } ABI_GUARD(c)
 

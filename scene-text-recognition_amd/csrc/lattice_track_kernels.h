@@ -13,6 +13,8 @@ namespace str_er {
 
 constexpr int LT_TAB_INTS = 3 + 33 + 128;        // int32 of a word's structure in the table: N, S0, S1, d0[33], erow[128]
 
+// k_lattice_track_table alone: tab [n_words x LT_TAB_INTS], the structure of every word (the track pool stages its members through it)
+void launch_lattice_track_table(hipStream_t s, int del, int split, const str_er_run_split *splits, const int32_t *first_run, const int32_t *n_of, int n_words, int32_t *tab);
 // lex, p, split: the matcher's and SPLIT; splits, run_costs, piece_costs, first_run / n_of [n_words]: what k_lattice_match reads.  Track g
 // has the members members[track_first[g] .. track_first[g] + track_count[g]); slot_track [n_members]: the track of every slot of the
 // member array, -1 for a slot of no track; pslot [n_members]: the part slot of every slot, the sum of the N <= 32 of the slots before it

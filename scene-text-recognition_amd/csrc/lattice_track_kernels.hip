@@ -14,8 +14,7 @@
 
 #include <algorithm>
 
-#include "lattice_track_kernels.h"
-#include "lattice_match_device.h"
+#include "lattice_track_device.h"
 
 namespace str_er {
 
@@ -23,18 +22,8 @@ namespace {
 
 constexpr int LT_THREADS = 256, LT_WAVES = LT_THREADS / 64;
 constexpr int LT_WAVE_GROUPS = TM_CHUNK_GROUPS / LT_WAVES;      // groups of a chunk that one wave takes
-constexpr int LT_N = 0, LT_S0 = 1, LT_S1 = 2, LT_D0 = 3, LT_EROW = LT_D0 + LM_MAX_NODES + 1;      // a word's ints in the table
 constexpr int LT_SLOT_WAVES = 4;                                // member slots of a workgroup of k_lattice_track_members: a wave each
 static_assert(LT_EROW + LM_SLOTS == LT_TAB_INTS, "the table's row");
-
-// bit l - 1 set iff max(1, R - band) <= l <= min(32, N + band) and N <= 32 (lattice_track_rules.h: len_mask_of)
-__device__ __forceinline__ uint32_t lt_len_mask(int R, int N, int band)
-{
-    const int lo = max(1, R - band), hi = min(32, N + band);
-    if (N > LM_MAX_NODES || lo > hi) return 0u;
-    const int n = hi - lo + 1;
-    return (n >= 32 ? ~0u : (1u << n) - 1u) << (lo - 1);
-}
 
 __device__ __forceinline__ uint32_t lt_wave_or(uint32_t v)
 {
@@ -311,12 +300,17 @@ __global__ void __launch_bounds__(64) k_lattice_track_best(const int32_t *__rest
 
 } // namespace
 
+void launch_lattice_track_table(hipStream_t s, int del, int split, const str_er_run_split *splits, const int32_t *first_run, const int32_t *n_of, int n_words, int32_t *tab)
+{
+    if (n_words > 0) hipLaunchKernelGGL(k_lattice_track_table, dim3((unsigned)((n_words + 63) / 64)), dim3(64), 0, s, del, split, splits, first_run, n_of, n_words, tab);
+}
+
 void launch_lattice_track(hipStream_t s, const WmLexDev &lex, const WmParams &p, int split, const str_er_run_split *splits, const uint8_t *run_costs,
                           const uint8_t *piece_costs, const int32_t *first_run, const int32_t *n_of, int n_words, const int32_t *track_first, const int32_t *track_count,
                           const int32_t *members, const int32_t *slot_track, const int32_t *pslot, int n_members, int n_tracks, int32_t *tab, uint64_t *partial,
                           int32_t *matches, int32_t *mrec, uint8_t *src, int32_t *parts, int32_t *mfree)
 {
-    if (n_words > 0) hipLaunchKernelGGL(k_lattice_track_table, dim3((unsigned)((n_words + 63) / 64)), dim3(64), 0, s, p.del, split, splits, first_run, n_of, n_words, tab);
+    launch_lattice_track_table(s, p.del, split, splits, first_run, n_of, n_words, tab);
     const int n_chunks = tm_chunks(lex);
     // (the tracks are the grid's y: at most 65535 a launch)
     for (int t0 = 0; t0 < n_tracks; t0 += 65535) {

@@ -334,6 +334,8 @@ struct str_er_ctx {
     PairBuf  lm_tab;                  // (str_er_lattice_match_words: splits | rows of the runs and pieces | first run, run count, slot per word) | chunk keys | records | sources | parts
     // STR_ER_WANT_LATTICE_TRACK / str_er_lattice_match_tracks
     PairBuf  lt_tab;                  // (str_er_lattice_match_tracks: splits | rows of the runs and pieces | first run, run count per word) | tracks, members and their slots | words' structure | chunk keys | records | member records | sources | parts | free costs
+    // str_er_track_pool_*: what a track pool is bound to (the lexicon, INS / DEL / band, SPLIT) has this generation; their setters bump it
+    uint64_t pool_gen = 0;
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
     uint16_t *d_nb_plane = nullptr; std::vector<uint16_t> h_nb_plane; uint32_t n_node_blocks = 0;      // plane of every workgroup of the per-record kernels

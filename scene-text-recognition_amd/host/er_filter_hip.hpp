@@ -1208,6 +1208,74 @@ public:
         bool     have_prev_ = false;
     };
 
+    // The track pool (str_er_track_pool_*; the contract is at str_er_pool_match in include/str_er.h): cap_tracks pooled word tracks
+    // on the device, per slot the summed costs of everything added to it against every entry of the filter's lexicon, kept from call
+    // to call.  Bound to the lexicon, INS / DEL / band and (lattice) SPLIT of the filter as they are at creation: after one of their
+    // setters every call throws (STR_ER_ESTATE) until reset().  The pool keeps its context alive.
+    class TrackPool {
+    public:
+        TrackPool(const ERFilter &f, int32_t cap_tracks, bool lattice = false) : ctx_(f.ctx_)
+        {
+            str_er_track_pool *p = nullptr;
+            check(str_er_track_pool_create(ctx_.get(), cap_tracks, lattice ? STR_ER_POOL_LATTICE : 0u, &p));
+            pool_.reset(p, str_er_track_pool_destroy);
+        }
+        // the tracks, given as for match_tracks, are added to the slots slots[g] (distinct)
+        void add(const std::vector<uint8_t> &costs, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs, const std::vector<int32_t> &track_first,
+                 const std::vector<int32_t> &track_count, const std::vector<int32_t> &members, const std::vector<int32_t> &slots)
+        {
+            if (costs.size() % 65 || first_run.size() != n_runs.size() || track_first.size() != track_count.size() || slots.size() != track_first.size())
+                throw std::invalid_argument("TrackPool::add: 65 bytes a run, one span a word, one span and one slot a track");
+            check(str_er_track_pool_add(pool_.get(), ptr(costs), (int32_t)(costs.size() / 65), ptr(first_run), ptr(n_runs), (int32_t)first_run.size(), ptr(track_first),
+                                        ptr(track_count), ptr(members), (int32_t)members.size(), (int32_t)track_first.size(), ptr(slots)));
+        }
+        // ... for a lattice pool, the tracks given as for lattice_match_tracks
+        void add_lattice(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                         const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs, const std::vector<int32_t> &track_first,
+                         const std::vector<int32_t> &track_count, const std::vector<int32_t> &members, const std::vector<int32_t> &slots)
+        {
+            if (run_costs.size() != 65 * splits.size() || piece_costs.size() % 65 || first_run.size() != n_runs.size() || track_first.size() != track_count.size() ||
+                slots.size() != track_first.size())
+                throw std::invalid_argument("TrackPool::add_lattice: 65 bytes a run and a piece, one record a run, one span a word, one span and one slot a track");
+            check(str_er_track_pool_add_lattice(pool_.get(), ptr(splits), (int32_t)splits.size(), ptr(run_costs), ptr(piece_costs), (int32_t)(piece_costs.size() / 65),
+                                                ptr(first_run), ptr(n_runs), (int32_t)first_run.size(), ptr(track_first), ptr(track_count), ptr(members),
+                                                (int32_t)members.size(), (int32_t)track_first.size(), ptr(slots)));
+        }
+        // slot dst takes the members of the slots srcs, which become empty
+        void join(int32_t dst, const std::vector<int32_t> &srcs) { check(str_er_track_pool_join(pool_.get(), dst, ptr(srcs), (int32_t)srcs.size())); }
+        void clear(const std::vector<int32_t> &slots) { check(str_er_track_pool_clear(pool_.get(), ptr(slots), (int32_t)slots.size())); }
+        // one record per slot named (a slot may be named more than once)
+        std::vector<str_er_pool_match> read(const std::vector<int32_t> &slots)
+        {
+            std::vector<str_er_pool_match> out(slots.size());
+            check(str_er_track_pool_read(pool_.get(), ptr(slots), (int32_t)slots.size(), out.empty() ? nullptr : out.data()));
+            return out;
+        }
+        // every slot empty, the pool bound to the filter's lexicon and parameters as they are now
+        void reset() { check(str_er_track_pool_reset(pool_.get())); }
+        struct Info {
+            int32_t  cap_tracks = 0;
+            uint32_t flags = 0;
+            int32_t  n_entries = 0;
+            uint64_t device_bytes = 0;
+            int32_t  in_use = 0, stale = 0;
+        };
+        Info info() const
+        {
+            Info i;
+            check(str_er_track_pool_info(pool_.get(), &i.cap_tracks, &i.flags, &i.n_entries, &i.device_bytes, &i.in_use, &i.stale));
+            return i;
+        }
+    private:
+        template <typename T> static const T *ptr(const std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
+        void check(int rc) const
+        {
+            if (rc != STR_ER_OK) throw std::runtime_error(std::string(str_er_strerror(rc)) + ": " + str_er_last_error(ctx_.get()));
+        }
+        std::shared_ptr<str_er_ctx>        ctx_;      // (declared first: the pool is destroyed before its context)
+        std::shared_ptr<str_er_track_pool> pool_;
+    };
+
     // vector<double> ERFilter::make_LBP_hist(Mat input, N = 2, normalize_size = 24) (src/ER.cpp:789-816)
     std::vector<double> make_LBP_hist(const Image8 &input)
     {

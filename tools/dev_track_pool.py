@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""Developer aid: what the track pool costs (profiles/track_pool.md).
+
+    python tools/dev_track_pool.py batch [--same-length] [--lattice] [--iters N] [--reps 7]
+        the shape of `dev_track_read.py kernel`: 1000 random words (3 .. 12 runs, band 2) in 125 tracks of 8 against 100 000 random
+        entries.  One batch into an empty pool (clear, add, read) beside match_tracks (or lattice_match_tracks) on the same tracks,
+        in the same process: the call times, the cells of the recurrence either computes, the pool's read-modify-write bytes, and the
+        records compared.  --iters: calls only, for a `rocprofv3 --kernel-trace --stats` run.
+    python tools/dev_track_pool.py stream [--lattice] [--batches 10]
+        ten successive batches, each adding 8 members to the same 125 tracks: pool add + read per batch beside match_tracks on all
+        members so far, which is what a caller without the pool runs.  The records are compared after every batch.
+    python tools/dev_track_pool.py slots [--slots 125]
+        join (pairs of slots) and read on a pool of --slots slots with 8 members each.
+"""
+import argparse, json, os, sys, time
+import numpy as np
+
+ap = argparse.ArgumentParser()
+ap.add_argument("mode", choices=["batch", "stream", "slots"])
+ap.add_argument("--words", type=int, default=1000)
+ap.add_argument("--per-track", type=int, default=8)
+ap.add_argument("--entries", type=int, default=100000)
+ap.add_argument("--batches", type=int, default=10)
+ap.add_argument("--slots", type=int, default=125)
+ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--iters", type=int, default=0)
+ap.add_argument("--same-length", action="store_true")
+ap.add_argument("--lattice", action="store_true")
+ap.add_argument("--out", default="")
+a = ap.parse_args()
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: F401,E402  (the HIP runtime PyTorch brings, loaded first)
+import str_er_amd as S  # noqa: E402
+
+ALPHABET = "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz&()"
+SEVEN = ["entry", "cost", "second_entry", "second_cost", "free_cost", "n_tried", "n_used"]
+
+
+def stats(t):
+    return {"calls": [round(x, 3) for x in t], "median": round(float(np.median(t)), 3), "min": round(min(t), 3), "max": round(max(t), 3)}
+
+
+def timed(fn, reps):
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append((time.perf_counter() - t0) * 1e3)
+    return stats(t)
+
+
+def make(rng, n_words, n_tracks, per_track):
+    """Words with their rows (and, for --lattice, split records and piece rows), in tracks of per_track."""
+    n_of = rng.integers(3, 13, n_words).astype(np.int32)
+    if a.same_length:
+        n_of[:n_tracks * per_track] = np.repeat(n_of[:n_tracks], per_track)
+    first = np.concatenate([[0], np.cumsum(n_of)[:-1]]).astype(np.int32)
+    rows = lambda n: np.where(rng.random((n, 65)) < 0.05, rng.integers(0, 16, (n, 65)), rng.integers(40, 256, (n, 65))).astype(np.uint8)
+    rc = rows(int(n_of.sum()))
+    sp = np.zeros(len(rc), S.RUN_SPLIT_DTYPE)
+    sp["cut"] = -1
+    if a.lattice:          # a third of the runs with one cut: a run of two atoms has the pieces (0, 1) and (1, 2)
+        sp["n_cuts"] = rng.random(len(rc)) < 1 / 3
+        sp["n_pieces"] = 2 * sp["n_cuts"]
+        sp["first_piece"] = np.concatenate([[0], np.cumsum(sp["n_pieces"])[:-1]])
+    pc = rows(int(sp["n_pieces"].sum()))
+    tf = (np.arange(n_tracks) * per_track).astype(np.int32)
+    return dict(n_of=n_of, first=first, rc=rc, sp=sp, pc=pc, tf=tf, tc=np.full(n_tracks, per_track, np.int32), mem=np.arange(n_tracks * per_track, dtype=np.int32))
+
+
+def context(rng):
+    letters = np.array(list(ALPHABET))
+    words = ["".join(letters[rng.integers(0, 65, int(l))]) for l in rng.integers(3, 13, a.entries)]
+    f = S.ERFilter(params=S.Params(max_width=64, max_height=64, max_frames=1))
+    f.set_lexicon(words)
+    f.set_word_match(64, 64, 2)
+    return f, np.bincount([len(w) for w in words], minlength=33)
+
+
+def adders(f, pool, W):
+    if a.lattice:
+        return (lambda slots: pool.add_lattice(W["sp"], W["rc"], W["pc"], W["first"], W["n_of"], W["tf"], W["tc"], W["mem"], slots),
+                lambda: f.lattice_match_tracks(W["sp"], W["rc"], W["pc"], W["first"], W["n_of"], W["tf"], W["tc"], W["mem"])[0])
+    return (lambda slots: pool.add(W["rc"], W["first"], W["n_of"], W["tf"], W["tc"], W["mem"], slots),
+            lambda: f.match_tracks(W["rc"], W["first"], W["n_of"], W["tf"], W["tc"], W["mem"])[0])
+
+
+def same(pool_rec, track_rec):
+    return all((pool_rec[k] == track_rec[k]).all() for k in SEVEN)
+
+
+def batch():
+    rng = np.random.default_rng(1)
+    f, lens = context(rng)
+    n_tracks = a.words // a.per_track
+    W = make(rng, a.words, n_tracks, a.per_track)
+    pool = S.TrackPool(f, n_tracks, lattice=a.lattice)
+    slots = np.arange(n_tracks, dtype=np.int32)
+    add, match = adders(f, pool, W)
+    nodes = W["n_of"] + np.add.reduceat(W["sp"]["n_cuts"], W["first"]) if a.lattice else W["n_of"]          # (the rows of the column: runs, or atoms)
+    out = {"lib": S.lib_path(), "tracks": n_tracks, "per_track": a.per_track, "entries": a.entries, "same_length": a.same_length, "lattice": a.lattice,
+           "lexicon": f.lexicon_info(), "pool": pool.info()}
+    cells_match = 0
+    for g in range(n_tracks):
+        ms, rs = nodes[g * a.per_track:(g + 1) * a.per_track], W["n_of"][g * a.per_track:(g + 1) * a.per_track]
+        tried = [l for l in range(1, 33) if any(max(1, int(r) - 2) <= l <= min(32, int(m) + 2) for r, m in zip(rs, ms))]
+        cells_match += sum(int(lens[l]) * int(m) * l for m in ms for l in tried)
+    out["dp_cells_track_match"] = cells_match
+    out["dp_cells_pool_add"] = int(sum(int(lens[l]) * l for l in range(1, 33)) * int(nodes[:n_tracks * a.per_track].sum()))
+    out["pool_row_rmw_bytes"] = 2 * 4 * 64 * int(f.lexicon_info()["n"] // 64 + 32) * n_tracks          # (an upper bound: a load and a store of every padded entry and track)
+    def one():
+        pool.clear(slots); add(slots); return pool.read(slots)
+    got, want = one(), match()
+    out["records_equal"] = bool(same(got, want))
+    if a.iters:
+        for _ in range(a.iters):
+            one(); match()
+        out["iters"] = a.iters
+    else:
+        out["pool_clear_add_read_call_ms"] = timed(one, a.reps)
+        out["match_tracks_call_ms"] = timed(match, a.reps)
+    pool.close(); f.close()
+    return out
+
+
+def stream():
+    rng = np.random.default_rng(2)
+    f, lens = context(rng)
+    n_tracks = a.words // a.per_track
+    pool = S.TrackPool(f, n_tracks, lattice=a.lattice)
+    slots = np.arange(n_tracks, dtype=np.int32)
+    out = {"lib": S.lib_path(), "tracks": n_tracks, "per_batch": a.per_track, "batches": a.batches, "entries": a.entries, "lattice": a.lattice, "per_batch_ms": []}
+    batches = [make(rng, a.words, n_tracks, a.per_track) for _ in range(a.batches)]
+    for k in range(a.batches):
+        # what a caller without the pool runs: the track match on all members so far (member j of batch b of track g, rows shifted behind the batches before)
+        off_r = np.cumsum([0] + [len(B["rc"]) for B in batches[:k + 1]]); off_w = np.cumsum([0] + [len(B["n_of"]) for B in batches[:k + 1]])
+        off_p = np.cumsum([0] + [len(B["pc"]) for B in batches[:k + 1]])
+        sp = np.concatenate([B["sp"] for B in batches[:k + 1]])
+        sp["first_piece"] += np.repeat(off_p[:-1], [len(B["sp"]) for B in batches[:k + 1]]).astype(np.int32)
+        All = dict(rc=np.concatenate([B["rc"] for B in batches[:k + 1]]), pc=np.concatenate([B["pc"] for B in batches[:k + 1]]), sp=sp,
+                   first=np.concatenate([B["first"] + off_r[b] for b, B in enumerate(batches[:k + 1])]).astype(np.int32),
+                   n_of=np.concatenate([B["n_of"] for B in batches[:k + 1]]),
+                   mem=np.concatenate([[off_w[b] + g * a.per_track + j for b in range(k + 1) for j in range(a.per_track)] for g in range(n_tracks)]).astype(np.int32),
+                   tf=(np.arange(n_tracks) * a.per_track * (k + 1)).astype(np.int32), tc=np.full(n_tracks, a.per_track * (k + 1), np.int32))
+        add, _ = adders(f, pool, batches[k])
+        _, match = adders(f, pool, All)
+        t0 = time.perf_counter(); add(slots); got = pool.read(slots); t1 = time.perf_counter(); want = match(); t2 = time.perf_counter()
+        out["per_batch_ms"].append({"batch": k, "pool_add_read": round((t1 - t0) * 1e3, 3), "match_all_so_far": round((t2 - t1) * 1e3, 3), "equal": bool(same(got, want)),
+                                    "members": int(got["n_members"][0])})
+    pool.close(); f.close()
+    return out
+
+
+def slots_mode():
+    rng = np.random.default_rng(3)
+    f, lens = context(rng)
+    n = a.slots
+    W = make(rng, n * a.per_track, n, a.per_track)
+    pool = S.TrackPool(f, n, lattice=False)
+    every = np.arange(n, dtype=np.int32)
+    pool.add(W["rc"], W["first"], W["n_of"], W["tf"], W["tc"], W["mem"], every)
+    out = {"lib": S.lib_path(), "slots": n, "entries": a.entries, "pool": pool.info(), "read_call_ms": timed(lambda: pool.read(every), a.reps)}
+    t = []
+    for s in range(0, n - 1, 2):          # every pair once: the odd slot into the even one
+        t0 = time.perf_counter(); pool.join(s, [s + 1]); t.append((time.perf_counter() - t0) * 1e3)
+    out["join_call_ms"] = stats(t)
+    out["read_after_joins_call_ms"] = timed(lambda: pool.read(every), a.reps)
+    pool.close(); f.close()
+    return out
+
+
+if __name__ == "__main__":
+    res = {"batch": batch, "stream": stream, "slots": slots_mode}[a.mode]()
+    print(json.dumps(res, indent=1))
+    if a.out:
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
