@@ -181,6 +181,15 @@ extern "C" {
  * calls), and a lexicon: STR_ER_ESTATE without one (the matcher's rule); the context is usable afterwards.  It changes no other output
  * of the call -- str_er_result_track_matches still reads the split sequence -- and combines with every other STR_ER_WANT_* flag.     */
 #define STR_ER_WANT_LATTICE_TRACK (268435456u)
+/* output option: every word track decoded without a lexicon: the median string of its members under the bigram table of
+ * str_er_set_bigram, found from the members' own decoder strings by single edits (str_er_result_track_decodes / _track_decode_chars /
+ * _track_decode_member_costs, and the word links and word tracks of str_er_word_link: str_er_result_word_links / _word_tracks /
+ * _word_track_members / _word_track_of_words; the contract is at str_er_track_decode, the parameters: str_er_set_track_decode).  Needs
+ * STR_ER_WANT_LINE_LINKS and STR_ER_WANT_WORD_DECODE (and through the latter STR_ER_WANT_RUN_READ): STR_ER_EINVAL without either and
+ * wherever either is refused (the strip path, the per-plane calls), and a table: STR_ER_ESTATE without one; the context is usable
+ * afterwards.  It needs neither STR_ER_WANT_WORD_MATCH nor a lexicon.  Beside STR_ER_WANT_RUN_SPLIT the members' rows are those of
+ * their parts.  It changes no other output of the call and combines with every other STR_ER_WANT_* flag.                            */
+#define STR_ER_WANT_TRACK_DECODE (536870912u)
 /* the bits of a STR_ER_WANT_TEXT_MAP pixel: the OR over every region that covers it */
 #define STR_ER_TEXT_MAP_STRONG 1u   /* a strong candidate (cls == STR_ER_CLS_STRONG)                                              */
 #define STR_ER_TEXT_MAP_WEAK   2u   /* a weak candidate                                                                            */
@@ -574,10 +583,10 @@ typedef struct str_er_word_match {
  *     A track of one usable member has the six fields of that word's str_er_word_match; a track of unusable members tries nothing.
  *   Limits: across calls and stream submissions a detect call remembers nothing -- str_er_word_links and
  *     str_er_word_tracks_from_links link words over submissions, and a track pool (str_er_pool_match) keeps the summed costs of a
- *     track on the device from call to call.  There is no pooled open-vocabulary decode
- *     (a median string over members with different run counts is another problem).  The members enter with the rows the matcher
- *     read; the track match in which every member's segmentation is free is a separate output, str_er_lattice_track_member
- *     (STR_ER_WANT_LATTICE_TRACK).                                                                                                */
+ *     track on the device from call to call.  The open-vocabulary reading of a track, a median string over members with different
+ *     run counts, is a separate output, str_er_track_decode (STR_ER_WANT_TRACK_DECODE).  The members enter with the rows the
+ *     matcher read; the track match in which every member's segmentation is free is a separate output,
+ *     str_er_lattice_track_member (STR_ER_WANT_LATTICE_TRACK).                                                                    */
 typedef struct str_er_word_link {
     int32_t  a, b;           /*  0: a word of frame f and a word of the adjacent frame f + 1            */
     uint32_t inter;          /*  8: the area of the intersection of their boxes, > 0                    */
@@ -613,7 +622,8 @@ typedef struct str_er_track_match {
  *   A slot holds at most 65536 members (STR_ER_ECAPACITY above), the bound under which the int32 sums are safe.
  *   Limits: member_cost, best_member and the members' segmentations are not pooled -- the winning entry can change with every
  *     addition, and the members' rows are not kept; str_er_match_tracks / str_er_lattice_match_tracks give them for the members of
- *     one call.  There is no pooled open-vocabulary decode.  The pool must be destroyed before its context.                        */
+ *     one call.  There is no pooled open-vocabulary decode across calls: str_er_track_decode (STR_ER_WANT_TRACK_DECODE) decodes the
+ *     word tracks of one call.  The pool must be destroyed before its context.                                                    */
 #define STR_ER_POOL_LATTICE 1u
 typedef struct str_er_track_pool str_er_track_pool;
 typedef struct str_er_pool_match {
@@ -658,6 +668,48 @@ typedef struct str_er_word_decode {
     int32_t  n_chars, n_sub;              /*  8, 12                                   */
     int32_t  n_del, n_ins;                /* 16, 20                                   */
 } str_er_word_decode;        /* 24 bytes; one per word of str_er_result_words()       */
+
+/* The decoding of a word track without a lexicon (STR_ER_WANT_TRACK_DECODE, str_er_decode_tracks): one string for all members of a
+ * word track of str_er_word_link, a median string of the members under their cost rows and the bigram table, reached from the members'
+ * own decoder strings by single edits.  A definition of this library; integers only, exact, and the host states the same rules
+ * (str_er_decode_tracks_host).
+ *   Members: a track with the members w_1 .. w_n is given as for str_er_match_tracks.  Member i has m_i cost rows C_i, the rows the
+ *     decoder read for that word: the unfolded 65-byte rows of str_er_word_decode, with STR_ER_WANT_RUN_SPLIT those of its parts; they
+ *     are never folded.  A member is usable iff m_i <= 32.  A track has at most 1024 members (STR_ER_ECAPACITY above): the loop over
+ *     the members runs inside one workgroup, so the track match's bound of 65536 does not carry over; the int32 sums are safe far
+ *     beyond this bound.
+ *   Parameters: INS and DEL in 1 .. 255, 64 each by default, and rounds in 0 .. 64, 8 by default (str_er_set_track_decode).  The
+ *     table B is the context's (str_er_set_bigram).
+ *   Score of a string s of length l, 1 <= l <= 32, over the labels 0 .. 64, with E = 65: lm(s) = B[E][s_1] + the sum over j of
+ *     B[s_j][s_{j+1}] + B[s_l][E].  A_i(s) = D[m_i][l] of the recurrence of str_er_word_match on C_i with this output's INS and DEL,
+ *     no band and no fold.  J(s) = lm(s) + the sum of A_i(s) over the usable members.  Every term is at most 32 * 255 * 2: with 1024
+ *     members J stays far inside int32.
+ *   Seeds: the first 32 usable members, in slot order, whose str_er_word_decode string -- made on these rows with the INS / DEL of
+ *     str_er_set_word_decode -- has 1 .. 32 characters; duplicates count as they come.  s^0 is the seed with the smallest (J, seed
+ *     rank), the set median; seed_cost = J(s^0), seed_member that member's word index.  A track without a seed is not decoded: cost,
+ *     seed_cost and lm_cost are -1, n_chars = n_edits = converged = 0, seed_member = -1 and every member cost is -1; n_used is still
+ *     made.
+ *   Polish: for round r = 1 .. rounds, the neighbours of the current s of length l, positions j from 0: SUB(j, a), s_j replaced by a
+ *     (j < l, a in 0 .. 64), has the index j * 65 + a; DEL(j), s_j removed (j < l, only if l > 1), the index 2080 + j; INS(j, a), a
+ *     inserted before position j (j <= l, only if l < 32), the index 2112 + j * 65 + a.  The step is the neighbour with the smallest
+ *     (J, index).  If its J is strictly below J(s) it becomes s and n_edits grows by one; otherwise the search stops with
+ *     converged = 1.  After `rounds` rounds without that stop converged = 0; rounds = 0 leaves the set median with converged = 0.  (A
+ *     neighbour equal to s is never taken.)
+ *   Record: cost = J(s), lm_cost = lm(s), n_chars = l, n_used the number of usable members.  Per slot of the member array
+ *     member_cost = A_i(s), -1 for an unusable member, in a slot of no track and where nothing was decoded.  Per track 32 bytes of
+ *     labels, padded with 0xFF.  Hence cost = lm_cost + the sum of the member costs >= 0; cost <= seed_cost <= J(every seed);
+ *     converged = 1 implies that no neighbour scores below cost; rounds = 0 gives the winning seed's decoder string byte for byte;
+ *     and for a track of one usable member decoded with the decoder's INS = DEL = 0, seed_cost <= that word's str_er_word_decode
+ *     cost (the diagonal alignment is one of the alignments).
+ *   Limits: this is a local optimum of single edits from the set median, not the global median string.  The members enter with the
+ *     rows the decoder read; a joint search over the members' piece lattices is not part of it.  Nothing is pooled across calls.
+ *     Whether the polish helps on real text has not been measured, and nothing here is tuned on labelled data.                      */
+typedef struct str_er_track_decode {
+    int32_t  cost, seed_cost;             /*  0,  4                                   */
+    int32_t  n_chars, n_edits;            /*  8, 12                                   */
+    int32_t  converged, n_used;           /* 16, 20                                   */
+    int32_t  seed_member, lm_cost;        /* 24, 28                                   */
+} str_er_track_decode;       /* 32 bytes; one per word track                          */
 
 /* The splitting of touching glyphs (str_er_feet_split, str_er_split_words): candidate cut columns inside a glyph run, the pieces they
  * make, the reading of every piece, and per run the segmentation the scorer likes best (STR_ER_WANT_RUN_SPLIT).  A definition of this library, like the word
@@ -1228,6 +1280,23 @@ int str_er_decode_words(str_er_ctx *ctx, const uint8_t *costs, int32_t n_runs, c
  * no context, no GPU.                                                                                                              */
 int str_er_decode_words_host(const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
                              const uint8_t *bigram, int32_t ins, int32_t del, str_er_word_decode *dec, uint8_t *chars, uint8_t *src);
+/* INS and DEL (1 .. 255) and the number of polish rounds (0 .. 64) of str_er_track_decode; defaults 64, 64 and 8.  Anything else ->
+ * STR_ER_EINVAL, the context unchanged.  A stream's contexts: str_er_stream_context.                                               */
+int str_er_set_track_decode(str_er_ctx *ctx, int32_t ins, int32_t del, int32_t rounds);
+/* The track decode (str_er_track_decode) on the caller's cost rows, on the GPU, under the context's table, its str_er_set_word_decode
+ * (the seeds' strings: the decoder runs on these rows first) and its str_er_set_track_decode: the rows, the words and the tracks are
+ * given as for str_er_match_tracks.  out receives n_tracks records, chars 32 bytes per track, member_cost n_members values (-1 in a
+ * slot of no track).  STR_ER_ESTATE without a table; STR_ER_EINVAL on a word outside the rows, a member outside the words, a track
+ * outside the member array; STR_ER_ECAPACITY on a track of more than 1024 members.  It needs no SVM model and no lexicon.           */
+int str_er_decode_tracks(str_er_ctx *ctx, const uint8_t *costs, int32_t n_rows, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
+                         const int32_t *track_first, const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks,
+                         str_er_track_decode *out, uint8_t *chars, int32_t *member_cost);
+/* The same rules on one host thread, with the table, the decoder's INS / DEL (dec_ins, dec_del: the checks of str_er_set_word_decode)
+ * and this output's parameters (the checks of str_er_set_track_decode) as arguments.  Pure: no context, no GPU.                     */
+int str_er_decode_tracks_host(const uint8_t *costs, int32_t n_rows, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
+                              const int32_t *track_first, const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks,
+                              const uint8_t *bigram, int32_t dec_ins, int32_t dec_del, int32_t ins, int32_t del, int32_t rounds,
+                              str_er_track_decode *out, uint8_t *chars, int32_t *member_cost);
 
 /* num / den of the valley threshold (1 .. 65535 each) and SPLIT (0 .. 255) of str_er_run_split; defaults 1 / 4 and 8.  Anything else
  * -> STR_ER_EINVAL, the context unchanged.                                                                                          */
@@ -1623,13 +1692,20 @@ const uint8_t               *str_er_result_lattice_match_src(const str_er_result
 const str_er_split_part     *str_er_result_lattice_match_parts(const str_er_result *r, int32_t *n);
 /* With STR_ER_WANT_TRACK_READ (str_er_word_link): the word links sorted by (a, b); the word tracks; their members (word indices); one
  * track index per word of str_er_result_words() (-1: not eligible); one match per word track; one cost per slot of the member array.
- * Each returns NULL and 0 without the flag; a call without words returns empty arrays (not NULL).                                  */
+ * Each returns NULL and 0 without the flag; a call without words returns empty arrays (not NULL).  The first four answer for
+ * STR_ER_WANT_TRACK_DECODE as well; the matches and their member costs are STR_ER_WANT_TRACK_READ's alone.                          */
 const str_er_word_link   *str_er_result_word_links(const str_er_result *r, int32_t *n);
 const str_er_word_track  *str_er_result_word_tracks(const str_er_result *r, int32_t *n);
 const int32_t            *str_er_result_word_track_members(const str_er_result *r, int32_t *n);
 const int32_t            *str_er_result_word_track_of_words(const str_er_result *r, int32_t *n);
 const str_er_track_match *str_er_result_track_matches(const str_er_result *r, int32_t *n);
 const int32_t            *str_er_result_track_member_costs(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_TRACK_DECODE (str_er_track_decode): one record and 32 label bytes per word track of str_er_result_word_tracks(), and
+ * one cost per slot of str_er_result_word_track_members().  Each returns NULL and 0 without the flag; a call without words returns
+ * empty arrays (not NULL).                                                                                                          */
+const str_er_track_decode *str_er_result_track_decodes(const str_er_result *r, int32_t *n);
+const uint8_t             *str_er_result_track_decode_chars(const str_er_result *r, uint64_t *n_bytes);
+const int32_t             *str_er_result_track_decode_member_costs(const str_er_result *r, int32_t *n);
 /* With STR_ER_WANT_LATTICE_TRACK (str_er_lattice_track_member): one match per word track of str_er_result_word_tracks(), one record and
  * 32 source bytes per slot of str_er_result_word_track_members(), and the members' parts back to back in slot order.  Each returns NULL
  * and 0 without the flag; a call without words returns empty arrays (not NULL).                                                      */

@@ -98,6 +98,16 @@ WANT_LATTICE_MATCH = 134217728
 # and for it every member gets its own parts and sources (needs WANT_TRACK_READ and WANT_LATTICE_MATCH; Result.lattice_track_matches /
 # lattice_track_members / lattice_track_src / lattice_track_parts / word_track_lattice_text; the contract is at str_er_lattice_track_member)
 WANT_LATTICE_TRACK = 268435456
+# every word track decoded without a lexicon: the median string of its members under the bigram table, from the members' own decoder
+# strings by single edits (needs WANT_LINE_LINKS and WANT_WORD_DECODE, no lexicon; Result.track_decodes / track_decode_chars /
+# track_decode_member_costs / word_track_decode_text / text_track_decode_text, and word_links / word_tracks / word_track_members /
+# word_track_of_words; the contract is at str_er_track_decode)
+WANT_TRACK_DECODE = 536870912
+# str_er_track_decode: per word track, J of the string and of the set median it started from (-1: no seed, not decoded), its length,
+# the edits taken, whether no single edit improves it, the usable members, the word whose decoder string was the seed, and lm of the string
+TRACK_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("seed_cost", "<i4"), ("n_chars", "<i4"), ("n_edits", "<i4"), ("converged", "<i4"), ("n_used", "<i4"),
+                               ("seed_member", "<i4"), ("lm_cost", "<i4")])
+assert TRACK_DECODE_DTYPE.itemsize == 32
 # str_er_lattice_track_member: per slot of the member array, the member's own cost for its track's entry (-1: none), its parts in the
 # lattice track part table, the parts dropped and the characters inserted, and the member (a word index; -1 in a slot of no track)
 LATTICE_TRACK_MEMBER_DTYPE = np.dtype([("cost", "<i4"), ("first_part", "<i4"), ("n_parts", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4"), ("word", "<i4")])
@@ -416,6 +426,13 @@ def load_library():
                L.str_er_result_track_matches, L.str_er_result_track_member_costs):
         fn.argtypes = [vp, i32p]
         fn.restype = vp
+    L.str_er_set_track_decode.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+    L.str_er_decode_tracks.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp]
+    L.str_er_decode_tracks_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, vp, vp, vp]
+    for name, cnt in (("track_decodes", i32p), ("track_decode_chars", C.POINTER(C.c_uint64)), ("track_decode_member_costs", i32p)):
+        fn = getattr(L, "str_er_result_" + name)
+        fn.argtypes, fn.restype = [vp, cnt], vp
     L.str_er_result_run_costs.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.str_er_result_run_costs.restype = vp
     L.str_er_result_run_probs.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -629,6 +646,7 @@ class Result:
         self._lattice_decodes = None  # with WANT_LATTICE_DECODE: the tables behind lattice_decodes / lattice_decode_chars / lattice_decode_src / lattice_parts
         self._word_links = None    # with WANT_TRACK_READ: the tables behind word_links / word_tracks / word_track_members / word_track_of_words / track_matches / track_member_costs
         self._word_tracks = self._word_track_members = self._word_track_of_words = self._track_matches = self._track_member_costs = None
+        self._track_decodes = self._track_decode_chars = self._track_decode_member_costs = None  # with WANT_TRACK_DECODE: the tables behind track_decodes / track_decode_chars / track_decode_member_costs
         self._lattice_track_matches = None  # with WANT_LATTICE_TRACK: the tables behind lattice_track_matches / lattice_track_members / lattice_track_src / lattice_track_parts
         self._lattice_track_members = self._lattice_track_src = self._lattice_track_parts = None
         self._run_pieces = None
@@ -934,6 +952,42 @@ class Result:
         if table is None:
             raise ValueError("the result has no word tracks (pass WANT_TRACK_READ / want_track_read=True)")
         return table
+
+    def _track_decode_table(self, table):
+        if table is None:
+            raise ValueError("the result has no track decodes (pass WANT_TRACK_DECODE / want_track_decode=True)")
+        return table
+
+    @property
+    def track_decodes(self) -> np.ndarray:
+        """With WANT_TRACK_DECODE: TRACK_DECODE_DTYPE per word track."""
+        return self._track_decode_table(self._track_decodes)
+
+    @property
+    def track_decode_chars(self) -> np.ndarray:
+        """With WANT_TRACK_DECODE: (n tracks, 32) uint8, the labels of every track's string, 0xFF past n_chars."""
+        return self._track_decode_table(self._track_decode_chars)
+
+    @property
+    def track_decode_member_costs(self) -> np.ndarray:
+        """With WANT_TRACK_DECODE: the own alignment cost of every member of word_track_members for its track's string (int32), -1 without one."""
+        return self._track_decode_table(self._track_decode_member_costs)
+
+    def word_track_decode_text(self, g: int) -> str:
+        """With WANT_TRACK_DECODE: the string word track g was decoded to; the representative's own reading (word_text) where the track
+        was not decoded."""
+        d = self.track_decodes[g]
+        if int(d["cost"]) < 0:
+            return self.word_text(int(self.word_tracks[g]["rep"]))
+        return "".join(_OCR_ALPHABET[int(a)] for a in self.track_decode_chars[g, :int(d["n_chars"])])
+
+    def text_track_decode_text(self, k: int) -> str:
+        """With WANT_TRACK_DECODE: the words of the representative line of text track k in order, each as its word track's decoded
+        string (its own word_text where the line is no reading line), joined by one blank."""
+        lw = self.line_words[int(self.text_tracks[k]["rep"])]
+        of = self.word_track_of_words
+        ws = range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))
+        return " ".join(self.word_track_decode_text(int(of[w])) if of[w] >= 0 else self.word_text(w) for w in ws)
 
     @property
     def word_links(self) -> np.ndarray:
@@ -1364,6 +1418,10 @@ class ERFilter:
                             res._word_track_of_words = table(L.str_er_result_word_track_of_words, np.int32)
                             res._track_matches = table(L.str_er_result_track_matches, TRACK_MATCH_DTYPE)
                             res._track_member_costs = table(L.str_er_result_track_member_costs, np.int32)
+                            res._track_decodes = table(L.str_er_result_track_decodes, TRACK_DECODE_DTYPE)
+                            if res._track_decodes is not None:
+                                res._track_decode_chars = table(L.str_er_result_track_decode_chars, np.uint8, n64).reshape(-1, 32)
+                                res._track_decode_member_costs = table(L.str_er_result_track_decode_member_costs, np.int32)
                             res._lattice_track_matches = table(L.str_er_result_lattice_track_matches, TRACK_MATCH_DTYPE)
                             if res._lattice_track_matches is not None:
                                 res._lattice_track_members = table(L.str_er_result_lattice_track_members, LATTICE_TRACK_MEMBER_DTYPE)
@@ -1434,7 +1492,7 @@ class ERFilter:
                     want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                     want_strokes: bool = False, want_frame_lines: bool = False,
                     want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False, want_track_decode: bool = False) -> Result:
         """ERFilter::text_detect up to classify (src/ER.cpp:33-60) for one BGR frame (H,W,3)
         or a batch (F,H,W,3) of uint8."""
         a = np.ascontiguousarray(src, dtype=np.uint8)
@@ -1447,7 +1505,7 @@ class ERFilter:
         self._check(self.L.str_er_detect_bgr(self.h, _np_ptr(a), w, h, 3 * w, 3 * w * h, f, MEM_HOST,
                                              stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                                   text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode, lattice_match=want_lattice_match, lattice_track=want_lattice_track), C.byref(rh)))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode, lattice_match=want_lattice_match, lattice_track=want_lattice_track, track_decode=want_track_decode), C.byref(rh)))
         return self._collect(rh)
 
     def text_detect_nv12(self, nv12: np.ndarray, w: int, h: int, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
@@ -1569,7 +1627,7 @@ class ERFilter:
                          want_line_crops=False, want_shapes: bool = False, want_text_map: bool = False, want_line_map: bool = False,
                          want_strokes: bool = False, want_frame_lines: bool = False,
                          want_line_links: bool = False, want_line_geom: bool = False, want_line_words: bool = False,
-                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> Result:
+                    want_run_read: bool = False, want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False, want_track_decode: bool = False) -> Result:
         """text_detect for a sequence of (H,W,3) uint8 BGR frames of any sizes (each within the capacity) in one call.  Frame i's
         planes and candidates are those text_detect gives for it alone, with frame = i.  Views with a row stride are not copied."""
         keep = [_row_view(f, 3) for f in frames]
@@ -1577,7 +1635,7 @@ class ERFilter:
         return self._detect_list(self.L.str_er_detect_bgr_list, refs, MEM_HOST,
                                  stages | _want_flags(nodes=want_nodes, masks=want_masks, line_crops=want_line_crops, shapes=want_shapes,
                                                       text_map=want_text_map, line_map=want_line_map, strokes=want_strokes, frame_lines=want_frame_lines,
-                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode, lattice_match=want_lattice_match, lattice_track=want_lattice_track))
+                                                                  line_links=want_line_links, line_geom=want_line_geom, line_words=want_line_words, run_read=want_run_read, word_match=want_word_match, word_decode=want_word_decode, run_split=want_run_split, track_read=want_track_read, lattice_decode=want_lattice_decode, lattice_match=want_lattice_match, lattice_track=want_lattice_track, track_decode=want_track_decode))
 
     def detect_planes_list(self, planes, stages: int = STAGE_ALL, want_nodes: bool = False) -> Result:
         """detect_planes for a sequence of (H,W) uint8 planes of any sizes in one call: plane i gets ch = i & 255."""
@@ -1851,6 +1909,23 @@ class ERFilter:
         self._check(self.L.str_er_match_tracks(self.h, opt(cs), len(cs), opt(fr), opt(no), len(fr), opt(tf), opt(tc), opt(mem), len(mem), len(tf),
                                                _np_ptr(out), _np_ptr(mc)))
         return out[:len(tf)], mc[:len(mem)]
+
+    def set_track_decode(self, ins: int = 64, dele: int = 64, rounds: int = 8) -> None:
+        """str_er_set_track_decode: INS and DEL (1 .. 255) and the polish rounds (0 .. 64) of the track decode."""
+        self._check(self.L.str_er_set_track_decode(self.h, int(ins), int(dele), int(rounds)))
+
+    def decode_tracks(self, costs: np.ndarray, first_run, n_runs_of_word, track_first, track_count, members):
+        """str_er_decode_tracks: the tracks members[track_first[g]:track_first[g] + track_count[g]] of the words [first_run[w],
+        first_run[w] + n_runs_of_word[w]) of the cost rows (n rows, 65) uint8 under the table, set_word_decode (the seeds) and
+        set_track_decode; returns (TRACK_DECODE_DTYPE per track, (n tracks, 32) uint8 labels, int32 member costs per slot of members)."""
+        cs, fr, no, tf, tc, mem = _track_args(costs, first_run, n_runs_of_word, track_first, track_count, members)
+        out = np.zeros(max(1, len(tf)), TRACK_DECODE_DTYPE)
+        ch = np.full((max(1, len(tf)), 32), 0xFF, np.uint8)
+        mc = np.zeros(max(1, len(mem)), np.int32)
+        opt = lambda a: _np_ptr(a) if len(a) else None
+        self._check(self.L.str_er_decode_tracks(self.h, opt(cs), len(cs), opt(fr), opt(no), len(fr), opt(tf), opt(tc), opt(mem), len(mem), len(tf),
+                                                _np_ptr(out), _np_ptr(ch), _np_ptr(mc)))
+        return out[:len(tf)], ch[:len(tf)], mc[:len(mem)]
 
     def set_bigram(self, table) -> None:
         """str_er_set_bigram: the (66, 66) uint8 table of the word decoder (str_er_word_decode; bigram_from_probs / bigram_from_words
@@ -2497,6 +2572,23 @@ def lattice_match_tracks_host(splits, run_costs, piece_costs, first_run, n_runs_
     return _lattice_track_out(a)
 
 
+def decode_tracks_host(costs: np.ndarray, first_run, n_runs_of_word, track_first, track_count, members, table, dec_ins: int = 0, dec_dele: int = 0,
+                       ins: int = 64, dele: int = 64, rounds: int = 8):
+    """str_er_decode_tracks_host (pure host, one thread): ERFilter.decode_tracks with the table, the decoder's INS / DEL and the
+    parameters as arguments."""
+    cs, fr, no, tf, tc, mem = _track_args(costs, first_run, n_runs_of_word, track_first, track_count, members)
+    out = np.zeros(max(1, len(tf)), TRACK_DECODE_DTYPE)
+    ch = np.full((max(1, len(tf)), 32), 0xFF, np.uint8)
+    mc = np.zeros(max(1, len(mem)), np.int32)
+    opt = lambda a: _np_ptr(a) if len(a) else None
+    rc = load_library().str_er_decode_tracks_host(opt(cs), len(cs), opt(fr), opt(no), len(fr), opt(tf), opt(tc), opt(mem), len(mem), len(tf),
+                                                  _np_ptr(_bigram_table(table)), int(dec_ins), int(dec_dele), int(ins), int(dele), int(rounds),
+                                                  _np_ptr(out), _np_ptr(ch), _np_ptr(mc))
+    if rc != 0:
+        raise StrErError(rc, "str_er_decode_tracks_host")
+    return out[:len(tf)], ch[:len(tf)], mc[:len(mem)]
+
+
 def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: int = 0, dele: int = 0):
     """str_er_decode_words_host (pure host, one thread): ERFilter.decode_words with the table and the parameters as arguments."""
     cs, fr, no, out, ch, sr = _decode_args(costs, first_run, n_runs_of_word)
@@ -2508,10 +2600,10 @@ def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: 
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
-                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False, track_read=False, lattice_decode=False, lattice_match=False, lattice_track=False) -> int:
+                frame_lines=False, line_links=False, line_geom=False, line_words=False, run_read=False, word_match=False, word_decode=False, run_split=False, track_read=False, lattice_decode=False, lattice_match=False, lattice_track=False, track_decode=False) -> int:
     """The WANT_* bits of the want_* arguments of a detect call (line_crops: False, True (grey crops) or "glyphs" (grey and glyph crops))."""
     bits = [(nodes, WANT_NODES), (masks, WANT_MASKS), (shapes, WANT_SHAPES), (strokes, WANT_STROKES), (text_map, WANT_TEXT_MAP),
-            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (track_read, WANT_TRACK_READ), (lattice_decode, WANT_LATTICE_DECODE), (lattice_match, WANT_LATTICE_MATCH), (lattice_track, WANT_LATTICE_TRACK), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
+            (line_map, WANT_LINE_MAP), (frame_lines, WANT_FRAME_LINES), (line_links, WANT_LINE_LINKS), (line_geom, WANT_LINE_GEOM), (line_words, WANT_LINE_WORDS), (run_read, WANT_RUN_READ), (word_match, WANT_WORD_MATCH), (word_decode, WANT_WORD_DECODE), (run_split, WANT_RUN_SPLIT), (track_read, WANT_TRACK_READ), (lattice_decode, WANT_LATTICE_DECODE), (lattice_match, WANT_LATTICE_MATCH), (lattice_track, WANT_LATTICE_TRACK), (track_decode, WANT_TRACK_DECODE), (line_crops, WANT_LINE_CROPS), (line_crops == "glyphs", WANT_LINE_GLYPHS)]
     return sum(bit for want, bit in bits if want)
 
 
@@ -3169,6 +3261,14 @@ class FrameStream:
             if rc != 0:
                 raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
 
+    def set_track_decode(self, ins: int = 64, dele: int = 64, rounds: int = 8) -> None:
+        """str_er_set_track_decode on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_track_decode(ctx, int(ins), int(dele), int(rounds))
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
     def set_word_decode(self, ins: int = 0, dele: int = 0) -> None:
         """str_er_set_word_decode on every context of the stream."""
         for i in range(int(self.L.str_er_stream_depth(self.h))):
@@ -3194,23 +3294,23 @@ class FrameStream:
         return slot.value, arr
 
     def submit(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False, want_track_decode: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0) | (WANT_TRACK_DECODE if want_track_decode else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit(self.h, slot, w, h, 3 * w, 3 * w * h, n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_nv12(self, slot: int, w: int, h: int, n_frames: int, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False, want_track_decode: bool = False) -> int:
         """The staging buffer holds n_frames tightly packed NV12 frames (w * h * 3 / 2 bytes each)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0) | (WANT_TRACK_DECODE if want_track_decode else 0)
         t = C.c_uint64()
         self._check(self.L.str_er_stream_submit_nv12(self.h, slot, w, h, w, w * (h + h // 2), n_frames, stages, C.byref(t)))
         return int(t.value)
 
     def submit_copy(self, frames: np.ndarray, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False, want_track_decode: bool = False) -> int:
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0) | (WANT_TRACK_DECODE if want_track_decode else 0)
         a = np.ascontiguousarray(frames, dtype=np.uint8)
         if a.ndim == 3:
             a = a[None]
@@ -3228,21 +3328,21 @@ class FrameStream:
         return int(t.value)
 
     def submit_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False, want_track_decode: bool = False) -> int:
         """BGR frames of assorted sizes in the acquired buffer: layout = [(byte offset, w, h, stride), ...] (str_er_stream_submit_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0) | (WANT_TRACK_DECODE if want_track_decode else 0)
         return self._submit_list(self.L.str_er_stream_submit_list, slot, layout, stages)
 
     def submit_nv12_list(self, slot: int, layout, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False, want_track_decode: bool = False) -> int:
         """The same for NV12 frames: at every offset h + h/2 rows of `stride` bytes (str_er_stream_submit_nv12_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0) | (WANT_TRACK_DECODE if want_track_decode else 0)
         return self._submit_list(self.L.str_er_stream_submit_nv12_list, slot, layout, stages)
 
     def submit_copy_list(self, frames, stages: int = STAGE_ALL, want_line_words: bool = False, want_run_read: bool = False,
-               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False) -> int:
+               want_word_match: bool = False, want_word_decode: bool = False, want_run_split: bool = False, want_track_read: bool = False, want_lattice_decode: bool = False, want_lattice_match: bool = False, want_lattice_track: bool = False, want_track_decode: bool = False) -> int:
         """(H,W,3) uint8 BGR frames of any sizes, copied into a buffer and submitted as one list (str_er_stream_submit_copy_list)."""
-        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0)
+        stages |= (WANT_LINE_WORDS if want_line_words else 0) | (WANT_RUN_READ if want_run_read else 0) | (WANT_WORD_MATCH if want_word_match else 0) | (WANT_WORD_DECODE if want_word_decode else 0) | (WANT_RUN_SPLIT if want_run_split else 0) | (WANT_TRACK_READ if want_track_read else 0) | (WANT_LATTICE_DECODE if want_lattice_decode else 0) | (WANT_LATTICE_MATCH if want_lattice_match else 0) | (WANT_LATTICE_TRACK if want_lattice_track else 0) | (WANT_TRACK_DECODE if want_track_decode else 0)
         keep = [_row_view(f, 3) for f in frames]
         refs = [ImageRef(_np_ptr(a), a.shape[1], a.shape[0], a.strides[0]) for a in keep]
         arr = (ImageRef * max(1, len(refs)))(*refs)

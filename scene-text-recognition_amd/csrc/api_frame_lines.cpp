@@ -17,6 +17,7 @@
 // the words (str_er_words_from_runs, words_host.cpp).  str_er_feet_words runs the same kernel on uploaded footprints.
 // STR_ER_WANT_RUN_READ behind that, with a second enqueue and wait: run_read_stage (api_run_read.cpp).
 #include "str_er_ctx.h"
+#include "track_decode_rules.h"
 #include "track_read_rules.h"
 
 #include <numeric>
@@ -702,7 +703,8 @@ int fill_geometry(str_er_ctx *c, str_er_result *r, const GeomPass &GP)
 // read, and its footprints are still in c->foot_bits
 // track: the word links and word tracks of STR_ER_WANT_TRACK_READ on the host before the reading (the text tracks of r are made: fill_links),
 // the track match behind the matcher, with ltrack the one over the members' piece lattices behind the lattice match (frame_of: the frame of every line, frame_wh: the level-0 sizes of the frames)
-int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode, bool split, bool lattice, bool lmatch, bool ltrack, bool track,
+// tdecode: the same links and tracks for STR_ER_WANT_TRACK_DECODE (made once where both flags are set), the track decode behind the decoder
+int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode, bool split, bool lattice, bool lmatch, bool ltrack, bool track, bool tdecode,
                const std::vector<uint32_t> &frame_of, const std::vector<int32_t> &frame_wh)
 {
     const auto   t2 = std::chrono::steady_clock::now();
@@ -729,9 +731,11 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
             out.lattice_decodes = &r->lattice_decodes; out.lattice_chars = &r->lattice_decode_chars; out.lattice_src = &r->lattice_decode_src; out.lattice_parts = &r->lattice_parts;
         }
         if (lmatch && split && match) { out.lattice_matches = &r->lattice_matches; out.lattice_match_src = &r->lattice_match_src; out.lattice_match_parts = &r->lattice_match_parts; }
-        if (track) {
-            out.tracks = &r->word_tracks; out.track_members = &r->word_track_members; out.track_matches = &r->track_matches; out.track_member_costs = &r->track_member_costs;
-            if (!r->have_line_links || !match) return fail(c, STR_ER_EHIP, "track read: no text tracks or no matcher (internal error)");
+        if (track || tdecode) {
+            out.tracks = &r->word_tracks; out.track_members = &r->word_track_members;
+            if (track) { out.track_matches = &r->track_matches; out.track_member_costs = &r->track_member_costs; }
+            if (tdecode) { out.track_decodes = &r->track_decodes; out.track_decode_chars = &r->track_decode_chars; out.track_decode_member_costs = &r->track_decode_member_costs; }
+            if (!r->have_line_links || (track && !match) || (tdecode && !decode)) return fail(c, STR_ER_EHIP, "track read: no text tracks, no matcher or no decoder (internal error)");
             for (const str_er_line_word &w : r->words)
                 if (w.line < 0 || (size_t)w.line >= n_lines || !str_er_tr::box_ok(w)) return fail(c, STR_ER_EHIP, "track read: a word outside the lines (internal error)");
             const auto           t3 = std::chrono::steady_clock::now();
@@ -743,6 +747,8 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
                                    (int32_t)r->word_links.size(), r->word_track_of_words, r->word_tracks, r->word_track_members);
             for (const str_er_word_track &G : r->word_tracks)
                 if (G.count > str_er_tr::MAX_MEMBERS) return fail(c, STR_ER_ECAPACITY, "STR_ER_WANT_TRACK_READ: a word track of more than 65536 members");
+            for (const str_er_word_track &G : r->word_tracks)
+                if (tdecode && G.count > str_er_td::MAX_MEMBERS) return fail(c, STR_ER_ECAPACITY, "STR_ER_WANT_TRACK_DECODE: a word track of more than 1024 members");
             if (c->dbg_stats)        // developer aid (tools/dev_track_read.py)
                 std::fprintf(stderr, "[str_er] track read: %zu words, %zu word links, %zu word tracks, %zu members, host %.3f ms\n", r->words.size(), r->word_links.size(),
                              r->word_tracks.size(), r->word_track_members.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t3).count());
@@ -754,6 +760,8 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features, split ? &rp : nullptr, &out); rcr != STR_ER_OK)
             return rcr;
         r->have_track_read = track;
+        r->have_word_tracks = track || tdecode;
+        r->have_track_decodes = tdecode;
         r->have_run_splits = split;
         r->have_lattice_decodes = lattice && split;
         r->have_lattice_matches = lmatch && split && match;
@@ -800,7 +808,7 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
     if ((rc = fill_frame_lines(c, r, frame_of, pyr_of, S.feet.pairs, n_fl)) != STR_ER_OK) return rc;
     if (want.links && (rc = fill_links(c, b, r, frame_of, T, S.links)) != STR_ER_OK) return rc;
     if (want.geom && (rc = fill_geometry(c, r, S.geom)) != STR_ER_OK) return rc;
-    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split, want.lattice, want.lmatch, want.ltrack, want.track, frame_of, b.frame_wh)) != STR_ER_OK) return rc;
+    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split, want.lattice, want.lmatch, want.ltrack, want.track, want.tdecode, frame_of, b.frame_wh)) != STR_ER_OK) return rc;
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
                              "%zu bytes back, host %.3f ms before + %.3f ms after the device\n",

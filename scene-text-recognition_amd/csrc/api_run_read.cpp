@@ -18,14 +18,15 @@
 //   lattice decode   U's rows (runs first, pieces from row n_run on) with (first, n_of, slot) and the split records
 //   lattice match    A's rows (runs first, pieces from row n_run on) with (first, n_of, slot) and the split records; iff match && split
 //   lattice track    the same rows and records as the lattice match, with the track match's tracks; iff the lattice match and the track match run
+//   track decode     the same window as the decoder, with the decoder's records and labels where it left them; iff decode
 //
 //   result table     source
 //   run_costs        A if match, else U
 //   piece_costs      A if match, else U
 //   run_probs        present iff match or decode
 //
-// The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, rs_tab, ld_tab, lm_tab, lt_tab and
-// tm_tab hold what their kernels leave.
+// The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, rs_tab, ld_tab, lm_tab, lt_tab,
+// tm_tab and td_tab hold what their kernels leave.
 #include "str_er_ctx.h"
 #include "lattice_decode_kernels.h"
 #include "lattice_match_kernels.h"
@@ -41,6 +42,10 @@ void ReadChainOut::preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k
     if (p.match) matches->assign(n_words, str_er_word_match{-1, -1, -1, -1, 0, 0});
     if (p.track) { track_matches->assign(tracks->size(), str_er_track_match{-1, -1, -1, -1, 0, 0, 0, -1}); track_member_costs->assign(track_members->size(), -1); }
     if (p.decode) { decodes->assign(n_words, str_er_word_decode{}); decode_chars->assign(64 * n_words, 0xFF); decode_src->assign(64 * n_words, 0xFF); }
+    if (p.tdecode) {
+        track_decodes->assign(tracks->size(), str_er_track_decode{-1, -1, 0, 0, 0, 0, -1, -1}); track_decode_chars->assign(32 * tracks->size(), 0xFF);
+        track_decode_member_costs->assign(track_members->size(), -1);
+    }
     if (p.split) { piece_costs->assign(65 * n_pc, 0); parts->clear(); word_splits->assign(n_words, str_er_word_split{0, 0, 0, 0}); }
     if (p.lattice) {
         lattice_decodes->assign(n_words, str_er_lattice_decode{}); lattice_chars->assign(64 * n_words, 0xFF); lattice_src->assign(64 * n_words, 0xFF);
@@ -95,7 +100,7 @@ struct ReadCall {
     RunTab   TH{}, TD{};
     OcrBuf   buf{};
     uint8_t *rows[2] = {nullptr, nullptr}, *parts[2] = {nullptr, nullptr};
-    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; TmTab KD{};
+    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; TmTab KD{}; TdTab EH{}, ED{};
 
     // phase 1 (host alone): the tiles and rotations of the runs and pieces, every box checked, and their places in the atlas
     int geometry(const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words, const std::vector<str_er_line_run> &runs, const double *slopes,
@@ -161,7 +166,7 @@ struct ReadCall {
                     return fail(c, STR_ER_EHIP, "run split: a run's pieces outside the piece table (internal error)");
             if (!rs_word_slots(o.splits->data(), TH.first, TH.n_of, n_words, slot, &n_slots)) return fail(c, STR_ER_ECAPACITY, "run split: more than 2^31 parts to reserve");
         }
-        if (p.track) {
+        if (p.track || p.tdecode) {
             const size_t n_members = o.track_members->size();
             for (const str_er_word_track &G : *o.tracks) {
                 if (G.first < 0 || G.count < 0 || (size_t)G.first + (size_t)G.count > n_members)
@@ -248,6 +253,11 @@ struct ReadCall {
         if (p.decode) {
             const Window W = window(p.decode_set);
             launch_word_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, W.rows, W.first, W.n, (int)n_words, DD.dec, DD.chars, DD.src);
+            if (p.tdecode && !tfirst.empty())          // the decoder's window, its records and labels where it left them
+                if (const int rc = track_decode_enqueue(c, s, 0, W.rows, W.first, W.n, DD.dec, DD.chars, tfirst.data(), tcount.data(), o.track_members->data(),
+                                                        o.track_members->size(), tfirst.size(), EH, ED);
+                    rc != STR_ER_OK)
+                    return rc;
         }
         if (p.lattice && n_words > 0)          // unfolded rows of the runs and, behind them, the pieces
             launch_lattice_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, c->rs_split, TD.splits, rows[p.lattice_set], rows[p.lattice_set] + 65 * n_run, TD.first, TD.n_of, TD.slot,
@@ -281,6 +291,7 @@ struct ReadCall {
             HIP_TRY(c, down(o.decode_chars->data(), DD.chars, 64 * n_words));
             HIP_TRY(c, down(o.decode_src->data(), DD.src, 64 * n_words));
         }
+        if (p.tdecode && !tfirst.empty()) HIP_TRY(c, down(c->td_tab.h() + EH.o_out, c->td_tab.d() + EH.o_out, EH.down_bytes));
         if (p.split && n_words > 0) HIP_TRY(c, down(c->rs_tab.h() + SH.o_out, c->rs_tab.d() + SH.o_out, SH.down_tables));          // (into page-locked memory: compacted below)
         if (p.lattice && n_words > 0) HIP_TRY(c, down(c->ld_tab.h() + LH.o_dec, c->ld_tab.d() + LH.o_dec, LH.down_bytes));
         if (p.lmatch && n_words > 0) HIP_TRY(c, down(c->lm_tab.h() + MH.o_matches, c->lm_tab.d() + MH.o_matches, MH.down_bytes));
@@ -300,6 +311,11 @@ struct ReadCall {
             lt_compact(GH, pslot, n_pslots, o.lattice_track_members->data(), o.lattice_track_parts->data(), &total);
             std::memcpy(o.lattice_track_matches->data(), GH.matches, sizeof(str_er_track_match) * tfirst.size());
             std::memcpy(o.lattice_track_src->data(), GH.src, 32 * o.track_members->size());
+        }
+        if (p.tdecode && !tfirst.empty()) {
+            std::memcpy(o.track_decodes->data(), EH.out, sizeof(str_er_track_decode) * tfirst.size());
+            std::memcpy(o.track_decode_chars->data(), EH.chars, 32 * tfirst.size());
+            if (!o.track_members->empty()) std::memcpy(o.track_decode_member_costs->data(), EH.member_cost, 4 * o.track_members->size());
         }
         if (p.lattice && n_words > 0) {          // the records with their first parts, the parts compacted, the strings as they are
             uint64_t total = 0;
@@ -334,8 +350,8 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     static const ReadChainOut none{};
     const ReadChainOut       &o = chain && reads ? *chain : none;
     const size_t              n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0;
-    const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.tracks != nullptr, c->lex.fold != 0,
-                                   o.lattice_matches != nullptr, o.lattice_track_matches != nullptr);
+    const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.track_matches != nullptr, c->lex.fold != 0,
+                                   o.lattice_matches != nullptr, o.lattice_track_matches != nullptr, o.track_decodes != nullptr);
     if (reads) reads->assign(n_run, str_er_run_read{});
     q.assign(1800 * n_run, 0);
     if (pieces) {

@@ -173,19 +173,19 @@ try {
 
 const str_er_word_link *str_er_result_word_links(const str_er_result *r, int32_t *n)
 {
-    return result_table(r, r && r->have_track_read, &str_er_result::word_links, n);
+    return result_table(r, r && r->have_word_tracks, &str_er_result::word_links, n);
 }
 const str_er_word_track *str_er_result_word_tracks(const str_er_result *r, int32_t *n)
 {
-    return result_table(r, r && r->have_track_read, &str_er_result::word_tracks, n);
+    return result_table(r, r && r->have_word_tracks, &str_er_result::word_tracks, n);
 }
 const int32_t *str_er_result_word_track_members(const str_er_result *r, int32_t *n)
 {
-    return result_table(r, r && r->have_track_read, &str_er_result::word_track_members, n);
+    return result_table(r, r && r->have_word_tracks, &str_er_result::word_track_members, n);
 }
 const int32_t *str_er_result_word_track_of_words(const str_er_result *r, int32_t *n)
 {
-    return result_table(r, r && r->have_track_read, &str_er_result::word_track_of_words, n);
+    return result_table(r, r && r->have_word_tracks, &str_er_result::word_track_of_words, n);
 }
 const str_er_track_match *str_er_result_track_matches(const str_er_result *r, int32_t *n)
 {

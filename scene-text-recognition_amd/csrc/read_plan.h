@@ -12,7 +12,7 @@ namespace str_er_host {
 enum { SET_A = 0, SET_U = 1, SET_NONE = -1 };
 
 struct ReadPlan {
-    bool match, decode, split, lattice, track;        // the flags as they count: track only with match, lattice only with split
+    bool match, decode, split, lattice, track;        // the flags as they count: track only with match, lattice only with split (tdecode, below, only with decode)
     bool lmatch;           // ... and the lattice match only with split and match
     bool ltrack;           // ... and the lattice track match only with the lattice match and the track match
     bool rows[2];          // a k_run_costs launch into the set ([SET_U]: only where U is a set of its own)
@@ -24,10 +24,11 @@ struct ReadPlan {
     int  result_set;       // the set run_costs and piece_costs come from (SET_NONE: the call returns no rows)
     int  split_down;       // the set of the last k_split_words (SET_NONE: none)
     bool run_probs;
+    bool tdecode;          // the track decode: only with decode; it reads the decoder's window (decode_set, with split its part rows)
     bool any() const { return match || decode || split; }      // some consumer reads the words and the class probabilities
 };
 
-inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, bool track, bool fold, bool lmatch = false, bool ltrack = false)
+inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, bool track, bool fold, bool lmatch = false, bool ltrack = false, bool tdecode = false)
 {
     ReadPlan p{};
     p.match = match; p.decode = decode; p.split = split; p.lattice = lattice && split; p.track = track && match;
@@ -46,6 +47,7 @@ inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, boo
     p.result_set = p.match ? SET_A : u;
     p.split_down = p.parts[SET_U] ? SET_U : p.parts[SET_A] ? SET_A : SET_NONE;
     p.run_probs = p.match || p.decode;
+    p.tdecode = tdecode && p.decode;
     return p;
 }
 

@@ -30,6 +30,16 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
     const uint32_t sup = STR_ER_GROUP_INNER_SUP | STR_ER_GROUP_OVERLAP_SUP;
     struct Rule { bool bad; int code; const char *msg; };
     const Rule rules[] = {
+        // STR_ER_WANT_TRACK_DECODE rides on STR_ER_WANT_LINE_LINKS (the text tracks) and on STR_ER_WANT_WORD_DECODE (the rows, the seeds'
+        // strings and the table), and through the latter on STR_ER_WANT_RUN_READ: refused without either and where either is refused,
+        // first of all, so that the refusal names this flag (the table rule stays the decoder's, below); it needs neither
+        // STR_ER_WANT_WORD_MATCH nor a lexicon; a call without the flag meets no new rule
+        {k.strip && any(STR_ER_WANT_TRACK_DECODE), STR_ER_EINVAL, "STR_ER_WANT_TRACK_DECODE is not supported by the strip path (str_er_strip_merge)"},
+        {!k.frames && any(STR_ER_WANT_TRACK_DECODE), STR_ER_EINVAL, "STR_ER_WANT_TRACK_DECODE needs frames (not the per-plane calls)"},
+        {any(STR_ER_WANT_TRACK_DECODE) && !any(STR_ER_WANT_LINE_LINKS), STR_ER_EINVAL, "STR_ER_WANT_TRACK_DECODE needs STR_ER_WANT_LINE_LINKS"},
+        {any(STR_ER_WANT_TRACK_DECODE) && !any(STR_ER_WANT_WORD_DECODE), STR_ER_EINVAL, "STR_ER_WANT_TRACK_DECODE needs STR_ER_WANT_WORD_DECODE"},
+        {any(STR_ER_WANT_TRACK_DECODE) && !any(STR_ER_WANT_RUN_READ), STR_ER_EINVAL,
+         "STR_ER_WANT_TRACK_DECODE needs STR_ER_WANT_RUN_READ (through STR_ER_WANT_WORD_DECODE)"},
         // STR_ER_WANT_LATTICE_TRACK rides on STR_ER_WANT_TRACK_READ (the word tracks) and on STR_ER_WANT_LATTICE_MATCH (the lattices, the
         // rows and the lexicon), and through them on STR_ER_WANT_RUN_SPLIT, _WORD_MATCH, _LINE_LINKS and _RUN_READ: refused without any
         // of them and where they are refused, first of all, so that the refusal names this flag (the lexicon rule stays the matcher's,

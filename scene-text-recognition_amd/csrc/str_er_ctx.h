@@ -188,6 +188,11 @@ struct str_er_result {
     std::vector<uint8_t> lattice_track_src;
     std::vector<str_er_split_part> lattice_track_parts;
     bool have_lattice_track = false;
+    bool have_word_tracks = false;                // the word links and word tracks above are made: STR_ER_WANT_TRACK_READ or STR_ER_WANT_TRACK_DECODE
+    std::vector<str_er_track_decode> track_decodes; // STR_ER_WANT_TRACK_DECODE: one record and 32 label bytes per word track, one cost per slot of the member array
+    std::vector<uint8_t> track_decode_chars;
+    std::vector<int32_t> track_decode_member_costs;
+    bool have_track_decodes = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -324,6 +329,9 @@ struct str_er_ctx {
     bool     bigram_set = false;
     int32_t  wd_ins = 0, wd_del = 0;
     PairBuf  wd_tab;                  // (str_er_decode_words: cost rows | first run, run count per word) | records | labels | sources
+    // STR_ER_WANT_TRACK_DECODE / str_er_decode_tracks (str_er_set_track_decode)
+    int32_t  td_ins = 64, td_del = 64, td_rounds = 8;
+    PairBuf  td_tab;                  // (str_er_decode_tracks: cost rows | first run, run count per word | the decoder's records, labels, sources) | first member, member count per track | members | records | labels | member costs
     // str_er_feet_split / str_er_split_words (str_er_set_run_split)
     int32_t  rs_num = 1, rs_den = 4, rs_split = 8;
     PairBuf  rs_out;                  // a record per run slot of k_run_cuts
@@ -625,6 +633,7 @@ struct LineStageWants {
     bool lattice = false;     // STR_ER_WANT_LATTICE_DECODE: every word over its piece lattice under the bigram table (k_lattice_decode behind the scorer, on what k_split_words reads)
     bool lmatch = false;      // STR_ER_WANT_LATTICE_MATCH: every word against the lexicon over its piece lattice (k_lattice_match behind k_split_words on the matcher's rows)
     bool ltrack = false;      // STR_ER_WANT_LATTICE_TRACK: every word track against the lexicon over its members' piece lattices (k_lattice_track_match behind k_lattice_match)
+    bool tdecode = false;     // STR_ER_WANT_TRACK_DECODE: the word links and word tracks on the host before the reading (as for track), k_track_decode behind the decoder
     bool split = false;       // STR_ER_WANT_RUN_SPLIT: the cuts of every run (k_run_cuts behind k_foot_words, down with the stage's wait), the pieces read with the runs, k_split_words behind the scorer
 };
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
@@ -686,6 +695,9 @@ struct ReadChainOut {
     // STR_ER_WANT_LATTICE_TRACK (with the lattice match and the track match): the word tracks over their members' piece lattices
     std::vector<str_er_track_match> *lattice_track_matches = nullptr; std::vector<str_er_lattice_track_member> *lattice_track_members = nullptr;
     std::vector<uint8_t> *lattice_track_src = nullptr; std::vector<str_er_split_part> *lattice_track_parts = nullptr;
+    // STR_ER_WANT_TRACK_DECODE (with decode): the track decode of the word tracks the host made before the call (tracks, track_members: above)
+    std::vector<str_er_track_decode> *track_decodes = nullptr; std::vector<uint8_t> *track_decode_chars = nullptr;
+    std::vector<int32_t> *track_decode_member_costs = nullptr;
     void preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k) const;      // every table of the plan as a call without runs leaves it (k: the model's classes)
 };
 // carving a table buffer: take(bytes) is the offset of the next piece, and the one after it starts at the next multiple of 256
@@ -780,6 +792,20 @@ TmTab tm_layout(uint8_t *base, size_t n_tracks, size_t n_members, int n_chunks);
 // preset to -1; D receives the device side of the layout (matches and member_cost come down from there)
 int track_match_enqueue(str_er_ctx *c, hipStream_t s, const uint8_t *d_rows, const int32_t *d_first, const int32_t *d_n_of, const int32_t *track_first,
                         const int32_t *track_count, const int32_t *members, size_t n_members, size_t n_tracks, TmTab &D);
+// ---- defined in api_track_decode.cpp
+// the layout of c->td_tab from byte `at` on (the inputs' bytes) for n_tracks tracks over a member array of n_members
+struct TdTab {
+    int32_t *first, *count, *members; str_er_track_decode *out; uint8_t *chars; int32_t *member_cost;
+    size_t o_up, up_bytes;                // first | count | members lie back to back: one copy up
+    size_t o_out, down_bytes, bytes;      // out | chars | member_cost lie back to back (each aligned): one copy down
+};
+TdTab td_layout(uint8_t *base, size_t at, size_t n_tracks, size_t n_members);
+// the track tables into c->td_tab (from byte `at` on) and up on s, k_track_decode behind what is on s (rows, first, n_of and the
+// decoder's records and labels for these rows: on the device), the member costs preset to -1; H and D receive the two sides of the
+// layout (what comes down: H.o_out, H.down_bytes)
+int track_decode_enqueue(str_er_ctx *c, hipStream_t s, size_t at, const uint8_t *d_rows, const int32_t *d_first, const int32_t *d_n_of, const void *d_dec,
+                         const uint8_t *d_dchars, const int32_t *track_first, const int32_t *track_count, const int32_t *members, size_t n_members, size_t n_tracks,
+                         TdTab &H, TdTab &D);
 // ---- defined in api_word_match.cpp
 // the layout of what the matcher leaves in c->wm_tab from byte `at` on (the inputs' bytes) for n_words words: chunk keys | matches
 struct WmTab {

@@ -683,6 +683,57 @@ public:
         return e >= 0 && (size_t)e < lexicon.size() ? lexicon[(size_t)e] : word_text(lw, rd, (size_t)tr.tracks.at(g).rep);
     }
 
+    // Every word track decoded without a lexicon: the median string of its members under the bigram table, from the members' own decoder
+    // strings by single edits (STR_ER_WANT_TRACK_DECODE; the contract is at str_er_track_decode in include/str_er.h): one record and 32
+    // label bytes per word track (0xFF past n_chars), one cost per slot of the member array.  The links and tracks come with the flag:
+    // track_read(r) fills them (its matches stay empty without STR_ER_WANT_TRACK_READ).  Needs STR_ER_WANT_LINE_LINKS, STR_ER_WANT_WORD_DECODE
+    // and a table in the context; no lexicon.
+    struct TrackDecodes {
+        std::vector<str_er_track_decode> decodes;
+        std::vector<uint8_t>             chars;
+        std::vector<int32_t>             member_costs;
+    };
+    // ... copied out of the result of a call with the flag (all empty without it)
+    static TrackDecodes track_decodes(const str_er_result *r)
+    {
+        TrackDecodes out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_track_decode *p = str_er_result_track_decodes(r, &n)) out.decodes.assign(p, p + n);
+        if (const uint8_t *p = str_er_result_track_decode_chars(r, &nb)) out.chars.assign(p, p + nb);
+        if (const int32_t *p = str_er_result_track_decode_member_costs(r, &n)) out.member_costs.assign(p, p + n);
+        return out;
+    }
+    // INS and DEL (1 .. 255) and the polish rounds (0 .. 64) of the track decode (str_er_set_track_decode; 64, 64 and 8 by default)
+    void set_track_decode(int32_t ins, int32_t del, int32_t rounds) { check(str_er_set_track_decode(ctx_.get(), ins, del, rounds)); }
+    // the tracks members[track_first[g] .. track_first[g] + track_count[g]) of the words of the caller's cost rows under the table
+    // (str_er_decode_tracks)
+    TrackDecodes decode_tracks(const std::vector<uint8_t> &costs, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs,
+                               const std::vector<int32_t> &track_first, const std::vector<int32_t> &track_count, const std::vector<int32_t> &members)
+    {
+        if (first_run.size() != n_runs.size() || track_first.size() != track_count.size() || costs.size() % 65)
+            throw std::invalid_argument("decode_tracks: 65 bytes a run, one span a word, one span a track");
+        TrackDecodes out;
+        out.decodes.resize(track_first.size());
+        out.chars.resize(32 * track_first.size());
+        out.member_costs.assign(members.size(), -1);
+        check(str_er_decode_tracks(ctx_.get(), costs.empty() ? nullptr : costs.data(), (int32_t)(costs.size() / 65), first_run.empty() ? nullptr : first_run.data(),
+                                   n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(), track_first.empty() ? nullptr : track_first.data(),
+                                   track_count.empty() ? nullptr : track_count.data(), members.empty() ? nullptr : members.data(), (int32_t)members.size(),
+                                   (int32_t)track_first.size(), out.decodes.empty() ? nullptr : out.decodes.data(), out.chars.empty() ? nullptr : out.chars.data(),
+                                   out.member_costs.empty() ? nullptr : out.member_costs.data()));
+        return out;
+    }
+    // the string word track g was decoded to: its representative's own reading where the track was not decoded (no seed)
+    static std::string word_track_decode_text(const LineWords &lw, const RunReads &rd, const TrackRead &tr, const TrackDecodes &td, size_t g)
+    {
+        const str_er_track_decode &d = td.decodes.at(g);
+        if (d.cost < 0) return word_text(lw, rd, (size_t)tr.tracks.at(g).rep);
+        std::string s;
+        for (int32_t k = 0; k < d.n_chars; ++k) s += (char)str_er_ocr_char(td.chars.at(32 * g + (size_t)k));
+        return s;
+    }
+
     // Every word decoded under a character bigram table (STR_ER_WANT_WORD_DECODE; the contract is at str_er_word_decode in
     // include/str_er.h): one record per word of LineWords::words, 64 label bytes and 64 source bytes per word (0xFF past n_chars), and
     // the cost bytes and class probabilities of the runs as in WordMatches.  Needs STR_ER_WANT_RUN_READ and a table in the context.
