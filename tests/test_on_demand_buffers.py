@@ -1,6 +1,7 @@
 """The on-demand buffers of a context (masks, crops, maps, footprints, link and geometry tables) grow and are reused: one context
 runs the single-stage calls on a small plane, on a large one and on the small one again.  Every output is compared with the reference
-its own test module uses, the third round equals the first byte for byte, and none of it shows in workspace_bytes()."""
+its own test module uses, the third round equals the first byte for byte, and none of it shows in workspace_bytes().
+The buffers behind feet_geom -- those of the reading chain, feet_words to decode_tracks and the track pools -- are test_read_chain_reuse.py's."""
 import numpy as np
 import pytest
 
