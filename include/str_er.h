@@ -622,8 +622,10 @@ typedef struct str_er_track_match {
  *   A slot holds at most 65536 members (STR_ER_ECAPACITY above), the bound under which the int32 sums are safe.
  *   Limits: member_cost, best_member and the members' segmentations are not pooled -- the winning entry can change with every
  *     addition, and the members' rows are not kept; str_er_match_tracks / str_er_lattice_match_tracks give them for the members of
- *     one call.  There is no pooled open-vocabulary decode across calls: str_er_track_decode (STR_ER_WANT_TRACK_DECODE) decodes the
- *     word tracks of one call.  The pool must be destroyed before its context.                                                    */
+ *     one call.  There is no pooled open-vocabulary decode across calls in a pool of this kind: str_er_track_decode
+ *     (STR_ER_WANT_TRACK_DECODE) decodes the word tracks of one call, and a pool of another kind, the decode pool
+ *     (str_er_pool_decode, below), keeps the newest members of a track on the device and decodes them.  The pool must be destroyed
+ *     before its context.                                                                                                          */
 #define STR_ER_POOL_LATTICE 1u
 typedef struct str_er_track_pool str_er_track_pool;
 typedef struct str_er_pool_match {
@@ -632,6 +634,41 @@ typedef struct str_er_pool_match {
     int32_t  free_cost, n_tried;          /* 16, 20                                   */
     int32_t  n_used, n_members;           /* 24, 28                                   */
 } str_er_pool_match;         /* 32 bytes; one per slot read                           */
+
+/* The decode pool: the track decode of str_er_track_decode pooled across calls.  It is a str_er_track_pool of another kind, made by
+ * str_er_track_pool_create_decode with cap_tracks slots and a per-slot limit keep, 1 .. 1024 (the member bound of the track decode);
+ * _info reports the flag STR_ER_POOL_DECODE and n_entries = 0.  The score J(s) = lm(s) + the sum of A_i(s) has to be evaluable for
+ * strings nobody has seen yet, so there is no sum to keep: the members' cost rows themselves stay on the device.
+ *   Binding: at creation and at every _reset the pool is bound to the context's bigram table, to the INS / DEL of
+ *     str_er_set_word_decode (they make the seeds' strings when a member is added) and to the INS / DEL / rounds of
+ *     str_er_set_track_decode (a read uses them).  str_er_set_bigram, str_er_set_word_decode and str_er_set_track_decode make every
+ *     decode pool of the context stale -- and no lexicon pool; str_er_set_lexicon, str_er_set_word_match and str_er_set_run_split
+ *     make every lexicon pool stale -- and no decode pool.  A stale pool answers STR_ER_ESTATE to everything except _reset, _info
+ *     and _destroy.  A decode pool needs no lexicon and no SVM model; without a bigram table its creation answers STR_ER_ESTATE.
+ *   Keys: every successful _add with n_tracks > 0 takes the next serial of the pool, 1, 2, ... (uint32, back to 0 at _reset).  The
+ *     key of a member is serial << 32 | its index in that call's member array.  Keys are unique in a pool: "newer" is a total order.
+ *   State of a slot: n_members counts everything ever added to the slot or joined into it, the unusable members (more than 32 rows)
+ *     included, under the pool's bound of 65536 (STR_ER_ECAPACITY).  The kept list is the `keep` largest keys among all usable
+ *     members ever added to the slot or to slots joined into it; per kept member the slot stores its key, its run count, its up to
+ *     32 rows of 65 bytes (unfolded, the rows of str_er_word_decode), its str_er_word_decode record and its 64 string bytes as the
+ *     decoder made them on those rows.  An unusable member is counted and not kept.  The top-keep of a union is the top-keep of the
+ *     union of top-keeps: the kept list does not depend on how joins were grouped.
+ *   Defining property: _read_decode of a slot gives a record, 32 label bytes and member costs in age order that equal what
+ *     str_er_decode_tracks_host gives for one track whose member list is the kept list in ascending key order, the words numbered
+ *     0 .. n_kept - 1 in that order, under the table and parameters the pool is bound to.  seed_member is therefore an age rank.
+ *     Age order matters: the seeds are the first 32 in order, and ties go to the seed rank.  n_members and n_kept follow the eight
+ *     fields of str_er_track_decode.  An empty slot reads as a track of no members: -1, -1, 0, 0, 0, 0, -1, -1, n_members = n_kept
+ *     = 0, labels 0xFF, no member costs.
+ *   Limits: a slot's reading uses at most keep members, the newest; evicted evidence is gone -- this is not a sum over all members
+ *     ever seen.  There is no lattice mode.  A read decodes what it is asked for every time: there is no cache of clean slots.      */
+#define STR_ER_POOL_DECODE 2u
+typedef struct str_er_pool_decode {
+    int32_t  cost, seed_cost;             /*  0,  4                                   */
+    int32_t  n_chars, n_edits;            /*  8, 12                                   */
+    int32_t  converged, n_used;           /* 16, 20                                   */
+    int32_t  seed_member, lm_cost;        /* 24, 28: seed_member is an age rank       */
+    int32_t  n_members, n_kept;           /* 32, 36                                   */
+} str_er_pool_decode;        /* 40 bytes; one per slot read                           */
 
 /* The decoding of a word under a character bigram table (STR_ER_WANT_WORD_DECODE, str_er_decode_words): the cheapest character string
  * of a word under the cost rows of its glyph runs plus a table of costs of one character after another, which may drop a run (a speck)
@@ -702,7 +739,8 @@ typedef struct str_er_word_decode {
  *     and for a track of one usable member decoded with the decoder's INS = DEL = 0, seed_cost <= that word's str_er_word_decode
  *     cost (the diagonal alignment is one of the alignments).
  *   Limits: this is a local optimum of single edits from the set median, not the global median string.  The members enter with the
- *     rows the decoder read; a joint search over the members' piece lattices is not part of it.  Nothing is pooled across calls.
+ *     rows the decoder read; a joint search over the members' piece lattices is not part of it.  Nothing is pooled across calls by this output: a decode
+ *     pool (str_er_pool_decode) keeps the newest members of a track on the device and decodes them, call after call.
  *     Whether the polish helps on real text has not been measured, and nothing here is tuned on labelled data.                      */
 typedef struct str_er_track_decode {
     int32_t  cost, seed_cost;             /*  0,  4                                   */
@@ -1427,6 +1465,24 @@ int str_er_track_pool_join(str_er_track_pool *pool, int32_t dst, const int32_t *
 int str_er_track_pool_clear(str_er_track_pool *pool, const int32_t *slots, int32_t n);
 /* out receives n records, out[i] of the slot slots[i]; a slot may be named more than once.                                          */
 int str_er_track_pool_read(str_er_track_pool *pool, const int32_t *slots, int32_t n, str_er_pool_match *out);
+
+/* The decode pool (str_er_pool_decode).  _destroy, _reset, _info, _add, _join and _clear above work on it as on a lexicon pool: _add
+ * takes the unfolded 65-byte rows of str_er_word_decode with the arguments and checks it has, a join leaves in dst the keep newest
+ * of the union and the srcs empty.  _add_lattice and _read on a decode pool and _read_decode and _members on a lexicon pool answer
+ * STR_ER_ESTATE.
+ * _create_decode: cap_tracks >= 1 empty slots of 1 <= keep <= 1024 kept members each (else STR_ER_EINVAL); STR_ER_ESTATE without a
+ * bigram table; STR_ER_ECAPACITY where cap_tracks * keep passes 2^24 (a kept member takes about 2.2 KB on the device),
+ * STR_ER_ENOMEM where the device does not have the memory.                                                                          */
+int str_er_track_pool_create_decode(str_er_ctx *ctx, int32_t cap_tracks, int32_t keep, str_er_track_pool **pool);
+/* The per-slot limit of a decode pool (0 for a lexicon pool).  Works on a stale pool.                                                */
+int str_er_track_pool_keep(const str_er_track_pool *pool, int32_t *keep);
+/* out receives n records, out[i] of the slot slots[i], chars 32 label bytes a slot and member_cost keep values a slot: the kept
+ * members' costs in age order, -1 past n_kept.  A slot may be named more than once.                                                 */
+int str_er_track_pool_read_decode(str_er_track_pool *pool, const int32_t *slots, int32_t n, str_er_pool_decode *out, uint8_t *chars, int32_t *member_cost);
+/* The kept list of one slot in age order: *n_kept members with their keys, run counts and rows (keep * 32 * 65 bytes, 32 rows a
+ * member, of which the first n_runs are the member's).  Any of keys, n_runs and rows may be NULL.  For callers who want the evidence
+ * back, e.g. to read it again over lattices.                                                                                        */
+int str_er_track_pool_members(str_er_track_pool *pool, int32_t slot, uint64_t *keys, int32_t *n_runs, uint8_t *rows, int32_t *n_kept);
 
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:

@@ -125,6 +125,11 @@ POOL_MATCH_DTYPE = np.dtype([("entry", "<i4"), ("cost", "<i4"), ("second_entry",
                              ("n_used", "<i4"), ("n_members", "<i4")])
 POOL_LATTICE = 1
 assert POOL_MATCH_DTYPE.itemsize == 32
+# str_er_pool_decode: the fields of TRACK_DECODE_DTYPE (seed_member: an age rank), then the members ever added and the members kept
+POOL_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("seed_cost", "<i4"), ("n_chars", "<i4"), ("n_edits", "<i4"), ("converged", "<i4"), ("n_used", "<i4"),
+                              ("seed_member", "<i4"), ("lm_cost", "<i4"), ("n_members", "<i4"), ("n_kept", "<i4")])
+POOL_DECODE = 2
+assert POOL_DECODE_DTYPE.itemsize == 40
 # str_er_word_decode: per word, the cost of the cheapest string (-1: more than 32 runs, not decoded) and of the plain reading, the
 # characters of the string and the runs read, dropped and the characters inserted
 WORD_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
@@ -480,6 +485,10 @@ def load_library():
     L.str_er_track_pool_join.argtypes = [vp, C.c_int32, vp, C.c_int32]
     L.str_er_track_pool_clear.argtypes = [vp, vp, C.c_int32]
     L.str_er_track_pool_read.argtypes = [vp, vp, C.c_int32, vp]
+    L.str_er_track_pool_create_decode.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.str_er_track_pool_keep.argtypes = [vp, i32p]
+    L.str_er_track_pool_read_decode.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
+    L.str_er_track_pool_members.argtypes = [vp, C.c_int32, vp, vp, vp, i32p]
     L.str_er_lattice_match_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, i32p]
     L.str_er_lattice_match_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_int32, vp, vp, vp, C.c_int32, i32p]
@@ -2909,8 +2918,61 @@ class TrackPool:
         slots in use and whether it is stale."""
         cap, fl, n, by, use, st = C.c_int32(), C.c_uint32(), C.c_int32(), C.c_uint64(), C.c_int32(), C.c_int32()
         self._check(self.L.str_er_track_pool_info(self.h, C.byref(cap), C.byref(fl), C.byref(n), C.byref(by), C.byref(use), C.byref(st)))
-        return {"cap_tracks": int(cap.value), "lattice": bool(fl.value & POOL_LATTICE), "n_entries": int(n.value), "device_bytes": int(by.value),
+        return {"cap_tracks": int(cap.value), "lattice": bool(fl.value & POOL_LATTICE), "decode": bool(fl.value & POOL_DECODE), "n_entries": int(n.value), "device_bytes": int(by.value),
                 "in_use": int(use.value), "stale": bool(st.value)}
+
+
+class DecodePool(TrackPool):
+    """str_er_track_pool_create_decode: cap_tracks pooled word tracks on the device of the ERFilter f without a lexicon
+    (str_er_pool_decode): per slot the newest `keep` usable members added to it, their cost rows and decoder strings, kept from call
+    to call; read() decodes a slot as ERFilter.decode_tracks decodes the track of its kept members in age order.  Bound to f's
+    set_bigram, set_word_decode and set_track_decode as they are at creation: after one of those setters every call raises
+    STR_ER_ESTATE until reset().  add, join, clear, reset and close are TrackPool's.  Close it before f."""
+
+    def __init__(self, f: "ERFilter", cap_tracks: int, keep: int = 32):
+        self.f, self.L, self.lattice = f, f.L, False
+        h = C.c_void_p()
+        f._check(self.L.str_er_track_pool_create_decode(f.h, int(cap_tracks), int(keep), C.byref(h)))
+        self.h = h
+        self.cap_tracks, self.keep = int(cap_tracks), int(keep)
+
+    def add_lattice(self, *args, **kw) -> None:
+        raise StrErError(-3, "a decode pool has no lattice mode")
+
+    def read(self, slots):
+        """str_er_track_pool_read_decode: (POOL_DECODE_DTYPE per slot named, (n, 32) uint8 labels, (n, keep) int32 member costs in
+        age order, -1 past n_kept); a slot may be named more than once."""
+        sl = self._slots(slots)
+        n = len(sl)
+        out = np.zeros(max(1, n), POOL_DECODE_DTYPE)
+        ch = np.full((max(1, n), 32), 0xFF, np.uint8)
+        mc = np.full((max(1, n), self.keep), -1, np.int32)
+        self._check(self.L.str_er_track_pool_read_decode(self.h, _np_ptr(sl) if n else None, n, _np_ptr(out), _np_ptr(ch), _np_ptr(mc)))
+        return out[:n], ch[:n], mc[:n]
+
+    def members(self, slot: int):
+        """str_er_track_pool_members: the kept list of a slot in age order: (uint64 keys, int32 run counts, (n_kept, 32, 65) uint8
+        rows, of which the first n_runs of a member are its own)."""
+        keys, nr, rows, n = np.zeros(self.keep, np.uint64), np.zeros(self.keep, np.int32), np.zeros((self.keep, 32, 65), np.uint8), C.c_int32()
+        self._check(self.L.str_er_track_pool_members(self.h, int(slot), _np_ptr(keys), _np_ptr(nr), _np_ptr(rows), C.byref(n)))
+        return keys[:n.value], nr[:n.value], rows[:n.value]
+
+    def text(self, slot: int):
+        """The string of the slot's pooled decode, None where nothing was decoded."""
+        rec, ch, _ = self.read([slot])
+        return _decode_text(rec[0], ch[0])
+
+    def info(self) -> dict:
+        """str_er_track_pool_info and _keep: the slots, keep, its bytes on the device, the slots in use and whether it is stale."""
+        d = TrackPool.info(self)
+        k = C.c_int32()
+        self._check(self.L.str_er_track_pool_keep(self.h, C.byref(k)))
+        d.update(decode=True, keep=int(k.value))
+        return d
+
+
+def _decode_text(rec, chars):
+    return "".join(_OCR_ALPHABET[int(a)] for a in chars[:int(rec["n_chars"])]) if int(rec["cost"]) >= 0 else None
 
 
 class WordTracker:
@@ -2924,16 +2986,29 @@ class WordTracker:
     own call and on lines whose persistent text ids are the same after TextTracker.update, are linked iff their boxes share pixels and
     inter * den >= num * (area(u) + area(v) - inter), the rule of str_er_word_link at linker's set_word_link threshold.  Linked ids
     are joined, the smaller id stays, and their slots are joined.  A pooled track without a member in the result's last frame cannot
-    be extended: its final record goes to `closed` as (id, record) and its slot is freed."""
+    be extended: its final record goes to `closed` as (id, record) and its slot is freed.
+      Without a lexicon: decode_pool, a DecodePool on `linker`, takes the place of `pool` or stands beside it (at least one of the two;
+    both get the same slot numbers, joins and clears, and the smaller capacity counts).  The results then need want_track_decode
+    (with want_word_decode) instead of, or beside, want_word_match and want_track_read; the decode pool is fed the unfolded rows of
+    the words, so a result whose run_costs a folding lexicon folded is refused with ValueError before either pool is touched.
+    read_decode / decode_text give the pooled decode of an id, and a closed track's final one goes to `closed_decodes` as
+    (id, record, chars)."""
 
-    def __init__(self, linker: "ERFilter", pool: TrackPool):
-        self.linker, self.pool = linker, pool
+    def __init__(self, linker: "ERFilter", pool: Optional[TrackPool] = None, decode_pool: Optional["DecodePool"] = None):
+        if pool is None and decode_pool is None:
+            raise ValueError("WordTracker: a TrackPool, a DecodePool or both")
+        if isinstance(pool, DecodePool) or (decode_pool is not None and not isinstance(decode_pool, DecodePool)):
+            raise ValueError("WordTracker: pool is a TrackPool and decode_pool a DecodePool")
+        self.linker, self.pool, self.decode_pool = linker, pool, decode_pool
         self.lines = TextTracker(linker)
         self.closed = []
+        self.closed_decodes = []
         self._parent = []            # union-find over the ids handed out; the root is the smallest
         self._slot = {}              # root id of a live track -> its slot
-        self._free = list(range(pool.cap_tracks - 1, -1, -1))      # (pop() hands out the smallest)
+        cap = min(p.cap_tracks for p in (pool, decode_pool) if p is not None)
+        self._free = list(range(cap - 1, -1, -1))      # (pop() hands out the smallest)
         self._final = {}             # id of a closed track -> its record
+        self._final_decode = {}      # id of a closed track -> (its decode record, its labels)
         self._prev = None            # (w, h, boxes (n, 4) int64, text ids, word track ids) of the eligible words of the last frame
 
     def _find(self, i: int) -> int:
@@ -2953,6 +3028,8 @@ class WordTracker:
 
     def read(self, ids) -> np.ndarray:
         """POOL_MATCH_DTYPE per id: the pooled record of a live track, the final record of a closed one."""
+        if self.pool is None:
+            raise ValueError("WordTracker.read: no lexicon pool (read_decode gives the pooled decode)")
         roots = self.resolve(ids)
         out = np.zeros(len(roots), POOL_MATCH_DTYPE)
         live = [k for k, r in enumerate(roots) if int(r) in self._slot]
@@ -2968,16 +3045,43 @@ class WordTracker:
         e = int(self.read([i])[0]["entry"])
         return self.linker._lexicon[e] if e >= 0 else None
 
+    def read_decode(self, ids):
+        """(POOL_DECODE_DTYPE per id, (n, 32) uint8 labels): the pooled decode of a live track, the final one of a closed track."""
+        if self.decode_pool is None:
+            raise ValueError("WordTracker.read_decode: no decode pool")
+        roots = self.resolve(ids)
+        out, ch = np.zeros(len(roots), POOL_DECODE_DTYPE), np.full((len(roots), 32), 0xFF, np.uint8)
+        live = [k for k, r in enumerate(roots) if int(r) in self._slot]
+        if live:
+            out[live], ch[live], _ = self.decode_pool.read([self._slot[int(roots[k])] for k in live])
+        for k, r in enumerate(roots):
+            if int(r) not in self._slot:
+                out[k], ch[k] = self._final_decode[int(r)]
+        return out, ch
+
+    def decode_text(self, i: int):
+        """The string of the track's pooled decode, None where nothing was decoded."""
+        rec, ch = self.read_decode([i])
+        return _decode_text(rec[0], ch[0])
+
     def _close(self, roots) -> None:
         roots = sorted(int(r) for r in roots)
         if not roots:
             return
         slots = [self._slot[r] for r in roots]
-        recs = self.pool.read(slots)
-        self.pool.clear(slots)
-        for r, s, rec in zip(roots, slots, recs):
-            self.closed.append((r, rec.copy()))
-            self._final[r] = rec.copy()
+        if self.pool is not None:
+            recs = self.pool.read(slots)
+            self.pool.clear(slots)
+            for r, rec in zip(roots, recs):
+                self.closed.append((r, rec.copy()))
+                self._final[r] = rec.copy()
+        if self.decode_pool is not None:
+            recs, chars, _ = self.decode_pool.read(slots)
+            self.decode_pool.clear(slots)
+            for r, rec, ch in zip(roots, recs, chars):
+                self.closed_decodes.append((r, rec.copy(), ch.copy()))
+                self._final_decode[r] = (rec.copy(), ch.copy())
+        for r, s in zip(roots, slots):
             del self._slot[r]
             self._free.append(s)
         self._free.sort(reverse=True)
@@ -2998,13 +3102,24 @@ class WordTracker:
         nt = len(tracks)
         if nt > len(self._free):
             raise StrErError(-7, "WordTracker: the pool has %d free slots, the result %d word tracks" % (len(self._free), nt))
+        if self.decode_pool is not None and res._word_matches is not None and self.linker.lexicon_info()["flags"] & LEXICON_FOLD_CASE:
+            raise ValueError("WordTracker: the result's run_costs are folded by the lexicon (want_word_match under fold_case); a decode pool "
+                             "takes the unfolded rows of the word decoder: set the lexicon with fold_case=False, or keep the two pools on separate calls")
         first, last = res.edge_feet(0), res.edge_feet(1)
         slots = self._free[::-1][:nt]          # (the smallest free slots; an addition that is refused leaves the tracker as it was)
         if nt:
-            if self.pool.lattice:
-                self.pool.add_lattice(res.run_splits, res.run_costs, res.piece_costs, words["first_run"], words["n_runs"], tracks["first"], tracks["count"], members, slots)
-            else:
-                self.pool.add(*self._rows(res), tracks["first"], tracks["count"], members, slots)
+            if self.pool is not None:
+                if self.pool.lattice:
+                    self.pool.add_lattice(res.run_splits, res.run_costs, res.piece_costs, words["first_run"], words["n_runs"], tracks["first"], tracks["count"], members, slots)
+                else:
+                    self.pool.add(*self._rows(res), tracks["first"], tracks["count"], members, slots)
+            if self.decode_pool is not None:
+                try:
+                    self.decode_pool.add(*self._rows(res), tracks["first"], tracks["count"], members, slots)
+                except Exception:
+                    if self.pool is not None:          # (the lexicon pool took the tracks already: it gives them back)
+                        self.pool.clear(slots)
+                    raise
             del self._free[-nt:]
         tids = self.lines.update(res)
         base = len(self._parent)
@@ -3038,7 +3153,9 @@ class WordTracker:
         for root, rs in comp.items():
             if len(rs) > 1:
                 srcs = [self._slot[r] for r in sorted(rs) if r != root]
-                self.pool.join(self._slot[root], srcs)
+                for p in (self.pool, self.decode_pool):
+                    if p is not None:
+                        p.join(self._slot[root], srcs)
                 for r in rs:
                     if r != root:
                         del self._slot[r]

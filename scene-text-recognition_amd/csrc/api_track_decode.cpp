@@ -72,6 +72,7 @@ try {
     if (!c) return STR_ER_EINVAL;
     if (!td::params_ok(ins, del, rounds)) return fail(c, STR_ER_EINVAL, "track decode: INS and DEL are in 1 .. 255, rounds in 0 .. 64");
     c->td_ins = ins; c->td_del = del; c->td_rounds = rounds;
+    ++c->decode_pool_gen;          // (a decode pool is bound to them: str_er_pool_decode)
     return STR_ER_OK;
 } ABI_GUARD(c)
 

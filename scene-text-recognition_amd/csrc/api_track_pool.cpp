@@ -2,27 +2,42 @@
 // rules are track_pool_rules.h: the checks of an addition's slots, of a join and of the member limit run from there on the host's mirror
 // of the slots' member counts, before anything is launched; the device side is track_pool_kernels.h on the matcher's lexicon.  The pool
 // owns its device memory in two on-demand buffers: the accumulator rows with the slots' state, and the tables of one call.
+//   A decode pool (str_er_track_pool_create_decode; the contract is at str_er_pool_decode) is the same object of another kind: the
+// rules are decode_pool_rules.h, the device side decode_pool_kernels.h in front of k_word_decode (an addition) and k_track_decode (a
+// read).  Its first buffer is the store of the kept members; the checks of the slots and of the member limit are the same.
 #include "str_er_ctx.h"
+#include "decode_pool_kernels.h"
+#include "decode_pool_rules.h"
+#include "track_decode_kernels.h"
 #include "track_pool_kernels.h"
 #include "track_pool_rules.h"
+#include "word_decode_kernels.h"
 
+namespace dp = str_er_dp;
 namespace rs = str_er_rs;
 namespace tp = str_er_tp;
 namespace tr = str_er_tr;
 
+static_assert(sizeof(str_er_pool_decode) == 40 && sizeof(str_er_word_decode) == 24 && dp::CELL_ROW_BYTES == DP_CELL_ROW_BYTES, "decode pool layout");
 static_assert(sizeof(str_er_pool_match) == 32 && sizeof(tp::SlotState) == 4 * TP_STATE_INTS, "track pool layout");
 
 struct str_er_track_pool {
     str_er_ctx *c = nullptr;
     int32_t     cap = 0;
     uint32_t    flags = 0;
-    uint64_t    gen = 0;            // c->pool_gen when the pool was bound
+    uint64_t    gen = 0;            // c->pool_gen (a decode pool: c->decode_pool_gen) when the pool was bound
     WmLexDev    lex{};              // what it is bound to: the lexicon on the device, INS / DEL / band, SPLIT
     WmParams    prm{};
     int32_t     split = 0, lex_n = 0;
     DevBuf      rows;               // cap accumulator rows | cap states
     PairBuf     tab;                // of one call: (the rows and words of an addition | its tracks, slots and members | the words' structure) or (slots | chunk keys | records)
     TpPoolDev   dev{};
+    // a decode pool (flags & STR_ER_POOL_DECODE): `rows` is the store of the kept members
+    int32_t     keep = 0;
+    uint32_t    serial = 0;         // of the last addition
+    DpPoolDev   store{};
+    const uint8_t *bigram = nullptr;        // what it is bound to: the table on the device, the decoder's INS / DEL, the track decode's INS / DEL / rounds
+    int32_t     wd_ins = 0, wd_del = 0, td_ins = 0, td_del = 0, td_rounds = 0;
     std::vector<int32_t> n_members; // the host's mirror of the slots' member counts
     std::vector<uint8_t> seen;      // scratch of the checks: cap zeroes
 };
@@ -51,10 +66,54 @@ int bind(str_er_track_pool *P)
     return STR_ER_OK;
 }
 
-bool stale(const str_er_track_pool *P) { return P->gen != P->c->pool_gen || !P->dev.acc; }
+bool is_decode(const str_er_track_pool *P) { return (P->flags & STR_ER_POOL_DECODE) != 0; }
+
+// the store of a decode pool: rows | keys | first rows | run counts | decoder records | labels of the cells, then the slots' counts
+DpPoolDev store_layout(uint8_t *base, int32_t cap, int32_t keep, size_t *bytes)
+{
+    const size_t n = (size_t)cap * (size_t)keep;
+    Carve        cv{};
+    const size_t o_rows = cv.take(n * DP_CELL_ROW_BYTES), o_key = cv.take(8 * n), o_first = cv.take(4 * n), o_n = cv.take(4 * n),
+                 o_dec = cv.take(sizeof(str_er_word_decode) * n), o_chars = cv.take(64 * n), o_mem = cv.take(4 * (size_t)cap);
+    if (bytes) *bytes = cv.off;
+    DpPoolDev D{};
+    D.cap = cap; D.keep = keep;
+    if (base) {
+        const auto i32 = [&](size_t o) { return reinterpret_cast<int32_t *>(base + o); };
+        D.costs = base + o_rows; D.key = reinterpret_cast<uint64_t *>(base + o_key); D.first_run = i32(o_first); D.n_of = i32(o_n); D.dec = i32(o_dec);
+        D.dchars = base + o_chars; D.n_members = i32(o_mem);
+    }
+    return D;
+}
+
+// the decode pool bound to the context as it is now, every slot empty
+int bind_decode(str_er_track_pool *P)
+{
+    str_er_ctx *c = P->c;
+    if (!c->bigram_set) return fail(c, STR_ER_ESTATE, "a decode pool needs a bigram table (str_er_set_bigram)");
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    size_t bytes = 0;
+    store_layout(nullptr, P->cap, P->keep, &bytes);
+    if (const int rc = P->rows.ensure(c, bytes, "decode pool store"); rc != STR_ER_OK) { P->store = DpPoolDev{}; return rc; }
+    const DpPoolDev D = store_layout(P->rows.d(), P->cap, P->keep, nullptr);
+    HIP_TRY(c, hipMemsetAsync(P->rows.d(), 0, bytes, c->stream));          // (the rows too: what str_er_track_pool_members hands out is the same bytes every run)
+    launch_dpool_reset(c->stream, D);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, wait_stream(c, c->stream));
+    P->store = D; P->bigram = c->bigram.d(); P->wd_ins = c->wd_ins; P->wd_del = c->wd_del; P->td_ins = c->td_ins; P->td_del = c->td_del; P->td_rounds = c->td_rounds;
+    P->gen = c->decode_pool_gen; P->serial = 0;
+    std::fill(P->n_members.begin(), P->n_members.end(), 0);
+    return STR_ER_OK;
+}
+
+bool stale(const str_er_track_pool *P) { return is_decode(P) ? P->gen != P->c->decode_pool_gen || !P->store.costs : P->gen != P->c->pool_gen || !P->dev.acc; }
 
 int usable(str_er_track_pool *P, bool lattice_call)
 {
+    if (is_decode(P)) {
+        if (stale(P)) return fail(P->c, STR_ER_ESTATE, "decode pool: the bigram table or the decode parameters changed since the pool was bound (str_er_track_pool_reset)");
+        return lattice_call ? fail(P->c, STR_ER_ESTATE, "str_er_track_pool_add_lattice on a decode pool") : STR_ER_OK;
+    }
     if (stale(P)) return fail(P->c, STR_ER_ESTATE, "track pool: the lexicon or the match parameters changed since the pool was bound (str_er_track_pool_reset)");
     if (lattice_call != ((P->flags & STR_ER_POOL_LATTICE) != 0))
         return fail(P->c, STR_ER_ESTATE, lattice_call ? "str_er_track_pool_add_lattice on a pool of rows" : "str_er_track_pool_add on a lattice pool");
@@ -83,10 +142,10 @@ AddTab add_layout(uint8_t *base, size_t at, size_t n_tracks, size_t n_members, s
     return t;
 }
 
-// the checks both additions share, then the upload of the rows and tables; I and D receive the device side
+// the checks the additions share, then the upload of the rows and tables; I and D receive the device side; `more`: bytes behind them
 int add_common(str_er_track_pool *P, const str_er_run_split *splits, const uint8_t *run_costs, size_t n_runs, const uint8_t *piece_costs, size_t n_pieces,
                const int32_t *first_run, const int32_t *n_of, int32_t n_words, const int32_t *track_first, const int32_t *track_count, const int32_t *members,
-               int32_t n_members, int32_t n_tracks, const int32_t *slots, RowsIn &I, AddTab &D)
+               int32_t n_members, int32_t n_tracks, const int32_t *slots, RowsIn &I, AddTab &D, size_t more = 0)
 {
     str_er_ctx *c = P->c;
     if (const int rc = tr::tracks_check(track_first, track_count, members, n_members, n_tracks, n_words); rc != STR_ER_OK)
@@ -98,7 +157,7 @@ int add_common(str_er_track_pool *P, const str_er_run_split *splits, const uint8
     const size_t nw = (size_t)n_words, nm = (size_t)n_members, nt = (size_t)n_tracks;
     if (n_runs + n_pieces > 0x7FFFFFFFull / 65 || nw > 0x7FFFFFFFull / (4 * (size_t)LT_TAB_INTS)) return fail(c, STR_ER_ECAPACITY, "track pool: too many rows or words");
     const size_t at = rows_in_layout(nullptr, splits ? n_runs : 0, n_runs + n_pieces, nw, false).bytes;
-    if (const int rc = P->tab.ensure(c, add_layout(nullptr, at, nt, nm, splits ? nw : 0).bytes, "track pool tables"); rc != STR_ER_OK) return rc;
+    if (const int rc = P->tab.ensure(c, add_layout(nullptr, at, nt, nm, splits ? nw : 0).bytes + more, "track pool tables"); rc != STR_ER_OK) return rc;
     hipStream_t s = c->stream;
     if (const int rc = rows_in_upload(c, s, P->tab, splits, run_costs, n_runs, piece_costs, n_pieces, first_run, n_of, nullptr, nw, I); rc != STR_ER_OK) return rc;
     const AddTab H = add_layout(P->tab.h(), at, nt, nm, splits ? nw : 0);
@@ -150,6 +209,31 @@ try {
     return STR_ER_OK;
 } ABI_GUARD(c)
 
+int str_er_track_pool_create_decode(str_er_ctx *c, int32_t cap_tracks, int32_t keep, str_er_track_pool **pool)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (!pool || !dp::create_ok(cap_tracks, keep)) return fail(c, STR_ER_EINVAL, "str_er_track_pool_create_decode: cap_tracks >= 1 and 1 <= keep <= 1024");
+    *pool = nullptr;
+    if (!dp::cells_fit(cap_tracks, keep)) return fail(c, STR_ER_ECAPACITY, "decode pool: more than 2^24 kept members");
+    str_er_track_pool *P = new str_er_track_pool;
+    P->c = c; P->cap = cap_tracks; P->flags = STR_ER_POOL_DECODE; P->keep = keep;
+    int rc = STR_ER_OK;
+    try {
+        P->n_members.assign((size_t)cap_tracks, 0); P->seen.assign((size_t)cap_tracks, 0);
+        rc = bind_decode(P);
+    } catch (...) { delete P; throw; }
+    if (rc != STR_ER_OK) { delete P; return rc; }
+    *pool = P;
+    return STR_ER_OK;
+} ABI_GUARD(c)
+
+int str_er_track_pool_keep(const str_er_track_pool *P, int32_t *keep)
+{
+    if (!P || !keep) return STR_ER_EINVAL;
+    *keep = P->keep;
+    return STR_ER_OK;
+}
+
 void str_er_track_pool_destroy(str_er_track_pool *P)
 {
     if (!P) return;
@@ -160,7 +244,7 @@ void str_er_track_pool_destroy(str_er_track_pool *P)
 int str_er_track_pool_reset(str_er_track_pool *P)
 try {
     if (!P) return STR_ER_EINVAL;
-    return bind(P);
+    return is_decode(P) ? bind_decode(P) : bind(P);
 } ABI_GUARD(P ? P->c : nullptr)
 
 int str_er_track_pool_info(const str_er_track_pool *P, int32_t *cap_tracks, uint32_t *flags, int32_t *n_entries, uint64_t *device_bytes, int32_t *n_in_use, int32_t *is_stale)
@@ -187,11 +271,21 @@ try {
     if (!words_in_rows(n_rows, first_run, n_runs_of_word, n_words)) return fail(c, STR_ER_EINVAL, "track pool: a word outside the cost rows");
     RowsIn I{};
     AddTab D{};
+    const bool decode = is_decode(P);
+    if (decode && n_tracks > 0 && P->serial == UINT32_MAX) return fail(c, STR_ER_ECAPACITY, "decode pool: the serials of its additions are used up (str_er_track_pool_reset)");
     if (const int rc = add_common(P, nullptr, costs, (size_t)n_rows, nullptr, 0, first_run, n_runs_of_word, n_words, track_first, track_count, members, n_members, n_tracks,
-                                  slots, I, D);
+                                  slots, I, D, decode ? wd_layout(nullptr, 0, (size_t)n_words).bytes : 0);
         rc != STR_ER_OK)
         return rc;
     if (n_tracks == 0) return STR_ER_OK;
+    if (decode) {          // the seeds' strings once, when the members come; then the members into their slots
+        const WdTab W = wd_layout(P->tab.d(), D.bytes, (size_t)n_words);
+        launch_word_decode(c->stream, P->bigram, P->wd_ins, P->wd_del, I.costs, I.first, I.n_of, n_words, W.dec, W.chars, W.src);
+        launch_dpool_keep(c->stream, P->store, P->serial + 1, I.costs, I.first, I.n_of, W.dec, W.chars, D.first, D.count, D.members, D.slots, n_tracks);
+        if (const int rc = add_done(P, track_count, n_tracks, slots); rc != STR_ER_OK) return rc;
+        ++P->serial;
+        return STR_ER_OK;
+    }
     launch_pool_add(c->stream, P->lex, P->prm, P->dev, I.costs, I.first, I.n_of, D.first, D.count, D.members, D.slots, n_tracks);
     return add_done(P, track_count, n_tracks, slots);
 } ABI_GUARD(P ? P->c : nullptr)
@@ -233,7 +327,8 @@ try {
                                                   : "track pool: a slot outside the pool, a repeated slot, or dst among the srcs");
     if (n_srcs == 0) return STR_ER_OK;
     if (const int rc = slots_upload(P, srcs, (size_t)n_srcs, 0); rc != STR_ER_OK) return rc;
-    launch_pool_join(c->stream, P->dev, dst, P->tab.d<int32_t>(), n_srcs);
+    if (is_decode(P)) launch_dpool_join(c->stream, P->store, dst, P->tab.d<int32_t>(), n_srcs);
+    else launch_pool_join(c->stream, P->dev, dst, P->tab.d<int32_t>(), n_srcs);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, wait_stream(c, c->stream));
     for (int32_t k = 0; k < n_srcs; ++k) { P->n_members[(size_t)dst] += P->n_members[(size_t)srcs[k]]; P->n_members[(size_t)srcs[k]] = 0; }
@@ -250,7 +345,8 @@ try {
         if (slots[i] < 0 || slots[i] >= P->cap) return fail(c, STR_ER_EINVAL, "track pool: a slot outside the pool");
     if (n == 0) return STR_ER_OK;
     if (const int rc = slots_upload(P, slots, (size_t)n, 0); rc != STR_ER_OK) return rc;
-    launch_pool_clear(c->stream, P->dev, P->tab.d<int32_t>(), n);
+    if (is_decode(P)) launch_dpool_clear(c->stream, P->store, P->tab.d<int32_t>(), n);
+    else launch_pool_clear(c->stream, P->dev, P->tab.d<int32_t>(), n);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, wait_stream(c, c->stream));
     for (int32_t i = 0; i < n; ++i) P->n_members[(size_t)slots[i]] = 0;
@@ -263,6 +359,7 @@ try {
     str_er_ctx *c = P->c;
     if (n < 0 || (n > 0 && (!slots || !out))) return fail(c, STR_ER_EINVAL, "bad arguments");
     if (stale(P)) return usable(P, (P->flags & STR_ER_POOL_LATTICE) != 0);
+    if (is_decode(P)) return fail(c, STR_ER_ESTATE, "str_er_track_pool_read on a decode pool (str_er_track_pool_read_decode)");
     for (int32_t i = 0; i < n; ++i)
         if (slots[i] < 0 || slots[i] >= P->cap) return fail(c, STR_ER_EINVAL, "track pool: a slot outside the pool");
     if (n == 0) return STR_ER_OK;
@@ -276,6 +373,75 @@ try {
     HIP_TRY(c, hipMemcpyAsync(P->tab.h() + o_out, P->tab.d() + o_out, out_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, wait_stream(c, s));
     std::memcpy(out, P->tab.h() + o_out, out_bytes);
+    return STR_ER_OK;
+} ABI_GUARD(P ? P->c : nullptr)
+
+int str_er_track_pool_read_decode(str_er_track_pool *P, const int32_t *slots, int32_t n, str_er_pool_decode *out, uint8_t *chars, int32_t *member_cost)
+try {
+    if (!P) return STR_ER_EINVAL;
+    str_er_ctx *c = P->c;
+    if (n < 0 || (n > 0 && (!slots || !out || !chars || !member_cost))) return fail(c, STR_ER_EINVAL, "bad arguments");
+    if (stale(P)) return usable(P, false);
+    if (!is_decode(P)) return fail(c, STR_ER_ESTATE, "str_er_track_pool_read_decode on a lexicon pool (str_er_track_pool_read)");
+    for (int32_t i = 0; i < n; ++i)
+        if (slots[i] < 0 || slots[i] >= P->cap) return fail(c, STR_ER_EINVAL, "decode pool: a slot outside the pool");
+    if (n == 0) return STR_ER_OK;
+    const size_t ns = (size_t)n, nk = ns * (size_t)P->keep;
+    if (nk > 0x7FFFFFFFull / 4) return fail(c, STR_ER_ECAPACITY, "decode pool: too many slots to read at once for this keep");
+    // slots | first member, member count per request | cells in age order | age rank per cell | the track decode's records, and what
+    // comes down: records | labels | member costs
+    Carve        cv{};
+    const size_t o_slots = cv.take(4 * ns), o_first = cv.take(4 * ns), o_count = cv.take(4 * ns), o_mem = cv.take(4 * nk), o_rank = cv.take(4 * nk),
+                 o_rec = cv.take(sizeof(str_er_track_decode) * ns), o_out = cv.take(sizeof(str_er_pool_decode) * ns), o_chars = cv.take(32 * ns), o_mcost = cv.take(4 * nk);
+    if (const int rc = slots_upload(P, slots, ns, cv.off - align_up(4 * ns, 256)); rc != STR_ER_OK) return rc;
+    (void)o_slots;
+    uint8_t    *d = P->tab.d(), *h = P->tab.h();
+    const auto  i32 = [&](size_t o) { return reinterpret_cast<int32_t *>(d + o); };
+    hipStream_t s = c->stream;
+    launch_dpool_plan(s, P->store, i32(0), n, i32(o_first), i32(o_count), i32(o_mem), i32(o_rank), i32(o_mcost));
+    launch_track_decode(s, P->bigram, P->td_ins, P->td_del, P->td_rounds, P->store.costs, P->store.first_run, P->store.n_of, P->store.dec, P->store.dchars, i32(o_first),
+                        i32(o_count), i32(o_mem), n, d + o_rec, d + o_chars, i32(o_mcost));
+    launch_dpool_records(s, P->store, i32(0), n, i32(o_rec), i32(o_count), i32(o_rank), i32(o_out));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(h + o_out, d + o_out, cv.off - o_out, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, wait_stream(c, s));
+    std::memcpy(out, h + o_out, sizeof(str_er_pool_decode) * ns);
+    std::memcpy(chars, h + o_chars, 32 * ns);
+    std::memcpy(member_cost, h + o_mcost, 4 * nk);
+    return STR_ER_OK;
+} ABI_GUARD(P ? P->c : nullptr)
+
+int str_er_track_pool_members(str_er_track_pool *P, int32_t slot, uint64_t *keys, int32_t *n_runs, uint8_t *rows, int32_t *n_kept)
+try {
+    if (!P) return STR_ER_EINVAL;
+    str_er_ctx *c = P->c;
+    if (!n_kept) return fail(c, STR_ER_EINVAL, "bad arguments");
+    if (stale(P)) return usable(P, false);
+    if (!is_decode(P)) return fail(c, STR_ER_ESTATE, "str_er_track_pool_members on a lexicon pool");
+    if (slot < 0 || slot >= P->cap) return fail(c, STR_ER_EINVAL, "decode pool: a slot outside the pool");
+    const size_t k = (size_t)P->keep, c0 = (size_t)slot * k;
+    Carve        cv{};
+    const size_t o_key = cv.take(8 * k), o_n = cv.take(4 * k), o_rows = cv.take(DP_CELL_ROW_BYTES * k);
+    if (const int rc = P->tab.ensure(c, cv.off, "track pool tables"); rc != STR_ER_OK) return rc;
+    uint8_t    *h = P->tab.h();
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipMemcpyAsync(h + o_key, P->store.key + c0, 8 * k, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(h + o_n, P->store.n_of + c0, 4 * k, hipMemcpyDeviceToHost, s));
+    if (rows) HIP_TRY(c, hipMemcpyAsync(h + o_rows, P->store.costs + c0 * DP_CELL_ROW_BYTES, DP_CELL_ROW_BYTES * k, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, wait_stream(c, s));
+    const uint64_t *hk = reinterpret_cast<const uint64_t *>(h + o_key);
+    const int32_t  *hn = reinterpret_cast<const int32_t *>(h + o_n);
+    std::vector<int32_t> order;          // the kept cells in age order
+    for (size_t q = 0; q < k; ++q)
+        if (hk[q] != 0) order.push_back((int32_t)q);
+    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return hk[a] < hk[b]; });
+    for (size_t i = 0; i < order.size(); ++i) {
+        const size_t q = (size_t)order[i];
+        if (keys) keys[i] = hk[q];
+        if (n_runs) n_runs[i] = hn[q];
+        if (rows) std::memcpy(rows + i * DP_CELL_ROW_BYTES, h + o_rows + q * DP_CELL_ROW_BYTES, DP_CELL_ROW_BYTES);
+    }
+    *n_kept = (int32_t)order.size();
     return STR_ER_OK;
 } ABI_GUARD(P ? P->c : nullptr)
 

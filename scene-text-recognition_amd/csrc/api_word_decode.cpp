@@ -41,6 +41,7 @@ int str_er_set_bigram(str_er_ctx *c, const uint8_t *cost)
 try {
     if (!c) return STR_ER_EINVAL;
     HIP_TRY(c, hipStreamSynchronize(c->stream));       // (a call in flight still reads the table that is replaced)
+    ++c->decode_pool_gen;          // (a decode pool is bound to the table it was made with: str_er_pool_decode)
     if (!cost) {
         c->bigram = DevBuf();
         c->bigram_set = false;
@@ -67,6 +68,7 @@ try {
     if (!c) return STR_ER_EINVAL;
     if (!wd::params_ok(ins, del)) return fail(c, STR_ER_EINVAL, "word decode: INS and DEL are in 0 .. 255");
     c->wd_ins = ins; c->wd_del = del;
+    ++c->decode_pool_gen;          // (a decode pool is bound to them: str_er_pool_decode)
     return STR_ER_OK;
 } ABI_GUARD(c)
 

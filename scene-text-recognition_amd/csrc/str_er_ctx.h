@@ -343,6 +343,7 @@ struct str_er_ctx {
     // STR_ER_WANT_LATTICE_TRACK / str_er_lattice_match_tracks
     PairBuf  lt_tab;                  // (str_er_lattice_match_tracks: splits | rows of the runs and pieces | first run, run count per word) | tracks, members and their slots | words' structure | chunk keys | records | member records | sources | parts | free costs
     // str_er_track_pool_*: what a track pool is bound to (the lexicon, INS / DEL / band, SPLIT) has this generation; their setters bump it
+    // (a decode pool has a generation of its own, decode_pool_gen, at the end of the context)
     uint64_t pool_gen = 0;
     DevBuf   strip_out, strip_in;     // strip blobs: made here / uploaded for a merge
     uint32_t *d_strip_flag = nullptr;                 // a strip blob named a node outside its records
@@ -394,6 +395,9 @@ struct str_er_ctx {
     int n_ev = 0;
     bool profiling = false;
     std::vector<std::pair<const char *, double>> profile;
+    // pool_gen's sibling: what a decode pool is bound to (the bigram table, the decoder's INS / DEL, the track decode's INS / DEL / rounds)
+    // has this generation; their setters bump it.  It stands here, behind everything else, so that no member a detect call touches moves.
+    uint64_t decode_pool_gen = 0;
 };
 
 namespace {

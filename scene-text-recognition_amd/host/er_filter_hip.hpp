@@ -1327,6 +1327,74 @@ public:
         std::shared_ptr<str_er_track_pool> pool_;
     };
 
+    // The decode pool (str_er_track_pool_create_decode; the contract is at str_er_pool_decode in include/str_er.h): cap_tracks pooled
+    // word tracks on the device without a lexicon, per slot the newest `keep` usable members added to it -- their cost rows and decoder
+    // strings -- kept from call to call; read() decodes a slot as decode_tracks decodes the track of its kept members in age order.
+    // Bound to the bigram table, set_word_decode and set_track_decode of the filter as they are at creation: after one of their
+    // setters every call throws (STR_ER_ESTATE) until reset().  The pool keeps its context alive.
+    class DecodePool {
+    public:
+        DecodePool(const ERFilter &f, int32_t cap_tracks, int32_t keep = 32) : ctx_(f.ctx_), keep_(keep)
+        {
+            str_er_track_pool *p = nullptr;
+            check(str_er_track_pool_create_decode(ctx_.get(), cap_tracks, keep, &p));
+            pool_.reset(p, str_er_track_pool_destroy);
+        }
+        int32_t keep() const { return keep_; }
+        // the tracks, given as for decode_tracks (unfolded rows), are added to the slots slots[g] (distinct)
+        void add(const std::vector<uint8_t> &costs, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs, const std::vector<int32_t> &track_first,
+                 const std::vector<int32_t> &track_count, const std::vector<int32_t> &members, const std::vector<int32_t> &slots)
+        {
+            if (costs.size() % 65 || first_run.size() != n_runs.size() || track_first.size() != track_count.size() || slots.size() != track_first.size())
+                throw std::invalid_argument("DecodePool::add: 65 bytes a run, one span a word, one span and one slot a track");
+            check(str_er_track_pool_add(pool_.get(), ptr(costs), (int32_t)(costs.size() / 65), ptr(first_run), ptr(n_runs), (int32_t)first_run.size(), ptr(track_first),
+                                        ptr(track_count), ptr(members), (int32_t)members.size(), (int32_t)track_first.size(), ptr(slots)));
+        }
+        // slot dst keeps the newest of its own and the srcs' kept members; the srcs become empty
+        void join(int32_t dst, const std::vector<int32_t> &srcs) { check(str_er_track_pool_join(pool_.get(), dst, ptr(srcs), (int32_t)srcs.size())); }
+        void clear(const std::vector<int32_t> &slots) { check(str_er_track_pool_clear(pool_.get(), ptr(slots), (int32_t)slots.size())); }
+        // per slot named (a slot may be named more than once) a record, 32 labels and keep member costs in age order, -1 past n_kept
+        struct Reads {
+            std::vector<str_er_pool_decode> records;
+            std::vector<uint8_t>            chars;
+            std::vector<int32_t>            member_costs;
+        };
+        Reads read(const std::vector<int32_t> &slots)
+        {
+            Reads r;
+            r.records.resize(slots.size()); r.chars.assign(32 * slots.size(), 0xFF); r.member_costs.assign((size_t)keep_ * slots.size(), -1);
+            check(str_er_track_pool_read_decode(pool_.get(), ptr(slots), (int32_t)slots.size(), r.records.empty() ? nullptr : r.records.data(),
+                                                r.chars.empty() ? nullptr : r.chars.data(), r.member_costs.empty() ? nullptr : r.member_costs.data()));
+            return r;
+        }
+        // the kept list of a slot in age order: keys, run counts and 32 rows of 65 bytes a member
+        struct Members {
+            std::vector<uint64_t> keys;
+            std::vector<int32_t>  n_runs;
+            std::vector<uint8_t>  rows;
+        };
+        Members members(int32_t slot)
+        {
+            Members m;
+            m.keys.resize((size_t)keep_); m.n_runs.resize((size_t)keep_); m.rows.resize((size_t)keep_ * 32 * 65);
+            int32_t n = 0;
+            check(str_er_track_pool_members(pool_.get(), slot, m.keys.data(), m.n_runs.data(), m.rows.data(), &n));
+            m.keys.resize((size_t)n); m.n_runs.resize((size_t)n); m.rows.resize((size_t)n * 32 * 65);
+            return m;
+        }
+        // every slot empty, the pool bound to the filter's table and parameters as they are now
+        void reset() { check(str_er_track_pool_reset(pool_.get())); }
+    private:
+        template <typename T> static const T *ptr(const std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
+        void check(int rc) const
+        {
+            if (rc != STR_ER_OK) throw std::runtime_error(std::string(str_er_strerror(rc)) + ": " + str_er_last_error(ctx_.get()));
+        }
+        std::shared_ptr<str_er_ctx>        ctx_;      // (declared first: the pool is destroyed before its context)
+        std::shared_ptr<str_er_track_pool> pool_;
+        int32_t                            keep_;
+    };
+
     // vector<double> ERFilter::make_LBP_hist(Mat input, N = 2, normalize_size = 24) (src/ER.cpp:789-816)
     std::vector<double> make_LBP_hist(const Image8 &input)
     {

@@ -71,6 +71,17 @@ int main(int argc, char **argv)
             for (const ER *e : t.ers) std::printf(" %d/%u", e->ch, e->key);
             std::printf("\n");
         }
+        {   // a decode pool: two readings of one word in two additions, pooled on the device and decoded without a lexicon
+            er_filter.set_bigram(std::vector<uint8_t>(66 * 66, 10));
+            ERFilter::DecodePool decodes(er_filter, 4, 8);
+            for (int call = 0; call < 2; ++call) {
+                std::vector<uint8_t> rows(3 * 65, 200);
+                for (int i = 0; i < 3; ++i) rows[(size_t)i * 65 + 10 + i + call * (i == 1)] = 0;          // "ABC", then "ACC"
+                decodes.add(rows, {0}, {3}, {0}, {1}, {0}, {2});
+            }
+            const ERFilter::DecodePool::Reads r = decodes.read({2});
+            std::printf("decode pool: members %d kept %d chars %d cost %d\n", r.records[0].n_members, r.records[0].n_kept, r.records[0].n_chars, r.records[0].cost);
+        }
         std::printf("staged == fused on plane 0: %s\n", same ? "yes" : "NO");
         return same ? 0 : 1;
     } catch (const std::exception &e) {

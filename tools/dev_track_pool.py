@@ -11,17 +11,26 @@
         members so far, which is what a caller without the pool runs.  The records are compared after every batch.
     python tools/dev_track_pool.py slots [--slots 125]
         join (pairs of slots) and read on a pool of --slots slots with 8 members each.
+    python tools/dev_track_pool.py decode [--per-track 8] [--keep K] [--rounds 8] [--iters N] [--reps 7]
+        the decode pool (profiles/decode_pool.md) on the shape of `dev_track_decode.py kernel`: 125 tracks of --per-track readings of
+        one truth string each, fed as --per-track additions of one member per track into a DecodePool of --keep (default
+        --per-track): the time of every addition (upload, k_word_decode, k_dpool_keep, wait), of a read of the 125 slots
+        (k_dpool_plan, k_track_decode, k_dpool_records, copy back, wait) and beside them decode_tracks on all members, which is
+        what a caller without the pool runs for every batch.  The records are compared.  --iters: one process of fill and read
+        rounds only, for a `rocprofv3 --kernel-trace --stats` run.
 """
 import argparse, json, os, sys, time
 import numpy as np
 
 ap = argparse.ArgumentParser()
-ap.add_argument("mode", choices=["batch", "stream", "slots"])
+ap.add_argument("mode", choices=["batch", "stream", "slots", "decode"])
 ap.add_argument("--words", type=int, default=1000)
 ap.add_argument("--per-track", type=int, default=8)
 ap.add_argument("--entries", type=int, default=100000)
 ap.add_argument("--batches", type=int, default=10)
 ap.add_argument("--slots", type=int, default=125)
+ap.add_argument("--keep", type=int, default=0)
+ap.add_argument("--rounds", type=int, default=8)
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--iters", type=int, default=0)
 ap.add_argument("--same-length", action="store_true")
@@ -169,8 +178,58 @@ def slots_mode():
     return out
 
 
+def decode_mode():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import track_decode_ref as TD
+    rng = np.random.default_rng(1)
+    n_tracks, per, keep = a.words // a.per_track, a.per_track, a.keep or a.per_track
+    tracks = [TD.make_track(rng, [int(x) for x in rng.integers(0, 65, int(rng.integers(3, 13)))], per) for _ in range(n_tracks)]
+    costs, first, n_of, tfirst, tcount, members = TD.pack(tracks)
+    B = rng.integers(0, 90, (66, 66)).astype(np.uint8)
+    f = S.ERFilter(params=S.Params(max_width=64, max_height=64, max_frames=1))
+    f.set_bigram(B)
+    f.set_track_decode(64, 64, a.rounds)
+    pool = S.DecodePool(f, n_tracks, keep)
+    slots = np.arange(n_tracks, dtype=np.int32)
+    # addition j: member j of every track, a track of one member each, with the rows of those words alone
+    adds = []
+    for j in range(per):
+        ws = members[tfirst + j]
+        rows = np.concatenate([costs[first[w]:first[w] + n_of[w]] for w in ws])
+        n = n_of[ws].astype(np.int32)
+        adds.append((rows, np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int32), n, np.arange(n_tracks, dtype=np.int32), np.ones(n_tracks, np.int32),
+                     np.arange(n_tracks, dtype=np.int32)))
+    def fill():
+        t = []
+        pool.clear(slots)
+        for args in adds:
+            t0 = time.perf_counter(); pool.add(*args, slots); t.append((time.perf_counter() - t0) * 1e3)
+        return t
+    one_call = lambda: f.decode_tracks(costs, first, n_of, tfirst, tcount, members)
+    info = pool.info()
+    out = {"lib": S.lib_path(), "tracks": n_tracks, "per_track": per, "keep": keep, "rounds": a.rounds, "words": int(len(first)), "rows": int(len(costs)),
+           "rows_of_an_addition": [int(len(x[0])) for x in adds], "pool": info, "device_bytes_per_slot": round((info["device_bytes"]) / n_tracks, 1),
+           "store_bytes_per_kept_member": 2184}
+    fill()
+    got, ch, mc = pool.read(slots)
+    want, wch, wmc = one_call()
+    same = [k for k in want.dtype.names if k != "seed_member"]
+    out["records_equal"] = bool(keep >= per and all((got[k] == want[k]).all() for k in same) and (ch == wch).all() and (mc[:, :per].reshape(-1) == wmc).all())
+    if a.iters:
+        for _ in range(a.iters):
+            fill(); pool.read(slots); one_call()
+        out["iters"] = a.iters
+    else:
+        t = np.array([fill() for _ in range(a.reps)])          # (reps, per): the j-th addition finds j members pooled
+        out["add_call_ms"] = [stats(t[:, j].tolist()) for j in range(per)]
+        out["read_decode_call_ms"] = timed(lambda: pool.read(slots), a.reps)
+        out["decode_tracks_call_ms"] = timed(one_call, a.reps)
+    pool.close(); f.close()
+    return out
+
+
 if __name__ == "__main__":
-    res = {"batch": batch, "stream": stream, "slots": slots_mode}[a.mode]()
+    res = {"batch": batch, "stream": stream, "slots": slots_mode, "decode": decode_mode}[a.mode]()
     print(json.dumps(res, indent=1))
     if a.out:
         with open(a.out, "w") as fh:
