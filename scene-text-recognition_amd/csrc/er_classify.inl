@@ -90,33 +90,36 @@ __device__ double block_cascade(ClsShared &sh, const CascadeDev &c)
     return score;
 }
 
-// Batched classify: one workgroup takes 64 pooled ERs.
-//   phase 1: each of the 16 waves builds the LBP histograms of 4 of them (wave per ER) and stores
+// Batched classify: one workgroup of WAVES waves takes PER pooled ERs at a time.
+//   phase 1: each wave builds the LBP histograms of PER / WAVES of them (wave per ER) and stores
 //            them as 1028-byte rows of 8-bit counts in LDS (1028 = 1024 + 4: lane j reading
 //            row j, column d hits bank (257 j + d/4) mod 32 -- conflict free);
-//   phase 2: ONE wave scores all 64 with one ER per lane: every lane walks the stumps in file
-//            order and adds in that order, so each stage sum is bit-identical to the
-//            reference's sequential `score_stage +=` (src/adaboost.cpp:526-541), while the stump
-//            parameters are wave-uniform (scalar loads).
+//   phase 2: the cascades with one ER per lane: every lane walks the stumps in file order and
+//            adds in that order, so each stage sum is bit-identical to the reference's
+//            sequential `score_stage +=` (src/adaboost.cpp:526-541), while the stump parameters
+//            are wave-uniform.  The stages of both cascades are dealt to the waves (below).
+// The workgroup's LDS and lanes decide where it can run while other batches' tile kernels fill the compute units (eight workgroups of 19.9 KB
+// and four waves each: DESIGN 3.2, 3.5): nothing cascade-wide is kept in LDS -- a wave stages the output pairs of the 64 stumps it is summing.
 constexpr int CLS_ROW = 1028;
-constexpr int CLS_PER_BLOCK = 64;
+constexpr int CLS_MAX_JOBS = 16;        // stages of both cascades together that the stage-parallel form takes
 
-constexpr int CLS64_WAVES = 16;
-constexpr int CLS64_THREADS = CLS64_WAVES * 64;
-
-struct Cls64Scratch {
-    uint32_t hist[CLS64_WAVES][1024];
-    uint8_t  tile[CLS64_WAVES][26 * 26 + 4];
+template <int PER, int WAVES>
+struct ClsWgShared {
+    double2 chunk[WAVES][64];               // phase 2: the (A, B) output pairs of the 64 stumps wave w is summing
+    double  stage_sum[CLS_MAX_JOBS][PER];   // phase 2: the sum of stage job j for every ER
+    uint8_t rows[PER * CLS_ROW];
+    uint8_t tile[WAVES][26 * 26 + 4];       // phase 1: the ARAN tile of the wave's ER
 };
-struct Cls64Shared {
-    uint8_t rows[CLS_PER_BLOCK * CLS_ROW];
-    union {                              // phase 1 scratch, then the (A,B) tables of both cascades
-        Cls64Scratch p1;
-        double       ab[sizeof(Cls64Scratch) / sizeof(double)];
-    } u;
-    double stage_sum[CLS64_WAVES][64];   // phase 2: wave w leaves the sum of "its" stage for every ER here
-};
-constexpr int CLS_AB_CAP = (int)(sizeof(Cls64Scratch) / (2 * sizeof(double)));   // stumps that fit
+// The builds (launch_classify).  A call of a frame or two on an empty chip: one ER per wave, 16 waves.  The batch build has to run beside the tile kernels of
+// other batches: 32 ERs on 4 waves, 43.8 KB -- five tile workgroups (100 KB, 20 waves) still fit on its compute unit.  Fewer waves a workgroup is the point,
+// not only fewer bytes: the longest stage (1210 of the shipped 4014 stumps) occupies one wave however many there are, and the waves that wait for it hold
+// their registers -- 8 waves for the same 32 ERs gained 1.3-1.4 % on the line, 4 waves 1.8-2.3 %, 2 waves 0.5 % (profiles/classify_footprint.md).
+constexpr int CLS_FEW_PER = 16, CLS_FEW_WAVES = 16;
+constexpr int CLS_BATCH_PER = 32, CLS_BATCH_WAVES = 4;
+static_assert(sizeof(ClsWgShared<CLS_BATCH_PER, CLS_BATCH_WAVES>) <= 60 * 1024 && CLS_BATCH_WAVES * 64 <= 512, "the batch build leaves room for five tile workgroups");
+// (developer switch STR_ER_CLASSIFY_FORM, the forms that lost: 8 = 32 ERs on 8 waves, 50.6 KB; 64 = 64 ERs on 8 waves, 87.6 KB: three tile workgroups beside it)
+static_assert(sizeof(ClsWgShared<CLS_BATCH_PER, 8>) <= 60 * 1024 && sizeof(ClsWgShared<64, 8>) <= 96 * 1024, "the other batch forms");
+static_assert(sizeof(ClsWgShared<CLS_FEW_PER, CLS_FEW_WAVES>) <= 64 * 1024, "static LDS");
 
 __device__ __forceinline__ double readlane_f64(double v, int j)
 {
@@ -189,71 +192,35 @@ __device__ __forceinline__ double lane_cascade_generic(const CascadeDev &c, cons
 
 // Fast form for dir = +-1 cascades: histogram counts are integers, so `fv*dir < thr*dir` is the
 // integer test h < T (T = ceil(thr), or floor(thr)+1 with the two outputs swapped for dir = -1).
-// The (A,B) output pairs of all stumps sit in LDS (s_ab); the packed (dim, T) words of 64 stumps
-// are fetched with one vector load and broadcast with v_readlane.  Adds stay in file order.
-__device__ __forceinline__ double lane_cascade_fast(const CascadeDev &c, const uint8_t *row, const double *s_ab, bool valid)
+//
+// The sum of the stumps [off, off + m) -- one stage -- for the ER of every lane.  A cascade's stages do not feed each other -- stage s is
+// "sum of its stumps >= thresh[s]" -- so the stages of both cascades can run on different waves at the same time; only the adds inside a
+// stage are ordered.  The packed (dim, T) words of 64 stumps are fetched with one vector load (lane i holds stump i) and broadcast with
+// v_readlane; their (A, B) output pairs are fetched the same way and put into `chunk`, 1 KB of LDS that belongs to this wave, where every lane
+// reads pair j at one address.  Nothing cascade-wide is in LDS, so no number of stumps is too many for this form.
+__device__ __forceinline__ double lane_stumps_fast(const CascadeDev &c, int off, int m, const uint8_t *row, double2 *chunk)
 {
-    const int lane = threadIdx.x & 63;
-    int    off = 0;
-    bool   alive = valid;
-    double score = 0;
-    for (int s = 0; s < c.n_stages; ++s) {
-        const int n = c.stage_n[s];
-        double    acc = 0;
-        const int m = min(n, max(0, c.n_stumps - off));
-        for (int base = 0; base < m; base += 64) {
-            const int pw = (base + lane < m) ? (int)c.w[off + base + lane] : 0;
-            const int cnt = min(64, m - base);
-            const double *ab = s_ab + 2 * (size_t)(off + base);
-            int j = 0;
-            for (; j + 8 <= cnt; j += 8) {
-                double v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const uint32_t w = (uint32_t)__builtin_amdgcn_readlane(pw, j + u);
-                    const uint32_t h = row[w & 1023u];
-                    v[u] = ab[2 * (j + u) + (h < (w >> 10) ? 0 : 1)];
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc += v[u];
-            }
-            for (; j < cnt; ++j) {
-                const uint32_t w = (uint32_t)__builtin_amdgcn_readlane(pw, j);
-                const uint32_t h = row[w & 1023u];
-                acc += ab[2 * j + (h < (w >> 10) ? 0 : 1)];
-            }
-        }
-        if (alive) {
-            if (acc < (double)c.stage_thresh[s]) alive = false;
-            else score = acc;
-        }
-        off += n;
-        if (!__any(alive)) break;
-    }
-    return alive ? score : -DBL_MAX;
-}
-
-// The sum of ONE stage for the ER of every lane (same arithmetic as the stage loop above).  A cascade's stages do
-// not feed each other -- stage s is "sum of its stumps >= thresh[s]" -- so the stages of both cascades can run on
-// different waves at the same time; only the adds inside a stage are ordered.
-__device__ __forceinline__ double lane_stage_fast(const CascadeDev &c, int s, const uint8_t *row, const double *s_ab)
-{
-    const int lane = threadIdx.x & 63;
-    int       off = 0;
-    for (int i = 0; i < s; ++i) off += c.stage_n[i];
-    const int n = c.stage_n[s];
-    const int m = min(n, max(0, c.n_stumps - off));
-    double    acc = 0;
+    const int      lane = threadIdx.x & 63;
+    const double2 *gab = reinterpret_cast<const double2 *>(c.ab) + off;
+    double         acc = 0;
     // (round 4, measured in place with tools/dev_cls_trace.py: the stage sums were 55 % of a workgroup's 140 us -- 137 cycles per stump in the longest stage.
-    // Two dependent waits went: the packed (dim, T) words of the NEXT 64 stumps are requested while this block is summed -- a trip to memory per block had
+    // Two dependent waits went: the words and pairs of the NEXT 64 stumps are requested while this block is summed -- a trip to memory per block had
     // been waited for at its top --, and a stump's output pair (A, B) is read whole, at an address that does not depend on the histogram byte, and
     // picked afterwards: one trip to LDS per batch of 8 stumps instead of two.  Same adds in the same order.)
-    int pw_next = (lane < m) ? (int)c.w[off + lane] : 0;
+    int     pw_next = (lane < m) ? (int)c.w[off + lane] : 0;
+    double2 ab_next = (lane < m) ? gab[lane] : make_double2(0.0, 0.0);
     for (int base = 0; base < m; base += 64) {
         const int pw = pw_next;
-        if (base + 64 < m) pw_next = (base + 64 + lane < m) ? (int)c.w[off + base + 64 + lane] : 0;
+        WAVE_SYNC();            // (the wave's reads of the block before are behind it: its LDS operations are carried out in the order it issues them)
+        chunk[lane] = ab_next;
+        if (base + 64 < m) {
+            const bool have = base + 64 + lane < m;
+            pw_next = have ? (int)c.w[off + base + 64 + lane] : 0;
+            ab_next = have ? gab[base + 64 + lane] : make_double2(0.0, 0.0);
+        }
+        WAVE_SYNC();
         const int cnt = min(64, m - base);
-        const double2 *ab = reinterpret_cast<const double2 *>(s_ab + 2 * (size_t)(off + base));
+        const double2 *ab = chunk;
         int j = 0;
         if (cnt == 64) {
             // a full block: the reads of batch q + 1 are on their way while batch q is summed (the wave of a long stage is soon alone on its SIMD:
@@ -302,6 +269,25 @@ __device__ __forceinline__ double lane_stage_fast(const CascadeDev &c, int s, co
     return acc;
 }
 
+// A whole cascade on one wave, stage after stage (cascades with more stages than the stage-parallel form takes)
+__device__ __forceinline__ double lane_cascade_fast(const CascadeDev &c, const uint8_t *row, double2 *chunk, bool valid)
+{
+    int    off = 0;
+    bool   alive = valid;
+    double score = 0;
+    for (int s = 0; s < c.n_stages; ++s) {
+        const int    n = c.stage_n[s];
+        const double acc = lane_stumps_fast(c, off, min(n, max(0, c.n_stumps - off)), row, chunk);
+        if (alive) {
+            if (acc < (double)c.stage_thresh[s]) alive = false;
+            else score = acc;
+        }
+        off += n;
+        if (!__any(alive)) break;
+    }
+    return alive ? score : -DBL_MAX;
+}
+
 // CascadeBoost::predict's stage loop (src/adaboost.cpp:507-542) over stage sums that are already there
 __device__ __forceinline__ double cascade_from_stage_sums(const CascadeDev &c, const double *sums, int stride)
 {
@@ -314,16 +300,88 @@ __device__ __forceinline__ double cascade_from_stage_sums(const CascadeDev &c, c
     return score;
 }
 
-// (list / n_list: only these candidates -- the planes whose pool the NMS tie pass changed)
-// PER = candidates a workgroup takes at a time: 64 (a lane per candidate in the cascades), or 16 -- one per wave in the histogram phase instead of four
-// in a row -- for calls with so few candidates (a frame or two: ~1000) that 64 a workgroup would leave most of the chip idle
-template <int PER>
-__global__ __launch_bounds__(CLS64_THREADS) void k_classify(BatchDev b, DetectParams prm, CascadeDev strong,
-                                                          CascadeDev weak, int run_cascades, const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list)
+// The candidate's record: what k_kept left of its node, and the classifier's answer
+__device__ __forceinline__ void write_cand_record(const BatchDev &b, uint32_t cidx, int cls, double ss, double sw)
 {
-    __shared__ Cls64Shared sh;
+    const int        pi = b.cand_plane[cidx];
+    const PlaneDesc &pd = b.planes[pi];
+    const uint32_t   slot = b.pool[pd.pool_base + (cidx - b.ctr[pi].cand_base)];
+    const size_t     ks = pd.kept_base + slot;
+    CandRec r;
+    r.frame = pd.frame; r.ch = pd.ch; r.pyr = pd.pyr; r.level = b.ka.level[ks]; r.cls = (uint8_t)cls;
+    r.x = b.ka.box[4 * ks]; r.y = b.ka.box[4 * ks + 1]; r.w = b.ka.box[4 * ks + 2]; r.h = b.ka.box[4 * ks + 3];
+    r.area = b.ka.area[ks]; r.key = b.ka.key[ks]; r.node = (int32_t)slot; r.plane = (uint32_t)pi;
+    r.score_strong = ss; r.score_weak = sw;
+    b.cands[cidx] = r;
+    if (cls == 1) atomicAdd(&b.ctr[pi].n_strong, 1u);
+    if (cls == 2) atomicAdd(&b.ctr[pi].n_weak, 1u);
+}
+
+// Calls without STR_ER_STAGE_CLASSIFY: the records alone (cls 0, no scores), a lane per candidate -- no LDS, so these workgroups start wherever four
+// wave slots are free
+constexpr int CAND_REC_THREADS = 256;
+__global__ __launch_bounds__(CAND_REC_THREADS) void k_cand_records(BatchDev b, const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list)
+{
     const uint32_t total = list ? *n_list : *b.total_cands;
-    const int      tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    for (uint32_t cpos = blockIdx.x * CAND_REC_THREADS + threadIdx.x; cpos < total; cpos += gridDim.x * CAND_REC_THREADS)
+        write_cand_record(b, list ? list[cpos] : cpos, 0, -DBL_MAX, 0.0);
+}
+
+// The stage jobs of the stage-parallel form -- job j < S is stage j of the strong cascade, job j >= S stage j - S of the weak one -- dealt to the
+// workgroup's waves longest first, each to the wave with the fewest stumps so far (the shipped cascades: ten jobs for four waves).  Every wave
+// works the deal out for itself, in lanes and wave-uniform values.  Returns the wave's jobs as a mask over RANKS (bit r: the r-th longest job);
+// `job_at`: lane r holds the job of rank r.
+template <int WAVES>
+__device__ __forceinline__ uint32_t deal_stage_jobs(const CascadeDev &strong, const CascadeDev &weak, int wv, int &job_at)
+{
+    const int lane = threadIdx.x & 63;
+    const int S = strong.n_stages, J = S + weak.n_stages;
+    int len = 0;
+    if (lane < J) len = lane < S ? strong.stage_n[lane] : weak.stage_n[lane - S];
+    int rank = 0;
+    for (int k = 0; k < J; ++k) {
+        const int lk = __builtin_amdgcn_readlane(len, k);
+        rank += (lk > len || (lk == len && k < lane)) ? 1 : 0;
+    }
+    job_at = 0;
+    int len_at = 0;
+    for (int k = 0; k < J; ++k) {
+        const int rk = __builtin_amdgcn_readlane(rank, k), lk = __builtin_amdgcn_readlane(len, k);
+        if (rk == lane) { job_at = k; len_at = lk; }
+    }
+    // ranks 0 .. WAVES - 1 go to waves 0 .. WAVES - 1 (all have nothing yet); lane w < WAVES keeps wave w's stumps
+    uint32_t mine = wv < J ? 1u << wv : 0u;
+    int      load = lane < WAVES ? len_at : 0;
+    for (int r = WAVES; r < J; ++r) {
+        int best = 0, best_load = __builtin_amdgcn_readlane(load, 0);
+        for (int w = 1; w < WAVES; ++w) {
+            const int lw = __builtin_amdgcn_readlane(load, w);
+            if (lw < best_load) { best = w; best_load = lw; }
+        }
+        const int lr = __builtin_amdgcn_readlane(len_at, r);
+        if (lane == best) load += lr;
+        if (best == wv) mine |= 1u << r;
+    }
+    return mine;
+}
+
+// (list / n_list: only these candidates -- the planes whose pool the NMS tie pass changed)
+// PER = candidates a workgroup takes at a time, WAVES its waves: each wave builds PER / WAVES histograms in a row, and the cascades have a lane per candidate
+// (launch_classify: the builds)
+template <int PER, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void k_classify(BatchDev b, DetectParams prm, CascadeDev strong,
+                                                         CascadeDev weak, const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_list)
+{
+    static_assert(PER % WAVES == 0 && PER <= 64 && (PER & (PER - 1)) == 0, "whole rounds of a histogram per wave; a lane per candidate");
+    __shared__ ClsWgShared<PER, WAVES> sh;
+    const uint32_t total = list ? *n_list : *b.total_cands;
+    const int      tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool fast = strong.all_unit && weak.all_unit;
+    // stage-parallel form: the stages of both cascades are jobs for the waves
+    const bool par = fast && strong.n_stages + weak.n_stages <= CLS_MAX_JOBS && strong.n_stages > 0 && weak.n_stages > 0;
+    int        job_at = 0;
+    uint32_t   my_jobs = 0;
+    if (par) my_jobs = deal_stage_jobs<WAVES>(strong, weak, wv, job_at);
 #ifdef STR_ER_WG_TRACE
 #define CLS_MARK(i) do { if (tid == 0 && blockIdx.x % 8u == 0u && blockIdx.x / 8u < 128u) g_wg_trace[384 + blockIdx.x / 8u][(i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -335,12 +393,12 @@ __global__ __launch_bounds__(CLS64_THREADS) void k_classify(BatchDev b, DetectPa
         const unsigned long long tp0 = wall_clock64();
 #endif
         // ---- phase 1: histograms --------------------------------------------------------------
-        // Every wave works on an ER of its own with scratch of its own (hist[wv], tile[wv], its row): between its steps it only has to wait for
+        // Every wave works on an ER of its own with scratch of its own (tile[wv], its row): between its steps it only has to wait for
         // ITSELF -- a wave's LDS operations are carried out in the order it issues them -- so the steps are separated by a wave-level fence, not
-        // by a workgroup barrier: the 16 waves' ERs differ in size, and a barrier per step had every wave wait for the largest four times per ER.
-        if (run_cascades) {
-            for (int it = 0; it < PER / CLS64_WAVES; ++it) {
-                const uint32_t cpos = c0 + it * CLS64_WAVES + wv;
+        // by a workgroup barrier: the waves' ERs differ in size, and a barrier per step had every wave wait for the largest four times per ER.
+        {
+            for (int it = 0; it < PER / WAVES; ++it) {
+                const uint32_t cpos = c0 + it * WAVES + wv;
                 const bool     ok = cpos < total;
                 const uint32_t cidx = ok && list ? list[cpos] : cpos;
                 int bx = 0, by = 0, bw = 1, bh = 1, stride = 0, inv = 0;
@@ -353,9 +411,9 @@ __global__ __launch_bounds__(CLS64_THREADS) void k_classify(BatchDev b, DetectPa
                     bx = b.ka.box[4 * ks]; by = b.ka.box[4 * ks + 1]; bw = b.ka.box[4 * ks + 2]; bh = b.ka.box[4 * ks + 3];
                     pix = pd.pix; stride = pd.stride; inv = pd.invert;
                 }
-                uint8_t  *tile = sh.u.p1.tile[wv];
+                uint8_t  *tile = sh.tile[wv];
                 if (it == 0) CLS_MARK(5);
-                uint32_t *rowq = reinterpret_cast<uint32_t *>(sh.rows + (size_t)(it * CLS64_WAVES + wv) * CLS_ROW);
+                uint32_t *rowq = reinterpret_cast<uint32_t *>(sh.rows + (size_t)(it * WAVES + wv) * CLS_ROW);
                 // The histogram is counted straight into the ER's packed row: a bin is a byte of it (a cell has 144 pixels, no count passes 255), so a pixel adds
                 // 1 << 8 * (bin & 3) to the dword of its bin -- no carry leaves a byte.
                 for (int k = 0; k < 4; ++k) rowq[lane + 64 * k] = 0;      // (a row starts on a dword, not on 16 bytes: CLS_ROW keeps the rows on different banks)
@@ -464,7 +522,7 @@ __global__ __launch_bounds__(CLS64_THREADS) void k_classify(BatchDev b, DetectPa
                 if (it == 0) CLS_MARK(8);
                 if (it == 0) CLS_MARK(9);
             }
-            __syncthreads();            // every wave's rows are in place; the scratch (aliased by the tables below) is free
+            __syncthreads();            // every wave's rows are in place
         }
         CLS_MARK(1);
 #ifdef STR_ER_PHASE_PROF
@@ -472,20 +530,19 @@ __global__ __launch_bounds__(CLS64_THREADS) void k_classify(BatchDev b, DetectPa
         if (tid == 0) atomicAdd(&g_tile_phase[12], tp1 - tp0);
 #endif
         // ---- phase 2: cascades, one ER per lane ---------------------------------------------------
-        const bool fast = run_cascades && strong.all_unit && weak.all_unit && strong.n_stumps + weak.n_stumps <= CLS_AB_CAP;
-        if (fast) {     // phase 1 is over (barrier above): reuse its scratch for the output tables
-            for (int i = tid; i < 2 * strong.n_stumps; i += CLS64_THREADS) sh.u.ab[i] = strong.ab[i];
-            for (int i = tid; i < 2 * weak.n_stumps; i += CLS64_THREADS) sh.u.ab[2 * strong.n_stumps + i] = weak.ab[i];
-            __syncthreads();
-        }
+        // (a lane beyond PER reads the row of lane & (PER - 1): its sums are nobody's)
+        const uint8_t *row = sh.rows + (size_t)(lane & (PER - 1)) * CLS_ROW;
         CLS_MARK(2);
-        // stage-parallel form: wave w < S + W sums stage w of the strong cascade or stage w - S of the weak one
-        const bool par = fast && strong.n_stages + weak.n_stages <= CLS64_WAVES && strong.n_stages > 0 && weak.n_stages > 0;
         if (par) {
-            if (wv < strong.n_stages + weak.n_stages) {
-                const uint8_t *row = sh.rows + (size_t)lane * CLS_ROW;
-                sh.stage_sum[wv][lane] = wv < strong.n_stages ? lane_stage_fast(strong, wv, row, sh.u.ab)
-                                                              : lane_stage_fast(weak, wv - strong.n_stages, row, sh.u.ab + 2 * strong.n_stumps);
+            const int S = strong.n_stages;
+            for (uint32_t left = my_jobs; left; left &= left - 1) {         // the wave's jobs, longest first
+                const int j = __builtin_amdgcn_readlane(job_at, __builtin_ctz(left));
+                const CascadeDev &c = j < S ? strong : weak;
+                const int         st = j < S ? j : j - S;
+                int               off = 0;
+                for (int i = 0; i < st; ++i) off += c.stage_n[i];
+                const double sum = lane_stumps_fast(c, off, min(c.stage_n[st], max(0, c.n_stumps - off)), row, sh.chunk[wv]);
+                if (lane < PER) sh.stage_sum[j][lane] = sum;
             }
             __syncthreads();
         }
@@ -496,50 +553,55 @@ __global__ __launch_bounds__(CLS64_THREADS) void k_classify(BatchDev b, DetectPa
             const uint32_t cidx = ok && list ? list[cpos] : cpos;
             int    cls = 0;
             double ss = -DBL_MAX, sw = 0;
-            if (run_cascades && par) {
-                ss = cascade_from_stage_sums(strong, &sh.stage_sum[0][lane], 64);
-                if (ss > -DBL_MAX) cls = 1;
-                else {                              // the weak cascade only speaks for what the strong one rejected (src/ER.cpp:521-526)
-                    sw = cascade_from_stage_sums(weak, &sh.stage_sum[strong.n_stages][lane], 64);
-                    if (sw > -DBL_MAX) cls = 2;
+            if (par) {
+                if (ok) {
+                    ss = cascade_from_stage_sums(strong, &sh.stage_sum[0][lane], PER);
+                    if (ss > -DBL_MAX) cls = 1;
+                    else {                              // the weak cascade only speaks for what the strong one rejected (src/ER.cpp:521-526)
+                        sw = cascade_from_stage_sums(weak, &sh.stage_sum[strong.n_stages][lane], PER);
+                        if (sw > -DBL_MAX) cls = 2;
+                    }
                 }
-            } else if (run_cascades) {
-                const uint8_t *row = sh.rows + (size_t)lane * CLS_ROW;
-                ss = fast ? lane_cascade_fast(strong, row, sh.u.ab, ok) : lane_cascade_generic(strong, row, ok);
+            } else {
+                ss = fast ? lane_cascade_fast(strong, row, sh.chunk[0], ok) : lane_cascade_generic(strong, row, ok);
                 const bool need_weak = ok && !(ss > -DBL_MAX);
                 if (ss > -DBL_MAX) cls = 1;
                 if (__any(need_weak)) {
-                    const double w = fast ? lane_cascade_fast(weak, row, sh.u.ab + 2 * strong.n_stumps, need_weak)
-                                          : lane_cascade_generic(weak, row, need_weak);
+                    const double w = fast ? lane_cascade_fast(weak, row, sh.chunk[0], need_weak) : lane_cascade_generic(weak, row, need_weak);
                     if (need_weak) { sw = w; if (sw > -DBL_MAX) cls = 2; }
                 }
             }
-            if (ok) {
-                const int        pi = b.cand_plane[cidx];
-                const PlaneDesc &pd = b.planes[pi];
-                const uint32_t   slot = b.pool[pd.pool_base + (cidx - b.ctr[pi].cand_base)];
-                const size_t     ks = pd.kept_base + slot;
-                CandRec r;
-                r.frame = pd.frame; r.ch = pd.ch; r.pyr = pd.pyr; r.level = b.ka.level[ks]; r.cls = (uint8_t)cls;
-                r.x = b.ka.box[4 * ks]; r.y = b.ka.box[4 * ks + 1]; r.w = b.ka.box[4 * ks + 2]; r.h = b.ka.box[4 * ks + 3];
-                r.area = b.ka.area[ks]; r.key = b.ka.key[ks]; r.node = (int32_t)slot; r.plane = (uint32_t)pi;
-                r.score_strong = ss; r.score_weak = sw;
-                b.cands[cidx] = r;
-                if (cls == 1) atomicAdd(&b.ctr[pi].n_strong, 1u);
-                if (cls == 2) atomicAdd(&b.ctr[pi].n_weak, 1u);
-            }
+            if (ok) write_cand_record(b, cidx, cls, ss, sw);
         }
         CLS_MARK(4);
         __syncthreads();
     }
 }
 
-void launch_classify(hipStream_t s, const BatchDev &b, const DetectParams &p, CascadeDev strong, CascadeDev weak,
-                     int run_cascades, const uint32_t *list, const uint32_t *n_list, bool few)
+// So many workgroups for `cands` candidates, an eighth and a few more as a margin (the count is the previous batch's: a hint -- the kernels' loops cover any count)
+static int hinted_grid(uint32_t cands, int per, int full)
 {
-    static_assert(CLS_PER_BLOCK == 64 && CLS64_WAVES == 16, "the two builds: four candidates a wave, or one");
-    if (few) hipLaunchKernelGGL(k_classify<16>, dim3(list ? 64 : 512), dim3(CLS64_THREADS), 0, s, b, p, strong, weak, run_cascades, list, n_list);
-    else hipLaunchKernelGGL(k_classify<64>, dim3(list ? 64 : 1024), dim3(CLS64_THREADS), 0, s, b, p, strong, weak, run_cascades, list, n_list);
+    if (!cands) return full;
+    const uint64_t wgs = ((uint64_t)cands + per - 1) / per;
+    return (int)std::min<uint64_t>((uint64_t)full, std::max<uint64_t>(1, wgs + wgs / 8 + 8));
+}
+
+// few: a call of at most SPEC_PLANES planes (a frame or two, ~1000 candidates, an empty chip): one candidate per wave in the histogram phase, 16 a workgroup.
+// Otherwise the batch build.  hint: the candidates of the context's previous batch (0: not known); force_grid, form: developer knobs (str_er_ctx.h).
+void launch_classify(hipStream_t s, const BatchDev &b, const DetectParams &p, CascadeDev strong, CascadeDev weak,
+                     int run_cascades, const uint32_t *list, const uint32_t *n_list, bool few, uint32_t hint, int force_grid, int form)
+{
+    if (!run_cascades) {
+        const int g = force_grid > 0 ? std::min(force_grid, 1024) : (list ? 64 : hinted_grid(hint, CAND_REC_THREADS, 1024));
+        hipLaunchKernelGGL(k_cand_records, dim3(g), dim3(CAND_REC_THREADS), 0, s, b, list, n_list);
+        return;
+    }
+    const int per = few ? CLS_FEW_PER : (form == 64 ? 64 : CLS_BATCH_PER);
+    const int g = force_grid > 0 ? std::min(force_grid, 1024) : (list ? 64 : hinted_grid(hint, per, few ? 512 : 1024));
+    if (few) hipLaunchKernelGGL((k_classify<CLS_FEW_PER, CLS_FEW_WAVES>), dim3(g), dim3(CLS_FEW_WAVES * 64), 0, s, b, p, strong, weak, list, n_list);
+    else if (form == 64) hipLaunchKernelGGL((k_classify<64, 8>), dim3(g), dim3(8 * 64), 0, s, b, p, strong, weak, list, n_list);
+    else if (form == 8) hipLaunchKernelGGL((k_classify<CLS_BATCH_PER, 8>), dim3(g), dim3(8 * 64), 0, s, b, p, strong, weak, list, n_list);
+    else hipLaunchKernelGGL((k_classify<CLS_BATCH_PER, CLS_BATCH_WAVES>), dim3(g), dim3(CLS_BATCH_WAVES * 64), 0, s, b, p, strong, weak, list, n_list);
 }
 
 // Single-stage entry points (str_er_classify_boxes / str_er_lbp_hist): explicit boxes.

@@ -118,7 +118,8 @@ void launch_nms_resolve(hipStream_t s, const BatchDev &b, const DetectParams &p,
 void launch_cand_prefix(hipStream_t s, const BatchDev &b);
 // classify (src/ER.cpp:507-528) over the packed pool of the batch.
 void launch_classify(hipStream_t s, const BatchDev &b, const DetectParams &p, CascadeDev strong,
-                     CascadeDev weak, int run_cascades, const uint32_t *list = nullptr, const uint32_t *n_list = nullptr, bool few = false);      // (few: a call of a frame or two -- 16 candidates a workgroup instead of 64)
+                     CascadeDev weak, int run_cascades, const uint32_t *list = nullptr, const uint32_t *n_list = nullptr, bool few = false,
+                     uint32_t hint = 0, int force_grid = 0, int form = 0);      // (few: a call of a frame or two -- 16 candidates on 16 waves instead of 32 on 4; hint: the previous batch's candidates, for the grid)
 // after the NMS tie pass: new candidate offsets (b.cands / b.cand_plane = the second set of buffers), the records of unchanged planes
 // moved over from `from`, the candidates of the changed planes listed in redo[0 .. *n_redo) for launch_classify
 // (calls of a frame or two) the counter block and the first candidate records to device-addressable host memory, one launch

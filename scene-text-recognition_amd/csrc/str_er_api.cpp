@@ -913,7 +913,9 @@ static int enqueue_batch(BatchRun &R, BatchSlot &slot, bool pre_recorded)
     // and the host knows how many of them are strong / weak (result_track): the colour pass is sized for exactly those boxes.
     if (stages & STR_ER_STAGE_NMS) {
         launch_cand_prefix(s, bd);
-        launch_classify(s, bd, dp, c->casc[0].dev, c->casc[1].dev, (stages & STR_ER_STAGE_CLASSIFY) ? 1 : 0, nullptr, nullptr, np <= SPEC_PLANES);
+        // (the grid from the candidates of the context's previous batch: a hint, 0 after an empty batch and on the first -- the full grid)
+        launch_classify(s, bd, dp, c->casc[0].dev, c->casc[1].dev, (stages & STR_ER_STAGE_CLASSIFY) ? 1 : 0, nullptr, nullptr, np <= SPEC_PLANES,
+                        c->last_total, c->dbg_cls_grid, c->dbg_cls_form);
     }
     rec(c, "classify", nullptr, true);
     R.i_cls = c->n_ev - 1;
@@ -1030,7 +1032,8 @@ static int settle_batch(BatchRun &R)
             R.bd = make_batchdev(c, b);
             uint32_t *n_redo = c->d_redo + c->pool_total;
             launch_cand_reprefix(sp, R.bd, first, c->d_redo, n_redo);
-            launch_classify(sp, R.bd, R.dp, c->casc[0].dev, c->casc[1].dev, (stages & STR_ER_STAGE_CLASSIFY) ? 1 : 0, c->d_redo, n_redo, true);
+            launch_classify(sp, R.bd, R.dp, c->casc[0].dev, c->casc[1].dev, (stages & STR_ER_STAGE_CLASSIFY) ? 1 : 0, c->d_redo, n_redo, np <= SPEC_PLANES,
+                            0, c->dbg_cls_grid, c->dbg_cls_form);
             if (R.ocr_cap && *ocr_pinned(c, R.ocr_cap).count <= R.ocr_cap) {
                 // the batch was scored behind classify: the candidates of the re-made planes are scored behind THEIR classify, again without a trip to the
                 // host -- as many as the device lists (the scratch is sized for the whole batch)
@@ -1646,6 +1649,8 @@ int str_er_create(const str_er_params *p, str_er_ctx **out)
     if (const char *g = std::getenv("STR_ER_GROUP_KERNEL")) c->dbg_group[2] = std::atoi(g);
     if (const char *g = std::getenv("STR_ER_GROUP_BINS")) c->group_bins = std::max(0, std::min(4, std::atoi(g)));      // developer switch: 0 = a launch per class of planes, 4 / 2 = four / two tables
     if (const char *g = std::getenv("STR_ER_GROUP_GRID")) c->dbg_group_grid = std::max(0, std::atoi(g));
+    if (const char *g = std::getenv("STR_ER_CLASSIFY_GRID")) c->dbg_cls_grid = std::max(0, std::atoi(g));
+    if (const char *g = std::getenv("STR_ER_CLASSIFY_FORM")) c->dbg_cls_form = std::atoi(g);
     if (const char *t2 = std::getenv("STR_ER_TILE2")) c->t2_mode = std::max(0, std::min(2, std::atoi(t2)));      // developer switch: 0 k_tile_tree only, 2 k_tile_tree2 on every plane
     c->dbg_tile_only = std::getenv("STR_ER_DEBUG_TILE_ONLY") != nullptr;
     if (c->dbg_tile_only) c->profiling = true;

@@ -358,6 +358,8 @@ struct str_er_ctx {
     uint32_t *d_bin_list = nullptr;
     int       group_bins = 1;                         // STR_ER_GROUP_BINS: 0 the launches per class of PLANE; else by record count: three tables (512 / 1024 / 2528 records), 4: four (+ 2048), 2: two (512 / 2528)
     int       dbg_group_grid = 0;                     // STR_ER_GROUP_GRID: so many workgroups per table, whatever its list holds (developer knob: the kernel's loop)
+    int       dbg_cls_grid = 0;                       // STR_ER_CLASSIFY_GRID: so many workgroups of k_classify / k_cand_records, whatever the batch pools (developer knob: the kernels' loops)
+    int       dbg_cls_form = 0;                       // STR_ER_CLASSIFY_FORM: another batch build of k_classify (developer knob, for measuring the forms that lost): 8 = 32 candidates on 8 waves, 64 = 64 on 8 waves
     uint32_t  bin_hint[4] = {0, 0, 0, 0}, bin_hint_groups = 0; bool bin_hint_valid = false;      // the lists' lengths in the context's last binned batch (of so many groups): the grids of the next one like it
     uint32_t  last_group_stats[6] = {0, 0, 0, 0, 0, 0};                     // str_er_last_group_stats: groups per table, listed for k_seam_undone, of one tile
     uint8_t  *d_group_done = nullptr;                 // per group of tiles: joined in LDS (k_group_merge -> k_seam)
