@@ -1,6 +1,7 @@
 """Region descriptors (STR_ER_WANT_SHAPES, str_er_er_shapes) on the GPU: every record against the numpy / scipy reference of the
 contract on the candidate's mask and plane, nothing else of a call changed by the flag, lists / NV12 / the stream / device frames,
-hand-made shapes for every size class of the kernels, the single-stage call against the fused one, and the errors."""
+hand-made shapes for every size class of the kernels and for boxes wider than 4096 pixels, the single-stage call against the fused one,
+and the errors."""
 import ctypes as C
 import os
 import subprocess
@@ -10,6 +11,7 @@ import numpy as np
 import pytest
 from scipy import ndimage
 
+from box_round_cases import mask_class
 from shape_ref import FOUR, as_dict, shape_ref
 
 pytestmark = pytest.mark.gpu
@@ -281,6 +283,93 @@ def test_er_shapes_hand_made(S, cascade_paths, oracle, step):
     assert ring["euler"] == 0 and ring["hole_pixels"] == 25                  # the island is hole
     assert as_dict(f.er_shapes(dg, _regions(S, [(1, 1, 4, 4, 41, 0)]))[0])["euler"] == 0
     assert as_dict(f.er_shapes(dg, _regions(S, [(10, 1, 3, 3, 50, 0)]))[0])["hole_pixels"] == 0
+    f.close()
+
+
+# ---- boxes wider than 4096 pixels: a lane owns 2 .. 4 words of a row, and neighbour bits cross from lane 63 to lane 0 of the next set ----
+
+# (w, h): each words-per-lane count on both sides of the LDS / scratch line (h * ceil(w / 64) <= 1024 is the LDS class)
+WIDE = ((4097, 15), (4097, 16), (4160, 15), (8193, 7), (8193, 8), (12289, 5), (12289, 6), (16384, 4), (16384, 5))
+
+
+def _border_holes(W, H):
+    """Level 0 everywhere but for wall pixels astride every word border x = 64 j, in three forms in turn: a 2 x 1 hole on the columns
+    64 j - 1 and 64 j; two hole pixels that touch only diagonally across the border (one 8-connected hole); a pixel at 64 j - 1 whose
+    only way out is the diagonal through a wall pixel of row 0 at column 64 j (a leak, not a hole)."""
+    p = np.zeros((H, W), np.uint8)
+    for j in range(1, (W - 1) // 64 + 1):
+        x = 64 * j
+        if j % 3 == 1:
+            p[1, x - 1] = p[1, x] = 255
+        elif j % 3 == 2:
+            p[1, x - 1] = p[2, x] = 255
+        else:
+            p[1, x - 1] = p[0, x] = 255
+    return p, 0, 0, 0
+
+
+def _ragged(W, H, level_of):
+    """A grey ramp under a ragged region, 255 elsewhere.  The rows h / 6, 3 h / 6 and 5 h / 6 (the crossing rows) start near column 0, so
+    their runs cross every word border; the others start past column 4096 -- in the lane's second, third or fourth word of the row, a
+    few columns further each row -- so their extents, and the hull's left side, come from those words alone.  Where the last word
+    set has room the right ends are ragged as well.  The level is the highest there is: the ramp's values above 251 are pinholes
+    (the crossing rows, one pixel high for most of their length, are capped at 251: a pinhole would cut them)."""
+    wpl = ((W + 63) // 64 + 63) // 64
+    yy, xx = np.mgrid[0:H, 0:W]
+    ramp = ((7 * xx + 3 * yy) % 256).astype(np.uint8)
+    p = np.full((H, W), 255, np.uint8)
+    room = W - 3 > 4096 * (wpl - 1) + 3 * H + 1
+    for y in range(H):
+        crossing = y in (H // 6, 3 * H // 6, 5 * H // 6)
+        xl = 2 + y if crossing else min(4096 * (1 + y % max(1, wpl - 1)) + 3 * y + 1, W - 1)
+        xr = W - y % 3 if room else W
+        p[y, xl:xr] = np.minimum(ramp[y, xl:xr], 251) if crossing else ramp[y, xl:xr]
+    level = int(level_of[251])
+    ky = H // 6
+    kx = int(np.nonzero(level_of[p[ky]] <= level)[0][0])
+    return p, kx, ky, level
+
+
+def test_er_shapes_wider_than_4096(S, cascade_paths, oracle):
+    step = 8
+    f = _ctx(S, cascade_paths, max_width=16384, max_height=600, max_frames=1, thresh_step=step)
+    lut = oracle.quant_lut(step)
+    assert int(lut[251]) == 255 // step < int(lut[252])
+    assert [mask_class(w, h) for w, h in WIDE] == [1, 2, 1, 1, 2, 1, 2, 1, 2] and 4 * 256 == 1024
+    assert [((w + 63) // 64 + 63) // 64 for w, h in WIDE] == [2, 2, 2, 3, 3, 4, 4, 4, 4]
+    SW = 16384
+    stack = np.full((2 * sum(h for _, h in WIDE), SW), 255, np.uint8)       # every plane below, one under the other, for the mixed call
+    boxes, exps, y0 = [], [], 0
+    for kind in ("holes", "ragged"):
+        for w, h in WIDE:
+            p, kx, ky, level = _border_holes(w, h) if kind == "holes" else _ragged(w, h, lut)
+            exp = _expect(lut[p], p, 0, 0, w, h, ky * w + kx, level)
+            if kind == "holes":                 # a hole and a leak on every word border, the borders between the lanes' word sets among them
+                assert exp["hole_pixels"] > 0 and exp["euler"] < 0 and exp["crossings"][0] > 2, (w, h, exp)
+                if (w, h) in ((4097, 15), (16384, 4)):
+                    assert (exp["hole_pixels"], exp["euler"]) == {4097: (84, -41), 16384: (340, -169)}[w]
+            else:                               # one region: every allowed pixel; rows that start past column 4096; runs on the crossing rows
+                assert exp["pixels"] == int((lut[p] <= level).sum()) and min(exp["crossings"]) >= 2
+                starts = [int(np.nonzero(row != 255)[0][0]) for row in p]
+                assert max(starts) >= 4096 and min(starts) < 64 and exp["grey_sum2"] > exp["grey_sum"] > 0
+            got = f.er_shapes(p, _regions(S, [(0, 0, w, h, ky * w + kx, level)]))
+            assert as_dict(got[0]) == exp, (kind, w, h)
+            stack[y0:y0 + h, :w] = p
+            boxes.append((0, y0, w, h, (y0 + ky) * SW + kx, level))
+            exps.append(exp)
+            y0 += h
+    # all of them in one call, and two boxes of the small class between them: the classes and the slots mixed
+    q = lut[stack]
+    for x, y, w, h in ((0, 0, 64, 15), (4090, 31, 64, 15)):
+        boxes.append((x, y, w, h, y * SW + x, 0))
+        exps.append(_expect(q, stack, *boxes[-1]))
+    order = list(range(len(boxes) - 1, -1, -1))
+    order.insert(5, order.pop()); order.insert(11, order.pop(0))
+    assert sorted(order) == list(range(len(boxes))) and {mask_class(b[2], b[3]) for b in boxes} == {0, 1, 2}
+    got = f.er_shapes(stack, _regions(S, [boxes[i] for i in order]))
+    assert len(got) == len(order)
+    for rec, i in zip(got, order):
+        assert as_dict(rec) == exps[i], boxes[i]
     f.close()
 
 

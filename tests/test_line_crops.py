@@ -1,7 +1,8 @@
 """Line crops on the GPU (STR_ER_WANT_LINE_CROPS / _GLYPHS, str_er_line_crops): every record against the numpy geometry of the
 contract, every grey byte against the numpy sampler on the Y plane of its (frame, pyr), every glyph byte against the nearest sample of
 the union of the member masks; nothing else of a call changed by the flags; lists, NV12, the stream and device frames against one
-call per frame; the crop settings; errors; the single-stage call against the fused one; the C++ example."""
+call per frame; the crop settings; hand-made geometry at the kernel's own edges; errors; the single-stage call against the fused one;
+the C++ example."""
 import importlib.util
 import os
 import subprocess
@@ -237,6 +238,109 @@ def test_crop_settings(S, cascade_paths, oracle, height, max_width, pad):
         assert (res.line_crops["width"] == 16).any()               # a line squeezed to max_width
     batch, widths = res.line_crop_batch()
     assert batch.shape == (len(res.texts), height, int(widths.max()))
+    f.close()
+
+
+# ---- str_er_line_crops on hand-made geometry: the kernel's own edges, placed exactly ------------------------------------------------------
+# The detector's lines have slopes near 0, lie inside the frame and get heights that are multiples of 8.  str_er_line_crops takes any
+# boxes, so these cases put the taps where the kernel can go wrong: clamped on each side of the plane, at negative source coordinates,
+# along steep slopes, many source pixels apart, and in crops whose 4-byte quads wrap from one row to the next or end with 1 to 3 bytes.
+
+HAND_PW, HAND_PH = 97, 61
+
+
+def _taps(g, pw, ph):
+    """Of the reference's taps of geometry g on a pw x ph plane: how many lie left of, right of, above and below the plane, and (sx, sy)."""
+    sx, sy = REF._coords(g)
+    x0, y0 = sx >> 16, sy >> 16
+    return {"left": int((x0 < 0).sum()), "right": int((x0 + 1 > pw - 1).sum()), "above": int((y0 < 0).sum()), "below": int((y0 + 1 > ph - 1).sum()),
+            "any": int(((x0 < 0) | (x0 + 1 > pw - 1) | (y0 < 0) | (y0 + 1 > ph - 1)).sum()), "n": int(x0.size)}, sx, sy
+
+
+def _hand_cases():
+    """[(name, (height, max_width, pad), [(boxes, slope), ...])]: the lines of one entry go through one call at its settings."""
+    return [("top_left", (32, 1024, 0.25), [([(0, 0, 40, 14)], 0.3)]),
+            ("bottom_right", (48, 1024, 0.25), [([(70, 47, 27, 14)], -0.4)]),
+            ("whole_plane", (16, 1024, 0.125), [([(0, 0, HAND_PW, HAND_PH)], 3.0)]),
+            ("outside_and_column", (32, 1024, 0.0), [([(-40, -20, 30, 10)], 0.0), ([(40, 10, 1, 40)], 0.0)]),
+            ("squeezed", (32, 5, 0.125), [([(0, 25, HAND_PW, 6)], 0.01)]),
+            ("tall_padded", (256, 8192, 1.0), [([(60, 40, 18, 19), (82, 42, 18, 15)], 0.0)]),
+            ("height_9", (9, 1024, 0.0), [([(10, 10, w, 9)], 0.0) for w in (13, 14, 15)] + [([(3, 30, 21, 9)], 0.25)]),
+            ("height_11", (11, 1024, 0.0), [([(20, 5, w, 11)], 0.0) for w in (5, 6, 7)] + [([(50, 40, 17, 11)], -0.3)])]
+
+
+def _check_reaches(name, lines, settings):
+    """What each case was made for, from the reference's own coordinates: a later change of the numbers cannot empty a case."""
+    gs = [REF.geometry(b, s, *settings) for b, s in lines]
+    t, sx, sy = _taps(gs[0], HAND_PW, HAND_PH)
+    if name == "top_left":
+        assert t["left"] > 0 and t["above"] > 0
+        assert (((sx >> 8) & 255)[sx < 0] != 0).any() and (((sy >> 8) & 255)[sy < 0] != 0).any()       # negative coordinates with a fraction
+    elif name == "bottom_right":
+        assert t["right"] > 0 and t["below"] > 0 and gs[0][0] == 59 and gs[0][0] % 4 == 3
+    elif name == "whole_plane":
+        assert min(t["left"], t["right"], t["above"], t["below"]) > 0 and abs(gs[0][5]) > abs(gs[0][4])           # steep: uy beyond ux
+    elif name == "outside_and_column":
+        assert ((sx >> 16) + 1 <= 0).all() and ((sy >> 16) + 1 <= 0).all()                                       # every tap is pixel (0, 0)
+        assert gs[1][0] == 1
+    elif name == "squeezed":
+        assert gs[0][0] == 5 and gs[0][4] >= 15 * 65536                                                           # many source pixels a column
+    elif name == "tall_padded":
+        assert gs[0][:2] == (351, 256) and 3 * t["any"] >= t["n"]
+    else:
+        assert {g[0] * g[1] % 4 for g in gs} == {1, 2, 3} and all(g[0] % 4 for g in gs)                           # a last quad of 1, 2 and 3 bytes
+
+
+def _run_hand(f, plane, name, settings, lines):
+    """All lines of a case in one call and one at a time: records, layout, padding, and every byte against the numpy sampler."""
+    f.set_line_crop(*settings)
+    boxes = np.array([b for bs, _ in lines for b in bs])
+    count = [len(bs) for bs, _ in lines]
+    first = np.concatenate([[0], np.cumsum(count)[:-1]])
+    recs, pixels = f.line_crops(plane, boxes, first, count, [s for _, s in lines])
+    assert len(recs) == len(lines)
+    off, crops = 0, []
+    for rec, (bs, s) in zip(recs, lines):
+        exp = REF.geometry(bs, s, *settings)
+        got = REF.fields(rec)
+        assert got[:2] == exp[:2], name
+        assert all(abs(a - b) <= 1 for a, b in zip(got[2:], exp[2:])), (name, got, exp)
+        assert int(rec["pix_off"]) == off and off % 4 == 0
+        nb = got[0] * got[1]
+        crop = pixels[off:off + nb].reshape(got[1], got[0])
+        assert (crop == REF.sample_grey(plane, got)).all(), (name, plane.shape, bs)
+        off += (nb + 3) // 4 * 4
+        assert not pixels[int(rec["pix_off"]) + nb:off].any(), name          # the padding between the crops
+        crops.append(crop)
+    assert off == len(pixels)
+    for k, (bs, s) in enumerate(lines):
+        r1, p1 = f.line_crops(plane, np.array(bs), [0], [len(bs)], [s])
+        assert REF.fields(r1[0]) == REF.fields(recs[k]) and int(r1[0]["pix_off"]) == 0
+        assert p1[:crops[k].size].tobytes() == crops[k].tobytes() and len(p1) == (crops[k].size + 3) // 4 * 4 and not p1[crops[k].size:].any()
+    return crops
+
+
+def test_line_crops_hand_made_geometry(S, cascade_paths):
+    f = _ctx(S, cascade_paths, max_width=640, max_height=480, max_frames=1)
+    rng = np.random.default_rng(61)
+    noise = rng.integers(0, 256, (HAND_PH, HAND_PW), dtype=np.uint8)
+    noise[0, 0], noise[HAND_PH - 1, HAND_PW - 1], noise[0, HAND_PW - 1], noise[HAND_PH - 1, 0] = 7, 255, 0, 200
+    cases = _hand_cases()
+    for name, settings, lines in cases:
+        _check_reaches(name, lines, settings)
+        crops = _run_hand(f, noise, name, settings, lines)
+        if name == "outside_and_column":
+            assert (crops[0] == 7).all()                                    # the corner pixel alone
+    # planes one pixel wide or high: every tap is clamped along that axis
+    for shape in ((HAND_PH, 1), (1, HAND_PW), (1, 1)):
+        thin = rng.integers(0, 256, shape, dtype=np.uint8)
+        for name, settings, lines in cases:
+            _run_hand(f, thin, name, settings, lines)
+    # interpolation between equal values, and the rounding, must not lose a level at the top
+    white = np.full((HAND_PH, HAND_PW), 255, np.uint8)
+    for name, settings, lines in cases:
+        assert all((c == 255).all() for c in _run_hand(f, white, name, settings, lines)), name
+    f.set_line_crop()
     f.close()
 
 
