@@ -697,7 +697,8 @@ typedef struct str_er_pool_decode {
  *     decoded: cost = -1 and the four counts are 0.
  *   Limits: runs are split in the image only with STR_ER_WANT_RUN_SPLIT (str_er_run_split), then the rows are those of the word's
  *     parts, a segmentation fixed ahead of the table; segmentation and string chosen together over all pieces are a separate output,
- *     str_er_lattice_decode (STR_ER_WANT_LATTICE_DECODE); one path per word, no margins; the table is the caller's.  The bridge from a table of
+ *     str_er_lattice_decode (STR_ER_WANT_LATTICE_DECODE); one path per word -- how far the next reading of every run lies from it is a
+ *     separate output, str_er_word_margin (str_er_set_word_margin); the table is the caller's.  The bridge from a table of
  *     transition probabilities (str_er_bigram_from_probs) takes 65 x 65 doubles as P(b after a); whether the floats of the
  *     reference's dictionary/tp_table.txt are such probabilities has not been checked, and nothing beyond that reading is promised. */
 typedef struct str_er_word_decode {
@@ -705,6 +706,37 @@ typedef struct str_er_word_decode {
     int32_t  n_chars, n_sub;              /*  8, 12                                   */
     int32_t  n_del, n_ins;                /* 16, 20                                   */
 } str_er_word_decode;        /* 24 bytes; one per word of str_er_result_words()       */
+
+/* The margins of a decoded word (str_er_set_word_margin beside STR_ER_WANT_WORD_DECODE, str_er_word_margins): the min-marginals of
+ * the recurrence of str_er_word_decode -- for every run of the word and every reading of it the cost of the cheapest whole path that
+ * reads the run that way -- and from them how much more the cheapest path costs that reads some run differently from the decoded
+ * string.  A definition of this library; integers only, exact, and the host states the same rules (str_er_word_margins_host).
+ *   Take a word with the rows C_1 .. C_m, 1 <= m <= 32.  B, INS, DEL, E = 65, INF and the forward values V_i[a], U_i[a] are those of
+ *     str_er_word_decode; S_i[b] is its SUB value before DEL is compared: min over a of (V_{i-1}[a] + B[a][b]) + C_i[b], for b < 65.
+ *   Backward values, in int32: G_m[a] = B[a][E] for a in 0 .. 65.  For i = m .. 1: GU_i[a] = G_i[a]; if INS > 0, for b < 65:
+ *     GU_i[b] = min(G_i[b], min over c < 65 of (B[b][c] + G_i[c]) + INS).  Then G_{i-1}[a] = min over b < 65 of (B[a][b] + C_i[b] +
+ *     GU_i[b]), and if DEL > 0 that value is also min-ed with DEL + GU_i[a].  min over a of (V_i[a] + G_i[a]) = cost for every i, and
+ *     G_0[E] = cost.
+ *   Marginals, 66 per row: M_i[b] = S_i[b] + GU_i[b] for b < 65, run i read as b; M_i[65] = min over a in 0 .. 65 of (V_{i-1}[a] + DEL
+ *     + GU_i[a]) if DEL > 0, else -1: run i dropped.  Every path does exactly one of these at run i, so the minimum of M_i[x] over the
+ *     entries >= 0 is cost.  Every marginal that exists is at most 16575 (the all-SUB path); INF never wins.
+ *   Reading of a row: x_i is the label of the character of the word's decoded string whose source is i-1 with bit 7 clear, or 65 if
+ *     there is none.  M_i[x_i] = cost.
+ *   Margin of a row: margin_i is the minimum of M_i[x] over x != x_i with M_i[x] >= 0, minus cost: >= 0, and 0 on a tie; alt_i is the
+ *     smallest such x that attains it (there are 65 labels: it always exists).
+ *   Record: margin = min over i of margin_i, row the smallest word-relative i-1 that attains it, read and alt those of that row.  So
+ *     margin is the extra cost of the cheapest path that reads some run differently.  All four fields are -1 for m = 0 and for m > 32
+ *     (not decoded).
+ *   Per word, beside the record: 32 int32 row margins, -1 past m; 32 bytes of row readings and 32 of row alternatives, 0xFF past m;
+ *     on request (str_er_word_margins) the marginals, 32 x 66 int32, -1 past m and where no path exists.  The layout is fixed per
+ *     word, as for the decoder's labels and sources.
+ *   Limits: an inserted character has no row, so it has no margin of its own, and paths that differ only in insertions are not told
+ *     apart.  This covers the word decoder only: no lattice decode, no tracks, no pool.  Nothing is calibrated against labelled text:
+ *     a margin is a cost difference in the unit of the cost rows, not a probability.                                                */
+typedef struct str_er_word_margin {
+    int32_t  margin, row;                 /*  0,  4                                   */
+    int32_t  read, alt;                   /*  8, 12                                   */
+} str_er_word_margin;        /* 16 bytes; one per word of str_er_result_words()       */
 
 /* The decoding of a word track without a lexicon (STR_ER_WANT_TRACK_DECODE, str_er_decode_tracks): one string for all members of a
  * word track of str_er_word_link, a median string of the members under their cost rows and the bigram table, reached from the members'
@@ -1318,6 +1350,22 @@ int str_er_decode_words(str_er_ctx *ctx, const uint8_t *costs, int32_t n_runs, c
  * no context, no GPU.                                                                                                              */
 int str_er_decode_words_host(const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
                              const uint8_t *bigram, int32_t ins, int32_t del, str_er_word_decode *dec, uint8_t *chars, uint8_t *src);
+/* Whether a detect call with STR_ER_WANT_WORD_DECODE also makes the margins of its words (str_er_word_margin): on != 0 switches them
+ * on; off by default.  A context setting, not a stage flag: without STR_ER_WANT_WORD_DECODE it does nothing, and while it is off no
+ * call does anything more than before.  A stream's contexts: str_er_stream_context.                                                */
+int str_er_set_word_margin(str_er_ctx *ctx, int32_t on);
+/* The margins (str_er_word_margin) on the caller's cost rows, on the GPU, under the context's table and the INS / DEL of
+ * str_er_set_word_decode: the arguments up to n_words and their checks are those of str_er_decode_words, and the decoder runs on
+ * these rows first.  margins receives n_words records, row_margin 32 int32 per word, row_read and row_alt 32 bytes per word each,
+ * marginals (NULL: not wanted) 32 x 66 int32 per word.  Words may share rows.  STR_ER_ESTATE without a table; STR_ER_EINVAL on a
+ * word outside the rows.  n_words = 0 is fine.                                                                                    */
+int str_er_word_margins(str_er_ctx *ctx, const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
+                        str_er_word_margin *margins, int32_t *row_margin, uint8_t *row_read, uint8_t *row_alt, int32_t *marginals);
+/* The same rules on one host thread, with the table and INS / DEL as arguments (with the checks of str_er_set_word_decode).  Pure:
+ * no context, no GPU.                                                                                                              */
+int str_er_word_margins_host(const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
+                             const uint8_t *bigram, int32_t ins, int32_t del, str_er_word_margin *margins, int32_t *row_margin, uint8_t *row_read,
+                             uint8_t *row_alt, int32_t *marginals);
 /* INS and DEL (1 .. 255) and the number of polish rounds (0 .. 64) of str_er_track_decode; defaults 64, 64 and 8.  Anything else ->
  * STR_ER_EINVAL, the context unchanged.  A stream's contexts: str_er_stream_context.                                               */
 int str_er_set_track_decode(str_er_ctx *ctx, int32_t ins, int32_t del, int32_t rounds);
@@ -1724,6 +1772,14 @@ const double            *str_er_result_run_probs(const str_er_result *r, uint64_
 const str_er_word_decode *str_er_result_word_decodes(const str_er_result *r, int32_t *n);
 const uint8_t            *str_er_result_word_decode_chars(const str_er_result *r, uint64_t *n_bytes);
 const uint8_t            *str_er_result_word_decode_src(const str_er_result *r, uint64_t *n_bytes);
+/* With STR_ER_WANT_WORD_DECODE on a context whose str_er_set_word_margin is on (str_er_word_margin): one record per word of
+ * str_er_result_words(), 32 int32 row margins per word (n_bytes: 128 per word) and 32 bytes of row readings and of row alternatives
+ * per word; with STR_ER_WANT_RUN_SPLIT the rows are the word's parts, as for the decoder.  Each returns NULL and 0 when the call made
+ * none; a call without words returns empty arrays (not NULL).                                                                      */
+const str_er_word_margin *str_er_result_word_margins(const str_er_result *r, int32_t *n);
+const int32_t            *str_er_result_word_row_margins(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t            *str_er_result_word_row_reads(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t            *str_er_result_word_row_alts(const str_er_result *r, uint64_t *n_bytes);
 /* With STR_ER_WANT_RUN_SPLIT (str_er_run_split): one split record per run of str_er_result_line_runs(); the pieces they index, with
  * one reading and one 65-byte cost row per piece; the parts of the words back to back in word order; one record per word of
  * str_er_result_words().  NULL (and *n = 0) without the flag.                                                                       */

@@ -134,6 +134,10 @@ assert POOL_DECODE_DTYPE.itemsize == 40
 # characters of the string and the runs read, dropped and the characters inserted
 WORD_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
 assert WORD_DECODE_DTYPE.itemsize == 24
+# str_er_word_margin: per word, the extra cost of the cheapest path that reads some run differently from the decoded string, the
+# word-relative row where it does, the decoded reading of that row and the alternative (65: the row dropped); all -1: not decoded
+WORD_MARGIN_DTYPE = np.dtype([("margin", "<i4"), ("row", "<i4"), ("read", "<i4"), ("alt", "<i4")])
+assert WORD_MARGIN_DTYPE.itemsize == 16
 # str_er_word_match: per word, the best and the second-best lexicon entry with their costs (-1: none), the cost of the word's own
 # reading and the number of entries tried
 WORD_MATCH_DTYPE = np.dtype([("entry", "<i4"), ("cost", "<i4"), ("second_entry", "<i4"), ("second_cost", "<i4"), ("free_cost", "<i4"), ("n_tried", "<i4")])
@@ -454,6 +458,14 @@ def load_library():
     L.str_er_result_word_decode_chars.restype = vp
     L.str_er_result_word_decode_src.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.str_er_result_word_decode_src.restype = vp
+    L.str_er_set_word_margin.argtypes = [vp, C.c_int32]
+    L.str_er_word_margins.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
+    L.str_er_word_margins_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
+    L.str_er_result_word_margins.argtypes = [vp, i32p]
+    L.str_er_result_word_margins.restype = vp
+    for fn in (L.str_er_result_word_row_margins, L.str_er_result_word_row_reads, L.str_er_result_word_row_alts):
+        fn.argtypes = [vp, C.POINTER(C.c_uint64)]
+        fn.restype = vp
     L.str_er_ocr_char.argtypes = [C.c_int32]
     L.str_er_ocr_char.restype = C.c_int32
     for name, cnt in (("run_splits", i32p), ("run_pieces", i32p), ("piece_reads", i32p), ("piece_costs", C.POINTER(C.c_uint64)), ("split_parts", i32p),
@@ -738,6 +750,11 @@ class Result:
             raise ValueError("the result has no word decodes (pass WANT_WORD_DECODE / want_word_decode=True)")
         return table
 
+    def _word_margin_table(self, table):
+        if table is None:
+            raise ValueError("the result has no word margins (ERFilter.set_word_margin(True) and WANT_WORD_DECODE / want_word_decode=True)")
+        return table
+
     def _run_split_table(self, table):
         if table is None:
             raise ValueError("the result has no run splits (pass WANT_RUN_SPLIT / want_run_split=True)")
@@ -916,6 +933,41 @@ class Result:
         if int(d["cost"]) < 0:
             return [(first + k, False) for k in range(int(self.words[w]["n_runs"]))]
         return [(first + (int(v) & 0x7F), bool(int(v) & 0x80)) for v in self.word_decode_src[w, :int(d["n_chars"])]]
+
+    @property
+    def word_margins(self) -> np.ndarray:
+        """With set_word_margin(True) and WANT_WORD_DECODE: WORD_MARGIN_DTYPE per word of words, in the same order."""
+        return self._word_margin_table(getattr(self, "_word_margins", None))
+
+    @property
+    def word_row_margins(self) -> np.ndarray:
+        """With set_word_margin(True) and WANT_WORD_DECODE: (n words, 32) int32, the margin of every row of every word, -1 past its rows."""
+        return self._word_margin_table(getattr(self, "_word_row_margins", None))
+
+    @property
+    def word_row_reads(self) -> np.ndarray:
+        """With set_word_margin(True) and WANT_WORD_DECODE: (n words, 32) uint8, how the decoded string reads every row (65: dropped),
+        0xFF past the word's rows."""
+        return self._word_margin_table(getattr(self, "_word_row_reads", None))
+
+    @property
+    def word_row_alts(self) -> np.ndarray:
+        """With set_word_margin(True) and WANT_WORD_DECODE: (n words, 32) uint8, the cheapest other reading of every row (65: dropped),
+        0xFF past the word's rows."""
+        return self._word_margin_table(getattr(self, "_word_row_alts", None))
+
+    def word_decode_margin(self, w: int) -> int:
+        """With set_word_margin(True) and WANT_WORD_DECODE: the margin of word w: the extra cost of the cheapest path that reads some
+        run differently from word_decode_text(w); -1 for a word that was not decoded or has no runs."""
+        return int(self.word_margins[w]["margin"])
+
+    def word_decode_char_margins(self, w: int) -> list:
+        """With set_word_margin(True) and WANT_WORD_DECODE: per character of word_decode_text(w), the margin of the row it came from,
+        and -1 for an inserted character (it has no row); for a word that was not decoded -1 per run."""
+        d, rows = self.word_decodes[w], self.word_row_margins[w]
+        if int(d["cost"]) < 0:
+            return [-1] * int(self.words[w]["n_runs"])
+        return [-1 if int(v) & 0x80 else int(rows[int(v)]) for v in self.word_decode_src[w, :int(d["n_chars"])]]
 
     def words_decode_text_of_line(self, t: int) -> list:
         """With WANT_WORD_DECODE: word_decode_text of the words of line t, left to right."""
@@ -1391,6 +1443,11 @@ class ERFilter:
                             if res._word_decodes is not None:
                                 res._word_decode_chars = table(L.str_er_result_word_decode_chars, np.uint8, n64).reshape(-1, 64)
                                 res._word_decode_src = table(L.str_er_result_word_decode_src, np.uint8, n64).reshape(-1, 64)
+                                res._word_margins = table(L.str_er_result_word_margins, WORD_MARGIN_DTYPE)
+                                if res._word_margins is not None:
+                                    res._word_row_margins = table(L.str_er_result_word_row_margins, np.uint8, n64).view(np.int32).reshape(-1, 32)
+                                    res._word_row_reads = table(L.str_er_result_word_row_reads, np.uint8, n64).reshape(-1, 32)
+                                    res._word_row_alts = table(L.str_er_result_word_row_alts, np.uint8, n64).reshape(-1, 32)
                             res._run_splits = table(L.str_er_result_run_splits, RUN_SPLIT_DTYPE)
                             if res._run_splits is not None:
                                 res._run_pieces = table(L.str_er_result_run_pieces, RUN_PIECE_DTYPE)
@@ -1959,6 +2016,20 @@ class ERFilter:
                                                _np_ptr(no) if len(no) else None, len(fr), _np_ptr(out), _np_ptr(ch), _np_ptr(sr)))
         return out[:len(fr)], ch[:len(fr)], sr[:len(fr)]
 
+    def set_word_margin(self, on: bool = True) -> None:
+        """str_er_set_word_margin: whether a detect call with WANT_WORD_DECODE also makes the margins of its words (off by default)."""
+        self._check(self.L.str_er_set_word_margin(self.h, 1 if on else 0))
+
+    def word_margins(self, costs: np.ndarray, first_run, n_runs_of_word, want_marginals: bool = False):
+        """str_er_word_margins: the margins (str_er_word_margin) of the words [first_run[w], first_run[w] + n_runs_of_word[w]) of the
+        cost rows (n runs, 65) uint8 under the table and set_word_decode; (WORD_MARGIN_DTYPE per word, (n, 32) int32 row margins,
+        (n, 32) uint8 row readings, (n, 32) uint8 row alternatives, and with want_marginals (n, 32, 66) int32 marginals, else None)."""
+        cs, fr, no, out, rm, rr, ra, mg = _margin_args(costs, first_run, n_runs_of_word, want_marginals)
+        self._check(self.L.str_er_word_margins(self.h, _np_ptr(cs) if len(cs) else None, len(cs), _np_ptr(fr) if len(fr) else None,
+                                               _np_ptr(no) if len(no) else None, len(fr), _np_ptr(out), _np_ptr(rm), _np_ptr(rr), _np_ptr(ra),
+                                               None if mg is None else _np_ptr(mg)))
+        return out[:len(fr)], rm[:len(fr)], rr[:len(fr)], ra[:len(fr)], None if mg is None else mg[:len(fr)]
+
     def feet_words(self, W: int, H: int, feet: np.ndarray, bits: np.ndarray):
         """str_er_feet_words: the glyph runs and words (str_er_line_run) of footprints in the pixels of one (H, W) frame, the runs made
         on the GPU: feet and bits as feet_geom takes them.  Returns (LINE_WORDS_DTYPE per footprint, LINE_RUN_DTYPE runs, LINE_WORD_DTYPE
@@ -2375,6 +2446,13 @@ def _decode_args(costs, first_run, n_runs_of_word):
     return cs, fr, no, np.zeros(n, WORD_DECODE_DTYPE), np.full((n, 64), 0xFF, np.uint8), np.full((n, 64), 0xFF, np.uint8)
 
 
+def _margin_args(costs, first_run, n_runs_of_word, want_marginals):
+    cs, fr, no = _decode_args(costs, first_run, n_runs_of_word)[:3]
+    n = max(1, len(fr))
+    return (cs, fr, no, np.full(n, -1, np.int32).repeat(4).view(WORD_MARGIN_DTYPE), np.full((n, 32), -1, np.int32), np.full((n, 32), 0xFF, np.uint8),
+            np.full((n, 32), 0xFF, np.uint8), np.full((n, 32, 66), -1, np.int32) if want_marginals else None)
+
+
 def bigram_from_probs(tp, start=None, end=None) -> np.ndarray:
     """str_er_bigram_from_probs (pure host): the (66, 66) uint8 table of (65, 65) probabilities tp[a][b] = P(b after a), with the
     boundary row from start (65) and the boundary column from end (65), 0 where they are None."""
@@ -2606,6 +2684,17 @@ def decode_words_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: 
     if rc != 0:
         raise StrErError(rc, "str_er_decode_words_host")
     return out[:len(fr)], ch[:len(fr)], sr[:len(fr)]
+
+
+def word_margins_host(costs: np.ndarray, first_run, n_runs_of_word, table, ins: int = 0, dele: int = 0, want_marginals: bool = False):
+    """str_er_word_margins_host (pure host, one thread): ERFilter.word_margins with the table and the parameters as arguments."""
+    cs, fr, no, out, rm, rr, ra, mg = _margin_args(costs, first_run, n_runs_of_word, want_marginals)
+    rc = load_library().str_er_word_margins_host(_np_ptr(cs) if len(cs) else None, len(cs), _np_ptr(fr) if len(fr) else None, _np_ptr(no) if len(no) else None,
+                                                 len(fr), _np_ptr(_bigram_table(table)), int(ins), int(dele), _np_ptr(out), _np_ptr(rm), _np_ptr(rr), _np_ptr(ra),
+                                                 None if mg is None else _np_ptr(mg))
+    if rc != 0:
+        raise StrErError(rc, "str_er_word_margins_host")
+    return out[:len(fr)], rm[:len(fr)], rr[:len(fr)], ra[:len(fr)], None if mg is None else mg[:len(fr)]
 
 
 def _want_flags(*, nodes=False, masks=False, line_crops=False, shapes=False, text_map=False, line_map=False, strokes=False,
@@ -3375,6 +3464,14 @@ class FrameStream:
         for i in range(int(self.L.str_er_stream_depth(self.h))):
             ctx = self.L.str_er_stream_context(self.h, i)
             rc = self.L.str_er_set_bigram(ctx, None if t is None else _np_ptr(t))
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
+    def set_word_margin(self, on: bool = True) -> None:
+        """str_er_set_word_margin on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_word_margin(ctx, 1 if on else 0)
             if rc != 0:
                 raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
 

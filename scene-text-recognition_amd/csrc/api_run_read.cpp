@@ -19,14 +19,15 @@
 //   lattice match    A's rows (runs first, pieces from row n_run on) with (first, n_of, slot) and the split records; iff match && split
 //   lattice track    the same rows and records as the lattice match, with the track match's tracks; iff the lattice match and the track match run
 //   track decode     the same window as the decoder, with the decoder's records and labels where it left them; iff decode
+//   margins          the same window as the decoder, with the decoder's records, labels and sources where it left them; iff decode and the context's setting
 //
 //   result table     source
 //   run_costs        A if match, else U
 //   piece_costs      A if match, else U
 //   run_probs        present iff match or decode
 //
-// The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, rs_tab, ld_tab, lm_tab, lt_tab,
-// tm_tab and td_tab hold what their kernels leave.
+// The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, wg_tab, rs_tab, ld_tab, lm_tab,
+// lt_tab, tm_tab and td_tab hold what their kernels leave.
 #include "str_er_ctx.h"
 #include "lattice_decode_kernels.h"
 #include "lattice_match_kernels.h"
@@ -42,6 +43,10 @@ void ReadChainOut::preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k
     if (p.match) matches->assign(n_words, str_er_word_match{-1, -1, -1, -1, 0, 0});
     if (p.track) { track_matches->assign(tracks->size(), str_er_track_match{-1, -1, -1, -1, 0, 0, 0, -1}); track_member_costs->assign(track_members->size(), -1); }
     if (p.decode) { decodes->assign(n_words, str_er_word_decode{}); decode_chars->assign(64 * n_words, 0xFF); decode_src->assign(64 * n_words, 0xFF); }
+    if (p.margin) {
+        margins->assign(n_words, str_er_word_margin{-1, -1, -1, -1}); row_margins->assign(32 * n_words, -1);
+        row_reads->assign(32 * n_words, 0xFF); row_alts->assign(32 * n_words, 0xFF);
+    }
     if (p.tdecode) {
         track_decodes->assign(tracks->size(), str_er_track_decode{-1, -1, 0, 0, 0, 0, -1, -1}); track_decode_chars->assign(32 * tracks->size(), 0xFF);
         track_decode_member_costs->assign(track_members->size(), -1);
@@ -100,7 +105,7 @@ struct ReadCall {
     RunTab   TH{}, TD{};
     OcrBuf   buf{};
     uint8_t *rows[2] = {nullptr, nullptr}, *parts[2] = {nullptr, nullptr};
-    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; TmTab KD{}; TdTab EH{}, ED{};
+    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; WgTab GM{}; TmTab KD{}; TdTab EH{}, ED{};
 
     // phase 1 (host alone): the tiles and rotations of the runs and pieces, every box checked, and their places in the atlas
     int geometry(const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words, const std::vector<str_er_line_run> &runs, const double *slopes,
@@ -193,12 +198,14 @@ struct ReadCall {
         const int n_chunks = p.match ? wm_chunks(c->lex) : 0;
         if ((p.match && (rc = c->wm_tab.ensure(c, wm_layout(nullptr, 0, n_words, n_chunks).bytes, "word match tables")) != STR_ER_OK) ||
             (p.decode && (rc = c->wd_tab.ensure(c, wd_layout(nullptr, 0, n_words).bytes, "word decode tables")) != STR_ER_OK) ||
+            (p.margin && (rc = c->wg_tab.ensure(c, wg_layout(nullptr, 0, n_words, false).bytes, "word margin tables")) != STR_ER_OK) ||
             (p.split && (rc = c->rs_tab.ensure(c, rs_layout(nullptr, 0, n_words, (size_t)n_slots, false).bytes, "run split tables")) != STR_ER_OK) ||
             (p.lattice && (rc = c->ld_tab.ensure(c, ld_layout(nullptr, 0, n_words, (size_t)n_slots).bytes, "lattice decode tables")) != STR_ER_OK) ||
             (p.lmatch && (rc = c->lm_tab.ensure(c, lm_layout(nullptr, 0, n_words, (size_t)n_slots, n_chunks).bytes, "lattice match tables")) != STR_ER_OK))
             return rc;
         if (p.match) WD = wm_layout(c->wm_tab.d(), 0, n_words, n_chunks);
         if (p.decode) DD = wd_layout(c->wd_tab.d(), 0, n_words);
+        if (p.margin) GM = wg_layout(c->wg_tab.d(), 0, n_words, false);
         if (p.split) { SH = rs_layout(c->rs_tab.h(), 0, n_words, (size_t)n_slots, false); SD = rs_layout(c->rs_tab.d(), 0, n_words, (size_t)n_slots, false); }
         if (p.lattice) { LH = ld_layout(c->ld_tab.h(), 0, n_words, (size_t)n_slots); LD = ld_layout(c->ld_tab.d(), 0, n_words, (size_t)n_slots); }
         if (p.lmatch) { MH = lm_layout(c->lm_tab.h(), 0, n_words, (size_t)n_slots, n_chunks); MD = lm_layout(c->lm_tab.d(), 0, n_words, (size_t)n_slots, n_chunks); }
@@ -253,6 +260,9 @@ struct ReadCall {
         if (p.decode) {
             const Window W = window(p.decode_set);
             launch_word_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, W.rows, W.first, W.n, (int)n_words, DD.dec, DD.chars, DD.src);
+            if (p.margin)          // the decoder's window, its records, labels and sources where it left them
+                launch_word_margin(s, c->bigram.d(), c->wd_ins, c->wd_del, W.rows, W.first, W.n, (int)n_words, DD.dec, DD.chars, DD.src, GM.margins, GM.row_margin, GM.row_read,
+                                   GM.row_alt, nullptr);
             if (p.tdecode && !tfirst.empty())          // the decoder's window, its records and labels where it left them
                 if (const int rc = track_decode_enqueue(c, s, 0, W.rows, W.first, W.n, DD.dec, DD.chars, tfirst.data(), tcount.data(), o.track_members->data(),
                                                         o.track_members->size(), tfirst.size(), EH, ED);
@@ -290,6 +300,12 @@ struct ReadCall {
             HIP_TRY(c, down(o.decodes->data(), DD.dec, sizeof(str_er_word_decode) * n_words));
             HIP_TRY(c, down(o.decode_chars->data(), DD.chars, 64 * n_words));
             HIP_TRY(c, down(o.decode_src->data(), DD.src, 64 * n_words));
+        }
+        if (p.margin) {
+            HIP_TRY(c, down(o.margins->data(), GM.margins, sizeof(str_er_word_margin) * n_words));
+            HIP_TRY(c, down(o.row_margins->data(), GM.row_margin, 4 * 32 * n_words));
+            HIP_TRY(c, down(o.row_reads->data(), GM.row_read, 32 * n_words));
+            HIP_TRY(c, down(o.row_alts->data(), GM.row_alt, 32 * n_words));
         }
         if (p.tdecode && !tfirst.empty()) HIP_TRY(c, down(c->td_tab.h() + EH.o_out, c->td_tab.d() + EH.o_out, EH.down_bytes));
         if (p.split && n_words > 0) HIP_TRY(c, down(c->rs_tab.h() + SH.o_out, c->rs_tab.d() + SH.o_out, SH.down_tables));          // (into page-locked memory: compacted below)
@@ -351,7 +367,7 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     const ReadChainOut       &o = chain && reads ? *chain : none;
     const size_t              n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0;
     const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.track_matches != nullptr, c->lex.fold != 0,
-                                   o.lattice_matches != nullptr, o.lattice_track_matches != nullptr, o.track_decodes != nullptr);
+                                   o.lattice_matches != nullptr, o.lattice_track_matches != nullptr, o.track_decodes != nullptr, o.margins != nullptr);
     if (reads) reads->assign(n_run, str_er_run_read{});
     q.assign(1800 * n_run, 0);
     if (pieces) {

@@ -25,10 +25,12 @@ struct ReadPlan {
     int  split_down;       // the set of the last k_split_words (SET_NONE: none)
     bool run_probs;
     bool tdecode;          // the track decode: only with decode; it reads the decoder's window (decode_set, with split its part rows)
+    bool margin;           // the decoder's margins (str_er_set_word_margin): only with decode; the decoder's window, records, labels and sources
     bool any() const { return match || decode || split; }      // some consumer reads the words and the class probabilities
 };
 
-inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, bool track, bool fold, bool lmatch = false, bool ltrack = false, bool tdecode = false)
+inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, bool track, bool fold, bool lmatch = false, bool ltrack = false, bool tdecode = false,
+                          bool margin = false)
 {
     ReadPlan p{};
     p.match = match; p.decode = decode; p.split = split; p.lattice = lattice && split; p.track = track && match;
@@ -48,6 +50,7 @@ inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, boo
     p.split_down = p.parts[SET_U] ? SET_U : p.parts[SET_A] ? SET_A : SET_NONE;
     p.run_probs = p.match || p.decode;
     p.tdecode = tdecode && p.decode;
+    p.margin = margin && p.decode;
     return p;
 }
 

@@ -27,6 +27,7 @@
 #include "word_match_kernels.h"
 #include "track_match_kernels.h"
 #include "word_decode_kernels.h"
+#include "word_margin_kernels.h"
 #include "er_group.h"
 #include "flood_order.h"
 #include "stage_rules.h"
@@ -162,6 +163,10 @@ struct str_er_result {
     std::vector<str_er_word_decode> word_decodes; // STR_ER_WANT_WORD_DECODE: per word of words, and 64 label and 64 source bytes per word (run_costs / run_probs too)
     std::vector<uint8_t> word_decode_chars, word_decode_src;
     bool have_word_decodes = false;
+    std::vector<str_er_word_margin> word_margins; // str_er_set_word_margin beside STR_ER_WANT_WORD_DECODE: per word of words, and 32 row margins, readings and alternatives per word
+    std::vector<int32_t> word_row_margins;
+    std::vector<uint8_t> word_row_reads, word_row_alts;
+    bool have_word_margins = false;
     std::vector<str_er_run_split> run_splits;    // STR_ER_WANT_RUN_SPLIT: per run of line_runs; the pieces they index with a reading and a cost row each;
     std::vector<str_er_run_piece> run_pieces;    // the parts of the words; per word of words
     std::vector<str_er_run_read> piece_reads;
@@ -329,6 +334,8 @@ struct str_er_ctx {
     bool     bigram_set = false;
     int32_t  wd_ins = 0, wd_del = 0;
     PairBuf  wd_tab;                  // (str_er_decode_words: cost rows | first run, run count per word) | records | labels | sources
+    bool     wd_margin = false;       // str_er_set_word_margin: a detect call with STR_ER_WANT_WORD_DECODE also makes the margins
+    PairBuf  wg_tab;                  // (str_er_word_margins: cost rows | first run, run count per word | the decoder's records, labels, sources) | records | row margins | row readings | row alternatives | (marginals)
     // STR_ER_WANT_TRACK_DECODE / str_er_decode_tracks (str_er_set_track_decode)
     int32_t  td_ins = 64, td_del = 64, td_rounds = 8;
     PairBuf  td_tab;                  // (str_er_decode_tracks: cost rows | first run, run count per word | the decoder's records, labels, sources) | first member, member count per track | members | records | labels | member costs
@@ -685,6 +692,9 @@ struct ReadChainOut {
     std::vector<str_er_word_match> *matches = nullptr;          // STR_ER_WANT_WORD_MATCH: the words against the context's lexicon
     std::vector<str_er_word_decode> *decodes = nullptr;         // STR_ER_WANT_WORD_DECODE: the words under the context's bigram table
     std::vector<uint8_t> *decode_chars = nullptr, *decode_src = nullptr;
+    // str_er_set_word_margin (with decode): the margins of the decoder's strings, behind it on the decoder's window
+    std::vector<str_er_word_margin> *margins = nullptr; std::vector<int32_t> *row_margins = nullptr;
+    std::vector<uint8_t> *row_reads = nullptr, *row_alts = nullptr;
     // STR_ER_WANT_RUN_SPLIT (with pieces): the segmentation of the words' runs (splits: their records; n_parts is filled in), the pieces'
     // cost rows, the parts and word records; the matcher and the decoder then work on the parts' rows
     std::vector<str_er_run_split> *splits = nullptr; std::vector<uint8_t> *piece_costs = nullptr;
@@ -828,6 +838,13 @@ struct WdTab {
     size_t o_dec, down_bytes, bytes;      // dec | chars | src lie back to back (each aligned): one copy down
 };
 WdTab wd_layout(uint8_t *base, size_t at, size_t n_words);
+// ---- defined in api_word_margin.cpp
+// the layout of what k_word_margin leaves in c->wg_tab from byte `at` on (the inputs' bytes), all of which comes down
+struct WgTab {
+    str_er_word_margin *margins; int32_t *row_margin; uint8_t *row_read, *row_alt; int32_t *marginals;      // marginals: null where they are not made
+    size_t o_out, down_bytes, bytes;      // margins | row_margin | row_read | row_alt | marginals lie back to back (each aligned): one copy down
+};
+WgTab wg_layout(uint8_t *base, size_t at, size_t n_words, bool marginals);
 // ---- defined in words_host.cpp and lines_host.cpp (HIP-free)
 bool word_gap_ok(int32_t num, int32_t den);       // what str_er_set_word_gap takes
 // inter * den >= num * (pa + pb - inter): footprints of pa and pb pixels, inter of them common, are duplicates (links) at num / den

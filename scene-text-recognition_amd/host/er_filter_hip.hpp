@@ -787,6 +787,44 @@ public:
                                   out.chars.empty() ? nullptr : out.chars.data(), out.src.empty() ? nullptr : out.src.data()));
         return out;
     }
+    // The margins of the decoded words (str_er_set_word_margin beside STR_ER_WANT_WORD_DECODE; the contract is at str_er_word_margin in
+    // include/str_er.h): one record per word, and per word 32 row margins (-1 past its rows), 32 row readings and 32 row alternatives
+    // (0xFF past its rows; 65: the row dropped); marginals only from word_margins on the caller's rows, 32 x 66 per word
+    struct WordMargins {
+        std::vector<str_er_word_margin> margins;
+        std::vector<int32_t>            row_margins, marginals;
+        std::vector<uint8_t>            row_reads, row_alts;
+    };
+    // whether a call with STR_ER_WANT_WORD_DECODE also makes the margins (str_er_set_word_margin; off by default)
+    void set_word_margin(bool on) { check(str_er_set_word_margin(ctx_.get(), on ? 1 : 0)); }
+    // ... copied out of the result of such a call (all empty when it made none)
+    static WordMargins word_margins(const str_er_result *r)
+    {
+        WordMargins out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_word_margin *p = str_er_result_word_margins(r, &n)) out.margins.assign(p, p + n);
+        if (const int32_t *p = str_er_result_word_row_margins(r, &nb)) out.row_margins.assign(p, p + nb / 4);
+        if (const uint8_t *p = str_er_result_word_row_reads(r, &nb)) out.row_reads.assign(p, p + nb);
+        if (const uint8_t *p = str_er_result_word_row_alts(r, &nb)) out.row_alts.assign(p, p + nb);
+        return out;
+    }
+    // the margins of the words [first_run[w], first_run[w] + n_runs[w]) of the caller's cost rows under the table (str_er_word_margins)
+    WordMargins word_margins(const std::vector<uint8_t> &costs, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs, bool marginals = false)
+    {
+        if (first_run.size() != n_runs.size() || costs.size() % 65) throw std::invalid_argument("word_margins: 65 bytes a run, one span a word");
+        const size_t n = first_run.size();
+        WordMargins  out;
+        out.margins.resize(n);
+        out.row_margins.resize(32 * n);
+        out.row_reads.resize(32 * n);
+        out.row_alts.resize(32 * n);
+        if (marginals) out.marginals.resize(32 * 66 * n);
+        check(str_er_word_margins(ctx_.get(), costs.empty() ? nullptr : costs.data(), (int32_t)(costs.size() / 65), n ? first_run.data() : nullptr,
+                                  n ? n_runs.data() : nullptr, (int32_t)n, n ? out.margins.data() : nullptr, n ? out.row_margins.data() : nullptr,
+                                  n ? out.row_reads.data() : nullptr, n ? out.row_alts.data() : nullptr, marginals && n ? out.marginals.data() : nullptr));
+        return out;
+    }
     // the decoded string of word w: its own reading where it was not decoded (more than 32 runs)
     static std::string word_decode_text(const LineWords &lw, const RunReads &rd, const WordDecodes &wd, size_t w)
     {

@@ -74,7 +74,7 @@ int main(int argc, char **argv)
     if (str_er_create(&p, &c) != STR_ER_OK) { std::fprintf(stderr, "create: %s\n", str_er_last_error(nullptr)); return 1; }
     std::unique_ptr<str_er_ctx, void (*)(str_er_ctx *)> ctx(c, str_er_destroy);
     if (str_er_load_cascade(c, 0, argv[1]) != STR_ER_OK || str_er_load_cascade(c, 1, argv[2]) != STR_ER_OK || str_er_load_svm_model(c, argv[3], 1800) != STR_ER_OK ||
-        str_er_set_bigram(c, table) != STR_ER_OK || str_er_set_word_decode(c, ins, del) != STR_ER_OK) {
+        str_er_set_bigram(c, table) != STR_ER_OK || str_er_set_word_decode(c, ins, del) != STR_ER_OK || str_er_set_word_margin(c, 1) != STR_ER_OK) {
         std::fprintf(stderr, "models and table: %s\n", str_er_last_error(c));
         return 1;
     }
@@ -88,14 +88,15 @@ int main(int argc, char **argv)
     const ERFilter::LineWords   lw = ERFilter::line_words(r);
     const ERFilter::RunReads    rd = ERFilter::run_reads(r);
     const ERFilter::WordDecodes wd = ERFilter::word_decodes(r);
+    const ERFilter::WordMargins wg = ERFilter::word_margins(r);          // (how much more the cheapest other reading of some run costs; -1: not decoded)
     for (size_t i = 0; i < fl.lines.size(); ++i) {
         if (fl.lines[i].rep < 0) continue;
         const str_er_line_words &L = lw.lines[(size_t)fl.lines[i].rep];
         for (int32_t k = L.first_word; k < L.first_word + L.n_words; ++k) {
             const str_er_word_decode &d = wd.decodes[(size_t)k];
-            std::printf("%u %zu %d %s -> %s %d (reading %d, %d read, %d dropped, %d inserted)\n", fl.lines[i].frame, i, k - L.first_word,
+            std::printf("%u %zu %d %s -> %s %d (reading %d, %d read, %d dropped, %d inserted) margin %d\n", fl.lines[i].frame, i, k - L.first_word,
                         ERFilter::word_text(lw, rd, (size_t)k).c_str(), ERFilter::word_decode_text(lw, rd, wd, (size_t)k).c_str(), d.cost, d.read_cost, d.n_sub,
-                        d.n_del, d.n_ins);
+                        d.n_del, d.n_ins, wg.margins[(size_t)k].margin);
         }
     }
     return 0;
