@@ -1658,6 +1658,15 @@ int str_er_flood_order(const uint8_t *plane, int32_t w, int32_t h, int64_t strid
 int str_er_resize_plane(str_er_ctx *ctx, const uint8_t *src, int32_t sw, int32_t sh,
                         int64_t sstride, uint8_t *dst, int32_t dw, int32_t dh);
 
+/* One pyramid level of one host plane through the dispatch the uniform-batch ingest uses for every level:
+ * k_pyr_level where the shape qualifies (a linear reduction with 1 < scale <= 1.5 in both directions, strides
+ * that are multiples of 4), k_resize otherwise.  The planes keep the given strides on the device.  rows: the
+ * output rows a wave walks, 8 / 16 / 32, or 0 for the library's choice.  *kernel_used: 1 k_pyr_level ran,
+ * 0 k_resize did.  Same bytes as str_er_resize_plane either way.                                              */
+int str_er_pyr_level_plane(str_er_ctx *ctx, const uint8_t *src, int32_t sw, int32_t sh, int64_t sstride,
+                           uint8_t *dst, int32_t dw, int32_t dh, int64_t dstride, int32_t rows,
+                           int32_t *kernel_used);
+
 /* ---- results (owned by the library until str_er_result_free) ----------------------- */
 int32_t str_er_result_n_planes(const str_er_result *r);
 int     str_er_result_plane_info(const str_er_result *r, int32_t plane, str_er_plane_info *info);

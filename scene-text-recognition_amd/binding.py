@@ -2352,6 +2352,20 @@ class ERFilter:
         self._check(self.L.str_er_resize_plane(self.h, _np_ptr(a), a.shape[1], a.shape[0], a.shape[1], _np_ptr(out), dw, dh))
         return out
 
+    def pyr_level_plane(self, src: np.ndarray, dw: int, dh: int, rows: int = 0, sstride: Optional[int] = None, dstride: Optional[int] = None):
+        """One pyramid level of a plane through launch_pyr_level's dispatch: (plane, True when k_pyr_level ran / False when k_resize did).
+        rows: 0 the library's choice, else 8 / 16 / 32.  sstride / dstride: the row strides of the planes on the device (default: the widths)."""
+        sh, sw = src.shape
+        sstride, dstride = sstride or sw, dstride or dw
+        a = np.zeros((sh, sstride), np.uint8)
+        a[:, :sw] = src
+        out = np.zeros((dh, dstride), np.uint8)
+        used = C.c_int32(-1)
+        fn = self.L.str_er_pyr_level_plane        # (bound here: STR_ER_LIB may name a build from before this entry point)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int32)]
+        self._check(fn(self.h, _np_ptr(a), sw, sh, sstride, _np_ptr(out), dw, dh, dstride, rows, C.byref(used)))
+        return np.ascontiguousarray(out[:, :dw]), bool(used.value)
+
     def tie_stats(self) -> dict:
         """Exact NMS ties: planes whose flood order had to be walked on a host core so far, the host time that took, pool size."""
         n, ms, th = C.c_uint64(), C.c_double(), C.c_int32()

@@ -196,6 +196,24 @@ try {
     return STR_ER_OK;
 } ABI_GUARD(c)
 
+int str_er_pyr_level_plane(str_er_ctx *c, const uint8_t *src, int32_t sw, int32_t sh, int64_t sstride, uint8_t *dst, int32_t dw, int32_t dh, int64_t dstride,
+                           int32_t rows, int32_t *kernel_used)
+try {
+    if (!c) return STR_ER_EINVAL;
+    if (!src || !dst || !kernel_used || sw < 1 || sh < 1 || dw < 1 || dh < 1 || sstride < sw || dstride < dw || sstride > INT32_MAX || dstride > INT32_MAX ||
+        !(rows == 0 || rows == 8 || rows == 16 || rows == 32))
+        return fail(c, STR_ER_EINVAL, "bad arguments");
+    HIP_TRY(c, hipSetDevice(c->prm.device));
+    // (the planes keep the caller's strides on the device: the dispatch looks at them)
+    if ((size_t)sstride * sh > c->in_bytes || (size_t)dstride * dh > c->pix_bytes) return fail(c, STR_ER_ECAPACITY, "plane larger than the context capacity");
+    HIP_TRY(c, hipMemcpy2DAsync(c->d_in, (size_t)sstride, src, (size_t)sstride, (size_t)sw, (size_t)sh, hipMemcpyHostToDevice, c->stream));
+    *kernel_used = launch_pyr_level(c->stream, c->d_in, sw, sh, (int)sstride, 0, 0, c->d_pix, dw, dh, (int)dstride, 0, 0, 1, 1, rows, c->pyr_kernel != 0) != 0;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpy2DAsync(dst, (size_t)dstride, c->d_pix, (size_t)dstride, (size_t)dw, (size_t)dh, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, wait_stream(c, c->stream));
+    return STR_ER_OK;
+} ABI_GUARD(c)
+
 // ---- results ---------------------------------------------------------------------------------
 int32_t str_er_result_n_planes(const str_er_result *r) { return r ? (int32_t)r->planes.size() : 0; }
 

@@ -52,6 +52,10 @@ void launch_invert(hipStream_t s, const uint8_t *src, uint8_t *dst, size_t n);
 void launch_resize(hipStream_t s, const uint8_t *src, int sw, int sh, int sstride, int64_t splane_pitch,
                    int64_t sframe_pitch, uint8_t *dst, int dw, int dh, int dstride, int64_t dplane_pitch,
                    int64_t dframe_pitch, int planes_per_frame, int n_frames);
+// A pyramid level: k_pyr_level where the shape qualifies (linear, 1 < scale <= 1.5 both ways, everything dword-aligned, `enable`), launch_resize otherwise.
+// rows: output rows a wave walks (8 / 16 / 32; 0: the kernel's own choice, 8).  Returns the rows k_pyr_level ran with, 0 when k_resize ran.
+int  launch_pyr_level(hipStream_t s, const uint8_t *src, int sw, int sh, int sstride, int64_t splane_pitch, int64_t sframe_pitch, uint8_t *dst, int dw, int dh,
+                      int dstride, int64_t dplane_pitch, int64_t dframe_pitch, int planes_per_frame, int n_frames, int rows, bool enable);
 
 // Lists of frames of different sizes (str_er_detect_bgr_list / _nv12_list): a job is one frame (ingest) or one frame's pyramid level (resize, `planes`
 // planes per job).  The kernels' device table -- *_table_bytes(n) bytes -- is built on the host into `out` and copied to the device by

@@ -1657,6 +1657,7 @@ int str_er_create(const str_er_params *p, str_er_ctx **out)
     c->dbg_stats = std::getenv("STR_ER_DEBUG_STATS") != nullptr;
     if (const char *os = std::getenv("STR_ER_OCR_SPEC")) c->ocr_spec = std::atoi(os) != 0;      // developer switch: 0 = the scorer is sized after the counters were read
     if (const char *nb = std::getenv("STR_ER_NODE_BLOCKS")) c->node_blocks_cap = (uint32_t)std::max(1, std::atoi(nb));
+    if (const char *pk = std::getenv("STR_ER_PYR_KERNEL")) { const int v = std::atoi(pk); c->pyr_kernel = (v == 0 || v == 8 || v == 16 || v == 32) ? v : 1; }      // developer switch: 0 = every pyramid level by k_resize, 8 / 16 / 32 = k_pyr_level's tile height
     if (const char *rp = std::getenv("STR_ER_REPLAY")) c->replay_on_gpu = !std::strcmp(rp, "gpu");
     for (int i = 0; i < 6; ++i) if (p->channel_mask & (1u << i)) c->chans.push_back(i);
     c->ppf = (int)c->chans.size() * p->n_pyr_levels;
@@ -1908,8 +1909,8 @@ int ingest_uniform(str_er_ctx *c, const FramePlan &p, const uint8_t *bgr, int32_
     rec(c, "channels", ws);
     for (int l = 1; l < p.nl; ++l) {
         const PlaneGeom &a = p.g(0, l - 1), &d = p.g(0, l);
-        launch_resize(ws, c->d_pix + a.off, a.w, a.h, a.stride, (int64_t)p.plane_sz(0, l - 1), frame_bytes, c->d_pix + d.off, d.w, d.h, d.stride,
-                      (int64_t)p.plane_sz(0, l), frame_bytes, 3, p.n);
+        launch_pyr_level(ws, c->d_pix + a.off, a.w, a.h, a.stride, (int64_t)p.plane_sz(0, l - 1), frame_bytes, c->d_pix + d.off, d.w, d.h, d.stride,
+                         (int64_t)p.plane_sz(0, l), frame_bytes, 3, p.n, c->pyr_kernel > 1 ? c->pyr_kernel : 0, c->pyr_kernel != 0);
     }
     rec(c, "pyramid", ws);
     return STR_ER_OK;

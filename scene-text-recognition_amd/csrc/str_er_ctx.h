@@ -288,6 +288,7 @@ struct str_er_ctx {
     uint64_t n_replayed = 0;                          // planes whose NMS ties were decided by a flood replay (statistics)
     double   walk_ms_total = 0;                       // host time those walks took, summed over planes (statistics)
     uint64_t n_batches = 0;
+    int  pyr_kernel = 1;                              // STR_ER_PYR_KERNEL: 0 every level of a uniform batch's pyramid by k_resize instead of k_pyr_level; 8 / 16 / 32: that tile height on every level (developer switch)
     bool replay_on_gpu = false;                       // STR_ER_REPLAY=gpu: walk the flood with k_flood_order instead of a host core
     uint16_t *d_cand_plane = nullptr, *d_cand_plane2 = nullptr;
     // the on-demand buffers of the stages (OnDemand)
