@@ -731,8 +731,9 @@ typedef struct str_er_word_decode {
  *     on request (str_er_word_margins) the marginals, 32 x 66 int32, -1 past m and where no path exists.  The layout is fixed per
  *     word, as for the decoder's labels and sources.
  *   Limits: an inserted character has no row, so it has no margin of its own, and paths that differ only in insertions are not told
- *     apart.  This covers the word decoder only: no lattice decode, no tracks, no pool.  Nothing is calibrated against labelled text:
- *     a margin is a cost difference in the unit of the cost rows, not a probability.                                                */
+ *     apart.  This covers the word decoder only: no lattice decode, no tracks, no pool (the lattice decoder has margins of its own,
+ *     str_er_lattice_margin).  Nothing is calibrated against labelled text: a margin is a cost difference in the unit of the cost
+ *     rows, not a probability.                                                                                                     */
 typedef struct str_er_word_margin {
     int32_t  margin, row;                 /*  0,  4                                   */
     int32_t  read, alt;                   /*  8, 12                                   */
@@ -875,7 +876,8 @@ typedef struct str_er_word_split {
  *     byte, and the parts are the runs; (2) cost <= the str_er_word_decode cost of the word on its runs; (3) cost <= the
  *     str_er_word_decode cost on the split sequence of str_er_run_split plus SPLIT * (n_parts of that sequence - n_runs) -- both are
  *     paths of the lattice (where those words are decoded at all).
- *   Limits: the lattice is that of str_er_run_split (at most 3 upright cuts a run); one path per word, no margins; no lexicon
+ *   Limits: the lattice is that of str_er_run_split (at most 3 upright cuts a run); one path per word -- how far the next reading
+ *     and the next cut of every part lie from it is a separate output, str_er_lattice_margin (str_er_set_lattice_margin); no lexicon
  *     enters here: the lexicon over the same lattice is a separate output, str_er_lattice_match (STR_ER_WANT_LATTICE_MATCH), while
  *     str_er_word_match still reads the split sequence of str_er_run_split.                                                            */
 typedef struct str_er_lattice_decode {
@@ -884,6 +886,54 @@ typedef struct str_er_lattice_decode {
     int32_t  n_del, n_ins;                /* 16, 20                                   */
     int32_t  first_part, n_parts;         /* 24, 28: into the lattice part table      */
 } str_er_lattice_decode;     /* 32 bytes; one per word                                */
+
+/* The margins of a word decoded over its lattice (str_er_set_lattice_margin beside STR_ER_WANT_LATTICE_DECODE, str_er_lattice_margins):
+ * the min-marginals of the recurrence of str_er_lattice_decode -- for every edge of the word's lattice and every reading of it the cost
+ * of the cheapest whole path that takes the edge and reads it that way -- and from them, for every part of the decoded path, how much
+ * more the cheapest path costs that reads the part differently (is this character right?) and that cuts the part's atoms differently
+ * (is this cut right?).  A definition of this library; integers only, exact, and the host states the same rules
+ * (str_er_lattice_margins_host).
+ *   Take a word with 1 <= N <= 32 nodes.  The lattice, B, E = 65, INF, INS, DEL, SPLIT, off_r, A_r, the rows C_{r,i,j}, the penalty
+ *     s(i) = (i > 0 ? SPLIT : 0) and the forward values V_n, U_n are exactly those of str_er_lattice_decode.  P_f[b] = min over a in
+ *     0 .. 65 of (V_f[a] + B[a][b]).
+ *   Backward values, in int32: G_N[a] = B[a][E] for a in 0 .. 65.  For n = N .. 1: GU_n[a] = G_n[a]; if INS > 0, for b < 65:
+ *     GU_n[b] = min(G_n[b], min over c < 65 of (B[b][c] + G_n[c]) + INS).  A node f < N is local node i of the run r whose edges leave
+ *     it (a run boundary off_r is local node 0 of run r): H_f[b] = min over j in i+1 .. A_r of (C_{r,i,j}[b] + GU_{off_r+j}[b]) for
+ *     b < 65; G_f[a] = min over b < 65 of (B[a][b] + H_f[b]) + s(i); if DEL > 0, G_f[a] is also min-ed with DEL + s(i) + min over j of
+ *     GU_{off_r+j}[a].  It follows that G_0[E] = cost, and min over a of (V_n[a] + G_n[a]) is the cheapest path through node n: >= cost
+ *     for every node, and cost at every run boundary.
+ *   Edge marginals, 66 per edge e = (r, i, j), with f = off_r + i and n = off_r + j: M_e[b] = P_f[b] + C_e[b] + s(i) + GU_n[b] for
+ *     b < 65, the edge taken and read as b; M_e[65] = min over a in 0 .. 65 of (V_f[a] + DEL + s(i) + GU_n[a]) if DEL > 0, else -1: the
+ *     edge taken and dropped.  An entry that is not below INF is -1.  m_e is the minimum of the entries >= 0: the cost of the cheapest
+ *     whole path that uses edge e.  Every path covers every atom with exactly one edge, so for every atom the minimum of m_e over the
+ *     edges covering it is cost.  Every marginal that exists is at most 32 * 5 * 255 + 255 = 41055; INF never wins.
+ *   Parts: the decoded path has the parts k = 0 .. n_parts - 1, part k on the edge e_k = (r_k, i_k, j_k).  x_k is the label of the
+ *     decoded character whose source byte is k with bit 7 clear, or 65 if there is none.  M_{e_k}[x_k] = cost.
+ *   Reading margin: read_margin_k = min over x != x_k with M_{e_k}[x] >= 0 of M_{e_k}[x] - cost: >= 0, and 0 on a tie; alt_k is the
+ *     smallest such x that attains it (there are 65 labels: it always exists).
+ *   Cut margin: cut_margin_k = min of m_e' - cost over the edges e' = (r_k, i', j') != e_k with i' < j_k and j' > i_k, the other edges
+ *     over the part's atoms -- none of them is on the path; -1 if there is none, which happens exactly when A_r = 1.
+ *     cut_alt_k = i' | j' << 4 of the smallest (i', j') that attains it, 0xFF if none.
+ *   Record: read_margin is the smallest reading margin, read_part the smallest part that attains it, read and alt those of that part.
+ *     cut_margin is the smallest cut margin >= 0, cut_part the smallest part that attains it and cut_alt that part's; all three -1 if
+ *     no run of the word is cut.  n_edges is the number of edges of the lattice.  cut_margin + cost is the cost of the cheapest path
+ *     whose part sequence differs from the decoded one: such a path uses an edge that is not on the path, and every such edge lies over
+ *     the atoms of some part.  All fields are -1 (and n_edges is 0) for N = 0 and for N > 32 (not decoded).
+ *   Per word, beside the record, in a layout fixed per word: 32 int32 reading margins and 32 int32 cut margins, -1 past n_parts; 32
+ *     bytes each of readings, alternatives and cut alternatives, 0xFF past n_parts.  On request, from str_er_lattice_margins only:
+ *     edge_min, int32 [32][4], entry [n-1][i] the m_e of the edge from the local node i into the word's node n, -1 where there is no
+ *     such edge; marginals, int32 [32][4][66], with the same index.
+ *   It follows: if no run of the word is cut, the reading margins, readings and alternatives equal str_er_word_margin's row outputs on
+ *     the runs byte for byte, and every cut field is -1 / 0xFF.
+ *   Limits: an inserted character has no part, so it has no margin of its own, and paths that differ only in insertions are not told
+ *     apart.  This covers the lattice decoder only: no tracks, no pool, no lattice match.  Nothing is calibrated against labelled text:
+ *     a margin is a cost difference in the unit of the cost rows, not a probability.                                                */
+typedef struct str_er_lattice_margin {
+    int32_t  read_margin, read_part;      /*  0,  4                                   */
+    int32_t  read, alt;                   /*  8, 12                                   */
+    int32_t  cut_margin, cut_part;        /* 16, 20                                   */
+    int32_t  cut_alt, n_edges;            /* 24, 28                                   */
+} str_er_lattice_margin;     /* 32 bytes; one per word                                */
 
 /* The lexicon match of a word over its piece lattice (STR_ER_WANT_LATTICE_MATCH, str_er_lattice_match_words): for every word the best
  * and the second-best entry of the lexicon when the segmentation of its runs is free, and for the best its segmentation and its
@@ -1434,6 +1484,24 @@ int str_er_lattice_decode_words_host(const str_er_run_split *splits, int32_t n_r
                                      const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, int32_t split_cost, const uint8_t *bigram,
                                      int32_t ins, int32_t del, str_er_lattice_decode *dec, uint8_t *chars, uint8_t *src, str_er_split_part *parts,
                                      int32_t cap_parts, int32_t *n_parts);
+/* Whether a detect call with STR_ER_WANT_LATTICE_DECODE also makes the margins of its words (str_er_lattice_margin): on != 0 switches
+ * them on; off by default.  A context setting, not a stage flag: without STR_ER_WANT_LATTICE_DECODE it does nothing, and while it is
+ * off no call enqueues, uploads or allocates anything more than before.  A stream's contexts: str_er_stream_context.               */
+int str_er_set_lattice_margin(str_er_ctx *ctx, int32_t on);
+/* The margins (str_er_lattice_margin) on the caller's rows, on the GPU, under the context's table, INS / DEL and SPLIT: the arguments
+ * up to n_words and their checks are those of str_er_lattice_decode_words, and the decoder runs on these rows first.  margins receives
+ * n_words records, read_margin and cut_margin 32 int32 per word each, read, alt and cut_alt 32 bytes per word each, edge_min (NULL: not
+ * wanted) 32 x 4 int32 per word, marginals (NULL: not wanted) 32 x 4 x 66 int32 per word.  Words may share runs.  STR_ER_ESTATE without
+ * a table; STR_ER_EINVAL on a word outside the runs or a record with cuts or pieces that are none.  n_words = 0 is fine.           */
+int str_er_lattice_margins(str_er_ctx *ctx, const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs,
+                           int32_t n_pieces, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, str_er_lattice_margin *margins,
+                           int32_t *read_margin, int32_t *cut_margin, uint8_t *read, uint8_t *alt, uint8_t *cut_alt, int32_t *edge_min, int32_t *marginals);
+/* The same rules on one host thread, with SPLIT, the table and INS / DEL as arguments (with the checks of
+ * str_er_lattice_decode_words_host).  Pure: no context, no GPU.                                                                     */
+int str_er_lattice_margins_host(const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs, int32_t n_pieces,
+                                const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, int32_t split_cost, const uint8_t *bigram,
+                                int32_t ins, int32_t del, str_er_lattice_margin *margins, int32_t *read_margin, int32_t *cut_margin, uint8_t *read,
+                                uint8_t *alt, uint8_t *cut_alt, int32_t *edge_min, int32_t *marginals);
 /* Statistics of the buffer of STR_ER_WANT_LATTICE_DECODE / str_er_lattice_decode_words: the bytes of its tables on the device (0: never
  * made).  The pointer may be NULL.                                                                                                  */
 int str_er_lattice_decode_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
@@ -1805,6 +1873,16 @@ const str_er_lattice_decode *str_er_result_lattice_decodes(const str_er_result *
 const uint8_t               *str_er_result_lattice_decode_chars(const str_er_result *r, uint64_t *n_bytes);
 const uint8_t               *str_er_result_lattice_decode_src(const str_er_result *r, uint64_t *n_bytes);
 const str_er_split_part     *str_er_result_lattice_parts(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_LATTICE_DECODE on a context whose str_er_set_lattice_margin is on (str_er_lattice_margin): one record per word of
+ * str_er_result_words(); per word 32 int32 reading margins and 32 int32 cut margins (n_bytes: 128 per word each) and 32 bytes each of
+ * readings, alternatives and cut alternatives, indexed by the word-relative part of str_er_result_lattice_parts().  Each returns NULL
+ * and 0 when the call made none; a call without words returns empty arrays (not NULL).                                              */
+const str_er_lattice_margin *str_er_result_lattice_margins(const str_er_result *r, int32_t *n);
+const int32_t               *str_er_result_lattice_read_margins(const str_er_result *r, uint64_t *n_bytes);
+const int32_t               *str_er_result_lattice_cut_margins(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t               *str_er_result_lattice_part_reads(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t               *str_er_result_lattice_part_alts(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t               *str_er_result_lattice_cut_alts(const str_er_result *r, uint64_t *n_bytes);
 /* With STR_ER_WANT_LATTICE_MATCH (str_er_lattice_match): one record per word of str_er_result_words(), 32 source bytes per word, and the
  * parts of the winning entries back to back in word order.  Each returns NULL and 0 without the flag; a call without words returns
  * empty arrays (not NULL).                                                                                                          */

@@ -22,6 +22,7 @@ from .binding import (  # noqa: F401
     WORD_MARGIN_DTYPE, word_margins_host,
     WANT_RUN_SPLIT, RUN_SPLIT_DTYPE, RUN_PIECE_DTYPE, SPLIT_PART_DTYPE, WORD_SPLIT_DTYPE, cuts_from_counts, split_words_host,
     WANT_LATTICE_DECODE, LATTICE_DECODE_DTYPE, lattice_decode_words_host,
+    LATTICE_MARGIN_DTYPE, lattice_margins_host,
     WANT_LATTICE_MATCH, LATTICE_MATCH_DTYPE, lattice_match_words_host,
     WANT_LATTICE_TRACK, LATTICE_TRACK_MEMBER_DTYPE, lattice_match_tracks_host,
     WANT_TRACK_READ, WORD_LINK_DTYPE, WORD_TRACK_DTYPE, TRACK_MATCH_DTYPE, word_links, word_tracks_from_links, match_tracks_host,

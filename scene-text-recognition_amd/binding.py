@@ -156,6 +156,12 @@ assert RUN_SPLIT_DTYPE.itemsize == 32 and RUN_PIECE_DTYPE.itemsize == 32 and SPL
 LATTICE_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4"),
                                  ("first_part", "<i4"), ("n_parts", "<i4")])
 assert LATTICE_DECODE_DTYPE.itemsize == 32
+# str_er_lattice_margin: per word, the smallest reading margin of its lattice parts with the part, its decoded reading and the
+# alternative (65: the part dropped); the smallest cut margin with the part and the other edge (i | j << 4) -- all three -1 where no
+# run of the word is cut; the edges of the lattice.  All -1 (n_edges 0): not decoded or no runs
+LATTICE_MARGIN_DTYPE = np.dtype([("read_margin", "<i4"), ("read_part", "<i4"), ("read", "<i4"), ("alt", "<i4"), ("cut_margin", "<i4"), ("cut_part", "<i4"),
+                                 ("cut_alt", "<i4"), ("n_edges", "<i4")])
+assert LATTICE_MARGIN_DTYPE.itemsize == 32
 LATTICE_MATCH_DTYPE = np.dtype([("entry", "<i4"), ("cost", "<i4"), ("second_entry", "<i4"), ("second_cost", "<i4"), ("free_cost", "<i4"), ("n_tried", "<i4"),
                                 ("first_part", "<i4"), ("n_parts", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
 assert LATTICE_MATCH_DTYPE.itemsize == 40
@@ -477,6 +483,15 @@ def load_library():
         fn = getattr(L, "str_er_result_" + name)
         fn.argtypes, fn.restype = [vp, cnt], vp
     L.str_er_lattice_decode_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_set_lattice_margin.argtypes = [vp, C.c_int32]
+    L.str_er_lattice_margins.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.str_er_lattice_margins_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.str_er_result_lattice_margins.argtypes = [vp, i32p]
+    L.str_er_result_lattice_margins.restype = vp
+    for fn in (L.str_er_result_lattice_read_margins, L.str_er_result_lattice_cut_margins, L.str_er_result_lattice_part_reads, L.str_er_result_lattice_part_alts,
+               L.str_er_result_lattice_cut_alts):
+        fn.argtypes = [vp, C.POINTER(C.c_uint64)]
+        fn.restype = vp
     for name, cnt in (("lattice_matches", i32p), ("lattice_match_src", C.POINTER(C.c_uint64)), ("lattice_match_parts", i32p)):
         fn = getattr(L, "str_er_result_" + name)
         fn.argtypes, fn.restype = [vp, cnt], vp
@@ -835,6 +850,59 @@ class Result:
         """With WANT_LATTICE_DECODE: SPLIT_PART_DTYPE, the lattice parts of the words back to back in word order (piece -1: a whole
         run; the indices are those of split_parts)."""
         return self._lattice_decode_table(getattr(self, "_lattice_parts", None))
+
+    def _lattice_margin_table(self, table):
+        if table is None:
+            raise ValueError("the result has no lattice margins (ERFilter.set_lattice_margin(True) and WANT_LATTICE_DECODE / want_lattice_decode=True)")
+        return table
+
+    @property
+    def lattice_margins(self) -> np.ndarray:
+        """With set_lattice_margin(True) and WANT_LATTICE_DECODE: LATTICE_MARGIN_DTYPE per word of words, in the same order."""
+        return self._lattice_margin_table(getattr(self, "_lattice_margins", None))
+
+    @property
+    def lattice_read_margins(self) -> np.ndarray:
+        """With set_lattice_margin(True) and WANT_LATTICE_DECODE: (n words, 32) int32, the reading margin of every lattice part of every
+        word, -1 past its parts."""
+        return self._lattice_margin_table(getattr(self, "_lattice_read_margins", None))
+
+    @property
+    def lattice_cut_margins(self) -> np.ndarray:
+        """With set_lattice_margin(True) and WANT_LATTICE_DECODE: (n words, 32) int32, the cut margin of every lattice part of every word,
+        -1 past its parts and for a part of a run without cuts."""
+        return self._lattice_margin_table(getattr(self, "_lattice_cut_margins", None))
+
+    @property
+    def lattice_part_reads(self) -> np.ndarray:
+        """With set_lattice_margin(True) and WANT_LATTICE_DECODE: (n words, 32) uint8, how the decoded string reads every lattice part
+        (65: dropped), 0xFF past the word's parts."""
+        return self._lattice_margin_table(getattr(self, "_lattice_part_reads", None))
+
+    @property
+    def lattice_part_alts(self) -> np.ndarray:
+        """With set_lattice_margin(True) and WANT_LATTICE_DECODE: (n words, 32) uint8, the cheapest other reading of every lattice part
+        (65: dropped), 0xFF past the word's parts."""
+        return self._lattice_margin_table(getattr(self, "_lattice_part_alts", None))
+
+    @property
+    def lattice_cut_alts(self) -> np.ndarray:
+        """With set_lattice_margin(True) and WANT_LATTICE_DECODE: (n words, 32) uint8, the cheapest other edge over every lattice part's
+        atoms as i | j << 4 (local nodes of the part's run), 0xFF past the word's parts and where there is none."""
+        return self._lattice_margin_table(getattr(self, "_lattice_cut_alts", None))
+
+    def word_lattice_margin(self, w: int) -> tuple:
+        """With set_lattice_margin(True) and WANT_LATTICE_DECODE: (reading margin, cut margin) of word w: the extra cost of the cheapest
+        path that reads some part differently from word_lattice_text(w), and of the cheapest path that cuts the word differently from
+        word_lattice_parts(w) (-1: no run of the word is cut); (-1, -1) for a word that was not decoded or has no runs."""
+        g = self.lattice_margins[w]
+        return int(g["read_margin"]), int(g["cut_margin"])
+
+    def word_lattice_part_margins(self, w: int) -> list:
+        """With set_lattice_margin(True) and WANT_LATTICE_DECODE: per lattice part of word w (word_lattice_parts(w)) the pair (reading
+        margin, cut margin), the cut margin -1 for a part of a run without cuts; none for a word that was not decoded."""
+        n = int(self.lattice_decodes[w]["n_parts"]) if int(self.lattice_decodes[w]["cost"]) >= 0 else 0
+        return [(int(a), int(b)) for a, b in zip(self.lattice_read_margins[w, :n], self.lattice_cut_margins[w, :n])]
 
     def word_lattice_text(self, w: int) -> str:
         """With WANT_LATTICE_DECODE: the jointly decoded string of word w; word_text(w) for a word that was not decoded (cost < 0)."""
@@ -1461,6 +1529,13 @@ class ERFilter:
                                     res._lattice_decode_chars = table(L.str_er_result_lattice_decode_chars, np.uint8, n64).reshape(-1, 64)
                                     res._lattice_decode_src = table(L.str_er_result_lattice_decode_src, np.uint8, n64).reshape(-1, 64)
                                     res._lattice_parts = table(L.str_er_result_lattice_parts, SPLIT_PART_DTYPE)
+                                    res._lattice_margins = table(L.str_er_result_lattice_margins, LATTICE_MARGIN_DTYPE)
+                                    if res._lattice_margins is not None:
+                                        res._lattice_read_margins = table(L.str_er_result_lattice_read_margins, np.uint8, n64).view(np.int32).reshape(-1, 32)
+                                        res._lattice_cut_margins = table(L.str_er_result_lattice_cut_margins, np.uint8, n64).view(np.int32).reshape(-1, 32)
+                                        res._lattice_part_reads = table(L.str_er_result_lattice_part_reads, np.uint8, n64).reshape(-1, 32)
+                                        res._lattice_part_alts = table(L.str_er_result_lattice_part_alts, np.uint8, n64).reshape(-1, 32)
+                                        res._lattice_cut_alts = table(L.str_er_result_lattice_cut_alts, np.uint8, n64).reshape(-1, 32)
                                 res._lattice_matches = table(L.str_er_result_lattice_matches, LATTICE_MATCH_DTYPE)
                                 if res._lattice_matches is not None:
                                     res._lattice_match_src = table(L.str_er_result_lattice_match_src, np.uint8, n64).reshape(-1, 32)
@@ -2145,6 +2220,19 @@ class ERFilter:
         self._check(self.L.str_er_lattice_decode_words(self.h, *a[0], *a[1]))
         return _lattice_out(a)
 
+    def set_lattice_margin(self, on: bool = True) -> None:
+        """str_er_set_lattice_margin: whether a detect call with WANT_LATTICE_DECODE also makes the margins of its words (off by default)."""
+        self._check(self.L.str_er_set_lattice_margin(self.h, 1 if on else 0))
+
+    def lattice_margins(self, splits, run_costs, piece_costs, first_run, n_runs_of_word, want_edges: bool = False, want_marginals: bool = False):
+        """str_er_lattice_margins: the margins (str_er_lattice_margin) of the words lattice_decode_words takes, under the same table and
+        settings; (LATTICE_MARGIN_DTYPE per word, (n, 32) int32 reading margins, (n, 32) int32 cut margins, (n, 32) uint8 readings,
+        (n, 32) uint8 alternatives, (n, 32) uint8 cut alternatives, with want_edges (n, 32, 4) int32 edge minima, else None, with
+        want_marginals (n, 32, 4, 66) int32 marginals, else None)."""
+        a, out = _lattice_margin_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, want_edges, want_marginals)
+        self._check(self.L.str_er_lattice_margins(self.h, *a[0], *[None if v is None else _np_ptr(v) for v in out]))
+        return tuple(None if v is None else v[:len(a[2][3])] for v in out)
+
     def lattice_track_stats(self) -> int:
         """str_er_lattice_track_stats: the bytes of the lattice track tables on the device; 0: never made."""
         a = C.c_uint64()
@@ -2583,6 +2671,27 @@ def _lattice_args(splits, run_costs, piece_costs, first_run, n_runs_of_word):
 def _lattice_out(a):
     nw = len(a[2][3])
     return a[3][:nw], a[4][:nw], a[5][:nw], a[6][:a[7].value].copy()
+
+
+def _lattice_margin_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, want_edges, want_marginals):
+    a = _lattice_args(splits, run_costs, piece_costs, first_run, n_runs_of_word)
+    n = max(1, len(a[2][3]))
+    rec = np.full(n, -1, np.int32).repeat(8).view(LATTICE_MARGIN_DTYPE)
+    rec["n_edges"] = 0
+    return a, (rec, np.full((n, 32), -1, np.int32), np.full((n, 32), -1, np.int32), np.full((n, 32), 0xFF, np.uint8), np.full((n, 32), 0xFF, np.uint8),
+               np.full((n, 32), 0xFF, np.uint8), np.full((n, 32, 4), -1, np.int32) if want_edges else None,
+               np.full((n, 32, 4, 66), -1, np.int32) if want_marginals else None)
+
+
+def lattice_margins_host(splits, run_costs, piece_costs, first_run, n_runs_of_word, table, ins: int = 0, dele: int = 0, split_cost: int = 8,
+                         want_edges: bool = False, want_marginals: bool = False):
+    """str_er_lattice_margins_host (pure host, one thread): ERFilter.lattice_margins with the table and the parameters as arguments."""
+    a, out = _lattice_margin_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, want_edges, want_marginals)
+    tb = _bigram_table(table)
+    rc = load_library().str_er_lattice_margins_host(*a[0], int(split_cost), _np_ptr(tb), int(ins), int(dele), *[None if v is None else _np_ptr(v) for v in out])
+    if rc != 0:
+        raise StrErError(rc, "str_er_lattice_margins_host")
+    return tuple(None if v is None else v[:len(a[2][3])] for v in out)
 
 
 def lattice_decode_words_host(splits, run_costs, piece_costs, first_run, n_runs_of_word, table, ins: int = 0, dele: int = 0, split_cost: int = 8):
@@ -3486,6 +3595,14 @@ class FrameStream:
         for i in range(int(self.L.str_er_stream_depth(self.h))):
             ctx = self.L.str_er_stream_context(self.h, i)
             rc = self.L.str_er_set_word_margin(ctx, 1 if on else 0)
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
+    def set_lattice_margin(self, on: bool = True) -> None:
+        """str_er_set_lattice_margin on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_lattice_margin(ctx, 1 if on else 0)
             if rc != 0:
                 raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
 

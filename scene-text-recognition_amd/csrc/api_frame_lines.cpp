@@ -732,6 +732,11 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         if (lattice && split) {
             out.lattice_decodes = &r->lattice_decodes; out.lattice_chars = &r->lattice_decode_chars; out.lattice_src = &r->lattice_decode_src; out.lattice_parts = &r->lattice_parts;
         }
+        const bool lmargin = lattice && split && c->ld_margin;          // (a context setting, str_er_set_lattice_margin: no flag of its own)
+        if (lmargin) {
+            out.lattice_margins = &r->lattice_margins; out.lattice_read_margins = &r->lattice_read_margins; out.lattice_cut_margins = &r->lattice_cut_margins;
+            out.lattice_part_reads = &r->lattice_part_reads; out.lattice_part_alts = &r->lattice_part_alts; out.lattice_cut_alts = &r->lattice_cut_alts;
+        }
         if (lmatch && split && match) { out.lattice_matches = &r->lattice_matches; out.lattice_match_src = &r->lattice_match_src; out.lattice_match_parts = &r->lattice_match_parts; }
         if (track || tdecode) {
             out.tracks = &r->word_tracks; out.track_members = &r->word_track_members;
@@ -766,6 +771,7 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         r->have_track_decodes = tdecode;
         r->have_run_splits = split;
         r->have_lattice_decodes = lattice && split;
+        r->have_lattice_margins = lmargin;
         r->have_lattice_matches = lmatch && split && match;
         r->have_lattice_track = ltrack && track && lmatch && split && match;
         r->have_run_reads = true;

@@ -19,6 +19,7 @@
 //   lattice match    A's rows (runs first, pieces from row n_run on) with (first, n_of, slot) and the split records; iff match && split
 //   lattice track    the same rows and records as the lattice match, with the track match's tracks; iff the lattice match and the track match run
 //   track decode     the same window as the decoder, with the decoder's records and labels where it left them; iff decode
+//   lattice margins  what the lattice decode read, with its records, labels, sources and parts where it left them; iff the lattice decode and the context's setting
 //   margins          the same window as the decoder, with the decoder's records, labels and sources where it left them; iff decode and the context's setting
 //
 //   result table     source
@@ -26,7 +27,7 @@
 //   piece_costs      A if match, else U
 //   run_probs        present iff match or decode
 //
-// The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, wg_tab, rs_tab, ld_tab, lm_tab,
+// The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, wg_tab, rs_tab, ld_tab, lg_tab, lm_tab,
 // lt_tab, tm_tab and td_tab hold what their kernels leave.
 #include "str_er_ctx.h"
 #include "lattice_decode_kernels.h"
@@ -55,6 +56,11 @@ void ReadChainOut::preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k
     if (p.lattice) {
         lattice_decodes->assign(n_words, str_er_lattice_decode{}); lattice_chars->assign(64 * n_words, 0xFF); lattice_src->assign(64 * n_words, 0xFF);
         lattice_parts->clear();
+    }
+    if (p.lmargin) {
+        lattice_margins->assign(n_words, str_er_lattice_margin{-1, -1, -1, -1, -1, -1, -1, 0});
+        lattice_read_margins->assign(32 * n_words, -1); lattice_cut_margins->assign(32 * n_words, -1);
+        lattice_part_reads->assign(32 * n_words, 0xFF); lattice_part_alts->assign(32 * n_words, 0xFF); lattice_cut_alts->assign(32 * n_words, 0xFF);
     }
     if (p.lmatch) {
         lattice_matches->assign(n_words, str_er_lattice_match{-1, -1, -1, -1, 0, 0, 0, 0, 0, 0}); lattice_match_src->assign(32 * n_words, 0xFF);
@@ -105,7 +111,7 @@ struct ReadCall {
     RunTab   TH{}, TD{};
     OcrBuf   buf{};
     uint8_t *rows[2] = {nullptr, nullptr}, *parts[2] = {nullptr, nullptr};
-    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; WgTab GM{}; TmTab KD{}; TdTab EH{}, ED{};
+    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; WgTab GM{}; LgTab LG{}; TmTab KD{}; TdTab EH{}, ED{};
 
     // phase 1 (host alone): the tiles and rotations of the runs and pieces, every box checked, and their places in the atlas
     int geometry(const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words, const std::vector<str_er_line_run> &runs, const double *slopes,
@@ -201,6 +207,7 @@ struct ReadCall {
             (p.margin && (rc = c->wg_tab.ensure(c, wg_layout(nullptr, 0, n_words, false).bytes, "word margin tables")) != STR_ER_OK) ||
             (p.split && (rc = c->rs_tab.ensure(c, rs_layout(nullptr, 0, n_words, (size_t)n_slots, false).bytes, "run split tables")) != STR_ER_OK) ||
             (p.lattice && (rc = c->ld_tab.ensure(c, ld_layout(nullptr, 0, n_words, (size_t)n_slots).bytes, "lattice decode tables")) != STR_ER_OK) ||
+            (p.lmargin && (rc = c->lg_tab.ensure(c, lg_layout(nullptr, 0, n_words, false, false).bytes, "lattice margin tables")) != STR_ER_OK) ||
             (p.lmatch && (rc = c->lm_tab.ensure(c, lm_layout(nullptr, 0, n_words, (size_t)n_slots, n_chunks).bytes, "lattice match tables")) != STR_ER_OK))
             return rc;
         if (p.match) WD = wm_layout(c->wm_tab.d(), 0, n_words, n_chunks);
@@ -208,6 +215,7 @@ struct ReadCall {
         if (p.margin) GM = wg_layout(c->wg_tab.d(), 0, n_words, false);
         if (p.split) { SH = rs_layout(c->rs_tab.h(), 0, n_words, (size_t)n_slots, false); SD = rs_layout(c->rs_tab.d(), 0, n_words, (size_t)n_slots, false); }
         if (p.lattice) { LH = ld_layout(c->ld_tab.h(), 0, n_words, (size_t)n_slots); LD = ld_layout(c->ld_tab.d(), 0, n_words, (size_t)n_slots); }
+        if (p.lmargin) LG = lg_layout(c->lg_tab.d(), 0, n_words, false, false);
         if (p.lmatch) { MH = lm_layout(c->lm_tab.h(), 0, n_words, (size_t)n_slots, n_chunks); MD = lm_layout(c->lm_tab.d(), 0, n_words, (size_t)n_slots, n_chunks); }
         return STR_ER_OK;
     }
@@ -269,9 +277,14 @@ struct ReadCall {
                     rc != STR_ER_OK)
                     return rc;
         }
-        if (p.lattice && n_words > 0)          // unfolded rows of the runs and, behind them, the pieces
+        if (p.lattice && n_words > 0) {          // unfolded rows of the runs and, behind them, the pieces
             launch_lattice_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, c->rs_split, TD.splits, rows[p.lattice_set], rows[p.lattice_set] + 65 * n_run, TD.first, TD.n_of, TD.slot,
                                   (int)n_words, reinterpret_cast<int32_t *>(LD.dec), LD.chars, LD.src, reinterpret_cast<int32_t *>(LD.parts));
+            if (p.lmargin)          // the same rows and words, the decoder's records, labels, sources and parts where it left them
+                launch_lattice_margin(s, c->bigram.d(), c->wd_ins, c->wd_del, c->rs_split, TD.splits, rows[p.lattice_set], rows[p.lattice_set] + 65 * n_run, TD.first, TD.n_of,
+                                      TD.slot, (int)n_words, reinterpret_cast<const int32_t *>(LD.dec), LD.chars, LD.src, reinterpret_cast<const int32_t *>(LD.parts), LG.margins,
+                                      LG.read_margin, LG.cut_margin, LG.read, LG.alt, LG.cut_alt, nullptr, nullptr);
+        }
         HIP_TRY(c, hipGetLastError());
         return STR_ER_OK;
     }
@@ -309,6 +322,14 @@ struct ReadCall {
         }
         if (p.tdecode && !tfirst.empty()) HIP_TRY(c, down(c->td_tab.h() + EH.o_out, c->td_tab.d() + EH.o_out, EH.down_bytes));
         if (p.split && n_words > 0) HIP_TRY(c, down(c->rs_tab.h() + SH.o_out, c->rs_tab.d() + SH.o_out, SH.down_tables));          // (into page-locked memory: compacted below)
+        if (p.lmargin && n_words > 0) {
+            HIP_TRY(c, down(o.lattice_margins->data(), LG.margins, sizeof(str_er_lattice_margin) * n_words));
+            HIP_TRY(c, down(o.lattice_read_margins->data(), LG.read_margin, 4 * 32 * n_words));
+            HIP_TRY(c, down(o.lattice_cut_margins->data(), LG.cut_margin, 4 * 32 * n_words));
+            HIP_TRY(c, down(o.lattice_part_reads->data(), LG.read, 32 * n_words));
+            HIP_TRY(c, down(o.lattice_part_alts->data(), LG.alt, 32 * n_words));
+            HIP_TRY(c, down(o.lattice_cut_alts->data(), LG.cut_alt, 32 * n_words));
+        }
         if (p.lattice && n_words > 0) HIP_TRY(c, down(c->ld_tab.h() + LH.o_dec, c->ld_tab.d() + LH.o_dec, LH.down_bytes));
         if (p.lmatch && n_words > 0) HIP_TRY(c, down(c->lm_tab.h() + MH.o_matches, c->lm_tab.d() + MH.o_matches, MH.down_bytes));
         if (p.ltrack && !tfirst.empty()) HIP_TRY(c, down(c->lt_tab.h() + GH.o_matches, c->lt_tab.d() + GH.o_matches, GH.down_bytes));
@@ -367,7 +388,7 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     const ReadChainOut       &o = chain && reads ? *chain : none;
     const size_t              n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0;
     const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.track_matches != nullptr, c->lex.fold != 0,
-                                   o.lattice_matches != nullptr, o.lattice_track_matches != nullptr, o.track_decodes != nullptr, o.margins != nullptr);
+                                   o.lattice_matches != nullptr, o.lattice_track_matches != nullptr, o.track_decodes != nullptr, o.margins != nullptr, o.lattice_margins != nullptr);
     if (reads) reads->assign(n_run, str_er_run_read{});
     q.assign(1800 * n_run, 0);
     if (pieces) {

@@ -26,11 +26,12 @@ struct ReadPlan {
     bool run_probs;
     bool tdecode;          // the track decode: only with decode; it reads the decoder's window (decode_set, with split its part rows)
     bool margin;           // the decoder's margins (str_er_set_word_margin): only with decode; the decoder's window, records, labels and sources
+    bool lmargin;          // the lattice decoder's margins (str_er_set_lattice_margin): only with lattice; the decoder's window, records, labels, sources and parts
     bool any() const { return match || decode || split; }      // some consumer reads the words and the class probabilities
 };
 
 inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, bool track, bool fold, bool lmatch = false, bool ltrack = false, bool tdecode = false,
-                          bool margin = false)
+                          bool margin = false, bool lmargin = false)
 {
     ReadPlan p{};
     p.match = match; p.decode = decode; p.split = split; p.lattice = lattice && split; p.track = track && match;
@@ -51,6 +52,7 @@ inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, boo
     p.run_probs = p.match || p.decode;
     p.tdecode = tdecode && p.decode;
     p.margin = margin && p.decode;
+    p.lmargin = lmargin && p.lattice;
     return p;
 }
 

@@ -28,6 +28,7 @@
 #include "track_match_kernels.h"
 #include "word_decode_kernels.h"
 #include "word_margin_kernels.h"
+#include "lattice_margin_kernels.h"
 #include "er_group.h"
 #include "flood_order.h"
 #include "stage_rules.h"
@@ -178,6 +179,10 @@ struct str_er_result {
     std::vector<uint8_t> lattice_decode_chars, lattice_decode_src;
     std::vector<str_er_split_part> lattice_parts;
     bool have_lattice_decodes = false;
+    std::vector<str_er_lattice_margin> lattice_margins; // str_er_set_lattice_margin beside STR_ER_WANT_LATTICE_DECODE: per word of words, and per word 32 reading and cut margins, readings, alternatives and cut alternatives
+    std::vector<int32_t> lattice_read_margins, lattice_cut_margins;
+    std::vector<uint8_t> lattice_part_reads, lattice_part_alts, lattice_cut_alts;
+    bool have_lattice_margins = false;
     std::vector<str_er_lattice_match> lattice_matches;  // STR_ER_WANT_LATTICE_MATCH: per word of words, 32 source bytes per word, and the parts of the winning entries
     std::vector<uint8_t> lattice_match_src;
     std::vector<str_er_split_part> lattice_match_parts;
@@ -345,6 +350,8 @@ struct str_er_ctx {
     PairBuf  rs_out;                  // a record per run slot of k_run_cuts
     PairBuf  rs_tab;                  // (str_er_split_words: splits | rows of the runs and pieces | first run, run count, slot per word) | records | parts | (its part rows) | part counts
     // STR_ER_WANT_LATTICE_DECODE / str_er_lattice_decode_words
+    bool     ld_margin = false;       // str_er_set_lattice_margin: a detect call with STR_ER_WANT_LATTICE_DECODE also makes the margins
+    PairBuf  lg_tab;                  // (str_er_lattice_margins: splits | rows | first run, run count, slot per word | the decoder's records, labels, sources, parts) | records | reading margins | cut margins | readings | alternatives | cut alternatives | (edge minima) | (marginals)
     PairBuf  ld_tab;                  // (str_er_lattice_decode_words: splits | rows of the runs and pieces | first run, run count, slot per word) | records | labels | sources | parts
     // STR_ER_WANT_LATTICE_MATCH / str_er_lattice_match_words
     PairBuf  lm_tab;                  // (str_er_lattice_match_words: splits | rows of the runs and pieces | first run, run count, slot per word) | chunk keys | records | sources | parts
@@ -706,6 +713,9 @@ struct ReadChainOut {
     // STR_ER_WANT_LATTICE_DECODE (with split): the words over their piece lattices under the bigram table
     std::vector<str_er_lattice_decode> *lattice_decodes = nullptr; std::vector<str_er_split_part> *lattice_parts = nullptr;
     std::vector<uint8_t> *lattice_chars = nullptr, *lattice_src = nullptr;
+    // str_er_set_lattice_margin (with the lattice decode): the margins of its paths, behind it on what it read and left
+    std::vector<str_er_lattice_margin> *lattice_margins = nullptr; std::vector<int32_t> *lattice_read_margins = nullptr, *lattice_cut_margins = nullptr;
+    std::vector<uint8_t> *lattice_part_reads = nullptr, *lattice_part_alts = nullptr, *lattice_cut_alts = nullptr;
     // STR_ER_WANT_LATTICE_MATCH (with split and match): the words against the context's lexicon over their piece lattices
     std::vector<str_er_lattice_match> *lattice_matches = nullptr; std::vector<uint8_t> *lattice_match_src = nullptr;
     std::vector<str_er_split_part> *lattice_match_parts = nullptr;
@@ -839,6 +849,13 @@ struct WdTab {
     size_t o_dec, down_bytes, bytes;      // dec | chars | src lie back to back (each aligned): one copy down
 };
 WdTab wd_layout(uint8_t *base, size_t at, size_t n_words);
+// ---- defined in api_lattice_margin.cpp
+// the layout of what k_lattice_margin leaves in c->lg_tab from byte `at` on (the inputs' bytes), all of which comes down
+struct LgTab {
+    str_er_lattice_margin *margins; int32_t *read_margin, *cut_margin; uint8_t *read, *alt, *cut_alt; int32_t *edge_min, *marginals;      // the last two: null where they are not made
+    size_t o_out, down_bytes, bytes;      // the tables lie back to back in that order (each aligned): one copy down
+};
+LgTab lg_layout(uint8_t *base, size_t at, size_t n_words, bool edge_min, bool marginals);
 // ---- defined in api_word_margin.cpp
 // the layout of what k_word_margin leaves in c->wg_tab from byte `at` on (the inputs' bytes), all of which comes down
 struct WgTab {

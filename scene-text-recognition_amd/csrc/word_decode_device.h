@@ -1,5 +1,6 @@
 // word_decode_device.h -- INTERNAL: the device pieces the bigram decoders share (word_decode_kernels.hip: k_word_decode,
-// lattice_decode_kernels.hip: k_lattice_decode, word_margin_kernels.hip: k_word_margin): the layout of the table in LDS, the wave-level sync, the min-plus product of a state
+// lattice_decode_kernels.hip: k_lattice_decode, word_margin_kernels.hip: k_word_margin,
+// lattice_margin_kernels.hip: k_lattice_margin): the layout of the table in LDS, the wave-level sync, the min-plus product of a state
 // vector with the table for the targets 0 .. 63 and its turned-round form for the target 64 and the end of the word, and a step of the
 // plain reading.  A value travels with its state as a key (value << 7 | state); every value of either decoder is below 2^21, so a key
 // is below 2^28 and the sum of a key and a table byte << 7 cannot wrap.

@@ -1037,6 +1037,55 @@ public:
         out.parts.resize((size_t)n);
         return out;
     }
+    // The margins of the jointly decoded words (str_er_set_lattice_margin beside STR_ER_WANT_LATTICE_DECODE; the contract is at
+    // str_er_lattice_margin in include/str_er.h): one record per word, and per word 32 reading margins and 32 cut margins (-1 past its
+    // parts), 32 readings, 32 alternatives and 32 cut alternatives (0xFF past its parts; 65: the part dropped; a cut alternative is
+    // i | j << 4); the edge minima (32 x 4 per word) and the marginals (32 x 4 x 66 per word) only from lattice_margins on the caller's rows
+    struct LatticeMargins {
+        std::vector<str_er_lattice_margin> margins;
+        std::vector<int32_t>               read_margins, cut_margins, edge_min, marginals;
+        std::vector<uint8_t>               reads, alts, cut_alts;
+    };
+    // whether a call with STR_ER_WANT_LATTICE_DECODE also makes the margins (str_er_set_lattice_margin; off by default)
+    void set_lattice_margin(bool on) { check(str_er_set_lattice_margin(ctx_.get(), on ? 1 : 0)); }
+    // ... copied out of the result of such a call (all empty when it made none)
+    static LatticeMargins lattice_margins(const str_er_result *r)
+    {
+        LatticeMargins out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_lattice_margin *p = str_er_result_lattice_margins(r, &n)) out.margins.assign(p, p + n);
+        if (const int32_t *p = str_er_result_lattice_read_margins(r, &nb)) out.read_margins.assign(p, p + nb / 4);
+        if (const int32_t *p = str_er_result_lattice_cut_margins(r, &nb)) out.cut_margins.assign(p, p + nb / 4);
+        if (const uint8_t *p = str_er_result_lattice_part_reads(r, &nb)) out.reads.assign(p, p + nb);
+        if (const uint8_t *p = str_er_result_lattice_part_alts(r, &nb)) out.alts.assign(p, p + nb);
+        if (const uint8_t *p = str_er_result_lattice_cut_alts(r, &nb)) out.cut_alts.assign(p, p + nb);
+        return out;
+    }
+    // the margins of the words lattice_decode_words takes, on the caller's unfolded cost rows under the context's table and settings
+    // (str_er_lattice_margins)
+    LatticeMargins lattice_margins(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                                   const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs, bool edges = false, bool marginals = false)
+    {
+        if (first_run.size() != n_runs.size() || run_costs.size() != 65 * splits.size() || piece_costs.size() % 65)
+            throw std::invalid_argument("lattice_margins: 65 bytes a run and a piece, one record a run, one span a word");
+        const size_t   n = first_run.size();
+        LatticeMargins out;
+        out.margins.resize(n);
+        out.read_margins.resize(32 * n);
+        out.cut_margins.resize(32 * n);
+        out.reads.resize(32 * n);
+        out.alts.resize(32 * n);
+        out.cut_alts.resize(32 * n);
+        if (edges) out.edge_min.resize(32 * 4 * n);
+        if (marginals) out.marginals.resize(32 * 4 * 66 * n);
+        check(str_er_lattice_margins(ctx_.get(), splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                     piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65), n ? first_run.data() : nullptr,
+                                     n ? n_runs.data() : nullptr, (int32_t)n, n ? out.margins.data() : nullptr, n ? out.read_margins.data() : nullptr,
+                                     n ? out.cut_margins.data() : nullptr, n ? out.reads.data() : nullptr, n ? out.alts.data() : nullptr,
+                                     n ? out.cut_alts.data() : nullptr, edges && n ? out.edge_min.data() : nullptr, marginals && n ? out.marginals.data() : nullptr));
+        return out;
+    }
     // the jointly decoded string of word w: its own reading where it was not decoded (more than 32 atoms)
     static std::string word_lattice_text(const LineWords &lw, const RunReads &rd, const LatticeDecodes &ld, size_t w)
     {

@@ -8,9 +8,11 @@
 // (characters of 0-9 A-Z a-z & ( ); other lines are skipped).  The table is the add-one bigram counts of the words with the word
 // boundary, every row normalised, through str_er_bigram_from_probs.  Prints one row per word of every frame line,
 // "<frame> <frame line> <word> <reading> / <split reading> -> <decoded> <cost> (reading <its cost>, <runs> runs in <parts> parts,
-// <parts read> read, <dropped> dropped, <inserted> inserted)": the reading is a character per glyph run, the split reading a character per
+// <parts read> read, <dropped> dropped, <inserted> inserted) margins <reading> <cut>": the reading is a character per glyph run, the split reading a character per
 // part of the scorer's own segmentation (str_er_run_split), the decoded string the cheapest over every segmentation of the runs into their
-// pieces under the pieces' cost rows plus the table (the contract is at str_er_lattice_decode in str_er.h).  Costs are in 1/8 bit.
+// pieces under the pieces' cost rows plus the table (the contract is at str_er_lattice_decode in str_er.h); the margins say how much more the
+// cheapest path costs that reads some part differently and that cuts the word differently (str_er_lattice_margin; -1: no run of the word is
+// cut, or the word was not decoded).  Costs are in 1/8 bit.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -75,7 +77,7 @@ int main(int argc, char **argv)
     if (str_er_create(&p, &c) != STR_ER_OK) { std::fprintf(stderr, "create: %s\n", str_er_last_error(nullptr)); return 1; }
     std::unique_ptr<str_er_ctx, void (*)(str_er_ctx *)> ctx(c, str_er_destroy);
     if (str_er_load_cascade(c, 0, argv[1]) != STR_ER_OK || str_er_load_cascade(c, 1, argv[2]) != STR_ER_OK || str_er_load_svm_model(c, argv[3], 1800) != STR_ER_OK ||
-        str_er_set_bigram(c, table) != STR_ER_OK || str_er_set_word_decode(c, ins, del) != STR_ER_OK) {
+        str_er_set_bigram(c, table) != STR_ER_OK || str_er_set_word_decode(c, ins, del) != STR_ER_OK || str_er_set_lattice_margin(c, 1) != STR_ER_OK) {
         std::fprintf(stderr, "models and table: %s\n", str_er_last_error(c));
         return 1;
     }
@@ -90,15 +92,16 @@ int main(int argc, char **argv)
     const ERFilter::RunReads    rd = ERFilter::run_reads(r);
     const ERFilter::RunSplits      sp = ERFilter::run_splits(r);
     const ERFilter::LatticeDecodes ld = ERFilter::lattice_decodes(r);
+    const ERFilter::LatticeMargins lg = ERFilter::lattice_margins(r);
     for (size_t i = 0; i < fl.lines.size(); ++i) {
         if (fl.lines[i].rep < 0) continue;
         const str_er_line_words &L = lw.lines[(size_t)fl.lines[i].rep];
         for (int32_t k = L.first_word; k < L.first_word + L.n_words; ++k) {
             const str_er_lattice_decode &d = ld.decodes[(size_t)k];
-            std::printf("%u %zu %d %s / %s -> %s %d (reading %d, %d runs in %d parts, %d read, %d dropped, %d inserted)\n", fl.lines[i].frame, i, k - L.first_word,
+            std::printf("%u %zu %d %s / %s -> %s %d (reading %d, %d runs in %d parts, %d read, %d dropped, %d inserted) margins %d %d\n", fl.lines[i].frame, i, k - L.first_word,
                         ERFilter::word_text(lw, rd, (size_t)k).c_str(), ERFilter::word_split_text(sp, (size_t)k).c_str(),
                         ERFilter::word_lattice_text(lw, rd, ld, (size_t)k).c_str(), d.cost, d.read_cost, lw.words[(size_t)k].n_runs, d.n_parts, d.n_sub, d.n_del,
-                        d.n_ins);
+                        d.n_ins, lg.margins[(size_t)k].read_margin, lg.margins[(size_t)k].cut_margin);
         }
     }
     return 0;
