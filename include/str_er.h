@@ -772,7 +772,7 @@ typedef struct str_er_word_margin {
  *     and for a track of one usable member decoded with the decoder's INS = DEL = 0, seed_cost <= that word's str_er_word_decode
  *     cost (the diagonal alignment is one of the alignments).
  *   Limits: this is a local optimum of single edits from the set median, not the global median string.  The members enter with the
- *     rows the decoder read; a joint search over the members' piece lattices is not part of it.  Nothing is pooled across calls by this output: a decode
+ *     rows the decoder read; a joint search over the members' piece lattices is not part of it: it is a separate output, str_er_lattice_track_decode.  Nothing is pooled across calls by this output: a decode
  *     pool (str_er_pool_decode) keeps the newest members of a track on the device and decodes them, call after call.
  *     Whether the polish helps on real text has not been measured, and nothing here is tuned on labelled data.                      */
 typedef struct str_er_track_decode {
@@ -1010,6 +1010,47 @@ typedef struct str_er_lattice_track_member {
     int32_t  n_del, n_ins;                /* 12, 16                                   */
     int32_t  word;                        /* 20: the member (a word index), -1 in a slot of no track */
 } str_er_lattice_track_member; /* 24 bytes; one per slot of the member array          */
+
+/* The decoding of a word track over the piece lattices of its members (str_er_set_lattice_track_decode beside STR_ER_WANT_TRACK_DECODE
+ * and STR_ER_WANT_LATTICE_DECODE, str_er_lattice_decode_tracks), here called str_er_lattice_track_decode: one string per word track, a
+ * local median under the bigram table with every member's segmentation free, and for that string every member's own cuts and
+ * alignment -- the consensus string says how each frame's touching glyphs split.  It is the cell track x bigram x lattice of the
+ * reading chain.  A definition of this library; integers only, exact, and the host states the same rules
+ * (str_er_lattice_decode_tracks_host).
+ *   Members: a track with the members w_1 .. w_n is given as for str_er_lattice_match_tracks.  Member i has the lattice of
+ *     str_er_lattice_decode on the unfolded 65-byte rows: N_i nodes, the edges (r, i, j) with the rows C_{r,i,j} and the penalty
+ *     s = SPLIT for i > 0, else 0.  A member is usable iff N_i <= 32; N_i = 0 is usable.  A track has at most 1024 members
+ *     (STR_ER_ECAPACITY above), as in str_er_track_decode.
+ *   Parameters: INS, DEL and rounds come from str_er_set_track_decode, SPLIT from str_er_set_run_split, the table B from
+ *     str_er_set_bigram.  The seeds' strings are the str_er_lattice_decode strings of the members, made with the INS / DEL of
+ *     str_er_set_word_decode.
+ *   Score of a string s of length l, 1 <= l <= 32: lm(s) is as in str_er_track_decode.  L_i(s) = D_i[N_i][l] of the recurrence of
+ *     str_er_lattice_match on member i's unfolded rows, with this output's INS / DEL, no band and no fold.  J(s) = lm(s) + the sum of
+ *     L_i(s) over the usable members.  L_i(s) is at most the cost of inserting every label and deleting every node over its shortest
+ *     edges, 32 * 255 + 32 * (255 + 255) = 24480, and lm(s) at most 33 * 255: with 1024 members J <= 25075935 < 2^31, inside int32.
+ *   Seeds: the first 32 usable members in slot order whose str_er_lattice_decode string has 1 .. 32 labels (those strings can have up
+ *     to 64 labels; longer or empty ones are no seed); duplicates count as they come.  s^0 is the seed with the smallest (J, seed
+ *     rank); seed_cost = J(s^0), seed_member that member's word index.  A track without a seed is not decoded, with exactly the "not
+ *     decoded" values of str_er_track_decode: cost, seed_cost and lm_cost are -1, n_chars = n_edits = converged = 0, seed_member = -1;
+ *     n_used is still made.
+ *   Polish: word for word that of str_er_track_decode, with J as above: the same neighbour indices (SUB j * 65 + a, DEL 2080 + j, INS
+ *     2112 + j * 65 + a), the smallest (J, index), a strict improvement or stop, converged and n_edits as there.
+ *   Record per track: a str_er_track_decode with cost = J(s), lm_cost = lm(s), n_chars = l, n_used the number of usable members, and 32
+ *     label bytes padded with 0xFF.
+ *   Record per slot of the member array, a str_er_lattice_track_member, for the final string s: cost = L_i(s), and the parts, n_del and
+ *     n_ins of member i's backtrack from (N_i, l) with the first-candidate rule of str_er_lattice_match; 32 source bytes with that
+ *     contract's meaning and padding; the parts as str_er_split_part in a table of their own, back to back in slot order.  For an
+ *     unusable member or an undecoded track, cost = -1 and the counts are 0.  In a slot of no track, word = -1.
+ *   It follows: (1) cost = lm_cost + the sum of the member costs; (2) cost <= seed_cost <= J(every seed); (3) n_parts - n_del + n_ins
+ *     = n_chars for every usable member of a decoded track; (4) rounds = 0 gives the winning seed's str_er_lattice_decode string byte
+ *     for byte; (5) if no member has a cut, the record, the labels and every member cost equal str_er_decode_tracks on the runs' rows
+ *     byte for byte, and every member's parts are its runs; (6) a track of one usable member decoded with the decoder's INS = DEL = 0
+ *     has seed_cost <= that word's str_er_lattice_decode cost: the decoded path is one alignment; (7) for the final string s taken as
+ *     a one-entry lexicon without fold, member i's cost, parts, n_del, n_ins and sources equal str_er_lattice_match_words' on that
+ *     word, wherever the band admits l.
+ *   Limits: the result is a local optimum of single edits, not the global median string.  Nothing is pooled across calls: the decode
+ *     pool (str_er_pool_decode) still has no lattice mode.  Nothing here is tuned on labelled text, and whether the joint search helps
+ *     on real video has not been measured.                                                                                           */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -1547,6 +1588,35 @@ int str_er_lattice_match_tracks_host(const str_er_run_split *splits, int32_t n_r
  * made).  The pointer may be NULL.                                                                                                  */
 int str_er_lattice_track_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
 
+/* Whether a detect call that carries both STR_ER_WANT_TRACK_DECODE and STR_ER_WANT_LATTICE_DECODE also decodes every word track over
+ * its members' piece lattices (str_er_lattice_track_decode; the tables: str_er_result_lattice_track_decodes and its neighbours).  Off
+ * by default; on is 0 or 1, anything else -> STR_ER_EINVAL.  It is a setting of the context and no stage flag: with either flag missing
+ * it does nothing, and while it is off every output of every call is byte for byte what it is without it.                          */
+int str_er_set_lattice_track_decode(str_er_ctx *ctx, int32_t on);
+/* The track decode over the members' piece lattices (str_er_lattice_track_decode) on the caller's rows, on the GPU, under the context's
+ * table, its str_er_set_word_decode INS / DEL for the seeds, its str_er_set_track_decode parameters and its SPLIT: the inputs are those
+ * of str_er_lattice_match_tracks, each with its validation; k_lattice_decode runs on the words first (the seeds), as
+ * str_er_decode_tracks runs the word decoder.  out receives n_tracks records, chars 32 label bytes per track, members_out n_members
+ * records, src 32 bytes per slot of the member array, parts the members' parts back to back in slot order and *n_parts their number.
+ * cap_parts too small -> STR_ER_ECAPACITY, *n_parts still set (it is at most the sum over the slots of the member's N).  STR_ER_ESTATE
+ * without a table; STR_ER_ECAPACITY on a track of more than 1024 members.  It needs no lexicon and no SVM model.                     */
+int str_er_lattice_decode_tracks(str_er_ctx *ctx, const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs,
+                                 int32_t n_pieces, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, const int32_t *track_first,
+                                 const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks, str_er_track_decode *out,
+                                 uint8_t *chars, str_er_lattice_track_member *members_out, uint8_t *src, str_er_split_part *parts, int32_t cap_parts,
+                                 int32_t *n_parts);
+/* The same rules on one host thread, with the table (66 x 66), the seeds' INS / DEL (dec_ins, dec_del: 0 .. 255), this output's INS /
+ * DEL (1 .. 255) and rounds (0 .. 64) and SPLIT (0 .. 255) as arguments.  Pure: no context, no GPU.                                  */
+int str_er_lattice_decode_tracks_host(const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs, int32_t n_pieces,
+                                      const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words, const int32_t *track_first,
+                                      const int32_t *track_count, const int32_t *members, int32_t n_members, int32_t n_tracks, const uint8_t *bigram,
+                                      int32_t dec_ins, int32_t dec_del, int32_t ins, int32_t del, int32_t rounds, int32_t split_cost,
+                                      str_er_track_decode *out, uint8_t *chars, str_er_lattice_track_member *members_out, uint8_t *src,
+                                      str_er_split_part *parts, int32_t cap_parts, int32_t *n_parts);
+/* Statistics of the buffer of str_er_lattice_decode_tracks and of the setting in a detect call: the bytes of its tables on the device
+ * (0: never made).  The pointer may be NULL.                                                                                          */
+int str_er_lattice_track_decode_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
+
 /* The track pool (str_er_pool_match).  Every entry point returns the library's codes and leaves the pool unchanged on any error; the
  * error text is the context's (str_er_last_error).  The calls run on the context's stream and wait for it.
  * _create: a pool of cap_tracks >= 1 empty slots in *pool; flags: 0 (the members' rows, as str_er_match_tracks) or
@@ -1912,6 +1982,15 @@ const str_er_track_match          *str_er_result_lattice_track_matches(const str
 const str_er_lattice_track_member *str_er_result_lattice_track_members(const str_er_result *r, int32_t *n);
 const uint8_t                     *str_er_result_lattice_track_src(const str_er_result *r, uint64_t *n_bytes);
 const str_er_split_part           *str_er_result_lattice_track_parts(const str_er_result *r, int32_t *n);
+/* With str_er_set_lattice_track_decode on and both STR_ER_WANT_TRACK_DECODE and STR_ER_WANT_LATTICE_DECODE (str_er_lattice_track_decode):
+ * one record and 32 label bytes per word track of str_er_result_word_tracks(), one record and 32 source bytes per slot of
+ * str_er_result_word_track_members(), and the members' parts back to back in slot order.  Each returns NULL and 0 otherwise; a call
+ * without words returns empty arrays (not NULL).                                                                                   */
+const str_er_track_decode         *str_er_result_lattice_track_decodes(const str_er_result *r, int32_t *n);
+const uint8_t                     *str_er_result_lattice_track_decode_chars(const str_er_result *r, uint64_t *n_bytes);
+const str_er_lattice_track_member *str_er_result_lattice_track_decode_members(const str_er_result *r, int32_t *n);
+const uint8_t                     *str_er_result_lattice_track_decode_src(const str_er_result *r, uint64_t *n_bytes);
+const str_er_split_part           *str_er_result_lattice_track_decode_parts(const str_er_result *r, int32_t *n);
 /* Kept-node table of one plane, ascending (key, level); NULL unless STR_ER_WANT_NODES. */
 const str_er_node *str_er_result_plane_nodes(const str_er_result *r, int32_t plane, int32_t *n);
 /* times[7] = {extract, nms, classify, track, group, ocr, total} seconds, the contract of

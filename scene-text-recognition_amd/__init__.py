@@ -26,7 +26,7 @@ from .binding import (  # noqa: F401
     WANT_LATTICE_MATCH, LATTICE_MATCH_DTYPE, lattice_match_words_host,
     WANT_LATTICE_TRACK, LATTICE_TRACK_MEMBER_DTYPE, lattice_match_tracks_host,
     WANT_TRACK_READ, WORD_LINK_DTYPE, WORD_TRACK_DTYPE, TRACK_MATCH_DTYPE, word_links, word_tracks_from_links, match_tracks_host,
-    WANT_TRACK_DECODE, TRACK_DECODE_DTYPE, decode_tracks_host,
+    WANT_TRACK_DECODE, TRACK_DECODE_DTYPE, decode_tracks_host, lattice_decode_tracks_host,
     POOL_MATCH_DTYPE, POOL_LATTICE, TrackPool, WordTracker, POOL_DECODE_DTYPE, POOL_DECODE, DecodePool,
     WANT_LINE_LINKS, LINE_LINK_DTYPE, TEXT_TRACK_DTYPE, text_tracks_from_links, EdgeFeet, TextTracker,
     WANT_FRAME_LINES, LINE_FOOT_DTYPE, LINE_PAIR_DTYPE, FRAME_LINE_DTYPE, frame_lines_from_pairs,

@@ -503,6 +503,15 @@ def load_library():
     L.str_er_lattice_match_tracks.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, i32p]
     L.str_er_lattice_match_tracks_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_uint32,
                                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, C.c_int32, i32p]
+    for name, cnt in (("lattice_track_decodes", i32p), ("lattice_track_decode_chars", C.POINTER(C.c_uint64)), ("lattice_track_decode_members", i32p),
+                      ("lattice_track_decode_src", C.POINTER(C.c_uint64)), ("lattice_track_decode_parts", i32p)):
+        fn = getattr(L, "str_er_result_" + name)
+        fn.argtypes, fn.restype = [vp, cnt], vp
+    L.str_er_set_lattice_track_decode.argtypes = [vp, C.c_int32]
+    L.str_er_lattice_track_decode_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_lattice_decode_tracks.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, i32p]
+    L.str_er_lattice_decode_tracks_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32,
+                                                    C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, i32p]
     L.str_er_track_pool_create.argtypes = [vp, C.c_int32, C.c_uint32, C.POINTER(vp)]
     L.str_er_track_pool_destroy.argtypes, L.str_er_track_pool_destroy.restype = [vp], None
     L.str_er_track_pool_reset.argtypes = [vp]
@@ -1209,6 +1218,60 @@ class Result:
         d = self.lattice_track_members[slot]
         return self.lattice_track_parts[int(d["first_part"]):int(d["first_part"]) + int(d["n_parts"])]
 
+    def _lattice_track_decode_table(self, table):
+        if table is None:
+            raise ValueError("the result has no lattice track decodes (ERFilter.set_lattice_track_decode(True) and WANT_TRACK_DECODE with WANT_LATTICE_DECODE)")
+        return table
+
+    @property
+    def lattice_track_decodes(self) -> np.ndarray:
+        """With set_lattice_track_decode(True), WANT_TRACK_DECODE and WANT_LATTICE_DECODE: TRACK_DECODE_DTYPE per word track, decoded over
+        the members' piece lattices (str_er_lattice_track_decode)."""
+        return self._lattice_track_decode_table(getattr(self, "_lattice_track_decodes", None))
+
+    @property
+    def lattice_track_decode_chars(self) -> np.ndarray:
+        """... (n tracks, 32) uint8, the labels of every track's string, 0xFF past n_chars."""
+        return self._lattice_track_decode_table(getattr(self, "_lattice_track_decode_chars", None))
+
+    @property
+    def lattice_track_decode_members(self) -> np.ndarray:
+        """... LATTICE_TRACK_MEMBER_DTYPE per slot of word_track_members: the member's cost, parts, n_del and n_ins for its track's string."""
+        return self._lattice_track_decode_table(getattr(self, "_lattice_track_decode_members", None))
+
+    @property
+    def lattice_track_decode_src(self) -> np.ndarray:
+        """... (slots of word_track_members, 32) uint8, per character of the track's string the member's part it was read from, or 0x80 |
+        the parts before the place it was inserted at; 0xFF behind the string's end."""
+        return self._lattice_track_decode_table(getattr(self, "_lattice_track_decode_src", None))
+
+    @property
+    def lattice_track_decode_parts(self) -> np.ndarray:
+        """... SPLIT_PART_DTYPE, the members' parts back to back in slot order (piece: an index of run_pieces, or -1 for a whole run)."""
+        return self._lattice_track_decode_table(getattr(self, "_lattice_track_decode_parts", None))
+
+    def word_track_lattice_decode_text(self, g: int) -> str:
+        """The string word track g was decoded to over its members' piece lattices; the representative's own reading (word_text) where
+        the track was not decoded."""
+        d = self.lattice_track_decodes[g]
+        if int(d["cost"]) < 0:
+            return self.word_text(int(self.word_tracks[g]["rep"]))
+        return "".join(_OCR_ALPHABET[int(a)] for a in self.lattice_track_decode_chars[g, :int(d["n_chars"])])
+
+    def text_track_lattice_decode_text(self, k: int) -> str:
+        """The words of the representative line of text track k in order, each as its word track's word_track_lattice_decode_text (its own
+        word_text where the line is no reading line), joined by one blank."""
+        lw = self.line_words[int(self.text_tracks[k]["rep"])]
+        of = self.word_track_of_words
+        ws = range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))
+        return " ".join(self.word_track_lattice_decode_text(int(of[w])) if of[w] >= 0 else self.word_text(w) for w in ws)
+
+    def track_member_lattice_decode_parts(self, slot: int) -> np.ndarray:
+        """The parts of the member in `slot` of word_track_members for its track's decoded string (SPLIT_PART_DTYPE; none for an unusable
+        member and an undecoded track): how the consensus string cuts that frame's touching glyphs."""
+        d = self.lattice_track_decode_members[slot]
+        return self.lattice_track_decode_parts[int(d["first_part"]):int(d["first_part"]) + int(d["n_parts"])]
+
     def _line_geom_table(self, table):
         if table is None:
             raise ValueError("the result has no line geometry (pass WANT_LINE_GEOM / want_line_geom=True)")
@@ -1568,6 +1631,12 @@ class ERFilter:
                                 res._lattice_track_members = table(L.str_er_result_lattice_track_members, LATTICE_TRACK_MEMBER_DTYPE)
                                 res._lattice_track_src = table(L.str_er_result_lattice_track_src, np.uint8, n64).reshape(-1, 32)
                                 res._lattice_track_parts = table(L.str_er_result_lattice_track_parts, SPLIT_PART_DTYPE)
+                            res._lattice_track_decodes = table(L.str_er_result_lattice_track_decodes, TRACK_DECODE_DTYPE)
+                            if res._lattice_track_decodes is not None:
+                                res._lattice_track_decode_chars = table(L.str_er_result_lattice_track_decode_chars, np.uint8, n64).reshape(-1, 32)
+                                res._lattice_track_decode_members = table(L.str_er_result_lattice_track_decode_members, LATTICE_TRACK_MEMBER_DTYPE)
+                                res._lattice_track_decode_src = table(L.str_er_result_lattice_track_decode_src, np.uint8, n64).reshape(-1, 32)
+                                res._lattice_track_decode_parts = table(L.str_er_result_lattice_track_decode_parts, SPLIT_PART_DTYPE)
             res.masks = table(L.str_er_result_masks, MASK_DTYPE)
             if res.masks is not None:
                 res.mask_bits = table(L.str_er_result_mask_bits, np.uint32, n64)
@@ -2248,6 +2317,26 @@ class ERFilter:
         self._check(self.L.str_er_lattice_match_tracks(self.h, *a[0], *a[1]))
         return _lattice_track_out(a)
 
+    def set_lattice_track_decode(self, on: bool = True) -> None:
+        """str_er_set_lattice_track_decode: whether a detect call with WANT_TRACK_DECODE and WANT_LATTICE_DECODE also decodes every word
+        track over its members' piece lattices (off by default)."""
+        self._check(self.L.str_er_set_lattice_track_decode(self.h, 1 if on else 0))
+
+    def lattice_track_decode_stats(self) -> int:
+        """str_er_lattice_track_decode_stats: the bytes of the lattice track decode tables on the device; 0: never made."""
+        a = C.c_uint64()
+        self._check(self.L.str_er_lattice_track_decode_stats(self.h, C.byref(a)))
+        return int(a.value)
+
+    def lattice_decode_tracks(self, splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members):
+        """str_er_lattice_decode_tracks: the track decode over the members' piece lattices (str_er_lattice_track_decode) of the tracks
+        members[track_first[g]:track_first[g] + track_count[g]] of the words lattice_match_tracks takes, under the context's table, its
+        set_word_decode INS / DEL for the seeds, its set_track_decode parameters and its SPLIT; returns (TRACK_DECODE_DTYPE per track,
+        (n tracks, 32) uint8 labels, LATTICE_TRACK_MEMBER_DTYPE per slot of members, (slots, 32) uint8 sources, SPLIT_PART_DTYPE parts)."""
+        a, out, ch = _lattice_track_decode_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members)
+        self._check(self.L.str_er_lattice_decode_tracks(self.h, *a[0], _np_ptr(out), _np_ptr(ch), *a[1][1:]))
+        return _lattice_track_decode_out(a, out, ch)
+
     def lattice_match_stats(self) -> int:
         """str_er_lattice_match_stats: the bytes of the lattice match tables on the device; 0: never made."""
         a = C.c_uint64()
@@ -2766,6 +2855,29 @@ def _lattice_track_args(splits, run_costs, piece_costs, first_run, n_runs_of_wor
 def _lattice_track_out(a):
     nt, nm = len(a[2][5]), len(a[2][7])
     return a[3][:nt], a[4][:nm], a[5][:nm], a[6][:a[7].value].copy()
+
+
+def _lattice_track_decode_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members):
+    a = _lattice_track_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members)
+    nt = len(a[2][5])
+    return a, np.zeros(max(1, nt), TRACK_DECODE_DTYPE), np.full((max(1, nt), 32), 0xFF, np.uint8)
+
+
+def _lattice_track_decode_out(a, out, ch):
+    nt, nm = len(a[2][5]), len(a[2][7])
+    return out[:nt], ch[:nt], a[4][:nm], a[5][:nm], a[6][:a[7].value].copy()
+
+
+def lattice_decode_tracks_host(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members, table, dec_ins: int = 0,
+                               dec_dele: int = 0, ins: int = 64, dele: int = 64, rounds: int = 8, split_cost: int = 8):
+    """str_er_lattice_decode_tracks_host (pure host, one thread): ERFilter.lattice_decode_tracks with the table, the lattice decoder's INS /
+    DEL, the track decode's parameters and SPLIT as arguments."""
+    a, out, ch = _lattice_track_decode_args(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members)
+    rc = load_library().str_er_lattice_decode_tracks_host(*a[0], _np_ptr(_bigram_table(table)), int(dec_ins), int(dec_dele), int(ins), int(dele), int(rounds),
+                                                          int(split_cost), _np_ptr(out), _np_ptr(ch), *a[1][1:])
+    if rc != 0:
+        raise StrErError(rc, "str_er_lattice_decode_tracks_host")
+    return _lattice_track_decode_out(a, out, ch)
 
 
 def lattice_match_tracks_host(splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members, words, fold_case: bool = True,
@@ -3603,6 +3715,14 @@ class FrameStream:
         for i in range(int(self.L.str_er_stream_depth(self.h))):
             ctx = self.L.str_er_stream_context(self.h, i)
             rc = self.L.str_er_set_lattice_margin(ctx, 1 if on else 0)
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
+    def set_lattice_track_decode(self, on: bool = True) -> None:
+        """str_er_set_lattice_track_decode on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_lattice_track_decode(ctx, 1 if on else 0)
             if rc != 0:
                 raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
 

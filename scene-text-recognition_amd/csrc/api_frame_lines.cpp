@@ -705,7 +705,7 @@ int fill_geometry(str_er_ctx *c, str_er_result *r, const GeomPass &GP)
 // the track match behind the matcher, with ltrack the one over the members' piece lattices behind the lattice match (frame_of: the frame of every line, frame_wh: the level-0 sizes of the frames)
 // tdecode: the same links and tracks for STR_ER_WANT_TRACK_DECODE (made once where both flags are set), the track decode behind the decoder
 int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables &T, const WordsPass &WP, bool read, bool match, bool decode, bool split, bool lattice, bool lmatch, bool ltrack, bool track, bool tdecode,
-               const std::vector<uint32_t> &frame_of, const std::vector<int32_t> &frame_wh)
+               bool ltdecode, const std::vector<uint32_t> &frame_of, const std::vector<int32_t> &frame_wh)
 {
     const auto   t2 = std::chrono::steady_clock::now();
     const size_t n_lines = r->line_feet.size();
@@ -764,11 +764,18 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
             out.lattice_track_matches = &r->lattice_track_matches; out.lattice_track_members = &r->lattice_track_members;
             out.lattice_track_src = &r->lattice_track_src; out.lattice_track_parts = &r->lattice_track_parts;
         }
+        const bool ltd = ltdecode && tdecode && decode && lattice && split;          // (a context setting, str_er_set_lattice_track_decode: no flag of its own)
+        if (ltd) {
+            out.lattice_track_decodes = &r->lattice_track_decodes; out.lattice_track_decode_chars = &r->lattice_track_decode_chars;
+            out.lattice_track_decode_members = &r->lattice_track_decode_members; out.lattice_track_decode_src = &r->lattice_track_decode_src;
+            out.lattice_track_decode_parts = &r->lattice_track_decode_parts;
+        }
         if (const int rcr = run_read_stage(c, s, T.lines, r->line_words, r->line_runs, slopes.data(), &r->run_reads, r->run_features, split ? &rp : nullptr, &out); rcr != STR_ER_OK)
             return rcr;
         r->have_track_read = track;
         r->have_word_tracks = track || tdecode;
         r->have_track_decodes = tdecode;
+        r->have_lattice_track_decodes = ltd;
         r->have_run_splits = split;
         r->have_lattice_decodes = lattice && split;
         r->have_lattice_margins = lmargin;
@@ -817,7 +824,7 @@ int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale
     if ((rc = fill_frame_lines(c, r, frame_of, pyr_of, S.feet.pairs, n_fl)) != STR_ER_OK) return rc;
     if (want.links && (rc = fill_links(c, b, r, frame_of, T, S.links)) != STR_ER_OK) return rc;
     if (want.geom && (rc = fill_geometry(c, r, S.geom)) != STR_ER_OK) return rc;
-    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split, want.lattice, want.lmatch, want.ltrack, want.track, want.tdecode, frame_of, b.frame_wh)) != STR_ER_OK) return rc;
+    if (want.words && (rc = fill_words(c, s, r, T, S.words, want.read, want.match, want.decode, want.split, want.lattice, want.lmatch, want.ltrack, want.track, want.tdecode, want.ltdecode, frame_of, b.frame_wh)) != STR_ER_OK) return rc;
     if (c->dbg_stats)        // developer aid (tools/dev_frame_lines.py): the counts and the host side of the stage
         std::fprintf(stderr, "[str_er] frame lines: %zu lines, %zu members, %zu jobs, %llu footprint words, %u candidate pairs, %zu pairs, %d frame lines, "
                              "%zu bytes back, host %.3f ms before + %.3f ms after the device\n",

@@ -19,6 +19,7 @@
 //   lattice match    A's rows (runs first, pieces from row n_run on) with (first, n_of, slot) and the split records; iff match && split
 //   lattice track    the same rows and records as the lattice match, with the track match's tracks; iff the lattice match and the track match run
 //   track decode     the same window as the decoder, with the decoder's records and labels where it left them; iff decode
+//   lattice track decode  what the lattice decode read, with its records and labels where it left them and the track decode's tracks; iff both run and the context's setting
 //   lattice margins  what the lattice decode read, with its records, labels, sources and parts where it left them; iff the lattice decode and the context's setting
 //   margins          the same window as the decoder, with the decoder's records, labels and sources where it left them; iff decode and the context's setting
 //
@@ -28,7 +29,7 @@
 //   run_probs        present iff match or decode
 //
 // The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, wg_tab, rs_tab, ld_tab, lg_tab, lm_tab,
-// lt_tab, tm_tab and td_tab hold what their kernels leave.
+// lt_tab, tm_tab, td_tab and ltd_tab hold what their kernels leave.
 #include "str_er_ctx.h"
 #include "lattice_decode_kernels.h"
 #include "lattice_match_kernels.h"
@@ -51,6 +52,11 @@ void ReadChainOut::preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k
     if (p.tdecode) {
         track_decodes->assign(tracks->size(), str_er_track_decode{-1, -1, 0, 0, 0, 0, -1, -1}); track_decode_chars->assign(32 * tracks->size(), 0xFF);
         track_decode_member_costs->assign(track_members->size(), -1);
+    }
+    if (p.ltdecode) {
+        lattice_track_decodes->assign(tracks->size(), str_er_track_decode{-1, -1, 0, 0, 0, 0, -1, -1}); lattice_track_decode_chars->assign(32 * tracks->size(), 0xFF);
+        lattice_track_decode_members->assign(track_members->size(), str_er_lattice_track_member{-1, 0, 0, 0, 0, -1});
+        lattice_track_decode_src->assign(32 * track_members->size(), 0xFF); lattice_track_decode_parts->clear();
     }
     if (p.split) { piece_costs->assign(65 * n_pc, 0); parts->clear(); word_splits->assign(n_words, str_er_word_split{0, 0, 0, 0}); }
     if (p.lattice) {
@@ -104,14 +110,14 @@ struct ReadCall {
     const SvmDev       *m;                           // null: the features only
     const size_t        n_run, n_pc, n, n_rows, n_words;      // n tiles: the runs' and behind them the pieces'; n_rows cost rows a set
     // on the host: the geometry, the tracks and with split the part slot of every word
-    std::vector<RunTile> tiles; std::vector<RotGeom> rot; std::vector<int32_t> boxes, slot, tfirst, tcount, pslot;
+    std::vector<RunTile> tiles; std::vector<RotGeom> rot; std::vector<int32_t> boxes, slot, tfirst, tcount, pslot, qslot;
     RunAtlas             A{}; size_t atlas_bytes = 0;
-    uint64_t             n_slots = 0, n_pslots = 0;
+    uint64_t             n_slots = 0, n_pslots = 0, n_qslots = 0;
     // the buffers (device, H: page-locked): the tables, the scorer's scratch, the row sets and their part rows in c->read_rows, what the consumers' kernels leave
     RunTab   TH{}, TD{};
     OcrBuf   buf{};
     uint8_t *rows[2] = {nullptr, nullptr}, *parts[2] = {nullptr, nullptr};
-    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; WgTab GM{}; LgTab LG{}; TmTab KD{}; TdTab EH{}, ED{};
+    RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; WgTab GM{}; LgTab LG{}; TmTab KD{}; TdTab EH{}, ED{}; LtdTab QH{}, QD{};
 
     // phase 1 (host alone): the tiles and rotations of the runs and pieces, every box checked, and their places in the atlas
     int geometry(const std::vector<FootLine> &lines, const std::vector<str_er_line_words> &line_words, const std::vector<str_er_line_run> &runs, const double *slopes,
@@ -284,6 +290,12 @@ struct ReadCall {
                 launch_lattice_margin(s, c->bigram.d(), c->wd_ins, c->wd_del, c->rs_split, TD.splits, rows[p.lattice_set], rows[p.lattice_set] + 65 * n_run, TD.first, TD.n_of,
                                       TD.slot, (int)n_words, reinterpret_cast<const int32_t *>(LD.dec), LD.chars, LD.src, reinterpret_cast<const int32_t *>(LD.parts), LG.margins,
                                       LG.read_margin, LG.cut_margin, LG.read, LG.alt, LG.cut_alt, nullptr, nullptr);
+            if (p.ltdecode && !tfirst.empty())          // the same rows and records, the decoder's records and labels where it left them, the track decode's tracks
+                if (const int rc = lattice_track_decode_enqueue(c, s, 0, TD.splits, rows[p.lattice_set], rows[p.lattice_set] + 65 * n_run, TD.first, TD.n_of, LD.dec, LD.chars,
+                                                                o.splits->data(), TH.first, TH.n_of, n_words, tfirst.data(), tcount.data(), o.track_members->data(),
+                                                                o.track_members->size(), tfirst.size(), qslot, &n_qslots, QH, QD);
+                    rc != STR_ER_OK)
+                    return rc;
         }
         HIP_TRY(c, hipGetLastError());
         return STR_ER_OK;
@@ -333,7 +345,18 @@ struct ReadCall {
         if (p.lattice && n_words > 0) HIP_TRY(c, down(c->ld_tab.h() + LH.o_dec, c->ld_tab.d() + LH.o_dec, LH.down_bytes));
         if (p.lmatch && n_words > 0) HIP_TRY(c, down(c->lm_tab.h() + MH.o_matches, c->lm_tab.d() + MH.o_matches, MH.down_bytes));
         if (p.ltrack && !tfirst.empty()) HIP_TRY(c, down(c->lt_tab.h() + GH.o_matches, c->lt_tab.d() + GH.o_matches, GH.down_bytes));
+        const bool ltd_ran = p.ltdecode && !tfirst.empty() && n_words > 0;
+        if (ltd_ran) HIP_TRY(c, down(c->ltd_tab.h() + QH.o_out, c->ltd_tab.d() + QH.o_out, QH.down_bytes));
         HIP_TRY(c, wait_stream(c, s));
+        if (ltd_ran) {          // the member records with their first parts, the parts compacted, the records, labels and sources as they are
+            uint64_t total = 0;
+            if (!ltd_compact(QH, qslot, n_qslots, nullptr, nullptr, &total)) return fail(c, STR_ER_EHIP, "lattice track decode: a member's parts outside its slots (internal error)");
+            o.lattice_track_decode_parts->assign((size_t)total, str_er_split_part{0, 0});
+            ltd_compact(QH, qslot, n_qslots, o.lattice_track_decode_members->data(), o.lattice_track_decode_parts->data(), &total);
+            std::memcpy(o.lattice_track_decodes->data(), QH.out, sizeof(str_er_track_decode) * tfirst.size());
+            std::memcpy(o.lattice_track_decode_chars->data(), QH.chars, 32 * tfirst.size());
+            std::memcpy(o.lattice_track_decode_src->data(), QH.src, 32 * o.track_members->size());
+        }
         if (p.lmatch && n_words > 0) {          // the records with their first parts, the parts compacted, the sources as they are
             uint64_t total = 0;
             if (!lm_compact(MH, slot, n_slots, nullptr, nullptr, &total)) return fail(c, STR_ER_EHIP, "lattice match: a word's parts outside its slots (internal error)");
@@ -388,7 +411,8 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     const ReadChainOut       &o = chain && reads ? *chain : none;
     const size_t              n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0;
     const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.track_matches != nullptr, c->lex.fold != 0,
-                                   o.lattice_matches != nullptr, o.lattice_track_matches != nullptr, o.track_decodes != nullptr, o.margins != nullptr, o.lattice_margins != nullptr);
+                                   o.lattice_matches != nullptr, o.lattice_track_matches != nullptr, o.track_decodes != nullptr, o.margins != nullptr, o.lattice_margins != nullptr,
+                                   o.lattice_track_decodes != nullptr);
     if (reads) reads->assign(n_run, str_er_run_read{});
     q.assign(1800 * n_run, 0);
     if (pieces) {

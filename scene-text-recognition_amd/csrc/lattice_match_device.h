@@ -1,7 +1,8 @@
 // lattice_match_device.h -- INTERNAL, device code: what the kernels of the lexicon match over the piece lattice
 // (lattice_match_kernels.hip) and of the track match over the members' lattices (lattice_track_kernels.hip) share -- the order of a
 // run's pieces, the edit distance of one entry over a lattice staged in LDS, and, a wave a word, the free segmentation with the nodes
-// of the word and the table of one entry with its backtrack.  The rules are stated for the host in lattice_match_rules.h.
+// of the word and the table of one entry with its backtrack (lattice_track_decode_kernels.hip runs that table on a string's labels from
+// memory).  The rules are stated for the host in lattice_match_rules.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -158,23 +159,17 @@ __device__ __forceinline__ int32_t lm_wave_nodes(LmWaveLds &L, const str_er_run_
     return fc;
 }
 
-// The table of the entry `entry` over the N <= 32 nodes lm_wave_nodes left in L, a column a lane, and lane 0's backtrack: L.rec, L.from
-// and L.part_* as k_lattice_match_final writes them out (lm_wave_store).  run (uniform) false: the record of a word without an entry.
-// Returns the entry's length (0 without), and in L.T[N * LM_TROW + len] its cost; the caller's lm_wave_sync comes before he reads L.
-__device__ __forceinline__ int lm_wave_winner(LmWaveLds &L, const WmLexDev &lex, const WmParams &prm, int split, const uint8_t *__restrict__ run_costs,
-                                              const uint8_t *__restrict__ piece_costs, int entry, int N, bool run, int lane)
+// The table of a string of `len` labels over the N <= 32 nodes lm_wave_nodes left in L, a column a lane (the lane j = min(lane, 32) brings
+// the label j of the string in a, 1 .. len, and its case partner -- or a again -- in ap), and lane 0's backtrack: L.rec, L.from and L.part_*
+// as lm_wave_store writes them out.  run (uniform) false: the record of a word without a string.  L.T[N * LM_TROW + len] is the cost; the
+// caller's lm_wave_sync comes before he reads L.
+__device__ __forceinline__ void lm_wave_path(LmWaveLds &L, const WmParams &prm, int split, const uint8_t *__restrict__ run_costs,
+                                             const uint8_t *__restrict__ piece_costs, int a, int ap, int len, int N, bool run, int lane)
 {
-    int len = 0;
     if (lane == 0) { L.rec[0] = L.rec[1] = L.rec[2] = 0; }
     if (lane < 32) L.from[lane] = 0xFF;
-    if (run) {          // (uniform) the table of the winner, a column a lane, and the backtrack
-        const int pos = __builtin_amdgcn_readfirstlane(lex.pos[entry]), g = pos >> 6, el = pos & 63;
-        len = 1;
-        while (len < 32 && g >= lex.len_first[len + 1]) ++len;
+    if (run) {          // (uniform) the table, a column a lane, and the backtrack
         const int j = min(lane, 32);
-        int       a = 0;          // the character j of the entry (1 .. len)
-        if (j >= 1 && j <= len) a = (int)(lex.chars[lex.goff[g] + (size_t)((j - 1) >> 2) * WM_GROUP + el] >> (8 * ((j - 1) & 3)) & 0xFFu);
-        const int ap = lex.fold ? wm_partner(a) : a;
         int32_t  *Tw = L.T;
         if (lane <= 32) Tw[j] = j * prm.ins;
         lm_wave_sync();
@@ -228,7 +223,33 @@ __device__ __forceinline__ int lm_wave_winner(LmWaveLds &L, const WmLexDev &lex,
             L.rec[0] = np; L.rec[1] = nd; L.rec[2] = ni;
         }
     }
+}
+
+// lm_wave_path for the entry `entry` of the lexicon.  run (uniform) false: the record of a word without an entry.  Returns the entry's
+// length (0 without).
+__device__ __forceinline__ int lm_wave_winner(LmWaveLds &L, const WmLexDev &lex, const WmParams &prm, int split, const uint8_t *__restrict__ run_costs,
+                                              const uint8_t *__restrict__ piece_costs, int entry, int N, bool run, int lane)
+{
+    int len = 0, a = 0;          // a: the character j of the entry (1 .. len)
+    if (run) {          // (uniform)
+        const int pos = __builtin_amdgcn_readfirstlane(lex.pos[entry]), g = pos >> 6, el = pos & 63;
+        len = 1;
+        while (len < 32 && g >= lex.len_first[len + 1]) ++len;
+        const int j = min(lane, 32);
+        if (j >= 1 && j <= len) a = (int)(lex.chars[lex.goff[g] + (size_t)((j - 1) >> 2) * WM_GROUP + el] >> (8 * ((j - 1) & 3)) & 0xFFu);
+    }
+    lm_wave_path(L, prm, split, run_costs, piece_costs, a, lex.fold ? wm_partner(a) : a, len, N, run, lane);
     return len;
+}
+
+// lm_wave_path for the l labels at s (l <= 32, read as they are: no fold); run (uniform) false: no string
+__device__ __forceinline__ void lm_wave_labels(LmWaveLds &L, const WmParams &prm, int split, const uint8_t *__restrict__ run_costs,
+                                               const uint8_t *__restrict__ piece_costs, const uint8_t *__restrict__ s, int l, int N, bool run, int lane)
+{
+    const int j = min(lane, 32);
+    int       a = 0;
+    if (run && j >= 1 && j <= l) a = (int)s[j - 1];
+    lm_wave_path(L, prm, split, run_costs, piece_costs, a, a, l, N, run, lane);
 }
 
 // after the caller's lm_wave_sync: the 32 source bytes to src and the L.rec[0] parts, in word order, to parts (pairs of int32)

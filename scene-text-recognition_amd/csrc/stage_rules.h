@@ -153,4 +153,12 @@ inline StageVerdict check_stages(uint32_t st, const CallShape &k, bool cascades,
     return {STR_ER_OK, nullptr};
 }
 
+// The track decode over the members' piece lattices (str_er_lattice_track_decode) has no flag of its own: it is a setting of the context
+// (str_er_set_lattice_track_decode) and runs in a detect call that carries both STR_ER_WANT_TRACK_DECODE and STR_ER_WANT_LATTICE_DECODE,
+// whose rules above already bring the word tracks, the lattice rows and the table.  With either flag missing the setting does nothing.
+inline bool lattice_track_decode_runs(uint32_t st, bool setting)
+{
+    return setting && (st & STR_ER_WANT_TRACK_DECODE) != 0 && (st & STR_ER_WANT_LATTICE_DECODE) != 0;
+}
+
 } // namespace str_er_host

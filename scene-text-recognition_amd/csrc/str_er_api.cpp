@@ -1369,6 +1369,7 @@ static int frame_lines_result(const BatchRun &R, str_er_result *r, const uint32_
     want.ltrack = (R.stages & STR_ER_WANT_LATTICE_TRACK) != 0; // (... and every word track against the lexicon over its members' piece lattices, behind the lattice match)
     want.track = (R.stages & STR_ER_WANT_TRACK_READ) != 0;      // (... and the words linked across frames, every word track against the lexicon behind the matcher)
     want.tdecode = (R.stages & STR_ER_WANT_TRACK_DECODE) != 0;  // (... and every word track decoded without a lexicon, behind the decoder)
+    want.ltdecode = lattice_track_decode_runs(R.stages, R.c->ltd_on);      // (... and, a context setting, over its members' piece lattices behind the lattice decode)
     if (d_mask_bits) {
         made_word_off.resize(r->masks.size());
         for (size_t k = 0; k < r->masks.size(); ++k) made_word_off[k] = r->masks[k].word_off;

@@ -203,6 +203,12 @@ struct str_er_result {
     std::vector<uint8_t> track_decode_chars;
     std::vector<int32_t> track_decode_member_costs;
     bool have_track_decodes = false;
+    std::vector<str_er_track_decode> lattice_track_decodes; // str_er_set_lattice_track_decode beside STR_ER_WANT_TRACK_DECODE and STR_ER_WANT_LATTICE_DECODE: one record and 32 label
+    std::vector<uint8_t> lattice_track_decode_chars;        // bytes per word track, one record and 32 source bytes per slot of the member array, and the members' parts
+    std::vector<str_er_lattice_track_member> lattice_track_decode_members;
+    std::vector<uint8_t> lattice_track_decode_src;
+    std::vector<str_er_split_part> lattice_track_decode_parts;
+    bool have_lattice_track_decodes = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -345,6 +351,8 @@ struct str_er_ctx {
     // STR_ER_WANT_TRACK_DECODE / str_er_decode_tracks (str_er_set_track_decode)
     int32_t  td_ins = 64, td_del = 64, td_rounds = 8;
     PairBuf  td_tab;                  // (str_er_decode_tracks: cost rows | first run, run count per word | the decoder's records, labels, sources) | first member, member count per track | members | records | labels | member costs
+    bool     ltd_on = false;          // str_er_set_lattice_track_decode: a detect call with STR_ER_WANT_TRACK_DECODE and STR_ER_WANT_LATTICE_DECODE also decodes the tracks over their members' lattices
+    PairBuf  ltd_tab;                 // (str_er_lattice_decode_tracks: splits | rows of the runs and pieces | first run, run count, slot per word | the lattice decoder's records, labels, sources, parts) | tracks, members and their slots | words' structure | records | labels | member records | sources | parts
     // str_er_feet_split / str_er_split_words (str_er_set_run_split)
     int32_t  rs_num = 1, rs_den = 4, rs_split = 8;
     PairBuf  rs_out;                  // a record per run slot of k_run_cuts
@@ -655,6 +663,7 @@ struct LineStageWants {
     bool lmatch = false;      // STR_ER_WANT_LATTICE_MATCH: every word against the lexicon over its piece lattice (k_lattice_match behind k_split_words on the matcher's rows)
     bool ltrack = false;      // STR_ER_WANT_LATTICE_TRACK: every word track against the lexicon over its members' piece lattices (k_lattice_track_match behind k_lattice_match)
     bool tdecode = false;     // STR_ER_WANT_TRACK_DECODE: the word links and word tracks on the host before the reading (as for track), k_track_decode behind the decoder
+    bool ltdecode = false;    // str_er_set_lattice_track_decode with tdecode and lattice: k_lattice_track_decode behind k_lattice_decode
     bool split = false;       // STR_ER_WANT_RUN_SPLIT: the cuts of every run (k_run_cuts behind k_foot_words, down with the stage's wait), the pieces read with the runs, k_split_words behind the scorer
 };
 int frame_lines_phase(str_er_ctx *c, hipStream_t s, const Batch &b, float qscale, const uint32_t *d_mask_bits, const std::vector<uint64_t> *word_off,
@@ -725,6 +734,9 @@ struct ReadChainOut {
     // STR_ER_WANT_TRACK_DECODE (with decode): the track decode of the word tracks the host made before the call (tracks, track_members: above)
     std::vector<str_er_track_decode> *track_decodes = nullptr; std::vector<uint8_t> *track_decode_chars = nullptr;
     std::vector<int32_t> *track_decode_member_costs = nullptr;
+    // str_er_set_lattice_track_decode (with the track decode and the lattice decode): the word tracks decoded over their members' piece lattices
+    std::vector<str_er_track_decode> *lattice_track_decodes = nullptr; std::vector<uint8_t> *lattice_track_decode_chars = nullptr, *lattice_track_decode_src = nullptr;
+    std::vector<str_er_lattice_track_member> *lattice_track_decode_members = nullptr; std::vector<str_er_split_part> *lattice_track_decode_parts = nullptr;
     void preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k) const;      // every table of the plan as a call without runs leaves it (k: the model's classes)
 };
 // carving a table buffer: take(bytes) is the offset of the next piece, and the one after it starts at the next multiple of 256
@@ -833,6 +845,28 @@ TdTab td_layout(uint8_t *base, size_t at, size_t n_tracks, size_t n_members);
 int track_decode_enqueue(str_er_ctx *c, hipStream_t s, size_t at, const uint8_t *d_rows, const int32_t *d_first, const int32_t *d_n_of, const void *d_dec,
                          const uint8_t *d_dchars, const int32_t *track_first, const int32_t *track_count, const int32_t *members, size_t n_members, size_t n_tracks,
                          TdTab &H, TdTab &D);
+// ---- defined in api_lattice_track_decode.cpp
+// the layout of c->ltd_tab from byte `at` on (the inputs' bytes) for n_tracks tracks over a member array of n_members with n_pslots part
+// slots: what goes up (the tracks, the members, the track and the part slot of every member slot), the structure of the n_words words,
+// and what comes down: the records, the labels, the member records, the sources and the parts
+struct LtdTab {
+    int32_t *first, *count, *members, *slot_track, *pslot, *tab; str_er_track_decode *out; uint8_t *chars; str_er_lattice_track_member *mrec;
+    uint8_t *src; str_er_split_part *parts;
+    size_t o_up, up_bytes;                // first | count | members | slot_track | pslot lie back to back: one copy up
+    size_t o_out, down_bytes, bytes;      // out | chars | mrec | src | parts lie back to back (each aligned): one copy down
+};
+LtdTab ltd_layout(uint8_t *base, size_t at, size_t n_words, size_t n_tracks, size_t n_members, size_t n_pslots);
+// The track tables into c->ltd_tab (from byte `at` on) and up on s, the kernels behind what is on s.  d_*: on the device (d_dec, d_dchars:
+// the lattice decoder's records and labels for these rows); splits, first_run, n_of: the same on the host, checked by the caller as the
+// tracks are (no track of more than 1024 members).  pslot receives the part slot of every member slot and *n_pslots their sum; H and D
+// the two sides of the layout (what comes down: H.o_out, H.down_bytes)
+int lattice_track_decode_enqueue(str_er_ctx *c, hipStream_t s, size_t at, const str_er_run_split *d_splits, const uint8_t *d_run_costs, const uint8_t *d_piece_costs,
+                                 const int32_t *d_first, const int32_t *d_n_of, const void *d_dec, const uint8_t *d_dchars, const str_er_run_split *splits,
+                                 const int32_t *first_run, const int32_t *n_of, size_t n_words, const int32_t *track_first, const int32_t *track_count,
+                                 const int32_t *members, size_t n_members, size_t n_tracks, std::vector<int32_t> &pslot, uint64_t *n_pslots, LtdTab &H, LtdTab &D);
+// after the wait: the member records with first_part set and the compacted parts from the host side of the layout (null: not copied);
+// false where a slot's parts lie outside its part slots
+bool ltd_compact(const LtdTab &H, const std::vector<int32_t> &pslot, uint64_t n_pslots, str_er_lattice_track_member *mrec, str_er_split_part *parts, uint64_t *n_parts);
 // ---- defined in api_word_match.cpp
 // the layout of what the matcher leaves in c->wm_tab from byte `at` on (the inputs' bytes) for n_words words: chunk keys | matches
 struct WmTab {
