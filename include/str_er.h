@@ -660,7 +660,9 @@ typedef struct str_er_pool_match {
  *     fields of str_er_track_decode.  An empty slot reads as a track of no members: -1, -1, 0, 0, 0, 0, -1, -1, n_members = n_kept
  *     = 0, labels 0xFF, no member costs.
  *   Limits: a slot's reading uses at most keep members, the newest; evicted evidence is gone -- this is not a sum over all members
- *     ever seen.  There is no lattice mode.  A read decodes what it is asked for every time: there is no cache of clean slots.      */
+ *     ever seen.  There is no lattice mode of a pool of this kind: a pool of a third kind, the lattice decode pool (below), keeps the
+ *     members' piece lattices and decodes them jointly.  A read decodes what it is asked for every time: there is no cache of clean
+ *     slots.                                                                                                                          */
 #define STR_ER_POOL_DECODE 2u
 typedef struct str_er_pool_decode {
     int32_t  cost, seed_cost;             /*  0,  4                                   */
@@ -669,6 +671,41 @@ typedef struct str_er_pool_decode {
     int32_t  seed_member, lm_cost;        /* 24, 28: seed_member is an age rank       */
     int32_t  n_members, n_kept;           /* 32, 36                                   */
 } str_er_pool_decode;        /* 40 bytes; one per slot read                           */
+
+/* The lattice decode pool: the track decode over the members' piece lattices (str_er_lattice_track_decode) pooled across calls -- the
+ * cell bigram table x piece lattice of the pools.  It is a str_er_track_pool of a third kind, made by
+ * str_er_track_pool_create_lattice_decode with cap_tracks slots and a per-slot limit keep, 1 .. 1024; _info reports the flags
+ * STR_ER_POOL_DECODE | STR_ER_POOL_LATTICE (3) and n_entries = 0.  str_er_track_pool_create with the flags 2 or 3 stays STR_ER_EINVAL.
+ *   Members: _add_lattice takes the arguments and checks of str_er_lattice_decode_tracks, plus slots, on the unfolded rows.  A member
+ *     is usable iff N_i <= 32, and N_i = 0 is usable: the rule of str_er_lattice_track_decode.  An unusable member is counted in
+ *     n_members and not kept.
+ *   Keys, keep and joins are the decode pool's, word for word: the key of a member is serial << 32 | its index in that call's member
+ *     array, keep is 1 .. 1024, the kept list is the `keep` largest keys among all usable members ever added to the slot or to slots
+ *     joined into it, the top-keep of a union is the top-keep of the union of top-keeps, and a slot counts at most 65536 members.
+ *     One bound is tighter: cap_tracks * keep is at most 13 421 772 (2^30 / 80), not 2^24 -- a kept member owns 80 piece rows and the
+ *     track decode tells a piece's row from a run's by bit 30 of its index, so every piece row of the store lies below 2^30.
+ *   Kept per member, on the device: its key and its run count; the str_er_run_split records of its runs; the rows of its runs (up to 32)
+ *     and of all its pieces (up to 72: 8 runs of 4 atoms with 9 pieces each); its str_er_lattice_decode record and the 64 label bytes
+ *     that the lattice decoder made on these rows under the bound table, INS / DEL and SPLIT.  A kept member takes 9072 bytes on the
+ *     device: 2080 of run rows, 5200 of piece rows (80 rows, so that every member's block starts at a multiple of 65 and of 16 bytes),
+ *     1024 of split records, 656 of lattice structure and 112 of key, counts, record and labels.
+ *   Binding: the pool is bound to what a decode pool is bound to -- the bigram table, str_er_set_word_decode and
+ *     str_er_set_track_decode -- and to the SPLIT of str_er_set_run_split.  It is stale after any setter that makes a decode pool
+ *     stale, and while the context's SPLIT differs from the bound one: the values are compared, so setting the same SPLIT again, or
+ *     another num / den only, leaves it usable (the pool never makes cuts).  A decode pool of rows does not go stale on
+ *     str_er_set_run_split.  _reset binds the pool to the context as it is then.
+ *   Defining property: take one track whose member list is the slot's kept list in ascending key order, the words numbered
+ *     0 .. n_kept - 1 in that order, word i with its runs at 32 * i and its pieces at 80 * i + its piece rows back to back in run
+ *     order, under the bound table and parameters.  _read_lattice_decode of the slot equals what str_er_lattice_decode_tracks_host
+ *     gives for that track: the record and the 32 label bytes; in age order, per kept member, its str_er_lattice_track_member, its 32
+ *     source bytes and its parts.  seed_member is an age rank, and the member records' word is the age rank too.  The record is
+ *     str_er_pool_decode.  An empty slot reads exactly as an empty slot of a decode pool.
+ *   It follows: (1) a lattice decode pool whose members have no cut reads, byte for byte, what a decode pool of rows fed the same
+ *     words reads (property (5) of str_er_lattice_track_decode); (2) one addition into empty slots with keep >= the track's usable
+ *     members equals str_er_lattice_decode_tracks of that call, up to seed_member and word being ranks and the parts' indices being
+ *     the store's.
+ *   Limits: those of the decode pool -- at most keep members, the newest, are read; evicted evidence is gone; a read decodes what it is
+ *     asked for every time -- and those of str_er_lattice_track_decode: a local optimum of single edits.                             */
 
 /* The decoding of a word under a character bigram table (STR_ER_WANT_WORD_DECODE, str_er_decode_words): the cheapest character string
  * of a word under the cost rows of its glyph runs plus a table of costs of one character after another, which may drop a run (a speck)
@@ -1048,9 +1085,10 @@ typedef struct str_er_lattice_track_member {
  *     has seed_cost <= that word's str_er_lattice_decode cost: the decoded path is one alignment; (7) for the final string s taken as
  *     a one-entry lexicon without fold, member i's cost, parts, n_del, n_ins and sources equal str_er_lattice_match_words' on that
  *     word, wherever the band admits l.
- *   Limits: the result is a local optimum of single edits, not the global median string.  Nothing is pooled across calls: the decode
- *     pool (str_er_pool_decode) still has no lattice mode.  Nothing here is tuned on labelled text, and whether the joint search helps
- *     on real video has not been measured.                                                                                           */
+ *   Limits: the result is a local optimum of single edits, not the global median string.  Nothing is pooled across calls by this entry
+ *     point: the decode pool of rows (str_er_pool_decode) still has no lattice mode, and pooling this decode across calls is a pool of
+ *     its own kind, the lattice decode pool (str_er_track_pool_create_lattice_decode).  Nothing here is tuned on labelled text, and
+ *     whether the joint search helps on real video has not been measured.                                                            */
 
 typedef struct str_er_plane_info {
     uint32_t frame;
@@ -1655,7 +1693,7 @@ int str_er_track_pool_read(str_er_track_pool *pool, const int32_t *slots, int32_
 /* The decode pool (str_er_pool_decode).  _destroy, _reset, _info, _add, _join and _clear above work on it as on a lexicon pool: _add
  * takes the unfolded 65-byte rows of str_er_word_decode with the arguments and checks it has, a join leaves in dst the keep newest
  * of the union and the srcs empty.  _add_lattice and _read on a decode pool and _read_decode and _members on a lexicon pool answer
- * STR_ER_ESTATE.
+ * STR_ER_ESTATE; the pool that takes _add_lattice without a lexicon is the lattice decode pool (below).
  * _create_decode: cap_tracks >= 1 empty slots of 1 <= keep <= 1024 kept members each (else STR_ER_EINVAL); STR_ER_ESTATE without a
  * bigram table; STR_ER_ECAPACITY where cap_tracks * keep passes 2^24 (a kept member takes about 2.2 KB on the device),
  * STR_ER_ENOMEM where the device does not have the memory.                                                                          */
@@ -1669,6 +1707,32 @@ int str_er_track_pool_read_decode(str_er_track_pool *pool, const int32_t *slots,
  * member, of which the first n_runs are the member's).  Any of keys, n_runs and rows may be NULL.  For callers who want the evidence
  * back, e.g. to read it again over lattices.                                                                                        */
 int str_er_track_pool_members(str_er_track_pool *pool, int32_t slot, uint64_t *keys, int32_t *n_runs, uint8_t *rows, int32_t *n_kept);
+
+/* The lattice decode pool (see "The lattice decode pool" at str_er_pool_decode).  _destroy, _reset, _info, _keep, _join and _clear
+ * work on it as on a decode pool; _add_lattice adds to it; _read_decode gives the decode pool's record, labels and member costs, the
+ * same shapes.  _add, _read and _members on it answer STR_ER_ESTATE, as _read_lattice_decode and _lattice_members do on every other
+ * kind of pool.
+ * _create_lattice_decode: cap_tracks >= 1 empty slots of 1 <= keep <= 1024 kept members each (else STR_ER_EINVAL); STR_ER_ESTATE
+ * without a bigram table; STR_ER_ECAPACITY where cap_tracks * keep passes 13 421 772 (2^30 / 80: the piece rows of the store stay
+ * below the bit that marks a piece's row) or the store (9072 bytes a kept member and 4 a slot: about 122 GB at that bound) passes 2^40
+ * bytes, STR_ER_ENOMEM where the device does not have the memory.                                                       */
+int str_er_track_pool_create_lattice_decode(str_er_ctx *ctx, int32_t cap_tracks, int32_t keep, str_er_track_pool **pool);
+/* out, chars and member_cost as str_er_track_pool_read_decode.  members_out receives keep records a slot, the kept members' in age
+ * order with word = the age rank, behind them records with cost = -1 and word = -1; src 32 bytes per such record; parts the kept
+ * members' parts of all slots read back to back in that order, first_part indexing that table, *n_parts their number.  A part's run
+ * is 32 * rank + the member's run and its piece 80 * rank + the member's piece row (-1: the whole run): the indices of
+ * str_er_track_pool_lattice_members' arrays for that slot.  members_out, src and parts may be NULL, each on its own; with parts
+ * cap_parts too small -> STR_ER_ECAPACITY, *n_parts still set (it is at most 32 * the kept members).  A slot may be named more than
+ * once.                                                                                                                              */
+int str_er_track_pool_read_lattice_decode(str_er_track_pool *pool, const int32_t *slots, int32_t n, str_er_pool_decode *out, uint8_t *chars, int32_t *member_cost,
+                                          str_er_lattice_track_member *members_out, uint8_t *src, str_er_split_part *parts, int32_t cap_parts, int32_t *n_parts);
+/* The kept list of one slot in age order, with fixed strides per member: *n_kept members with their keys [keep], run counts [keep],
+ * split records [keep x 32], run rows [keep x 32 x 65 bytes] and piece rows [keep x 80 x 65 bytes].  Of a member's 32 records and run
+ * rows the first n_runs are its own, of its 80 piece rows the first sum of its runs' n_pieces (at most 72); what lies behind them is
+ * zero.  The first_piece of a returned split record indexes that member's own piece rows.  Any of keys, n_runs, splits, run_rows and
+ * piece_rows may be NULL.                                                                                                            */
+int str_er_track_pool_lattice_members(str_er_track_pool *pool, int32_t slot, uint64_t *keys, int32_t *n_runs, str_er_run_split *splits, uint8_t *run_rows,
+                                      uint8_t *piece_rows, int32_t *n_kept);
 
 /* The crops of STR_ER_WANT_LINE_CROPS: height (8..256), max_width (1..8192) and pad (0..1, a fraction of the line's height on every
  * side).  Defaults 32, 1024, 0.125.  Anything else -> STR_ER_EINVAL, the context unchanged.  A stream's contexts:

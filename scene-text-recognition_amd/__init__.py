@@ -27,7 +27,7 @@ from .binding import (  # noqa: F401
     WANT_LATTICE_TRACK, LATTICE_TRACK_MEMBER_DTYPE, lattice_match_tracks_host,
     WANT_TRACK_READ, WORD_LINK_DTYPE, WORD_TRACK_DTYPE, TRACK_MATCH_DTYPE, word_links, word_tracks_from_links, match_tracks_host,
     WANT_TRACK_DECODE, TRACK_DECODE_DTYPE, decode_tracks_host, lattice_decode_tracks_host,
-    POOL_MATCH_DTYPE, POOL_LATTICE, TrackPool, WordTracker, POOL_DECODE_DTYPE, POOL_DECODE, DecodePool,
+    POOL_MATCH_DTYPE, POOL_LATTICE, TrackPool, WordTracker, POOL_DECODE_DTYPE, POOL_DECODE, DecodePool, LatticeDecodePool,
     WANT_LINE_LINKS, LINE_LINK_DTYPE, TEXT_TRACK_DTYPE, text_tracks_from_links, EdgeFeet, TextTracker,
     WANT_FRAME_LINES, LINE_FOOT_DTYPE, LINE_PAIR_DTYPE, FRAME_LINE_DTYPE, frame_lines_from_pairs,
     CAND_DTYPE, NODE_DTYPE, PLANE_DTYPE, ERFilter, FrameStream, PlaneResult, Params, Result, StrErError, apply_runtime_hint, set_batch_slots, lib_path, load_library,

@@ -525,6 +525,9 @@ def load_library():
     L.str_er_track_pool_keep.argtypes = [vp, i32p]
     L.str_er_track_pool_read_decode.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
     L.str_er_track_pool_members.argtypes = [vp, C.c_int32, vp, vp, vp, i32p]
+    L.str_er_track_pool_create_lattice_decode.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.str_er_track_pool_read_lattice_decode.argtypes = [vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, i32p]
+    L.str_er_track_pool_lattice_members.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, i32p]
     L.str_er_lattice_match_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, i32p]
     L.str_er_lattice_match_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_int32, vp, vp, vp, C.c_int32, i32p]
@@ -3295,6 +3298,58 @@ class DecodePool(TrackPool):
         return d
 
 
+class LatticeDecodePool(DecodePool):
+    """str_er_track_pool_create_lattice_decode: a DecodePool over the members' piece lattices (the lattice decode pool of str_er.h):
+    per slot the newest `keep` usable members (N <= 32 nodes) added to it -- their split records, run rows, piece rows and lattice
+    decoder strings -- kept from call to call; a read decodes a slot as ERFilter.lattice_decode_tracks decodes the track of its kept
+    members in age order, every member's segmentation free.  Bound to what a DecodePool is bound to and to the SPLIT of
+    set_run_split: after set_bigram, set_word_decode, set_track_decode or a set_run_split with another split_cost every call raises
+    STR_ER_ESTATE until reset().  add_lattice feeds it and add raises; join, clear, reset, text and close are DecodePool's."""
+
+    def __init__(self, f: "ERFilter", cap_tracks: int, keep: int = 32):
+        self.f, self.L, self.lattice = f, f.L, True
+        h = C.c_void_p()
+        f._check(self.L.str_er_track_pool_create_lattice_decode(f.h, int(cap_tracks), int(keep), C.byref(h)))
+        self.h = h
+        self.cap_tracks, self.keep = int(cap_tracks), int(keep)
+
+    def add(self, *args, **kw) -> None:
+        raise StrErError(-6, "a lattice decode pool takes add_lattice")
+
+    def add_lattice(self, splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members, slots) -> None:
+        """str_er_track_pool_add_lattice: the tracks, given as for ERFilter.lattice_decode_tracks, are added to the slots slots[g]
+        (distinct)."""
+        TrackPool.add_lattice(self, splits, run_costs, piece_costs, first_run, n_runs_of_word, track_first, track_count, members, slots)
+
+    def read_lattice(self, slots):
+        """str_er_track_pool_read_lattice_decode: read()'s triple, then (n, keep) LATTICE_TRACK_MEMBER_DTYPE (the kept members in age
+        order, word = the age rank; cost = word = -1 past n_kept), (n, keep, 32) uint8 sources and the SPLIT_PART_DTYPE parts of all
+        slots back to back (run 32 * rank + the member's run, piece 80 * rank + the member's piece row)."""
+        sl = self._slots(slots)
+        n = len(sl)
+        out = np.zeros(max(1, n), POOL_DECODE_DTYPE)
+        ch = np.full((max(1, n), 32), 0xFF, np.uint8)
+        mc = np.full((max(1, n), self.keep), -1, np.int32)
+        mrec = np.zeros((max(1, n), self.keep), LATTICE_TRACK_MEMBER_DTYPE)
+        sr = np.full((max(1, n), self.keep, 32), 0xFF, np.uint8)
+        cap = int(min(32 * max(1, n) * self.keep, 2 ** 31 - 1))
+        parts = np.zeros(cap, SPLIT_PART_DTYPE)
+        k = C.c_int32()
+        self._check(self.L.str_er_track_pool_read_lattice_decode(self.h, _np_ptr(sl) if n else None, n, _np_ptr(out), _np_ptr(ch), _np_ptr(mc), _np_ptr(mrec), _np_ptr(sr),
+                                                                 _np_ptr(parts), cap, C.byref(k)))
+        return out[:n], ch[:n], mc[:n], mrec[:n], sr[:n], parts[:k.value].copy()
+
+    def members(self, slot: int):
+        """str_er_track_pool_lattice_members: the kept list of a slot in age order: (uint64 keys, int32 run counts, (n_kept, 32)
+        RUN_SPLIT_DTYPE whose first_piece indexes the member's own piece rows, (n_kept, 32, 65) uint8 run rows, (n_kept, 80, 65) uint8
+        piece rows); what lies behind a member's own records and rows is zero."""
+        kp = self.keep
+        keys, nr, sp = np.zeros(kp, np.uint64), np.zeros(kp, np.int32), np.zeros((kp, 32), RUN_SPLIT_DTYPE)
+        rr, pr, n = np.zeros((kp, 32, 65), np.uint8), np.zeros((kp, 80, 65), np.uint8), C.c_int32()
+        self._check(self.L.str_er_track_pool_lattice_members(self.h, int(slot), _np_ptr(keys), _np_ptr(nr), _np_ptr(sp), _np_ptr(rr), _np_ptr(pr), C.byref(n)))
+        return keys[:n.value], nr[:n.value], sp[:n.value], rr[:n.value], pr[:n.value]
+
+
 def _decode_text(rec, chars):
     return "".join(_OCR_ALPHABET[int(a)] for a in chars[:int(rec["n_chars"])]) if int(rec["cost"]) >= 0 else None
 
@@ -3316,7 +3371,11 @@ class WordTracker:
     (with want_word_decode) instead of, or beside, want_word_match and want_track_read; the decode pool is fed the unfolded rows of
     the words, so a result whose run_costs a folding lexicon folded is refused with ValueError before either pool is touched.
     read_decode / decode_text give the pooled decode of an id, and a closed track's final one goes to `closed_decodes` as
-    (id, record, chars)."""
+    (id, record, chars).
+      A LatticeDecodePool as decode_pool pools the joint decode over the members' piece lattices instead: it is fed run_splits,
+    run_costs and piece_costs of the result, which then needs want_run_split and want_lattice_decode beside want_track_decode.  The
+    refusal of folded rows applies unchanged, the pieces' rows being folded where the runs' are; read_decode, decode_text and
+    closed_decodes work as with a DecodePool."""
 
     def __init__(self, linker: "ERFilter", pool: Optional[TrackPool] = None, decode_pool: Optional["DecodePool"] = None):
         if pool is None and decode_pool is None:
@@ -3439,7 +3498,11 @@ class WordTracker:
                     self.pool.add(*self._rows(res), tracks["first"], tracks["count"], members, slots)
             if self.decode_pool is not None:
                 try:
-                    self.decode_pool.add(*self._rows(res), tracks["first"], tracks["count"], members, slots)
+                    if isinstance(self.decode_pool, LatticeDecodePool):
+                        self.decode_pool.add_lattice(res.run_splits, res.run_costs, res.piece_costs, words["first_run"], words["n_runs"], tracks["first"], tracks["count"],
+                                                     members, slots)
+                    else:
+                        self.decode_pool.add(*self._rows(res), tracks["first"], tracks["count"], members, slots)
                 except Exception:
                     if self.pool is not None:          # (the lexicon pool took the tracks already: it gives them back)
                         self.pool.clear(slots)

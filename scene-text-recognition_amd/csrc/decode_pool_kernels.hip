@@ -6,53 +6,19 @@
 // waits for another: a workgroup owns the slot it writes (the slots of a call are distinct), so the pool holds the same bytes every
 // run.  The rules are stated for the host in decode_pool_rules.h; the contract is at str_er_pool_decode in str_er.h.
 //
-// Placement, the same in k_dpool_keep and k_dpool_join: the survivors are the `keep` largest keys of old and incoming together.  A
-// surviving old cell stays where it is; the i-th freed or empty cell, ascending, takes the i-th incoming survivor, ascending by key (a
-// prefix sum over the cells).  Keys are ranked by counting in LDS: at most 1024 x 1024 comparisons a workgroup.
+// The placement (which cells stay, which cell an incoming member takes) is decode_pool_device.h, shared with the lattice decode pool.
 #include <hip/hip_runtime.h>
 
+#include "decode_pool_device.h"
 #include "decode_pool_kernels.h"
 
 namespace str_er {
 
 namespace {
 
-constexpr int DP_THREADS = 256, DP_WAVES = DP_THREADS / 64;
-constexpr int DP_MAX_KEEP = 1024, DP_PER_THREAD = DP_MAX_KEEP / DP_THREADS;      // a thread takes up to four neighbouring cells
 constexpr int DP_ALPHABET = 65, DP_MAX_ROWS = 32, DP_CHARS = 64, DP_DEC_INTS = 6;
 constexpr int DP_CELL_CHUNKS = DP_CELL_ROW_BYTES / 16;
-static_assert(DP_CELL_ROW_BYTES % 16 == 0 && DP_PER_THREAD == 4, "cell layout");
-
-// the exclusive prefix sum of v over the workgroup's threads and its total; called by every thread (wsum: DP_WAVES ints of LDS)
-__device__ __forceinline__ int dp_scan(int v, int *wsum, int tid, int &total)
-{
-    const int lane = tid & 63, wave = tid >> 6;
-    int       inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    __syncthreads();          // (the sums of the scan before are read)
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < DP_WAVES; ++w) {
-        if (w < wave) base += wsum[w];
-        total += wsum[w];
-    }
-    return base + inc - v;
-}
-
-// how many of the n keys at k (LDS) are larger than key
-__device__ __forceinline__ int dp_larger(const uint64_t *k, int n, uint64_t key)
-{
-    int g = 0;
-    for (int i = 0; i < n; ++i) g += k[i] > key ? 1 : 0;
-    return g;
-}
+static_assert(DP_CELL_ROW_BYTES % 16 == 0, "cell layout");
 
 // the decoder's record and labels of a member into a cell, by the lanes of a wave
 __device__ __forceinline__ void dp_copy_strings(const DpPoolDev &pool, size_t cell, const int32_t *dec, const uint8_t *dchars, int lane)
@@ -67,58 +33,16 @@ __global__ void __launch_bounds__(DP_THREADS) k_dpool_keep(DpPoolDev pool, uint3
                                                            const int32_t *__restrict__ track_first, const int32_t *__restrict__ track_count,
                                                            const int32_t *__restrict__ members, const int32_t *__restrict__ slots)
 {
-    __shared__ uint64_t okey[DP_MAX_KEEP];
-    __shared__ int32_t  inc[DP_MAX_KEEP];            // the i-th incoming survivor, ascending: its index in the member array
-    __shared__ int32_t  cell_of[DP_MAX_KEEP];        // ... and the cell it takes
-    __shared__ int      wsum[DP_WAVES];
+    __shared__ DpKeepLds L;
     const int    t = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int    first = track_first[t], count = track_count[t], slot = slots[t], keep = pool.keep;
     const size_t c0 = (size_t)slot * (size_t)keep;
-    for (int c = tid; c < keep; c += DP_THREADS) okey[c] = pool.key[c0 + c];
-    // the usable members of the call: how many, then their ranks in the order of the member array.  Their keys ascend with the index
-    // and are all larger than the slot's, so the newest min(U, keep) of them survive and nothing else of the call is ever written.
-    int u = 0;
-    for (int j = tid; j < count; j += DP_THREADS) u += n_of[members[first + j]] <= DP_MAX_ROWS ? 1 : 0;
-    int U;
-    dp_scan(u, wsum, tid, U);          // (okey is written behind its barriers)
-    const int nin = min(U, keep), skip = U - nin;
-    int       base = 0;
-    for (int j0 = 0; j0 < count; j0 += DP_THREADS) {          // (at most 256 rounds: a track has at most 65536 members)
-        const int  j = j0 + tid;
-        const bool q = j < count && n_of[members[first + j]] <= DP_MAX_ROWS;
-        int        total;
-        const int  r = base + dp_scan(q ? 1 : 0, wsum, tid, total);
-        if (q && r >= skip) inc[r - skip] = first + j;
-        base += total;
-    }
-    // the old cells that stay: those with fewer than keep - nin larger old keys
-    const int room = keep - nin, cpt = (keep + DP_THREADS - 1) / DP_THREADS;
-    int       n_free = 0;
-    uint32_t  freed = 0, evicted = 0;
-#pragma unroll
-    for (int q = 0; q < DP_PER_THREAD; ++q) {
-        const int c = tid * cpt + q;
-        if (q >= cpt || c >= keep) continue;
-        const uint64_t key = okey[c];
-        const bool     stays = key != 0 && dp_larger(okey, keep, key) < room;
-        if (!stays) { freed |= 1u << q; ++n_free; }
-        if (!stays && key != 0) evicted |= 1u << q;
-    }
-    int total_free;
-    int rank = dp_scan(n_free, wsum, tid, total_free);
-#pragma unroll
-    for (int q = 0; q < DP_PER_THREAD; ++q) {
-        if (!(freed >> q & 1u)) continue;
-        const int c = tid * cpt + q;
-        if (rank < nin) cell_of[rank] = c;
-        else if (evicted >> q & 1u) pool.key[c0 + c] = 0;          // (an evicted cell that nothing takes)
-        ++rank;
-    }
-    __syncthreads();
+    // the usable members of the call: at most 32 rows
+    const int nin = dp_place_add(L, pool.key + c0, keep, first, count, members, [&](int w) { return n_of[w] <= DP_MAX_ROWS; }, tid);
     // a wave a survivor: its rows come from any multiple of 65 bytes, so they are read byte by byte; the cell takes 16-byte stores
     for (int i = wave; i < nin; i += DP_WAVES) {
-        const int      idx = inc[i], w = members[idx], m = max(n_of[w], 0), n_bytes = m * DP_ALPHABET;
-        const size_t   cell = c0 + (size_t)cell_of[i];
+        const int      idx = L.inc[i], w = members[idx], m = max(n_of[w], 0), n_bytes = m * DP_ALPHABET;
+        const size_t   cell = c0 + (size_t)L.cell_of[i];
         const uint8_t *src = costs + (size_t)first_run[w] * DP_ALPHABET;
         uint4         *dst = reinterpret_cast<uint4 *>(pool.costs + cell * DP_CELL_ROW_BYTES);
         for (int ch = lane; ch * 16 < n_bytes; ch += 64) {
@@ -139,68 +63,21 @@ __global__ void __launch_bounds__(DP_THREADS) k_dpool_keep(DpPoolDev pool, uint3
     if (tid == 0) pool.n_members[slot] += count;
 }
 
-// One workgroup: dst takes the srcs one at a time.  The `keep` largest keys of a union are those of the union of the lists' own `keep`
-// largest, so LDS holds the keys of two slots, whatever n_srcs is.
+// One workgroup: dst takes the srcs one at a time.
 __global__ void __launch_bounds__(DP_THREADS) k_dpool_join(DpPoolDev pool, int dst, const int32_t *__restrict__ srcs, int n_srcs)
 {
-    __shared__ uint64_t dkey[DP_MAX_KEEP], skey[DP_MAX_KEEP];
-    __shared__ int32_t  take[DP_MAX_KEEP];           // the i-th surviving cell of the src, ascending by key
-    __shared__ int32_t  cell_of[DP_MAX_KEEP];        // ... and the cell of dst it takes
-    __shared__ int      wsum[DP_WAVES];
-    const int    tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, keep = pool.keep, cpt = (keep + DP_THREADS - 1) / DP_THREADS;
+    __shared__ DpJoinLds L;
+    const int    tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, keep = pool.keep;
     const size_t d0 = (size_t)dst * (size_t)keep;
-    for (int c = tid; c < keep; c += DP_THREADS) dkey[c] = pool.key[d0 + c];
+    for (int c = tid; c < keep; c += DP_THREADS) L.dkey[c] = pool.key[d0 + c];
     int32_t joined = 0;          // (thread 0) the members of the srcs
     for (int k = 0; k < n_srcs; ++k) {
         const int    src = srcs[k];
         const size_t s0 = (size_t)src * (size_t)keep;
-        __syncthreads();          // (the keys and places of the src before are read)
-        for (int c = tid; c < keep; c += DP_THREADS) skey[c] = pool.key[s0 + c];
-        __syncthreads();
-        // the src's survivors: fewer than keep larger keys in both lists
-        int      n_surv = 0, larger_own[DP_PER_THREAD];
-        uint32_t surv = 0;
-#pragma unroll
-        for (int q = 0; q < DP_PER_THREAD; ++q) {
-            const int c = tid * cpt + q;
-            larger_own[q] = 0;
-            if (q >= cpt || c >= keep) continue;
-            const uint64_t key = skey[c];
-            if (key == 0) continue;
-            larger_own[q] = dp_larger(skey, keep, key);
-            if (larger_own[q] + dp_larger(dkey, keep, key) < keep) { surv |= 1u << q; ++n_surv; }
-        }
-        int n_in;
-        dp_scan(n_surv, wsum, tid, n_in);
-#pragma unroll
-        for (int q = 0; q < DP_PER_THREAD; ++q)
-            if (surv >> q & 1u) take[n_in - 1 - larger_own[q]] = tid * cpt + q;          // (every larger key of the src survives too)
-        // the cells of dst that stay
-        int      n_free = 0;
-        uint32_t freed = 0, evicted = 0;
-#pragma unroll
-        for (int q = 0; q < DP_PER_THREAD; ++q) {
-            const int c = tid * cpt + q;
-            if (q >= cpt || c >= keep) continue;
-            const uint64_t key = dkey[c];
-            const bool     stays = key != 0 && dp_larger(dkey, keep, key) + dp_larger(skey, keep, key) < keep;
-            if (!stays) { freed |= 1u << q; ++n_free; }
-            if (!stays && key != 0) evicted |= 1u << q;
-        }
-        int total_free;
-        int rank = dp_scan(n_free, wsum, tid, total_free);          // (its barriers: every count above is made before dkey changes)
-#pragma unroll
-        for (int q = 0; q < DP_PER_THREAD; ++q) {
-            if (!(freed >> q & 1u)) continue;
-            const int c = tid * cpt + q;
-            if (rank < n_in) cell_of[rank] = c;
-            else if (evicted >> q & 1u) { pool.key[d0 + c] = 0; dkey[c] = 0; }          // (an evicted cell that nothing takes)
-            ++rank;
-        }
-        __syncthreads();
+        const int    n_in = dp_place_join(L, pool.key + d0, pool.key + s0, keep, tid);
         // a wave a survivor, cell to cell in 16-byte pieces
         for (int i = wave; i < n_in; i += DP_WAVES) {
-            const size_t from = s0 + (size_t)take[i], to = d0 + (size_t)cell_of[i];
+            const size_t from = s0 + (size_t)L.take[i], to = d0 + (size_t)L.cell_of[i];
             const int    m = pool.n_of[from], n_bytes = m * DP_ALPHABET;
             const uint4 *a = reinterpret_cast<const uint4 *>(pool.costs + from * DP_CELL_ROW_BYTES);
             uint4       *b = reinterpret_cast<uint4 *>(pool.costs + to * DP_CELL_ROW_BYTES);
@@ -208,8 +85,8 @@ __global__ void __launch_bounds__(DP_THREADS) k_dpool_join(DpPoolDev pool, int d
             dp_copy_strings(pool, to, pool.dec + from * DP_DEC_INTS, pool.dchars + from * DP_CHARS, lane);
             if (lane == 0) {
                 pool.n_of[to] = m;
-                pool.key[to] = skey[take[i]];
-                dkey[cell_of[i]] = skey[take[i]];
+                pool.key[to] = L.skey[L.take[i]];
+                L.dkey[L.cell_of[i]] = L.skey[L.take[i]];
             }
         }
         for (int c = tid; c < keep; c += DP_THREADS) pool.key[s0 + c] = 0;

@@ -23,5 +23,12 @@ void launch_lattice_track_decode(hipStream_t s, const uint8_t *bigram, int ins, 
                                  const uint8_t *piece_costs, const int32_t *first_run, const int32_t *n_of, int n_words, const void *dec, const uint8_t *dchars,
                                  const int32_t *track_first, const int32_t *track_count, const int32_t *members, const int32_t *slot_track, const int32_t *pslot,
                                  int n_members, int n_tracks, int32_t *tab, void *out, uint8_t *chars, int32_t *mrec, uint8_t *src, int32_t *parts);
+// The two steps on their own: launch_lattice_track_table (lattice_track_kernels.h) makes tab, and this one decodes on a tab that is
+// given -- the rows of the words the members name must have been made with the same del and split.  The lattice decode pool keeps a
+// row per cell of its store and makes those of the cells it reads.
+void launch_lattice_track_decode_tab(hipStream_t s, const uint8_t *bigram, int ins, int del, int rounds, int split, const str_er_run_split *splits, const uint8_t *run_costs,
+                                     const uint8_t *piece_costs, const int32_t *first_run, const int32_t *n_of, const void *dec, const uint8_t *dchars,
+                                     const int32_t *track_first, const int32_t *track_count, const int32_t *members, const int32_t *slot_track, const int32_t *pslot,
+                                     int n_members, int n_tracks, const int32_t *tab, void *out, uint8_t *chars, int32_t *mrec, uint8_t *src, int32_t *parts);
 
 } // namespace str_er

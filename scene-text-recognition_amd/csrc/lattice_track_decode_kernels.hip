@@ -495,19 +495,27 @@ __global__ void __launch_bounds__(64 * LTD_WAVES) k_lattice_track_decode_members
 
 } // namespace
 
+void launch_lattice_track_decode_tab(hipStream_t s, const uint8_t *bigram, int ins, int del, int rounds, int split, const str_er_run_split *splits, const uint8_t *run_costs,
+                                     const uint8_t *piece_costs, const int32_t *first_run, const int32_t *n_of, const void *dec, const uint8_t *dchars,
+                                     const int32_t *track_first, const int32_t *track_count, const int32_t *members, const int32_t *slot_track, const int32_t *pslot,
+                                     int n_members, int n_tracks, const int32_t *tab, void *out, uint8_t *chars, int32_t *mrec, uint8_t *src, int32_t *parts)
+{
+    if (n_tracks > 0)
+        hipLaunchKernelGGL(k_lattice_track_decode, dim3((unsigned)n_tracks), dim3(LTD_THREADS), 0, s, bigram, ins, del, rounds, split, run_costs, piece_costs, tab,
+                           static_cast<const int32_t *>(dec), dchars, track_first, track_count, members, static_cast<int32_t *>(out), chars);
+    if (n_members > 0)
+        hipLaunchKernelGGL(k_lattice_track_decode_members, dim3((unsigned)((n_members + LTD_WAVES - 1) / LTD_WAVES)), dim3(64 * LTD_WAVES), 0, s, ins, del, split, splits,
+                           run_costs, piece_costs, first_run, n_of, members, slot_track, pslot, n_members, static_cast<const int32_t *>(out), chars, mrec, src, parts);
+}
+
 void launch_lattice_track_decode(hipStream_t s, const uint8_t *bigram, int ins, int del, int rounds, int split, const str_er_run_split *splits, const uint8_t *run_costs,
                                  const uint8_t *piece_costs, const int32_t *first_run, const int32_t *n_of, int n_words, const void *dec, const uint8_t *dchars,
                                  const int32_t *track_first, const int32_t *track_count, const int32_t *members, const int32_t *slot_track, const int32_t *pslot,
                                  int n_members, int n_tracks, int32_t *tab, void *out, uint8_t *chars, int32_t *mrec, uint8_t *src, int32_t *parts)
 {
-    if (n_tracks > 0) {
-        launch_lattice_track_table(s, del, split, splits, first_run, n_of, n_words, tab);
-        hipLaunchKernelGGL(k_lattice_track_decode, dim3((unsigned)n_tracks), dim3(LTD_THREADS), 0, s, bigram, ins, del, rounds, split, run_costs, piece_costs, tab,
-                           static_cast<const int32_t *>(dec), dchars, track_first, track_count, members, static_cast<int32_t *>(out), chars);
-    }
-    if (n_members > 0)
-        hipLaunchKernelGGL(k_lattice_track_decode_members, dim3((unsigned)((n_members + LTD_WAVES - 1) / LTD_WAVES)), dim3(64 * LTD_WAVES), 0, s, ins, del, split, splits,
-                           run_costs, piece_costs, first_run, n_of, members, slot_track, pslot, n_members, static_cast<const int32_t *>(out), chars, mrec, src, parts);
+    if (n_tracks > 0) launch_lattice_track_table(s, del, split, splits, first_run, n_of, n_words, tab);
+    launch_lattice_track_decode_tab(s, bigram, ins, del, rounds, split, splits, run_costs, piece_costs, first_run, n_of, dec, dchars, track_first, track_count, members,
+                                    slot_track, pslot, n_members, n_tracks, tab, out, chars, mrec, src, parts);
 }
 
 } // namespace str_er

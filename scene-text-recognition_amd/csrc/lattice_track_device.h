@@ -23,6 +23,39 @@ __device__ __forceinline__ uint32_t lt_len_mask(int R, int N, int band)
     return (n >= 32 ? ~0u : (1u << n) - 1u) << (lo - 1);
 }
 
+// The structure of one word (its runs first .. first + n_runs of splits) into its row T of the table, by one thread: N (33: more than
+// 32 nodes), the two structure words, D[n][0] and the row of every (node, span) slot.  k_lattice_track_table makes it for every word of
+// a call; the lattice decode pool makes it for the cells of a read.
+__device__ __forceinline__ void lt_table_row(int32_t *__restrict__ T, int del, int split, const str_er_run_split *__restrict__ splits, int first, int n_runs)
+{
+    const int m = max(n_runs, 0), mr = min(m, LM_MAX_RUNS);
+    for (int k = 0; k < LM_SLOTS; ++k) T[LT_EROW + k] = -1;
+    int      N = 0;
+    uint32_t s0 = 0, s1 = 0;
+    T[LT_D0] = 0;
+    for (int t = 0; t < mr; ++t) {
+        const int A = lm_atoms(splits, first + t), fp = splits[first + t].first_piece;
+        if (N + A > LM_MAX_NODES) { N = LM_MAX_NODES + 1; break; }
+        for (int jl = 1; jl <= A; ++jl) {
+            const int      n = N + jl;
+            int            dn = 0x7FFFFFFF;
+            const uint32_t bits = (uint32_t)(jl - 1) << (2 * ((n - 1) & 15));
+            if (n <= 16) s0 |= bits;
+            else s1 |= bits;
+            for (int d = 1; d <= jl; ++d) {
+                const int i = jl - d, k = lm_piece_index(A, i, jl);
+                T[LT_EROW + (n - 1) * 4 + d - 1] = k < 0 ? first + t : (fp + k) | LM_PIECE;
+                dn = min(dn, T[LT_D0 + n - d] + del + (i > 0 ? split : 0));          // (this thread's own writes)
+            }
+            T[LT_D0 + n] = dn;
+        }
+        N += A;
+    }
+    if (m > mr) N = LM_MAX_NODES + 1;
+    for (int n = N + 1; n <= LM_MAX_NODES; ++n) T[LT_D0 + n] = 0;      // (past N: jl = 1, computed and not used)
+    T[LT_N] = N; T[LT_S0] = (int32_t)s0; T[LT_S1] = (int32_t)s1;
+}
+
 } // namespace
 
 } // namespace str_er

@@ -65,33 +65,7 @@ __global__ void __launch_bounds__(64) k_lattice_track_table(int del, int split, 
 {
     const int w = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (w >= n_words) return;
-    int32_t  *T = tab + (size_t)w * LT_TAB_INTS;
-    const int m = max(n_of[w], 0), first = first_run[w], mr = min(m, LM_MAX_RUNS);
-    for (int k = 0; k < LM_SLOTS; ++k) T[LT_EROW + k] = -1;
-    int      N = 0;
-    uint32_t s0 = 0, s1 = 0;
-    T[LT_D0] = 0;
-    for (int t = 0; t < mr; ++t) {
-        const int A = lm_atoms(splits, first + t), fp = splits[first + t].first_piece;
-        if (N + A > LM_MAX_NODES) { N = LM_MAX_NODES + 1; break; }
-        for (int jl = 1; jl <= A; ++jl) {
-            const int      n = N + jl;
-            int            dn = 0x7FFFFFFF;
-            const uint32_t bits = (uint32_t)(jl - 1) << (2 * ((n - 1) & 15));
-            if (n <= 16) s0 |= bits;
-            else s1 |= bits;
-            for (int d = 1; d <= jl; ++d) {
-                const int i = jl - d, k = lm_piece_index(A, i, jl);
-                T[LT_EROW + (n - 1) * 4 + d - 1] = k < 0 ? first + t : (fp + k) | LM_PIECE;
-                dn = min(dn, T[LT_D0 + n - d] + del + (i > 0 ? split : 0));          // (this thread's own writes)
-            }
-            T[LT_D0 + n] = dn;
-        }
-        N += A;
-    }
-    if (m > mr) N = LM_MAX_NODES + 1;
-    for (int n = N + 1; n <= LM_MAX_NODES; ++n) T[LT_D0 + n] = 0;      // (past N: jl = 1, computed and not used)
-    T[LT_N] = N; T[LT_S0] = (int32_t)s0; T[LT_S1] = (int32_t)s1;
+    lt_table_row(tab + (size_t)w * LT_TAB_INTS, del, split, splits, first_run[w], n_of[w]);
 }
 
 // grid (chunks of the whole lexicon, tracks).  The workgroup walks the track's members one at a time: the rows of the member's (node,

@@ -1247,6 +1247,37 @@ public:
         out.parts.resize((size_t)n);
         return out;
     }
+    // The decode of the same tracks over their members' piece lattices, without a lexicon (str_er_lattice_decode_tracks; the contract is
+    // at str_er_lattice_track_decode in include/str_er.h): the context's table, str_er_set_word_decode INS / DEL for the seeds,
+    // str_er_set_track_decode parameters and SPLIT.  Per track a record and 32 labels, per slot of the member array a record and 32
+    // source bytes, and the members' parts back to back.
+    struct LatticeTrackDecodes {
+        std::vector<str_er_track_decode>         decodes;
+        std::vector<uint8_t>                     chars;
+        std::vector<str_er_lattice_track_member> members;
+        std::vector<uint8_t>                     src;
+        std::vector<str_er_split_part>           parts;
+    };
+    LatticeTrackDecodes lattice_decode_tracks(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                                              const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs, const std::vector<int32_t> &track_first,
+                                              const std::vector<int32_t> &track_count, const std::vector<int32_t> &members)
+    {
+        LatticeTrackMatches sized = lattice_track_out(splits, run_costs, piece_costs, first_run, n_runs, track_first, track_count, members);
+        LatticeTrackDecodes out;
+        out.decodes.resize(track_first.size()); out.chars.assign(32 * track_first.size(), 0xFF);
+        out.members.swap(sized.members); out.src.swap(sized.src); out.parts.swap(sized.parts);
+        int32_t n = 0;
+        check(str_er_lattice_decode_tracks(ctx_.get(), splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                           piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65),
+                                           first_run.empty() ? nullptr : first_run.data(), n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(),
+                                           track_first.empty() ? nullptr : track_first.data(), track_count.empty() ? nullptr : track_count.data(),
+                                           members.empty() ? nullptr : members.data(), (int32_t)members.size(), (int32_t)track_first.size(),
+                                           out.decodes.empty() ? nullptr : out.decodes.data(), out.chars.empty() ? nullptr : out.chars.data(),
+                                           out.members.empty() ? nullptr : out.members.data(), out.src.empty() ? nullptr : out.src.data(), out.parts.data(),
+                                           (int32_t)out.parts.size(), &n));
+        out.parts.resize((size_t)n);
+        return out;
+    }
     // the string word track g takes over its members' piece lattices: the lexicon entry (as given in `lexicon`), "" where it has none
     static std::string word_track_lattice_text(const LatticeTrackMatches &lt, const std::vector<std::string> &lexicon, size_t g)
     {
@@ -1473,6 +1504,102 @@ public:
         void reset() { check(str_er_track_pool_reset(pool_.get())); }
     private:
         template <typename T> static const T *ptr(const std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
+        void check(int rc) const
+        {
+            if (rc != STR_ER_OK) throw std::runtime_error(std::string(str_er_strerror(rc)) + ": " + str_er_last_error(ctx_.get()));
+        }
+        std::shared_ptr<str_er_ctx>        ctx_;      // (declared first: the pool is destroyed before its context)
+        std::shared_ptr<str_er_track_pool> pool_;
+        int32_t                            keep_;
+    };
+
+    // The lattice decode pool (str_er_track_pool_create_lattice_decode; the contract is at "The lattice decode pool" in
+    // include/str_er.h): a decode pool over the members' piece lattices -- per slot the newest `keep` usable members (N <= 32 nodes),
+    // their split records, run rows, piece rows and lattice decoder strings, kept from call to call; a read decodes a slot as
+    // lattice_decode_tracks decodes the track of its kept members in age order.  Bound to what a DecodePool is bound to and to SPLIT:
+    // after one of their setters (set_run_split with another SPLIT) every call throws (STR_ER_ESTATE) until reset().
+    class LatticeDecodePool {
+    public:
+        LatticeDecodePool(const ERFilter &f, int32_t cap_tracks, int32_t keep = 32) : ctx_(f.ctx_), keep_(keep)
+        {
+            str_er_track_pool *p = nullptr;
+            check(str_er_track_pool_create_lattice_decode(ctx_.get(), cap_tracks, keep, &p));
+            pool_.reset(p, str_er_track_pool_destroy);
+        }
+        int32_t keep() const { return keep_; }
+        // the tracks, given as for lattice_decode_tracks (unfolded rows), are added to the slots slots[g] (distinct)
+        void add_lattice(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                         const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs, const std::vector<int32_t> &track_first,
+                         const std::vector<int32_t> &track_count, const std::vector<int32_t> &members, const std::vector<int32_t> &slots)
+        {
+            if (run_costs.size() != 65 * splits.size() || piece_costs.size() % 65 || first_run.size() != n_runs.size() || track_first.size() != track_count.size() ||
+                slots.size() != track_first.size())
+                throw std::invalid_argument("LatticeDecodePool::add_lattice: 65 bytes a run and a piece, one record a run, one span a word, one span and one slot a track");
+            check(str_er_track_pool_add_lattice(pool_.get(), ptr(splits), (int32_t)splits.size(), ptr(run_costs), ptr(piece_costs), (int32_t)(piece_costs.size() / 65),
+                                                ptr(first_run), ptr(n_runs), (int32_t)first_run.size(), ptr(track_first), ptr(track_count), ptr(members),
+                                                (int32_t)members.size(), (int32_t)track_first.size(), ptr(slots)));
+        }
+        // slot dst keeps the newest of its own and the srcs' kept members; the srcs become empty
+        void join(int32_t dst, const std::vector<int32_t> &srcs) { check(str_er_track_pool_join(pool_.get(), dst, ptr(srcs), (int32_t)srcs.size())); }
+        void clear(const std::vector<int32_t> &slots) { check(str_er_track_pool_clear(pool_.get(), ptr(slots), (int32_t)slots.size())); }
+        // per slot named (a slot may be named more than once) a record, 32 labels and keep member costs in age order (-1 past n_kept);
+        // keep member records (word: the age rank; cost = word = -1 past n_kept) and 32 source bytes each; the kept members' parts of
+        // all slots back to back (run 32 * rank + the member's run, piece 80 * rank + the member's piece row)
+        struct Reads {
+            std::vector<str_er_pool_decode>          records;
+            std::vector<uint8_t>                     chars;
+            std::vector<int32_t>                     member_costs;
+            std::vector<str_er_lattice_track_member> members;
+            std::vector<uint8_t>                     src;
+            std::vector<str_er_split_part>           parts;
+        };
+        Reads read(const std::vector<int32_t> &slots)
+        {
+            const size_t nk = (size_t)keep_ * slots.size();
+            if (32 * nk + 1 > 0x7FFFFFFFull) throw std::invalid_argument("LatticeDecodePool::read: too many slots");
+            Reads r;
+            r.records.resize(slots.size()); r.chars.assign(32 * slots.size(), 0xFF); r.member_costs.assign(nk, -1);
+            r.members.resize(nk); r.src.assign(32 * nk, 0xFF); r.parts.resize(32 * nk + 1);
+            int32_t n = 0;
+            check(str_er_track_pool_read_lattice_decode(pool_.get(), ptr(slots), (int32_t)slots.size(), ptr(r.records), r.chars.empty() ? nullptr : r.chars.data(),
+                                                        r.member_costs.empty() ? nullptr : r.member_costs.data(), r.members.empty() ? nullptr : r.members.data(),
+                                                        r.src.empty() ? nullptr : r.src.data(), r.parts.data(), (int32_t)r.parts.size(), &n));
+            r.parts.resize((size_t)n);
+            return r;
+        }
+        // the record, the labels and the member costs alone (str_er_track_pool_read_decode: the same decode, less to copy back)
+        Reads read_decode(const std::vector<int32_t> &slots)
+        {
+            Reads r;
+            r.records.resize(slots.size()); r.chars.assign(32 * slots.size(), 0xFF); r.member_costs.assign((size_t)keep_ * slots.size(), -1);
+            check(str_er_track_pool_read_decode(pool_.get(), ptr(slots), (int32_t)slots.size(), ptr(r.records), r.chars.empty() ? nullptr : r.chars.data(),
+                                                r.member_costs.empty() ? nullptr : r.member_costs.data()));
+            return r;
+        }
+        // the kept list of a slot in age order: keys, run counts, and per member 32 split records (first_piece: into its own piece
+        // rows), 32 run rows and 80 piece rows of 65 bytes
+        struct Members {
+            std::vector<uint64_t>         keys;
+            std::vector<int32_t>          n_runs;
+            std::vector<str_er_run_split> splits;
+            std::vector<uint8_t>          run_rows, piece_rows;
+        };
+        Members members(int32_t slot)
+        {
+            Members      m;
+            const size_t k = (size_t)keep_;
+            m.keys.resize(k); m.n_runs.resize(k); m.splits.resize(k * 32); m.run_rows.resize(k * 32 * 65); m.piece_rows.resize(k * 80 * 65);
+            int32_t n = 0;
+            check(str_er_track_pool_lattice_members(pool_.get(), slot, m.keys.data(), m.n_runs.data(), m.splits.data(), m.run_rows.data(), m.piece_rows.data(), &n));
+            m.keys.resize((size_t)n); m.n_runs.resize((size_t)n); m.splits.resize((size_t)n * 32); m.run_rows.resize((size_t)n * 32 * 65);
+            m.piece_rows.resize((size_t)n * 80 * 65);
+            return m;
+        }
+        // every slot empty, the pool bound to the filter's table, parameters and SPLIT as they are now
+        void reset() { check(str_er_track_pool_reset(pool_.get())); }
+    private:
+        template <typename T> static const T *ptr(const std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
+        template <typename T> static T *ptr(std::vector<T> &v) { return v.empty() ? nullptr : v.data(); }
         void check(int rc) const
         {
             if (rc != STR_ER_OK) throw std::runtime_error(std::string(str_er_strerror(rc)) + ": " + str_er_last_error(ctx_.get()));

@@ -18,12 +18,19 @@
         (k_dpool_plan, k_track_decode, k_dpool_records, copy back, wait) and beside them decode_tracks on all members, which is
         what a caller without the pool runs for every batch.  The records are compared.  --iters: one process of fill and read
         rounds only, for a `rocprofv3 --kernel-trace --stats` run.
+    python tools/dev_track_pool.py lattice-decode [--touch 0.2] [--per-track 8] [--keep K] [--rounds 8] [--iters N] [--reps 7]
+        the lattice decode pool (profiles/lattice_decode_pool.md) on the workloads of `dev_lattice_track_decode.py kernel`: 125 tracks
+        of --per-track readings (--touch 0: no cut anywhere; --touch p: that share of the neighbouring glyphs touch), fed as
+        --per-track additions of one member per track into a LatticeDecodePool of --keep: the time of every addition (upload,
+        k_lattice_decode, k_ldpool_keep, wait), of a read of the 125 slots (k_dpool_plan, k_ldpool_tracks, k_lattice_track_decode,
+        k_lattice_track_decode_members, k_ldpool_records, copy back, wait) and beside them lattice_decode_tracks on all members.  The
+        records are compared.  --iters: one process of fill and read rounds only, for a `rocprofv3 --kernel-trace --stats` run.
 """
 import argparse, json, os, sys, time
 import numpy as np
 
 ap = argparse.ArgumentParser()
-ap.add_argument("mode", choices=["batch", "stream", "slots", "decode"])
+ap.add_argument("mode", choices=["batch", "stream", "slots", "decode", "lattice-decode"])
 ap.add_argument("--words", type=int, default=1000)
 ap.add_argument("--per-track", type=int, default=8)
 ap.add_argument("--entries", type=int, default=100000)
@@ -31,6 +38,7 @@ ap.add_argument("--batches", type=int, default=10)
 ap.add_argument("--slots", type=int, default=125)
 ap.add_argument("--keep", type=int, default=0)
 ap.add_argument("--rounds", type=int, default=8)
+ap.add_argument("--touch", type=float, default=0.2)
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--iters", type=int, default=0)
 ap.add_argument("--same-length", action="store_true")
@@ -228,8 +236,72 @@ def decode_mode():
     return out
 
 
+def lattice_decode_mode():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import lattice_track_decode_ref as R
+    import track_decode_ref as TD
+    rng = np.random.default_rng(1)
+    n_tracks, per, keep = a.words // a.per_track, a.per_track, a.keep or a.per_track
+    truths = lambda: [int(x) for x in rng.integers(0, 65, int(rng.integers(3, 13)))]
+    if a.touch > 0:
+        packed = R.pack([R.make_track(rng, truths(), per, touch=a.touch) for _ in range(n_tracks)])
+    else:          # the tracks of the `decode` mode, every run a word's run without a cut
+        costs, first, n_of, tfirst, tcount, members = TD.pack([TD.make_track(rng, truths(), per) for _ in range(n_tracks)])
+        sp = np.zeros(len(costs), S.RUN_SPLIT_DTYPE)
+        sp["cut"] = -1
+        packed = (sp, costs, np.zeros((0, 65), np.uint8), first, n_of, tfirst, tcount, members)
+    sp, rr, pr, first, n_of, tfirst, tcount, members = packed
+    B = rng.integers(0, 90, (66, 66)).astype(np.uint8)
+    f = S.ERFilter(params=S.Params(max_width=64, max_height=64, max_frames=1))
+    f.set_bigram(B)
+    f.set_track_decode(64, 64, a.rounds)
+    pool = S.LatticeDecodePool(f, n_tracks, keep)
+    slots = np.arange(n_tracks, dtype=np.int32)
+    # addition j: member j of every track, a track of one member each, with the runs and pieces of those words alone
+    adds = []
+    for j in range(per):
+        ws = members[tfirst + j]
+        runs = np.concatenate([np.arange(first[w], first[w] + n_of[w]) for w in ws]).astype(np.int64)
+        s = sp[runs].copy()
+        rows = [pr[int(q["first_piece"]):int(q["first_piece"]) + int(q["n_pieces"])] for q in s]
+        s["first_piece"] = np.concatenate([[0], np.cumsum(s["n_pieces"])[:-1]])
+        n = n_of[ws].astype(np.int32)
+        adds.append((s, rr[runs], np.concatenate(rows + [np.zeros((0, 65), np.uint8)]), np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int32), n,
+                     np.arange(n_tracks, dtype=np.int32), np.ones(n_tracks, np.int32), np.arange(n_tracks, dtype=np.int32)))
+    def fill():
+        t = []
+        pool.clear(slots)
+        for args in adds:
+            t0 = time.perf_counter(); pool.add_lattice(*args, slots); t.append((time.perf_counter() - t0) * 1e3)
+        return t
+    one_call = lambda: f.lattice_decode_tracks(*packed)
+    info = pool.info()
+    out = {"lib": S.lib_path(), "tracks": n_tracks, "per_track": per, "keep": keep, "rounds": a.rounds, "touch": a.touch, "words": int(len(first)), "runs": int(len(rr)),
+           "pieces": int(len(pr)), "cut_runs": int((sp["n_cuts"] > 0).sum()), "pool": info, "device_bytes_per_slot": round(info["device_bytes"] / n_tracks, 1),
+           "store_bytes_per_kept_member": 9072}
+    fill()
+    got = pool.read_lattice(slots)
+    want = one_call()
+    same = [k for k in want[0].dtype.names if k != "seed_member"]
+    out["records_equal"] = bool(keep >= per and all((got[0][k] == want[0][k]).all() for k in same) and (got[1] == want[1]).all() and
+                                (got[2][:, :per].reshape(-1) == want[2]["cost"]).all() and (got[4][:, :per].reshape(-1, 32) == want[3]).all() and
+                                len(got[5]) == len(want[4]))
+    if a.iters:
+        for _ in range(a.iters):
+            fill(); pool.read_lattice(slots); one_call()
+        out["iters"] = a.iters
+    else:
+        t = np.array([fill() for _ in range(a.reps)])          # (reps, per): the j-th addition finds j members pooled
+        out["add_call_ms"] = [stats(t[:, j].tolist()) for j in range(per)]
+        out["read_lattice_call_ms"] = timed(lambda: pool.read_lattice(slots), a.reps)
+        out["read_call_ms"] = timed(lambda: pool.read(slots), a.reps)
+        out["lattice_decode_tracks_call_ms"] = timed(one_call, a.reps)
+    pool.close(); f.close()
+    return out
+
+
 if __name__ == "__main__":
-    res = {"batch": batch, "stream": stream, "slots": slots_mode, "decode": decode_mode}[a.mode]()
+    res = {"batch": batch, "stream": stream, "slots": slots_mode, "decode": decode_mode, "lattice-decode": lattice_decode_mode}[a.mode]()
     print(json.dumps(res, indent=1))
     if a.out:
         with open(a.out, "w") as fh:
