@@ -776,6 +776,61 @@ typedef struct str_er_word_margin {
     int32_t  read, alt;                   /*  8, 12                                   */
 } str_er_word_margin;        /* 16 bytes; one per word of str_er_result_words()       */
 
+/* The decoding of a whole text line under the bigram table (str_er_set_line_decode beside STR_ER_WANT_WORD_DECODE, str_er_decode_lines):
+ * one Viterbi pass over all rows of a line in which every gap between two rows either joins them into one word or breaks the line into
+ * two words, so that the word breaks are chosen together with the string.  The cheapest string of the line, blanks included, and the
+ * word segmentation that goes with it.  A definition of this library; integers only, exact, and the host states the same rules
+ * (str_er_decode_lines_host).  The word gap of str_er_line_run stays what it is: it is one path this decoder is never worse than.
+ *   Symbols and moves: the symbols, the table B (66 x 66, E = 65), INS, DEL (str_er_set_word_decode), INF = 2^20 and the unfolded
+ *     65-byte cost rows are those of str_er_word_decode.
+ *   Gap costs: one pair of bytes (J_i, K_i) per row, for the gap in front of row i: J_i the cost of joining row i to the word of row
+ *     i-1, K_i of breaking in front of it.  The pair of a line's first row is ignored.  255 means the move is off; a pair with both
+ *     entries off is an argument error (STR_ER_EINVAL).
+ *   Recurrence, for a line with the rows 1 .. n, n <= 1024, in int32: V_0[E] = 0, V_0[a] = INF for a < 65.  For i = 1 .. n:
+ *     Gap step, for i >= 2, on V = V_{i-1}: W[a] = V[a] + J_i for all a in 0 .. 65; if J_i is off, W[a] = INF exactly.  If K_i is not
+ *     off: X = min over a in 0 .. 65 of (V[a] + B[a][E]) + K_i, attained at the smallest such a; if X < W[E] then W[E] = X and the gap is
+ *     a BREAK from a; on a tie the join stays.  A break from a = E is allowed: that is an empty word and it costs B[E][E].  For i = 1,
+ *     W = V_0.
+ *     Run step on W: exactly the step of str_er_word_decode (SUB with the smallest predecessor in 0 .. 65, U[E] = INF, DEL on a strict
+ *     <, INS over b < 65 on a strict <).  It gives V_i.
+ *     cost = min over a of V_n[a] + B[a][E], attained at the smallest a.  For n = 0 it is B[E][E].
+ *   Why 1024: the all-SUB path that takes at every gap a move that is on costs at most 255 + 255 for the first row, for every further
+ *     row the row byte 255 plus the larger of a join, B[a][b] + J <= 255 + 254, and a break, B[a][E] + K + B[E][b] <= 255 + 254 + 255,
+ *     that is 1019, and 255 at the end: cost <= 510 + 1019 * 1023 + 255 = 1 043 202 < 2^20 for n = 1024, so INF never wins, and every
+ *     value stays below 2^25.  A line with n > 1024 is not decoded: cost = -1, the counts are 0, the labels are 0xFF, the sources
+ *     0xFFFF and word_of_row is -1.
+ *   Backtrack, from the end state, for i = n .. 1: undo the run step as str_er_word_decode does (INS emits c and goes to the U-level
+ *     state, SUB emits b, DEL emits nothing).  If the state is now E and gap i recorded a BREAK, emit the label 65 and go to the
+ *     recorded a.  Reversed, the labels are the line's string: 0 .. 64 for characters, 65 for a blank.
+ *   Sources (uint16, the line-relative row index): i-1 for SUB, (i-1) | 0x8000 for INS, (i-1) | 0x4000 for the break in front of row
+ *     i-1.
+ *   Per line: the record below, with n_chars counting the breaks too: n_sub + n_ins + n_breaks = n_chars and n_sub + n_del = n.
+ *     Labels (uint8) and sources (uint16): the line's slice begins at entry 3 * first_row of a table of 3 * n_rows entries (3n - 1 is
+ *     the most a line can emit) and is padded with 0xFF / 0xFFFF past n_chars.  One int32 per row, word_of_row: the number of breaks
+ *     emitted before the row's character, or -1 for a dropped row.  So the line has n_breaks + 1 words, empty ones included.
+ *   It follows: (1) with (J, K) = (0, off) at every gap and n <= 32, cost, labels and sources equal str_er_word_decode's on the same
+ *     rows (bit 7 of its source is 0x8000 here).  (2) With (0, off) inside the words of some segmentation and (off, 0) at its word
+ *     gaps, every word of <= 32 rows: cost is the sum of the words' str_er_word_decode costs, and the labels are the words' labels
+ *     joined by one 65, for any table, B[E][E] != 0 included.  (3) For any gap costs with both moves on, cost <= that same sum plus
+ *     the J / K the segmentation pays at its gaps.
+ *   Gap costs from the geometry (str_er_line_gap_costs; a definition of this library, like the word gap itself, not tuned): for
+ *     consecutive rows of one line that belong to different runs p, q: g = q.x0 - p.x1 (below 0 counts as 0),
+ *     x = min(16, (8 * g * den) / (num * colmax)) in 64-bit integers with num / den the word gap, so x = 8 is exactly the threshold
+ *     of str_er_line_run; with the weight w in 0 .. 127: J = (w * x) / 8, K = (w * (16 - x)) / 8.  Both are <= 254 and never off, they
+ *     tie at the old threshold, and w = 0 leaves the decision to the table alone.  Rows of the same run (the parts of
+ *     STR_ER_WANT_RUN_SPLIT) get (0, 255): a cut inside a run is never a blank.  The first row of a line, and a row of no line, gets
+ *     (0, 255) as well.
+ *   Limits: one path per line, no margins.  The segmentation of the runs themselves is the fixed one of the decoder's window: joint
+ *     decoding over the piece lattice is not part of this.  No tracks, no pool.  Nothing is calibrated: the weight is the caller's.
+ *   In a detect call the rows are the decoder's: the runs of the line, and with STR_ER_WANT_RUN_SPLIT the parts of its words in word
+ *     order (the rows of str_er_result_split_parts(); the windows then index that table, and the line is decoded behind a second wait,
+ *     once the parts are known).  A line's window runs from the first row of its first word to the last row of its last word.       */
+typedef struct str_er_line_decode {
+    int32_t  cost, n_chars;               /*  0,  4                                   */
+    int32_t  n_breaks, n_sub;             /*  8, 12                                   */
+    int32_t  n_del, n_ins;                /* 16, 20                                   */
+} str_er_line_decode;        /* 24 bytes; one per line of str_er_result_texts()       */
+
 /* The decoding of a word track without a lexicon (STR_ER_WANT_TRACK_DECODE, str_er_decode_tracks): one string for all members of a
  * word track of str_er_word_link, a median string of the members under their cost rows and the bigram table, reached from the members'
  * own decoder strings by single edits.  A definition of this library; integers only, exact, and the host states the same rules
@@ -1495,6 +1550,32 @@ int str_er_word_margins(str_er_ctx *ctx, const uint8_t *costs, int32_t n_runs, c
 int str_er_word_margins_host(const uint8_t *costs, int32_t n_runs, const int32_t *first_run, const int32_t *n_runs_of_word, int32_t n_words,
                              const uint8_t *bigram, int32_t ins, int32_t del, str_er_word_margin *margins, int32_t *row_margin, uint8_t *row_read,
                              uint8_t *row_alt, int32_t *marginals);
+/* Whether a detect call with STR_ER_WANT_WORD_DECODE also decodes every line of str_er_result_texts() (str_er_line_decode), and the
+ * weight (0 .. 127) of its gap costs: on != 0 switches it on; off by default, the weight 16.  A weight outside 0 .. 127 ->
+ * STR_ER_EINVAL, the context unchanged.  A context setting, not a stage flag: without STR_ER_WANT_WORD_DECODE it does nothing, and while
+ * it is off no call does anything more than before.  A stream's contexts: str_er_stream_context.                                  */
+int str_er_set_line_decode(str_er_ctx *ctx, int32_t on, int32_t weight);
+/* The gap costs of str_er_line_decode from the geometry.  Line t has the rows first_row[t] .. first_row[t] + n_rows_of_line[t] of
+ * n_rows rows and the colmax colmax[t] of str_er_line_words; row r belongs to the run row_run[r] of runs (row_run == NULL: row r is
+ * run r); num / den is the word gap (1 .. 65535 each), weight is in 0 .. 127.  gaps receives 2 * n_rows bytes, (J, K) per row.  Pure:
+ * no context, no GPU.  STR_ER_EINVAL on NULL arguments, a window outside the rows, a row outside the runs, num, den or weight out of
+ * range, or a line of more than one run with colmax 0.                                                                           */
+int str_er_line_gap_costs(const str_er_line_run *runs, int32_t n_runs, const int32_t *row_run, int32_t n_rows, const int32_t *first_row,
+                          const int32_t *n_rows_of_line, const uint32_t *colmax, int32_t n_lines, int32_t num, int32_t den, int32_t weight, uint8_t *gaps);
+/* The line decoder (str_er_line_decode) on the caller's cost rows, on the GPU, under the context's table and the INS / DEL of
+ * str_er_set_word_decode: costs holds n_rows rows of 65 bytes and gaps 2 * n_rows bytes, line t has the rows first_row[t] ..
+ * first_row[t] + n_rows_of_line[t]; the windows lie in ascending order and do not overlap (every line writes its own slice).  dec
+ * receives n_lines records, chars 3 * n_rows bytes, src 3 * n_rows uint16 and word_of_row n_rows int32; what lies in no line is
+ * 0xFF / 0xFFFF / -1.  STR_ER_ESTATE without a table; STR_ER_EINVAL on NULL arguments, a window outside the rows or out of order, or a
+ * gap of a line with both moves off; the context stays usable.  n_lines = 0 is fine.                                               */
+int str_er_decode_lines(str_er_ctx *ctx, const uint8_t *costs, int32_t n_rows, const uint8_t *gaps, const int32_t *first_row, const int32_t *n_rows_of_line,
+                        int32_t n_lines, str_er_line_decode *dec, uint8_t *chars, uint16_t *src, int32_t *word_of_row);
+/* The same rules on one host thread, with the table and INS / DEL as arguments (with the checks of str_er_set_word_decode).  Pure:
+ * no context, no GPU.                                                                                                              */
+int str_er_decode_lines_host(const uint8_t *costs, int32_t n_rows, const uint8_t *gaps, const int32_t *first_row, const int32_t *n_rows_of_line, int32_t n_lines,
+                             const uint8_t *bigram, int32_t ins, int32_t del, str_er_line_decode *dec, uint8_t *chars, uint16_t *src, int32_t *word_of_row);
+/* The bytes of the line decoder's back-pointer table on the device (68 uint16 per row of the largest call so far; 0 before the first).  */
+int str_er_line_decode_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
 /* INS and DEL (1 .. 255) and the number of polish rounds (0 .. 64) of str_er_track_decode; defaults 64, 64 and 8.  Anything else ->
  * STR_ER_EINVAL, the context unchanged.  A stream's contexts: str_er_stream_context.                                               */
 int str_er_set_track_decode(str_er_ctx *ctx, int32_t ins, int32_t del, int32_t rounds);
@@ -1991,6 +2072,16 @@ const str_er_word_margin *str_er_result_word_margins(const str_er_result *r, int
 const int32_t            *str_er_result_word_row_margins(const str_er_result *r, uint64_t *n_bytes);
 const uint8_t            *str_er_result_word_row_reads(const str_er_result *r, uint64_t *n_bytes);
 const uint8_t            *str_er_result_word_row_alts(const str_er_result *r, uint64_t *n_bytes);
+/* With STR_ER_WANT_WORD_DECODE on a context whose str_er_set_line_decode is on (str_er_line_decode): one record per line of
+ * str_er_result_texts(); the labels (3 bytes per row: a row is a run of str_er_result_line_runs(), with STR_ER_WANT_RUN_SPLIT a part
+ * of str_er_result_split_parts()), the sources (uint16, n: their number) and word_of_row (one per row); the gap costs used (2 bytes
+ * per row) and the lines' windows into the rows (2 int32 per line: first row, row count).  Each returns NULL and 0 when the call made none; a call without lines returns empty arrays (not NULL).             */
+const str_er_line_decode *str_er_result_line_decodes(const str_er_result *r, int32_t *n);
+const uint8_t            *str_er_result_line_decode_chars(const str_er_result *r, uint64_t *n_bytes);
+const uint16_t           *str_er_result_line_decode_src(const str_er_result *r, uint64_t *n);
+const int32_t            *str_er_result_line_decode_word_of_row(const str_er_result *r, uint64_t *n);
+const uint8_t            *str_er_result_line_gap_costs(const str_er_result *r, uint64_t *n_bytes);
+const int32_t            *str_er_result_line_decode_windows(const str_er_result *r, uint64_t *n);
 /* With STR_ER_WANT_RUN_SPLIT (str_er_run_split): one split record per run of str_er_result_line_runs(); the pieces they index, with
  * one reading and one 65-byte cost row per piece; the parts of the words back to back in word order; one record per word of
  * str_er_result_words().  NULL (and *n = 0) without the flag.                                                                       */

@@ -133,6 +133,7 @@ assert POOL_DECODE_DTYPE.itemsize == 40
 # str_er_word_decode: per word, the cost of the cheapest string (-1: more than 32 runs, not decoded) and of the plain reading, the
 # characters of the string and the runs read, dropped and the characters inserted
 WORD_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
+LINE_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("n_chars", "<i4"), ("n_breaks", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
 assert WORD_DECODE_DTYPE.itemsize == 24
 # str_er_word_margin: per word, the extra cost of the cheapest path that reads some run differently from the decoded string, the
 # word-relative row where it does, the decoded reading of that row and the alternative (65: the row dropped); all -1: not decoded
@@ -464,6 +465,17 @@ def load_library():
     L.str_er_result_word_decode_chars.restype = vp
     L.str_er_result_word_decode_src.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.str_er_result_word_decode_src.restype = vp
+    L.str_er_set_line_decode.argtypes = [vp, C.c_int32, C.c_int32]
+    L.str_er_line_gap_costs.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.str_er_decode_lines.argtypes = [vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp]
+    L.str_er_decode_lines_host.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp]
+    L.str_er_line_decode_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_result_line_decodes.argtypes = [vp, i32p]
+    L.str_er_result_line_decodes.restype = vp
+    for fn in (L.str_er_result_line_decode_chars, L.str_er_result_line_decode_src, L.str_er_result_line_decode_word_of_row, L.str_er_result_line_gap_costs,
+               L.str_er_result_line_decode_windows):
+        fn.argtypes = [vp, C.POINTER(C.c_uint64)]
+        fn.restype = vp
     L.str_er_set_word_margin.argtypes = [vp, C.c_int32]
     L.str_er_word_margins.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
     L.str_er_word_margins_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
@@ -782,6 +794,11 @@ class Result:
             raise ValueError("the result has no word margins (ERFilter.set_word_margin(True) and WANT_WORD_DECODE / want_word_decode=True)")
         return table
 
+    def _line_decode_table(self, table):
+        if table is None:
+            raise ValueError("the result has no line decodes (ERFilter.set_line_decode(True) and WANT_WORD_DECODE / want_word_decode=True)")
+        return table
+
     def _run_split_table(self, table):
         if table is None:
             raise ValueError("the result has no run splits (pass WANT_RUN_SPLIT / want_run_split=True)")
@@ -1013,6 +1030,79 @@ class Result:
         if int(d["cost"]) < 0:
             return [(first + k, False) for k in range(int(self.words[w]["n_runs"]))]
         return [(first + (int(v) & 0x7F), bool(int(v) & 0x80)) for v in self.word_decode_src[w, :int(d["n_chars"])]]
+
+    @property
+    def line_decodes(self) -> np.ndarray:
+        """With set_line_decode(True) and WANT_WORD_DECODE: LINE_DECODE_DTYPE per line of texts, in the same order."""
+        return self._line_decode_table(getattr(self, "_line_decodes", None))
+
+    @property
+    def line_decode_chars(self) -> np.ndarray:
+        """With set_line_decode(True) and WANT_WORD_DECODE: (3 x n rows) uint8, the labels of every line's string (65: a blank) from entry
+        3 * first row of its window on, 0xFF past n_chars.  A row is a run of line_runs, with WANT_RUN_SPLIT a part of split_parts."""
+        return self._line_decode_table(getattr(self, "_line_decode_chars", None))
+
+    @property
+    def line_decode_src(self) -> np.ndarray:
+        """With set_line_decode(True) and WANT_WORD_DECODE: (3 x n rows) uint16, per label the line-relative row it came from, 0x8000 set
+        on an inserted character and 0x4000 on the break in front of that row; 0xFFFF past n_chars."""
+        return self._line_decode_table(getattr(self, "_line_decode_src", None))
+
+    @property
+    def line_decode_word_of_row(self) -> np.ndarray:
+        """With set_line_decode(True) and WANT_WORD_DECODE: int32 per row, the decoded word of its line it is read in, -1 for a dropped
+        row."""
+        return self._line_decode_table(getattr(self, "_line_decode_word_of_row", None))
+
+    @property
+    def line_gap_costs(self) -> np.ndarray:
+        """With set_line_decode(True) and WANT_WORD_DECODE: (n rows, 2) uint8, the (join, break) costs of the gap in front of every row."""
+        return self._line_decode_table(getattr(self, "_line_gap_costs", None))
+
+    @property
+    def line_decode_windows(self) -> np.ndarray:
+        """With set_line_decode(True) and WANT_WORD_DECODE: (n lines, 2) int32, the first row and the row count of every line."""
+        return self._line_decode_table(getattr(self, "_line_decode_windows", None))
+
+    def _line_decode_slice(self, t: int):
+        d, first = self.line_decodes[t], int(self.line_decode_windows[t, 0])
+        n = max(0, int(d["n_chars"]))
+        return d, first, self.line_decode_chars[3 * first:3 * first + n], self.line_decode_src[3 * first:3 * first + n]
+
+    def line_decode_text(self, t: int) -> str:
+        """With set_line_decode(True): the decoded string of line t, a blank per break (consecutive blanks are kept); for a line that
+        was not decoded (cost < 0) its words' decoded strings joined by one blank."""
+        d, first, lab, src = self._line_decode_slice(t)
+        if int(d["cost"]) < 0:
+            return " ".join(self.words_decode_text_of_line(t))
+        return "".join(" " if int(a) == 65 else _OCR_ALPHABET[int(a)] for a in lab)
+
+    def frame_line_line_decode_text(self, i: int) -> str:
+        """With set_line_decode(True): line_decode_text of the representative line of frame line i."""
+        return self.line_decode_text(int(self.frame_lines[i]["rep"]))
+
+    def line_decode_words(self, t: int) -> list:
+        """With set_line_decode(True): the words of line t under the decoded segmentation, empty ones included: per word (text,
+        (x, y, w, h) the bounding box of the runs of its rows that are read, None for a word without one)."""
+        d, first, lab, src = self._line_decode_slice(t)
+        if int(d["cost"]) < 0:
+            lw = self.line_words[t]
+            return [(self.word_decode_text(w), tuple(int(self.words[w][k]) for k in ("x", "y", "w", "h")))
+                    for w in range(int(lw["first_word"]), int(lw["first_word"]) + int(lw["n_words"]))]
+        texts, boxes = [""], [None]
+        for a, v in zip(lab, src):
+            if int(a) == 65:
+                texts.append(""); boxes.append(None)
+                continue
+            texts[-1] += _OCR_ALPHABET[int(a)]
+            if not int(v) & 0x8000:
+                row = first + (int(v) & 0x3FFF)          # (a run, or with WANT_RUN_SPLIT a part: its run's box)
+                parts = getattr(self, "_split_parts", None)
+                q = self.line_runs[row if parts is None else int(parts[row]["run"])]
+                b = boxes[-1]
+                x0, y0, x1, y1 = int(q["x0"]), int(q["y0"]), int(q["x1"]), int(q["y1"])
+                boxes[-1] = (x0, y0, x1, y1) if b is None else (min(b[0], x0), min(b[1], y0), max(b[2], x1), max(b[3], y1))
+        return [(s, None if b is None else (b[0], b[1], b[2] - b[0], b[3] - b[1])) for s, b in zip(texts, boxes)]
 
     @property
     def word_margins(self) -> np.ndarray:
@@ -1582,6 +1672,13 @@ class ERFilter:
                                     res._word_row_margins = table(L.str_er_result_word_row_margins, np.uint8, n64).view(np.int32).reshape(-1, 32)
                                     res._word_row_reads = table(L.str_er_result_word_row_reads, np.uint8, n64).reshape(-1, 32)
                                     res._word_row_alts = table(L.str_er_result_word_row_alts, np.uint8, n64).reshape(-1, 32)
+                                res._line_decodes = table(L.str_er_result_line_decodes, LINE_DECODE_DTYPE)
+                                if res._line_decodes is not None:
+                                    res._line_decode_chars = table(L.str_er_result_line_decode_chars, np.uint8, n64)
+                                    res._line_decode_src = table(L.str_er_result_line_decode_src, np.uint16, n64)
+                                    res._line_decode_word_of_row = table(L.str_er_result_line_decode_word_of_row, np.int32, n64)
+                                    res._line_gap_costs = table(L.str_er_result_line_gap_costs, np.uint8, n64).reshape(-1, 2)
+                                    res._line_decode_windows = table(L.str_er_result_line_decode_windows, np.int32, n64).reshape(-1, 2)
                             res._run_splits = table(L.str_er_result_run_splits, RUN_SPLIT_DTYPE)
                             if res._run_splits is not None:
                                 res._run_pieces = table(L.str_er_result_run_pieces, RUN_PIECE_DTYPE)
@@ -2167,6 +2264,26 @@ class ERFilter:
         """str_er_set_word_margin: whether a detect call with WANT_WORD_DECODE also makes the margins of its words (off by default)."""
         self._check(self.L.str_er_set_word_margin(self.h, 1 if on else 0))
 
+    def set_line_decode(self, on: bool = True, weight: int = 16) -> None:
+        """str_er_set_line_decode: whether a detect call with WANT_WORD_DECODE also decodes every line jointly with its word breaks
+        (str_er_line_decode; off by default), and the weight (0 .. 127) of the gap costs."""
+        self._check(self.L.str_er_set_line_decode(self.h, 1 if on else 0, int(weight)))
+
+    def decode_lines(self, costs: np.ndarray, gaps, first_row, n_rows):
+        """str_er_decode_lines: the lines [first_row[t], first_row[t] + n_rows[t]) of the cost rows (n, 65) uint8 with the gap costs
+        (n, 2) uint8 under the table and set_word_decode; (LINE_DECODE_DTYPE per line, (3n,) uint8 labels, (3n,) uint16 sources, (n,)
+        int32 word of every row)."""
+        cs, gp, fr, no, out, ch, sr, wr = _line_decode_args(costs, gaps, first_row, n_rows)
+        opt = lambda a: _np_ptr(a) if len(a) else None
+        self._check(self.L.str_er_decode_lines(self.h, opt(cs), len(cs), opt(gp), opt(fr), opt(no), len(fr), _np_ptr(out), _np_ptr(ch), _np_ptr(sr), _np_ptr(wr)))
+        return out[:len(fr)], ch[:3 * len(cs)], sr[:3 * len(cs)], wr[:len(cs)]
+
+    def line_decode_stats(self) -> dict:
+        """str_er_line_decode_stats: the bytes of the line decoder's back-pointer table on the device."""
+        by = C.c_uint64()
+        self._check(self.L.str_er_line_decode_stats(self.h, C.byref(by)))
+        return {"table_bytes": int(by.value)}
+
     def word_margins(self, costs: np.ndarray, first_run, n_runs_of_word, want_marginals: bool = False):
         """str_er_word_margins: the margins (str_er_word_margin) of the words [first_run[w], first_run[w] + n_runs_of_word[w]) of the
         cost rows (n runs, 65) uint8 under the table and set_word_decode; (WORD_MARGIN_DTYPE per word, (n, 32) int32 row margins,
@@ -2638,6 +2755,54 @@ def _decode_args(costs, first_run, n_runs_of_word):
         raise ValueError("first_run and n_runs_of_word: one value per word each")
     n = max(1, len(fr))
     return cs, fr, no, np.zeros(n, WORD_DECODE_DTYPE), np.full((n, 64), 0xFF, np.uint8), np.full((n, 64), 0xFF, np.uint8)
+
+
+def _line_decode_args(costs, gaps, first_row, n_rows):
+    cs = np.ascontiguousarray(costs, dtype=np.uint8).reshape(-1, 65)
+    gp = np.ascontiguousarray(gaps, dtype=np.uint8).reshape(-1, 2)
+    fr = np.ascontiguousarray(first_row, dtype=np.int32).reshape(-1)
+    no = np.ascontiguousarray(n_rows, dtype=np.int32).reshape(-1)
+    if len(fr) != len(no):
+        raise ValueError("first_row and n_rows: one value per line each")
+    if len(gp) != len(cs):
+        raise ValueError("gaps: one (join, break) pair per cost row")
+    n = max(1, len(cs))
+    return (cs, gp, fr, no, np.zeros(max(1, len(fr)), LINE_DECODE_DTYPE), np.full(3 * n, 0xFF, np.uint8), np.full(3 * n, 0xFFFF, np.uint16),
+            np.full(n, -1, np.int32))
+
+
+def decode_lines_host(costs: np.ndarray, gaps, first_row, n_rows, table, ins: int = 0, dele: int = 0):
+    """str_er_decode_lines_host (pure host, one thread): ERFilter.decode_lines with the table and the parameters as arguments."""
+    cs, gp, fr, no, out, ch, sr, wr = _line_decode_args(costs, gaps, first_row, n_rows)
+    opt = lambda a: _np_ptr(a) if len(a) else None
+    rc = load_library().str_er_decode_lines_host(opt(cs), len(cs), opt(gp), opt(fr), opt(no), len(fr), _np_ptr(_bigram_table(table)), int(ins), int(dele),
+                                                 _np_ptr(out), _np_ptr(ch), _np_ptr(sr), _np_ptr(wr))
+    if rc != 0:
+        raise StrErError(rc, "str_er_decode_lines_host")
+    return out[:len(fr)], ch[:3 * len(cs)], sr[:3 * len(cs)], wr[:len(cs)]
+
+
+def line_gap_costs(runs, first_row, n_rows_of_line, colmax, num: int = 1, den: int = 3, weight: int = 16, row_run=None, n_rows=None) -> np.ndarray:
+    """str_er_line_gap_costs (pure host): the (join, break) costs of str_er_line_decode from the geometry, (n_rows, 2) uint8.  Line t has
+    the rows [first_row[t], first_row[t] + n_rows_of_line[t]) and the colmax colmax[t]; row r is the run row_run[r] of runs
+    (LINE_RUN_DTYPE; x0 and x1 are read), or run r where row_run is None; n_rows: the rows there are (default: one per run, or per
+    entry of row_run)."""
+    rs = np.ascontiguousarray(runs, dtype=LINE_RUN_DTYPE).reshape(-1)
+    fr = np.ascontiguousarray(first_row, dtype=np.int32).reshape(-1)
+    no = np.ascontiguousarray(n_rows_of_line, dtype=np.int32).reshape(-1)
+    cm = np.ascontiguousarray(colmax, dtype=np.uint32).reshape(-1)
+    rr = None if row_run is None else np.ascontiguousarray(row_run, dtype=np.int32).reshape(-1)
+    if not len(fr) == len(no) == len(cm):
+        raise ValueError("first_row, n_rows_of_line and colmax: one value per line each")
+    n = int(n_rows) if n_rows is not None else len(rs) if rr is None else len(rr)
+    if rr is not None and len(rr) != n:
+        raise ValueError("row_run: one run per row")
+    out = np.zeros((max(1, n), 2), np.uint8)
+    opt = lambda a: _np_ptr(a) if a is not None and len(a) else None
+    rc = load_library().str_er_line_gap_costs(opt(rs), len(rs), opt(rr), n, opt(fr), opt(no), opt(cm), len(fr), int(num), int(den), int(weight), _np_ptr(out))
+    if rc != 0:
+        raise StrErError(rc, "str_er_line_gap_costs")
+    return out[:n]
 
 
 def _margin_args(costs, first_run, n_runs_of_word, want_marginals):
@@ -3770,6 +3935,14 @@ class FrameStream:
         for i in range(int(self.L.str_er_stream_depth(self.h))):
             ctx = self.L.str_er_stream_context(self.h, i)
             rc = self.L.str_er_set_word_margin(ctx, 1 if on else 0)
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
+    def set_line_decode(self, on: bool = True, weight: int = 16) -> None:
+        """str_er_set_line_decode on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_line_decode(ctx, 1 if on else 0, int(weight))
             if rc != 0:
                 raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
 

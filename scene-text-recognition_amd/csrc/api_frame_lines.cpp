@@ -720,6 +720,11 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         if (decode) { out.decodes = &r->word_decodes; out.decode_chars = &r->word_decode_chars; out.decode_src = &r->word_decode_src; }
         const bool margin = decode && c->wd_margin;          // (a context setting, str_er_set_word_margin: no flag of its own)
         if (margin) { out.margins = &r->word_margins; out.row_margins = &r->word_row_margins; out.row_reads = &r->word_row_reads; out.row_alts = &r->word_row_alts; }
+        const bool ldecode = decode && c->ln_on;          // (a context setting, str_er_set_line_decode: no flag of its own)
+        if (ldecode) {
+            out.line_decodes = &r->line_decodes; out.line_chars = &r->line_decode_chars; out.line_src = &r->line_decode_src; out.line_word_of_row = &r->line_decode_word_of_row;
+            out.line_gaps = &r->line_gap_costs; out.line_windows = &r->line_decode_windows; out.n_lines = n_lines; out.line_bee = c->bigram_ee;
+        }
         std::vector<uint8_t> piece_q;          // (the pieces' features are not part of the result)
         const RunPieces rp{&r->run_pieces, &r->piece_reads, &piece_q};
         if (split) {          // (the cut records of the compacted runs: down with the stage's wait)
@@ -785,6 +790,7 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         r->have_word_matches = match;
         r->have_word_decodes = decode;
         r->have_word_margins = margin;
+        r->have_line_decodes = ldecode;
     }
     if (c->dbg_stats)        // developer aid (tools/dev_line_words.py)
         std::fprintf(stderr, "[str_er] line words: %zu lines, %zu run slots reserved, %zu runs, %zu words, %zu bytes back, host %.3f ms\n", n_lines,

@@ -22,6 +22,9 @@
 //   lattice track decode  what the lattice decode read, with its records and labels where it left them and the track decode's tracks; iff both run and the context's setting
 //   lattice margins  what the lattice decode read, with its records, labels, sources and parts where it left them; iff the lattice decode and the context's setting
 //   margins          the same window as the decoder, with the decoder's records, labels and sources where it left them; iff decode and the context's setting
+//   line decode      the decoder's rows, every line one window from the first row of its first word to the last of its last, with the gap costs the host makes from the runs; iff decode
+//                    and the context's setting.  With split the rows are the parts' rows of U (A's where U is A), which lie at the words' slots and whose number only the device
+//                    knows: the line decode is then enqueued behind the stage's wait, once the parts are down, with the cost row of every part, and has a wait of its own
 //
 //   result table     source
 //   run_costs        A if match, else U
@@ -29,8 +32,9 @@
 //   run_probs        present iff match or decode
 //
 // The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, wg_tab, rs_tab, ld_tab, lg_tab, lm_tab,
-// lt_tab, tm_tab, td_tab and ltd_tab hold what their kernels leave.
+// lt_tab, tm_tab, td_tab, ltd_tab and ln_tab hold what their kernels leave.
 #include "str_er_ctx.h"
+#include "line_decode_rules.h"
 #include "lattice_decode_kernels.h"
 #include "lattice_match_kernels.h"
 #include "run_split_kernels.h"
@@ -59,6 +63,11 @@ void ReadChainOut::preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k
         lattice_track_decode_src->assign(32 * track_members->size(), 0xFF); lattice_track_decode_parts->clear();
     }
     if (p.split) { piece_costs->assign(65 * n_pc, 0); parts->clear(); word_splits->assign(n_words, str_er_word_split{0, 0, 0, 0}); }
+    if (p.ldecode) {          // (a line without rows is the empty line: B[E][E])
+        const size_t lr = p.split ? 0 : n_run;          // (with split the rows are the parts: sized once they are known)
+        line_decodes->assign(n_lines, str_er_line_decode{line_bee, 0, 0, 0, 0, 0}); line_chars->assign(3 * lr, 0xFF); line_src->assign(3 * lr, 0xFFFF);
+        line_word_of_row->assign(lr, -1); line_gaps->assign(2 * lr, 0); line_windows->assign(2 * n_lines, 0);
+    }
     if (p.lattice) {
         lattice_decodes->assign(n_words, str_er_lattice_decode{}); lattice_chars->assign(64 * n_words, 0xFF); lattice_src->assign(64 * n_words, 0xFF);
         lattice_parts->clear();
@@ -117,6 +126,8 @@ struct ReadCall {
     RunTab   TH{}, TD{};
     OcrBuf   buf{};
     uint8_t *rows[2] = {nullptr, nullptr}, *parts[2] = {nullptr, nullptr};
+    LnTab    NH{}, ND{};
+    const std::vector<str_er_line_words> *lines_of = nullptr; const std::vector<str_er_line_run> *runs_of = nullptr;      // (geometry keeps them for the line decode)
     RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; WgTab GM{}; LgTab LG{}; TmTab KD{}; TdTab EH{}, ED{}; LtdTab QH{}, QD{};
 
     // phase 1 (host alone): the tiles and rotations of the runs and pieces, every box checked, and their places in the atlas
@@ -124,6 +135,7 @@ struct ReadCall {
                  const RunPieces *pieces)
     {
         if (n > 0x7FFFFFFFull / 1800) return fail(c, STR_ER_ECAPACITY, "run read: too many glyph runs");
+        lines_of = &line_words; runs_of = &runs;
         tiles.resize(n); rot.resize(n);
         std::vector<int32_t> line_of(n_pc ? n_run : 0);
         const auto           tile = [&](size_t i, const FootLine &L, int32_t x0, int32_t x1, int32_t y0, int32_t y1, double slope) {
@@ -216,6 +228,7 @@ struct ReadCall {
             (p.lmargin && (rc = c->lg_tab.ensure(c, lg_layout(nullptr, 0, n_words, false, false).bytes, "lattice margin tables")) != STR_ER_OK) ||
             (p.lmatch && (rc = c->lm_tab.ensure(c, lm_layout(nullptr, 0, n_words, (size_t)n_slots, n_chunks).bytes, "lattice match tables")) != STR_ER_OK))
             return rc;
+        if (p.ldecode && !p.split && (rc = line_windows()) != STR_ER_OK) return rc;
         if (p.match) WD = wm_layout(c->wm_tab.d(), 0, n_words, n_chunks);
         if (p.decode) DD = wd_layout(c->wd_tab.d(), 0, n_words);
         if (p.margin) GM = wg_layout(c->wg_tab.d(), 0, n_words, false);
@@ -223,6 +236,86 @@ struct ReadCall {
         if (p.lattice) { LH = ld_layout(c->ld_tab.h(), 0, n_words, (size_t)n_slots); LD = ld_layout(c->ld_tab.d(), 0, n_words, (size_t)n_slots); }
         if (p.lmargin) LG = lg_layout(c->lg_tab.d(), 0, n_words, false, false);
         if (p.lmatch) { MH = lm_layout(c->lm_tab.h(), 0, n_words, (size_t)n_slots, n_chunks); MD = lm_layout(c->lm_tab.d(), 0, n_words, (size_t)n_slots, n_chunks); }
+        return STR_ER_OK;
+    }
+
+    // the line decode's windows and gap costs, where the word windows are made: a line runs from the first row of its first word to
+    // the last row of its last word -- the words of a line lie back to back and cover its runs -- and a gap costs what the runs say
+    int line_windows()
+    {
+        const std::vector<str_er_line_words> &LW = *lines_of;
+        std::vector<int32_t> &win = *o.line_windows;
+        std::vector<uint32_t> colmax(LW.size());
+        std::vector<int32_t>  first(LW.size()), n_of(LW.size());
+        for (size_t t = 0; t < LW.size(); ++t) {
+            int64_t at = LW[t].first_run;
+            if (LW[t].n_words < 0 || (size_t)LW[t].first_word + (size_t)LW[t].n_words > n_words) return fail(c, STR_ER_EHIP, "line decode: a line's words outside the words (internal error)");
+            for (int32_t k = 0; k < LW[t].n_words; ++k) {
+                const str_er_line_word &W = (*o.words)[(size_t)LW[t].first_word + (size_t)k];
+                if (W.first_run != at) return fail(c, STR_ER_EHIP, "line decode: the words of a line do not lie back to back (internal error)");
+                at += W.n_runs;
+            }
+            if (at != (int64_t)LW[t].first_run + LW[t].n_runs) return fail(c, STR_ER_EHIP, "line decode: the words of a line do not cover its runs (internal error)");
+            first[t] = win[2 * t] = LW[t].first_run; n_of[t] = win[2 * t + 1] = LW[t].n_runs; colmax[t] = LW[t].colmax;
+        }
+        if (!str_er_ld::lines_in_rows((int64_t)n_run, first.data(), n_of.data(), (int64_t)LW.size()) ||
+            !str_er_ld::gap_costs(runs_of->data(), (int64_t)n_run, nullptr, (int64_t)n_run, first.data(), n_of.data(), colmax.data(), (int64_t)LW.size(), c->word_num, c->word_den,
+                                  c->ln_weight, o.line_gaps->data()))
+            return fail(c, STR_ER_EHIP, "line decode: a line outside the glyph runs (internal error)");
+        return STR_ER_OK;
+    }
+
+    // the line decode's launch on n_lrows rows of `from` (row_map, null: row r is cost row r) with the windows and gap costs of o, and
+    // its tables back after the wait
+    int line_enqueue(const uint8_t *from, size_t n_lrows, const int32_t *row_map)
+    {
+        const std::vector<int32_t> &win = *o.line_windows;
+        std::vector<int32_t>        first(win.size() / 2), n_of(win.size() / 2);
+        for (size_t t = 0; t < first.size(); ++t) { first[t] = win[2 * t]; n_of[t] = win[2 * t + 1]; }
+        return line_decode_enqueue(c, s, 0, from, n_lrows, o.line_gaps->data(), first.data(), n_of.data(), nullptr, nullptr, first.size(), row_map, NH, ND);
+    }
+    void line_collect(size_t n_lrows)
+    {
+        std::memcpy(o.line_decodes->data(), NH.dec, sizeof(str_er_line_decode) * o.line_decodes->size());
+        if (n_lrows == 0) return;
+        std::memcpy(o.line_chars->data(), NH.chars, 3 * n_lrows); std::memcpy(o.line_src->data(), NH.src, 2 * 3 * n_lrows);
+        std::memcpy(o.line_word_of_row->data(), NH.word_of_row, 4 * n_lrows);
+    }
+
+    // With split, behind the stage's wait: the rows of a line are the parts of its words in word order (the compacted part table of the
+    // call), part k of word w has the cost row slot[w] + k of the decoder's part rows, and rows of one run get no blank between them.
+    // One more upload, launch, copy back and wait.
+    int line_pass_split()
+    {
+        const std::vector<str_er_line_words> &LW = *lines_of;
+        const size_t          n_lrows = o.parts->size();
+        std::vector<int32_t> &win = *o.line_windows;
+        std::vector<uint32_t> colmax(LW.size());
+        std::vector<int32_t>  first(LW.size()), n_of(LW.size()), row_run(n_lrows), row_map(n_lrows);
+        int64_t               at = 0;
+        for (size_t t = 0; t < LW.size(); ++t) {
+            if (LW[t].n_words < 0 || (size_t)LW[t].first_word + (size_t)LW[t].n_words > n_words) return fail(c, STR_ER_EHIP, "line decode: a line's words outside the words (internal error)");
+            const int64_t begin = at;
+            for (int32_t k = 0; k < LW[t].n_words; ++k) {
+                const size_t             w = (size_t)LW[t].first_word + (size_t)k;
+                const str_er_word_split &W = (*o.word_splits)[w];
+                if (W.first_part != at || W.n_parts < 0 || (size_t)at + (size_t)W.n_parts > n_lrows)
+                    return fail(c, STR_ER_EHIP, "line decode: the parts of a line's words do not lie back to back (internal error)");
+                for (int32_t j = 0; j < W.n_parts; ++j) { row_map[(size_t)at + (size_t)j] = slot[w] + j; row_run[(size_t)at + (size_t)j] = (*o.parts)[(size_t)at + (size_t)j].run; }
+                at += W.n_parts;
+            }
+            first[t] = win[2 * t] = (int32_t)begin; n_of[t] = win[2 * t + 1] = (int32_t)(at - begin); colmax[t] = LW[t].colmax;
+        }
+        o.line_chars->assign(3 * n_lrows, 0xFF); o.line_src->assign(3 * n_lrows, 0xFFFF); o.line_word_of_row->assign(n_lrows, -1); o.line_gaps->assign(2 * n_lrows, 0);
+        if (!str_er_ld::gap_costs(runs_of->data(), (int64_t)n_run, row_run.data(), (int64_t)n_lrows, first.data(), n_of.data(), colmax.data(), (int64_t)LW.size(), c->word_num,
+                                  c->word_den, c->ln_weight, o.line_gaps->data()))
+            return fail(c, STR_ER_EHIP, "line decode: a part outside the glyph runs (internal error)");
+        if (LW.empty()) return STR_ER_OK;
+        if (const int rc = line_enqueue(parts[p.decode_set], n_lrows, row_map.data()); rc != STR_ER_OK) return rc;
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(c->ln_tab.h() + NH.o_dec, c->ln_tab.d() + NH.o_dec, NH.down_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(c, wait_stream(c, s));
+        line_collect(n_lrows);
         return STR_ER_OK;
     }
 
@@ -277,6 +370,8 @@ struct ReadCall {
             if (p.margin)          // the decoder's window, its records, labels and sources where it left them
                 launch_word_margin(s, c->bigram.d(), c->wd_ins, c->wd_del, W.rows, W.first, W.n, (int)n_words, DD.dec, DD.chars, DD.src, GM.margins, GM.row_margin, GM.row_read,
                                    GM.row_alt, nullptr);
+            if (p.ldecode && !p.split)          // the runs' rows of the decoder's set, a window a line
+                if (const int rc = line_enqueue(rows[p.decode_set], n_run, nullptr); rc != STR_ER_OK) return rc;
             if (p.tdecode && !tfirst.empty())          // the decoder's window, its records and labels where it left them
                 if (const int rc = track_decode_enqueue(c, s, 0, W.rows, W.first, W.n, DD.dec, DD.chars, tfirst.data(), tcount.data(), o.track_members->data(),
                                                         o.track_members->size(), tfirst.size(), EH, ED);
@@ -333,6 +428,8 @@ struct ReadCall {
             HIP_TRY(c, down(o.row_alts->data(), GM.row_alt, 32 * n_words));
         }
         if (p.tdecode && !tfirst.empty()) HIP_TRY(c, down(c->td_tab.h() + EH.o_out, c->td_tab.d() + EH.o_out, EH.down_bytes));
+        const bool ld_ran = p.ldecode && !p.split && !o.line_decodes->empty();
+        if (ld_ran) HIP_TRY(c, down(c->ln_tab.h() + NH.o_dec, c->ln_tab.d() + NH.o_dec, NH.down_bytes));
         if (p.split && n_words > 0) HIP_TRY(c, down(c->rs_tab.h() + SH.o_out, c->rs_tab.d() + SH.o_out, SH.down_tables));          // (into page-locked memory: compacted below)
         if (p.lmargin && n_words > 0) {
             HIP_TRY(c, down(o.lattice_margins->data(), LG.margins, sizeof(str_er_lattice_margin) * n_words));
@@ -348,6 +445,7 @@ struct ReadCall {
         const bool ltd_ran = p.ltdecode && !tfirst.empty() && n_words > 0;
         if (ltd_ran) HIP_TRY(c, down(c->ltd_tab.h() + QH.o_out, c->ltd_tab.d() + QH.o_out, QH.down_bytes));
         HIP_TRY(c, wait_stream(c, s));
+        if (ld_ran) line_collect(n_run);
         if (ltd_ran) {          // the member records with their first parts, the parts compacted, the records, labels and sources as they are
             uint64_t total = 0;
             if (!ltd_compact(QH, qslot, n_qslots, nullptr, nullptr, &total)) return fail(c, STR_ER_EHIP, "lattice track decode: a member's parts outside its slots (internal error)");
@@ -392,6 +490,8 @@ struct ReadCall {
             rs_compact(SH, slot, n_slots, o.word_splits->data(), o.parts->data(), nullptr, &total);
             for (const str_er_split_part &P : *o.parts)
                 if (P.run >= 0 && (size_t)P.run < n_run) ++(*o.splits)[(size_t)P.run].n_parts;
+            if (p.ldecode)
+                if (const int rc = line_pass_split(); rc != STR_ER_OK) return rc;
         }
         for (size_t i = 0; reads && i < n_run; ++i) (*reads)[i] = str_er_run_read{label[i], str_er_ocr_char(label[i]), prob[i]};
         for (size_t i = 0; reads && pieces && pieces->reads && i < n_pc; ++i)
@@ -412,7 +512,7 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     const size_t              n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0;
     const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.track_matches != nullptr, c->lex.fold != 0,
                                    o.lattice_matches != nullptr, o.lattice_track_matches != nullptr, o.track_decodes != nullptr, o.margins != nullptr, o.lattice_margins != nullptr,
-                                   o.lattice_track_decodes != nullptr);
+                                   o.lattice_track_decodes != nullptr, o.line_decodes != nullptr);
     if (reads) reads->assign(n_run, str_er_run_read{});
     q.assign(1800 * n_run, 0);
     if (pieces) {

@@ -52,6 +52,7 @@ try {
     HIP_TRY(c, hipMemcpy(fresh.d(), cost, wd::TABLE, hipMemcpyHostToDevice));
     c->bigram = std::move(fresh);
     c->bigram_set = true;
+    c->bigram_ee = cost[wd::E * wd::STATES + wd::E];
     return STR_ER_OK;
 } ABI_GUARD(c)
 

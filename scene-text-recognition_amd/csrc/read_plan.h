@@ -28,11 +28,12 @@ struct ReadPlan {
     bool margin;           // the decoder's margins (str_er_set_word_margin): only with decode; the decoder's window, records, labels and sources
     bool lmargin;          // the lattice decoder's margins (str_er_set_lattice_margin): only with lattice; the decoder's window, records, labels, sources and parts
     bool ltdecode;         // the track decode over the members' lattices (str_er_set_lattice_track_decode): only with tdecode and lattice; it reads lattice_set, the lattice decoder's records and labels
+    bool ldecode;          // the line decode (str_er_set_line_decode): only with decode; it reads the runs' rows of decode_set, every line one window
     bool any() const { return match || decode || split; }      // some consumer reads the words and the class probabilities
 };
 
 inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, bool track, bool fold, bool lmatch = false, bool ltrack = false, bool tdecode = false,
-                          bool margin = false, bool lmargin = false, bool ltdecode = false)
+                          bool margin = false, bool lmargin = false, bool ltdecode = false, bool ldecode = false)
 {
     ReadPlan p{};
     p.match = match; p.decode = decode; p.split = split; p.lattice = lattice && split; p.track = track && match;
@@ -55,6 +56,7 @@ inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, boo
     p.margin = margin && p.decode;
     p.lmargin = lmargin && p.lattice;
     p.ltdecode = ltdecode && p.tdecode && p.lattice;
+    p.ldecode = ldecode && p.decode;
     return p;
 }
 

@@ -28,6 +28,7 @@
 #include "track_match_kernels.h"
 #include "word_decode_kernels.h"
 #include "word_margin_kernels.h"
+#include "line_decode_kernels.h"
 #include "lattice_margin_kernels.h"
 #include "er_group.h"
 #include "flood_order.h"
@@ -210,6 +211,12 @@ struct str_er_result {
     std::vector<str_er_split_part> lattice_track_decode_parts;
     bool have_lattice_track_decodes = false;
     double times[7] = {0, 0, 0, 0, 0, 0, 0};
+    std::vector<str_er_line_decode> line_decodes; // str_er_set_line_decode beside STR_ER_WANT_WORD_DECODE: per line of texts; 3 labels and 3 sources per run of line_runs, a word
+    std::vector<uint8_t> line_decode_chars;       // per run, the gap costs used (2 bytes per run) and the lines' windows into the runs (first row, row count)
+    std::vector<uint16_t> line_decode_src;
+    std::vector<int32_t> line_decode_word_of_row, line_decode_windows;
+    std::vector<uint8_t> line_gap_costs;
+    bool have_line_decodes = false;
 };
 
 // A table of a result, as the str_er_result_* accessors hand it out: null (and *n = 0) when its stage did not run, and when it ran but made no
@@ -423,6 +430,12 @@ struct str_er_ctx {
     // pool_gen's sibling: what a decode pool is bound to (the bigram table, the decoder's INS / DEL, the track decode's INS / DEL / rounds)
     // has this generation; their setters bump it.  It stands here, behind everything else, so that no member a detect call touches moves.
     uint64_t decode_pool_gen = 0;
+    // str_er_set_line_decode / str_er_decode_lines (behind everything else for the same reason)
+    bool     ln_on = false;           // a detect call with STR_ER_WANT_WORD_DECODE also decodes every line
+    int32_t  ln_weight = 16;          // the weight of its gap costs
+    PairBuf  ln_tab;                  // (str_er_decode_lines: cost rows | first row, row count per line) | gap costs | records | labels | sources | word of every row
+    DevBuf   ln_bp;                   // the back pointers of k_line_decode: 68 uint16 per row, scratch
+    int32_t  bigram_ee = 0;           // B[E][E] of the table that is set: what a line without rows costs
 };
 
 namespace {
@@ -737,6 +750,11 @@ struct ReadChainOut {
     // str_er_set_lattice_track_decode (with the track decode and the lattice decode): the word tracks decoded over their members' piece lattices
     std::vector<str_er_track_decode> *lattice_track_decodes = nullptr; std::vector<uint8_t> *lattice_track_decode_chars = nullptr, *lattice_track_decode_src = nullptr;
     std::vector<str_er_lattice_track_member> *lattice_track_decode_members = nullptr; std::vector<str_er_split_part> *lattice_track_decode_parts = nullptr;
+    // str_er_set_line_decode (with decode): every line decoded jointly with its word breaks, behind the decoder on the runs' rows of its set
+    // (line_bee: B[E][E], the cost of a line without rows)
+    std::vector<str_er_line_decode> *line_decodes = nullptr; std::vector<uint8_t> *line_chars = nullptr, *line_gaps = nullptr;
+    std::vector<uint16_t> *line_src = nullptr; std::vector<int32_t> *line_word_of_row = nullptr, *line_windows = nullptr;
+    size_t n_lines = 0; int32_t line_bee = 0;
     void preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k) const;      // every table of the plan as a call without runs leaves it (k: the model's classes)
 };
 // carving a table buffer: take(bytes) is the offset of the next piece, and the one after it starts at the next multiple of 256
@@ -883,6 +901,20 @@ struct WdTab {
     size_t o_dec, down_bytes, bytes;      // dec | chars | src lie back to back (each aligned): one copy down
 };
 WdTab wd_layout(uint8_t *base, size_t at, size_t n_words);
+// ---- defined in api_line_decode.cpp
+// the layout of c->ln_tab from byte `at` on (the inputs' bytes) for n_lines lines over n_rows rows: what goes up (the gap costs, and with
+// windows the lines' first row and row count) and what k_line_decode leaves, all of which comes down
+struct LnTab {
+    uint8_t *gaps; int32_t *first, *n_of, *row_map; str_er_line_decode *dec; uint8_t *chars; uint16_t *src; int32_t *word_of_row;
+    size_t o_up, up_bytes;                // gaps | first | n_of | row_map lie back to back: one copy up
+    size_t o_dec, down_bytes, bytes;      // dec | chars | src | word_of_row lie back to back (each aligned): one copy down
+};
+LnTab ln_layout(uint8_t *base, size_t at, size_t n_rows, size_t n_lines, bool windows, bool map);
+// k_line_decode behind what is on s: the gap costs (and with first / n_of the windows, else d_first / d_n_of are on the device already;
+// with row_map the cost row of every row, else row r is cost row r) into c->ln_tab from byte `at` on and up, the back-pointer table sized, the outputs preset for the rows of no line, the launch; H and D
+// receive the two sides of the layout (what comes down: H.o_dec, H.down_bytes)
+int line_decode_enqueue(str_er_ctx *c, hipStream_t s, size_t at, const uint8_t *d_rows, size_t n_rows, const uint8_t *gaps, const int32_t *first, const int32_t *n_of,
+                        const int32_t *d_first, const int32_t *d_n_of, size_t n_lines, const int32_t *row_map, LnTab &H, LnTab &D);
 // ---- defined in api_lattice_margin.cpp
 // the layout of what k_lattice_margin leaves in c->lg_tab from byte `at` on (the inputs' bytes), all of which comes down
 struct LgTab {

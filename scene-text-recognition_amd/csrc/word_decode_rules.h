@@ -53,6 +53,49 @@ inline int32_t read_cost(const uint8_t *C, int m, const uint8_t *B)
 // state the inserted character follows
 struct Step { uint8_t sub_pred, del, ins, ins_pred; };
 
+// One run of the recurrence: V_{i-1} in V becomes V_i under the row's 65 bytes, and st[0 .. 65] records the moves (the line decoder,
+// line_decode_rules.h, takes the same step between its gaps)
+inline void run_step(int32_t V[STATES], const uint8_t *row, const uint8_t *B, int32_t ins, int32_t del, Step *st)
+{
+    int32_t U[STATES];
+    for (int b = 0; b < ALPHABET; ++b) {
+        int32_t best = V[0] + B[b];
+        int     pred = 0;
+        for (int a = 1; a < STATES; ++a) {
+            const int32_t v = V[a] + B[a * STATES + b];
+            if (v < best) { best = v; pred = a; }
+        }
+        U[b] = best + row[b];
+        st[b] = Step{(uint8_t)pred, 0, 0, 0};
+    }
+    U[E] = INF;
+    st[E] = Step{0, 0, 0, 0};
+    if (del > 0)
+        for (int a = 0; a < STATES; ++a)
+            if (V[a] + del < U[a]) { U[a] = V[a] + del; st[a].del = 1; }
+    for (int c = 0; c < STATES; ++c) V[c] = U[c];
+    if (ins > 0)
+        for (int c = 0; c < ALPHABET; ++c) {
+            int32_t best = U[0] + B[c];
+            int     pred = 0;
+            for (int b = 1; b < ALPHABET; ++b) {
+                const int32_t v = U[b] + B[b * STATES + c];
+                if (v < best) { best = v; pred = b; }
+            }
+            if (best + ins < U[c]) { V[c] = best + ins; st[c].ins = 1; st[c].ins_pred = (uint8_t)pred; }
+        }
+}
+
+// the end of a string: min over a of V[a] + B[a][E] with the smallest a, which is the state the backtrack starts from
+inline int32_t end_cost(const int32_t V[STATES], const uint8_t *B, int *state)
+{
+    int32_t cost = V[0] + B[E];
+    *state = 0;
+    for (int a = 1; a < STATES; ++a)
+        if (V[a] + B[a * STATES + E] < cost) { cost = V[a] + B[a * STATES + E]; *state = a; }
+    return cost;
+}
+
 // One word: the m cost rows C (65 bytes each, back to back) under B with the moves INS and DEL (0: off).  chars / src receive 64 bytes
 // each, padded with 0xFF.
 inline str_er_word_decode decode_word(const uint8_t *C, int m, const uint8_t *B, int32_t ins, int32_t del, uint8_t *chars, uint8_t *src)
@@ -64,43 +107,12 @@ inline str_er_word_decode decode_word(const uint8_t *C, int m, const uint8_t *B,
     if (m > MAX_RUNS) { r.cost = -1; return r; }
     static_assert(sizeof(Step) == 4, "step");
     Step    steps[MAX_RUNS][STATES];
-    int32_t V[STATES], U[STATES];
+    int32_t V[STATES];
     for (int a = 0; a < ALPHABET; ++a) V[a] = INF;
     V[E] = 0;
-    for (int i = 1; i <= m; ++i) {
-        const uint8_t *row = C + (size_t)(i - 1) * ALPHABET;
-        Step          *st = steps[i - 1];
-        for (int b = 0; b < ALPHABET; ++b) {
-            int32_t best = V[0] + B[b];
-            int     pred = 0;
-            for (int a = 1; a < STATES; ++a) {
-                const int32_t v = V[a] + B[a * STATES + b];
-                if (v < best) { best = v; pred = a; }
-            }
-            U[b] = best + row[b];
-            st[b] = Step{(uint8_t)pred, 0, 0, 0};
-        }
-        U[E] = INF;
-        st[E] = Step{0, 0, 0, 0};
-        if (del > 0)
-            for (int a = 0; a < STATES; ++a)
-                if (V[a] + del < U[a]) { U[a] = V[a] + del; st[a].del = 1; }
-        for (int c = 0; c < STATES; ++c) V[c] = U[c];
-        if (ins > 0)
-            for (int c = 0; c < ALPHABET; ++c) {
-                int32_t best = U[0] + B[c];
-                int     pred = 0;
-                for (int b = 1; b < ALPHABET; ++b) {
-                    const int32_t v = U[b] + B[b * STATES + c];
-                    if (v < best) { best = v; pred = b; }
-                }
-                if (best + ins < U[c]) { V[c] = best + ins; st[c].ins = 1; st[c].ins_pred = (uint8_t)pred; }
-            }
-    }
+    for (int i = 1; i <= m; ++i) run_step(V, C + (size_t)(i - 1) * ALPHABET, B, ins, del, steps[i - 1]);
     int state = 0;
-    r.cost = V[0] + B[E];
-    for (int a = 1; a < STATES; ++a)
-        if (V[a] + B[a * STATES + E] < r.cost) { r.cost = V[a] + B[a * STATES + E]; state = a; }
+    r.cost = end_cost(V, B, &state);
     // the backtrack writes the string from its end
     uint8_t lab[MAX_CHARS], from[MAX_CHARS];
     int     at = MAX_CHARS;
