@@ -820,8 +820,9 @@ typedef struct str_er_word_margin {
  *     tie at the old threshold, and w = 0 leaves the decision to the table alone.  Rows of the same run (the parts of
  *     STR_ER_WANT_RUN_SPLIT) get (0, 255): a cut inside a run is never a blank.  The first row of a line, and a row of no line, gets
  *     (0, 255) as well.
- *   Limits: one path per line, no margins.  The segmentation of the runs themselves is the fixed one of the decoder's window: joint
- *     decoding over the piece lattice is not part of this.  No tracks, no pool.  Nothing is calibrated: the weight is the caller's.
+ *   Limits: one path per line, no margins in this record: how firmly its readings and breaks hold is str_er_line_margin's to say.
+ *     The segmentation of the runs themselves is the fixed one of the decoder's window: joint decoding over the piece lattice is not
+ *     part of this.  No tracks, no pool.  Nothing is calibrated: the weight is the caller's.
  *   In a detect call the rows are the decoder's: the runs of the line, and with STR_ER_WANT_RUN_SPLIT the parts of its words in word
  *     order (the rows of str_er_result_split_parts(); the windows then index that table, and the line is decoded behind a second wait,
  *     once the parts are known).  A line's window runs from the first row of its first word to the last row of its last word.       */
@@ -830,6 +831,57 @@ typedef struct str_er_line_decode {
     int32_t  n_breaks, n_sub;             /*  8, 12                                   */
     int32_t  n_del, n_ins;                /* 16, 20                                   */
 } str_er_line_decode;        /* 24 bytes; one per line of str_er_result_texts()       */
+
+/* The margins of a decoded line (str_er_set_line_margin beside str_er_set_line_decode, str_er_line_margins): the min-marginals of the
+ * recurrence of str_er_line_decode -- for every row and every reading of it, and for every gap and either move at it, the cost of the
+ * cheapest whole path that does just that -- and from them how much more the cheapest path costs that reads some row differently or
+ * decides some gap differently from the decoded string.  A definition of this library; integers only, exact, and the host states the
+ * same rules (str_er_line_margins_host).
+ *   Symbols, B, E = 65, INS, DEL, INF = 2^20, the cost rows C_i, the gap pairs (J_i, K_i) with 255 = off and the forward values are
+ *     those of str_er_line_decode.  Take a line with the rows 1 .. n, 1 <= n <= 1024.
+ *   Forward values: V_{i-1} is the state vector before gap i, W_i the one behind the gap step (W_1 = V_0);
+ *     X_i = min over a of (V_{i-1}[a] + B[a][E]) + K_i where K_i is on; S_i[b] = min over a in 0 .. 65 of (W_i[a] + B[a][b]) + C_i[b]
+ *     for b < 65, the SUB value before DEL is compared.
+ *   Backward values, in int32: G_n[a] = B[a][E] for a in 0 .. 65.  For i = n .. 1, in this order: GU_i = G_i; if INS > 0, for b < 65:
+ *     GU_i[b] = min(G_i[b], min over c < 65 of (B[b][c] + G_i[c]) + INS).  H_i[a] = min over b < 65 of (B[a][b] + C_i[b] + GU_i[b]),
+ *     and if DEL > 0 also min-ed with DEL + GU_i[a].  For i >= 2: G_{i-1}[a] = the smaller of J_i + H_i[a] (if J_i is on) and
+ *     B[a][E] + K_i + H_i[E] (if K_i is on).  For i = 1: G_0 = H_1, and G_0[E] = cost.
+ *   Row marginals, 66 per row: M_i[b] = S_i[b] + GU_i[b] for b < 65, row i read as b; M_i[65] = min over a of (W_i[a] + DEL + GU_i[a])
+ *     if DEL > 0, else none: row i dropped.
+ *   Gap marginals, 2 per row i >= 2: the join MJ_i = min over a of (V_{i-1}[a] + J_i + H_i[a]) if J_i is on; the break
+ *     MK_i = X_i + H_i[E] if K_i is on.
+ *   A value >= INF means "no path" and is reported as -1.  Every marginal that exists is at most 1 043 202, the bound of
+ *     str_er_line_decode, and every unreachable forward value is >= INF.  Every path does exactly one thing at a row and one at a gap:
+ *     the minimum over the entries of M_i that exist is cost, and so is the minimum of MJ_i and MK_i over those that exist.
+ *   Readings: x_i is the label of the character of the decoded string whose source is exactly i-1 (no flag bit), or 65 if there is
+ *     none; d_i = 1 if the string has the source (i-1) | 0x4000, else 0.  M_i[x_i] = cost, and the marginal of the move d_i at gap i is
+ *     cost.
+ *   Margins: row_margin_i = min over x != x_i with M_i[x] >= 0 of M_i[x] - cost, >= 0; alt_i is the smallest x that attains it.  For
+ *     i >= 2, gap_margin_i = (the marginal of the move 1 - d_i) - cost if that move is on, else -1: no alternative.  The first row of a
+ *     line has no gap: its gap_margin is -1 and its gap_move 0xFF.
+ *   Record: read_margin, row, read, alt: the smallest row margin, at the smallest line-relative row.  gap_margin, gap, gap_move: the
+ *     smallest gap margin that exists, at the smallest line-relative row i-1, with d of that gap; all three -1 if no gap has an
+ *     alternative.  margin: the smaller of read_margin and gap_margin where both exist, else read_margin.  All eight fields are -1 for
+ *     n = 0 and for n > 1024 (not decoded).
+ *   Per row, indexed like word_of_row (the row of the line's window, not the cost row behind a row map): row_margin (int32, -1 where
+ *     nothing is written), row_read and row_alt (uint8, 0xFF), gap_margin (int32, -1), gap_move (uint8: 0 join, 1 break, 0xFF).  On
+ *     request, from str_er_line_margins only: the marginals, 68 int32 per row: [0 .. 64] the row read as b, [65] dropped, [66] the join
+ *     and [67] the break in front of it; -1 where there is none.
+ *   It follows: (1) with (0, off) at every gap and n <= 32, row_margin, row_read, row_alt and the marginals [0 .. 65] equal
+ *     str_er_word_margin's on the same rows, and every gap_margin is -1.  (2) With (0, off) inside the words of a segmentation and
+ *     (off, 0) at its word gaps, every word of <= 32 rows: the row outputs of a row equal the word margin's row outputs of its word,
+ *     and its marginals are the word's plus the other words' costs.  (3) For a gap whose margin g >= 0: the same line decoded again
+ *     with only the decided move of that gap set to 255 costs exactly cost + g.  So, all else fixed, the decision flips exactly when
+ *     the byte of the decided move rises by more than g.
+ *   Limits: an inserted character has no row, so it has no margin of its own, and paths that differ only in insertions are not told
+ *     apart.  One gap or one row is varied at a time.  This covers the line decoder only: no lattice, no tracks, no pool.  Nothing is
+ *     calibrated: a margin is a cost difference in the unit of the cost rows and the gap bytes, not a probability.                  */
+typedef struct str_er_line_margin {
+    int32_t  margin, read_margin;         /*  0,  4                                   */
+    int32_t  row, read;                   /*  8, 12                                   */
+    int32_t  alt, gap_margin;             /* 16, 20                                   */
+    int32_t  gap, gap_move;               /* 24, 28                                   */
+} str_er_line_margin;        /* 32 bytes; one per line of str_er_result_texts()       */
 
 /* The decoding of a word track without a lexicon (STR_ER_WANT_TRACK_DECODE, str_er_decode_tracks): one string for all members of a
  * word track of str_er_word_link, a median string of the members under their cost rows and the bigram table, reached from the members'
@@ -1576,6 +1628,24 @@ int str_er_decode_lines_host(const uint8_t *costs, int32_t n_rows, const uint8_t
                              const uint8_t *bigram, int32_t ins, int32_t del, str_er_line_decode *dec, uint8_t *chars, uint16_t *src, int32_t *word_of_row);
 /* The bytes of the line decoder's back-pointer table on the device (68 uint16 per row of the largest call so far; 0 before the first).  */
 int str_er_line_decode_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
+/* Whether a detect call that decodes its lines (STR_ER_WANT_WORD_DECODE on a context whose str_er_set_line_decode is on) also makes
+ * their margins (str_er_line_margin): on != 0 switches it on; off by default.  A context setting, not a stage flag: without the line
+ * decode it does nothing, and while it is off no call enqueues or allocates anything more than before.  A stream's contexts:
+ * str_er_stream_context.                                                                                                          */
+int str_er_set_line_margin(str_er_ctx *ctx, int32_t on);
+/* The line decoder and its margins (str_er_line_margin) on the caller's cost rows, on the GPU, in one enqueue with one wait: the
+ * arguments, checks and error codes of str_er_decode_lines.  margins receives n_lines records; row_margin and gap_margin n_rows int32,
+ * row_read, row_alt and gap_move n_rows bytes; marginals (NULL: not wanted) 68 * n_rows int32.  What lies in no line is -1 / 0xFF.
+ * STR_ER_ECAPACITY where the forward table of the rows would pass 2^31 bytes.                                                     */
+int str_er_line_margins(str_er_ctx *ctx, const uint8_t *costs, int32_t n_rows, const uint8_t *gaps, const int32_t *first_row, const int32_t *n_rows_of_line,
+                        int32_t n_lines, str_er_line_margin *margins, int32_t *row_margin, uint8_t *row_read, uint8_t *row_alt, int32_t *gap_margin,
+                        uint8_t *gap_move, int32_t *marginals);
+/* The same rules on one host thread, with the table and INS / DEL as arguments.  Pure: no context, no GPU.                          */
+int str_er_line_margins_host(const uint8_t *costs, int32_t n_rows, const uint8_t *gaps, const int32_t *first_row, const int32_t *n_rows_of_line, int32_t n_lines,
+                             const uint8_t *bigram, int32_t ins, int32_t del, str_er_line_margin *margins, int32_t *row_margin, uint8_t *row_read,
+                             uint8_t *row_alt, int32_t *gap_margin, uint8_t *gap_move, int32_t *marginals);
+/* The bytes of the margins' forward table on the device (136 uint32 per row of the largest call so far; 0 before the first).          */
+int str_er_line_margin_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
 /* INS and DEL (1 .. 255) and the number of polish rounds (0 .. 64) of str_er_track_decode; defaults 64, 64 and 8.  Anything else ->
  * STR_ER_EINVAL, the context unchanged.  A stream's contexts: str_er_stream_context.                                               */
 int str_er_set_track_decode(str_er_ctx *ctx, int32_t ins, int32_t del, int32_t rounds);
@@ -2082,6 +2152,16 @@ const uint16_t           *str_er_result_line_decode_src(const str_er_result *r, 
 const int32_t            *str_er_result_line_decode_word_of_row(const str_er_result *r, uint64_t *n);
 const uint8_t            *str_er_result_line_gap_costs(const str_er_result *r, uint64_t *n_bytes);
 const int32_t            *str_er_result_line_decode_windows(const str_er_result *r, uint64_t *n);
+/* With the line decode on a context whose str_er_set_line_margin is on (str_er_line_margin): one record per line of
+ * str_er_result_texts(), and per row of the line decode's rows a row margin and a gap margin (int32, n_bytes: their bytes), a reading,
+ * an alternative and a gap move (one byte each).  Each returns NULL and 0 when the call made none; a call without lines returns empty
+ * arrays (not NULL).                                                                                                              */
+const str_er_line_margin *str_er_result_line_margins(const str_er_result *r, int32_t *n);
+const int32_t            *str_er_result_line_row_margins(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t            *str_er_result_line_row_reads(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t            *str_er_result_line_row_alts(const str_er_result *r, uint64_t *n_bytes);
+const int32_t            *str_er_result_line_gap_margins(const str_er_result *r, uint64_t *n_bytes);
+const uint8_t            *str_er_result_line_gap_moves(const str_er_result *r, uint64_t *n_bytes);
 /* With STR_ER_WANT_RUN_SPLIT (str_er_run_split): one split record per run of str_er_result_line_runs(); the pieces they index, with
  * one reading and one 65-byte cost row per piece; the parts of the words back to back in word order; one record per word of
  * str_er_result_words().  NULL (and *n = 0) without the flag.                                                                       */

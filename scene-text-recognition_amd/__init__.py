@@ -20,7 +20,7 @@ from .binding import (  # noqa: F401
     WANT_WORD_MATCH, LEXICON_FOLD_CASE, WORD_MATCH_DTYPE, cost_thresholds, prob_costs, match_words_host,
     WANT_WORD_DECODE, WORD_DECODE_DTYPE, bigram_from_probs, bigram_from_words, load_tp_table, decode_words_host,
     WORD_MARGIN_DTYPE, word_margins_host,
-    LINE_DECODE_DTYPE, line_gap_costs, decode_lines_host,
+    LINE_DECODE_DTYPE, line_gap_costs, decode_lines_host, LINE_MARGIN_DTYPE, line_margins_host,
     WANT_RUN_SPLIT, RUN_SPLIT_DTYPE, RUN_PIECE_DTYPE, SPLIT_PART_DTYPE, WORD_SPLIT_DTYPE, cuts_from_counts, split_words_host,
     WANT_LATTICE_DECODE, LATTICE_DECODE_DTYPE, lattice_decode_words_host,
     LATTICE_MARGIN_DTYPE, lattice_margins_host,

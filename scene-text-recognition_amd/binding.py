@@ -134,7 +134,13 @@ assert POOL_DECODE_DTYPE.itemsize == 40
 # characters of the string and the runs read, dropped and the characters inserted
 WORD_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
 LINE_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("n_chars", "<i4"), ("n_breaks", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4")])
-assert WORD_DECODE_DTYPE.itemsize == 24
+assert WORD_DECODE_DTYPE.itemsize == 24 and LINE_DECODE_DTYPE.itemsize == 24
+# str_er_line_margin: per line, the smaller of its smallest row margin and its smallest gap margin; the smallest row margin, the
+# line-relative row, its decoded reading and the alternative (65: the row dropped); the smallest gap margin, the line-relative row the
+# gap lies in front of and its decided move (0 join, 1 break), all three -1 where no gap has an alternative; all -1: not decoded
+LINE_MARGIN_DTYPE = np.dtype([("margin", "<i4"), ("read_margin", "<i4"), ("row", "<i4"), ("read", "<i4"), ("alt", "<i4"), ("gap_margin", "<i4"), ("gap", "<i4"),
+                              ("gap_move", "<i4")])
+assert LINE_MARGIN_DTYPE.itemsize == 32
 # str_er_word_margin: per word, the extra cost of the cheapest path that reads some run differently from the decoded string, the
 # word-relative row where it does, the decoded reading of that row and the alternative (65: the row dropped); all -1: not decoded
 WORD_MARGIN_DTYPE = np.dtype([("margin", "<i4"), ("row", "<i4"), ("read", "<i4"), ("alt", "<i4")])
@@ -476,6 +482,16 @@ def load_library():
                L.str_er_result_line_decode_windows):
         fn.argtypes = [vp, C.POINTER(C.c_uint64)]
         fn.restype = vp
+    L.str_er_set_line_margin.argtypes = [vp, C.c_int32]
+    L.str_er_line_margins.argtypes = [vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+    L.str_er_line_margins_host.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+    L.str_er_line_margin_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_result_line_margins.argtypes = [vp, i32p]
+    L.str_er_result_line_margins.restype = vp
+    for fn in (L.str_er_result_line_row_margins, L.str_er_result_line_row_reads, L.str_er_result_line_row_alts, L.str_er_result_line_gap_margins,
+               L.str_er_result_line_gap_moves):
+        fn.argtypes = [vp, C.POINTER(C.c_uint64)]
+        fn.restype = vp
     L.str_er_set_word_margin.argtypes = [vp, C.c_int32]
     L.str_er_word_margins.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
     L.str_er_word_margins_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp]
@@ -799,6 +815,11 @@ class Result:
             raise ValueError("the result has no line decodes (ERFilter.set_line_decode(True) and WANT_WORD_DECODE / want_word_decode=True)")
         return table
 
+    def _line_margin_table(self, table):
+        if table is None:
+            raise ValueError("the result has no line margins (ERFilter.set_line_margin(True) beside set_line_decode(True) and WANT_WORD_DECODE)")
+        return table
+
     def _run_split_table(self, table):
         if table is None:
             raise ValueError("the result has no run splits (pass WANT_RUN_SPLIT / want_run_split=True)")
@@ -1063,6 +1084,52 @@ class Result:
     def line_decode_windows(self) -> np.ndarray:
         """With set_line_decode(True) and WANT_WORD_DECODE: (n lines, 2) int32, the first row and the row count of every line."""
         return self._line_decode_table(getattr(self, "_line_decode_windows", None))
+
+    @property
+    def line_margins(self) -> np.ndarray:
+        """With set_line_margin(True) beside the line decode: LINE_MARGIN_DTYPE per line of texts, in the same order."""
+        return self._line_margin_table(getattr(self, "_line_margins", None))
+
+    @property
+    def line_row_margins(self) -> np.ndarray:
+        """With set_line_margin(True): int32 per row of the line decode's rows, how much more the cheapest path costs that reads the row
+        differently; -1 for a row of a line that was not decoded."""
+        return self._line_margin_table(getattr(self, "_line_row_margins", None))
+
+    @property
+    def line_row_reads(self) -> np.ndarray:
+        """With set_line_margin(True): uint8 per row, the label the decoded string reads it as (65: dropped), 0xFF where there is none."""
+        return self._line_margin_table(getattr(self, "_line_row_reads", None))
+
+    @property
+    def line_row_alts(self) -> np.ndarray:
+        """With set_line_margin(True): uint8 per row, the reading of the cheapest path that reads it differently (65: dropped)."""
+        return self._line_margin_table(getattr(self, "_line_row_alts", None))
+
+    @property
+    def line_gap_margins(self) -> np.ndarray:
+        """With set_line_margin(True): int32 per row, how much more the cheapest path costs that takes the other move at the gap in
+        front of it; -1 for the first row of a line and where the other move is off."""
+        return self._line_margin_table(getattr(self, "_line_gap_margins", None))
+
+    @property
+    def line_gap_moves(self) -> np.ndarray:
+        """With set_line_margin(True): uint8 per row, the decided move of the gap in front of it: 0 join, 1 break, 0xFF for the first
+        row of a line."""
+        return self._line_margin_table(getattr(self, "_line_gap_moves", None))
+
+    def line_decode_margin(self, t: int) -> int:
+        """With set_line_margin(True): the margin of line t (the smaller of its smallest row margin and its smallest gap margin), -1
+        for a line without rows or one that was not decoded."""
+        return int(self.line_margins[t]["margin"])
+
+    def line_break_margins(self, t: int) -> list:
+        """With set_line_margin(True): per gap of line t (line-relative row it lies in front of, move: 0 join / 1 break, margin: -1
+        where the other move is off)."""
+        first, n = (int(v) for v in self.line_decode_windows[t])
+        if int(self.line_margins[t]["margin"]) < 0:
+            return []
+        return [(k, int(self.line_gap_moves[first + k]), int(self.line_gap_margins[first + k])) for k in range(1, n)]
 
     def _line_decode_slice(self, t: int):
         d, first = self.line_decodes[t], int(self.line_decode_windows[t, 0])
@@ -1679,6 +1746,13 @@ class ERFilter:
                                     res._line_decode_word_of_row = table(L.str_er_result_line_decode_word_of_row, np.int32, n64)
                                     res._line_gap_costs = table(L.str_er_result_line_gap_costs, np.uint8, n64).reshape(-1, 2)
                                     res._line_decode_windows = table(L.str_er_result_line_decode_windows, np.int32, n64).reshape(-1, 2)
+                                    res._line_margins = table(L.str_er_result_line_margins, LINE_MARGIN_DTYPE)
+                                    if res._line_margins is not None:
+                                        res._line_row_margins = table(L.str_er_result_line_row_margins, np.uint8, n64).view(np.int32)
+                                        res._line_row_reads = table(L.str_er_result_line_row_reads, np.uint8, n64)
+                                        res._line_row_alts = table(L.str_er_result_line_row_alts, np.uint8, n64)
+                                        res._line_gap_margins = table(L.str_er_result_line_gap_margins, np.uint8, n64).view(np.int32)
+                                        res._line_gap_moves = table(L.str_er_result_line_gap_moves, np.uint8, n64)
                             res._run_splits = table(L.str_er_result_run_splits, RUN_SPLIT_DTYPE)
                             if res._run_splits is not None:
                                 res._run_pieces = table(L.str_er_result_run_pieces, RUN_PIECE_DTYPE)
@@ -2278,6 +2352,27 @@ class ERFilter:
         self._check(self.L.str_er_decode_lines(self.h, opt(cs), len(cs), opt(gp), opt(fr), opt(no), len(fr), _np_ptr(out), _np_ptr(ch), _np_ptr(sr), _np_ptr(wr)))
         return out[:len(fr)], ch[:3 * len(cs)], sr[:3 * len(cs)], wr[:len(cs)]
 
+    def set_line_margin(self, on: bool = True) -> None:
+        """str_er_set_line_margin: whether a detect call that decodes its lines (set_line_decode(True) and WANT_WORD_DECODE) also makes
+        their margins (str_er_line_margin; off by default)."""
+        self._check(self.L.str_er_set_line_margin(self.h, 1 if on else 0))
+
+    def line_margins(self, costs: np.ndarray, gaps, first_row, n_rows, want_marginals: bool = False):
+        """str_er_line_margins: the margins (str_er_line_margin) of the lines decode_lines takes, under the table and set_word_decode;
+        (LINE_MARGIN_DTYPE per line, (n,) int32 row margins, (n,) uint8 row readings, (n,) uint8 row alternatives, (n,) int32 gap
+        margins, (n,) uint8 gap moves[, (n, 68) int32 marginals])."""
+        cs, gp, fr, no, out, rm, rr, ra, gm, gv, mg = _line_margin_args(costs, gaps, first_row, n_rows, want_marginals)
+        opt = lambda a: _np_ptr(a) if len(a) else None
+        self._check(self.L.str_er_line_margins(self.h, opt(cs), len(cs), opt(gp), opt(fr), opt(no), len(fr), _np_ptr(out), _np_ptr(rm), _np_ptr(rr), _np_ptr(ra),
+                                               _np_ptr(gm), _np_ptr(gv), _np_ptr(mg) if want_marginals else None))
+        return _line_margin_out(len(cs), len(fr), out, rm, rr, ra, gm, gv, mg, want_marginals)
+
+    def line_margin_stats(self) -> dict:
+        """str_er_line_margin_stats: the bytes of the margins' forward table on the device."""
+        by = C.c_uint64()
+        self._check(self.L.str_er_line_margin_stats(self.h, C.byref(by)))
+        return {"table_bytes": int(by.value)}
+
     def line_decode_stats(self) -> dict:
         """str_er_line_decode_stats: the bytes of the line decoder's back-pointer table on the device."""
         by = C.c_uint64()
@@ -2769,6 +2864,29 @@ def _line_decode_args(costs, gaps, first_row, n_rows):
     n = max(1, len(cs))
     return (cs, gp, fr, no, np.zeros(max(1, len(fr)), LINE_DECODE_DTYPE), np.full(3 * n, 0xFF, np.uint8), np.full(3 * n, 0xFFFF, np.uint16),
             np.full(n, -1, np.int32))
+
+
+def _line_margin_args(costs, gaps, first_row, n_rows, want_marginals):
+    cs, gp, fr, no = _line_decode_args(costs, gaps, first_row, n_rows)[:4]
+    n = max(1, len(cs))
+    return (cs, gp, fr, no, np.full(max(1, len(fr)), -1, LINE_MARGIN_DTYPE), np.full(n, -1, np.int32), np.full(n, 0xFF, np.uint8), np.full(n, 0xFF, np.uint8),
+            np.full(n, -1, np.int32), np.full(n, 0xFF, np.uint8), np.full((n if want_marginals else 1, 68), -1, np.int32))
+
+
+def _line_margin_out(n, n_lines, out, rm, rr, ra, gm, gv, mg, want_marginals):
+    res = (out[:n_lines], rm[:n], rr[:n], ra[:n], gm[:n], gv[:n])
+    return res + (mg[:n],) if want_marginals else res
+
+
+def line_margins_host(costs: np.ndarray, gaps, first_row, n_rows, table, ins: int = 0, dele: int = 0, want_marginals: bool = False):
+    """str_er_line_margins_host (pure host, one thread): ERFilter.line_margins with the table and the parameters as arguments."""
+    cs, gp, fr, no, out, rm, rr, ra, gm, gv, mg = _line_margin_args(costs, gaps, first_row, n_rows, want_marginals)
+    opt = lambda a: _np_ptr(a) if len(a) else None
+    rc = load_library().str_er_line_margins_host(opt(cs), len(cs), opt(gp), opt(fr), opt(no), len(fr), _np_ptr(_bigram_table(table)), int(ins), int(dele),
+                                                 _np_ptr(out), _np_ptr(rm), _np_ptr(rr), _np_ptr(ra), _np_ptr(gm), _np_ptr(gv), _np_ptr(mg) if want_marginals else None)
+    if rc != 0:
+        raise StrErError(rc, "str_er_line_margins_host")
+    return _line_margin_out(len(cs), len(fr), out, rm, rr, ra, gm, gv, mg, want_marginals)
 
 
 def decode_lines_host(costs: np.ndarray, gaps, first_row, n_rows, table, ins: int = 0, dele: int = 0):
@@ -3943,6 +4061,14 @@ class FrameStream:
         for i in range(int(self.L.str_er_stream_depth(self.h))):
             ctx = self.L.str_er_stream_context(self.h, i)
             rc = self.L.str_er_set_line_decode(ctx, 1 if on else 0, int(weight))
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
+    def set_line_margin(self, on: bool = True) -> None:
+        """str_er_set_line_margin on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_line_margin(ctx, 1 if on else 0)
             if rc != 0:
                 raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
 

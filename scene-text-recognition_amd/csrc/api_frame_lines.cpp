@@ -725,6 +725,11 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
             out.line_decodes = &r->line_decodes; out.line_chars = &r->line_decode_chars; out.line_src = &r->line_decode_src; out.line_word_of_row = &r->line_decode_word_of_row;
             out.line_gaps = &r->line_gap_costs; out.line_windows = &r->line_decode_windows; out.n_lines = n_lines; out.line_bee = c->bigram_ee;
         }
+        const bool lnmargin = ldecode && c->ln_margin;          // (a context setting, str_er_set_line_margin: no flag of its own)
+        if (lnmargin) {
+            out.line_margins = &r->line_margins; out.line_row_margins = &r->line_row_margins; out.line_row_reads = &r->line_row_reads; out.line_row_alts = &r->line_row_alts;
+            out.line_gap_margins = &r->line_gap_margins; out.line_gap_moves = &r->line_gap_moves;
+        }
         std::vector<uint8_t> piece_q;          // (the pieces' features are not part of the result)
         const RunPieces rp{&r->run_pieces, &r->piece_reads, &piece_q};
         if (split) {          // (the cut records of the compacted runs: down with the stage's wait)
@@ -791,6 +796,7 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         r->have_word_decodes = decode;
         r->have_word_margins = margin;
         r->have_line_decodes = ldecode;
+        r->have_line_margins = lnmargin;
     }
     if (c->dbg_stats)        // developer aid (tools/dev_line_words.py)
         std::fprintf(stderr, "[str_er] line words: %zu lines, %zu run slots reserved, %zu runs, %zu words, %zu bytes back, host %.3f ms\n", n_lines,

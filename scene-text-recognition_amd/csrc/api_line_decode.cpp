@@ -13,7 +13,7 @@ static_assert(ld::MAX_ROWS == 1024 && LD_BP_ROW >= wd::STATES + 1, "the kernel's
 
 namespace str_er_host {
 
-LnTab ln_layout(uint8_t *base, size_t at, size_t n_rows, size_t n_lines, bool windows, bool map)
+LnTab ln_layout(uint8_t *base, size_t at, size_t n_rows, size_t n_lines, bool windows, bool map, bool margin, bool marginals)
 {
     LnTab t{};
     Carve cv{at};
@@ -23,6 +23,10 @@ LnTab ln_layout(uint8_t *base, size_t at, size_t n_rows, size_t n_lines, bool wi
     t.up_bytes = cv.off - t.o_up;
     t.o_dec = cv.take(sizeof(str_er_line_decode) * n_lines);
     const size_t o_chars = cv.take(ld::PER_ROW * n_rows), o_src = cv.take(2 * ld::PER_ROW * n_rows), o_wor = cv.take(4 * n_rows);
+    // (behind the labels: all of it is preset with bytes of 0xFF, which read -1 in the margins' tables too)
+    const size_t o_lm = cv.take(margin ? sizeof(str_er_line_margin) * n_lines : 0), o_rm = cv.take(margin ? 4 * n_rows : 0), o_gm = cv.take(margin ? 4 * n_rows : 0),
+                 o_rr = cv.take(margin ? n_rows : 0), o_ra = cv.take(margin ? n_rows : 0), o_gv = cv.take(margin ? n_rows : 0),
+                 o_mg = cv.take(margin && marginals ? 4 * (size_t)LM_MARGINALS * n_rows : 0);
     t.bytes = cv.off;
     t.down_bytes = cv.off - t.o_dec;
     if (base) {
@@ -30,17 +34,26 @@ LnTab ln_layout(uint8_t *base, size_t at, size_t n_rows, size_t n_lines, bool wi
         t.row_map = map ? reinterpret_cast<int32_t *>(base + o_map) : nullptr;
         t.dec = reinterpret_cast<str_er_line_decode *>(base + t.o_dec); t.chars = base + o_chars; t.src = reinterpret_cast<uint16_t *>(base + o_src);
         t.word_of_row = reinterpret_cast<int32_t *>(base + o_wor);
+        if (margin) {
+            t.margins = reinterpret_cast<str_er_line_margin *>(base + o_lm); t.row_margin = reinterpret_cast<int32_t *>(base + o_rm);
+            t.gap_margin = reinterpret_cast<int32_t *>(base + o_gm); t.row_read = base + o_rr; t.row_alt = base + o_ra; t.gap_move = base + o_gv;
+            t.marginals = marginals ? reinterpret_cast<int32_t *>(base + o_mg) : nullptr;
+        }
     }
     return t;
 }
 
 int line_decode_enqueue(str_er_ctx *c, hipStream_t s, size_t at, const uint8_t *d_rows, size_t n_rows, const uint8_t *gaps, const int32_t *first, const int32_t *n_of,
-                        const int32_t *d_first, const int32_t *d_n_of, size_t n_lines, const int32_t *row_map, LnTab &H, LnTab &D)
+                        const int32_t *d_first, const int32_t *d_n_of, size_t n_lines, const int32_t *row_map, LnTab &H, LnTab &D, bool margin, bool marginals)
 {
     const bool windows = first != nullptr, map = row_map != nullptr;
-    if (const int rc = c->ln_tab.ensure(c, ln_layout(nullptr, at, n_rows, n_lines, windows, map).bytes, "line decode tables"); rc != STR_ER_OK) return rc;
+    if (const int rc = c->ln_tab.ensure(c, ln_layout(nullptr, at, n_rows, n_lines, windows, map, margin, marginals).bytes, "line decode tables"); rc != STR_ER_OK) return rc;
     if (const int rc = c->ln_bp.ensure(c, 2 * (size_t)LD_BP_ROW * n_rows, "line decode back pointers"); rc != STR_ER_OK) return rc;
-    H = ln_layout(c->ln_tab.h(), at, n_rows, n_lines, windows, map); D = ln_layout(c->ln_tab.d(), at, n_rows, n_lines, windows, map);
+    if (margin) {
+        if ((uint64_t)n_rows > 0x7FFFFFFFull / (4 * LM_FW_ROW)) return fail(c, STR_ER_ECAPACITY, "line margins: too many rows");
+        if (const int rc = c->ln_fw.ensure(c, 4 * (size_t)LM_FW_ROW * n_rows, "line margin forward values"); rc != STR_ER_OK) return rc;
+    }
+    H = ln_layout(c->ln_tab.h(), at, n_rows, n_lines, windows, map, margin, marginals); D = ln_layout(c->ln_tab.d(), at, n_rows, n_lines, windows, map, margin, marginals);
     if (n_rows > 0) std::memcpy(H.gaps, gaps, 2 * n_rows);
     if (map && n_rows > 0) std::memcpy(H.row_map, row_map, 4 * n_rows);
     if (windows && n_lines > 0) { std::memcpy(H.first, first, 4 * n_lines); std::memcpy(H.n_of, n_of, 4 * n_lines); }
@@ -49,6 +62,9 @@ int line_decode_enqueue(str_er_ctx *c, hipStream_t s, size_t at, const uint8_t *
     if (n_rows > 0) HIP_TRY(c, hipMemsetAsync(D.chars, 0xFF, (size_t)(c->ln_tab.d() + D.bytes - D.chars), s));
     launch_line_decode(s, c->bigram.d(), c->wd_ins, c->wd_del, d_rows, D.gaps, windows ? D.first : d_first, windows ? D.n_of : d_n_of, D.row_map, (int)n_lines, c->ln_bp.d<uint16_t>(),
                        D.dec, D.chars, D.src, D.word_of_row);
+    if (margin)          // the decoder's rows, gaps and windows, its records, labels and sources where it left them
+        launch_line_margin(s, c->bigram.d(), c->wd_ins, c->wd_del, d_rows, D.gaps, windows ? D.first : d_first, windows ? D.n_of : d_n_of, D.row_map, (int)n_lines, D.dec, D.chars,
+                           D.src, c->ln_fw.d<uint32_t>(), D.margins, D.row_margin, D.row_read, D.row_alt, D.gap_margin, D.gap_move, D.marginals);
     return STR_ER_OK;
 }
 

@@ -68,6 +68,11 @@ void ReadChainOut::preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k
         line_decodes->assign(n_lines, str_er_line_decode{line_bee, 0, 0, 0, 0, 0}); line_chars->assign(3 * lr, 0xFF); line_src->assign(3 * lr, 0xFFFF);
         line_word_of_row->assign(lr, -1); line_gaps->assign(2 * lr, 0); line_windows->assign(2 * n_lines, 0);
     }
+    if (p.lnmargin) {          // (a line without rows has no margin)
+        const size_t lr = p.split ? 0 : n_run;
+        line_margins->assign(n_lines, str_er_line_margin{-1, -1, -1, -1, -1, -1, -1, -1}); line_row_margins->assign(lr, -1); line_gap_margins->assign(lr, -1);
+        line_row_reads->assign(lr, 0xFF); line_row_alts->assign(lr, 0xFF); line_gap_moves->assign(lr, 0xFF);
+    }
     if (p.lattice) {
         lattice_decodes->assign(n_words, str_er_lattice_decode{}); lattice_chars->assign(64 * n_words, 0xFF); lattice_src->assign(64 * n_words, 0xFF);
         lattice_parts->clear();
@@ -272,14 +277,20 @@ struct ReadCall {
         const std::vector<int32_t> &win = *o.line_windows;
         std::vector<int32_t>        first(win.size() / 2), n_of(win.size() / 2);
         for (size_t t = 0; t < first.size(); ++t) { first[t] = win[2 * t]; n_of[t] = win[2 * t + 1]; }
-        return line_decode_enqueue(c, s, 0, from, n_lrows, o.line_gaps->data(), first.data(), n_of.data(), nullptr, nullptr, first.size(), row_map, NH, ND);
+        return line_decode_enqueue(c, s, 0, from, n_lrows, o.line_gaps->data(), first.data(), n_of.data(), nullptr, nullptr, first.size(), row_map, NH, ND, p.lnmargin, false);
     }
     void line_collect(size_t n_lrows)
     {
         std::memcpy(o.line_decodes->data(), NH.dec, sizeof(str_er_line_decode) * o.line_decodes->size());
+        if (p.lnmargin) std::memcpy(o.line_margins->data(), NH.margins, sizeof(str_er_line_margin) * o.line_margins->size());
         if (n_lrows == 0) return;
         std::memcpy(o.line_chars->data(), NH.chars, 3 * n_lrows); std::memcpy(o.line_src->data(), NH.src, 2 * 3 * n_lrows);
         std::memcpy(o.line_word_of_row->data(), NH.word_of_row, 4 * n_lrows);
+        if (p.lnmargin) {
+            std::memcpy(o.line_row_margins->data(), NH.row_margin, 4 * n_lrows); std::memcpy(o.line_gap_margins->data(), NH.gap_margin, 4 * n_lrows);
+            std::memcpy(o.line_row_reads->data(), NH.row_read, n_lrows); std::memcpy(o.line_row_alts->data(), NH.row_alt, n_lrows);
+            std::memcpy(o.line_gap_moves->data(), NH.gap_move, n_lrows);
+        }
     }
 
     // With split, behind the stage's wait: the rows of a line are the parts of its words in word order (the compacted part table of the
@@ -307,6 +318,10 @@ struct ReadCall {
             first[t] = win[2 * t] = (int32_t)begin; n_of[t] = win[2 * t + 1] = (int32_t)(at - begin); colmax[t] = LW[t].colmax;
         }
         o.line_chars->assign(3 * n_lrows, 0xFF); o.line_src->assign(3 * n_lrows, 0xFFFF); o.line_word_of_row->assign(n_lrows, -1); o.line_gaps->assign(2 * n_lrows, 0);
+        if (p.lnmargin) {
+            o.line_row_margins->assign(n_lrows, -1); o.line_gap_margins->assign(n_lrows, -1);
+            o.line_row_reads->assign(n_lrows, 0xFF); o.line_row_alts->assign(n_lrows, 0xFF); o.line_gap_moves->assign(n_lrows, 0xFF);
+        }
         if (!str_er_ld::gap_costs(runs_of->data(), (int64_t)n_run, row_run.data(), (int64_t)n_lrows, first.data(), n_of.data(), colmax.data(), (int64_t)LW.size(), c->word_num,
                                   c->word_den, c->ln_weight, o.line_gaps->data()))
             return fail(c, STR_ER_EHIP, "line decode: a part outside the glyph runs (internal error)");
@@ -370,7 +385,7 @@ struct ReadCall {
             if (p.margin)          // the decoder's window, its records, labels and sources where it left them
                 launch_word_margin(s, c->bigram.d(), c->wd_ins, c->wd_del, W.rows, W.first, W.n, (int)n_words, DD.dec, DD.chars, DD.src, GM.margins, GM.row_margin, GM.row_read,
                                    GM.row_alt, nullptr);
-            if (p.ldecode && !p.split)          // the runs' rows of the decoder's set, a window a line
+            if (p.ldecode && !p.split)          // the runs' rows of the decoder's set, a window a line (and with lnmargin k_line_margin behind it)
                 if (const int rc = line_enqueue(rows[p.decode_set], n_run, nullptr); rc != STR_ER_OK) return rc;
             if (p.tdecode && !tfirst.empty())          // the decoder's window, its records and labels where it left them
                 if (const int rc = track_decode_enqueue(c, s, 0, W.rows, W.first, W.n, DD.dec, DD.chars, tfirst.data(), tcount.data(), o.track_members->data(),
@@ -512,7 +527,7 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     const size_t              n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0;
     const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.track_matches != nullptr, c->lex.fold != 0,
                                    o.lattice_matches != nullptr, o.lattice_track_matches != nullptr, o.track_decodes != nullptr, o.margins != nullptr, o.lattice_margins != nullptr,
-                                   o.lattice_track_decodes != nullptr, o.line_decodes != nullptr);
+                                   o.lattice_track_decodes != nullptr, o.line_decodes != nullptr, o.line_margins != nullptr);
     if (reads) reads->assign(n_run, str_er_run_read{});
     q.assign(1800 * n_run, 0);
     if (pieces) {

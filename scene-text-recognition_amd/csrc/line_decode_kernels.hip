@@ -24,14 +24,6 @@ namespace {
 constexpr int      LD_THREADS = 64 * LD_LINES, LD_MAX_ROWS = 1024, LD_GAP = 66;
 constexpr uint32_t LD_OFF = 255, LD_BREAK = 1u << 7;
 
-// what the lanes of a wave leave in device memory for each other: as wd_wave_sync, with the stores of the wave completed
-__device__ __forceinline__ void ld_global_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 __global__ void __launch_bounds__(LD_THREADS) k_line_decode(const uint8_t *__restrict__ bigram, int ins, int del, const uint8_t *__restrict__ costs,
                                                             const uint8_t *__restrict__ gaps, const int32_t *__restrict__ first_row, const int32_t *__restrict__ n_of,
                                                             const int32_t *__restrict__ row_map, int n_lines, uint16_t *bp, int32_t *__restrict__ dec, uint8_t *chars, uint16_t *src, int32_t *word_of_row)
@@ -118,7 +110,7 @@ __global__ void __launch_bounds__(LD_THREADS) k_line_decode(const uint8_t *__res
         if (lane < 2) { vkw[64 + lane] = key_hi; st[64 + lane] = (uint16_t)e_hi; }
     }
     const uint32_t end = wd_column(Bs, lane, WD_E, key_lo, key_hi, 2);
-    ld_global_sync();
+    wd_global_sync();
     if (lane == 0) {          // the backtrack: the string from its end, into the tail of the line's slice
         int state = (int)(end & 127u), at = 3 * n, n_sub = 0, n_del = 0, n_ins = 0, n_brk = 0;
         for (int i = n; i >= 1; --i) {
@@ -149,14 +141,14 @@ __global__ void __launch_bounds__(LD_THREADS) k_line_decode(const uint8_t *__res
         rec[wave][0] = (int32_t)(end >> 7); rec[wave][1] = 3 * n - at; rec[wave][2] = n_brk;
         rec[wave][3] = n_sub; rec[wave][4] = n_del; rec[wave][5] = n_ins;
     }
-    ld_global_sync();
+    wd_global_sync();
     const int n_chars = rec[wave][1], n_brk = rec[wave][2], from = 3 * n - n_chars;          // (from >= 1 where n >= 1: a line emits at most 3n - 1)
     for (int c0 = 0; c0 < n_chars; c0 += 64) {          // ascending: chunk c is written below everything a later chunk reads
         const int k = c0 + lane;
         uint8_t   ch = 0;
         uint16_t  sv = 0;
         if (k < n_chars) { ch = oc[from + k]; sv = os[from + k]; }
-        ld_global_sync();
+        wd_global_sync();
         if (k < n_chars) { oc[k] = ch; os[k] = sv; }
     }
     for (int k = n_chars + lane; k < 3 * n; k += 64) { oc[k] = (uint8_t)0xFF; os[k] = (uint16_t)0xFFFF; }

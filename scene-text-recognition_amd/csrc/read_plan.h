@@ -29,11 +29,12 @@ struct ReadPlan {
     bool lmargin;          // the lattice decoder's margins (str_er_set_lattice_margin): only with lattice; the decoder's window, records, labels, sources and parts
     bool ltdecode;         // the track decode over the members' lattices (str_er_set_lattice_track_decode): only with tdecode and lattice; it reads lattice_set, the lattice decoder's records and labels
     bool ldecode;          // the line decode (str_er_set_line_decode): only with decode; it reads the runs' rows of decode_set, every line one window
+    bool lnmargin;         // the line decode's margins (str_er_set_line_margin): only with ldecode; behind it on its rows, gaps, windows, records, labels and sources
     bool any() const { return match || decode || split; }      // some consumer reads the words and the class probabilities
 };
 
 inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, bool track, bool fold, bool lmatch = false, bool ltrack = false, bool tdecode = false,
-                          bool margin = false, bool lmargin = false, bool ltdecode = false, bool ldecode = false)
+                          bool margin = false, bool lmargin = false, bool ltdecode = false, bool ldecode = false, bool lnmargin = false)
 {
     ReadPlan p{};
     p.match = match; p.decode = decode; p.split = split; p.lattice = lattice && split; p.track = track && match;
@@ -57,6 +58,7 @@ inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, boo
     p.lmargin = lmargin && p.lattice;
     p.ltdecode = ltdecode && p.tdecode && p.lattice;
     p.ldecode = ldecode && p.decode;
+    p.lnmargin = lnmargin && p.ldecode;
     return p;
 }
 

@@ -29,6 +29,7 @@
 #include "word_decode_kernels.h"
 #include "word_margin_kernels.h"
 #include "line_decode_kernels.h"
+#include "line_margin_kernels.h"
 #include "lattice_margin_kernels.h"
 #include "er_group.h"
 #include "flood_order.h"
@@ -217,6 +218,10 @@ struct str_er_result {
     std::vector<int32_t> line_decode_word_of_row, line_decode_windows;
     std::vector<uint8_t> line_gap_costs;
     bool have_line_decodes = false;
+    std::vector<str_er_line_margin> line_margins; // str_er_set_line_margin beside the line decode: per line of texts, and per row of the line decode's rows a row margin, a reading,
+    std::vector<int32_t> line_row_margins, line_gap_margins;      // an alternative, a gap margin and a gap move
+    std::vector<uint8_t> line_row_reads, line_row_alts, line_gap_moves;
+    bool have_line_margins = false;
 };
 
 // A table of a result, as the str_er_result_* accessors hand it out: null (and *n = 0) when its stage did not run, and when it ran but made no
@@ -435,6 +440,8 @@ struct str_er_ctx {
     int32_t  ln_weight = 16;          // the weight of its gap costs
     PairBuf  ln_tab;                  // (str_er_decode_lines: cost rows | first row, row count per line) | gap costs | records | labels | sources | word of every row
     DevBuf   ln_bp;                   // the back pointers of k_line_decode: 68 uint16 per row, scratch
+    bool     ln_margin = false;       // str_er_set_line_margin: a detect call that decodes its lines also makes their margins
+    DevBuf   ln_fw;                   // the forward values of k_line_margin: 136 uint32 per row, scratch
     int32_t  bigram_ee = 0;           // B[E][E] of the table that is set: what a line without rows costs
 };
 
@@ -755,6 +762,9 @@ struct ReadChainOut {
     std::vector<str_er_line_decode> *line_decodes = nullptr; std::vector<uint8_t> *line_chars = nullptr, *line_gaps = nullptr;
     std::vector<uint16_t> *line_src = nullptr; std::vector<int32_t> *line_word_of_row = nullptr, *line_windows = nullptr;
     size_t n_lines = 0; int32_t line_bee = 0;
+    // str_er_set_line_margin (with the line decode): the margins of the lines' strings, behind the line decode on its rows
+    std::vector<str_er_line_margin> *line_margins = nullptr; std::vector<int32_t> *line_row_margins = nullptr, *line_gap_margins = nullptr;
+    std::vector<uint8_t> *line_row_reads = nullptr, *line_row_alts = nullptr, *line_gap_moves = nullptr;
     void preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k) const;      // every table of the plan as a call without runs leaves it (k: the model's classes)
 };
 // carving a table buffer: take(bytes) is the offset of the next piece, and the one after it starts at the next multiple of 256
@@ -906,15 +916,18 @@ WdTab wd_layout(uint8_t *base, size_t at, size_t n_words);
 // windows the lines' first row and row count) and what k_line_decode leaves, all of which comes down
 struct LnTab {
     uint8_t *gaps; int32_t *first, *n_of, *row_map; str_er_line_decode *dec; uint8_t *chars; uint16_t *src; int32_t *word_of_row;
+    // with margin, what k_line_margin leaves behind them (marginals: null where they are not made)
+    str_er_line_margin *margins; int32_t *row_margin, *gap_margin; uint8_t *row_read, *row_alt, *gap_move; int32_t *marginals;
     size_t o_up, up_bytes;                // gaps | first | n_of | row_map lie back to back: one copy up
-    size_t o_dec, down_bytes, bytes;      // dec | chars | src | word_of_row lie back to back (each aligned): one copy down
+    size_t o_dec, down_bytes, bytes;      // dec | chars | src | word_of_row | the margins' tables lie back to back (each aligned): one copy down
 };
-LnTab ln_layout(uint8_t *base, size_t at, size_t n_rows, size_t n_lines, bool windows, bool map);
+LnTab ln_layout(uint8_t *base, size_t at, size_t n_rows, size_t n_lines, bool windows, bool map, bool margin = false, bool marginals = false);
 // k_line_decode behind what is on s: the gap costs (and with first / n_of the windows, else d_first / d_n_of are on the device already;
 // with row_map the cost row of every row, else row r is cost row r) into c->ln_tab from byte `at` on and up, the back-pointer table sized, the outputs preset for the rows of no line, the launch; H and D
 // receive the two sides of the layout (what comes down: H.o_dec, H.down_bytes)
 int line_decode_enqueue(str_er_ctx *c, hipStream_t s, size_t at, const uint8_t *d_rows, size_t n_rows, const uint8_t *gaps, const int32_t *first, const int32_t *n_of,
-                        const int32_t *d_first, const int32_t *d_n_of, size_t n_lines, const int32_t *row_map, LnTab &H, LnTab &D);
+                        const int32_t *d_first, const int32_t *d_n_of, size_t n_lines, const int32_t *row_map, LnTab &H, LnTab &D, bool margin = false, bool marginals = false);
+// (margin: k_line_margin behind it on the same rows, its forward table sized and its tables behind the decoder's in the same layout)
 // ---- defined in api_lattice_margin.cpp
 // the layout of what k_lattice_margin leaves in c->lg_tab from byte `at` on (the inputs' bytes), all of which comes down
 struct LgTab {

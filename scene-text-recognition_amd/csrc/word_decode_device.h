@@ -1,7 +1,7 @@
 // word_decode_device.h -- INTERNAL: the device pieces the bigram decoders share (word_decode_kernels.hip: k_word_decode,
 // lattice_decode_kernels.hip: k_lattice_decode, word_margin_kernels.hip: k_word_margin,
-// lattice_margin_kernels.hip: k_lattice_margin): the layout of the table in LDS, the wave-level sync, the min-plus product of a state
-// vector with the table for the targets 0 .. 63 and its turned-round form for the target 64 and the end of the word, and a step of the
+// lattice_margin_kernels.hip: k_lattice_margin, line_decode_kernels.hip: k_line_decode, line_margin_kernels.hip: k_line_margin): the
+// layout of the table in LDS, the wave-level syncs, the min-plus product of a state vector with the table for the targets 0 .. 63 and its turned-round form for the target 64 and the end of the word, and a step of the
 // plain reading.  A value travels with its state as a key (value << 7 | state); every value of either decoder is below 2^21, so a key
 // is below 2^28 and the sum of a key and a table byte << 7 cannot wrap.
 #pragma once
@@ -28,6 +28,15 @@ __device__ __forceinline__ void wd_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// what the lanes of a wave leave in device memory for each other (the scratch tables of k_line_decode and k_line_margin): as
+// wd_wave_sync, with the stores of the wave completed
+__device__ __forceinline__ void wd_global_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 __device__ __forceinline__ uint32_t wd_wave_min(uint32_t v)

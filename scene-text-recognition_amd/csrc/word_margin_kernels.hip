@@ -18,39 +18,18 @@
 // padding between them, three workgroups (twelve waves) a CU by LDS.
 #include <hip/hip_runtime.h>
 
-#include "word_decode_device.h"
+#include "word_margin_device.h"
 #include "word_margin_kernels.h"
 
 namespace str_er {
 
 namespace {
 
-constexpr int      WG_THREADS = 64 * WG_WORDS, WG_MARGINALS = WD_STATES, WG_ROW_WORDS = WD_ROW / 4;
+constexpr int      WG_THREADS = 64 * WG_WORDS, WG_MARGINALS = WD_STATES;
 constexpr uint32_t WG_NONE16 = 0xFFFFu;
 
 __device__ __forceinline__ uint32_t wg_load16(uint16_t v) { return v == WG_NONE16 ? WD_INF : (uint32_t)v; }
 __device__ __forceinline__ uint16_t wg_store16(uint32_t v) { return (uint16_t)min(v, WG_NONE16); }
-
-// min over c in [0, 65) of B[lane][c] + vec[c]; brow = the words of the table's row of the lane.  Fully unrolled: every offset is an immediate.
-__device__ __forceinline__ uint32_t wg_product_t(const uint32_t *vec, const uint32_t *brow)
-{
-    uint32_t best = ~0u;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const uint32_t b4 = brow[k];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) best = min(best, vec[4 * k + j] + ((b4 >> (8 * j)) & 255u));
-    }
-    return min(best, vec[64] + (brow[16] & 255u));
-}
-
-// the same for the row a = 64 or 65 of the table, turned round: a lane a column, the column 64 in lane 0; every lane gets the minimum
-__device__ __forceinline__ uint32_t wg_row(const uint8_t *Bs, int lane, int a, uint32_t v_lo, uint32_t v_64)
-{
-    uint32_t t = v_lo + (uint32_t)Bs[a * WD_ROW + lane];
-    if (lane == 0) t = min(t, v_64 + (uint32_t)Bs[a * WD_ROW + 64]);
-    return wd_wave_min(t);
-}
 
 __global__ void __launch_bounds__(WG_THREADS) k_word_margin(const uint8_t *__restrict__ bigram, int ins, int del, const uint8_t *__restrict__ costs,
                                                             const int32_t *__restrict__ first_run, const int32_t *__restrict__ n_of, int n_words,

@@ -825,6 +825,50 @@ public:
                                   n ? out.row_reads.data() : nullptr, n ? out.row_alts.data() : nullptr, marginals && n ? out.marginals.data() : nullptr));
         return out;
     }
+    // The margins of the decoded lines (str_er_set_line_margin beside str_er_set_line_decode and STR_ER_WANT_WORD_DECODE; the contract is at
+    // str_er_line_margin in include/str_er.h): one record per line, and per row of the line decode's rows a row margin and a gap margin
+    // (-1 where there is none), a reading, an alternative (65: the row dropped) and a gap move (0 join, 1 break; 0xFF where there is
+    // none); marginals only from line_margins on the caller's rows, 68 per row
+    struct LineMargins {
+        std::vector<str_er_line_margin> margins;
+        std::vector<int32_t>            row_margins, gap_margins, marginals;
+        std::vector<uint8_t>            row_reads, row_alts, gap_moves;
+    };
+    // whether a call that decodes its lines also makes their margins (str_er_set_line_margin; off by default)
+    void set_line_margin(bool on) { check(str_er_set_line_margin(ctx_.get(), on ? 1 : 0)); }
+    // ... copied out of the result of such a call (all empty when it made none)
+    static LineMargins line_margins(const str_er_result *r)
+    {
+        LineMargins out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_line_margin *p = str_er_result_line_margins(r, &n)) out.margins.assign(p, p + n);
+        if (const int32_t *p = str_er_result_line_row_margins(r, &nb)) out.row_margins.assign(p, p + nb / 4);
+        if (const uint8_t *p = str_er_result_line_row_reads(r, &nb)) out.row_reads.assign(p, p + nb);
+        if (const uint8_t *p = str_er_result_line_row_alts(r, &nb)) out.row_alts.assign(p, p + nb);
+        if (const int32_t *p = str_er_result_line_gap_margins(r, &nb)) out.gap_margins.assign(p, p + nb / 4);
+        if (const uint8_t *p = str_er_result_line_gap_moves(r, &nb)) out.gap_moves.assign(p, p + nb);
+        return out;
+    }
+    // the margins of the lines [first_row[t], first_row[t] + n_rows[t]) of the caller's cost rows and gap pairs under the table
+    // (str_er_line_margins: the line decoder and its margins in one call)
+    LineMargins line_margins(const std::vector<uint8_t> &costs, const std::vector<uint8_t> &gaps, const std::vector<int32_t> &first_row, const std::vector<int32_t> &n_rows,
+                             bool marginals = false)
+    {
+        if (first_row.size() != n_rows.size() || costs.size() % 65 || gaps.size() != 2 * (costs.size() / 65))
+            throw std::invalid_argument("line_margins: 65 bytes and one gap pair a row, one span a line");
+        const size_t n = first_row.size(), nr = costs.size() / 65;
+        LineMargins  out;
+        out.margins.resize(n);
+        out.row_margins.resize(nr); out.gap_margins.resize(nr);
+        out.row_reads.resize(nr); out.row_alts.resize(nr); out.gap_moves.resize(nr);
+        if (marginals) out.marginals.resize(68 * nr);
+        check(str_er_line_margins(ctx_.get(), nr ? costs.data() : nullptr, (int32_t)nr, nr ? gaps.data() : nullptr, n ? first_row.data() : nullptr, n ? n_rows.data() : nullptr,
+                                  (int32_t)n, n ? out.margins.data() : nullptr, nr ? out.row_margins.data() : nullptr, nr ? out.row_reads.data() : nullptr,
+                                  nr ? out.row_alts.data() : nullptr, nr ? out.gap_margins.data() : nullptr, nr ? out.gap_moves.data() : nullptr,
+                                  marginals && nr ? out.marginals.data() : nullptr));
+        return out;
+    }
     // the decoded string of word w: its own reading where it was not decoded (more than 32 runs)
     static std::string word_decode_text(const LineWords &lw, const RunReads &rd, const WordDecodes &wd, size_t w)
     {

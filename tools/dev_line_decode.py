@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
-"""Developer aid: what the line decoder (str_er_set_line_decode, str_er_decode_lines) costs (profiles/line_decode.md).
+"""Developer aid: what the line decoder (str_er_set_line_decode, str_er_decode_lines) and its margins (str_er_set_line_margin,
+str_er_line_margins) cost (profiles/line_decode.md, profiles/line_margin.md).
 
-    python tools/dev_line_decode.py kernel [--lines 100] [--rows 75] [--reps 7] [--ins 0] [--del 0] [--iters N]
+    python tools/dev_line_decode.py kernel [--lines 100] [--rows 75] [--reps 7] [--ins 0] [--del 0] [--margin] [--iters N]
         decode_lines on lines of --rows rows each, beside decode_words on the same rows cut into words of 3 .. 12 runs (the workload
         of tools/dev_word_decode.py kernel): the time of every call, and the single-thread time of the host rules
         (str_er_decode_lines_host) on the same input, with the tables compared.  --iters: calls only, for a
-        `rocprofv3 --kernel-trace --stats` run, which gives the two kernels' times side by side.
-    python tools/dev_line_decode.py detect [--reps 40] [--line] [--weight 16] [--ins 0] [--del 0] [--iters N]
+        `rocprofv3 --kernel-trace --stats` run, which gives the two kernels' times side by side.  --margin: line_margins as well
+        (k_line_decode and k_line_margin in one call), its call time beside decode_lines', the host rules compared.
+    python tools/dev_line_decode.py detect [--reps 40] [--line] [--margin] [--split] [--weight 16] [--ins 0] [--del 0] [--iters N]
         the detect call of tests/test_line_decode_pipeline.py (two 640 x 480 S-text frames, two pyramid levels, grouped stages, masks,
         frame lines, line words, run reading, word decode): every call time, median, minimum, maximum.  --line switches the setting on
-        and prints the lines' strings beside the word gap's.
+        and prints the lines' strings beside the word gap's.  --margin (with --line) switches the margins on as well and prints every
+        line's margin and its unsure breaks; without --iters it times the call with the margins off and on, alternated.  --split adds
+        WANT_RUN_SPLIT: the rows are the words' parts and the line kernels run behind a second wait.
 """
 import argparse, gzip, json, os, sys, tempfile, time
 import numpy as np
@@ -24,6 +28,8 @@ ap.add_argument("--ins", type=int, default=0)
 ap.add_argument("--del", dest="dele", type=int, default=0)
 ap.add_argument("--weight", type=int, default=16)
 ap.add_argument("--line", action="store_true")
+ap.add_argument("--margin", action="store_true")
+ap.add_argument("--split", action="store_true")
 ap.add_argument("--out", default="")
 a = ap.parse_args()
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -69,10 +75,17 @@ def kernel():
     dec, chars, src, wor = f.decode_lines(costs, gaps, lfirst, ln)
     out["breaks"] = int(dec["n_breaks"].sum())
     out["table_bytes"] = f.line_decode_stats()["table_bytes"]
+    if a.margin:
+        mg = f.line_margins(costs, gaps, lfirst, ln)
+        out["margin_table_bytes"] = f.line_margin_stats()["table_bytes"]
+        out["gaps_with_an_alternative"] = int((mg[4] >= 0).sum())
+        out["gap_margins_of_0"] = int((mg[4] == 0).sum())
     if a.iters:
         for _ in range(a.iters):
             f.decode_words(costs, wfirst, wn)
             f.decode_lines(costs, gaps, lfirst, ln)
+            if a.margin:
+                f.line_margins(costs, gaps, lfirst, ln)
         out["iters"] = a.iters
     else:
         reps = a.reps or 7
@@ -83,6 +96,13 @@ def kernel():
         dt = time.perf_counter() - t0
         assert all(x.tobytes() == y.tobytes() for x, y in zip(host, (dec, chars, src, wor)))
         out["host_one_thread_ms"] = round(dt * 1e3, 2)
+        if a.margin:
+            out["line_margins_call_ms"] = timed(lambda: f.line_margins(costs, gaps, lfirst, ln), reps)
+            t0 = time.perf_counter()
+            host = S.line_margins_host(costs, gaps, lfirst, ln, table, a.ins, a.dele)
+            dt = time.perf_counter() - t0
+            assert all(x.tobytes() == y.tobytes() for x, y in zip(host, mg))
+            out["margins_host_one_thread_ms"] = round(dt * 1e3, 2)
     f.close()
     return out
 
@@ -104,7 +124,7 @@ def detect():
     read = sorted({plain.word_text(w) for w in range(len(plain.words))})
     f.set_bigram(S.bigram_from_words([t for t in read if t and all(ch in ALPHABET for ch in t)]))
     f.set_word_decode(a.ins, a.dele)
-    flags |= S.WANT_WORD_DECODE
+    flags |= S.WANT_WORD_DECODE | (S.WANT_RUN_SPLIT if a.split else 0)
     if a.line:
         f.set_line_decode(True, a.weight)
         r = f.text_detect(frames, flags)
@@ -112,10 +132,25 @@ def detect():
         out["word_gap_breaks"] = int((r.line_words["n_words"].clip(1) - 1).sum())
         out["texts"] = [[r.line_decode_text(t), " ".join(r.words_decode_text_of_line(t))] for t in range(len(r.texts))]
         out["table_bytes"] = f.line_decode_stats()["table_bytes"]
+    if a.line and a.margin:
+        f.set_line_margin(True)
+        r = f.text_detect(frames, flags)
+        out["margins"] = [[r.line_decode_margin(t), [g for g in r.line_break_margins(t) if 0 <= g[2] < 8]] for t in range(len(r.texts))]
+        out["margin_table_bytes"] = f.line_margin_stats()["table_bytes"]
     if a.iters:
         for _ in range(a.iters):
             f.text_detect(frames, flags)
         out["iters"] = a.iters
+    elif a.line and a.margin:          # off and on, alternated
+        off, on = [], []
+        for k in range(5 + (a.reps or 40)):
+            for t, flag in ((off, False), (on, True)):
+                f.set_line_margin(flag)
+                t0 = time.perf_counter()
+                f.text_detect(frames, flags)
+                if k >= 5:
+                    t.append((time.perf_counter() - t0) * 1e3)
+        out["detect_call_ms_margin_off"], out["detect_call_ms_margin_on"] = stats(off), stats(on)
     else:
         for _ in range(5):
             f.text_detect(frames, flags)
