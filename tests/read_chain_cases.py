@@ -8,7 +8,13 @@ small   the records a kernel writes as constants -- a word of no runs, a word of
 large   at least 16 times the words, member slots, part slots and footprints, and a live record in every slot: every word usable with a
         cut run, every member slot in a track, every footprint with runs and most with a cut run.  The track decode's large case holds tracks of exactly 252
         and 253 rows of usable members (the two sides of TD_RES = 16384 bytes of 65-byte rows) and a track of nine members of 32 rows
-        (288 rows: not resident, and the polish runs on members of 32 rows)."""
+        (288 rows: not resident, and the polish runs on members of 32 rows).
+
+The lattice track decode has the tracks of the matchers and more (`ltd`): in the small case a track of the word without runs alone, in the
+large one 32 further tracks.  The line
+decoder and its margins have lines over the words' run rows, repeated to the length they need (lines_case): small is a line without rows,
+a line of 1025 rows (one more than the decoder takes), an ordinary line, and GAP rows of no line behind each of the latter two; large is
+17 lines of 1024 rows and 64 short ones, every row in a line."""
 import numpy as np
 
 import lexicon_layout as LL
@@ -22,6 +28,7 @@ W, H = 320, 128                         # the frame of the hand-made footprints 
 GAP = 2                                 # member slots of no track behind every track of a small case
 SIZES = ("small", "large")
 TD_RES_ROWS = 16384 // 65               # rows of usable members that stay resident in k_track_decode
+LINE_MAX = 1024                         # rows of the longest line the line decoder takes
 
 
 def feet_case(size):
@@ -62,7 +69,35 @@ def rows_case(S, size):
     sp, rc, pc = make_rows(S, rng, np.array([k for c in shapes for k in c], np.int64))
     rc, pc = cheapen(rng, rc), cheapen(rng, pc)
     tf, tc, mem = _track_table(len(shapes), tracks, gap)
-    return {"sp": sp, "rc": rc, "pc": pc, "first": first, "n_of": n_of, "tf": tf, "tc": tc, "mem": mem, "tracks": tracks, "shapes": shapes}
+    # the lattice track decode: in the small case a track of the word without runs alone as well (no seeds); in the large one 32 more
+    # tracks, 16 times the small case's
+    more = np.random.default_rng(9103)
+    ltd_tracks = tracks + ([[0, 0]] if size == "small" else [[int(w) for w in more.integers(0, len(shapes), int(k))] for k in more.integers(1, 12, 32)])
+    return {"sp": sp, "rc": rc, "pc": pc, "first": first, "n_of": n_of, "tf": tf, "tc": tc, "mem": mem, "tracks": tracks, "shapes": shapes,
+            "ltd": _track_table(len(shapes), ltd_tracks, gap), "ltd_tracks": ltd_tracks}
+
+
+def lines_case(rows, size):
+    """The lines of the line decoder and its margins over the run rows of rows_case, repeated: {costs, gaps, first, n_of, no_line (the
+    rows of no line)}.  Both moves are on at every gap inside a line; the first row of a line and a row of no line have (0, 255), as
+    str_er_line_gap_costs gives them."""
+    if size == "small":
+        rng = np.random.default_rng(9501)
+        n_of, gap = [0, LINE_MAX + 1, 3], [0, GAP, GAP]          # no rows; one row too many; ordinary
+    else:
+        rng = np.random.default_rng(9502)
+        n_of = [LINE_MAX] * 17 + [int(k) for k in rng.integers(1, 13, 64)]
+        gap = [0] * len(n_of)
+    first = np.concatenate([[0], np.cumsum(np.add(n_of, gap))[:-1]]).astype(np.int32)
+    total = int(first[-1]) + n_of[-1] + gap[-1]
+    costs = np.ascontiguousarray(np.resize(rows["rc"], (total, 65)))
+    gaps = rng.integers(0, 48, (total, 2)).astype(np.uint8)
+    in_line = np.zeros(total, bool)
+    for a, k in zip(first, n_of):
+        in_line[a:a + k] = True
+    gaps[~in_line] = (0, 255)
+    gaps[first[np.array(n_of) > 0]] = (0, 255)
+    return {"costs": costs, "gaps": gaps, "first": first, "n_of": np.array(n_of, np.int32), "no_line": np.flatnonzero(~in_line)}
 
 
 def _variant(rng, truth, n_sub):

@@ -1,13 +1,15 @@
 """The reading chain on a reused context: feet_words, feet_read, feet_split, split_words, match_words, decode_words, lattice_decode_words,
-lattice_match_words, match_tracks, lattice_match_tracks, decode_tracks and two track pools run on ONE context on a small input, a large
-one, the small one again, both again with the entry points in reverse order, and under a lexicon of several chunks that is swapped in
-and out -- so that every call finds in its on-demand buffers (wm_tab, wd_tab, rs_tab, rs_out, ld_tab, lm_tab, tm_tab, lt_tab, td_tab,
-run_tab, run_atlas, the pools' rows / tab) the records of a call with another layout.  The small input (read_chain_cases.py) consists of
+lattice_match_words, match_tracks, lattice_match_tracks, decode_tracks, word_margins, lattice_margins, lattice_decode_tracks, decode_lines,
+line_margins and two track pools run on ONE context on a small input, a large one, the small one again, both again with the entry
+points in reverse order, and under a lexicon of several chunks that is swapped in and out -- so that every call finds in its on-demand
+buffers (wm_tab, wd_tab, wg_tab, rs_tab, rs_out, ld_tab, lg_tab, lm_tab, tm_tab, lt_tab, td_tab, ltd_tab, ln_tab, ln_bp, ln_fw, run_tab,
+run_atlas, the pools' rows / tab) the records of a call with another layout.  The small input (read_chain_cases.py) consists of
 the records a kernel or a fill writes as constants, the large one has a live record in every slot: a slot nobody writes shows as a
 stale record.  Every output equals the host entry point's on the same input byte for byte (feet_words: line_words_ref.py; feet_read
 and feet_split, which have no host twin: the same call on a brand-new context, and once their modules' references), every small round
-equals the first, the buffers grow once and workspace_bytes() never.  Then the fused detect call, a blank frame, a list call and the
-single-stage rounds take turns on one context (read_rows and the shared scratch change hands).  test_on_demand_buffers.py does the
+equals the first, the buffers grow once and workspace_bytes() never.  Then the fused detect call with the five settings on
+(set_word_margin, set_lattice_margin, set_lattice_track_decode, set_line_decode, set_line_margin), a blank frame, a list call and the
+single-stage rounds take turns on one context (read_rows, the shared scratch, ln_bp and ln_fw change hands).  test_on_demand_buffers.py does the
 same for the buffers up to feet_geom.
 
 What was tried against it, each edit only leaving out a write of default values: without the 0xFF fill of member_cost in
@@ -15,6 +17,23 @@ track_match_enqueue the member slots of no track hold 0 on a fresh buffer and a 
 every small round after a large one fail against match_tracks_host); the same fill in track_decode_enqueue likewise.  The loop that writes
 -1 for the members of an undecoded track in k_track_decode cannot be seen by any test: that fill has written the same slots on the same
 stream before the launch.  Without both, the slots of the tracks of unusable members and of no seeds are stale as well.
+
+The five newer stages, one library build for each edit, all rounds run until the first failure:
+  decode_lines, line_margins   without the 0xFF preset of the line tables in line_decode_enqueue the labels of the rows of no line are not
+                               0xFF: round 1 fails at decode_lines (the label bytes from 3 * 1025 on, against decode_lines_host).
+                               Without the loops of k_line_decode that write 0xFF / 0xFFFF / -1 over a line of more than 1024 rows, and
+                               without the loops and the record of -1 that k_line_margin writes for a line without rows or of more than 1024
+                               rows, every round passes: no test can see them, that preset has written the same bytes into the same slots on
+                               the same stream before the launch (the records of the margins lie in the preset too).
+  word_margins                 without the stores of the record and the rows of a word that is not decoded (0 or 33 runs), and of the rows
+                               a decoded word does not have, in k_word_margin: round 1 fails at word_margins, records 0 and 1.
+  lattice_margins              the same stores of k_lattice_margin for a word of no runs or of an unusable lattice: round 1 fails at
+                               lattice_margins, records 0, 1 and 2.
+  lattice_decode_tracks        without the member record and the 0xFF sources that k_lattice_track_decode_members writes for a slot of no
+                               track: round 1 fails at the member records 0, 1, 4, 5, 8 ...; without the record and the 0xFF labels of a track
+                               without seeds in the track kernel (n_used kept): round 1 fails at the track records 0, 1, 3, 4.
+A fresh buffer holds zeros and these defaults are -1 and 0xFF, so each of them shows in round 1 already; the small rounds behind a large
+one hold the same slots against a larger call's records.
 
 The first section needs no GPU: it proves on the host entry points that the cases are what they claim to be."""
 import numpy as np
@@ -27,26 +46,36 @@ import run_split_ref as RS
 import track_decode_ref as TD
 from test_frame_lines import GROUPED
 from test_lattice_decode_pipeline import INS as DEC_INS, DEL as DEC_DEL, LATTICE_TABLES, proto  # noqa: F401  (the fixture)
+from test_lattice_margin_pipeline import MARGIN_TABLES as LATTICE_MARGIN_TABLES
 from test_lattice_match_pipeline import BAND, DEL, INS, MATCH_TABLES, OTHER_TABLES, lex  # noqa: F401  (the fixture)
+from test_lattice_track_decode_pipeline import NEW as LATTICE_TRACK_DECODE_TABLES
 from test_lattice_track_pipeline import READ_TABLES, TRACK_TABLES
+from test_line_decode_pipeline import LINE_TABLES
+from test_line_margin_pipeline import MARGIN_TABLES as LINE_MARGIN_TABLES
 from test_line_words import _feet
 from test_read_chain_combos import DECODE_TABLES
 from test_run_split_pipeline import DEN, NUM, SPLIT, scene  # noqa: F401  (the fixture lex builds on)
 from test_svm_exact import _shipped
 from test_track_decode_pipeline import NEW as TRACK_DECODE_TABLES
 from test_track_pool import EMPTY as POOL_EMPTY, reference as pool_reference
+from test_word_margin_pipeline import MARGIN_TABLES as WORD_MARGIN_TABLES
 
 STAGES = ("feet_words", "feet_read", "feet_split", "split_words", "match_words", "decode_words", "lattice_decode_words", "lattice_match_words",
-          "match_tracks", "lattice_match_tracks", "decode_tracks")
+          "match_tracks", "lattice_match_tracks", "decode_tracks", "word_margins", "lattice_margins", "lattice_decode_tracks", "decode_lines", "line_margins")
 FEET_STAGES = STAGES[:3]
 SPLIT_KEYS = ("line_words", "runs", "words", "reads", "q", "splits", "pieces", "piece_reads", "piece_q")
 NO_MATCH = (-1, -1, -1, -1)
+NO_MARGIN, NO_LATTICE_MARGIN, NO_LINE_MARGIN = (-1,) * 4, (-1,) * 7 + (0,), (-1,) * 8
+NO_LINE = (-1, 0, 0, 0, 0, 0)
+NO_MEMBER = (-1, 0, 0, 0)               # (cost, n_parts, n_del, n_ins of a member that took no part; first_part is where the parts stand, word the slot's)
 DEFAULTS = dict(fold=True, ins=64, dele=64, band=2, num=1, den=4, split=8, dec_ins=0, dec_dele=0, td_ins=64, td_dele=64, rounds=8)
 # every table a result of the fused call exposes
 FUSED = dict(want_masks=True, want_frame_lines=True, want_line_links=True, want_line_words=True, want_run_read=True, want_word_match=True, want_word_decode=True,
              want_run_split=True, want_track_read=True, want_lattice_decode=True, want_lattice_match=True, want_lattice_track=True, want_track_decode=True)
 assert OTHER_TABLES[:5] == ("line_words", "line_runs", "words", "run_reads", "run_features") and OTHER_TABLES[11] == "run_splits" and READ_TABLES[5] == "track_member_costs"
-READING_TABLES = tuple(dict.fromkeys(OTHER_TABLES[:5] + OTHER_TABLES[11:] + DECODE_TABLES + LATTICE_TABLES + MATCH_TABLES + READ_TABLES[:6] + TRACK_TABLES + TRACK_DECODE_TABLES))
+SETTING_TABLES = WORD_MARGIN_TABLES + LATTICE_MARGIN_TABLES + LATTICE_TRACK_DECODE_TABLES + LINE_TABLES + LINE_MARGIN_TABLES          # the five settings'
+READING_TABLES = tuple(dict.fromkeys(OTHER_TABLES[:5] + OTHER_TABLES[11:] + DECODE_TABLES + LATTICE_TABLES + MATCH_TABLES + READ_TABLES[:6] + TRACK_TABLES + TRACK_DECODE_TABLES
+                                     + SETTING_TABLES))
 FUSED_TABLES = tuple(dict.fromkeys(OTHER_TABLES + READ_TABLES + READING_TABLES))
 
 
@@ -54,18 +83,24 @@ FUSED_TABLES = tuple(dict.fromkeys(OTHER_TABLES + READ_TABLES + READING_TABLES))
 
 @pytest.fixture(scope="module")
 def cases(S):
-    """{size: {feet, ft, bits, rows, td}} and the lexicons and the table."""
+    """{size: {feet, ft, bits, rows, td, lines}} and the lexicons and the table."""
     out = {"lex": dict(zip(("one", "big"), RC.lexicons())), "B": RC.bigram()}
     for size in RC.SIZES:
         feet = RC.feet_case(size)
         ft, bits = _feet(S, feet["items"])
-        out[size] = {"feet": feet, "ft": ft, "bits": bits, "rows": RC.rows_case(S, size), "td": RC.track_decode_case(size)}
+        rows = RC.rows_case(S, size)
+        out[size] = {"feet": feet, "ft": ft, "bits": bits, "rows": rows, "td": RC.track_decode_case(size), "lines": RC.lines_case(rows, size)}
     return out
 
 
 def _args(c):
     r = c["rows"]
     return (r["rc"], r["first"], r["n_of"]), (r["sp"], r["rc"], r["pc"], r["first"], r["n_of"]), (r["tf"], r["tc"], r["mem"])
+
+
+def _lines(c):
+    L = c["lines"]
+    return L["costs"], L["gaps"], L["first"], L["n_of"]
 
 
 def host_round(S, c, words, B, p=DEFAULTS):
@@ -78,7 +113,12 @@ def host_round(S, c, words, B, p=DEFAULTS):
             "lattice_match_words": S.lattice_match_words_host(*lat, words, p["fold"], p["ins"], p["dele"], p["band"], p["split"]),
             "match_tracks": S.match_tracks_host(*rows, *tr, words, p["fold"], p["ins"], p["dele"], p["band"]),
             "lattice_match_tracks": S.lattice_match_tracks_host(*lat, *tr, words, p["fold"], p["ins"], p["dele"], p["band"], p["split"]),
-            "decode_tracks": S.decode_tracks_host(*c["td"]["packed"], B, p["dec_ins"], p["dec_dele"], p["td_ins"], p["td_dele"], p["rounds"])}
+            "decode_tracks": S.decode_tracks_host(*c["td"]["packed"], B, p["dec_ins"], p["dec_dele"], p["td_ins"], p["td_dele"], p["rounds"]),
+            "word_margins": S.word_margins_host(*rows, B, p["dec_ins"], p["dec_dele"])[:4],
+            "lattice_margins": S.lattice_margins_host(*lat, B, p["dec_ins"], p["dec_dele"], p["split"])[:6],
+            "lattice_decode_tracks": S.lattice_decode_tracks_host(*lat, *c["rows"]["ltd"], B, p["dec_ins"], p["dec_dele"], p["td_ins"], p["td_dele"], p["rounds"], p["split"]),
+            "decode_lines": S.decode_lines_host(*_lines(c), B, p["dec_ins"], p["dec_dele"]),
+            "line_margins": S.line_margins_host(*_lines(c), B, p["dec_ins"], p["dec_dele"])}
 
 
 @pytest.fixture(scope="module")
@@ -117,6 +157,10 @@ def test_the_large_case_is_16_times_the_small_one(cases, host):
         hs, hl = host("small", name), host("large", name)
         for stage, at in (("split_words", 1), ("lattice_decode_words", 3), ("lattice_match_words", 2), ("lattice_match_tracks", 3)):          # part slots
             assert len(hl[stage][at]) >= 16 * max(1, len(hs[stage][at])), (name, stage)
+    hs, hl = host("small", "one"), host("large", "one")
+    for stage in STAGES[11:]:                                  # every table of the five newer stages: words, tracks, member slots, parts, lines, rows
+        for at, (a, b) in enumerate(zip(hs[stage], hl[stage])):
+            assert len(b) >= 16 * max(1, len(a)), (stage, at)
 
 
 @pytest.mark.parametrize("name", ["one", "big"])
@@ -196,6 +240,52 @@ def test_the_large_case_has_no_empty_record(cases, host, name):
     assert (lmem["n_parts"] + lmem["n_ins"] > 0).all() and (lsrc[:, 0] != 255).all()
 
 
+def test_the_small_margin_track_and_line_cases_are_the_constant_records(cases, host):
+    """Which records of the five newer stages' small case no input decides, and that the ordinary ones beside them are live."""
+    h, c = host("small", "one"), cases["small"]
+    check_small_margins(h)
+    wg, lg = tuples(h["word_margins"][0]), tuples(h["lattice_margins"][0])
+    assert all(m[0] >= 0 and 0 <= m[1] < n for m, n in zip(wg[2:], (9, 4, 3))) and all(m[0] >= 0 and m[7] > 0 for m in lg[3:])          # 9 runs: decoded by its rows, not by its lattice
+    assert lg[3][4] >= 0 and lg[4][4] >= 0                     # ... and a cut margin in both ordinary words
+    r = c["rows"]
+    assert r["ltd_tracks"] == r["tracks"] + [[0, 0]] and r["ltd"][0].tolist() == [0, 2, 6, 10, 14] and len(r["ltd"][2]) == 18
+    rec, ch, mem, src, parts = h["lattice_decode_tracks"]
+    assert int(rec[2]["cost"]) >= 0 and int(rec[2]["n_used"]) == 2 and (ch[2, :int(rec[2]["n_chars"])] != 255).all() and (mem["cost"][[6, 7]] >= 0).all() and len(parts) > 0
+    L = c["lines"]
+    assert L["n_of"].tolist() == [0, RC.LINE_MAX + 1, 3] and L["first"].tolist() == [0, 0, RC.LINE_MAX + 1 + RC.GAP] and len(L["costs"]) == RC.LINE_MAX + 1 + 3 + 2 * RC.GAP
+    assert L["no_line"].tolist() == [1025, 1026, 1030, 1031] and (L["gaps"][L["no_line"]] == (0, 255)).all()
+    dec, lch, lsrc, wor = h["decode_lines"]
+    assert int(dec[0]["cost"]) == int(cases["B"][65, 65]) and tuples(dec)[2][0] >= 0 and tuples(dec)[2][3] == 3 and (wor[1027:1030] >= 0).all() and lch[3 * 1027] != 255
+    lm = tuples(h["line_margins"][0])
+    assert lm[2][0] >= 0 and (h["line_margins"][1][1027:1030] >= 0).all() and (h["line_margins"][4][1028:1030] >= 0).all()
+
+
+def test_the_large_margin_track_and_line_cases_have_no_empty_record(cases, host):
+    h, c = host("large", "one"), cases["large"]
+    wg, wrm, wrr, wra = h["word_margins"]
+    n_of = c["rows"]["n_of"]
+    assert (wg["margin"] >= 0).all() and all((wrm[w, :k] >= 0).all() and (wrr[w, :k] != 255).all() and (wra[w, :k] != 255).all() for w, k in enumerate(n_of))
+    lg = h["lattice_margins"]
+    ld = h["lattice_decode_words"][0]
+    assert (lg[0]["read_margin"] >= 0).all() and (lg[0]["cut_margin"] >= 0).all() and (lg[0]["n_edges"] > 0).all()          # (a cut run in every word)
+    assert all((lg[1][w, :k] >= 0).all() and (lg[3][w, :k] != 255).all() and (lg[4][w, :k] != 255).all() for w, k in enumerate(ld["n_parts"]))
+    r = c["rows"]
+    tf, tc, slots = r["ltd"]
+    assert r["ltd_tracks"][:len(r["tracks"])] == r["tracks"] and len(tf) == len(r["tracks"]) + 32 and tc.sum() == len(slots) and (tc >= 1).all()          # every slot in a track
+    rec, ch, mem, src, parts = h["lattice_decode_tracks"]
+    assert (rec["cost"] >= 0).all() and (rec["n_used"] == tc).all() and (mem["cost"] >= 0).all() and (mem["word"] == slots).all() and (mem["n_parts"] + mem["n_ins"] > 0).all()
+    assert (ch[:, 0] != 255).all() and (src[:, 0] != 255).all()
+    L = c["lines"]
+    assert len(L["no_line"]) == 0 and (L["n_of"] >= 1).all() and (L["n_of"][:17] == RC.LINE_MAX).all() and int(L["n_of"].sum()) == len(L["costs"])
+    dec, lch, lsrc, wor = h["decode_lines"]
+    assert (dec["cost"] >= 0).all() and (dec["n_sub"] == L["n_of"]).all() and (wor >= 0).all() and int(dec["n_breaks"].sum()) > 0          # (INS / DEL are off: a character a row)
+    assert (lch.reshape(-1, 3)[:, 0][L["first"]] != 255).all() and (lsrc.reshape(-1, 3)[:, 0][L["first"]] != 0xFFFF).all()
+    lm, rm, rr, ra, gm, gv = h["line_margins"]
+    inner = np.setdiff1d(np.arange(len(rm)), L["first"])                 # (the first row of a line has no gap)
+    assert (lm["margin"] >= 0).all() and (rm >= 0).all() and (rr != 255).all() and (ra != 255).all() and (gm[inner] >= 0).all() and (gv[inner] != 255).all()
+    assert (lm["gap_margin"][L["n_of"] >= 2] >= 0).all()
+
+
 def test_the_footprints(cases):
     small, large = cases["small"]["feet"], cases["large"]["feet"]
     tabs, splits, pieces, _ = RS.tables(small["items"])
@@ -226,6 +316,14 @@ def run_stage(f, name, c):
         return f.decode_words(*rows)
     if name == "decode_tracks":
         return f.decode_tracks(*c["td"]["packed"])
+    if name == "word_margins":
+        return f.word_margins(*rows)[:4]
+    if name == "lattice_margins":
+        return f.lattice_margins(*lat)[:6]
+    if name == "lattice_decode_tracks":
+        return f.lattice_decode_tracks(*lat, *c["rows"]["ltd"])
+    if name in ("decode_lines", "line_margins"):
+        return getattr(f, name)(*_lines(c))
     if name in ("match_tracks", "lattice_match_tracks"):
         return getattr(f, name)(*(rows if name == "match_tracks" else lat), *tr)
     return getattr(f, name)(*lat)
@@ -244,6 +342,7 @@ def same(got, want, what):
 def check_round(out, want, fresh, c, what):
     """A round against the host entry points (want), line_words_ref and the brand-new context's feet_read / feet_split (fresh)."""
     for name in STAGES[3:]:
+        assert all(a is not None for a in want[name]), name
         same(out[name], want[name], (what, name))
     for table, a, b in zip(("line_words", "line_runs", "words"), LW.as_lists(*out["feet_words"]), LW.tables(c["feet"]["items"])):
         assert a == b, (what, "feet_words", table)
@@ -294,6 +393,38 @@ def check_small_constants(out):
     assert (ch[:3] == 255).all(), "decode_tracks: the label bytes of an undecoded track"
     for i in (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 13, 14):
         assert int(tmc[i]) == -1, ("decode_tracks: member_cost", i)
+    check_small_margins(out)
+
+
+def check_small_margins(out):
+    """... and those of the margins, the lattice track decode and the lines."""
+    wg, wrm, wrr, wra = out["word_margins"]
+    runs = [0, 33, 9, 4, 3]
+    for w in (0, 1):
+        assert tuples(wg)[w] == NO_MARGIN, ("word_margins", w)
+    for w, n in enumerate(runs):          # the rows a word does not have, and every row of a word that is not decoded
+        k = n if n <= 32 and w >= 2 else 0
+        assert (wrm[w, k:] == -1).all() and (wrr[w, k:] == 255).all() and (wra[w, k:] == 255).all(), ("word_margins: rows", w)
+    lg = out["lattice_margins"]
+    for w in (0, 1, 2):
+        assert tuples(lg[0])[w] == NO_LATTICE_MARGIN, ("lattice_margins", w)
+        assert all((t[w] == -1).all() for t in lg[1:3]) and all((t[w] == 255).all() for t in lg[3:]), ("lattice_margins: parts", w)
+    rec, ch, mem, src, parts = out["lattice_decode_tracks"]
+    assert TD.as_tuples(rec)[:2] == [TD.NOT_DECODED] * 2 and TD.as_tuples(rec)[3:] == [TD.NOT_DECODED, (-1, -1, 0, 0, 0, 2, -1, -1)]          # none, unusable, (ordinary,) unusable, no seeds
+    assert (ch[[0, 1, 3, 4]] == 255).all(), "lattice_decode_tracks: the label bytes of an undecoded track"
+    in_track = {2: 1, 3: 1, 6: 3, 7: 4, 10: 2, 11: 2, 14: 0, 15: 0}
+    for i in range(18):
+        if i not in (6, 7):
+            m = tuples(mem)[i]
+            assert (m[0],) + m[2:5] == NO_MEMBER and m[5] == in_track.get(i, -1) and (src[i] == 255).all(), ("lattice_decode_tracks: member", i)
+    assert len(parts) == int(mem[6]["n_parts"]) + int(mem[7]["n_parts"])
+    dec, lch, lsrc, wor = out["decode_lines"]
+    assert tuples(dec)[1] == NO_LINE and tuples(dec)[0][1:] == NO_LINE[1:], "decode_lines: the line of 1025 rows and the line without rows"
+    nowhere = list(range(RC.LINE_MAX + 1 + RC.GAP)) + [len(wor) - 2, len(wor) - 1]          # the rows of the undecoded line and of no line
+    assert (wor[nowhere] == -1).all() and (lch.reshape(-1, 3)[nowhere] == 255).all() and (lsrc.reshape(-1, 3)[nowhere] == 0xFFFF).all(), "decode_lines: rows"
+    lm, rm, rr, ra, gm, gv = out["line_margins"]
+    assert tuples(lm)[:2] == [NO_LINE_MARGIN] * 2, "line_margins: the line without rows and the line of 1025 rows"
+    assert (rm[nowhere] == -1).all() and (gm[nowhere] == -1).all() and (rr[nowhere] == 255).all() and (ra[nowhere] == 255).all() and (gv[nowhere] == 255).all(), "line_margins: rows"
 
 
 class Pools:
@@ -349,7 +480,9 @@ class Pools:
 
 def stats(f, pools):
     return {"run_atlas_stats": f.run_atlas_stats(), "run_split_stats": f.run_split_stats(), "lattice_decode_stats": (f.lattice_decode_stats(),),
-            "lattice_match_stats": (f.lattice_match_stats(),), "lattice_track_stats": (f.lattice_track_stats(),), "pool device_bytes": pools.bytes()}
+            "lattice_match_stats": (f.lattice_match_stats(),), "lattice_track_stats": (f.lattice_track_stats(),), "pool device_bytes": pools.bytes(),
+            "lattice_track_decode_stats": (f.lattice_track_decode_stats(),), "line_decode_stats": (f.line_decode_stats()["table_bytes"],),
+            "line_margin_stats": (f.line_margin_stats()["table_bytes"],)}
 
 
 @pytest.mark.gpu
@@ -445,6 +578,7 @@ def test_the_fused_call_and_the_single_stage_calls_take_turns(S, cascade_paths, 
         g.set_word_decode(DEC_INS, DEC_DEL)
         g.set_lexicon(words, fold_case=True)
         g.set_word_match(INS, DEL, BAND)
+        g.set_word_margin(True); g.set_lattice_margin(True); g.set_lattice_track_decode(True); g.set_line_decode(True); g.set_line_margin(True)
         return g
 
     busy = np.stack([uniform[0], uniform[0]])                  # the S-text frame of seed 2, twice: the word tracks have two members
@@ -460,6 +594,8 @@ def test_the_fused_call_and_the_single_stage_calls_take_turns(S, cascade_paths, 
         one = tables_of(f.text_detect(busy, GROUPED, **FUSED))
         assert len(one["word_tracks"]) > 0 and int(one["word_tracks"]["count"].max()) >= 2 and (one["run_splits"]["n_cuts"] > 0).any()          # the scene's conditions
         assert (one["lattice_track_members"]["n_parts"] > 0).any() and (one["track_decodes"]["cost"] >= 0).any() and len(one["split_parts"]) > len(one["line_runs"])
+        assert (one["word_margins"]["margin"] >= 0).any() and (one["lattice_margins"]["cut_margin"] >= 0).any() and (one["lattice_track_decodes"]["cost"] >= 0).any()
+        assert (one["line_decodes"]["n_breaks"] > 0).any() and (one["line_margins"]["margin"] >= 0).any() and len(one["line_decode_word_of_row"]) == len(one["split_parts"])
         blank = tables_of(f.text_detect(np.full((480, 640, 3), 128, np.uint8), GROUPED, **FUSED))
         for k in READING_TABLES:
             assert len(blank[k]) == 0, k
