@@ -822,7 +822,9 @@ typedef struct str_er_word_margin {
  *     (0, 255) as well.
  *   Limits: one path per line, no margins in this record: how firmly its readings and breaks hold is str_er_line_margin's to say.
  *     The segmentation of the runs themselves is the fixed one of the decoder's window: joint decoding over the piece lattice is not
- *     part of this.  No tracks, no pool.  Nothing is calibrated: the weight is the caller's.
+ *     part of this.  The cuts of touching glyphs chosen together with the word breaks over the runs' piece lattices are a separate
+ *     output, str_er_line_lattice_decode (str_er_lattice_decode_lines).  No tracks, no pool.  Nothing is calibrated: the weight is
+ *     the caller's.
  *   In a detect call the rows are the decoder's: the runs of the line, and with STR_ER_WANT_RUN_SPLIT the parts of its words in word
  *     order (the rows of str_er_result_split_parts(); the windows then index that table, and the line is decoded behind a second wait,
  *     once the parts are known).  A line's window runs from the first row of its first word to the last row of its last word.       */
@@ -1023,13 +1025,66 @@ typedef struct str_er_word_split {
  *   Limits: the lattice is that of str_er_run_split (at most 3 upright cuts a run); one path per word -- how far the next reading
  *     and the next cut of every part lie from it is a separate output, str_er_lattice_margin (str_er_set_lattice_margin); no lexicon
  *     enters here: the lexicon over the same lattice is a separate output, str_er_lattice_match (STR_ER_WANT_LATTICE_MATCH), while
- *     str_er_word_match still reads the split sequence of str_er_run_split.                                                            */
+ *     str_er_word_match still reads the split sequence of str_er_run_split.  A word is what the word gap made of the line before any
+ *     table was asked: the cuts chosen together with the word breaks of the line are a separate output, str_er_line_lattice_decode
+ *     (str_er_lattice_decode_lines).                                                                                                   */
 typedef struct str_er_lattice_decode {
     int32_t  cost, read_cost;             /*  0,  4                                   */
     int32_t  n_chars, n_sub;              /*  8, 12                                   */
     int32_t  n_del, n_ins;                /* 16, 20                                   */
     int32_t  first_part, n_parts;         /* 24, 28: into the lattice part table      */
 } str_er_lattice_decode;     /* 32 bytes; one per word                                */
+
+/* The joint decode of a text line over the piece lattices of its runs (str_er_lattice_decode_lines), here called
+ * str_er_line_lattice_decode: one Viterbi pass per line over the atoms' ends of all its runs, under the table of str_er_word_decode.
+ * The cuts of touching glyphs, the word breaks and the string come out together: inside a run it takes the edges of
+ * str_er_lattice_decode, between two runs the gap step of str_er_line_decode.  A definition of this library; integers only, exact, and
+ * the host states the same rules (str_er_lattice_decode_lines_host).
+ *   Inputs: symbols, the table B (66 x 66, E = 65), INS, DEL, INF = 2^20, the unfolded 65-byte rows of runs and pieces and SPLIT are
+ *     those of str_er_lattice_decode.  The gap pairs (J, K), 255 meaning the move is off, are those of str_er_line_decode, but here
+ *     there is one pair per run, for the gap in front of it: the pair of a line's first run is ignored, and a pair of a later run of a
+ *     line with both moves off is STR_ER_EINVAL.
+ *   Nodes: the atoms' ends of the runs of the line, in order.  Run r has A_r = n_cuts + 1 <= 4 atoms and the local nodes 0 .. A_r; the
+ *     line's nodes are 0 .. N, N = sum of A_r, off_r = sum of A_r' over the line's runs r' < r.  A line of more than 1024 runs is not
+ *     decoded: cost = -1, the counts 0, labels 0xFF, sources 0xFFFF, no parts.  So a decoded line has at most 4096 nodes.
+ *   Recurrence, in int32: V_0 is that of str_er_line_decode (V_0[E] = 0, INF elsewhere).  For every run of the line in turn:
+ *     Gap step, for every run but the first, on V at the run's local node 0 (node off_r): exactly the gap step of str_er_line_decode.
+ *     W[a] = V[a] + J for all a, or INF exactly if J is off; if K is on, X = min over a in 0 .. 65 of (V[a] + B[a][E]) + K at the
+ *     smallest a, and if X < W[E] then W[E] = X and the gap breaks: the comparison is strict, on a tie the join stays; a break from
+ *     a = E is allowed.  W replaces V at that node: no edge crosses a run boundary, so V before the gap has no other reader.
+ *     Node step, for the local nodes j = 1 .. A_r: exactly the step of str_er_lattice_decode at n = off_r + j, with the edges (i, j),
+ *     i < j, from the gapped local node 0 and the later local nodes; the row of an edge is that of the piece (i, j) in the order of
+ *     str_er_run_split, the run's own row for (0, A_r); SPLIT is added where i > 0; SUB over the predecessors 0 .. 65 with U[E] = INF,
+ *     DEL costs V_i[a] + DEL + s; on equal values the smaller i wins, then SUB before DEL, then the smallest a; then INS over b < 65
+ *     on a strict comparison.  cost = min over a of V_N[a] + B[a][E] at the smallest a; a line without runs costs B[E][E].
+ *   Bounds: the path that takes every run whole and reads it is a path of str_er_line_decode on 1024 rows, 510 + 1019 * 1023 + 255 =
+ *     1 043 202 < 2^20 at the most, so INF is never the minimum; every value stays below 2^20 + 4096 * (509 + 510 + 255 + 510) + 255 =
+ *     8 356 095 < 2^25.
+ *   Backtrack from the end state by the recorded moves as in str_er_lattice_decode, per node, a SUB or DEL step from the local node i
+ *     going to the node off_r + i; where that is local node 0 of a run but the line's first, the state is E and the gap broke, a blank
+ *     is emitted and the state becomes the break's predecessor (the check of str_er_line_decode).
+ *   Outputs: one record per line; n_sub + n_ins + n_breaks = n_chars and n_sub + n_del = n_parts, runs of the line <= n_parts <= N.
+ *     Labels (uint8, 65 = blank) and sources (uint16) lie in a slice of 3 entries per node at the line's node slot -- the number of
+ *     atoms of all runs before the line's first run, so the slice begins at entry 3 * slot -- padded with 0xFF / 0xFFFF; a line emits
+ *     at most 2 * n_parts + runs - 1 <= 3N - 1 entries.  A source is the line-relative index p of a part: p for the character read
+ *     from it, p | 0x8000 for a character inserted behind it, p | 0x4000 for the blank in front of it.  The parts are
+ *     str_er_split_part {run, piece} in line order, the lines' back to back (first_part, n_parts); with them one int32 per part,
+ *     word_of_part: the number of breaks before it, or -1 for a dropped part.
+ *   It follows: (1) if no run has a cut, cost, labels, sources and word indices equal str_er_line_decode's on the runs' rows and the
+ *     same pairs, byte for byte; (2) with the pair (0, off) at every gap and at most 32 atoms, cost, labels, parts and counts equal
+ *     str_er_lattice_decode's on the same word; (3) with (0, off) inside the words of a segmentation into words of at most 32 atoms
+ *     and (off, k) at its word gaps, cost = the sum of those words' str_er_lattice_decode costs + the sum of k, the labels are the
+ *     words' joined by one 65 and the parts their concatenation, for any table, B[E][E] != 0 included; (4) for any gap costs with
+ *     both moves on, cost <= the str_er_line_decode cost on the runs' rows; (5) cost <= the str_er_line_decode cost over the parts of
+ *     str_er_run_split on the same rows (gaps inside a run (0, 255)) + SPLIT * (those parts - runs): both are paths of this decoder.
+ *   Limits: one path per line; no margins, tracks, pool or lexicon for it; the weight of the gap costs is not calibrated; the lattice
+ *     is that of str_er_run_split (at most 3 upright cuts a run).                                                                     */
+typedef struct str_er_line_lattice_decode {
+    int32_t  cost, n_chars;               /*  0,  4                                   */
+    int32_t  n_breaks, n_sub;             /*  8, 12                                   */
+    int32_t  n_del, n_ins;                /* 16, 20                                   */
+    int32_t  first_part, n_parts;         /* 24, 28: into the line lattice part table */
+} str_er_line_lattice_decode; /* 32 bytes; one per line                               */
 
 /* The margins of a word decoded over its lattice (str_er_set_lattice_margin beside STR_ER_WANT_LATTICE_DECODE, str_er_lattice_margins):
  * the min-marginals of the recurrence of str_er_lattice_decode -- for every edge of the word's lattice and every reading of it the cost
@@ -1735,6 +1790,34 @@ int str_er_lattice_margins_host(const str_er_run_split *splits, int32_t n_runs, 
 /* Statistics of the buffer of STR_ER_WANT_LATTICE_DECODE / str_er_lattice_decode_words: the bytes of its tables on the device (0: never
  * made).  The pointer may be NULL.                                                                                                  */
 int str_er_lattice_decode_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
+/* Whether a detect call with STR_ER_WANT_LATTICE_DECODE also decodes every line of str_er_result_texts() over the piece lattices of
+ * its runs (str_er_line_lattice_decode), and the weight (0 .. 127) of its gap costs: on != 0 switches it on; off by default, the
+ * weight 16.  A weight outside 0 .. 127 -> STR_ER_EINVAL, the context unchanged.  A context setting, not a stage flag: without
+ * STR_ER_WANT_LATTICE_DECODE (and STR_ER_WANT_RUN_SPLIT, which it needs) it does nothing, and while it is off no call enqueues,
+ * uploads or allocates anything more than before.  A stream's contexts: str_er_stream_context.                                       */
+int str_er_set_line_lattice_decode(str_er_ctx *ctx, int32_t on, int32_t weight);
+/* The joint decode of lines over their runs' piece lattices (str_er_line_lattice_decode) on the caller's rows, on the GPU, with the
+ * context's table, INS / DEL (str_er_set_word_decode) and SPLIT (str_er_set_run_split): splits, the rows and n_pieces are those of
+ * str_er_lattice_decode_words; gaps holds 2 * n_runs bytes, (J, K) per run; line t has the runs first_run[t] .. first_run[t] +
+ * n_runs_of_line[t], the windows in ascending order and none over another (every line writes its own slices).  With S the sum of
+ * n_cuts + 1 over all n_runs runs: dec receives n_lines records, chars 3 * S bytes and src 3 * S uint16 (0xFF / 0xFFFF in no line's
+ * slice), parts and word_of_part the parts of the lines back to back in line order and *n_parts their number.  cap_parts too small
+ * -> STR_ER_ECAPACITY, *n_parts still set (it is at most the sum over the lines' runs of n_cuts + 1) and nothing else written.
+ * STR_ER_ESTATE without a table; STR_ER_EINVAL on NULL arguments, a record with cuts or pieces that are none, a window outside the
+ * runs or out of order, or a gap of a line with both moves off; the context stays usable.  n_lines = 0 is fine.  It needs no model. */
+int str_er_lattice_decode_lines(str_er_ctx *ctx, const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs,
+                                int32_t n_pieces, const uint8_t *gaps, const int32_t *first_run, const int32_t *n_runs_of_line, int32_t n_lines,
+                                str_er_line_lattice_decode *dec, uint8_t *chars, uint16_t *src, str_er_split_part *parts, int32_t cap_parts,
+                                int32_t *n_parts, int32_t *word_of_part);
+/* The same rules on one host thread, with SPLIT, the table and INS / DEL as arguments (with the checks of str_er_set_run_split and
+ * str_er_set_word_decode).  Pure: no context, no GPU.                                                                              */
+int str_er_lattice_decode_lines_host(const str_er_run_split *splits, int32_t n_runs, const uint8_t *run_costs, const uint8_t *piece_costs, int32_t n_pieces,
+                                     const uint8_t *gaps, const int32_t *first_run, const int32_t *n_runs_of_line, int32_t n_lines, int32_t split_cost,
+                                     const uint8_t *bigram, int32_t ins, int32_t del, str_er_line_lattice_decode *dec, uint8_t *chars, uint16_t *src,
+                                     str_er_split_part *parts, int32_t cap_parts, int32_t *n_parts, int32_t *word_of_part);
+/* The bytes of the line lattice decoder's back-pointer table on the device (68 uint32 per node of the largest call so far; 0 before
+ * the first).  The pointer may be NULL.                                                                                            */
+int str_er_line_lattice_decode_stats(const str_er_ctx *ctx, uint64_t *table_bytes);
 
 /* The lexicon match over the piece lattice (str_er_lattice_match) of n_words words on the caller's rows, on the GPU, with the context's
  * lexicon (str_er_set_lexicon), INS / DEL / band (str_er_set_word_match) and SPLIT (str_er_set_run_split): the arguments up to n_words,
@@ -2175,6 +2258,21 @@ const str_er_word_split  *str_er_result_word_splits(const str_er_result *r, int3
  * bytes per word, and the lattice parts of the words back to back in word order.  Each returns NULL and 0 without the flag; a call
  * without words returns empty arrays (not NULL).                                                                                   */
 const str_er_lattice_decode *str_er_result_lattice_decodes(const str_er_result *r, int32_t *n);
+/* With STR_ER_WANT_LATTICE_DECODE on a context whose str_er_set_line_lattice_decode is on (str_er_line_lattice_decode): one record per
+ * line of str_er_result_texts(); with S the sum of n_cuts + 1 over str_er_result_run_splits(), 3 * S label bytes and 3 * S uint16
+ * sources, a line's slice at 3 * (the atoms of all runs before its first run); the lines' parts back to back (first_part, n_parts)
+ * with the indices of str_er_result_split_parts() and one int32 per part, the number of breaks before it (-1: dropped); the gap
+ * costs used, 2 bytes per run of str_er_result_line_runs() (str_er_line_gap_costs on the runs, row_run == NULL, at the setting's
+ * weight); and the lines' windows into the runs, (first run, run count) per line.  In a detect call a line's window runs from the
+ * first run of its first word to the last run of its last word; the kernel follows the lattice decode on the same stream and its
+ * tables come down with the stage's one wait.  NULL (and 0) without the flag or the setting.                                         */
+const str_er_line_lattice_decode *str_er_result_line_lattice_decodes(const str_er_result *r, int32_t *n);
+const uint8_t *str_er_result_line_lattice_chars(const str_er_result *r, uint64_t *n_bytes);
+const uint16_t *str_er_result_line_lattice_src(const str_er_result *r, uint64_t *n);
+const str_er_split_part *str_er_result_line_lattice_parts(const str_er_result *r, int32_t *n);
+const int32_t *str_er_result_line_lattice_word_of_part(const str_er_result *r, uint64_t *n);
+const uint8_t *str_er_result_line_lattice_gap_costs(const str_er_result *r, uint64_t *n_bytes);
+const int32_t *str_er_result_line_lattice_windows(const str_er_result *r, uint64_t *n);
 const uint8_t               *str_er_result_lattice_decode_chars(const str_er_result *r, uint64_t *n_bytes);
 const uint8_t               *str_er_result_lattice_decode_src(const str_er_result *r, uint64_t *n_bytes);
 const str_er_split_part     *str_er_result_lattice_parts(const str_er_result *r, int32_t *n);

@@ -22,7 +22,7 @@ from .binding import (  # noqa: F401
     WORD_MARGIN_DTYPE, word_margins_host,
     LINE_DECODE_DTYPE, line_gap_costs, decode_lines_host, LINE_MARGIN_DTYPE, line_margins_host,
     WANT_RUN_SPLIT, RUN_SPLIT_DTYPE, RUN_PIECE_DTYPE, SPLIT_PART_DTYPE, WORD_SPLIT_DTYPE, cuts_from_counts, split_words_host,
-    WANT_LATTICE_DECODE, LATTICE_DECODE_DTYPE, lattice_decode_words_host,
+    WANT_LATTICE_DECODE, LATTICE_DECODE_DTYPE, lattice_decode_words_host, LINE_LATTICE_DECODE_DTYPE, lattice_decode_lines_host, line_lattice_node_slots,
     LATTICE_MARGIN_DTYPE, lattice_margins_host,
     WANT_LATTICE_MATCH, LATTICE_MATCH_DTYPE, lattice_match_words_host,
     WANT_LATTICE_TRACK, LATTICE_TRACK_MEMBER_DTYPE, lattice_match_tracks_host,

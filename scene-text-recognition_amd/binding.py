@@ -163,6 +163,9 @@ assert RUN_SPLIT_DTYPE.itemsize == 32 and RUN_PIECE_DTYPE.itemsize == 32 and SPL
 LATTICE_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("read_cost", "<i4"), ("n_chars", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4"),
                                  ("first_part", "<i4"), ("n_parts", "<i4")])
 assert LATTICE_DECODE_DTYPE.itemsize == 32
+LINE_LATTICE_DECODE_DTYPE = np.dtype([("cost", "<i4"), ("n_chars", "<i4"), ("n_breaks", "<i4"), ("n_sub", "<i4"), ("n_del", "<i4"), ("n_ins", "<i4"),
+                                      ("first_part", "<i4"), ("n_parts", "<i4")])
+assert LINE_LATTICE_DECODE_DTYPE.itemsize == 32
 # str_er_lattice_margin: per word, the smallest reading margin of its lattice parts with the part, its decoded reading and the
 # alternative (65: the part dropped); the smallest cut margin with the part and the other edge (i | j << 4) -- all three -1 where no
 # run of the word is cut; the edges of the lattice.  All -1 (n_edges 0): not decoded or no runs
@@ -560,6 +563,18 @@ def load_library():
     L.str_er_lattice_match_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
                                                   C.c_int32, vp, vp, vp, C.c_int32, i32p]
     L.str_er_lattice_decode_words.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, i32p]
+    L.str_er_lattice_decode_lines.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.c_int32, i32p, vp]
+    L.str_er_lattice_decode_lines_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp,
+                                                   C.c_int32, i32p, vp]
+    L.str_er_line_lattice_decode_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.str_er_set_line_lattice_decode.argtypes = [vp, C.c_int32, C.c_int32]
+    for fn in (L.str_er_result_line_lattice_decodes, L.str_er_result_line_lattice_parts):
+        fn.argtypes = [vp, i32p]
+        fn.restype = vp
+    for fn in (L.str_er_result_line_lattice_chars, L.str_er_result_line_lattice_src, L.str_er_result_line_lattice_word_of_part, L.str_er_result_line_lattice_gap_costs,
+               L.str_er_result_line_lattice_windows):
+        fn.argtypes = [vp, C.POINTER(C.c_uint64)]
+        fn.restype = vp
     L.str_er_lattice_decode_words_host.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, vp, vp, vp, vp,
                                                    C.c_int32, i32p]
     L.str_er_set_run_split.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
@@ -813,6 +828,11 @@ class Result:
     def _line_decode_table(self, table):
         if table is None:
             raise ValueError("the result has no line decodes (ERFilter.set_line_decode(True) and WANT_WORD_DECODE / want_word_decode=True)")
+        return table
+
+    def _line_lattice_table(self, table):
+        if table is None:
+            raise ValueError("the result has no line lattice decodes (ERFilter.set_line_lattice_decode(True) and WANT_LATTICE_DECODE / want_lattice_decode=True)")
         return table
 
     def _line_margin_table(self, table):
@@ -1170,6 +1190,85 @@ class Result:
                 x0, y0, x1, y1 = int(q["x0"]), int(q["y0"]), int(q["x1"]), int(q["y1"])
                 boxes[-1] = (x0, y0, x1, y1) if b is None else (min(b[0], x0), min(b[1], y0), max(b[2], x1), max(b[3], y1))
         return [(s, None if b is None else (b[0], b[1], b[2] - b[0], b[3] - b[1])) for s, b in zip(texts, boxes)]
+
+    @property
+    def line_lattice_decodes(self) -> np.ndarray:
+        """With set_line_lattice_decode(True) and WANT_LATTICE_DECODE: LINE_LATTICE_DECODE_DTYPE per line of texts, in the same order."""
+        return self._line_lattice_table(getattr(self, "_line_lattice_decodes", None))
+
+    @property
+    def line_lattice_chars(self) -> np.ndarray:
+        """With set_line_lattice_decode(True): (3 x atoms of run_splits) uint8, the labels of every line's string (65: a blank) from entry
+        3 * (the atoms of the runs before the first run of its window) on, 0xFF past n_chars."""
+        return self._line_lattice_table(getattr(self, "_line_lattice_chars", None))
+
+    @property
+    def line_lattice_src(self) -> np.ndarray:
+        """With set_line_lattice_decode(True): (3 x atoms) uint16, per label the line-relative part it came from, 0x8000 set on an
+        inserted character and 0x4000 on the break in front of that part; 0xFFFF past n_chars."""
+        return self._line_lattice_table(getattr(self, "_line_lattice_src", None))
+
+    @property
+    def line_lattice_parts(self) -> np.ndarray:
+        """With set_line_lattice_decode(True): SPLIT_PART_DTYPE, the parts of the lines' paths back to back (first_part, n_parts of the
+        records), with the indices of run_pieces."""
+        return self._line_lattice_table(getattr(self, "_line_lattice_parts", None))
+
+    @property
+    def line_lattice_word_of_part(self) -> np.ndarray:
+        """With set_line_lattice_decode(True): int32 per part, the decoded word of its line it is read in, -1 for a dropped part."""
+        return self._line_lattice_table(getattr(self, "_line_lattice_word_of_part", None))
+
+    @property
+    def line_lattice_gap_costs(self) -> np.ndarray:
+        """With set_line_lattice_decode(True): (n runs, 2) uint8, the (join, break) costs of the gap in front of every run of line_runs."""
+        return self._line_lattice_table(getattr(self, "_line_lattice_gap_costs", None))
+
+    @property
+    def line_lattice_windows(self) -> np.ndarray:
+        """With set_line_lattice_decode(True): (n lines, 2) int32, the first run and the run count of every line."""
+        return self._line_lattice_table(getattr(self, "_line_lattice_windows", None))
+
+    def _line_lattice_slice(self, t: int):
+        d, first = self.line_lattice_decodes[t], int(self.line_lattice_windows[t, 0])
+        at = 3 * int(line_lattice_node_slots(self.run_splits, [first])[0]) if len(self.run_splits) else 0
+        n = max(0, int(d["n_chars"]))
+        return d, self.line_lattice_chars[at:at + n], self.line_lattice_src[at:at + n]
+
+    def line_lattice_text(self, t: int) -> str:
+        """With set_line_lattice_decode(True): the decoded string of line t, a blank per break (consecutive blanks are kept); for a
+        line that was not decoded (cost < 0) its words' lattice strings joined by one blank."""
+        d, lab, src = self._line_lattice_slice(t)
+        if int(d["cost"]) < 0:
+            return " ".join(self.words_lattice_text_of_line(t))
+        return "".join(" " if int(a) == 65 else _OCR_ALPHABET[int(a)] for a in lab)
+
+    def frame_line_line_lattice_text(self, i: int) -> str:
+        """With set_line_lattice_decode(True): line_lattice_text of the representative line of frame line i."""
+        return self.line_lattice_text(int(self.frame_lines[i]["rep"]))
+
+    def line_lattice_words(self, t: int) -> list:
+        """With set_line_lattice_decode(True): the words of line t under the decoded cuts and breaks, empty ones included: per word
+        (text, its parts as SPLIT_PART_DTYPE, (x, y, w, h) the union of the boxes of its parts that are read -- a piece's box, a whole
+        run's -- or None for a word without one).  A line that was not decoded has no words here."""
+        d, lab, src = self._line_lattice_slice(t)
+        if int(d["cost"]) < 0:
+            return []
+        parts = self.line_lattice_parts[int(d["first_part"]):int(d["first_part"]) + int(d["n_parts"])]
+        texts, boxes, own = [""], [None], [[]]
+        for a, v in zip(lab, src):
+            if int(a) == 65:
+                texts.append(""); boxes.append(None); own.append([])
+                continue
+            texts[-1] += _OCR_ALPHABET[int(a)]
+            if not int(v) & 0x8000:
+                k = int(v) & 0x3FFF
+                own[-1].append(k)
+                q = self.line_runs[int(parts[k]["run"])] if int(parts[k]["piece"]) < 0 else self.run_pieces[int(parts[k]["piece"])]
+                b = boxes[-1]
+                x0, y0, x1, y1 = int(q["x0"]), int(q["y0"]), int(q["x1"]), int(q["y1"])
+                boxes[-1] = (x0, y0, x1, y1) if b is None else (min(b[0], x0), min(b[1], y0), max(b[2], x1), max(b[3], y1))
+        return [(s, parts[np.asarray(ks, np.int64)], None if b is None else (b[0], b[1], b[2] - b[0], b[3] - b[1])) for s, ks, b in zip(texts, own, boxes)]
 
     @property
     def word_margins(self) -> np.ndarray:
@@ -1766,6 +1865,14 @@ class ERFilter:
                                     res._lattice_decode_chars = table(L.str_er_result_lattice_decode_chars, np.uint8, n64).reshape(-1, 64)
                                     res._lattice_decode_src = table(L.str_er_result_lattice_decode_src, np.uint8, n64).reshape(-1, 64)
                                     res._lattice_parts = table(L.str_er_result_lattice_parts, SPLIT_PART_DTYPE)
+                                    res._line_lattice_decodes = table(L.str_er_result_line_lattice_decodes, LINE_LATTICE_DECODE_DTYPE)
+                                    if res._line_lattice_decodes is not None:
+                                        res._line_lattice_chars = table(L.str_er_result_line_lattice_chars, np.uint8, n64)
+                                        res._line_lattice_src = table(L.str_er_result_line_lattice_src, np.uint16, n64)
+                                        res._line_lattice_parts = table(L.str_er_result_line_lattice_parts, SPLIT_PART_DTYPE)
+                                        res._line_lattice_word_of_part = table(L.str_er_result_line_lattice_word_of_part, np.int32, n64)
+                                        res._line_lattice_gap_costs = table(L.str_er_result_line_lattice_gap_costs, np.uint8, n64).reshape(-1, 2)
+                                        res._line_lattice_windows = table(L.str_er_result_line_lattice_windows, np.int32, n64).reshape(-1, 2)
                                     res._lattice_margins = table(L.str_er_result_lattice_margins, LATTICE_MARGIN_DTYPE)
                                     if res._lattice_margins is not None:
                                         res._lattice_read_margins = table(L.str_er_result_lattice_read_margins, np.uint8, n64).view(np.int32).reshape(-1, 32)
@@ -2504,6 +2611,28 @@ class ERFilter:
         self._check(self.L.str_er_lattice_decode_words(self.h, *a[0], *a[1]))
         return _lattice_out(a)
 
+    def set_line_lattice_decode(self, on: bool = True, weight: int = 16) -> None:
+        """str_er_set_line_lattice_decode: whether a detect call with WANT_LATTICE_DECODE also decodes every line over the piece lattices
+        of its runs, cuts, word breaks and string together (str_er_line_lattice_decode; off by default), and the weight (0 .. 127) of
+        the gap costs."""
+        self._check(self.L.str_er_set_line_lattice_decode(self.h, 1 if on else 0, int(weight)))
+
+    def lattice_decode_lines(self, splits, run_costs, piece_costs, gaps, first_run, n_runs_of_line):
+        """str_er_lattice_decode_lines: the joint decode (str_er_line_lattice_decode) of the lines [first_run[t], first_run[t] +
+        n_runs_of_line[t]) over the pieces of their runs, from the unfolded cost rows of the runs (n runs, 65) and of their pieces
+        (n pieces, 65) and the gap costs (n runs, 2) uint8, under the table of set_bigram with INS / DEL of set_word_decode and SPLIT
+        of set_run_split.  With S the atoms of all runs, returns (LINE_LATTICE_DECODE_DTYPE per line, (3S,) uint8 labels, (3S,) uint16
+        sources, SPLIT_PART_DTYPE parts, int32 word of every part)."""
+        a = _line_lattice_args(splits, run_costs, piece_costs, gaps, first_run, n_runs_of_line)
+        self._check(self.L.str_er_lattice_decode_lines(self.h, *a[0], *a[1]))
+        return _line_lattice_out(a)
+
+    def line_lattice_decode_stats(self) -> dict:
+        """str_er_line_lattice_decode_stats: the bytes of the line lattice decoder's back-pointer table on the device."""
+        by = C.c_uint64()
+        self._check(self.L.str_er_line_lattice_decode_stats(self.h, C.byref(by)))
+        return {"table_bytes": int(by.value)}
+
     def set_lattice_margin(self, on: bool = True) -> None:
         """str_er_set_lattice_margin: whether a detect call with WANT_LATTICE_DECODE also makes the margins of its words (off by default)."""
         self._check(self.L.str_er_set_lattice_margin(self.h, 1 if on else 0))
@@ -3077,6 +3206,50 @@ def lattice_decode_words_host(splits, run_costs, piece_costs, first_run, n_runs_
     if rc != 0:
         raise StrErError(rc, "str_er_lattice_decode_words_host")
     return _lattice_out(a)
+
+
+def _line_lattice_args(splits, run_costs, piece_costs, gaps, first_run, n_runs_of_line):
+    sp = np.ascontiguousarray(splits, dtype=RUN_SPLIT_DTYPE).reshape(-1)
+    rc = np.ascontiguousarray(run_costs, dtype=np.uint8).reshape(-1, 65)
+    pc = np.ascontiguousarray(piece_costs, dtype=np.uint8).reshape(-1, 65)
+    gp = np.ascontiguousarray(gaps, dtype=np.uint8).reshape(-1, 2)
+    fr = np.ascontiguousarray(first_run, dtype=np.int32).reshape(-1)
+    no = np.ascontiguousarray(n_runs_of_line, dtype=np.int32).reshape(-1)
+    if len(sp) != len(rc) or len(gp) != len(rc) or len(fr) != len(no):
+        raise ValueError("splits, run_costs and gaps need one row per run, first_run and n_runs_of_line one entry per line")
+    atoms = int((sp["n_cuts"].astype(np.int64).clip(0, 3) + 1).sum())          # (the slices of all runs; a line has at most as many parts)
+    cap = int(min(atoms, 2 ** 31 - 1))
+    dec = np.zeros(max(1, len(fr)), LINE_LATTICE_DECODE_DTYPE)
+    ch = np.full(max(1, 3 * atoms), 0xFF, np.uint8)
+    sr = np.full(max(1, 3 * atoms), 0xFFFF, np.uint16)
+    parts = np.zeros(max(1, cap), SPLIT_PART_DTYPE)
+    wop = np.full(max(1, cap), -1, np.int32)
+    n = C.c_int32()
+    p = lambda a: _np_ptr(a) if len(a) else None
+    return ((p(sp), len(sp), p(rc), p(pc), len(pc), p(gp), p(fr), p(no), len(fr)), (_np_ptr(dec), _np_ptr(ch), _np_ptr(sr), _np_ptr(parts), cap, C.byref(n), _np_ptr(wop)),
+            (sp, rc, pc, gp, fr, no), dec, ch, sr, parts, wop, n, atoms)
+
+
+def _line_lattice_out(a):
+    nl, atoms, n = len(a[2][4]), a[9], a[8].value
+    return a[3][:nl], a[4][:3 * atoms], a[5][:3 * atoms], a[6][:n].copy(), a[7][:n].copy()
+
+
+def lattice_decode_lines_host(splits, run_costs, piece_costs, gaps, first_run, n_runs_of_line, table, ins: int = 0, dele: int = 0, split_cost: int = 8):
+    """str_er_lattice_decode_lines_host (pure host, one thread): ERFilter.lattice_decode_lines with the table and the parameters as arguments."""
+    a = _line_lattice_args(splits, run_costs, piece_costs, gaps, first_run, n_runs_of_line)
+    tb = _bigram_table(table)
+    rc = load_library().str_er_lattice_decode_lines_host(*a[0], int(split_cost), _np_ptr(tb), int(ins), int(dele), *a[1])
+    if rc != 0:
+        raise StrErError(rc, "str_er_lattice_decode_lines_host")
+    return _line_lattice_out(a)
+
+
+def line_lattice_node_slots(splits, first_run):
+    """The node slot of every line of lattice_decode_lines: the atoms of all runs before its first run (its labels begin at 3 * slot)."""
+    sp = np.ascontiguousarray(splits, dtype=RUN_SPLIT_DTYPE).reshape(-1)
+    at = np.concatenate([[0], np.cumsum(sp["n_cuts"].astype(np.int64).clip(0, 3) + 1)])
+    return at[np.asarray(first_run, np.int64).reshape(-1)]
 
 
 def _lattice_match_args(splits, run_costs, piece_costs, first_run, n_runs_of_word):
@@ -4061,6 +4234,14 @@ class FrameStream:
         for i in range(int(self.L.str_er_stream_depth(self.h))):
             ctx = self.L.str_er_stream_context(self.h, i)
             rc = self.L.str_er_set_line_decode(ctx, 1 if on else 0, int(weight))
+            if rc != 0:
+                raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
+
+    def set_line_lattice_decode(self, on: bool = True, weight: int = 16) -> None:
+        """str_er_set_line_lattice_decode on every context of the stream."""
+        for i in range(int(self.L.str_er_stream_depth(self.h))):
+            ctx = self.L.str_er_stream_context(self.h, i)
+            rc = self.L.str_er_set_line_lattice_decode(ctx, 1 if on else 0, int(weight))
             if rc != 0:
                 raise StrErError(rc, (self.L.str_er_last_error(ctx) or b"").decode())
 

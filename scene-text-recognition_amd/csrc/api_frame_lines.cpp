@@ -747,6 +747,12 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
             out.lattice_margins = &r->lattice_margins; out.lattice_read_margins = &r->lattice_read_margins; out.lattice_cut_margins = &r->lattice_cut_margins;
             out.lattice_part_reads = &r->lattice_part_reads; out.lattice_part_alts = &r->lattice_part_alts; out.lattice_cut_alts = &r->lattice_cut_alts;
         }
+        const bool lldecode = lattice && split && c->ll_on;          // (a context setting, str_er_set_line_lattice_decode: no flag of its own)
+        if (lldecode) {
+            out.ll_decodes = &r->line_lattice_decodes; out.ll_chars = &r->line_lattice_chars; out.ll_src = &r->line_lattice_src; out.ll_parts = &r->line_lattice_parts;
+            out.ll_word_of_part = &r->line_lattice_word_of_part; out.ll_gaps = &r->line_lattice_gap_costs; out.ll_windows = &r->line_lattice_windows;
+            out.n_lines = n_lines; out.line_bee = c->bigram_ee;
+        }
         if (lmatch && split && match) { out.lattice_matches = &r->lattice_matches; out.lattice_match_src = &r->lattice_match_src; out.lattice_match_parts = &r->lattice_match_parts; }
         if (track || tdecode) {
             out.tracks = &r->word_tracks; out.track_members = &r->word_track_members;
@@ -797,6 +803,7 @@ int fill_words(str_er_ctx *c, hipStream_t s, str_er_result *r, const FootTables 
         r->have_word_margins = margin;
         r->have_line_decodes = ldecode;
         r->have_line_margins = lnmargin;
+        r->have_line_lattice_decodes = lldecode;
     }
     if (c->dbg_stats)        // developer aid (tools/dev_line_words.py)
         std::fprintf(stderr, "[str_er] line words: %zu lines, %zu run slots reserved, %zu runs, %zu words, %zu bytes back, host %.3f ms\n", n_lines,

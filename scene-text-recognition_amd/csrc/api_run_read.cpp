@@ -25,6 +25,9 @@
 //   line decode      the decoder's rows, every line one window from the first row of its first word to the last of its last, with the gap costs the host makes from the runs; iff decode
 //                    and the context's setting.  With split the rows are the parts' rows of U (A's where U is A), which lie at the words' slots and whose number only the device
 //                    knows: the line decode is then enqueued behind the stage's wait, once the parts are down, with the cost row of every part, and has a wait of its own
+//   line lattice decode  what the lattice decode read (U's rows of the runs and pieces, the split records), every line one window of runs from the first run of its first word to
+//                    the last of its last, with a gap pair per run the host makes from the runs and the node slots it makes from the split records; iff the lattice decode and
+//                    the context's setting.  All of it is known before the scorer is enqueued: behind k_lattice_decode on the same stream, down with the stage's one wait
 //
 //   result table     source
 //   run_costs        A if match, else U
@@ -32,10 +35,12 @@
 //   run_probs        present iff match or decode
 //
 // The words' (first, n_of, slot) and the split records go up once, behind the tiles in c->run_tab; wm_tab, wd_tab, wg_tab, rs_tab, ld_tab, lg_tab, lm_tab,
-// lt_tab, tm_tab, td_tab, ltd_tab and ln_tab hold what their kernels leave.
+// lt_tab, tm_tab, td_tab, ltd_tab, ln_tab and ll_tab hold what their kernels leave.
 #include "str_er_ctx.h"
 #include "line_decode_rules.h"
+#include "line_lattice_rules.h"
 #include "lattice_decode_kernels.h"
+#include "line_lattice_kernels.h"
 #include "lattice_match_kernels.h"
 #include "run_split_kernels.h"
 
@@ -72,6 +77,10 @@ void ReadChainOut::preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k
         const size_t lr = p.split ? 0 : n_run;
         line_margins->assign(n_lines, str_er_line_margin{-1, -1, -1, -1, -1, -1, -1, -1}); line_row_margins->assign(lr, -1); line_gap_margins->assign(lr, -1);
         line_row_reads->assign(lr, 0xFF); line_row_alts->assign(lr, 0xFF); line_gap_moves->assign(lr, 0xFF);
+    }
+    if (p.lldecode) {          // (a line without runs is the empty line: B[E][E]; labels, sources and gap costs are sized once the atoms are known)
+        ll_decodes->assign(n_lines, str_er_line_lattice_decode{line_bee, 0, 0, 0, 0, 0, 0, 0}); ll_chars->clear(); ll_src->clear(); ll_parts->clear(); ll_word_of_part->clear();
+        ll_gaps->assign(2 * n_run, 0); ll_windows->assign(2 * n_lines, 0);
     }
     if (p.lattice) {
         lattice_decodes->assign(n_words, str_er_lattice_decode{}); lattice_chars->assign(64 * n_words, 0xFF); lattice_src->assign(64 * n_words, 0xFF);
@@ -132,6 +141,7 @@ struct ReadCall {
     OcrBuf   buf{};
     uint8_t *rows[2] = {nullptr, nullptr}, *parts[2] = {nullptr, nullptr};
     LnTab    NH{}, ND{};
+    LlTab    YH{}, YD{}; std::vector<int32_t> ll_first, ll_n_of, ll_slot, ll_slot_end; size_t ll_atoms = 0;      // (the line lattice decode: its windows and node slots)
     const std::vector<str_er_line_words> *lines_of = nullptr; const std::vector<str_er_line_run> *runs_of = nullptr;      // (geometry keeps them for the line decode)
     RsTab    SH{}, SD{}; LdTab LH{}, LD{}; LmTab MH{}, MD{}; LtTab GH{}, GD{}; WmTab WD{}; WdTab DD{}; WgTab GM{}; LgTab LG{}; TmTab KD{}; TdTab EH{}, ED{}; LtdTab QH{}, QD{};
 
@@ -234,6 +244,7 @@ struct ReadCall {
             (p.lmatch && (rc = c->lm_tab.ensure(c, lm_layout(nullptr, 0, n_words, (size_t)n_slots, n_chunks).bytes, "lattice match tables")) != STR_ER_OK))
             return rc;
         if (p.ldecode && !p.split && (rc = line_windows()) != STR_ER_OK) return rc;
+        if (p.lldecode && (rc = line_lattice_windows()) != STR_ER_OK) return rc;
         if (p.match) WD = wm_layout(c->wm_tab.d(), 0, n_words, n_chunks);
         if (p.decode) DD = wd_layout(c->wd_tab.d(), 0, n_words);
         if (p.margin) GM = wg_layout(c->wg_tab.d(), 0, n_words, false);
@@ -267,6 +278,39 @@ struct ReadCall {
             !str_er_ld::gap_costs(runs_of->data(), (int64_t)n_run, nullptr, (int64_t)n_run, first.data(), n_of.data(), colmax.data(), (int64_t)LW.size(), c->word_num, c->word_den,
                                   c->ln_weight, o.line_gaps->data()))
             return fail(c, STR_ER_EHIP, "line decode: a line outside the glyph runs (internal error)");
+        return STR_ER_OK;
+    }
+
+    // the line lattice decode's windows, gap costs and node slots: a line runs from the first run of its first word to the last run of
+    // its last word (the same check as line_windows), a gap costs what the runs say at this setting's weight, and a line's node slot
+    // is the atoms of all runs before its first, from the split records the host holds
+    int line_lattice_windows()
+    {
+        const std::vector<str_er_line_words> &LW = *lines_of;
+        std::vector<int32_t> &win = *o.ll_windows;
+        std::vector<uint32_t> colmax(LW.size());
+        ll_first.resize(LW.size()); ll_n_of.resize(LW.size()); ll_slot.resize(LW.size()); ll_slot_end.resize(LW.size());
+        for (size_t t = 0; t < LW.size(); ++t) {
+            int64_t at = LW[t].first_run;
+            if (LW[t].n_words < 0 || (size_t)LW[t].first_word + (size_t)LW[t].n_words > n_words) return fail(c, STR_ER_EHIP, "line lattice decode: a line's words outside the words (internal error)");
+            for (int32_t k = 0; k < LW[t].n_words; ++k) {
+                const str_er_line_word &W = (*o.words)[(size_t)LW[t].first_word + (size_t)k];
+                if (W.first_run != at) return fail(c, STR_ER_EHIP, "line lattice decode: the words of a line do not lie back to back (internal error)");
+                at += W.n_runs;
+            }
+            if (at != (int64_t)LW[t].first_run + LW[t].n_runs) return fail(c, STR_ER_EHIP, "line lattice decode: the words of a line do not cover its runs (internal error)");
+            ll_first[t] = win[2 * t] = LW[t].first_run; ll_n_of[t] = win[2 * t + 1] = LW[t].n_runs; colmax[t] = LW[t].colmax;
+        }
+        std::vector<int32_t> run_slot;
+        if (!str_er_ld::lines_in_rows((int64_t)n_run, ll_first.data(), ll_n_of.data(), (int64_t)LW.size()) ||
+            !str_er_ld::gap_costs(runs_of->data(), (int64_t)n_run, nullptr, (int64_t)n_run, ll_first.data(), ll_n_of.data(), colmax.data(), (int64_t)LW.size(), c->word_num, c->word_den,
+                                  c->ll_weight, o.ll_gaps->data()))
+            return fail(c, STR_ER_EHIP, "line lattice decode: a line outside the glyph runs (internal error)");
+        if (!str_er_ld::ll_node_slots(o.splits->data(), (int64_t)n_run, run_slot) || (uint64_t)run_slot[n_run] > 0x7FFFFFFFull / (4 * LL_BP_ROW))
+            return fail(c, STR_ER_ECAPACITY, "line lattice decode: too many nodes");
+        ll_atoms = (size_t)run_slot[n_run];
+        for (size_t t = 0; t < LW.size(); ++t) { ll_slot[t] = run_slot[(size_t)ll_first[t]]; ll_slot_end[t] = run_slot[(size_t)ll_first[t] + (size_t)ll_n_of[t]]; }
+        o.ll_chars->assign(str_er_ld::LL_PER_NODE * ll_atoms, 0xFF); o.ll_src->assign(str_er_ld::LL_PER_NODE * ll_atoms, 0xFFFF);
         return STR_ER_OK;
     }
 
@@ -406,6 +450,11 @@ struct ReadCall {
                                                                 o.track_members->size(), tfirst.size(), qslot, &n_qslots, QH, QD);
                     rc != STR_ER_OK)
                     return rc;
+            if (p.lldecode && !ll_first.empty())          // the same rows and records, a window a line: nothing of it waits for the device
+                if (const int rc = line_lattice_enqueue(c, s, 0, TD.splits, rows[p.lattice_set], rows[p.lattice_set] + 65 * n_run, n_run, o.ll_gaps->data(), ll_first.data(),
+                                                        ll_n_of.data(), ll_slot.data(), ll_first.size(), ll_atoms, YH, YD);
+                    rc != STR_ER_OK)
+                    return rc;
         }
         HIP_TRY(c, hipGetLastError());
         return STR_ER_OK;
@@ -455,12 +504,22 @@ struct ReadCall {
             HIP_TRY(c, down(o.lattice_cut_alts->data(), LG.cut_alt, 32 * n_words));
         }
         if (p.lattice && n_words > 0) HIP_TRY(c, down(c->ld_tab.h() + LH.o_dec, c->ld_tab.d() + LH.o_dec, LH.down_bytes));
+        const bool ll_ran = p.lldecode && n_words > 0 && !ll_first.empty();
+        if (ll_ran) HIP_TRY(c, down(c->ll_tab.h() + YH.o_dec, c->ll_tab.d() + YH.o_dec, YH.down_bytes));
         if (p.lmatch && n_words > 0) HIP_TRY(c, down(c->lm_tab.h() + MH.o_matches, c->lm_tab.d() + MH.o_matches, MH.down_bytes));
         if (p.ltrack && !tfirst.empty()) HIP_TRY(c, down(c->lt_tab.h() + GH.o_matches, c->lt_tab.d() + GH.o_matches, GH.down_bytes));
         const bool ltd_ran = p.ltdecode && !tfirst.empty() && n_words > 0;
         if (ltd_ran) HIP_TRY(c, down(c->ltd_tab.h() + QH.o_out, c->ltd_tab.d() + QH.o_out, QH.down_bytes));
         HIP_TRY(c, wait_stream(c, s));
         if (ld_ran) line_collect(n_run);
+        if (ll_ran) {          // the records with their first parts, the parts and their words compacted, labels and sources as they are
+            uint64_t total = 0;
+            if (!ll_compact(YH.dec, YH.parts, YH.word_of_part, ll_slot.data(), ll_slot_end.data(), ll_first.size(), nullptr, nullptr, nullptr, &total))
+                return fail(c, STR_ER_EHIP, "line lattice decode: a line's parts outside its slots (internal error)");
+            o.ll_parts->assign((size_t)total, str_er_split_part{0, 0}); o.ll_word_of_part->assign((size_t)total, -1);
+            ll_compact(YH.dec, YH.parts, YH.word_of_part, ll_slot.data(), ll_slot_end.data(), ll_first.size(), o.ll_decodes->data(), o.ll_parts->data(), o.ll_word_of_part->data(), &total);
+            if (ll_atoms > 0) { std::memcpy(o.ll_chars->data(), YH.chars, str_er_ld::LL_PER_NODE * ll_atoms); std::memcpy(o.ll_src->data(), YH.src, 2 * str_er_ld::LL_PER_NODE * ll_atoms); }
+        }
         if (ltd_ran) {          // the member records with their first parts, the parts compacted, the records, labels and sources as they are
             uint64_t total = 0;
             if (!ltd_compact(QH, qslot, n_qslots, nullptr, nullptr, &total)) return fail(c, STR_ER_EHIP, "lattice track decode: a member's parts outside its slots (internal error)");
@@ -527,7 +586,7 @@ int run_read_stage(str_er_ctx *c, hipStream_t s, const std::vector<FootLine> &li
     const size_t              n_run = runs.size(), n_pc = pieces ? pieces->pieces->size() : 0;
     const ReadPlan p = read_plan(o.matches != nullptr, o.decodes != nullptr, o.splits != nullptr && pieces != nullptr, o.lattice_decodes != nullptr, o.track_matches != nullptr, c->lex.fold != 0,
                                    o.lattice_matches != nullptr, o.lattice_track_matches != nullptr, o.track_decodes != nullptr, o.margins != nullptr, o.lattice_margins != nullptr,
-                                   o.lattice_track_decodes != nullptr, o.line_decodes != nullptr, o.line_margins != nullptr);
+                                   o.lattice_track_decodes != nullptr, o.line_decodes != nullptr, o.line_margins != nullptr, o.ll_decodes != nullptr);
     if (reads) reads->assign(n_run, str_er_run_read{});
     q.assign(1800 * n_run, 0);
     if (pieces) {

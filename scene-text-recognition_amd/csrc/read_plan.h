@@ -30,11 +30,12 @@ struct ReadPlan {
     bool ltdecode;         // the track decode over the members' lattices (str_er_set_lattice_track_decode): only with tdecode and lattice; it reads lattice_set, the lattice decoder's records and labels
     bool ldecode;          // the line decode (str_er_set_line_decode): only with decode; it reads the runs' rows of decode_set, every line one window
     bool lnmargin;         // the line decode's margins (str_er_set_line_margin): only with ldecode; behind it on its rows, gaps, windows, records, labels and sources
+    bool lldecode;         // the line decode over the runs' piece lattices (str_er_set_line_lattice_decode): only with lattice; it reads what the lattice decode reads and a gap pair per run
     bool any() const { return match || decode || split; }      // some consumer reads the words and the class probabilities
 };
 
 inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, bool track, bool fold, bool lmatch = false, bool ltrack = false, bool tdecode = false,
-                          bool margin = false, bool lmargin = false, bool ltdecode = false, bool ldecode = false, bool lnmargin = false)
+                          bool margin = false, bool lmargin = false, bool ltdecode = false, bool ldecode = false, bool lnmargin = false, bool lldecode = false)
 {
     ReadPlan p{};
     p.match = match; p.decode = decode; p.split = split; p.lattice = lattice && split; p.track = track && match;
@@ -59,6 +60,7 @@ inline ReadPlan read_plan(bool match, bool decode, bool split, bool lattice, boo
     p.ltdecode = ltdecode && p.tdecode && p.lattice;
     p.ldecode = ldecode && p.decode;
     p.lnmargin = lnmargin && p.ldecode;
+    p.lldecode = lldecode && p.lattice;
     return p;
 }
 

@@ -222,6 +222,12 @@ struct str_er_result {
     std::vector<int32_t> line_row_margins, line_gap_margins;      // an alternative, a gap margin and a gap move
     std::vector<uint8_t> line_row_reads, line_row_alts, line_gap_moves;
     bool have_line_margins = false;
+    std::vector<str_er_line_lattice_decode> line_lattice_decodes; // str_er_set_line_lattice_decode beside STR_ER_WANT_LATTICE_DECODE: per line of texts; 3 labels and 3 sources per atom
+    std::vector<uint8_t> line_lattice_chars, line_lattice_gap_costs;      // of line_runs, the lines' parts and the word of every part, the gap costs used (2 bytes per run) and the
+    std::vector<uint16_t> line_lattice_src;                               // lines' windows into the runs (first run, run count)
+    std::vector<str_er_split_part> line_lattice_parts;
+    std::vector<int32_t> line_lattice_word_of_part, line_lattice_windows;
+    bool have_line_lattice_decodes = false;
 };
 
 // A table of a result, as the str_er_result_* accessors hand it out: null (and *n = 0) when its stage did not run, and when it ran but made no
@@ -443,6 +449,11 @@ struct str_er_ctx {
     bool     ln_margin = false;       // str_er_set_line_margin: a detect call that decodes its lines also makes their margins
     DevBuf   ln_fw;                   // the forward values of k_line_margin: 136 uint32 per row, scratch
     int32_t  bigram_ee = 0;           // B[E][E] of the table that is set: what a line without rows costs
+    // str_er_set_line_lattice_decode / str_er_lattice_decode_lines (behind everything else for the same reason)
+    bool     ll_on = false;           // a detect call with STR_ER_WANT_LATTICE_DECODE also decodes every line over its runs' piece lattices
+    int32_t  ll_weight = 16;          // the weight of its gap costs
+    PairBuf  ll_tab;                  // splits | rows of the runs and pieces | first run, run count, node slot per line | gap costs | records | labels | sources | parts | word of every part
+    DevBuf   ll_bp;                   // the back pointers of k_line_lattice_decode: 68 uint32 per node, scratch
 };
 
 namespace {
@@ -765,6 +776,10 @@ struct ReadChainOut {
     // str_er_set_line_margin (with the line decode): the margins of the lines' strings, behind the line decode on its rows
     std::vector<str_er_line_margin> *line_margins = nullptr; std::vector<int32_t> *line_row_margins = nullptr, *line_gap_margins = nullptr;
     std::vector<uint8_t> *line_row_reads = nullptr, *line_row_alts = nullptr, *line_gap_moves = nullptr;
+    // str_er_set_line_lattice_decode (with the lattice decode): every line decoded over the piece lattices of its runs, behind the lattice decode on what it
+    // read (n_lines and line_bee as for the line decode)
+    std::vector<str_er_line_lattice_decode> *ll_decodes = nullptr; std::vector<uint8_t> *ll_chars = nullptr, *ll_gaps = nullptr; std::vector<uint16_t> *ll_src = nullptr;
+    std::vector<str_er_split_part> *ll_parts = nullptr; std::vector<int32_t> *ll_word_of_part = nullptr, *ll_windows = nullptr;
     void preset(const ReadPlan &p, size_t n_run, size_t n_pc, size_t k) const;      // every table of the plan as a call without runs leaves it (k: the model's classes)
 };
 // carving a table buffer: take(bytes) is the offset of the next piece, and the one after it starts at the next multiple of 256
@@ -815,6 +830,24 @@ LdTab ld_layout(uint8_t *base, size_t at, size_t n_words, size_t n_slots);
 // after the wait: the records with first_part set and the compacted parts from the host side of the layout (null: not copied); false
 // where a word's parts lie outside its slots
 bool ld_compact(const LdTab &H, const std::vector<int32_t> &slot, uint64_t n_slots, str_er_lattice_decode *dec, str_er_split_part *parts, uint64_t *n_parts);
+// ---- defined in api_line_lattice.cpp
+// the layout of c->ll_tab from byte `at` on (the inputs' bytes) for n_lines lines over n_runs runs of n_slots atoms: what goes up (the
+// gap costs and the lines' first run, run count and node slot) and what k_line_lattice_decode leaves, all of which comes down
+struct LlTab {
+    uint8_t *gaps; int32_t *first, *n_of, *slot; str_er_line_lattice_decode *dec; uint8_t *chars; uint16_t *src; str_er_split_part *parts; int32_t *word_of_part;
+    size_t o_up, up_bytes;                // gaps | first | n_of | slot lie back to back: one copy up
+    size_t o_dec, down_bytes, bytes;      // dec | chars | src | parts | word_of_part lie back to back (each aligned): one copy down
+};
+LlTab ll_layout(uint8_t *base, size_t at, size_t n_runs, size_t n_lines, size_t n_slots);
+// k_line_lattice_decode behind what is on s: the gap costs and the windows (host arrays) into c->ll_tab from byte `at` on and up, the
+// back-pointer table sized, the outputs preset with bytes of 0xFF, the launch on the device's split records and rows; H and D receive
+// the two sides of the layout (what comes down: H.o_dec, H.down_bytes)
+int line_lattice_enqueue(str_er_ctx *c, hipStream_t s, size_t at, const str_er_run_split *d_splits, const uint8_t *d_run_costs, const uint8_t *d_piece_costs, size_t n_runs,
+                         const uint8_t *gaps, const int32_t *first, const int32_t *n_of, const int32_t *slot, size_t n_lines, size_t n_slots, LlTab &H, LlTab &D);
+// after the wait: the records with first_part set, the parts and their words compacted from the lines' slots (null: not copied); false
+// where a line's parts lie outside its slots
+bool ll_compact(const str_er_line_lattice_decode *from, const str_er_split_part *from_parts, const int32_t *from_wop, const int32_t *slot, const int32_t *slot_end, size_t n_lines,
+                str_er_line_lattice_decode *dec, str_er_split_part *parts, int32_t *word_of_part, uint64_t *n_parts);
 // ---- defined in api_lattice_match.cpp
 // the layout of what k_lattice_match and k_lattice_match_final leave in c->lm_tab from byte `at` on (the inputs' bytes): the chunk keys
 // of n_words words, and what comes down: their records and sources and n_slots part slots

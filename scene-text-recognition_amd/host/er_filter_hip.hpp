@@ -1081,6 +1081,81 @@ public:
         out.parts.resize((size_t)n);
         return out;
     }
+    // The joint decode of lines over the piece lattices of their runs (str_er_lattice_decode_lines; the contract is at
+    // str_er_line_lattice_decode in include/str_er.h): one record per line; labels (65: a blank) and sources in slices of 3 entries per
+    // node at the line's node slot (the atoms of all runs before its first run), 0xFF / 0xFFFF where nothing is written; the parts of the
+    // lines back to back and, per part, the number of breaks before it (-1: dropped)
+    struct LineLatticeDecodes {
+        std::vector<str_er_line_lattice_decode> decodes;
+        std::vector<uint8_t>                    chars;
+        std::vector<uint16_t>                   src;
+        std::vector<str_er_split_part>          parts;
+        std::vector<int32_t>                    word_of_part;
+    };
+    // whether a detect call with STR_ER_WANT_LATTICE_DECODE also decodes its lines so, and the weight (0 .. 127) of the gap costs
+    // (str_er_set_line_lattice_decode; off by default)
+    void set_line_lattice_decode(bool on, int32_t weight = 16) { check(str_er_set_line_lattice_decode(ctx_.get(), on ? 1 : 0, weight)); }
+    // the tables of such a call, the gap costs used (2 bytes a run) and the lines' windows (first run, run count) with them (all empty
+    // when it made none)
+    struct LineLatticeResult {
+        LineLatticeDecodes   tables;
+        std::vector<uint8_t> gap_costs;
+        std::vector<int32_t> windows;
+    };
+    static LineLatticeResult line_lattice_decodes(const str_er_result *r)
+    {
+        LineLatticeResult out;
+        int32_t  n = 0;
+        uint64_t nb = 0;
+        if (const str_er_line_lattice_decode *p = str_er_result_line_lattice_decodes(r, &n)) out.tables.decodes.assign(p, p + n);
+        if (const uint8_t *p = str_er_result_line_lattice_chars(r, &nb)) out.tables.chars.assign(p, p + nb);
+        if (const uint16_t *p = str_er_result_line_lattice_src(r, &nb)) out.tables.src.assign(p, p + nb);
+        if (const str_er_split_part *p = str_er_result_line_lattice_parts(r, &n)) out.tables.parts.assign(p, p + n);
+        if (const int32_t *p = str_er_result_line_lattice_word_of_part(r, &nb)) out.tables.word_of_part.assign(p, p + nb);
+        if (const uint8_t *p = str_er_result_line_lattice_gap_costs(r, &nb)) out.gap_costs.assign(p, p + nb);
+        if (const int32_t *p = str_er_result_line_lattice_windows(r, &nb)) out.windows.assign(p, p + nb);
+        return out;
+    }
+    // the lines [first_run[t], first_run[t] + n_runs[t]) on the caller's unfolded cost rows: splits one record per run, run_costs and
+    // piece_costs 65 bytes a row, gaps 2 bytes a run; the context's table, INS / DEL and SPLIT
+    LineLatticeDecodes lattice_decode_lines(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                                            const std::vector<uint8_t> &gaps, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs)
+    {
+        LineLatticeDecodes out = line_lattice_out(splits, run_costs, piece_costs, gaps, first_run, n_runs);
+        int32_t n = 0;
+        check(str_er_lattice_decode_lines(ctx_.get(), splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                          piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65), gaps.empty() ? nullptr : gaps.data(),
+                                          first_run.empty() ? nullptr : first_run.data(), n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(),
+                                          out.decodes.empty() ? nullptr : out.decodes.data(), out.chars.data(), out.src.data(), out.parts.data(),
+                                          (int32_t)out.parts.size(), &n, out.word_of_part.data()));
+        line_lattice_trim(out, n);
+        return out;
+    }
+    // the same rules on one host thread, with the table (66 x 66 bytes), INS / DEL and SPLIT as arguments (str_er_lattice_decode_lines_host)
+    static LineLatticeDecodes lattice_decode_lines_host(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs,
+                                                        const std::vector<uint8_t> &piece_costs, const std::vector<uint8_t> &gaps, const std::vector<int32_t> &first_run,
+                                                        const std::vector<int32_t> &n_runs, const std::vector<uint8_t> &table, int32_t ins = 0, int32_t del = 0,
+                                                        int32_t split_cost = 8)
+    {
+        if (table.size() != 66 * 66) throw std::invalid_argument("lattice_decode_lines_host: 66 x 66 bytes");
+        LineLatticeDecodes out = line_lattice_out(splits, run_costs, piece_costs, gaps, first_run, n_runs);
+        int32_t n = 0;
+        if (str_er_lattice_decode_lines_host(splits.empty() ? nullptr : splits.data(), (int32_t)splits.size(), run_costs.empty() ? nullptr : run_costs.data(),
+                                             piece_costs.empty() ? nullptr : piece_costs.data(), (int32_t)(piece_costs.size() / 65), gaps.empty() ? nullptr : gaps.data(),
+                                             first_run.empty() ? nullptr : first_run.data(), n_runs.empty() ? nullptr : n_runs.data(), (int32_t)first_run.size(),
+                                             split_cost, table.data(), ins, del, out.decodes.empty() ? nullptr : out.decodes.data(), out.chars.data(), out.src.data(),
+                                             out.parts.data(), (int32_t)out.parts.size(), &n, out.word_of_part.data()) != STR_ER_OK)
+            throw std::invalid_argument("lattice_decode_lines_host");
+        line_lattice_trim(out, n);
+        return out;
+    }
+    // the bytes of the line lattice decoder's back-pointer table on the device (str_er_line_lattice_decode_stats)
+    uint64_t line_lattice_decode_table_bytes() const
+    {
+        uint64_t b = 0;
+        check(str_er_line_lattice_decode_stats(ctx_.get(), &b));
+        return b;
+    }
     // The margins of the jointly decoded words (str_er_set_lattice_margin beside STR_ER_WANT_LATTICE_DECODE; the contract is at
     // str_er_lattice_margin in include/str_er.h): one record per word, and per word 32 reading margins and 32 cut margins (-1 past its
     // parts), 32 readings, 32 alternatives and 32 cut alternatives (0xFF past its parts; 65: the part dropped; a cut alternative is
@@ -1784,6 +1859,29 @@ private:
         out.src.resize(64 * first_run.size());
         out.parts.resize(cap);
         return out;
+    }
+    // the outputs of lattice_decode_lines(_host) sized for the runs: 3 labels a node, a part a node at the most (one entry more than
+    // needed, so that no pointer is null)
+    static LineLatticeDecodes line_lattice_out(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
+                                               const std::vector<uint8_t> &gaps, const std::vector<int32_t> &first_run, const std::vector<int32_t> &n_runs)
+    {
+        if (first_run.size() != n_runs.size() || run_costs.size() != 65 * splits.size() || gaps.size() != 2 * splits.size() || piece_costs.size() % 65)
+            throw std::invalid_argument("lattice_decode_lines: 65 bytes a run and a piece, one record and one gap pair a run, one span a line");
+        size_t atoms = 0;
+        for (const str_er_run_split &S : splits) atoms += (size_t)(S.n_cuts < 0 ? 0 : S.n_cuts > 3 ? 3 : S.n_cuts) + 1;
+        if (atoms > 0x7FFFFFFFull / 3) throw std::invalid_argument("lattice_decode_lines: too many runs");
+        LineLatticeDecodes out;
+        out.decodes.resize(first_run.size());
+        out.chars.assign(3 * atoms + 1, 0xFF);
+        out.src.assign(3 * atoms + 1, 0xFFFF);
+        out.parts.resize(atoms + 1);
+        out.word_of_part.assign(atoms + 1, -1);
+        return out;
+    }
+    static void line_lattice_trim(LineLatticeDecodes &out, int32_t n_parts)
+    {
+        out.chars.pop_back(); out.src.pop_back();
+        out.parts.resize((size_t)n_parts); out.word_of_part.resize((size_t)n_parts);
     }
     // the outputs of lattice_match_words(_host) sized for the words: a run has at most 4 parts
     static LatticeMatches lattice_match_out(const std::vector<str_er_run_split> &splits, const std::vector<uint8_t> &run_costs, const std::vector<uint8_t> &piece_costs,
